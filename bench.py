@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the integrator loop on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Headline = BASELINE.json's metric: Msamples/s of the Cornell box 800x800, spp 400, depth 50, MIS
@@ -33,6 +33,11 @@ SURVEY 8(d) prescribes -- algorithmic state bytes of a wavefront tracer (172 B/s
 168 B/shadow segment) over the same time against 8 TB/s -- is kept as `hbm_equivalent`; it is the binding roofline
 only when the wavefront pipeline ran, and then `bound` says "hbm".  `traffic` = HBM bytes of one render from
 separate FETCH_SIZE / WRITE_SIZE passes (same file).
+
+`--dump-outputs DIR` writes, after the timed steps, the image the last timed step of the main workload rendered (linear
+mean radiance, float64, the gathered framebuffer rank 0 receives) as DIR/image.npy.  Inputs are fixed (scene, seed 1),
+so two builds can be compared output for output.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the rendered pixels
+is written instead: DIR/image_sample.npy (n, 3) and DIR/image_sample_pixel.npy (n,), the row-major pixel indices.
 """
 import argparse
 import glob
@@ -52,6 +57,7 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s
 FP64_PEAK_TFLOPS = 78.6    # FP64 vector: 256 CUs x 4 SIMDs x 16 lanes/clk x 2 flop x 2.4 GHz
 B_SAMPLE, B_CLOSEST, B_SHADOW = 172, 280, 168  # SURVEY 8(d), FP64 state
 HEADLINE = "cornell_mis"
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 WORKLOADS = {
     # name: scene id, integrator, W, H, spp, tile_stride (this process renders tiles index % stride == rank)
@@ -194,6 +200,24 @@ def crop_parity(pkg, ctx, scene, wl, chunks_used, pipeline, timed_image=None, ti
     return out
 
 
+def dump_outputs(out_dir, image, mask):
+    """DIR/image.npy of the timed render (or, above DUMP_LIMIT_BYTES, a seeded sample of the pixels `mask` marks as
+    rendered).  Returns {file name: shape} for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float64)
+    if image.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), image)
+        return {"image.npy": list(image.shape)}
+    rendered = np.flatnonzero(mask.reshape(-1))
+    n = min(len(rendered), DUMP_LIMIT_BYTES // (4 * 8))  # three radiance values and one index per pixel
+    pick = np.sort(np.random.default_rng(0).choice(rendered, size=n, replace=False))
+    sample = image.reshape(-1, 3)[pick]
+    np.save(os.path.join(out_dir, "image_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "image_sample_pixel.npy"), pick.astype(np.float64))
+    return {"image_sample.npy": list(sample.shape), "image_sample_pixel.npy": [n]}
+
+
 def roofline(name, pipe_name, counts, samples, closest, shadow, kernel_ms, n_gpus):
     """Roofline object of one workload (per GPU over its kernels)."""
     t = kernel_ms * 1e-3
@@ -256,8 +280,10 @@ def roofline(name, pipe_name, counts, samples, closest, shadow, kernel_ms, n_gpu
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (renders) of the main workload")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step of the main workload to DIR/*.npy")
     ap.add_argument("--workload", default=HEADLINE, choices=sorted(WORKLOADS), help="the line's main workload")
     ap.add_argument("--extras", default=None,
                     help="comma list of further workloads timed in the same run ('none'; default: every other "
@@ -273,6 +299,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N>1 (gloo + RTR_BENCH_ONE_GPU=1 rehearses the N>1 path on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.extra_steps < 1 or args.warmup < 0 or args.extra_warmup < 0:
+        ap.error("--steps and --extra-steps must be >= 1, --warmup and --extra-warmup >= 0")
 
     import numpy as np
     import torch
@@ -317,8 +345,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(name, steps, warmup, with_cpu, with_parity):
-        """Time one workload; returns its (sub-)line on rank 0."""
+    def run(name, steps, warmup, with_cpu, with_parity, dump_dir=None):
+        """Time one workload; returns its (sub-)line on rank 0.  `dump_dir`: write the last timed step's image there."""
         wl = dict(WORKLOADS[name])
         if args.spp:
             wl["spp"] = args.spp
@@ -399,6 +427,8 @@ def main():
             "gather_ms": round(gather_ms, 2), "gather_bytes_per_rank": R.gather_tiles.bytes_sent,
             "image_mean": round(mean, 6),
         }
+        if dump_dir:
+            line["dump_outputs"] = {"dir": dump_dir, "files": dump_outputs(dump_dir, image, px_mask)}
         if with_parity:
             line["parity"] = crop_parity(pkg, ctx, scene, wl, st["spp_chunks"], pipeline, image, px_mask)
         if with_cpu:
@@ -413,7 +443,7 @@ def main():
     elif args.extras != "none":
         extras = [e for e in args.extras.split(",") if e]
     line = run(args.workload, args.steps, args.warmup, single and not args.no_cpu_baseline,
-               single and not args.no_parity)
+               single and not args.no_parity, args.dump_outputs)
     if rank == 0 and counts_file:
         line["counts_file"] = "profiles/" + counts_file
     subs = []
