@@ -7,7 +7,10 @@ scene file (commands `hits-rtrs`, `render-rtrs`) and lets them answer.  Written 
   random_<seed>.rtrs.gz        the scene as generated (the fixture holds the scene itself, not the generator)
   random_<seed>_hits.bin       512 rays: hit flag, t, p, n, u, v, front_face, material, RNG state after the cast
   random_<seed>_i1.f64 / _i4.f64   48x32 spp 4 linear images of RRPathInterator / MISPathIntegrator
-and their entries in manifest.json (argv, sha256).  Run from the repository root:  python oracle/gen_random_golden.py
+and their entries in manifest.json (argv, sha256).  Run from the repository root:
+  python oracle/gen_random_golden.py [TAG ...]
+With tags (e.g. `54 64` or `13b`) only those fixtures are written and only their manifest entries change: add a case,
+generate its tag alone, and every committed fixture stays as it is.  Without tags everything is regenerated.
 """
 import gzip
 import hashlib
@@ -28,7 +31,10 @@ HARNESS = os.path.join(HERE, "_ref", "ref_harness")
 CASES = [(11, {}), (13, dict(n_objects=90)), (14, dict(media=True)), (15, dict(media=True, n_objects=60)),
          (16, dict(hollow=True)), (17, dict(n_objects=8, ties=True)), (18, dict(media=True, hollow=True)),
          (19, dict(n_objects=200)), (27, dict(delta_lights=True)), (28, dict(delta_lights=True, media=True)),
-         (32, dict(moved_media=True)), (33, dict(moved_media=True, media=True, n_objects=50))]
+         (32, dict(moved_media=True)), (33, dict(moved_media=True, media=True, n_objects=50)),
+         # the material palettes of the kernel-variant tests: lean with a top tree over its instances, QuadLights-only
+         # materials with media in the middle of the visiting order
+         (54, dict(n_objects=200, palette="lean")), (64, dict(media=True, palette="quadlit"))]
 W, H, SPP, N_RAYS = 48, 32, 4, 512
 # the same generator output under the reference's own bvh_node (harness command wrap-bvh: its constructor draws the
 # split axes): fixtures random_<seed>b.*
@@ -43,7 +49,7 @@ def sha(path):
         return hashlib.sha256(f.read()).hexdigest()
 
 
-def main():
+def main(tags=()):
     subprocess.run(["make", "-C", HERE, "_ref/ref_harness"], check=True, stdout=subprocess.DEVNULL)
     with open(os.path.join(GOLD, "manifest.json")) as f:
         manifest = json.load(f)
@@ -53,7 +59,13 @@ def main():
         manifest["files"][name] = {"argv": argv, "info": info, "sha256": sha(p), "bytes": os.path.getsize(p), **extra}
 
     with tempfile.TemporaryDirectory() as td:
-        for seed, kw, wrap in [(s_, k_, False) for s_, k_ in CASES] + [(s_, k_, True) for s_, k_ in BVH_CASES]:
+        jobs = [(s_, k_, False) for s_, k_ in CASES] + [(s_, k_, True) for s_, k_ in BVH_CASES]
+        known = {"%02d%s" % (s_, "b" if w_ else "") for s_, k_, w_ in jobs} | {"xties"}
+        if set(tags) - known:
+            raise SystemExit("unknown tags %s (cases: %s)" % (sorted(set(tags) - known), sorted(known)))
+        for seed, kw, wrap in jobs:
+            if tags and "%02d%s" % (seed, "b" if wrap else "") not in tags:
+                continue
             sc = R.random_scene(seed, **kw)
             raw = os.path.join(td, "scene.rtrs")
             sc.save(raw)
@@ -86,23 +98,24 @@ def main():
                      integrator=integ, width=W, height=H, spp=SPP, seed=100 + seed)
             print("random_%s done" % tag, flush=True)
         # exact ties in t ACROSS transform chains (box faces in the planes of rects visited before and after them)
-        sc = R.cross_instance_tie_scene()
-        raw = os.path.join(td, "xties.rtrs")
-        sc.save(raw)
-        with open(raw, "rb") as f, open(os.path.join(GOLD, "xties.rtrs.gz"), "wb") as fo, \
-                gzip.GzipFile(filename="", fileobj=fo, mode="wb", mtime=0) as g:
-            g.write(f.read())
-        note("xties.rtrs.gz", ["tests/_randscene.py: cross_instance_tie_scene()"], {}, raw_sha256=sha(raw))
-        rays = os.path.join(td, "xrays.bin")
-        R.cross_instance_tie_rays().tofile(rays)
-        out = subprocess.run([HARNESS, "hits-rtrs", raw, rays, os.path.join(GOLD, "xties_hits.bin")], check=True,
-                             stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode()
-        note("xties_hits.bin", ["ref_harness", "hits-rtrs", "xties.rtrs", "cross_instance_tie_rays()", "xties_hits.bin"],
-             json.loads(out.strip().splitlines()[-1]), scene="xties")
+        if not tags or "xties" in tags:
+            sc = R.cross_instance_tie_scene()
+            raw = os.path.join(td, "xties.rtrs")
+            sc.save(raw)
+            with open(raw, "rb") as f, open(os.path.join(GOLD, "xties.rtrs.gz"), "wb") as fo, \
+                    gzip.GzipFile(filename="", fileobj=fo, mode="wb", mtime=0) as g:
+                g.write(f.read())
+            note("xties.rtrs.gz", ["tests/_randscene.py: cross_instance_tie_scene()"], {}, raw_sha256=sha(raw))
+            rays = os.path.join(td, "xrays.bin")
+            R.cross_instance_tie_rays().tofile(rays)
+            out = subprocess.run([HARNESS, "hits-rtrs", raw, rays, os.path.join(GOLD, "xties_hits.bin")], check=True,
+                                 stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode()
+            note("xties_hits.bin", ["ref_harness", "hits-rtrs", "xties.rtrs", "cross_instance_tie_rays()", "xties_hits.bin"],
+                 json.loads(out.strip().splitlines()[-1]), scene="xties")
     with open(os.path.join(GOLD, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     return 0
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(tuple(sys.argv[1:])))

@@ -15,6 +15,17 @@ struct rtr_debug_view {
     int trav;           /* RT_TRAV_* a call with `flags` uses (RT_TRAV_FLAT reported as RT_TRAV_FAST: same results) */
     size_t stack_bytes; /* LDS traversal stack per workgroup of that traversal */
 };
+/* the kernels the last render call launched, recorded on the host when they are enqueued (no device work) */
+struct rtr_debug_kernel {
+    int pipeline;   /* RTR_PIPELINE_MEGAKERNEL / RTR_PIPELINE_WAVEFRONT; -1: no render has launched anything yet */
+    int integrator; /* RTR_INTEGRATOR_* */
+    int trav;       /* megakernel: RT_TRAV_* template value of k_mega (RT_TRAV_FLAT_GUARD, RT_TRAV_PROGRAM_EXT included);
+                       wavefront: WavefrontPlan::trav (RT_TRAV_FLAT / RT_TRAV_FAST / RT_TRAV_PROGRAM) */
+    int ms;         /* RT_MS_* of k_mega / of the wf_shade stage */
+    int sorted;     /* k_mega's sorted instantiation / wf_shade<..., true> */
+    int shade_phases; /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched; 0 for the megakernel */
+    int lean, quadlit, sort, media, machine; /* wavefront: the WavefrontPlan fields; 0 for the megakernel */
+};
 struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     double L[3];
     uint32_t rng_exit;
@@ -22,6 +33,7 @@ struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
 };
 extern "C" {
 int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t size_of_view);
+int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);
 void rtr_debug_set_error(rtr_context* ctx, const char* msg); /* rtr_last_error() of a failing rtr_test_* call */
 }

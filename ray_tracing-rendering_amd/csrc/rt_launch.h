@@ -11,6 +11,14 @@
 #include <atomic>
 #include <string>
 
+/* which instantiation a launch actually ran, recorded on the host (rtr_debug_last_kernel) */
+struct LaunchedKernel {
+    int trav = -1;   /* RT_TRAV_* template value of k_mega (RT_TRAV_FLAT_GUARD, RT_TRAV_PROGRAM_EXT included) / WavefrontPlan::trav */
+    int ms = -1;     /* RT_MS_* of k_mega / of the wf_shade stage */
+    int sorted = 0;  /* k_mega's sorted instantiation / wf_shade<..., true> */
+    int phases = 0;  /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched */
+};
+
 /* what rtr_render_device decided about one megakernel launch */
 struct MegaLaunch {
     int integrator, trav;
@@ -24,6 +32,7 @@ struct MegaLaunch {
     RenderK P;
     bool dry;           /* only what can fail without touching the stream: LDS attribute, occupancy query */
     int* blocks_per_cu; /* dry: resident workgroups per CU of the variant that would run */
+    LaunchedKernel* launched; /* not dry: receives the instantiation launched (may be null) */
 };
 /* return an rtr_status; `err` receives the text of a failure */
 int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err);
@@ -49,4 +58,4 @@ struct WavefrontPlan {
 int wavefront_render(WavefrontPool& pool, const DScene* sc, const WavefrontPlan& plan, const RenderK& P, int integrator,
                      double* d_rgb, int64_t row_stride, unsigned char* tile_done, hipStream_t stream,
                      std::atomic<uint32_t>* cancelled_upto,
-                     int* launches, std::string& err);
+                     int* launches, LaunchedKernel* launched, std::string& err);

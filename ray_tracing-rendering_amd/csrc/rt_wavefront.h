@@ -667,7 +667,7 @@ inline int wf_lds_attr(K kernel, size_t bytes, std::string& err) {
  * point finds empty lists); it does not wait for the stream to drain. */
 int wavefront_render(WavefrontPool& pool, const DScene* sc, const WavefrontPlan& plan, const RenderK& Pin, int integrator,
                      double* d_rgb, int64_t row_stride, unsigned char* tile_done, hipStream_t stream,
-                     std::atomic<uint32_t>* cancelled_upto, int* launches, std::string& err) {
+                     std::atomic<uint32_t>* cancelled_upto, int* launches, LaunchedKernel* launched, std::string& err) {
     RenderK P = Pin;
     const long long n_slots_ll = (long long)P.n_tiles * P.chunks * RTR_BLOCK;
     if (n_slots_ll > (1ll << 30)) return wf_fail(err, RTR_ERR_UNSUPPORTED, "path pool larger than 2^30 slots");
@@ -695,6 +695,7 @@ int wavefront_render(WavefrontPool& pool, const DScene* sc, const WavefrontPlan&
     if (plan.lds > 160 * 1024) return wf_lds_attr(wf_extend<true>, plan.lds, err);
     const bool rich = !(plan.lean || plan.quadlit);
     int n_launch = 0;
+    if (launched) *launched = LaunchedKernel{}, launched->trav = plan.trav;
     *pool.h_live = (uint32_t)S.n_blocks;
     hipLaunchKernelGGL(wf_init, grid_all, block, 0, stream, S, P);
     ++n_launch;
@@ -706,8 +707,10 @@ int wavefront_render(WavefrontPool& pool, const DScene* sc, const WavefrontPlan&
         else                                                                                             \
             hipLaunchKernelGGL((wf_shade<I, PH, M, false>), grid_shade, block, 0, stream, sc, S, P, par); \
         ++n_launch;                                                                                      \
+        if (launched) launched->ms = M, launched->sorted = plan.sort, launched->phases |= 1 << PH;        \
     } while (0)
-/* material-set variants as in the megakernel: lean (RR / MIS), QuadLights only (MIS), everything */
+/* material-set variants as in the megakernel: lean (RR / MIS), QuadLights only (MIS), everything.
+ * tests/test_kernel_variants.py holds the table of the wf_shade cells this reaches and renders each against the oracle */
 #define WF_SHADE(PH)                                                                    \
     do {                                                                                \
         switch (integrator) {                                                           \

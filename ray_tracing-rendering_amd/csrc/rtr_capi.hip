@@ -61,6 +61,7 @@ struct rtr_context {
     bool stats_pending = false;
     bool in_flight = false; /* stream-ordered work of a render call is queued whose statistics are not pending (an error return) */
     rtr_render_stats stats{};
+    rtr_debug_kernel last_kernel{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0}; /* rtr_debug_last_kernel */
     /* Cancel.  Renders are numbered; rtr_cancel() covers every render issued so far: it stores the newest
      * id in `cancelled_upto` and in the device word the kernels poll.  A render issued afterwards carries a
      * larger id, so nothing has to be reset between renders and a cancel that arrives while a render waits
@@ -419,7 +420,7 @@ int set_lds(rtr_context* c, K kernel, size_t bytes) {
 
 /* `dry`: only what can fail without touching the stream (the LDS size check / attribute, the occupancy query) */
 int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, bool dry, int* blocks_per_cu, int flags,
-                int* flags_in_effect = nullptr) {
+                int* flags_in_effect = nullptr, LaunchedKernel* launched = nullptr) {
     MegaLaunch L{};
     /* the flat variants exist for integrators 1 and 4; the others take the general compiled-scene kernel */
     L.trav = trav_in == RT_TRAV_FLAT && integrator != RTR_INTEGRATOR_MIS && integrator != RTR_INTEGRATOR_RR ? RT_TRAV_FAST : trav_in;
@@ -439,6 +440,7 @@ int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, b
     L.P = P;
     L.dry = dry;
     L.blocks_per_cu = blocks_per_cu;
+    L.launched = launched;
     if (flags_in_effect && L.sorted) *flags_in_effect |= RTR_FLAG_SORTED_SHADING;
     switch (integrator) {
     case RTR_INTEGRATOR_MIS: return rtr_mega_launch_mis(L, c->err);
@@ -1006,6 +1008,7 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     if (P.n_tiles == 0) { /* nothing to do: this call's statistics are all zero (an earlier render's are dropped) */
         if ((rc = finish_stats(c))) return rc;
         c->stats = rtr_render_stats{};
+        c->last_kernel = rtr_debug_kernel{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0};
         return RTR_OK;
     }
 
@@ -1060,6 +1063,8 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
                                  the tile list, the workspace or the wavefront pool */
     c->stats = rtr_render_stats{};
     c->stats.spp_chunks = chunks;
+    c->last_kernel = rtr_debug_kernel{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0};
+    LaunchedKernel launched{};
     c->pending_id = id;
     HIPCHK(c, hipMemsetAsync(c->b_stats.p, 0, RT_STATS_WORDS * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
@@ -1077,12 +1082,15 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
         plan.machine = (p->flags & RTR_FLAG_WF_PERSISTENT) != 0;
         if (plan.machine) c->stats.flags_in_effect |= RTR_FLAG_WF_PERSISTENT;
         rc = wavefront_render(c->pool, static_cast<const DScene*>(c->b_dscene.p), plan, P, p->integrator, d_rgb, row_stride,
-                              tile_done, c->stream, &c->cancelled_upto, &launches, c->err);
+                              tile_done, c->stream, &c->cancelled_upto, &launches, &launched, c->err);
+        c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, launched.phases,
+                                          plan.lean, plan.quadlit, plan.sort, plan.media, plan.machine};
         if (rc && rc != RTR_ERR_CANCELLED) return rc;
         if (rc == RTR_ERR_CANCELLED) c->stats.cancelled = 1;
         c->stats.kernel_launches = launches;
     } else {
-        if ((rc = launch_mega(c, P, p->integrator, trav, false, nullptr, p->flags, &c->stats.flags_in_effect))) return rc;
+        if ((rc = launch_mega(c, P, p->integrator, trav, false, nullptr, p->flags, &c->stats.flags_in_effect, &launched))) return rc;
+        c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, 0, 0, 0, 0, 0, 0};
         ResolveK R{P, d_rgb, (long long)row_stride, tile_done};
         rtr_launch_resolve(R, c->stream);
         HIPCHK(c, hipGetLastError());
@@ -1325,6 +1333,11 @@ int rtr_debug_view_get(rtr_context* c, int flags, rtr_debug_view* v, size_t size
     if (trav == RT_TRAV_FAST && c->ds.top_root0 >= 0) trav = RT_TRAV_TOP; /* the unit kernels walk what the megakernel walks */
     v->trav = trav;
     v->stack_bytes = stack_bytes(c, trav);
+    return RTR_OK;
+}
+int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {
+    if (!c || !out || size != sizeof(rtr_debug_kernel)) return RTR_ERR_INVALID;
+    *out = c->last_kernel;
     return RTR_OK;
 }
 int rtr_debug_li(rtr_context* c, const rtr_render_params* p, const int32_t* ijs, rtr_debug_li_out* out, int64_t n) {

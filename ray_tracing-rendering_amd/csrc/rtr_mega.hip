@@ -1,6 +1,9 @@
 /*
  * rtr_mega.hip -- megakernel instantiations of one integrator group (see rt_launch.h); compiled three
  * times with -DRTR_MEGA_GROUP=0/1/2 so the variants build in parallel.
+ *
+ * tests/test_kernel_variants.py holds the table of every instantiation the launchers below can pick and renders
+ * each against the oracle: a variant added or removed here goes into that table too.
  */
 #include "rt_kernels.h"
 #include "rt_launch.h"
@@ -38,7 +41,18 @@ int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
     return RTR_OK;
 }
 
-#define RTR_LAUNCH(I, T, M) return launch_one(k_mega<I, T, M>, L, err)
+template <int I, int T, int M, bool S = false>
+int launch_rec(const MegaLaunch& L, std::string& err) {
+    const int rc = launch_one(k_mega<I, T, M, S>, L, err);
+    if (rc == RTR_OK && !L.dry && L.launched) {
+        L.launched->trav = T;
+        L.launched->ms = M;
+        L.launched->sorted = S;
+    }
+    return rc;
+}
+
+#define RTR_LAUNCH(I, T, M) return launch_rec<I, T, M>(L, err)
 
 /* integrators 1 and 4: every traversal, material-set variants.  FULLQ = the variant for "every material,
  * QuadLights only" (the RR integrator has no light code) */
@@ -49,7 +63,7 @@ int launch_t(const MegaLaunch& L, std::string& err) {
         if (L.lean) RTR_LAUNCH(I, RT_TRAV_FLAT, RT_MS_LEAN);
         if (L.quadlit) {
             if (mega_sortable(I, RT_TRAV_FLAT, FULLQ) && L.sorted)
-                return launch_one(k_mega<I, RT_TRAV_FLAT, FULLQ, mega_sortable(I, RT_TRAV_FLAT, FULLQ)>, L, err);
+                return launch_rec<I, RT_TRAV_FLAT, FULLQ, mega_sortable(I, RT_TRAV_FLAT, FULLQ)>(L, err);
             RTR_LAUNCH(I, RT_TRAV_FLAT, FULLQ);
         }
         RTR_LAUNCH(I, RT_TRAV_FLAT, RT_MS_FULL);

@@ -166,6 +166,12 @@ int rtr_test_li(rtr_context* c, const rtr_render_params* p, rtr_li_record* recs,
     return RTR_OK;
 }
 
+int rtr_test_last_kernel(rtr_context* c, rtr_kernel_record* out, size_t size) {
+    static_assert(sizeof(rtr_kernel_record) == sizeof(rtr_debug_kernel), "one layout");
+    if (size != sizeof(rtr_kernel_record)) return RTR_ERR_INVALID;
+    return rtr_debug_last_kernel(c, reinterpret_cast<rtr_debug_kernel*>(out), sizeof(rtr_debug_kernel));
+}
+
 int rtr_test_reference_order(rtr_context* c, int on) {
     if (!c) return RTR_ERR_INVALID;
     state_of(c).reference_order = on != 0;

@@ -23,7 +23,7 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_synchronize", "rtr_cancel", "rtr_get_stats", "rtr_last_error", "rtr_sample_seed", "rtr_validate_scene")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
-                "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates")
+                "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
 _TEST_LIB = None
 
 
@@ -32,6 +32,12 @@ class SceneInfoC(C.Structure):
                 ("graph_depth", C.c_int32), ("fast_ok", C.c_int32), ("fast_instances", C.c_int32),
                 ("fast_refs", C.c_int32), ("fast_stack_words", C.c_int32), ("compiled_subtrees", C.c_int32),
                 ("program_steps", C.c_int32), ("inverted_boxes", C.c_int32), ("top_trees", C.c_int32)]
+
+
+class KernelRecordC(C.Structure):
+    """rtr_kernel_record of include/rtr_hip_test.h"""
+    _fields_ = [(name, C.c_int32) for name in ("pipeline", "integrator", "trav", "ms", "sorted", "shade_phases", "lean",
+                                               "quadlit", "sort", "media", "machine")]
 
 
 class RtrError(RuntimeError):
@@ -106,6 +112,7 @@ def test_lib():
     T.rtr_test_sincos_exhaustive.argtypes = [vp, C.POINTER(C.c_uint64)]
     T.rtr_test_issue_rates.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     T.rtr_test_shared_division.argtypes = [vp, C.POINTER(C.c_uint64)]
+    T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
     _TEST_LIB = T
     return T
 
@@ -225,6 +232,15 @@ class Context:
         return {"samples": s.samples, "closest_segments": s.closest_segments, "shadow_segments": s.shadow_segments,
                 "device_ms": s.device_ms, "kernel_launches": s.kernel_launches, "pipeline": s.pipeline,
                 "spp_chunks": s.spp_chunks, "cancelled": bool(s.cancelled), "flags_in_effect": s.flags_in_effect}
+
+    def last_kernel(self):
+        """The kernel instantiation the last render call launched (include/rtr_hip_test.h: rtr_kernel_record), as a dict;
+        None before any render of this context launched one."""
+        r = KernelRecordC()
+        self._chk(test_lib().rtr_test_last_kernel(self._h, C.byref(r), C.sizeof(r)))
+        if r.pipeline < 0:
+            return None
+        return {name: int(getattr(r, name)) for name, _ in KernelRecordC._fields_}
 
     def reference_order(self, on):
         """Force the reference-order traversal for rtr_test_hits (renders use params.flags)."""

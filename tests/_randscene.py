@@ -12,9 +12,19 @@ A = G.A
 rtr = G.rtr
 
 
+# material palettes of random_scene: which material / texture / light classes a scene may use.  They aim at the
+# material-set variants of the kernels (csrc/rt_device.h: RT_MS_*), which upload picks from what the scene holds.
+#   full     every material, checker and noise textures, any light (RT_MS_FULL)
+#   quadlit  every material, solid textures only, QuadLights only (RT_MS_QUADLIT: no texture reads (u,v))
+#   lean     lambertian and diffuse_light with solid textures, QuadLights only (RT_MS_LEAN)
+PALETTES = ("full", "quadlit", "lean")
+
+
 class Builder:
-    def __init__(self, rng):
+    def __init__(self, rng, palette="full"):
+        assert palette in PALETTES, palette
         self.rng = rng
+        self.palette = palette
         self.nodes, self.kids, self.mats, self.texs, self.lights = [], [], [], [], []
         self.uses_noise = False
 
@@ -62,6 +72,12 @@ class Builder:
     def random_material(self, allow_glass=True):
         r = self.rng
         k = int(r.integers(0, 6 if allow_glass else 5))
+        if self.palette == "lean":  # the glass draw becomes an emitter that is no QuadLight, the rest solid lambertian
+            if k == 5:
+                return self.material(A.MAT_DIFFUSE_LIGHT, [self.solid(r.uniform(1.0, 4.0, 3))])
+            return self.material(A.MAT_LAMBERTIAN, [self.solid(r.uniform(0.1, 0.9, 3))])
+        if self.palette == "quadlit" and k in (0, 1):  # no checker, no noise
+            return self.material(A.MAT_LAMBERTIAN, [self.solid(r.uniform(0.1, 0.9, 3))])
         if k == 0 and r.random() < 0.3:  # marble-like noise_texture (texture.h:78-92)
             return self.material(A.MAT_LAMBERTIAN, [self.noise(float(r.uniform(0.5, 6.0)))])
         if k == 0:
@@ -134,13 +150,20 @@ def _cat(parts, dtype):
 
 
 def random_scene(seed, n_objects=24, media=False, hollow=False, ties=True, delta_lights=False, lens=0.0, moved_media=False,
-                 big_group=False):
-    """One scene in front of scene 23's camera (origin (0,3,8), looking at the origin)."""
+                 big_group=False, palette="full"):
+    """One scene in front of scene 23's camera (origin (0,3,8), looking at the origin).  `palette` (PALETTES): the
+    material and light classes it may use; "full" draws exactly what this generator always drew, so every seed of
+    the default palette gives the same scene, byte for byte, as before palettes existed."""
+    if delta_lights and palette != "full":
+        raise ValueError("palette %r has QuadLights only" % palette)
     rng = np.random.default_rng(seed)
-    b = Builder(rng)
+    b = Builder(rng, palette)
     base = G.scene(23)
     top = []
-    ground = b.material(A.MAT_LAMBERTIAN, [b.checker(b.solid([0.2, 0.3, 0.1]), b.solid([0.9, 0.9, 0.9]))])
+    if palette == "full":
+        ground = b.material(A.MAT_LAMBERTIAN, [b.checker(b.solid([0.2, 0.3, 0.1]), b.solid([0.9, 0.9, 0.9]))])
+    else:
+        ground = b.material(A.MAT_LAMBERTIAN, [b.solid([0.45, 0.5, 0.35])])
     # (not at y = 0: there sin(10 * p.y) of the checker would be the sign of the hit point's rounding noise, and a
     # last-bit difference between two libms upstream of the hit would flip whole checker cells)
     top.append(b.rect("xz", -12.0, 12.0, -12.0, 12.0, -0.013, ground))
@@ -199,14 +222,18 @@ def random_scene(seed, n_objects=24, media=False, hollow=False, ties=True, delta
         grp = [b.sphere(rng.uniform(-1.2, 1.2, 3), float(rng.uniform(0.08, 0.25)), b.random_material()) for _ in range(40)]
         grp += [b.box(p0, p0 + rng.uniform(0.15, 0.5, 3), b.random_material()) for p0 in rng.uniform(-1.2, 1.0, (6, 3))]
         top.append(b.translate(b.rotate_y(b.hlist(grp), float(rng.uniform(-40.0, 40.0))), pos((-3.0, 1.2, -4.0), (3.0, 2.5, 0.0))))
-    if hollow:  # hollow glass (scenes.cpp:903): negative radius inside a glass sphere
+    if hollow:  # hollow glass (scenes.cpp:903): negative radius inside a glass sphere (lean palette: a lambertian shell)
         c = pos()
-        glass = b.material(A.MAT_DIELECTRIC, f=[1.5])
+        if palette == "lean":
+            glass = b.material(A.MAT_LAMBERTIAN, [b.solid([0.8, 0.6, 0.3])])
+        else:
+            glass = b.material(A.MAT_DIELECTRIC, f=[1.5])
         top.append(b.sphere(c, 0.6, glass))
         top.append(b.sphere(c, -0.5, glass))
     if media:
         c = pos()
-        top.append(b.medium(b.sphere(c, 0.9, b.material(A.MAT_DIELECTRIC, f=[1.5])), 0.8, [0.2, 0.4, 0.9]))
+        shell = ground if palette == "lean" else b.material(A.MAT_DIELECTRIC, f=[1.5])
+        top.append(b.medium(b.sphere(c, 0.9, shell), 0.8, [0.2, 0.4, 0.9]))
         p0 = pos()
         top.append(b.medium(b.box(p0, p0 + rng.uniform(0.6, 1.5, 3), ground), 1.5, [0.9, 0.9, 0.9]))
         top.append(b.medium(b.sphere([0.0, 0.0, 0.0], 40.0, ground), 0.01, [1.0, 1.0, 1.0]))  # mist around everything
@@ -224,6 +251,47 @@ def random_scene(seed, n_objects=24, media=False, hollow=False, ties=True, delta
                    base.images[:0], base.image_bytes[:0],
                    _cat(b.lights, A.LIGHT_DTYPE), camera, np.array([0.55, 0.65, 0.8]))
     return sc
+
+
+def single_type_scene(seed, kind="metal", light="quad", n_objects=10):
+    """A scene whose materials are all of ONE type, so the wavefront pipeline shades it without sorting by material
+    class (WavefrontPlan::sort needs two types; every random_scene has at least lambertian + diffuse_light).
+      kind   "metal": metal spheres and boxes; "fog": constant_media whose boundaries carry the phase material too
+             (a scene with media shades in two phases where it has lights)
+      light  "quad": one QuadLight (RT_MS_QUADLIT where no texture reads (u,v)); "point": a point light (RT_MS_FULL)
+    The lights sit in the light list only: nothing in the graph emits, the light sampling alone reaches them."""
+    rng = np.random.default_rng(seed)
+    b = Builder(rng)
+    base = G.scene(23)
+    top = []
+    if kind == "metal":
+        for _ in range(n_objects):
+            mat = b.material(A.MAT_METAL, f=list(rng.uniform(0.5, 0.95, 3)) + [float(rng.choice([0.0, 0.1, 0.5]))])
+            p0 = rng.uniform((-4.5, 0.3, -6.0), (4.5, 3.5, 2.0))
+            if rng.random() < 0.5:
+                top.append(b.sphere(p0, float(rng.uniform(0.2, 0.8)), mat))
+            else:
+                top.append(b.box(p0, p0 + rng.uniform(0.3, 1.2, 3), mat))
+        top.append(b.rect("xz", -12.0, 12.0, -12.0, 12.0, -0.013, b.material(A.MAT_METAL, f=[0.7, 0.7, 0.7, 0.3])))
+    else:
+        assert kind == "fog", kind
+        for _ in range(n_objects):
+            phase = b.material(A.MAT_ISOTROPIC, [b.solid(rng.uniform(0.2, 0.9, 3))])
+            p0 = rng.uniform((-4.5, 0.3, -6.0), (4.5, 3.5, 2.0))
+            if rng.random() < 0.5:
+                boundary = b.sphere(p0, float(rng.uniform(0.4, 1.0)), phase)
+            else:
+                boundary = b.box(p0, p0 + rng.uniform(0.5, 1.5, 3), phase)
+            top.append(b.node(A.NODE_MEDIUM, boundary, phase, f=[-1.0 / float(rng.uniform(0.3, 3.0))]))
+    if light == "quad":
+        b.quad_light([-2.0, 6.0, -3.0], [4.0, 0.0, 0.0], [0.0, 0.0, 3.0], [7.0, 7.0, 7.0])
+    else:
+        assert light == "point", light
+        b.simple_light(A.LIGHT_POINT, [1.0, 5.0, -1.0, 30.0, 28.0, 25.0])
+    root = b.hlist(top)
+    return rtr.Scene(root, _cat(b.nodes, A.NODE_DTYPE), np.asarray(b.kids, dtype=np.int32), _cat(b.mats, A.MATERIAL_DTYPE),
+                     _cat(b.texs, A.TEXTURE_DTYPE), base.perlin[:0], base.images[:0], base.image_bytes[:0],
+                     _cat(b.lights, A.LIGHT_DTYPE), base.camera.copy(), np.array([0.55, 0.65, 0.8]))
 
 
 def random_rays(seed, n):

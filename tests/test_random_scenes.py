@@ -3,6 +3,9 @@ traversal and small renders of every integrator on both pipelines.  The golden s
 forty demo scenes; these graphs add what none of them contains -- coplanar overlapping rects (exact ties in t),
 media in the middle of the visiting order next to transformed boxes, dozens of small instances, nested lists
 under transforms -- with the oracle (bit-exact against the reference on every golden vector) as the checker."""
+import gzip
+import os
+
 import numpy as np
 import pytest
 
@@ -22,8 +25,54 @@ CASES = [(11, {}), (12, {}), (13, dict(n_objects=90)), (14, dict(media=True)), (
          (32, dict(moved_media=True)), (33, dict(moved_media=True, media=True, n_objects=50))]
 
 
+# sha256 of every scene above (and of TOP_CASES' big groups) as the generator drew them before it had palettes: the
+# default palette must keep drawing the same numbers in the same order
+DEFAULT_PALETTE_SHA256 = {
+    11: "7515fb056f5ea279cc00e2c31e760743776365928007e0235540dd8dc3dc3d81",
+    12: "17ee3e2e091d9b3f01ce85300ead9e6e3c9c905d83105cf1c0eb60da05345a77",
+    13: "37e940aa32bb0ed308524b6ef092792dc715281e1235b45aeb014252d77a30e8",
+    14: "422a96b1fbef462da4b7d61807ce4a697858af2679533c0132d5361843063633",
+    15: "dc0ace99baeedbbb9b96b9bcd677bb62953a66115c68fd35246bb86f2d4d6855",
+    16: "6c3cbad091f786bfd2729fe6c5effea01180e153c9da38dec72a79911448fb43",
+    17: "fb934a4125d92dfe77f17042ad5b297dfa42c7757b0fbf5a408dcdaa35509877",
+    18: "2193c4595285e1230a18e768ce9ed9ed5f1c260086a00e539fe2cddc028112b7",
+    19: "e4132255f1784e4033e6096480231a4d2e4edf23c5c96b65496e26db2e814f10",
+    20: "89edfb3199bd918a32e65cb836280f5b33cca493f0f0cf0a38be0caf03186f81",
+    21: "d76b496fca0efedbd7d6e9a6cb143aafef2d58305fd7f99c9e769515257a101c",
+    22: "a82f70b90ff3acbf7e29e2bae2f3fe4161bbf62dca6ba974626eda369e50da71",
+    23: "4421fee78d693494168224d89b6a97c0604029c1916e3c1cd8ed40bc1fcab22a",
+    24: "e88f743a061b2c5e389ca60694efc4820c7db884c14bdb0cbbd7ec5f789e8967",
+    25: "362d55e3d16e39347b7c5f5ee572db700acd776eb75e836dbe750b82418eceb0",
+    26: "67c423845707da6df9ac431504bd310a17f7da83de1e593ef1f45f6146b20591",
+    27: "8cb9e962549fc0cc0e8218fcea6295542c7787ad7d2dad40477d62fe82776e06",
+    28: "686ceec8456f2547b158d8a10eb7e224095cef875cc278ab0d3b4942fec0e6ee",
+    29: "2fe17c29ba2fd1f7671d7698afa1e8a8fc8bf0bfd9720398661cef86296e283b",
+    30: "458257391f2c118ec0a0f01a4eb1aa2258b6dc17e2c7b8120466c5216ecf0377",
+    31: "fe55f3ddc0c7305854a28933880cc631e23ae53adc9275c9ad49390413a048f8",
+    32: "b4614150b1f687f3050ab413be3e8c5fdfd6b6396298e0dc393f0711c4ab1c87",
+    33: "938dea6ea0b761588756be7b74be9cee3b16c2e565cac443137c33cd5d19e66c",
+    41: "8905623d856ddf1bb2fc2de94d45b2ad96d59730837da977d1a800dd6e8d39d5",
+    42: "178ee16123b8f7f53ab8821abffae5abc126bb75bac5dbd9bddcad12eca5c3ef",
+}
+
+
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint64)
+
+
+def test_default_palette_reproduces_every_scene_byte_for_byte():
+    """CPU: random_scene(seed, **kw) and random_scene(seed, palette="full", **kw) give the scenes they always gave --
+    same RNG draws in the same order -- so every seed of CASES and every committed random_<seed> fixture keeps its scene."""
+    for seed, kw in CASES + [(41, dict(big_group=True)), (42, dict(big_group=True, n_objects=70))]:
+        sc = R.random_scene(seed, **kw)
+        assert sc.sha256() == DEFAULT_PALETTE_SHA256[seed], (seed, kw)
+        assert R.random_scene(seed, palette="full", **kw).to_bytes() == sc.to_bytes(), (seed, kw)
+    assert len(DEFAULT_PALETTE_SHA256) == len(CASES) + 2
+    for seed, kw in CASES:  # the fixtures the reference answered (tests/test_random_reference.py)
+        path = os.path.join(G.GOLD, "random_%02d.rtrs.gz" % seed)
+        if os.path.exists(path):
+            with gzip.open(path, "rb") as f:
+                assert f.read() == R.random_scene(seed, **kw).to_bytes(), seed
 
 
 @pytest.mark.parametrize("seed,kw", CASES)
