@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define RTR_ABI_VERSION 3 /* 2: rtr_render_stats grew spp_chunks / cancelled; 3: ... flags_in_effect */
+#define RTR_ABI_VERSION 4 /* 2: rtr_render_stats grew spp_chunks / cancelled; 3: ... flags_in_effect; 4: the accumulator
+                             entry points rtr_accum_* (no struct changed) */
 
 /* ------------------------------------------------------------------------- */
 /* status codes                                                              */
@@ -382,6 +383,49 @@ typedef struct rtr_scene_info {
     int32_t top_trees;         /* compiled sub-scenes whose many transformed instances sit in a box tree of their own
                                   (walked per lane by the megakernel) instead of being scanned one after the other */
 } rtr_scene_info;
+
+/* ------------------------------------------------------------------------- */
+/* progressive accumulation (megakernel pipeline)                            */
+
+/* A device-resident accumulator: per owned pixel ONE running FP64 sum in sample order and, per owned tile, the number
+ * of samples it holds.  Passes continue the sums: a sample's generator state depends on (seed, W, i, j, s) only, so
+ * after any sequence of passes that ends at target T the resolved image is the bits of rtr_render_host with spp = T
+ * and spp_chunks = 1 (it differs from the spp_chunks = 0 default by summation order only, within 1e-13 relative), and
+ * the statistics summed over the passes are the one-shot render's.  The accumulator owns its sums, counts and tile
+ * list: one-shot renders on the same context between its passes do not disturb it. */
+typedef struct rtr_accum rtr_accum;
+
+/* Bind an accumulator to the context's current scene and to region, image size, tile sharding (tile_first /
+ * tile_stride), seed, integrator, max_depth, rr_start_depth, pipeline and flags of *params (params->spp and
+ * params->spp_chunks are ignored).  Every owned tile starts at 0 samples.  RTR_ERR_UNSUPPORTED for
+ * RTR_PIPELINE_WAVEFRONT; RTR_ERR_NO_SCENE before rtr_upload_scene.  rtr_destroy() frees the accumulators left on
+ * the context. */
+int rtr_accum_create(rtr_context* ctx, const rtr_render_params* params, rtr_accum** out);
+
+/* One pass: every owned tile continues from its own sample count to spp_target (samples [count, spp_target)); tiles
+ * already there do no work, a target equal to every count is a no-op, a target below some count is RTR_ERR_INVALID.
+ * Asynchronous on the context stream unless `blocking`, like rtr_render_device; rtr_get_stats reports the pass.
+ * rtr_cancel() stops it with RTR_ERR_CANCELLED, atomically per tile: a tile then holds either its old sums and count
+ * or the new ones, and the same call again finishes the tiles that are still behind.  RTR_ERR_INVALID after the
+ * context's scene was uploaded again, or with a handle of another context. */
+int rtr_accum_render(rtr_context* ctx, rtr_accum* acc, int32_t spp_target, int blocking);
+
+/* The mean of the samples so far, (1.0 / count) * sum as in a render, into HOST buffers (blocking); either may be NULL:
+ *   h_linear  linear radiance, 3 doubles per pixel, h_linear[((j - y0) * row_stride + (i - x0)) * 3 + c]
+ *   h_rgb8    the bytes RenderBuffer::save_to_png writes for the region (renderer.h:126-140, render_buffer.h:35-55):
+ *             uchar(clamp(sqrt(c), 0, 1) * 255), rows of (x1 - x0) pixels, the TOP row of the region (j = y1 - 1) first
+ * Pixels of tiles the accumulator does not own or that hold no sample yet keep the caller's values, so the
+ * accumulators of a tile-sharded render can resolve into one buffer.  Only the owned tiles cross PCIe, packed. */
+int rtr_accum_resolve(rtr_context* ctx, rtr_accum* acc, double* h_linear, int64_t row_stride, uint8_t* h_rgb8);
+
+/* The owned tiles (reference dispatch numbering, renderer.h:61-62) and the samples each holds: the first
+ * min(cap, *n_tiles) entries go to tile_ids / counts (either may be NULL), *n_tiles receives the number of owned
+ * tiles.  Blocking. */
+int rtr_accum_tiles(rtr_context* ctx, const rtr_accum* acc, int32_t* tile_ids, int32_t* counts, int64_t cap,
+                    int64_t* n_tiles);
+
+/* Free an accumulator (waits for its queued work).  NULL is ignored. */
+void rtr_accum_destroy(rtr_accum* acc);
 
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */

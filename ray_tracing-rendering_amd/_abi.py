@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-RTR_ABI_VERSION = 3
+RTR_ABI_VERSION = 4  # 4: the accumulator entry points rtr_accum_* (include/rtr_hip.h)
 
 # status codes (rtr_status)
 RTR_OK = 0

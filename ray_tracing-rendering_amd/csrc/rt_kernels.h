@@ -10,6 +10,8 @@
  *  k_resolve   adds the per-chunk partial sums of a pixel in chunk order, scales by 1/spp
  *              (renderer.h:131) and stores linear mean radiance.
  *  k_li        Integrator::Li of single camera samples or caller-given rays, one lane each (rtr_li_samples / rtr_li_rays).
+ *  k_accum_commit / k_accum_resolve   progressive accumulators (rtr_accum_*): keep the sums of the tiles a pass
+ *              finished, and turn sums + per-tile sample counts into linear mean radiance and the 8-bit store.
  */
 #pragma once
 
@@ -88,7 +90,18 @@ RT_DEV int material_class(int type) { /* what shades alike */
     return type == RTR_MAT_LAMBERTIAN ? 0 : (type == RTR_MAT_PBR ? 1 : ((type == RTR_MAT_DIELECTRIC || type == RTR_MAT_METAL) ? 2 : 3));
 }
 
-template <int INTEG, int TRAV, int MS, bool SORT = false>
+/* the sum a pixel's samples are added to: 0, or for an accumulator pass what the accumulator holds (RenderK::acc_in) */
+template <bool ACC>
+RT_DEV V3 acc_start(const RenderK& P, int slot) {
+    if (!ACC) return mk(0, 0, 0);
+    const double* a = P.acc_in + (size_t)slot * 3 * RTR_BLOCK + threadIdx.x;
+    return mk(a[0], a[RTR_BLOCK], a[2 * RTR_BLOCK]);
+}
+
+/* ACC: an accumulator pass (rtr_accum_render) -- a kernel of its own, so that the registers of the one-shot
+ * kernels do not pay for the two pointers: every tile starts at its sample count RenderK::tile_s0 with the sums
+ * RenderK::acc_in */
+template <int INTEG, int TRAV, int MS, bool SORT = false, bool ACC = false>
 __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     k_mega(const DScene* __restrict__ scp, const RenderK P, const int stack_words) {
     static_assert(!SORT || mega_sortable(INTEG, TRAV, MS), "no sorted variant of this kernel");
@@ -111,8 +124,12 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     /* samples [s, s_end) of this pixel belong to this chunk */
     int s, s_end_;
     chunk_range(P, chunk, s, s_end_);
+    if (ACC) { /* the tile's earlier samples are in P.acc_in */
+        const int s0 = P.tile_s0[slot];
+        s = s > s0 ? s : s0;
+    }
     const int s_end = s_end_;
-    if (!SORT) pk.set3(PK_ACC, mk(0, 0, 0));
+    if (!SORT) pk.set3(PK_ACC, acc_start<ACC>(P, slot));
     PathCounters cnt;
     cnt.closest = 0, cnt.shadow = 0;
     uint32_t n_samples = 0;
@@ -127,7 +144,10 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         const double* const xin = pk.base - threadIdx.x + SK_X * RTR_BLOCK; /* slot q, word k: xin[k * RTR_BLOCK + q] */
         double* const xw = const_cast<double*>(xin);
         double* const accp = P.partial + (size_t)cell * 3 * RTR_BLOCK + threadIdx.x; /* this lane's pixel sum */
-        accp[0] = 0.0, accp[RTR_BLOCK] = 0.0, accp[2 * RTR_BLOCK] = 0.0;
+        {
+            const V3 a0 = acc_start<ACC>(P, slot);
+            accp[0] = a0.x, accp[RTR_BLOCK] = a0.y, accp[2 * RTR_BLOCK] = a0.z;
+        }
         if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
         auto begin_sample = [&]() { /* renderer.h:73-75 under the per-sample seed */
             int pi, pj;
@@ -278,7 +298,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         cnt.shadow = (uint32_t)pk.get(SK_NSHADOW);
     } else if (TRAV == RT_TRAV_MEDIA) {
         /* media draw random numbers inside both ray casts: keep the reference's statement order */
-        V3 acc = mk(0, 0, 0);
+        V3 acc = acc_start<ACC>(P, slot);
         while (!done) {
             if (fresh) { /* renderer.h:73-75 under the per-sample seed */
                 if ((s & 7) == 0 && render_cancelled(P)) break;
@@ -520,6 +540,36 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_resolve(const ResolveK R) {
     o[0] = scale * r;
     o[1] = scale * g;
     o[2] = scale * b;
+}
+
+/* rtr_accum_render, after the pass's k_mega (chunks = 1, so cell = tile slot): a tile whose workgroup ran to the end
+ * takes the pass's sums and the target count; an interrupted one keeps its old sums and count (cancel is atomic per
+ * tile, in every variant: the sorted one sums in place in P.partial) */
+__global__ void __launch_bounds__(RTR_BLOCK) k_accum_commit(const RenderK P, double* __restrict__ sum, int* __restrict__ count) {
+    if (!P.done[blockIdx.x]) return; /* wave-uniform */
+    const size_t o = (size_t)blockIdx.x * 3 * RTR_BLOCK + threadIdx.x;
+    sum[o] = P.partial[o];
+    sum[o + RTR_BLOCK] = P.partial[o + RTR_BLOCK];
+    sum[o + 2 * RTR_BLOCK] = P.partial[o + 2 * RTR_BLOCK];
+    if (threadIdx.x == 0) count[blockIdx.x] = P.spp;
+}
+
+/* rtr_accum_resolve: (1 / count) * sum, the expression of k_resolve, and the reference's store of it
+ * (renderer.h:126-140: sqrt gamma, clamp to [0, 1]; render_buffer.h:35-55: uchar(c * 255) truncation) */
+__global__ void __launch_bounds__(RTR_BLOCK) k_accum_resolve(const AccumResolveK R) {
+    const int n = R.count[blockIdx.x];
+    if (n == 0) return; /* wave-uniform: the host leaves such a tile alone */
+    const size_t in = (size_t)blockIdx.x * 3 * RTR_BLOCK + threadIdx.x;
+    const size_t o = ((size_t)blockIdx.x * RTR_BLOCK + threadIdx.x) * 3;
+    const double scale = 1.0 / n;
+    const double v[3] = {scale * R.sum[in], scale * R.sum[in + RTR_BLOCK], scale * R.sum[in + 2 * RTR_BLOCK]};
+    if (R.out) R.out[o] = v[0], R.out[o + 1] = v[1], R.out[o + 2] = v[2];
+    if (R.rgb8)
+        for (int c = 0; c < 3; ++c) {
+            double g = __builtin_sqrt(v[c]); /* correctly rounded, like std::sqrt */
+            g = g < 0.0 ? 0.0 : (g > 1.0 ? 1.0 : g); /* clamp (rtweekend.h): NaN passes through */
+            R.rgb8[o + c] = static_cast<unsigned char>(g * 255);
+        }
 }
 
 #endif /* RTR_TU_CAPI */

@@ -25,6 +25,11 @@ struct RenderK {
     const uint32_t* cancel;      /* rtr_cancel(): id of the newest render it covers; this render stops once *cancel >= render_id */
     uint32_t render_id;
     int* done;                   /* [n_tiles*chunks]: 1 = the workgroup finished every sample of its chunk */
+    /* Accumulator passes (rtr_accum_render: k_mega<..., ACC = true>, chunks = 1); unused elsewhere.  tile_s0[slot]:
+     * samples the tile already holds -- the pass renders samples [max(s, tile_s0[slot]), s_end) of its chunk;
+     * acc_in: [n_tiles][3][RTR_BLOCK] sums the pass continues instead of starting from 0 */
+    const int* tile_s0;
+    const double* acc_in;
 };
 
 RT_DEV bool render_cancelled(const RenderK& P) {
@@ -78,5 +83,15 @@ struct ResolveK {
     long long row_stride; /* pixels per row of `out`; < 0: `out` is PACKED -- owned tile k of the call at out[k * 768 ...]
                              as 16 rows (lowest y first) of 16 pixels, and tile_done[k] = 1 once its sums are stored */
     unsigned char* tile_done;
+};
+
+/* rtr_accum_resolve: the accumulator's sums and sample counts (r.tile_ids = its owned tiles) -> packed tiles of linear
+ * mean radiance and/or of the reference's 8-bit store; a tile with count 0 is not written */
+struct AccumResolveK {
+    RenderK r;
+    const double* sum;    /* [n_tiles][3][RTR_BLOCK] */
+    const int* count;     /* [n_tiles] */
+    double* out;          /* null or [n_tiles][RTR_BLOCK][3], lowest row first */
+    unsigned char* rgb8;  /* null or [n_tiles][RTR_BLOCK][3], lowest row first (the host flips Y) */
 };
 

@@ -75,6 +75,23 @@ struct rtr_context {
     bool flat_guarded = false; /* a flat scene but for guarded references: RT_TRAV_FAST everywhere, RT_TRAV_FLAT_GUARD in the megakernel */
     bool machine_ok = false; /* the compiled scene fits the position word of the traversal machine (rt_machine.h) */
     bool guarded_program = false; /* the step program holds guarded primitives (FStep kind 3) or media under wrappers: not a program of the machine */
+    uint64_t scene_gen = 0; /* rtr_upload_scene calls that reached the device: an accumulator belongs to one scene */
+    std::vector<rtr_accum*> accums; /* live accumulators (rtr_destroy frees what is left) */
+};
+
+/* rtr_accum_*: one running sum per owned pixel and a sample count per owned tile, on the device */
+struct rtr_accum {
+    rtr_context* ctx = nullptr;
+    rtr_render_params params{}; /* spp / spp_chunks normalised to 1 */
+    uint64_t scene_gen = 0;
+    std::vector<int> tiles; /* owned tiles, dispatch order; slot k = tiles[k] */
+    int tiles_x = 0, tiles_y = 0;
+    DevBuf d_tiles, d_sum, d_count; /* [n] int, [n][3][RTR_BLOCK] double, [n] int */
+    mutable std::vector<int> h_counts; /* host copy of d_count ... */
+    mutable bool counts_stale = false; /* ... unless a pass was queued since it was read */
+    DevBuf d_out; /* rtr_accum_resolve staging: [n][RTR_BLOCK][3] doubles, then [n][RTR_BLOCK][3] bytes */
+    void* h_out = nullptr; /* pinned, same layout */
+    size_t h_out_cap = 0;
 };
 
 namespace {
@@ -436,6 +453,7 @@ int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, b
     L.sorted = (flags & RTR_FLAG_SORTED_SHADING) && c->n_materials <= 65535 && mega_sortable(integrator, L.trav, L.lean ? RT_MS_LEAN : (L.quadlit ? RT_MS_QUADLIT : RT_MS_FULL));
     L.lds = stack_bytes(c, L.trav) + (size_t)(L.sorted ? SK_WORDS : park_words(integrator, L.trav)) * RTR_BLOCK * sizeof(double);
     L.program_ext = c->guarded_program;
+    L.accum = P.tile_s0 != nullptr;
     L.stream = c->stream;
     L.P = P;
     L.dry = dry;
@@ -507,6 +525,22 @@ int choose_chunks(rtr_context* c, RenderK P, int integrator, int pipeline, int t
     return RTR_OK;
 }
 
+/* the host copy of an accumulator's counts, once every pass queued before has finished */
+int refresh_counts(rtr_context* c, const rtr_accum* a) {
+    if (!a->counts_stale || a->tiles.empty()) return RTR_OK;
+    HIPCHK(c, hipMemcpyAsync(a->h_counts.data(), a->d_count.p, a->tiles.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    a->counts_stale = false;
+    return RTR_OK;
+}
+
+/* the checks every rtr_accum_* call of a context makes */
+int accum_check(rtr_context* c, const rtr_accum* a) {
+    if (!a) return fail(c, RTR_ERR_INVALID, "null accumulator");
+    if (a->ctx != c) return fail(c, RTR_ERR_INVALID, "the accumulator belongs to another context");
+    return RTR_OK;
+}
+
 int finish_stats(rtr_context* c) {
     if (!c->stats_pending) {
         if (c->in_flight) { /* a call that failed after its first stream-ordered step: wait for what it queued */
@@ -553,6 +587,14 @@ int finish_stats(rtr_context* c) {
 }
 
 } // namespace
+
+static void free_accum(rtr_accum* a) {
+    DevBuf* bufs[] = {&a->d_tiles, &a->d_sum, &a->d_count, &a->d_out};
+    for (DevBuf* b : bufs)
+        if (b->p) hipFree(b->p);
+    if (a->h_out) hipHostFree(a->h_out);
+    delete a;
+}
 
 void rtr_launch_resolve(const ResolveK& R, hipStream_t stream) {
     hipLaunchKernelGGL(k_resolve, dim3((unsigned)R.r.n_tiles), dim3(RTR_BLOCK), 0, stream, R);
@@ -642,6 +684,8 @@ void rtr_destroy(rtr_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
+    for (rtr_accum* a : c->accums) free_accum(a);
+    c->accums.clear();
     DevBuf* bufs[] = {&c->b_nodes, &c->b_kids,  &c->b_mats,    &c->b_tex,   &c->b_perlin, &c->b_images, &c->b_imgbytes,
                       &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage,
                       &c->b_finst, &c->b_fxf, &c->b_fref, &c->b_fexit, &c->b_fbvh, &c->b_dscene, &c->b_fprim, &c->b_fsub, &c->b_fstep, &c->b_fvisit, &c->b_fscan, &c->b_fleaf, &c->b_fmat, &c->b_fguard};
@@ -674,6 +718,7 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->has_scene = false;
+    ++c->scene_gen;
     CompiledScene cs = compile_scene(s, info.has_media != 0 || info.inverted_boxes != 0, info.has_media == 0 && info.inverted_boxes != 0);
     if ((rc = upload(c, c->b_nodes, cs.dev_nodes.data(), sizeof(rtr_node) * cs.dev_nodes.size()))) return rc;
     if ((rc = upload(c, c->b_kids, s->list_children, sizeof(int32_t) * s->n_list_children))) return rc;
@@ -981,7 +1026,7 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
 
 /* the render call proper; tile_done != nullptr: packed output (see ResolveK) */
 static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb, int64_t row_stride, unsigned char* tile_done,
-                       int blocking);
+                       int blocking, rtr_accum* acc = nullptr);
 
 int rtr_render_device(rtr_context* c, const rtr_render_params* p, double* d_rgb, int64_t row_stride, int blocking) {
     if (!c) return RTR_ERR_INVALID;
@@ -991,8 +1036,10 @@ int rtr_render_device(rtr_context* c, const rtr_render_params* p, double* d_rgb,
     return render_core(c, p, d_rgb, row_stride, nullptr, blocking);
 }
 
+/* acc != nullptr: a pass of that accumulator (p->spp = the target, p->spp_chunks = 1): its tile list, its counts as start
+ * samples and its sums as start values; the commit kernel takes the place of k_resolve */
 static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb, int64_t row_stride, unsigned char* tile_done,
-                       int blocking) {
+                       int blocking, rtr_accum* acc) {
     HIPCHK(c, hipSetDevice(c->device));
     (void)hipGetLastError(); /* a launch error of an earlier call (ours or the host framework's) is not this call's */
     int rc = RTR_OK;
@@ -1003,8 +1050,12 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     P.spp = p->spp, P.max_depth = p->max_depth, P.rr_start = p->rr_start_depth;
     P.seed = p->seed;
     P.integrator = p->integrator;
-    std::vector<int> tiles = owned_tiles(*p, P.tiles_x, P.tiles_y);
-    P.n_tiles = (int)tiles.size();
+    std::vector<int> tiles;
+    if (acc)
+        P.tiles_x = acc->tiles_x, P.tiles_y = acc->tiles_y;
+    else
+        tiles = owned_tiles(*p, P.tiles_x, P.tiles_y);
+    P.n_tiles = (int)(acc ? acc->tiles.size() : tiles.size());
     if (P.n_tiles == 0) { /* nothing to do: this call's statistics are all zero (an earlier render's are dropped) */
         if ((rc = finish_stats(c))) return rc;
         c->stats = rtr_render_stats{};
@@ -1034,7 +1085,7 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
      * asked for are dropped. */
     const size_t partial_bytes = (size_t)P.n_tiles * chunks * 3 * RTR_BLOCK * sizeof(double);
     const size_t done_bytes = (size_t)P.n_tiles * chunks * sizeof(int);
-    const bool same_tiles = tiles == c->last_tiles;
+    const bool same_tiles = acc || tiles == c->last_tiles; /* (an accumulator's tile list is its own) */
     if ((c->stats_pending || c->in_flight) && (!same_tiles || partial_bytes > c->b_partial.cap || done_bytes > c->b_done.cap ||
                                                pipeline == RTR_PIPELINE_WAVEFRONT)) {
         if ((rc = finish_stats(c))) return rc;
@@ -1048,7 +1099,11 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     }
     if ((rc = ensure(c, c->b_partial, partial_bytes))) return rc;
     if ((rc = ensure(c, c->b_done, done_bytes))) return rc;
-    P.tile_ids = static_cast<const int*>(c->b_tiles.p);
+    P.tile_ids = static_cast<const int*>(acc ? acc->d_tiles.p : c->b_tiles.p);
+    if (acc) {
+        P.tile_s0 = static_cast<const int*>(acc->d_count.p);
+        P.acc_in = static_cast<const double*>(acc->d_sum.p);
+    }
     P.stats = static_cast<unsigned long long*>(c->b_stats.p);
     P.cancel = static_cast<const uint32_t*>(c->b_cancel.p);
     P.partial = static_cast<double*>(c->b_partial.p);
@@ -1091,8 +1146,14 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     } else {
         if ((rc = launch_mega(c, P, p->integrator, trav, false, nullptr, p->flags, &c->stats.flags_in_effect, &launched))) return rc;
         c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, 0, 0, 0, 0, 0, 0};
-        ResolveK R{P, d_rgb, (long long)row_stride, tile_done};
-        rtr_launch_resolve(R, c->stream);
+        if (acc) {
+            acc->counts_stale = true;
+            hipLaunchKernelGGL(k_accum_commit, dim3((unsigned)P.n_tiles), dim3(RTR_BLOCK), 0, c->stream, P,
+                               static_cast<double*>(acc->d_sum.p), static_cast<int*>(acc->d_count.p));
+        } else {
+            ResolveK R{P, d_rgb, (long long)row_stride, tile_done};
+            rtr_launch_resolve(R, c->stream);
+        }
         HIPCHK(c, hipGetLastError());
         c->stats.kernel_launches = 2;
     }
@@ -1189,6 +1250,150 @@ int rtr_plan_chunks(rtr_context* c, const rtr_render_params* p) {
     int chunks = 1, guided[3];
     if (int rc = choose_chunks(c, P, p->integrator, pipeline, pick_trav(c, p->flags), p->spp, p->flags, &chunks, guided)) return rc;
     return chunks;
+}
+
+int rtr_accum_create(rtr_context* c, const rtr_render_params* p, rtr_accum** out) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!out) return fail(c, RTR_ERR_INVALID, "null out");
+    *out = nullptr;
+    if (!p) return fail(c, RTR_ERR_INVALID, "null params");
+    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_accum_create before rtr_upload_scene");
+    rtr_render_params q = *p;
+    q.spp = 1, q.spp_chunks = 1; /* ignored: one running sum per pixel, targets come with the passes */
+    if (int prc = params_check(c, &q)) return prc;
+    if (q.pipeline == RTR_PIPELINE_WAVEFRONT) return fail(c, RTR_ERR_UNSUPPORTED, "accumulators run the megakernel pipeline only");
+    HIPCHK(c, hipSetDevice(c->device));
+    rtr_accum* a = new rtr_accum();
+    a->ctx = c;
+    a->params = q;
+    a->scene_gen = c->scene_gen;
+    a->tiles = owned_tiles(q, a->tiles_x, a->tiles_y);
+    const size_t n = a->tiles.size();
+    a->h_counts.assign(n, 0);
+    int rc = upload(c, a->d_tiles, a->tiles.data(), n * sizeof(int));
+    if (!rc) rc = ensure(c, a->d_sum, n * 3 * RTR_BLOCK * sizeof(double));
+    if (!rc) rc = ensure(c, a->d_count, n * sizeof(int));
+    if (!rc && n) {
+        hipError_t e = hipMemsetAsync(a->d_sum.p, 0, n * 3 * RTR_BLOCK * sizeof(double), c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a->d_count.p, 0, n * sizeof(int), c->stream);
+        if (e != hipSuccess) rc = fail(c, RTR_ERR_DEVICE, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        free_accum(a);
+        return rc;
+    }
+    c->accums.push_back(a);
+    *out = a;
+    return RTR_OK;
+}
+
+int rtr_accum_render(rtr_context* c, rtr_accum* a, int32_t spp_target, int blocking) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    if (!c->has_scene || a->scene_gen != c->scene_gen)
+        return fail(c, RTR_ERR_INVALID, "the scene changed since the accumulator was created (rtr_upload_scene)");
+    if (spp_target < 0) return fail(c, RTR_ERR_INVALID, "negative target");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refresh_counts(c, a)) return rc;
+    bool behind = false;
+    for (int n : a->h_counts) {
+        if (spp_target < n) return fail(c, RTR_ERR_INVALID, "target below the sample count of a tile");
+        behind = behind || n < spp_target;
+    }
+    if (!behind) { /* every tile is there: nothing to do, and the statistics of this call are all zero */
+        if (int rc = finish_stats(c)) return rc;
+        c->stats = rtr_render_stats{};
+        return RTR_OK;
+    }
+    rtr_render_params q = a->params;
+    q.spp = spp_target, q.spp_chunks = 1;
+    return render_core(c, &q, nullptr, 0, nullptr, blocking, a);
+}
+
+int rtr_accum_resolve(rtr_context* c, rtr_accum* a, double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    const rtr_render_params& p = a->params;
+    const int w = p.x1 - p.x0;
+    if (!h_linear && !h_rgb8) return fail(c, RTR_ERR_INVALID, "no output buffer");
+    if (h_linear && row_stride < (int64_t)w) return fail(c, RTR_ERR_INVALID, "bad output stride");
+    const size_t n = a->tiles.size();
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refresh_counts(c, a)) return rc; /* (waits for the passes queued before) */
+    const size_t lin_bytes = n * RTR_BLOCK * 3 * sizeof(double), rgb_bytes = n * RTR_BLOCK * 3;
+    if (int rc = ensure(c, a->d_out, lin_bytes + rgb_bytes)) return rc;
+    if (lin_bytes + rgb_bytes > a->h_out_cap) {
+        if (a->h_out) HIPCHK(c, hipHostFree(a->h_out));
+        a->h_out = nullptr, a->h_out_cap = 0;
+        if (hipHostMalloc(&a->h_out, lin_bytes + rgb_bytes, hipHostMallocDefault) != hipSuccess)
+            return fail(c, RTR_ERR_NOMEM, "hipHostMalloc of the resolve staging buffer");
+        a->h_out_cap = lin_bytes + rgb_bytes;
+    }
+    char* d = static_cast<char*>(a->d_out.p);
+    char* h = static_cast<char*>(a->h_out);
+    AccumResolveK R{};
+    R.r.W = p.image_width, R.r.H = p.image_height;
+    R.r.x0 = p.x0, R.r.y0 = p.y0, R.r.x1 = p.x1, R.r.y1 = p.y1;
+    R.r.tiles_x = a->tiles_x, R.r.tiles_y = a->tiles_y;
+    R.r.tile_ids = static_cast<const int*>(a->d_tiles.p);
+    R.r.n_tiles = (int)n;
+    R.sum = static_cast<const double*>(a->d_sum.p);
+    R.count = static_cast<const int*>(a->d_count.p);
+    R.out = h_linear ? reinterpret_cast<double*>(d) : nullptr;
+    R.rgb8 = h_rgb8 ? reinterpret_cast<unsigned char*>(d + lin_bytes) : nullptr;
+    hipLaunchKernelGGL(k_accum_resolve, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, R);
+    HIPCHK(c, hipGetLastError());
+    if (h_linear) HIPCHK(c, hipMemcpyAsync(h, d, lin_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (h_rgb8) HIPCHK(c, hipMemcpyAsync(h + lin_bytes, d + lin_bytes, rgb_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    /* scatter the owned tiles that hold samples into the region (the caller's other pixels stay) */
+    const double* lin = reinterpret_cast<const double*>(h);
+    const unsigned char* rgb = reinterpret_cast<const unsigned char*>(h + lin_bytes);
+    for (size_t k = 0; k < n; ++k) {
+        if (a->h_counts[k] == 0) continue;
+        const int t = a->tiles[k];
+        const int tx0 = (t % a->tiles_x) * 16, ty0 = ((a->tiles_y - 1) - t / a->tiles_x) * 16; /* renderer.h:61-62 */
+        for (int r = 0; r < 16; ++r) {
+            const int j = ty0 + r;
+            if (j < p.y0 || j >= p.y1) continue;
+            const int i0 = std::max(tx0, p.x0), i1 = std::min(tx0 + 16, p.x1);
+            if (i0 >= i1) continue;
+            const size_t src = (k * RTR_BLOCK + (size_t)r * 16 + (size_t)(i0 - tx0)) * 3, len = (size_t)(i1 - i0) * 3;
+            if (h_linear)
+                std::memcpy(h_linear + ((size_t)(j - p.y0) * (size_t)row_stride + (size_t)(i0 - p.x0)) * 3, lin + src,
+                            len * sizeof(double));
+            if (h_rgb8) /* Y flipped: the top row of the region first (render_buffer.h:40-41) */
+                std::memcpy(h_rgb8 + ((size_t)(p.y1 - 1 - j) * (size_t)w + (size_t)(i0 - p.x0)) * 3, rgb + src, len);
+        }
+    }
+    return RTR_OK;
+}
+
+int rtr_accum_tiles(rtr_context* c, const rtr_accum* a, int32_t* tile_ids, int32_t* counts, int64_t cap, int64_t* n_tiles) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    if (!n_tiles || cap < 0) return fail(c, RTR_ERR_INVALID, "null n_tiles or negative cap");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refresh_counts(c, a)) return rc;
+    const size_t n = a->tiles.size(), m = std::min(n, (size_t)cap);
+    *n_tiles = (int64_t)n;
+    if (tile_ids && m) std::memcpy(tile_ids, a->tiles.data(), m * sizeof(int32_t));
+    if (counts && m) std::memcpy(counts, a->h_counts.data(), m * sizeof(int32_t));
+    return RTR_OK;
+}
+
+void rtr_accum_destroy(rtr_accum* a) {
+    if (!a) return;
+    rtr_context* c = a->ctx;
+    hipSetDevice(c->device);
+    if (c->stream) hipStreamSynchronize(c->stream); /* a pass may still use the buffers */
+    for (size_t k = 0; k < c->accums.size(); ++k)
+        if (c->accums[k] == a) {
+            c->accums.erase(c->accums.begin() + (long)k);
+            break;
+        }
+    free_accum(a);
 }
 
 int rtr_synchronize(rtr_context* c) {

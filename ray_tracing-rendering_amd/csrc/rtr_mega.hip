@@ -43,7 +43,8 @@ int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
 
 template <int I, int T, int M, bool S = false>
 int launch_rec(const MegaLaunch& L, std::string& err) {
-    const int rc = launch_one(k_mega<I, T, M, S>, L, err);
+    /* (an accumulator pass: the same variant with ACC, rt_kernels.h) */
+    const int rc = L.accum ? launch_one(k_mega<I, T, M, S, true>, L, err) : launch_one(k_mega<I, T, M, S>, L, err);
     if (rc == RTR_OK && !L.dry && L.launched) {
         L.launched->trav = T;
         L.launched->ms = M;

@@ -6,6 +6,8 @@
  *
  *   rtr_cli <scene 7|9|21|22|23> <integrator 0..4> [--width W] [--spp N] [--seed S] [--bands N] [--out img.ppm|img.png]
  *           [--devices 0,1,...|all] [--repeat N]   one context + host thread per listed GPU (an ordinal may repeat)
+ *           [--passes 1,4,16,...]   progressive: Renderer::render_progressive through these increasing sample counts (the
+ *                                   last one replaces --spp; the image is the one --spp gives), time per pass
  */
 #include "rtr_renderer.h"
 
@@ -13,7 +15,7 @@
 
 int main(int argc, char** argv) {
     int scene_id = 21, integrator_id = 4, width = 0, spp = 0, bands = 0, repeat = 1;
-    std::vector<int> devices{0};
+    std::vector<int> devices{0}, passes;
     unsigned seed = 1;
     std::string out;
     int pos = 0;
@@ -24,6 +26,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--out") && k + 1 < argc) out = argv[++k];
         else if (!std::strcmp(argv[k], "--bands") && k + 1 < argc) bands = std::atoi(argv[++k]);
         else if (!std::strcmp(argv[k], "--repeat") && k + 1 < argc) repeat = std::atoi(argv[++k]);
+        else if (!std::strcmp(argv[k], "--passes") && k + 1 < argc) {
+            const std::string v = argv[++k];
+            for (size_t a = 0; a < v.size();) {
+                size_t b = v.find(',', a);
+                if (b == std::string::npos) b = v.size();
+                passes.push_back(std::atoi(v.substr(a, b - a).c_str()));
+                a = b + 1;
+            }
+        }
         else if (!std::strcmp(argv[k], "--devices") && k + 1 < argc) {
             const std::string v = argv[++k];
             devices.clear();
@@ -49,6 +60,7 @@ int main(int argc, char** argv) {
     }
     if (width > 0) config.image_width = width;
     if (spp > 0) config.samples_per_pixel = spp;
+    if (!passes.empty()) config.samples_per_pixel = passes.back();
     auto cam = make_shared<camera>(config.lookfrom, config.lookat, config.vup, config.vfov, config.aspect_ratio,
                                    config.aperture, config.focus_dist, 0.0, 1.0); /* main.cpp:63-66 */
     const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);
@@ -66,7 +78,16 @@ int main(int argc, char** argv) {
     renderer.set_seed(seed);
     renderer.set_progress_bands(bands);
     for (int r = 0; r < repeat; ++r) { /* a second call finds the flattened scene on the GPUs */
-        renderer.render(config.world, cam, config.background, buffer, config.lights);
+        if (passes.empty()) {
+            renderer.render(config.world, cam, config.background, buffer, config.lights);
+        } else {
+            auto t = std::chrono::high_resolution_clock::now();
+            renderer.render_progressive(config.world, cam, config.background, buffer, config.lights, passes, [&](int target) {
+                const auto now = std::chrono::high_resolution_clock::now();
+                std::cout << "pass to " << target << " spp: " << std::chrono::duration<double>(now - t).count() * 1e3 << " ms\n";
+                t = now;
+            });
+        }
         if (renderer.last_status() != RTR_OK) return 1;
     }
     std::cout << "contexts: " << renderer.device_contexts() << "  scene uploads: " << renderer.scene_uploads() << "\n";

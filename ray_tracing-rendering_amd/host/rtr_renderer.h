@@ -19,6 +19,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <thread>
 
@@ -70,6 +71,15 @@ class RenderBuffer {
                 m_pixels[j][i] = color(clamp(sqrt(v[0]), 0.0, 1.0), clamp(sqrt(v[1]), 0.0, 1.0), clamp(sqrt(v[2]), 0.0, 1.0));
             }
         }
+    }
+    /* write_color_to_buffer for the pixels [x0, x1) x [y0, y1) of a full-size linear image of mean radiance (`lin`: rows
+     * of `stride` pixels, row 0 = the bottom row) */
+    void store_linear_rect(const double* lin, int stride, int x0, int y0, int x1, int y1) {
+        for (int j = std::max(0, y0); j < std::min(y1, m_height); ++j)
+            for (int i = std::max(0, x0); i < std::min(x1, m_width); ++i) {
+                const double* v = &lin[((size_t)j * stride + i) * 3];
+                m_pixels[j][i] = color(clamp(sqrt(v[0]), 0.0, 1.0), clamp(sqrt(v[1]), 0.0, 1.0), clamp(sqrt(v[2]), 0.0, 1.0));
+            }
     }
     /* render_buffer.h:35-55: the bytes of to_rgb8() as an 8-bit RGB PNG.  The reference hands them to stb_image_write;
      * here a plain encoder (filter 0 on every row, one zlib stream): another compressed byte stream, the same pixels
@@ -288,13 +298,37 @@ class Renderer {
             std::cerr << "render failed (" << m_status << "): " << m_error << "\n";
     }
 
+    /* Progressive rendering (no counterpart in the reference, whose window polls one render: main.cpp:115-124).  Every
+     * context keeps one accumulator (include/rtr_hip.h: rtr_accum_*) on the tiles it owns; for each of the increasing
+     * `targets` all contexts continue their sums to that many samples per pixel side by side, store their tiles into
+     * `target_buffer`, and then on_pass(target) is called.  The image after target T is the bits of a render with
+     * spp = T and one running sum per pixel (spp_chunks = 1); render() (spp_chunks = 0) agrees with it within 1e-13.
+     * cancel() stops it between or inside passes: the buffer then holds the last completed target.  Uses the scene cache
+     * of render(). */
+    void render_progressive(shared_ptr<hittable> world, shared_ptr<camera> cam, const color& background,
+                            RenderBuffer& target_buffer, const std::vector<shared_ptr<Light>>& lights,
+                            const std::vector<int>& targets, const std::function<void(int)>& on_pass = nullptr) {
+        m_is_rendering = true;
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        const bool same_scene = world == m_world && cam == m_cam && lights == m_lights &&
+                                background[0] == m_scene_bg[0] && background[1] == m_scene_bg[1] && background[2] == m_scene_bg[2];
+        m_status = progressive_impl(*world, *cam, background, target_buffer, lights, same_scene && m_scene_valid, targets, on_pass);
+        if (m_scene_valid) m_world = world, m_cam = cam, m_lights = lights;
+        m_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        m_is_rendering = false;
+        if (m_status == RTR_OK)
+            std::cout << "Rendering finished in " << m_seconds << " seconds." << std::endl;
+        else
+            std::cerr << "render failed (" << m_status << "): " << m_error << "\n";
+    }
+
   private:
-    int render_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,
-                    const std::vector<shared_ptr<Light>>& lights, bool scene_on_device) {
+    /* what render() and render_progressive() check and upload before they render */
+    int prepare(const hittable& world, const camera& cam, const color& background, const std::vector<shared_ptr<Light>>& lights,
+                bool scene_on_device) {
         if (m_create_status != RTR_OK) return m_error = m_create_error, m_create_status;
         if (m_ctx.empty()) return m_error = rtr_last_error(nullptr), RTR_ERR_DEVICE;
         if (!m_integrator) return m_error = "no integrator set", RTR_ERR_INVALID;
-        const int n = (int)m_ctx.size();
         /* flatten + upload once per scene, not once per render() call */
         if (!scene_on_device) {
             m_scene_valid = false;
@@ -309,7 +343,9 @@ class Renderer {
             m_scene_valid = true;
             ++m_scene_uploads;
         }
-        const int W = buf.width(), H = buf.height();
+        return RTR_OK;
+    }
+    rtr_render_params base_params(int W, int H) const {
         rtr_render_params p{};
         p.image_width = W, p.image_height = H;
         p.x0 = 0, p.y0 = 0, p.x1 = W, p.y1 = H;
@@ -320,6 +356,61 @@ class Renderer {
         p.seed = m_seed;
         p.pipeline = RTR_PIPELINE_AUTO;
         p.spp_chunks = 0;
+        return p;
+    }
+
+    int progressive_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,
+                         const std::vector<shared_ptr<Light>>& lights, bool scene_on_device, const std::vector<int>& targets,
+                         const std::function<void(int)>& on_pass) {
+        for (size_t t = 0; t < targets.size(); ++t)
+            if (targets[t] < 1 || (t && targets[t] <= targets[t - 1])) return m_error = "targets must increase from 1 on", RTR_ERR_INVALID;
+        if (int rc = prepare(world, cam, background, lights, scene_on_device)) return rc;
+        const int n = (int)m_ctx.size(), W = buf.width(), H = buf.height();
+        const rtr_render_params p = base_params(W, H);
+        std::vector<rtr_accum*> acc(n, nullptr);
+        struct Release {
+            std::vector<rtr_accum*>& a;
+            ~Release() {
+                for (rtr_accum* x : a) rtr_accum_destroy(x);
+            }
+        } release{acc};
+        for (int k = 0; k < n; ++k) {
+            rtr_render_params q = p;
+            q.tile_first = k, q.tile_stride = n;
+            if (int rc = rtr_accum_create(m_ctx[k], &q, &acc[k])) return m_error = rtr_last_error(m_ctx[k]), rc;
+        }
+        std::vector<double> lin((size_t)W * H * 3);
+        for (int target : targets) {
+            if (!m_is_rendering) return m_error = "render cancelled", RTR_ERR_CANCELLED;
+            /* one host thread per context: its pass, then its resolve into the tiles it owns of `lin` (distinct pixels, no
+             * lock); the buffer takes the image once every context has finished the target */
+            std::vector<int> rcs(n, RTR_OK);
+            std::vector<std::string> errs(n);
+            auto work = [&](int k) {
+                int rc = rtr_accum_render(m_ctx[k], acc[k], target, 1);
+                if (!rc) rc = rtr_accum_resolve(m_ctx[k], acc[k], lin.data(), W, nullptr);
+                if (rc) rcs[k] = rc, errs[k] = rtr_last_error(m_ctx[k]);
+            };
+            if (n == 1) {
+                work(0);
+            } else {
+                std::vector<std::thread> th;
+                for (int k = 0; k < n; ++k) th.emplace_back(work, k);
+                for (auto& t : th) t.join();
+            }
+            for (int k = 0; k < n; ++k)
+                if (rcs[k]) return m_error = errs[k], rcs[k];
+            buf.store_linear_rect(lin.data(), W, 0, 0, W, H);
+            if (on_pass) on_pass(target);
+        }
+        return RTR_OK;
+    }
+
+    int render_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,
+                    const std::vector<shared_ptr<Light>>& lights, bool scene_on_device) {
+        if (int rc = prepare(world, cam, background, lights, scene_on_device)) return rc;
+        const int n = (int)m_ctx.size(), W = buf.width(), H = buf.height();
+        const rtr_render_params p = base_params(W, H);
         int bands = m_bands > 0 ? m_bands : (H + 255) / 256;
         const int tile_rows = (H + 15) / 16, tiles_x = (W + 15) / 16;
         bands = std::max(1, std::min(bands, tile_rows));

@@ -4,6 +4,7 @@ There is no CPU fallback: if the library is missing or no GPU is visible, every 
 point raises.  The oracle under ``oracle/`` is test infrastructure and is never loaded here."""
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -20,7 +21,8 @@ _STATUS = {A.RTR_ERR_INVALID: "RTR_ERR_INVALID", A.RTR_ERR_UNSUPPORTED: "RTR_ERR
 # every symbol include/rtr_hip.h declares (librtr_hip.so) ...
 EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "rtr_set_stream",
            "rtr_upload_scene", "rtr_render_device", "rtr_render_host", "rtr_render_tiles_host", "rtr_plan_chunks", "rtr_li_samples", "rtr_li_rays",
-           "rtr_synchronize", "rtr_cancel", "rtr_get_stats", "rtr_last_error", "rtr_sample_seed", "rtr_validate_scene")
+           "rtr_synchronize", "rtr_cancel", "rtr_get_stats", "rtr_last_error", "rtr_sample_seed", "rtr_validate_scene",
+           "rtr_accum_create", "rtr_accum_render", "rtr_accum_resolve", "rtr_accum_tiles", "rtr_accum_destroy")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
@@ -84,6 +86,12 @@ def lib():
     L.rtr_sample_seed.restype = C.c_uint32
     L.rtr_validate_scene.argtypes = [P(A.SceneDescC), P(SceneInfoC), C.c_char_p, C.c_size_t]
     L.rtr_li_rays.argtypes = [vp, P(A.RenderParamsC), vp, vp, C.c_int64]
+    L.rtr_accum_create.argtypes = [vp, P(A.RenderParamsC), P(vp)]
+    L.rtr_accum_render.argtypes = [vp, vp, C.c_int32, C.c_int]
+    L.rtr_accum_resolve.argtypes = [vp, vp, vp, C.c_int64, vp]
+    L.rtr_accum_tiles.argtypes = [vp, vp, vp, vp, C.c_int64, P(C.c_int64)]
+    L.rtr_accum_destroy.argtypes = [vp]
+    L.rtr_accum_destroy.restype = None
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -146,9 +154,12 @@ class Context:
         self._h = h
         self.device = int(device)
         self.scene = None
+        self._accums = weakref.WeakSet()
 
     def close(self):
         if getattr(self, "_h", None):
+            for a in list(self._accums):  # rtr_destroy frees them: their handles die with the context
+                a._h = None
             self._L.rtr_destroy(self._h)
             self._h = None
 
@@ -220,6 +231,13 @@ class Context:
         self._chk(self._L.rtr_li_rays(self._h, C.byref(params), rays.ctypes.data, out.ctypes.data, n))
         return out
 
+    def accumulator(self, params):
+        """A progressive accumulator (rtr_accum_*) bound to ``params``' region, image size, tile sharding, seed,
+        integrator, depths, pipeline and flags (its spp and spp_chunks are ignored) and to the scene uploaded now."""
+        a = Accumulator(self, params)
+        self._accums.add(a)
+        return a
+
     def synchronize(self):
         self._chk(self._L.rtr_synchronize(self._h))
 
@@ -282,3 +300,77 @@ class Context:
         else:
             self._chk(fn(self._h, out.ctypes.data, len(out)))
         return out
+
+
+class Accumulator:
+    """Progressive sample accumulation (include/rtr_hip.h: rtr_accum_*): every owned tile continues its one running
+    sum per pixel from its own sample count, so the image after passes ending at T is the bits of
+    ``Context.render`` with spp = T and spp_chunks = 1.  Use as a context manager or call ``close()``."""
+
+    def __init__(self, ctx, params):
+        self._ctx = ctx
+        self._L = ctx._L
+        self.params = params
+        h = C.c_void_p()
+        ctx._chk(self._L.rtr_accum_create(ctx._h, C.byref(params), C.byref(h)))
+        self._h = h
+        self.shape = (params.y1 - params.y0, params.x1 - params.x0)
+
+    def _handle(self):
+        if not self._h:
+            raise RtrError(A.RTR_ERR_INVALID, "accumulator closed")
+        return self._h
+
+    def render(self, spp_target, blocking=True):
+        """One pass: every owned tile continues to ``spp_target`` samples (raises RtrError, RTR_ERR_CANCELLED
+        after rtr_cancel: the tiles then hold their old or their new samples)."""
+        self._ctx._chk(self._L.rtr_accum_render(self._ctx._h, self._handle(), int(spp_target), 1 if blocking else 0))
+
+    def _out(self, out, dtype):
+        h, w = self.shape
+        if out is None:
+            return np.zeros((h, w, 3), dtype=dtype)
+        if out.shape != (h, w, 3) or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous %s array of shape (%d, %d, 3)" % (np.dtype(dtype).name, h, w))
+        return out
+
+    def resolve(self, out=None):
+        """Linear mean radiance (H, W, 3) float64 of the region, row 0 = its lowest row; pixels of tiles this
+        accumulator does not own or that hold no sample keep the values of ``out``."""
+        out = self._out(out, np.float64)
+        self._ctx._chk(self._L.rtr_accum_resolve(self._ctx._h, self._handle(), out.ctypes.data, self.shape[1], None))
+        return out
+
+    def rgb8(self, out=None):
+        """The bytes ``RenderBuffer.to_rgb8()`` gives for the region (Y flipped: row 0 = its top row), (H, W, 3)
+        uint8; pixels of tiles not owned or without samples keep the values of ``out``."""
+        out = self._out(out, np.uint8)
+        self._ctx._chk(self._L.rtr_accum_resolve(self._ctx._h, self._handle(), None, 0, out.ctypes.data))
+        return out
+
+    def tiles(self):
+        """(tile ids in the reference's dispatch numbering, samples per tile) as two int32 arrays."""
+        n = C.c_int64(0)
+        self._ctx._chk(self._L.rtr_accum_tiles(self._ctx._h, self._handle(), None, None, 0, C.byref(n)))
+        ids = np.zeros(n.value, dtype=np.int32)
+        counts = np.zeros(n.value, dtype=np.int32)
+        self._ctx._chk(self._L.rtr_accum_tiles(self._ctx._h, self._handle(), ids.ctypes.data, counts.ctypes.data,
+                                               n.value, C.byref(n)))
+        return ids, counts
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rtr_accum_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -89,6 +89,7 @@ class Renderer:
         self.pipeline = A.PIPELINE_AUTO
         self.seed = 1
         self._rendering = False
+        self._cancel_requested = False
 
     def set_integrator(self, integrator_id):
         """Integrator ids of the reference CLI (main.cpp:52): 1 = RR path, 4 = MIS path."""
@@ -101,6 +102,7 @@ class Renderer:
         self._max_depth = int(depth)
 
     def cancel(self):
+        self._cancel_requested = True  # (render_progressive: also between its passes)
         self._ctx.cancel()
 
     def is_rendering(self):
@@ -124,6 +126,42 @@ class Renderer:
         finally:
             self._rendering = False
         return target_buffer
+
+    def render_progressive(self, scene, target_buffer, targets, rank=0, world=1):
+        """Progressive ``render``: a generator that, for each of the increasing sample counts ``targets``, continues
+        the per-pixel sums of the tiles ``rank`` owns to that many samples (one accumulator, include/rtr_hip.h:
+        rtr_accum_*), stores the image into ``target_buffer`` and yields the count.  The image at count T is the
+        bits of a render with spp = T and spp_chunks = 1.  ``cancel()`` ends it: the buffer then holds the last
+        count yielded.  Bad schedules raise ValueError here, before any device call."""
+        targets = [int(t) for t in targets]
+        if not targets or targets[0] < 1 or any(b <= a for a, b in zip(targets, targets[1:])):
+            raise ValueError("targets must be a non-empty, strictly increasing list of sample counts >= 1: %r" % (targets,))
+        self._cancel_requested = False
+        return self._progressive(scene, target_buffer, targets, rank, world)
+
+    def _progressive(self, scene, target_buffer, targets, rank, world):
+        from .native import RtrError
+        self._rendering = True
+        try:
+            if self._ctx.scene is not scene:
+                self._ctx.upload(scene)
+            p = A.make_params(target_buffer.width, target_buffer.height, 1, integrator=self._integrator, seed=self.seed,
+                              max_depth=self._max_depth, pipeline=self.pipeline, tile_first=rank, tile_stride=world)
+            with self._ctx.accumulator(p) as acc:
+                for t in targets:
+                    if self._cancel_requested:
+                        return
+                    try:
+                        acc.render(t)
+                    except RtrError as e:
+                        if e.code == A.RTR_ERR_CANCELLED:
+                            return
+                        raise
+                    # pixels of tiles other ranks own keep what the buffer holds
+                    target_buffer.store_linear(acc.resolve(target_buffer.linear.copy()))
+                    yield t
+        finally:
+            self._rendering = False
 
 
 def _tile_view(t, width, height):
