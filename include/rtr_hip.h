@@ -427,6 +427,51 @@ int rtr_accum_tiles(rtr_context* ctx, const rtr_accum* acc, int32_t* tile_ids, i
 /* Free an accumulator (waits for its queued work).  NULL is ignored. */
 void rtr_accum_destroy(rtr_accum* acc);
 
+/* ---- adaptive sampling: per-tile targets, second moments, noise estimates (megakernel pipeline) ----
+ *
+ * rtr_accum_create_ex with RTR_ACCUM_MOMENTS: the accumulator also keeps, per owned pixel and in sample order,
+ * Q = sum over samples of y_s * y_s, y_s = 0.2126 * L.x + 0.7152 * L.y + 0.0722 * L.z (left to right) of the sample's
+ * radiance L.  Its passes run a third megakernel twin (k_mega<..., ACC = 2>); the sums stay the bits of a plain
+ * accumulator.  A cancel leaves a tile's sums, moments and count all old or all new.
+ *
+ * The error of a pixel of a tile holding n samples, with m = (1.0 / n) * sum per channel and y_m its luminance:
+ *   var = max(0, (1.0 / n) * Q - y_m * y_m) / (n - 1),   err = sqrt(var) / (2 * sqrt(max(y_m, 1e-4)))
+ * -- the standard error of the gamma-2 value RenderBuffer stores (renderer.h:126-140), so 1/255 is one 8-bit step.  A
+ * tile's error is the largest of its pixels inside the region, +inf below 2 samples.  Only + - * / sqrt max are used:
+ * the values are reproducible bit for bit on the host. */
+#define RTR_ACCUM_MOMENTS 1u /* accum_flags of rtr_accum_create_ex */
+
+/* rtr_accum_create with flags: 0 or RTR_ACCUM_MOMENTS (rtr_accum_create(ctx, p, out) = rtr_accum_create_ex(ctx, p, 0, out)).
+ * RTR_ERR_INVALID for an unknown flag, RTR_ERR_UNSUPPORTED for RTR_PIPELINE_WAVEFRONT. */
+int rtr_accum_create_ex(rtr_context* ctx, const rtr_render_params* params, uint32_t accum_flags, rtr_accum** out);
+
+/* One pass with a target per owned tile: targets[k] for the k-th tile of rtr_accum_tiles; every tile continues from its
+ * count to its target (a tile already there does no work; all there: a no-op).  Each tile is one workgroup and the
+ * tiles with most samples to go are dispatched first; a tile holding T samples is the bits of a render with spp = T and
+ * spp_chunks = 1, whatever the passes were.  RTR_ERR_INVALID if n is not the number of owned tiles or a target is below
+ * its tile's count.  Asynchronous unless `blocking`; cancel as rtr_accum_render. */
+int rtr_accum_render_tiles(rtr_context* ctx, rtr_accum* acc, const int32_t* targets, int64_t n, int blocking);
+
+/* The raw second moments Q, one double per pixel into a HOST buffer, h_q[(j - y0) * row_stride + (i - x0)]; pixels of
+ * tiles not owned or without samples keep the caller's values.  Blocking.  RTR_ERR_INVALID without RTR_ACCUM_MOMENTS. */
+int rtr_accum_moments(rtr_context* ctx, rtr_accum* acc, double* h_q, int64_t row_stride);
+
+/* The error of every owned tile (above) in the order of rtr_accum_tiles: the first min(cap, *n_tiles) go to tile_err
+ * (may be NULL), *n_tiles receives the number of owned tiles.  Blocking.  RTR_ERR_INVALID without RTR_ACCUM_MOMENTS. */
+int rtr_accum_errors(rtr_context* ctx, rtr_accum* acc, double* tile_err, int64_t cap, int64_t* n_tiles);
+
+/* One refinement pass, decided on the device with no host round trip: per owned tile holding n samples with error e
+ *   n < spp_min                        -> target spp_min
+ *   e > threshold and n < spp_max      -> target min(spp_max, 2 * n)
+ *   otherwise                          -> the tile stops (no work)
+ * then the pass as rtr_accum_render_tiles.  Decisions are tile-local, so a tile-sharded render (one context and
+ * accumulator per shard) reaches the counts and bits of an unsharded one.  Blocking: *n_active (may be NULL) receives
+ * the number of tiles the pass refined, 0 = the render is done; not blocking: -1.  RTR_ERR_INVALID without
+ * RTR_ACCUM_MOMENTS, for threshold <= 0 or NaN, spp_min < 1 or spp_max < spp_min (before any device work).  Cancel as
+ * rtr_accum_render: the same call again redoes the tiles that were interrupted. */
+int rtr_accum_refine(rtr_context* ctx, rtr_accum* acc, double threshold, int32_t spp_min, int32_t spp_max, int blocking,
+                     int32_t* n_active);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

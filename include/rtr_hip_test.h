@@ -22,12 +22,14 @@ int rtr_test_lights(rtr_context* ctx, rtr_light_record* recs, int64_t n);
 int rtr_test_li(rtr_context* ctx, const rtr_render_params* params, rtr_li_record* recs, int64_t n);
 
 /* Which kernel instantiation the context's last render call launched, recorded on the host as it was enqueued.
- * Megakernel: k_mega<integrator, trav, ms, sorted>; wavefront: the plan (lean / quadlit / sort / media / machine /
+ * Megakernel: k_mega<integrator, trav, ms, sorted, accum> (accum: 0 one-shot, 1 accumulator pass, 2 accumulator pass
+ * with moments); wavefront: the plan (lean / quadlit / sort / media / machine /
  * trav) and wf_shade<integrator, PH, ms, sorted> for every PH bit of shade_phases.  trav and ms are the RT_TRAV_* and
  * RT_MS_* values of csrc/rt_device.h.  pipeline = -1: no render of this context has launched anything yet. */
 typedef struct rtr_kernel_record {
     int32_t pipeline, integrator, trav, ms, sorted, shade_phases;
     int32_t lean, quadlit, sort, media, machine;
+    int32_t accum;
 } rtr_kernel_record;
 /* size_of_out must be sizeof(rtr_kernel_record) */
 int rtr_test_last_kernel(rtr_context* ctx, rtr_kernel_record* out, size_t size_of_out);

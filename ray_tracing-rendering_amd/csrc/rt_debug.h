@@ -25,6 +25,7 @@ struct rtr_debug_kernel {
     int sorted;     /* k_mega's sorted instantiation / wf_shade<..., true> */
     int shade_phases; /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched; 0 for the megakernel */
     int lean, quadlit, sort, media, machine; /* wavefront: the WavefrontPlan fields; 0 for the megakernel */
+    int accum;      /* megakernel: the ACC template value of k_mega (0 one-shot, 1 accumulator pass, 2 with moments) */
 };
 struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     double L[3];

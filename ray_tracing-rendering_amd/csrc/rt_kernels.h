@@ -12,6 +12,8 @@
  *  k_li        Integrator::Li of single camera samples or caller-given rays, one lane each (rtr_li_samples / rtr_li_rays).
  *  k_accum_commit / k_accum_resolve   progressive accumulators (rtr_accum_*): keep the sums of the tiles a pass
  *              finished, and turn sums + per-tile sample counts into linear mean radiance and the 8-bit store.
+ *  k_accum_errors / k_accum_plan   adaptive sampling: per-tile noise estimates from sums + second moments, and the
+ *              per-tile targets and active-tile list of the next pass, on the device.
  */
 #pragma once
 
@@ -91,17 +93,19 @@ RT_DEV int material_class(int type) { /* what shades alike */
 }
 
 /* the sum a pixel's samples are added to: 0, or for an accumulator pass what the accumulator holds (RenderK::acc_in) */
-template <bool ACC>
+template <int ACC>
 RT_DEV V3 acc_start(const RenderK& P, int slot) {
     if (!ACC) return mk(0, 0, 0);
     const double* a = P.acc_in + (size_t)slot * 3 * RTR_BLOCK + threadIdx.x;
     return mk(a[0], a[RTR_BLOCK], a[2 * RTR_BLOCK]);
 }
 
-/* ACC: an accumulator pass (rtr_accum_render) -- a kernel of its own, so that the registers of the one-shot
- * kernels do not pay for the two pointers: every tile starts at its sample count RenderK::tile_s0 with the sums
- * RenderK::acc_in */
-template <int INTEG, int TRAV, int MS, bool SORT = false, bool ACC = false>
+/* ACC: 0 = a one-shot render; 1 = an accumulator pass (rtr_accum_*) -- a kernel of its own, so that the registers of
+ * the one-shot kernels do not pay for its pointers: workgroup b renders the active tile slot RenderK::active[b] from
+ * its sample count RenderK::tile_s0 to RenderK::tile_s1 with the sums RenderK::acc_in; 2 = a pass of an accumulator
+ * with moments, which also continues Q = sum of y_s * y_s (y_s = luminance of sample s) in a register, in sample
+ * order, and leaves it in RenderK::q_part */
+template <int INTEG, int TRAV, int MS, bool SORT = false, int ACC = 0>
 __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     k_mega(const DScene* __restrict__ scp, const RenderK P, const int stack_words) {
     static_assert(!SORT || mega_sortable(INTEG, TRAV, MS), "no sorted variant of this kernel");
@@ -116,20 +120,25 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     if ((threadIdx.x & 63) == 0) rt_prof_lds[4 * 2 * RT_PROF_REGIONS + (threadIdx.x >> 6) * 2] = __builtin_readcyclecounter();
 #endif
     int slot, chunk;
-    mega_work(P, blockIdx.x, slot, chunk);
+    if (ACC) { /* the launch covers every owned tile; the active ones come first, most pending samples first */
+        if ((int)blockIdx.x >= *P.n_active) return; /* workgroup-uniform */
+        slot = P.active[blockIdx.x], chunk = 0;
+    } else {
+        mega_work(P, blockIdx.x, slot, chunk);
+    }
     const int cell = slot * P.chunks + chunk; /* partial sum / completion word of this (tile, chunk) */
     int i, j;
     bool active;
     tile_pixel(P, slot, threadIdx.x, i, j, active);
     /* samples [s, s_end) of this pixel belong to this chunk */
     int s, s_end_;
-    chunk_range(P, chunk, s, s_end_);
-    if (ACC) { /* the tile's earlier samples are in P.acc_in */
-        const int s0 = P.tile_s0[slot];
-        s = s > s0 ? s : s0;
-    }
+    if (ACC) /* the tile's earlier samples are in P.acc_in */
+        s = P.tile_s0[slot], s_end_ = P.tile_s1[slot];
+    else
+        chunk_range(P, chunk, s, s_end_);
     const int s_end = s_end_;
     if (!SORT) pk.set3(PK_ACC, acc_start<ACC>(P, slot));
+    double q = ACC == 2 ? P.q_in[(size_t)slot * RTR_BLOCK + threadIdx.x] : 0.0; /* (dead unless ACC == 2) */
     PathCounters cnt;
     cnt.closest = 0, cnt.shadow = 0;
     uint32_t n_samples = 0;
@@ -288,6 +297,10 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             if (ended) {
                 const V3 L = pk.get3(SK_L);
                 accp[0] += L.x, accp[RTR_BLOCK] += L.y, accp[2 * RTR_BLOCK] += L.z; /* renderer.h:77-78 */
+                if (ACC == 2) {
+                    const double y = luminance(L);
+                    q += y * y;
+                }
                 ++n_samples;
                 ++s;
                 done = s >= s_end || ((s & 7) == 0 && render_cancelled(P));
@@ -313,6 +326,10 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             }
             if (!bounce<INTEG, TRAV>(sc, ps, rng, st, P.max_depth, P.rr_start, cnt)) {
                 acc = add(acc, ps.L); /* renderer.h:77-78 */
+                if (ACC == 2) {
+                    const double y = luminance(ps.L);
+                    q += y * y;
+                }
                 ++n_samples;
                 ++s;
                 fresh = true;
@@ -421,6 +438,10 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             RT_REGION(RG_REGEN);
             if (ended) {
                 pk.set3(PK_ACC, add(pk.get3(PK_ACC), pk.get3(PK_L))); /* renderer.h:77-78 */
+                if (ACC == 2) {
+                    const double y = luminance(pk.get3(PK_L));
+                    q += y * y;
+                }
                 ++n_samples;
                 ++s;
                 /* rtr_cancel(): polled every 8th sample of a pixel -- the load is a dependent memory round
@@ -456,6 +477,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         out[RTR_BLOCK] = acc.y;
         out[2 * RTR_BLOCK] = acc.z;
     }
+    if (ACC == 2) P.q_part[(size_t)cell * RTR_BLOCK + threadIdx.x] = q;
     unsigned long long a = wave_sum(n_samples), b = wave_sum(cnt.closest), c = wave_sum(cnt.shadow);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&P.stats[0], a);
@@ -542,16 +564,111 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_resolve(const ResolveK R) {
     o[2] = scale * b;
 }
 
-/* rtr_accum_render, after the pass's k_mega (chunks = 1, so cell = tile slot): a tile whose workgroup ran to the end
- * takes the pass's sums and the target count; an interrupted one keeps its old sums and count (cancel is atomic per
- * tile, in every variant: the sorted one sums in place in P.partial) */
-__global__ void __launch_bounds__(RTR_BLOCK) k_accum_commit(const RenderK P, double* __restrict__ sum, int* __restrict__ count) {
-    if (!P.done[blockIdx.x]) return; /* wave-uniform */
-    const size_t o = (size_t)blockIdx.x * 3 * RTR_BLOCK + threadIdx.x;
+/* every accumulator pass, after its k_mega (chunks = 1, so cell = tile slot), workgroup b for the slot active[b]: a tile
+ * whose workgroup ran to the end takes the pass's sums (and moments) and its target count; an interrupted one keeps its
+ * old sums, moments and count (cancel is atomic per tile, in every variant: the sorted one sums in place in P.partial) */
+__global__ void __launch_bounds__(RTR_BLOCK) k_accum_commit(const RenderK P, double* __restrict__ sum, double* __restrict__ q,
+                                                            int* __restrict__ count) {
+    if ((int)blockIdx.x >= *P.n_active) return; /* workgroup-uniform */
+    const int slot = P.active[blockIdx.x];
+    if (!P.done[slot]) return;
+    const size_t o = (size_t)slot * 3 * RTR_BLOCK + threadIdx.x;
     sum[o] = P.partial[o];
     sum[o + RTR_BLOCK] = P.partial[o + RTR_BLOCK];
     sum[o + 2 * RTR_BLOCK] = P.partial[o + 2 * RTR_BLOCK];
-    if (threadIdx.x == 0) count[blockIdx.x] = P.spp;
+    if (q) q[(size_t)slot * RTR_BLOCK + threadIdx.x] = P.q_part[(size_t)slot * RTR_BLOCK + threadIdx.x];
+    if (threadIdx.x == 0) count[slot] = P.tile_s1[slot];
+}
+
+/* rtr_accum_errors / rtr_accum_refine: one workgroup per owned tile, the largest per-pixel error of the tile's pixels
+ * inside the region (include/rtr_hip.h); +inf below 2 samples.  Only + - * / sqrt max: a numpy restatement gives the
+ * same bits. */
+__global__ void __launch_bounds__(RTR_BLOCK) k_accum_errors(const AccumResolveK R, const double* __restrict__ q,
+                                                            double* __restrict__ err) {
+    __shared__ double wmax[RTR_BLOCK / 64];
+    const int n = R.count[blockIdx.x];
+    if (n < 2) { /* workgroup-uniform */
+        if (threadIdx.x == 0) err[blockIdx.x] = __builtin_inf();
+        return;
+    }
+    int i, j;
+    bool active;
+    tile_pixel(R.r, blockIdx.x, threadIdx.x, i, j, active);
+    double e = 0.0;
+    if (active) {
+        const size_t in = (size_t)blockIdx.x * 3 * RTR_BLOCK + threadIdx.x;
+        const double scale = 1.0 / n; /* the mean of k_accum_resolve */
+        const V3 m = mk(scale * R.sum[in], scale * R.sum[in + RTR_BLOCK], scale * R.sum[in + 2 * RTR_BLOCK]);
+        const double ym = luminance(m);
+        const double d = scale * q[(size_t)blockIdx.x * RTR_BLOCK + threadIdx.x] - ym * ym;
+        const double var = (d > 0.0 ? d : 0.0) / (double)(n - 1);
+        e = __builtin_sqrt(var) / (2.0 * __builtin_sqrt(ym > 1e-4 ? ym : 1e-4));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(e, off, 64);
+        e = o > e ? o : e;
+    }
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = wmax[0];
+        for (int w = 1; w < RTR_BLOCK / 64; ++w) t = wmax[w] > t ? wmax[w] : t;
+        err[blockIdx.x] = t;
+    }
+}
+
+/* the plan of an accumulator pass, one workgroup: every slot's target tile_s1 and the active list (the slots with
+ * target > count, the most pending samples first: by the bucket floor(log2(target - count)), descending; the order inside
+ * a bucket does not matter, every tile is one workgroup).  The targets come from
+ *   mode 0  tile_s1 as given (rtr_accum_render_tiles uploaded it)
+ *   mode 1  max(count, spp) (rtr_accum_render)
+ *   mode 2  the refinement rule of rtr_accum_refine on err: count < spp_min -> spp_min; err > threshold and count <
+ *           spp_max -> min(spp_max, 2 * count); else count */
+struct AccumPlanK {
+    int n_tiles, mode;
+    const int* count;
+    const double* err;
+    int* tile_s1;
+    int* active;
+    int* n_active;
+    int spp, spp_min, spp_max;
+    double threshold;
+};
+__global__ void __launch_bounds__(1024) k_accum_plan(const AccumPlanK K) {
+    __shared__ int bucket_n[32];
+    if (threadIdx.x < 32) bucket_n[threadIdx.x] = 0;
+    __syncthreads();
+    for (int t = threadIdx.x; t < K.n_tiles; t += blockDim.x) {
+        const int c = K.count[t];
+        int target = c;
+        if (K.mode == 0) {
+            target = K.tile_s1[t];
+        } else if (K.mode == 1) {
+            target = K.spp > c ? K.spp : c;
+        } else if (c < K.spp_min) {
+            target = K.spp_min;
+        } else if (K.err[t] > K.threshold && c < K.spp_max) {
+            target = c < K.spp_max - c ? 2 * c : K.spp_max; /* min(spp_max, 2 * count) without overflow */
+        }
+        K.tile_s1[t] = target;
+        if (target > c) atomicAdd(&bucket_n[31 - __builtin_clz((unsigned)(target - c))], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { /* bucket b starts after every larger bucket */
+        int base = 0;
+        for (int b = 31; b >= 0; --b) {
+            const int n = bucket_n[b];
+            bucket_n[b] = base;
+            base += n;
+        }
+        *K.n_active = base;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < K.n_tiles; t += blockDim.x) {
+        const int c = K.count[t], target = K.tile_s1[t];
+        if (target > c) K.active[atomicAdd(&bucket_n[31 - __builtin_clz((unsigned)(target - c))], 1)] = t;
+    }
 }
 
 /* rtr_accum_resolve: (1 / count) * sum, the expression of k_resolve, and the reference's store of it

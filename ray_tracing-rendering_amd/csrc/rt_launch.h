@@ -25,7 +25,7 @@ struct MegaLaunch {
     bool lean, quadlit; /* material / light set of the scene (rtr_upload_scene) */
     bool sorted;        /* RTR_FLAG_SORTED_SHADING and a sorted instantiation exists for this launch (rt_kernels.h) */
     bool program_ext;   /* RT_TRAV_PROGRAM: the program holds guarded steps or media under wrappers (RT_TRAV_PROGRAM_EXT kernels) */
-    bool accum;         /* an accumulator pass: the k_mega<..., ACC = true> twin of the variant */
+    int accum;          /* 0, or an accumulator pass: the k_mega<..., ACC = 1> twin of the variant, 2 with moments */
     size_t lds;         /* traversal stack + parked path state, bytes per workgroup */
     int stack_words;
     hipStream_t stream;

@@ -25,12 +25,21 @@ struct RenderK {
     const uint32_t* cancel;      /* rtr_cancel(): id of the newest render it covers; this render stops once *cancel >= render_id */
     uint32_t render_id;
     int* done;                   /* [n_tiles*chunks]: 1 = the workgroup finished every sample of its chunk */
-    /* Accumulator passes (rtr_accum_render: k_mega<..., ACC = true>, chunks = 1); unused elsewhere.  tile_s0[slot]:
-     * samples the tile already holds -- the pass renders samples [max(s, tile_s0[slot]), s_end) of its chunk;
-     * acc_in: [n_tiles][3][RTR_BLOCK] sums the pass continues instead of starting from 0 */
+    /* Accumulator passes (rtr_accum_*: k_mega<..., ACC = 1 | 2>, chunks = 1); unused elsewhere.  Workgroup b renders
+     * the tile slot active[b] if b < *n_active (k_accum_plan wrote both on the device), samples [tile_s0[slot],
+     * tile_s1[slot]); acc_in: [n_tiles][3][RTR_BLOCK] sums the pass continues instead of starting from 0.  ACC = 2 also
+     * continues the second moments q_in ([n_tiles][RTR_BLOCK]) and leaves them in q_part (same layout) */
     const int* tile_s0;
     const double* acc_in;
+    const int* tile_s1;
+    const int* active;
+    const int* n_active;
+    const double* q_in;
+    double* q_part;
 };
+
+/* the luminance weights of the adaptive error (rtr_accum_refine), left to right */
+RT_DEV double luminance(const V3 c) { return 0.2126 * c.x + 0.7152 * c.y + 0.0722 * c.z; }
 
 RT_DEV bool render_cancelled(const RenderK& P) {
     return __hip_atomic_load(P.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.render_id;

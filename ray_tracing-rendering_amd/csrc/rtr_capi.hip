@@ -86,7 +86,10 @@ struct rtr_accum {
     uint64_t scene_gen = 0;
     std::vector<int> tiles; /* owned tiles, dispatch order; slot k = tiles[k] */
     int tiles_x = 0, tiles_y = 0;
+    bool moments = false; /* RTR_ACCUM_MOMENTS: d_q / d_qpart exist and the passes run k_mega<..., ACC = 2> */
     DevBuf d_tiles, d_sum, d_count; /* [n] int, [n][3][RTR_BLOCK] double, [n] int */
+    DevBuf d_q, d_qpart; /* [n][RTR_BLOCK] double: committed second moments, and the pass's (committed by k_accum_commit) */
+    DevBuf d_s1, d_active, d_nactive, d_err; /* plan of a pass (k_accum_plan): [n] targets, [n] active slots, 1 int; [n] errors */
     mutable std::vector<int> h_counts; /* host copy of d_count ... */
     mutable bool counts_stale = false; /* ... unless a pass was queued since it was read */
     DevBuf d_out; /* rtr_accum_resolve staging: [n][RTR_BLOCK][3] doubles, then [n][RTR_BLOCK][3] bytes */
@@ -453,7 +456,7 @@ int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, b
     L.sorted = (flags & RTR_FLAG_SORTED_SHADING) && c->n_materials <= 65535 && mega_sortable(integrator, L.trav, L.lean ? RT_MS_LEAN : (L.quadlit ? RT_MS_QUADLIT : RT_MS_FULL));
     L.lds = stack_bytes(c, L.trav) + (size_t)(L.sorted ? SK_WORDS : park_words(integrator, L.trav)) * RTR_BLOCK * sizeof(double);
     L.program_ext = c->guarded_program;
-    L.accum = P.tile_s0 != nullptr;
+    L.accum = P.tile_s0 == nullptr ? 0 : (P.q_in ? 2 : 1);
     L.stream = c->stream;
     L.P = P;
     L.dry = dry;
@@ -541,6 +544,59 @@ int accum_check(rtr_context* c, const rtr_accum* a) {
     return RTR_OK;
 }
 
+/* ... and those of the calls that render */
+int accum_render_check(rtr_context* c, const rtr_accum* a) {
+    if (int rc = accum_check(c, a)) return rc;
+    if (!c->has_scene || a->scene_gen != c->scene_gen)
+        return fail(c, RTR_ERR_INVALID, "the scene changed since the accumulator was created (rtr_upload_scene)");
+    return RTR_OK;
+}
+
+/* an accumulator's sums and counts as kernel parameters (k_accum_resolve, k_accum_errors) */
+AccumResolveK accum_view(const rtr_accum* a) {
+    const rtr_render_params& p = a->params;
+    AccumResolveK R{};
+    R.r.W = p.image_width, R.r.H = p.image_height;
+    R.r.x0 = p.x0, R.r.y0 = p.y0, R.r.x1 = p.x1, R.r.y1 = p.y1;
+    R.r.tiles_x = a->tiles_x, R.r.tiles_y = a->tiles_y;
+    R.r.tile_ids = static_cast<const int*>(a->d_tiles.p);
+    R.r.n_tiles = (int)a->tiles.size();
+    R.sum = static_cast<const double*>(a->d_sum.p);
+    R.count = static_cast<const int*>(a->d_count.p);
+    return R;
+}
+
+/* the device and pinned host staging of rtr_accum_resolve / rtr_accum_moments, at least `bytes` each */
+int staging(rtr_context* c, rtr_accum* a, size_t bytes) {
+    if (int rc = ensure(c, a->d_out, bytes)) return rc;
+    if (bytes > a->h_out_cap) {
+        if (a->h_out) HIPCHK(c, hipHostFree(a->h_out));
+        a->h_out = nullptr, a->h_out_cap = 0;
+        if (hipHostMalloc(&a->h_out, bytes, hipHostMallocDefault) != hipSuccess)
+            return fail(c, RTR_ERR_NOMEM, "hipHostMalloc of the resolve staging buffer");
+        a->h_out_cap = bytes;
+    }
+    return RTR_OK;
+}
+
+/* every row of an owned tile that holds samples, clipped to the region: f(slot, row in the tile, j, i0, i1, tile x0) --
+ * where the host scatters packed tiles into a caller's region (its other pixels stay) */
+template <class F>
+void for_each_owned_row(const rtr_accum* a, F f) {
+    const rtr_render_params& p = a->params;
+    for (size_t k = 0; k < a->tiles.size(); ++k) {
+        if (a->h_counts[k] == 0) continue;
+        const int t = a->tiles[k];
+        const int tx0 = (t % a->tiles_x) * 16, ty0 = ((a->tiles_y - 1) - t / a->tiles_x) * 16; /* renderer.h:61-62 */
+        const int i0 = std::max(tx0, p.x0), i1 = std::min(tx0 + 16, p.x1);
+        if (i0 >= i1) continue;
+        for (int r = 0; r < 16; ++r) {
+            const int j = ty0 + r;
+            if (j >= p.y0 && j < p.y1) f(k, r, j, i0, i1, tx0);
+        }
+    }
+}
+
 int finish_stats(rtr_context* c) {
     if (!c->stats_pending) {
         if (c->in_flight) { /* a call that failed after its first stream-ordered step: wait for what it queued */
@@ -589,7 +645,7 @@ int finish_stats(rtr_context* c) {
 } // namespace
 
 static void free_accum(rtr_accum* a) {
-    DevBuf* bufs[] = {&a->d_tiles, &a->d_sum, &a->d_count, &a->d_out};
+    DevBuf* bufs[] = {&a->d_tiles, &a->d_sum, &a->d_count, &a->d_out, &a->d_q, &a->d_qpart, &a->d_s1, &a->d_active, &a->d_nactive, &a->d_err};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (a->h_out) hipHostFree(a->h_out);
@@ -1026,7 +1082,7 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
 
 /* the render call proper; tile_done != nullptr: packed output (see ResolveK) */
 static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb, int64_t row_stride, unsigned char* tile_done,
-                       int blocking, rtr_accum* acc = nullptr);
+                       int blocking, rtr_accum* acc = nullptr, const AccumPlanK* plan = nullptr);
 
 int rtr_render_device(rtr_context* c, const rtr_render_params* p, double* d_rgb, int64_t row_stride, int blocking) {
     if (!c) return RTR_ERR_INVALID;
@@ -1036,10 +1092,12 @@ int rtr_render_device(rtr_context* c, const rtr_render_params* p, double* d_rgb,
     return render_core(c, p, d_rgb, row_stride, nullptr, blocking);
 }
 
-/* acc != nullptr: a pass of that accumulator (p->spp = the target, p->spp_chunks = 1): its tile list, its counts as start
- * samples and its sums as start values; the commit kernel takes the place of k_resolve */
+/* acc != nullptr: a pass of that accumulator (p->spp_chunks = 1): its tile list, its counts as start samples and its
+ * sums (and moments) as start values; `plan` (mode, targets, refinement bounds) says how k_accum_plan sets each tile's
+ * end sample and the active list before the megakernel, k_accum_errors runs first for a refinement, and the commit
+ * kernel takes the place of k_resolve */
 static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb, int64_t row_stride, unsigned char* tile_done,
-                       int blocking, rtr_accum* acc) {
+                       int blocking, rtr_accum* acc, const AccumPlanK* plan) {
     HIPCHK(c, hipSetDevice(c->device));
     (void)hipGetLastError(); /* a launch error of an earlier call (ours or the host framework's) is not this call's */
     int rc = RTR_OK;
@@ -1103,6 +1161,13 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     if (acc) {
         P.tile_s0 = static_cast<const int*>(acc->d_count.p);
         P.acc_in = static_cast<const double*>(acc->d_sum.p);
+        P.tile_s1 = static_cast<const int*>(acc->d_s1.p);
+        P.active = static_cast<const int*>(acc->d_active.p);
+        P.n_active = static_cast<const int*>(acc->d_nactive.p);
+        if (acc->moments) {
+            P.q_in = static_cast<const double*>(acc->d_q.p);
+            P.q_part = static_cast<double*>(acc->d_qpart.p);
+        }
     }
     P.stats = static_cast<unsigned long long*>(c->b_stats.p);
     P.cancel = static_cast<const uint32_t*>(c->b_cancel.p);
@@ -1144,18 +1209,38 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
         if (rc == RTR_ERR_CANCELLED) c->stats.cancelled = 1;
         c->stats.kernel_launches = launches;
     } else {
-        if ((rc = launch_mega(c, P, p->integrator, trav, false, nullptr, p->flags, &c->stats.flags_in_effect, &launched))) return rc;
-        c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, 0, 0, 0, 0, 0, 0};
-        if (acc) {
+        int launches = 2;
+        if (acc) { /* the pass's plan, on the device: no host round trip between a refinement's decision and its pass */
             acc->counts_stale = true;
+            AccumPlanK K = *plan;
+            K.n_tiles = P.n_tiles;
+            K.count = static_cast<const int*>(acc->d_count.p);
+            K.err = static_cast<const double*>(acc->d_err.p);
+            K.tile_s1 = static_cast<int*>(acc->d_s1.p);
+            K.active = static_cast<int*>(acc->d_active.p);
+            K.n_active = static_cast<int*>(acc->d_nactive.p);
+            if (K.mode == 2) {
+                hipLaunchKernelGGL(k_accum_errors, dim3((unsigned)P.n_tiles), dim3(RTR_BLOCK), 0, c->stream, accum_view(acc),
+                                   static_cast<const double*>(acc->d_q.p), static_cast<double*>(acc->d_err.p));
+                ++launches;
+            }
+            hipLaunchKernelGGL(k_accum_plan, dim3(1), dim3(1024), 0, c->stream, K);
+            ++launches;
+            HIPCHK(c, hipGetLastError());
+        }
+        if ((rc = launch_mega(c, P, p->integrator, trav, false, nullptr, p->flags, &c->stats.flags_in_effect, &launched))) return rc;
+        c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, 0, 0, 0, 0, 0, 0,
+                                          acc ? (acc->moments ? 2 : 1) : 0};
+        if (acc) {
             hipLaunchKernelGGL(k_accum_commit, dim3((unsigned)P.n_tiles), dim3(RTR_BLOCK), 0, c->stream, P,
-                               static_cast<double*>(acc->d_sum.p), static_cast<int*>(acc->d_count.p));
+                               static_cast<double*>(acc->d_sum.p), static_cast<double*>(acc->moments ? acc->d_q.p : nullptr),
+                               static_cast<int*>(acc->d_count.p));
         } else {
             ResolveK R{P, d_rgb, (long long)row_stride, tile_done};
             rtr_launch_resolve(R, c->stream);
         }
         HIPCHK(c, hipGetLastError());
-        c->stats.kernel_launches = 2;
+        c->stats.kernel_launches = launches;
     }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->stats.pipeline = pipeline;
@@ -1252,11 +1337,14 @@ int rtr_plan_chunks(rtr_context* c, const rtr_render_params* p) {
     return chunks;
 }
 
-int rtr_accum_create(rtr_context* c, const rtr_render_params* p, rtr_accum** out) {
+int rtr_accum_create(rtr_context* c, const rtr_render_params* p, rtr_accum** out) { return rtr_accum_create_ex(c, p, 0, out); }
+
+int rtr_accum_create_ex(rtr_context* c, const rtr_render_params* p, uint32_t accum_flags, rtr_accum** out) {
     if (!c) return RTR_ERR_INVALID;
     if (!out) return fail(c, RTR_ERR_INVALID, "null out");
     *out = nullptr;
     if (!p) return fail(c, RTR_ERR_INVALID, "null params");
+    if (accum_flags & ~(uint32_t)RTR_ACCUM_MOMENTS) return fail(c, RTR_ERR_INVALID, "unknown accumulator flags");
     if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_accum_create before rtr_upload_scene");
     rtr_render_params q = *p;
     q.spp = 1, q.spp_chunks = 1; /* ignored: one running sum per pixel, targets come with the passes */
@@ -1267,15 +1355,23 @@ int rtr_accum_create(rtr_context* c, const rtr_render_params* p, rtr_accum** out
     a->ctx = c;
     a->params = q;
     a->scene_gen = c->scene_gen;
+    a->moments = (accum_flags & RTR_ACCUM_MOMENTS) != 0;
     a->tiles = owned_tiles(q, a->tiles_x, a->tiles_y);
     const size_t n = a->tiles.size();
     a->h_counts.assign(n, 0);
     int rc = upload(c, a->d_tiles, a->tiles.data(), n * sizeof(int));
     if (!rc) rc = ensure(c, a->d_sum, n * 3 * RTR_BLOCK * sizeof(double));
     if (!rc) rc = ensure(c, a->d_count, n * sizeof(int));
+    if (!rc) rc = ensure(c, a->d_s1, n * sizeof(int));
+    if (!rc) rc = ensure(c, a->d_active, n * sizeof(int));
+    if (!rc) rc = ensure(c, a->d_nactive, sizeof(int));
+    if (!rc && a->moments) rc = ensure(c, a->d_q, n * RTR_BLOCK * sizeof(double));
+    if (!rc && a->moments) rc = ensure(c, a->d_qpart, n * RTR_BLOCK * sizeof(double));
+    if (!rc && a->moments) rc = ensure(c, a->d_err, n * sizeof(double));
     if (!rc && n) {
         hipError_t e = hipMemsetAsync(a->d_sum.p, 0, n * 3 * RTR_BLOCK * sizeof(double), c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(a->d_count.p, 0, n * sizeof(int), c->stream);
+        if (e == hipSuccess && a->moments) e = hipMemsetAsync(a->d_q.p, 0, n * RTR_BLOCK * sizeof(double), c->stream);
         if (e != hipSuccess) rc = fail(c, RTR_ERR_DEVICE, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
     }
     if (rc) {
@@ -1289,9 +1385,7 @@ int rtr_accum_create(rtr_context* c, const rtr_render_params* p, rtr_accum** out
 
 int rtr_accum_render(rtr_context* c, rtr_accum* a, int32_t spp_target, int blocking) {
     if (!c) return RTR_ERR_INVALID;
-    if (int rc = accum_check(c, a)) return rc;
-    if (!c->has_scene || a->scene_gen != c->scene_gen)
-        return fail(c, RTR_ERR_INVALID, "the scene changed since the accumulator was created (rtr_upload_scene)");
+    if (int rc = accum_render_check(c, a)) return rc;
     if (spp_target < 0) return fail(c, RTR_ERR_INVALID, "negative target");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = refresh_counts(c, a)) return rc;
@@ -1307,7 +1401,58 @@ int rtr_accum_render(rtr_context* c, rtr_accum* a, int32_t spp_target, int block
     }
     rtr_render_params q = a->params;
     q.spp = spp_target, q.spp_chunks = 1;
-    return render_core(c, &q, nullptr, 0, nullptr, blocking, a);
+    AccumPlanK plan{};
+    plan.mode = 1, plan.spp = spp_target;
+    return render_core(c, &q, nullptr, 0, nullptr, blocking, a, &plan);
+}
+
+int rtr_accum_render_tiles(rtr_context* c, rtr_accum* a, const int32_t* targets, int64_t n, int blocking) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_render_check(c, a)) return rc;
+    if (!targets) return fail(c, RTR_ERR_INVALID, "null targets");
+    if (n != (int64_t)a->tiles.size()) return fail(c, RTR_ERR_INVALID, "n is not the number of owned tiles");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refresh_counts(c, a)) return rc; /* (and the passes that read the old targets have finished) */
+    bool behind = false;
+    for (int64_t k = 0; k < n; ++k) {
+        if (targets[k] < a->h_counts[k]) return fail(c, RTR_ERR_INVALID, "target below the sample count of a tile");
+        behind = behind || a->h_counts[k] < targets[k];
+    }
+    if (!behind) {
+        if (int rc = finish_stats(c)) return rc;
+        c->stats = rtr_render_stats{};
+        return RTR_OK;
+    }
+    if (int rc = upload(c, a->d_s1, targets, (size_t)n * sizeof(int32_t))) return rc;
+    rtr_render_params q = a->params;
+    q.spp = *std::max_element(targets, targets + n), q.spp_chunks = 1;
+    AccumPlanK plan{};
+    plan.mode = 0;
+    return render_core(c, &q, nullptr, 0, nullptr, blocking, a, &plan);
+}
+
+int rtr_accum_refine(rtr_context* c, rtr_accum* a, double threshold, int32_t spp_min, int32_t spp_max, int blocking,
+                     int32_t* n_active) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_render_check(c, a)) return rc;
+    if (!a->moments) return fail(c, RTR_ERR_INVALID, "the accumulator keeps no moments (RTR_ACCUM_MOMENTS)");
+    if (!(threshold > 0.0)) return fail(c, RTR_ERR_INVALID, "threshold must be > 0");
+    if (spp_min < 1 || spp_max < spp_min) return fail(c, RTR_ERR_INVALID, "need 1 <= spp_min <= spp_max");
+    if (n_active) *n_active = -1;
+    HIPCHK(c, hipSetDevice(c->device));
+    rtr_render_params q = a->params;
+    q.spp = spp_max, q.spp_chunks = 1;
+    AccumPlanK plan{};
+    plan.mode = 2, plan.spp_min = spp_min, plan.spp_max = spp_max, plan.threshold = threshold;
+    int rc = render_core(c, &q, nullptr, 0, nullptr, blocking, a, &plan);
+    if ((rc == RTR_OK || rc == RTR_ERR_CANCELLED) && blocking && n_active && !a->tiles.empty()) {
+        int na = 0;
+        HIPCHK(c, hipMemcpy(&na, a->d_nactive.p, sizeof(int), hipMemcpyDeviceToHost));
+        *n_active = na;
+    } else if (rc == RTR_OK && n_active && a->tiles.empty()) {
+        *n_active = 0;
+    }
+    return rc;
 }
 
 int rtr_accum_resolve(rtr_context* c, rtr_accum* a, double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
@@ -1322,24 +1467,10 @@ int rtr_accum_resolve(rtr_context* c, rtr_accum* a, double* h_linear, int64_t ro
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = refresh_counts(c, a)) return rc; /* (waits for the passes queued before) */
     const size_t lin_bytes = n * RTR_BLOCK * 3 * sizeof(double), rgb_bytes = n * RTR_BLOCK * 3;
-    if (int rc = ensure(c, a->d_out, lin_bytes + rgb_bytes)) return rc;
-    if (lin_bytes + rgb_bytes > a->h_out_cap) {
-        if (a->h_out) HIPCHK(c, hipHostFree(a->h_out));
-        a->h_out = nullptr, a->h_out_cap = 0;
-        if (hipHostMalloc(&a->h_out, lin_bytes + rgb_bytes, hipHostMallocDefault) != hipSuccess)
-            return fail(c, RTR_ERR_NOMEM, "hipHostMalloc of the resolve staging buffer");
-        a->h_out_cap = lin_bytes + rgb_bytes;
-    }
+    if (int rc = staging(c, a, lin_bytes + rgb_bytes)) return rc;
     char* d = static_cast<char*>(a->d_out.p);
     char* h = static_cast<char*>(a->h_out);
-    AccumResolveK R{};
-    R.r.W = p.image_width, R.r.H = p.image_height;
-    R.r.x0 = p.x0, R.r.y0 = p.y0, R.r.x1 = p.x1, R.r.y1 = p.y1;
-    R.r.tiles_x = a->tiles_x, R.r.tiles_y = a->tiles_y;
-    R.r.tile_ids = static_cast<const int*>(a->d_tiles.p);
-    R.r.n_tiles = (int)n;
-    R.sum = static_cast<const double*>(a->d_sum.p);
-    R.count = static_cast<const int*>(a->d_count.p);
+    AccumResolveK R = accum_view(a);
     R.out = h_linear ? reinterpret_cast<double*>(d) : nullptr;
     R.rgb8 = h_rgb8 ? reinterpret_cast<unsigned char*>(d + lin_bytes) : nullptr;
     hipLaunchKernelGGL(k_accum_resolve, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, R);
@@ -1350,23 +1481,14 @@ int rtr_accum_resolve(rtr_context* c, rtr_accum* a, double* h_linear, int64_t ro
     /* scatter the owned tiles that hold samples into the region (the caller's other pixels stay) */
     const double* lin = reinterpret_cast<const double*>(h);
     const unsigned char* rgb = reinterpret_cast<const unsigned char*>(h + lin_bytes);
-    for (size_t k = 0; k < n; ++k) {
-        if (a->h_counts[k] == 0) continue;
-        const int t = a->tiles[k];
-        const int tx0 = (t % a->tiles_x) * 16, ty0 = ((a->tiles_y - 1) - t / a->tiles_x) * 16; /* renderer.h:61-62 */
-        for (int r = 0; r < 16; ++r) {
-            const int j = ty0 + r;
-            if (j < p.y0 || j >= p.y1) continue;
-            const int i0 = std::max(tx0, p.x0), i1 = std::min(tx0 + 16, p.x1);
-            if (i0 >= i1) continue;
-            const size_t src = (k * RTR_BLOCK + (size_t)r * 16 + (size_t)(i0 - tx0)) * 3, len = (size_t)(i1 - i0) * 3;
-            if (h_linear)
-                std::memcpy(h_linear + ((size_t)(j - p.y0) * (size_t)row_stride + (size_t)(i0 - p.x0)) * 3, lin + src,
-                            len * sizeof(double));
-            if (h_rgb8) /* Y flipped: the top row of the region first (render_buffer.h:40-41) */
-                std::memcpy(h_rgb8 + ((size_t)(p.y1 - 1 - j) * (size_t)w + (size_t)(i0 - p.x0)) * 3, rgb + src, len);
-        }
-    }
+    for_each_owned_row(a, [&](size_t k, int r, int j, int i0, int i1, int tx0) {
+        const size_t src = (k * RTR_BLOCK + (size_t)r * 16 + (size_t)(i0 - tx0)) * 3, len = (size_t)(i1 - i0) * 3;
+        if (h_linear)
+            std::memcpy(h_linear + ((size_t)(j - p.y0) * (size_t)row_stride + (size_t)(i0 - p.x0)) * 3, lin + src,
+                        len * sizeof(double));
+        if (h_rgb8) /* Y flipped: the top row of the region first (render_buffer.h:40-41) */
+            std::memcpy(h_rgb8 + ((size_t)(p.y1 - 1 - j) * (size_t)w + (size_t)(i0 - p.x0)) * 3, rgb + src, len);
+    });
     return RTR_OK;
 }
 
@@ -1380,6 +1502,45 @@ int rtr_accum_tiles(rtr_context* c, const rtr_accum* a, int32_t* tile_ids, int32
     *n_tiles = (int64_t)n;
     if (tile_ids && m) std::memcpy(tile_ids, a->tiles.data(), m * sizeof(int32_t));
     if (counts && m) std::memcpy(counts, a->h_counts.data(), m * sizeof(int32_t));
+    return RTR_OK;
+}
+
+int rtr_accum_moments(rtr_context* c, rtr_accum* a, double* h_q, int64_t row_stride) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    if (!a->moments) return fail(c, RTR_ERR_INVALID, "the accumulator keeps no moments (RTR_ACCUM_MOMENTS)");
+    const rtr_render_params& p = a->params;
+    if (!h_q || row_stride < (int64_t)(p.x1 - p.x0)) return fail(c, RTR_ERR_INVALID, "bad output buffer / stride");
+    const size_t n = a->tiles.size();
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refresh_counts(c, a)) return rc;
+    const size_t bytes = n * RTR_BLOCK * sizeof(double);
+    if (int rc = staging(c, a, bytes)) return rc;
+    HIPCHK(c, hipMemcpyAsync(a->h_out, a->d_q.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double* q = static_cast<const double*>(a->h_out);
+    for_each_owned_row(a, [&](size_t k, int r, int j, int i0, int i1, int tx0) {
+        std::memcpy(h_q + (size_t)(j - p.y0) * (size_t)row_stride + (size_t)(i0 - p.x0),
+                    q + k * RTR_BLOCK + (size_t)r * 16 + (size_t)(i0 - tx0), (size_t)(i1 - i0) * sizeof(double));
+    });
+    return RTR_OK;
+}
+
+int rtr_accum_errors(rtr_context* c, rtr_accum* a, double* tile_err, int64_t cap, int64_t* n_tiles) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    if (!a->moments) return fail(c, RTR_ERR_INVALID, "the accumulator keeps no moments (RTR_ACCUM_MOMENTS)");
+    if (!n_tiles || cap < 0) return fail(c, RTR_ERR_INVALID, "null n_tiles or negative cap");
+    const size_t n = a->tiles.size(), m = std::min(n, (size_t)cap);
+    *n_tiles = (int64_t)n;
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_accum_errors, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, accum_view(a),
+                       static_cast<const double*>(a->d_q.p), static_cast<double*>(a->d_err.p));
+    HIPCHK(c, hipGetLastError());
+    if (tile_err && m) HIPCHK(c, hipMemcpyAsync(tile_err, a->d_err.p, m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTR_OK;
 }
 

@@ -43,8 +43,10 @@ int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
 
 template <int I, int T, int M, bool S = false>
 int launch_rec(const MegaLaunch& L, std::string& err) {
-    /* (an accumulator pass: the same variant with ACC, rt_kernels.h) */
-    const int rc = L.accum ? launch_one(k_mega<I, T, M, S, true>, L, err) : launch_one(k_mega<I, T, M, S>, L, err);
+    /* (an accumulator pass: the same variant with ACC = 1, or 2 with moments, rt_kernels.h) */
+    const int rc = L.accum == 2 ? launch_one(k_mega<I, T, M, S, 2>, L, err)
+                   : L.accum    ? launch_one(k_mega<I, T, M, S, 1>, L, err)
+                                : launch_one(k_mega<I, T, M, S>, L, err);
     if (rc == RTR_OK && !L.dry && L.launched) {
         L.launched->trav = T;
         L.launched->ms = M;

@@ -8,13 +8,34 @@
  *           [--devices 0,1,...|all] [--repeat N]   one context + host thread per listed GPU (an ordinal may repeat)
  *           [--passes 1,4,16,...]   progressive: Renderer::render_progressive through these increasing sample counts (the
  *                                   last one replaces --spp; the image is the one --spp gives), time per pass
+ *           [--adaptive THRESH [--spp-min N]]   adaptive: Renderer::render_adaptive with error threshold THRESH (a number
+ *                                   or a fraction such as 1/255), spp_min N (default min(16, spp_max)) and --spp as spp_max;
+ *                                   time, tiles refined and samples per pass, and the total samples against W*H*spp_max
  */
 #include "rtr_renderer.h"
 
+#include <cmath>
 #include <cstring>
 
+/* "0.004" or "1/255"; false unless the whole string is such a number */
+static bool parse_threshold(const char* s, double& out) {
+    char* end = nullptr;
+    double v = std::strtod(s, &end);
+    if (end == s) return false;
+    if (*end == '/') {
+        const char* d = end + 1;
+        const double den = std::strtod(d, &end);
+        if (end == d || den == 0.0) return false;
+        v /= den;
+    }
+    out = v;
+    return *end == '\0';
+}
+
 int main(int argc, char** argv) {
-    int scene_id = 21, integrator_id = 4, width = 0, spp = 0, bands = 0, repeat = 1;
+    int scene_id = 21, integrator_id = 4, width = 0, spp = 0, bands = 0, repeat = 1, spp_min = 0;
+    bool adaptive = false;
+    double threshold = 0.0;
     std::vector<int> devices{0}, passes;
     unsigned seed = 1;
     std::string out;
@@ -26,6 +47,20 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--out") && k + 1 < argc) out = argv[++k];
         else if (!std::strcmp(argv[k], "--bands") && k + 1 < argc) bands = std::atoi(argv[++k]);
         else if (!std::strcmp(argv[k], "--repeat") && k + 1 < argc) repeat = std::atoi(argv[++k]);
+        else if (!std::strcmp(argv[k], "--adaptive") && k + 1 < argc) {
+            adaptive = true;
+            if (!parse_threshold(argv[++k], threshold) || !(threshold > 0.0) || !std::isfinite(threshold)) {
+                std::cerr << "--adaptive: the threshold must be a finite number > 0, not " << argv[k] << "\n";
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--spp-min") && k + 1 < argc) {
+            spp_min = std::atoi(argv[++k]);
+            if (spp_min < 1) {
+                std::cerr << "--spp-min must be >= 1, not " << argv[k] << "\n";
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[k], "--passes") && k + 1 < argc) {
             const std::string v = argv[++k];
             for (size_t a = 0; a < v.size();) {
@@ -50,6 +85,18 @@ int main(int argc, char** argv) {
         else if (pos == 0) scene_id = std::atoi(argv[k]), ++pos;
         else if (pos == 1) integrator_id = std::atoi(argv[k]), ++pos;
     }
+    if (spp_min && !adaptive) {
+        std::cerr << "--spp-min goes with --adaptive\n";
+        return 2;
+    }
+    if (adaptive && !passes.empty()) {
+        std::cerr << "--adaptive and --passes exclude each other\n";
+        return 2;
+    }
+    if (adaptive && spp_min && spp > 0 && spp < spp_min) {
+        std::cerr << "--adaptive: --spp (the maximum) must be >= --spp-min\n";
+        return 2;
+    }
     rtr::rng_state() = 12345u; /* scene-construction seed */
     SceneConfig config;
     try {
@@ -61,6 +108,11 @@ int main(int argc, char** argv) {
     if (width > 0) config.image_width = width;
     if (spp > 0) config.samples_per_pixel = spp;
     if (!passes.empty()) config.samples_per_pixel = passes.back();
+    if (adaptive && spp_min > config.samples_per_pixel) {
+        std::cerr << "--adaptive: the scene's " << config.samples_per_pixel << " spp (the maximum) is below --spp-min\n";
+        return 2;
+    }
+    if (adaptive && !spp_min) spp_min = std::min(16, config.samples_per_pixel);
     auto cam = make_shared<camera>(config.lookfrom, config.lookat, config.vup, config.vfov, config.aspect_ratio,
                                    config.aperture, config.focus_dist, 0.0, 1.0); /* main.cpp:63-66 */
     const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);
@@ -78,7 +130,21 @@ int main(int argc, char** argv) {
     renderer.set_seed(seed);
     renderer.set_progress_bands(bands);
     for (int r = 0; r < repeat; ++r) { /* a second call finds the flattened scene on the GPUs */
-        if (passes.empty()) {
+        if (adaptive) {
+            auto t = std::chrono::high_resolution_clock::now();
+            long long total = 0;
+            renderer.render_adaptive(config.world, cam, config.background, buffer, config.lights, threshold, spp_min,
+                                     config.samples_per_pixel, [&](int pass, int active, long long samples) {
+                const auto now = std::chrono::high_resolution_clock::now();
+                std::cout << "adaptive pass " << pass << ": " << std::chrono::duration<double>(now - t).count() * 1e3
+                          << " ms, " << active << " tiles refined, " << samples << " samples\n";
+                t = now;
+                total = samples;
+            });
+            const double uniform = (double)W * H * config.samples_per_pixel;
+            std::cout << "adaptive total: " << total << " samples of " << (long long)uniform << " (W*H*spp_max), "
+                      << 100.0 * (double)total / uniform << " %\n";
+        } else if (passes.empty()) {
             renderer.render(config.world, cam, config.background, buffer, config.lights);
         } else {
             auto t = std::chrono::high_resolution_clock::now();

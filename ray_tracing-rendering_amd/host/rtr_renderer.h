@@ -322,8 +322,34 @@ class Renderer {
             std::cerr << "render failed (" << m_status << "): " << m_error << "\n";
     }
 
+    /* Adaptive rendering: every context keeps one accumulator with second moments (include/rtr_hip.h:
+     * rtr_accum_refine) on the tiles it owns.  The first pass takes every tile to spp_min samples; each later pass
+     * doubles the samples of the tiles whose error estimate is above `threshold` (1/255 = one 8-bit step), up to
+     * spp_max.  All contexts run a pass side by side, store their tiles into `target_buffer`, and then
+     * on_pass(pass from 1, tiles refined, samples rendered so far) is called; it ends when no tile of any context is
+     * left to refine.  The decisions are tile-local, so the counts and the image do not depend on the number of
+     * contexts; a tile holding T samples is the bits of a render with spp = T and spp_chunks = 1.  cancel() stops it
+     * between or inside passes.  Uses the scene cache of render(). */
+    void render_adaptive(shared_ptr<hittable> world, shared_ptr<camera> cam, const color& background,
+                         RenderBuffer& target_buffer, const std::vector<shared_ptr<Light>>& lights, double threshold,
+                         int spp_min, int spp_max, const std::function<void(int, int, long long)>& on_pass = nullptr) {
+        m_is_rendering = true;
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        const bool same_scene = world == m_world && cam == m_cam && lights == m_lights &&
+                                background[0] == m_scene_bg[0] && background[1] == m_scene_bg[1] && background[2] == m_scene_bg[2];
+        m_status = adaptive_impl(*world, *cam, background, target_buffer, lights, same_scene && m_scene_valid, threshold,
+                                 spp_min, spp_max, on_pass);
+        if (m_scene_valid) m_world = world, m_cam = cam, m_lights = lights;
+        m_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        m_is_rendering = false;
+        if (m_status == RTR_OK)
+            std::cout << "Rendering finished in " << m_seconds << " seconds." << std::endl;
+        else
+            std::cerr << "render failed (" << m_status << "): " << m_error << "\n";
+    }
+
   private:
-    /* what render() and render_progressive() check and upload before they render */
+    /* what render(), render_progressive() and render_adaptive() check and upload before they render */
     int prepare(const hittable& world, const camera& cam, const color& background, const std::vector<shared_ptr<Light>>& lights,
                 bool scene_on_device) {
         if (m_create_status != RTR_OK) return m_error = m_create_error, m_create_status;
@@ -404,6 +430,59 @@ class Renderer {
             if (on_pass) on_pass(target);
         }
         return RTR_OK;
+    }
+
+    int adaptive_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,
+                      const std::vector<shared_ptr<Light>>& lights, bool scene_on_device, double threshold, int spp_min,
+                      int spp_max, const std::function<void(int, int, long long)>& on_pass) {
+        if (!(threshold > 0.0)) return m_error = "threshold must be > 0", RTR_ERR_INVALID;
+        if (spp_min < 1 || spp_max < spp_min) return m_error = "need 1 <= spp_min <= spp_max", RTR_ERR_INVALID;
+        if (int rc = prepare(world, cam, background, lights, scene_on_device)) return rc;
+        const int n = (int)m_ctx.size(), W = buf.width(), H = buf.height();
+        const rtr_render_params p = base_params(W, H);
+        std::vector<rtr_accum*> acc(n, nullptr);
+        struct Release {
+            std::vector<rtr_accum*>& a;
+            ~Release() {
+                for (rtr_accum* x : a) rtr_accum_destroy(x);
+            }
+        } release{acc};
+        for (int k = 0; k < n; ++k) {
+            rtr_render_params q = p;
+            q.tile_first = k, q.tile_stride = n;
+            if (int rc = rtr_accum_create_ex(m_ctx[k], &q, RTR_ACCUM_MOMENTS, &acc[k])) return m_error = rtr_last_error(m_ctx[k]), rc;
+        }
+        std::vector<double> lin((size_t)W * H * 3);
+        long long total = 0;
+        for (int pass = 1;; ++pass) {
+            if (!m_is_rendering) return m_error = "render cancelled", RTR_ERR_CANCELLED;
+            /* one host thread per context: its refinement pass, then its resolve into the tiles it owns of `lin` */
+            std::vector<int> rcs(n, RTR_OK), active(n, 0);
+            std::vector<long long> samples(n, 0);
+            std::vector<std::string> errs(n);
+            auto work = [&](int k) {
+                int rc = rtr_accum_refine(m_ctx[k], acc[k], threshold, spp_min, spp_max, 1, &active[k]);
+                rtr_render_stats st{};
+                if (!rc) rc = rtr_get_stats(m_ctx[k], &st);
+                samples[k] = (long long)st.samples;
+                if (!rc && active[k]) rc = rtr_accum_resolve(m_ctx[k], acc[k], lin.data(), W, nullptr);
+                if (rc) rcs[k] = rc, errs[k] = rtr_last_error(m_ctx[k]);
+            };
+            if (n == 1) {
+                work(0);
+            } else {
+                std::vector<std::thread> th;
+                for (int k = 0; k < n; ++k) th.emplace_back(work, k);
+                for (auto& t : th) t.join();
+            }
+            for (int k = 0; k < n; ++k)
+                if (rcs[k]) return m_error = errs[k], rcs[k];
+            int n_active = 0;
+            for (int k = 0; k < n; ++k) n_active += active[k], total += samples[k];
+            if (n_active == 0) return RTR_OK;
+            buf.store_linear_rect(lin.data(), W, 0, 0, W, H);
+            if (on_pass) on_pass(pass, n_active, total);
+        }
     }
 
     int render_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,

@@ -22,7 +22,8 @@ _STATUS = {A.RTR_ERR_INVALID: "RTR_ERR_INVALID", A.RTR_ERR_UNSUPPORTED: "RTR_ERR
 EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "rtr_set_stream",
            "rtr_upload_scene", "rtr_render_device", "rtr_render_host", "rtr_render_tiles_host", "rtr_plan_chunks", "rtr_li_samples", "rtr_li_rays",
            "rtr_synchronize", "rtr_cancel", "rtr_get_stats", "rtr_last_error", "rtr_sample_seed", "rtr_validate_scene",
-           "rtr_accum_create", "rtr_accum_render", "rtr_accum_resolve", "rtr_accum_tiles", "rtr_accum_destroy")
+           "rtr_accum_create", "rtr_accum_render", "rtr_accum_resolve", "rtr_accum_tiles", "rtr_accum_destroy",
+           "rtr_accum_create_ex", "rtr_accum_render_tiles", "rtr_accum_moments", "rtr_accum_errors", "rtr_accum_refine")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
@@ -39,7 +40,7 @@ class SceneInfoC(C.Structure):
 class KernelRecordC(C.Structure):
     """rtr_kernel_record of include/rtr_hip_test.h"""
     _fields_ = [(name, C.c_int32) for name in ("pipeline", "integrator", "trav", "ms", "sorted", "shade_phases", "lean",
-                                               "quadlit", "sort", "media", "machine")]
+                                               "quadlit", "sort", "media", "machine", "accum")]
 
 
 class RtrError(RuntimeError):
@@ -92,6 +93,11 @@ def lib():
     L.rtr_accum_tiles.argtypes = [vp, vp, vp, vp, C.c_int64, P(C.c_int64)]
     L.rtr_accum_destroy.argtypes = [vp]
     L.rtr_accum_destroy.restype = None
+    L.rtr_accum_create_ex.argtypes = [vp, P(A.RenderParamsC), C.c_uint32, P(vp)]
+    L.rtr_accum_render_tiles.argtypes = [vp, vp, vp, C.c_int64, C.c_int]
+    L.rtr_accum_moments.argtypes = [vp, vp, vp, C.c_int64]
+    L.rtr_accum_errors.argtypes = [vp, vp, vp, C.c_int64, P(C.c_int64)]
+    L.rtr_accum_refine.argtypes = [vp, vp, C.c_double, C.c_int32, C.c_int32, C.c_int, P(C.c_int32)]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -231,10 +237,11 @@ class Context:
         self._chk(self._L.rtr_li_rays(self._h, C.byref(params), rays.ctypes.data, out.ctypes.data, n))
         return out
 
-    def accumulator(self, params):
+    def accumulator(self, params, moments=False):
         """A progressive accumulator (rtr_accum_*) bound to ``params``' region, image size, tile sharding, seed,
-        integrator, depths, pipeline and flags (its spp and spp_chunks are ignored) and to the scene uploaded now."""
-        a = Accumulator(self, params)
+        integrator, depths, pipeline and flags (its spp and spp_chunks are ignored) and to the scene uploaded now.
+        ``moments``: it also keeps per-pixel second moments (RTR_ACCUM_MOMENTS), for ``errors`` and ``refine``."""
+        a = Accumulator(self, params, moments)
         self._accums.add(a)
         return a
 
@@ -307,12 +314,13 @@ class Accumulator:
     sum per pixel from its own sample count, so the image after passes ending at T is the bits of
     ``Context.render`` with spp = T and spp_chunks = 1.  Use as a context manager or call ``close()``."""
 
-    def __init__(self, ctx, params):
+    def __init__(self, ctx, params, moments=False):
         self._ctx = ctx
         self._L = ctx._L
         self.params = params
+        self.moments_kept = bool(moments)
         h = C.c_void_p()
-        ctx._chk(self._L.rtr_accum_create(ctx._h, C.byref(params), C.byref(h)))
+        ctx._chk(self._L.rtr_accum_create_ex(ctx._h, C.byref(params), A.ACCUM_MOMENTS if moments else 0, C.byref(h)))
         self._h = h
         self.shape = (params.y1 - params.y0, params.x1 - params.x0)
 
@@ -357,6 +365,40 @@ class Accumulator:
         self._ctx._chk(self._L.rtr_accum_tiles(self._ctx._h, self._handle(), ids.ctypes.data, counts.ctypes.data,
                                                n.value, C.byref(n)))
         return ids, counts
+
+    def render_tiles(self, targets, blocking=True):
+        """One pass with a target per owned tile, in the order of ``tiles()`` (rtr_accum_render_tiles)."""
+        t = np.ascontiguousarray(targets, dtype=np.int32)
+        self._ctx._chk(self._L.rtr_accum_render_tiles(self._ctx._h, self._handle(), t.ctypes.data, len(t),
+                                                      1 if blocking else 0))
+
+    def moments(self, out=None):
+        """The raw second moments Q = sum of y * y over the samples, (H, W) float64 like ``resolve``; pixels of tiles
+        not owned or without samples keep the values of ``out``."""
+        h, w = self.shape
+        if out is None:
+            out = np.zeros((h, w), dtype=np.float64)
+        elif out.shape != (h, w) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float64 array of shape (%d, %d)" % (h, w))
+        self._ctx._chk(self._L.rtr_accum_moments(self._ctx._h, self._handle(), out.ctypes.data, w))
+        return out
+
+    def errors(self):
+        """The error estimate of every owned tile (include/rtr_hip.h), float64 in the order of ``tiles()``."""
+        n = C.c_int64(0)
+        self._ctx._chk(self._L.rtr_accum_errors(self._ctx._h, self._handle(), None, 0, C.byref(n)))
+        err = np.zeros(n.value, dtype=np.float64)
+        self._ctx._chk(self._L.rtr_accum_errors(self._ctx._h, self._handle(), err.ctypes.data, n.value, C.byref(n)))
+        return err
+
+    def refine(self, threshold, spp_min, spp_max, blocking=True):
+        """One refinement pass decided on the device (rtr_accum_refine): tiles below ``spp_min`` go there, tiles whose
+        error is above ``threshold`` double their samples up to ``spp_max``, the others stop.  Returns the number of
+        tiles refined (0: done), or -1 when not blocking."""
+        n = C.c_int32(-1)
+        self._ctx._chk(self._L.rtr_accum_refine(self._ctx._h, self._handle(), float(threshold), int(spp_min),
+                                                int(spp_max), 1 if blocking else 0, C.byref(n)))
+        return int(n.value)
 
     def close(self):
         if getattr(self, "_h", None):

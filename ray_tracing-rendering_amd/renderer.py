@@ -1,6 +1,8 @@
 """Host-side mirror of the reference's ``Renderer`` / ``RenderBuffer``
 (renderer/renderer.h:17-142, renderer/render_buffer.h:11-84) on top of the HIP library, and the
 multi-GPU tile sharding (one process per GPU, no data-path collective)."""
+import itertools
+
 import numpy as np
 
 from . import _abi as A
@@ -160,6 +162,49 @@ class Renderer:
                     # pixels of tiles other ranks own keep what the buffer holds
                     target_buffer.store_linear(acc.resolve(target_buffer.linear.copy()))
                     yield t
+        finally:
+            self._rendering = False
+
+    def render_adaptive(self, scene, target_buffer, threshold, spp_min, spp_max, rank=0, world=1):
+        """Adaptive ``render``: a generator of refinement passes over the tiles ``rank`` owns (one accumulator with
+        second moments, include/rtr_hip.h: rtr_accum_refine).  The first pass takes every tile to ``spp_min`` samples;
+        each later one doubles the samples of the tiles whose error estimate is above ``threshold`` (1/255 = one 8-bit
+        step of the stored image), up to ``spp_max``.  After each pass the image goes into ``target_buffer`` and
+        (pass number from 1, tiles refined, samples rendered so far) is yielded; it ends when no tile is left to refine
+        or on ``cancel()``.  A tile holding T samples is the bits of a render with spp = T and spp_chunks = 1.  Bad
+        arguments raise ValueError here, before any device call."""
+        threshold = float(threshold)
+        if not threshold > 0.0:
+            raise ValueError("threshold must be > 0: %r" % threshold)
+        if int(spp_min) != spp_min or int(spp_max) != spp_max or not 1 <= spp_min <= spp_max:
+            raise ValueError("need integers 1 <= spp_min <= spp_max: %r, %r" % (spp_min, spp_max))
+        self._cancel_requested = False
+        return self._adaptive(scene, target_buffer, threshold, int(spp_min), int(spp_max), rank, world)
+
+    def _adaptive(self, scene, target_buffer, threshold, spp_min, spp_max, rank, world):
+        from .native import RtrError
+        self._rendering = True
+        try:
+            if self._ctx.scene is not scene:
+                self._ctx.upload(scene)
+            p = A.make_params(target_buffer.width, target_buffer.height, 1, integrator=self._integrator, seed=self.seed,
+                              max_depth=self._max_depth, pipeline=self.pipeline, tile_first=rank, tile_stride=world)
+            total = 0
+            with self._ctx.accumulator(p, moments=True) as acc:
+                for k in itertools.count(1):
+                    if self._cancel_requested:
+                        return
+                    try:
+                        n_active = acc.refine(threshold, spp_min, spp_max)
+                    except RtrError as e:
+                        if e.code == A.RTR_ERR_CANCELLED:
+                            return
+                        raise
+                    if n_active == 0:
+                        return
+                    total += self._ctx.stats()["samples"]
+                    target_buffer.store_linear(acc.resolve(target_buffer.linear.copy()))
+                    yield k, n_active, total
         finally:
             self._rendering = False
 
