@@ -472,6 +472,69 @@ int rtr_accum_errors(rtr_context* ctx, rtr_accum* acc, double* tile_err, int64_t
 int rtr_accum_refine(rtr_context* ctx, rtr_accum* acc, double threshold, int32_t spp_min, int32_t spp_max, int blocking,
                      int32_t* n_active);
 
+/* ---- first-hit feature buffers and an a-trous denoiser (megakernel pipeline) ----
+ *
+ * Features.  For samples s = 0 .. K-1 of pixel (i, j) the camera ray sample s of a render builds is cast to its closest
+ * hit with the traversal of the accumulator's renders (RTR_FLAG_REFERENCE_ORDER included); a medium draws from the
+ * sample's own generator state after the camera ray.  Per sample, 7 doubles:
+ *   surface hit   albedo: lambertian / isotropic / PBR the value of tex[0] at the hit, metal f[0..2], dielectric and
+ *                 diffuse_light (1, 1, 1); normal: the hit record's (no normal map); depth: t * sqrt(d.x*d.x + d.y*d.y +
+ *                 d.z*d.z), d the unnormalised ray direction
+ *   medium event  (the hit's material is isotropic) albedo as above, normal (0, 0, 0), depth as above
+ *   miss          albedo (1, 1, 1), normal (0, 0, 0), depth 0
+ * A pixel's feature is (1.0 / K) * (the sum over s in sample order).  It depends on (seed, W, i, j, K) and the scene only.
+ *
+ * Filter: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with the variance-guided luminance weight of
+ * SVGF's spatial part (Schied et al. 2017), FP64, only + - * / sqrt and compares (a numpy restatement gives the same
+ * bits).  Per valid pixel p of the region (n the tile's count, m = (1.0 / n) * sum, lum(c) = 0.2126 * c.x + 0.7152 *
+ * c.y + 0.0722 * c.z left to right, a / nn / z the features):
+ *   var_p = max(0, (1.0 / n) * Q - lum(m)^2) / (n - 1) / n, or 1e30 when n < 2; var_p /= max(lum(a), 1e-3)^2
+ *   c_p   = m / a per channel where a > 1e-3, else m
+ * Pass k = 0 .. iterations-1, step = 2^k, reading buffer k % 2 and writing the other:
+ *   g_p = sum of k3[dx] * k3[dy] * var_q / sum of k3[dx] * k3[dy] over the valid q = p + (dx, dy), dy (outer) and dx in
+ *         -1..1, k3 = {1/4, 1/2, 1/4}
+ *   taps q = p + step * (dx, dy), dy (outer) and dx in -2..2, valid ones only; h = {1, 4, 6, 4, 1} / 16;
+ *   w = h[dx] * h[dy] * w_l * w_n * w_a * w_z (left to right) with, l = lum(c),
+ *     w_l = 1 / (1 + (l_p - l_q)^2 / (sigma_l^2 * g_p + 1e-10))
+ *     w_n = 1 / (1 + |nn_p - nn_q|^2 / sigma_n^2),  w_a = 1 / (1 + |a_p - a_q|^2 / sigma_a^2)
+ *     w_z = 1 / (1 + (z_p - z_q)^2 / (sigma_z^2 * step^2 * max(z_p, 1e-3)^2))
+ *   c'_p = sum of w * c_q / sum of w,  var'_p = sum of w * w * var_q / (sum of w)^2   (sums in tap order)
+ * Output: c_p * a_p per channel where a_p > 1e-3, else c_p; iterations = 0 gives m itself (the bits of
+ * rtr_accum_resolve).  A pixel is valid if its tile holds a sample; pixels outside the region are never taps. */
+typedef struct rtr_denoise_params {
+    int32_t iterations;  /* 0..10 */
+    int32_t feature_spp; /* K >= 1: camera samples averaged per pixel feature */
+    double sigma_l, sigma_n, sigma_a, sigma_z; /* > 0, finite */
+    double reserved[4];  /* must be 0 */
+} rtr_denoise_params;
+
+/* The defaults (measured on scenes 21, 22 and 23: INTEGRATION.md section 4, "Denoising"). */
+void rtr_denoise_defaults(rtr_denoise_params* p);
+
+/* The features of every pixel of the owned tiles inside the region into a HOST buffer, 7 doubles per pixel:
+ * h_feat[((j - y0) * row_stride + (i - x0)) * 7 + c], c = albedo 0..2, normal 3..5, depth 6; other pixels keep the
+ * caller's values.  With or without RTR_ACCUM_MOMENTS; the accumulator keeps the features of the last K it computed
+ * until it is destroyed.  Blocking.  RTR_ERR_INVALID for K < 1, a re-uploaded scene or a handle of another context. */
+int rtr_accum_features(rtr_context* ctx, rtr_accum* acc, int32_t feature_spp, double* h_feat, int64_t row_stride);
+
+/* The denoised image of the accumulator's samples so far (features of params->feature_spp samples, computed unless
+ * cached), in the layouts of rtr_accum_resolve; either output may be NULL, not both.  Pixels of tiles holding no sample
+ * keep the caller's values.  Sums, moments, counts and tile list are not modified.  Blocking.  RTR_ERR_INVALID without
+ * RTR_ACCUM_MOMENTS, for bad params (NULL params too), a re-uploaded scene or a handle of another context, before any
+ * device work; RTR_ERR_UNSUPPORTED if the accumulator does not own every tile of its region (tile_stride > 1). */
+int rtr_accum_denoise(rtr_context* ctx, rtr_accum* acc, const rtr_denoise_params* params, double* h_linear,
+                      int64_t row_stride, uint8_t* h_rgb8);
+
+/* The same filter over row-major HOST planes of a width x height region (pixel p = row * width + col, row 0 = the lowest
+ * row y0): h_color the linear mean (3 doubles per pixel), h_q the second moments, h_count the sample count of the
+ * pixel's tile (0: not a tap, its outputs keep the caller's values), h_feat the features (7 per pixel).  h_linear gets
+ * 3 doubles per pixel in the same layout, h_rgb8 the 8-bit store with the TOP row first; either may be NULL, not both.
+ * The shards of a tile-sharded render gathered with rtr_accum_resolve / _moments / _tiles / _features give the bits of
+ * the unsharded rtr_accum_denoise.  Needs no scene.  Blocking.  RTR_ERR_INVALID for bad params or sizes. */
+int rtr_denoise_host(rtr_context* ctx, const rtr_denoise_params* params, int32_t width, int32_t height,
+                     const double* h_color, const double* h_q, const int32_t* h_count, const double* h_feat,
+                     double* h_linear, uint8_t* h_rgb8);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

@@ -97,6 +97,17 @@ class RenderStatsC(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class DenoiseParamsC(C.Structure):
+    """rtr_denoise_params (include/rtr_hip.h): the a-trous denoiser of rtr_accum_denoise / rtr_denoise_host"""
+    _fields_ = [("iterations", C.c_int32), ("feature_spp", C.c_int32), ("sigma_l", C.c_double),
+                ("sigma_n", C.c_double), ("sigma_a", C.c_double), ("sigma_z", C.c_double), ("reserved", C.c_double * 4)]
+
+
+DENOISE_PARAMS_SIZE = 72
+assert C.sizeof(DenoiseParamsC) == DENOISE_PARAMS_SIZE
+FEATURES = 7  # doubles per pixel of rtr_accum_features: albedo 3, normal 3, depth 1
+
+
 def make_params(width, height, spp, *, integrator=INTEGRATOR_MIS, seed=1, max_depth=50, rr_start_depth=3,
                 region=None, pipeline=PIPELINE_AUTO, tile_first=0, tile_stride=1, spp_chunks=1, flags=0):
     """Build an ``rtr_render_params``.  Defaults follow the reference driver (main.cpp:102,

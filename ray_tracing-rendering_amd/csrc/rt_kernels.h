@@ -14,6 +14,8 @@
  *              finished, and turn sums + per-tile sample counts into linear mean radiance and the 8-bit store.
  *  k_accum_errors / k_accum_plan   adaptive sampling: per-tile noise estimates from sums + second moments, and the
  *              per-tile targets and active-tile list of the next pass, on the device.
+ *  k_features  first-hit albedo / normal / depth of a pixel's first K camera samples (rtr_accum_features).
+ *  k_denoise_gather / _prep / _pass / _out   the a-trous denoiser (rtr_accum_denoise, rtr_denoise_host).
  */
 #pragma once
 
@@ -535,6 +537,50 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_li(const DScene sc, const RenderK
     out[k] = o;
 }
 
+/* rtr_accum_features: first-hit feature buffers, one workgroup per owned tile and one lane per pixel.  Samples s = 0 .. K-1
+ * of pixel (i, j) build the camera ray of k_li (the ray sample s of a render builds) and cast it to its closest hit with
+ * the render's traversal; the generator goes on from its state after get_ray, so a medium's free path is the path's own.
+ * Per sample: albedo (3), normal (3), depth (1) -- include/rtr_hip.h -- summed in sample order and scaled by 1.0 / K
+ * like k_resolve.  feat: [n_tiles][7][RTR_BLOCK]. */
+#define RTR_FEAT 7
+template <int TRAV>
+__global__ void __launch_bounds__(RTR_BLOCK) k_features(const DScene sc, const RenderK P, int K, double* __restrict__ feat) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    int i, j;
+    bool active;
+    tile_pixel(P, blockIdx.x, threadIdx.x, i, j, active);
+    if (!active) return;
+    double acc[RTR_FEAT];
+    for (int s = 0; s < K; ++s) {
+        uint32_t rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
+        const Real u = (i + rng_next(rng)) / (P.W - 1);
+        const Real v = (j + rng_next(rng)) / (P.H - 1);
+        V3 ro, rd;
+        Real tm;
+        camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+        Hit rec;
+        rec.u = 0, rec.v = 0;
+        double f[RTR_FEAT] = {1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0}; /* a miss */
+        if (cast_closest<TRAV>(sc, ro, rd, tm, rec, rng, st)) {
+            const FMat m = ld_const(sc.fmat, rec.mat);
+            V3 a = mk(1.0, 1.0, 1.0);
+            if (m.type == RTR_MAT_LAMBERTIAN || m.type == RTR_MAT_ISOTROPIC || m.type == RTR_MAT_PBR)
+                a = tex_value(sc, m.tex[0], rec.u, rec.v, rec.p);
+            else if (m.type == RTR_MAT_METAL)
+                a = mk(m.f[0], m.f[1], m.f[2]);
+            f[0] = a.x, f[1] = a.y, f[2] = a.z;
+            if (m.type != RTR_MAT_ISOTROPIC) /* the phase material of a medium event: no normal */
+                f[3] = rec.n.x, f[4] = rec.n.y, f[5] = rec.n.z;
+            f[6] = rec.t * __builtin_sqrt(rd.x * rd.x + rd.y * rd.y + rd.z * rd.z);
+        }
+        for (int c = 0; c < RTR_FEAT; ++c) acc[c] = s == 0 ? f[c] : acc[c] + f[c];
+    }
+    const double scale = 1.0 / K;
+    double* o = feat + (size_t)blockIdx.x * RTR_FEAT * RTR_BLOCK + threadIdx.x;
+    for (int c = 0; c < RTR_FEAT; ++c) o[c * RTR_BLOCK] = scale * acc[c];
+}
+
 #ifdef RTR_TU_CAPI /* non-template kernels live in one translation unit */
 __global__ void __launch_bounds__(RTR_BLOCK) k_resolve(const ResolveK R) {
     const RenderK& P = R.r;
@@ -686,6 +732,224 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_accum_resolve(const AccumResolveK
             double g = __builtin_sqrt(v[c]); /* correctly rounded, like std::sqrt */
             g = g < 0.0 ? 0.0 : (g > 1.0 ? 1.0 : g); /* clamp (rtweekend.h): NaN passes through */
             R.rgb8[o + c] = static_cast<unsigned char>(g * 255);
+        }
+}
+
+/* ---- rtr_accum_denoise / rtr_denoise_host: edge-avoiding a-trous filter (include/rtr_hip.h) ----
+ * Every plane is row-major over the w x h region, pixel p = y * w + x (y = j - y0).  Inputs (AoS, the layout of the host
+ * entry point): m [p][3] mean radiance, q [p] second moments, n [p] sample count (0 = not a tap, left alone), feat [p][7].
+ * Working planes (SoA): c[b] [3][np] colour and v[b] [np] variance of ping-pong buffer b, a / nrm [3][np], z [np].
+ * Only + - * / sqrt and compares: a numpy restatement gives the same bits. */
+struct DenoiseK {
+    int w, h, iterations;
+    double sl2, sn2, sa2, sz2; /* sigma * sigma */
+    double* m;
+    double* q;
+    int* n;
+    double* feat;
+    double* c[2];
+    double* v[2];
+    double* a;
+    double* nrm;
+    double* z;
+    double* out;         /* null or [p][3] */
+    unsigned char* rgb8; /* null or [p][3], Y flipped: region row h - 1 - y */
+};
+
+/* the accumulator's packed tiles -> the input planes; every pixel of the region is in an owned tile (tile_stride <= 1) */
+__global__ void __launch_bounds__(RTR_BLOCK) k_denoise_gather(const AccumResolveK R, const double* __restrict__ q,
+                                                              const double* __restrict__ feat, const DenoiseK D) {
+    int i, j;
+    bool active;
+    tile_pixel(R.r, blockIdx.x, threadIdx.x, i, j, active);
+    if (!active) return;
+    const size_t p = (size_t)(j - R.r.y0) * D.w + (i - R.r.x0);
+    const int n = R.count[blockIdx.x];
+    D.n[p] = n;
+    const size_t in = (size_t)blockIdx.x * 3 * RTR_BLOCK + threadIdx.x;
+    const double* f = feat + (size_t)blockIdx.x * RTR_FEAT * RTR_BLOCK + threadIdx.x;
+    double* fo = D.feat + p * RTR_FEAT;
+    for (int c = 0; c < RTR_FEAT; ++c) fo[c] = f[c * RTR_BLOCK];
+    if (n == 0) return;
+    const double scale = 1.0 / n; /* the mean of k_accum_resolve */
+    double* mo = D.m + p * 3;
+    mo[0] = scale * R.sum[in], mo[1] = scale * R.sum[in + RTR_BLOCK], mo[2] = scale * R.sum[in + 2 * RTR_BLOCK];
+    D.q[p] = q[(size_t)blockIdx.x * RTR_BLOCK + threadIdx.x];
+}
+
+/* the variance of the mean and demodulation by the albedo -> c[0], v[0]; the features -> a, nrm, z */
+__global__ void __launch_bounds__(RTR_BLOCK) k_denoise_prep(const DenoiseK D) {
+    const long long np = (long long)D.w * D.h, p = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (p >= np) return;
+    const int n = D.n[p];
+    if (n == 0) return;
+    const double* f = D.feat + p * RTR_FEAT;
+    const V3 a = mk(f[0], f[1], f[2]);
+    const V3 m = mk(D.m[3 * p], D.m[3 * p + 1], D.m[3 * p + 2]);
+    double var = 1e30;
+    if (n >= 2) {
+        const double scale = 1.0 / n, ym = luminance(m);
+        const double d = scale * D.q[p] - ym * ym;
+        var = (d > 0.0 ? d : 0.0) / (double)(n - 1) / (double)n;
+    }
+    double la = luminance(a);
+    la = la > 1e-3 ? la : 1e-3;
+    D.v[0][p] = var / (la * la);
+    D.c[0][p] = a.x > 1e-3 ? m.x / a.x : m.x;
+    D.c[0][p + np] = a.y > 1e-3 ? m.y / a.y : m.y;
+    D.c[0][p + 2 * np] = a.z > 1e-3 ? m.z / a.z : m.z;
+    for (int c = 0; c < 3; ++c) D.a[p + c * np] = f[c], D.nrm[p + c * np] = f[3 + c];
+    D.z[p] = f[6];
+}
+
+/* one a-trous pass with step 2^k: 16 x 16 pixels per workgroup, buffer src -> src ^ 1 */
+__global__ void __launch_bounds__(RTR_BLOCK) k_denoise_pass(const DenoiseK D, int step, int src) {
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= D.w || y >= D.h) return;
+    const long long np = (long long)D.w * D.h, p = (long long)y * D.w + x;
+    if (D.n[p] == 0) return;
+    const double* __restrict__ c = D.c[src];
+    const double* __restrict__ v = D.v[src];
+    /* variance prefilter: 3 x 3 binomial average over the valid neighbours */
+    const double k3[3] = {0.25, 0.5, 0.25};
+    double gs = 0.0, gw = 0.0;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= D.w || qy < 0 || qy >= D.h) continue;
+            const long long q = (long long)qy * D.w + qx;
+            if (D.n[q] == 0) continue;
+            const double wk = k3[dx + 1] * k3[dy + 1];
+            gs += wk * v[q];
+            gw += wk;
+        }
+    const double g = gs / gw;
+    const double h5[5] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
+    const double c0 = c[p], c1 = c[p + np], c2 = c[p + 2 * np];
+    const double lp = 0.2126 * c0 + 0.7152 * c1 + 0.0722 * c2;
+    const double n0 = D.nrm[p], n1 = D.nrm[p + np], n2 = D.nrm[p + 2 * np];
+    const double a0 = D.a[p], a1 = D.a[p + np], a2 = D.a[p + 2 * np];
+    const double zp = D.z[p], zz = zp > 1e-3 ? zp : 1e-3;
+    const double l_den = D.sl2 * g + 1e-10, z_den = D.sz2 * ((double)step * (double)step) * (zz * zz);
+    double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, sv = 0.0;
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + step * dy;
+        if (qy < 0 || qy >= D.h) continue;
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + step * dx;
+            if (qx < 0 || qx >= D.w) continue;
+            const long long q = (long long)qy * D.w + qx;
+            if (D.n[q] == 0) continue;
+            const double q0 = c[q], q1 = c[q + np], q2 = c[q + 2 * np];
+            const double dl = lp - (0.2126 * q0 + 0.7152 * q1 + 0.0722 * q2);
+            const double wl = 1.0 / (1.0 + dl * dl / l_den);
+            const double e0 = n0 - D.nrm[q], e1 = n1 - D.nrm[q + np], e2 = n2 - D.nrm[q + 2 * np];
+            const double wn = 1.0 / (1.0 + (e0 * e0 + e1 * e1 + e2 * e2) / D.sn2);
+            const double f0 = a0 - D.a[q], f1 = a1 - D.a[q + np], f2 = a2 - D.a[q + 2 * np];
+            const double wa = 1.0 / (1.0 + (f0 * f0 + f1 * f1 + f2 * f2) / D.sa2);
+            const double ez = zp - D.z[q];
+            const double wz = 1.0 / (1.0 + ez * ez / z_den);
+            const double wt = h5[dx + 2] * h5[dy + 2] * wl * wn * wa * wz;
+            sw += wt;
+            s0 += wt * q0, s1 += wt * q1, s2 += wt * q2;
+            sv += wt * wt * v[q];
+        }
+    }
+    double* co = D.c[src ^ 1];
+    co[p] = s0 / sw, co[p + np] = s1 / sw, co[p + 2 * np] = s2 / sw;
+    D.v[src ^ 1][p] = sv / (sw * sw);
+}
+
+/* k_denoise_pass for the small steps 1 and 2: the workgroup first stages its 16 x 16 pixels and a halo of 2 * STEP
+ * (which holds the prefilter's 1-pixel halo) in LDS -- 20 x 20 or 24 x 24 pixels, 11 doubles and a validity flag each,
+ * 37 / 53 KiB -- and then runs the arithmetic of k_denoise_pass, in its order, on the staged values: the same bits */
+template <int STEP>
+__global__ void __launch_bounds__(RTR_BLOCK) k_denoise_pass_lds(const DenoiseK D, int src) {
+    constexpr int R = 2 * STEP, S = 16 + 2 * R, N = S * S;
+    __shared__ double lc[3][N], lv[N], la[3][N], ln[3][N], lz[N];
+    __shared__ int lok[N];
+    const long long np = (long long)D.w * D.h;
+    const int bx = blockIdx.x * 16 - R, by = blockIdx.y * 16 - R;
+    const double* __restrict__ c = D.c[src];
+    for (int k = threadIdx.x; k < N; k += RTR_BLOCK) {
+        const int gx = bx + k % S, gy = by + k / S;
+        const long long q = (long long)gy * D.w + gx;
+        const bool ok = gx >= 0 && gx < D.w && gy >= 0 && gy < D.h && D.n[q] != 0;
+        lok[k] = ok;
+        if (ok) {
+            for (int ch = 0; ch < 3; ++ch)
+                lc[ch][k] = c[q + ch * np], la[ch][k] = D.a[q + ch * np], ln[ch][k] = D.nrm[q + ch * np];
+            lv[k] = D.v[src][q], lz[k] = D.z[q];
+        }
+    }
+    __syncthreads();
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int x = blockIdx.x * 16 + tx, y = blockIdx.y * 16 + ty;
+    const int l = (ty + R) * S + tx + R;
+    if (x >= D.w || y >= D.h || !lok[l]) return;
+    const long long p = (long long)y * D.w + x;
+    const double k3[3] = {0.25, 0.5, 0.25};
+    double gs = 0.0, gw = 0.0;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int m = l + dy * S + dx;
+            if (!lok[m]) continue;
+            const double wk = k3[dx + 1] * k3[dy + 1];
+            gs += wk * lv[m];
+            gw += wk;
+        }
+    const double g = gs / gw;
+    const double h5[5] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
+    const double c0 = lc[0][l], c1 = lc[1][l], c2 = lc[2][l];
+    const double lp = 0.2126 * c0 + 0.7152 * c1 + 0.0722 * c2;
+    const double n0 = ln[0][l], n1 = ln[1][l], n2 = ln[2][l];
+    const double a0 = la[0][l], a1 = la[1][l], a2 = la[2][l];
+    const double zp = lz[l], zz = zp > 1e-3 ? zp : 1e-3;
+    const double l_den = D.sl2 * g + 1e-10, z_den = D.sz2 * ((double)STEP * (double)STEP) * (zz * zz);
+    double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, sv = 0.0;
+    for (int dy = -2; dy <= 2; ++dy)
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int m = l + STEP * (dy * S + dx);
+            if (!lok[m]) continue;
+            const double q0 = lc[0][m], q1 = lc[1][m], q2 = lc[2][m];
+            const double dl = lp - (0.2126 * q0 + 0.7152 * q1 + 0.0722 * q2);
+            const double wl = 1.0 / (1.0 + dl * dl / l_den);
+            const double e0 = n0 - ln[0][m], e1 = n1 - ln[1][m], e2 = n2 - ln[2][m];
+            const double wn = 1.0 / (1.0 + (e0 * e0 + e1 * e1 + e2 * e2) / D.sn2);
+            const double f0 = a0 - la[0][m], f1 = a1 - la[1][m], f2 = a2 - la[2][m];
+            const double wa = 1.0 / (1.0 + (f0 * f0 + f1 * f1 + f2 * f2) / D.sa2);
+            const double ez = zp - lz[m];
+            const double wz = 1.0 / (1.0 + ez * ez / z_den);
+            const double wt = h5[dx + 2] * h5[dy + 2] * wl * wn * wa * wz;
+            sw += wt;
+            s0 += wt * q0, s1 += wt * q1, s2 += wt * q2;
+            sv += wt * wt * lv[m];
+        }
+    double* co = D.c[src ^ 1];
+    co[p] = s0 / sw, co[p + np] = s1 / sw, co[p + 2 * np] = s2 / sw;
+    D.v[src ^ 1][p] = sv / (sw * sw);
+}
+
+/* remodulate (iterations = 0: the mean itself, the bits of k_accum_resolve) and store linear and / or 8-bit */
+__global__ void __launch_bounds__(RTR_BLOCK) k_denoise_out(const DenoiseK D, int src) {
+    const long long np = (long long)D.w * D.h, p = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (p >= np || D.n[p] == 0) return;
+    const int x = (int)(p % D.w), y = (int)(p / D.w);
+    double o[3];
+    for (int c = 0; c < 3; ++c) {
+        if (D.iterations == 0) {
+            o[c] = D.m[3 * p + c];
+        } else {
+            const double a = D.a[p + c * np], v = D.c[src][p + c * np];
+            o[c] = a > 1e-3 ? v * a : v;
+        }
+    }
+    if (D.out) D.out[3 * p] = o[0], D.out[3 * p + 1] = o[1], D.out[3 * p + 2] = o[2];
+    if (D.rgb8)
+        for (int c = 0; c < 3; ++c) { /* the store of k_accum_resolve */
+            double g = __builtin_sqrt(o[c]);
+            g = g < 0.0 ? 0.0 : (g > 1.0 ? 1.0 : g);
+            D.rgb8[((size_t)(D.h - 1 - y) * D.w + x) * 3 + c] = static_cast<unsigned char>(g * 255);
         }
 }
 

@@ -53,6 +53,7 @@ struct rtr_context {
     int n_material_types = 0;
     /* per-render workspace */
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
+    DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
     std::vector<int> last_tiles; /* what b_tiles holds */
     WavefrontPool pool;
     void* h_stage = nullptr; /* pinned: rtr_render_tiles_host */
@@ -93,6 +94,8 @@ struct rtr_accum {
     mutable std::vector<int> h_counts; /* host copy of d_count ... */
     mutable bool counts_stale = false; /* ... unless a pass was queued since it was read */
     DevBuf d_out; /* rtr_accum_resolve staging: [n][RTR_BLOCK][3] doubles, then [n][RTR_BLOCK][3] bytes */
+    DevBuf d_feat; /* rtr_accum_features: [n][RTR_FEAT][RTR_BLOCK] doubles of feat_k samples (0: none yet) */
+    int feat_k = 0;
     void* h_out = nullptr; /* pinned, same layout */
     size_t h_out_cap = 0;
 };
@@ -645,7 +648,8 @@ int finish_stats(rtr_context* c) {
 } // namespace
 
 static void free_accum(rtr_accum* a) {
-    DevBuf* bufs[] = {&a->d_tiles, &a->d_sum, &a->d_count, &a->d_out, &a->d_q, &a->d_qpart, &a->d_s1, &a->d_active, &a->d_nactive, &a->d_err};
+    DevBuf* bufs[] = {&a->d_tiles, &a->d_sum, &a->d_count, &a->d_out, &a->d_q, &a->d_qpart, &a->d_s1, &a->d_active, &a->d_nactive, &a->d_err,
+                      &a->d_feat};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (a->h_out) hipHostFree(a->h_out);
@@ -743,7 +747,7 @@ void rtr_destroy(rtr_context* c) {
     for (rtr_accum* a : c->accums) free_accum(a);
     c->accums.clear();
     DevBuf* bufs[] = {&c->b_nodes, &c->b_kids,  &c->b_mats,    &c->b_tex,   &c->b_perlin, &c->b_images, &c->b_imgbytes,
-                      &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage,
+                      &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise,
                       &c->b_finst, &c->b_fxf, &c->b_fref, &c->b_fexit, &c->b_fbvh, &c->b_dscene, &c->b_fprim, &c->b_fsub, &c->b_fstep, &c->b_fvisit, &c->b_fscan, &c->b_fleaf, &c->b_fmat, &c->b_fguard};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
@@ -1542,6 +1546,211 @@ int rtr_accum_errors(rtr_context* c, rtr_accum* a, double* tile_err, int64_t cap
     if (tile_err && m) HIPCHK(c, hipMemcpyAsync(tile_err, a->d_err.p, m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTR_OK;
+}
+
+} // extern "C"
+
+/* ---- first-hit features and the a-trous denoiser ------------------------------------------------------------------ */
+namespace {
+
+/* the defaults of rtr_denoise_defaults: the sweep of INTEGRATION.md section 4, "Denoising" */
+constexpr rtr_denoise_params kDenoiseDefaults = {4, 8, 16.0, 0.2, 0.3, 1.0, {0.0, 0.0, 0.0, 0.0}};
+
+int denoise_check(rtr_context* c, const rtr_denoise_params* p) {
+    if (!p) return fail(c, RTR_ERR_INVALID, "null denoise params");
+    if (p->iterations < 0 || p->iterations > 10) return fail(c, RTR_ERR_INVALID, "iterations must be in 0..10");
+    if (p->feature_spp < 1) return fail(c, RTR_ERR_INVALID, "feature_spp must be >= 1");
+    for (double s : {p->sigma_l, p->sigma_n, p->sigma_a, p->sigma_z})
+        if (!(s > 0.0) || !std::isfinite(s)) return fail(c, RTR_ERR_INVALID, "the sigmas must be finite and > 0");
+    for (double r : p->reserved)
+        if (r != 0.0) return fail(c, RTR_ERR_INVALID, "reserved fields must be 0");
+    return RTR_OK;
+}
+
+/* the features of K samples per pixel of every owned tile in a->d_feat, unless they are there already */
+int accum_features(rtr_context* c, rtr_accum* a, int K) {
+    const size_t n = a->tiles.size();
+    if (a->feat_k == K || n == 0) return RTR_OK;
+    a->feat_k = 0;
+    if (int rc = ensure(c, a->d_feat, n * RTR_FEAT * RTR_BLOCK * sizeof(double))) return rc;
+    RenderK P = accum_view(a).r;
+    P.seed = a->params.seed;
+    double* feat = static_cast<double*>(a->d_feat.p);
+    int trav = pick_trav(c, a->params.flags);
+    if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST; /* the traversals of k_li: same hits */
+    const size_t lds = stack_bytes(c, trav);
+    int rc = RTR_OK;
+#define RTR_LAUNCH(T)                                                                                         \
+    do {                                                                                                      \
+        if ((rc = set_lds(c, k_features<T>, lds))) return rc;                                                 \
+        hipLaunchKernelGGL((k_features<T>), dim3((unsigned)n), dim3(RTR_BLOCK), lds, c->stream, c->ds, P, K, feat); \
+    } while (0)
+    if (trav == RT_TRAV_FAST)
+        RTR_LAUNCH(RT_TRAV_FAST);
+    else if (trav == RT_TRAV_PROGRAM)
+        RTR_LAUNCH(RT_TRAV_PROGRAM_EXT);
+    else if (trav == RT_TRAV_MEDIA)
+        RTR_LAUNCH(RT_TRAV_MEDIA);
+    else
+        RTR_LAUNCH(RT_TRAV_EXACT);
+#undef RTR_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    a->feat_k = K;
+    return RTR_OK;
+}
+
+/* the planes of a w x h region in c->b_denoise */
+int denoise_planes(rtr_context* c, int w, int h, const rtr_denoise_params* prm, DenoiseK& D) {
+    const size_t np = (size_t)w * h;
+    /* doubles: m 3, q 1, feat 7, c 3 + 3, v 1 + 1, a 3, nrm 3, z 1, out 3; then n (int) and rgb8 (3 bytes) */
+    const size_t n_doubles = 29 * np;
+    if (int rc = ensure(c, c->b_denoise, n_doubles * sizeof(double) + np * sizeof(int) + 3 * np)) return rc;
+    double* d = static_cast<double*>(c->b_denoise.p);
+    D = DenoiseK{};
+    D.w = w, D.h = h, D.iterations = prm->iterations;
+    D.sl2 = prm->sigma_l * prm->sigma_l, D.sn2 = prm->sigma_n * prm->sigma_n;
+    D.sa2 = prm->sigma_a * prm->sigma_a, D.sz2 = prm->sigma_z * prm->sigma_z;
+    D.m = d, d += 3 * np;
+    D.q = d, d += np;
+    D.feat = d, d += RTR_FEAT * np;
+    D.c[0] = d, d += 3 * np;
+    D.c[1] = d, d += 3 * np;
+    D.v[0] = d, d += np;
+    D.v[1] = d, d += np;
+    D.a = d, d += 3 * np;
+    D.nrm = d, d += 3 * np;
+    D.z = d, d += np;
+    D.out = d, d += 3 * np;
+    D.n = reinterpret_cast<int*>(d);
+    D.rgb8 = reinterpret_cast<unsigned char*>(D.n + np);
+    return RTR_OK;
+}
+
+/* prep, the passes and the output on the filled input planes; then the valid pixels into the caller's buffers (linear:
+ * row r at h_linear + r * row_stride * 3; 8-bit: rows of w pixels, the top row first) */
+int denoise_run(rtr_context* c, DenoiseK D, double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
+    const size_t np = (size_t)D.w * D.h;
+    const dim3 grid1((unsigned)((np + RTR_BLOCK - 1) / RTR_BLOCK)), grid2((unsigned)((D.w + 15) / 16), (unsigned)((D.h + 15) / 16));
+    if (!h_linear) D.out = nullptr;
+    if (!h_rgb8) D.rgb8 = nullptr;
+    hipLaunchKernelGGL(k_denoise_prep, grid1, dim3(RTR_BLOCK), 0, c->stream, D);
+    int src = 0;
+    /* steps 1 and 2 from LDS unless RTR_DENOISE_LDS=0 (A/B measurement: INTEGRATION.md section 4, "Denoising") */
+    const char* lds_env = getenv("RTR_DENOISE_LDS");
+    const bool lds = !(lds_env && lds_env[0] == '0');
+    for (int k = 0; k < D.iterations; ++k, src ^= 1) {
+        if (lds && k == 0)
+            hipLaunchKernelGGL(k_denoise_pass_lds<1>, grid2, dim3(RTR_BLOCK), 0, c->stream, D, src);
+        else if (lds && k == 1)
+            hipLaunchKernelGGL(k_denoise_pass_lds<2>, grid2, dim3(RTR_BLOCK), 0, c->stream, D, src);
+        else
+            hipLaunchKernelGGL(k_denoise_pass, grid2, dim3(RTR_BLOCK), 0, c->stream, D, 1 << k, src);
+    }
+    hipLaunchKernelGGL(k_denoise_out, grid1, dim3(RTR_BLOCK), 0, c->stream, D, src);
+    HIPCHK(c, hipGetLastError());
+    std::vector<int> n(np);
+    std::vector<double> lin(h_linear ? 3 * np : 0);
+    std::vector<unsigned char> rgb(h_rgb8 ? 3 * np : 0);
+    HIPCHK(c, hipMemcpyAsync(n.data(), D.n, np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (h_linear) HIPCHK(c, hipMemcpyAsync(lin.data(), D.out, 3 * np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_rgb8) HIPCHK(c, hipMemcpyAsync(rgb.data(), D.rgb8, 3 * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int y = 0; y < D.h; ++y)
+        for (int x = 0; x < D.w; ++x) {
+            const size_t p = (size_t)y * D.w + x;
+            if (n[p] == 0) continue;
+            if (h_linear) std::memcpy(h_linear + ((size_t)y * (size_t)row_stride + x) * 3, &lin[3 * p], 3 * sizeof(double));
+            if (h_rgb8) {
+                const size_t o = ((size_t)(D.h - 1 - y) * D.w + x) * 3;
+                h_rgb8[o] = rgb[o], h_rgb8[o + 1] = rgb[o + 1], h_rgb8[o + 2] = rgb[o + 2];
+            }
+        }
+    return RTR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void rtr_denoise_defaults(rtr_denoise_params* p) {
+    if (p) *p = kDenoiseDefaults;
+}
+
+int rtr_accum_features(rtr_context* c, rtr_accum* a, int32_t feature_spp, double* h_feat, int64_t row_stride) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_render_check(c, a)) return rc;
+    if (feature_spp < 1) return fail(c, RTR_ERR_INVALID, "feature_spp must be >= 1");
+    const rtr_render_params& p = a->params;
+    if (!h_feat || row_stride < (int64_t)(p.x1 - p.x0)) return fail(c, RTR_ERR_INVALID, "bad output buffer / stride");
+    const size_t n = a->tiles.size();
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = accum_features(c, a, feature_spp)) return rc;
+    const size_t bytes = n * RTR_FEAT * RTR_BLOCK * sizeof(double);
+    if (int rc = staging(c, a, bytes)) return rc;
+    HIPCHK(c, hipMemcpyAsync(a->h_out, a->d_feat.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double* f = static_cast<const double*>(a->h_out);
+    for (size_t k = 0; k < n; ++k) { /* every owned tile, with or without samples */
+        const int t = a->tiles[k];
+        const int tx0 = (t % a->tiles_x) * 16, ty0 = ((a->tiles_y - 1) - t / a->tiles_x) * 16;
+        for (int r = 0; r < 16; ++r) {
+            const int j = ty0 + r;
+            if (j < p.y0 || j >= p.y1) continue;
+            for (int i = std::max(tx0, p.x0); i < std::min(tx0 + 16, p.x1); ++i)
+                for (int ch = 0; ch < RTR_FEAT; ++ch)
+                    h_feat[((size_t)(j - p.y0) * (size_t)row_stride + (size_t)(i - p.x0)) * RTR_FEAT + ch] =
+                        f[(k * RTR_FEAT + ch) * RTR_BLOCK + (size_t)r * 16 + (size_t)(i - tx0)];
+        }
+    }
+    return RTR_OK;
+}
+
+int rtr_accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, double* h_linear, int64_t row_stride,
+                      uint8_t* h_rgb8) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_render_check(c, a)) return rc;
+    if (int rc = denoise_check(c, prm)) return rc;
+    if (!a->moments) return fail(c, RTR_ERR_INVALID, "the accumulator keeps no moments (RTR_ACCUM_MOMENTS)");
+    const rtr_render_params& p = a->params;
+    const int w = p.x1 - p.x0, h = p.y1 - p.y0;
+    if (!h_linear && !h_rgb8) return fail(c, RTR_ERR_INVALID, "no output buffer");
+    if (h_linear && row_stride < (int64_t)w) return fail(c, RTR_ERR_INVALID, "bad output stride");
+    if (p.tile_stride > 1)
+        return fail(c, RTR_ERR_UNSUPPORTED, "a tile-sharded accumulator: gather the shards and call rtr_denoise_host");
+    const size_t n = a->tiles.size();
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refresh_counts(c, a)) return rc;
+    if (int rc = accum_features(c, a, prm->feature_spp)) return rc;
+    DenoiseK D;
+    if (int rc = denoise_planes(c, w, h, prm, D)) return rc;
+    hipLaunchKernelGGL(k_denoise_gather, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, accum_view(a),
+                       static_cast<const double*>(a->d_q.p), static_cast<const double*>(a->d_feat.p), D);
+    HIPCHK(c, hipGetLastError());
+    return denoise_run(c, D, h_linear, row_stride, h_rgb8);
+}
+
+int rtr_denoise_host(rtr_context* c, const rtr_denoise_params* prm, int32_t width, int32_t height, const double* h_color,
+                     const double* h_q, const int32_t* h_count, const double* h_feat, double* h_linear, uint8_t* h_rgb8) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = denoise_check(c, prm)) return rc;
+    if (width < 1 || height < 1 || (int64_t)width * height > ((int64_t)1 << 28))
+        return fail(c, RTR_ERR_INVALID, "region size out of range");
+    if (!h_color || !h_q || !h_count || !h_feat) return fail(c, RTR_ERR_INVALID, "null input plane");
+    if (!h_linear && !h_rgb8) return fail(c, RTR_ERR_INVALID, "no output buffer");
+    const size_t np = (size_t)width * height;
+    for (size_t p = 0; p < np; ++p)
+        if (h_count[p] < 0) return fail(c, RTR_ERR_INVALID, "negative sample count");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    DenoiseK D;
+    if (int rc = denoise_planes(c, width, height, prm, D)) return rc;
+    HIPCHK(c, hipMemcpy(D.m, h_color, 3 * np * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(D.q, h_q, np * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(D.n, h_count, np * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(D.feat, h_feat, RTR_FEAT * np * sizeof(double), hipMemcpyHostToDevice));
+    return denoise_run(c, D, h_linear, width, h_rgb8);
 }
 
 void rtr_accum_destroy(rtr_accum* a) {

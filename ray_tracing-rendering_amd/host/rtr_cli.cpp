@@ -11,6 +11,9 @@
  *           [--adaptive THRESH [--spp-min N]]   adaptive: Renderer::render_adaptive with error threshold THRESH (a number
  *                                   or a fraction such as 1/255), spp_min N (default min(16, spp_max)) and --spp as spp_max;
  *                                   time, tiles refined and samples per pass, and the total samples against W*H*spp_max
+ *           [--denoise [ITER]]   with --passes, --adaptive or a plain --spp (then one accumulator pass): the image after the
+ *                                   last pass is denoised (include/rtr_hip.h: rtr_accum_denoise, the library's defaults;
+ *                                   ITER in 0..10 replaces their iteration count); prints the denoise time
  */
 #include "rtr_renderer.h"
 
@@ -34,7 +37,8 @@ static bool parse_threshold(const char* s, double& out) {
 
 int main(int argc, char** argv) {
     int scene_id = 21, integrator_id = 4, width = 0, spp = 0, bands = 0, repeat = 1, spp_min = 0;
-    bool adaptive = false;
+    bool adaptive = false, denoise = false;
+    int denoise_iter = -1;
     double threshold = 0.0;
     std::vector<int> devices{0}, passes;
     unsigned seed = 1;
@@ -52,6 +56,18 @@ int main(int argc, char** argv) {
             if (!parse_threshold(argv[++k], threshold) || !(threshold > 0.0) || !std::isfinite(threshold)) {
                 std::cerr << "--adaptive: the threshold must be a finite number > 0, not " << argv[k] << "\n";
                 return 2;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--denoise")) {
+            denoise = true;
+            if (k + 1 < argc && std::strncmp(argv[k + 1], "--", 2) != 0) {
+                char* end = nullptr;
+                const long v = std::strtol(argv[++k], &end, 10);
+                if (end == argv[k] || *end != '\0' || v < 0 || v > 10) {
+                    std::cerr << "--denoise: ITER must be an integer in 0..10, not " << argv[k] << "\n";
+                    return 2;
+                }
+                denoise_iter = (int)v;
             }
         }
         else if (!std::strcmp(argv[k], "--spp-min") && k + 1 < argc) {
@@ -97,6 +113,13 @@ int main(int argc, char** argv) {
         std::cerr << "--adaptive: --spp (the maximum) must be >= --spp-min\n";
         return 2;
     }
+    if (denoise && repeat != 1) {
+        std::cerr << "--denoise takes one render (--repeat 1)\n";
+        return 2;
+    }
+    rtr_denoise_params dn{};
+    rtr_denoise_defaults(&dn);
+    if (denoise_iter >= 0) dn.iterations = denoise_iter;
     rtr::rng_state() = 12345u; /* scene-construction seed */
     SceneConfig config;
     try {
@@ -140,21 +163,25 @@ int main(int argc, char** argv) {
                           << " ms, " << active << " tiles refined, " << samples << " samples\n";
                 t = now;
                 total = samples;
-            });
+            }, denoise ? &dn : nullptr);
             const double uniform = (double)W * H * config.samples_per_pixel;
             std::cout << "adaptive total: " << total << " samples of " << (long long)uniform << " (W*H*spp_max), "
                       << 100.0 * (double)total / uniform << " %\n";
-        } else if (passes.empty()) {
+        } else if (passes.empty() && !denoise) {
             renderer.render(config.world, cam, config.background, buffer, config.lights);
         } else {
+            if (passes.empty()) passes.push_back(config.samples_per_pixel); /* --denoise: one accumulator pass */
             auto t = std::chrono::high_resolution_clock::now();
             renderer.render_progressive(config.world, cam, config.background, buffer, config.lights, passes, [&](int target) {
                 const auto now = std::chrono::high_resolution_clock::now();
                 std::cout << "pass to " << target << " spp: " << std::chrono::duration<double>(now - t).count() * 1e3 << " ms\n";
                 t = now;
-            });
+            }, denoise ? &dn : nullptr);
         }
         if (renderer.last_status() != RTR_OK) return 1;
+        if (denoise)
+            std::cout << "denoise: " << renderer.last_denoise_seconds() * 1e3 << " ms (" << dn.iterations << " iterations, features of "
+                      << dn.feature_spp << " spp)\n";
     }
     std::cout << "contexts: " << renderer.device_contexts() << "  scene uploads: " << renderer.scene_uploads() << "\n";
     std::cout << "Msamples/s: " << (double)W * H * config.samples_per_pixel / renderer.last_seconds() * 1e-6

@@ -274,6 +274,8 @@ class Renderer {
     int last_status() const { return m_status; }
     const char* last_error() const { return m_error.c_str(); }
     double last_seconds() const { return m_seconds; }
+    /* wall time of the denoise of the last render_progressive / render_adaptive that asked for one (features included) */
+    double last_denoise_seconds() const { return m_denoise_seconds; }
     int device_contexts() const { return (int)m_ctx.size(); }
     /* The flattened scene stays on the GPUs between render() calls with the same world / camera / lights objects
      * and background (the reference's scene graph is immutable once built; the Renderer holds the objects, so an
@@ -304,15 +306,19 @@ class Renderer {
      * `target_buffer`, and then on_pass(target) is called.  The image after target T is the bits of a render with
      * spp = T and one running sum per pixel (spp_chunks = 1); render() (spp_chunks = 0) agrees with it within 1e-13.
      * cancel() stops it between or inside passes: the buffer then holds the last completed target.  Uses the scene cache
-     * of render(). */
+     * of render().  `denoise` (may be NULL): the accumulators keep moments and the last target's image is the denoised
+     * one (include/rtr_hip.h: rtr_accum_denoise; with several contexts their planes are gathered on the host and go
+     * through rtr_denoise_host, which gives the same bits). */
     void render_progressive(shared_ptr<hittable> world, shared_ptr<camera> cam, const color& background,
                             RenderBuffer& target_buffer, const std::vector<shared_ptr<Light>>& lights,
-                            const std::vector<int>& targets, const std::function<void(int)>& on_pass = nullptr) {
+                            const std::vector<int>& targets, const std::function<void(int)>& on_pass = nullptr,
+                            const rtr_denoise_params* denoise = nullptr) {
         m_is_rendering = true;
         const auto t0 = std::chrono::high_resolution_clock::now();
         const bool same_scene = world == m_world && cam == m_cam && lights == m_lights &&
                                 background[0] == m_scene_bg[0] && background[1] == m_scene_bg[1] && background[2] == m_scene_bg[2];
-        m_status = progressive_impl(*world, *cam, background, target_buffer, lights, same_scene && m_scene_valid, targets, on_pass);
+        m_status = progressive_impl(*world, *cam, background, target_buffer, lights, same_scene && m_scene_valid, targets, on_pass,
+                                    denoise);
         if (m_scene_valid) m_world = world, m_cam = cam, m_lights = lights;
         m_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         m_is_rendering = false;
@@ -329,16 +335,18 @@ class Renderer {
      * on_pass(pass from 1, tiles refined, samples rendered so far) is called; it ends when no tile of any context is
      * left to refine.  The decisions are tile-local, so the counts and the image do not depend on the number of
      * contexts; a tile holding T samples is the bits of a render with spp = T and spp_chunks = 1.  cancel() stops it
-     * between or inside passes.  Uses the scene cache of render(). */
+     * between or inside passes.  Uses the scene cache of render().  `denoise` (may be NULL): once no tile is left to
+     * refine, the buffer takes the denoised image (as render_progressive). */
     void render_adaptive(shared_ptr<hittable> world, shared_ptr<camera> cam, const color& background,
                          RenderBuffer& target_buffer, const std::vector<shared_ptr<Light>>& lights, double threshold,
-                         int spp_min, int spp_max, const std::function<void(int, int, long long)>& on_pass = nullptr) {
+                         int spp_min, int spp_max, const std::function<void(int, int, long long)>& on_pass = nullptr,
+                         const rtr_denoise_params* denoise = nullptr) {
         m_is_rendering = true;
         const auto t0 = std::chrono::high_resolution_clock::now();
         const bool same_scene = world == m_world && cam == m_cam && lights == m_lights &&
                                 background[0] == m_scene_bg[0] && background[1] == m_scene_bg[1] && background[2] == m_scene_bg[2];
         m_status = adaptive_impl(*world, *cam, background, target_buffer, lights, same_scene && m_scene_valid, threshold,
-                                 spp_min, spp_max, on_pass);
+                                 spp_min, spp_max, on_pass, denoise);
         if (m_scene_valid) m_world = world, m_cam = cam, m_lights = lights;
         m_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         m_is_rendering = false;
@@ -387,7 +395,7 @@ class Renderer {
 
     int progressive_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,
                          const std::vector<shared_ptr<Light>>& lights, bool scene_on_device, const std::vector<int>& targets,
-                         const std::function<void(int)>& on_pass) {
+                         const std::function<void(int)>& on_pass, const rtr_denoise_params* denoise) {
         for (size_t t = 0; t < targets.size(); ++t)
             if (targets[t] < 1 || (t && targets[t] <= targets[t - 1])) return m_error = "targets must increase from 1 on", RTR_ERR_INVALID;
         if (int rc = prepare(world, cam, background, lights, scene_on_device)) return rc;
@@ -403,7 +411,8 @@ class Renderer {
         for (int k = 0; k < n; ++k) {
             rtr_render_params q = p;
             q.tile_first = k, q.tile_stride = n;
-            if (int rc = rtr_accum_create(m_ctx[k], &q, &acc[k])) return m_error = rtr_last_error(m_ctx[k]), rc;
+            if (int rc = rtr_accum_create_ex(m_ctx[k], &q, denoise ? RTR_ACCUM_MOMENTS : 0u, &acc[k]))
+                return m_error = rtr_last_error(m_ctx[k]), rc;
         }
         std::vector<double> lin((size_t)W * H * 3);
         for (int target : targets) {
@@ -426,6 +435,8 @@ class Renderer {
             }
             for (int k = 0; k < n; ++k)
                 if (rcs[k]) return m_error = errs[k], rcs[k];
+            if (denoise && target == targets.back())
+                if (int rc = denoise_into(acc, *denoise, W, H, lin)) return rc;
             buf.store_linear_rect(lin.data(), W, 0, 0, W, H);
             if (on_pass) on_pass(target);
         }
@@ -434,7 +445,7 @@ class Renderer {
 
     int adaptive_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,
                       const std::vector<shared_ptr<Light>>& lights, bool scene_on_device, double threshold, int spp_min,
-                      int spp_max, const std::function<void(int, int, long long)>& on_pass) {
+                      int spp_max, const std::function<void(int, int, long long)>& on_pass, const rtr_denoise_params* denoise) {
         if (!(threshold > 0.0)) return m_error = "threshold must be > 0", RTR_ERR_INVALID;
         if (spp_min < 1 || spp_max < spp_min) return m_error = "need 1 <= spp_min <= spp_max", RTR_ERR_INVALID;
         if (int rc = prepare(world, cam, background, lights, scene_on_device)) return rc;
@@ -479,10 +490,50 @@ class Renderer {
                 if (rcs[k]) return m_error = errs[k], rcs[k];
             int n_active = 0;
             for (int k = 0; k < n; ++k) n_active += active[k], total += samples[k];
-            if (n_active == 0) return RTR_OK;
+            if (n_active == 0) {
+                if (!denoise) return RTR_OK;
+                if (int rc = denoise_into(acc, *denoise, W, H, lin)) return rc;
+                buf.store_linear_rect(lin.data(), W, 0, 0, W, H);
+                return RTR_OK;
+            }
             buf.store_linear_rect(lin.data(), W, 0, 0, W, H);
             if (on_pass) on_pass(pass, n_active, total);
         }
+    }
+
+    /* the denoised image of the accumulators (every tile of the W x H image among them) into `lin`: one context --
+     * rtr_accum_denoise; several -- resolve, moments, per-pixel counts and features of each gathered on the host (each
+     * call fills the pixels of its own tiles), then rtr_denoise_host on the first context */
+    int denoise_into(const std::vector<rtr_accum*>& acc, const rtr_denoise_params& prm, int W, int H, std::vector<double>& lin) {
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        const int n = (int)m_ctx.size();
+        if (n == 1) {
+            if (int rc = rtr_accum_denoise(m_ctx[0], acc[0], &prm, lin.data(), W, nullptr)) return m_error = rtr_last_error(m_ctx[0]), rc;
+        } else {
+            const size_t np = (size_t)W * H;
+            const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
+            std::vector<double> q(np), feat(7 * np);
+            std::vector<int32_t> count(np, 0);
+            for (int k = 0; k < n; ++k) {
+                int64_t nt = 0;
+                int rc = rtr_accum_resolve(m_ctx[k], acc[k], lin.data(), W, nullptr);
+                if (!rc) rc = rtr_accum_moments(m_ctx[k], acc[k], q.data(), W);
+                if (!rc) rc = rtr_accum_features(m_ctx[k], acc[k], prm.feature_spp, feat.data(), W);
+                if (!rc) rc = rtr_accum_tiles(m_ctx[k], acc[k], nullptr, nullptr, 0, &nt);
+                std::vector<int32_t> ids((size_t)nt), counts((size_t)nt);
+                if (!rc) rc = rtr_accum_tiles(m_ctx[k], acc[k], ids.data(), counts.data(), nt, &nt);
+                if (rc) return m_error = rtr_last_error(m_ctx[k]), rc;
+                for (int64_t t = 0; t < nt; ++t) { /* renderer.h:61-62 */
+                    const int tx0 = (ids[t] % tiles_x) * 16, ty0 = ((tiles_y - 1) - ids[t] / tiles_x) * 16;
+                    for (int j = ty0; j < std::min(ty0 + 16, H); ++j)
+                        for (int i = tx0; i < std::min(tx0 + 16, W); ++i) count[(size_t)j * W + i] = counts[t];
+                }
+            }
+            if (int rc = rtr_denoise_host(m_ctx[0], &prm, W, H, lin.data(), q.data(), count.data(), feat.data(), lin.data(), nullptr))
+                return m_error = rtr_last_error(m_ctx[0]), rc;
+        }
+        m_denoise_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        return RTR_OK;
     }
 
     int render_impl(const hittable& world, const camera& cam, const color& background, RenderBuffer& buf,
@@ -554,6 +605,7 @@ class Renderer {
     shared_ptr<camera> m_cam;
     std::vector<shared_ptr<Light>> m_lights;
     double m_scene_bg[3] = {0, 0, 0};
+    double m_denoise_seconds = 0;
     bool m_scene_valid = false;
     int m_scene_uploads = 0;
     int m_status = RTR_OK;

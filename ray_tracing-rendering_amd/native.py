@@ -23,7 +23,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_upload_scene", "rtr_render_device", "rtr_render_host", "rtr_render_tiles_host", "rtr_plan_chunks", "rtr_li_samples", "rtr_li_rays",
            "rtr_synchronize", "rtr_cancel", "rtr_get_stats", "rtr_last_error", "rtr_sample_seed", "rtr_validate_scene",
            "rtr_accum_create", "rtr_accum_render", "rtr_accum_resolve", "rtr_accum_tiles", "rtr_accum_destroy",
-           "rtr_accum_create_ex", "rtr_accum_render_tiles", "rtr_accum_moments", "rtr_accum_errors", "rtr_accum_refine")
+           "rtr_accum_create_ex", "rtr_accum_render_tiles", "rtr_accum_moments", "rtr_accum_errors", "rtr_accum_refine",
+           "rtr_denoise_defaults", "rtr_accum_features", "rtr_accum_denoise", "rtr_denoise_host")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
@@ -98,6 +99,11 @@ def lib():
     L.rtr_accum_moments.argtypes = [vp, vp, vp, C.c_int64]
     L.rtr_accum_errors.argtypes = [vp, vp, vp, C.c_int64, P(C.c_int64)]
     L.rtr_accum_refine.argtypes = [vp, vp, C.c_double, C.c_int32, C.c_int32, C.c_int, P(C.c_int32)]
+    L.rtr_denoise_defaults.argtypes = [P(A.DenoiseParamsC)]
+    L.rtr_denoise_defaults.restype = None
+    L.rtr_accum_features.argtypes = [vp, vp, C.c_int32, vp, C.c_int64]
+    L.rtr_accum_denoise.argtypes = [vp, vp, P(A.DenoiseParamsC), vp, C.c_int64, vp]
+    L.rtr_denoise_host.argtypes = [vp, P(A.DenoiseParamsC), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -145,6 +151,41 @@ def validate_scene(scene):
             "fast_refs": info.fast_refs, "fast_stack_words": info.fast_stack_words,
             "compiled_subtrees": info.compiled_subtrees, "program_steps": info.program_steps,
             "inverted_boxes": info.inverted_boxes, "top_trees": info.top_trees}
+
+
+def denoise_defaults(**overrides):
+    """rtr_denoise_params with the library's defaults (rtr_denoise_defaults), fields replaced by ``overrides``."""
+    p = A.DenoiseParamsC()
+    lib().rtr_denoise_defaults(C.byref(p))
+    for k, v in overrides.items():
+        if k not in ("iterations", "feature_spp", "sigma_l", "sigma_n", "sigma_a", "sigma_z"):
+            raise TypeError("no denoise parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def denoise_host(ctx, color, q, count, feat, params=None, rgb8=False, out=None):
+    """rtr_denoise_host on ``ctx``: the denoiser over host planes of a region (row 0 = its lowest row) -- ``color``
+    (H, W, 3) linear mean, ``q`` (H, W) second moments, ``count`` (H, W) samples of the pixel's tile (0: not a tap, its
+    output keeps the value of ``out``), ``feat`` (H, W, 7) features; what a tile-sharded render gathers from its shards'
+    resolve / moments / tiles / features.  Returns linear (H, W, 3) float64, or with ``rgb8`` the 8-bit store (Y
+    flipped) as ``Accumulator.denoise``."""
+    color = np.ascontiguousarray(color, dtype=np.float64)
+    h, w = color.shape[:2]
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    count = np.ascontiguousarray(count, dtype=np.int32)
+    feat = np.ascontiguousarray(feat, dtype=np.float64)
+    if color.shape != (h, w, 3) or q.shape != (h, w) or count.shape != (h, w) or feat.shape != (h, w, A.FEATURES):
+        raise ValueError("planes of shapes (H, W, 3), (H, W), (H, W), (H, W, 7) expected")
+    dtype = np.uint8 if rgb8 else np.float64
+    if out is None:
+        out = np.zeros((h, w, 3), dtype=dtype)
+    elif out.shape != (h, w, 3) or out.dtype != dtype or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous %s array of shape (%d, %d, 3)" % (np.dtype(dtype).name, h, w))
+    prm = params if params is not None else denoise_defaults()
+    ctx._chk(ctx._L.rtr_denoise_host(ctx._h, C.byref(prm), w, h, color.ctypes.data, q.ctypes.data, count.ctypes.data,
+                                     feat.ctypes.data, None if rgb8 else out.ctypes.data, out.ctypes.data if rgb8 else None))
+    return out
 
 
 class Context:
@@ -399,6 +440,31 @@ class Accumulator:
         self._ctx._chk(self._L.rtr_accum_refine(self._ctx._h, self._handle(), float(threshold), int(spp_min),
                                                 int(spp_max), 1 if blocking else 0, C.byref(n)))
         return int(n.value)
+
+    def features(self, feature_spp, out=None):
+        """First-hit features of ``feature_spp`` camera samples per pixel (rtr_accum_features), (H, W, 7) float64 like
+        ``resolve``: albedo 0..2, normal 3..5, depth 6; pixels of tiles not owned keep the values of ``out``."""
+        h, w = self.shape
+        if out is None:
+            out = np.zeros((h, w, A.FEATURES), dtype=np.float64)
+        elif out.shape != (h, w, A.FEATURES) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float64 array of shape (%d, %d, %d)" % (h, w, A.FEATURES))
+        self._ctx._chk(self._L.rtr_accum_features(self._ctx._h, self._handle(), int(feature_spp), out.ctypes.data, w))
+        return out
+
+    def denoise(self, params=None, rgb8=False, out=None):
+        """The denoised image (rtr_accum_denoise; ``params``: an rtr_denoise_params, default ``denoise_defaults()``):
+        linear (H, W, 3) float64 like ``resolve``, or with ``rgb8`` the bytes of ``rgb8()``.  Pixels of tiles without
+        samples keep the values of ``out``.  Needs an accumulator with moments and every tile of its region."""
+        prm = params if params is not None else denoise_defaults()
+        if rgb8:
+            out = self._out(out, np.uint8)
+            self._ctx._chk(self._L.rtr_accum_denoise(self._ctx._h, self._handle(), C.byref(prm), None, 0, out.ctypes.data))
+        else:
+            out = self._out(out, np.float64)
+            self._ctx._chk(self._L.rtr_accum_denoise(self._ctx._h, self._handle(), C.byref(prm), out.ctypes.data,
+                                                     self.shape[1], None))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -129,19 +129,23 @@ class Renderer:
             self._rendering = False
         return target_buffer
 
-    def render_progressive(self, scene, target_buffer, targets, rank=0, world=1):
+    def render_progressive(self, scene, target_buffer, targets, rank=0, world=1, denoise=None):
         """Progressive ``render``: a generator that, for each of the increasing sample counts ``targets``, continues
         the per-pixel sums of the tiles ``rank`` owns to that many samples (one accumulator, include/rtr_hip.h:
         rtr_accum_*), stores the image into ``target_buffer`` and yields the count.  The image at count T is the
         bits of a render with spp = T and spp_chunks = 1.  ``cancel()`` ends it: the buffer then holds the last
-        count yielded.  Bad schedules raise ValueError here, before any device call."""
+        count yielded.  ``denoise`` (an rtr_denoise_params, e.g. ``denoise_defaults()``): the accumulator keeps moments
+        and the image stored after the last pass is the denoised one (rtr_accum_denoise; with world > 1 the ranks'
+        planes are gathered and passed through rtr_denoise_host).  Bad schedules or denoise parameters raise
+        ValueError here, before any device call."""
         targets = [int(t) for t in targets]
         if not targets or targets[0] < 1 or any(b <= a for a, b in zip(targets, targets[1:])):
             raise ValueError("targets must be a non-empty, strictly increasing list of sample counts >= 1: %r" % (targets,))
+        check_denoise(denoise)
         self._cancel_requested = False
-        return self._progressive(scene, target_buffer, targets, rank, world)
+        return self._progressive(scene, target_buffer, targets, rank, world, denoise)
 
-    def _progressive(self, scene, target_buffer, targets, rank, world):
+    def _progressive(self, scene, target_buffer, targets, rank, world, denoise):
         from .native import RtrError
         self._rendering = True
         try:
@@ -149,7 +153,7 @@ class Renderer:
                 self._ctx.upload(scene)
             p = A.make_params(target_buffer.width, target_buffer.height, 1, integrator=self._integrator, seed=self.seed,
                               max_depth=self._max_depth, pipeline=self.pipeline, tile_first=rank, tile_stride=world)
-            with self._ctx.accumulator(p) as acc:
+            with self._ctx.accumulator(p, moments=denoise is not None) as acc:
                 for t in targets:
                     if self._cancel_requested:
                         return
@@ -160,28 +164,33 @@ class Renderer:
                             return
                         raise
                     # pixels of tiles other ranks own keep what the buffer holds
-                    target_buffer.store_linear(acc.resolve(target_buffer.linear.copy()))
+                    if denoise is not None and t == targets[-1]:
+                        target_buffer.store_linear(self._denoised(acc, denoise, target_buffer, rank, world))
+                    else:
+                        target_buffer.store_linear(acc.resolve(target_buffer.linear.copy()))
                     yield t
         finally:
             self._rendering = False
 
-    def render_adaptive(self, scene, target_buffer, threshold, spp_min, spp_max, rank=0, world=1):
+    def render_adaptive(self, scene, target_buffer, threshold, spp_min, spp_max, rank=0, world=1, denoise=None):
         """Adaptive ``render``: a generator of refinement passes over the tiles ``rank`` owns (one accumulator with
         second moments, include/rtr_hip.h: rtr_accum_refine).  The first pass takes every tile to ``spp_min`` samples;
         each later one doubles the samples of the tiles whose error estimate is above ``threshold`` (1/255 = one 8-bit
         step of the stored image), up to ``spp_max``.  After each pass the image goes into ``target_buffer`` and
         (pass number from 1, tiles refined, samples rendered so far) is yielded; it ends when no tile is left to refine
-        or on ``cancel()``.  A tile holding T samples is the bits of a render with spp = T and spp_chunks = 1.  Bad
-        arguments raise ValueError here, before any device call."""
+        or on ``cancel()``.  A tile holding T samples is the bits of a render with spp = T and spp_chunks = 1.
+        ``denoise`` (an rtr_denoise_params): once no tile is left to refine, the buffer takes the denoised image
+        (as ``render_progressive``).  Bad arguments raise ValueError here, before any device call."""
         threshold = float(threshold)
         if not threshold > 0.0:
             raise ValueError("threshold must be > 0: %r" % threshold)
         if int(spp_min) != spp_min or int(spp_max) != spp_max or not 1 <= spp_min <= spp_max:
             raise ValueError("need integers 1 <= spp_min <= spp_max: %r, %r" % (spp_min, spp_max))
+        check_denoise(denoise)
         self._cancel_requested = False
-        return self._adaptive(scene, target_buffer, threshold, int(spp_min), int(spp_max), rank, world)
+        return self._adaptive(scene, target_buffer, threshold, int(spp_min), int(spp_max), rank, world, denoise)
 
-    def _adaptive(self, scene, target_buffer, threshold, spp_min, spp_max, rank, world):
+    def _adaptive(self, scene, target_buffer, threshold, spp_min, spp_max, rank, world, denoise):
         from .native import RtrError
         self._rendering = True
         try:
@@ -201,12 +210,58 @@ class Renderer:
                             return
                         raise
                     if n_active == 0:
+                        if denoise is not None:
+                            target_buffer.store_linear(self._denoised(acc, denoise, target_buffer, rank, world))
                         return
                     total += self._ctx.stats()["samples"]
                     target_buffer.store_linear(acc.resolve(target_buffer.linear.copy()))
                     yield k, n_active, total
         finally:
             self._rendering = False
+
+    def _denoised(self, acc, params, target_buffer, rank, world):
+        """The denoised image of ``acc`` over the buffer's linear image.  world > 1: every rank's resolve, moments,
+        counts and features are summed over the default torch.distributed group (each pixel is owned by one rank, the
+        others contribute zeros) and denoised with rtr_denoise_host: the bits of the unsharded rtr_accum_denoise."""
+        if world == 1:
+            return acc.denoise(params, out=target_buffer.linear.copy())
+        import torch
+        import torch.distributed as dist
+        from .native import denoise_host
+        h, w = acc.shape
+        own = ownership_mask(w, h, rank, world)
+        ids, counts = acc.tiles()
+        count = np.zeros((h, w), dtype=np.int32)
+        for t, n in zip(ids, counts):
+            x0, y0, x1, y1 = tile_rect(w, h, int(t))
+            count[y0:y1, x0:x1] = n
+        planes = [acc.resolve(), acc.moments(), count, acc.features(params.feature_spp)]
+        planes = [np.where(own.reshape(own.shape + (1,) * (x.ndim - 2)), x, 0) for x in planes]
+        summed = []
+        for x in planes:
+            t = torch.from_numpy(np.ascontiguousarray(x))
+            dist.all_reduce(t)
+            summed.append(t.numpy())
+        return denoise_host(self._ctx, *summed, params=params, out=target_buffer.linear.copy())
+
+
+def check_denoise(params):
+    """ValueError unless ``params`` is None or valid rtr_denoise_params (the checks of rtr_accum_denoise)."""
+    import math
+    if params is None:
+        return
+    if not isinstance(params, A.DenoiseParamsC):
+        raise ValueError("denoise must be None or rtr_denoise_params (denoise_defaults())")
+    if not 0 <= params.iterations <= 10:
+        raise ValueError("denoise iterations must be in 0..10: %r" % params.iterations)
+    if params.feature_spp < 1:
+        raise ValueError("denoise feature_spp must be >= 1: %r" % params.feature_spp)
+    for k in ("sigma_l", "sigma_n", "sigma_a", "sigma_z"):
+        v = getattr(params, k)
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError("denoise %s must be finite and > 0: %r" % (k, v))
+    if any(r != 0.0 for r in params.reserved):
+        raise ValueError("denoise reserved fields must be 0")
 
 
 def _tile_view(t, width, height):
