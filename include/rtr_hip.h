@@ -250,6 +250,11 @@ typedef struct rtr_render_params {
  * Same image bit for bit; measured slower on MI355X (4.06 against 6.62 Gsamples/s on scene 23), kept
  * selectable. */
 #define RTR_FLAG_SORTED_SHADING 4
+/* Megakernel only: cast a bounce's shadow ray and the next closest-hit ray one after the other instead of in one pass over
+ * the instances.  The pair cast is what the MIS integrator runs on lit flat scenes of at most four instances made of
+ * rectangles, boxes and spheres (scenes 21 and 23); this flag asks for the split casts there, and is reported in
+ * flags_in_effect where it changed the kernel.  Same image and segment counts bit for bit. */
+#define RTR_FLAG_SPLIT_CASTS 8
 
 typedef struct rtr_render_stats {
     uint64_t samples;          /* camera samples finished                               */

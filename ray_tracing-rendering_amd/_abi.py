@@ -27,6 +27,7 @@ PIPELINE_AUTO, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT = 0, 1, 2
 FLAG_REFERENCE_ORDER = 1
 FLAG_WF_PERSISTENT = 2
 FLAG_SORTED_SHADING = 4
+FLAG_SPLIT_CASTS = 8
 ACCUM_MOMENTS = 1  # rtr_accum_create_ex: keep per-pixel second moments (adaptive sampling)
 
 NODE_DTYPE = np.dtype([("type", "<i4"), ("a", "<i4"), ("b", "<i4"), ("reserved", "<i4"), ("f", "<f8", (10,))])

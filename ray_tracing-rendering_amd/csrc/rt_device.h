@@ -40,7 +40,8 @@ typedef double Real;
 enum { RG_OTHER = 0, RG_SETUP = 1, RG_RECTS = 2, RG_SPHERES = 3, RG_GENERIC = 4, RG_TREE = 5, RG_LEAVES = 6, RG_FINISH = 7,
        RG_SH_SETUP = 8, RG_SH_RECTS = 9, RG_SH_SPHERES = 10, RG_SH_GENERIC = 11, RG_SH_TREE = 12, RG_SH_LEAVES = 13,
        RG_MEDIA = 14, RG_MATPREP = 15, RG_SHADE_A = 16, RG_SHADE_B = 17, RG_MISS = 18, RG_REGEN = 19, RG_SHADE_RR = 20,
-       RG_PARK = 21, RG_BARRIER = 22, RG_EXCHANGE = 23, RG_N = 24 };
+       RG_PARK = 21, RG_BARRIER = 22, RG_EXCHANGE = 23, RG_PAIR_SETUP = 24, RG_PAIR_RUNS = 25, RG_PAIR_SPHERES = 26,
+       RG_N = 27 };
 #ifdef RTR_REGION_PROFILE
 __shared__ unsigned long long rt_prof_lds[4 * 2 * RT_PROF_REGIONS + 4 * 2]; /* [wave][cycles | visits][region], then [wave][last, current] */
 RT_DEV void rt_region(int id) {
@@ -275,7 +276,9 @@ struct DScene {
     int32_t needs_uv; /* some texture reads (u,v): image textures */
     int32_t shared_div; /* every coordinate of the scene is below 2^60 and no transform chain is deeper than 30: the primitive
                            tests may divide through RayDiv (div_shared's range argument) */
-    int32_t pad_;
+    int32_t pair_cast; /* the MIS kernels of flat scenes cast a bounce's shadow ray and the next closest-hit ray in one pass
+                          over the instances (trace_pair): every instance is a packed scan without moving spheres, no instance
+                          boxes are tested (at most RT_FAST_NO_BOX_MAX instances) and shared_div holds */
     /* compiled scene for the order-free traversal (trace_fast); scenes with media use it per step (FStep) */
     const struct FInst* finst;
     const struct FXf* fxf;
@@ -1421,6 +1424,186 @@ __device__ __forceinline__ bool trace_fast(const DScene& sc, const FSub sub, V3 
         if (trace_top<ANY>(sc, sub, o, d, time, tmin, tmax, hit_ref, hit_inst, order, st, sp0) && ANY) return true;
     }
     return hit_ref >= 0;
+}
+
+/* ---- the pair cast ------------------------------------------------------------------------------------------------
+ * The MIS kernels of flat scenes (rt_kernels.h, k_mega<..., PAIR>) cast the shadow ray of bounce k (ray B: any hit in
+ * [0.001, tmax]) and the closest-hit ray of bounce k + 1 (ray A: [0.001, inf)) in ONE walk over the instances: the instance
+ * record, its run list and every packed record are loaded and decoded once for both rays, and each record is tested
+ * against A and then B -- two independent FP64 chains per record where the single casts have one.  Each ray still meets
+ * every reference with the arithmetic of trace_fast<false> / trace_fast<true> and the same `t == t_max` rule, so
+ * hit_ref, hit_inst and t of A and "occluded" of B are those of the two single casts bit for bit (B tests on after its
+ * first hit, which changes nothing but its t).  A ray that a lane does not cast arrives as the dummy (0, 0, 0) + t (1, 1, 1)
+ * with t_max = 0: no record accepts it and it keeps the shared-division checks (wave-level votes) true.  A frame where
+ * either ray needs the plain divisions (RayDiv::fast, wave-uniform) runs the two single-ray scans of trace_fast. */
+/* the rectangle test of run_rect_test_x for two rays: both t first (interleaved), A's in-plane coordinates under the full
+ * mask, then A's acceptance block and B's with its wave-level exit, EXEC saved once and put back after each block */
+template <int TYPE>
+RT_DEV void pair_rect(Real a0, Real a1, Real b0, Real b1, Real k, int ref, V3 oA, V3 dA, const RayDiv& qA, Real& tmaxA,
+                      int& hitA, V3 oB, V3 dB, const RayDiv& qB, Real& tmaxB, int& hitB) {
+    const Real tmin = 0.001;
+#define RT_PAIR_SEL(V, XY, XZ, YZ) (TYPE == RTR_NODE_XY_RECT ? V.XY : (TYPE == RTR_NODE_XZ_RECT ? V.XZ : V.YZ))
+    const Real okA = RT_PAIR_SEL(oA, z, y, x), dkA = RT_PAIR_SEL(dA, z, y, x), rkA = RT_PAIR_SEL(qA, rz, ry, rx);
+    const Real okB = RT_PAIR_SEL(oB, z, y, x), dkB = RT_PAIR_SEL(dB, z, y, x), rkB = RT_PAIR_SEL(qB, rz, ry, rx);
+    const Real oaA = TYPE == RTR_NODE_YZ_RECT ? oA.y : oA.x, daA = TYPE == RTR_NODE_YZ_RECT ? dA.y : dA.x;
+    const Real obA = TYPE == RTR_NODE_XY_RECT ? oA.y : oA.z, dbA = TYPE == RTR_NODE_XY_RECT ? dA.y : dA.z;
+    const Real oaB = TYPE == RTR_NODE_YZ_RECT ? oB.y : oB.x, daB = TYPE == RTR_NODE_YZ_RECT ? dB.y : dB.x;
+    const Real obB = TYPE == RTR_NODE_XY_RECT ? oB.y : oB.z, dbB = TYPE == RTR_NODE_XY_RECT ? dB.y : dB.z;
+#undef RT_PAIR_SEL
+    Real nA, nB, tA, tB, uA, wA, u;
+    unsigned long long save;
+    asm volatile("v_add_f64 %[nA], %[k], -%[okA]\n\t"
+                 "v_add_f64 %[nB], %[k], -%[okB]\n\t"
+                 "v_mul_f64 %[tA], %[nA], %[rkA]\n\t"
+                 "v_mul_f64 %[tB], %[nB], %[rkB]\n\t"
+                 "v_fma_f64 %[nA], -%[dkA], %[tA], %[nA]\n\t"
+                 "v_fma_f64 %[nB], -%[dkB], %[tB], %[nB]\n\t"
+                 "v_fma_f64 %[tA], %[nA], %[rkA], %[tA]\n\t"
+                 "v_fma_f64 %[tB], %[nB], %[rkB], %[tB]\n\t"
+                 "v_mul_f64 %[uA], %[tA], %[daA]\n\t"
+                 "v_mul_f64 %[wA], %[tA], %[dbA]\n\t"
+                 "v_add_f64 %[uA], %[oaA], %[uA]\n\t"
+                 "v_add_f64 %[wA], %[obA], %[wA]"
+                 : [nA] "=&v"(nA), [nB] "=&v"(nB), [tA] "=&v"(tA), [tB] "=&v"(tB), [uA] "=&v"(uA), [wA] "=&v"(wA)
+                 : [k] "s"(k), [okA] "v"(okA), [dkA] "v"(dkA), [rkA] "v"(rkA), [okB] "v"(okB), [dkB] "v"(dkB), [rkB] "v"(rkB),
+                   [oaA] "v"(oaA), [daA] "v"(daA), [obA] "v"(obA), [dbA] "v"(dbA));
+    asm volatile("s_mov_b64 %[save], exec\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[tmin], %[tA]\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[tA], %[tmaxA]\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[a0], %[uA]\n\t"
+                 "v_cmpx_nlt_f64 vcc, %[a1], %[uA]\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[b0], %[wA]\n\t"
+                 "v_cmpx_nlt_f64 vcc, %[b1], %[wA]\n\t"
+                 "v_mov_b64 %[tmaxA], %[tA]\n\t"
+                 "v_mov_b32 %[hitA], %[ref]\n\t"
+                 "s_mov_b64 exec, %[save]\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[tmin], %[tB]\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[tB], %[tmaxB]\n\t"
+                 "s_cbranch_execz .Lpx%=\n\t"
+                 "v_mul_f64 %[u], %[tB], %[daB]\n\t"
+                 "v_add_f64 %[u], %[oaB], %[u]\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[a0], %[u]\n\t"
+                 "v_cmpx_nlt_f64 vcc, %[a1], %[u]\n\t"
+                 "v_mul_f64 %[u], %[tB], %[dbB]\n\t"
+                 "v_add_f64 %[u], %[obB], %[u]\n\t"
+                 "v_cmpx_ngt_f64 vcc, %[b0], %[u]\n\t"
+                 "v_cmpx_nlt_f64 vcc, %[b1], %[u]\n\t"
+                 "v_mov_b64 %[tmaxB], %[tB]\n\t"
+                 "v_mov_b32 %[hitB], %[ref]\n"
+                 ".Lpx%=:\n\t"
+                 "s_mov_b64 exec, %[save]"
+                 : [u] "=&v"(u), [save] "=&s"(save), [tmaxA] "+v"(tmaxA), [hitA] "+v"(hitA), [tmaxB] "+v"(tmaxB), [hitB] "+v"(hitB)
+                 : [tA] "v"(tA), [uA] "v"(uA), [wA] "v"(wA), [tB] "v"(tB), [oaB] "v"(oaB), [daB] "v"(daB), [obB] "v"(obB),
+                   [dbB] "v"(dbB), [a0] "s"(a0), [a1] "s"(a1), [b0] "s"(b0), [b1] "s"(b1), [ref] "s"(ref), [tmin] "s"(tmin)
+                 : "vcc");
+}
+/* one ray of a pair in the frame of the current instance */
+struct PairRay {
+    V3 o, d;
+    RayDiv q;
+};
+template <int TYPE>
+RT_DEV void pair_rects(const RT_CONST_AS double* p, int cnt, int ref, const PairRay& A, Real& tmaxA, int& hitA, const PairRay& B,
+                       Real& tmaxB, int& hitB) {
+    int k = 0;
+    for (; k + 1 < cnt; k += 2, p += 10) { /* two records, one scalar-load round trip (run_rects) */
+        const Real f0 = p[0], f1 = p[1], f2 = p[2], f3 = p[3], f4 = p[4];
+        const Real g0 = p[5], g1 = p[6], g2 = p[7], g3 = p[8], g4 = p[9];
+        pair_rect<TYPE>(f0, f1, f2, f3, f4, ref + k, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+        pair_rect<TYPE>(g0, g1, g2, g3, g4, ref + k + 1, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+    }
+    if (k < cnt) pair_rect<TYPE>(p[0], p[1], p[2], p[3], p[4], ref + k, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+}
+/* the runs of one instance (scan_runs) for both rays: every record is fetched once */
+RT_DEV void pair_runs(const DScene& sc, const FInst& I, const PairRay& A, Real time, Real& tmaxA, int& hitA, const PairRay& B,
+                      Real& tmaxB, int& hitB) {
+    const RT_CONST_AS double* p = as_const(sc.fscan) + I.scan_first;
+    int ref = I.ref_first;
+#pragma nounroll
+    for (uint64_t runs = I.runs; runs != 0; runs >>= RT_RUN_BITS) {
+        const int type = RTR_NODE_SPHERE + (int)((runs >> RT_RUN_COUNT_BITS) & 7), cnt = (int)(runs & RT_RUN_COUNT_MAX);
+        RT_REGION(type >= RTR_NODE_XY_RECT ? RG_PAIR_RUNS : RG_PAIR_SPHERES); /* boxes count as rects */
+        if (type == RTR_NODE_XY_RECT) {
+            pair_rects<RTR_NODE_XY_RECT>(p, cnt, ref, A, tmaxA, hitA, B, tmaxB, hitB);
+            p += 5 * cnt;
+        } else if (type == RTR_NODE_XZ_RECT) {
+            pair_rects<RTR_NODE_XZ_RECT>(p, cnt, ref, A, tmaxA, hitA, B, tmaxB, hitB);
+            p += 5 * cnt;
+        } else if (type == RTR_NODE_YZ_RECT) {
+            pair_rects<RTR_NODE_YZ_RECT>(p, cnt, ref, A, tmaxA, hitA, B, tmaxB, hitB);
+            p += 5 * cnt;
+        } else if (type == RTR_NODE_SPHERE + RT_RUN_BOX) { /* run_box: the six sides in list order */
+            for (int b = 0, r = ref; b < cnt; ++b, p += 6, r += 6) {
+                const Real x0 = p[0], x1 = p[1], y0 = p[2], y1 = p[3], z0 = p[4], z1 = p[5];
+                pair_rect<RTR_NODE_XY_RECT>(x0, x1, y0, y1, z1, r, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+                pair_rect<RTR_NODE_XY_RECT>(x0, x1, y0, y1, z0, r + 1, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+                pair_rect<RTR_NODE_XZ_RECT>(x0, x1, z0, z1, y1, r + 2, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+                pair_rect<RTR_NODE_XZ_RECT>(x0, x1, z0, z1, y0, r + 3, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+                pair_rect<RTR_NODE_YZ_RECT>(y0, y1, z0, z1, x1, r + 4, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+                pair_rect<RTR_NODE_YZ_RECT>(y0, y1, z0, z1, x0, r + 5, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
+            }
+            ref += 5 * cnt; /* six references per box */
+        } else { /* RTR_NODE_SPHERE (upload leaves moving spheres out of pair_cast scenes) */
+            for (int k = 0; k < cnt; ++k, p += 4) {
+                const V3 c = mk(p[0], p[1], p[2]);
+                const Real r = p[3];
+                Real t;
+                if (sphere_hit_t<true>(c, r, A.o, A.d, A.q, 0.001, tmaxA, t)) tmaxA = t, hitA = ref + k;
+                if (sphere_hit_t<true>(c, r, B.o, B.d, B.q, 0.001, tmaxB, t)) tmaxB = t, hitB = ref + k;
+            }
+        }
+        ref += cnt;
+    }
+}
+/* A: closest hit from (ao, ad) at `atime` -> a_ref, a_inst, a_tmax (in: the ray's t_max); B: any hit from (bo, bd) within
+ * b_tmax -> b_ref >= 0.  Sub-scene 0 of a DScene::pair_cast scene only. */
+__device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
+                                           V3 bo, V3 bd, Real& b_tmax, int& b_ref, const Stack st) {
+    a_ref = -1, a_inst = -1, b_ref = -1;
+#ifndef RTR_NO_SHARED_DIV
+    const bool ok_a = raydiv_origin_ok(ao), ok_b = raydiv_origin_ok(bo); /* (pair_cast implies shared_div) */
+#else /* experiments without the shared reciprocals: every frame takes the single-ray scans with plain divisions */
+    const bool ok_a = false, ok_b = false;
+#endif
+    for (int ii = 0; ii < sc.n_finst; ++ii) {
+        RT_REGION(RG_PAIR_SETUP);
+        const FInst I = ld_const(sc.finst, ii);
+        PairRay A, B;
+        A.o = ao, A.d = ad, B.o = bo, B.d = bd;
+        const int n_xf = I.n_xf;
+        if (n_xf) {
+            wrapper_enter(I.xf_type[0], I.xf_f[0], A.o, A.d);
+            wrapper_enter(I.xf_type[0], I.xf_f[0], B.o, B.d);
+            if (n_xf > 1) {
+                wrapper_enter(I.xf_type[1], I.xf_f[1], A.o, A.d);
+                wrapper_enter(I.xf_type[1], I.xf_f[1], B.o, B.d);
+            }
+            for (int k = RT_INST_XF_INLINE; k < n_xf; ++k) {
+                const FXf x = ld_const(sc.fxf, I.xf_first + k);
+                wrapper_enter(x.type, x.f, A.o, A.d);
+                wrapper_enter(x.type, x.f, B.o, B.d);
+            }
+        }
+        A.q = raydiv_make(A.d, 0.001, ok_a);
+        B.q = raydiv_make(B.d, 0.001, ok_b);
+        if (I.flags & RT_INST_SPHERES) raydiv_spheres(A.q, A.d), raydiv_spheres(B.q, B.d);
+        if (A.q.fast && B.q.fast) {
+            pair_runs(sc, I, A, atime, a_tmax, a_ref, B, b_tmax, b_ref);
+        } else { /* the single-ray scans of trace_fast, one after the other, with its template arguments (a direction
+                  * component or |d|^2 outside [2^-100, 2^100], an origin beyond 2^80: tests/test_pair_cast.py) */
+            int order = -1;
+            if (A.q.fast)
+                scan_instance<false, false, false, true>(sc, I, A.o, A.d, A.q, atime, 0.001, a_tmax, a_ref, order, st, 0);
+            else
+                scan_instance<false, false, false, false>(sc, I, A.o, A.d, A.q, atime, 0.001, a_tmax, a_ref, order, st, 0);
+            if (B.q.fast)
+                scan_instance<true, false, true, true>(sc, I, B.o, B.d, B.q, 0.0, 0.001, b_tmax, b_ref, order, st, 0);
+            else
+                scan_instance<true, false, true, false>(sc, I, B.o, B.d, B.q, 0.0, 0.001, b_tmax, b_ref, order, st, 0);
+        }
+        RT_REGION(RG_PAIR_SETUP);
+        if (a_ref >= I.ref_first) a_inst = ii;
+    }
 }
 
 /* Build the reference's hit_record for (reference, instance, t): the primitive's own hit()

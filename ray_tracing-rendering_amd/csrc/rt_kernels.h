@@ -86,6 +86,9 @@ constexpr int park_words(int integ, int trav) {
 constexpr bool mega_sortable(int integ, int trav, int ms) {
     return integ == RTR_INTEGRATOR_MIS && trav == RT_TRAV_FLAT && ms == RT_MS_QUADLIT;
 }
+/* which (integrator, traversal) has a pair-cast instantiation (k_mega's PAIR branch, trace_pair): what a DScene::pair_cast
+ * scene runs unless RTR_FLAG_SPLIT_CASTS asks for the split casts */
+constexpr bool mega_pairable(int integ, int trav) { return integ == RTR_INTEGRATOR_MIS && trav == RT_TRAV_FLAT; }
 /* parked words of the sorted variant (the pixel sum lives in the partial-sum buffer itself) + the exchange slot */
 enum { SK_THR = 0, SK_L = 3, SK_PDF = 6, SK_NCLOSEST = 7, SK_NSHADOW = 8, SK_CONTRIB = 9, SK_SWI = 12, SK_STMAX = 15, SK_X = 16,
        SK_WORDS = 26 };
@@ -107,10 +110,11 @@ RT_DEV V3 acc_start(const RenderK& P, int slot) {
  * its sample count RenderK::tile_s0 to RenderK::tile_s1 with the sums RenderK::acc_in; 2 = a pass of an accumulator
  * with moments, which also continues Q = sum of y_s * y_s (y_s = luminance of sample s) in a register, in sample
  * order, and leaves it in RenderK::q_part */
-template <int INTEG, int TRAV, int MS, bool SORT = false, int ACC = 0>
+template <int INTEG, int TRAV, int MS, bool SORT = false, int ACC = 0, bool PAIR = false>
 __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     k_mega(const DScene* __restrict__ scp, const RenderK P, const int stack_words) {
     static_assert(!SORT || mega_sortable(INTEG, TRAV, MS), "no sorted variant of this kernel");
+    static_assert(!PAIR || (mega_pairable(INTEG, TRAV) && !SORT), "no pair-cast variant of this kernel");
     extern __shared__ int lds_stack[];
     const DScene& sc = *scp;
     const Stack st{lds_stack + threadIdx.x};
@@ -339,6 +343,136 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             }
         }
         pk.set3(PK_ACC, acc);
+    } else if (PAIR) {
+        /* The MIS kernel of a DScene::pair_cast scene: the shadow ray of bounce k and the closest-hit ray of bounce k + 1
+         * are both known once the BSDF sample of bounce k is drawn, and neither cast draws a random number (no media), so
+         * one trace_pair per iteration casts both.  An iteration: (1) the pair cast of the parked shadow request (B) and
+         * the lane's ray (A); (2) the light sample of B reaches L; (3) a sample that ended in the previous iteration --
+         * its L complete now -- is added to the pixel sum; (4) A's hit is shaded (emission, light sample, BSDF sample) or
+         * its miss term added; (5) the new shadow request is parked; (6) an ended sample's lane starts the next one.  The
+         * terms reach L in the reference's order (the light sample of bounce k, then the emission or miss term of bounce
+         * k + 1), samples reach the pixel sum in sample order, and a lane whose sample ended keeps that sample's L in
+         * PK_L, and the origin of its shadow ray in `so`, while it casts the new sample's camera ray. */
+        auto begin_sample = [&]() { /* renderer.h:73-75 under the per-sample seed; PK_L is cleared by step (3) */
+            int pi, pj;
+            bool in_region;
+            tile_pixel(P, slot, threadIdx.x, pi, pj, in_region);
+            rng = rtr_sample_seed_inline(P.seed, P.W, pi, pj, s);
+            const Real u = (pi + rng_next(rng)) / (P.W - 1);
+            const Real v = (pj + rng_next(rng)) / (P.H - 1);
+            camera_get_ray(sc.camera, u, v, rng, ps.ro, ps.rd, ps.tm);
+            ps.depth = 0, ps.specular_bounce = false;
+            pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
+            pk.set(PK_PDF, 0.0);
+        };
+        pk.set(PK_NCLOSEST, 0.0);
+        pk.set(PK_NSHADOW, 0.0);
+        pk.set3(PK_L, mk(0.0, 0.0, 0.0));
+        if (!done) begin_sample();
+        bool pending = false; /* a shadow request is parked: PK_SWI, PK_STMAX, PK_CONTRIB, origin `so` */
+        bool settle = false;  /* the sample in PK_L has ended: add it to the pixel sum once its shadow ray is resolved */
+        V3 so = mk(0.0, 0.0, 0.0);
+#ifdef RTR_PHASE_CLOCKS /* closest = the pair casts, shadow = resolving them + settling ended samples */
+        long long clk_closest = 0, clk_shade = 0, clk_shadow = 0, clk_other = 0, clk_t = wall_clock64();
+#define RTR_CLK(acc) do { const long long now_ = wall_clock64(); acc += now_ - clk_t; clk_t = now_; } while (0)
+#else
+#define RTR_CLK(acc) do { } while (0)
+#endif
+        while (!done || settle) {
+            RTR_CLK(clk_other);
+            RT_REGION(RG_OTHER);
+            const bool cast_a = !done;
+            Real a_tmax = RT_INF, b_tmax = 0.0;
+            int a_ref, a_inst, b_ref;
+            V3 swi = mk(1.0, 1.0, 1.0);
+            if (cast_a) {
+                pk.set(PK_NCLOSEST, pk.get(PK_NCLOSEST) + 1.0);
+            } else { /* (the lane's path state is dead: the dummy ray in place, no copies live across the cast) */
+                ps.ro = mk(0.0, 0.0, 0.0), ps.rd = mk(1.0, 1.0, 1.0), ps.tm = 0.0;
+                a_tmax = 0.0;
+            }
+            if (pending) {
+                pk.set(PK_NSHADOW, pk.get(PK_NSHADOW) + 1.0);
+                swi = pk.get3(PK_SWI);
+                b_tmax = pk.get(PK_STMAX);
+            } else {
+                so = mk(0.0, 0.0, 0.0);
+            }
+            trace_pair(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
+            RTR_CLK(clk_closest);
+            RT_REGION(RG_OTHER);
+            if (pending && b_ref < 0) pk.set3(PK_L, add(pk.get3(PK_L), pk.get3(PK_CONTRIB))); /* mis_path_integrator.h:210-213 */
+            pending = false;
+            RT_REGION(RG_REGEN);
+            if (settle) {
+                const V3 L = pk.get3(PK_L);
+                pk.set3(PK_ACC, add(pk.get3(PK_ACC), L)); /* renderer.h:77-78 */
+                if (ACC == 2) {
+                    const double y = luminance(L);
+                    q += y * y;
+                }
+                pk.set3(PK_L, mk(0.0, 0.0, 0.0));
+                settle = false;
+            }
+            RTR_CLK(clk_shadow);
+            if (cast_a) {
+                bool ended;
+                if (a_ref < 0) {
+                    RT_REGION(RG_MISS);
+                    pk.set3(PK_L, add(pk.get3(PK_L), miss_radiance<INTEG, MS>(sc, pk.get3(PK_THR), ps.ro, ps.rd, ps.depth,
+                                                                          ps.specular_bounce, pk.get(PK_PDF))));
+                    ended = true;
+                } else {
+                    Hit rec;
+                    rec.u = 0, rec.v = 0;
+                    if (MS == RT_MS_FULL && sc.needs_uv) /* (cast_closest's hit record) */
+                        fast_finish<true>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
+                    else
+                        fast_finish<false>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
+                    ps.thr = pk.get3(PK_THR);
+                    ps.L = mk(0.0, 0.0, 0.0); /* see the split loop below: L + e is the reference's L += e */
+                    ps.prev_bsdf_pdf = pk.get(PK_PDF);
+                    const V3 wo = neg(unit(ps.rd));
+                    ShadowReq rq;
+                    const MatCtx mc = mat_prepare<MS>(sc, rec);
+                    shade_a_mis<MS, INTEG>(sc, ps, rec, mc, wo, rng, rq);
+                    if (rq.valid) { /* parked until the next pair cast */
+                        pending = true;
+                        pk.set3(PK_SWI, rq.wi);
+                        pk.set(PK_STMAX, rq.tmax);
+                        pk.set3(PK_CONTRIB, rq.contrib);
+                    }
+                    const bool go = shade_b_mis<MS, INTEG>(sc, ps, rec, mc, wo, rng, P.rr_start);
+                    RT_REGION(RG_PARK);
+                    ps.ro = rec.p; /* next ray origin and shadow ray origin */
+                    so = rec.p;
+                    pk.set3(PK_THR, ps.thr);
+                    if (ps.L.x != 0.0 || ps.L.y != 0.0 || ps.L.z != 0.0) pk.set3(PK_L, add(pk.get3(PK_L), ps.L));
+                    pk.set(PK_PDF, ps.prev_bsdf_pdf);
+                    ended = !go || ++ps.depth >= P.max_depth;
+                }
+                RTR_CLK(clk_shade);
+                RT_REGION(RG_REGEN);
+                if (ended) {
+                    settle = true;
+                    ++n_samples;
+                    ++s;
+                    done = s >= s_end || ((s & 7) == 0 && render_cancelled(P)); /* (see the split loop) */
+                    if (!done) begin_sample();
+                }
+            }
+        }
+        cnt.closest = (uint32_t)pk.get(PK_NCLOSEST);
+        cnt.shadow = (uint32_t)pk.get(PK_NSHADOW);
+#ifdef RTR_PHASE_CLOCKS
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&P.stats[3], (unsigned long long)clk_closest);
+            atomicAdd(&P.stats[4], (unsigned long long)clk_shade);
+            atomicAdd(&P.stats[5], (unsigned long long)clk_shadow);
+            atomicAdd(&P.stats[6], (unsigned long long)clk_other);
+        }
+#endif
+#undef RTR_CLK
     } else {
         /* Without media the shadow ray draws nothing, so it can be cast AFTER the BSDF sample of
          * the same bounce, when the hit record is dead.  Every live lane runs the same phases in

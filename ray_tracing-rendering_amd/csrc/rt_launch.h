@@ -24,6 +24,7 @@ struct MegaLaunch {
     int integrator, trav;
     bool lean, quadlit; /* material / light set of the scene (rtr_upload_scene) */
     bool sorted;        /* RTR_FLAG_SORTED_SHADING and a sorted instantiation exists for this launch (rt_kernels.h) */
+    bool pair;          /* the pair-cast twin of a flat MIS kernel (DScene::pair_cast, no RTR_FLAG_SPLIT_CASTS) */
     bool program_ext;   /* RT_TRAV_PROGRAM: the program holds guarded steps or media under wrappers (RT_TRAV_PROGRAM_EXT kernels) */
     int accum;          /* 0, or an accumulator pass: the k_mega<..., ACC = 1> twin of the variant, 2 with moments */
     size_t lds;         /* traversal stack + parked path state, bytes per workgroup */

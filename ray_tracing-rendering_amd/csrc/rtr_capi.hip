@@ -391,7 +391,7 @@ int params_check(rtr_context* c, const rtr_render_params* p) {
     if (p->tile_stride > 1 && (p->tile_first < 0 || p->tile_first >= p->tile_stride))
         return fail(c, RTR_ERR_INVALID, "tile_first must be in [0, tile_stride)");
     if (p->spp_chunks < 0 || p->spp_chunks > p->spp) return fail(c, RTR_ERR_INVALID, "spp_chunks must be in [0, spp]");
-    if (p->flags & ~(RTR_FLAG_REFERENCE_ORDER | RTR_FLAG_WF_PERSISTENT | RTR_FLAG_SORTED_SHADING)) return fail(c, RTR_ERR_INVALID, "unknown flag bits");
+    if (p->flags & ~(RTR_FLAG_REFERENCE_ORDER | RTR_FLAG_WF_PERSISTENT | RTR_FLAG_SORTED_SHADING | RTR_FLAG_SPLIT_CASTS)) return fail(c, RTR_ERR_INVALID, "unknown flag bits");
     if (p->pipeline < RTR_PIPELINE_AUTO || p->pipeline > RTR_PIPELINE_WAVEFRONT)
         return fail(c, RTR_ERR_INVALID, "unknown pipeline");
     return RTR_OK;
@@ -466,6 +466,9 @@ int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, b
     L.blocks_per_cu = blocks_per_cu;
     L.launched = launched;
     if (flags_in_effect && L.sorted) *flags_in_effect |= RTR_FLAG_SORTED_SHADING;
+    const bool pairable = mega_pairable(integrator, L.trav) && !L.sorted && c->ds.pair_cast;
+    L.pair = pairable && !(flags & RTR_FLAG_SPLIT_CASTS);
+    if (flags_in_effect && pairable && !L.pair) *flags_in_effect |= RTR_FLAG_SPLIT_CASTS;
     switch (integrator) {
     case RTR_INTEGRATOR_MIS: return rtr_mega_launch_mis(L, c->err);
     case RTR_INTEGRATOR_RR:
@@ -621,7 +624,8 @@ int finish_stats(rtr_context* c) {
                                           "shadow: tree leaves", "media steps", "mat_prepare", "shade_a (emission, light sample)",
                                           "shade_b (BSDF sample, roulette)", "miss", "end of sample + regeneration",
                                           "shade_rr / shade_path", "park path state", "sorted shading: barrier waits",
-                                          "sorted shading: tickets + exchange"};
+                                          "sorted shading: tickets + exchange", "pair cast: instance setup",
+                                          "pair cast: rect runs", "pair cast: sphere runs"};
         double total = 0;
         for (int k = 0; k < RG_N; ++k) total += (double)h[RT_PROF_BASE + k];
         std::fprintf(stderr, "[region profile] %.4g wave cycles in all, %llu samples\n", total, h[0]);
@@ -1019,6 +1023,21 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
     for (const FInst& I : cs.inst)
         if (I.n_xf > 30) d.shared_div = 0;
     if (getenv("RTR_NO_SHARED_DIV")) d.shared_div = 0; /* experiments: the plain divisions */
+    /* trace_pair's scenes (DScene::pair_cast): flat, lit (without lights no shadow ray is ever cast, and the pair walk
+     * would test a dummy ray against every record: scene 7, 7 515 -> 6 122 Msamples/s), few enough instances that no
+     * instance box is tested, every instance a packed scan without moving spheres, shared divisions allowed; the others
+     * keep the split casts */
+    d.pair_cast = c->flat_scene && s->n_lights > 0 && d.shared_div && d.top_root0 < 0 && d.n_finst > 0 && d.n_finst <= RT_FAST_NO_BOX_MAX;
+    for (int k = 0; k < d.n_finst && d.pair_cast; ++k) {
+        const FInst& I = cs.inst[k];
+        if (!(I.flags & RT_INST_RUNS)) d.pair_cast = 0;
+        for (uint64_t runs = I.runs; runs != 0; runs >>= RT_RUN_BITS) {
+            const int type = RTR_NODE_SPHERE + (int)((runs >> RT_RUN_COUNT_BITS) & 7);
+            if (type != RTR_NODE_SPHERE && type != RTR_NODE_XY_RECT && type != RTR_NODE_XZ_RECT && type != RTR_NODE_YZ_RECT &&
+                type != RTR_NODE_SPHERE + RT_RUN_BOX)
+                d.pair_cast = 0;
+        }
+    }
     c->info = info;
     c->n_materials = s->n_materials;
     c->lean_materials = true;

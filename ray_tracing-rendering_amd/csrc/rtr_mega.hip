@@ -41,12 +41,12 @@ int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
     return RTR_OK;
 }
 
-template <int I, int T, int M, bool S = false>
+template <int I, int T, int M, bool S = false, bool PR = false>
 int launch_rec(const MegaLaunch& L, std::string& err) {
     /* (an accumulator pass: the same variant with ACC = 1, or 2 with moments, rt_kernels.h) */
-    const int rc = L.accum == 2 ? launch_one(k_mega<I, T, M, S, 2>, L, err)
-                   : L.accum    ? launch_one(k_mega<I, T, M, S, 1>, L, err)
-                                : launch_one(k_mega<I, T, M, S>, L, err);
+    const int rc = L.accum == 2 ? launch_one(k_mega<I, T, M, S, 2, PR>, L, err)
+                   : L.accum    ? launch_one(k_mega<I, T, M, S, 1, PR>, L, err)
+                                : launch_one(k_mega<I, T, M, S, 0, PR>, L, err);
     if (rc == RTR_OK && !L.dry && L.launched) {
         L.launched->trav = T;
         L.launched->ms = M;
@@ -56,6 +56,13 @@ int launch_rec(const MegaLaunch& L, std::string& err) {
 }
 
 #define RTR_LAUNCH(I, T, M) return launch_rec<I, T, M>(L, err)
+/* the flat MIS kernels: the pair-cast twin where the scene allows it (MegaLaunch::pair) */
+#define RTR_LAUNCH_FLAT(I, M)                                                                                               \
+    do {                                                                                                                    \
+        if constexpr (mega_pairable(I, RT_TRAV_FLAT))                                                                       \
+            if (L.pair) return launch_rec<I, RT_TRAV_FLAT, M, false, mega_pairable(I, RT_TRAV_FLAT)>(L, err);               \
+        RTR_LAUNCH(I, RT_TRAV_FLAT, M);                                                                                     \
+    } while (0)
 
 /* integrators 1 and 4: every traversal, material-set variants.  FULLQ = the variant for "every material,
  * QuadLights only" (the RR integrator has no light code) */
@@ -63,13 +70,13 @@ template <int I, int FULLQ>
 int launch_t(const MegaLaunch& L, std::string& err) {
     const int trav = L.trav;
     if (trav == RT_TRAV_FLAT) {
-        if (L.lean) RTR_LAUNCH(I, RT_TRAV_FLAT, RT_MS_LEAN);
+        if (L.lean) RTR_LAUNCH_FLAT(I, RT_MS_LEAN);
         if (L.quadlit) {
             if (mega_sortable(I, RT_TRAV_FLAT, FULLQ) && L.sorted)
                 return launch_rec<I, RT_TRAV_FLAT, FULLQ, mega_sortable(I, RT_TRAV_FLAT, FULLQ)>(L, err);
-            RTR_LAUNCH(I, RT_TRAV_FLAT, FULLQ);
+            RTR_LAUNCH_FLAT(I, FULLQ);
         }
-        RTR_LAUNCH(I, RT_TRAV_FLAT, RT_MS_FULL);
+        RTR_LAUNCH_FLAT(I, RT_MS_FULL);
     }
     if (trav == RT_TRAV_FLAT_GUARD) {
         if (L.quadlit) RTR_LAUNCH(I, RT_TRAV_FLAT_GUARD, FULLQ);
