@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the integrator loop on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Headline = BASELINE.json's metric: Msamples/s of the Cornell box 800x800, spp 400, depth 50, MIS
@@ -12,7 +12,8 @@ device framebuffer and, after the timed region, sends the tiles it owns (nothing
 (SURVEY 8e).  Total work is fixed as N grows ("strong" scaling on the named config).
 
 Rank 0 prints ONE JSON line.  `value` is whole-job Msamples/s = W*H*spp*K / max-over-ranks seconds,
-with scene and framebuffer resident in HBM.  At N = 1 the same run also
+with scene and framebuffer resident in HBM.  A plain run times the main workload and nothing else.  With `--full`
+at N = 1 the same run also
   * times every other BASELINE configuration (`extra`: scene07/i4 literal, scene09/i1, scene22/i4,
     scene23/i4 1080p spp 1024, and ONE rank's eighth of C5 = scene21 4096x4096 spp 4096), each with
     its own roofline and cpu_baseline;
@@ -277,30 +278,52 @@ def roofline(name, pipe_name, counts, samples, closest, shadow, kernel_ms, n_gpu
     return r
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3, help="timed steps (renders) of the main workload")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the image of the last timed step of the main workload to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="at N = 1 also time every other BASELINE config, check full-spp crops against the oracle "
+                         "(`parity`) and time the reference on the host cores (`cpu_baseline`)")
     ap.add_argument("--workload", default=HEADLINE, choices=sorted(WORKLOADS), help="the line's main workload")
     ap.add_argument("--extras", default=None,
                     help="comma list of further workloads timed in the same run ('none'; default: every other "
-                         "BASELINE config when the main workload is the headline and N = 1)")
+                         "BASELINE config with --full when the main workload is the headline and N = 1)")
     ap.add_argument("--extra-steps", type=int, default=2)
     ap.add_argument("--extra-warmup", type=int, default=1)
     ap.add_argument("--pipeline", default="auto", choices=["auto", "mega", "wavefront"])
     ap.add_argument("--sorted-shading", action="store_true",
                     help="experiment: RTR_FLAG_SORTED_SHADING on the timed renders (invalidates the headline)")
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (invalidates the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the full-spp crop check against the oracle")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the full-spp crop check against the oracle")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N>1 (gloo + RTR_BENCH_ONE_GPU=1 rehearses the N>1 path on one GPU)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.extra_steps < 1 or args.warmup < 0 or args.extra_warmup < 0:
         ap.error("--steps and --extra-steps must be >= 1, --warmup and --extra-warmup >= 0")
+    return args
+
+
+def run_plan(args, world):
+    """What the run does besides timing its main workload: (further workloads, cpu_baseline?, parity?).  A plain run
+    does none of it, so that its headline line costs set-up, warm-up and the timed steps alone; --full (N = 1) adds
+    the other BASELINE configs, the oracle crops and the CPU baseline.  An explicit --extras list is timed either way."""
+    full = args.full and world == 1
+    if args.extras is None:
+        extras = list(EXTRAS) if (full and args.workload == HEADLINE and not args.spp) else []
+    elif args.extras == "none":
+        extras = []
+    else:
+        extras = [e for e in args.extras.split(",") if e]
+    return extras, full and not args.no_cpu_baseline, full and not args.no_parity
+
+
+def main():
+    args = parse_args()
 
     import numpy as np
     import torch
@@ -436,19 +459,13 @@ def main():
             line["speedup_vs_cpu"] = round(value / line["cpu_baseline"]["value"], 2)
         return line
 
-    single = world == 1
-    extras = []
-    if args.extras is None:
-        extras = EXTRAS if (single and args.workload == HEADLINE and not args.spp) else []
-    elif args.extras != "none":
-        extras = [e for e in args.extras.split(",") if e]
-    line = run(args.workload, args.steps, args.warmup, single and not args.no_cpu_baseline,
-               single and not args.no_parity, args.dump_outputs)
+    extras, with_cpu, with_parity = run_plan(args, world)
+    line = run(args.workload, args.steps, args.warmup, with_cpu, with_parity, args.dump_outputs)
     if rank == 0 and counts_file:
         line["counts_file"] = "profiles/" + counts_file
     subs = []
     for e in extras:
-        sub = run(e, args.extra_steps, args.extra_warmup, single and not args.no_cpu_baseline, single and not args.no_parity)
+        sub = run(e, args.extra_steps, args.extra_warmup, with_cpu, with_parity)
         if sub is not None:
             subs.append(sub)
     if rank == 0:

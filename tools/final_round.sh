@@ -1,10 +1,12 @@
 #!/bin/bash
 # tools/final_round.sh <tag>: the measurements of a round that are not counter passes (run on the GPU box from the repo root,
 # after tools/profile_round.sh <tag> has written profiles/<tag>_counts.json for the same sources):
-#   the default bench line, the many-instance and hollow-sphere scenes, the region profiles (-DRTR_REGION_PROFILE variant)
+#   the bench.py --full line (build/bench_<tag>.json), the many-instance and hollow-sphere scenes, the region profiles (-DRTR_REGION_PROFILE variant)
 tag=${1:-r03}
 mkdir -p gpurun_out
-timeout -k 10 900 python bench.py > gpurun_out/bench_${tag}.json 2> gpurun_out/bench_${tag}.err; echo "bench rc=$?"
+bench=build/bench_${tag}
+mkdir -p build
+timeout -k 10 900 python bench.py --full > $bench.json 2> $bench.err; echo "bench rc=$?"
 for spp in 16 64; do
   echo "== tools/time_random.py, 640x360, spp $spp"
   SPP=$spp timeout -k 10 300 python tools/time_random.py 2>&1 | grep objects
@@ -20,7 +22,7 @@ export RTR_HIP_LIBRARY=$(pwd)/ray_tracing-rendering_amd/variants/librtr_hip_prof
  timeout -k 10 300 python tools/bench_scenes.py 2>&1 | awk '/wave cycles in all/ {last = ""} /region profile\]/ {last = last $0 "\n"} /^scene/ {printf "%s%s\n", last, $0; last = ""}') > gpurun_out/${tag}_scene_regions.txt
 tail -3 gpurun_out/${tag}_time_random.txt; cat gpurun_out/${tag}_bench_scenes.txt; python - <<PY
 import json
-for l in open("gpurun_out/bench_${tag}.json"):
+for l in open("$bench.json"):
     j = json.loads(l)
     print(j["metric"], j["value"], j["roofline"]["frac"], j["roofline"].get("stale"), j["parity_ok"], j["cpu_baseline"]["value"])
     for e in j["extra"]:
