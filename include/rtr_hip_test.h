@@ -46,8 +46,9 @@ int rtr_test_stream8(rtr_context* ctx, int64_t n_doubles, int repeat);
 
 /* The samplers take sin and cos of phi = 2 pi r for r = s * 2^-32, s any state of the 32-bit generator
  * (vec3.h:261-269, material.h:268-275); the device evaluates both with ONE sincos().  This walks ALL 2^32 values of
- * s and counts those where sincos(phi) and the pair sin(phi), cos(phi) differ in any bit: *mismatches must be 0. */
-int rtr_test_sincos_exhaustive(rtr_context* ctx, uint64_t* mismatches);
+ * s and counts those where sincos(phi) and the pair sin(phi), cos(phi) differ in any bit: *mismatches must be 0.
+ * *tested: the values of s the kernel compared, 2^32 when it walked them all. */
+int rtr_test_sincos_exhaustive(rtr_context* ctx, uint64_t* mismatches, uint64_t* tested);
 
 /* Measured issue costs for bench.py's `valu_slot_utilisation`: shader cycles a wave spends per instruction of one class
  * while four waves share each SIMD (so a pipe-bound class reads four times its pipe cost), classes in this order:
@@ -59,8 +60,9 @@ int rtr_test_issue_rates(rtr_context* ctx, double* cycles_per_inst, int n);
 
 /* The primitive tests divide many numerators by the same ray-direction component through a shared refined reciprocal
  * (rt_device.h: div_shared) instead of the compiler's eleven-instruction division.  This compares the two on 2^32
- * operand pairs from the range the short form is used in; *mismatches (quotients that differ in any bit) must be 0. */
-int rtr_test_shared_division(rtr_context* ctx, uint64_t* mismatches);
+ * operand pairs from the range the short form is used in; *mismatches (quotients that differ in any bit) must be 0.
+ * *tested: the pairs the kernel compared, 2^32 when every pair drawn was in that range. */
+int rtr_test_shared_division(rtr_context* ctx, uint64_t* mismatches, uint64_t* tested);
 
 #ifdef __cplusplus
 }

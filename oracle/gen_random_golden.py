@@ -32,6 +32,8 @@ CASES = [(11, {}), (13, dict(n_objects=90)), (14, dict(media=True)), (15, dict(m
          (16, dict(hollow=True)), (17, dict(n_objects=8, ties=True)), (18, dict(media=True, hollow=True)),
          (19, dict(n_objects=200)), (27, dict(delta_lights=True)), (28, dict(delta_lights=True, media=True)),
          (32, dict(moved_media=True)), (33, dict(moved_media=True, media=True, n_objects=50)),
+         # several hollow spheres without a bvh_node: nothing above them to test
+         (2, dict(spheres_only=True, n_objects=20, hollow_lists=3, hollow_pairs=2)),
          # the material palettes of the kernel-variant tests: lean with a top tree over its instances, QuadLights-only
          # materials with media in the middle of the visiting order
          (54, dict(n_objects=200, palette="lean")), (64, dict(media=True, palette="quadlit"))]
@@ -41,7 +43,15 @@ W, H, SPP, N_RAYS = 48, 32, 4, 512
 BVH_CASES = [(13, dict(n_objects=90)), (15, dict(media=True, n_objects=60)), (16, dict(hollow=True)),
              (18, dict(media=True, hollow=True)), (19, dict(n_objects=200)), (23, dict(media=True, n_objects=100)),
              (26, dict(n_objects=30, hollow=True)), (28, dict(delta_lights=True, media=True)),
-             (32, dict(moved_media=True)), (33, dict(moved_media=True, media=True, n_objects=50))]
+             (32, dict(moved_media=True)), (33, dict(moved_media=True, media=True, n_objects=50)),
+             # several hollow spheres under the tree: nested lists of them next to solid spheres only (3b, 5b) and next
+             # to transformed boxes (1b); hollow-in-glass pairs and bare ones straight under bvh_nodes (4b)
+             (4, dict(spheres_only=True, n_objects=20, hollow_pairs=4, bare_hollows=2)),
+             (1, dict(n_objects=20, hollow_lists=4)), (3, dict(spheres_only=True, n_objects=20, hollow_lists=4)),
+             (5, dict(spheres_only=True, n_objects=20, hollow_lists=4))]
+# fixtures whose rays are first those on which the two rules for the boxes above a hollow sphere disagree (the oracle's
+# rto_hits and rto_hits_running_guard, tests/_randscene.py: discriminating_rays), then random_rays as everywhere else
+DISCRIMINATED = {"01b", "02", "03b", "04b", "05b"}
 
 
 def sha(path):
@@ -82,11 +92,16 @@ def main(tags=()):
                  (["ref_harness", "wrap-bvh", "<that scene>", str(777 + seed), "random_%s.rtrs" % tag] if wrap else []), {},
                  raw_sha256=sha(raw))
             rays = os.path.join(td, "rays.bin")
-            R.random_rays(seed, N_RAYS).tofile(rays)
+            if tag in DISCRIMINATED:
+                R.discriminating_rays(R.rtr.Scene.load(raw), seed, N_RAYS).tofile(rays)
+                ray_argv = "discriminating_rays(random_%s, %d, %d)" % (tag, seed, N_RAYS)
+            else:
+                R.random_rays(seed, N_RAYS).tofile(rays)
+                ray_argv = "random_rays(%d, %d)" % (seed, N_RAYS)
             name = "random_%s_hits.bin" % tag
             out = subprocess.run([HARNESS, "hits-rtrs", raw, rays, os.path.join(GOLD, name)], check=True,
                                  stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode()
-            note(name, ["ref_harness", "hits-rtrs", "random_%s.rtrs" % tag, "random_rays(%d, %d)" % (seed, N_RAYS), name],
+            note(name, ["ref_harness", "hits-rtrs", "random_%s.rtrs" % tag, ray_argv, name],
                  json.loads(out.strip().splitlines()[-1]), scene="random_%s" % tag)
             for integ in (1, 4):
                 name = "random_%s_i%d.f64" % (tag, integ)

@@ -333,6 +333,85 @@ bool hit_node(const Scene& sc, int ix, const Ray& r, double t_min, double t_max,
     }
 }
 
+/* ---- NOT the reference: the device's rule for hollow spheres, as a discriminator for tests ------------------------
+ * hit_node tests every bvh_node box with the t_max that node was ENTERED with (bvh.h:40-50).  The device's guarded
+ * references (RT_GUARD_FLAG, FStep kind 3) instead test all bvh_node boxes above a hollow sphere (negative radius)
+ * with the RUNNING t_max at the sphere's visit.  This walk restates that rule: it descends every bvh_node without
+ * testing its box, keeps the boxes above the current node (each with the ray of its own frame), and tests them all
+ * with the closest t so far when it meets a hollow sphere.  Other nodes are walked as in hit_node; a constant_medium
+ * is handed to hit_node whole.  Rays on which the two walks differ are the ones that separate the two rules. */
+struct GuardBox {
+    const double* box;
+    Ray r;
+};
+
+bool hit_node_running_guard(const Scene& sc, int ix, const Ray& r, double t_min, double t_max, Rec& rec, Rng& g,
+                            std::vector<GuardBox>& above) {
+    const rtr_node& n = sc.d->nodes[ix];
+    switch (n.type) {
+    case RTR_NODE_BVH: {
+        above.push_back(GuardBox{n.f, r});
+        bool hit_left = hit_node_running_guard(sc, n.a, r, t_min, t_max, rec, g, above);
+        bool hit_right = hit_node_running_guard(sc, n.b, r, t_min, hit_left ? rec.t : t_max, rec, g, above);
+        above.pop_back();
+        return hit_left || hit_right;
+    }
+    case RTR_NODE_LIST: {
+        Rec temp;
+        temp.u = temp.v = std::numeric_limits<double>::quiet_NaN();
+        bool hit_anything = false;
+        double closest = t_max;
+        for (int k = 0; k < n.b; ++k) {
+            if (hit_node_running_guard(sc, sc.d->list_children[n.a + k], r, t_min, closest, temp, g, above)) {
+                hit_anything = true;
+                closest = temp.t;
+                rec = temp;
+            }
+        }
+        return hit_anything;
+    }
+    case RTR_NODE_TRANSLATE: {
+        V3 off = ld(n.f);
+        Ray moved = make_ray(sub(r.o, off), r.d, r.tm);
+        if (!hit_node_running_guard(sc, n.a, moved, t_min, t_max, rec, g, above)) return false;
+        rec.p = add(rec.p, off);
+        set_face_normal(rec, moved, rec.normal);
+        return true;
+    }
+    case RTR_NODE_ROTATE_Y: {
+        double s = n.f[0], c = n.f[1];
+        V3 o = r.o, d = r.d;
+        o.x = c * r.o.x - s * r.o.z;
+        o.z = s * r.o.x + c * r.o.z;
+        d.x = c * r.d.x - s * r.d.z;
+        d.z = s * r.d.x + c * r.d.z;
+        Ray rot = make_ray(o, d, r.tm);
+        if (!hit_node_running_guard(sc, n.a, rot, t_min, t_max, rec, g, above)) return false;
+        V3 p = rec.p, nn = rec.normal;
+        p.x = c * rec.p.x + s * rec.p.z;
+        p.z = -s * rec.p.x + c * rec.p.z;
+        nn.x = c * rec.normal.x + s * rec.normal.z;
+        nn.z = -s * rec.normal.x + c * rec.normal.z;
+        rec.p = p;
+        set_face_normal(rec, rot, nn);
+        return true;
+    }
+    case RTR_NODE_FLIP_FACE:
+        if (!hit_node_running_guard(sc, n.a, r, t_min, t_max, rec, g, above)) return false;
+        rec.front_face = !rec.front_face;
+        return true;
+    case RTR_NODE_SPHERE:
+    case RTR_NODE_MOVING_SPHERE: {
+        const bool moving = n.type == RTR_NODE_MOVING_SPHERE;
+        if ((moving ? n.f[8] : n.f[3]) < 0)
+            for (const GuardBox& b : above)
+                if (!aabb_hit(b.box, b.r, t_min, t_max)) return false;
+        return sphere_hit(n, moving, r, t_min, t_max, rec);
+    }
+    default: return hit_node(sc, ix, r, t_min, t_max, rec, g);
+    }
+}
+
 /* ---- materials/perlin.h:21-111 ------------------------------------------------- */
 inline double perlin_noise(const rtr_perlin& pn, V3 p) { /* perlin.h:21-39,95-111 */
     double u = p.x - std::floor(p.x);
@@ -1333,6 +1412,38 @@ int rto_hits(const rtr_scene_desc* scene, rtr_hit_record* recs, int64_t n) {
         rec.u = rec.v = std::numeric_limits<double>::quiet_NaN();
         rec.mat = -1;
         bool h = hit_node(sc, scene->root, r, o.t_min, o.t_max, rec, g);
+        o.rng_out = g.s;
+        o.hit = h;
+        o.front_face = 0, o.material = -1, o.pad = 0;
+        o.t = 0, o.u = 0, o.v = 0;
+        for (int c = 0; c < 3; ++c) o.p[c] = o.n[c] = 0;
+        if (h) {
+            o.front_face = rec.front_face;
+            o.material = rec.mat;
+            o.t = rec.t;
+            o.p[0] = rec.p.x, o.p[1] = rec.p.y, o.p[2] = rec.p.z;
+            o.n[0] = rec.normal.x, o.n[1] = rec.normal.y, o.n[2] = rec.normal.z;
+            o.u = rec.u, o.v = rec.v;
+        }
+    }
+    return RTR_OK;
+}
+
+/* rto_hits under the device's running-t_max guard rule (hit_node_running_guard): NOT the reference, a discriminator.
+ * Records are written the same way; where they differ from rto_hits the two rules disagree on that ray. */
+int rto_hits_running_guard(const rtr_scene_desc* scene, rtr_hit_record* recs, int64_t n) {
+    if (!scene || !recs) return RTR_ERR_INVALID;
+    Scene sc{scene};
+    std::vector<GuardBox> above;
+    for (int64_t k = 0; k < n; ++k) {
+        rtr_hit_record& o = recs[k];
+        Ray r = make_ray(ld(o.o), ld(o.d), o.time);
+        Rng g{o.rng_in};
+        Rec rec;
+        rec.u = rec.v = std::numeric_limits<double>::quiet_NaN();
+        rec.mat = -1;
+        above.clear();
+        bool h = hit_node_running_guard(sc, scene->root, r, o.t_min, o.t_max, rec, g, above);
         o.rng_out = g.s;
         o.hit = h;
         o.front_face = 0, o.material = -1, o.pad = 0;

@@ -104,15 +104,21 @@ struct Builder {
     bool too_complex = false;
     /* Guard mode: a graph with hollow spheres (negative radius: inverted bounding box, sphere.h:62-66) and nothing else
      * that depends on the visiting order.  The reference reaches such a sphere only through rays that pass the boxes of
-     * the bvh_nodes above it within [t_min, closest t so far] (bvh.h:40-50).  If everything sits under ONE transform
-     * chain (the empty one) and is scanned linearly, the scan order IS the reference's visiting order, so the running
-     * t_max at the sphere's reference is the reference's "closest so far" and the box tests can be run right there
-     * (RT_GUARD_FLAG).  Anything else (several instances, too many references for a linear scan, a shared object whose
-     * visits lie on both sides of a hollow sphere) makes run() fail: the caller falls back to the step program. */
+     * the bvh_nodes above it, each within [t_min, closest t so far when that node was ENTERED] (bvh.h:40-50).  If
+     * everything sits under ONE transform chain (the empty one) and is scanned linearly, the scan order IS the
+     * reference's visiting order, and the box tests are run right at the sphere's reference with the RUNNING t_max
+     * (RT_GUARD_FLAG).  That is the same test as long as no hit between a node's entry and the sphere lies outside
+     * the node's box: hits of solid primitives lie inside it, only an earlier hollow sphere under the same node can.
+     * If the deepest bvh_node above the sphere holds no other hollow sphere visited earlier, its box gives the
+     * reference's answer, and every box further up contains it, so it passes where that one passes; otherwise
+     * (hollows_under) the rule could reject a ray the reference lets through.  That, and anything else (several
+     * instances, too many references for a linear scan, a shared object whose visits lie on both sides of a hollow
+     * sphere) makes run() fail: the caller falls back to the step program. */
     bool guard_mode = false, guard_fail = false;
     int hollows_seen = 0;
     std::vector<int> bvh_stack;
     std::map<std::pair<int, std::vector<uint64_t>>, int> hollows_at_first_visit;
+    std::map<int, std::set<int>> hollows_under; /* bvh_node -> the hollow spheres visited under it so far */
     static constexpr int kGuardLinearMax = 256;
 
     static uint64_t bits(double v) {
@@ -217,6 +223,11 @@ struct Builder {
                 if (hollow) {
                     ++hollows_seen;
                     if (!chain.empty() || n.type != RTR_NODE_SPHERE) guard_fail = true; /* boxes above a transform; f[] full */
+                    if (!bvh_stack.empty()) {
+                        const std::set<int>& under = hollows_under[bvh_stack.back()];
+                        if (under.size() > under.count(ix)) guard_fail = true; /* another hollow sphere, no box between */
+                    }
+                    for (int b : bvh_stack) hollows_under[b].insert(ix);
                 }
             }
             const std::vector<uint64_t> key = chain_key();
@@ -782,11 +793,19 @@ inline CompiledScene compile_scene(const rtr_scene_desc* scene, bool has_media, 
             cs.steps.push_back(st);
         };
         const size_t guard_mark = cs.guards.size();
+        /* per bvh_node visit (`chain`): the hollow spheres met under it so far.  A guarded step tests the boxes above its
+         * sphere with the running t_max, which is the reference's test unless another hollow sphere under the deepest
+         * of those nodes came first (Builder::guard_mode): then the reference-order walk */
+        std::vector<std::vector<int>> hollows_under(chain.size());
         for (size_t k = 0; k < items.size() && possible; ++k) {
             const rtr_node& n = scene->nodes[items[k]];
             if (n.type == RTR_NODE_SPHERE || n.type == RTR_NODE_MOVING_SPHERE) {
                 const bool hollow = (n.type == RTR_NODE_SPHERE && n.f[3] < 0) || (n.type == RTR_NODE_MOVING_SPHERE && n.f[8] < 0);
                 if (hollow) { /* a guarded step of its own (FStep kind 3) */
+                    if (item_chain[k] >= 0) /* (bvh_node with left = right: the same sphere twice, which cannot hit twice) */
+                        for (int h : hollows_under[item_chain[k]]) possible = possible && h == items[k];
+                    for (int c = item_chain[k]; c >= 0; c = chain[c].up) hollows_under[c].push_back(items[k]);
+                    if (!possible) break;
                     flush();
                     if (!possible) break;
                     rtc::Builder b(cs);

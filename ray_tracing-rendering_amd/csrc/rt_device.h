@@ -927,8 +927,10 @@ RT_DEV bool fast_prim_hit(const rtr_node& n, V3 o, V3 d, const RayDiv& q, Real t
 /* References behind box tests of the reference's bvh_nodes (RT_GUARD_FLAG): a sphere with a negative radius -- hollow
  * glass, scenes.cpp:903 -- has an inverted bounding box (sphere.h:62-66), the boxes of the bvh_nodes above it do not
  * enclose it, and bvh_node::hit (bvh.h:40-50) lets a ray through to it only if every one of them is hit within
- * [t_min, closest t so far] (aabb.h:31-48, with ray.h's 1 / d).  In a sub-scene scanned in the reference's visiting
- * order the running t_max IS that "closest so far" (rt_compile.h: guard_mode). */
+ * [t_min, closest t so far when that node was entered] (aabb.h:31-48, with ray.h's 1 / d).  guard_pass tests them all
+ * with the running t_max at the sphere's visit instead, in a sub-scene scanned in the reference's visiting order.  The
+ * two agree unless another hollow sphere under the deepest of those nodes was hit first, outside its box; upload sends
+ * such scenes to the reference-order walk (rt_compile.h: guard_mode, and the guarded steps, FStep kind 3). */
 #define RT_GUARD_FLAG (1 << 29) /* in rtr_node::reserved / FLeaf::tag of a reference, next to RT_TIE_FLAG */
 RT_DEV bool guard_pass(const DScene& sc, int first, int count, V3 o, V3 d, Real tmin, Real tmax) {
     const V3 inv = mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
@@ -1805,7 +1807,7 @@ __device__ __forceinline__ bool run_program(const DScene& sc, V3 o, V3 d, Real t
         const FSub sub = ld_const(sc.fsub, step.sub);
         const bool medium = step.kind == 1;
         bool enter = true;
-        if (EXT && step.kind == 3) { /* the bvh_node::hit calls above the primitive, with the closest t so far */
+        if (EXT && step.kind == 3) { /* the bvh_node::hit calls above the primitive, with the running t_max (RT_GUARD_FLAG) */
             enter = guard_pass(sc, step.pad, step.mat, o, d, tmin, tmax);
             if (!__any(enter)) continue;
         }

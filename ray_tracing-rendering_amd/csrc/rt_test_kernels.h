@@ -88,8 +88,9 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_lights(const DScene sc, rtr_
 }
 
 /* rtr_test_stream8: 8 bytes per lane in, 8 bytes per lane out */
-__global__ void __launch_bounds__(RTR_BLOCK) k_test_sincos(unsigned long long* mismatches) {
-    unsigned long long bad = 0;
+/* out[0] += angles whose sincos differs from sin, cos; out[1] += angles tested */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_sincos(unsigned long long* out) {
+    unsigned long long bad = 0, tested = 0;
     const unsigned long long stride = (unsigned long long)gridDim.x * RTR_BLOCK;
     for (unsigned long long s = (unsigned long long)blockIdx.x * RTR_BLOCK + threadIdx.x; s < (1ull << 32); s += stride) {
         const Real phi = 2.0 * RT_PI * ((uint32_t)s * 2.3283064365386963e-10); /* as random_cosine_direction / pbr_sample */
@@ -97,9 +98,12 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_sincos(unsigned long long* m
         sincos(phi, &s2, &c2);
         const Real s1 = sin(phi), c1 = cos(phi);
         bad += (__double_as_longlong(s1) != __double_as_longlong(s2)) | (__double_as_longlong(c1) != __double_as_longlong(c2));
+        ++tested;
     }
     bad = wave_sum(bad);
-    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(mismatches, bad);
+    tested = wave_sum(tested);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, bad);
+    if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
 }
 
 /* rtr_test_shared_division: div_shared() against the compiler's n / d on 2^32 operand pairs.  Three quarters of them
@@ -107,7 +111,8 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_sincos(unsigned long long* m
  * random mantissas and signs); the rest are shaped like the rectangle test's (k - o) / d: a difference of two
  * coordinates below 1000 over a direction component in (-1, 1), small values of both included.  Quotients of
  * numerators below 2^-300 are only required to stay below 2^-200 (see div_shared). */
-__global__ void __launch_bounds__(RTR_BLOCK) k_test_shared_div(unsigned long long* mismatches, unsigned per_thread) {
+/* out[0] += quotients that differ; out[1] += operand pairs tested */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_shared_div(unsigned long long* out, unsigned per_thread) {
     unsigned long long x = 0x9E3779B97F4A7C15ull * ((unsigned long long)blockIdx.x * RTR_BLOCK + threadIdx.x + 1);
     auto next = [&]() {
         x ^= x >> 12, x ^= x << 25, x ^= x >> 27;
@@ -119,7 +124,7 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_shared_div(unsigned long lon
         const double m = __longlong_as_double((u & 0x800FFFFFFFFFFFFFull) | 0x3FF0000000000000ull);
         return ldexp(m, e);
     };
-    unsigned long long bad = 0;
+    unsigned long long bad = 0, tested = 0;
     for (unsigned k = 0; k < per_thread; ++k) {
         double n, d;
         if (k & 3) {
@@ -139,9 +144,12 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_shared_div(unsigned long lon
             bad += !(__builtin_fabs(t) < 0x1p-200) || !(__builtin_fabs(ref) < 0x1p-200);
         const double g = div_shared<true>(n, d, r, true); /* guarded: every numerator */
         bad += __double_as_longlong(g) != __double_as_longlong(ref);
+        ++tested;
     }
     bad = wave_sum(bad);
-    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(mismatches, bad);
+    tested = wave_sum(tested);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, bad);
+    if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
 }
 
 /* rtr_test_issue_rates: shader cycles per wave-instruction, one instruction class per launch.  Every wave runs

@@ -196,20 +196,22 @@ int rtr_test_stream8(rtr_context* c, int64_t n_doubles, int repeat) {
     return RTR_OK;
 }
 
-int rtr_test_sincos_exhaustive(rtr_context* c, uint64_t* mismatches) {
-    if (!c || !mismatches) return RTR_ERR_INVALID;
+int rtr_test_sincos_exhaustive(rtr_context* c, uint64_t* mismatches, uint64_t* tested) {
+    if (!c || !mismatches || !tested) return RTR_ERR_INVALID;
     hipStream_t stream;
     int n_cus;
     TestState* t;
     int rc = bare(c, stream, n_cus, t);
     if (rc) return rc;
-    if ((rc = ensure(c, *t, 8))) return rc;
-    TCHK(c, hipMemsetAsync(t->buf, 0, 8, stream));
+    if ((rc = ensure(c, *t, 16))) return rc;
+    TCHK(c, hipMemsetAsync(t->buf, 0, 16, stream));
     hipLaunchKernelGGL(k_test_sincos, dim3((unsigned)(n_cus * 16)), dim3(RTR_BLOCK), 0, stream, static_cast<unsigned long long*>(t->buf));
     TCHK(c, hipGetLastError());
-    unsigned long long h = 0;
-    TCHK(c, hipMemcpy(&h, t->buf, 8, hipMemcpyDeviceToHost));
-    *mismatches = h;
+    /* (the context's stream is non-blocking: the null-stream copy below does not wait for it) */
+    TCHK(c, hipStreamSynchronize(stream));
+    unsigned long long h[2] = {0, 0};
+    TCHK(c, hipMemcpy(h, t->buf, 16, hipMemcpyDeviceToHost));
+    *mismatches = h[0], *tested = h[1];
     return RTR_OK;
 }
 
@@ -234,6 +236,7 @@ int rtr_test_issue_rates(rtr_context* c, double* cycles_per_inst, int n) {
         }
 #undef RTR_RATE
         TCHK(c, hipGetLastError());
+        TCHK(c, hipStreamSynchronize(stream));
         unsigned long long h[2] = {0, 0};
         TCHK(c, hipMemcpy(h, d, 16, hipMemcpyDeviceToHost));
         cycles_per_inst[k] = h[1] ? (double)h[0] / (double)h[1] / (32.0 * iters * (k == 12 || k == 15 || k == 17 ? 2 : (k == 16 ? 4 : 1))) : 0.0;
@@ -241,21 +244,22 @@ int rtr_test_issue_rates(rtr_context* c, double* cycles_per_inst, int n) {
     return RTR_OK;
 }
 
-int rtr_test_shared_division(rtr_context* c, uint64_t* mismatches) {
-    if (!c || !mismatches) return RTR_ERR_INVALID;
+int rtr_test_shared_division(rtr_context* c, uint64_t* mismatches, uint64_t* tested) {
+    if (!c || !mismatches || !tested) return RTR_ERR_INVALID;
     hipStream_t stream;
     int n_cus;
     TestState* t;
     int rc = bare(c, stream, n_cus, t);
     if (rc) return rc;
-    if ((rc = ensure(c, *t, 8))) return rc;
-    TCHK(c, hipMemsetAsync(t->buf, 0, 8, stream));
+    if ((rc = ensure(c, *t, 16))) return rc;
+    TCHK(c, hipMemsetAsync(t->buf, 0, 16, stream));
     const unsigned blocks = 4096, per_thread = (unsigned)((1ull << 32) / ((unsigned long long)blocks * RTR_BLOCK));
     hipLaunchKernelGGL(k_test_shared_div, dim3(blocks), dim3(RTR_BLOCK), 0, stream, static_cast<unsigned long long*>(t->buf), per_thread);
     TCHK(c, hipGetLastError());
-    unsigned long long h = 0;
-    TCHK(c, hipMemcpy(&h, t->buf, 8, hipMemcpyDeviceToHost));
-    *mismatches = h;
+    TCHK(c, hipStreamSynchronize(stream));
+    unsigned long long h[2] = {0, 0};
+    TCHK(c, hipMemcpy(h, t->buf, 16, hipMemcpyDeviceToHost));
+    *mismatches = h[0], *tested = h[1];
     return RTR_OK;
 }
 

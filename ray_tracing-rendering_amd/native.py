@@ -129,9 +129,9 @@ def test_lib():
     T.rtr_test_li.argtypes = [vp, C.POINTER(A.RenderParamsC), vp, C.c_int64]
     T.rtr_test_reference_order.argtypes = [vp, C.c_int]
     T.rtr_test_stream8.argtypes = [vp, C.c_int64, C.c_int]
-    T.rtr_test_sincos_exhaustive.argtypes = [vp, C.POINTER(C.c_uint64)]
+    T.rtr_test_sincos_exhaustive.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_issue_rates.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
-    T.rtr_test_shared_division.argtypes = [vp, C.POINTER(C.c_uint64)]
+    T.rtr_test_shared_division.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
     _TEST_LIB = T
     return T
@@ -316,11 +316,16 @@ class Context:
         """Counter calibration: stream n_doubles doubles in and out, 8 bytes per lane (include/rtr_hip_test.h)."""
         self._chk(test_lib().rtr_test_stream8(self._h, int(n_doubles), int(repeat)))
 
+    def sincos_exhaustive(self):
+        """All 2^32 sampler angles: (how many give sincos(phi) != (sin(phi), cos(phi)) in some bit, how many the kernel
+        compared) (include/rtr_hip_test.h)."""
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        self._chk(test_lib().rtr_test_sincos_exhaustive(self._h, C.byref(n), C.byref(tested)))
+        return int(n.value), int(tested.value)
+
     def sincos_mismatches(self):
         """All 2^32 sampler angles: how many give sincos(phi) != (sin(phi), cos(phi)) in some bit (include/rtr_hip_test.h)."""
-        n = C.c_uint64(0)
-        self._chk(test_lib().rtr_test_sincos_exhaustive(self._h, C.byref(n)))
-        return int(n.value)
+        return self.sincos_exhaustive()[0]
 
     ISSUE_CLASSES = ("v_fma_f64", "v_add_f64", "v_mul_f64", "v_rcp_f64", "v_rsq_f64", "v_cmp_lt_f64", "v_cndmask_b32",
                      "v_mov_b32", "v_fma_f32", "s_and_b64", "v_div_scale_f64", "v_div_fixup_f64", "v_cmp_f64+s_and_b64",
@@ -333,11 +338,16 @@ class Context:
         self._chk(test_lib().rtr_test_issue_rates(self._h, out, len(self.ISSUE_CLASSES)))
         return dict(zip(self.ISSUE_CLASSES, [float(x) for x in out]))
 
+    def shared_division_exhaustive(self):
+        """2^32 operand pairs: (how many quotients of the shared-reciprocal division differ from n / d, how many pairs the
+        kernel compared) (include/rtr_hip_test.h)."""
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        self._chk(test_lib().rtr_test_shared_division(self._h, C.byref(n), C.byref(tested)))
+        return int(n.value), int(tested.value)
+
     def shared_division_mismatches(self):
         """2^32 operand pairs: how many quotients of the shared-reciprocal division differ from n / d (include/rtr_hip_test.h)."""
-        n = C.c_uint64(0)
-        self._chk(test_lib().rtr_test_shared_division(self._h, C.byref(n)))
-        return int(n.value)
+        return self.shared_division_exhaustive()[0]
 
     # device unit kernels over golden-vector records (include/rtr_hip_test.h)
     def test_records(self, kind, recs, params=None):

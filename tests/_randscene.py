@@ -150,10 +150,18 @@ def _cat(parts, dtype):
 
 
 def random_scene(seed, n_objects=24, media=False, hollow=False, ties=True, delta_lights=False, lens=0.0, moved_media=False,
-                 big_group=False, palette="full"):
+                 big_group=False, palette="full", hollow_pairs=0, bare_hollows=0, hollow_lists=0, spheres_only=False):
     """One scene in front of scene 23's camera (origin (0,3,8), looking at the origin).  `palette` (PALETTES): the
     material and light classes it may use; "full" draws exactly what this generator always drew, so every seed of
-    the default palette gives the same scene, byte for byte, as before palettes existed."""
+    the default palette gives the same scene, byte for byte, as before palettes existed.
+    Several hollow spheres (negative radius: an inverted bounding box, so the bvh_node boxes above one do not enclose
+    it), all off by default and drawn after everything else, so the scenes without them stay as they were:
+      hollow_pairs   that many more hollow-in-glass pairs like `hollow`'s
+      bare_hollows   that many hollow spheres on their own
+      hollow_lists   that many nested hittable_lists of 2-4 bare hollow spheres each (under a bvh_node, no box is
+                     entered between two of them, so an earlier one's hit can shrink t_max below the boxes above both)
+      spheres_only   the n_objects drawn are solid spheres only (no transforms, no rects beyond ground and light), so a
+                     scene with hollow spheres stays one linearly scanned instance (the guarded references)"""
     if delta_lights and palette != "full":
         raise ValueError("palette %r has QuadLights only" % palette)
     rng = np.random.default_rng(seed)
@@ -185,7 +193,7 @@ def random_scene(seed, n_objects=24, media=False, hollow=False, ties=True, delta
         return rng.uniform(lo, hi)
 
     for _ in range(n_objects):
-        kind = int(rng.integers(0, 8))
+        kind = int(rng.integers(0, 8)) if not spheres_only else 0
         mat = b.random_material()
         if kind == 0:
             top.append(b.sphere(pos(), float(rng.uniform(0.15, 0.7)), mat))
@@ -230,6 +238,18 @@ def random_scene(seed, n_objects=24, media=False, hollow=False, ties=True, delta
             glass = b.material(A.MAT_DIELECTRIC, f=[1.5])
         top.append(b.sphere(c, 0.6, glass))
         top.append(b.sphere(c, -0.5, glass))
+    for _ in range(hollow_pairs):
+        c, r = pos(), float(rng.uniform(0.4, 0.8))
+        glass = b.material(A.MAT_DIELECTRIC, f=[1.5]) if palette != "lean" else b.random_material()
+        top.append(b.sphere(c, r, glass))
+        top.append(b.sphere(c, -0.85 * r, glass))
+    for _ in range(bare_hollows):
+        top.append(b.sphere(pos(), -float(rng.uniform(0.2, 0.6)), b.random_material()))
+    for _ in range(hollow_lists):
+        c = pos()
+        members = [b.sphere(c + rng.uniform(-1.0, 1.0, 3), -float(rng.uniform(0.2, 0.6)), b.random_material())
+                   for _ in range(int(rng.integers(2, 5)))]
+        top.insert(int(rng.integers(0, len(top) + 1)), b.hlist(members))
     if media:
         c = pos()
         shell = ground if palette == "lean" else b.material(A.MAT_DIELECTRIC, f=[1.5])
@@ -340,3 +360,86 @@ def cross_instance_tie_rays(n=1536):
     r["o"], r["d"] = o, t - o
     r["time"], r["t_min"], r["t_max"], r["rng_in"] = 0.5, 0.001, np.inf, 7
     return r
+
+
+# ---- several hollow spheres under bvh_nodes ---------------------------------------------------------------------------
+_PAD = 0.0001  # aarect.h: kAABBPadding around a rect's plane
+
+
+def _node_box(sc, ix):
+    """bounding_box of the reference's classes for the node kinds of spheres_only scenes (sphere.h:62-66: a negative
+    radius gives an inverted box; aarect.h; hittable_list.h:49-62 and aabb.h:50-59: surrounding boxes; flip_face)"""
+    n = sc.nodes[ix]
+    t, f = int(n["type"]), n["f"]
+    if t == A.NODE_SPHERE:
+        c, r = np.array(f[:3]), float(f[3])
+        return c - r, c + r
+    if t in (A.NODE_XY_RECT, A.NODE_XZ_RECT, A.NODE_YZ_RECT):
+        k = {A.NODE_XY_RECT: 2, A.NODE_XZ_RECT: 1, A.NODE_YZ_RECT: 0}[t]
+        a, b_ = [ax for ax in range(3) if ax != k]
+        lo, hi = np.empty(3), np.empty(3)
+        lo[a], hi[a], lo[b_], hi[b_] = f[0], f[1], f[2], f[3]
+        lo[k], hi[k] = f[4] - _PAD, f[4] + _PAD
+        return lo, hi
+    if t == A.NODE_FLIP_FACE:
+        return _node_box(sc, int(n["a"]))
+    if t == A.NODE_LIST:
+        boxes = [_node_box(sc, int(sc.list_children[int(n["a"]) + k])) for k in range(int(n["b"]))]
+        return np.min([b_[0] for b_ in boxes], axis=0), np.max([b_[1] for b_ in boxes], axis=0)
+    raise ValueError("bvh_over_top: no box rule for node type %d" % t)
+
+
+def bvh_over_top(sc, seed):
+    """The scene with its root hittable_list replaced by a tree of bvh_nodes over the list's objects, built the way
+    bvh_node's constructor builds one (bvh.h:53-96: a random split axis per node, objects sorted by their boxes'
+    minimum on it, one object -> left = right = it, two -> in comparator order, more -> halves).  The axes come from
+    numpy, not from the reference's RNG, so this is not the tree `wrap-bvh` builds -- it needs no reference to run,
+    and the oracle answers for it.  Node kinds: those of spheres_only scenes."""
+    rng = np.random.default_rng(seed)
+    nodes = list(sc.nodes)
+    root = sc.nodes[sc.root]
+    assert int(root["type"]) == A.NODE_LIST
+    objs = [int(sc.list_children[int(root["a"]) + k]) for k in range(int(root["b"]))]
+    box = {ix: _node_box(sc, ix) for ix in objs}
+
+    def build(items):
+        axis = int(rng.integers(0, 3))
+        if len(items) == 1:
+            left = right = items[0]
+        elif len(items) == 2:
+            left, right = items if box[items[0]][0][axis] < box[items[1]][0][axis] else items[::-1]
+        else:
+            items = sorted(items, key=lambda ix: box[ix][0][axis])  # (stable, like std::sort on distinct keys)
+            mid = len(items) // 2
+            left, right = build(items[:mid]), build(items[mid:])
+        n = np.zeros(1, dtype=A.NODE_DTYPE)
+        n["type"], n["a"], n["b"] = A.NODE_BVH, left, right
+        lo = np.minimum(box[left][0], box[right][0])
+        hi = np.maximum(box[left][1], box[right][1])
+        n["f"][0, :6] = list(lo) + list(hi)
+        nodes.append(n[0])
+        me = len(nodes) - 1
+        box[me] = (lo, hi)
+        return me
+
+    top = build(objs)
+    return rtr.Scene(top, np.array(nodes, dtype=A.NODE_DTYPE), sc.list_children, sc.materials, sc.textures, sc.perlin,
+                     sc.images, sc.image_bytes, sc.lights, sc.camera, sc.background)
+
+
+def guard_rule_split(sc, rays):
+    """Indices of the rays on which the device's former guard rule (oracle rto_hits_running_guard: every bvh_node box
+    above a hollow sphere tested with the running t_max) and the reference's walk (rto_hits: each box with the t_max
+    its node was entered with) give different hit records."""
+    ref = G.oracle_records(sc, "rto_hits", rays)
+    run = G.oracle_records(sc, "rto_hits_running_guard", rays)
+    return np.flatnonzero((ref["hit"] != run["hit"]) | (ref["material"] != run["material"]) |
+                          (ref["t"].view(np.uint64) != run["t"].view(np.uint64)))
+
+
+def discriminating_rays(sc, seed, n, pool=65536, most=None):
+    """`n` rays: those of `pool` candidates (random_rays(100000 + seed, pool)) on which the two guard rules disagree --
+    at most `most` of them, n // 2 by default --, topped up with random_rays(seed, ...) in their usual order."""
+    cand = random_rays(100000 + seed, pool)
+    pick = cand[guard_rule_split(sc, cand)[:n // 2 if most is None else most]]
+    return np.concatenate([pick, random_rays(seed, n - len(pick))])

@@ -964,6 +964,7 @@ def test_one_sincos_equals_sin_and_cos_on_every_sampler_angle(ctx):
     """random_cosine_direction (vec3.h:261-269) and PBRMaterial::sample (material.h:268-275) call cos(phi) and
     sin(phi); the device takes both from one sincos().  Exhaustive over the 2^32 states of the generator."""
     assert ctx.sincos_mismatches() == 0
+    assert ctx.sincos_exhaustive() == (0, 2 ** 32)  # (mismatches, angles compared: all of them)
 
 
 def test_error_behaviour(ctx, rtr):
@@ -999,3 +1000,4 @@ def test_shared_reciprocal_division_equals_plain_division(ctx):
     |d|^2 (sphere.h:43-47) through ONE refined reciprocal per ray and frame; the last three instructions of the
     compiler's own division sequence then give the quotient.  2^32 operand pairs of the range it is used in: 0 differ."""
     assert ctx.shared_division_mismatches() == 0
+    assert ctx.shared_division_exhaustive() == (0, 2 ** 32)  # (mismatches, pairs compared: all of them)

@@ -15,8 +15,19 @@ rtr = G.rtr
 # "<seed>": a flat hittable_list as generated; "<seed>b": the same objects under the reference's own bvh_node
 # 32 / 33: a constant_medium UNDER translate / rotate_y (a step with a transform chain, FStep::xf_first)
 # 54: lean materials (palette="lean") with a top tree over its instances; 64: QuadLights-only materials with media
+# 02 / 01b / 03b / 04b / 05b: several hollow spheres (GUARD_CASES below)
 SEEDS = ["11", "13", "14", "15", "16", "17", "18", "19", "27", "28", "32", "33", "54", "64",
-         "13b", "15b", "16b", "18b", "19b", "23b", "26b", "28b", "32b", "33b"]
+         "13b", "15b", "16b", "18b", "19b", "23b", "26b", "28b", "32b", "33b", "02", "01b", "03b", "04b", "05b"]
+# Several hollow spheres (negative radius: an inverted bounding box).  The reference tests each bvh_node box above one
+# with the t_max that node was entered with (bvh.h:40-50); testing them all with the running t_max at the sphere's
+# visit (the oracle's rto_hits_running_guard) differs where an earlier hollow sphere under the same bvh_node, with no
+# box entered in between, was hit outside that node's box.  The fixtures' rays start with such rays.
+#   03b, 05b  nested lists of hollow spheres next to solid spheres only: the rule differs; would be one linear scan
+#   01b       the same next to transformed boxes: the rule differs; would be guarded program steps (FStep kind 3)
+#   04b       hollow-in-glass pairs and bare hollow spheres straight under the tree: the rules agree, the guarded
+#             linear scan (RT_TRAV_FLAT_GUARD) stays
+#   02        lists of hollow spheres without a bvh_node: nothing to guard
+GUARD_CASES = {"03b": "differs", "05b": "differs", "01b": "differs", "04b": "agrees", "02": "agrees"}
 W, H, SPP = 48, 32, 4
 
 
@@ -63,6 +74,38 @@ def test_oracle_equals_the_reference_on_random_scenes(seed):
         # (the harness counts a cast as a shadow ray by its finite t_max: rays towards a directional or
         # environment light have none, so the split differs there; the sum does not)
         assert st["closest_segments"] + st["shadow_segments"] == info["closest_segments"] + info["shadow_segments"]
+
+
+@pytest.mark.parametrize("seed", sorted(GUARD_CASES))
+def test_guard_fixtures_separate_the_two_box_rules(seed):
+    """CPU: the reference's records against the running-t_max rule (rto_hits_running_guard) on the hollow-sphere
+    fixtures -- a regeneration that loses the rays on which the rules differ makes this fail, not the GPU test vacuous."""
+    sc = _scene(seed)
+    gold = G.records("random_%s_hits.bin" % seed, A.HIT_DTYPE)
+    run = G.oracle_records(sc, "rto_hits_running_guard", gold)
+    differ = int(((run["hit"] != gold["hit"]) | (run["material"] != gold["material"]) |
+                  (_bits(run["t"]) != _bits(gold["t"]))).sum())
+    if GUARD_CASES[seed] == "differs":
+        assert differ >= 8, (seed, differ)
+    else:
+        assert differ == 0, (seed, differ)
+
+
+@pytest.mark.parametrize("seed", sorted(GUARD_CASES))
+def test_guard_fixtures_take_their_paths(seed):
+    """CPU: which traversal upload picks.  Where the running t_max would decide differently from the reference (03b /
+    05b / 01b) neither the guarded linear scan nor guarded program steps may run: the reference-order walk answers.
+    The control 04b keeps the guarded linear scan, 02 (no bvh_node) the plain one."""
+    sc = _scene(seed)
+    info = rtr.native.validate_scene(sc)
+    hollow = int(((sc.nodes["type"] == A.NODE_SPHERE) & (sc.nodes["f"][:, 3] < 0)).sum())
+    assert hollow >= 6 and info["inverted_boxes"] == hollow, (info, hollow)
+    if GUARD_CASES[seed] == "differs":
+        assert not info["fast_ok"] and info["program_steps"] == 0, info
+    else:
+        assert info["fast_ok"] and info["program_steps"] == 0, info
+    if seed == "04b":
+        assert (sc.nodes["type"] == A.NODE_BVH).sum() >= 10
 
 
 def _xties():
@@ -124,6 +167,26 @@ def test_device_equals_the_reference_on_random_scenes(ctx, seed):
             worst = max(worst, err)
             assert err <= 1e-12, (seed, integ, pipe, err)
     G.residue("random%s.vs_reference.worst_rel_l2" % seed, worst, 1e-12)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", sorted(GUARD_CASES))
+def test_split_casts_leave_guarded_scenes_alone(ctx, seed):
+    """The pair cast (one instance pass for the shadow ray and the next closest-hit ray) runs on the plain linear scan
+    only: on the hollow-sphere fixtures (guarded references, or the reference-order walk) RTR_FLAG_SPLIT_CASTS changes
+    no kernel, and the MIS image equals the reference's either way."""
+    sc = _scene(seed)
+    ctx.upload(sc)
+    want = _image(seed, 4)
+    kw = dict(integrator=4, seed=100 + int(seed.rstrip("b")), pipeline=A.PIPELINE_MEGAKERNEL)
+    out = ctx.render(A.make_params(W, H, SPP, **kw))
+    st = ctx.stats()
+    split = ctx.render(A.make_params(W, H, SPP, flags=A.FLAG_SPLIT_CASTS, **kw))
+    ss = ctx.stats()
+    assert np.array_equal(_bits(out), _bits(split))
+    assert (st["closest_segments"], st["shadow_segments"]) == (ss["closest_segments"], ss["shadow_segments"])
+    assert ss["flags_in_effect"] & A.FLAG_SPLIT_CASTS == 0
+    assert G.rel_l2(split, want) <= 1e-12
 
 
 @pytest.mark.gpu

@@ -75,12 +75,21 @@ def test_default_palette_reproduces_every_scene_byte_for_byte():
                 assert f.read() == R.random_scene(seed, **kw).to_bytes(), seed
 
 
+def _hollow_count(sc, kw):
+    """hollow spheres the generator's knobs ask for, checked against the scene: exactly 1 / 0 for `hollow` alone"""
+    n = int(((sc.nodes["type"] == A.NODE_SPHERE) & (sc.nodes["f"][:, 3] < 0)).sum())
+    lists = kw.get("hollow_lists", 0)
+    fixed = (1 if kw.get("hollow") else 0) + kw.get("hollow_pairs", 0) + kw.get("bare_hollows", 0)
+    assert fixed + 2 * lists <= n <= fixed + 4 * lists, (n, kw)
+    return n
+
+
 @pytest.mark.parametrize("seed,kw", CASES)
 def test_random_scenes_validate_and_run_on_the_oracle(seed, kw):
     """CPU: the generator's scenes are well-formed and the oracle traces them (no GPU)."""
     sc = R.random_scene(seed, **kw)
     info = rtr.native.validate_scene(sc)
-    assert info["has_media"] == bool(kw.get("media") or kw.get("moved_media")) and info["inverted_boxes"] == (1 if kw.get("hollow") else 0)
+    assert info["has_media"] == bool(kw.get("media") or kw.get("moved_media")) and info["inverted_boxes"] == _hollow_count(sc, kw)
     if not kw.get("media") and not kw.get("hollow") and not kw.get("moved_media"):
         assert info["fast_ok"] and info["fast_refs"] >= 3
         # dozens of transformed instances sit in a box tree of their own (FSub::top_root): seeds 13 / 19 / 24 / 29
@@ -232,3 +241,73 @@ def test_traversal_machine_refuses_what_it_cannot_run(ctx, seed, kw):
         ctx.render(p)
     assert e.value.code == A.RTR_ERR_UNSUPPORTED
     ctx.render(A.make_params(32, 16, 2, integrator=4, seed=1, pipeline=A.PIPELINE_WAVEFRONT))
+
+
+# Several hollow spheres under bvh_nodes (R.bvh_over_top: a tree like bvh_node's over the scene's list, built without
+# the reference): nested lists of hollow spheres -- where testing the boxes above one with the running t_max differs
+# from the reference's t_max at each node's entry -- and, as controls, hollow-in-glass pairs and bare ones straight
+# under the tree, where the two rules agree and the guarded linear scan (RT_TRAV_FLAT_GUARD) must stay.
+GUARD_SWEEP = [(s_, dict(spheres_only=True, n_objects=20, hollow_lists=4)) for s_ in (101, 103, 104, 106)] + \
+              [(107, dict(spheres_only=True, n_objects=16, hollow_lists=2, bare_hollows=3)),
+               (110, dict(spheres_only=True, n_objects=20, hollow_pairs=4, bare_hollows=2)),
+               (109, dict(spheres_only=True, n_objects=30, hollow_pairs=3))]
+
+
+def _guard_scene(seed, kw):
+    return R.bvh_over_top(R.random_scene(seed, **kw), seed)
+
+
+@pytest.mark.parametrize("seed,kw", GUARD_SWEEP)
+def test_guard_sweep_scenes_separate_the_rules_and_take_their_paths(seed, kw):
+    """CPU: the sweep's scenes with lists of hollow spheres hold rays on which the two box rules differ, and upload
+    sends them to the reference-order walk; the pairs-only controls hold none and keep the guarded linear scan."""
+    sc = _guard_scene(seed, kw)
+    info = rtr.native.validate_scene(sc)
+    assert info["inverted_boxes"] == _hollow_count(sc, kw) and not info["has_media"]
+    differ = len(R.guard_rule_split(sc, R.random_rays(100000 + seed, 65536)))
+    if kw.get("hollow_lists"):
+        assert differ > 0 and not info["fast_ok"] and info["program_steps"] == 0, (differ, info)
+    else:
+        assert differ == 0 and info["fast_ok"], (differ, info)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,kw", GUARD_SWEEP)
+def test_guard_sweep_equals_the_oracle(ctx, seed, kw):
+    """The device against the oracle on the sweep's scenes: hit records bit for bit on rays the discriminator picked
+    (half of them rays where the running-t_max rule would differ), both reference_order settings; MIS and RR renders
+    on every pipeline that runs the scene, the MIS one also with RTR_FLAG_SPLIT_CASTS (a guarded scene has no pair cast)."""
+    sc = _guard_scene(seed, kw)
+    ctx.upload(sc)
+    info = rtr.native.validate_scene(sc)
+    rays = R.discriminating_rays(sc, seed, 2048)
+    ora = G.oracle_records(sc, "rto_hits", rays)
+    h = ora["hit"] == 1
+    for exact_order in (False, True):
+        ctx.reference_order(exact_order)
+        dev = ctx.test_records("hits", rays)
+        ctx.reference_order(False)
+        tag = "guard%d.%s" % (seed, "reference_order" if exact_order else "compiled")
+        assert np.array_equal(dev["hit"], ora["hit"]), (tag, int((dev["hit"] != ora["hit"]).sum()))
+        for f in ("front_face", "material"):
+            assert np.array_equal(dev[f][h], ora[f][h]), (tag, f, int((dev[f][h] != ora[f][h]).sum()))
+        for f in ("t", "p", "n"):
+            assert np.array_equal(_bits(dev[f][h]), _bits(ora[f][h])), (tag, f)
+        for f in ("u", "v"):  # acos / atan2: OCML against glibc
+            assert np.allclose(dev[f][h], ora[f][h], rtol=0, atol=1e-12), (tag, f)
+    pipes = [A.PIPELINE_MEGAKERNEL] + ([A.PIPELINE_WAVEFRONT] if info["fast_ok"] or info["program_steps"] > 0 else [])
+    worst = 0.0
+    for integ in (1, 4):
+        p = A.make_params(48, 32, 4, integrator=integ, seed=300 + seed)
+        want, wst = G.oracle_render(sc, p)
+        runs = [(pipe, 0) for pipe in pipes] + ([(A.PIPELINE_MEGAKERNEL, A.FLAG_SPLIT_CASTS)] if integ == 4 else [])
+        for pipe, flags in runs:
+            got = ctx.render(A.make_params(48, 32, 4, integrator=integ, seed=300 + seed, pipeline=pipe, flags=flags))
+            st = ctx.stats()
+            tag = "guard%d.i%d.pipe%d.flags%d" % (seed, integ, pipe, flags)
+            assert st["closest_segments"] == wst["closest_segments"] and st["shadow_segments"] == wst["shadow_segments"], tag
+            assert st["flags_in_effect"] & A.FLAG_SPLIT_CASTS == 0, tag
+            err = G.rel_l2(got, want)
+            worst = max(worst, err)
+            assert err <= 1e-12, (tag, err)
+    G.residue("guard%d.renders.worst_rel_l2" % seed, worst, 1e-12)
