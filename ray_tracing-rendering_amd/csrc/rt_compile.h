@@ -526,9 +526,12 @@ struct Builder {
                 I.bound = float_up(bound);
                 stack = std::max(stack, depth + 2);
             }
-            I.flags = 0;
-            for (int k = 0; k < I.n_xf; ++k)
-                if (out.xf[I.xf_first + k].type == RTR_NODE_ROTATE_Y) I.flags |= RT_INST_ROTATED;
+            I.flags = RT_INST_KEEP_Y; /* until an op changes d.y (none of translate / rotate_y does) */
+            for (int k = 0; k < I.n_xf; ++k) {
+                const int type = out.xf[I.xf_first + k].type;
+                if (type == RTR_NODE_ROTATE_Y) I.flags |= RT_INST_ROTATED;
+                if (type != RTR_NODE_TRANSLATE && type != RTR_NODE_ROTATE_Y) I.flags &= ~RT_INST_KEEP_Y;
+            }
             for (int k = 0; k < RT_INST_XF_INLINE; ++k) {
                 I.xf_type[k] = k < I.n_xf ? out.xf[I.xf_first + k].type : 0;
                 for (int c = 0; c < 3; ++c) I.xf_f[k][c] = k < I.n_xf ? out.xf[I.xf_first + k].f[c] : 0.0;

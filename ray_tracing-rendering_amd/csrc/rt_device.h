@@ -349,6 +349,9 @@ struct FInst {
 #define RT_INST_ROTATED 1 /* a rotate_y in the chain: the direction's x and z differ from the frame above */
 #define RT_INST_SPHERES 2 /* holds sphere / moving_sphere references: the frame needs |d|^2 and its reciprocal */
 #define RT_INST_RUNS 4    /* scan_first / run[] describe the references (see FInst) */
+/* the chain leaves the direction's y as it is in the world frame (translate leaves the whole direction, rotate_y its y):
+ * the frame's reciprocal of d.y and its rcp_safe verdict are the world frame's, bit for bit (trace_pair) */
+#define RT_INST_KEEP_Y 8
 struct FXf {
     int32_t type; /* RTR_NODE_TRANSLATE (f = offset) or RTR_NODE_ROTATE_Y (f[0] = sin, f[1] = cos) */
     int32_t pad;
@@ -1558,7 +1561,13 @@ RT_DEV void pair_runs(const DScene& sc, const FInst& I, const PairRay& A, Real t
     }
 }
 /* A: closest hit from (ao, ad) at `atime` -> a_ref, a_inst, a_tmax (in: the ray's t_max); B: any hit from (bo, bd) within
- * b_tmax -> b_ref >= 0.  Sub-scene 0 of a DScene::pair_cast scene only. */
+ * b_tmax -> b_ref >= 0.  Sub-scene 0 of a DScene::pair_cast scene only.
+ * The reciprocal of the world direction's y is made once per cast: every frame whose chain leaves d.y as it is
+ * (RT_INST_KEEP_Y: the same operand, so the same reciprocal and the same rcp_safe verdict) takes it from there.  Carrying
+ * x and z as well, for the frames without a rotate_y, put ten VGPRs of the lean kernel back into scratch: those two
+ * are made per frame.  RayDiv::fast of a ray in a frame is origin_ok && __all(every lane's
+ * verdicts), and __all(p) && __all(q) == __all(p & q): the per-lane verdicts are combined first and voted on once per
+ * frame for both rays, and only a frame that fails that vote votes per ray to choose the single-ray scans. */
 __device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
                                            V3 bo, V3 bd, Real& b_tmax, int& b_ref, const Stack st) {
     a_ref = -1, a_inst = -1, b_ref = -1;
@@ -1567,6 +1576,8 @@ __device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real 
 #else /* experiments without the shared reciprocals: every frame takes the single-ray scans with plain divisions */
     const bool ok_a = false, ok_b = false;
 #endif
+    const Real way = rcp_refined(ad.y), wby = rcp_refined(bd.y);
+    const bool wa_y = rcp_safe(ad.y), wb_y = rcp_safe(bd.y); /* per lane */
     for (int ii = 0; ii < sc.n_finst; ++ii) {
         RT_REGION(RG_PAIR_SETUP);
         const FInst I = ld_const(sc.finst, ii);
@@ -1586,13 +1597,29 @@ __device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real 
                 wrapper_enter(x.type, x.f, B.o, B.d);
             }
         }
-        A.q = raydiv_make(A.d, 0.001, ok_a);
-        B.q = raydiv_make(B.d, 0.001, ok_b);
-        if (I.flags & RT_INST_SPHERES) raydiv_spheres(A.q, A.d), raydiv_spheres(B.q, B.d);
-        if (A.q.fast && B.q.fast) {
+        A.q.guard = B.q.guard = false; /* t_min = 0.001 */
+        A.q.rx = rcp_refined(A.d.x), A.q.rz = rcp_refined(A.d.z);
+        B.q.rx = rcp_refined(B.d.x), B.q.rz = rcp_refined(B.d.z);
+        bool sa = rcp_safe(A.d.x) & rcp_safe(A.d.z), sb = rcp_safe(B.d.x) & rcp_safe(B.d.z); /* every divisor: this lane */
+        if (I.flags & RT_INST_KEEP_Y) {
+            A.q.ry = way, B.q.ry = wby;
+            sa = sa & wa_y, sb = sb & wb_y;
+        } else {
+            A.q.ry = rcp_refined(A.d.y), B.q.ry = rcp_refined(B.d.y);
+            sa = sa & rcp_safe(A.d.y), sb = sb & rcp_safe(B.d.y);
+        }
+        A.q.a = A.q.ra = B.q.a = B.q.ra = 0;
+        if (I.flags & RT_INST_SPHERES) { /* raydiv_spheres */
+            A.q.a = len2(A.d), B.q.a = len2(B.d);
+            A.q.ra = rcp_refined(A.q.a), B.q.ra = rcp_refined(B.q.a);
+            sa = sa & rcp_safe(A.q.a), sb = sb & rcp_safe(B.q.a);
+        }
+        if (ok_a && ok_b && __all(sa & sb)) {
+            A.q.fast = B.q.fast = true;
             pair_runs(sc, I, A, atime, a_tmax, a_ref, B, b_tmax, b_ref);
         } else { /* the single-ray scans of trace_fast, one after the other, with its template arguments (a direction
                   * component or |d|^2 outside [2^-100, 2^100], an origin beyond 2^80: tests/test_pair_cast.py) */
+            A.q.fast = ok_a && __all(sa), B.q.fast = ok_b && __all(sb);
             int order = -1;
             if (A.q.fast)
                 scan_instance<false, false, false, true>(sc, I, A.o, A.d, A.q, atime, 0.001, a_tmax, a_ref, order, st, 0);
@@ -2663,6 +2690,7 @@ struct ShadowReq {
     V3 wi;      /* shadow_ray = ray(rec.p, wi, time 0), mis_path_integrator.h:210 */
     Real tmax;  /* ls.dist - 0.001 */
     V3 contrib; /* clamp_radiance(throughput * L_direct) if unshadowed */
+    RT_DEV void put(V3 wi_, Real tmax_, V3 contrib_) { valid = true, wi = wi_, tmax = tmax_, contrib = contrib_; }
 };
 
 /*
@@ -2679,9 +2707,11 @@ struct ShadowReq {
  *   RTR_INTEGRATOR_PBR  pbr_path_integrator.h:38-68     (emission unweighted, no light sample, no fallback) */
 /* the two parts of shade_a_mis, callable on their own (the material-sorted megakernel runs the first on the lane that
  * owns the path and the second on the lane that shades it): PART bit 0 = emission, bit 1 = light sample */
-template <int MS = RT_MS_FULL, int INTEG = RTR_INTEGRATOR_MIS, int PART = 3>
+/* REQ: ShadowReq, or a type with the same `valid` and put() that stores the request where it is consumed (the pair-cast
+ * kernel parks it in LDS as soon as it is formed: held in registers to the end of shading, it was spilled) */
+template <int MS = RT_MS_FULL, int INTEG = RTR_INTEGRATOR_MIS, int PART = 3, class REQ = ShadowReq>
 RT_DEV void shade_a_mis(const DScene& sc, PathState& ps, const Hit& rec, const MatCtx& mc, V3 wo, uint32_t& rng,
-                        ShadowReq& rq) {
+                        REQ& rq) {
     RT_REGION(RG_SHADE_A);
     const bool have_lights = sc.n_lights > 0;
     rq.valid = false;
@@ -2743,10 +2773,8 @@ RT_DEV void shade_a_mis(const DScene& sc, PathState& ps, const Hit& rec, const M
                 Real mis_weight = power_heuristic(lpdf, bsdf_pdf);
                 L_direct = divs(scl(mis_weight, scl(cos_theta, mul(f, ls.Li))), lpdf);
             }
-            rq.valid = true;
-            rq.wi = ls.wi;
-            rq.tmax = ls.dist - 0.001;
-            rq.contrib = INTEG == RTR_INTEGRATOR_NEE ? mul(ps.thr, L_direct) : clamp_radiance(mul(ps.thr, L_direct));
+            rq.put(ls.wi, ls.dist - 0.001,
+                   INTEG == RTR_INTEGRATOR_NEE ? mul(ps.thr, L_direct) : clamp_radiance(mul(ps.thr, L_direct)));
         }
     }
 }

@@ -56,6 +56,17 @@ struct Park {
 };
 enum { PK_THR = 0, PK_L = 3, PK_ACC = 6, PK_PDF = 9, PK_NCLOSEST = 10, PK_NSHADOW = 11, /* every variant */
        PK_CONTRIB = 12, PK_SWI = 15, PK_STMAX = 18 };                                       /* deferred shadow ray only */
+/* a shadow request of shade_a_mis written straight into the parked words PK_SWI, PK_STMAX, PK_CONTRIB */
+struct ParkedReq {
+    bool valid;
+    Park pk;
+    RT_DEV void put(V3 wi, Real tmax, V3 contrib) {
+        valid = true;
+        pk.set3(PK_SWI, wi);
+        pk.set(PK_STMAX, tmax);
+        pk.set3(PK_CONTRIB, contrib);
+    }
+};
 /* words a variant parks: the deferred shadow request exists only where the shadow ray is cast after the
  * BSDF sample (MIS-type integrators on scenes without media); fewer words = more workgroups per CU where
  * LDS, not registers, is the limit (the lean RR kernel: 92 VGPRs) */
@@ -433,15 +444,10 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                     ps.L = mk(0.0, 0.0, 0.0); /* see the split loop below: L + e is the reference's L += e */
                     ps.prev_bsdf_pdf = pk.get(PK_PDF);
                     const V3 wo = neg(unit(ps.rd));
-                    ShadowReq rq;
+                    ParkedReq rq{false, pk}; /* parked until the next pair cast */
                     const MatCtx mc = mat_prepare<MS>(sc, rec);
                     shade_a_mis<MS, INTEG>(sc, ps, rec, mc, wo, rng, rq);
-                    if (rq.valid) { /* parked until the next pair cast */
-                        pending = true;
-                        pk.set3(PK_SWI, rq.wi);
-                        pk.set(PK_STMAX, rq.tmax);
-                        pk.set3(PK_CONTRIB, rq.contrib);
-                    }
+                    pending = rq.valid;
                     const bool go = shade_b_mis<MS, INTEG>(sc, ps, rec, mc, wo, rng, P.rr_start);
                     RT_REGION(RG_PARK);
                     ps.ro = rec.p; /* next ray origin and shadow ray origin */
