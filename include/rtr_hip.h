@@ -540,6 +540,51 @@ int rtr_denoise_host(rtr_context* ctx, const rtr_denoise_params* params, int32_t
                      const double* h_color, const double* h_q, const int32_t* h_count, const double* h_feat,
                      double* h_linear, uint8_t* h_rgb8);
 
+/* ---- ray queries: closest hit and occlusion of caller-given rays on the uploaded scene ----
+ * rtr_query_closest is `world->hit(ray, t_min, t_max, rec)` (geometry/hittable.h:25-32) on the scene's root for each of
+ * `n` rays, one GPU lane each; rtr_query_occluded is the boolean of the same call, taken through the any-hit forms the
+ * integrators' shadow rays use.  The traversal is the one a render of the scene with `flags` walks (compiled scene, top
+ * tree, step program of a scene with media, or the reference-order walk), so t, p, n, front_face and material are the
+ * reference's bits wherever a render's are.  (u, v) are always computed, whether or not a texture of the scene reads
+ * them.  In a scene with media the draws inside constant_medium::hit happen in both calls: occluded[k] and rng_out[k]
+ * equal hits[k].hit and hits[k].rng_out of the closest query on the same ray.
+ *
+ * flags: 0 or RTR_FLAG_REFERENCE_ORDER (as in a render); any other bit is RTR_ERR_INVALID.  n == 0 is RTR_OK without a
+ * launch; n < 0 or a NULL array (rng_out may be NULL) is RTR_ERR_INVALID; a call before rtr_upload_scene is
+ * RTR_ERR_NO_SCENE -- all before any device work.
+ *
+ * A ray is BAD if origin, direction, time or t_min is not finite, t_max is NaN (+-inf are fine), or rng_state is 0 in
+ * a scene with media.  The host entries reject the whole batch with RTR_ERR_INVALID, name the first bad index in
+ * rtr_last_error and leave the outputs untouched; the device entries cannot see the data: there the kernel writes a
+ * miss (occluded = 0, rng_out = rng_state) for such a ray without casting it.  Any finite t_min is allowed, 0 and
+ * negative values included: a wave holding a ray with t_min < 2^-100 takes the plain IEEE divisions instead of the
+ * shared reciprocals, so the results are the reference's bits there too.
+ *
+ * The host entries take host arrays and block; they copy through a staging buffer of the context that only grows, in
+ * slices of at most 2^22 rays, so n is bounded by the caller's memory only.  The device entries take device pointers
+ * (8-byte aligned; in and out must not overlap), run on the context stream behind whatever is queued there -- renders
+ * and accumulator passes included -- and return at once unless `blocking`.  Neither touches anything a queued render
+ * or accumulator pass uses, nor the statistics of rtr_get_stats.  rtr_cancel does not apply to queries. */
+typedef struct rtr_ray {            /* 80 bytes */
+    double origin[3], direction[3]; /* direction is not normalised by the library, like the reference's ray */
+    double time, t_min, t_max;      /* t_max may be +inf */
+    uint32_t rng_state, pad;        /* xorshift32 state when hit() is entered; read only where the scene has media */
+} rtr_ray;
+
+typedef struct rtr_ray_hit {        /* 88 bytes */
+    double t, p[3], n[3], u, v;     /* u, v are NaN where the reference leaves them unset; all 0 on a miss */
+    int32_t hit, front_face, material; /* material = -1 on a miss */
+    uint32_t rng_out;               /* generator state after the call (= rng_state without media) */
+} rtr_ray_hit;
+
+int rtr_query_closest(rtr_context* ctx, const rtr_ray* rays, rtr_ray_hit* hits, int64_t n, int32_t flags);
+int rtr_query_occluded(rtr_context* ctx, const rtr_ray* rays, uint8_t* occluded, uint32_t* rng_out, int64_t n,
+                       int32_t flags);
+int rtr_query_closest_device(rtr_context* ctx, const rtr_ray* d_rays, rtr_ray_hit* d_hits, int64_t n, int32_t flags,
+                             int blocking);
+int rtr_query_occluded_device(rtr_context* ctx, const rtr_ray* d_rays, uint8_t* d_occluded, uint32_t* d_rng_out,
+                              int64_t n, int32_t flags, int blocking);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

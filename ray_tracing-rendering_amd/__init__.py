@@ -13,7 +13,7 @@ Layout:
 """
 from . import _abi  # noqa: F401
 from ._abi import (INTEGRATOR_MIS, INTEGRATOR_RR, PIPELINE_AUTO, PIPELINE_MEGAKERNEL,  # noqa: F401
-                   PIPELINE_WAVEFRONT, make_params)
+                   PIPELINE_WAVEFRONT, RAY_DTYPE, RAY_HIT_DTYPE, make_params)
 from .scene import Scene  # noqa: F401
 
 

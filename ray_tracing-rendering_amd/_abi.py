@@ -46,6 +46,12 @@ assert CAMERA_DTYPE.itemsize == 192
 LI_RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("time", "<f8"), ("rng_state", "<u4"),
                          ("pad", "<u4")])  # rtr_li_ray
 assert LI_RAY_DTYPE.itemsize == 64
+# ray queries (rtr_query_*): rtr_ray in, rtr_ray_hit out
+RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("time", "<f8"), ("t_min", "<f8"),
+                      ("t_max", "<f8"), ("rng_state", "<u4"), ("pad", "<u4")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("n", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
+                          ("hit", "<i4"), ("front_face", "<i4"), ("material", "<i4"), ("rng_out", "<u4")])
+assert RAY_DTYPE.itemsize == 80 and RAY_HIT_DTYPE.itemsize == 88
 
 # golden-vector records (rtr_testrec.h, packed)
 LI_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("s", "<i4"), ("rng_exit", "<u4"), ("L", "<f8", (3,)),
@@ -96,6 +102,21 @@ class RenderStatsC(C.Structure):
                 ("device_ms", C.c_double), ("kernel_launches", C.c_int32), ("pipeline", C.c_int32),
                 ("spp_chunks", C.c_int32), ("cancelled", C.c_int32), ("flags_in_effect", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class RayC(C.Structure):
+    """rtr_ray (include/rtr_hip.h): one ray of rtr_query_*"""
+    _fields_ = [("origin", C.c_double * 3), ("direction", C.c_double * 3), ("time", C.c_double), ("t_min", C.c_double),
+                ("t_max", C.c_double), ("rng_state", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class RayHitC(C.Structure):
+    """rtr_ray_hit (include/rtr_hip.h): the hit record of rtr_query_closest"""
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("n", C.c_double * 3), ("u", C.c_double), ("v", C.c_double),
+                ("hit", C.c_int32), ("front_face", C.c_int32), ("material", C.c_int32), ("rng_out", C.c_uint32)]
+
+
+assert C.sizeof(RayC) == RAY_DTYPE.itemsize and C.sizeof(RayHitC) == RAY_HIT_DTYPE.itemsize
 
 
 class DenoiseParamsC(C.Structure):

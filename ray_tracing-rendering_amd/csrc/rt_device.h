@@ -1931,18 +1931,20 @@ __device__ __forceinline__ bool cast_closest(const DScene& sc, V3 o, V3 d, Real 
     }
     return traverse<true, TRAV == RT_TRAV_MEDIA>(sc, sc.root, o, d, time, tmin, tmax, rec, rng, st, 0);
 }
+/* (time, tmin): the integrators' shadow rays take the defaults -- literals at every call site; the ray queries pass a ray's own */
 template <int TRAV>
-__device__ __forceinline__ bool cast_shadow(const DScene& sc, V3 o, V3 d, Real tmax, uint32_t& rng, const Stack st) {
+__device__ __forceinline__ bool cast_shadow(const DScene& sc, V3 o, V3 d, Real tmax, uint32_t& rng, const Stack st,
+                                            Real time = 0.0, Real tmin = 0.001) {
     if (TRAV == RT_TRAV_FAST || rt_is_flat(TRAV) || TRAV == RT_TRAV_TOP) {
         int ref, inst;
-        return trace_fast<true, !rt_is_flat(TRAV), true, TRAV == RT_TRAV_TOP, TRAV == RT_TRAV_FLAT_GUARD>(sc, sub_scene0(sc), o, d, 0.0, 0.001, tmax, ref, inst, st, 0);
+        return trace_fast<true, !rt_is_flat(TRAV), true, TRAV == RT_TRAV_TOP, TRAV == RT_TRAV_FLAT_GUARD>(sc, sub_scene0(sc), o, d, time, tmin, tmax, ref, inst, st, 0);
     }
     if (rt_is_program(TRAV)) { /* the media behind a blocker still draw */
         int ref, inst, med;
-        return run_program<true, TRAV == RT_TRAV_PROGRAM_EXT>(sc, o, d, 0.0, 0.001, tmax, ref, inst, med, rng, st);
+        return run_program<true, TRAV == RT_TRAV_PROGRAM_EXT>(sc, o, d, time, tmin, tmax, ref, inst, med, rng, st);
     }
     Hit dummy;
-    return traverse<false, TRAV == RT_TRAV_MEDIA>(sc, sc.root, o, d, 0.0, 0.001, tmax, dummy, rng, st, 0);
+    return traverse<false, TRAV == RT_TRAV_MEDIA>(sc, sc.root, o, d, time, tmin, tmax, dummy, rng, st, 0);
 }
 /* ---- materials/perlin.h:21-111 -------------------------------------------------------------- */
 RT_DEV Real perlin_noise(const rtr_perlin* pnp, V3 p) {

@@ -721,6 +721,114 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_features(const DScene sc, const R
     for (int c = 0; c < RTR_FEAT; ++c) o[c * RTR_BLOCK] = scale * acc[c];
 }
 
+/* rtr_query_closest / rtr_query_occluded: hittable::hit of the scene root (geometry/hittable.h:25-32) for n caller-given
+ * rays, one lane each, with the traversal a render of the scene walks.  The DScene arrives with needs_uv set: the hit
+ * record's (u, v) are computed whether or not a texture reads them.
+ * A bad ray (rtr_ray_bad: include/rtr_hip.h) is answered with a miss before any traversal code.  The shared-reciprocal
+ * divisions hold for t_min >= 2^-100 (div_shared); a wave that holds a ray below that clears its copy of
+ * DScene::shared_div, which makes RayDiv::fast false in every frame of its casts: the plain divisions, wave-uniform,
+ * like the other operands RayDiv::fast votes on.
+ * STAGED: the workgroup moves its RTR_BLOCK contiguous records with coalesced 8-byte loads and stores through dynamic
+ * LDS behind the traversal stack (word `stage_word` of it) instead of every lane moving its own 80 / 88 bytes. */
+#define RTR_QUERY_STAGE_BYTES (RTR_BLOCK * sizeof(rtr_ray_hit)) /* the larger of the two records */
+#ifndef RTR_QUERY_STAGED_DEFAULT
+#define RTR_QUERY_STAGED_DEFAULT 0 /* which form the library launches (RTR_QUERY_STAGED=0/1 overrides it: DESIGN.md 4.6) */
+#endif
+__host__ __device__ inline bool rtr_ray_bad(const rtr_ray& r, bool media) {
+    bool ok = __builtin_isfinite(r.time) && __builtin_isfinite(r.t_min) && !(r.t_max != r.t_max);
+    for (int a = 0; a < 3; ++a) ok = ok && __builtin_isfinite(r.origin[a]) && __builtin_isfinite(r.direction[a]);
+    return !ok || (media && r.rng_state == 0);
+}
+/* this lane's ray; false past the end of the batch */
+template <bool STAGED>
+RT_DEV bool query_fetch(const rtr_ray* __restrict__ rays, long long n, double* stage, rtr_ray& r) {
+    constexpr int W = (int)(sizeof(rtr_ray) / sizeof(double));
+    const long long base = (long long)blockIdx.x * RTR_BLOCK;
+    const bool live = base + threadIdx.x < n;
+    if (STAGED) {
+        const long long left = n - base;
+        const int words = (int)(left < RTR_BLOCK ? left : RTR_BLOCK) * W;
+        const double* src = reinterpret_cast<const double*>(rays + base);
+        for (int w = threadIdx.x; w < words; w += RTR_BLOCK) stage[w] = src[w];
+        __syncthreads();
+        double v[W];
+        for (int k = 0; k < W; ++k) v[k] = live ? stage[threadIdx.x * W + k] : 0.0;
+        __builtin_memcpy(&r, v, sizeof r);
+        __syncthreads(); /* the results go through the same words */
+    } else if (live) {
+        r = rays[base + threadIdx.x];
+    }
+    return live;
+}
+template <bool STAGED>
+RT_DEV void query_store(rtr_ray_hit* __restrict__ hits, long long n, double* stage, bool live, const rtr_ray_hit& h) {
+    constexpr int W = (int)(sizeof(rtr_ray_hit) / sizeof(double));
+    const long long base = (long long)blockIdx.x * RTR_BLOCK;
+    if (STAGED) {
+        double v[W];
+        __builtin_memcpy(v, &h, sizeof h);
+        if (live)
+            for (int k = 0; k < W; ++k) stage[threadIdx.x * W + k] = v[k];
+        __syncthreads();
+        const long long left = n - base;
+        const int words = (int)(left < RTR_BLOCK ? left : RTR_BLOCK) * W;
+        double* dst = reinterpret_cast<double*>(hits + base);
+        for (int w = threadIdx.x; w < words; w += RTR_BLOCK) dst[w] = stage[w];
+    } else if (live) {
+        hits[base + threadIdx.x] = h;
+    }
+}
+template <int TRAV, bool STAGED>
+__global__ void __launch_bounds__(RTR_BLOCK) k_query_closest(DScene sc, const rtr_ray* __restrict__ rays,
+                                                              rtr_ray_hit* __restrict__ hits, long long n, int media, int stage_word) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    double* stage = reinterpret_cast<double*>(lds_stack + stage_word);
+    rtr_ray r;
+    const bool live = query_fetch<STAGED>(rays, n, stage, r);
+    if (!STAGED && !live) return;
+    rtr_ray_hit h;
+    h.t = 0, h.u = 0, h.v = 0;
+    for (int a = 0; a < 3; ++a) h.p[a] = 0, h.n[a] = 0;
+    h.hit = 0, h.front_face = 0, h.material = -1, h.rng_out = r.rng_state;
+    const bool cast = live && !rtr_ray_bad(r, media != 0);
+    if (__any(cast && !(r.t_min >= 0x1p-100))) sc.shared_div = 0;
+    if (cast) {
+        uint32_t rng = r.rng_state;
+        Hit rec;
+        rec.u = rec.v = __builtin_nan("");
+        rec.mat = -1;
+        rec.t = 0, rec.p = mk(0, 0, 0), rec.n = mk(0, 0, 0), rec.front = false;
+        if (cast_closest<TRAV>(sc, ld3(r.origin), ld3(r.direction), r.time, rec, rng, st, r.t_min, r.t_max)) {
+            h.hit = 1, h.front_face = (int)rec.front, h.material = rec.mat;
+            h.t = rec.t, h.u = rec.u, h.v = rec.v;
+            h.p[0] = rec.p.x, h.p[1] = rec.p.y, h.p[2] = rec.p.z;
+            h.n[0] = rec.n.x, h.n[1] = rec.n.y, h.n[2] = rec.n.z;
+        }
+        h.rng_out = rng;
+    }
+    query_store<STAGED>(hits, n, stage, live, h);
+}
+template <int TRAV, bool STAGED>
+__global__ void __launch_bounds__(RTR_BLOCK) k_query_any(DScene sc, const rtr_ray* __restrict__ rays, uint8_t* __restrict__ occluded,
+                                                          uint32_t* __restrict__ rng_out, long long n, int media, int stage_word) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    double* stage = reinterpret_cast<double*>(lds_stack + stage_word);
+    rtr_ray r;
+    if (!query_fetch<STAGED>(rays, n, stage, r)) return; /* (no barrier follows) */
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    uint32_t rng = r.rng_state;
+    bool blocked = false;
+    const bool cast = !rtr_ray_bad(r, media != 0);
+    if (__any(cast && !(r.t_min >= 0x1p-100))) sc.shared_div = 0;
+    if (cast) {
+        blocked = cast_shadow<TRAV>(sc, ld3(r.origin), ld3(r.direction), r.t_max, rng, st, r.time, r.t_min);
+    }
+    occluded[k] = blocked ? 1 : 0;
+    if (rng_out) rng_out[k] = rng;
+}
+
 #ifdef RTR_TU_CAPI /* non-template kernels live in one translation unit */
 __global__ void __launch_bounds__(RTR_BLOCK) k_resolve(const ResolveK R) {
     const RenderK& P = R.r;

@@ -54,6 +54,7 @@ struct rtr_context {
     /* per-render workspace */
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
+    DevBuf b_query; /* rtr_query_closest / rtr_query_occluded: one slice of rays and its results (nothing else uses it) */
     std::vector<int> last_tiles; /* what b_tiles holds */
     WavefrontPool pool;
     void* h_stage = nullptr; /* pinned: rtr_render_tiles_host */
@@ -751,7 +752,7 @@ void rtr_destroy(rtr_context* c) {
     for (rtr_accum* a : c->accums) free_accum(a);
     c->accums.clear();
     DevBuf* bufs[] = {&c->b_nodes, &c->b_kids,  &c->b_mats,    &c->b_tex,   &c->b_perlin, &c->b_images, &c->b_imgbytes,
-                      &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise,
+                      &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise, &c->b_query,
                       &c->b_finst, &c->b_fxf, &c->b_fref, &c->b_fexit, &c->b_fbvh, &c->b_dscene, &c->b_fprim, &c->b_fsub, &c->b_fstep, &c->b_fvisit, &c->b_fscan, &c->b_fleaf, &c->b_fmat, &c->b_fguard};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
@@ -1941,6 +1942,164 @@ int rtr_debug_li(rtr_context* c, const rtr_render_params* p, const int32_t* ijs,
 }
 void rtr_debug_set_error(rtr_context* c, const char* msg) {
     if (c) c->err = msg ? msg : "";
+}
+
+} /* extern "C" */
+
+/* ---- ray queries: hittable::hit of the scene root for caller-given rays ----------------------------------------- */
+namespace {
+
+constexpr int64_t kQuerySlice = (int64_t)1 << 22; /* rays per slice of the host entries */
+
+/* what every query entry checks before any device work */
+int query_check(rtr_context* c, const void* rays, const void* out, int64_t n, int32_t flags) {
+    if (!c) return RTR_ERR_INVALID;
+    if (flags & ~RTR_FLAG_REFERENCE_ORDER) return fail(c, RTR_ERR_INVALID, "rtr_query_*: unknown flag bits");
+    if (n < 0 || (n > 0 && (!rays || !out))) return fail(c, RTR_ERR_INVALID, "rtr_query_*: negative n or NULL array");
+    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_query_* before rtr_upload_scene");
+    return RTR_OK;
+}
+int query_check_rays(rtr_context* c, const rtr_ray* rays, int64_t n) {
+    const bool media = c->info.has_media != 0;
+    for (int64_t k = 0; k < n; ++k)
+        if (rtr_ray_bad(rays[k], media))
+            return fail(c, RTR_ERR_INVALID, "rtr_query_*: bad ray at index " + std::to_string(k) +
+                                                " (non-finite origin / direction / time / t_min, NaN t_max, or rng_state 0 in a "
+                                                "scene with media)");
+    return RTR_OK;
+}
+
+/* the traversal of a query: the one a render with `flags` walks (the per-ray kernels' set: RT_TRAV_FLAT scenes take
+ * RT_TRAV_FAST -- same hits --, a sub-scene 0 with a top tree RT_TRAV_TOP like the megakernel) */
+int query_trav(const rtr_context* c, int flags) {
+    int trav = pick_trav(c, flags);
+    if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST;
+    if (trav == RT_TRAV_FAST && c->ds.top_root0 >= 0) trav = RT_TRAV_TOP;
+    return trav;
+}
+/* the staged record access (k_query_*<.., STAGED>) unless RTR_QUERY_STAGED=0 or the stack leaves no room for it
+ * (tools/time_queries.py measures both forms: DESIGN.md 4.6) */
+bool query_staged(size_t stack) {
+    const char* e = getenv("RTR_QUERY_STAGED");
+    const bool want = e ? e[0] != '0' : RTR_QUERY_STAGED_DEFAULT != 0;
+    return want && stack + RTR_QUERY_STAGE_BYTES <= 160 * 1024;
+}
+
+/* one launch over device arrays on the context stream; hits != nullptr: closest hit, else occlusion */
+int query_launch(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, uint8_t* d_occ, uint32_t* d_rng, int64_t n, int flags) {
+    const int trav = query_trav(c, flags);
+    const size_t stack = stack_bytes(c, trav);
+    const bool staged = query_staged(stack);
+    const size_t lds = stack + (staged ? RTR_QUERY_STAGE_BYTES : 0);
+    const int stage_word = (int)(stack / sizeof(int));
+    const int media = c->info.has_media != 0;
+    DScene ds = c->ds;
+    ds.needs_uv = 1; /* (u, v) of the hit record whether or not a texture reads them */
+    const dim3 grid((unsigned)((n + RTR_BLOCK - 1) / RTR_BLOCK));
+    int rc = RTR_OK;
+#define RTR_LAUNCH_S(T, S)                                                                                              \
+    do {                                                                                                                 \
+        if (d_hits) {                                                                                                    \
+            if ((rc = set_lds(c, k_query_closest<T, S>, lds))) return rc;                                                \
+            hipLaunchKernelGGL((k_query_closest<T, S>), grid, dim3(RTR_BLOCK), lds, c->stream, ds, d_rays, d_hits,       \
+                               (long long)n, media, stage_word);                                                         \
+        } else {                                                                                                         \
+            if ((rc = set_lds(c, k_query_any<T, S>, lds))) return rc;                                                    \
+            hipLaunchKernelGGL((k_query_any<T, S>), grid, dim3(RTR_BLOCK), lds, c->stream, ds, d_rays, d_occ, d_rng,     \
+                               (long long)n, media, stage_word);                                                         \
+        }                                                                                                                \
+    } while (0)
+#define RTR_LAUNCH(T)              \
+    do {                           \
+        if (staged)                \
+            RTR_LAUNCH_S(T, true); \
+        else                       \
+            RTR_LAUNCH_S(T, false); \
+    } while (0)
+    if (trav == RT_TRAV_FAST)
+        RTR_LAUNCH(RT_TRAV_FAST);
+    else if (trav == RT_TRAV_TOP)
+        RTR_LAUNCH(RT_TRAV_TOP);
+    else if (trav == RT_TRAV_PROGRAM)
+        RTR_LAUNCH(RT_TRAV_PROGRAM_EXT);
+    else if (trav == RT_TRAV_MEDIA)
+        RTR_LAUNCH(RT_TRAV_MEDIA);
+    else
+        RTR_LAUNCH(RT_TRAV_EXACT);
+#undef RTR_LAUNCH
+#undef RTR_LAUNCH_S
+    HIPCHK(c, hipGetLastError());
+    return RTR_OK;
+}
+
+/* the host entries: slices of at most kQuerySlice rays through c->b_query, everything stream-ordered on the context
+ * stream (behind a render that is still running; its workspace, statistics and events are not touched) */
+int query_host(rtr_context* c, const rtr_ray* rays, rtr_ray_hit* hits, uint8_t* occ, uint32_t* rng_out, int64_t n, int flags) {
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError(); /* a launch error of an earlier call is not this call's */
+    const int64_t slice = std::min(n, kQuerySlice);
+    const size_t in_bytes = (size_t)slice * sizeof(rtr_ray);
+    const size_t out_bytes = hits ? (size_t)slice * sizeof(rtr_ray_hit) : (size_t)slice * sizeof(uint32_t);
+    const size_t occ_bytes = hits ? 0 : (((size_t)slice + 15) & ~(size_t)15);
+    if (int rc = ensure(c, c->b_query, in_bytes + out_bytes + occ_bytes)) return rc;
+    char* base = static_cast<char*>(c->b_query.p);
+    rtr_ray* d_rays = reinterpret_cast<rtr_ray*>(base);
+    rtr_ray_hit* d_hits = hits ? reinterpret_cast<rtr_ray_hit*>(base + in_bytes) : nullptr;
+    uint32_t* d_rng = hits ? nullptr : reinterpret_cast<uint32_t*>(base + in_bytes);
+    uint8_t* d_occ = hits ? nullptr : reinterpret_cast<uint8_t*>(base + in_bytes + out_bytes);
+    for (int64_t k0 = 0; k0 < n; k0 += slice) {
+        const int64_t m = std::min(slice, n - k0);
+        HIPCHK(c, hipMemcpyAsync(d_rays, rays + k0, (size_t)m * sizeof(rtr_ray), hipMemcpyHostToDevice, c->stream));
+        if (int rc = query_launch(c, d_rays, d_hits, d_occ, d_rng, m, flags)) return rc;
+        if (hits) {
+            HIPCHK(c, hipMemcpyAsync(hits + k0, d_hits, (size_t)m * sizeof(rtr_ray_hit), hipMemcpyDeviceToHost, c->stream));
+        } else {
+            HIPCHK(c, hipMemcpyAsync(occ + k0, d_occ, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+            if (rng_out) HIPCHK(c, hipMemcpyAsync(rng_out + k0, d_rng, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream)); /* the next slice reuses the buffer */
+    }
+    return RTR_OK;
+}
+
+int query_device(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, uint8_t* d_occ, uint32_t* d_rng, int64_t n, int flags,
+                 int blocking) {
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    if (int rc = query_launch(c, d_rays, d_hits, d_occ, d_rng, n, flags)) return rc;
+    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rtr_query_closest(rtr_context* c, const rtr_ray* rays, rtr_ray_hit* hits, int64_t n, int32_t flags) {
+    if (int rc = query_check(c, rays, hits, n, flags)) return rc;
+    if (n == 0) return RTR_OK;
+    if (int rc = query_check_rays(c, rays, n)) return rc;
+    return query_host(c, rays, hits, nullptr, nullptr, n, flags);
+}
+
+int rtr_query_occluded(rtr_context* c, const rtr_ray* rays, uint8_t* occluded, uint32_t* rng_out, int64_t n, int32_t flags) {
+    if (int rc = query_check(c, rays, occluded, n, flags)) return rc;
+    if (n == 0) return RTR_OK;
+    if (int rc = query_check_rays(c, rays, n)) return rc;
+    return query_host(c, rays, nullptr, occluded, rng_out, n, flags);
+}
+
+int rtr_query_closest_device(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, int64_t n, int32_t flags, int blocking) {
+    if (int rc = query_check(c, d_rays, d_hits, n, flags)) return rc;
+    if (n == 0) return RTR_OK;
+    return query_device(c, d_rays, d_hits, nullptr, nullptr, n, flags, blocking);
+}
+
+int rtr_query_occluded_device(rtr_context* c, const rtr_ray* d_rays, uint8_t* d_occluded, uint32_t* d_rng_out, int64_t n,
+                              int32_t flags, int blocking) {
+    if (int rc = query_check(c, d_rays, d_occluded, n, flags)) return rc;
+    if (n == 0) return RTR_OK;
+    return query_device(c, d_rays, nullptr, d_occluded, d_rng_out, n, flags, blocking);
 }
 
 } /* extern "C" */

@@ -14,10 +14,14 @@
  *           [--denoise [ITER]]   with --passes, --adaptive or a plain --spp (then one accumulator pass): the image after the
  *                                   last pass is denoised (include/rtr_hip.h: rtr_accum_denoise, the library's defaults;
  *                                   ITER in 0..10 replaces their iteration count); prints the denoise time
+ *           [--pick i,j]   nothing is rendered: the closest hit of pixel (i, j)'s centre ray -- u = (i + 0.5) / (W - 1),
+ *                                   v = (j + 0.5) / (H - 1), no lens offset, time0 -- through Renderer::closest_hits, as one line
+ *                                   `hit front_face material t p n` with the doubles as %.17g
  */
 #include "rtr_renderer.h"
 
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 /* "0.004" or "1/255"; false unless the whole string is such a number */
@@ -37,7 +41,8 @@ static bool parse_threshold(const char* s, double& out) {
 
 int main(int argc, char** argv) {
     int scene_id = 21, integrator_id = 4, width = 0, spp = 0, bands = 0, repeat = 1, spp_min = 0;
-    bool adaptive = false, denoise = false;
+    bool adaptive = false, denoise = false, pick = false;
+    int pick_i = 0, pick_j = 0;
     int denoise_iter = -1;
     double threshold = 0.0;
     std::vector<int> devices{0}, passes;
@@ -68,6 +73,13 @@ int main(int argc, char** argv) {
                     return 2;
                 }
                 denoise_iter = (int)v;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--pick") && k + 1 < argc) {
+            pick = std::sscanf(argv[++k], "%d,%d", &pick_i, &pick_j) == 2;
+            if (!pick) {
+                std::cerr << "--pick takes a pixel as i,j, not " << argv[k] << "\n";
+                return 2;
             }
         }
         else if (!std::strcmp(argv[k], "--spp-min") && k + 1 < argc) {
@@ -141,6 +153,27 @@ int main(int argc, char** argv) {
     const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);
     RenderBuffer buffer(W, H);
     Renderer renderer(devices);
+    if (pick) {
+        if (pick_i < 0 || pick_i >= W || pick_j < 0 || pick_j >= H) {
+            std::cerr << "--pick: pixel outside the " << W << " x " << H << " image\n";
+            return 2;
+        }
+        if (renderer.upload_scene(config.world, cam, config.background, config.lights) != RTR_OK) {
+            std::cerr << "upload failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        const double u = (pick_i + 0.5) / (W - 1), v = (pick_j + 0.5) / (H - 1);
+        const ray r(cam->origin, cam->lower_left_corner + u * cam->horizontal + v * cam->vertical - cam->origin, cam->time0);
+        const std::vector<rtr_ray_hit> hits = renderer.closest_hits({r});
+        if (hits.size() != 1) {
+            std::cerr << "query failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        const rtr_ray_hit& h = hits[0];
+        std::printf("%d %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", h.hit, h.front_face, h.material, h.t, h.p[0], h.p[1],
+                    h.p[2], h.n[0], h.n[1], h.n[2]);
+        return 0;
+    }
     renderer.set_samples(config.samples_per_pixel);
     switch (integrator_id) { /* main.cpp:80-100 */
     case 0: renderer.set_integrator(make_shared<PathIntegrator>()); break;

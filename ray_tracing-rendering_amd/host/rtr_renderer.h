@@ -356,13 +356,56 @@ class Renderer {
             std::cerr << "render failed (" << m_status << "): " << m_error << "\n";
     }
 
+    /* Ray queries (include/rtr_hip.h: rtr_query_*), on the first context and the scene already uploaded there -- by a
+     * render, or by upload_scene() where nothing is to be rendered.  closest_hits: world->hit(r, t_min, t_max, rec) per
+     * ray as rtr_ray_hit records (material = the flattened scene's index); occluded: its boolean per ray.  Scenes with
+     * media draw from xorshift32 state 1 for every ray.  An empty vector and last_status() / last_error() on failure. */
+    int upload_scene(shared_ptr<hittable> world, shared_ptr<camera> cam, const color& background,
+                     const std::vector<shared_ptr<Light>>& lights = {}) {
+        const bool same_scene = world == m_world && cam == m_cam && lights == m_lights &&
+                                background[0] == m_scene_bg[0] && background[1] == m_scene_bg[1] && background[2] == m_scene_bg[2];
+        m_status = prepare(*world, *cam, background, lights, same_scene && m_scene_valid, false);
+        if (m_scene_valid) m_world = world, m_cam = cam, m_lights = lights;
+        return m_status;
+    }
+    std::vector<rtr_ray_hit> closest_hits(const std::vector<ray>& rays, double t_min = 0.001, double t_max = infinity) {
+        std::vector<rtr_ray_hit> hits(rays.size());
+        const std::vector<rtr_ray> q = query_rays(rays, t_min, t_max);
+        if (m_status == RTR_OK && (m_status = rtr_query_closest(m_ctx[0], q.data(), hits.data(), (int64_t)q.size(), 0)))
+            m_error = rtr_last_error(m_ctx[0]);
+        if (m_status != RTR_OK) hits.clear();
+        return hits;
+    }
+    std::vector<uint8_t> occluded(const std::vector<ray>& rays, double t_min = 0.001, double t_max = infinity) {
+        std::vector<uint8_t> occ(rays.size());
+        const std::vector<rtr_ray> q = query_rays(rays, t_min, t_max);
+        if (m_status == RTR_OK && (m_status = rtr_query_occluded(m_ctx[0], q.data(), occ.data(), nullptr, (int64_t)q.size(), 0)))
+            m_error = rtr_last_error(m_ctx[0]);
+        if (m_status != RTR_OK) occ.clear();
+        return occ;
+    }
+
   private:
+    std::vector<rtr_ray> query_rays(const std::vector<ray>& rays, double t_min, double t_max) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        std::vector<rtr_ray> q(rays.size());
+        for (size_t k = 0; k < rays.size(); ++k) {
+            const point3 o = rays[k].origin();
+            const vec3 d = rays[k].direction();
+            for (int a = 0; a < 3; ++a) q[k].origin[a] = o[a], q[k].direction[a] = d[a];
+            q[k].time = rays[k].time(), q[k].t_min = t_min, q[k].t_max = t_max;
+            q[k].rng_state = 1u, q[k].pad = 0;
+        }
+        return q;
+    }
     /* what render(), render_progressive() and render_adaptive() check and upload before they render */
     int prepare(const hittable& world, const camera& cam, const color& background, const std::vector<shared_ptr<Light>>& lights,
-                bool scene_on_device) {
+                bool scene_on_device, bool need_integrator = true) {
         if (m_create_status != RTR_OK) return m_error = m_create_error, m_create_status;
         if (m_ctx.empty()) return m_error = rtr_last_error(nullptr), RTR_ERR_DEVICE;
-        if (!m_integrator) return m_error = "no integrator set", RTR_ERR_INVALID;
+        if (need_integrator && !m_integrator) return m_error = "no integrator set", RTR_ERR_INVALID;
         /* flatten + upload once per scene, not once per render() call */
         if (!scene_on_device) {
             m_scene_valid = false;

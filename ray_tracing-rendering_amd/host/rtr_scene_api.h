@@ -71,9 +71,9 @@ inline uint32_t& rng_state() {
     static thread_local uint32_t s = static_cast<uint32_t>(std::hash<std::thread::id>{}(std::this_thread::get_id()));
     return s;
 }
-[[noreturn]] inline void device_only(const char* what) {
+[[noreturn]] inline void device_only(const char* what, const char* instead = nullptr) {
     throw std::logic_error(std::string(what) + " runs in the HIP kernels; flatten the scene and render through "
-                                               "rtr_hip.h (no CPU fallback)");
+                                               "rtr_hip.h (no CPU fallback)" + (instead ? std::string("; ") + instead : std::string()));
 }
 } // namespace rtr
 
@@ -289,7 +289,10 @@ struct hit_record { /* hittable.h:10-23 */
 class hittable {
   public:
     virtual ~hittable() = default;
-    virtual bool hit(const ray&, double, double, hit_record&) const { rtr::device_only("hittable::hit"); }
+    /* (a graph node has no context: the hit of the uploaded world is Renderer::closest_hits / Renderer::occluded) */
+    virtual bool hit(const ray&, double, double, hit_record&) const {
+        rtr::device_only("hittable::hit", "for the uploaded world call Renderer::closest_hits (rtr_query_closest)");
+    }
     virtual bool bounding_box(double time0, double time1, aabb& output_box) const = 0;
     virtual int rtr_flatten(rtr::Flattener&) const; /* default: unsupported subclass */
 };

@@ -24,7 +24,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_synchronize", "rtr_cancel", "rtr_get_stats", "rtr_last_error", "rtr_sample_seed", "rtr_validate_scene",
            "rtr_accum_create", "rtr_accum_render", "rtr_accum_resolve", "rtr_accum_tiles", "rtr_accum_destroy",
            "rtr_accum_create_ex", "rtr_accum_render_tiles", "rtr_accum_moments", "rtr_accum_errors", "rtr_accum_refine",
-           "rtr_denoise_defaults", "rtr_accum_features", "rtr_accum_denoise", "rtr_denoise_host")
+           "rtr_denoise_defaults", "rtr_accum_features", "rtr_accum_denoise", "rtr_denoise_host",
+           "rtr_query_closest", "rtr_query_occluded", "rtr_query_closest_device", "rtr_query_occluded_device")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
@@ -104,6 +105,10 @@ def lib():
     L.rtr_accum_features.argtypes = [vp, vp, C.c_int32, vp, C.c_int64]
     L.rtr_accum_denoise.argtypes = [vp, vp, P(A.DenoiseParamsC), vp, C.c_int64, vp]
     L.rtr_denoise_host.argtypes = [vp, P(A.DenoiseParamsC), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+    L.rtr_query_closest.argtypes = [vp, vp, vp, C.c_int64, C.c_int32]
+    L.rtr_query_occluded.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32]
+    L.rtr_query_closest_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int]
+    L.rtr_query_occluded_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -277,6 +282,77 @@ class Context:
         out = np.zeros((n, 3), dtype=np.float64)
         self._chk(self._L.rtr_li_rays(self._h, C.byref(params), rays.ctypes.data, out.ctypes.data, n))
         return out
+
+    # ray queries (include/rtr_hip.h: rtr_query_*)
+    @staticmethod
+    def make_rays(origins, directions, times=None, t_min=0.001, t_max=np.inf, rng_states=None):
+        """An ``RAY_DTYPE`` array from (n, 3) origins and directions; ``times`` (default 0), ``t_min``, ``t_max`` and
+        ``rng_states`` (default 1; read only where the scene has media) are scalars or (n,) arrays."""
+        o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+        rays = np.zeros(len(o), dtype=A.RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+        rays["time"] = 0.0 if times is None else times
+        rays["t_min"], rays["t_max"] = t_min, t_max
+        rays["rng_state"] = 1 if rng_states is None else rng_states
+        return rays
+
+    def _rays(self, origins, directions, times, t_min, t_max, rng_states):
+        if isinstance(origins, np.ndarray) and origins.dtype == A.RAY_DTYPE:
+            return np.ascontiguousarray(origins)
+        return self.make_rays(origins, directions, times, t_min, t_max, rng_states)
+
+    def query_closest(self, origins, directions=None, times=None, t_min=0.001, t_max=np.inf, rng_states=None,
+                      reference_order=False, out=None):
+        """``world->hit(ray, t_min, t_max, rec)`` of the uploaded scene for n rays (rtr_query_closest): a structured
+        ``RAY_HIT_DTYPE`` array.  ``origins`` may be a ready ``RAY_DTYPE`` array (the other ray arguments are then
+        ignored).  Blocking; raises RtrError (RTR_ERR_INVALID) naming the first bad ray, with ``out`` untouched."""
+        rays = self._rays(origins, directions, times, t_min, t_max, rng_states)
+        if out is None:
+            out = np.zeros(len(rays), dtype=A.RAY_HIT_DTYPE)
+        elif out.dtype != A.RAY_HIT_DTYPE or len(out) < len(rays) or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous RAY_HIT_DTYPE array of at least %d records" % len(rays))
+        flags = A.FLAG_REFERENCE_ORDER if reference_order else 0
+        self._chk(self._L.rtr_query_closest(self._h, rays.ctypes.data, out.ctypes.data, len(rays), flags))
+        return out
+
+    def query_occluded(self, origins, directions=None, times=None, t_min=0.001, t_max=np.inf, rng_states=None,
+                       reference_order=False, return_rng=False):
+        """Whether anything is hit in [t_min, t_max] (rtr_query_occluded): a bool array, or with ``return_rng`` the
+        pair (bool array, uint32 generator states after the call)."""
+        rays = self._rays(origins, directions, times, t_min, t_max, rng_states)
+        occ = np.zeros(len(rays), dtype=np.uint8)
+        rng = np.zeros(len(rays), dtype=np.uint32) if return_rng else None
+        flags = A.FLAG_REFERENCE_ORDER if reference_order else 0
+        self._chk(self._L.rtr_query_occluded(self._h, rays.ctypes.data, occ.ctypes.data,
+                                             rng.ctypes.data if return_rng else None, len(rays), flags))
+        return (occ.astype(bool), rng) if return_rng else occ.astype(bool)
+
+    def query_closest_into(self, rays_ptr, hits_ptr, n, reference_order=False, blocking=False):
+        """rtr_query_closest_device: n ``RAY_DTYPE`` records at device pointer ``rays_ptr`` -> ``RAY_HIT_DTYPE`` records at
+        ``hits_ptr`` (e.g. a torch tensor's ``data_ptr()``), on the context stream behind what is queued there."""
+        self._chk(self._L.rtr_query_closest_device(self._h, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), int(n),
+                                                   A.FLAG_REFERENCE_ORDER if reference_order else 0, 1 if blocking else 0))
+
+    def query_occluded_into(self, rays_ptr, occluded_ptr, n, rng_out_ptr=None, reference_order=False, blocking=False):
+        """rtr_query_occluded_device: one byte per ray at ``occluded_ptr`` and, unless None, one uint32 at ``rng_out_ptr``."""
+        self._chk(self._L.rtr_query_occluded_device(self._h, C.c_void_p(rays_ptr), C.c_void_p(occluded_ptr),
+                                                    C.c_void_p(rng_out_ptr or None), int(n),
+                                                    A.FLAG_REFERENCE_ORDER if reference_order else 0, 1 if blocking else 0))
+
+    def camera_ray(self, params, i, j):
+        """The pixel-centre ray of pixel (i, j) of the image ``params`` describes, as a one-element ``RAY_DTYPE`` array with
+        the query defaults (t_min 0.001, t_max inf): u = (i + 0.5) / (W - 1), v = (j + 0.5) / (H - 1), origin = the
+        camera's, direction = lower_left_corner + u horizontal + v vertical - origin in the reference's operation order
+        (camera.h get_ray without a lens offset), time = time0; no draw."""
+        if self.scene is None:
+            raise RtrError(A.RTR_ERR_NO_SCENE, "camera_ray before upload")
+        cam = self.scene.camera
+        u = (i + 0.5) / (params.image_width - 1)
+        v = (j + 0.5) / (params.image_height - 1)
+        o = np.asarray(cam["origin"], dtype=np.float64).reshape(3)
+        d = (np.asarray(cam["lower_left_corner"], dtype=np.float64).reshape(3) + u * np.asarray(cam["horizontal"], dtype=np.float64).reshape(3)
+             + v * np.asarray(cam["vertical"], dtype=np.float64).reshape(3)) - o
+        return self.make_rays(o[None, :], d[None, :], times=float(np.asarray(cam["time0"]).reshape(-1)[0]))
 
     def accumulator(self, params, moments=False):
         """A progressive accumulator (rtr_accum_*) bound to ``params``' region, image size, tile sharding, seed,
