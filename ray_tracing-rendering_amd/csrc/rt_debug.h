@@ -12,7 +12,7 @@ struct rtr_debug_view {
     DScene ds;          /* device pointers of the uploaded scene */
     hipStream_t stream; /* the context's stream */
     int device, n_cus, n_materials;
-    int trav;           /* RT_TRAV_* a call with `flags` uses (RT_TRAV_FLAT reported as RT_TRAV_FAST: same results) */
+    int trav;           /* RT_TRAV_* template value of the per-ray kernels for a call with `flags` (per_ray_trav, rtr_capi.hip) */
     size_t stack_bytes; /* LDS traversal stack per workgroup of that traversal */
 };
 /* the kernels the last render call launched, recorded on the host when they are enqueued (no device work) */

@@ -116,6 +116,42 @@ RT_DEV V3 acc_start(const RenderK& P, int slot) {
     return mk(a[0], a[RTR_BLOCK], a[2 * RTR_BLOCK]);
 }
 
+/* cycles per phase of the lockstep loops, summed per wave into RenderK::stats[3..6] (builds with -DRTR_PHASE_CLOCKS) */
+#ifdef RTR_PHASE_CLOCKS
+struct PhaseClocks {
+    long long closest = 0, shade = 0, shadow = 0, other = 0, t = wall_clock64();
+    RT_DEV void flush(const RenderK& P) const {
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&P.stats[3], (unsigned long long)closest);
+            atomicAdd(&P.stats[4], (unsigned long long)shade);
+            atomicAdd(&P.stats[5], (unsigned long long)shadow);
+            atomicAdd(&P.stats[6], (unsigned long long)other);
+        }
+    }
+};
+#define RTR_CLK(phase) do { const long long now_ = wall_clock64(); clk.phase += now_ - clk.t; clk.t = now_; } while (0)
+#else
+struct PhaseClocks {
+    RT_DEV void flush(const RenderK&) const {}
+};
+#define RTR_CLK(phase) do { } while (0)
+#endif
+
+/* renderer.h:73-75 under the per-sample seed: the camera ray of sample s of the lane's pixel and the parked words of a
+ * new path.  K_* : the variant's parked words (PK_* / SK_*); K_L < 0: the loop clears the radiance word itself (the
+ * pair cast, step (3)) */
+template <int K_THR, int K_L, int K_PDF>
+RT_DEV void begin_sample(const DScene& sc, const RenderK& P, const Park& pk, int slot, int s, uint32_t& rng, PathState& ps) {
+    int pi, pj;
+    bool in_region;
+    tile_pixel(P, slot, threadIdx.x, pi, pj, in_region); /* recomputed: not worth two live registers */
+    camera_sample(sc, P, pi, pj, s, rng, ps.ro, ps.rd, ps.tm);
+    ps.depth = 0, ps.specular_bounce = false;
+    pk.set3(K_THR, mk(1.0, 1.0, 1.0));
+    if (K_L >= 0) pk.set3(K_L, mk(0.0, 0.0, 0.0));
+    pk.set(K_PDF, 0.0);
+}
+
 /* ACC: 0 = a one-shot render; 1 = an accumulator pass (rtr_accum_*) -- a kernel of its own, so that the registers of
  * the one-shot kernels do not pay for its pointers: workgroup b renders the active tile slot RenderK::active[b] from
  * its sample count RenderK::tile_s0 to RenderK::tile_s1 with the sums RenderK::acc_in; 2 = a pass of an accumulator
@@ -175,22 +211,9 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             accp[0] = a0.x, accp[RTR_BLOCK] = a0.y, accp[2 * RTR_BLOCK] = a0.z;
         }
         if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
-        auto begin_sample = [&]() { /* renderer.h:73-75 under the per-sample seed */
-            int pi, pj;
-            bool in_region;
-            tile_pixel(P, slot, threadIdx.x, pi, pj, in_region);
-            rng = rtr_sample_seed_inline(P.seed, P.W, pi, pj, s);
-            const Real u = (pi + rng_next(rng)) / (P.W - 1);
-            const Real v = (pj + rng_next(rng)) / (P.H - 1);
-            camera_get_ray(sc.camera, u, v, rng, ps.ro, ps.rd, ps.tm);
-            ps.depth = 0, ps.specular_bounce = false;
-            pk.set3(SK_THR, mk(1.0, 1.0, 1.0));
-            pk.set3(SK_L, mk(0.0, 0.0, 0.0));
-            pk.set(SK_PDF, 0.0);
-        };
         pk.set(SK_NCLOSEST, 0.0);
         pk.set(SK_NSHADOW, 0.0);
-        if (!done) begin_sample();
+        if (!done) begin_sample<SK_THR, SK_L, SK_PDF>(sc, P, pk, slot, s, rng, ps);
         __syncthreads();
         for (;;) {
             bool pending = false, ended = false, shade_me = false;
@@ -321,7 +344,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 ++n_samples;
                 ++s;
                 done = s >= s_end || ((s & 7) == 0 && render_cancelled(P));
-                if (!done) begin_sample();
+                if (!done) begin_sample<SK_THR, SK_L, SK_PDF>(sc, P, pk, slot, s, rng, ps);
             }
         }
         cnt.closest = (uint32_t)pk.get(SK_NCLOSEST);
@@ -332,12 +355,9 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         while (!done) {
             if (fresh) { /* renderer.h:73-75 under the per-sample seed */
                 if ((s & 7) == 0 && render_cancelled(P)) break;
-                rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
-                const Real u = (i + rng_next(rng)) / (P.W - 1);
-                const Real v = (j + rng_next(rng)) / (P.H - 1);
                 V3 ro, rd;
                 Real tm;
-                camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+                camera_sample(sc, P, i, j, s, rng, ro, rd, tm);
                 path_begin(ps, ro, rd, tm);
                 fresh = false;
             }
@@ -364,33 +384,16 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
          * terms reach L in the reference's order (the light sample of bounce k, then the emission or miss term of bounce
          * k + 1), samples reach the pixel sum in sample order, and a lane whose sample ended keeps that sample's L in
          * PK_L, and the origin of its shadow ray in `so`, while it casts the new sample's camera ray. */
-        auto begin_sample = [&]() { /* renderer.h:73-75 under the per-sample seed; PK_L is cleared by step (3) */
-            int pi, pj;
-            bool in_region;
-            tile_pixel(P, slot, threadIdx.x, pi, pj, in_region);
-            rng = rtr_sample_seed_inline(P.seed, P.W, pi, pj, s);
-            const Real u = (pi + rng_next(rng)) / (P.W - 1);
-            const Real v = (pj + rng_next(rng)) / (P.H - 1);
-            camera_get_ray(sc.camera, u, v, rng, ps.ro, ps.rd, ps.tm);
-            ps.depth = 0, ps.specular_bounce = false;
-            pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
-            pk.set(PK_PDF, 0.0);
-        };
         pk.set(PK_NCLOSEST, 0.0);
         pk.set(PK_NSHADOW, 0.0);
         pk.set3(PK_L, mk(0.0, 0.0, 0.0));
-        if (!done) begin_sample();
+        if (!done) begin_sample<PK_THR, -1, PK_PDF>(sc, P, pk, slot, s, rng, ps);
         bool pending = false; /* a shadow request is parked: PK_SWI, PK_STMAX, PK_CONTRIB, origin `so` */
         bool settle = false;  /* the sample in PK_L has ended: add it to the pixel sum once its shadow ray is resolved */
         V3 so = mk(0.0, 0.0, 0.0);
-#ifdef RTR_PHASE_CLOCKS /* closest = the pair casts, shadow = resolving them + settling ended samples */
-        long long clk_closest = 0, clk_shade = 0, clk_shadow = 0, clk_other = 0, clk_t = wall_clock64();
-#define RTR_CLK(acc) do { const long long now_ = wall_clock64(); acc += now_ - clk_t; clk_t = now_; } while (0)
-#else
-#define RTR_CLK(acc) do { } while (0)
-#endif
+        PhaseClocks clk; /* closest = the pair casts, shadow = resolving them + settling ended samples */
         while (!done || settle) {
-            RTR_CLK(clk_other);
+            RTR_CLK(other);
             RT_REGION(RG_OTHER);
             const bool cast_a = !done;
             Real a_tmax = RT_INF, b_tmax = 0.0;
@@ -410,7 +413,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 so = mk(0.0, 0.0, 0.0);
             }
             trace_pair(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
-            RTR_CLK(clk_closest);
+            RTR_CLK(closest);
             RT_REGION(RG_OTHER);
             if (pending && b_ref < 0) pk.set3(PK_L, add(pk.get3(PK_L), pk.get3(PK_CONTRIB))); /* mis_path_integrator.h:210-213 */
             pending = false;
@@ -425,7 +428,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 pk.set3(PK_L, mk(0.0, 0.0, 0.0));
                 settle = false;
             }
-            RTR_CLK(clk_shadow);
+            RTR_CLK(shadow);
             if (cast_a) {
                 bool ended;
                 if (a_ref < 0) {
@@ -457,67 +460,41 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                     pk.set(PK_PDF, ps.prev_bsdf_pdf);
                     ended = !go || ++ps.depth >= P.max_depth;
                 }
-                RTR_CLK(clk_shade);
+                RTR_CLK(shade);
                 RT_REGION(RG_REGEN);
                 if (ended) {
                     settle = true;
                     ++n_samples;
                     ++s;
                     done = s >= s_end || ((s & 7) == 0 && render_cancelled(P)); /* (see the split loop) */
-                    if (!done) begin_sample();
+                    if (!done) begin_sample<PK_THR, -1, PK_PDF>(sc, P, pk, slot, s, rng, ps);
                 }
             }
         }
         cnt.closest = (uint32_t)pk.get(PK_NCLOSEST);
         cnt.shadow = (uint32_t)pk.get(PK_NSHADOW);
-#ifdef RTR_PHASE_CLOCKS
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&P.stats[3], (unsigned long long)clk_closest);
-            atomicAdd(&P.stats[4], (unsigned long long)clk_shade);
-            atomicAdd(&P.stats[5], (unsigned long long)clk_shadow);
-            atomicAdd(&P.stats[6], (unsigned long long)clk_other);
-        }
-#endif
-#undef RTR_CLK
+        clk.flush(P);
     } else {
         /* Without media the shadow ray draws nothing, so it can be cast AFTER the BSDF sample of
          * the same bounce, when the hit record is dead.  Every live lane runs the same phases in
          * every iteration (closest hit, shade, shadow ray, end-of-sample + regeneration), so a wave
          * stays in lockstep although path lengths differ; the sums still see their terms in the
          * reference's order (emission, then the light sample of the same bounce). */
-        auto begin_sample = [&]() { /* renderer.h:73-75 under the per-sample seed */
-            int pi, pj;
-            bool in_region;
-            tile_pixel(P, slot, threadIdx.x, pi, pj, in_region); /* recomputed: not worth two live registers */
-            rng = rtr_sample_seed_inline(P.seed, P.W, pi, pj, s);
-            const Real u = (pi + rng_next(rng)) / (P.W - 1);
-            const Real v = (pj + rng_next(rng)) / (P.H - 1);
-            camera_get_ray(sc.camera, u, v, rng, ps.ro, ps.rd, ps.tm);
-            ps.depth = 0, ps.specular_bounce = false;
-            pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
-            pk.set3(PK_L, mk(0.0, 0.0, 0.0));
-            pk.set(PK_PDF, 0.0);
-        };
         /* cast counters live in LDS as well (exact in a double up to 2^53) */
         pk.set(PK_NCLOSEST, 0.0);
         pk.set(PK_NSHADOW, 0.0);
-        if (!done) begin_sample();
-#ifdef RTR_PHASE_CLOCKS
-        long long clk_closest = 0, clk_shade = 0, clk_shadow = 0, clk_other = 0, clk_t = wall_clock64();
-#define RTR_CLK(acc) do { const long long now_ = wall_clock64(); acc += now_ - clk_t; clk_t = now_; } while (0)
-#else
-#define RTR_CLK(acc) do { } while (0)
-#endif
+        if (!done) begin_sample<PK_THR, PK_L, PK_PDF>(sc, P, pk, slot, s, rng, ps);
+        PhaseClocks clk;
         while (!done) {
             bool pending = false, ended = false;
-            RTR_CLK(clk_other);
+            RTR_CLK(other);
             RT_REGION(RG_OTHER);
             {
                 Hit rec;
                 rec.u = 0, rec.v = 0;
                 pk.set(PK_NCLOSEST, pk.get(PK_NCLOSEST) + 1.0);
                 const bool hit_any = cast_closest<TRAV, MS == RT_MS_FULL>(sc, ps.ro, ps.rd, ps.tm, rec, rng, st);
-                RTR_CLK(clk_closest);
+                RTR_CLK(closest);
                 if (!hit_any) {
                     RT_REGION(RG_MISS);
                     pk.set3(PK_L, add(pk.get3(PK_L), miss_radiance<INTEG, MS>(sc, pk.get3(PK_THR), ps.ro, ps.rd, ps.depth,
@@ -569,14 +546,14 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                     ended = !go || ++ps.depth >= P.max_depth;
                 }
             }
-            RTR_CLK(clk_shade);
+            RTR_CLK(shade);
             RT_REGION(RG_OTHER);
             if (pending) { /* mis_path_integrator.h:210-213, origin = the hit point = ps.ro */
                 pk.set(PK_NSHADOW, pk.get(PK_NSHADOW) + 1.0);
                 if (!cast_shadow<TRAV>(sc, ps.ro, pk.get3(PK_SWI), pk.get(PK_STMAX), rng, st))
                     pk.set3(PK_L, add(pk.get3(PK_L), pk.get3(PK_CONTRIB)));
             }
-            RTR_CLK(clk_shadow);
+            RTR_CLK(shadow);
             RT_REGION(RG_REGEN);
             if (ended) {
                 pk.set3(PK_ACC, add(pk.get3(PK_ACC), pk.get3(PK_L))); /* renderer.h:77-78 */
@@ -589,19 +566,12 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 /* rtr_cancel(): polled every 8th sample of a pixel -- the load is a dependent memory round
                  * trip in the lane's critical path */
                 done = s >= s_end || ((s & 7) == 0 && render_cancelled(P));
-                if (!done) begin_sample();
+                if (!done) begin_sample<PK_THR, PK_L, PK_PDF>(sc, P, pk, slot, s, rng, ps);
             }
         }
         cnt.closest = (uint32_t)pk.get(PK_NCLOSEST);
         cnt.shadow = (uint32_t)pk.get(PK_NSHADOW);
-#ifdef RTR_PHASE_CLOCKS
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&P.stats[3], (unsigned long long)clk_closest);
-            atomicAdd(&P.stats[4], (unsigned long long)clk_shade);
-            atomicAdd(&P.stats[5], (unsigned long long)clk_shadow);
-            atomicAdd(&P.stats[6], (unsigned long long)clk_other);
-        }
-#endif
+        clk.flush(P);
     }
 #ifdef RTR_REGION_PROFILE
     RT_REGION(RG_OTHER);
@@ -660,10 +630,7 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_li(const DScene sc, const RenderK
         ro = ld3(r.origin), rd = ld3(r.direction), tm = r.time, rng = r.rng_state;
     } else {
         const int i = ijs[3 * k], j = ijs[3 * k + 1], s = ijs[3 * k + 2];
-        rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
-        const Real u = (i + rng_next(rng)) / (P.W - 1);
-        const Real v = (j + rng_next(rng)) / (P.H - 1);
-        camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+        camera_sample(sc, P, i, j, s, rng, ro, rd, tm);
     }
     PathState ps;
     path_begin(ps, ro, rd, tm);
@@ -693,12 +660,10 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_features(const DScene sc, const R
     if (!active) return;
     double acc[RTR_FEAT];
     for (int s = 0; s < K; ++s) {
-        uint32_t rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
-        const Real u = (i + rng_next(rng)) / (P.W - 1);
-        const Real v = (j + rng_next(rng)) / (P.H - 1);
+        uint32_t rng;
         V3 ro, rd;
         Real tm;
-        camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+        camera_sample(sc, P, i, j, s, rng, ro, rd, tm);
         Hit rec;
         rec.u = 0, rec.v = 0;
         double f[RTR_FEAT] = {1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0}; /* a miss */

@@ -1,8 +1,13 @@
 /*
  * rt_launch.h -- host-side seams between the translation units of librtr_hip.so.  The kernels are
- * compiled in parallel: rtr_capi.hip (C ABI, scene upload, unit-test kernels, k_resolve), rtr_mega.hip
+ * compiled in parallel: rtr_capi.hip (C ABI, scene upload, per-ray kernels, k_resolve), rtr_mega.hip
  * three times (one integrator group each: RTR_MEGA_GROUP 0 = MIS, 1 = RR + path, 2 = PBR + NEE) and
  * rtr_wavefront.hip (stage kernels + their host driver).
+ *
+ * Which k_mega instantiation a render runs is decided once, by mega_variant() in rtr_capi.hip; the
+ * MegaVariant travels in MegaLaunch to the group's unit, which looks it up in its explicit list of
+ * instantiations.  kernel_lds() is the one LDS-limit check of every launcher, and dispatch_trav() the
+ * one place a runtime RT_TRAV_* becomes a template argument of the per-ray kernels.
  */
 #pragma once
 
@@ -10,6 +15,7 @@
 
 #include <atomic>
 #include <string>
+#include <utility>
 
 /* which instantiation a launch actually ran, recorded on the host (rtr_debug_last_kernel) */
 struct LaunchedKernel {
@@ -19,13 +25,24 @@ struct LaunchedKernel {
     int phases = 0;  /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched */
 };
 
-/* what rtr_render_device decided about one megakernel launch */
+/* the k_mega<integ, trav, ms, sorted, ACC, pair> a render runs (ACC follows from the call: MegaLaunch::accum) */
+struct MegaVariant {
+    int integ, trav, ms; /* RTR_INTEGRATOR_*, RT_TRAV_* template value, RT_MS_* */
+    bool sorted, pair;   /* the sorted instantiation (RTR_FLAG_SORTED_SHADING) / the pair-cast twin of a flat MIS kernel */
+};
+/* what mega_variant() needs to know about the uploaded scene (rtr_upload_scene) */
+struct MegaFacts {
+    bool top_tree;        /* sub-scene 0 has a top tree: the per-lane instance walk (FSub) */
+    bool flat_guarded;    /* a flat scene with guarded references (hollow spheres) */
+    bool guarded_program; /* the program holds guarded steps or media under wrappers (RT_TRAV_PROGRAM_EXT kernels) */
+    bool lean, quad_only, needs_uv; /* material / light set */
+    bool pair_cast;       /* DScene::pair_cast */
+    int n_materials;
+};
+
+/* one megakernel launch */
 struct MegaLaunch {
-    int integrator, trav;
-    bool lean, quadlit; /* material / light set of the scene (rtr_upload_scene) */
-    bool sorted;        /* RTR_FLAG_SORTED_SHADING and a sorted instantiation exists for this launch (rt_kernels.h) */
-    bool pair;          /* the pair-cast twin of a flat MIS kernel (DScene::pair_cast, no RTR_FLAG_SPLIT_CASTS) */
-    bool program_ext;   /* RT_TRAV_PROGRAM: the program holds guarded steps or media under wrappers (RT_TRAV_PROGRAM_EXT kernels) */
+    MegaVariant variant;
     int accum;          /* 0, or an accumulator pass: the k_mega<..., ACC = 1> twin of the variant, 2 with moments */
     size_t lds;         /* traversal stack + parked path state, bytes per workgroup */
     int stack_words;
@@ -34,7 +51,6 @@ struct MegaLaunch {
     RenderK P;
     bool dry;           /* only what can fail without touching the stream: LDS attribute, occupancy query */
     int* blocks_per_cu; /* dry: resident workgroups per CU of the variant that would run */
-    LaunchedKernel* launched; /* not dry: receives the instantiation launched (may be null) */
 };
 /* return an rtr_status; `err` receives the text of a failure */
 int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err);
@@ -42,6 +58,32 @@ int rtr_mega_launch_rr_path(const MegaLaunch& L, std::string& err);
 int rtr_mega_launch_pbr_nee(const MegaLaunch& L, std::string& err);
 
 void rtr_launch_resolve(const ResolveK& R, hipStream_t stream);
+
+/* The per-lane traversal stack lives in LDS: a graph that needs more than the CU has (e.g. the reference-order walk
+ * of a hittable_list with thousands of direct children) cannot run that way.  `static_bytes`: the kernel's own static
+ * LDS, which counts against the same 160 KiB.  Raises the kernel's dynamic limit where the launch needs it. */
+template <typename K>
+int kernel_lds(K kernel, size_t dynamic_bytes, size_t static_bytes, std::string& err) {
+    if (dynamic_bytes + static_bytes > 160 * 1024) {
+        err = "this traversal of the scene needs a deeper stack than 160 KiB of LDS holds";
+        return RTR_ERR_UNSUPPORTED;
+    }
+    if (dynamic_bytes <= 64 * 1024) return RTR_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)dynamic_bytes);
+    if (e == hipSuccess) return RTR_OK;
+    err = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e);
+    return RTR_ERR_DEVICE;
+}
+
+/* Runtime traversal -> template argument: calls f(std::integral_constant<int, T>{}) for the T among Ts that equals
+ * `trav`; false, and no call, when none does.  Ts is the set of instantiations the caller's kernel has. */
+template <int... Ts>
+using TravSet = std::integer_sequence<int, Ts...>;
+template <int... Ts, typename F>
+bool dispatch_trav(TravSet<Ts...>, int trav, F&& f) {
+    return ((trav == Ts && (f(std::integral_constant<int, Ts>{}), true)) || ...);
+}
 
 struct WavefrontPool {
     void* slab = nullptr;

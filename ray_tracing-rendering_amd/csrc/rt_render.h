@@ -54,6 +54,15 @@ RT_DEV void tile_pixel(const RenderK& P, int slot, int tid, int& i, int& j, bool
     active = i >= P.x0 && i < P.x1 && j >= P.y0 && j < P.y1;
 }
 
+/* sample s of pixel (i, j): the generator under the per-sample seed, its two jitter draws and the camera ray
+ * (renderer.h:73-75); rng goes on from its state after get_ray */
+RT_DEV void camera_sample(const DScene& sc, const RenderK& P, int i, int j, int s, uint32_t& rng, V3& ro, V3& rd, Real& tm) {
+    rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
+    const Real u = (i + rng_next(rng)) / (P.W - 1);
+    const Real v = (j + rng_next(rng)) / (P.H - 1);
+    camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+}
+
 /* samples [s0, s1) of chunk c of a pixel */
 RT_DEV void chunk_range(const RenderK& P, int c, int& s0, int& s1) {
     if (P.small_spp == 0) {

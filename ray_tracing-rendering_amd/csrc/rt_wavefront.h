@@ -256,10 +256,7 @@ RT_DEV bool wf_extend_load(const DScene& sc, const WfState& S, const RenderK& P,
             return false;
         }
         stv(S.ax, S.ay, S.az, slot, acc);
-        rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
-        const Real u = (i + rng_next(rng)) / (P.W - 1);
-        const Real v = (j + rng_next(rng)) / (P.H - 1);
-        camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+        camera_sample(sc, P, i, j, s, rng, ro, rd, tm);
         stv(S.ox, S.oy, S.oz, slot, ro);
         stv(S.dx, S.dy, S.dz, slot, rd);
         S.tm[slot] = tm;

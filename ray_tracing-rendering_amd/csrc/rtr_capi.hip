@@ -425,57 +425,91 @@ int pick_trav(const rtr_context* c, int flags) {
     return c->flat_scene ? RT_TRAV_FLAT : RT_TRAV_FAST;
 }
 size_t stack_bytes(const rtr_context* c, int trav) {
-    const int words = trav == RT_TRAV_FAST || trav == RT_TRAV_FLAT || trav == RT_TRAV_PROGRAM || trav == RT_TRAV_TOP || trav == RT_TRAV_FLAT_GUARD ? c->fast_stack_words
-                                                                      : c->info.stack_words + c->walk_extra_words;
+    const bool compiled = trav == RT_TRAV_FAST || trav == RT_TRAV_FLAT || rt_is_program(trav) || trav == RT_TRAV_TOP || trav == RT_TRAV_FLAT_GUARD;
+    const int words = compiled ? c->fast_stack_words : c->info.stack_words + c->walk_extra_words;
     return (size_t)words * RTR_BLOCK * sizeof(int);
+}
+/* The RT_TRAV_* template value a per-ray kernel (k_li, k_features, k_query_*, the unit kernels of the test library)
+ * takes for a call with `flags`: flat scenes take RT_TRAV_FAST (same hits, one kernel for both), a program the general
+ * program kernel, and with `top` a sub-scene 0 with a top tree RT_TRAV_TOP, like the megakernel. */
+int per_ray_trav(const rtr_context* c, int flags, bool top) {
+    int trav = pick_trav(c, flags);
+    if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST;
+    if (top && trav == RT_TRAV_FAST && c->ds.top_root0 >= 0) trav = RT_TRAV_TOP;
+    return trav == RT_TRAV_PROGRAM ? RT_TRAV_PROGRAM_EXT : trav;
+}
+/* the traversals k_li and k_features are instantiated for; the queries and the unit kernels also walk a top tree */
+using PerRayTravs = TravSet<RT_TRAV_FAST, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA, RT_TRAV_EXACT>;
+using PerRayTravsTop = TravSet<RT_TRAV_FAST, RT_TRAV_TOP, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA, RT_TRAV_EXACT>;
+int no_per_ray_kernel(rtr_context* c, int trav) {
+    return fail(c, RTR_ERR_UNSUPPORTED, "no per-ray kernel for traversal " + std::to_string(trav));
 }
 
 template <typename K>
 int set_lds(rtr_context* c, K kernel, size_t bytes) {
-    /* the per-lane traversal stack lives in LDS: a graph that needs more than the CU has (e.g. the
-     * reference-order walk of a hittable_list with thousands of direct children) cannot run that way */
-    if (bytes > 160 * 1024)
-        return fail(c, RTR_ERR_UNSUPPORTED, "this traversal of the scene needs a deeper stack than 160 KiB of LDS holds");
-    if (bytes > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return RTR_OK;
+    return kernel_lds(kernel, bytes, 0, c->err);
+}
+
+/* THE place that decides which k_mega instantiation a render runs: from what the upload found out about the scene,
+ * the integrator, the traversal pick_trav() chose and the render flags.  `flags_in_effect` (may be null) receives the
+ * flags that changed the choice. */
+MegaVariant mega_variant(const MegaFacts& f, int integ, int trav, int flags, int* flags_in_effect) {
+    MegaVariant v{integ, trav, RT_MS_FULL, false, false};
+    /* MIS and RR have flat, lean and guarded kernels; the others the generic material set on the
+     * general compiled-scene kernel, one program kernel -- the general one --, and the media kernel, which also serves
+     * the reference-order traversal of scenes without media */
+    const bool n1 = integ != RTR_INTEGRATOR_MIS && integ != RTR_INTEGRATOR_RR;
+    if (v.trav == RT_TRAV_FLAT && n1) v.trav = RT_TRAV_FAST;
+    if (v.trav == RT_TRAV_FAST && f.top_tree) v.trav = RT_TRAV_TOP; /* many instances: the per-lane walk (FSub) */
+    if (v.trav == RT_TRAV_FAST && f.flat_guarded && !n1) v.trav = RT_TRAV_FLAT_GUARD;
+    if (v.trav == RT_TRAV_PROGRAM && (f.guarded_program || n1)) v.trav = RT_TRAV_PROGRAM_EXT;
+    if (n1) {
+        if (v.trav == RT_TRAV_EXACT) v.trav = RT_TRAV_MEDIA;
+        return v;
+    }
+    const int t = v.trav;
+    const bool lean = f.lean && (t == RT_TRAV_FLAT || t == RT_TRAV_FAST || t == RT_TRAV_TOP || t == RT_TRAV_EXACT);
+    /* "every material, QuadLights only": a kernel of the MIS integrator (RR has no light code) on the compiled scene */
+    const bool quadlit = f.quad_only && !f.needs_uv && integ == RTR_INTEGRATOR_MIS && t != RT_TRAV_MEDIA && t != RT_TRAV_EXACT;
+    v.ms = lean ? RT_MS_LEAN : (quadlit ? RT_MS_QUADLIT : RT_MS_FULL);
+    /* (the sorted variant packs the material index into 16 bits) */
+    v.sorted = (flags & RTR_FLAG_SORTED_SHADING) && f.n_materials <= 65535 && mega_sortable(integ, t, v.ms);
+    const bool pairable = mega_pairable(integ, t) && !v.sorted && f.pair_cast;
+    v.pair = pairable && !(flags & RTR_FLAG_SPLIT_CASTS);
+    if (flags_in_effect && v.sorted) *flags_in_effect |= RTR_FLAG_SORTED_SHADING;
+    if (flags_in_effect && pairable && !v.pair) *flags_in_effect |= RTR_FLAG_SPLIT_CASTS;
+    return v;
 }
 
 /* `dry`: only what can fail without touching the stream (the LDS size check / attribute, the occupancy query) */
 int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, bool dry, int* blocks_per_cu, int flags,
                 int* flags_in_effect = nullptr, LaunchedKernel* launched = nullptr) {
+    MegaFacts facts{};
+    facts.top_tree = c->ds.top_root0 >= 0, facts.flat_guarded = c->flat_guarded, facts.guarded_program = c->guarded_program;
+    facts.lean = c->lean_materials, facts.quad_only = c->quad_lights_only, facts.needs_uv = c->info.needs_uv != 0;
+    facts.pair_cast = c->ds.pair_cast != 0, facts.n_materials = c->n_materials;
     MegaLaunch L{};
-    /* the flat variants exist for integrators 1 and 4; the others take the general compiled-scene kernel */
-    L.trav = trav_in == RT_TRAV_FLAT && integrator != RTR_INTEGRATOR_MIS && integrator != RTR_INTEGRATOR_RR ? RT_TRAV_FAST : trav_in;
-    if (L.trav == RT_TRAV_FAST && c->ds.top_root0 >= 0) L.trav = RT_TRAV_TOP; /* many instances: the per-lane walk (FSub) */
-    if (L.trav == RT_TRAV_FAST && c->flat_guarded && (integrator == RTR_INTEGRATOR_MIS || integrator == RTR_INTEGRATOR_RR))
-        L.trav = RT_TRAV_FLAT_GUARD;
-    L.integrator = integrator;
-    L.stack_words = (int)(stack_bytes(c, L.trav) / (RTR_BLOCK * sizeof(int)));
+    const MegaVariant& v = L.variant = mega_variant(facts, integrator, trav_in, flags, flags_in_effect);
+    L.stack_words = (int)(stack_bytes(c, v.trav) / (RTR_BLOCK * sizeof(int)));
     L.dsc = static_cast<const DScene*>(c->b_dscene.p);
-    L.lean = c->lean_materials && L.trav != RT_TRAV_MEDIA && L.trav != RT_TRAV_PROGRAM;
-    L.quadlit = c->quad_lights_only && !c->info.needs_uv;
-    /* (the sorted variant packs the material index into 16 bits) */
-    L.sorted = (flags & RTR_FLAG_SORTED_SHADING) && c->n_materials <= 65535 && mega_sortable(integrator, L.trav, L.lean ? RT_MS_LEAN : (L.quadlit ? RT_MS_QUADLIT : RT_MS_FULL));
-    L.lds = stack_bytes(c, L.trav) + (size_t)(L.sorted ? SK_WORDS : park_words(integrator, L.trav)) * RTR_BLOCK * sizeof(double);
-    L.program_ext = c->guarded_program;
+    /* (the reference-order walk of PBR / NEE runs the media kernel with the parked words of the traversal that was
+     * asked for, as it always has: workgroups per CU decide the chunking of a render, and that its rounding) */
+    const int park = v.sorted ? SK_WORDS : park_words(integrator, trav_in == RT_TRAV_EXACT ? RT_TRAV_EXACT : v.trav);
+    L.lds = stack_bytes(c, v.trav) + (size_t)park * RTR_BLOCK * sizeof(double);
     L.accum = P.tile_s0 == nullptr ? 0 : (P.q_in ? 2 : 1);
     L.stream = c->stream;
     L.P = P;
     L.dry = dry;
     L.blocks_per_cu = blocks_per_cu;
-    L.launched = launched;
-    if (flags_in_effect && L.sorted) *flags_in_effect |= RTR_FLAG_SORTED_SHADING;
-    const bool pairable = mega_pairable(integrator, L.trav) && !L.sorted && c->ds.pair_cast;
-    L.pair = pairable && !(flags & RTR_FLAG_SPLIT_CASTS);
-    if (flags_in_effect && pairable && !L.pair) *flags_in_effect |= RTR_FLAG_SPLIT_CASTS;
+    int rc;
     switch (integrator) {
-    case RTR_INTEGRATOR_MIS: return rtr_mega_launch_mis(L, c->err);
+    case RTR_INTEGRATOR_MIS: rc = rtr_mega_launch_mis(L, c->err); break;
     case RTR_INTEGRATOR_RR:
-    case RTR_INTEGRATOR_PATH: return rtr_mega_launch_rr_path(L, c->err);
-    default: return rtr_mega_launch_pbr_nee(L, c->err);
+    case RTR_INTEGRATOR_PATH: rc = rtr_mega_launch_rr_path(L, c->err); break;
+    default: rc = rtr_mega_launch_pbr_nee(L, c->err); break;
     }
+    if (rc == RTR_OK && !dry && launched) launched->trav = v.trav, launched->ms = v.ms, launched->sorted = v.sorted;
+    return rc;
 }
 
 /* auto chunking.  A workgroup renders one tile for one chunk of the samples.  More chunks = more, shorter
@@ -1596,24 +1630,16 @@ int accum_features(rtr_context* c, rtr_accum* a, int K) {
     RenderK P = accum_view(a).r;
     P.seed = a->params.seed;
     double* feat = static_cast<double*>(a->d_feat.p);
-    int trav = pick_trav(c, a->params.flags);
-    if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST; /* the traversals of k_li: same hits */
+    const int trav = per_ray_trav(c, a->params.flags, false); /* the traversals of k_li */
     const size_t lds = stack_bytes(c, trav);
     int rc = RTR_OK;
-#define RTR_LAUNCH(T)                                                                                         \
-    do {                                                                                                      \
-        if ((rc = set_lds(c, k_features<T>, lds))) return rc;                                                 \
-        hipLaunchKernelGGL((k_features<T>), dim3((unsigned)n), dim3(RTR_BLOCK), lds, c->stream, c->ds, P, K, feat); \
-    } while (0)
-    if (trav == RT_TRAV_FAST)
-        RTR_LAUNCH(RT_TRAV_FAST);
-    else if (trav == RT_TRAV_PROGRAM)
-        RTR_LAUNCH(RT_TRAV_PROGRAM_EXT);
-    else if (trav == RT_TRAV_MEDIA)
-        RTR_LAUNCH(RT_TRAV_MEDIA);
-    else
-        RTR_LAUNCH(RT_TRAV_EXACT);
-#undef RTR_LAUNCH
+    if (!dispatch_trav(PerRayTravs{}, trav, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            if ((rc = set_lds(c, k_features<T>, lds))) return;
+            hipLaunchKernelGGL((k_features<T>), dim3((unsigned)n), dim3(RTR_BLOCK), lds, c->stream, c->ds, P, K, feat);
+        }))
+        return no_per_ray_kernel(c, trav);
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     a->feat_k = K;
     return RTR_OK;
@@ -1840,45 +1866,31 @@ static int li_run(rtr_context* c, const rtr_render_params* p, const int32_t* ijs
     const int32_t* d_ijs = rays ? nullptr : reinterpret_cast<const int32_t*>(base);
     const rtr_li_ray* d_rays = rays ? reinterpret_cast<const rtr_li_ray*>(base) : nullptr;
     LiOut* d_out = reinterpret_cast<LiOut*>(base + in_pad);
-    int trav = pick_trav(c, p->flags);
-    if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST; /* same results; one per-ray kernel for both */
+    int trav = per_ray_trav(c, p->flags, false);
     const size_t lds = stack_bytes(c, trav);
     const dim3 grid((unsigned)((n + RTR_BLOCK - 1) / RTR_BLOCK));
-#define RTR_LAUNCH(I, T)                                                                                            \
-    do {                                                                                                            \
-        if ((rc = set_lds(c, k_li<I, T>, lds))) return rc;                                                          \
-        hipLaunchKernelGGL((k_li<I, T>), grid, dim3(RTR_BLOCK), lds, c->stream, c->ds, P, d_ijs, d_rays, d_out, (long long)n); \
-    } while (0)
-#define RTR_LAUNCH_T(I)                                        \
-    do {                                                       \
-        if (trav == RT_TRAV_FAST)                              \
-            RTR_LAUNCH(I, RT_TRAV_FAST);                       \
-        else if (trav == RT_TRAV_PROGRAM)                      \
-            RTR_LAUNCH(I, RT_TRAV_PROGRAM_EXT);                \
-        else if (trav == RT_TRAV_MEDIA)                        \
-            RTR_LAUNCH(I, RT_TRAV_MEDIA);                      \
-        else                                                   \
-            RTR_LAUNCH(I, RT_TRAV_EXACT);                      \
-    } while (0)
-#define RTR_LAUNCH_N1(I)                                   \
-    do {                                                   \
-        if (trav == RT_TRAV_FAST)                          \
-            RTR_LAUNCH(I, RT_TRAV_FAST);                   \
-        else if (trav == RT_TRAV_PROGRAM)                  \
-            RTR_LAUNCH(I, RT_TRAV_PROGRAM_EXT);            \
-        else                                               \
-            RTR_LAUNCH(I, RT_TRAV_MEDIA);                  \
-    } while (0)
+    /* integrators 0 / 2 / 3: the media kernel also serves the reference-order traversal */
+    const bool n1 = p->integrator != RTR_INTEGRATOR_MIS && p->integrator != RTR_INTEGRATOR_RR;
+    if (n1 && trav == RT_TRAV_EXACT) trav = RT_TRAV_MEDIA;
+    auto launch = [&](auto integ, auto travs) {
+        constexpr int I = decltype(integ)::value;
+        return dispatch_trav(travs, trav, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            if ((rc = set_lds(c, k_li<I, T>, lds))) return;
+            hipLaunchKernelGGL((k_li<I, T>), grid, dim3(RTR_BLOCK), lds, c->stream, c->ds, P, d_ijs, d_rays, d_out, (long long)n);
+        });
+    };
+    using TravsN1 = TravSet<RT_TRAV_FAST, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA>;
+    bool found;
     switch (p->integrator) {
-    case RTR_INTEGRATOR_MIS: RTR_LAUNCH_T(RTR_INTEGRATOR_MIS); break;
-    case RTR_INTEGRATOR_RR: RTR_LAUNCH_T(RTR_INTEGRATOR_RR); break;
-    case RTR_INTEGRATOR_PATH: RTR_LAUNCH_N1(RTR_INTEGRATOR_PATH); break;
-    case RTR_INTEGRATOR_PBR: RTR_LAUNCH_N1(RTR_INTEGRATOR_PBR); break;
-    default: RTR_LAUNCH_N1(RTR_INTEGRATOR_NEE); break;
+    case RTR_INTEGRATOR_MIS: found = launch(std::integral_constant<int, RTR_INTEGRATOR_MIS>{}, PerRayTravs{}); break;
+    case RTR_INTEGRATOR_RR: found = launch(std::integral_constant<int, RTR_INTEGRATOR_RR>{}, PerRayTravs{}); break;
+    case RTR_INTEGRATOR_PATH: found = launch(std::integral_constant<int, RTR_INTEGRATOR_PATH>{}, TravsN1{}); break;
+    case RTR_INTEGRATOR_PBR: found = launch(std::integral_constant<int, RTR_INTEGRATOR_PBR>{}, TravsN1{}); break;
+    default: found = launch(std::integral_constant<int, RTR_INTEGRATOR_NEE>{}, TravsN1{}); break;
     }
-#undef RTR_LAUNCH_N1
-#undef RTR_LAUNCH_T
-#undef RTR_LAUNCH
+    if (!found) return no_per_ray_kernel(c, trav);
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(host_out, d_out, (size_t)n * sizeof(LiOut), hipMemcpyDeviceToHost));
@@ -1923,11 +1935,8 @@ int rtr_debug_view_get(rtr_context* c, int flags, rtr_debug_view* v, size_t size
     v->device = c->device;
     v->n_cus = c->n_cus;
     v->n_materials = c->n_materials;
-    int trav = pick_trav(c, flags);
-    if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST;
-    if (trav == RT_TRAV_FAST && c->ds.top_root0 >= 0) trav = RT_TRAV_TOP; /* the unit kernels walk what the megakernel walks */
-    v->trav = trav;
-    v->stack_bytes = stack_bytes(c, trav);
+    v->trav = per_ray_trav(c, flags, true); /* the unit kernels walk what the megakernel walks */
+    v->stack_bytes = stack_bytes(c, v->trav);
     return RTR_OK;
 }
 int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {
@@ -1969,14 +1978,6 @@ int query_check_rays(rtr_context* c, const rtr_ray* rays, int64_t n) {
     return RTR_OK;
 }
 
-/* the traversal of a query: the one a render with `flags` walks (the per-ray kernels' set: RT_TRAV_FLAT scenes take
- * RT_TRAV_FAST -- same hits --, a sub-scene 0 with a top tree RT_TRAV_TOP like the megakernel) */
-int query_trav(const rtr_context* c, int flags) {
-    int trav = pick_trav(c, flags);
-    if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST;
-    if (trav == RT_TRAV_FAST && c->ds.top_root0 >= 0) trav = RT_TRAV_TOP;
-    return trav;
-}
 /* the staged record access (k_query_*<.., STAGED>) unless RTR_QUERY_STAGED=0 or the stack leaves no room for it
  * (tools/time_queries.py measures both forms: DESIGN.md 4.6) */
 bool query_staged(size_t stack) {
@@ -1987,7 +1988,7 @@ bool query_staged(size_t stack) {
 
 /* one launch over device arrays on the context stream; hits != nullptr: closest hit, else occlusion */
 int query_launch(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, uint8_t* d_occ, uint32_t* d_rng, int64_t n, int flags) {
-    const int trav = query_trav(c, flags);
+    const int trav = per_ray_trav(c, flags, true); /* what a render with `flags` walks */
     const size_t stack = stack_bytes(c, trav);
     const bool staged = query_staged(stack);
     const size_t lds = stack + (staged ? RTR_QUERY_STAGE_BYTES : 0);
@@ -1997,37 +1998,22 @@ int query_launch(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, uin
     ds.needs_uv = 1; /* (u, v) of the hit record whether or not a texture reads them */
     const dim3 grid((unsigned)((n + RTR_BLOCK - 1) / RTR_BLOCK));
     int rc = RTR_OK;
-#define RTR_LAUNCH_S(T, S)                                                                                              \
-    do {                                                                                                                 \
-        if (d_hits) {                                                                                                    \
-            if ((rc = set_lds(c, k_query_closest<T, S>, lds))) return rc;                                                \
-            hipLaunchKernelGGL((k_query_closest<T, S>), grid, dim3(RTR_BLOCK), lds, c->stream, ds, d_rays, d_hits,       \
-                               (long long)n, media, stage_word);                                                         \
-        } else {                                                                                                         \
-            if ((rc = set_lds(c, k_query_any<T, S>, lds))) return rc;                                                    \
-            hipLaunchKernelGGL((k_query_any<T, S>), grid, dim3(RTR_BLOCK), lds, c->stream, ds, d_rays, d_occ, d_rng,     \
-                               (long long)n, media, stage_word);                                                         \
-        }                                                                                                                \
-    } while (0)
-#define RTR_LAUNCH(T)              \
-    do {                           \
-        if (staged)                \
-            RTR_LAUNCH_S(T, true); \
-        else                       \
-            RTR_LAUNCH_S(T, false); \
-    } while (0)
-    if (trav == RT_TRAV_FAST)
-        RTR_LAUNCH(RT_TRAV_FAST);
-    else if (trav == RT_TRAV_TOP)
-        RTR_LAUNCH(RT_TRAV_TOP);
-    else if (trav == RT_TRAV_PROGRAM)
-        RTR_LAUNCH(RT_TRAV_PROGRAM_EXT);
-    else if (trav == RT_TRAV_MEDIA)
-        RTR_LAUNCH(RT_TRAV_MEDIA);
-    else
-        RTR_LAUNCH(RT_TRAV_EXACT);
-#undef RTR_LAUNCH
-#undef RTR_LAUNCH_S
+    auto launch = [&](auto t, auto s) {
+        constexpr int T = decltype(t)::value;
+        constexpr bool S = decltype(s)::value;
+        if (d_hits) {
+            if ((rc = set_lds(c, k_query_closest<T, S>, lds))) return;
+            hipLaunchKernelGGL((k_query_closest<T, S>), grid, dim3(RTR_BLOCK), lds, c->stream, ds, d_rays, d_hits, (long long)n, media,
+                               stage_word);
+        } else {
+            if ((rc = set_lds(c, k_query_any<T, S>, lds))) return;
+            hipLaunchKernelGGL((k_query_any<T, S>), grid, dim3(RTR_BLOCK), lds, c->stream, ds, d_rays, d_occ, d_rng, (long long)n, media,
+                               stage_word);
+        }
+    };
+    if (!dispatch_trav(PerRayTravsTop{}, trav, [&](auto t) { staged ? launch(t, std::true_type{}) : launch(t, std::false_type{}); }))
+        return no_per_ray_kernel(c, trav);
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     return RTR_OK;
 }

@@ -2,8 +2,9 @@
  * rtr_mega.hip -- megakernel instantiations of one integrator group (see rt_launch.h); compiled three
  * times with -DRTR_MEGA_GROUP=0/1/2 so the variants build in parallel.
  *
- * tests/test_kernel_variants.py holds the table of every instantiation the launchers below can pick and renders
- * each against the oracle: a variant added or removed here goes into that table too.
+ * Each group dispatches over the explicit list of its instantiations at the end of this file, one Row per
+ * (I, T, M[, S][, PAIR]); every row stands for its three ACC twins.  tests/test_kernel_variants.py holds the same
+ * table and renders each row against the oracle: a variant added or removed here goes into that table too.
  */
 #include "rt_kernels.h"
 #include "rt_launch.h"
@@ -21,15 +22,11 @@ int mega_fail(std::string& err, int code, const std::string& m) {
 
 template <typename K>
 int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
-    /* the per-lane traversal stack lives in LDS: a graph that needs more than the CU has (e.g. the
-     * reference-order walk of a hittable_list with thousands of direct children) cannot run that way */
     hipFuncAttributes fa{};
     hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
     /* the kernel's own static LDS (a few words of the workgroup vote) counts against the same 160 KiB */
-    if (e == hipSuccess && L.lds + fa.sharedSizeBytes > 160 * 1024)
-        return mega_fail(err, RTR_ERR_UNSUPPORTED, "this traversal of the scene needs a deeper stack than 160 KiB of LDS holds");
-    if (e == hipSuccess && L.lds > 64 * 1024)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
+    if (e == hipSuccess)
+        if (int rc = kernel_lds(kernel, L.lds, fa.sharedSizeBytes, err)) return rc;
     if (e == hipSuccess && L.dry && L.blocks_per_cu)
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(L.blocks_per_cu, kernel, RTR_BLOCK, L.lds);
     if (e == hipSuccess && !L.dry) {
@@ -41,91 +38,94 @@ int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
     return RTR_OK;
 }
 
+/* one line of a group's list: k_mega<I, T, M, S, ACC, PR> for ACC = 0, 1, 2 */
 template <int I, int T, int M, bool S = false, bool PR = false>
-int launch_rec(const MegaLaunch& L, std::string& err) {
-    /* (an accumulator pass: the same variant with ACC = 1, or 2 with moments, rt_kernels.h) */
-    const int rc = L.accum == 2 ? launch_one(k_mega<I, T, M, S, 2, PR>, L, err)
-                   : L.accum    ? launch_one(k_mega<I, T, M, S, 1, PR>, L, err)
-                                : launch_one(k_mega<I, T, M, S, 0, PR>, L, err);
-    if (rc == RTR_OK && !L.dry && L.launched) {
-        L.launched->trav = T;
-        L.launched->ms = M;
-        L.launched->sorted = S;
+struct Row {
+    static bool is(const MegaVariant& v) { return v.integ == I && v.trav == T && v.ms == M && v.sorted == S && v.pair == PR; }
+    static int launch(const MegaLaunch& L, std::string& err) {
+        /* (an accumulator pass: the same variant with ACC = 1, or 2 with moments, rt_kernels.h) */
+        return L.accum == 2 ? launch_one(k_mega<I, T, M, S, 2, PR>, L, err)
+               : L.accum    ? launch_one(k_mega<I, T, M, S, 1, PR>, L, err)
+                            : launch_one(k_mega<I, T, M, S, 0, PR>, L, err);
     }
-    return rc;
-}
-
-#define RTR_LAUNCH(I, T, M) return launch_rec<I, T, M>(L, err)
-/* the flat MIS kernels: the pair-cast twin where the scene allows it (MegaLaunch::pair) */
-#define RTR_LAUNCH_FLAT(I, M)                                                                                               \
-    do {                                                                                                                    \
-        if constexpr (mega_pairable(I, RT_TRAV_FLAT))                                                                       \
-            if (L.pair) return launch_rec<I, RT_TRAV_FLAT, M, false, mega_pairable(I, RT_TRAV_FLAT)>(L, err);               \
-        RTR_LAUNCH(I, RT_TRAV_FLAT, M);                                                                                     \
-    } while (0)
-
-/* integrators 1 and 4: every traversal, material-set variants.  FULLQ = the variant for "every material,
- * QuadLights only" (the RR integrator has no light code) */
-template <int I, int FULLQ>
-int launch_t(const MegaLaunch& L, std::string& err) {
-    const int trav = L.trav;
-    if (trav == RT_TRAV_FLAT) {
-        if (L.lean) RTR_LAUNCH_FLAT(I, RT_MS_LEAN);
-        if (L.quadlit) {
-            if (mega_sortable(I, RT_TRAV_FLAT, FULLQ) && L.sorted)
-                return launch_rec<I, RT_TRAV_FLAT, FULLQ, mega_sortable(I, RT_TRAV_FLAT, FULLQ)>(L, err);
-            RTR_LAUNCH_FLAT(I, FULLQ);
-        }
-        RTR_LAUNCH_FLAT(I, RT_MS_FULL);
-    }
-    if (trav == RT_TRAV_FLAT_GUARD) {
-        if (L.quadlit) RTR_LAUNCH(I, RT_TRAV_FLAT_GUARD, FULLQ);
-        RTR_LAUNCH(I, RT_TRAV_FLAT_GUARD, RT_MS_FULL);
-    }
-    if (trav == RT_TRAV_FAST) {
-        if (L.lean) RTR_LAUNCH(I, RT_TRAV_FAST, RT_MS_LEAN);
-        if (L.quadlit) RTR_LAUNCH(I, RT_TRAV_FAST, FULLQ);
-        RTR_LAUNCH(I, RT_TRAV_FAST, RT_MS_FULL);
-    }
-    if (trav == RT_TRAV_TOP) {
-        if (L.lean) RTR_LAUNCH(I, RT_TRAV_TOP, RT_MS_LEAN);
-        if (L.quadlit) RTR_LAUNCH(I, RT_TRAV_TOP, FULLQ);
-        RTR_LAUNCH(I, RT_TRAV_TOP, RT_MS_FULL);
-    }
-    if (trav == RT_TRAV_PROGRAM && L.program_ext) {
-        if (L.quadlit) RTR_LAUNCH(I, RT_TRAV_PROGRAM_EXT, FULLQ);
-        RTR_LAUNCH(I, RT_TRAV_PROGRAM_EXT, RT_MS_FULL);
-    }
-    if (trav == RT_TRAV_PROGRAM) {
-        if (L.quadlit) RTR_LAUNCH(I, RT_TRAV_PROGRAM, FULLQ);
-        RTR_LAUNCH(I, RT_TRAV_PROGRAM, RT_MS_FULL);
-    }
-    if (trav == RT_TRAV_MEDIA) RTR_LAUNCH(I, RT_TRAV_MEDIA, RT_MS_FULL);
-    if (L.lean) RTR_LAUNCH(I, RT_TRAV_EXACT, RT_MS_LEAN);
-    RTR_LAUNCH(I, RT_TRAV_EXACT, RT_MS_FULL);
-}
-/* integrators 0 / 2 / 3: generic material set; the media kernel also serves the
- * reference-order traversal of scenes without media */
-template <int I>
-int launch_n1(const MegaLaunch& L, std::string& err) {
-    if (L.trav == RT_TRAV_FAST) RTR_LAUNCH(I, RT_TRAV_FAST, RT_MS_FULL);
-    if (L.trav == RT_TRAV_TOP) RTR_LAUNCH(I, RT_TRAV_TOP, RT_MS_FULL);
-    if (L.trav == RT_TRAV_PROGRAM) RTR_LAUNCH(I, RT_TRAV_PROGRAM_EXT, RT_MS_FULL); /* (one program kernel here: the general one) */
-    RTR_LAUNCH(I, RT_TRAV_MEDIA, RT_MS_FULL);
+};
+/* the row that is MegaLaunch::variant, or RTR_ERR_UNSUPPORTED: never another kernel in its place */
+template <typename... Rows>
+int launch_from(const MegaLaunch& L, std::string& err) {
+    int rc = RTR_OK;
+    if (((Rows::is(L.variant) && (rc = Rows::launch(L, err), true)) || ...)) return rc;
+    const MegaVariant& v = L.variant;
+    return mega_fail(err, RTR_ERR_UNSUPPORTED,
+                     "no megakernel instantiation for integrator " + std::to_string(v.integ) + ", traversal " + std::to_string(v.trav) +
+                         ", material set " + std::to_string(v.ms) + (v.sorted ? ", sorted" : "") + (v.pair ? ", pair cast" : ""));
 }
 
 } // namespace
 
 #if RTR_MEGA_GROUP == 0
-int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err) { return launch_t<RTR_INTEGRATOR_MIS, RT_MS_QUADLIT>(L, err); }
+/* MIS: every traversal; lean / QuadLights-only / full material sets; the flat kernels have a pair-cast twin and the
+ * flat QuadLights-only one a sorted twin */
+int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err) {
+    constexpr int I = RTR_INTEGRATOR_MIS;
+    return launch_from<
+        Row<I, RT_TRAV_FLAT, RT_MS_LEAN>,
+        Row<I, RT_TRAV_FLAT, RT_MS_LEAN, false, true>,
+        Row<I, RT_TRAV_FLAT, RT_MS_QUADLIT>,
+        Row<I, RT_TRAV_FLAT, RT_MS_QUADLIT, false, true>,
+        Row<I, RT_TRAV_FLAT, RT_MS_QUADLIT, true>,
+        Row<I, RT_TRAV_FLAT, RT_MS_FULL>,
+        Row<I, RT_TRAV_FLAT, RT_MS_FULL, false, true>,
+        Row<I, RT_TRAV_FLAT_GUARD, RT_MS_QUADLIT>,
+        Row<I, RT_TRAV_FLAT_GUARD, RT_MS_FULL>,
+        Row<I, RT_TRAV_FAST, RT_MS_LEAN>,
+        Row<I, RT_TRAV_FAST, RT_MS_QUADLIT>,
+        Row<I, RT_TRAV_FAST, RT_MS_FULL>,
+        Row<I, RT_TRAV_TOP, RT_MS_LEAN>,
+        Row<I, RT_TRAV_TOP, RT_MS_QUADLIT>,
+        Row<I, RT_TRAV_TOP, RT_MS_FULL>,
+        Row<I, RT_TRAV_PROGRAM_EXT, RT_MS_QUADLIT>,
+        Row<I, RT_TRAV_PROGRAM_EXT, RT_MS_FULL>,
+        Row<I, RT_TRAV_PROGRAM, RT_MS_QUADLIT>,
+        Row<I, RT_TRAV_PROGRAM, RT_MS_FULL>,
+        Row<I, RT_TRAV_MEDIA, RT_MS_FULL>,
+        Row<I, RT_TRAV_EXACT, RT_MS_LEAN>,
+        Row<I, RT_TRAV_EXACT, RT_MS_FULL>>(L, err);
+}
 #elif RTR_MEGA_GROUP == 1
+/* RR: every traversal, lean / full (it has no light code).  Path (like PBR and NEE): the generic
+ * material set, one program kernel -- the general one --, and the media kernel, which also serves the reference-order
+ * traversal of scenes without media */
 int rtr_mega_launch_rr_path(const MegaLaunch& L, std::string& err) {
-    if (L.integrator == RTR_INTEGRATOR_RR) return launch_t<RTR_INTEGRATOR_RR, RT_MS_FULL>(L, err);
-    return launch_n1<RTR_INTEGRATOR_PATH>(L, err);
+    constexpr int R = RTR_INTEGRATOR_RR, P = RTR_INTEGRATOR_PATH;
+    return launch_from<
+        Row<R, RT_TRAV_FLAT, RT_MS_LEAN>,
+        Row<R, RT_TRAV_FLAT, RT_MS_FULL>,
+        Row<R, RT_TRAV_FLAT_GUARD, RT_MS_FULL>,
+        Row<R, RT_TRAV_FAST, RT_MS_LEAN>,
+        Row<R, RT_TRAV_FAST, RT_MS_FULL>,
+        Row<R, RT_TRAV_TOP, RT_MS_LEAN>,
+        Row<R, RT_TRAV_TOP, RT_MS_FULL>,
+        Row<R, RT_TRAV_PROGRAM_EXT, RT_MS_FULL>,
+        Row<R, RT_TRAV_PROGRAM, RT_MS_FULL>,
+        Row<R, RT_TRAV_MEDIA, RT_MS_FULL>,
+        Row<R, RT_TRAV_EXACT, RT_MS_LEAN>,
+        Row<R, RT_TRAV_EXACT, RT_MS_FULL>,
+        Row<P, RT_TRAV_FAST, RT_MS_FULL>,
+        Row<P, RT_TRAV_TOP, RT_MS_FULL>,
+        Row<P, RT_TRAV_PROGRAM_EXT, RT_MS_FULL>,
+        Row<P, RT_TRAV_MEDIA, RT_MS_FULL>>(L, err);
 }
 #else
 int rtr_mega_launch_pbr_nee(const MegaLaunch& L, std::string& err) {
-    if (L.integrator == RTR_INTEGRATOR_PBR) return launch_n1<RTR_INTEGRATOR_PBR>(L, err);
-    return launch_n1<RTR_INTEGRATOR_NEE>(L, err);
+    constexpr int B = RTR_INTEGRATOR_PBR, N = RTR_INTEGRATOR_NEE;
+    return launch_from<
+        Row<B, RT_TRAV_FAST, RT_MS_FULL>,
+        Row<B, RT_TRAV_TOP, RT_MS_FULL>,
+        Row<B, RT_TRAV_PROGRAM_EXT, RT_MS_FULL>,
+        Row<B, RT_TRAV_MEDIA, RT_MS_FULL>,
+        Row<N, RT_TRAV_FAST, RT_MS_FULL>,
+        Row<N, RT_TRAV_TOP, RT_MS_FULL>,
+        Row<N, RT_TRAV_PROGRAM_EXT, RT_MS_FULL>,
+        Row<N, RT_TRAV_MEDIA, RT_MS_FULL>>(L, err);
 }
 #endif

@@ -3,6 +3,7 @@
  * librtr_hip.so and linked against it; it reaches a context only through the seam of csrc/rt_debug.h.
  */
 #include "rt_debug.h"
+#include "rt_launch.h"
 #include "rt_test_kernels.h"
 #include "rtr_hip_test.h"
 
@@ -67,11 +68,9 @@ dim3 grid_of(int64_t n) { return dim3((unsigned)((n + RTR_BLOCK - 1) / RTR_BLOCK
 
 template <typename K>
 int set_lds(rtr_context* c, K kernel, size_t bytes) {
-    if (bytes > 160 * 1024)
-        return fail(c, RTR_ERR_UNSUPPORTED, "this traversal of the scene needs a deeper stack than 160 KiB of LDS holds");
-    if (bytes > 64 * 1024)
-        TCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return RTR_OK;
+    std::string err;
+    const int rc = kernel_lds(kernel, bytes, 0, err);
+    return rc ? fail(c, rc, err) : RTR_OK;
 }
 /* a bare context: stream, device and CU count without a scene */
 int bare(rtr_context* c, hipStream_t& stream, int& n_cus, TestState*& t) {
@@ -101,22 +100,14 @@ int rtr_test_hits(rtr_context* c, rtr_hit_record* recs, int64_t n) {
     ds.needs_uv = 1; /* the vectors pin u,v although no flattened texture of these scenes reads them */
     auto* d = static_cast<rtr_hit_record*>(t->buf);
     const size_t lds = v.stack_bytes;
-#define RTR_HITS(T)                                                                                          \
-    do {                                                                                                      \
-        if ((rc = set_lds(c, k_test_hits<T>, lds))) return rc;                                                 \
-        hipLaunchKernelGGL(k_test_hits<T>, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, ds, d, (long long)n);   \
-    } while (0)
-    if (v.trav == RT_TRAV_FAST)
-        RTR_HITS(RT_TRAV_FAST);
-    else if (v.trav == RT_TRAV_TOP)
-        RTR_HITS(RT_TRAV_TOP);
-    else if (v.trav == RT_TRAV_PROGRAM)
-        RTR_HITS(RT_TRAV_PROGRAM_EXT);
-    else if (v.trav == RT_TRAV_MEDIA)
-        RTR_HITS(RT_TRAV_MEDIA);
-    else
-        RTR_HITS(RT_TRAV_EXACT);
-#undef RTR_HITS
+    /* (rtr_debug_view::trav is a template value already: per_ray_trav of rtr_capi.hip) */
+    if (!dispatch_trav(TravSet<RT_TRAV_FAST, RT_TRAV_TOP, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA, RT_TRAV_EXACT>{}, v.trav, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            if ((rc = set_lds(c, k_test_hits<T>, lds))) return;
+            hipLaunchKernelGGL(k_test_hits<T>, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, ds, d, (long long)n);
+        }))
+        return fail(c, RTR_ERR_UNSUPPORTED, "no unit kernel for traversal " + std::to_string(v.trav));
+    if (rc) return rc;
     return end(c, v.stream, t, recs, n, sizeof *recs);
 }
 

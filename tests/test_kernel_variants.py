@@ -24,9 +24,10 @@ LEAN, FULL, QUADLIT = 0, 1, 2
 TRAV_NAME = ["EXACT", "MEDIA", "FAST", "PROGRAM", "FLAT", "TOP", "PROGRAM_EXT", "FLAT_GUARD"]
 MS_NAME = ["LEAN", "FULL", "QUADLIT"]
 
-# k_mega<integrator, traversal, material set, sorted>: every instantiation csrc/rtr_mega.hip launches (43)
+# k_mega<integrator, traversal, material set, sorted>: every row of the instantiation lists at the end of
+# csrc/rtr_mega.hip (43; the pair-cast twins of the flat MIS rows are tests/test_pair_cast.py's)
 MEGA_TABLE = {
-    # MIS (launch_t<MIS, RT_MS_QUADLIT>): 19
+    # MIS (the list of rtr_mega_launch_mis): 19
     (I_MIS, FLAT, LEAN, 0), (I_MIS, FLAT, QUADLIT, 0), (I_MIS, FLAT, QUADLIT, 1), (I_MIS, FLAT, FULL, 0),
     (I_MIS, FLAT_GUARD, QUADLIT, 0), (I_MIS, FLAT_GUARD, FULL, 0),
     (I_MIS, FAST, LEAN, 0), (I_MIS, FAST, QUADLIT, 0), (I_MIS, FAST, FULL, 0),
@@ -35,12 +36,12 @@ MEGA_TABLE = {
     (I_MIS, PROGRAM, QUADLIT, 0), (I_MIS, PROGRAM, FULL, 0),
     (I_MIS, MEDIA, FULL, 0),
     (I_MIS, EXACT, LEAN, 0), (I_MIS, EXACT, FULL, 0),
-    # RR (launch_t<RR, RT_MS_FULL>: no light code, so QuadLights-only scenes take the full set): 12
+    # RR (rtr_mega_launch_rr_path: no light code, so QuadLights-only scenes take the full set): 12
     (I_RR, FLAT, LEAN, 0), (I_RR, FLAT, FULL, 0), (I_RR, FLAT_GUARD, FULL, 0),
     (I_RR, FAST, LEAN, 0), (I_RR, FAST, FULL, 0), (I_RR, TOP, LEAN, 0), (I_RR, TOP, FULL, 0),
     (I_RR, PROGRAM_EXT, FULL, 0), (I_RR, PROGRAM, FULL, 0), (I_RR, MEDIA, FULL, 0),
     (I_RR, EXACT, LEAN, 0), (I_RR, EXACT, FULL, 0),
-    # PATH / PBR / NEE (launch_n1): 4 each
+    # PATH / PBR / NEE (rtr_mega_launch_rr_path / rtr_mega_launch_pbr_nee): 4 each
     *[(i, t, FULL, 0) for i in (I_PATH, I_PBR, I_NEE) for t in (FAST, TOP, PROGRAM_EXT, MEDIA)],
 }
 # wf_shade<integrator, phase, material set, sorted>: the instantiations csrc/rt_wavefront.h (WF_SHADE) launches.  Phase
