@@ -585,6 +585,80 @@ int rtr_query_closest_device(rtr_context* ctx, const rtr_ray* d_rays, rtr_ray_hi
 int rtr_query_occluded_device(rtr_context* ctx, const rtr_ray* d_rays, uint8_t* d_occluded, uint32_t* d_rng_out,
                               int64_t n, int32_t flags, int blocking);
 
+/* ---- camera updates: a new camera for the uploaded scene without another upload ----
+ * rtr_set_camera replaces the camera of the uploaded scene for every call issued afterwards (one-shot renders of both
+ * pipelines, rtr_li_samples, accumulator passes, features): the image is the bits of rtr_upload_scene of the same scene
+ * with that camera.  The call itself does no device work and does not wait: work already queued keeps the camera it was
+ * issued with, and the next render carries the new one to the device in stream order.  Nothing rtr_upload_scene derives
+ * from a scene depends on the camera but the range of ray times its boxes of moving spheres were built for.
+ * RTR_ERR_NO_SCENE before an upload; RTR_ERR_INVALID for NULL or a non-finite member; RTR_ERR_UNSUPPORTED (with a
+ * message) when time0 or time1 lies outside [min(0, time0, time1), max(0, time0, time1)] of the uploaded camera, or
+ * crosses the 2^60 bound of the shared divisions: such a camera needs an upload.
+ *
+ * The context counts camera updates.  An accumulator remembers the count of its creation or last reset; with a stale
+ * one rtr_accum_render, _render_tiles, _refine, _features, _denoise and _denoise_temporal return RTR_ERR_INVALID before
+ * any device work (its samples belong to the old camera: rtr_accum_resolve, _moments, _tiles and _errors still return
+ * them).  rtr_accum_reset waits for the accumulator's queued work, sets every owned tile to 0 samples, drops the cached
+ * features, binds the accumulator to the current camera and replaces its seed: afterwards it is indistinguishable from
+ * one created now with that seed.  After rtr_upload_scene it stays RTR_ERR_INVALID, reset included. */
+int rtr_set_camera(rtr_context* ctx, const rtr_camera* cam);
+int rtr_get_camera(rtr_context* ctx, rtr_camera* out);
+int rtr_accum_reset(rtr_context* ctx, rtr_accum* acc, uint32_t seed);
+
+/* ---- temporal reprojection: the other half of SVGF (Schied et al. 2017) in front of the a-trous filter ----
+ * A history keeps, per pixel of its region, 10 doubles of the last frame -- c[3] demodulated colour, mu1, mu2 raw
+ * luminance moments, n effective sample count (0: no history), z, nn[3] -- in two plane sets (a frame reads one and
+ * writes the other), and the camera they were seen from.
+ *
+ * rtr_accum_denoise_temporal is rtr_accum_denoise with the history blended in before the filter.  Per valid pixel
+ * (i, j) (full-image coordinates) with m, Q, n, a, nn, z, lum, la = max(lum(a), 1e-3) and c_p of the filter definition
+ * above, mu1_cur = lum(m), mu2_cur = (1.0 / n) * Q, n_cur = double(n); cam the context's camera, prev the history's;
+ * vector operations per component, sums left to right, compares in binary64:
+ *   su = (i + 0.5) / (W - 1), sv = (j + 0.5) / (H - 1);  d = llc + su * hor + sv * ver - origin
+ *   len = sqrt(d.x*d.x + d.y*d.y + d.z*d.z);  P = origin + (z / len) * d      (no history when z <= 0 or it is cleared)
+ *   q = P - prev.origin, e = prev.llc - prev.origin, zc = -(q . prev.w) (no history unless zc > 0), F = -(e . prev.w)
+ *   k = F / zc;  s = (k * (q . prev.u) - e . prev.u) / (prev.hor . prev.u);  t likewise with prev.v and prev.ver
+ *   x = s * (W - 1) - 0.5, y = t * (H - 1) - 0.5;  x0 = floor(x), fx = x - x0, y likewise;  z_exp = sqrt(q . q)
+ * Taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with weights (1-fx)*(1-fy), fx*(1-fy), (1-fx)*fy, fx*fy; a tap
+ * is accepted when it lies inside the region, its history n > 0, |z_exp - z_tap| <= tau_z * max(z_exp, 1e-3) and
+ * |nn_p - nn_tap|^2 <= tau_n.  sw = the sum of the accepted weights in tap order; no history unless sw >= min_weight;
+ * else each history value is (sum of w * value) / sw in tap order, for c, mu1, mu2 and n.
+ *   with history:  alpha = max(n_cur / (n_cur + n_h), alpha_min);  c' = alpha * c_p + (1 - alpha) * c_h, mu1' and mu2'
+ *                  likewise;  n' = n_cur / alpha
+ *   without:       c', mu1', mu2', n' are the current values
+ *   var' = max(0, mu2' - mu1' * mu1') / (n' - 1) / n', or 1e30 when n' < 2;  var' /= la * la
+ * The a-trous passes and the output stage then run unchanged on (c', var', a, nn, z), and the history takes c', mu1',
+ * mu2', n', z, nn per pixel (n = 0 where the pixel is invalid) and the current camera -- on every successful call.  The
+ * first frame on a cleared history is therefore the bits of rtr_accum_denoise. */
+typedef struct rtr_history rtr_history;
+typedef struct rtr_temporal_params {
+    double alpha_min;   /* (0, 1]: lower bound of the current frame's blend weight */
+    double tau_z;       /* > 0: relative depth tolerance of a history tap */
+    double tau_n;       /* > 0: largest |n_p - n_q|^2 of a history tap */
+    double min_weight;  /* (0, 1): smallest sum of accepted bilinear weights */
+    double reserved[4]; /* must be 0 */
+} rtr_temporal_params;
+
+/* The defaults ("Camera updates and temporal reprojection"). */
+void rtr_temporal_defaults(rtr_temporal_params* p);
+
+/* A cleared history for the image size and region of *p (nothing else of *p is read).  rtr_destroy() frees the
+ * histories left on the context. */
+int rtr_history_create(rtr_context* ctx, const rtr_render_params* p, rtr_history** out);
+/* Forget everything (waits for queued work): the next frame has no history. */
+int rtr_history_clear(rtr_context* ctx, rtr_history* hist);
+void rtr_history_destroy(rtr_history* hist);
+/* The plane set the next frame will read, into a HOST buffer: h_planes[((j - y0) * row_stride + (i - x0)) * 10 + k],
+ * k = c 0..2, mu1 3, mu2 4, n 5, z 6, nn 7..9.  Blocking. */
+int rtr_history_planes(rtr_context* ctx, rtr_history* hist, double* h_planes, int64_t row_stride);
+
+/* rtr_accum_denoise with the temporal stage above; outputs as there (either may be NULL, not both).  Every check of
+ * rtr_accum_denoise, the ranges of rtr_temporal_params, and a history of the same context, image size and region
+ * (RTR_ERR_INVALID) -- all before any device work: after an error the history and the accumulator are unchanged. */
+int rtr_accum_denoise_temporal(rtr_context* ctx, rtr_accum* acc, rtr_history* hist, const rtr_denoise_params* params,
+                               const rtr_temporal_params* temporal, double* h_linear, int64_t row_stride,
+                               uint8_t* h_rgb8);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

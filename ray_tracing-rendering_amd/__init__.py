@@ -22,7 +22,8 @@ def __getattr__(name):
     if name in ("native", "renderer", "hostscene", "build"):
         import importlib
         return importlib.import_module(__name__ + "." + name)
-    if name in ("Context", "RtrError", "library_path", "denoise_defaults", "denoise_host"):
+    if name in ("Context", "RtrError", "library_path", "denoise_defaults", "denoise_host", "temporal_defaults",
+                "History"):
         from . import native
         return getattr(native, name)
     if name in ("Renderer", "RenderBuffer", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):

@@ -130,6 +130,17 @@ assert C.sizeof(DenoiseParamsC) == DENOISE_PARAMS_SIZE
 FEATURES = 7  # doubles per pixel of rtr_accum_features: albedo 3, normal 3, depth 1
 
 
+class TemporalParamsC(C.Structure):
+    """rtr_temporal_params (include/rtr_hip.h): the reprojection stage of rtr_accum_denoise_temporal"""
+    _fields_ = [("alpha_min", C.c_double), ("tau_z", C.c_double), ("tau_n", C.c_double), ("min_weight", C.c_double),
+                ("reserved", C.c_double * 4)]
+
+
+TEMPORAL_PARAMS_SIZE = 64
+assert C.sizeof(TemporalParamsC) == TEMPORAL_PARAMS_SIZE
+HISTORY = 10  # doubles per pixel of rtr_history_planes: c 3, mu1, mu2, n, z, nn 3
+
+
 def make_params(width, height, spp, *, integrator=INTEGRATOR_MIS, seed=1, max_depth=50, rr_start_depth=3,
                 region=None, pipeline=PIPELINE_AUTO, tile_first=0, tile_stride=1, spp_chunks=1, flags=0):
     """Build an ``rtr_render_params``.  Defaults follow the reference driver (main.cpp:102,

@@ -1166,4 +1166,126 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_denoise_out(const DenoiseK D, int
         }
 }
 
+/* ---- rtr_accum_denoise_temporal: reprojection of the last frame in front of the filter (include/rtr_hip.h) ----
+ * A history plane set is AoS over the region, RTR_HIST doubles per pixel (c 0..2, mu1 3, mu2 4, n 5, z 6, nn 7..9): a tap
+ * of the gather is 80 contiguous bytes, and rtr_history_planes is a plain copy. */
+#define RTR_HIST 10
+struct TemporalK {
+    rtr_camera cam, prev;   /* the context's camera / the one the history was seen from */
+    int W, H, x0, y0;       /* full image size, the region's origin (its size is DenoiseK's w x h) */
+    int have;               /* 0: the history is cleared */
+    double alpha_min, tau_z, tau_n, min_weight;
+    const double* hist_in;  /* [p][RTR_HIST], the last frame */
+    double* hist_out;       /* [p][RTR_HIST], this frame (k_temporal_store) */
+    double* mom;            /* [3][np]: mu1', mu2', n' between k_temporal_blend and k_temporal_store */
+};
+
+RT_DEV double temporal_dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+/* k_denoise_prep with the history blended in: c', var' -> c[0], v[0]; the features -> a, nrm, z; mu1', mu2', n' -> mom.
+ * One workgroup per 16 x 16 pixels like k_denoise_pass; the four taps of a pixel come through L2. */
+__global__ void __launch_bounds__(RTR_BLOCK) k_temporal_blend(const DenoiseK D, const TemporalK T) {
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= D.w || y >= D.h) return;
+    const long long np = (long long)D.w * D.h, p = (long long)y * D.w + x;
+    const int n = D.n[p];
+    if (n == 0) return;
+    const double* f = D.feat + p * RTR_FEAT;
+    const V3 a = mk(f[0], f[1], f[2]);
+    const V3 m = mk(D.m[3 * p], D.m[3 * p + 1], D.m[3 * p + 2]);
+    const double nn[3] = {f[3], f[4], f[5]};
+    const double z = f[6];
+    double la = luminance(a);
+    la = la > 1e-3 ? la : 1e-3;
+    double c[3] = {a.x > 1e-3 ? m.x / a.x : m.x, a.y > 1e-3 ? m.y / a.y : m.y, a.z > 1e-3 ? m.z / a.z : m.z};
+    double mu1 = luminance(m), mu2 = (1.0 / n) * D.q[p], ne = (double)n;
+    if (T.have && z > 0.0) {
+        const rtr_camera& cam = T.cam;
+        const rtr_camera& pv = T.prev;
+        const double su = ((T.x0 + x) + 0.5) / (T.W - 1), sv = ((T.y0 + y) + 0.5) / (T.H - 1);
+        double d[3], q[3], e[3];
+        for (int k = 0; k < 3; ++k)
+            d[k] = cam.lower_left_corner[k] + su * cam.horizontal[k] + sv * cam.vertical[k] - cam.origin[k];
+        const double len = __builtin_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        const double zl = z / len;
+        for (int k = 0; k < 3; ++k) {
+            const double P = cam.origin[k] + zl * d[k];
+            q[k] = P - pv.origin[k];
+            e[k] = pv.lower_left_corner[k] - pv.origin[k];
+        }
+        const double zc = -temporal_dot3(q, pv.w);
+        if (zc > 0.0) {
+            const double F = -temporal_dot3(e, pv.w);
+            const double kk = F / zc;
+            const double s = (kk * temporal_dot3(q, pv.u) - temporal_dot3(e, pv.u)) / temporal_dot3(pv.horizontal, pv.u);
+            const double t = (kk * temporal_dot3(q, pv.v) - temporal_dot3(e, pv.v)) / temporal_dot3(pv.vertical, pv.v);
+            const double hx = s * (T.W - 1) - 0.5, hy = t * (T.H - 1) - 0.5;
+            const double fx0 = __builtin_floor(hx), fy0 = __builtin_floor(hy);
+            const double fx = hx - fx0, fy = hy - fy0;
+            const double z_exp = __builtin_sqrt(temporal_dot3(q, q));
+            const double z_tol = T.tau_z * (z_exp > 1e-3 ? z_exp : 1e-3);
+            /* region bounds in binary64: a NaN or far-away position fails every compare and is never made an index */
+            const double rx0 = (double)T.x0, ry0 = (double)T.y0, rx1 = (double)(T.x0 + D.w - 1), ry1 = (double)(T.y0 + D.h - 1);
+            double sw = 0.0, hc[3] = {0.0, 0.0, 0.0}, h1 = 0.0, h2 = 0.0, hn = 0.0;
+            for (int tap = 0; tap < 4; ++tap) {
+                const double tx = fx0 + (double)(tap & 1), ty = fy0 + (double)(tap >> 1);
+                if (!(tx >= rx0 && tx <= rx1 && ty >= ry0 && ty <= ry1)) continue;
+                const double* h = T.hist_in + ((long long)((int)ty - T.y0) * D.w + ((int)tx - T.x0)) * RTR_HIST;
+                if (!(h[5] > 0.0)) continue;
+                const double ez = z_exp - h[6];
+                if (!((ez < 0.0 ? -ez : ez) <= z_tol)) continue;
+                const double e0 = nn[0] - h[7], e1 = nn[1] - h[8], e2 = nn[2] - h[9];
+                if (!(e0 * e0 + e1 * e1 + e2 * e2 <= T.tau_n)) continue;
+                const double w = ((tap & 1) ? fx : 1.0 - fx) * ((tap >> 1) ? fy : 1.0 - fy);
+                sw += w;
+                hc[0] += w * h[0], hc[1] += w * h[1], hc[2] += w * h[2];
+                h1 += w * h[3], h2 += w * h[4], hn += w * h[5];
+            }
+            if (sw >= T.min_weight) {
+                const double n_h = hn / sw;
+                double alpha = ne / (ne + n_h);
+                alpha = alpha > T.alpha_min ? alpha : T.alpha_min;
+                const double beta = 1.0 - alpha;
+                for (int k = 0; k < 3; ++k) c[k] = alpha * c[k] + beta * (hc[k] / sw);
+                mu1 = alpha * mu1 + beta * (h1 / sw);
+                mu2 = alpha * mu2 + beta * (h2 / sw);
+                ne = ne / alpha;
+            }
+        }
+    }
+    double var = 1e30;
+    if (!(ne < 2.0)) {
+        const double dv = mu2 - mu1 * mu1;
+        var = (dv > 0.0 ? dv : 0.0) / (ne - 1.0) / ne;
+    }
+    D.v[0][p] = var / (la * la);
+    for (int k = 0; k < 3; ++k) D.c[0][p + k * np] = c[k], D.a[p + k * np] = f[k], D.nrm[p + k * np] = nn[k];
+    D.z[p] = z;
+    T.mom[p] = mu1, T.mom[p + np] = mu2, T.mom[p + 2 * np] = ne;
+}
+
+/* the write-back: what k_temporal_blend left in c[0], mom, nrm and z -> the history's other plane set (before the passes
+ * overwrite c[0]); n = 0 where the pixel is invalid */
+__global__ void __launch_bounds__(RTR_BLOCK) k_temporal_store(const DenoiseK D, const TemporalK T) {
+    const long long np = (long long)D.w * D.h, p = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (p >= np) return;
+    double* h = T.hist_out + p * RTR_HIST;
+    if (D.n[p] == 0) {
+        for (int k = 0; k < RTR_HIST; ++k) h[k] = 0.0;
+        return;
+    }
+    for (int k = 0; k < 3; ++k) h[k] = D.c[0][p + k * np], h[7 + k] = D.nrm[p + k * np];
+    h[3] = T.mom[p], h[4] = T.mom[p + np], h[5] = T.mom[p + 2 * np];
+    h[6] = D.z[p];
+}
+
+/* rtr_set_camera: the camera of the DScene the megakernel and the wavefront stages read through a pointer, replaced in
+ * stream order (the per-ray kernels take the DScene by value) */
+__global__ void __launch_bounds__(64) k_camera_store(DScene* sc, const rtr_camera cam) {
+    static_assert(sizeof(rtr_camera) == 24 * sizeof(double), "24 doubles");
+    const double* src = reinterpret_cast<const double*>(&cam);
+    double* dst = reinterpret_cast<double*>(&sc->camera);
+    if (threadIdx.x < 24) dst[threadIdx.x] = src[threadIdx.x];
+}
+
 #endif /* RTR_TU_CAPI */

@@ -79,6 +79,13 @@ struct rtr_context {
     bool guarded_program = false; /* the step program holds guarded primitives (FStep kind 3) or media under wrappers: not a program of the machine */
     uint64_t scene_gen = 0; /* rtr_upload_scene calls that reached the device: an accumulator belongs to one scene */
     std::vector<rtr_accum*> accums; /* live accumulators (rtr_destroy frees what is left) */
+    /* rtr_set_camera: ds.camera is the current camera; the DScene on the device (b_dscene: the megakernel and the
+     * wavefront stages read it through a pointer) takes it, in stream order, when the next render is issued */
+    uint64_t camera_gen = 0;   /* rtr_set_camera calls that succeeded: an accumulator's samples belong to one camera */
+    bool camera_dirty = false; /* b_dscene still holds an older camera */
+    double t_lo = 0, t_hi = 0; /* the ray times the scene was compiled for (rt_compile.h: t_lo, t_hi) */
+    bool camera_times_small = true; /* the uploaded camera passed the 2^60 test of DScene::shared_div */
+    std::vector<rtr_history*> histories; /* live histories (rtr_destroy frees what is left) */
 };
 
 /* rtr_accum_*: one running sum per owned pixel and a sample count per owned tile, on the device */
@@ -86,6 +93,7 @@ struct rtr_accum {
     rtr_context* ctx = nullptr;
     rtr_render_params params{}; /* spp / spp_chunks normalised to 1 */
     uint64_t scene_gen = 0;
+    uint64_t camera_gen = 0; /* the context's at creation or at the last rtr_accum_reset */
     std::vector<int> tiles; /* owned tiles, dispatch order; slot k = tiles[k] */
     int tiles_x = 0, tiles_y = 0;
     bool moments = false; /* RTR_ACCUM_MOMENTS: d_q / d_qpart exist and the passes run k_mega<..., ACC = 2> */
@@ -99,6 +107,17 @@ struct rtr_accum {
     int feat_k = 0;
     void* h_out = nullptr; /* pinned, same layout */
     size_t h_out_cap = 0;
+};
+
+/* rtr_history_*: the last frame of rtr_accum_denoise_temporal */
+struct rtr_history {
+    rtr_context* ctx = nullptr;
+    int W = 0, H = 0, x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    DevBuf d_planes[2]; /* [np][RTR_HIST] each; `cur` is the set the next frame reads */
+    DevBuf d_mom;       /* [3][np]: TemporalK::mom */
+    int cur = 0;
+    bool have = false;  /* false: cleared */
+    rtr_camera cam{};   /* the camera d_planes[cur] was seen from */
 };
 
 namespace {
@@ -590,6 +609,9 @@ int accum_render_check(rtr_context* c, const rtr_accum* a) {
     if (int rc = accum_check(c, a)) return rc;
     if (!c->has_scene || a->scene_gen != c->scene_gen)
         return fail(c, RTR_ERR_INVALID, "the scene changed since the accumulator was created (rtr_upload_scene)");
+    if (a->camera_gen != c->camera_gen)
+        return fail(c, RTR_ERR_INVALID, "the camera changed since the accumulator was created or reset (rtr_set_camera): its "
+                                        "samples belong to the old camera, call rtr_accum_reset");
     return RTR_OK;
 }
 
@@ -695,6 +717,12 @@ static void free_accum(rtr_accum* a) {
     delete a;
 }
 
+static void free_history(rtr_history* h) {
+    for (DevBuf* b : {&h->d_planes[0], &h->d_planes[1], &h->d_mom})
+        if (b->p) hipFree(b->p);
+    delete h;
+}
+
 void rtr_launch_resolve(const ResolveK& R, hipStream_t stream) {
     hipLaunchKernelGGL(k_resolve, dim3((unsigned)R.r.n_tiles), dim3(RTR_BLOCK), 0, stream, R);
 }
@@ -785,6 +813,8 @@ void rtr_destroy(rtr_context* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     for (rtr_accum* a : c->accums) free_accum(a);
     c->accums.clear();
+    for (rtr_history* h : c->histories) free_history(h);
+    c->histories.clear();
     DevBuf* bufs[] = {&c->b_nodes, &c->b_kids,  &c->b_mats,    &c->b_tex,   &c->b_perlin, &c->b_images, &c->b_imgbytes,
                       &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise, &c->b_query,
                       &c->b_finst, &c->b_fxf, &c->b_fref, &c->b_fexit, &c->b_fbvh, &c->b_dscene, &c->b_fprim, &c->b_fsub, &c->b_fstep, &c->b_fvisit, &c->b_fscan, &c->b_fleaf, &c->b_fmat, &c->b_fguard};
@@ -1134,6 +1164,10 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
         d.fmat = static_cast<const FMat*>(c->b_fmat.p);
     }
     if ((rc = upload(c, c->b_dscene, &c->ds, sizeof(DScene)))) return rc;
+    c->camera_dirty = false;
+    c->t_lo = std::min(0.0, std::min(s->camera.time0, s->camera.time1)); /* Builder::run of rt_compile.h */
+    c->t_hi = std::max(0.0, std::max(s->camera.time0, s->camera.time1));
+    c->camera_times_small = std::fabs(s->camera.time0) <= 0x1p60 && std::fabs(s->camera.time1) <= 0x1p60;
     c->has_scene = true;
     return RTR_OK;
 }
@@ -1245,6 +1279,11 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     LaunchedKernel launched{};
     c->pending_id = id;
     HIPCHK(c, hipMemsetAsync(c->b_stats.p, 0, RT_STATS_WORDS * sizeof(unsigned long long), c->stream));
+    if (c->camera_dirty) { /* rtr_set_camera: behind every render queued with the old camera, in front of this one */
+        hipLaunchKernelGGL(k_camera_store, dim3(1), dim3(64), 0, c->stream, static_cast<DScene*>(c->b_dscene.p), c->ds.camera);
+        HIPCHK(c, hipGetLastError());
+        c->camera_dirty = false;
+    }
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (pipeline == RTR_PIPELINE_WAVEFRONT) {
         int launches = 0;
@@ -1413,6 +1452,7 @@ int rtr_accum_create_ex(rtr_context* c, const rtr_render_params* p, uint32_t acc
     a->ctx = c;
     a->params = q;
     a->scene_gen = c->scene_gen;
+    a->camera_gen = c->camera_gen;
     a->moments = (accum_flags & RTR_ACCUM_MOMENTS) != 0;
     a->tiles = owned_tiles(q, a->tiles_x, a->tiles_y);
     const size_t n = a->tiles.size();
@@ -1673,13 +1713,19 @@ int denoise_planes(rtr_context* c, int w, int h, const rtr_denoise_params* prm, 
 }
 
 /* prep, the passes and the output on the filled input planes; then the valid pixels into the caller's buffers (linear:
- * row r at h_linear + r * row_stride * 3; 8-bit: rows of w pixels, the top row first) */
-int denoise_run(rtr_context* c, DenoiseK D, double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
+ * row r at h_linear + r * row_stride * 3; 8-bit: rows of w pixels, the top row first).  With `T` the temporal blend and
+ * the history write-back take the place of the prep (rtr_accum_denoise_temporal). */
+int denoise_run(rtr_context* c, DenoiseK D, double* h_linear, int64_t row_stride, uint8_t* h_rgb8, const TemporalK* T = nullptr) {
     const size_t np = (size_t)D.w * D.h;
     const dim3 grid1((unsigned)((np + RTR_BLOCK - 1) / RTR_BLOCK)), grid2((unsigned)((D.w + 15) / 16), (unsigned)((D.h + 15) / 16));
     if (!h_linear) D.out = nullptr;
     if (!h_rgb8) D.rgb8 = nullptr;
-    hipLaunchKernelGGL(k_denoise_prep, grid1, dim3(RTR_BLOCK), 0, c->stream, D);
+    if (T) {
+        hipLaunchKernelGGL(k_temporal_blend, grid2, dim3(RTR_BLOCK), 0, c->stream, D, *T);
+        hipLaunchKernelGGL(k_temporal_store, grid1, dim3(RTR_BLOCK), 0, c->stream, D, *T);
+    } else {
+        hipLaunchKernelGGL(k_denoise_prep, grid1, dim3(RTR_BLOCK), 0, c->stream, D);
+    }
     int src = 0;
     /* steps 1 and 2 from LDS unless RTR_DENOISE_LDS=0 (A/B measurement: INTEGRATION.md section 4, "Denoising") */
     const char* lds_env = getenv("RTR_DENOISE_LDS");
@@ -1711,6 +1757,73 @@ int denoise_run(rtr_context* c, DenoiseK D, double* h_linear, int64_t row_stride
                 h_rgb8[o] = rgb[o], h_rgb8[o + 1] = rgb[o + 1], h_rgb8[o + 2] = rgb[o + 2];
             }
         }
+    return RTR_OK;
+}
+
+/* the defaults of rtr_temporal_defaults ("Camera updates and temporal reprojection") */
+constexpr rtr_temporal_params kTemporalDefaults = {0.05, 0.1, 0.25, 0.25, {0.0, 0.0, 0.0, 0.0}};
+
+int temporal_check(rtr_context* c, const rtr_temporal_params* t) {
+    if (!t) return fail(c, RTR_ERR_INVALID, "null temporal params");
+    if (!(t->alpha_min > 0.0 && t->alpha_min <= 1.0)) return fail(c, RTR_ERR_INVALID, "alpha_min must be in (0, 1]");
+    if (!(t->tau_z > 0.0) || !std::isfinite(t->tau_z) || !(t->tau_n > 0.0) || !std::isfinite(t->tau_n))
+        return fail(c, RTR_ERR_INVALID, "tau_z and tau_n must be finite and > 0");
+    if (!(t->min_weight > 0.0 && t->min_weight < 1.0)) return fail(c, RTR_ERR_INVALID, "min_weight must be in (0, 1)");
+    for (double r : t->reserved)
+        if (r != 0.0) return fail(c, RTR_ERR_INVALID, "reserved fields must be 0");
+    return RTR_OK;
+}
+
+int history_check(rtr_context* c, const rtr_history* h) {
+    if (!h) return fail(c, RTR_ERR_INVALID, "null history");
+    if (h->ctx != c) return fail(c, RTR_ERR_INVALID, "the history belongs to another context");
+    return RTR_OK;
+}
+
+/* rtr_accum_denoise, and with `hist` rtr_accum_denoise_temporal: ONE list of checks, all before any device work; then
+ * features, gather and the filter, with the temporal stage in the prep's place */
+int accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, rtr_history* hist, const rtr_temporal_params* tp,
+                  double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_render_check(c, a)) return rc;
+    if (int rc = denoise_check(c, prm)) return rc;
+    if (hist)
+        if (int rc = temporal_check(c, tp)) return rc;
+    if (!a->moments) return fail(c, RTR_ERR_INVALID, "the accumulator keeps no moments (RTR_ACCUM_MOMENTS)");
+    const rtr_render_params& p = a->params;
+    const int w = p.x1 - p.x0, h = p.y1 - p.y0;
+    if (!h_linear && !h_rgb8) return fail(c, RTR_ERR_INVALID, "no output buffer");
+    if (h_linear && row_stride < (int64_t)w) return fail(c, RTR_ERR_INVALID, "bad output stride");
+    if (p.tile_stride > 1)
+        return fail(c, RTR_ERR_UNSUPPORTED, hist ? "a tile-sharded accumulator: temporal denoising is single-context"
+                                                 : "a tile-sharded accumulator: gather the shards and call rtr_denoise_host");
+    if (hist) {
+        if (int rc = history_check(c, hist)) return rc;
+        if (hist->W != p.image_width || hist->H != p.image_height || hist->x0 != p.x0 || hist->y0 != p.y0 || hist->x1 != p.x1 ||
+            hist->y1 != p.y1)
+            return fail(c, RTR_ERR_INVALID, "the history was created for another image size or region");
+    }
+    const size_t n = a->tiles.size();
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refresh_counts(c, a)) return rc;
+    if (int rc = accum_features(c, a, prm->feature_spp)) return rc;
+    DenoiseK D;
+    if (int rc = denoise_planes(c, w, h, prm, D)) return rc;
+    hipLaunchKernelGGL(k_denoise_gather, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, accum_view(a),
+                       static_cast<const double*>(a->d_q.p), static_cast<const double*>(a->d_feat.p), D);
+    HIPCHK(c, hipGetLastError());
+    if (!hist) return denoise_run(c, D, h_linear, row_stride, h_rgb8);
+    TemporalK T{};
+    T.cam = c->ds.camera, T.prev = hist->cam;
+    T.W = p.image_width, T.H = p.image_height, T.x0 = p.x0, T.y0 = p.y0;
+    T.have = hist->have ? 1 : 0;
+    T.alpha_min = tp->alpha_min, T.tau_z = tp->tau_z, T.tau_n = tp->tau_n, T.min_weight = tp->min_weight;
+    T.hist_in = static_cast<const double*>(hist->d_planes[hist->cur].p);
+    T.hist_out = static_cast<double*>(hist->d_planes[hist->cur ^ 1].p);
+    T.mom = static_cast<double*>(hist->d_mom.p);
+    if (int rc = denoise_run(c, D, h_linear, row_stride, h_rgb8, &T)) return rc;
+    hist->cur ^= 1, hist->have = true, hist->cam = c->ds.camera; /* the write-back counts once the frame has finished */
     return RTR_OK;
 }
 
@@ -1754,27 +1867,7 @@ int rtr_accum_features(rtr_context* c, rtr_accum* a, int32_t feature_spp, double
 
 int rtr_accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, double* h_linear, int64_t row_stride,
                       uint8_t* h_rgb8) {
-    if (!c) return RTR_ERR_INVALID;
-    if (int rc = accum_render_check(c, a)) return rc;
-    if (int rc = denoise_check(c, prm)) return rc;
-    if (!a->moments) return fail(c, RTR_ERR_INVALID, "the accumulator keeps no moments (RTR_ACCUM_MOMENTS)");
-    const rtr_render_params& p = a->params;
-    const int w = p.x1 - p.x0, h = p.y1 - p.y0;
-    if (!h_linear && !h_rgb8) return fail(c, RTR_ERR_INVALID, "no output buffer");
-    if (h_linear && row_stride < (int64_t)w) return fail(c, RTR_ERR_INVALID, "bad output stride");
-    if (p.tile_stride > 1)
-        return fail(c, RTR_ERR_UNSUPPORTED, "a tile-sharded accumulator: gather the shards and call rtr_denoise_host");
-    const size_t n = a->tiles.size();
-    if (n == 0) return RTR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = refresh_counts(c, a)) return rc;
-    if (int rc = accum_features(c, a, prm->feature_spp)) return rc;
-    DenoiseK D;
-    if (int rc = denoise_planes(c, w, h, prm, D)) return rc;
-    hipLaunchKernelGGL(k_denoise_gather, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, accum_view(a),
-                       static_cast<const double*>(a->d_q.p), static_cast<const double*>(a->d_feat.p), D);
-    HIPCHK(c, hipGetLastError());
-    return denoise_run(c, D, h_linear, row_stride, h_rgb8);
+    return accum_denoise(c, a, prm, nullptr, nullptr, h_linear, row_stride, h_rgb8);
 }
 
 int rtr_denoise_host(rtr_context* c, const rtr_denoise_params* prm, int32_t width, int32_t height, const double* h_color,
@@ -2086,6 +2179,143 @@ int rtr_query_occluded_device(rtr_context* c, const rtr_ray* d_rays, uint8_t* d_
     if (int rc = query_check(c, d_rays, d_occluded, n, flags)) return rc;
     if (n == 0) return RTR_OK;
     return query_device(c, d_rays, nullptr, d_occluded, d_rng_out, n, flags, blocking);
+}
+
+} /* extern "C" */
+
+/* ---- camera updates, accumulator reset, temporal reprojection (include/rtr_hip.h) --------------------------------- */
+extern "C" {
+
+int rtr_set_camera(rtr_context* c, const rtr_camera* cam) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!cam) return fail(c, RTR_ERR_INVALID, "null camera");
+    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_set_camera before rtr_upload_scene");
+    static_assert(sizeof(rtr_camera) == 24 * sizeof(double), "rtr_camera is 24 doubles");
+    double v[24];
+    std::memcpy(v, cam, sizeof v);
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(c, RTR_ERR_INVALID, "non-finite camera member");
+    /* what rtr_upload_scene derived from the old camera: the boxes of moving spheres cover the ray times [t_lo, t_hi],
+     * and DScene::shared_div asked for |time| <= 2^60 */
+    for (double t : {cam->time0, cam->time1})
+        if (t < c->t_lo || t > c->t_hi)
+            return fail(c, RTR_ERR_UNSUPPORTED, "camera time " + std::to_string(t) + " outside the range [" + std::to_string(c->t_lo) +
+                                                    ", " + std::to_string(c->t_hi) + "] the scene was compiled for: upload the scene "
+                                                    "with this camera (rtr_upload_scene)");
+    if ((std::fabs(cam->time0) <= 0x1p60 && std::fabs(cam->time1) <= 0x1p60) != c->camera_times_small)
+        return fail(c, RTR_ERR_UNSUPPORTED, "camera times cross the 2^60 bound of the shared divisions: upload the scene with "
+                                            "this camera (rtr_upload_scene)");
+    c->ds.camera = *cam;
+    c->camera_dirty = true;
+    ++c->camera_gen;
+    return RTR_OK;
+}
+
+int rtr_get_camera(rtr_context* c, rtr_camera* out) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!out) return fail(c, RTR_ERR_INVALID, "null out");
+    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_get_camera before rtr_upload_scene");
+    *out = c->ds.camera;
+    return RTR_OK;
+}
+
+int rtr_accum_reset(rtr_context* c, rtr_accum* a, uint32_t seed) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    if (!c->has_scene || a->scene_gen != c->scene_gen)
+        return fail(c, RTR_ERR_INVALID, "the scene changed since the accumulator was created (rtr_upload_scene)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* its queued passes */
+    const size_t n = a->tiles.size();
+    if (n) { /* what rtr_accum_create_ex leaves */
+        HIPCHK(c, hipMemsetAsync(a->d_sum.p, 0, n * 3 * RTR_BLOCK * sizeof(double), c->stream));
+        HIPCHK(c, hipMemsetAsync(a->d_count.p, 0, n * sizeof(int), c->stream));
+        if (a->moments) HIPCHK(c, hipMemsetAsync(a->d_q.p, 0, n * RTR_BLOCK * sizeof(double), c->stream));
+    }
+    a->h_counts.assign(n, 0);
+    a->counts_stale = false;
+    a->feat_k = 0;
+    a->params.seed = seed;
+    a->camera_gen = c->camera_gen;
+    return RTR_OK;
+}
+
+void rtr_temporal_defaults(rtr_temporal_params* p) {
+    if (p) *p = kTemporalDefaults;
+}
+
+int rtr_history_create(rtr_context* c, const rtr_render_params* p, rtr_history** out) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!out) return fail(c, RTR_ERR_INVALID, "null out");
+    *out = nullptr;
+    if (!p) return fail(c, RTR_ERR_INVALID, "null params");
+    if (p->image_width < 2 || p->image_height < 2) return fail(c, RTR_ERR_INVALID, "image smaller than 2x2");
+    if (p->x0 < 0 || p->y0 < 0 || p->x1 > p->image_width || p->y1 > p->image_height || p->x0 >= p->x1 || p->y0 >= p->y1)
+        return fail(c, RTR_ERR_INVALID, "region outside the image or empty");
+    HIPCHK(c, hipSetDevice(c->device));
+    rtr_history* h = new rtr_history();
+    h->ctx = c;
+    h->W = p->image_width, h->H = p->image_height;
+    h->x0 = p->x0, h->y0 = p->y0, h->x1 = p->x1, h->y1 = p->y1;
+    const size_t np = (size_t)(p->x1 - p->x0) * (size_t)(p->y1 - p->y0), bytes = np * RTR_HIST * sizeof(double);
+    int rc = ensure(c, h->d_planes[0], bytes);
+    if (!rc) rc = ensure(c, h->d_planes[1], bytes);
+    if (!rc) rc = ensure(c, h->d_mom, np * 3 * sizeof(double));
+    for (int k = 0; k < 2 && !rc; ++k)
+        if (hipMemsetAsync(h->d_planes[k].p, 0, bytes, c->stream) != hipSuccess) rc = fail(c, RTR_ERR_DEVICE, "hipMemsetAsync of a history");
+    if (rc) {
+        free_history(h);
+        return rc;
+    }
+    c->histories.push_back(h);
+    *out = h;
+    return RTR_OK;
+}
+
+int rtr_history_clear(rtr_context* c, rtr_history* h) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = history_check(c, h)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = (size_t)(h->x1 - h->x0) * (size_t)(h->y1 - h->y0) * RTR_HIST * sizeof(double);
+    for (DevBuf& b : h->d_planes) HIPCHK(c, hipMemsetAsync(b.p, 0, bytes, c->stream));
+    h->have = false;
+    h->cur = 0;
+    h->cam = rtr_camera{};
+    return RTR_OK;
+}
+
+void rtr_history_destroy(rtr_history* h) {
+    if (!h) return;
+    rtr_context* c = h->ctx;
+    hipSetDevice(c->device);
+    if (c->stream) hipStreamSynchronize(c->stream); /* a frame may still use the planes */
+    for (size_t k = 0; k < c->histories.size(); ++k)
+        if (c->histories[k] == h) {
+            c->histories.erase(c->histories.begin() + (long)k);
+            break;
+        }
+    free_history(h);
+}
+
+int rtr_history_planes(rtr_context* c, rtr_history* h, double* h_planes, int64_t row_stride) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = history_check(c, h)) return rc;
+    const int w = h->x1 - h->x0, ht = h->y1 - h->y0;
+    if (!h_planes || row_stride < (int64_t)w) return fail(c, RTR_ERR_INVALID, "bad output buffer / stride");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t row = (size_t)w * RTR_HIST * sizeof(double);
+    HIPCHK(c, hipMemcpy2D(h_planes, (size_t)row_stride * RTR_HIST * sizeof(double), h->d_planes[h->cur].p, row, row, (size_t)ht,
+                          hipMemcpyDeviceToHost));
+    return RTR_OK;
+}
+
+int rtr_accum_denoise_temporal(rtr_context* c, rtr_accum* a, rtr_history* hist, const rtr_denoise_params* prm,
+                               const rtr_temporal_params* tp, double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!hist) return fail(c, RTR_ERR_INVALID, "null history");
+    return accum_denoise(c, a, prm, hist, tp, h_linear, row_stride, h_rgb8);
 }
 
 } /* extern "C" */

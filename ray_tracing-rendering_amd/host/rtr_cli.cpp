@@ -14,6 +14,11 @@
  *           [--denoise [ITER]]   with --passes, --adaptive or a plain --spp (then one accumulator pass): the image after the
  *                                   last pass is denoised (include/rtr_hip.h: rtr_accum_denoise, the library's defaults;
  *                                   ITER in 0..10 replaces their iteration count); prints the denoise time
+ *           [--turntable N [--temporal]]   N frames of a camera orbiting `lookat` about the world y axis (frame k at angle
+ *                                   2 pi k / N), ONE upload: per frame rtr_set_camera, rtr_accum_reset with seed + k, the passes
+ *                                   of --passes (or one to --spp), and with --denoise the filter -- with --temporal (implies
+ *                                   --denoise) rtr_accum_denoise_temporal over one history.  Frames go to out_000.ppm ... (from
+ *                                   --out out.ppm); first device of --devices only; time per frame
  *           [--pick i,j]   nothing is rendered: the closest hit of pixel (i, j)'s centre ray -- u = (i + 0.5) / (W - 1),
  *                                   v = (j + 0.5) / (H - 1), no lens offset, time0 -- through Renderer::closest_hits, as one line
  *                                   `hit front_face material t p n` with the doubles as %.17g
@@ -23,6 +28,75 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+
+/* --turntable: the frame loop of INTEGRATION.md section 4 on the C ABI itself.  Returns the exit status. */
+static int turntable(const SceneConfig& config, int device, int frames, int integrator_id, unsigned seed, std::vector<int> passes,
+                     const rtr_denoise_params* dn, bool temporal, const std::string& out) {
+    const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);
+    auto camera_of = [&](int k) {
+        const double a = 2.0 * 3.14159265358979323846 * k / frames, ca = std::cos(a), sa = std::sin(a);
+        const vec3 d = config.lookfrom - config.lookat;
+        const point3 from = config.lookat + vec3(ca * d[0] + sa * d[2], d[1], -sa * d[0] + ca * d[2]);
+        return camera(from, config.lookat, config.vup, config.vfov, config.aspect_ratio, config.aperture, config.focus_dist, 0.0, 1.0);
+    };
+    rtr_context* ctx = nullptr;
+    if (rtr_create(device, &ctx) != RTR_OK) {
+        std::cerr << "rtr_create: " << rtr_last_error(nullptr) << "\n";
+        return 1;
+    }
+    auto fail = [&](const char* what) {
+        std::cerr << what << ": " << rtr_last_error(ctx) << "\n";
+        rtr_destroy(ctx); /* frees the accumulator and the history */
+        return 1;
+    };
+    rtr_scene_storage st;
+    std::string err;
+    if (!rtr::flatten(*config.world, config.lights, camera_of(0), config.background, st, err)) {
+        std::cerr << "flatten: " << err << "\n";
+        rtr_destroy(ctx);
+        return 1;
+    }
+    rtr_scene_desc d = st.desc();
+    if (rtr_upload_scene(ctx, &d) != RTR_OK) return fail("rtr_upload_scene");
+    rtr_render_params p{};
+    p.image_width = W, p.image_height = H, p.x1 = W, p.y1 = H;
+    p.spp = 1, p.max_depth = 50, p.rr_start_depth = 3, p.integrator = integrator_id, p.seed = seed, p.spp_chunks = 1;
+    rtr_accum* acc = nullptr;
+    rtr_history* hist = nullptr;
+    if (rtr_accum_create_ex(ctx, &p, dn ? RTR_ACCUM_MOMENTS : 0u, &acc) != RTR_OK) return fail("rtr_accum_create_ex");
+    if (temporal && rtr_history_create(ctx, &p, &hist) != RTR_OK) return fail("rtr_history_create");
+    rtr_temporal_params tp{};
+    rtr_temporal_defaults(&tp);
+    std::vector<unsigned char> rgb((size_t)W * H * 3);
+    const size_t dot = out.rfind('.');
+    const std::string stem = dot == std::string::npos ? out : out.substr(0, dot);
+    for (int k = 0; k < frames; ++k) {
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        const rtr_camera cam = camera_of(k).rtr_flatten();
+        if (rtr_set_camera(ctx, &cam) != RTR_OK) return fail("rtr_set_camera");
+        if (rtr_accum_reset(ctx, acc, seed + (unsigned)k) != RTR_OK) return fail("rtr_accum_reset");
+        for (int target : passes)
+            if (rtr_accum_render(ctx, acc, target, 1) != RTR_OK) return fail("rtr_accum_render");
+        const int rc = temporal ? rtr_accum_denoise_temporal(ctx, acc, hist, dn, &tp, nullptr, 0, rgb.data())
+                       : dn     ? rtr_accum_denoise(ctx, acc, dn, nullptr, 0, rgb.data())
+                                : rtr_accum_resolve(ctx, acc, nullptr, 0, rgb.data());
+        if (rc != RTR_OK) return fail("frame output");
+        const double ms = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count() * 1e3;
+        std::cout << "frame " << k << ": " << ms << " ms\n";
+        if (!out.empty()) {
+            char name[32];
+            std::snprintf(name, sizeof name, "_%03d.ppm", k);
+            FILE* f = std::fopen((stem + name).c_str(), "wb");
+            if (!f) return fail("cannot write a frame");
+            std::fprintf(f, "P6\n%d %d\n255\n", W, H);
+            const bool ok = std::fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
+            if (std::fclose(f) != 0 || !ok) return fail("cannot write a frame");
+        }
+    }
+    std::cout << "turntable: " << frames << " frames, scene uploads: 1\n";
+    rtr_destroy(ctx);
+    return 0;
+}
 
 /* "0.004" or "1/255"; false unless the whole string is such a number */
 static bool parse_threshold(const char* s, double& out) {
@@ -41,7 +115,8 @@ static bool parse_threshold(const char* s, double& out) {
 
 int main(int argc, char** argv) {
     int scene_id = 21, integrator_id = 4, width = 0, spp = 0, bands = 0, repeat = 1, spp_min = 0;
-    bool adaptive = false, denoise = false, pick = false;
+    bool adaptive = false, denoise = false, pick = false, temporal = false;
+    int turntable_frames = 0;
     int pick_i = 0, pick_j = 0;
     int denoise_iter = -1;
     double threshold = 0.0;
@@ -74,6 +149,16 @@ int main(int argc, char** argv) {
                 }
                 denoise_iter = (int)v;
             }
+        }
+        else if (!std::strcmp(argv[k], "--temporal")) temporal = true;
+        else if (!std::strcmp(argv[k], "--turntable") && k + 1 < argc) {
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (end == argv[k] || *end != '\0' || v < 1 || v > 999) {
+                std::cerr << "--turntable: N must be an integer in 1..999, not " << argv[k] << "\n";
+                return 2;
+            }
+            turntable_frames = (int)v;
         }
         else if (!std::strcmp(argv[k], "--pick") && k + 1 < argc) {
             pick = std::sscanf(argv[++k], "%d,%d", &pick_i, &pick_j) == 2;
@@ -125,6 +210,15 @@ int main(int argc, char** argv) {
         std::cerr << "--adaptive: --spp (the maximum) must be >= --spp-min\n";
         return 2;
     }
+    if (temporal && !turntable_frames) {
+        std::cerr << "--temporal goes with --turntable\n";
+        return 2;
+    }
+    if (turntable_frames && (adaptive || repeat != 1 || pick)) {
+        std::cerr << "--turntable excludes --adaptive, --repeat and --pick\n";
+        return 2;
+    }
+    if (temporal) denoise = true;
     if (denoise && repeat != 1) {
         std::cerr << "--denoise takes one render (--repeat 1)\n";
         return 2;
@@ -148,6 +242,16 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (adaptive && !spp_min) spp_min = std::min(16, config.samples_per_pixel);
+    if (turntable_frames) {
+        for (size_t k = 0; k < passes.size(); ++k)
+            if (passes[k] < 1 || (k && passes[k] <= passes[k - 1])) {
+                std::cerr << "--passes: increasing sample counts >= 1\n";
+                return 2;
+            }
+        if (passes.empty()) passes.push_back(config.samples_per_pixel);
+        return turntable(config, devices.empty() ? 0 : devices[0], turntable_frames, integrator_id < 0 || integrator_id > 4 ? 4 : integrator_id,
+                         seed, passes, denoise ? &dn : nullptr, temporal, out);
+    }
     auto cam = make_shared<camera>(config.lookfrom, config.lookat, config.vup, config.vfov, config.aspect_ratio,
                                    config.aperture, config.focus_dist, 0.0, 1.0); /* main.cpp:63-66 */
     const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);

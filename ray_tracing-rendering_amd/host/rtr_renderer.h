@@ -259,6 +259,17 @@ class Renderer {
         if (m_integrator) m_integrator->set_max_depth(depth);
     }
     void set_seed(uint32_t seed) { m_seed = seed; } /* the reference has no seed control */
+    /* A new camera for the scene that is on the GPUs (rtr_set_camera on every context): no flattening, no upload.  The
+     * renders that follow use it; accumulators need rtr_accum_reset first.  Returns an rtr_status (RTR_ERR_NO_SCENE
+     * before the first render()).  A later render() with the camera object the scene was uploaded with puts that camera
+     * back first (no upload); one with another camera object uploads, as always. */
+    int set_camera(const camera& cam) {
+        const rtr_camera c = cam.rtr_flatten();
+        for (rtr_context* ctx : m_ctx)
+            if (const int rc = rtr_set_camera(ctx, &c)) return m_error = rtr_last_error(ctx), m_status = rc;
+        m_camera_overridden = true;
+        return RTR_OK;
+    }
     /* The reference's workers store pixels as they finish tiles and main.cpp:124 polls
      * RenderBuffer::get_data() meanwhile.  Here every context renders the image in `n` horizontal bands of whole
      * tile rows, top band first like the reference's tile order (renderer.h:61-62), and stores the tiles it owns
@@ -418,7 +429,13 @@ class Renderer {
             }
             m_scene_bg[0] = background[0], m_scene_bg[1] = background[1], m_scene_bg[2] = background[2];
             m_scene_valid = true;
+            m_camera_overridden = false;
             ++m_scene_uploads;
+        } else if (m_camera_overridden) { /* set_camera() since the upload: the scene's own camera back, without an upload */
+            const rtr_camera c = cam.rtr_flatten();
+            for (rtr_context* ctx : m_ctx)
+                if (const int rc = rtr_set_camera(ctx, &c)) return m_error = rtr_last_error(ctx), rc;
+            m_camera_overridden = false;
         }
         return RTR_OK;
     }
@@ -650,6 +667,7 @@ class Renderer {
     double m_scene_bg[3] = {0, 0, 0};
     double m_denoise_seconds = 0;
     bool m_scene_valid = false;
+    bool m_camera_overridden = false; /* set_camera() replaced the camera the scene was uploaded with */
     int m_scene_uploads = 0;
     int m_status = RTR_OK;
     int m_create_status = RTR_OK; /* a context that could not be created: render() refuses */

@@ -25,7 +25,9 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_accum_create", "rtr_accum_render", "rtr_accum_resolve", "rtr_accum_tiles", "rtr_accum_destroy",
            "rtr_accum_create_ex", "rtr_accum_render_tiles", "rtr_accum_moments", "rtr_accum_errors", "rtr_accum_refine",
            "rtr_denoise_defaults", "rtr_accum_features", "rtr_accum_denoise", "rtr_denoise_host",
-           "rtr_query_closest", "rtr_query_occluded", "rtr_query_closest_device", "rtr_query_occluded_device")
+           "rtr_query_closest", "rtr_query_occluded", "rtr_query_closest_device", "rtr_query_occluded_device",
+           "rtr_set_camera", "rtr_get_camera", "rtr_accum_reset", "rtr_temporal_defaults", "rtr_history_create",
+           "rtr_history_clear", "rtr_history_destroy", "rtr_history_planes", "rtr_accum_denoise_temporal")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
@@ -109,6 +111,17 @@ def lib():
     L.rtr_query_occluded.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32]
     L.rtr_query_closest_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int]
     L.rtr_query_occluded_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int]
+    L.rtr_set_camera.argtypes = [vp, P(A.CameraC)]
+    L.rtr_get_camera.argtypes = [vp, P(A.CameraC)]
+    L.rtr_accum_reset.argtypes = [vp, vp, C.c_uint32]
+    L.rtr_temporal_defaults.argtypes = [P(A.TemporalParamsC)]
+    L.rtr_temporal_defaults.restype = None
+    L.rtr_history_create.argtypes = [vp, P(A.RenderParamsC), P(vp)]
+    L.rtr_history_clear.argtypes = [vp, vp]
+    L.rtr_history_destroy.argtypes = [vp]
+    L.rtr_history_destroy.restype = None
+    L.rtr_history_planes.argtypes = [vp, vp, vp, C.c_int64]
+    L.rtr_accum_denoise_temporal.argtypes = [vp, vp, vp, P(A.DenoiseParamsC), P(A.TemporalParamsC), vp, C.c_int64, vp]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -169,6 +182,34 @@ def denoise_defaults(**overrides):
     return p
 
 
+def temporal_defaults(**overrides):
+    """rtr_temporal_params with the library's defaults (rtr_temporal_defaults), fields replaced by ``overrides``."""
+    p = A.TemporalParamsC()
+    lib().rtr_temporal_defaults(C.byref(p))
+    for k, v in overrides.items():
+        if k not in ("alpha_min", "tau_z", "tau_n", "min_weight"):
+            raise TypeError("no temporal parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def camera_struct(cam):
+    """An ``rtr_camera`` from a ``CAMERA_DTYPE`` record (``Scene.camera``, one element), a mapping of its fields, or a
+    ready ``CameraC``."""
+    if isinstance(cam, A.CameraC):
+        return cam
+    if isinstance(cam, np.ndarray):
+        rec = np.ascontiguousarray(cam, dtype=A.CAMERA_DTYPE).reshape(-1)
+        if len(rec) != 1:
+            raise ValueError("one camera record expected")
+        return A.CameraC.from_buffer_copy(rec.tobytes())
+    out = A.CameraC()
+    for name, ctype in A.CameraC._fields_:
+        v = np.asarray(cam[name], dtype=np.float64).reshape(-1)
+        setattr(out, name, float(v[0]) if ctype is C.c_double else ctype(*v))
+    return out
+
+
 def denoise_host(ctx, color, q, count, feat, params=None, rgb8=False, out=None):
     """rtr_denoise_host on ``ctx``: the denoiser over host planes of a region (row 0 = its lowest row) -- ``color``
     (H, W, 3) linear mean, ``q`` (H, W) second moments, ``count`` (H, W) samples of the pixel's tile (0: not a tap, its
@@ -206,7 +247,8 @@ class Context:
         self._h = h
         self.device = int(device)
         self.scene = None
-        self._accums = weakref.WeakSet()
+        self.camera_updated = False  # set_camera replaced the camera ``scene`` was uploaded with
+        self._accums = weakref.WeakSet()  # (and histories: everything whose handle dies with the context)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -241,6 +283,29 @@ class Context:
         d = scene.desc()
         self._chk(self._L.rtr_upload_scene(self._h, C.byref(d)))
         self.scene = scene
+        self.camera_updated = False
+
+    def set_camera(self, cam):
+        """rtr_set_camera: a new camera (a ``CAMERA_DTYPE`` record, a mapping of its fields or a ``CameraC``) for every
+        call issued from now on, without another upload; the image is the bits of an upload with that camera.
+        Accumulators need ``reset`` before they render again.  ``Context.scene`` stays the uploaded scene;
+        ``Context.camera_updated`` says whether the context's camera differs from ``scene.camera`` (``Renderer`` then puts
+        it back before it renders that scene, and ``camera_ray`` follows the context's camera)."""
+        c = camera_struct(cam)
+        self._chk(self._L.rtr_set_camera(self._h, C.byref(c)))
+        self.camera_updated = self.scene is None or bytes(c) != self.scene.camera.tobytes()
+
+    def camera(self):
+        """rtr_get_camera: the current camera as a one-element ``CAMERA_DTYPE`` array."""
+        c = A.CameraC()
+        self._chk(self._L.rtr_get_camera(self._h, C.byref(c)))
+        return np.frombuffer(bytes(c), dtype=A.CAMERA_DTYPE).copy()
+
+    def history(self, params):
+        """A cleared temporal history (rtr_history_*) for the image size and region of ``params``."""
+        h = History(self, params)
+        self._accums.add(h)
+        return h
 
     def render_into(self, params, device_ptr, row_stride, blocking=False):
         """Linear mean radiance of params' region into a device buffer of doubles."""
@@ -346,7 +411,7 @@ class Context:
         (camera.h get_ray without a lens offset), time = time0; no draw."""
         if self.scene is None:
             raise RtrError(A.RTR_ERR_NO_SCENE, "camera_ray before upload")
-        cam = self.scene.camera
+        cam = self.camera()  # the context's current camera: scene.camera unless set_camera replaced it
         u = (i + 0.5) / (params.image_width - 1)
         v = (j + 0.5) / (params.image_height - 1)
         o = np.asarray(cam["origin"], dtype=np.float64).reshape(3)
@@ -552,9 +617,77 @@ class Accumulator:
                                                      self.shape[1], None))
         return out
 
+    def reset(self, seed):
+        """rtr_accum_reset: every owned tile back to 0 samples, cached features dropped, bound to the context's current
+        camera, with a new seed -- afterwards indistinguishable from a fresh accumulator created with ``seed``."""
+        self._ctx._chk(self._L.rtr_accum_reset(self._ctx._h, self._handle(), int(seed) & 0xFFFFFFFF))
+        self.params.seed = int(seed) & 0xFFFFFFFF
+
+    def denoise_temporal(self, history, params=None, temporal=None, rgb8=False, out=None):
+        """``denoise`` with ``history`` (a ``History`` of the same region) reprojected and blended in before the filter
+        (rtr_accum_denoise_temporal; ``temporal``: an rtr_temporal_params, default ``temporal_defaults()``).  The
+        history then holds this frame, whichever output was asked for."""
+        prm = params if params is not None else denoise_defaults()
+        tp = temporal if temporal is not None else temporal_defaults()
+        out = self._out(out, np.uint8 if rgb8 else np.float64)
+        self._ctx._chk(self._L.rtr_accum_denoise_temporal(
+            self._ctx._h, self._handle(), history._handle(), C.byref(prm), C.byref(tp), None if rgb8 else out.ctypes.data,
+            0 if rgb8 else self.shape[1], out.ctypes.data if rgb8 else None))
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.rtr_accum_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class History:
+    """The last frame of ``Accumulator.denoise_temporal`` (include/rtr_hip.h: rtr_history_*): per pixel of the region 10
+    doubles and the camera they were seen from.  Use as a context manager or call ``close()``."""
+
+    def __init__(self, ctx, params):
+        self._ctx = ctx
+        self._L = ctx._L
+        h = C.c_void_p()
+        ctx._chk(self._L.rtr_history_create(ctx._h, C.byref(params), C.byref(h)))
+        self._h = h
+        self.shape = (params.y1 - params.y0, params.x1 - params.x0)
+
+    def _handle(self):
+        if not self._h:
+            raise RtrError(A.RTR_ERR_INVALID, "history closed")
+        return self._h
+
+    def clear(self):
+        """Forget everything: the next frame has no history."""
+        self._ctx._chk(self._L.rtr_history_clear(self._ctx._h, self._handle()))
+
+    def planes(self, out=None):
+        """What the next frame will read, (H, W, 10) float64, row 0 = the lowest row: demodulated colour 0..2, mu1 3,
+        mu2 4, effective sample count 5 (0: no history), depth 6, normal 7..9."""
+        h, w = self.shape
+        if out is None:
+            out = np.zeros((h, w, A.HISTORY), dtype=np.float64)
+        elif out.shape != (h, w, A.HISTORY) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float64 array of shape (%d, %d, %d)" % (h, w, A.HISTORY))
+        self._ctx._chk(self._L.rtr_history_planes(self._ctx._h, self._handle(), out.ctypes.data, w))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rtr_history_destroy(self._h)
             self._h = None
 
     def __enter__(self):

@@ -115,8 +115,7 @@ class Renderer:
         already flattened; fills the tiles ``rank`` owns."""
         self._rendering = True
         try:
-            if self._ctx.scene is not scene:
-                self._ctx.upload(scene)
+            self._scene_on_device(scene)
             p = A.make_params(target_buffer.width, target_buffer.height, self._spp, integrator=self._integrator,
                               seed=self.seed, max_depth=self._max_depth, pipeline=self.pipeline, tile_first=rank,
                               tile_stride=world, spp_chunks=0)
@@ -149,8 +148,7 @@ class Renderer:
         from .native import RtrError
         self._rendering = True
         try:
-            if self._ctx.scene is not scene:
-                self._ctx.upload(scene)
+            self._scene_on_device(scene)
             p = A.make_params(target_buffer.width, target_buffer.height, 1, integrator=self._integrator, seed=self.seed,
                               max_depth=self._max_depth, pipeline=self.pipeline, tile_first=rank, tile_stride=world)
             with self._ctx.accumulator(p, moments=denoise is not None) as acc:
@@ -194,8 +192,7 @@ class Renderer:
         from .native import RtrError
         self._rendering = True
         try:
-            if self._ctx.scene is not scene:
-                self._ctx.upload(scene)
+            self._scene_on_device(scene)
             p = A.make_params(target_buffer.width, target_buffer.height, 1, integrator=self._integrator, seed=self.seed,
                               max_depth=self._max_depth, pipeline=self.pipeline, tile_first=rank, tile_stride=world)
             total = 0
@@ -218,6 +215,76 @@ class Renderer:
                     yield k, n_active, total
         finally:
             self._rendering = False
+
+    def render_sequence(self, scene, cameras, target_buffer, spp, seeds=None, denoise=None, temporal=None, rank=0, world=1):
+        """The frames of a moving camera: a generator with ONE upload of ``scene`` and, per camera of ``cameras`` (each
+        what ``Context.set_camera`` takes), set_camera, a reset of one accumulator with the frame's seed, a pass to
+        ``spp`` samples and the store into ``target_buffer``; yields the frame index once the buffer holds that frame.
+        ``seeds``: one per frame (default ``self.seed + frame``; frames sharing a seed share their noise pattern, which a
+        temporal blend cannot average away).  ``denoise`` (an rtr_denoise_params) filters each frame; ``temporal`` (an
+        rtr_temporal_params; ``denoise`` then defaults to ``denoise_defaults()``) blends the reprojected last frame in
+        first (rtr_accum_denoise_temporal) over one history that lives as long as the generator.  Single rank:
+        ``world`` > 1 raises ValueError.  Afterwards the context keeps the last camera (``Context.camera_updated``); the
+        other render methods of this class put ``scene.camera`` back before they render ``scene``."""
+        from .native import denoise_defaults
+        if world != 1 or rank != 0:
+            raise ValueError("render_sequence is single rank (a temporal history is not sharded)")
+        cameras = list(cameras)
+        seeds = [self.seed + k for k in range(len(cameras))] if seeds is None else list(seeds)
+        if len(seeds) != len(cameras):
+            raise ValueError("one seed per camera expected: %d seeds, %d cameras" % (len(seeds), len(cameras)))
+        if int(spp) != spp or spp < 1:
+            raise ValueError("spp must be an integer >= 1: %r" % (spp,))
+        if temporal is not None and not isinstance(temporal, A.TemporalParamsC):
+            raise ValueError("temporal must be None or rtr_temporal_params (temporal_defaults())")
+        if temporal is not None and denoise is None:
+            denoise = denoise_defaults()
+        check_denoise(denoise)
+        self._cancel_requested = False
+        return self._sequence(scene, cameras, target_buffer, int(spp), seeds, denoise, temporal)
+
+    def _sequence(self, scene, cameras, target_buffer, spp, seeds, denoise, temporal):
+        from .native import RtrError
+        self._rendering = True
+        try:
+            self._scene_on_device(scene, own_camera=False)  # every frame sets its camera
+            p = A.make_params(target_buffer.width, target_buffer.height, 1, integrator=self._integrator, seed=seeds[0] if seeds else 0,
+                              max_depth=self._max_depth, pipeline=self.pipeline)
+            hist = self._ctx.history(p) if temporal is not None else None
+            try:
+                with self._ctx.accumulator(p, moments=denoise is not None) as acc:
+                    for k, (cam, seed) in enumerate(zip(cameras, seeds)):
+                        if self._cancel_requested:
+                            return
+                        self._ctx.set_camera(cam)
+                        acc.reset(seed)
+                        try:
+                            acc.render(spp)
+                        except RtrError as e:
+                            if e.code == A.RTR_ERR_CANCELLED:
+                                return
+                            raise
+                        if temporal is not None:
+                            target_buffer.store_linear(acc.denoise_temporal(hist, denoise, temporal, out=target_buffer.linear.copy()))
+                        elif denoise is not None:
+                            target_buffer.store_linear(acc.denoise(denoise, out=target_buffer.linear.copy()))
+                        else:
+                            target_buffer.store_linear(acc.resolve(target_buffer.linear.copy()))
+                        yield k
+            finally:
+                if hist is not None:
+                    hist.close()
+        finally:
+            self._rendering = False
+
+    def _scene_on_device(self, scene, own_camera=True):
+        """Upload ``scene`` unless the context holds it already.  ``own_camera``: a scene that is there but is seen from
+        another camera since ``Context.set_camera`` (a ``render_sequence``) gets its own camera back, so a render of
+        ``scene`` is always the image of ``scene.camera``."""
+        if self._ctx.scene is not scene:
+            self._ctx.upload(scene)
+        elif own_camera and self._ctx.camera_updated:
+            self._ctx.set_camera(scene.camera)
 
     def _denoised(self, acc, params, target_buffer, rank, world):
         """The denoised image of ``acc`` over the buffer's linear image.  world > 1: every rank's resolve, moments,
