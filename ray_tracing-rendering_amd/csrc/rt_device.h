@@ -41,7 +41,8 @@ enum { RG_OTHER = 0, RG_SETUP = 1, RG_RECTS = 2, RG_SPHERES = 3, RG_GENERIC = 4,
        RG_SH_SETUP = 8, RG_SH_RECTS = 9, RG_SH_SPHERES = 10, RG_SH_GENERIC = 11, RG_SH_TREE = 12, RG_SH_LEAVES = 13,
        RG_MEDIA = 14, RG_MATPREP = 15, RG_SHADE_A = 16, RG_SHADE_B = 17, RG_MISS = 18, RG_REGEN = 19, RG_SHADE_RR = 20,
        RG_PARK = 21, RG_BARRIER = 22, RG_EXCHANGE = 23, RG_PAIR_SETUP = 24, RG_PAIR_RUNS = 25, RG_PAIR_SPHERES = 26,
-       RG_N = 27 };
+       RG_POLL = 27, RG_BEGIN = 28, RG_SETTLE = 29, RG_COUNT = 30, RG_REJECT = 31, /* the sample boundary of the lockstep loops, split */
+       RG_N = 32 };
 #ifdef RTR_REGION_PROFILE
 __shared__ unsigned long long rt_prof_lds[4 * 2 * RT_PROF_REGIONS + 4 * 2]; /* [wave][cycles | visits][region], then [wave][last, current] */
 RT_DEV void rt_region(int id) {
@@ -56,9 +57,13 @@ RT_DEV void rt_region(int id) {
         st[0] = now, st[1] = (unsigned long long)id;
     }
 }
+/* the region that is current: what a helper called from several regions goes back to */
+RT_DEV int rt_region_current() { return (int)rt_prof_lds[4 * 2 * RT_PROF_REGIONS + (threadIdx.x >> 6) * 2 + 1]; }
 #define RT_REGION(id) rt_region(id)
+#define RT_REGION_CURRENT() rt_region_current()
 #else
 #define RT_REGION(id) do { } while (0)
+#define RT_REGION_CURRENT() 0
 #endif
 
 #define RT_INF (__builtin_huge_val())
@@ -130,12 +135,15 @@ RT_DEV Real rng_sym(uint32_t& s) {
 
 /* vec3::random(-1,1) accepted into the unit ball (vec3.h:226-233); z takes the first draw */
 RT_DEV V3 random_in_unit_sphere(uint32_t& s) {
+    const int region = RT_REGION_CURRENT();
+    RT_REGION(RG_REJECT);
     for (;;) {
         Real z = rng_sym(s);
         Real y = rng_sym(s);
         Real x = rng_sym(s);
         V3 p = mk(x, y, z);
         if (len2(p) >= 1) continue;
+        RT_REGION(region);
         return p;
     }
 }

@@ -53,9 +53,20 @@ struct Park {
     }
     RT_DEV double get(int k) const { return base[k * RTR_BLOCK]; }
     RT_DEV void set(int k, double v) const { base[k * RTR_BLOCK] = v; }
+    /* a word that holds two 32-bit integers (lo, hi): one ds_read_b64 / ds_write_b64 like every other word */
+    RT_DEV void get2(int k, uint32_t& lo, uint32_t& hi) const {
+        const unsigned long long w = (unsigned long long)__double_as_longlong(base[k * RTR_BLOCK]);
+        lo = (uint32_t)w, hi = (uint32_t)(w >> 32);
+    }
+    RT_DEV void set2(int k, uint32_t lo, uint32_t hi) const {
+        base[k * RTR_BLOCK] = __longlong_as_double((long long)((unsigned long long)lo | ((unsigned long long)hi << 32)));
+    }
 };
-enum { PK_THR = 0, PK_L = 3, PK_ACC = 6, PK_PDF = 9, PK_NCLOSEST = 10, PK_NSHADOW = 11, /* every variant */
-       PK_CONTRIB = 12, PK_SWI = 15, PK_STMAX = 18 };                                       /* deferred shadow ray only */
+/* PK_NCAST: the lane's closest-hit (lo) and shadow (hi) cast counts, two uint32 (they end in the uint32 PathCounters);
+ * PK_PIXEL: the lane's pixel (i lo, j hi), which never changes during the kernel: begin_sample reads it back instead
+ * of walking tile_ids and dividing by the tile geometry for every new sample */
+enum { PK_THR = 0, PK_L = 3, PK_ACC = 6, PK_PDF = 9, PK_NCAST = 10, PK_PIXEL = 11, /* every variant */
+       PK_CONTRIB = 12, PK_SWI = 15, PK_STMAX = 18 };                                /* deferred shadow ray only */
 /* a shadow request of shade_a_mis written straight into the parked words PK_SWI, PK_STMAX, PK_CONTRIB */
 struct ParkedReq {
     bool valid;
@@ -137,14 +148,37 @@ struct PhaseClocks {
 #define RTR_CLK(phase) do { } while (0)
 #endif
 
+/* rtr_cancel() in the lockstep loops: the wave polls the cancel word once every RT_POLL_EVERY loop iterations, every
+ * lane in the same iteration (one request for the wave), and reads it before it looks at it: the pair loop issues the
+ * load when the iteration's pair cast is over and takes it after shading, so nobody waits for the round trip (the split
+ * loop issues it after its shadow cast: no register of the poll lives across a cast).  `it` counts the wave's
+ * iterations.  A set word stops every lane of the wave within RT_POLL_EVERY iterations of its arrival: an
+ * iteration is one bounce and a sample has at least one, so that is never later than the 8 samples of the slowest
+ * lane that a per-lane poll keyed on the sample index allowed, and a render cancelled before its launch stops in its
+ * first iteration.  A lane that stops in mid-sample has s < s_end: its workgroup counts as interrupted and the tile
+ * stays untouched, as before.  The word is 0 where no poll was made, and render ids start at 1. */
+#define RT_POLL_EVERY 8
+RT_DEV uint32_t cancel_poll_issue(const RenderK& P, uint32_t it) {
+    uint32_t word = 0;
+    if ((it & (RT_POLL_EVERY - 1)) == 0) word = __hip_atomic_load(P.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return word;
+}
+RT_DEV bool cancel_poll_take(const RenderK& P, uint32_t word) { return word >= P.render_id; }
+
 /* renderer.h:73-75 under the per-sample seed: the camera ray of sample s of the lane's pixel and the parked words of a
  * new path.  K_* : the variant's parked words (PK_* / SK_*); K_L < 0: the loop clears the radiance word itself (the
- * pair cast, step (3)) */
-template <int K_THR, int K_L, int K_PDF>
+ * pair cast, step (3)); K_PIX >= 0: the word that holds the lane's pixel (PK_PIXEL), else it is worked out again */
+template <int K_THR, int K_L, int K_PDF, int K_PIX = -1>
 RT_DEV void begin_sample(const DScene& sc, const RenderK& P, const Park& pk, int slot, int s, uint32_t& rng, PathState& ps) {
     int pi, pj;
-    bool in_region;
-    tile_pixel(P, slot, threadIdx.x, pi, pj, in_region); /* recomputed: not worth two live registers */
+    if (K_PIX >= 0) {
+        uint32_t ui, uj;
+        pk.get2(K_PIX, ui, uj);
+        pi = (int)ui, pj = (int)uj;
+    } else {
+        bool in_region;
+        tile_pixel(P, slot, threadIdx.x, pi, pj, in_region); /* recomputed: not worth two live registers */
+    }
     camera_sample(sc, P, pi, pj, s, rng, ps.ro, ps.rd, ps.tm);
     ps.depth = 0, ps.specular_bounce = false;
     pk.set3(K_THR, mk(1.0, 1.0, 1.0));
@@ -384,10 +418,11 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
          * terms reach L in the reference's order (the light sample of bounce k, then the emission or miss term of bounce
          * k + 1), samples reach the pixel sum in sample order, and a lane whose sample ended keeps that sample's L in
          * PK_L, and the origin of its shadow ray in `so`, while it casts the new sample's camera ray. */
-        pk.set(PK_NCLOSEST, 0.0);
-        pk.set(PK_NSHADOW, 0.0);
+        pk.set2(PK_NCAST, 0u, 0u);
+        pk.set2(PK_PIXEL, (uint32_t)i, (uint32_t)j);
         pk.set3(PK_L, mk(0.0, 0.0, 0.0));
-        if (!done) begin_sample<PK_THR, -1, PK_PDF>(sc, P, pk, slot, s, rng, ps);
+        if (!done) begin_sample<PK_THR, -1, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
+        uint32_t it = 0; /* iterations of the wave: wave-uniform */
         bool pending = false; /* a shadow request is parked: PK_SWI, PK_STMAX, PK_CONTRIB, origin `so` */
         bool settle = false;  /* the sample in PK_L has ended: add it to the pixel sum once its shadow ray is resolved */
         V3 so = mk(0.0, 0.0, 0.0);
@@ -399,14 +434,18 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             Real a_tmax = RT_INF, b_tmax = 0.0;
             int a_ref, a_inst, b_ref;
             V3 swi = mk(1.0, 1.0, 1.0);
-            if (cast_a) {
-                pk.set(PK_NCLOSEST, pk.get(PK_NCLOSEST) + 1.0);
-            } else { /* (the lane's path state is dead: the dummy ray in place, no copies live across the cast) */
+            RT_REGION(RG_COUNT);
+            { /* both counters in one pass over their word, every lane alike (the wave-scalar form miscounts) */
+                uint32_t n_closest, n_shadow;
+                pk.get2(PK_NCAST, n_closest, n_shadow);
+                pk.set2(PK_NCAST, n_closest + (cast_a ? 1u : 0u), n_shadow + (pending ? 1u : 0u));
+            }
+            RT_REGION(RG_OTHER);
+            if (!cast_a) { /* (the lane's path state is dead: the dummy ray in place, no copies live across the cast) */
                 ps.ro = mk(0.0, 0.0, 0.0), ps.rd = mk(1.0, 1.0, 1.0), ps.tm = 0.0;
                 a_tmax = 0.0;
             }
             if (pending) {
-                pk.set(PK_NSHADOW, pk.get(PK_NSHADOW) + 1.0);
                 swi = pk.get3(PK_SWI);
                 b_tmax = pk.get(PK_STMAX);
             } else {
@@ -414,20 +453,26 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             }
             trace_pair(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
             RTR_CLK(closest);
-            RT_REGION(RG_OTHER);
-            if (pending && b_ref < 0) pk.set3(PK_L, add(pk.get3(PK_L), pk.get3(PK_CONTRIB))); /* mis_path_integrator.h:210-213 */
-            pending = false;
-            RT_REGION(RG_REGEN);
-            if (settle) {
-                const V3 L = pk.get3(PK_L);
-                pk.set3(PK_ACC, add(pk.get3(PK_ACC), L)); /* renderer.h:77-78 */
-                if (ACC == 2) {
-                    const double y = luminance(L);
-                    q += y * y;
+            RT_REGION(RG_POLL);
+            const uint32_t cancel_word = cancel_poll_issue(P, it++);
+            RT_REGION(RG_SETTLE);
+            /* steps (2) and (3) in one pass over PK_L: the light sample of B, then the ended sample into the pixel sum */
+            const bool lit = pending && b_ref < 0;
+            if (lit || settle) {
+                V3 L = pk.get3(PK_L);
+                if (lit) L = add(L, pk.get3(PK_CONTRIB)); /* mis_path_integrator.h:210-213 */
+                if (settle) {
+                    pk.set3(PK_ACC, add(pk.get3(PK_ACC), L)); /* renderer.h:77-78 */
+                    if (ACC == 2) {
+                        const double y = luminance(L);
+                        q += y * y;
+                    }
+                    L = mk(0.0, 0.0, 0.0);
+                    settle = false;
                 }
-                pk.set3(PK_L, mk(0.0, 0.0, 0.0));
-                settle = false;
+                pk.set3(PK_L, L);
             }
+            pending = false;
             RTR_CLK(shadow);
             if (cast_a) {
                 bool ended;
@@ -466,13 +511,15 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                     settle = true;
                     ++n_samples;
                     ++s;
-                    done = s >= s_end || ((s & 7) == 0 && render_cancelled(P)); /* (see the split loop) */
-                    if (!done) begin_sample<PK_THR, -1, PK_PDF>(sc, P, pk, slot, s, rng, ps);
+                    done = s >= s_end;
+                    RT_REGION(RG_BEGIN);
+                    if (!done) begin_sample<PK_THR, -1, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
                 }
             }
+            RT_REGION(RG_POLL);
+            if (cancel_poll_take(P, cancel_word)) done = true; /* (an ended sample still settles: the loop's condition) */
         }
-        cnt.closest = (uint32_t)pk.get(PK_NCLOSEST);
-        cnt.shadow = (uint32_t)pk.get(PK_NSHADOW);
+        pk.get2(PK_NCAST, cnt.closest, cnt.shadow);
         clk.flush(P);
     } else {
         /* Without media the shadow ray draws nothing, so it can be cast AFTER the BSDF sample of
@@ -480,19 +527,20 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
          * every iteration (closest hit, shade, shadow ray, end-of-sample + regeneration), so a wave
          * stays in lockstep although path lengths differ; the sums still see their terms in the
          * reference's order (emission, then the light sample of the same bounce). */
-        /* cast counters live in LDS as well (exact in a double up to 2^53) */
-        pk.set(PK_NCLOSEST, 0.0);
-        pk.set(PK_NSHADOW, 0.0);
-        if (!done) begin_sample<PK_THR, PK_L, PK_PDF>(sc, P, pk, slot, s, rng, ps);
+        /* cast counters live in LDS as well */
+        pk.set2(PK_NCAST, 0u, 0u);
+        pk.set2(PK_PIXEL, (uint32_t)i, (uint32_t)j);
+        if (!done) begin_sample<PK_THR, PK_L, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
         PhaseClocks clk;
+        uint32_t it = 0; /* iterations of the wave: wave-uniform */
         while (!done) {
             bool pending = false, ended = false;
+            bool shadowed = false; /* a shadow ray was cast inside the shading (program traversals) */
             RTR_CLK(other);
             RT_REGION(RG_OTHER);
             {
                 Hit rec;
                 rec.u = 0, rec.v = 0;
-                pk.set(PK_NCLOSEST, pk.get(PK_NCLOSEST) + 1.0);
                 const bool hit_any = cast_closest<TRAV, MS == RT_MS_FULL>(sc, ps.ro, ps.rd, ps.tm, rec, rng, st);
                 RTR_CLK(closest);
                 if (!hit_any) {
@@ -525,7 +573,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                                 ps.L = mk(0.0, 0.0, 0.0);
                             }
                             if (rq.valid) {
-                                pk.set(PK_NSHADOW, pk.get(PK_NSHADOW) + 1.0);
+                                shadowed = true;
                                 if (!cast_shadow<TRAV>(sc, rec.p, rq.wi, rq.tmax, rng, st))
                                     pk.set3(PK_L, add(pk.get3(PK_L), rq.contrib));
                                 mc = mat_prepare<MS>(sc, rec); /* cheaper than keeping it in registers across the cast */
@@ -549,11 +597,12 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             RTR_CLK(shade);
             RT_REGION(RG_OTHER);
             if (pending) { /* mis_path_integrator.h:210-213, origin = the hit point = ps.ro */
-                pk.set(PK_NSHADOW, pk.get(PK_NSHADOW) + 1.0);
                 if (!cast_shadow<TRAV>(sc, ps.ro, pk.get3(PK_SWI), pk.get(PK_STMAX), rng, st))
                     pk.set3(PK_L, add(pk.get3(PK_L), pk.get3(PK_CONTRIB)));
             }
             RTR_CLK(shadow);
+            RT_REGION(RG_POLL);
+            const uint32_t cancel_word = cancel_poll_issue(P, it++); /* (no register of it lives across a cast) */
             RT_REGION(RG_REGEN);
             if (ended) {
                 pk.set3(PK_ACC, add(pk.get3(PK_ACC), pk.get3(PK_L))); /* renderer.h:77-78 */
@@ -563,14 +612,20 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 }
                 ++n_samples;
                 ++s;
-                /* rtr_cancel(): polled every 8th sample of a pixel -- the load is a dependent memory round
-                 * trip in the lane's critical path */
-                done = s >= s_end || ((s & 7) == 0 && render_cancelled(P));
-                if (!done) begin_sample<PK_THR, PK_L, PK_PDF>(sc, P, pk, slot, s, rng, ps);
+                done = s >= s_end;
+                RT_REGION(RG_BEGIN);
+                if (!done) begin_sample<PK_THR, PK_L, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
             }
+            RT_REGION(RG_COUNT);
+            { /* one closest-hit cast per iteration of a live lane, and its shadow ray if it cast one */
+                uint32_t n_closest, n_shadow;
+                pk.get2(PK_NCAST, n_closest, n_shadow);
+                pk.set2(PK_NCAST, n_closest + 1u, n_shadow + ((pending || shadowed) ? 1u : 0u));
+            }
+            RT_REGION(RG_POLL);
+            if (cancel_poll_take(P, cancel_word)) done = true; /* rtr_cancel(): cancel_poll_issue */
         }
-        cnt.closest = (uint32_t)pk.get(PK_NCLOSEST);
-        cnt.shadow = (uint32_t)pk.get(PK_NSHADOW);
+        pk.get2(PK_NCAST, cnt.closest, cnt.shadow);
         clk.flush(P);
     }
 #ifdef RTR_REGION_PROFILE

@@ -682,7 +682,9 @@ int finish_stats(rtr_context* c) {
                                           "shade_b (BSDF sample, roulette)", "miss", "end of sample + regeneration",
                                           "shade_rr / shade_path", "park path state", "sorted shading: barrier waits",
                                           "sorted shading: tickets + exchange", "pair cast: instance setup",
-                                          "pair cast: rect runs", "pair cast: sphere runs"};
+                                          "pair cast: rect runs", "pair cast: sphere runs", "sample end: cancel poll",
+                                          "sample end: begin_sample (camera ray)", "sample end: settle into the pixel sum",
+                                          "cast counters", "random_in_unit_sphere rejection loop"};
         double total = 0;
         for (int k = 0; k < RG_N; ++k) total += (double)h[RT_PROF_BASE + k];
         std::fprintf(stderr, "[region profile] %.4g wave cycles in all, %llu samples\n", total, h[0]);
