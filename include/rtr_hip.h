@@ -659,6 +659,82 @@ int rtr_accum_denoise_temporal(rtr_context* ctx, rtr_accum* acc, rtr_history* hi
                                const rtr_temporal_params* temporal, double* h_linear, int64_t row_stride,
                                uint8_t* h_rgb8);
 
+/* ---- display transform: metered exposure, tone curve, 8-bit encoding ----
+ * The last stage in front of a viewer, separate from every output path above (those keep the reference's store).  The
+ * input is linear radiance, 3 doubles per pixel, row 0 the LOWEST row, `row_stride` pixels from one row to the next: the
+ * layout rtr_denoise_host and rtr_accum_resolve write.  Only + - * / sqrt, compares and integer bit operations are used,
+ * so a numpy restatement gives the same bits.  With the defaults the bytes are the reference's store for every finite
+ * input.  bits(v) is the 64-bit pattern of the double v.
+ *
+ * Metering (auto_exposure = 1 and rtr_display_histogram), exact:
+ *   y = 0.2126 * c.x + 0.7152 * c.y + 0.0722 * c.z, left to right
+ *   a pixel is metered if c.x, c.y and c.z are all finite and y >= 2^-20
+ *   its bin: 511 if y >= 2^12, else (bits(y) >> 48) - 0x3EB0 -- 512 bins, 16 per octave (the exponent and the top four
+ *            mantissa bits; no log); the lower edge of bin m is the double with bits (uint64)(m + 0x3EB0) << 48
+ *   n_metered = the number of metered pixels; T = (n_metered * meter_permille + 999) / 1000 in 64-bit integers
+ *   m = the first bin whose cumulative count reaches T; metered = edge(m); scale = (exposure * key) / metered
+ *   with n_metered = 0: scale = exposure, metered = 0
+ * With auto_exposure = 0 nothing is metered: scale = exposure, metered = 0, n_metered = 0.
+ *
+ * Mapping, per channel c of a pixel:
+ *   x = (c is finite and c > 0) ? min(scale * c, 1e30) : 0
+ *   u = the tone curve of x (below), t = u > 0 ? min(u, 1) : 0   (compares only; a NaN becomes 0)
+ *   byte = the code of the encoding (below); the optional FP64 output holds t
+ *
+ * RTR_ENCODE_SRGB is defined by the table S of rtr_display_srgb_thresholds, not by a pow on the device: S[0] = 0 and, for
+ * b = 1..255 with v = b / 255.0, S[b] = v / 12.92 if v <= 0.04045, else pow((v + 0.055) / 1.055, 2.4), computed once on
+ * the host.  The code of t is the number of b in 1..255 with S[b] <= t (each byte's range starts at its own inverse
+ * transfer: truncation, like the gamma-2 store). */
+#define RTR_TONE_CLAMP    0   /* u = x: with exposure 1 and gamma-2 encoding, the reference's store */
+#define RTR_TONE_REINHARD 1   /* u = x * (1.0 + x / (white * white)) / (1.0 + x), left to right */
+#define RTR_TONE_ACES     2   /* u = (x * (2.51 * x + 0.03)) / (x * (2.43 * x + 0.59) + 0.14)   (Narkowicz fit) */
+#define RTR_ENCODE_GAMMA2 0   /* uchar(sqrt(t) * 255), the reference's */
+#define RTR_ENCODE_SRGB   1   /* the number of b in 1..255 with S[b] <= t */
+
+typedef struct rtr_display_params {
+    int32_t auto_exposure;   /* 0: scale = exposure; 1: scale = exposure * key / metered */
+    int32_t meter_permille;  /* 1..1000: which quantile of the metered pixels is `metered` */
+    int32_t tone_curve, encoding;
+    double exposure;         /* finite, > 0 */
+    double key;              /* finite, > 0 */
+    double white;            /* finite, > 0 (Reinhard only) */
+    double reserved[5];      /* must be 0 */
+} rtr_display_params;        /* 80 bytes */
+
+typedef struct rtr_display_result {
+    double scale, metered;
+    int64_t n_metered, reserved;
+} rtr_display_result;        /* 32 bytes */
+
+/* The defaults: auto_exposure 0, meter_permille 500 (the median), RTR_TONE_CLAMP, RTR_ENCODE_GAMMA2, exposure 1,
+ * key 0.18 (middle grey), white 4.  Conventional values, not tuned ones. */
+void rtr_display_defaults(rtr_display_params* p);
+
+/* The 256 thresholds S the library encodes RTR_ENCODE_SRGB with (S[0] = 0, strictly increasing, S[255] = 1). */
+void rtr_display_srgb_thresholds(double out[256]);
+
+/* The metering pass alone over a HOST image: the 512 counts and (unless NULL) their sum.  Needs no scene.  Blocking.
+ * RTR_ERR_INVALID for a NULL buffer, a size outside 1 .. 2^28 pixels or row_stride < width, before any device work. */
+int rtr_display_histogram(rtr_context* ctx, int32_t width, int32_t height, const double* h_linear, int64_t row_stride,
+                          uint32_t h_hist[512], int64_t* n_metered);
+
+/* The transform over a HOST image.  h_rgb8 gets rows of `width` pixels, the TOP row first, like every other 8-bit output
+ * here; h_mapped gets t in the input's layout with row_stride = width.  Either may be NULL, not both; `result` may be
+ * NULL.  Needs no scene.  Blocking.  RTR_ERR_INVALID -- before any device work, outputs untouched -- for NULL params, an
+ * unknown curve or encoding, auto_exposure outside 0..1, meter_permille outside 1..1000, exposure, key or white not
+ * finite or <= 0, non-zero reserved, a size outside 1 .. 2^28 pixels, row_stride < width or a NULL input. */
+int rtr_display_host(rtr_context* ctx, const rtr_display_params* params, int32_t width, int32_t height,
+                     const double* h_linear, int64_t row_stride, uint8_t* h_rgb8, double* h_mapped,
+                     rtr_display_result* result);
+
+/* The same with DEVICE pointers, on the context stream behind whatever is queued there: it follows a non-blocking
+ * rtr_render_device into the same buffer with no host wait in between, and the scale never visits the host.  Returns at
+ * once unless `blocking`; h_result must be NULL unless `blocking`.  The histogram, the scale record and the thresholds
+ * live in a buffer of the context nothing else uses: a queued render or accumulator pass is not disturbed. */
+int rtr_display_device(rtr_context* ctx, const rtr_display_params* params, int32_t width, int32_t height,
+                       const double* d_linear, int64_t row_stride, uint8_t* d_rgb8, double* d_mapped,
+                       rtr_display_result* h_result, int blocking);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

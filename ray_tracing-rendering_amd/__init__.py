@@ -23,7 +23,7 @@ def __getattr__(name):
         import importlib
         return importlib.import_module(__name__ + "." + name)
     if name in ("Context", "RtrError", "library_path", "denoise_defaults", "denoise_host", "temporal_defaults",
-                "History"):
+                "History", "display_defaults", "srgb_thresholds"):
         from . import native
         return getattr(native, name)
     if name in ("Renderer", "RenderBuffer", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):

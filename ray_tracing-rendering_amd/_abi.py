@@ -141,6 +141,25 @@ assert C.sizeof(TemporalParamsC) == TEMPORAL_PARAMS_SIZE
 HISTORY = 10  # doubles per pixel of rtr_history_planes: c 3, mu1, mu2, n, z, nn 3
 
 
+class DisplayParamsC(C.Structure):
+    """rtr_display_params (include/rtr_hip.h): the display transform of rtr_display_host / rtr_display_device"""
+    _fields_ = [("auto_exposure", C.c_int32), ("meter_permille", C.c_int32), ("tone_curve", C.c_int32),
+                ("encoding", C.c_int32), ("exposure", C.c_double), ("key", C.c_double), ("white", C.c_double),
+                ("reserved", C.c_double * 5)]
+
+
+class DisplayResultC(C.Structure):
+    """rtr_display_result (include/rtr_hip.h): the scale a display call used and what it metered"""
+    _fields_ = [("scale", C.c_double), ("metered", C.c_double), ("n_metered", C.c_int64), ("reserved", C.c_int64)]
+
+
+DISPLAY_PARAMS_SIZE, DISPLAY_RESULT_SIZE = 80, 32
+assert C.sizeof(DisplayParamsC) == DISPLAY_PARAMS_SIZE and C.sizeof(DisplayResultC) == DISPLAY_RESULT_SIZE
+TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2
+ENCODE_GAMMA2, ENCODE_SRGB = 0, 1
+DISPLAY_BINS = 512  # bins of rtr_display_histogram: 16 per octave from 2^-20 to 2^12
+
+
 def make_params(width, height, spp, *, integrator=INTEGRATOR_MIS, seed=1, max_depth=50, rr_start_depth=3,
                 region=None, pipeline=PIPELINE_AUTO, tile_first=0, tile_stride=1, spp_chunks=1, flags=0):
     """Build an ``rtr_render_params``.  Defaults follow the reference driver (main.cpp:102,

@@ -1343,4 +1343,148 @@ __global__ void __launch_bounds__(64) k_camera_store(DScene* sc, const rtr_camer
     if (threadIdx.x < 24) dst[threadIdx.x] = src[threadIdx.x];
 }
 
+/* ---- rtr_display_*: metered exposure, tone curve, 8-bit encoding (include/rtr_hip.h) ----
+ * The input is row-major, 3 doubles per pixel, row 0 the lowest row, `row_stride` pixels from row to row.  Three
+ * launches, ordered by the stream alone: k_display_meter (luminance histogram), k_display_scale (the quantile and the
+ * scale into DisplayRec), k_display_apply (curve and encoding).  Only + - * / sqrt, compares and integer bit operations:
+ * a numpy restatement gives the same bits. */
+#define RTR_DISPLAY_BINS 512
+#define RTR_DISPLAY_TRIPS 8 /* pixels per lane of k_display_meter at most: one flush per 2048 pixels */
+struct DisplayRec { /* the layout of rtr_display_result */
+    double scale, metered;
+    long long n_metered, reserved;
+};
+struct DisplayK {
+    int w, h;
+    long long row_stride;
+    const double* in;
+    unsigned* hist;     /* [RTR_DISPLAY_BINS], zeroed on the stream before k_display_meter */
+    DisplayRec* rec;
+    const double* srgb; /* [256]: rtr_display_srgb_thresholds */
+    int auto_exposure, permille, curve, encoding;
+    double exposure, key, white;
+    unsigned char* rgb8; /* null or [h][w][3], Y flipped */
+    double* mapped;      /* null or [h][w][3] */
+};
+
+/* the bin of a pixel, -1 when it is not metered */
+RT_DEV int display_bin(const double r, const double g, const double b) {
+    const unsigned long long inf = 0x7FF0000000000000ull, mag = 0x7FFFFFFFFFFFFFFFull;
+    if ((__double_as_longlong(r) & mag) >= inf || (__double_as_longlong(g) & mag) >= inf || (__double_as_longlong(b) & mag) >= inf)
+        return -1;
+    const double y = 0.2126 * r + 0.7152 * g + 0.0722 * b;
+    if (!(y >= 0x1p-20)) return -1;
+    if (y >= 0x1p12) return RTR_DISPLAY_BINS - 1;
+    return (int)((unsigned long long)__double_as_longlong(y) >> 48) - 0x3EB0;
+}
+
+/* 256 lanes, one pixel per lane per trip; the workgroup's counts gather in LDS and each lane then adds its two bins to
+ * the context's histogram (integer adds: the result does not depend on the order of arrival) */
+__global__ void __launch_bounds__(RTR_BLOCK) k_display_meter(const DisplayK D) {
+    static_assert(RTR_DISPLAY_BINS == 2 * RTR_BLOCK, "two bins per lane");
+    __shared__ unsigned bins[RTR_DISPLAY_BINS];
+    bins[threadIdx.x] = 0, bins[threadIdx.x + RTR_BLOCK] = 0;
+    __syncthreads();
+    const int np = D.w * D.h; /* <= 2^28 */
+    for (long long p = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x; p < np; p += (long long)gridDim.x * RTR_BLOCK) {
+        const int y = (int)p / D.w, x = (int)p - y * D.w;
+        const double* c = D.in + ((long long)y * D.row_stride + x) * 3;
+        const int m = display_bin(c[0], c[1], c[2]);
+        if (m >= 0) atomicAdd(&bins[m], 1u);
+    }
+    __syncthreads();
+    const unsigned n0 = bins[threadIdx.x], n1 = bins[threadIdx.x + RTR_BLOCK];
+    if (n0) atomicAdd(&D.hist[threadIdx.x], n0);
+    if (n1) atomicAdd(&D.hist[threadIdx.x + RTR_BLOCK], n1);
+}
+
+/* one wave: lane l sums bins 8l .. 8l+7, a scan over the lanes finds the lane holding the quantile, that lane walks its
+ * bins.  Without auto exposure the histogram is not read (and was not built). */
+__global__ void __launch_bounds__(64) k_display_scale(const DisplayK D) {
+    const int lane = threadIdx.x;
+    if (!D.auto_exposure) {
+        if (lane == 0) D.rec->scale = D.exposure, D.rec->metered = 0.0, D.rec->n_metered = 0, D.rec->reserved = 0;
+        return;
+    }
+    unsigned cnt[8];
+    long long own = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cnt[k] = D.hist[lane * 8 + k], own += cnt[k];
+    long long incl = own;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const long long o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    const long long n = __shfl(incl, 63, 64);
+    if (n == 0) {
+        if (lane == 0) D.rec->scale = D.exposure, D.rec->metered = 0.0, D.rec->n_metered = 0, D.rec->reserved = 0;
+        return;
+    }
+    const long long T = (n * D.permille + 999) / 1000; /* 1 .. n */
+    long long cum = incl - own;
+    if (cum < T && T <= incl) { /* exactly one lane */
+        int m = lane * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            cum += cnt[k];
+            if (cum >= T) break;
+            ++m;
+        }
+        const double metered = __longlong_as_double((long long)((unsigned long long)(m + 0x3EB0) << 48));
+        D.rec->scale = (D.exposure * D.key) / metered;
+        D.rec->metered = metered, D.rec->n_metered = n, D.rec->reserved = 0;
+    }
+}
+
+/* one lane per pixel: x = scale * c, the tone curve, the clamp, the code; the scale is one address for every lane */
+__global__ void __launch_bounds__(RTR_BLOCK) k_display_apply(const DisplayK D) {
+    static_assert(RTR_BLOCK == 256, "one threshold per lane");
+    __shared__ double S[256];
+    if (D.encoding == RTR_ENCODE_SRGB) { /* workgroup-uniform */
+        S[threadIdx.x] = D.srgb[threadIdx.x];
+        __syncthreads();
+    }
+    const int np = D.w * D.h, p = (int)(blockIdx.x * RTR_BLOCK + threadIdx.x);
+    if (p >= np) return;
+    const double scale = *as_const(&D.rec->scale);
+    const int y = p / D.w, x = p - y * D.w;
+    const double* in = D.in + ((long long)y * D.row_stride + x) * 3;
+    const double ww = D.white * D.white;
+    double t[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double v = in[c];
+        const bool ok = (__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFull) < 0x7FF0000000000000ull && v > 0.0;
+        double e = scale * v;
+        e = e < 1e30 ? e : 1e30;
+        e = ok ? e : 0.0;
+        double u = e;
+        if (D.curve == RTR_TONE_REINHARD)
+            u = e * (1.0 + e / ww) / (1.0 + e);
+        else if (D.curve == RTR_TONE_ACES)
+            u = (e * (2.51 * e + 0.03)) / (e * (2.43 * e + 0.59) + 0.14);
+        t[c] = u > 0.0 ? (u < 1.0 ? u : 1.0) : 0.0; /* NaN -> 0 */
+    }
+    if (D.mapped) {
+        double* o = D.mapped + (long long)p * 3;
+        o[0] = t[0], o[1] = t[1], o[2] = t[2];
+    }
+    if (D.rgb8) {
+        unsigned char* o = D.rgb8 + ((long long)(D.h - 1 - y) * D.w + x) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (D.encoding == RTR_ENCODE_SRGB) {
+                int code = 0;
+#pragma unroll
+                for (int step = 128; step > 0; step >>= 1)
+                    if (S[code + step] <= t[c]) code += step;
+                o[c] = (unsigned char)code;
+            } else {
+                o[c] = static_cast<unsigned char>(__builtin_sqrt(t[c]) * 255);
+            }
+        }
+    }
+}
+
 #endif /* RTR_TU_CAPI */

@@ -55,6 +55,8 @@ struct rtr_context {
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
     DevBuf b_query; /* rtr_query_closest / rtr_query_occluded: one slice of rays and its results (nothing else uses it) */
+    DevBuf b_display;    /* rtr_display_*: the sRGB thresholds (uploaded by rtr_create), the histogram, the DisplayRec */
+    DevBuf b_display_io; /* rtr_display_host / _histogram: the image and its outputs (nothing else uses it) */
     std::vector<int> last_tiles; /* what b_tiles holds */
     WavefrontPool pool;
     void* h_stage = nullptr; /* pinned: rtr_render_tiles_host */
@@ -157,6 +159,25 @@ int upload(rtr_context* c, DevBuf& b, const void* src, size_t bytes) {
     if (bytes) HIPCHK(c, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
     return RTR_OK;
 }
+
+/* rtr_display_srgb_thresholds: S[b] = the inverse sRGB transfer of b / 255.0, computed once on the host.  This table, not
+ * a pow on the device, defines RTR_ENCODE_SRGB. */
+const double* display_srgb_table() {
+    static const struct Table {
+        double s[256];
+        Table() {
+            s[0] = 0.0;
+            for (int b = 1; b < 256; ++b) {
+                const double v = b / 255.0;
+                s[b] = v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4);
+            }
+        }
+    } table;
+    return table.s;
+}
+/* c->b_display: thresholds, histogram, record */
+constexpr size_t kDisplayHistOff = 256 * sizeof(double), kDisplayRecOff = kDisplayHistOff + RTR_DISPLAY_BINS * sizeof(unsigned);
+constexpr size_t kDisplayBytes = kDisplayRecOff + sizeof(DisplayRec);
 
 /* ---- host-only scene validation + traversal stack analysis -------------------------------- */
 struct Validator {
@@ -800,6 +821,9 @@ int rtr_create(int device_ordinal, rtr_context** out_ctx) {
     int rc = ensure(c, c->b_stats, RT_STATS_WORDS * sizeof(unsigned long long));
     if (!rc) rc = ensure(c, c->b_cancel, sizeof(uint32_t));
     if (!rc && hipMemset(c->b_cancel.p, 0, sizeof(uint32_t)) != hipSuccess) rc = RTR_ERR_DEVICE;
+    if (!rc) rc = ensure(c, c->b_display, kDisplayBytes);
+    if (!rc && hipMemcpy(c->b_display.p, display_srgb_table(), 256 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        rc = RTR_ERR_DEVICE;
     if (rc) {
         g_create_error = c->err;
         rtr_destroy(c);
@@ -818,7 +842,7 @@ void rtr_destroy(rtr_context* c) {
     for (rtr_history* h : c->histories) free_history(h);
     c->histories.clear();
     DevBuf* bufs[] = {&c->b_nodes, &c->b_kids,  &c->b_mats,    &c->b_tex,   &c->b_perlin, &c->b_images, &c->b_imgbytes,
-                      &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise, &c->b_query,
+                      &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise, &c->b_query, &c->b_display, &c->b_display_io,
                       &c->b_finst, &c->b_fxf, &c->b_fref, &c->b_fexit, &c->b_fbvh, &c->b_dscene, &c->b_fprim, &c->b_fsub, &c->b_fstep, &c->b_fvisit, &c->b_fscan, &c->b_fleaf, &c->b_fmat, &c->b_fguard};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
@@ -2318,6 +2342,151 @@ int rtr_accum_denoise_temporal(rtr_context* c, rtr_accum* a, rtr_history* hist, 
     if (!c) return RTR_ERR_INVALID;
     if (!hist) return fail(c, RTR_ERR_INVALID, "null history");
     return accum_denoise(c, a, prm, hist, tp, h_linear, row_stride, h_rgb8);
+}
+
+} /* extern "C" */
+
+/* ---- the display transform: metered exposure, tone curve, 8-bit encoding ------------------------------------------- */
+namespace {
+
+/* the defaults of rtr_display_defaults: conventional values (median metering, 18 % grey key), not tuned ones */
+constexpr rtr_display_params kDisplayDefaults = {0, 500, RTR_TONE_CLAMP, RTR_ENCODE_GAMMA2, 1.0, 0.18, 4.0, {0.0, 0.0, 0.0, 0.0, 0.0}};
+
+int display_size_check(rtr_context* c, int32_t w, int32_t h, const void* linear, int64_t row_stride) {
+    if (w < 1 || h < 1 || (int64_t)w * h > ((int64_t)1 << 28)) return fail(c, RTR_ERR_INVALID, "image size out of range");
+    if (!linear || row_stride < (int64_t)w) return fail(c, RTR_ERR_INVALID, "bad input buffer / stride");
+    return RTR_OK;
+}
+
+int display_check(rtr_context* c, const rtr_display_params* p, int32_t w, int32_t h, const void* linear, int64_t row_stride,
+                  const void* rgb8, const void* mapped) {
+    if (!p) return fail(c, RTR_ERR_INVALID, "null display params");
+    if (p->auto_exposure != 0 && p->auto_exposure != 1) return fail(c, RTR_ERR_INVALID, "auto_exposure must be 0 or 1");
+    if (p->meter_permille < 1 || p->meter_permille > 1000) return fail(c, RTR_ERR_INVALID, "meter_permille must be in 1..1000");
+    if (p->tone_curve < RTR_TONE_CLAMP || p->tone_curve > RTR_TONE_ACES) return fail(c, RTR_ERR_INVALID, "unknown tone curve");
+    if (p->encoding != RTR_ENCODE_GAMMA2 && p->encoding != RTR_ENCODE_SRGB) return fail(c, RTR_ERR_INVALID, "unknown encoding");
+    for (double v : {p->exposure, p->key, p->white})
+        if (!(v > 0.0) || !std::isfinite(v)) return fail(c, RTR_ERR_INVALID, "exposure, key and white must be finite and > 0");
+    for (double r : p->reserved)
+        if (r != 0.0) return fail(c, RTR_ERR_INVALID, "reserved fields must be 0");
+    if (int rc = display_size_check(c, w, h, linear, row_stride)) return rc;
+    if (!rgb8 && !mapped) return fail(c, RTR_ERR_INVALID, "no output buffer");
+    return RTR_OK;
+}
+
+DisplayK display_view(rtr_context* c, const rtr_display_params* p, int w, int h, const double* d_linear, int64_t row_stride) {
+    char* base = static_cast<char*>(c->b_display.p);
+    DisplayK D{};
+    D.w = w, D.h = h, D.row_stride = row_stride, D.in = d_linear;
+    D.srgb = reinterpret_cast<const double*>(base);
+    D.hist = reinterpret_cast<unsigned*>(base + kDisplayHistOff);
+    D.rec = reinterpret_cast<DisplayRec*>(base + kDisplayRecOff);
+    if (p) {
+        D.auto_exposure = p->auto_exposure, D.permille = p->meter_permille, D.curve = p->tone_curve, D.encoding = p->encoding;
+        D.exposure = p->exposure, D.key = p->key, D.white = p->white;
+    }
+    return D;
+}
+
+/* the histogram of D.in into D.hist, on the stream: the grid follows the region (RTR_DISPLAY_TRIPS pixels per lane) */
+int display_meter(rtr_context* c, const DisplayK& D) {
+    HIPCHK(c, hipMemsetAsync(D.hist, 0, RTR_DISPLAY_BINS * sizeof(unsigned), c->stream));
+    const size_t np = (size_t)D.w * D.h, per_group = (size_t)RTR_BLOCK * RTR_DISPLAY_TRIPS;
+    hipLaunchKernelGGL(k_display_meter, dim3((unsigned)((np + per_group - 1) / per_group)), dim3(RTR_BLOCK), 0, c->stream, D);
+    return RTR_OK;
+}
+
+/* meter (with auto exposure only), scale, apply: all on the stream, no host wait */
+int display_run(rtr_context* c, const DisplayK& D) {
+    if (D.auto_exposure)
+        if (int rc = display_meter(c, D)) return rc;
+    hipLaunchKernelGGL(k_display_scale, dim3(1), dim3(64), 0, c->stream, D);
+    const size_t np = (size_t)D.w * D.h;
+    hipLaunchKernelGGL(k_display_apply, dim3((unsigned)((np + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), 0, c->stream, D);
+    HIPCHK(c, hipGetLastError());
+    return RTR_OK;
+}
+
+/* after the stream has been waited for */
+int display_result(rtr_context* c, const DisplayK& D, rtr_display_result* out) {
+    static_assert(sizeof(DisplayRec) == sizeof(rtr_display_result), "one layout");
+    if (out) HIPCHK(c, hipMemcpy(out, D.rec, sizeof(DisplayRec), hipMemcpyDeviceToHost));
+    return RTR_OK;
+}
+
+/* the image of a host entry in c->b_display_io: [h][w][3] doubles in, [h][w][3] doubles mapped, [h][w][3] bytes */
+int display_upload(rtr_context* c, int w, int h, const double* h_linear, int64_t row_stride, double*& d_in) {
+    const size_t np = (size_t)w * h, row = (size_t)w * 3 * sizeof(double);
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = ensure(c, c->b_display_io, np * (6 * sizeof(double) + 3))) return rc;
+    d_in = static_cast<double*>(c->b_display_io.p);
+    HIPCHK(c, hipMemcpy2D(d_in, row, h_linear, (size_t)row_stride * 3 * sizeof(double), row, (size_t)h, hipMemcpyHostToDevice));
+    return RTR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void rtr_display_defaults(rtr_display_params* p) {
+    if (p) *p = kDisplayDefaults;
+}
+
+void rtr_display_srgb_thresholds(double out[256]) {
+    if (out) std::memcpy(out, display_srgb_table(), 256 * sizeof(double));
+}
+
+int rtr_display_histogram(rtr_context* c, int32_t width, int32_t height, const double* h_linear, int64_t row_stride,
+                          uint32_t h_hist[512], int64_t* n_metered) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = display_size_check(c, width, height, h_linear, row_stride)) return rc;
+    if (!h_hist) return fail(c, RTR_ERR_INVALID, "no output buffer");
+    double* d_in = nullptr;
+    if (int rc = display_upload(c, width, height, h_linear, row_stride, d_in)) return rc;
+    const DisplayK D = display_view(c, nullptr, width, height, d_in, width);
+    if (int rc = display_meter(c, D)) return rc;
+    HIPCHK(c, hipGetLastError());
+    uint32_t hist[RTR_DISPLAY_BINS];
+    HIPCHK(c, hipMemcpyAsync(hist, D.hist, sizeof(hist), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int64_t n = 0;
+    for (int m = 0; m < RTR_DISPLAY_BINS; ++m) h_hist[m] = hist[m], n += hist[m];
+    if (n_metered) *n_metered = n;
+    return RTR_OK;
+}
+
+int rtr_display_host(rtr_context* c, const rtr_display_params* p, int32_t width, int32_t height, const double* h_linear,
+                     int64_t row_stride, uint8_t* h_rgb8, double* h_mapped, rtr_display_result* result) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = display_check(c, p, width, height, h_linear, row_stride, h_rgb8, h_mapped)) return rc;
+    double* d_in = nullptr;
+    if (int rc = display_upload(c, width, height, h_linear, row_stride, d_in)) return rc;
+    const size_t np = (size_t)width * height;
+    DisplayK D = display_view(c, p, width, height, d_in, width);
+    if (h_mapped) D.mapped = d_in + 3 * np;
+    if (h_rgb8) D.rgb8 = reinterpret_cast<unsigned char*>(d_in + 6 * np);
+    if (int rc = display_run(c, D)) return rc;
+    if (h_mapped) HIPCHK(c, hipMemcpyAsync(h_mapped, D.mapped, 3 * np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_rgb8) HIPCHK(c, hipMemcpyAsync(h_rgb8, D.rgb8, 3 * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return display_result(c, D, result);
+}
+
+int rtr_display_device(rtr_context* c, const rtr_display_params* p, int32_t width, int32_t height, const double* d_linear,
+                       int64_t row_stride, uint8_t* d_rgb8, double* d_mapped, rtr_display_result* h_result, int blocking) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = display_check(c, p, width, height, d_linear, row_stride, d_rgb8, d_mapped)) return rc;
+    if (h_result && !blocking) return fail(c, RTR_ERR_INVALID, "a result needs a blocking call");
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    DisplayK D = display_view(c, p, width, height, d_linear, row_stride);
+    D.mapped = d_mapped, D.rgb8 = d_rgb8;
+    if (int rc = display_run(c, D)) return rc;
+    if (!blocking) return RTR_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return display_result(c, D, h_result);
 }
 
 } /* extern "C" */

@@ -22,6 +22,10 @@
  *           [--pick i,j]   nothing is rendered: the closest hit of pixel (i, j)'s centre ray -- u = (i + 0.5) / (W - 1),
  *                                   v = (j + 0.5) / (H - 1), no lens offset, time0 -- through Renderer::closest_hits, as one line
  *                                   `hit front_face material t p n` with the doubles as %.17g
+ *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
+ *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
+ *                                   rtr_display_host through Renderer::display) of the finished image instead of the
+ *                                   reference's store; prints the scale used.  Not with --turntable
  */
 #include "rtr_renderer.h"
 
@@ -98,6 +102,15 @@ static int turntable(const SceneConfig& config, int device, int frames, int inte
     return 0;
 }
 
+/* a finite number > 0 and nothing else */
+static bool parse_positive(const char* s, double& out) {
+    char* end = nullptr;
+    const double v = std::strtod(s, &end);
+    if (end == s || *end != '\0' || !(v > 0.0) || !std::isfinite(v)) return false;
+    out = v;
+    return true;
+}
+
 /* "0.004" or "1/255"; false unless the whole string is such a number */
 static bool parse_threshold(const char* s, double& out) {
     char* end = nullptr;
@@ -115,7 +128,9 @@ static bool parse_threshold(const char* s, double& out) {
 
 int main(int argc, char** argv) {
     int scene_id = 21, integrator_id = 4, width = 0, spp = 0, bands = 0, repeat = 1, spp_min = 0;
-    bool adaptive = false, denoise = false, pick = false, temporal = false;
+    bool adaptive = false, denoise = false, pick = false, temporal = false, display = false;
+    rtr_display_params dp{};
+    rtr_display_defaults(&dp);
     int turntable_frames = 0;
     int pick_i = 0, pick_j = 0;
     int denoise_iter = -1;
@@ -151,6 +166,28 @@ int main(int argc, char** argv) {
             }
         }
         else if (!std::strcmp(argv[k], "--temporal")) temporal = true;
+        else if (!std::strcmp(argv[k], "--tonemap") && k + 1 < argc) {
+            const char* v = argv[++k];
+            display = true;
+            if (!std::strcmp(v, "clamp")) dp.tone_curve = RTR_TONE_CLAMP;
+            else if (!std::strcmp(v, "reinhard")) dp.tone_curve = RTR_TONE_REINHARD;
+            else if (!std::strcmp(v, "aces")) dp.tone_curve = RTR_TONE_ACES;
+            else {
+                std::cerr << "--tonemap takes clamp, reinhard or aces, not " << v << "\n";
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--auto-exposure")) display = true, dp.auto_exposure = 1;
+        else if (!std::strcmp(argv[k], "--srgb")) display = true, dp.encoding = RTR_ENCODE_SRGB;
+        else if ((!std::strcmp(argv[k], "--exposure") || !std::strcmp(argv[k], "--key") || !std::strcmp(argv[k], "--white")) && k + 1 < argc) {
+            double& field = argv[k][2] == 'e' ? dp.exposure : argv[k][2] == 'k' ? dp.key : dp.white;
+            display = true;
+            if (!parse_positive(argv[k + 1], field)) {
+                std::cerr << argv[k] << " takes a finite number > 0, not " << argv[k + 1] << "\n";
+                return 2;
+            }
+            ++k;
+        }
         else if (!std::strcmp(argv[k], "--turntable") && k + 1 < argc) {
             char* end = nullptr;
             const long v = std::strtol(argv[++k], &end, 10);
@@ -216,6 +253,10 @@ int main(int argc, char** argv) {
     }
     if (turntable_frames && (adaptive || repeat != 1 || pick)) {
         std::cerr << "--turntable excludes --adaptive, --repeat and --pick\n";
+        return 2;
+    }
+    if (display && (turntable_frames || pick)) {
+        std::cerr << "the display options exclude --turntable and --pick\n";
         return 2;
     }
     if (temporal) denoise = true;
@@ -323,8 +364,18 @@ int main(int argc, char** argv) {
     std::cout << "contexts: " << renderer.device_contexts() << "  scene uploads: " << renderer.scene_uploads() << "\n";
     std::cout << "Msamples/s: " << (double)W * H * config.samples_per_pixel / renderer.last_seconds() * 1e-6
               << " (includes flatten, upload and D2H)\n";
+    std::vector<unsigned char> shown;
+    if (display) {
+        rtr_display_result res{};
+        if (renderer.display(buffer, dp, shown, &res) != RTR_OK) {
+            std::cerr << "display failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        std::printf("display: scale %.17g (metered %.17g over %lld pixels)\n", res.scale, res.metered, (long long)res.n_metered);
+    }
+    const std::vector<unsigned char>* bytes = display ? &shown : nullptr;
     const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0; /* main.cpp:138-151 writes a PNG */
-    if (!out.empty() && !(png ? buffer.save_to_png(out) : buffer.save_to_ppm(out))) {
+    if (!out.empty() && !(png ? buffer.save_to_png(out, bytes) : buffer.save_to_ppm(out, bytes))) {
         std::cerr << "Failed to save image to " << out << "\n";
         return 1;
     }

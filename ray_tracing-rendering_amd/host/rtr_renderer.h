@@ -29,6 +29,7 @@ class RenderBuffer {
   public:
     RenderBuffer(int width, int height) : m_width(width), m_height(height) {
         m_pixels.resize(height, std::vector<color>(width));
+        m_linear.assign((size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0) * 3, 0.0);
     }
     void set_pixel(int x, int y, const color& c) {
         if (x >= 0 && x < m_width && y >= 0 && y < m_height) m_pixels[y][x] = c;
@@ -36,12 +37,16 @@ class RenderBuffer {
     const std::vector<std::vector<color>>& get_data() const { return m_pixels; }
     int width() const { return m_width; }
     int height() const { return m_height; }
+    /* the linear mean radiance the store_linear_* calls were given (set_pixel does not touch it): rows of width() pixels,
+     * row 0 = the bottom row, 3 doubles per pixel -- the input of Renderer::display */
+    const double* linear() const { return m_linear.data(); }
     /* write_color_to_buffer (renderer.h:126-140) for rows [y0, y1) of linear mean radiance (the device already
      * applied scale = 1 / samples): sqrt gamma, clamp to [0, 1]; `lin` holds (y1 - y0) rows of `stride` pixels */
     void store_linear_rows(const double* lin, int y0, int y1, int stride) {
         for (int j = y0; j < y1; ++j)
             for (int i = 0; i < m_width; ++i) {
                 const double* px = &lin[((size_t)(j - y0) * stride + i) * 3];
+                keep_linear(i, j, px);
                 set_pixel(i, j, color(clamp(sqrt(px[0]), 0.0, 1.0), clamp(sqrt(px[1]), 0.0, 1.0), clamp(sqrt(px[2]), 0.0, 1.0)));
             }
     }
@@ -68,6 +73,7 @@ class RenderBuffer {
                 const int i = tx0 + q;
                 if (i >= m_width) break;
                 const double* v = &px[(r * 16 + q) * 3];
+                keep_linear(i, j, v);
                 m_pixels[j][i] = color(clamp(sqrt(v[0]), 0.0, 1.0), clamp(sqrt(v[1]), 0.0, 1.0), clamp(sqrt(v[2]), 0.0, 1.0));
             }
         }
@@ -78,14 +84,17 @@ class RenderBuffer {
         for (int j = std::max(0, y0); j < std::min(y1, m_height); ++j)
             for (int i = std::max(0, x0); i < std::min(x1, m_width); ++i) {
                 const double* v = &lin[((size_t)j * stride + i) * 3];
+                keep_linear(i, j, v);
                 m_pixels[j][i] = color(clamp(sqrt(v[0]), 0.0, 1.0), clamp(sqrt(v[1]), 0.0, 1.0), clamp(sqrt(v[2]), 0.0, 1.0));
             }
     }
     /* render_buffer.h:35-55: the bytes of to_rgb8() as an 8-bit RGB PNG.  The reference hands them to stb_image_write;
      * here a plain encoder (filter 0 on every row, one zlib stream): another compressed byte stream, the same pixels
-     * (tests/test_output_stage.py decodes the file and compares them with the reference's own PNG). */
-    bool save_to_png(const std::string& filename) const {
-        const std::vector<unsigned char> rgb = to_rgb8();
+     * (tests/test_output_stage.py decodes the file and compares them with the reference's own PNG).  With `rgb8` (width *
+     * height * 3 bytes, the top row first: what Renderer::display gives) the file holds those bytes instead. */
+    bool save_to_png(const std::string& filename, const std::vector<unsigned char>* rgb8 = nullptr) const {
+        if (rgb8 && rgb8->size() != (size_t)m_width * m_height * 3) return false;
+        const std::vector<unsigned char> rgb = rgb8 ? *rgb8 : to_rgb8();
         std::vector<unsigned char> raw((size_t)m_height * (1 + (size_t)m_width * 3));
         for (int j = 0; j < m_height; ++j) {
             raw[(size_t)j * (1 + (size_t)m_width * 3)] = 0;
@@ -126,11 +135,12 @@ class RenderBuffer {
         std::cerr << "save_to_jpg(" << filename << "): no JPEG encoder in this build; use save_to_png\n";
         return false;
     }
-    /* binary PPM of those bytes */
-    bool save_to_ppm(const std::string& filename) const {
+    /* binary PPM of those bytes (or of `rgb8`, as save_to_png) */
+    bool save_to_ppm(const std::string& filename, const std::vector<unsigned char>* rgb8 = nullptr) const {
+        if (rgb8 && rgb8->size() != (size_t)m_width * m_height * 3) return false;
         FILE* f = std::fopen(filename.c_str(), "wb");
         if (!f) return false;
-        const std::vector<unsigned char> rgb = to_rgb8();
+        const std::vector<unsigned char> rgb = rgb8 ? *rgb8 : to_rgb8();
         std::fprintf(f, "P6\n%d %d\n255\n", m_width, m_height);
         const bool ok = std::fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
         std::fclose(f);
@@ -138,8 +148,12 @@ class RenderBuffer {
     }
 
   private:
+    void keep_linear(int x, int y, const double* v) {
+        if (x >= 0 && x < m_width && y >= 0 && y < m_height) std::memcpy(&m_linear[((size_t)y * m_width + x) * 3], v, 3 * sizeof(double));
+    }
     int m_width, m_height;
     std::vector<std::vector<color>> m_pixels;
+    std::vector<double> m_linear;
 };
 
 class Integrator {
@@ -394,6 +408,21 @@ class Renderer {
             m_error = rtr_last_error(m_ctx[0]);
         if (m_status != RTR_OK) occ.clear();
         return occ;
+    }
+
+    /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
+     * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
+     * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */
+    int display(const RenderBuffer& buf, const rtr_display_params& params, std::vector<uint8_t>& rgb8,
+                rtr_display_result* result = nullptr) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) return m_error = m_create_error, m_status = m_create_status;
+        if (m_ctx.empty()) return m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        rgb8.assign((size_t)buf.width() * buf.height() * 3, 0);
+        if ((m_status = rtr_display_host(m_ctx[0], &params, buf.width(), buf.height(), buf.linear(), buf.width(), rgb8.data(),
+                                         nullptr, result)))
+            m_error = rtr_last_error(m_ctx[0]);
+        return m_status;
     }
 
   private:

@@ -27,7 +27,9 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_denoise_defaults", "rtr_accum_features", "rtr_accum_denoise", "rtr_denoise_host",
            "rtr_query_closest", "rtr_query_occluded", "rtr_query_closest_device", "rtr_query_occluded_device",
            "rtr_set_camera", "rtr_get_camera", "rtr_accum_reset", "rtr_temporal_defaults", "rtr_history_create",
-           "rtr_history_clear", "rtr_history_destroy", "rtr_history_planes", "rtr_accum_denoise_temporal")
+           "rtr_history_clear", "rtr_history_destroy", "rtr_history_planes", "rtr_accum_denoise_temporal",
+           "rtr_display_defaults", "rtr_display_srgb_thresholds", "rtr_display_histogram", "rtr_display_host",
+           "rtr_display_device")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
@@ -122,6 +124,14 @@ def lib():
     L.rtr_history_destroy.restype = None
     L.rtr_history_planes.argtypes = [vp, vp, vp, C.c_int64]
     L.rtr_accum_denoise_temporal.argtypes = [vp, vp, vp, P(A.DenoiseParamsC), P(A.TemporalParamsC), vp, C.c_int64, vp]
+    L.rtr_display_defaults.argtypes = [P(A.DisplayParamsC)]
+    L.rtr_display_defaults.restype = None
+    L.rtr_display_srgb_thresholds.argtypes = [vp]
+    L.rtr_display_srgb_thresholds.restype = None
+    L.rtr_display_histogram.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64, vp, P(C.c_int64)]
+    L.rtr_display_host.argtypes = [vp, P(A.DisplayParamsC), C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, P(A.DisplayResultC)]
+    L.rtr_display_device.argtypes = [vp, P(A.DisplayParamsC), C.c_int32, C.c_int32, vp, C.c_int64, vp, vp,
+                                     P(A.DisplayResultC), C.c_int]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -191,6 +201,28 @@ def temporal_defaults(**overrides):
             raise TypeError("no temporal parameter %r" % k)
         setattr(p, k, v)
     return p
+
+
+def display_defaults(**overrides):
+    """rtr_display_params with the library's defaults (rtr_display_defaults), fields replaced by ``overrides``."""
+    p = A.DisplayParamsC()
+    lib().rtr_display_defaults(C.byref(p))
+    for k, v in overrides.items():
+        if k not in ("auto_exposure", "meter_permille", "tone_curve", "encoding", "exposure", "key", "white"):
+            raise TypeError("no display parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def srgb_thresholds():
+    """rtr_display_srgb_thresholds: the 256 doubles S that define RTR_ENCODE_SRGB (code = how many of S[1..255] are <= t)."""
+    out = np.zeros(256, dtype=np.float64)
+    lib().rtr_display_srgb_thresholds(out.ctypes.data)
+    return out
+
+
+def _display_result(r):
+    return {"scale": r.scale, "metered": r.metered, "n_metered": int(r.n_metered)}
 
 
 def camera_struct(cam):
@@ -403,6 +435,53 @@ class Context:
         self._chk(self._L.rtr_query_occluded_device(self._h, C.c_void_p(rays_ptr), C.c_void_p(occluded_ptr),
                                                     C.c_void_p(rng_out_ptr or None), int(n),
                                                     A.FLAG_REFERENCE_ORDER if reference_order else 0, 1 if blocking else 0))
+
+    # display transform (include/rtr_hip.h: rtr_display_*)
+    @staticmethod
+    def _linear_image(linear):
+        """(array, width, height, row stride in pixels) of an (H, W, 3) float64 image whose rows may be strided"""
+        a = np.asarray(linear, dtype=np.float64)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("an (H, W, 3) image expected")
+        h, w = a.shape[:2]
+        if a.strides[2] != 8 or a.strides[1] != 24 or a.strides[0] % 24 or a.strides[0] < 24 * w:
+            a = np.ascontiguousarray(a)
+        return a, w, h, a.strides[0] // 24
+
+    def luminance_histogram(self, linear):
+        """rtr_display_histogram: (the 512 counts of the metering pass as uint32, the number of metered pixels) of an
+        (H, W, 3) linear image."""
+        a, w, h, stride = self._linear_image(linear)
+        hist = np.zeros(A.DISPLAY_BINS, dtype=np.uint32)
+        n = C.c_int64(0)
+        self._chk(self._L.rtr_display_histogram(self._h, w, h, a.ctypes.data, stride, hist.ctypes.data, C.byref(n)))
+        return hist, int(n.value)
+
+    def display(self, linear, params=None, mapped=False):
+        """rtr_display_host: the display transform (``params``: an rtr_display_params, default ``display_defaults()``)
+        of an (H, W, 3) linear image whose row 0 is the lowest row.  Returns ``(rgb8, result)`` -- (H, W, 3) uint8 with
+        the TOP row first and a dict of scale, metered, n_metered -- or with ``mapped`` ``(rgb8, t, result)``, t the
+        tone-mapped values in [0, 1] as (H, W, 3) float64 in the input's row order."""
+        a, w, h, stride = self._linear_image(linear)
+        prm = params if params is not None else display_defaults()
+        rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
+        t = np.zeros((h, w, 3), dtype=np.float64) if mapped else None
+        res = A.DisplayResultC()
+        self._chk(self._L.rtr_display_host(self._h, C.byref(prm), w, h, a.ctypes.data, stride, rgb8.ctypes.data,
+                                           t.ctypes.data if mapped else None, C.byref(res)))
+        return (rgb8, t, _display_result(res)) if mapped else (rgb8, _display_result(res))
+
+    def display_into(self, linear_ptr, row_stride, width, height, rgb8_ptr, params=None, mapped_ptr=None, blocking=False):
+        """rtr_display_device: the transform of ``height`` rows of ``width`` pixels at device pointer ``linear_ptr``
+        (``row_stride`` pixels apart) into ``rgb8_ptr`` (bytes, top row first) and / or ``mapped_ptr`` (doubles), on the
+        context stream behind what is queued there -- a non-blocking ``render_into`` included.  Returns the result dict
+        when ``blocking``, else None."""
+        prm = params if params is not None else display_defaults()
+        res = A.DisplayResultC()
+        self._chk(self._L.rtr_display_device(self._h, C.byref(prm), int(width), int(height), C.c_void_p(linear_ptr),
+                                             int(row_stride), C.c_void_p(rgb8_ptr or None), C.c_void_p(mapped_ptr or None),
+                                             C.byref(res) if blocking else None, 1 if blocking else 0))
+        return _display_result(res) if blocking else None
 
     def camera_ray(self, params, i, j):
         """The pixel-centre ray of pixel (i, j) of the image ``params`` describes, as a one-element ``RAY_DTYPE`` array with

@@ -32,12 +32,18 @@ class RenderBuffer:
         """The bytes save_to_png writes (render_buffer.h:35-55): Y flipped, uchar(c * 255) truncation."""
         return (self.pixels[::-1] * 255.0).astype(np.uint8)
 
-    def save_to_png(self, filename):
+    def save_to_png(self, filename, rgb8=None):
         """8-bit RGB PNG with the reference's pixel bytes (render_buffer.h:35-55).  The reference
-        encodes with stb_image_write; the zlib stream differs, the decoded pixels do not."""
+        encodes with stb_image_write; the zlib stream differs, the decoded pixels do not.  ``rgb8``: write these
+        (height, width, 3) uint8 pixels, top row first -- what ``Renderer.display`` returns -- instead of ``to_rgb8()``."""
         import struct
         import zlib
-        rgb = self.to_rgb8()
+        if rgb8 is None:
+            rgb = self.to_rgb8()
+        else:
+            rgb = np.ascontiguousarray(rgb8)
+            if rgb.shape != (self.height, self.width, 3) or rgb.dtype != np.uint8:
+                raise ValueError("rgb8 must be a uint8 array of shape (%d, %d, 3)" % (self.height, self.width))
         raw = b"".join(b"\x00" + rgb[j].tobytes() for j in range(self.height))
 
         def chunk(tag, data):
@@ -276,6 +282,13 @@ class Renderer:
                     hist.close()
         finally:
             self._rendering = False
+
+    def display(self, target_buffer, params=None):
+        """The display transform (include/rtr_hip.h: rtr_display_host; ``params``: an rtr_display_params, default
+        ``display_defaults()``) of the buffer's linear image: (height, width, 3) uint8 with the top row first, for
+        ``RenderBuffer.save_to_png(filename, rgb8=...)``.  Metering is global: in a sharded render call it on the rank
+        that holds the gathered image."""
+        return self._ctx.display(target_buffer.linear, params)[0]
 
     def _scene_on_device(self, scene, own_camera=True):
         """Upload ``scene`` unless the context holds it already.  ``own_camera``: a scene that is there but is seen from
