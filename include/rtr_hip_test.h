@@ -1,7 +1,8 @@
 /*
  * rtr_hip_test.h -- entry points of librtr_hip_test.so, a SEPARATE library next to librtr_hip.so (it links against
  * it): device unit kernels that run the product's own device functions (csrc/rt_device.h) over golden-vector records
- * (include/rtr_testrec.h), one lane per record, plus counter-calibration and instruction-level checks.  They exist
+ * (include/rtr_testrec.h), one lane per record, plus counter-calibration and instruction-level checks, and a unit
+ * entry that runs the temporal kernels of the denoiser over caller-given planes (rtr_test_temporal_planes).  They exist
  * so tests can compare the HIP path with the oracle below the whole-image level; none of this code is in the
  * product library, and a renderer integration only needs rtr_hip.h.
  */
@@ -63,6 +64,20 @@ int rtr_test_issue_rates(rtr_context* ctx, double* cycles_per_inst, int n);
  * operand pairs from the range the short form is used in; *mismatches (quotients that differ in any bit) must be 0.
  * *tested: the pairs the kernel compared, 2^32 when every pair drawn was in that range. */
 int rtr_test_shared_division(rtr_context* ctx, uint64_t* mismatches, uint64_t* tested);
+
+/* The temporal stage of rtr_accum_denoise_temporal alone, over HOST planes: the product's k_temporal_blend and
+ * k_temporal_store, launched with the grids of a frame, on a width x height region at (x0, y0) of an image_width x
+ * image_height image.  h_color, h_q, h_count and h_feat are the planes of rtr_denoise_host, h_hist_in the last frame's
+ * history in the layout of rtr_history_planes (10 doubles per pixel, rows of `width` pixels; read only when `have`), cam
+ * the current camera and prev the one the history was seen from.  h_c gets the blended demodulated colour c' (3 doubles
+ * per pixel), h_var the variance var' that enters the first a-trous pass, h_hist_out the history the frame writes.
+ * Pixels with count 0 keep the caller's h_c and h_var values and have an all-zero history.  Needs no scene.  Blocking.
+ * RTR_ERR_INVALID for a NULL pointer, a region outside the image, a negative count or parameters out of range. */
+int rtr_test_temporal_planes(rtr_context* ctx, int32_t width, int32_t height, int32_t image_width, int32_t image_height,
+                             int32_t x0, int32_t y0, const rtr_camera* cam, const rtr_camera* prev, int have,
+                             const rtr_temporal_params* tp, const double* h_color, const double* h_q,
+                             const int32_t* h_count, const double* h_feat, const double* h_hist_in,
+                             double* h_c, double* h_var, double* h_hist_out);
 
 #ifdef __cplusplus
 }

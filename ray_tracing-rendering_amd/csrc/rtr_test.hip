@@ -2,6 +2,9 @@
  * rtr_test.hip -- librtr_hip_test.so: the entry points of include/rtr_hip_test.h.  Test infrastructure, built next to
  * librtr_hip.so and linked against it; it reaches a context only through the seam of csrc/rt_debug.h.
  */
+/* this library is a link unit of its own: it takes its own copy of the non-template kernels of rt_kernels.h, which
+ * inside librtr_hip.so live in rtr_capi.hip alone (rtr_test_temporal_planes launches k_temporal_blend / _store) */
+#define RTR_TU_CAPI
 #include "rt_debug.h"
 #include "rt_launch.h"
 #include "rt_test_kernels.h"
@@ -251,6 +254,75 @@ int rtr_test_shared_division(rtr_context* c, uint64_t* mismatches, uint64_t* tes
     unsigned long long h[2] = {0, 0};
     TCHK(c, hipMemcpy(h, t->buf, 16, hipMemcpyDeviceToHost));
     *mismatches = h[0], *tested = h[1];
+    return RTR_OK;
+}
+
+/* k_temporal_blend and k_temporal_store of the product on caller-given planes: the planes they touch in the test buffer,
+ * the grids of denoise_run (rtr_capi.hip) */
+int rtr_test_temporal_planes(rtr_context* c, int32_t width, int32_t height, int32_t image_width, int32_t image_height, int32_t x0,
+                             int32_t y0, const rtr_camera* cam, const rtr_camera* prev, int have, const rtr_temporal_params* tp,
+                             const double* h_color, const double* h_q, const int32_t* h_count, const double* h_feat,
+                             const double* h_hist_in, double* h_c, double* h_var, double* h_hist_out) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!cam || !prev || !tp || !h_color || !h_q || !h_count || !h_feat || !h_hist_in || !h_c || !h_var || !h_hist_out)
+        return fail(c, RTR_ERR_INVALID, "null argument");
+    if (width < 1 || height < 1 || image_width < 2 || image_height < 2 || x0 < 0 || y0 < 0 || width > image_width - x0 ||
+        height > image_height - y0 || (int64_t)image_width * image_height > ((int64_t)1 << 24))
+        return fail(c, RTR_ERR_INVALID, "region outside the image, or image size out of range");
+    if (!(tp->alpha_min > 0.0 && tp->alpha_min <= 1.0) || !(tp->tau_z > 0.0) || !(tp->tau_n > 0.0) ||
+        !(tp->min_weight > 0.0 && tp->min_weight < 1.0))
+        return fail(c, RTR_ERR_INVALID, "temporal parameter out of range");
+    const size_t np = (size_t)width * height;
+    for (size_t p = 0; p < np; ++p)
+        if (h_count[p] < 0) return fail(c, RTR_ERR_INVALID, "negative sample count");
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc) return rc;
+    /* doubles: m 3, q 1, feat 7, c[0] 3, v[0] 1, a 3, nrm 3, z 1, hist_in 10, hist_out 10, mom 3; then n (int) */
+    const size_t n_doubles = (22 + 2 * RTR_HIST + 3) * np;
+    if ((rc = ensure(c, *t, n_doubles * sizeof(double) + np * sizeof(int)))) return rc;
+    double* d = static_cast<double*>(t->buf);
+    DenoiseK D{};
+    D.w = width, D.h = height;
+    D.m = d, d += 3 * np;
+    D.q = d, d += np;
+    D.feat = d, d += RTR_FEAT * np;
+    D.c[0] = d, d += 3 * np;
+    D.v[0] = d, d += np;
+    D.a = d, d += 3 * np;
+    D.nrm = d, d += 3 * np;
+    D.z = d, d += np;
+    TemporalK T{};
+    T.cam = *cam, T.prev = *prev;
+    T.W = image_width, T.H = image_height, T.x0 = x0, T.y0 = y0;
+    T.have = have ? 1 : 0;
+    T.alpha_min = tp->alpha_min, T.tau_z = tp->tau_z, T.tau_n = tp->tau_n, T.min_weight = tp->min_weight;
+    double* hist_in = d;
+    T.hist_in = hist_in, d += RTR_HIST * np;
+    T.hist_out = d, d += RTR_HIST * np;
+    T.mom = d, d += 3 * np;
+    D.n = reinterpret_cast<int*>(d);
+    TCHK(c, hipMemcpy(D.m, h_color, 3 * np * sizeof(double), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(D.q, h_q, np * sizeof(double), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(D.n, h_count, np * sizeof(int), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(D.feat, h_feat, RTR_FEAT * np * sizeof(double), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(hist_in, h_hist_in, RTR_HIST * np * sizeof(double), hipMemcpyHostToDevice));
+    const dim3 grid1((unsigned)((np + RTR_BLOCK - 1) / RTR_BLOCK)), grid2((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+    hipLaunchKernelGGL(k_temporal_blend, grid2, dim3(RTR_BLOCK), 0, stream, D, T);
+    hipLaunchKernelGGL(k_temporal_store, grid1, dim3(RTR_BLOCK), 0, stream, D, T);
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream));
+    std::vector<double> cc(3 * np), vv(np);
+    TCHK(c, hipMemcpy(cc.data(), D.c[0], 3 * np * sizeof(double), hipMemcpyDeviceToHost));
+    TCHK(c, hipMemcpy(vv.data(), D.v[0], np * sizeof(double), hipMemcpyDeviceToHost));
+    TCHK(c, hipMemcpy(h_hist_out, T.hist_out, RTR_HIST * np * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < np; ++p) {
+        if (h_count[p] == 0) continue;
+        for (int k = 0; k < 3; ++k) h_c[3 * p + k] = cc[p + k * np];
+        h_var[p] = vv[p];
+    }
     return RTR_OK;
 }
 

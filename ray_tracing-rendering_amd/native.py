@@ -32,7 +32,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_display_device")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
-                "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel")
+                "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
+                "rtr_test_temporal_planes")
 _TEST_LIB = None
 
 
@@ -161,6 +162,8 @@ def test_lib():
     T.rtr_test_issue_rates.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     T.rtr_test_shared_division.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
+    T.rtr_test_temporal_planes.argtypes = [vp] + [C.c_int32] * 6 + [C.POINTER(A.CameraC), C.POINTER(A.CameraC), C.c_int,
+                                                                    C.POINTER(A.TemporalParamsC)] + [vp] * 8
     _TEST_LIB = T
     return T
 
@@ -568,6 +571,33 @@ class Context:
     def shared_division_mismatches(self):
         """2^32 operand pairs: how many quotients of the shared-reciprocal division differ from n / d (include/rtr_hip_test.h)."""
         return self.shared_division_exhaustive()[0]
+
+    def temporal_planes(self, color, q, count, feat, hist, have, cam, prev, image_size, origin, params=None, c=None, var=None):
+        """rtr_test_temporal_planes (include/rtr_hip_test.h): the temporal kernels alone over host planes of a region at
+        ``origin`` = (x0, y0) of an image of ``image_size`` = (W, H) -- planes as ``denoise_host`` takes them, ``hist`` (H, W,
+        10) as ``History.planes`` returns it, cameras as ``set_camera`` takes them.  Returns (c' (H, W, 3), var' (H, W),
+        the history written (H, W, 10)); pixels with count 0 keep the values of ``c`` and ``var`` (zeros if not given)."""
+        color = np.ascontiguousarray(color, dtype=np.float64)
+        h, w = color.shape[:2]
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        count = np.ascontiguousarray(count, dtype=np.int32)
+        feat = np.ascontiguousarray(feat, dtype=np.float64)
+        hist = np.ascontiguousarray(hist, dtype=np.float64)
+        if (color.shape != (h, w, 3) or q.shape != (h, w) or count.shape != (h, w) or feat.shape != (h, w, A.FEATURES)
+                or hist.shape != (h, w, 10)):
+            raise ValueError("planes of shapes (H, W, 3), (H, W), (H, W), (H, W, 7), (H, W, 10) expected")
+        c = np.zeros((h, w, 3)) if c is None else np.array(c, dtype=np.float64, order="C")
+        var = np.zeros((h, w)) if var is None else np.array(var, dtype=np.float64, order="C")
+        if c.shape != (h, w, 3) or var.shape != (h, w):
+            raise ValueError("c of shape (H, W, 3) and var of shape (H, W) expected")
+        new = np.zeros((h, w, 10))
+        tp = params if params is not None else temporal_defaults()
+        cc, pc = camera_struct(cam), camera_struct(prev)
+        self._chk(test_lib().rtr_test_temporal_planes(
+            self._h, w, h, int(image_size[0]), int(image_size[1]), int(origin[0]), int(origin[1]), C.byref(cc), C.byref(pc),
+            1 if have else 0, C.byref(tp), color.ctypes.data, q.ctypes.data, count.ctypes.data, feat.ctypes.data,
+            hist.ctypes.data, c.ctypes.data, var.ctypes.data, new.ctypes.data))
+        return c, var, new
 
     # device unit kernels over golden-vector records (include/rtr_hip_test.h)
     def test_records(self, kind, recs, params=None):

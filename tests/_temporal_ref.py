@@ -49,7 +49,9 @@ def reproject(cam, prev, W, H, x0, y0, z):
 
 def blend(color, q, count, feat, hist, have, cam, prev, W, H, x0, y0, alpha_min, tau_z, tau_n, min_weight):
     """The stage in front of the filter: (c', var', a, nn, z, valid, new history, info); info holds the masks the tests
-    look at: ``has_history`` and ``accepted`` (taps accepted per pixel, 0..4)."""
+    look at: ``has_history``, ``accepted`` (taps accepted per pixel, 0..4), ``rejected`` (taps turned down per pixel, by the
+    first compare that failed: ``border`` outside the region, ``empty`` history n <= 0, ``depth``, ``normal``) and the pixels
+    without history because z <= 0 (``no_depth``), zc <= 0 (``behind``) or sw < min_weight (``light``), and ``sw`` itself."""
     color = np.asarray(color, dtype=np.float64)
     q = np.asarray(q, dtype=np.float64)
     count = np.asarray(count)
@@ -68,6 +70,9 @@ def blend(color, q, count, feat, hist, have, cam, prev, W, H, x0, y0, alpha_min,
         ne = n_cur
         accepted = np.zeros((h, w), dtype=np.int32)
         has = np.zeros((h, w), dtype=bool)
+        rejected = {k: np.zeros((h, w), dtype=np.int32) for k in ("border", "empty", "depth", "normal")}
+        no_depth = behind = light = np.zeros((h, w), dtype=bool)
+        sw = np.zeros((h, w))
         if have:
             x, y, z_exp, zc = reproject(cam, prev, W, H, x0, y0, z)
             ok = valid & (z > 0.0) & (zc > 0.0)
@@ -82,16 +87,23 @@ def blend(color, q, count, feat, hist, have, cam, prev, W, H, x0, y0, alpha_min,
                 ix = (np.where(inside, tx, float(x0)) - x0).astype(np.int64)
                 iy = (np.where(inside, ty, float(y0)) - y0).astype(np.int64)
                 ht = hist[iy, ix]
-                acc = inside & (ht[..., 5] > 0.0)
+                has_n = ht[..., 5] > 0.0
                 ez = z_exp - ht[..., 6]
-                acc &= np.where(ez < 0.0, -ez, ez) <= z_tol
+                z_ok = np.where(ez < 0.0, -ez, ez) <= z_tol
                 e = nn - ht[..., 7:10]
-                acc &= e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1] + e[..., 2] * e[..., 2] <= tau_n
+                n_ok = e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1] + e[..., 2] * e[..., 2] <= tau_n
+                acc = inside & has_n & z_ok & n_ok
+                # why a tap was turned down, in the order of the compares
+                rejected["border"] += ok & ~inside
+                rejected["empty"] += inside & ~has_n
+                rejected["depth"] += inside & has_n & ~z_ok
+                rejected["normal"] += inside & has_n & z_ok & ~n_ok
                 wt = (fx if tap & 1 else 1.0 - fx) * (fy if tap >> 1 else 1.0 - fy)
                 sw = np.where(acc, sw + wt, sw)
                 hs = np.where(acc[..., None], hs + wt[..., None] * ht[..., 0:6], hs)
                 accepted += acc
             has = ok & (sw >= min_weight)
+            no_depth, behind, light = valid & ~(z > 0.0), valid & (z > 0.0) & ~(zc > 0.0), ok & ~(sw >= min_weight)
             n_h = hs[..., 5] / sw
             alpha = n_cur / (n_cur + n_h)
             alpha = np.where(alpha > alpha_min, alpha, alpha_min)
@@ -107,7 +119,8 @@ def blend(color, q, count, feat, hist, have, cam, prev, W, H, x0, y0, alpha_min,
     new = np.zeros((h, w, HISTORY))
     new[..., 0:3], new[..., 3], new[..., 4], new[..., 5], new[..., 6], new[..., 7:10] = c, mu1, mu2, ne, z, nn
     new[~valid] = 0.0
-    return c, var, a, nn, z, valid, new, {"has_history": has, "accepted": accepted}
+    return c, var, a, nn, z, valid, new, {"has_history": has, "accepted": accepted, "rejected": rejected, "no_depth": no_depth,
+                                          "behind": behind, "light": light, "sw": sw}
 
 
 def denoise_temporal(color, q, count, feat, hist, have, cam, prev, W, H, x0, y0, prm, tp):

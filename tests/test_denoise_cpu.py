@@ -200,3 +200,106 @@ def test_invalid_pixels_are_never_taps():
     feat[:, 10:] = -3.0
     b = D.denoise(color, q, count, feat, **prm)
     assert np.array_equal(a[:, :10], b[:, :10]) and np.isfinite(a[:, :10]).all()
+
+
+# ---- synthetic planes (tests/_planes.py): the builders hit what they aim at, and the restatement equals a scalar
+# reference written from the header alone ------------------------------------------------------------------------------
+
+import _planes as P  # noqa: E402
+
+DEFAULTS = D.denoise_params(rtr.native.denoise_defaults())
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def test_planes_hold_every_special_value_on_valid_pixels():
+    """the plane of the GPU pattern tests, without a mask: every count, albedo and depth occurs on a valid pixel, next to
+    holes; q lies on both sides of n * lum(m)^2; holes are NaN in every plane"""
+    color, q, count, feat = P.planes(40, 36, 1)
+    v = count > 0
+    assert set(np.unique(count)) == set(P.COUNTS) and P.COUNTS[-1] == np.iinfo(np.int32).max
+    for a in P.ALBEDOS:
+        assert (feat[v][:, 0:3] == a).any(), a
+    assert np.nextafter(1e-3, 0.0) < 1e-3 < np.nextafter(1e-3, 1.0) and len(set(P.ALBEDOS)) == 7
+    z = feat[v][:, 6]
+    for d in P.DEPTHS:
+        assert ((z == d) & (np.signbit(z) == np.signbit(d))).any(), d
+    assert len(set(P.DEPTHS)) == 8 and len(P.DEPTHS) == 9  # 0.0 and -0.0 are one value, two bit patterns
+    length = np.sqrt((feat[v][:, 3:6] ** 2).sum(-1))
+    assert (length == 0.0).any() and (np.abs(length[length > 0.0] - 1.0) < 1e-15).all()
+    d = q[v] / count[v] - D.lum(color[v]) ** 2
+    assert (d > 0.0).mean() > 0.5 and (d < 0.0).sum() > 20
+    assert ((color[v] >= 0.0) & (color[v] < 2.0)).all()
+    for plane in (color, q, feat):
+        assert np.isnan(plane[~v]).all() and np.isfinite(plane[v]).all()
+    # n = 1 (variance 1e30) next to n >= 2
+    one = count == 1
+    assert (one[:, :-1] & (count[:, 1:] >= 2)).any()
+    # the same seed gives the same planes; a 1 x 1 plane has its one pixel valid
+    again = P.planes(40, 36, 1)
+    assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip((color, q, count, feat), again))
+    for seed in range(8):
+        assert P.planes(1, 1, seed)[2][0, 0] > 0
+
+
+def test_hole_patterns_have_the_neighbours_they_are_meant_to_have():
+    m = P.patterns(40, 36)
+    assert set(m) == {"checkerboard", "lone_valid", "lone_hole", "seam_15", "seam_16", "seam_17", "frame"}
+    c = m["checkerboard"]
+    assert (c[:, 1:] != c[:, :-1]).all() and (c[1:] != c[:-1]).all()  # every 4-neighbour of a valid pixel is a hole
+    assert m["lone_valid"].sum() == 1 and m["lone_valid"][16, 15]      # in the corner of a workgroup
+    assert (~m["lone_hole"]).sum() == 1 and not m["lone_hole"][16, 15]
+    for s in (15, 16, 17):
+        k = m["seam_%d" % s]
+        assert not k[s].any() and not k[:, s].any() and k.sum() == 39 * 35
+    f = m["frame"]
+    assert f[0].all() and f[-1].all() and f[:, 0].all() and f[:, -1].all() and not f[1:-1, 1:-1].any()
+    for name, mask in m.items():
+        count = P.planes(40, 36, 2, valid=mask)[2]
+        assert np.array_equal(count > 0, mask), name
+    assert set(P.patterns(1, 1)) == {"checkerboard", "lone_valid", "lone_hole"}  # (lone_hole of one pixel is empty)
+
+
+def _scalar_equals_restatement(planes, prm):
+    want = P.scalar_denoise(*planes, **prm)
+    got = D.denoise(*planes, **prm)
+    v = planes[2] > 0
+    assert np.isfinite(got[v]).all()  # a condition on the inputs: the "finite" planes give finite outputs
+    assert np.array_equal(_bits(got[v]), _bits(want[v])) and np.isnan(got[~v]).all() and np.isnan(want[~v]).all()
+
+
+@pytest.mark.parametrize("iterations", [0, 1, 2, 3, 10])
+@pytest.mark.parametrize("h,w", [(1, 1), (1, 17), (17, 1), (13, 20), (33, 18)])
+def test_restatement_equals_the_scalar_reference(h, w, iterations):
+    """_denoise_ref.denoise, the oracle of the GPU tests, against plain Python floats looping over pixels and taps as the
+    header's "Filter" comment orders them: every bit of every valid pixel"""
+    _scalar_equals_restatement(P.planes(h, w, 10 + h * w), dict(DEFAULTS, iterations=iterations))
+
+
+@pytest.mark.parametrize("pattern", ["checkerboard", "lone_valid", "lone_hole", "seam_15", "seam_16", "seam_17", "frame"])
+def test_restatement_equals_the_scalar_reference_on_hole_patterns(pattern):
+    h, w = 24, 25
+    _scalar_equals_restatement(P.planes(h, w, 3, valid=P.patterns(h, w)[pattern]), DEFAULTS)
+
+
+@pytest.mark.parametrize("sigma", ["sigma_l", "sigma_n", "sigma_a", "sigma_z"])
+@pytest.mark.parametrize("value", [1e-6, 1e6])
+def test_restatement_equals_the_scalar_reference_at_sigma_extremes(sigma, value):
+    _scalar_equals_restatement(P.planes(17, 17, 4), dict(DEFAULTS, **{sigma: value}))
+
+
+def test_restatement_is_translation_invariant():
+    """a 13 x 20 patch anywhere in a field of NaN-filled holes: the bits of the patch alone"""
+    patch = P.planes(13, 20, 5)
+    want = D.denoise(*patch, **DEFAULTS)
+    for oy, ox in [(0, 0), (0, 1), (15, 15), (16, 16), (29, 13), (48 - 13, 64 - 20)]:
+        field = [np.full((48, 64) + x.shape[2:], 0 if x.dtype == np.int32 else np.nan, dtype=x.dtype) for x in patch]
+        for big, small in zip(field, patch):
+            big[oy:oy + 13, ox:ox + 20] = small
+        got = D.denoise(*field, **DEFAULTS)
+        assert np.array_equal(_bits(got[oy:oy + 13, ox:ox + 20]), _bits(want))
+        outside = np.ones((48, 64), dtype=bool)
+        outside[oy:oy + 13, ox:ox + 20] = False
+        assert np.isnan(got[outside]).all()

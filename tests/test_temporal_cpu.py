@@ -254,3 +254,174 @@ def test_cli_turntable_rejects_bad_arguments(extra, tmp_path):
     assert r.returncode == 2, (r.returncode, r.stderr)
     assert r.stderr.strip()
     assert not list(tmp_path.iterdir())
+
+
+# ---- synthetic temporal cases (tests/_planes.py): the restatement equals a scalar reference written from the header
+# alone, and the cases reach every branch of the blend ----------------------------------------------------------------
+
+import _planes as P  # noqa: E402
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+@pytest.fixture(scope="module")
+def cases():
+    """every case with what the restatement makes of it, computed once"""
+    out = {}
+    for name in P.TEMPORAL_CASES:
+        case = P.temporal_case(name)
+        args, tp = P.blend_args(case)
+        out[name] = (case, T.blend(*args, **tp))
+    return out
+
+
+def test_case_defaults_are_the_librarys():
+    tp = rtr.native.temporal_defaults()
+    assert P.TEMPORAL_DEFAULTS == {k: getattr(tp, k) for k in ("alpha_min", "tau_z", "tau_n", "min_weight")}
+
+
+@pytest.mark.parametrize("name", P.TEMPORAL_CASES)
+def test_restatement_equals_the_scalar_reference(cases, name):
+    """_temporal_ref.blend, the oracle of the GPU tests, against plain Python floats, one pixel and one tap at a time in
+    the order of the header's comment: c', var' and the history it writes, every bit of every valid pixel -- and once
+    more with that history fed back in under a static camera"""
+    case, got = cases[name]
+    args, tp = P.blend_args(case)
+    for frame in range(2):
+        c, var, new = P.scalar_blend(*args, **tp)
+        v = case["count"] > 0
+        assert np.array_equal(_bits(got[0][v]), _bits(c[v])) and np.array_equal(_bits(got[1][v]), _bits(var[v]))
+        assert np.array_equal(_bits(got[6]), _bits(new)) and (new[~v] == 0.0).all()
+        assert np.isfinite(got[0][v]).all() and np.isfinite(got[1][v]).all()
+        args[4], args[7] = new, case["cam"]
+        got = T.blend(*args, **tp)
+
+
+def test_cases_reach_every_branch(cases):
+    """over all cases: every number of accepted taps, pixels with and without history for each reason, every reason to
+    turn a tap down"""
+    accepted, rejected = set(), {"border": 0, "empty": 0, "depth": 0, "normal": 0}
+    without = {"no_depth": 0, "behind": 0, "light": 0}
+    with_history = 0
+    for name, (case, got) in cases.items():
+        info = got[7]
+        v = case["count"] > 0
+        accepted |= set(np.unique(info["accepted"][v & (case["feat"][..., 6] > 0.0)]))
+        with_history += int(info["has_history"].sum())
+        for k in rejected:
+            rejected[k] += int(info["rejected"][k].sum())
+        for k in without:
+            without[k] += int(info[k].sum())
+        assert not info["has_history"][~v].any() and (info["accepted"][~v] == 0).all()
+    assert accepted == {0, 1, 2, 3, 4}
+    assert with_history > 0 and all(n > 0 for n in rejected.values()) and all(n > 0 for n in without.values()), (rejected, without)
+
+
+def test_static_camera_lands_on_pixel_centres_and_floor_falls_either_side(cases):
+    case, got = cases["static-whole"]
+    x, y, _, _ = T.reproject(case["cam"], case["prev"], P.IMAGE_W, P.IMAGE_H, 0, 0, case["feat"][..., 6])
+    v = (case["count"] > 0) & (case["feat"][..., 6] > 0.0)
+    jj, ii = np.mgrid[0:P.IMAGE_H, 0:P.IMAGE_W]
+    assert np.abs(x - ii)[v].max() < 1e-12 and np.abs(y - jj)[v].max() < 1e-12
+    below, above = (np.floor(x) == ii - 1) & v, (np.floor(x) == ii) & v
+    assert below.any() and above.any() and ((np.floor(y) == jj - 1) & v).any()
+    # a tap at x0 - 1 or y0 - 1 is turned down at the border of a region inside the image
+    case, got = cases["static-17x16_inside"]
+    x, y, _, _ = T.reproject(case["cam"], case["prev"], P.IMAGE_W, P.IMAGE_H, case["x0"], case["y0"], case["feat"][..., 6])
+    v = (case["count"] > 0) & (case["feat"][..., 6] > 0.0)
+    left, low = v & (np.floor(x) == case["x0"] - 1), v & (np.floor(y) == case["y0"] - 1)
+    assert left.any() and low.any()
+    assert (got[7]["rejected"]["border"][left] >= 2).all() and (got[7]["rejected"]["border"][low] >= 2).all()
+
+
+def test_moves_do_what_they_are_named_for(cases):
+    for region in P.temporal_regions():
+        case, got = cases["yaw_180-" + region]
+        v = case["count"] > 0
+        assert not got[7]["has_history"].any() and np.array_equal(got[7]["behind"], v & (case["feat"][..., 6] > 0.0))
+        args, tp = P.blend_args(case)
+        args[5] = False  # the cleared-history result
+        clear = T.blend(*args, **tp)
+        assert all(np.array_equal(_bits(got[k][v]), _bits(clear[k][v])) for k in (0, 1, 6))
+    case, got = cases["dolly-whole"]
+    on_plate = (case["feat"][..., 3:6] == P.PLATE_NORMAL).all(-1)
+    assert on_plate.sum() > 50 and got[7]["behind"][on_plate].all() and got[7]["has_history"][~on_plate].any()
+    for name, shift in (("half_pixel", 0.5), ("pixel_and_a_quarter", 1.25)):
+        case, got = cases[name + "-whole"]
+        x, y, _, _ = T.reproject(case["cam"], case["prev"], P.IMAGE_W, P.IMAGE_H, 0, 0, case["feat"][..., 6])
+        v = (case["count"] > 0) & (case["feat"][..., 6] > 0.0)
+        jj, ii = np.mgrid[0:P.IMAGE_H, 0:P.IMAGE_W]
+        assert np.abs(np.abs(x - ii)[v] - shift).max() < 1e-9 and np.abs(np.abs(y - jj)[v] - shift).max() < 1e-9
+    case, got = cases["sideways-whole"]  # the plate's silhouette: taps turned down by depth, pixels left without history
+    assert got[7]["rejected"]["depth"].sum() > 20 and (got[7]["accepted"] == 4).sum() > 1000
+    case, got = cases["yaw_90-whole"]  # in front of prev, but up to 1e18 pixels outside its image: never made an index
+    x, _, _, zc = T.reproject(case["cam"], case["prev"], P.IMAGE_W, P.IMAGE_H, 0, 0, case["feat"][..., 6])
+    ahead = (case["count"] > 0) & (case["feat"][..., 6] > 0.0) & (zc > 0.0)
+    assert ahead.sum() > 1000 and np.abs(x[ahead]).max() > 2.0 ** 32 and np.abs(x[ahead]).min() > P.IMAGE_W + 1
+    assert not got[7]["has_history"].any() and (got[7]["rejected"]["border"][ahead] == 4).all()
+    case, got = cases["fov-whole"]
+    assert got[7]["has_history"].sum() > 1000 and got[7]["rejected"]["border"].sum() == 0  # prev sees more than cam
+
+
+def test_special_cases_hit_what_they_aim_at(cases):
+    case, got = cases["depths-whole"]
+    z, v, info = case["feat"][..., 6], case["count"] > 0, got[7]
+    for d in (0.0, -1.0, 1e300, 1.7976931348623157e308):
+        assert ((z == d) & v).sum() > 20, d
+    assert ((z == 0.0) & np.signbit(z) & v).any()
+    assert info["no_depth"][v & (z <= 0.0)].all() and not info["has_history"][v & (z <= 0.0)].any()
+    x, y, z_exp, zc = T.reproject(case["cam"], case["prev"], P.IMAGE_W, P.IMAGE_H, 0, 0, z)
+    tiny, huge = v & (z == 5e-324), v & (z >= 1e300)
+    assert tiny.sum() > 20 and (zc[tiny] == 0.0).all() and info["behind"][tiny].all()  # zc > 0 fails at 0 itself
+    # a huge depth keeps its direction, so its position is an ordinary one; z_exp and with it the tolerance are inf, and
+    # |inf - z_tap| <= inf holds: the header's formula accepts such taps, and so must the kernel
+    assert np.isinf(z_exp[huge]).all() and np.isfinite(x[huge]).all() and info["has_history"][huge].sum() > 100
+    case, got = cases["hand_history-whole"]
+    n = case["hist"][..., 5]
+    for k in (0.0, -2.0, 0.5, 1e9):
+        assert (n == k).sum() > 50, k
+    assert got[7]["rejected"]["empty"].sum() > 100 and ((got[7]["accepted"] > 0) & (got[7]["rejected"]["empty"] > 0)).sum() > 100
+    with np.errstate(all="ignore"):
+        alpha = case["count"] / got[6][..., 5]  # n' = n_cur / alpha
+        assert (np.abs(alpha[got[7]["has_history"]] - case["alpha_min"]) < 1e-15).any()  # the clamp, under n = 1e9
+    # alpha_min = 1: with a finite history the frame is the cleared-history frame, bit for bit
+    case, got = cases["alpha_one-whole"]
+    args, tp = P.blend_args(case)
+    assert got[7]["has_history"].sum() > 1000 and np.isfinite(case["hist"]).all()
+    args[5] = False
+    clear = T.blend(*args, **tp)
+    v = case["count"] > 0
+    assert all(np.array_equal(_bits(got[k][v]), _bits(clear[k][v])) for k in (0, 1, 6))
+    # a tiny alpha_min: no pixel is clamped
+    case, got = cases["alpha_tiny-whole"]
+    has = got[7]["has_history"]
+    assert has.sum() > 1000 and (case["count"][has] / got[6][..., 5][has] > 1e-10).all()
+    # n = 1 over n_h = 0.5: n' = 1.5 and the variance is 1e30 / la^2
+    case, got = cases["n_below_two-whole"]
+    has = got[7]["has_history"]
+    la = np.maximum(D.lum(case["feat"][..., 0:3]), 1e-3)
+    assert has.sum() > 1000 and (got[6][..., 5][has] == 1.5).all() and np.array_equal(got[1][has], (1e30 / (la * la))[has])
+
+
+@pytest.mark.parametrize("kind", ["edge_depth", "edge_normal"])
+def test_edges_of_the_tap_compares_fall_both_ways(cases, kind):
+    """a tap whose depth (normal) difference is the tolerance itself is accepted; the next double beyond is not"""
+    case, got = cases[kind + "-whole"]
+    info, marks = got[7], case["marks"]
+    assert len(marks["at"]) >= 2 and len(marks["beyond"]) >= 2
+    for y, x in marks["at"]:
+        assert info["accepted"][y, x] == 4
+    for y, x in marks["beyond"]:
+        assert info["accepted"][y, x] == 3 and info["rejected"][kind[5:]][y, x] == 1
+
+
+def test_edge_of_the_weight_compare_falls_both_ways(cases):
+    case, got = cases["edge_weight_at-whole"]
+    (y, x), = case["marks"]["at"]
+    assert got[7]["sw"][y, x] == case["min_weight"] and got[7]["has_history"][y, x] and got[7]["accepted"][y, x] == 2
+    case, got = cases["edge_weight_above-whole"]
+    (y, x), = case["marks"]["beyond"]
+    assert got[7]["sw"][y, x] == np.nextafter(case["min_weight"], 0.0) and got[7]["light"][y, x]
+    assert not got[7]["has_history"][y, x] and got[6][y, x, 5] == case["count"][y, x]
