@@ -1,9 +1,10 @@
 /*
  * rtr_hip_test.h -- entry points of librtr_hip_test.so, a SEPARATE library next to librtr_hip.so (it links against
  * it): device unit kernels that run the product's own device functions (csrc/rt_device.h) over golden-vector records
- * (include/rtr_testrec.h), one lane per record, plus counter-calibration and instruction-level checks, and a unit
- * entry that runs the temporal kernels of the denoiser over caller-given planes (rtr_test_temporal_planes).  They exist
- * so tests can compare the HIP path with the oracle below the whole-image level; none of this code is in the
+ * (include/rtr_testrec.h), one lane per record, plus counter-calibration and instruction-level checks, a unit
+ * entry that runs the temporal kernels of the denoiser over caller-given planes (rtr_test_temporal_planes), and a
+ * host-only entry that says what lowering makes of a scene and which kernel it would get (rtr_test_scene_plan).  They
+ * exist so tests can compare the HIP path with the oracle below the whole-image level; none of this code is in the
  * product library, and a renderer integration only needs rtr_hip.h.
  */
 #ifndef RTR_HIP_TEST_H
@@ -34,6 +35,29 @@ typedef struct rtr_kernel_record {
 } rtr_kernel_record;
 /* size_of_out must be sizeof(rtr_kernel_record) */
 int rtr_test_last_kernel(rtr_context* ctx, rtr_kernel_record* out, size_t size_of_out);
+
+/* What the library makes of a scene before anything reaches a device: the validator, the host-only lowering
+ * (csrc/rt_lower.h: lower_scene) and the two decisions every launch hangs on -- pick_trav and, for `integrator` and the
+ * render `flags`, mega_variant (csrc/rtr_capi.hip).  Needs no context and no GPU.  RT_TRAV_*, RT_MS_*, RT_TIE_FLAG and
+ * RT_GUARD_FLAG are those of csrc/rt_device.h. */
+typedef struct rtr_scene_plan {
+    int32_t fast_ok, has_media;                /* rtr_scene_info */
+    int32_t flat_scene, flat_guarded;          /* no box tree, no tie-capable reference; without / with guarded references */
+    int32_t lean_materials, quad_lights_only;  /* the material and light class of the kernels */
+    int32_t uv_order_dependent;                /* a moving_sphere carries a material that reads (u,v) */
+    int32_t machine_ok, guarded_program;       /* the traversal machine has a program / one it does not run */
+    int32_t top_tree, needs_uv, n_material_types;
+    int32_t shared_div, pair_cast;             /* DScene members of the same names */
+    int32_t n_steps, n_visits, n_refs;         /* step program (the default one-step program included), visits, references */
+    int32_t fast_stack_words, walk_stack_words; /* LDS stack words per lane: compiled traversals / reference-order walk */
+    int32_t n_tie_refs, n_guard_refs;          /* references that carry RT_TIE_FLAG / RT_GUARD_FLAG */
+    int32_t pick_trav;                         /* RT_TRAV_* pick_trav chooses for `flags` */
+    int32_t mega_trav, mega_ms, mega_sorted, mega_pair; /* the MegaVariant: k_mega<integrator, trav, ms, sorted, ., pair> */
+} rtr_scene_plan;
+/* ref_flags (may be NULL when cap is 0) receives the `reserved` word of the first min(cap, n_refs) reference records:
+ * visiting order | RT_TIE_FLAG | RT_GUARD_FLAG.  Returns RTR_OK or the validator's status for a scene it rejects. */
+int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t flags, rtr_scene_plan* out,
+                        int32_t* ref_flags, int64_t cap);
 
 /* Make rtr_test_hits (which takes no render params) use the reference-order traversal. */
 int rtr_test_reference_order(rtr_context* ctx, int on);

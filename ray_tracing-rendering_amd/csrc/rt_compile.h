@@ -1,6 +1,7 @@
 /*
- * rt_compile.h -- host side: lower a validated hittable graph to the compiled scene of rt_device.h
- * (instances / references / wrapper epilogue lists / SAH box trees with single-precision boxes).
+ * rt_compile.h -- host side, first half of scene compilation: a validated hittable graph to a CompiledScene
+ * (instances / references / wrapper epilogue lists / SAH box trees with single-precision boxes / the step program).
+ * rt_lower.h turns that into the arrays and facts of the device (per-reference records, tie flags, scan runs, ...).
  *   - no order-sensitive part: sub-scene 0 = the whole graph (RT_TRAV_FAST / RT_TRAV_FLAT);
  *   - constant_media under bvh_nodes / lists: the step program (FStep, RT_TRAV_PROGRAM);
  *   - anything else that is order-sensitive (a medium under a transform, a sphere with a negative
@@ -38,13 +39,6 @@ struct CompiledScene {
 };
 
 namespace rtc {
-
-/* FInst::scan_first / run[] of every linearly scanned instance; `prims` = the per-reference node records with their tie
- * flags (rtr_upload_scene).  Instances whose references do not fit RT_INST_RUNS_MAX runs, or that hold a tie-capable
- * reference (its visiting position takes part in the test), keep the generic loop. */
-inline void build_scan_runs(CompiledScene& cs, const std::vector<rtr_node>& prims);
-/* FLeaf record of every reference */
-inline std::vector<FLeaf> build_leaf_records(const CompiledScene& cs, const std::vector<rtr_node>& prims);
 
 constexpr int kLinearMax = 12; /* instances with more references get a box tree */
 constexpr int kLeafMax = 4;
@@ -882,79 +876,4 @@ inline CompiledScene compile_scene(const rtr_scene_desc* scene, bool has_media, 
         }
     }
     return cs;
-}
-
-inline void rtc::build_scan_runs(CompiledScene& cs, const std::vector<rtr_node>& prims) {
-    cs.scan.clear();
-    for (FInst& I : cs.inst) {
-        I.flags &= ~RT_INST_RUNS;
-        I.scan_first = 0;
-        I.runs = 0;
-        if (I.bvh_root >= 0 || I.n_ref == 0) continue;
-        std::vector<std::pair<int, int>> runs; /* type, count */
-        std::vector<double> data;
-        bool ok = true;
-        const int kBox = RTR_NODE_SPHERE + RT_RUN_BOX;
-        auto same = [](double a, double b) { return std::memcmp(&a, &b, 8) == 0; };
-        /* the six references from r on are the sides of one box, in box.h's order and with its extents */
-        auto box_at = [&](int r) {
-            if (r + 6 > I.ref_first + I.n_ref) return false;
-            const rtr_node* p = &prims[r];
-            static const int want_type[6] = {RTR_NODE_XY_RECT, RTR_NODE_XY_RECT, RTR_NODE_XZ_RECT,
-                                             RTR_NODE_XZ_RECT, RTR_NODE_YZ_RECT, RTR_NODE_YZ_RECT};
-            for (int k = 0; k < 6; ++k)
-                if (p[k].type != want_type[k] || (p[k].reserved & RT_TIE_FLAG)) return false;
-            const double x0 = p[0].f[0], x1 = p[0].f[1], y0 = p[0].f[2], y1 = p[0].f[3], z1 = p[0].f[4], z0 = p[1].f[4];
-            const double want[6][5] = {{x0, x1, y0, y1, z1}, {x0, x1, y0, y1, z0}, {x0, x1, z0, z1, y1},
-                                       {x0, x1, z0, z1, y0}, {y0, y1, z0, z1, x1}, {y0, y1, z0, z1, x0}};
-            for (int k = 0; k < 6; ++k)
-                for (int c = 0; c < 5; ++c)
-                    if (!same(p[k].f[c], want[k][c])) return false;
-            return true;
-        };
-        for (int r = I.ref_first; r < I.ref_first + I.n_ref && ok;) {
-            const rtr_node& n = prims[r];
-            if (n.reserved & RT_TIE_FLAG) ok = false;
-            const bool box = box_at(r);
-            /* (a guarded run is read by the kernels of guarded scenes only -- RT_TRAV_FLAT_GUARD --, the others that meet
-             * such an instance scan it through the generic loop) */
-            const bool guarded = (n.reserved & RT_GUARD_FLAG) != 0;
-            const int type = box ? kBox : (guarded ? RTR_NODE_SPHERE + RT_RUN_GUARDED : n.type);
-            if (runs.empty() || runs.back().first != type || runs.back().second == RT_RUN_COUNT_MAX) runs.push_back({type, 0});
-            ++runs.back().second;
-            if (guarded) { /* centre, radius, first guard and guard count (as the integers' bits): six words */
-                data.insert(data.end(), n.f, n.f + 6);
-                r += 1;
-            } else if (box) {
-                const double rec[6] = {n.f[0], n.f[1], n.f[2], n.f[3], prims[r + 1].f[4], n.f[4]}; /* x0 x1 y0 y1 z0 z1 */
-                data.insert(data.end(), rec, rec + 6);
-                r += 6;
-            } else {
-                const int nf = n.type == RTR_NODE_SPHERE ? 4 : (n.type == RTR_NODE_MOVING_SPHERE ? 9 : 5);
-                data.insert(data.end(), n.f, n.f + nf);
-                r += 1;
-            }
-        }
-        if (!ok || (int)runs.size() > RT_INST_RUNS_MAX) continue;
-        I.scan_first = (int32_t)cs.scan.size();
-        for (size_t k = 0; k < runs.size(); ++k)
-            I.runs |= (uint64_t)((runs[k].first - RTR_NODE_SPHERE) << RT_RUN_COUNT_BITS | runs[k].second) << (RT_RUN_BITS * k);
-        cs.scan.insert(cs.scan.end(), data.begin(), data.end());
-        for (size_t k = 0; k < 6; ++k) I.head[k] = k < data.size() ? data[k] : 0.0;
-        I.flags |= RT_INST_RUNS;
-    }
-    cs.scan.resize(cs.scan.size() + 16, 0.0); /* the two-records-per-trip loads never leave the array */
-}
-
-inline std::vector<FLeaf> rtc::build_leaf_records(const CompiledScene& cs, const std::vector<rtr_node>& prims) {
-    std::vector<FLeaf> out(prims.size());
-    for (size_t r = 0; r < prims.size(); ++r) {
-        FLeaf L{};
-        const rtr_node& n = prims[r];
-        const int nf = n.type == RTR_NODE_SPHERE ? 4 : (n.type == RTR_NODE_MOVING_SPHERE ? 0 : 5);
-        for (int k = 0; k < nf; ++k) L.f[k] = n.f[k];
-        L.type = n.type, L.tag = n.reserved;
-        out[r] = L;
-    }
-    return out;
 }

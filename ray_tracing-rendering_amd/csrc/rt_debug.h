@@ -1,7 +1,8 @@
 /*
  * rt_debug.h -- the seam between librtr_hip.so and librtr_hip_test.so (NOT part of include/: a renderer integration
  * never sees it).  The test library runs its own unit kernels over the device functions of rt_device.h; what it needs
- * from a context is where the uploaded scene lives and which stream and traversal a call would use.
+ * from a context is where the uploaded scene lives and which stream and traversal a call would use.  One entry needs no
+ * context: rtr_debug_scene_plan, the host-only answer to "which kernel will this scene get, and why".
  */
 #pragma once
 
@@ -32,7 +33,19 @@ struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     uint32_t rng_exit;
     int32_t n_closest, n_shadow, pad;
 };
+/* what lowering (rt_lower.h) and the variant decisions of rtr_capi.hip make of a scene, without a device; the layout of
+ * rtr_scene_plan (include/rtr_hip_test.h), which documents the members */
+struct rtr_debug_plan {
+    int32_t fast_ok, has_media, flat_scene, flat_guarded, lean_materials, quad_lights_only, uv_order_dependent, machine_ok;
+    int32_t guarded_program, top_tree, needs_uv, n_material_types, shared_div, pair_cast;
+    int32_t n_steps, n_visits, n_refs, fast_stack_words, walk_stack_words, n_tie_refs, n_guard_refs;
+    int32_t pick_trav, mega_trav, mega_ms, mega_sorted, mega_pair;
+};
 extern "C" {
+/* validator + lower_scene + pick_trav + mega_variant for `integrator` and render `flags`; ref_flags[0 .. min(cap, n_refs))
+ * receives rtr_node::reserved of every reference record.  Returns the validator's status. */
+int rtr_debug_scene_plan(const rtr_scene_desc* scene, int integrator, int flags, rtr_debug_plan* out, size_t size_of_out,
+                         int32_t* ref_flags, int64_t cap);
 int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t size_of_view);
 int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);

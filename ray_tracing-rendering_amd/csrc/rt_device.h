@@ -929,7 +929,7 @@ RT_DEV bool fast_prim_hit(const rtr_node& n, V3 o, V3 d, const RayDiv& q, Real t
  * pay for the comparison: a tie is accepted only from a primitive visited later than the current
  * holder.  Across instances the scan order is the visiting order of each instance's first primitive and
  * `t == t_max` is accepted, so the later instance wins like the reference's later visit; coplanar rects
- * whose instance order contradicts their visiting order are flagged as well (rtr_upload_scene), their
+ * whose instance order contradicts their visiting order are flagged as well (rt_lower.h: flag_ties_across_instances), their
  * positions are comparable because `order` lives across the instance loop.  Not reproduced: coplanar
  * rotated faces of two different transform chains, and ties where the reference's own choice hangs on
  * 1-ulp noise of an UNPADDED box test (faces of `box` objects that touch: the later one is only
@@ -957,7 +957,7 @@ RT_DEV bool fast_ref_hit(const DScene& sc, int ref, V3 o, V3 d, const RayDiv& q,
                          int& order) {
     const rtr_node n = ld_const(sc.fprim, ref);
     const int tag = n.reserved;
-    /* (guarded references exist only in scenes that take the kernels with TIES or GUARD: rtr_upload_scene) */
+    /* (guarded references exist only in scenes that take the kernels with TIES or GUARD: rt_lower.h) */
     if (GUARD && (tag & RT_GUARD_FLAG) &&
         !guard_pass(sc, (int)__double_as_longlong(n.f[4]), (int)__double_as_longlong(n.f[5]), o, d, tmin, tmax))
         return false;
@@ -1293,7 +1293,7 @@ __device__ __forceinline__ bool scan_instance(const DScene& sc, const FInst& I, 
  * has reached a leaf handles ITS leaf -- references of the untransformed instance in the world frame, or one transformed
  * instance: its record through vector loads, the ray into its frame, its references (or its own box tree, nested on
  * the same stack).  Visiting order is whatever the tree gives; exact ties in t are decided by the visiting positions
- * of the tagged references like everywhere else (RT_TIE_FLAG; rtr_upload_scene tags every pair of coplanar rects of
+ * of the tagged references like everywhere else (RT_TIE_FLAG; rt_lower.h tags every pair of coplanar rects of
  * two instances of such a sub-scene, whatever their order). */
 template <bool ANY>
 __device__ __forceinline__ bool trace_top(const DScene& sc, const FSub sub, V3 o, V3 d, Real time, Real tmin, Real& tmax,
@@ -2528,7 +2528,7 @@ RT_DEV Real env_pdf(const EnvMap& m, V3 direction) { /* :291-331 */
     return map_pdf * m.w * m.h / (2.0 * RT_PI * RT_PI * sin_theta);
 }
 
-/* only MS == RT_MS_FULL kernels know lights other than QuadLights (rtr_upload_scene decides) */
+/* only MS == RT_MS_FULL kernels know lights other than QuadLights (mega_variant decides) */
 template <int MS = RT_MS_FULL>
 RT_DEV LightSample light_sample(const rtr_light& l, V3 p, Real ux, Real uy, uint32_t& rng, const uint8_t* blob) {
     LightSample s;

@@ -1,11 +1,11 @@
 /*
  * rt_launch.h -- host-side seams between the translation units of librtr_hip.so.  The kernels are
- * compiled in parallel: rtr_capi.hip (C ABI, scene upload, per-ray kernels, k_resolve), rtr_mega.hip
+ * compiled in parallel: rtr_capi.hip (C ABI, scene lowering and upload, per-ray kernels, k_resolve), rtr_mega.hip
  * three times (one integrator group each: RTR_MEGA_GROUP 0 = MIS, 1 = RR + path, 2 = PBR + NEE) and
  * rtr_wavefront.hip (stage kernels + their host driver).
  *
- * Which k_mega instantiation a render runs is decided once, by mega_variant() in rtr_capi.hip; the
- * MegaVariant travels in MegaLaunch to the group's unit, which looks it up in its explicit list of
+ * Which k_mega instantiation a render runs is decided once, by mega_variant() in rtr_capi.hip from the
+ * SceneFacts of rt_lower.h (which only that unit includes); the MegaVariant travels in MegaLaunch to the group's unit, which looks it up in its explicit list of
  * instantiations.  kernel_lds() is the one LDS-limit check of every launcher, and dispatch_trav() the
  * one place a runtime RT_TRAV_* becomes a template argument of the per-ray kernels.
  */
@@ -29,15 +29,6 @@ struct LaunchedKernel {
 struct MegaVariant {
     int integ, trav, ms; /* RTR_INTEGRATOR_*, RT_TRAV_* template value, RT_MS_* */
     bool sorted, pair;   /* the sorted instantiation (RTR_FLAG_SORTED_SHADING) / the pair-cast twin of a flat MIS kernel */
-};
-/* what mega_variant() needs to know about the uploaded scene (rtr_upload_scene) */
-struct MegaFacts {
-    bool top_tree;        /* sub-scene 0 has a top tree: the per-lane instance walk (FSub) */
-    bool flat_guarded;    /* a flat scene with guarded references (hollow spheres) */
-    bool guarded_program; /* the program holds guarded steps or media under wrappers (RT_TRAV_PROGRAM_EXT kernels) */
-    bool lean, quad_only, needs_uv; /* material / light set */
-    bool pair_cast;       /* DScene::pair_cast */
-    int n_materials;
 };
 
 /* one megakernel launch */

@@ -31,7 +31,7 @@
 
 #include "rt_device.h"
 
-/* One instance visit of the ray-cast program, in execution order (built by rtr_upload_scene from
+/* One instance visit of the ray-cast program, in execution order (built by rt_lower.h: build_visits from
  * FStep / FSub / FInst).  A medium step is walked twice (constant_medium.h:62-66): pass 1 restarts at
  * `step_first`. */
 struct FVisit {

@@ -1,10 +1,11 @@
 /*
  * rtr_capi.hip -- implementation of the C ABI (include/rtr_hip.h) on top of the HIP
- * kernels of rt_kernels.h.  Host side only: scene validation and upload, launch geometry,
- * workspace, cancel, statistics.  Built by hipcc for gfx950 into librtr_hip.so.
+ * kernels of rt_kernels.h.  Host side only: scene validation, the copy of the lowered scene
+ * (rt_lower.h: lower_scene) to the device, the kernel-variant decisions (pick_trav, mega_variant),
+ * launch geometry, workspace, cancel, statistics.  Built by hipcc for gfx950 into librtr_hip.so.
  */
 #define RTR_TU_CAPI
-#include "rt_compile.h"
+#include "rt_lower.h"
 #include "rt_kernels.h"
 #include "rt_launch.h"
 #include "rt_machine.h"
@@ -27,6 +28,15 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
 };
+/* the device arrays of the uploaded scene, one per pointer of DScene, and the DScene itself.  DevBufs only: rtr_destroy
+ * frees them as an array, so a new one needs its declaration here and its line in rtr_upload_scene, nothing else */
+struct SceneBufs {
+    DevBuf nodes, kids, mats, tex, perlin, images, imgbytes, lights;
+    DevBuf finst, fxf, fref, fexit, fbvh, fsub, fscan, fguard, fstep, fvisit, fprim, fleaf, fmat, dscene;
+    DevBuf* begin() { return &nodes; }
+    DevBuf* end() { return begin() + sizeof(SceneBufs) / sizeof(DevBuf); }
+};
+static_assert(sizeof(SceneBufs) == 22 * sizeof(DevBuf), "SceneBufs holds DevBufs only");
 
 } // namespace
 
@@ -40,17 +50,8 @@ struct rtr_context {
     bool has_scene = false;
     rtr_scene_info info{};
     DScene ds{};
-    DevBuf b_nodes, b_kids, b_mats, b_tex, b_perlin, b_images, b_imgbytes, b_lights;
-    DevBuf b_finst, b_fxf, b_fref, b_fexit, b_fbvh, b_dscene, b_fprim, b_fsub, b_fstep, b_fvisit, b_fscan, b_fleaf, b_fmat, b_fguard;
-    int fast_stack_words = 1;
-    int walk_extra_words = 0; /* stack of a compiled subtree's box tree on top of the walk's own */
-    bool lean_materials = false; /* only lambertian / diffuse_light with solid_color textures, only QuadLights */
-    bool quad_lights_only = false;
-    bool flat_scene = false; /* compiled scene without box trees and without tie-capable references */
-    /* a moving_sphere (its hit() writes no u,v: the record keeps those of an earlier, farther hit of the
-     * reference's walk) carries a material that reads (u,v): only the reference-order walk reproduces that */
-    bool uv_order_dependent = false;
-    int n_material_types = 0;
+    SceneFacts facts; /* what lower_scene found out about it */
+    SceneBufs sb;
     /* per-render workspace */
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
@@ -74,19 +75,13 @@ struct rtr_context {
     std::atomic<uint32_t> cancelled_upto{0};
     uint32_t pending_id = 0; /* id of the render whose statistics are pending */
     std::mutex cancel_mu;
-    int n_materials = 0;
     int n_cus = 256; /* hipDeviceProp.multiProcessorCount */
-    bool flat_guarded = false; /* a flat scene but for guarded references: RT_TRAV_FAST everywhere, RT_TRAV_FLAT_GUARD in the megakernel */
-    bool machine_ok = false; /* the compiled scene fits the position word of the traversal machine (rt_machine.h) */
-    bool guarded_program = false; /* the step program holds guarded primitives (FStep kind 3) or media under wrappers: not a program of the machine */
     uint64_t scene_gen = 0; /* rtr_upload_scene calls that reached the device: an accumulator belongs to one scene */
     std::vector<rtr_accum*> accums; /* live accumulators (rtr_destroy frees what is left) */
-    /* rtr_set_camera: ds.camera is the current camera; the DScene on the device (b_dscene: the megakernel and the
+    /* rtr_set_camera: ds.camera is the current camera; the DScene on the device (sb.dscene: the megakernel and the
      * wavefront stages read it through a pointer) takes it, in stream order, when the next render is issued */
     uint64_t camera_gen = 0;   /* rtr_set_camera calls that succeeded: an accumulator's samples belong to one camera */
-    bool camera_dirty = false; /* b_dscene still holds an older camera */
-    double t_lo = 0, t_hi = 0; /* the ray times the scene was compiled for (rt_compile.h: t_lo, t_hi) */
-    bool camera_times_small = true; /* the uploaded camera passed the 2^60 test of DScene::shared_div */
+    bool camera_dirty = false; /* sb.dscene still holds an older camera */
     std::vector<rtr_history*> histories; /* live histories (rtr_destroy frees what is left) */
 };
 
@@ -158,6 +153,17 @@ int upload(rtr_context* c, DevBuf& b, const void* src, size_t bytes) {
     if (rc) return rc;
     if (bytes) HIPCHK(c, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
     return RTR_OK;
+}
+/* rtr_upload_scene: one array to the device and its address into the DScene member that names it */
+template <typename T>
+int put(rtr_context* c, DevBuf& b, const T* src, size_t n, const T*& member) {
+    const int rc = upload(c, b, src, sizeof(T) * n);
+    member = static_cast<const T*>(b.p);
+    return rc;
+}
+template <typename T>
+int put(rtr_context* c, DevBuf& b, const std::vector<T>& src, const T*& member) {
+    return put(c, b, src.data(), src.size(), member);
 }
 
 /* rtr_display_srgb_thresholds: S[b] = the inverse sRGB transfer of b / 255.0, computed once on the host.  This table, not
@@ -456,26 +462,25 @@ std::vector<int> owned_tiles(const rtr_render_params& p, int& tiles_x, int& tile
 
 /* which traversal a call uses: the compiled scene unless it does not exist or the caller asks
  * for the reference's visiting order */
-int pick_trav(const rtr_context* c, int flags) {
-    if (c->info.has_media || (c->info.inverted_boxes && !c->info.fast_ok)) /* (hollow spheres as guarded references: compiled) */
-        return c->info.program_steps > 0 && !(flags & RTR_FLAG_REFERENCE_ORDER) ? RT_TRAV_PROGRAM
-                                                                                                     : RT_TRAV_MEDIA;
-    if (!c->info.fast_ok || c->uv_order_dependent || (flags & RTR_FLAG_REFERENCE_ORDER))
+int pick_trav(const SceneFacts& f, const rtr_scene_info& info, int flags) {
+    if (info.has_media || (info.inverted_boxes && !info.fast_ok)) /* (hollow spheres as guarded references: compiled) */
+        return info.program_steps > 0 && !(flags & RTR_FLAG_REFERENCE_ORDER) ? RT_TRAV_PROGRAM : RT_TRAV_MEDIA;
+    if (!info.fast_ok || f.uv_order_dependent || (flags & RTR_FLAG_REFERENCE_ORDER))
         return RT_TRAV_EXACT;
-    return c->flat_scene ? RT_TRAV_FLAT : RT_TRAV_FAST;
+    return f.flat_scene ? RT_TRAV_FLAT : RT_TRAV_FAST;
 }
-size_t stack_bytes(const rtr_context* c, int trav) {
+size_t stack_bytes(const SceneFacts& f, const rtr_scene_info& info, int trav) {
     const bool compiled = trav == RT_TRAV_FAST || trav == RT_TRAV_FLAT || rt_is_program(trav) || trav == RT_TRAV_TOP || trav == RT_TRAV_FLAT_GUARD;
-    const int words = compiled ? c->fast_stack_words : c->info.stack_words + c->walk_extra_words;
+    const int words = compiled ? f.fast_stack_words : info.stack_words + f.walk_extra_words;
     return (size_t)words * RTR_BLOCK * sizeof(int);
 }
 /* The RT_TRAV_* template value a per-ray kernel (k_li, k_features, k_query_*, the unit kernels of the test library)
  * takes for a call with `flags`: flat scenes take RT_TRAV_FAST (same hits, one kernel for both), a program the general
  * program kernel, and with `top` a sub-scene 0 with a top tree RT_TRAV_TOP, like the megakernel. */
-int per_ray_trav(const rtr_context* c, int flags, bool top) {
-    int trav = pick_trav(c, flags);
+int per_ray_trav(const SceneFacts& f, const rtr_scene_info& info, int flags, bool top) {
+    int trav = pick_trav(f, info, flags);
     if (trav == RT_TRAV_FLAT) trav = RT_TRAV_FAST;
-    if (top && trav == RT_TRAV_FAST && c->ds.top_root0 >= 0) trav = RT_TRAV_TOP;
+    if (top && trav == RT_TRAV_FAST && f.top_tree) trav = RT_TRAV_TOP;
     return trav == RT_TRAV_PROGRAM ? RT_TRAV_PROGRAM_EXT : trav;
 }
 /* the traversals k_li and k_features are instantiated for; the queries and the unit kernels also walk a top tree */
@@ -490,10 +495,10 @@ int set_lds(rtr_context* c, K kernel, size_t bytes) {
     return kernel_lds(kernel, bytes, 0, c->err);
 }
 
-/* THE place that decides which k_mega instantiation a render runs: from what the upload found out about the scene,
+/* THE place that decides which k_mega instantiation a render runs: from what lower_scene found out about the scene,
  * the integrator, the traversal pick_trav() chose and the render flags.  `flags_in_effect` (may be null) receives the
  * flags that changed the choice. */
-MegaVariant mega_variant(const MegaFacts& f, int integ, int trav, int flags, int* flags_in_effect) {
+MegaVariant mega_variant(const SceneFacts& f, int integ, int trav, int flags, int* flags_in_effect) {
     MegaVariant v{integ, trav, RT_MS_FULL, false, false};
     /* MIS and RR have flat, lean and guarded kernels; the others the generic material set on the
      * general compiled-scene kernel, one program kernel -- the general one --, and the media kernel, which also serves
@@ -508,9 +513,9 @@ MegaVariant mega_variant(const MegaFacts& f, int integ, int trav, int flags, int
         return v;
     }
     const int t = v.trav;
-    const bool lean = f.lean && (t == RT_TRAV_FLAT || t == RT_TRAV_FAST || t == RT_TRAV_TOP || t == RT_TRAV_EXACT);
+    const bool lean = f.lean_materials && (t == RT_TRAV_FLAT || t == RT_TRAV_FAST || t == RT_TRAV_TOP || t == RT_TRAV_EXACT);
     /* "every material, QuadLights only": a kernel of the MIS integrator (RR has no light code) on the compiled scene */
-    const bool quadlit = f.quad_only && !f.needs_uv && integ == RTR_INTEGRATOR_MIS && t != RT_TRAV_MEDIA && t != RT_TRAV_EXACT;
+    const bool quadlit = f.quad_lights_only && !f.needs_uv && integ == RTR_INTEGRATOR_MIS && t != RT_TRAV_MEDIA && t != RT_TRAV_EXACT;
     v.ms = lean ? RT_MS_LEAN : (quadlit ? RT_MS_QUADLIT : RT_MS_FULL);
     /* (the sorted variant packs the material index into 16 bits) */
     v.sorted = (flags & RTR_FLAG_SORTED_SHADING) && f.n_materials <= 65535 && mega_sortable(integ, t, v.ms);
@@ -524,18 +529,14 @@ MegaVariant mega_variant(const MegaFacts& f, int integ, int trav, int flags, int
 /* `dry`: only what can fail without touching the stream (the LDS size check / attribute, the occupancy query) */
 int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, bool dry, int* blocks_per_cu, int flags,
                 int* flags_in_effect = nullptr, LaunchedKernel* launched = nullptr) {
-    MegaFacts facts{};
-    facts.top_tree = c->ds.top_root0 >= 0, facts.flat_guarded = c->flat_guarded, facts.guarded_program = c->guarded_program;
-    facts.lean = c->lean_materials, facts.quad_only = c->quad_lights_only, facts.needs_uv = c->info.needs_uv != 0;
-    facts.pair_cast = c->ds.pair_cast != 0, facts.n_materials = c->n_materials;
     MegaLaunch L{};
-    const MegaVariant& v = L.variant = mega_variant(facts, integrator, trav_in, flags, flags_in_effect);
-    L.stack_words = (int)(stack_bytes(c, v.trav) / (RTR_BLOCK * sizeof(int)));
-    L.dsc = static_cast<const DScene*>(c->b_dscene.p);
+    const MegaVariant& v = L.variant = mega_variant(c->facts, integrator, trav_in, flags, flags_in_effect);
+    L.stack_words = (int)(stack_bytes(c->facts, c->info, v.trav) / (RTR_BLOCK * sizeof(int)));
+    L.dsc = static_cast<const DScene*>(c->sb.dscene.p);
     /* (the reference-order walk of PBR / NEE runs the media kernel with the parked words of the traversal that was
      * asked for, as it always has: workgroups per CU decide the chunking of a render, and that its rounding) */
     const int park = v.sorted ? SK_WORDS : park_words(integrator, trav_in == RT_TRAV_EXACT ? RT_TRAV_EXACT : v.trav);
-    L.lds = stack_bytes(c, v.trav) + (size_t)park * RTR_BLOCK * sizeof(double);
+    L.lds = stack_bytes(c->facts, c->info, v.trav) + (size_t)park * RTR_BLOCK * sizeof(double);
     L.accum = P.tile_s0 == nullptr ? 0 : (P.q_in ? 2 : 1);
     L.stream = c->stream;
     L.P = P;
@@ -772,17 +773,7 @@ int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* 
     if (msg && msg_cap) {
         std::snprintf(msg, msg_cap, "%s", v.msg.c_str());
     }
-    if (rc == RTR_OK && info) {
-        CompiledScene cs = compile_scene(scene, info->has_media != 0 || info->inverted_boxes != 0, info->has_media == 0 && info->inverted_boxes != 0);
-        info->fast_ok = cs.ok;
-        info->fast_instances = (int32_t)cs.inst.size();
-        info->fast_refs = (int32_t)cs.ref.size();
-        info->fast_stack_words = cs.stack_words;
-        info->compiled_subtrees = cs.n_compiled_subtrees;
-        info->program_steps = (int32_t)cs.steps.size();
-        info->top_trees = 0;
-        for (const FSub& sub : cs.subs) info->top_trees += sub.top_root >= 0;
-    }
+    if (rc == RTR_OK && info) rtc::compile_validated(scene, *info);
     return rc;
 }
 
@@ -841,9 +832,10 @@ void rtr_destroy(rtr_context* c) {
     c->accums.clear();
     for (rtr_history* h : c->histories) free_history(h);
     c->histories.clear();
-    DevBuf* bufs[] = {&c->b_nodes, &c->b_kids,  &c->b_mats,    &c->b_tex,   &c->b_perlin, &c->b_images, &c->b_imgbytes,
-                      &c->b_lights, &c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise, &c->b_query, &c->b_display, &c->b_display_io,
-                      &c->b_finst, &c->b_fxf, &c->b_fref, &c->b_fexit, &c->b_fbvh, &c->b_dscene, &c->b_fprim, &c->b_fsub, &c->b_fstep, &c->b_fvisit, &c->b_fscan, &c->b_fleaf, &c->b_fmat, &c->b_fguard};
+    for (DevBuf& b : c->sb)
+        if (b.p) hipFree(b.p);
+    DevBuf* bufs[] = {&c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise,
+                      &c->b_query, &c->b_display, &c->b_display_io};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     c->pool.release();
@@ -874,326 +866,35 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->has_scene = false;
     ++c->scene_gen;
-    CompiledScene cs = compile_scene(s, info.has_media != 0 || info.inverted_boxes != 0, info.has_media == 0 && info.inverted_boxes != 0);
-    if ((rc = upload(c, c->b_nodes, cs.dev_nodes.data(), sizeof(rtr_node) * cs.dev_nodes.size()))) return rc;
-    if ((rc = upload(c, c->b_kids, s->list_children, sizeof(int32_t) * s->n_list_children))) return rc;
-    if ((rc = upload(c, c->b_mats, s->materials, sizeof(rtr_material) * s->n_materials))) return rc;
-    if ((rc = upload(c, c->b_tex, s->textures, sizeof(rtr_texture) * s->n_textures))) return rc;
-    if ((rc = upload(c, c->b_perlin, s->perlin, sizeof(rtr_perlin) * s->n_perlin))) return rc;
-    if ((rc = upload(c, c->b_images, s->images, sizeof(rtr_image) * s->n_images))) return rc;
-    if ((rc = upload(c, c->b_imgbytes, s->image_bytes, s->n_image_bytes))) return rc;
-    if ((rc = upload(c, c->b_lights, s->lights, sizeof(rtr_light) * s->n_lights))) return rc;
-    info.fast_ok = cs.ok;
-    info.fast_instances = (int32_t)cs.inst.size();
-    info.fast_refs = (int32_t)cs.ref.size();
-    info.fast_stack_words = cs.stack_words;
-    info.compiled_subtrees = cs.n_compiled_subtrees;
-    if ((rc = upload(c, c->b_fxf, cs.xf.data(), sizeof(FXf) * cs.xf.size()))) return rc;
-    if ((rc = upload(c, c->b_fref, cs.ref.data(), sizeof(FRef) * cs.ref.size()))) return rc;
-    if ((rc = upload(c, c->b_fexit, cs.exits.data(), sizeof(int32_t) * cs.exits.size()))) return rc;
-    if ((rc = upload(c, c->b_fbvh, cs.bvh.data(), sizeof(FBvh) * cs.bvh.size()))) return rc;
-    if ((rc = upload(c, c->b_fsub, cs.subs.data(), sizeof(FSub) * cs.subs.size()))) return rc;
-    info.program_steps = (int32_t)cs.steps.size();
-    info.top_trees = 0;
-    for (const FSub& sub : cs.subs) info.top_trees += sub.top_root >= 0;
-    /* the traversal machine of the wavefront stages always runs a step program: a scene without media is
-     * the one-step program "sub-scene 0" */
-    std::vector<FStep> dev_steps = cs.steps;
-    if (cs.ok && dev_steps.empty()) {
-        FStep whole{};
-        whole.kind = 0, whole.sub = 0;
-        dev_steps.push_back(whole);
-    }
-    if ((rc = upload(c, c->b_fstep, dev_steps.data(), sizeof(FStep) * dev_steps.size()))) return rc;
-    if ((rc = upload(c, c->b_fguard, cs.guards.data(), sizeof(FGuard) * cs.guards.size()))) return rc;
-    /* ... flattened into instance visits in execution order */
-    std::vector<FVisit> visits;
-    for (size_t k = 0; k < dev_steps.size(); ++k) {
-        const FStep& st = dev_steps[k];
-        const FSub& sub = cs.subs[st.sub];
-        const int first = (int)visits.size();
-        for (int q = 0; q < sub.n_inst; ++q) {
-            const FInst& I = cs.inst[sub.inst_first + q];
-            FVisit v{};
-            v.flags = (q == 0 ? FV_FIRST : 0) | (q == sub.n_inst - 1 ? FV_LAST : 0) | (st.kind != 0 ? FV_MEDIUM : 0) |
-                      (sub.n_inst > RT_FAST_NO_BOX_MAX ? FV_BOXES : 0) | ((int)k >= cs.step_tail ? FV_TAIL : 0);
-            v.step = (int32_t)k, v.inst = sub.inst_first + q, v.step_first = first;
-            v.xf_first = I.xf_first, v.n_xf = I.n_xf, v.ref_first = I.ref_first, v.n_ref = I.n_ref;
-            v.bvh_root = I.bvh_root, v.bound = I.bound;
-            v.neg_inv_density = st.neg_inv_density;
-            visits.push_back(v);
-        }
-    }
-    if ((rc = upload(c, c->b_fvisit, visits.data(), sizeof(FVisit) * visits.size()))) return rc;
-    c->machine_ok = !visits.empty();
-    c->guarded_program = false;
-    for (const FStep& st : dev_steps) c->guarded_program |= st.kind == 3 || st.n_xf > 0 || st.n_exit > 0;
-    bool any_tie = false;
-    {
-        std::vector<rtr_node> prims(cs.ref.size());
-        for (size_t k = 0; k < cs.ref.size(); ++k) {
-            prims[k] = s->nodes[cs.ref[k].node]; /* original records */
-            prims[k].reserved = cs.ref[k].pad;      /* visiting order of the reference's walk */
-            /* the wrappers above the reference as a code in f[9] (see RT_EXIT_LONG) */
-            unsigned long long code = 0;
-            bool fits = prims[k].type != RTR_NODE_MOVING_SPHERE && cs.ref[k].n_exit <= 31;
-            for (int e = 0; e < cs.ref[k].n_exit && fits; ++e) {
-                const int wt = s->nodes[cs.exits[cs.ref[k].exit_first + e]].type;
-                code |= (unsigned long long)(wt == RTR_NODE_FLIP_FACE ? 2 : 1) << (2 * e);
-            }
-            if (!fits) code = RT_EXIT_LONG;
-            if (prims[k].type != RTR_NODE_MOVING_SPHERE) std::memcpy(&prims[k].f[9], &code, 8);
-            const auto guard = cs.guard_of_ref.find((int)k);
-            if (guard != cs.guard_of_ref.end()) { /* RT_GUARD_FLAG: first guard and count in a sphere's free words */
-                const long long first = guard->second.first, count = guard->second.second;
-                std::memcpy(&prims[k].f[4], &first, 8), std::memcpy(&prims[k].f[5], &count, 8);
-                prims[k].reserved |= RT_GUARD_FLAG;
-            }
-        }
-        /* references that can tie exactly in t with another one of their instance (see RT_TIE_FLAG) */
-        for (const FInst& I : cs.inst) {
-            std::map<std::vector<uint64_t>, std::vector<int>> groups; /* same plane / same sphere */
-            auto bits = [](double v) {
-                uint64_t u;
-                std::memcpy(&u, &v, 8);
-                return u;
-            };
-            for (int r = I.ref_first; r < I.ref_first + I.n_ref; ++r) {
-                const rtr_node& n = prims[r];
-                if (n.type >= RTR_NODE_XY_RECT)
-                    groups[{(uint64_t)n.type, bits(n.f[4])}].push_back(r);
-                else if (n.type == RTR_NODE_SPHERE)
-                    groups[{(uint64_t)n.type, bits(n.f[0]), bits(n.f[1]), bits(n.f[2]), bits(std::fabs(n.f[3]))}].push_back(r);
-            }
-            for (const auto& g : groups) {
-                const std::vector<int>& v = g.second;
-                if (v.size() > 512) { /* a huge coplanar set (tiled floor): flag all rather than test every pair */
-                    for (int r : v) prims[r].reserved |= RT_TIE_FLAG;
-                    any_tie = true;
-                    continue;
-                }
-                for (size_t x = 0; x < v.size(); ++x)
-                    for (size_t y = x + 1; y < v.size(); ++y) {
-                        rtr_node &p = prims[v[x]], &q = prims[v[y]];
-                        const bool overlap = p.type == RTR_NODE_SPHERE ||
-                                             (std::max(p.f[0], q.f[0]) <= std::min(p.f[1], q.f[1]) &&
-                                              std::max(p.f[2], q.f[2]) <= std::min(p.f[3], q.f[3]));
-                        if (overlap) p.reserved |= RT_TIE_FLAG, q.reserved |= RT_TIE_FLAG, any_tie = true;
-                    }
-            }
-        }
-        /* Ties ACROSS instances of a sub-scene.  Instances are scanned in the order their first primitive is
-         * visited and every test accepts t == t_max, so of two instances the later one wins a tie -- which is the
-         * reference's choice (it keeps what it visits later) unless the EARLIER instance holds the later-visited
-         * primitive (all primitives under the same transform chain share an instance: [wall, box, floor] puts the
-         * floor into the first instance, in front of the box whose bottom face lies in its plane).  Exactly those
-         * pairs -- rects whose planes coincide in world space, visiting order against instance order -- get the
-         * tie flag; their visiting positions then decide.  A y-plane keeps its orientation under every chain
-         * (translate, rotate_y), x- and z-planes under translations only; rotated side faces of different
-         * chains are not looked at. */
-        for (const FSub& sub : cs.subs) {
-            struct PlaneRef {
-                double k;
-                int axis, inst, ref, visit;
-            };
-            std::vector<PlaneRef> planes;
-            for (int ii = sub.inst_first; ii < sub.inst_first + sub.n_inst; ++ii) {
-                const FInst& I = cs.inst[ii];
-                double off[3] = {0, 0, 0};
-                bool rotated = false;
-                for (int k = 0; k < I.n_xf; ++k) {
-                    const FXf& x = cs.xf[I.xf_first + k];
-                    if (x.type == RTR_NODE_TRANSLATE)
-                        off[0] += x.f[0], off[1] += x.f[1], off[2] += x.f[2];
-                    else
-                        rotated = true;
-                }
-                for (int r = I.ref_first; r < I.ref_first + I.n_ref; ++r) {
-                    const rtr_node& n = prims[r];
-                    if (n.type < RTR_NODE_XY_RECT) continue;
-                    const int axis = n.type == RTR_NODE_XY_RECT ? 2 : (n.type == RTR_NODE_XZ_RECT ? 1 : 0);
-                    if (rotated && axis != 1) continue;
-                    planes.push_back({n.f[4] + off[axis], axis, ii, r, n.reserved & ~RT_TIE_FLAG});
-                }
-            }
-            std::sort(planes.begin(), planes.end(), [](const PlaneRef& a, const PlaneRef& b) {
-                return a.axis != b.axis ? a.axis < b.axis : a.k < b.k;
-            });
-            for (size_t lo = 0; lo < planes.size();) { /* clusters of (nearly) the same world plane */
-                size_t hi = lo + 1;
-                while (hi < planes.size() && planes[hi].axis == planes[lo].axis &&
-                       planes[hi].k - planes[hi - 1].k <= 1e-9 * std::max(1.0, std::fabs(planes[hi].k)))
-                    ++hi;
-                if (hi - lo > 1) {
-                    std::vector<PlaneRef> cl(planes.begin() + lo, planes.begin() + hi);
-                    std::sort(cl.begin(), cl.end(), [](const PlaneRef& a, const PlaneRef& b) { return a.inst < b.inst; });
-                    /* flag P (earlier instance) and Q (later instance) whenever visit(P) > visit(Q) */
-                    std::vector<int> max_before(cl.size()), min_after(cl.size());
-                    int mx = -1;
-                    for (size_t i = 0, j = 0; i < cl.size(); i = j) { /* per instance block */
-                        for (j = i; j < cl.size() && cl[j].inst == cl[i].inst; ++j) max_before[j] = mx;
-                        for (size_t q = i; q < j; ++q) mx = std::max(mx, cl[q].visit);
-                    }
-                    int mn = INT32_MAX;
-                    for (size_t j = cl.size(), i; j > 0; j = i) {
-                        for (i = j; i > 0 && cl[i - 1].inst == cl[j - 1].inst; --i) min_after[i - 1] = mn;
-                        for (size_t q = i; q < j; ++q) mn = std::min(mn, cl[q].visit);
-                    }
-                    /* (a sub-scene with a top tree meets its instances in any order: every such pair then) */
-                    const bool any_order = sub.top_root >= 0;
-                    for (size_t q = 0; q < cl.size(); ++q)
-                        if (max_before[q] > cl[q].visit || min_after[q] < cl[q].visit ||
-                            (any_order && (max_before[q] >= 0 || min_after[q] < INT32_MAX)))
-                            prims[cl[q].ref].reserved |= RT_TIE_FLAG, any_tie = true;
-                }
-                lo = hi;
-            }
-        }
-        if ((rc = upload(c, c->b_fprim, prims.data(), sizeof(rtr_node) * prims.size()))) return rc;
-        {
-            const std::vector<FLeaf> leaves = rtc::build_leaf_records(cs, prims);
-            if ((rc = upload(c, c->b_fleaf, leaves.data(), sizeof(FLeaf) * leaves.size()))) return rc;
-        }
-        rtc::build_scan_runs(cs, prims);
-        if ((rc = upload(c, c->b_fscan, cs.scan.data(), sizeof(double) * cs.scan.size()))) return rc;
-        if ((rc = upload(c, c->b_finst, cs.inst.data(), sizeof(FInst) * cs.inst.size()))) return rc;
-    }
-    c->fast_stack_words = cs.stack_words;
-    /* (guarded references -- hollow spheres -- are tested by the generic loop of the kernels that know about ties: the
-     * flat kernels carry neither) */
-    c->flat_scene = cs.ok && cs.bvh.empty() && !any_tie && cs.guard_of_ref.empty();
-    c->flat_guarded = cs.ok && cs.bvh.empty() && !any_tie && !cs.guard_of_ref.empty(); /* the megakernel's RT_TRAV_FLAT_GUARD */
-    c->walk_extra_words = cs.n_compiled_subtrees ? cs.stack_words : 0;
-    DScene& d = c->ds;
-    d.finst = static_cast<const FInst*>(c->b_finst.p);
-    d.fxf = static_cast<const FXf*>(c->b_fxf.p);
-    d.fref = static_cast<const FRef*>(c->b_fref.p);
-    d.fprim = static_cast<const rtr_node*>(c->b_fprim.p);
-    d.fscan = static_cast<const double*>(c->b_fscan.p);
-    d.fleaf = static_cast<const FLeaf*>(c->b_fleaf.p);
-    d.fexit = static_cast<const int32_t*>(c->b_fexit.p);
-    d.fbvh = static_cast<const FBvh*>(c->b_fbvh.p);
-    d.fsub = static_cast<const FSub*>(c->b_fsub.p);
-    d.n_finst = cs.ok ? cs.subs[0].n_inst : 0;
-    d.top_root0 = cs.ok ? cs.subs[0].top_root : -1;
-    d.world_inst0 = cs.ok ? cs.subs[0].world_inst : -1;
-    d.world_linear0 = cs.ok ? cs.subs[0].world_linear : 0;
-    d.top_bound0 = cs.ok ? cs.subs[0].top_bound : 0.0f;
-    d.fstep = static_cast<const FStep*>(c->b_fstep.p);
-    d.n_fstep = (int32_t)dev_steps.size();
-    d.fstep_tail = cs.step_tail;
-    d.fguard = static_cast<const FGuard*>(c->b_fguard.p);
-    d.fvisit = static_cast<const FVisit*>(c->b_fvisit.p);
-    d.n_fvisit = (int32_t)visits.size();
-    d.nodes = static_cast<const rtr_node*>(c->b_nodes.p);
-    d.list_children = static_cast<const int32_t*>(c->b_kids.p);
-    d.materials = static_cast<const rtr_material*>(c->b_mats.p);
-    d.textures = static_cast<const rtr_texture*>(c->b_tex.p);
-    d.perlin = static_cast<const rtr_perlin*>(c->b_perlin.p);
-    d.images = static_cast<const rtr_image*>(c->b_images.p);
-    d.image_bytes = static_cast<const uint8_t*>(c->b_imgbytes.p);
-    d.lights = static_cast<const rtr_light*>(c->b_lights.p);
-    d.camera = s->camera;
-    for (int k = 0; k < 3; ++k) d.background[k] = s->background[k];
-    d.root = s->root;
-    d.n_nodes = s->n_nodes;
-    d.n_lights = s->n_lights;
-    d.needs_uv = info.needs_uv;
-    /* div_shared's range argument: numerators are differences of scene coordinates and ray origins */
-    d.shared_div = 1;
-    for (int k = 0; k < s->n_nodes && d.shared_div; ++k) {
-        const rtr_node& n = s->nodes[k];
-        const int nf = n.type == RTR_NODE_TRANSLATE ? 3 : n.type == RTR_NODE_SPHERE ? 4 : n.type == RTR_NODE_MOVING_SPHERE ? 9
-                       : n.type >= RTR_NODE_XY_RECT ? 5 : 0;
-        for (int q = 0; q < nf; ++q)
-            if (!(std::fabs(n.f[q]) <= 0x1p60)) d.shared_div = 0;
-        /* moving_sphere::center(time) scales (c1 - c0) by (time - t0) / (t1 - t0) */
-        if (n.type == RTR_NODE_MOVING_SPHERE && !(std::fabs(n.f[7] - n.f[6]) >= 0x1p-20)) d.shared_div = 0;
-    }
-    if (!(std::fabs(s->camera.time0) <= 0x1p60 && std::fabs(s->camera.time1) <= 0x1p60)) d.shared_div = 0;
-    for (const FInst& I : cs.inst)
-        if (I.n_xf > 30) d.shared_div = 0;
-    if (getenv("RTR_NO_SHARED_DIV")) d.shared_div = 0; /* experiments: the plain divisions */
-    /* trace_pair's scenes (DScene::pair_cast): flat, lit (without lights no shadow ray is ever cast, and the pair walk
-     * would test a dummy ray against every record: scene 7, 7 515 -> 6 122 Msamples/s), few enough instances that no
-     * instance box is tested, every instance a packed scan without moving spheres, shared divisions allowed; the others
-     * keep the split casts */
-    d.pair_cast = c->flat_scene && s->n_lights > 0 && d.shared_div && d.top_root0 < 0 && d.n_finst > 0 && d.n_finst <= RT_FAST_NO_BOX_MAX;
-    for (int k = 0; k < d.n_finst && d.pair_cast; ++k) {
-        const FInst& I = cs.inst[k];
-        if (!(I.flags & RT_INST_RUNS)) d.pair_cast = 0;
-        for (uint64_t runs = I.runs; runs != 0; runs >>= RT_RUN_BITS) {
-            const int type = RTR_NODE_SPHERE + (int)((runs >> RT_RUN_COUNT_BITS) & 7);
-            if (type != RTR_NODE_SPHERE && type != RTR_NODE_XY_RECT && type != RTR_NODE_XZ_RECT && type != RTR_NODE_YZ_RECT &&
-                type != RTR_NODE_SPHERE + RT_RUN_BOX)
-                d.pair_cast = 0;
-        }
-    }
+    const LoweredScene L = lower_scene(s, info);
+    const CompiledScene& cs = L.cs;
+    SceneBufs& b = c->sb;
+    DScene& d = c->ds = L.ds; /* the members that are no pointers; one line per array below */
+    if ((rc = put(c, b.nodes, cs.dev_nodes, d.nodes))) return rc;
+    if ((rc = put(c, b.kids, s->list_children, s->n_list_children, d.list_children))) return rc;
+    if ((rc = put(c, b.mats, s->materials, s->n_materials, d.materials))) return rc;
+    if ((rc = put(c, b.tex, s->textures, s->n_textures, d.textures))) return rc;
+    if ((rc = put(c, b.perlin, s->perlin, s->n_perlin, d.perlin))) return rc;
+    if ((rc = put(c, b.images, s->images, s->n_images, d.images))) return rc;
+    if ((rc = put(c, b.imgbytes, s->image_bytes, s->n_image_bytes, d.image_bytes))) return rc;
+    if ((rc = put(c, b.lights, s->lights, s->n_lights, d.lights))) return rc;
+    if ((rc = put(c, b.finst, cs.inst, d.finst))) return rc;
+    if ((rc = put(c, b.fxf, cs.xf, d.fxf))) return rc;
+    if ((rc = put(c, b.fref, cs.ref, d.fref))) return rc;
+    if ((rc = put(c, b.fexit, cs.exits, d.fexit))) return rc;
+    if ((rc = put(c, b.fbvh, cs.bvh, d.fbvh))) return rc;
+    if ((rc = put(c, b.fsub, cs.subs, d.fsub))) return rc;
+    if ((rc = put(c, b.fscan, cs.scan, d.fscan))) return rc;
+    if ((rc = put(c, b.fguard, cs.guards, d.fguard))) return rc;
+    if ((rc = put(c, b.fstep, L.steps, d.fstep))) return rc;
+    if ((rc = put(c, b.fvisit, L.visits, d.fvisit))) return rc;
+    if ((rc = put(c, b.fprim, L.prims, d.fprim))) return rc;
+    if ((rc = put(c, b.fleaf, L.leaves, d.fleaf))) return rc;
+    if ((rc = put(c, b.fmat, L.mats, d.fmat))) return rc;
+    if ((rc = upload(c, b.dscene, &d, sizeof(DScene)))) return rc;
     c->info = info;
-    c->n_materials = s->n_materials;
-    c->lean_materials = true;
-    unsigned type_mask = 0;
-    for (int k = 0; k < s->n_materials; ++k) type_mask |= 1u << s->materials[k].type;
-    c->n_material_types = __builtin_popcount(type_mask);
-    c->quad_lights_only = true;
-    for (int k = 0; k < s->n_lights; ++k)
-        if (s->lights[k].type != RTR_LIGHT_QUAD) c->quad_lights_only = false;
-    if (!c->quad_lights_only) c->lean_materials = false; /* the lean kernels know QuadLights only */
-    for (int k = 0; k < s->n_materials; ++k) {
-        const rtr_material& m = s->materials[k];
-        if (m.type != RTR_MAT_LAMBERTIAN && m.type != RTR_MAT_DIFFUSE_LIGHT) c->lean_materials = false;
-        else if (s->textures[m.tex[0]].type != RTR_TEX_SOLID) c->lean_materials = false;
-    }
-    c->uv_order_dependent = false;
-    if (info.needs_uv) {
-        std::function<bool(int, int)> tex_reads_uv = [&](int t, int guard) {
-            if (t < 0 || guard > 8) return false;
-            const rtr_texture& x = s->textures[t];
-            if (x.type == RTR_TEX_IMAGE) return x.a >= 0;
-            if (x.type == RTR_TEX_CHECKER) return tex_reads_uv(x.a, guard + 1) || tex_reads_uv(x.b, guard + 1);
-            return false;
-        };
-        for (int k = 0; k < s->n_nodes; ++k) {
-            if (s->nodes[k].type != RTR_NODE_MOVING_SPHERE) continue;
-            const rtr_material& m = s->materials[s->nodes[k].a];
-            const int n_tex = m.type == RTR_MAT_PBR ? 4 : (m.type == RTR_MAT_METAL || m.type == RTR_MAT_DIELECTRIC ? 0 : 1);
-            for (int q = 0; q < n_tex; ++q)
-                if (tex_reads_uv(m.tex[q], 0)) c->uv_order_dependent = true;
-        }
-    }
-    { /* FMat: materials with their solid textures' values inline */
-        std::vector<FMat> fm((size_t)s->n_materials);
-        auto solid = [&](int t) { return t >= 0 && s->textures[t].type == RTR_TEX_SOLID; };
-        auto clampd = [](double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }; /* rtweekend.h:40-46 */
-        for (int k = 0; k < s->n_materials; ++k) {
-            const rtr_material& m = s->materials[k];
-            FMat f{};
-            f.type = m.type;
-            for (int q = 0; q < 4; ++q) f.tex[q] = m.tex[q], f.f[q] = m.f[q];
-            switch (m.type) {
-            case RTR_MAT_LAMBERTIAN:
-            case RTR_MAT_DIFFUSE_LIGHT:
-            case RTR_MAT_ISOTROPIC: f.solid = solid(m.tex[0]); break;
-            case RTR_MAT_PBR: f.solid = solid(m.tex[0]) && solid(m.tex[1]) && solid(m.tex[2]) && m.tex[3] < 0; break;
-            default: f.solid = 1; /* metal, dielectric: no texture */
-            }
-            if (f.solid && m.type != RTR_MAT_METAL && m.type != RTR_MAT_DIELECTRIC) {
-                for (int q = 0; q < 3; ++q) f.albedo[q] = s->textures[m.tex[0]].f[q];
-                if (m.type == RTR_MAT_PBR) {
-                    f.rough = clampd(s->textures[m.tex[1]].f[0], 0.01, 1.0);
-                    f.metal = s->textures[m.tex[2]].f[0];
-                }
-            }
-            fm[(size_t)k] = f;
-        }
-        if ((rc = upload(c, c->b_fmat, fm.data(), sizeof(FMat) * fm.size()))) return rc;
-        d.fmat = static_cast<const FMat*>(c->b_fmat.p);
-    }
-    if ((rc = upload(c, c->b_dscene, &c->ds, sizeof(DScene)))) return rc;
+    c->facts = L.facts;
     c->camera_dirty = false;
-    c->t_lo = std::min(0.0, std::min(s->camera.time0, s->camera.time1)); /* Builder::run of rt_compile.h */
-    c->t_hi = std::max(0.0, std::max(s->camera.time0, s->camera.time1));
-    c->camera_times_small = std::fabs(s->camera.time0) <= 0x1p60 && std::fabs(s->camera.time1) <= 0x1p60;
     c->has_scene = true;
     return RTR_OK;
 }
@@ -1241,11 +942,11 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
 
     int pipeline = p->pipeline;
     if (pipeline == RTR_PIPELINE_AUTO) pipeline = RTR_PIPELINE_MEGAKERNEL;
-    const int trav = pick_trav(c, p->flags);
-    if (pipeline == RTR_PIPELINE_WAVEFRONT && (!c->machine_ok || (trav != RT_TRAV_FLAT && trav != RT_TRAV_FAST && trav != RT_TRAV_PROGRAM)))
+    const int trav = pick_trav(c->facts, c->info, p->flags);
+    if (pipeline == RTR_PIPELINE_WAVEFRONT && (!c->facts.machine_ok || (trav != RT_TRAV_FLAT && trav != RT_TRAV_FAST && trav != RT_TRAV_PROGRAM)))
         return fail(c, RTR_ERR_UNSUPPORTED, "the wavefront pipeline runs the compiled traversals only: this graph (or "
                                             "RTR_FLAG_REFERENCE_ORDER) needs the reference-order walk of the megakernel");
-    if (pipeline == RTR_PIPELINE_WAVEFRONT && (p->flags & RTR_FLAG_WF_PERSISTENT) && c->guarded_program)
+    if (pipeline == RTR_PIPELINE_WAVEFRONT && (p->flags & RTR_FLAG_WF_PERSISTENT) && c->facts.guarded_program)
         return fail(c, RTR_ERR_UNSUPPORTED, "RTR_FLAG_WF_PERSISTENT: the traversal machine does not run step programs with "
                                             "guarded primitives (hollow spheres under bvh_nodes) or media under transforms; "
                                             "the lockstep stages do");
@@ -1306,7 +1007,7 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     c->pending_id = id;
     HIPCHK(c, hipMemsetAsync(c->b_stats.p, 0, RT_STATS_WORDS * sizeof(unsigned long long), c->stream));
     if (c->camera_dirty) { /* rtr_set_camera: behind every render queued with the old camera, in front of this one */
-        hipLaunchKernelGGL(k_camera_store, dim3(1), dim3(64), 0, c->stream, static_cast<DScene*>(c->b_dscene.p), c->ds.camera);
+        hipLaunchKernelGGL(k_camera_store, dim3(1), dim3(64), 0, c->stream, static_cast<DScene*>(c->sb.dscene.p), c->ds.camera);
         HIPCHK(c, hipGetLastError());
         c->camera_dirty = false;
     }
@@ -1316,15 +1017,15 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
         WavefrontPlan plan{};
         plan.has_lights = c->ds.n_lights > 0;
         plan.media = trav == RT_TRAV_PROGRAM;
-        plan.lean = c->lean_materials && !plan.media;
-        plan.quadlit = c->quad_lights_only && !c->info.needs_uv;
-        plan.sort = !plan.lean && c->n_material_types > 1;
+        plan.lean = c->facts.lean_materials && !plan.media;
+        plan.quadlit = c->facts.quad_lights_only && !c->info.needs_uv;
+        plan.sort = !plan.lean && c->facts.n_material_types > 1;
         plan.n_cus = c->n_cus;
-        plan.lds = stack_bytes(c, trav);
+        plan.lds = stack_bytes(c->facts, c->info, trav);
         plan.trav = trav;
         plan.machine = (p->flags & RTR_FLAG_WF_PERSISTENT) != 0;
         if (plan.machine) c->stats.flags_in_effect |= RTR_FLAG_WF_PERSISTENT;
-        rc = wavefront_render(c->pool, static_cast<const DScene*>(c->b_dscene.p), plan, P, p->integrator, d_rgb, row_stride,
+        rc = wavefront_render(c->pool, static_cast<const DScene*>(c->sb.dscene.p), plan, P, p->integrator, d_rgb, row_stride,
                               tile_done, c->stream, &c->cancelled_upto, &launches, &launched, c->err);
         c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, launched.phases,
                                           plan.lean, plan.quadlit, plan.sort, plan.media, plan.machine};
@@ -1456,7 +1157,7 @@ int rtr_plan_chunks(rtr_context* c, const rtr_render_params* p) {
     if (P.n_tiles == 0) return 1;
     const int pipeline = p->pipeline == RTR_PIPELINE_AUTO ? RTR_PIPELINE_MEGAKERNEL : p->pipeline;
     int chunks = 1, guided[3];
-    if (int rc = choose_chunks(c, P, p->integrator, pipeline, pick_trav(c, p->flags), p->spp, p->flags, &chunks, guided)) return rc;
+    if (int rc = choose_chunks(c, P, p->integrator, pipeline, pick_trav(c->facts, c->info, p->flags), p->spp, p->flags, &chunks, guided)) return rc;
     return chunks;
 }
 
@@ -1696,8 +1397,8 @@ int accum_features(rtr_context* c, rtr_accum* a, int K) {
     RenderK P = accum_view(a).r;
     P.seed = a->params.seed;
     double* feat = static_cast<double*>(a->d_feat.p);
-    const int trav = per_ray_trav(c, a->params.flags, false); /* the traversals of k_li */
-    const size_t lds = stack_bytes(c, trav);
+    const int trav = per_ray_trav(c->facts, c->info, a->params.flags, false); /* the traversals of k_li */
+    const size_t lds = stack_bytes(c->facts, c->info, trav);
     int rc = RTR_OK;
     if (!dispatch_trav(PerRayTravs{}, trav, [&](auto t) {
             constexpr int T = decltype(t)::value;
@@ -1985,8 +1686,8 @@ static int li_run(rtr_context* c, const rtr_render_params* p, const int32_t* ijs
     const int32_t* d_ijs = rays ? nullptr : reinterpret_cast<const int32_t*>(base);
     const rtr_li_ray* d_rays = rays ? reinterpret_cast<const rtr_li_ray*>(base) : nullptr;
     LiOut* d_out = reinterpret_cast<LiOut*>(base + in_pad);
-    int trav = per_ray_trav(c, p->flags, false);
-    const size_t lds = stack_bytes(c, trav);
+    int trav = per_ray_trav(c->facts, c->info, p->flags, false);
+    const size_t lds = stack_bytes(c->facts, c->info, trav);
     const dim3 grid((unsigned)((n + RTR_BLOCK - 1) / RTR_BLOCK));
     /* integrators 0 / 2 / 3: the media kernel also serves the reference-order traversal */
     const bool n1 = p->integrator != RTR_INTEGRATOR_MIS && p->integrator != RTR_INTEGRATOR_RR;
@@ -2053,9 +1754,32 @@ int rtr_debug_view_get(rtr_context* c, int flags, rtr_debug_view* v, size_t size
     v->stream = c->stream;
     v->device = c->device;
     v->n_cus = c->n_cus;
-    v->n_materials = c->n_materials;
-    v->trav = per_ray_trav(c, flags, true); /* the unit kernels walk what the megakernel walks */
-    v->stack_bytes = stack_bytes(c, v->trav);
+    v->n_materials = c->facts.n_materials;
+    v->trav = per_ray_trav(c->facts, c->info, flags, true); /* the unit kernels walk what the megakernel walks */
+    v->stack_bytes = stack_bytes(c->facts, c->info, v->trav);
+    return RTR_OK;
+}
+int rtr_debug_scene_plan(const rtr_scene_desc* s, int integrator, int flags, rtr_debug_plan* out, size_t size, int32_t* ref_flags,
+                         int64_t cap) {
+    if (!out || size != sizeof(rtr_debug_plan) || cap < 0 || (cap > 0 && !ref_flags)) return RTR_ERR_INVALID;
+    Validator v;
+    v.s = s;
+    rtr_scene_info info{};
+    if (int rc = v.run(&info)) return rc;
+    const LoweredScene L = lower_scene(s, info);
+    const SceneFacts& f = L.facts;
+    int ties = 0, guards = 0;
+    for (size_t k = 0; k < L.prims.size(); ++k) {
+        ties += (L.prims[k].reserved & RT_TIE_FLAG) != 0, guards += (L.prims[k].reserved & RT_GUARD_FLAG) != 0;
+        if ((int64_t)k < cap) ref_flags[k] = L.prims[k].reserved;
+    }
+    const int trav = pick_trav(f, info, flags);
+    const MegaVariant m = mega_variant(f, integrator, trav, flags, nullptr);
+    *out = rtr_debug_plan{info.fast_ok, info.has_media, f.flat_scene, f.flat_guarded, f.lean_materials, f.quad_lights_only,
+                          f.uv_order_dependent, f.machine_ok, f.guarded_program, f.top_tree, f.needs_uv, f.n_material_types,
+                          L.ds.shared_div, L.ds.pair_cast, (int32_t)L.steps.size(), (int32_t)L.visits.size(),
+                          (int32_t)L.prims.size(), f.fast_stack_words, info.stack_words + f.walk_extra_words, ties, guards,
+                          trav, m.trav, m.ms, m.sorted, m.pair};
     return RTR_OK;
 }
 int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {
@@ -2107,8 +1831,8 @@ bool query_staged(size_t stack) {
 
 /* one launch over device arrays on the context stream; hits != nullptr: closest hit, else occlusion */
 int query_launch(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, uint8_t* d_occ, uint32_t* d_rng, int64_t n, int flags) {
-    const int trav = per_ray_trav(c, flags, true); /* what a render with `flags` walks */
-    const size_t stack = stack_bytes(c, trav);
+    const int trav = per_ray_trav(c->facts, c->info, flags, true); /* what a render with `flags` walks */
+    const size_t stack = stack_bytes(c->facts, c->info, trav);
     const bool staged = query_staged(stack);
     const size_t lds = stack + (staged ? RTR_QUERY_STAGE_BYTES : 0);
     const int stage_word = (int)(stack / sizeof(int));
@@ -2224,11 +1948,11 @@ int rtr_set_camera(rtr_context* c, const rtr_camera* cam) {
     /* what rtr_upload_scene derived from the old camera: the boxes of moving spheres cover the ray times [t_lo, t_hi],
      * and DScene::shared_div asked for |time| <= 2^60 */
     for (double t : {cam->time0, cam->time1})
-        if (t < c->t_lo || t > c->t_hi)
-            return fail(c, RTR_ERR_UNSUPPORTED, "camera time " + std::to_string(t) + " outside the range [" + std::to_string(c->t_lo) +
-                                                    ", " + std::to_string(c->t_hi) + "] the scene was compiled for: upload the scene "
+        if (t < c->facts.t_lo || t > c->facts.t_hi)
+            return fail(c, RTR_ERR_UNSUPPORTED, "camera time " + std::to_string(t) + " outside the range [" + std::to_string(c->facts.t_lo) +
+                                                    ", " + std::to_string(c->facts.t_hi) + "] the scene was compiled for: upload the scene "
                                                     "with this camera (rtr_upload_scene)");
-    if ((std::fabs(cam->time0) <= 0x1p60 && std::fabs(cam->time1) <= 0x1p60) != c->camera_times_small)
+    if ((std::fabs(cam->time0) <= 0x1p60 && std::fabs(cam->time1) <= 0x1p60) != c->facts.camera_times_small)
         return fail(c, RTR_ERR_UNSUPPORTED, "camera times cross the 2^60 bound of the shared divisions: upload the scene with "
                                             "this camera (rtr_upload_scene)");
     c->ds.camera = *cam;

@@ -166,6 +166,13 @@ int rtr_test_last_kernel(rtr_context* c, rtr_kernel_record* out, size_t size) {
     return rtr_debug_last_kernel(c, reinterpret_cast<rtr_debug_kernel*>(out), sizeof(rtr_debug_kernel));
 }
 
+int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t flags, rtr_scene_plan* out, int32_t* ref_flags,
+                        int64_t cap) {
+    static_assert(sizeof(rtr_scene_plan) == sizeof(rtr_debug_plan), "one layout");
+    return rtr_debug_scene_plan(scene, integrator, flags, reinterpret_cast<rtr_debug_plan*>(out), sizeof(rtr_debug_plan),
+                                ref_flags, cap);
+}
+
 int rtr_test_reference_order(rtr_context* c, int on) {
     if (!c) return RTR_ERR_INVALID;
     state_of(c).reference_order = on != 0;

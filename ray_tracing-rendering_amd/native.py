@@ -33,7 +33,7 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
-                "rtr_test_temporal_planes")
+                "rtr_test_temporal_planes", "rtr_test_scene_plan")
 _TEST_LIB = None
 
 
@@ -48,6 +48,15 @@ class KernelRecordC(C.Structure):
     """rtr_kernel_record of include/rtr_hip_test.h"""
     _fields_ = [(name, C.c_int32) for name in ("pipeline", "integrator", "trav", "ms", "sorted", "shade_phases", "lean",
                                                "quadlit", "sort", "media", "machine", "accum")]
+
+
+class ScenePlanC(C.Structure):
+    """rtr_scene_plan of include/rtr_hip_test.h"""
+    _fields_ = [(name, C.c_int32) for name in (
+        "fast_ok", "has_media", "flat_scene", "flat_guarded", "lean_materials", "quad_lights_only", "uv_order_dependent",
+        "machine_ok", "guarded_program", "top_tree", "needs_uv", "n_material_types", "shared_div", "pair_cast", "n_steps",
+        "n_visits", "n_refs", "fast_stack_words", "walk_stack_words", "n_tie_refs", "n_guard_refs", "pick_trav", "mega_trav",
+        "mega_ms", "mega_sorted", "mega_pair")]
 
 
 class RtrError(RuntimeError):
@@ -164,6 +173,7 @@ def test_lib():
     T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
     T.rtr_test_temporal_planes.argtypes = [vp] + [C.c_int32] * 6 + [C.POINTER(A.CameraC), C.POINTER(A.CameraC), C.c_int,
                                                                     C.POINTER(A.TemporalParamsC)] + [vp] * 8
+    T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64]
     _TEST_LIB = T
     return T
 
@@ -182,6 +192,23 @@ def validate_scene(scene):
             "fast_refs": info.fast_refs, "fast_stack_words": info.fast_stack_words,
             "compiled_subtrees": info.compiled_subtrees, "program_steps": info.program_steps,
             "inverted_boxes": info.inverted_boxes, "top_trees": info.top_trees}
+
+
+def scene_plan(scene, integrator=4, flags=0):
+    """rtr_test_scene_plan (include/rtr_hip_test.h; no GPU needed): what lowering finds out about ``scene`` and the kernel
+    a megakernel render with ``integrator`` and ``flags`` would run, as a dict of the rtr_scene_plan members plus
+    ``ref_flags``, the ``reserved`` word of every reference record (int32 array).  Raises RtrError for a rejected scene."""
+    T = test_lib()
+    d = scene.desc()
+    plan = ScenePlanC()
+    rc = T.rtr_test_scene_plan(C.byref(d), int(integrator), int(flags), C.byref(plan), None, 0)
+    if rc != 0:
+        raise RtrError(rc, "scene rejected")
+    ref_flags = np.zeros(plan.n_refs, dtype=np.int32)
+    T.rtr_test_scene_plan(C.byref(d), int(integrator), int(flags), C.byref(plan), ref_flags.ctypes.data, len(ref_flags))
+    out = {name: int(getattr(plan, name)) for name, _ in ScenePlanC._fields_}
+    out["ref_flags"] = ref_flags
+    return out
 
 
 def denoise_defaults(**overrides):

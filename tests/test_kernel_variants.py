@@ -108,11 +108,14 @@ def _scene(name):
 
 
 def material_class(sc):
-    """The material / light class upload derives (rtr_upload_scene: lean_materials, quad_lights_only && !needs_uv)."""
+    """The material / light class lowering derives (csrc/rt_lower.h material_facts: lean_materials, quad_lights_only &&
+    !needs_uv): the rule written out here, and checked against what the library itself reports (native.scene_plan)."""
     info = rtr.native.validate_scene(sc)
     quad_only = bool((sc.lights["type"] == A.LIGHT_QUAD).all())
     lean = quad_only and all(m["type"] in (A.MAT_LAMBERTIAN, A.MAT_DIFFUSE_LIGHT) and
                              sc.textures["type"][m["tex"][0]] == A.TEX_SOLID for m in sc.materials)
+    plan = rtr.native.scene_plan(sc)
+    assert (bool(plan["lean_materials"]), bool(plan["quad_lights_only"]), bool(plan["needs_uv"])) == (lean, quad_only, info["needs_uv"])
     return "lean" if lean else ("quadlit" if quad_only and not info["needs_uv"] else "full")
 
 
