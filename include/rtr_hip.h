@@ -659,6 +659,44 @@ int rtr_accum_denoise_temporal(rtr_context* ctx, rtr_accum* acc, rtr_history* hi
                                const rtr_temporal_params* temporal, double* h_linear, int64_t row_stride,
                                uint8_t* h_rgb8);
 
+/* ---- device outputs for accumulators: resolve, features, denoise and temporal frames without a host round trip ----
+ * The four calls below are rtr_accum_resolve, _features, _denoise and _denoise_temporal with DEVICE pointers for the
+ * outputs: the same layouts and, per pixel written, the same bits.
+ *   d_linear  d_linear[((j - y0) * row_stride + (i - x0)) * 3 + c], 8-byte aligned
+ *   d_rgb8    rows of (x1 - x0) pixels, the TOP row of the region first: the layout rtr_display_device writes too
+ *   d_feat    d_feat[((j - y0) * row_stride + (i - x0)) * 7 + c], 8-byte aligned
+ * Which pixels are written is decided ON THE DEVICE, when the kernels execute: a pixel whose tile holds no sample then
+ * (never rendered, reset, left behind by a cancelled pass or by rtr_accum_render_tiles with a target of 0) keeps the
+ * caller's bytes in both outputs, and so does, for resolve and features, a pixel of a tile the accumulator does not own
+ * (features are written for every owned tile, like rtr_accum_features).  The host does not read the sample counts: the
+ * calls neither wait for the passes queued before nor refresh the copy rtr_accum_tiles returns.
+ *
+ * Stream order: the work goes on the context stream (rtr_set_stream included) behind whatever is queued there -- a
+ * non-blocking rtr_accum_render of the same accumulator included -- and the call returns at once unless `blocking`;
+ * rtr_display_device on d_linear may follow with no host wait in between.  Once the workspace has reached its size, a
+ * call makes no allocation, no copy to the host and no wait; the host waits for the stream only when the call has to
+ * replace the filter's planes (a larger region than any denoise call of the context before) or the accumulator's feature
+ * planes by larger ones while queued work may still use the old ones.  The temporal form takes the context's camera and
+ * the history's by value at the call and advances the history (plane set, camera) when it returns RTR_OK: queued frames
+ * see the history in call order.  rtr_history_planes, rtr_history_clear, rtr_accum_reset and rtr_accum_destroy wait for
+ * queued work as before.  rtr_cancel does not apply to these calls, and they leave the statistics of rtr_get_stats alone.
+ *
+ * Checks, all before any device work (outputs and history untouched): every check of the host form of the same name
+ * (rtr_accum_resolve_device and rtr_accum_features_device accept tile-sharded accumulators, so the shards of one image
+ * held on one device compose into one buffer; the two denoise forms return RTR_ERR_UNSUPPORTED for them); a NULL
+ * d_linear together with a NULL d_rgb8, or a NULL d_feat; row_stride below the region's width (where d_linear or d_feat
+ * is given); a d_linear or d_feat that is not 8-byte aligned -- RTR_ERR_INVALID.  The outputs must not overlap each
+ * other or any buffer of the library, and must hold the region at the given stride; neither is checked. */
+int rtr_accum_resolve_device(rtr_context* ctx, rtr_accum* acc, double* d_linear, int64_t row_stride, uint8_t* d_rgb8,
+                             int blocking);
+int rtr_accum_features_device(rtr_context* ctx, rtr_accum* acc, int32_t feature_spp, double* d_feat, int64_t row_stride,
+                              int blocking);
+int rtr_accum_denoise_device(rtr_context* ctx, rtr_accum* acc, const rtr_denoise_params* params, double* d_linear,
+                             int64_t row_stride, uint8_t* d_rgb8, int blocking);
+int rtr_accum_denoise_temporal_device(rtr_context* ctx, rtr_accum* acc, rtr_history* hist,
+                                      const rtr_denoise_params* params, const rtr_temporal_params* temporal,
+                                      double* d_linear, int64_t row_stride, uint8_t* d_rgb8, int blocking);
+
 /* ---- display transform: metered exposure, tone curve, 8-bit encoding ----
  * The last stage in front of a viewer, separate from every output path above (those keep the reference's store).  The
  * input is linear radiance, 3 doubles per pixel, row 0 the LOWEST row, `row_stride` pixels from one row to the next: the

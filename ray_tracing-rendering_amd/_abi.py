@@ -159,6 +159,17 @@ TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2
 ENCODE_GAMMA2, ENCODE_SRGB = 0, 1
 DISPLAY_BINS = 512  # bins of rtr_display_histogram: 16 per octave from 2^-20 to 2^12
 
+# the device forms of the accumulator outputs (include/rtr_hip.h): their argument types in the header's order -- handles
+# and device pointers are void pointers, everything returns int
+_P, _VP = C.POINTER, C.c_void_p
+DEVICE_OUTPUT_SIGNATURES = {
+    "rtr_accum_resolve_device": [_VP, _VP, _VP, C.c_int64, _VP, C.c_int],
+    "rtr_accum_features_device": [_VP, _VP, C.c_int32, _VP, C.c_int64, C.c_int],
+    "rtr_accum_denoise_device": [_VP, _VP, _P(DenoiseParamsC), _VP, C.c_int64, _VP, C.c_int],
+    "rtr_accum_denoise_temporal_device": [_VP, _VP, _VP, _P(DenoiseParamsC), _P(TemporalParamsC), _VP, C.c_int64, _VP,
+                                          C.c_int],
+}
+
 
 def make_params(width, height, spp, *, integrator=INTEGRATOR_MIS, seed=1, max_depth=50, rr_start_depth=3,
                 region=None, pipeline=PIPELINE_AUTO, tile_first=0, tile_stride=1, spp_chunks=1, flags=0):

@@ -116,8 +116,14 @@ def build_host(force=False):
     return out
 
 
+def rocm_root():
+    """the ROCm installation hipcc belongs to: the HIP runtime for host code that g++ links"""
+    return os.path.dirname(os.path.dirname(os.path.realpath(hipcc())))
+
+
 def build_cli(force=False):
-    """Headless C++ driver (host/rtr_cli.cpp) linked against librtr_hip.so: the C++ face of the boundary."""
+    """Headless C++ driver (host/rtr_cli.cpp) linked against librtr_hip.so: the C++ face of the boundary.  Its turntable
+    loop owns device buffers, so it also links the HIP runtime (host functions only: still g++)."""
     src = os.path.join(HOST, "rtr_cli.cpp")
     out = os.path.join(HERE, "rtr_cli")
     lib = os.path.join(HERE, "librtr_hip.so")
@@ -125,8 +131,10 @@ def build_cli(force=False):
         return None
     if not force and not _newer(out, _sources(HOST, (".cpp", ".h")) + [lib]):
         return out
+    rocm = rocm_root()
     cmd = ["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-I" + INC, "-I" + HOST, src,
-           os.path.join(HOST, "rtr_host.cpp"), "-L" + HERE, "-lrtr_hip", "-Wl,-rpath,$ORIGIN",
+           os.path.join(HOST, "rtr_host.cpp"), "-L" + HERE, "-lrtr_hip",
+           "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(rocm, "lib"),
            "-Wl,--allow-shlib-undefined", "-lz", "-o", out]
     subprocess.run(cmd, check=True)
     return out

@@ -1003,6 +1003,59 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_accum_resolve(const AccumResolveK
         }
 }
 
+/* rtr_accum_resolve_device: the values of k_accum_resolve stored straight into the caller's region, R.out with
+ * `row_stride` pixels from row to row and R.rgb8 in rows of x1 - x0 pixels, Y flipped (what the host form's scatter loop
+ * does on the CPU).  One workgroup per owned tile; a tile with count 0 is not written, and that test is all the validity
+ * there is: the host never reads the counts.  The lanes compute per pixel and store per element: through LDS, lane t
+ * takes elements t, t + 256, t + 512 of the tile's [16][16][3], so the 48 doubles (384 B) and the 48 bytes of a tile row
+ * leave as one run of consecutive lanes. */
+__global__ void __launch_bounds__(RTR_BLOCK) k_accum_resolve_scatter(const AccumResolveK R, long long row_stride) {
+    __shared__ double lin[3 * RTR_BLOCK];
+    __shared__ unsigned char bytes[3 * RTR_BLOCK];
+    const int n = R.count[blockIdx.x];
+    if (n == 0) return; /* workgroup-uniform */
+    const size_t in = (size_t)blockIdx.x * 3 * RTR_BLOCK + threadIdx.x;
+    const double scale = 1.0 / n;
+    const double v[3] = {scale * R.sum[in], scale * R.sum[in + RTR_BLOCK], scale * R.sum[in + 2 * RTR_BLOCK]};
+    for (int c = 0; c < 3; ++c) {
+        lin[3 * threadIdx.x + c] = v[c];
+        if (!R.rgb8) continue;
+        double g = __builtin_sqrt(v[c]); /* the store of k_accum_resolve */
+        g = g < 0.0 ? 0.0 : (g > 1.0 ? 1.0 : g);
+        bytes[3 * threadIdx.x + c] = static_cast<unsigned char>(g * 255);
+    }
+    __syncthreads();
+    const RenderK& P = R.r;
+    const int w = P.x1 - P.x0;
+    for (int k = 0; k < 3; ++k) {
+        const int e = k * RTR_BLOCK + threadIdx.x, c = e % 3;
+        int i, j;
+        bool active;
+        tile_pixel(P, blockIdx.x, e / 3, i, j, active);
+        if (!active) continue;
+        if (R.out) R.out[((long long)(j - P.y0) * row_stride + (i - P.x0)) * 3 + c] = lin[e];
+        if (R.rgb8) R.rgb8[((long long)(P.y1 - 1 - j) * w + (i - P.x0)) * 3 + c] = bytes[e];
+    }
+}
+
+/* rtr_accum_features_device: the packed [tile][RTR_FEAT][RTR_BLOCK] planes of k_features -> the caller's [row][col][RTR_FEAT]
+ * region, every owned tile (the features do not depend on the samples a tile holds).  Loads per plane, stores per
+ * element like k_accum_resolve_scatter: a tile row is 16 * RTR_FEAT consecutive doubles. */
+__global__ void __launch_bounds__(RTR_BLOCK) k_accum_features_scatter(const RenderK P, const double* __restrict__ feat,
+                                                                      double* __restrict__ out, long long row_stride) {
+    __shared__ double s[RTR_FEAT * RTR_BLOCK];
+    const double* f = feat + (size_t)blockIdx.x * RTR_FEAT * RTR_BLOCK + threadIdx.x;
+    for (int c = 0; c < RTR_FEAT; ++c) s[RTR_FEAT * threadIdx.x + c] = f[c * RTR_BLOCK];
+    __syncthreads();
+    for (int k = 0; k < RTR_FEAT; ++k) {
+        const int e = k * RTR_BLOCK + threadIdx.x;
+        int i, j;
+        bool active;
+        tile_pixel(P, blockIdx.x, e / RTR_FEAT, i, j, active);
+        if (active) out[((long long)(j - P.y0) * row_stride + (i - P.x0)) * RTR_FEAT + e % RTR_FEAT] = s[e];
+    }
+}
+
 /* ---- rtr_accum_denoise / rtr_denoise_host: edge-avoiding a-trous filter (include/rtr_hip.h) ----
  * Every plane is row-major over the w x h region, pixel p = y * w + x (y = j - y0).  Inputs (AoS, the layout of the host
  * entry point): m [p][3] mean radiance, q [p] second moments, n [p] sample count (0 = not a tap, left alone), feat [p][7].
@@ -1198,8 +1251,11 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_denoise_pass_lds(const DenoiseK D
     D.v[src ^ 1][p] = sv / (sw * sw);
 }
 
-/* remodulate (iterations = 0: the mean itself, the bits of k_accum_resolve) and store linear and / or 8-bit */
-__global__ void __launch_bounds__(RTR_BLOCK) k_denoise_out(const DenoiseK D, int src) {
+/* remodulate (iterations = 0: the mean itself, the bits of k_accum_resolve) and store linear and / or 8-bit: D.out with
+ * `row_stride` pixels from row to row (D.w for the host forms' plane, the caller's for the device forms, whose D.out and
+ * D.rgb8 are the caller's buffers), D.rgb8 in rows of D.w pixels.  A pixel with n = 0 is not written: on the device forms
+ * this test is the whole validity decision */
+__global__ void __launch_bounds__(RTR_BLOCK) k_denoise_out(const DenoiseK D, int src, long long row_stride) {
     const long long np = (long long)D.w * D.h, p = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
     if (p >= np || D.n[p] == 0) return;
     const int x = (int)(p % D.w), y = (int)(p / D.w);
@@ -1212,7 +1268,10 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_denoise_out(const DenoiseK D, int
             o[c] = a > 1e-3 ? v * a : v;
         }
     }
-    if (D.out) D.out[3 * p] = o[0], D.out[3 * p + 1] = o[1], D.out[3 * p + 2] = o[2];
+    if (D.out) {
+        double* lo = D.out + ((long long)y * row_stride + x) * 3;
+        lo[0] = o[0], lo[1] = o[1], lo[2] = o[2];
+    }
     if (D.rgb8)
         for (int c = 0; c < 3; ++c) { /* the store of k_accum_resolve */
             double g = __builtin_sqrt(o[c]);

@@ -148,6 +148,13 @@ int ensure(rtr_context* c, DevBuf& b, size_t bytes) {
     return RTR_OK;
 }
 
+/* ensure() for a buffer that work queued without blocking may still read or write (b_denoise, an accumulator's d_feat:
+ * the rtr_accum_*_device calls): the stream is waited for only when the buffer has to be replaced by a larger one */
+int ensure_behind_queue(rtr_context* c, DevBuf& b, size_t bytes) {
+    if (b.p && b.cap < std::max(bytes, (size_t)16)) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ensure(c, b, bytes);
+}
+
 int upload(rtr_context* c, DevBuf& b, const void* src, size_t bytes) {
     int rc = ensure(c, b, bytes);
     if (rc) return rc;
@@ -1317,6 +1324,25 @@ int rtr_accum_resolve(rtr_context* c, rtr_accum* a, double* h_linear, int64_t ro
     return RTR_OK;
 }
 
+int rtr_accum_resolve_device(rtr_context* c, rtr_accum* a, double* d_linear, int64_t row_stride, uint8_t* d_rgb8, int blocking) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    const rtr_render_params& p = a->params;
+    if (!d_linear && !d_rgb8) return fail(c, RTR_ERR_INVALID, "no output buffer");
+    if (d_linear && row_stride < (int64_t)(p.x1 - p.x0)) return fail(c, RTR_ERR_INVALID, "bad output stride");
+    if (reinterpret_cast<uintptr_t>(d_linear) % sizeof(double)) return fail(c, RTR_ERR_INVALID, "d_linear is not 8-byte aligned");
+    const size_t n = a->tiles.size();
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    AccumResolveK R = accum_view(a); /* the counts stay on the device: the kernel leaves a tile without samples alone */
+    R.out = d_linear, R.rgb8 = d_rgb8;
+    hipLaunchKernelGGL(k_accum_resolve_scatter, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, R, (long long)row_stride);
+    HIPCHK(c, hipGetLastError());
+    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
 int rtr_accum_tiles(rtr_context* c, const rtr_accum* a, int32_t* tile_ids, int32_t* counts, int64_t cap, int64_t* n_tiles) {
     if (!c) return RTR_ERR_INVALID;
     if (int rc = accum_check(c, a)) return rc;
@@ -1393,7 +1419,7 @@ int accum_features(rtr_context* c, rtr_accum* a, int K) {
     const size_t n = a->tiles.size();
     if (a->feat_k == K || n == 0) return RTR_OK;
     a->feat_k = 0;
-    if (int rc = ensure(c, a->d_feat, n * RTR_FEAT * RTR_BLOCK * sizeof(double))) return rc;
+    if (int rc = ensure_behind_queue(c, a->d_feat, n * RTR_FEAT * RTR_BLOCK * sizeof(double))) return rc;
     RenderK P = accum_view(a).r;
     P.seed = a->params.seed;
     double* feat = static_cast<double*>(a->d_feat.p);
@@ -1417,7 +1443,7 @@ int denoise_planes(rtr_context* c, int w, int h, const rtr_denoise_params* prm, 
     const size_t np = (size_t)w * h;
     /* doubles: m 3, q 1, feat 7, c 3 + 3, v 1 + 1, a 3, nrm 3, z 1, out 3; then n (int) and rgb8 (3 bytes) */
     const size_t n_doubles = 29 * np;
-    if (int rc = ensure(c, c->b_denoise, n_doubles * sizeof(double) + np * sizeof(int) + 3 * np)) return rc;
+    if (int rc = ensure_behind_queue(c, c->b_denoise, n_doubles * sizeof(double) + np * sizeof(int) + 3 * np)) return rc;
     double* d = static_cast<double*>(c->b_denoise.p);
     D = DenoiseK{};
     D.w = w, D.h = h, D.iterations = prm->iterations;
@@ -1439,14 +1465,28 @@ int denoise_planes(rtr_context* c, int w, int h, const rtr_denoise_params* prm, 
     return RTR_OK;
 }
 
+/* where a denoise call's outputs go: HOST buffers (the library's planes, a copy, a wait and a per-pixel loop on the CPU)
+ * or, with `device`, the caller's DEVICE buffers, written by k_denoise_out itself with nothing after it on the host */
+struct DenoiseOut {
+    double* linear;
+    int64_t row_stride;
+    uint8_t* rgb8;
+    bool device;
+    int blocking; /* device only */
+};
+
 /* prep, the passes and the output on the filled input planes; then the valid pixels into the caller's buffers (linear:
- * row r at h_linear + r * row_stride * 3; 8-bit: rows of w pixels, the top row first).  With `T` the temporal blend and
+ * row r at linear + r * row_stride * 3; 8-bit: rows of w pixels, the top row first).  With `T` the temporal blend and
  * the history write-back take the place of the prep (rtr_accum_denoise_temporal). */
-int denoise_run(rtr_context* c, DenoiseK D, double* h_linear, int64_t row_stride, uint8_t* h_rgb8, const TemporalK* T = nullptr) {
+int denoise_run(rtr_context* c, DenoiseK D, const DenoiseOut& O, const TemporalK* T = nullptr) {
+    double* const h_linear = O.linear;
+    uint8_t* const h_rgb8 = O.rgb8;
     const size_t np = (size_t)D.w * D.h;
     const dim3 grid1((unsigned)((np + RTR_BLOCK - 1) / RTR_BLOCK)), grid2((unsigned)((D.w + 15) / 16), (unsigned)((D.h + 15) / 16));
     if (!h_linear) D.out = nullptr;
     if (!h_rgb8) D.rgb8 = nullptr;
+    const int64_t row_stride = O.device ? O.row_stride : D.w; /* of D.out: the host forms read the library's plane */
+    if (O.device) D.out = O.linear, D.rgb8 = O.rgb8;
     if (T) {
         hipLaunchKernelGGL(k_temporal_blend, grid2, dim3(RTR_BLOCK), 0, c->stream, D, *T);
         hipLaunchKernelGGL(k_temporal_store, grid1, dim3(RTR_BLOCK), 0, c->stream, D, *T);
@@ -1465,8 +1505,12 @@ int denoise_run(rtr_context* c, DenoiseK D, double* h_linear, int64_t row_stride
         else
             hipLaunchKernelGGL(k_denoise_pass, grid2, dim3(RTR_BLOCK), 0, c->stream, D, 1 << k, src);
     }
-    hipLaunchKernelGGL(k_denoise_out, grid1, dim3(RTR_BLOCK), 0, c->stream, D, src);
+    hipLaunchKernelGGL(k_denoise_out, grid1, dim3(RTR_BLOCK), 0, c->stream, D, src, (long long)row_stride);
     HIPCHK(c, hipGetLastError());
+    if (O.device) { /* D.n decided on the device which pixels were written */
+        if (O.blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
+        return RTR_OK;
+    }
     std::vector<int> n(np);
     std::vector<double> lin(h_linear ? 3 * np : 0);
     std::vector<unsigned char> rgb(h_rgb8 ? 3 * np : 0);
@@ -1478,7 +1522,7 @@ int denoise_run(rtr_context* c, DenoiseK D, double* h_linear, int64_t row_stride
         for (int x = 0; x < D.w; ++x) {
             const size_t p = (size_t)y * D.w + x;
             if (n[p] == 0) continue;
-            if (h_linear) std::memcpy(h_linear + ((size_t)y * (size_t)row_stride + x) * 3, &lin[3 * p], 3 * sizeof(double));
+            if (h_linear) std::memcpy(h_linear + ((size_t)y * (size_t)O.row_stride + x) * 3, &lin[3 * p], 3 * sizeof(double));
             if (h_rgb8) {
                 const size_t o = ((size_t)(D.h - 1 - y) * D.w + x) * 3;
                 h_rgb8[o] = rgb[o], h_rgb8[o + 1] = rgb[o + 1], h_rgb8[o + 2] = rgb[o + 2];
@@ -1510,7 +1554,10 @@ int history_check(rtr_context* c, const rtr_history* h) {
 /* rtr_accum_denoise, and with `hist` rtr_accum_denoise_temporal: ONE list of checks, all before any device work; then
  * features, gather and the filter, with the temporal stage in the prep's place */
 int accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, rtr_history* hist, const rtr_temporal_params* tp,
-                  double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
+                  const DenoiseOut& O) {
+    double* const h_linear = O.linear;
+    uint8_t* const h_rgb8 = O.rgb8;
+    const int64_t row_stride = O.row_stride;
     if (!c) return RTR_ERR_INVALID;
     if (int rc = accum_render_check(c, a)) return rc;
     if (int rc = denoise_check(c, prm)) return rc;
@@ -1521,6 +1568,8 @@ int accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, r
     const int w = p.x1 - p.x0, h = p.y1 - p.y0;
     if (!h_linear && !h_rgb8) return fail(c, RTR_ERR_INVALID, "no output buffer");
     if (h_linear && row_stride < (int64_t)w) return fail(c, RTR_ERR_INVALID, "bad output stride");
+    if (O.device && reinterpret_cast<uintptr_t>(h_linear) % sizeof(double))
+        return fail(c, RTR_ERR_INVALID, "d_linear is not 8-byte aligned");
     if (p.tile_stride > 1)
         return fail(c, RTR_ERR_UNSUPPORTED, hist ? "a tile-sharded accumulator: temporal denoising is single-context"
                                                  : "a tile-sharded accumulator: gather the shards and call rtr_denoise_host");
@@ -1533,14 +1582,17 @@ int accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, r
     const size_t n = a->tiles.size();
     if (n == 0) return RTR_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = refresh_counts(c, a)) return rc;
+    if (O.device)
+        (void)hipGetLastError();
+    else if (int rc = refresh_counts(c, a)) /* (the device forms leave the counts where they are: k_denoise_gather reads them) */
+        return rc;
     if (int rc = accum_features(c, a, prm->feature_spp)) return rc;
     DenoiseK D;
     if (int rc = denoise_planes(c, w, h, prm, D)) return rc;
     hipLaunchKernelGGL(k_denoise_gather, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, accum_view(a),
                        static_cast<const double*>(a->d_q.p), static_cast<const double*>(a->d_feat.p), D);
     HIPCHK(c, hipGetLastError());
-    if (!hist) return denoise_run(c, D, h_linear, row_stride, h_rgb8);
+    if (!hist) return denoise_run(c, D, O);
     TemporalK T{};
     T.cam = c->ds.camera, T.prev = hist->cam;
     T.W = p.image_width, T.H = p.image_height, T.x0 = p.x0, T.y0 = p.y0;
@@ -1549,7 +1601,7 @@ int accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, r
     T.hist_in = static_cast<const double*>(hist->d_planes[hist->cur].p);
     T.hist_out = static_cast<double*>(hist->d_planes[hist->cur ^ 1].p);
     T.mom = static_cast<double*>(hist->d_mom.p);
-    if (int rc = denoise_run(c, D, h_linear, row_stride, h_rgb8, &T)) return rc;
+    if (int rc = denoise_run(c, D, O, &T)) return rc;
     hist->cur ^= 1, hist->have = true, hist->cam = c->ds.camera; /* the write-back counts once the frame has finished */
     return RTR_OK;
 }
@@ -1594,7 +1646,31 @@ int rtr_accum_features(rtr_context* c, rtr_accum* a, int32_t feature_spp, double
 
 int rtr_accum_denoise(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, double* h_linear, int64_t row_stride,
                       uint8_t* h_rgb8) {
-    return accum_denoise(c, a, prm, nullptr, nullptr, h_linear, row_stride, h_rgb8);
+    return accum_denoise(c, a, prm, nullptr, nullptr, DenoiseOut{h_linear, row_stride, h_rgb8, false, 1});
+}
+
+int rtr_accum_denoise_device(rtr_context* c, rtr_accum* a, const rtr_denoise_params* prm, double* d_linear, int64_t row_stride,
+                             uint8_t* d_rgb8, int blocking) {
+    return accum_denoise(c, a, prm, nullptr, nullptr, DenoiseOut{d_linear, row_stride, d_rgb8, true, blocking});
+}
+
+int rtr_accum_features_device(rtr_context* c, rtr_accum* a, int32_t feature_spp, double* d_feat, int64_t row_stride, int blocking) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_render_check(c, a)) return rc;
+    if (feature_spp < 1) return fail(c, RTR_ERR_INVALID, "feature_spp must be >= 1");
+    const rtr_render_params& p = a->params;
+    if (!d_feat || row_stride < (int64_t)(p.x1 - p.x0)) return fail(c, RTR_ERR_INVALID, "bad output buffer / stride");
+    if (reinterpret_cast<uintptr_t>(d_feat) % sizeof(double)) return fail(c, RTR_ERR_INVALID, "d_feat is not 8-byte aligned");
+    const size_t n = a->tiles.size();
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    if (int rc = accum_features(c, a, feature_spp)) return rc;
+    hipLaunchKernelGGL(k_accum_features_scatter, dim3((unsigned)n), dim3(RTR_BLOCK), 0, c->stream, accum_view(a).r,
+                       static_cast<const double*>(a->d_feat.p), d_feat, (long long)row_stride);
+    HIPCHK(c, hipGetLastError());
+    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTR_OK;
 }
 
 int rtr_denoise_host(rtr_context* c, const rtr_denoise_params* prm, int32_t width, int32_t height, const double* h_color,
@@ -1616,7 +1692,7 @@ int rtr_denoise_host(rtr_context* c, const rtr_denoise_params* prm, int32_t widt
     HIPCHK(c, hipMemcpy(D.q, h_q, np * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(D.n, h_count, np * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(D.feat, h_feat, RTR_FEAT * np * sizeof(double), hipMemcpyHostToDevice));
-    return denoise_run(c, D, h_linear, width, h_rgb8);
+    return denoise_run(c, D, DenoiseOut{h_linear, width, h_rgb8, false, 1});
 }
 
 void rtr_accum_destroy(rtr_accum* a) {
@@ -2065,7 +2141,15 @@ int rtr_accum_denoise_temporal(rtr_context* c, rtr_accum* a, rtr_history* hist, 
                                const rtr_temporal_params* tp, double* h_linear, int64_t row_stride, uint8_t* h_rgb8) {
     if (!c) return RTR_ERR_INVALID;
     if (!hist) return fail(c, RTR_ERR_INVALID, "null history");
-    return accum_denoise(c, a, prm, hist, tp, h_linear, row_stride, h_rgb8);
+    return accum_denoise(c, a, prm, hist, tp, DenoiseOut{h_linear, row_stride, h_rgb8, false, 1});
+}
+
+int rtr_accum_denoise_temporal_device(rtr_context* c, rtr_accum* a, rtr_history* hist, const rtr_denoise_params* prm,
+                                      const rtr_temporal_params* tp, double* d_linear, int64_t row_stride, uint8_t* d_rgb8,
+                                      int blocking) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!hist) return fail(c, RTR_ERR_INVALID, "null history");
+    return accum_denoise(c, a, prm, hist, tp, DenoiseOut{d_linear, row_stride, d_rgb8, true, blocking});
 }
 
 } /* extern "C" */

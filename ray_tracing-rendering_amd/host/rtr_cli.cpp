@@ -17,25 +17,44 @@
  *           [--turntable N [--temporal]]   N frames of a camera orbiting `lookat` about the world y axis (frame k at angle
  *                                   2 pi k / N), ONE upload: per frame rtr_set_camera, rtr_accum_reset with seed + k, the passes
  *                                   of --passes (or one to --spp), and with --denoise the filter -- with --temporal (implies
- *                                   --denoise) rtr_accum_denoise_temporal over one history.  Frames go to out_000.ppm ... (from
- *                                   --out out.ppm); first device of --devices only; time per frame
+ *                                   --denoise) the temporal form over one history.  Every frame stays on the device: the
+ *                                   passes, rtr_accum_resolve_device / _denoise_device / _denoise_temporal_device and, with the
+ *                                   display options below, rtr_display_device are queued on the context stream, and only the
+ *                                   frame's bytes come back.  Frames go to out_000.ppm ... (from --out out.ppm); first device
+ *                                   of --devices only; time per frame
  *           [--pick i,j]   nothing is rendered: the closest hit of pixel (i, j)'s centre ray -- u = (i + 0.5) / (W - 1),
  *                                   v = (j + 0.5) / (H - 1), no lens offset, time0 -- through Renderer::closest_hits, as one line
  *                                   `hit front_face material t p n` with the doubles as %.17g
  *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
  *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
- *                                   rtr_display_host through Renderer::display) of the finished image instead of the
- *                                   reference's store; prints the scale used.  Not with --turntable
+ *                                   rtr_display_host through Renderer::display; with --turntable rtr_display_device on
+ *                                   every frame) of the finished image instead of the reference's store; prints the scale
+ *                                   used (not per --turntable frame: nothing waits for it).  Not with --pick
  */
 #include "rtr_renderer.h"
+
+/* --turntable owns the frame's device buffers (the library takes raw device pointers).  The six HIP runtime calls it
+ * needs, declared here: hip/hip_runtime_api.h declares a global `texture` template, which the reference's class `texture`
+ * (texture.h) cannot share a translation unit with.  hipError_t is an int-sized enum, hipSuccess is 0. */
+extern "C" {
+int hipSetDevice(int device);
+int hipMalloc(void** ptr, size_t bytes);
+int hipFree(void* ptr);
+int hipMemset(void* dst, int value, size_t bytes);
+int hipMemcpy(void* dst, const void* src, size_t bytes, int kind);
+int hipDeviceSynchronize(void);
+}
+static const int hipSuccess = 0, hipMemcpyDeviceToHost = 2;
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 
-/* --turntable: the frame loop of INTEGRATION.md section 4 on the C ABI itself.  Returns the exit status. */
+/* --turntable: the device form of the frame loop of INTEGRATION.md section 4 on the C ABI itself: per frame everything is
+ * queued, then one wait and one copy of the bytes.  `dp`: the display transform takes the place of the reference's store.
+ * Returns the exit status. */
 static int turntable(const SceneConfig& config, int device, int frames, int integrator_id, unsigned seed, std::vector<int> passes,
-                     const rtr_denoise_params* dn, bool temporal, const std::string& out) {
+                     const rtr_denoise_params* dn, bool temporal, const rtr_display_params* dp, const std::string& out) {
     const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);
     auto camera_of = [&](int k) {
         const double a = 2.0 * 3.14159265358979323846 * k / frames, ca = std::cos(a), sa = std::sin(a);
@@ -48,9 +67,13 @@ static int turntable(const SceneConfig& config, int device, int frames, int inte
         std::cerr << "rtr_create: " << rtr_last_error(nullptr) << "\n";
         return 1;
     }
+    double* d_lin = nullptr; /* [H][W][3] linear radiance, only in front of the display transform */
+    uint8_t* d_rgb = nullptr; /* [H][W][3] the frame's bytes, top row first */
     auto fail = [&](const char* what) {
         std::cerr << what << ": " << rtr_last_error(ctx) << "\n";
-        rtr_destroy(ctx); /* frees the accumulator and the history */
+        rtr_destroy(ctx); /* frees the accumulator and the history (and waits for queued work) */
+        (void)hipFree(d_lin);
+        (void)hipFree(d_rgb);
         return 1;
     };
     rtr_scene_storage st;
@@ -72,6 +95,12 @@ static int turntable(const SceneConfig& config, int device, int frames, int inte
     rtr_temporal_params tp{};
     rtr_temporal_defaults(&tp);
     std::vector<unsigned char> rgb((size_t)W * H * 3);
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_rgb), rgb.size()) != hipSuccess ||
+        hipMemset(d_rgb, 0, rgb.size()) != hipSuccess ||
+        (dp && (hipMalloc(reinterpret_cast<void**>(&d_lin), rgb.size() * sizeof(double)) != hipSuccess ||
+                hipMemset(d_lin, 0, rgb.size() * sizeof(double)) != hipSuccess)) ||
+        hipDeviceSynchronize() != hipSuccess) /* the fills are not on the context's stream */
+        return fail("device buffers of a frame (the HIP runtime, not the library)");
     const size_t dot = out.rfind('.');
     const std::string stem = dot == std::string::npos ? out : out.substr(0, dot);
     for (int k = 0; k < frames; ++k) {
@@ -80,11 +109,15 @@ static int turntable(const SceneConfig& config, int device, int frames, int inte
         if (rtr_set_camera(ctx, &cam) != RTR_OK) return fail("rtr_set_camera");
         if (rtr_accum_reset(ctx, acc, seed + (unsigned)k) != RTR_OK) return fail("rtr_accum_reset");
         for (int target : passes)
-            if (rtr_accum_render(ctx, acc, target, 1) != RTR_OK) return fail("rtr_accum_render");
-        const int rc = temporal ? rtr_accum_denoise_temporal(ctx, acc, hist, dn, &tp, nullptr, 0, rgb.data())
-                       : dn     ? rtr_accum_denoise(ctx, acc, dn, nullptr, 0, rgb.data())
-                                : rtr_accum_resolve(ctx, acc, nullptr, 0, rgb.data());
+            if (rtr_accum_render(ctx, acc, target, 0) != RTR_OK) return fail("rtr_accum_render");
+        uint8_t* const store = dp ? nullptr : d_rgb; /* the reference's store, unless the display transform follows */
+        const int rc = temporal ? rtr_accum_denoise_temporal_device(ctx, acc, hist, dn, &tp, d_lin, W, store, 0)
+                       : dn     ? rtr_accum_denoise_device(ctx, acc, dn, d_lin, W, store, 0)
+                                : rtr_accum_resolve_device(ctx, acc, d_lin, W, store, 0);
         if (rc != RTR_OK) return fail("frame output");
+        if (dp && rtr_display_device(ctx, dp, W, H, d_lin, W, d_rgb, nullptr, nullptr, 0) != RTR_OK) return fail("rtr_display_device");
+        if (rtr_synchronize(ctx) != RTR_OK) return fail("rtr_synchronize");
+        if (hipMemcpy(rgb.data(), d_rgb, rgb.size(), hipMemcpyDeviceToHost) != hipSuccess) return fail("copy of the frame's bytes");
         const double ms = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count() * 1e3;
         std::cout << "frame " << k << ": " << ms << " ms\n";
         if (!out.empty()) {
@@ -99,6 +132,8 @@ static int turntable(const SceneConfig& config, int device, int frames, int inte
     }
     std::cout << "turntable: " << frames << " frames, scene uploads: 1\n";
     rtr_destroy(ctx);
+    (void)hipFree(d_lin);
+    (void)hipFree(d_rgb);
     return 0;
 }
 
@@ -255,8 +290,8 @@ int main(int argc, char** argv) {
         std::cerr << "--turntable excludes --adaptive, --repeat and --pick\n";
         return 2;
     }
-    if (display && (turntable_frames || pick)) {
-        std::cerr << "the display options exclude --turntable and --pick\n";
+    if (display && pick) {
+        std::cerr << "the display options exclude --pick\n";
         return 2;
     }
     if (temporal) denoise = true;
@@ -291,7 +326,7 @@ int main(int argc, char** argv) {
             }
         if (passes.empty()) passes.push_back(config.samples_per_pixel);
         return turntable(config, devices.empty() ? 0 : devices[0], turntable_frames, integrator_id < 0 || integrator_id > 4 ? 4 : integrator_id,
-                         seed, passes, denoise ? &dn : nullptr, temporal, out);
+                         seed, passes, denoise ? &dn : nullptr, temporal, display ? &dp : nullptr, out);
     }
     auto cam = make_shared<camera>(config.lookfrom, config.lookat, config.vup, config.vfov, config.aspect_ratio,
                                    config.aperture, config.focus_dist, 0.0, 1.0); /* main.cpp:63-66 */

@@ -29,7 +29,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_set_camera", "rtr_get_camera", "rtr_accum_reset", "rtr_temporal_defaults", "rtr_history_create",
            "rtr_history_clear", "rtr_history_destroy", "rtr_history_planes", "rtr_accum_denoise_temporal",
            "rtr_display_defaults", "rtr_display_srgb_thresholds", "rtr_display_histogram", "rtr_display_host",
-           "rtr_display_device")
+           "rtr_display_device", "rtr_accum_resolve_device", "rtr_accum_features_device", "rtr_accum_denoise_device",
+           "rtr_accum_denoise_temporal_device")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
@@ -142,6 +143,8 @@ def lib():
     L.rtr_display_host.argtypes = [vp, P(A.DisplayParamsC), C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, P(A.DisplayResultC)]
     L.rtr_display_device.argtypes = [vp, P(A.DisplayParamsC), C.c_int32, C.c_int32, vp, C.c_int64, vp, vp,
                                      P(A.DisplayResultC), C.c_int]
+    for name, argtypes in A.DEVICE_OUTPUT_SIGNATURES.items():
+        getattr(L, name).argtypes = argtypes
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -770,6 +773,35 @@ class Accumulator:
             self._ctx._h, self._handle(), history._handle(), C.byref(prm), C.byref(tp), None if rgb8 else out.ctypes.data,
             0 if rgb8 else self.shape[1], out.ctypes.data if rgb8 else None))
         return out
+
+    # device outputs (include/rtr_hip.h: rtr_accum_*_device): raw device pointers, e.g. a torch tensor's ``data_ptr()``,
+    # on the context stream behind what is queued there -- a non-blocking ``render`` included.  Which pixels are written
+    # is decided on the device: pixels of tiles without samples (or not owned) keep what the buffers hold.
+    def resolve_into(self, linear_ptr, row_stride, rgb8_ptr=None, blocking=False):
+        """rtr_accum_resolve_device: ``resolve`` into ``linear_ptr`` (doubles, ``row_stride`` pixels from row to row) and /
+        or ``rgb8`` into ``rgb8_ptr`` (bytes, rows of the region's width, top row first); either may be None."""
+        self._ctx._chk(self._L.rtr_accum_resolve_device(self._ctx._h, self._handle(), C.c_void_p(linear_ptr or None),
+                                                        int(row_stride), C.c_void_p(rgb8_ptr or None), 1 if blocking else 0))
+
+    def features_into(self, feature_spp, feat_ptr, row_stride, blocking=False):
+        """rtr_accum_features_device: ``features`` into ``feat_ptr``, 7 doubles per pixel, ``row_stride`` pixels per row."""
+        self._ctx._chk(self._L.rtr_accum_features_device(self._ctx._h, self._handle(), int(feature_spp),
+                                                         C.c_void_p(feat_ptr or None), int(row_stride), 1 if blocking else 0))
+
+    def denoise_into(self, linear_ptr, row_stride, rgb8_ptr=None, params=None, blocking=False):
+        """rtr_accum_denoise_device: ``denoise`` into the buffers of ``resolve_into``."""
+        prm = params if params is not None else denoise_defaults()
+        self._ctx._chk(self._L.rtr_accum_denoise_device(self._ctx._h, self._handle(), C.byref(prm), C.c_void_p(linear_ptr or None),
+                                                        int(row_stride), C.c_void_p(rgb8_ptr or None), 1 if blocking else 0))
+
+    def denoise_temporal_into(self, history, linear_ptr, row_stride, rgb8_ptr=None, params=None, temporal=None, blocking=False):
+        """rtr_accum_denoise_temporal_device: ``denoise_temporal`` into the buffers of ``resolve_into``.  The cameras are
+        taken at the call and the history advances when it returns: frames may be queued one behind the other."""
+        prm = params if params is not None else denoise_defaults()
+        tp = temporal if temporal is not None else temporal_defaults()
+        self._ctx._chk(self._L.rtr_accum_denoise_temporal_device(
+            self._ctx._h, self._handle(), history._handle(), C.byref(prm), C.byref(tp), C.c_void_p(linear_ptr or None),
+            int(row_stride), C.c_void_p(rgb8_ptr or None), 1 if blocking else 0))
 
     def close(self):
         if getattr(self, "_h", None):

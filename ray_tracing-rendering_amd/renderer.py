@@ -222,7 +222,8 @@ class Renderer:
         finally:
             self._rendering = False
 
-    def render_sequence(self, scene, cameras, target_buffer, spp, seeds=None, denoise=None, temporal=None, rank=0, world=1):
+    def render_sequence(self, scene, cameras, target_buffer, spp, seeds=None, denoise=None, temporal=None, rank=0, world=1,
+                        display=None):
         """The frames of a moving camera: a generator with ONE upload of ``scene`` and, per camera of ``cameras`` (each
         what ``Context.set_camera`` takes), set_camera, a reset of one accumulator with the frame's seed, a pass to
         ``spp`` samples and the store into ``target_buffer``; yields the frame index once the buffer holds that frame.
@@ -231,7 +232,14 @@ class Renderer:
         rtr_temporal_params; ``denoise`` then defaults to ``denoise_defaults()``) blends the reprojected last frame in
         first (rtr_accum_denoise_temporal) over one history that lives as long as the generator.  Single rank:
         ``world`` > 1 raises ValueError.  Afterwards the context keeps the last camera (``Context.camera_updated``); the
-        other render methods of this class put ``scene.camera`` back before they render ``scene``."""
+        other render methods of this class put ``scene.camera`` back before they render ``scene``.
+
+        ``display`` (an rtr_display_params): each frame stays on the device -- reset, a non-blocking pass, the device form
+        of the resolve or denoise (rtr_accum_*_device) and rtr_display_device are queued on the context stream into
+        device buffers the generator owns (torch tensors: import torch before this package, as bench.py does), and only
+        the frame's display bytes come back, in one copy.  They are left in ``target_buffer.display_rgb8`` -- (height,
+        width, 3) uint8, top row first, for ``target_buffer.save_to_png(filename, rgb8=target_buffer.display_rgb8)``;
+        the buffer's ``linear`` and ``pixels`` are not touched.  Without ``display`` nothing changes."""
         from .native import denoise_defaults
         if world != 1 or rank != 0:
             raise ValueError("render_sequence is single rank (a temporal history is not sharded)")
@@ -246,10 +254,12 @@ class Renderer:
         if temporal is not None and denoise is None:
             denoise = denoise_defaults()
         check_denoise(denoise)
+        if display is not None and not isinstance(display, A.DisplayParamsC):
+            raise ValueError("display must be None or rtr_display_params (display_defaults())")
         self._cancel_requested = False
-        return self._sequence(scene, cameras, target_buffer, int(spp), seeds, denoise, temporal)
+        return self._sequence(scene, cameras, target_buffer, int(spp), seeds, denoise, temporal, display)
 
-    def _sequence(self, scene, cameras, target_buffer, spp, seeds, denoise, temporal):
+    def _sequence(self, scene, cameras, target_buffer, spp, seeds, denoise, temporal, display=None):
         from .native import RtrError
         self._rendering = True
         try:
@@ -259,11 +269,32 @@ class Renderer:
             hist = self._ctx.history(p) if temporal is not None else None
             try:
                 with self._ctx.accumulator(p, moments=denoise is not None) as acc:
+                    if display is not None:
+                        import torch
+                        w, h = target_buffer.width, target_buffer.height
+                        d_lin = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda:%d" % self._ctx.device)
+                        d_rgb = torch.zeros((h, w, 3), dtype=torch.uint8, device=d_lin.device)
+                        torch.cuda.synchronize(d_lin.device)  # the library works on a stream of its own
                     for k, (cam, seed) in enumerate(zip(cameras, seeds)):
                         if self._cancel_requested:
                             return
                         self._ctx.set_camera(cam)
                         acc.reset(seed)
+                        if display is not None:  # the device chain: nothing below waits but the copy of the bytes
+                            acc.render(spp, blocking=False)
+                            if temporal is not None:
+                                acc.denoise_temporal_into(hist, d_lin.data_ptr(), w, None, denoise, temporal)
+                            elif denoise is not None:
+                                acc.denoise_into(d_lin.data_ptr(), w, None, denoise)
+                            else:
+                                acc.resolve_into(d_lin.data_ptr(), w)
+                            self._ctx.display_into(d_lin.data_ptr(), w, w, h, d_rgb.data_ptr(), display)
+                            self._ctx.synchronize()
+                            if self._ctx.stats()["cancelled"]:
+                                return
+                            target_buffer.display_rgb8 = d_rgb.cpu().numpy()
+                            yield k
+                            continue
                         try:
                             acc.render(spp)
                         except RtrError as e:
