@@ -22,6 +22,12 @@ int rtr_test_hits(rtr_context* ctx, rtr_hit_record* recs, int64_t n);
 int rtr_test_materials(rtr_context* ctx, rtr_mat_record* recs, int64_t n);
 int rtr_test_lights(rtr_context* ctx, rtr_light_record* recs, int64_t n);
 int rtr_test_li(rtr_context* ctx, const rtr_render_params* params, rtr_li_record* recs, int64_t n);
+/* rtr_test_hits through the closest-hit cast of the FLAT kernels (cast_closest<RT_TRAV_FLAT> or, in a scene with guarded
+ * references, <RT_TRAV_FLAT_GUARD>), which the megakernel runs on flat scenes and no query or per-ray kernel does: the flat
+ * scan, then the hit record from the scene's finish records (rtr_finish_record) where it has them.  with_uv: compute
+ * (u, v) as a scene with image textures would.  *used_finish (may be NULL): whether the uploaded scene has finish
+ * records.  RTR_ERR_UNSUPPORTED where no flat kernel runs the scene (or rtr_test_reference_order is on). */
+int rtr_test_flat_hits(rtr_context* ctx, rtr_hit_record* recs, int64_t n, int with_uv, int32_t* used_finish);
 
 /* Which kernel instantiation the context's last render call launched, recorded on the host as it was enqueued.
  * Megakernel: k_mega<integrator, trav, ms, sorted, accum> (accum: 0 one-shot, 1 accumulator pass, 2 accumulator pass
@@ -53,11 +59,28 @@ typedef struct rtr_scene_plan {
     int32_t n_tie_refs, n_guard_refs;          /* references that carry RT_TIE_FLAG / RT_GUARD_FLAG */
     int32_t pick_trav;                         /* RT_TRAV_* pick_trav chooses for `flags` */
     int32_t mega_trav, mega_ms, mega_sorted, mega_pair; /* the MegaVariant: k_mega<integrator, trav, ms, sorted, ., pair> */
+    int32_t n_finish;                          /* finish records: n_refs, or 0 for a scene that gets none */
 } rtr_scene_plan;
+/* The finish record of a reference (csrc/rt_device.h: struct FFin): what the flat kernels fetch to build the hit record
+ * of a hit on it.  A scene gets them when it is flat (flat_scene or flat_guarded), every transform chain of its instances
+ * has at most two ops, and no reference is a moving sphere or sits under more than 31 wrappers.
+ * The reference's hit record is: the primitive's own hit() tail on the ray taken through level 0, then level 1; then the
+ * epilogue of level 1 and of level 0 (translate::hit / rotate_y::hit after the child's hit); then front ^= flip. */
+typedef struct rtr_finish_record {
+    int32_t kind;    /* 0, 1, 2: rectangle with its normal along x, y, z (yz_rect, xz_rect, xy_rect); 3: sphere */
+    int32_t material;
+    int32_t levels;  /* bits 0-1: transforms above the primitive (0..2); bit 2: level 0, the OUTERMOST, is a rotate_y (else a
+                        translate); bit 3: level 1 is a rotate_y */
+    int32_t flip;    /* parity of the flip_face wrappers outside the outermost transform (of all of them without a level):
+                        those inside are overwritten by the set_face_normal of the level above them */
+    double op[2][3]; /* per level: the translate's offset, or the rotate_y's sin, cos, 0; zero where absent */
+    double g[4];     /* sphere: centre, radius; rectangle: a0 a1 b0 b1 */
+} rtr_finish_record; /* 96 bytes */
 /* ref_flags (may be NULL when cap is 0) receives the `reserved` word of the first min(cap, n_refs) reference records:
- * visiting order | RT_TIE_FLAG | RT_GUARD_FLAG.  Returns RTR_OK or the validator's status for a scene it rejects. */
+ * visiting order | RT_TIE_FLAG | RT_GUARD_FLAG; finish (may be NULL when finish_cap is 0) the first min(finish_cap,
+ * n_finish) finish records, in reference order.  Returns RTR_OK or the validator's status for a scene it rejects. */
 int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t flags, rtr_scene_plan* out,
-                        int32_t* ref_flags, int64_t cap);
+                        int32_t* ref_flags, int64_t cap, rtr_finish_record* finish, int64_t finish_cap);
 
 /* Make rtr_test_hits (which takes no render params) use the reference-order traversal. */
 int rtr_test_reference_order(rtr_context* ctx, int on);

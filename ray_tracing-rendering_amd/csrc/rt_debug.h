@@ -15,6 +15,7 @@ struct rtr_debug_view {
     int device, n_cus, n_materials;
     int trav;           /* RT_TRAV_* template value of the per-ray kernels for a call with `flags` (per_ray_trav, rtr_capi.hip) */
     size_t stack_bytes; /* LDS traversal stack per workgroup of that traversal */
+    int flat_trav;      /* RT_TRAV_FLAT / RT_TRAV_FLAT_GUARD where the megakernel of such a call runs a flat kernel, else -1 */
 };
 /* the kernels the last render call launched, recorded on the host when they are enqueued (no device work) */
 struct rtr_debug_kernel {
@@ -40,12 +41,14 @@ struct rtr_debug_plan {
     int32_t guarded_program, top_tree, needs_uv, n_material_types, shared_div, pair_cast;
     int32_t n_steps, n_visits, n_refs, fast_stack_words, walk_stack_words, n_tie_refs, n_guard_refs;
     int32_t pick_trav, mega_trav, mega_ms, mega_sorted, mega_pair;
+    int32_t n_finish;
 };
 extern "C" {
 /* validator + lower_scene + pick_trav + mega_variant for `integrator` and render `flags`; ref_flags[0 .. min(cap, n_refs))
- * receives rtr_node::reserved of every reference record.  Returns the validator's status. */
+ * receives rtr_node::reserved of every reference record, finish[0 .. min(finish_cap, n_finish)) the finish records
+ * (struct FFin, 96 bytes each).  Returns the validator's status. */
 int rtr_debug_scene_plan(const rtr_scene_desc* scene, int integrator, int flags, rtr_debug_plan* out, size_t size_of_out,
-                         int32_t* ref_flags, int64_t cap);
+                         int32_t* ref_flags, int64_t cap, void* finish, int64_t finish_cap);
 int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t size_of_view);
 int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);

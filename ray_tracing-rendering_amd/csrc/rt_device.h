@@ -307,6 +307,7 @@ struct DScene {
     const struct FGuard* fguard; /* boxes of the guarded steps (FStep kind 3) */
     int32_t n_fvisit;        /* visits of the traversal machine's flattened program (rt_machine.h) */
     const struct FVisit* fvisit;
+    const struct FFin* ffin; /* finish record per reference (see FFin); null: the scene has none, fast_finish's own loads */
 };
 
 /*
@@ -375,6 +376,25 @@ struct FRef {
     int32_t n_exit;
     int32_t pad;        /* host side: visiting order (copied into fprim[].reserved) */
 };
+/* Finish record of a reference: all fast_finish needs to build the hit record of (reference, t), in ONE 96-byte fetch of
+ * six 16-byte loads issued together -- the primitive's kind and material, the transform chain of its instance (at most
+ * RT_INST_XF_INLINE levels, outermost first as in FInst::xf_f) and what the hit() tail of the primitive reads.  Lowering
+ * makes the array for flat scenes whose chains all fit, without moving spheres and RT_EXIT_LONG codes (rt_lower.h:
+ * build_finish); the flat kernels read it, every other kernel keeps FInst + fprim.
+ * `flip`: of the flip_face wrappers above the reference only the parity of those OUTSIDE the outermost translate / rotate_y
+ * reaches the record -- every level's epilogue ends in set_face_normal, which assigns `front` outright, and flip_face
+ * touches nothing but `front` (hittable.h:19-22,168).  Without a level that is the parity of all of them. */
+struct alignas(16) FFin {
+    int32_t kind;   /* 0, 1, 2: a rectangle whose normal is the x, y, z axis (yz_, xz_, xy_rect); RT_FIN_SPHERE: a sphere */
+    int32_t mat;    /* material index */
+    int32_t levels; /* bits 0-1: number of levels; RT_FIN_ROT0 / RT_FIN_ROT1: level 0 (the outermost) / level 1 is a rotate_y */
+    int32_t flip;   /* 1: front is inverted at the end */
+    double op[2][3]; /* per level: translate offset, or sin, cos, 0 */
+    double g[4];    /* sphere: centre, radius; rectangle: a0 a1 b0 b1 (read for (u,v) only) */
+};
+#define RT_FIN_SPHERE 3
+#define RT_FIN_ROT0 4
+#define RT_FIN_ROT1 8
 /* One INNER node of an instance's box tree: the boxes of both children next to their links, so a
  * traversal step costs one 64-byte record.  A link >= 0 is another inner node; a negative link is a
  * leaf, -1 - ((first_reference << 3) | (count - 1)), count <= 8.  The tree is built with a binned
@@ -650,15 +670,19 @@ RT_DEV void wrapper_epilogue(const rtr_node& n, V3 d, Hit& rec) {
     }
 }
 /* the ray translate::hit / rotate_y::hit pass down (hittable.h:53,128-138) */
-RT_DEV void wrapper_enter(int type, const double* f, V3& o, V3& d) {
-    if (type == RTR_NODE_TRANSLATE) {
-        o = sub(o, ld3(f));
+/* (one text for every caller: `rot` = a rotate_y with f0 = sin, f1 = cos, else a translate by (f0, f1, f2)) */
+RT_DEV void xf_enter(bool rot, Real f0, Real f1, Real f2, V3& o, V3& d) {
+    if (!rot) {
+        o = sub(o, mk(f0, f1, f2));
     } else {
-        const Real s = f[0], c = f[1];
+        const Real s = f0, c = f1;
         const Real ox = c * o.x - s * o.z, oz = s * o.x + c * o.z;
         const Real dx = c * d.x - s * d.z, dz = s * d.x + c * d.z;
         o.x = ox, o.z = oz, d.x = dx, d.z = dz;
     }
+}
+RT_DEV void wrapper_enter(int type, const double* f, V3& o, V3& d) {
+    xf_enter(type != RTR_NODE_TRANSLATE, f[0], f[1], f[2], o, d);
 }
 
 /* defined below (order-free traversal of compiled sub-scenes) */
@@ -673,7 +697,7 @@ RT_DEV FSub sub_scene0(const DScene& sc) {
     s.pad[0] = s.pad[1] = 0;
     return s;
 }
-template <bool UV>
+template <bool UV, bool FLAT = false>
 RT_DEV void fast_finish(const DScene& sc, V3 o, V3 d, Real time, Real t, int ref, int inst, Hit& rec);
 
 /*
@@ -1692,12 +1716,12 @@ __device__ __forceinline__ void fast_finish_long(const DScene& sc, V3 o, V3 d, R
 }
 /* translate::hit / rotate_y::hit / flip_face::hit after the child hit, from a transform op instead of a node record
  * (hittable.h:58-61,142-155,168: the arithmetic of wrapper_epilogue) */
-RT_DEV void xf_epilogue(int type, const double* f, V3 wd, Hit& rec) {
-    if (type == RTR_NODE_TRANSLATE) {
-        rec.p = add(rec.p, ld3(f));
+RT_DEV void xf_exit(bool rot, Real f0, Real f1, Real f2, V3 wd, Hit& rec) {
+    if (!rot) {
+        rec.p = add(rec.p, mk(f0, f1, f2));
         set_face_normal(rec, wd, rec.n);
     } else {
-        const Real s = f[0], c = f[1];
+        const Real s = f0, c = f1;
         V3 p = rec.p, nn = rec.n;
         p.x = c * rec.p.x + s * rec.p.z;
         p.z = -s * rec.p.x + c * rec.p.z;
@@ -1707,12 +1731,64 @@ RT_DEV void xf_epilogue(int type, const double* f, V3 wd, Hit& rec) {
         set_face_normal(rec, wd, nn);
     }
 }
+RT_DEV void xf_epilogue(int type, const double* f, V3 wd, Hit& rec) {
+    xf_exit(type != RTR_NODE_TRANSLATE, f[0], f[1], f[2], wd, rec);
+}
+/* fast_finish of the flat kernels from the reference's finish record (struct FFin): one fetch, no loop over wrapper codes.
+ * The operations are those of fast_finish below, operand for operand (xf_enter / xf_exit are what wrapper_enter / xf_epilogue
+ * call; `rot` differs from lane to lane); an absent level is skipped, never multiplied through
+ * as an identity (0 * dx + 1 * dz would turn -0 into +0). */
+template <bool UV>
+RT_DEV void fast_finish_flat(const FFin* ffin, V3 o, V3 d, Real t, int ref, Hit& rec) {
+    FFin F = ld_const(ffin, ref);
+    /* every word is wanted here: the six loads leave together instead of sinking below the tests that read the header */
+    asm volatile("" : "+v"(F.kind), "+v"(F.mat), "+v"(F.levels), "+v"(F.flip));
+    asm volatile("" : "+v"(F.op[0][0]), "+v"(F.op[0][1]), "+v"(F.op[0][2]), "+v"(F.op[1][0]), "+v"(F.op[1][1]), "+v"(F.op[1][2]));
+    asm volatile("" : "+v"(F.g[0]), "+v"(F.g[1]), "+v"(F.g[2]), "+v"(F.g[3]));
+    const int n_lev = F.levels & 3;
+    const bool rot0 = (F.levels & RT_FIN_ROT0) != 0, rot1 = (F.levels & RT_FIN_ROT1) != 0;
+    /* the ray as each level passed it down: after level 0, after level 1 (only directions matter to the epilogues) */
+    V3 lo = o, ld = d, d1 = d;
+    if (n_lev > 0) {
+        xf_enter(rot0, F.op[0][0], F.op[0][1], F.op[0][2], lo, ld);
+        d1 = ld;
+        if (n_lev > 1) xf_enter(rot1, F.op[1][0], F.op[1][1], F.op[1][2], lo, ld);
+    }
+    rec.t = t;
+    if (F.kind != RT_FIN_SPHERE) { /* rect_fill */
+        if (UV) {
+            const Real oa = F.kind == 0 ? lo.y : lo.x, da = F.kind == 0 ? ld.y : ld.x;
+            const Real ob = F.kind == 2 ? lo.y : lo.z, db = F.kind == 2 ? ld.y : ld.z;
+            const Real a = oa + t * da, b = ob + t * db;
+            rec.u = (a - F.g[0]) / (F.g[1] - F.g[0]);
+            rec.v = (b - F.g[2]) / (F.g[3] - F.g[2]);
+        }
+        const V3 outward = mk(F.kind == 0 ? 1.0 : 0.0, F.kind == 1 ? 1.0 : 0.0, F.kind == 2 ? 1.0 : 0.0);
+        set_face_normal(rec, ld, outward);
+        rec.p = add(lo, scl(t, ld));
+    } else { /* sphere_fill */
+        rec.p = add(lo, scl(t, ld));
+        const V3 outward = divs(sub(rec.p, mk(F.g[0], F.g[1], F.g[2])), F.g[3]);
+        set_face_normal(rec, ld, outward);
+        if (UV) sphere_uv(outward, rec.u, rec.v);
+    }
+    rec.mat = F.mat;
+    /* each level's set_face_normal sees the ray that level passed DOWN (hittable.h:58-61,142-155: moved_r, rotated_r) */
+    if (n_lev > 1) xf_exit(rot1, F.op[1][0], F.op[1][1], F.op[1][2], ld, rec);
+    if (n_lev > 0) xf_exit(rot0, F.op[0][0], F.op[0][1], F.op[0][2], d1, rec);
+    rec.front = rec.front != (F.flip != 0);
+}
 /* The usual case -- a chain of at most two transforms -- needs the instance record (ops inline) and the primitive
  * record (geometry + wrapper code in f[9]): two independent loads, one round trip, where the generic form chases
- * FInst -> FXf, FRef -> fexit -> nodes per wrapper. */
-template <bool UV>
+ * FInst -> FXf, FRef -> fexit -> nodes per wrapper.  FLAT (the flat kernels): a scene with finish records takes those
+ * instead (fast_finish_flat); the branch is the scene's, the same for every wave. */
+template <bool UV, bool FLAT>
 RT_DEV void fast_finish(const DScene& sc, V3 o, V3 d, Real time, Real t, int ref, int inst, Hit& rec) {
     RT_REGION(RG_FINISH);
+    if (FLAT && sc.ffin != nullptr) {
+        fast_finish_flat<UV>(sc.ffin, o, d, t, ref, rec);
+        return;
+    }
     const FInst I = ld_const(sc.finst, inst);
     const rtr_node n = ld_const(sc.fprim, ref);
     unsigned long long code = (unsigned long long)__double_as_longlong(n.f[9]);
@@ -1920,9 +1996,9 @@ __device__ __forceinline__ bool cast_closest(const DScene& sc, V3 o, V3 d, Real 
         if (!trace_fast<false, !rt_is_flat(TRAV), false, TRAV == RT_TRAV_TOP, TRAV == RT_TRAV_FLAT_GUARD>(sc, sub_scene0(sc), o, d, time, tmin, tmax, ref, inst, st, 0))
             return false;
         if (UV_POSSIBLE && sc.needs_uv)
-            fast_finish<true>(sc, o, d, time, tmax, ref, inst, rec);
+            fast_finish<true, rt_is_flat(TRAV)>(sc, o, d, time, tmax, ref, inst, rec);
         else
-            fast_finish<false>(sc, o, d, time, tmax, ref, inst, rec);
+            fast_finish<false, rt_is_flat(TRAV)>(sc, o, d, time, tmax, ref, inst, rec);
         return true;
     }
     if (rt_is_program(TRAV)) {

@@ -485,9 +485,9 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                     Hit rec;
                     rec.u = 0, rec.v = 0;
                     if (MS == RT_MS_FULL && sc.needs_uv) /* (cast_closest's hit record) */
-                        fast_finish<true>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
+                        fast_finish<true, true>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
                     else
-                        fast_finish<false>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
+                        fast_finish<false, true>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
                     ps.thr = pk.get3(PK_THR);
                     ps.L = mk(0.0, 0.0, 0.0); /* see the split loop below: L + e is the reference's L += e */
                     ps.prev_bsdf_pdf = pk.get(PK_PDF);

@@ -42,6 +42,7 @@ struct LoweredScene {
     std::vector<rtr_node> prims; /* per reference: the node record with visiting order, exit code, guard words, tie flag */
     std::vector<FLeaf> leaves;
     std::vector<FMat> mats;
+    std::vector<FFin> finish;    /* per reference, or empty: the scene gets none (build_finish) */
     SceneFacts facts;
     DScene ds; /* every member that is not a device pointer; the others, and the padding, zero */
 };
@@ -375,6 +376,46 @@ inline bool pair_cast_allowed(const rtr_scene_desc* s, const CompiledScene& cs, 
     return true;
 }
 
+/* FFin of every reference of a flat scene, or nothing where some reference does not fit the record: an instance of
+ * sub-scene 0 with more than RT_INST_XF_INLINE transform ops, a moving sphere, an RT_EXIT_LONG code.  The two-bit wrapper
+ * code of build_prims is reduced to "levels, then one flip bit" (see FFin::flip). */
+inline std::vector<FFin> build_finish(const CompiledScene& cs, const std::vector<rtr_node>& prims, bool flat) {
+    std::vector<FFin> out;
+    if (!flat || !cs.ok || cs.subs.empty()) return out;
+    const FSub& sub0 = cs.subs[0];
+    out.assign(prims.size(), FFin{});
+    for (int ii = sub0.inst_first; ii < sub0.inst_first + sub0.n_inst; ++ii) {
+        const FInst& I = cs.inst[ii];
+        if (I.n_xf > RT_INST_XF_INLINE) return {};
+        for (int r = I.ref_first; r < I.ref_first + I.n_ref; ++r) {
+            const rtr_node& n = prims[r];
+            unsigned long long code;
+            std::memcpy(&code, &n.f[9], 8);
+            if (n.type == RTR_NODE_MOVING_SPHERE || code == RT_EXIT_LONG) return {};
+            FFin F{};
+            F.kind = n.type == RTR_NODE_SPHERE ? RT_FIN_SPHERE : (n.type == RTR_NODE_YZ_RECT ? 0 : (n.type == RTR_NODE_XZ_RECT ? 1 : 2));
+            F.mat = n.a;
+            F.levels = I.n_xf;
+            for (int k = 0; k < I.n_xf; ++k) {
+                if (I.xf_type[k] == RTR_NODE_ROTATE_Y) F.levels |= k == 0 ? RT_FIN_ROT0 : RT_FIN_ROT1;
+                for (int q = 0; q < 3; ++q) F.op[k][q] = I.xf_f[k][q];
+            }
+            int left = I.n_xf, flips = 0; /* levels not yet left, flip_face wrappers since the last one */
+            for (; code != 0; code >>= 2) {
+                if ((code & 3) == 2)
+                    ++flips;
+                else
+                    --left, flips = 0;
+            }
+            if (left != 0) return {}; /* (the code names every level of the chain once) */
+            F.flip = flips & 1;
+            for (int q = 0; q < 4; ++q) F.g[q] = n.f[q];
+            out[(size_t)r] = F;
+        }
+    }
+    return out;
+}
+
 /* the material and light class: lean_materials, quad_lights_only, n_material_types, n_materials */
 inline void material_facts(const rtr_scene_desc* s, SceneFacts& f) {
     f.n_materials = s->n_materials;
@@ -456,6 +497,7 @@ inline LoweredScene lower_scene(const rtr_scene_desc* s, rtr_scene_info& info) {
     d.shared_div = rtc::shared_div_allowed(s, cs);
     d.pair_cast = rtc::pair_cast_allowed(s, cs, d, f.flat_scene);
     f.top_tree = d.top_root0 >= 0, f.needs_uv = info.needs_uv != 0, f.pair_cast = d.pair_cast != 0;
+    L.finish = rtc::build_finish(cs, L.prims, f.flat_scene || f.flat_guarded);
     rtc::material_facts(s, f);
     f.uv_order_dependent = rtc::uv_order_dependent(s, info);
     L.mats = rtc::build_materials(s);

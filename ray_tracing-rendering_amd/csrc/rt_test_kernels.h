@@ -44,6 +44,33 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_hits(const DScene sc, rtr_hi
     recs[k] = r;
 }
 
+/* the closest-hit cast of the flat kernels, cast_closest<RT_TRAV_FLAT / RT_TRAV_FLAT_GUARD>: the flat scan and the hit record
+ * from the scene's finish records (fast_finish_flat), or from FInst + fprim where it has none */
+template <int TRAV>
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_flat_hits(const DScene sc, rtr_hit_record* recs, long long n) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    rtr_hit_record r = recs[k];
+    uint32_t rng = r.rng_in;
+    Hit rec;
+    rec.u = rec.v = __builtin_nan("");
+    rec.mat = -1;
+    rec.t = 0, rec.p = mk(0, 0, 0), rec.n = mk(0, 0, 0), rec.front = false;
+    const bool h = cast_closest<TRAV>(sc, ld3(r.o), ld3(r.d), r.time, rec, rng, st, r.t_min, r.t_max);
+    r.rng_out = rng;
+    r.hit = h;
+    r.front_face = h ? (int)rec.front : 0;
+    r.material = h ? rec.mat : -1;
+    r.pad = 0;
+    r.t = h ? rec.t : 0;
+    r.p[0] = h ? rec.p.x : 0, r.p[1] = h ? rec.p.y : 0, r.p[2] = h ? rec.p.z : 0;
+    r.n[0] = h ? rec.n.x : 0, r.n[1] = h ? rec.n.y : 0, r.n[2] = h ? rec.n.z : 0;
+    r.u = h ? rec.u : 0, r.v = h ? rec.v : 0;
+    recs[k] = r;
+}
+
 __global__ void __launch_bounds__(RTR_BLOCK) k_test_materials(const DScene sc, rtr_mat_record* recs, long long n) {
     const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
     if (k >= n) return;

@@ -32,11 +32,11 @@ struct DevBuf {
  * frees them as an array, so a new one needs its declaration here and its line in rtr_upload_scene, nothing else */
 struct SceneBufs {
     DevBuf nodes, kids, mats, tex, perlin, images, imgbytes, lights;
-    DevBuf finst, fxf, fref, fexit, fbvh, fsub, fscan, fguard, fstep, fvisit, fprim, fleaf, fmat, dscene;
+    DevBuf finst, fxf, fref, fexit, fbvh, fsub, fscan, fguard, fstep, fvisit, fprim, fleaf, fmat, ffin, dscene;
     DevBuf* begin() { return &nodes; }
     DevBuf* end() { return begin() + sizeof(SceneBufs) / sizeof(DevBuf); }
 };
-static_assert(sizeof(SceneBufs) == 22 * sizeof(DevBuf), "SceneBufs holds DevBufs only");
+static_assert(sizeof(SceneBufs) == 23 * sizeof(DevBuf), "SceneBufs holds DevBufs only");
 
 } // namespace
 
@@ -898,6 +898,8 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
     if ((rc = put(c, b.fprim, L.prims, d.fprim))) return rc;
     if ((rc = put(c, b.fleaf, L.leaves, d.fleaf))) return rc;
     if ((rc = put(c, b.fmat, L.mats, d.fmat))) return rc;
+    if ((rc = put(c, b.ffin, L.finish, d.ffin))) return rc;
+    if (L.finish.empty()) d.ffin = nullptr; /* (an earlier scene's buffer may still be there: null means "no records") */
     if ((rc = upload(c, b.dscene, &d, sizeof(DScene)))) return rc;
     c->info = info;
     c->facts = L.facts;
@@ -1833,11 +1835,16 @@ int rtr_debug_view_get(rtr_context* c, int flags, rtr_debug_view* v, size_t size
     v->n_materials = c->facts.n_materials;
     v->trav = per_ray_trav(c->facts, c->info, flags, true); /* the unit kernels walk what the megakernel walks */
     v->stack_bytes = stack_bytes(c->facts, c->info, v->trav);
+    /* mega_variant's choice for MIS / RR: a flat scene keeps RT_TRAV_FLAT, a guarded one takes its kernel unless a top tree does */
+    const int picked = pick_trav(c->facts, c->info, flags);
+    v->flat_trav = picked == RT_TRAV_FLAT ? RT_TRAV_FLAT
+                   : (picked == RT_TRAV_FAST && c->facts.flat_guarded && !c->facts.top_tree ? RT_TRAV_FLAT_GUARD : -1);
     return RTR_OK;
 }
 int rtr_debug_scene_plan(const rtr_scene_desc* s, int integrator, int flags, rtr_debug_plan* out, size_t size, int32_t* ref_flags,
-                         int64_t cap) {
+                         int64_t cap, void* finish, int64_t finish_cap) {
     if (!out || size != sizeof(rtr_debug_plan) || cap < 0 || (cap > 0 && !ref_flags)) return RTR_ERR_INVALID;
+    if (finish_cap < 0 || (finish_cap > 0 && !finish)) return RTR_ERR_INVALID;
     Validator v;
     v.s = s;
     rtr_scene_info info{};
@@ -1855,7 +1862,9 @@ int rtr_debug_scene_plan(const rtr_scene_desc* s, int integrator, int flags, rtr
                           f.uv_order_dependent, f.machine_ok, f.guarded_program, f.top_tree, f.needs_uv, f.n_material_types,
                           L.ds.shared_div, L.ds.pair_cast, (int32_t)L.steps.size(), (int32_t)L.visits.size(),
                           (int32_t)L.prims.size(), f.fast_stack_words, info.stack_words + f.walk_extra_words, ties, guards,
-                          trav, m.trav, m.ms, m.sorted, m.pair};
+                          trav, m.trav, m.ms, m.sorted, m.pair, (int32_t)L.finish.size()};
+    if (finish_cap > 0 && !L.finish.empty())
+        std::memcpy(finish, L.finish.data(), sizeof(FFin) * (size_t)std::min<int64_t>(finish_cap, (int64_t)L.finish.size()));
     return RTR_OK;
 }
 int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {

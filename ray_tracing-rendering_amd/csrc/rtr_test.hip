@@ -114,6 +114,29 @@ int rtr_test_hits(rtr_context* c, rtr_hit_record* recs, int64_t n) {
     return end(c, v.stream, t, recs, n, sizeof *recs);
 }
 
+int rtr_test_flat_hits(rtr_context* c, rtr_hit_record* recs, int64_t n, int with_uv, int32_t* used_finish) {
+    rtr_debug_view v;
+    TestState* t;
+    int rc = begin(c, recs, n, sizeof *recs, v, t);
+    if (rc) return rc;
+    if (v.flat_trav < 0) return fail(c, RTR_ERR_UNSUPPORTED, "no flat kernel runs this scene");
+    if (used_finish) *used_finish = v.ds.ffin != nullptr;
+    if (n == 0) return RTR_OK;
+    TCHK(c, hipSetDevice(v.device));
+    DScene ds = v.ds;
+    ds.needs_uv = with_uv ? 1 : 0;
+    auto* d = static_cast<rtr_hit_record*>(t->buf);
+    const size_t lds = v.stack_bytes;
+    if (!dispatch_trav(TravSet<RT_TRAV_FLAT, RT_TRAV_FLAT_GUARD>{}, v.flat_trav, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            if ((rc = set_lds(c, k_test_flat_hits<T>, lds))) return;
+            hipLaunchKernelGGL(k_test_flat_hits<T>, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, ds, d, (long long)n);
+        }))
+        return fail(c, RTR_ERR_UNSUPPORTED, "no unit kernel for traversal " + std::to_string(v.flat_trav));
+    if (rc) return rc;
+    return end(c, v.stream, t, recs, n, sizeof *recs);
+}
+
 int rtr_test_materials(rtr_context* c, rtr_mat_record* recs, int64_t n) {
     rtr_debug_view v;
     TestState* t;
@@ -167,10 +190,11 @@ int rtr_test_last_kernel(rtr_context* c, rtr_kernel_record* out, size_t size) {
 }
 
 int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t flags, rtr_scene_plan* out, int32_t* ref_flags,
-                        int64_t cap) {
+                        int64_t cap, rtr_finish_record* finish, int64_t finish_cap) {
     static_assert(sizeof(rtr_scene_plan) == sizeof(rtr_debug_plan), "one layout");
+    static_assert(sizeof(rtr_finish_record) == sizeof(FFin), "one layout");
     return rtr_debug_scene_plan(scene, integrator, flags, reinterpret_cast<rtr_debug_plan*>(out), sizeof(rtr_debug_plan),
-                                ref_flags, cap);
+                                ref_flags, cap, finish, finish_cap);
 }
 
 int rtr_test_reference_order(rtr_context* c, int on) {

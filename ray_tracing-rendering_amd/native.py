@@ -34,7 +34,7 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
-                "rtr_test_temporal_planes", "rtr_test_scene_plan")
+                "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits")
 _TEST_LIB = None
 
 
@@ -57,7 +57,12 @@ class ScenePlanC(C.Structure):
         "fast_ok", "has_media", "flat_scene", "flat_guarded", "lean_materials", "quad_lights_only", "uv_order_dependent",
         "machine_ok", "guarded_program", "top_tree", "needs_uv", "n_material_types", "shared_div", "pair_cast", "n_steps",
         "n_visits", "n_refs", "fast_stack_words", "walk_stack_words", "n_tie_refs", "n_guard_refs", "pick_trav", "mega_trav",
-        "mega_ms", "mega_sorted", "mega_pair")]
+        "mega_ms", "mega_sorted", "mega_pair", "n_finish")]
+
+
+# rtr_finish_record of include/rtr_hip_test.h
+FINISH_DTYPE = np.dtype([("kind", "<i4"), ("material", "<i4"), ("levels", "<i4"), ("flip", "<i4"), ("op", "<f8", (2, 3)),
+                         ("g", "<f8", (4,))])
 
 
 class RtrError(RuntimeError):
@@ -176,7 +181,9 @@ def test_lib():
     T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
     T.rtr_test_temporal_planes.argtypes = [vp] + [C.c_int32] * 6 + [C.POINTER(A.CameraC), C.POINTER(A.CameraC), C.c_int,
                                                                     C.POINTER(A.TemporalParamsC)] + [vp] * 8
-    T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64]
+    T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64,
+                                      vp, C.c_int64]
+    T.rtr_test_flat_hits.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
     _TEST_LIB = T
     return T
 
@@ -200,17 +207,21 @@ def validate_scene(scene):
 def scene_plan(scene, integrator=4, flags=0):
     """rtr_test_scene_plan (include/rtr_hip_test.h; no GPU needed): what lowering finds out about ``scene`` and the kernel
     a megakernel render with ``integrator`` and ``flags`` would run, as a dict of the rtr_scene_plan members plus
-    ``ref_flags``, the ``reserved`` word of every reference record (int32 array).  Raises RtrError for a rejected scene."""
+    ``ref_flags``, the ``reserved`` word of every reference record (int32 array), and ``finish``, the finish records
+    (``FINISH_DTYPE`` array, one per reference; empty for a scene that gets none).  Raises RtrError for a rejected scene."""
     T = test_lib()
     d = scene.desc()
     plan = ScenePlanC()
-    rc = T.rtr_test_scene_plan(C.byref(d), int(integrator), int(flags), C.byref(plan), None, 0)
+    rc = T.rtr_test_scene_plan(C.byref(d), int(integrator), int(flags), C.byref(plan), None, 0, None, 0)
     if rc != 0:
         raise RtrError(rc, "scene rejected")
     ref_flags = np.zeros(plan.n_refs, dtype=np.int32)
-    T.rtr_test_scene_plan(C.byref(d), int(integrator), int(flags), C.byref(plan), ref_flags.ctypes.data, len(ref_flags))
+    finish = np.zeros(plan.n_finish, dtype=FINISH_DTYPE)
+    T.rtr_test_scene_plan(C.byref(d), int(integrator), int(flags), C.byref(plan), ref_flags.ctypes.data, len(ref_flags),
+                          finish.ctypes.data, len(finish))
     out = {name: int(getattr(plan, name)) for name, _ in ScenePlanC._fields_}
     out["ref_flags"] = ref_flags
+    out["finish"] = finish
     return out
 
 
@@ -628,6 +639,14 @@ class Context:
             1 if have else 0, C.byref(tp), color.ctypes.data, q.ctypes.data, count.ctypes.data, feat.ctypes.data,
             hist.ctypes.data, c.ctypes.data, var.ctypes.data, new.ctypes.data))
         return c, var, new
+
+    def flat_hits(self, recs, with_uv=True):
+        """rtr_test_flat_hits (include/rtr_hip_test.h): ``HIT_DTYPE`` records through the closest-hit cast of the flat
+        kernels.  Returns (records, whether the scene has finish records); RtrError where no flat kernel runs the scene."""
+        out = np.ascontiguousarray(recs.copy())
+        used = C.c_int32(0)
+        self._chk(test_lib().rtr_test_flat_hits(self._h, out.ctypes.data, len(out), 1 if with_uv else 0, C.byref(used)))
+        return out, bool(used.value)
 
     # device unit kernels over golden-vector records (include/rtr_hip_test.h)
     def test_records(self, kind, recs, params=None):
