@@ -82,6 +82,33 @@ typedef struct rtr_finish_record {
 int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t flags, rtr_scene_plan* out,
                         int32_t* ref_flags, int64_t cap, rtr_finish_record* finish, int64_t finish_cap);
 
+/* The frame shape lowering gives every instance of the scene's sub-scene 0 (csrc/rt_device.h: FInst::shape), which the
+ * pair cast switches on: 0 none, 1 T, 2 R, 3 T.R (translate outermost), 4 R.T, 5 other (more than two ops, or two of a
+ * kind).  shapes receives the first min(cap, *n_instances) of them.  Needs no context and no GPU. */
+int rtr_test_pair_frames(const rtr_scene_desc* scene, int32_t* shapes, int64_t cap, int32_t* n_instances);
+/* Host build of the pair cast's frame block (csrc/rt_device.h: pair_frame) on one ray pair per record, for a frame of
+ * `shape` (0..4) with the operands ops[0..2] of the outer op and ops[3..5] of the inner one (translate: offset; rotate_y:
+ * sin, cos, 0; unused ones are ignored).  same_frame: pair_frame's origins and directions equal, in every bit, the ray
+ * taken down op by op as translate::hit / rotate_y::hit do (restated in the test library), d.y untouched.  fo, fd: what
+ * pair_frame made of ray A.  Needs no context and no GPU. */
+typedef struct rtr_pair_frame_record {
+    double ao[3], ad[3], bo[3], bd[3]; /* in */
+    double fo[3], fd[3];               /* out */
+    int32_t same_frame, pad;           /* out */
+} rtr_pair_frame_record;
+int rtr_test_pair_frame_host(int32_t shape, const double* ops, rtr_pair_frame_record* recs, int64_t n);
+/* trace_pair of the MIS pair-cast kernels on one ray pair per lane -- A: closest hit in [0.001, a_tmax], B: any hit in
+ * [0.001, b_tmax] -- next to the two single casts of the flat kernels for the same lanes, trace_fast<false> for A and
+ * trace_fast<true> for B.  Lanes of one wave share the wave-level votes of the pair cast, as in a render.
+ * RTR_ERR_UNSUPPORTED unless the uploaded scene is a pair-cast scene (rtr_scene_plan::pair_cast). */
+typedef struct rtr_pair_record {
+    double ao[3], ad[3], a_tmax, bo[3], bd[3], b_tmax; /* in */
+    double a_t, s_a_t;                                  /* out: t of A's hit (a_tmax without one), pair / single */
+    int32_t a_ref, a_inst, b_hit;                       /* out, pair cast: A's reference and instance (-1: none), B hit */
+    int32_t s_a_ref, s_a_inst, s_b_hit;                 /* out, single casts */
+} rtr_pair_record; /* 152 bytes */
+int rtr_test_pair_cast(rtr_context* ctx, rtr_pair_record* recs, int64_t n);
+
 /* Make rtr_test_hits (which takes no render params) use the reference-order traversal. */
 int rtr_test_reference_order(rtr_context* ctx, int on);
 

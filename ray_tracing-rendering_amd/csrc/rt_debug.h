@@ -49,6 +49,8 @@ extern "C" {
  * (struct FFin, 96 bytes each).  Returns the validator's status. */
 int rtr_debug_scene_plan(const rtr_scene_desc* scene, int integrator, int flags, rtr_debug_plan* out, size_t size_of_out,
                          int32_t* ref_flags, int64_t cap, void* finish, int64_t finish_cap);
+/* FInst::shape (RT_SHAPE_*) of the first min(cap, *n_inst) instances of sub-scene 0 after lower_scene; host only */
+int rtr_debug_frame_shapes(const rtr_scene_desc* scene, int32_t* shapes, int64_t cap, int32_t* n_inst);
 int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t size_of_view);
 int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);

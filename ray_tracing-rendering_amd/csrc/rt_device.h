@@ -26,6 +26,7 @@
 #endif
 
 #define RT_DEV __device__ __forceinline__
+#define RT_HD __host__ __device__ __forceinline__ /* also run by host-side test hooks */
 
 typedef double Real;
 
@@ -339,7 +340,7 @@ struct FInst {
      * (RT_INST_RUNS clear).  Type codes beyond the node types: RT_RUN_BOX, and RT_RUN_GUARDED in scenes with guarded
      * references (read by their own kernel variant, RT_TRAV_FLAT_GUARD). */
     int32_t scan_first;
-    int32_t pad;
+    int32_t shape;           /* RT_SHAPE_*: what the first ops of the chain are, for trace_pair's frame setup (rt_lower.h) */
     uint64_t runs;
     /* the first two transform ops of the chain, inline (a copy of fxf[xf_first ...]): translate(rotate_y(...)) of the
      * reference's scenes comes in with the record itself instead of through two more dependent loads */
@@ -361,6 +362,15 @@ struct FInst {
 /* the chain leaves the direction's y as it is in the world frame (translate leaves the whole direction, rotate_y its y):
  * the frame's reciprocal of d.y and its rcp_safe verdict are the world frame's, bit for bit (trace_pair) */
 #define RT_INST_KEEP_Y 8
+/* FInst::shape -- the chain of an instance as ONE value, outermost op first, so that trace_pair decides once per frame
+ * which straight-line block takes both rays into it.  T = translate, R = rotate_y; the operands are FInst::xf_f.  OTHER:
+ * more than two ops, or two of a kind -- the generic loop over the ops. */
+#define RT_SHAPE_NONE 0
+#define RT_SHAPE_T 1
+#define RT_SHAPE_R 2
+#define RT_SHAPE_TR 3 /* translate(rotate_y(.)): the ray is translated, then rotated */
+#define RT_SHAPE_RT 4 /* rotate_y(translate(.)) */
+#define RT_SHAPE_OTHER 5
 struct FXf {
     int32_t type; /* RTR_NODE_TRANSLATE (f = offset) or RTR_NODE_ROTATE_Y (f[0] = sin, f[1] = cos) */
     int32_t pad;
@@ -1592,12 +1602,66 @@ RT_DEV void pair_runs(const DScene& sc, const FInst& I, const PairRay& A, Real t
         ref += cnt;
     }
 }
+/* ---- frames of the pair cast -----------------------------------------------------------------------------------------
+ * Both rays of a pair into the frame of an instance whose chain has one of the shapes RT_SHAPE_NONE .. RT_SHAPE_RT, as
+ * ONE straight-line block per shape: the shape is wave-uniform and decided once, A and B go through the block together,
+ * and every arm writes the frame's values directly.  The arithmetic is xf_enter's, operand for operand and op by op
+ * (translate: o - offset; rotate_y: c x - s z and s x + c z, mul, mul, add unfused), so the bits are those of the
+ * generic loop.  No shape is run as another one with identity operands (0 * z turns a -0 into +0).
+ * d.y is no output: translate and rotate_y both leave it alone, the frame's d.y IS the world ray's (RT_INST_KEEP_Y,
+ * which lowering asks of every instance of a pair-cast scene), and the runs read it from there.  What a shape leaves
+ * alone besides -- the origin under NONE, o.y under R, d.x and d.z under NONE and T -- is copied. */
+struct PairFrame {
+    V3 ao, bo;              /* origins in the frame */
+    Real adx, adz, bdx, bdz; /* direction components in the frame (d.y: the world ray's) */
+};
+RT_HD void pair_rot(Real s, Real c, Real x, Real z, Real& rx, Real& rz) {
+    rx = c * x - s * z;
+    rz = s * x + c * z;
+}
+RT_HD PairFrame pair_frame(int shape, const double* f0, const double* f1, V3 ao, V3 ad, V3 bo, V3 bd) {
+    PairFrame F;
+    switch (shape) {
+    case RT_SHAPE_T:
+        F.ao.x = ao.x - f0[0], F.bo.x = bo.x - f0[0];
+        F.ao.y = ao.y - f0[1], F.bo.y = bo.y - f0[1];
+        F.ao.z = ao.z - f0[2], F.bo.z = bo.z - f0[2];
+        F.adx = ad.x, F.adz = ad.z, F.bdx = bd.x, F.bdz = bd.z;
+        break;
+    case RT_SHAPE_R:
+        pair_rot(f0[0], f0[1], ao.x, ao.z, F.ao.x, F.ao.z), pair_rot(f0[0], f0[1], bo.x, bo.z, F.bo.x, F.bo.z);
+        F.ao.y = ao.y, F.bo.y = bo.y;
+        pair_rot(f0[0], f0[1], ad.x, ad.z, F.adx, F.adz), pair_rot(f0[0], f0[1], bd.x, bd.z, F.bdx, F.bdz);
+        break;
+    case RT_SHAPE_TR: {
+        const Real ax = ao.x - f0[0], bx = bo.x - f0[0];
+        const Real az = ao.z - f0[2], bz = bo.z - f0[2];
+        F.ao.y = ao.y - f0[1], F.bo.y = bo.y - f0[1];
+        pair_rot(f1[0], f1[1], ax, az, F.ao.x, F.ao.z), pair_rot(f1[0], f1[1], bx, bz, F.bo.x, F.bo.z);
+        pair_rot(f1[0], f1[1], ad.x, ad.z, F.adx, F.adz), pair_rot(f1[0], f1[1], bd.x, bd.z, F.bdx, F.bdz);
+        break;
+    }
+    case RT_SHAPE_RT: {
+        Real ax, az, bx, bz;
+        pair_rot(f0[0], f0[1], ao.x, ao.z, ax, az), pair_rot(f0[0], f0[1], bo.x, bo.z, bx, bz);
+        pair_rot(f0[0], f0[1], ad.x, ad.z, F.adx, F.adz), pair_rot(f0[0], f0[1], bd.x, bd.z, F.bdx, F.bdz);
+        F.ao.x = ax - f1[0], F.bo.x = bx - f1[0];
+        F.ao.y = ao.y - f1[1], F.bo.y = bo.y - f1[1];
+        F.ao.z = az - f1[2], F.bo.z = bz - f1[2];
+        break;
+    }
+    default: /* RT_SHAPE_NONE */
+        F.ao = ao, F.bo = bo;
+        F.adx = ad.x, F.adz = ad.z, F.bdx = bd.x, F.bdz = bd.z;
+        break;
+    }
+    return F;
+}
 /* A: closest hit from (ao, ad) at `atime` -> a_ref, a_inst, a_tmax (in: the ray's t_max); B: any hit from (bo, bd) within
  * b_tmax -> b_ref >= 0.  Sub-scene 0 of a DScene::pair_cast scene only.
- * The reciprocal of the world direction's y is made once per cast: every frame whose chain leaves d.y as it is
- * (RT_INST_KEEP_Y: the same operand, so the same reciprocal and the same rcp_safe verdict) takes it from there.  Carrying
- * x and z as well, for the frames without a rotate_y, put ten VGPRs of the lean kernel back into scratch: those two
- * are made per frame.  RayDiv::fast of a ray in a frame is origin_ok && __all(every lane's
+ * The reciprocal of the world direction's y and its rcp_safe verdict are made once per cast and serve every frame
+ * (RT_INST_KEEP_Y: the same operand); x and z are made per frame (carrying them for the frames without a rotate_y put
+ * ten VGPRs of the lean kernel back into scratch).  RayDiv::fast of a ray in a frame is origin_ok && __all(every lane's
  * verdicts), and __all(p) && __all(q) == __all(p & q): the per-lane verdicts are combined first and voted on once per
  * frame for both rays, and only a frame that fails that vote votes per ray to choose the single-ray scans. */
 __device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
@@ -1614,16 +1678,19 @@ __device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real 
         RT_REGION(RG_PAIR_SETUP);
         const FInst I = ld_const(sc.finst, ii);
         PairRay A, B;
-        A.o = ao, A.d = ad, B.o = bo, B.d = bd;
-        const int n_xf = I.n_xf;
-        if (n_xf) {
+        if (I.shape != RT_SHAPE_OTHER) {
+            const PairFrame F = pair_frame(I.shape, I.xf_f[0], I.xf_f[1], ao, ad, bo, bd);
+            A.o = F.ao, B.o = F.bo;
+            A.d = mk(F.adx, ad.y, F.adz), B.d = mk(F.bdx, bd.y, F.bdz);
+        } else { /* the generic loop over the ops (none of them touches d.y) */
+            A.o = ao, A.d = ad, B.o = bo, B.d = bd;
             wrapper_enter(I.xf_type[0], I.xf_f[0], A.o, A.d);
             wrapper_enter(I.xf_type[0], I.xf_f[0], B.o, B.d);
-            if (n_xf > 1) {
+            if (I.n_xf > 1) {
                 wrapper_enter(I.xf_type[1], I.xf_f[1], A.o, A.d);
                 wrapper_enter(I.xf_type[1], I.xf_f[1], B.o, B.d);
             }
-            for (int k = RT_INST_XF_INLINE; k < n_xf; ++k) {
+            for (int k = RT_INST_XF_INLINE; k < I.n_xf; ++k) {
                 const FXf x = ld_const(sc.fxf, I.xf_first + k);
                 wrapper_enter(x.type, x.f, A.o, A.d);
                 wrapper_enter(x.type, x.f, B.o, B.d);
@@ -1632,14 +1699,8 @@ __device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real 
         A.q.guard = B.q.guard = false; /* t_min = 0.001 */
         A.q.rx = rcp_refined(A.d.x), A.q.rz = rcp_refined(A.d.z);
         B.q.rx = rcp_refined(B.d.x), B.q.rz = rcp_refined(B.d.z);
-        bool sa = rcp_safe(A.d.x) & rcp_safe(A.d.z), sb = rcp_safe(B.d.x) & rcp_safe(B.d.z); /* every divisor: this lane */
-        if (I.flags & RT_INST_KEEP_Y) {
-            A.q.ry = way, B.q.ry = wby;
-            sa = sa & wa_y, sb = sb & wb_y;
-        } else {
-            A.q.ry = rcp_refined(A.d.y), B.q.ry = rcp_refined(B.d.y);
-            sa = sa & rcp_safe(A.d.y), sb = sb & rcp_safe(B.d.y);
-        }
+        A.q.ry = way, B.q.ry = wby;
+        bool sa = rcp_safe(A.d.x) & rcp_safe(A.d.z) & wa_y, sb = rcp_safe(B.d.x) & rcp_safe(B.d.z) & wb_y; /* every divisor: this lane */
         A.q.a = A.q.ra = B.q.a = B.q.ra = 0;
         if (I.flags & RT_INST_SPHERES) { /* raydiv_spheres */
             A.q.a = len2(A.d), B.q.a = len2(B.d);

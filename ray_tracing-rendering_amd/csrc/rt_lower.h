@@ -356,6 +356,29 @@ inline bool shared_div_allowed(const rtr_scene_desc* s, const CompiledScene& cs)
     return !getenv("RTR_NO_SHARED_DIV"); /* experiments: the plain divisions */
 }
 
+/* FInst::shape of a chain (RT_SHAPE_*): which straight-line block of trace_pair takes a ray pair into the frame */
+inline int frame_shape(const FInst& I) {
+    if (I.n_xf == 0) return RT_SHAPE_NONE;
+    if (I.n_xf > RT_INST_XF_INLINE) return RT_SHAPE_OTHER;
+    int code = 0; /* two bits per op, outermost first: 1 translate, 2 rotate_y */
+    for (int k = 0; k < I.n_xf; ++k) {
+        if (I.xf_type[k] == RTR_NODE_TRANSLATE) {
+            code = code << 2 | 1;
+        } else if (I.xf_type[k] == RTR_NODE_ROTATE_Y) {
+            code = code << 2 | 2;
+        } else {
+            return RT_SHAPE_OTHER;
+        }
+    }
+    switch (code) {
+    case 1: return RT_SHAPE_T;
+    case 2: return RT_SHAPE_R;
+    case 1 << 2 | 2: return RT_SHAPE_TR;
+    case 2 << 2 | 1: return RT_SHAPE_RT;
+    default: return RT_SHAPE_OTHER; /* T T, R R: rare enough to keep the generic loop */
+    }
+}
+
 /* trace_pair's scenes (DScene::pair_cast): flat, lit (without lights no shadow ray is ever cast, and the pair walk
  * would test a dummy ray against every record: scene 7, 7 515 -> 6 122 Msamples/s), few enough instances that no
  * instance box is tested, every instance a packed scan without moving spheres, shared divisions allowed; the others
@@ -366,6 +389,7 @@ inline bool pair_cast_allowed(const rtr_scene_desc* s, const CompiledScene& cs, 
     for (int k = 0; k < d.n_finst; ++k) {
         const FInst& I = cs.inst[k];
         if (!(I.flags & RT_INST_RUNS)) return false;
+        if (!(I.flags & RT_INST_KEEP_Y)) return false; /* trace_pair reads every frame's d.y from the world ray */
         for (uint64_t runs = I.runs; runs != 0; runs >>= RT_RUN_BITS) {
             const int type = RTR_NODE_SPHERE + (int)((runs >> RT_RUN_COUNT_BITS) & 7);
             if (type != RTR_NODE_SPHERE && type != RTR_NODE_XY_RECT && type != RTR_NODE_XZ_RECT && type != RTR_NODE_YZ_RECT &&
@@ -472,6 +496,7 @@ inline LoweredScene lower_scene(const rtr_scene_desc* s, rtr_scene_info& info) {
     any_tie |= rtc::flag_ties_across_instances(cs, L.prims);
     L.leaves = rtc::build_leaf_records(cs, L.prims);
     rtc::build_scan_runs(cs, L.prims);
+    for (FInst& I : cs.inst) I.shape = rtc::frame_shape(I);
     f.fast_stack_words = cs.stack_words;
     /* (guarded references -- hollow spheres -- are tested by the generic loop of the kernels that know about ties: the
      * flat kernels carry neither) */

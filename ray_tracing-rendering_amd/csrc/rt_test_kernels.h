@@ -6,6 +6,7 @@
 #pragma once
 
 #include "rt_kernels.h"
+#include "rtr_hip_test.h" /* rtr_pair_record */
 #include "rtr_testrec.h"
 
 /* ---- device unit kernels over golden-vector records ---------------------------------------- */
@@ -68,6 +69,27 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_flat_hits(const DScene sc, r
     r.p[0] = h ? rec.p.x : 0, r.p[1] = h ? rec.p.y : 0, r.p[2] = h ? rec.p.z : 0;
     r.n[0] = h ? rec.n.x : 0, r.n[1] = h ? rec.n.y : 0, r.n[2] = h ? rec.n.z : 0;
     r.u = h ? rec.u : 0, r.v = h ? rec.v : 0;
+    recs[k] = r;
+}
+
+/* trace_pair on one ray pair per lane, and the single casts of the flat kernels (cast_closest / cast_any<RT_TRAV_FLAT>'s
+ * trace_fast instantiations) for the same lanes */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_pair(const DScene sc, rtr_pair_record* recs, long long n) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    rtr_pair_record r = recs[k];
+    Real a_t = r.a_tmax, b_t = r.b_tmax;
+    int a_ref, a_inst, b_ref;
+    trace_pair(sc, ld3(r.ao), ld3(r.ad), 0.0, a_t, a_ref, a_inst, ld3(r.bo), ld3(r.bd), b_t, b_ref, st);
+    Real s_t = r.a_tmax, sb_t = r.b_tmax;
+    int s_ref, s_inst, sb_ref, sb_inst;
+    trace_fast<false, false, false, false, false>(sc, sub_scene0(sc), ld3(r.ao), ld3(r.ad), 0.0, 0.001, s_t, s_ref, s_inst, st, 0);
+    trace_fast<true, false, true, false, false>(sc, sub_scene0(sc), ld3(r.bo), ld3(r.bd), 0.0, 0.001, sb_t, sb_ref, sb_inst, st, 0);
+    r.a_t = a_t, r.s_a_t = s_t;
+    r.a_ref = a_ref, r.a_inst = a_inst, r.b_hit = b_ref >= 0;
+    r.s_a_ref = s_ref, r.s_a_inst = s_inst, r.s_b_hit = sb_ref >= 0;
     recs[k] = r;
 }
 

@@ -1867,6 +1867,17 @@ int rtr_debug_scene_plan(const rtr_scene_desc* s, int integrator, int flags, rtr
         std::memcpy(finish, L.finish.data(), sizeof(FFin) * (size_t)std::min<int64_t>(finish_cap, (int64_t)L.finish.size()));
     return RTR_OK;
 }
+int rtr_debug_frame_shapes(const rtr_scene_desc* s, int32_t* shapes, int64_t cap, int32_t* n_inst) {
+    if (!n_inst || cap < 0 || (cap > 0 && !shapes)) return RTR_ERR_INVALID;
+    Validator v;
+    v.s = s;
+    rtr_scene_info info{};
+    if (int rc = v.run(&info)) return rc;
+    const LoweredScene L = lower_scene(s, info);
+    *n_inst = L.ds.n_finst;
+    for (int k = 0; k < L.ds.n_finst && k < cap; ++k) shapes[k] = L.cs.inst[(size_t)k].shape;
+    return RTR_OK;
+}
 int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {
     if (!c || !out || size != sizeof(rtr_debug_kernel)) return RTR_ERR_INVALID;
     *out = c->last_kernel;

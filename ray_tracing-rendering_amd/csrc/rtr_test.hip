@@ -10,6 +10,7 @@
 #include "rt_test_kernels.h"
 #include "rtr_hip_test.h"
 
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -195,6 +196,57 @@ int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t
     static_assert(sizeof(rtr_finish_record) == sizeof(FFin), "one layout");
     return rtr_debug_scene_plan(scene, integrator, flags, reinterpret_cast<rtr_debug_plan*>(out), sizeof(rtr_debug_plan),
                                 ref_flags, cap, finish, finish_cap);
+}
+
+int rtr_test_pair_frames(const rtr_scene_desc* scene, int32_t* shapes, int64_t cap, int32_t* n_instances) {
+    return rtr_debug_frame_shapes(scene, shapes, cap, n_instances);
+}
+
+int rtr_test_pair_frame_host(int32_t shape, const double* ops, rtr_pair_frame_record* recs, int64_t n) {
+    if (shape < RT_SHAPE_NONE || shape > RT_SHAPE_RT || !ops || n < 0 || (n > 0 && !recs)) return RTR_ERR_INVALID;
+    /* the chain op by op, as hittable.h:53,128-138 pass a ray down: 1 = translate, 2 = rotate_y */
+    const int kinds[5][2] = {{0, 0}, {1, 0}, {2, 0}, {1, 2}, {2, 1}};
+    auto enter = [&](V3& o, V3& d) {
+        for (int k = 0; k < 2; ++k) {
+            const double* f = ops + 3 * k;
+            if (kinds[shape][k] == 1) {
+                o.x = o.x - f[0], o.y = o.y - f[1], o.z = o.z - f[2];
+            } else if (kinds[shape][k] == 2) {
+                const double sn = f[0], cs = f[1];
+                const double ox = cs * o.x - sn * o.z, oz = sn * o.x + cs * o.z;
+                const double dx = cs * d.x - sn * d.z, dz = sn * d.x + cs * d.z;
+                o.x = ox, o.z = oz, d.x = dx, d.z = dz;
+            }
+        }
+    };
+    auto same = [](double a, double b) { return std::memcmp(&a, &b, 8) == 0; };
+    for (int64_t q = 0; q < n; ++q) {
+        rtr_pair_frame_record& r = recs[q];
+        V3 ao{r.ao[0], r.ao[1], r.ao[2]}, ad{r.ad[0], r.ad[1], r.ad[2]}, bo{r.bo[0], r.bo[1], r.bo[2]}, bd{r.bd[0], r.bd[1], r.bd[2]};
+        const PairFrame F = pair_frame(shape, ops, ops + 3, ao, ad, bo, bd);
+        V3 eao = ao, ead = ad, ebo = bo, ebd = bd;
+        enter(eao, ead), enter(ebo, ebd);
+        r.fo[0] = F.ao.x, r.fo[1] = F.ao.y, r.fo[2] = F.ao.z, r.fd[0] = F.adx, r.fd[1] = ad.y, r.fd[2] = F.adz;
+        r.same_frame = same(F.ao.x, eao.x) && same(F.ao.y, eao.y) && same(F.ao.z, eao.z) && same(F.bo.x, ebo.x) &&
+                       same(F.bo.y, ebo.y) && same(F.bo.z, ebo.z) && same(F.adx, ead.x) && same(F.adz, ead.z) &&
+                       same(F.bdx, ebd.x) && same(F.bdz, ebd.z) && same(ad.y, ead.y) && same(bd.y, ebd.y);
+        r.pad = 0;
+    }
+    return RTR_OK;
+}
+
+int rtr_test_pair_cast(rtr_context* c, rtr_pair_record* recs, int64_t n) {
+    rtr_debug_view v;
+    TestState* t;
+    int rc = begin(c, recs, n, sizeof *recs, v, t);
+    if (rc) return rc;
+    if (!v.ds.pair_cast) return fail(c, RTR_ERR_UNSUPPORTED, "the uploaded scene is no pair-cast scene");
+    if (n == 0) return RTR_OK;
+    TCHK(c, hipSetDevice(v.device));
+    const size_t lds = v.stack_bytes;
+    if ((rc = set_lds(c, k_test_pair, lds))) return rc;
+    hipLaunchKernelGGL(k_test_pair, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, v.ds, static_cast<rtr_pair_record*>(t->buf), (long long)n);
+    return end(c, v.stream, t, recs, n, sizeof *recs);
 }
 
 int rtr_test_reference_order(rtr_context* c, int on) {

@@ -34,7 +34,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
-                "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits")
+                "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
+                "rtr_test_pair_frame_host", "rtr_test_pair_cast")
 _TEST_LIB = None
 
 
@@ -63,6 +64,15 @@ class ScenePlanC(C.Structure):
 # rtr_finish_record of include/rtr_hip_test.h
 FINISH_DTYPE = np.dtype([("kind", "<i4"), ("material", "<i4"), ("levels", "<i4"), ("flip", "<i4"), ("op", "<f8", (2, 3)),
                          ("g", "<f8", (4,))])
+
+
+# rtr_pair_frame_record and rtr_pair_record of include/rtr_hip_test.h
+PAIR_FRAME_DTYPE = np.dtype([("ao", "<f8", (3,)), ("ad", "<f8", (3,)), ("bo", "<f8", (3,)), ("bd", "<f8", (3,)),
+                             ("fo", "<f8", (3,)), ("fd", "<f8", (3,)), ("same_frame", "<i4"), ("pad", "<i4")])
+PAIR_DTYPE = np.dtype([("ao", "<f8", (3,)), ("ad", "<f8", (3,)), ("a_tmax", "<f8"), ("bo", "<f8", (3,)), ("bd", "<f8", (3,)),
+                       ("b_tmax", "<f8"), ("a_t", "<f8"), ("s_a_t", "<f8"), ("a_ref", "<i4"), ("a_inst", "<i4"),
+                       ("b_hit", "<i4"), ("s_a_ref", "<i4"), ("s_a_inst", "<i4"), ("s_b_hit", "<i4")])
+FRAME_SHAPES = ("none", "T", "R", "TR", "RT", "other")  # FInst::shape (csrc/rt_device.h: RT_SHAPE_*)
 
 
 class RtrError(RuntimeError):
@@ -184,6 +194,9 @@ def test_lib():
     T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64,
                                       vp, C.c_int64]
     T.rtr_test_flat_hits.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
+    T.rtr_test_pair_frames.argtypes = [C.POINTER(A.SceneDescC), vp, C.c_int64, C.POINTER(C.c_int32)]
+    T.rtr_test_pair_frame_host.argtypes = [C.c_int32, vp, vp, C.c_int64]
+    T.rtr_test_pair_cast.argtypes = [vp, vp, C.c_int64]
     _TEST_LIB = T
     return T
 
@@ -223,6 +236,33 @@ def scene_plan(scene, integrator=4, flags=0):
     out["ref_flags"] = ref_flags
     out["finish"] = finish
     return out
+
+
+def pair_frames(scene):
+    """rtr_test_pair_frames (include/rtr_hip_test.h; no GPU needed): the frame shape of every instance of ``scene``'s
+    sub-scene 0 as a list of ``FRAME_SHAPES`` names.  Raises RtrError for a rejected scene."""
+    T = test_lib()
+    d = scene.desc()
+    n = C.c_int32(0)
+    rc = T.rtr_test_pair_frames(C.byref(d), None, 0, C.byref(n))
+    if rc != 0:
+        raise RtrError(rc, "scene rejected")
+    shapes = np.zeros(n.value, dtype=np.int32)
+    T.rtr_test_pair_frames(C.byref(d), shapes.ctypes.data, len(shapes), C.byref(n))
+    return [FRAME_SHAPES[k] for k in shapes]
+
+
+def pair_frame_host(shape, ops, ao, ad, bo, bd):
+    """rtr_test_pair_frame_host (include/rtr_hip_test.h; no GPU needed): the host build of the pair cast's frame block for
+    a frame of ``shape`` (a ``FRAME_SHAPES`` name but "other") with operands ``ops`` ((2, 3): outer, inner) on n ray pairs
+    given as (n, 3) arrays.  Returns the ``PAIR_FRAME_DTYPE`` records."""
+    recs = np.zeros(len(ao), dtype=PAIR_FRAME_DTYPE)
+    recs["ao"], recs["ad"], recs["bo"], recs["bd"] = ao, ad, bo, bd
+    ops = np.ascontiguousarray(ops, dtype=np.float64).reshape(6)
+    rc = test_lib().rtr_test_pair_frame_host(FRAME_SHAPES.index(shape), ops.ctypes.data, recs.ctypes.data, len(recs))
+    if rc != 0:
+        raise RtrError(rc, "rtr_test_pair_frame_host")
+    return recs
 
 
 def denoise_defaults(**overrides):
@@ -647,6 +687,15 @@ class Context:
         used = C.c_int32(0)
         self._chk(test_lib().rtr_test_flat_hits(self._h, out.ctypes.data, len(out), 1 if with_uv else 0, C.byref(used)))
         return out, bool(used.value)
+
+    def pair_cast(self, ao, ad, bo, bd, a_tmax=np.inf, b_tmax=np.inf):
+        """rtr_test_pair_cast (include/rtr_hip_test.h): trace_pair on n ray pairs ((n, 3) arrays; t_max scalars or (n,))
+        next to the two single casts of the flat kernels.  Returns the ``PAIR_DTYPE`` records."""
+        recs = np.zeros(len(ao), dtype=PAIR_DTYPE)
+        recs["ao"], recs["ad"], recs["bo"], recs["bd"] = ao, ad, bo, bd
+        recs["a_tmax"], recs["b_tmax"] = a_tmax, b_tmax
+        self._chk(test_lib().rtr_test_pair_cast(self._h, recs.ctypes.data, len(recs)))
+        return recs
 
     # device unit kernels over golden-vector records (include/rtr_hip_test.h)
     def test_records(self, kind, recs, params=None):
