@@ -255,6 +255,14 @@ typedef struct rtr_render_params {
  * rectangles, boxes and spheres (scenes 21 and 23); this flag asks for the split casts there, and is reported in
  * flags_in_effect where it changed the kernel.  Same image and segment counts bit for bit. */
 #define RTR_FLAG_SPLIT_CASTS 8
+/* Megakernel only: one workgroup per (tile, chunk of samples), every lane on one pixel until the slowest pixel of its wave
+ * has finished the chunk.  A one-shot render with the pair cast otherwise runs a persistent grid whose lanes pull (pixel,
+ * chunk) jobs from a launch-wide queue as they finish (images up to 65 535 x 65 535; accumulator passes keep the static
+ * grid).  The jobs are the static grid's partial sums, summed in the same order and added in the same order: same image
+ * and counts bit for bit, so this flag is the A/B switch of tests and measurements; reported in flags_in_effect where it
+ * changed the kernel.  The environment variable RTR_QUEUE_WORKGROUPS=n, read at every launch, caps the persistent grid
+ * at n workgroups (a test hook, like RTR_GUIDED for the guided chunk split). */
+#define RTR_FLAG_STATIC_GRID 16
 
 typedef struct rtr_render_stats {
     uint64_t samples;          /* camera samples finished                               */

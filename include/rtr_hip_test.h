@@ -109,6 +109,19 @@ typedef struct rtr_pair_record {
 } rtr_pair_record; /* 152 bytes */
 int rtr_test_pair_cast(rtr_context* ctx, rtr_pair_record* recs, int64_t n);
 
+/* Host builds of the job queue's own device functions (csrc/rt_render.h: queue_block, queue_pack / queue_unpack), which
+ * k_mega_queue -- the persistent-grid twin of the pair-cast kernels -- decodes block ids and keeps its per-lane job with.
+ * rtr_test_queue_blocks_host: blocks 0 .. n-1 of a launch over n_tiles owned tiles with `chunks` partial sums of `spp`
+ * samples (n_big, big_spp, small_spp: the guided split, all 0 for equal chunks); ref_s0 / ref_s1 are chunk_range of the
+ * decoded chunk.  rtr_test_queue_pack_host: packs (i, j, s_end) into the two halves of the parked word and unpacks them
+ * again into out[0..2].  Neither needs a context or a GPU. */
+typedef struct rtr_queue_block_record {
+    int32_t slot, quarter, chunk, s0, s1, ref_s0, ref_s1, pad;
+} rtr_queue_block_record;
+int rtr_test_queue_blocks_host(int32_t n_tiles, int32_t spp, int32_t chunks, int32_t n_big, int32_t big_spp, int32_t small_spp,
+                               rtr_queue_block_record* recs, int64_t n);
+int rtr_test_queue_pack_host(int32_t i, int32_t j, int32_t s_end, uint32_t* lo, uint32_t* hi, int32_t* out);
+
 /* Make rtr_test_hits (which takes no render params) use the reference-order traversal. */
 int rtr_test_reference_order(rtr_context* ctx, int on);
 

@@ -28,6 +28,7 @@ FLAG_REFERENCE_ORDER = 1
 FLAG_WF_PERSISTENT = 2
 FLAG_SORTED_SHADING = 4
 FLAG_SPLIT_CASTS = 8
+FLAG_STATIC_GRID = 16
 ACCUM_MOMENTS = 1  # rtr_accum_create_ex: keep per-pixel second moments (adaptive sampling)
 
 NODE_DTYPE = np.dtype([("type", "<i4"), ("a", "<i4"), ("b", "<i4"), ("reserved", "<i4"), ("f", "<f8", (10,))])

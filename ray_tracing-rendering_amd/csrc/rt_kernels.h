@@ -7,6 +7,9 @@
  *              (in-lane path regeneration), so the 64 lanes of a wave stay busy although path
  *              lengths differ (P(k=4)=0.45, long tail).  Samples of a pixel are
  *              summed in sample order like renderer.h:72-79.
+ *  k_mega_queue  the pair-cast loop of k_mega on a persistent grid: a lane whose (pixel, chunk) job is over pulls the next
+ *              one from a launch-wide queue instead of idling until the slowest lane of its wave is through; same
+ *              partial sums, same image (what a one-shot render of a pair-cast scene runs).
  *  k_resolve   adds the per-chunk partial sums of a pixel in chunk order, scales by 1/spp
  *              (renderer.h:131) and stores linear mean radiance.
  *  k_li        Integrator::Li of single camera samples or caller-given rays, one lane each (rtr_li_samples / rtr_li_rays).
@@ -661,6 +664,277 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
 }
 
 
+/* ---- k_mega_queue: the pair-cast loop of k_mega<..., ACC = 0, PAIR = true> over a launch-wide job queue ----------------
+ * k_mega's pair loop runs until the slowest of a wave's 64 pixels has finished its chunk of samples; the other lanes cast
+ * dummy rays meanwhile (a quarter more iterations than rays on the headline).  Here the launch is a persistent grid, and
+ * a lane whose job -- one pixel of one (tile, chunk) cell, rt_render.h: queue_block -- is over takes the next one: of
+ * the wave's current block, or of the block the wave fetches with ONE atomic add on the launch-wide counter `q_counter`
+ * (block ids >= n_blocks: the queue has run out, and the wave never asks again).  No spin loop, no barrier: the four
+ * waves of a workgroup never meet after they have started, and no wave waits for another.
+ *
+ * No sum changes.  A job has the cell, the sample range and the sample order of the static kernel, one lane sums it
+ * from start to end in PK_ACC and stores it where the static kernel stores it, so the image is that kernel's bit for
+ * bit in every chunk mode; only which lane of which wave computes a cell differs.
+ *
+ * Job switch, with the loop's own states: (1) the job's last sample ends: the lane is `done` and stops casting ray A;
+ * (2) in the next iteration the sample settles into PK_ACC; (3) later in that iteration the lane stores PK_ACC to its
+ * cell and adds 1 to the cell's completion word RenderK::done (k_resolve takes a cell whose word is RTR_BLOCK), clears
+ * PK_ACC, takes the next job and begins its first sample: one idle iteration per job.  A pixel outside the region, or
+ * an empty sample range, is a null job: it counts as finished when it is taken.  A lane that finds no job is done for
+ * good, and the loop ends as k_mega's does.
+ *
+ * State: the pixel (16 bits each) and the job's s_end share PK_PIXEL (queue_pack), read at a sample's end, where the
+ * camera ray needs the pixel anyway; the lane's cell lives in its traversal-stack word of LDS, which a flat scan never
+ * touches (-1: no job); the wave's block and its cursor are wave-uniform.  Nothing new is live across the pair cast.
+ *
+ * rtr_cancel(): the wave polls as k_mega does.  A wave that takes the cancel drops its jobs -- no lane of it stores or
+ * counts again, so their cells stay incomplete and their tiles untouched -- and adds 1 to stats[7]: here that word
+ * counts interrupted WAVES (inside the loop a wave always holds a job that is not stored yet). */
+struct QueueWave {
+    int block; /* the block the wave takes jobs from; -1: the queue has run out */
+    int next;  /* jobs of it that are taken */
+    unsigned long long samples; /* samples of the jobs the wave's lanes have taken (wave-uniform: a lane has no register
+                                   to count its own in); a cancel takes back what its dropped jobs had left */
+};
+/* Lanes with `need` take consecutive jobs, by their rank among those lanes, until each has a job with samples or the
+ * queue has run out; the wave-uniform loop fetches a block whenever the current one has none left.  true: the lane has a
+ * job (PK_PIXEL and *my_cell are set, `s` is its first sample); a lane in need that gets none has *my_cell = -1. */
+RT_DEV bool queue_take(const RenderK& P, uint32_t* __restrict__ q_counter, const int n_blocks, QueueWave& qw, bool need,
+                       const Park& pk, int* my_cell, int& s) {
+    bool got = false;
+    unsigned long long m = __ballot(need);
+    while (m) { /* wave-uniform */
+        if (qw.block >= 0 && qw.next == RT_QUEUE_JOBS) {
+            const int first = __builtin_ctzll(m);
+            uint32_t b = 0;
+            if ((int)__lane_id() == first) b = atomicAdd(q_counter, 1u);
+            b = (uint32_t)__builtin_amdgcn_readlane((int)b, first);
+            qw.block = b < (uint32_t)n_blocks ? (int)b : -1;
+            qw.next = 0;
+        }
+        if (qw.block < 0) {
+            if (need) *my_cell = -1;
+            break;
+        }
+        const QueueBlock qb = queue_block(P, qw.block);
+        const int tile = P.tile_ids[qb.slot];
+        const int tile_y = (P.tiles_y - 1) - tile / P.tiles_x; /* tile_pixel */
+        const int tile_x = tile % P.tiles_x;
+        const int cell = qb.slot * P.chunks + qb.chunk;
+        const int k = qw.next + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        bool now = false;
+        if (need && k < RT_QUEUE_JOBS) {
+            const int i = tile_x * 16 + (k & 15), j = tile_y * 16 + qb.quarter * 4 + (k >> 4);
+            if (i >= P.x0 && i < P.x1 && j >= P.y0 && j < P.y1 && qb.s0 < qb.s1) {
+                uint32_t lo, hi;
+                queue_pack(i, j, qb.s1, lo, hi);
+                pk.set2(PK_PIXEL, lo, hi);
+                *my_cell = cell;
+                s = qb.s0;
+                got = now = true, need = false;
+            } else {
+                atomicAdd(&P.done[cell], 1); /* a null job */
+            }
+        }
+        qw.samples += (unsigned long long)__builtin_popcountll(__ballot(now)) * (unsigned long long)(qb.s1 - qb.s0);
+        const int taken = qw.next + (int)__builtin_popcountll(m);
+        qw.next = taken < RT_QUEUE_JOBS ? taken : RT_QUEUE_JOBS;
+        m = __ballot(need);
+    }
+    return got;
+}
+
+template <int INTEG, int TRAV, int MS>
+__global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
+    k_mega_queue(const DScene* __restrict__ scp, const RenderK P, const int stack_words, uint32_t* __restrict__ q_counter,
+                 const int n_blocks) {
+    static_assert(mega_pairable(INTEG, TRAV), "no pair-cast variant of this kernel");
+    extern __shared__ int lds_stack[];
+    const DScene& sc = *scp;
+    const Stack st{lds_stack + threadIdx.x};
+    const Park pk{reinterpret_cast<double*>(lds_stack + stack_words * RTR_BLOCK) + threadIdx.x};
+    int* const my_cell = lds_stack + threadIdx.x; /* the lane's cell, in its stack word */
+#ifdef RTR_REGION_PROFILE
+    if (threadIdx.x < 4 * 2 * RT_PROF_REGIONS + 8) rt_prof_lds[threadIdx.x] = 0;
+    if (threadIdx.x + 256 < 4 * 2 * RT_PROF_REGIONS + 8) rt_prof_lds[threadIdx.x + 256] = 0;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) rt_prof_lds[4 * 2 * RT_PROF_REGIONS + (threadIdx.x >> 6) * 2] = __builtin_readcyclecounter();
+#endif
+    PathCounters cnt;
+    cnt.closest = 0, cnt.shadow = 0;
+    PathState ps;
+    uint32_t rng = 1;
+    int s = 0;
+    QueueWave qw{0, RT_QUEUE_JOBS, 0ull};
+    pk.set3(PK_ACC, mk(0.0, 0.0, 0.0));
+    pk.set2(PK_NCAST, 0u, 0u);
+    pk.set3(PK_L, mk(0.0, 0.0, 0.0));
+    *my_cell = -1;
+    bool done = !queue_take(P, q_counter, n_blocks, qw, true, pk, my_cell, s);
+    if (!done) {
+        uint32_t lo, hi;
+        int i, j, s_end;
+        pk.get2(PK_PIXEL, lo, hi);
+        queue_unpack(lo, hi, i, j, s_end);
+        camera_sample(sc, P, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
+        ps.depth = 0, ps.specular_bounce = false;
+        pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
+        pk.set(PK_PDF, 0.0);
+    }
+    uint32_t it = 0; /* iterations of the wave: wave-uniform */
+    bool pending = false; /* k_mega's pair loop: a shadow request is parked */
+    bool settle = false;  /* the sample in PK_L has ended */
+    V3 so = mk(0.0, 0.0, 0.0);
+    PhaseClocks clk;
+    while (!done || settle) {
+        RTR_CLK(other);
+        RT_REGION(RG_OTHER);
+        const bool cast_a = !done;
+        Real a_tmax = RT_INF, b_tmax = 0.0;
+        int a_ref, a_inst, b_ref;
+        V3 swi = mk(1.0, 1.0, 1.0);
+        RT_REGION(RG_COUNT);
+        {
+            uint32_t n_closest, n_shadow;
+            pk.get2(PK_NCAST, n_closest, n_shadow);
+            pk.set2(PK_NCAST, n_closest + (cast_a ? 1u : 0u), n_shadow + (pending ? 1u : 0u));
+        }
+        RT_REGION(RG_OTHER);
+        if (!cast_a) {
+            ps.ro = mk(0.0, 0.0, 0.0), ps.rd = mk(1.0, 1.0, 1.0), ps.tm = 0.0;
+            a_tmax = 0.0;
+        }
+        if (pending) {
+            swi = pk.get3(PK_SWI);
+            b_tmax = pk.get(PK_STMAX);
+        } else {
+            so = mk(0.0, 0.0, 0.0);
+        }
+        trace_pair(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
+        RTR_CLK(closest);
+        RT_REGION(RG_POLL);
+        const uint32_t cancel_word = cancel_poll_issue(P, it++);
+        RT_REGION(RG_SETTLE);
+        const bool lit = pending && b_ref < 0;
+        if (lit || settle) {
+            V3 L = pk.get3(PK_L);
+            if (lit) L = add(L, pk.get3(PK_CONTRIB)); /* mis_path_integrator.h:210-213 */
+            if (settle) {
+                pk.set3(PK_ACC, add(pk.get3(PK_ACC), L)); /* renderer.h:77-78 */
+                L = mk(0.0, 0.0, 0.0);
+                settle = false;
+            }
+            pk.set3(PK_L, L);
+        }
+        pending = false;
+        RTR_CLK(shadow);
+        bool begin = false; /* the lane starts sample s at the end of this iteration */
+        if (cast_a) {
+            bool ended;
+            if (a_ref < 0) {
+                RT_REGION(RG_MISS);
+                pk.set3(PK_L, add(pk.get3(PK_L), miss_radiance<INTEG, MS>(sc, pk.get3(PK_THR), ps.ro, ps.rd, ps.depth,
+                                                                      ps.specular_bounce, pk.get(PK_PDF))));
+                ended = true;
+            } else {
+                Hit rec;
+                rec.u = 0, rec.v = 0;
+                if (MS == RT_MS_FULL && sc.needs_uv) /* (cast_closest's hit record) */
+                    fast_finish<true, true>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
+                else
+                    fast_finish<false, true>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, rec);
+                ps.thr = pk.get3(PK_THR);
+                ps.L = mk(0.0, 0.0, 0.0);
+                ps.prev_bsdf_pdf = pk.get(PK_PDF);
+                const V3 wo = neg(unit(ps.rd));
+                ParkedReq rq{false, pk}; /* parked until the next pair cast */
+                const MatCtx mc = mat_prepare<MS>(sc, rec);
+                shade_a_mis<MS, INTEG>(sc, ps, rec, mc, wo, rng, rq);
+                pending = rq.valid;
+                const bool go = shade_b_mis<MS, INTEG>(sc, ps, rec, mc, wo, rng, P.rr_start);
+                RT_REGION(RG_PARK);
+                ps.ro = rec.p; /* next ray origin and shadow ray origin */
+                so = rec.p;
+                pk.set3(PK_THR, ps.thr);
+                if (ps.L.x != 0.0 || ps.L.y != 0.0 || ps.L.z != 0.0) pk.set3(PK_L, add(pk.get3(PK_L), ps.L));
+                pk.set(PK_PDF, ps.prev_bsdf_pdf);
+                ended = !go || ++ps.depth >= P.max_depth;
+            }
+            RTR_CLK(shade);
+            RT_REGION(RG_REGEN);
+            if (ended) {
+                settle = true;
+                ++s;
+                begin = true; /* (unless the job is over: the pixel's word says, below) */
+            }
+        }
+        /* a lane that was not casting has settled its job's last sample in this iteration: the job switch, step (3) */
+        const bool job_end = !cast_a && *my_cell >= 0;
+        if (__ballot(job_end)) { /* wave-uniform */
+            RT_REGION(RG_EXCHANGE);
+            if (job_end) {
+                uint32_t lo, hi;
+                pk.get2(PK_PIXEL, lo, hi);
+                const V3 acc = pk.get3(PK_ACC);
+                const int cell = *my_cell;
+                double* out = P.partial + (size_t)cell * 3 * RTR_BLOCK + ((lo >> 12) & 0xf0u) + (lo & 0xfu); /* tile_pixel's tid */
+                out[0] = acc.x;
+                out[RTR_BLOCK] = acc.y;
+                out[2 * RTR_BLOCK] = acc.z;
+                atomicAdd(&P.done[cell], 1);
+                pk.set3(PK_ACC, mk(0.0, 0.0, 0.0));
+            }
+            if (queue_take(P, q_counter, n_blocks, qw, job_end, pk, my_cell, s)) done = false, begin = true;
+        }
+        if (begin) {
+            uint32_t lo, hi;
+            int i, j, s_end;
+            pk.get2(PK_PIXEL, lo, hi);
+            queue_unpack(lo, hi, i, j, s_end);
+            done = s >= s_end;
+            if (!done) {
+                RT_REGION(RG_BEGIN);
+                camera_sample(sc, P, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
+                ps.depth = 0, ps.specular_bounce = false;
+                pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
+                pk.set(PK_PDF, 0.0);
+            }
+        }
+        RT_REGION(RG_POLL);
+        if (__any(cancel_poll_take(P, cancel_word))) { /* wave-uniform: every lane polled the same word */
+            const unsigned long long here = __ballot(1);
+            if ((int)__lane_id() == __builtin_ctzll(here)) atomicAdd(&P.stats[7], 1ull);
+            int left = 0; /* samples of the lane's job that have not ended */
+            if (*my_cell >= 0) {
+                uint32_t lo, hi;
+                pk.get2(PK_PIXEL, lo, hi);
+                left = (int)hi - s;
+            }
+            for (unsigned long long m = __ballot(left > 0); m; m &= m - 1) /* wave-uniform */
+                qw.samples -= (unsigned long long)__builtin_amdgcn_readlane(left, __builtin_ctzll(m));
+            *my_cell = -1; /* the wave's jobs are dropped (an ended sample still settles: the loop's condition) */
+            done = true;
+        }
+    }
+    pk.get2(PK_NCAST, cnt.closest, cnt.shadow);
+    clk.flush(P);
+#ifdef RTR_REGION_PROFILE
+    RT_REGION(RG_OTHER);
+    __syncthreads();
+    if (threadIdx.x < 2 * RT_PROF_REGIONS) {
+        unsigned long long v = 0;
+        for (int w = 0; w < 4; ++w) v += rt_prof_lds[w * 2 * RT_PROF_REGIONS + threadIdx.x];
+        if (v) atomicAdd(&P.stats[RT_PROF_BASE + threadIdx.x], v);
+    }
+#endif
+    unsigned long long b = wave_sum(cnt.closest), c = wave_sum(cnt.shadow);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&P.stats[0], qw.samples);
+        atomicAdd(&P.stats[1], b);
+        atomicAdd(&P.stats[2], c);
+    }
+}
+
 /* rtr_li_samples / rtr_li_rays: Integrator::Li (renderer/integrator.h:12-19) of n camera samples of the image P
  * describes, or of n caller-given rays; one lane each.  `in` per item: camera sample = (i, j, s) as three int32 in
  * the first 12 bytes; ray = rtr_li_ray.  `out` per item: radiance (3 doubles), rng state at exit, closest / shadow
@@ -855,8 +1129,10 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_resolve(const ResolveK R) {
     int i, j;
     bool active;
     tile_pixel(P, blockIdx.x, threadIdx.x, i, j, active);
-    for (int c = 0; c < P.chunks; ++c) /* wave-uniform: scalar loads */
-        if (!P.done[blockIdx.x * P.chunks + c]) return;
+    for (int c = 0; c < P.chunks; ++c) { /* wave-uniform: scalar loads */
+        const int d = P.done[blockIdx.x * P.chunks + c];
+        if (R.done_full ? d != R.done_full : !d) return;
+    }
     const bool packed = R.row_stride < 0;
     if (packed && threadIdx.x == 0) R.tile_done[blockIdx.x] = 1;
     if (!active) return;

@@ -25,7 +25,8 @@ struct LaunchedKernel {
     int phases = 0;  /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched */
 };
 
-/* the k_mega<integ, trav, ms, sorted, ACC, pair> a render runs (ACC follows from the call: MegaLaunch::accum) */
+/* the k_mega<integ, trav, ms, sorted, ACC, pair> a render runs (ACC follows from the call: MegaLaunch::accum; a one-shot
+ * render of a pair variant runs k_mega_queue<integ, trav, ms> instead unless RTR_FLAG_STATIC_GRID is set: MegaLaunch::queue) */
 struct MegaVariant {
     int integ, trav, ms; /* RTR_INTEGRATOR_*, RT_TRAV_* template value, RT_MS_* */
     bool sorted, pair;   /* the sorted instantiation (RTR_FLAG_SORTED_SHADING) / the pair-cast twin of a flat MIS kernel */
@@ -42,6 +43,12 @@ struct MegaLaunch {
     RenderK P;
     bool dry;           /* only what can fail without touching the stream: LDS attribute, occupancy query */
     int* blocks_per_cu; /* dry: resident workgroups per CU of the variant that would run */
+    /* the job-queue twin of a pair-cast variant (rt_kernels.h: k_mega_queue; accum = 0 only): a persistent grid of the
+     * workgroups the chip holds -- occupancy x n_cus, at most one per (tile, chunk), at most grid_cap if that is > 0 --
+     * whose waves pull blocks of jobs through the counter behind the completion words, P.done[n_tiles * chunks];
+     * the caller zeroes the words and the counter on the stream before the launch */
+    bool queue;
+    int n_cus, grid_cap;
 };
 /* return an rtr_status; `err` receives the text of a failure */
 int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err);

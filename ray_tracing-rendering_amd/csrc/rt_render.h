@@ -21,10 +21,11 @@ struct RenderK {
     int n_big, big_spp, small_spp;
     int integrator; /* RTR_INTEGRATOR_* (the wavefront's extend stage needs it for rays that miss) */
     double* partial;             /* [n_tiles*chunks][3][RTR_BLOCK] un-normalised sums */
-    unsigned long long* stats;   /* samples, closest segments, shadow segments; [7] = workgroups a cancel interrupted */
+    unsigned long long* stats;   /* samples, closest segments, shadow segments; [7] = workgroups (queue renders: waves) a cancel interrupted */
     const uint32_t* cancel;      /* rtr_cancel(): id of the newest render it covers; this render stops once *cancel >= render_id */
     uint32_t render_id;
-    int* done;                   /* [n_tiles*chunks]: 1 = the workgroup finished every sample of its chunk */
+    int* done;                   /* [n_tiles*chunks]: 1 = the workgroup finished every sample of its chunk; a queue render
+                                    (k_mega_queue): the jobs of the cell that have finished, RTR_BLOCK when all have */
     /* Accumulator passes (rtr_accum_*: k_mega<..., ACC = 1 | 2>, chunks = 1); unused elsewhere.  Workgroup b renders
      * the tile slot active[b] if b < *n_active (k_accum_plan wrote both on the device), samples [tile_s0[slot],
      * tile_s1[slot]); acc_in: [n_tiles][3][RTR_BLOCK] sums the pass continues instead of starting from 0.  ACC = 2 also
@@ -64,7 +65,7 @@ RT_DEV void camera_sample(const DScene& sc, const RenderK& P, int i, int j, int 
 }
 
 /* samples [s0, s1) of chunk c of a pixel */
-RT_DEV void chunk_range(const RenderK& P, int c, int& s0, int& s1) {
+RT_HD void chunk_range(const RenderK& P, int c, int& s0, int& s1) {
     if (P.small_spp == 0) {
         s0 = (int)((long long)c * P.spp / P.chunks);
         s1 = (int)((long long)(c + 1) * P.spp / P.chunks);
@@ -78,7 +79,7 @@ RT_DEV void chunk_range(const RenderK& P, int c, int& s0, int& s1) {
     if (c == P.chunks - 1) s1 = P.spp;
 }
 /* which (owned tile, chunk) workgroup `b` of a megakernel launch renders: big chunks of every tile first */
-RT_DEV void mega_work(const RenderK& P, int b, int& tile_slot, int& c) {
+RT_HD void mega_work(const RenderK& P, int b, int& tile_slot, int& c) {
     if (P.small_spp == 0) {
         tile_slot = b / P.chunks, c = b % P.chunks;
     } else if (b < P.n_tiles * P.n_big) {
@@ -87,6 +88,31 @@ RT_DEV void mega_work(const RenderK& P, int b, int& tile_slot, int& c) {
         const int n_small = P.chunks - P.n_big, q = b - P.n_tiles * P.n_big;
         tile_slot = q / n_small, c = P.n_big + q % n_small;
     }
+}
+
+/* The job queue of the pair-cast kernels (k_mega_queue).  A job is one pixel of one (tile, chunk) cell; a BLOCK is the
+ * 64 jobs of one wave-quarter of a tile (rows 4q .. 4q + 3, the pixels wave q of a static workgroup renders) for one
+ * chunk.  Blocks are numbered in the order mega_work gives workgroups: a launch has n_tiles * chunks * 4 of them, the
+ * big chunks of every tile first.  Job k of a block is pixel (k & 15, 4q + (k >> 4)) of the tile. */
+#define RT_QUEUE_JOBS 64 /* jobs per block */
+struct QueueBlock {
+    int slot, quarter, chunk; /* owned tile, wave-quarter of it, chunk */
+    int s0, s1;               /* chunk_range of the chunk */
+};
+RT_HD QueueBlock queue_block(const RenderK& P, int b) {
+    QueueBlock q;
+    mega_work(P, b >> 2, q.slot, q.chunk);
+    q.quarter = b & 3;
+    chunk_range(P, q.chunk, q.s0, q.s1);
+    return q;
+}
+/* what a lane keeps of its job in the parked word PK_PIXEL: the pixel, 16 bits each (a queue render's image is at most
+ * 65 535 wide and high), and the end of the job's sample range */
+RT_HD void queue_pack(int i, int j, int s_end, uint32_t& lo, uint32_t& hi) {
+    lo = (uint32_t)i | ((uint32_t)j << 16), hi = (uint32_t)s_end;
+}
+RT_HD void queue_unpack(uint32_t lo, uint32_t hi, int& i, int& j, int& s_end) {
+    i = (int)(lo & 0xffffu), j = (int)(lo >> 16), s_end = (int)hi;
 }
 
 RT_DEV unsigned long long wave_sum(unsigned long long v) {
@@ -101,6 +127,8 @@ struct ResolveK {
     long long row_stride; /* pixels per row of `out`; < 0: `out` is PACKED -- owned tile k of the call at out[k * 768 ...]
                              as 16 rows (lowest y first) of 16 pixels, and tile_done[k] = 1 once its sums are stored */
     unsigned char* tile_done;
+    int done_full; /* a chunk ran to the end when its word of r.done is nonzero (0), or equals this count: the jobs of a
+                      cell of a queue render (k_mega_queue), which count themselves there one by one */
 };
 
 /* rtr_accum_resolve: the accumulator's sums and sample counts (r.tile_ids = its owned tiles) -> packed tiles of linear

@@ -445,7 +445,7 @@ int params_check(rtr_context* c, const rtr_render_params* p) {
     if (p->tile_stride > 1 && (p->tile_first < 0 || p->tile_first >= p->tile_stride))
         return fail(c, RTR_ERR_INVALID, "tile_first must be in [0, tile_stride)");
     if (p->spp_chunks < 0 || p->spp_chunks > p->spp) return fail(c, RTR_ERR_INVALID, "spp_chunks must be in [0, spp]");
-    if (p->flags & ~(RTR_FLAG_REFERENCE_ORDER | RTR_FLAG_WF_PERSISTENT | RTR_FLAG_SORTED_SHADING | RTR_FLAG_SPLIT_CASTS)) return fail(c, RTR_ERR_INVALID, "unknown flag bits");
+    if (p->flags & ~(RTR_FLAG_REFERENCE_ORDER | RTR_FLAG_WF_PERSISTENT | RTR_FLAG_SORTED_SHADING | RTR_FLAG_SPLIT_CASTS | RTR_FLAG_STATIC_GRID)) return fail(c, RTR_ERR_INVALID, "unknown flag bits");
     if (p->pipeline < RTR_PIPELINE_AUTO || p->pipeline > RTR_PIPELINE_WAVEFRONT)
         return fail(c, RTR_ERR_INVALID, "unknown pipeline");
     return RTR_OK;
@@ -533,6 +533,13 @@ MegaVariant mega_variant(const SceneFacts& f, int integ, int trav, int flags, in
     return v;
 }
 
+/* Whether a render of variant `v` runs the job-queue twin of its pair-cast kernel (rt_kernels.h: k_mega_queue): one-shot
+ * renders only; the pixel is packed into 16 + 16 bits and block ids are int32, beyond that the static grid stays. */
+bool mega_queue(const MegaVariant& v, const RenderK& P, int flags) {
+    return v.pair && P.tile_s0 == nullptr && !(flags & RTR_FLAG_STATIC_GRID) && P.W <= 65535 && P.H <= 65535 &&
+           (long long)P.n_tiles * P.chunks * 4 < (1ll << 31);
+}
+
 /* `dry`: only what can fail without touching the stream (the LDS size check / attribute, the occupancy query) */
 int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, bool dry, int* blocks_per_cu, int flags,
                 int* flags_in_effect = nullptr, LaunchedKernel* launched = nullptr) {
@@ -549,6 +556,11 @@ int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, b
     L.P = P;
     L.dry = dry;
     L.blocks_per_cu = blocks_per_cu;
+    L.queue = mega_queue(v, P, flags);
+    L.n_cus = c->n_cus;
+    /* (RTR_QUEUE_WORKGROUPS = n caps the persistent grid: with 1, four waves eat every block of a small image) */
+    if (const char* g = getenv("RTR_QUEUE_WORKGROUPS")) L.grid_cap = std::atoi(g);
+    if (flags_in_effect && v.pair && L.accum == 0 && (flags & RTR_FLAG_STATIC_GRID)) *flags_in_effect |= RTR_FLAG_STATIC_GRID;
     int rc;
     switch (integrator) {
     case RTR_INTEGRATOR_MIS: rc = rtr_mega_launch_mis(L, c->err); break;
@@ -710,7 +722,7 @@ int finish_stats(rtr_context* c) {
                                           "shadow: tree leaves", "media steps", "mat_prepare", "shade_a (emission, light sample)",
                                           "shade_b (BSDF sample, roulette)", "miss", "end of sample + regeneration",
                                           "shade_rr / shade_path", "park path state", "sorted shading: barrier waits",
-                                          "sorted shading: tickets + exchange", "pair cast: instance setup",
+                                          "sorted shading: tickets + exchange / queue: job switch", "pair cast: instance setup",
                                           "pair cast: rect runs", "pair cast: sphere runs", "sample end: cancel poll",
                                           "sample end: begin_sample (camera ray)", "sample end: settle into the pixel sum",
                                           "cast counters", "random_in_unit_sphere rejection loop"};
@@ -970,7 +982,7 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
      * shape (bench.py's steps) then queue up without a bubble between them; the statistics of a render nobody
      * asked for are dropped. */
     const size_t partial_bytes = (size_t)P.n_tiles * chunks * 3 * RTR_BLOCK * sizeof(double);
-    const size_t done_bytes = (size_t)P.n_tiles * chunks * sizeof(int);
+    const size_t done_bytes = ((size_t)P.n_tiles * chunks + 1) * sizeof(int); /* + the block counter of a queue render */
     const bool same_tiles = acc || tiles == c->last_tiles; /* (an accumulator's tile list is its own) */
     if ((c->stats_pending || c->in_flight) && (!same_tiles || partial_bytes > c->b_partial.cap || done_bytes > c->b_done.cap ||
                                                pipeline == RTR_PIPELINE_WAVEFRONT)) {
@@ -1002,6 +1014,7 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
     P.partial = static_cast<double*>(c->b_partial.p);
     P.done = static_cast<int*>(c->b_done.p);
     if (pipeline == RTR_PIPELINE_MEGAKERNEL && (rc = launch_mega(c, P, p->integrator, trav, true, nullptr, p->flags))) return rc;
+    const bool queue = pipeline == RTR_PIPELINE_MEGAKERNEL && mega_queue(mega_variant(c->facts, p->integrator, trav, p->flags, nullptr), P, p->flags);
 
     const uint32_t id = c->render_seq.fetch_add(1) + 1; /* rtr_cancel() from now on covers this render */
     P.render_id = id;
@@ -1061,6 +1074,8 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
             ++launches;
             HIPCHK(c, hipGetLastError());
         }
+        if (queue) /* the jobs count themselves in the completion words, and the waves pull blocks through the counter behind them */
+            HIPCHK(c, hipMemsetAsync(c->b_done.p, 0, done_bytes, c->stream));
         if ((rc = launch_mega(c, P, p->integrator, trav, false, nullptr, p->flags, &c->stats.flags_in_effect, &launched))) return rc;
         c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, 0, 0, 0, 0, 0, 0,
                                           acc ? (acc->moments ? 2 : 1) : 0};
@@ -1069,7 +1084,7 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
                                static_cast<double*>(acc->d_sum.p), static_cast<double*>(acc->moments ? acc->d_q.p : nullptr),
                                static_cast<int*>(acc->d_count.p));
         } else {
-            ResolveK R{P, d_rgb, (long long)row_stride, tile_done};
+            ResolveK R{P, d_rgb, (long long)row_stride, tile_done, queue ? RTR_BLOCK : 0};
             rtr_launch_resolve(R, c->stream);
         }
         HIPCHK(c, hipGetLastError());

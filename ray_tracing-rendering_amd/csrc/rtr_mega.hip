@@ -3,7 +3,7 @@
  * times with -DRTR_MEGA_GROUP=0/1/2 so the variants build in parallel.
  *
  * Each group dispatches over the explicit list of its instantiations at the end of this file, one Row per
- * (I, T, M[, S][, PAIR]); every row stands for its three ACC twins.  tests/test_kernel_variants.py holds the same
+ * (I, T, M[, S][, PAIR]); every row stands for its three ACC twins, a PAIR row also for its job-queue twin k_mega_queue.  tests/test_kernel_variants.py holds the same
  * table and renders each row against the oracle: a variant added or removed here goes into that table too.
  */
 #include "rt_kernels.h"
@@ -38,11 +38,36 @@ int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
     return RTR_OK;
 }
 
+/* the job-queue twin of a pair-cast variant: a persistent grid (MegaLaunch::queue) */
+template <typename K>
+int launch_queue(K kernel, const MegaLaunch& L, std::string& err) {
+    hipFuncAttributes fa{};
+    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
+    if (e == hipSuccess)
+        if (int rc = kernel_lds(kernel, L.lds, fa.sharedSizeBytes, err)) return rc;
+    int per_cu = 0;
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RTR_BLOCK, L.lds);
+    if (e == hipSuccess && L.dry && L.blocks_per_cu) *L.blocks_per_cu = per_cu;
+    if (e == hipSuccess && !L.dry) {
+        const long long cells = (long long)L.P.n_tiles * L.P.chunks; /* four blocks each */
+        long long grid = (long long)(per_cu > 0 ? per_cu : 1) * (L.n_cus > 0 ? L.n_cus : 1);
+        if (grid > cells) grid = cells;
+        if (L.grid_cap > 0 && grid > L.grid_cap) grid = L.grid_cap;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(RTR_BLOCK), L.lds, L.stream, L.dsc, L.P, L.stack_words,
+                           reinterpret_cast<uint32_t*>(L.P.done + cells), (int)(cells * 4));
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return mega_fail(err, RTR_ERR_DEVICE, std::string("megakernel launch: ") + hipGetErrorString(e));
+    return RTR_OK;
+}
+
 /* one line of a group's list: k_mega<I, T, M, S, ACC, PR> for ACC = 0, 1, 2 */
 template <int I, int T, int M, bool S = false, bool PR = false>
 struct Row {
     static bool is(const MegaVariant& v) { return v.integ == I && v.trav == T && v.ms == M && v.sorted == S && v.pair == PR; }
     static int launch(const MegaLaunch& L, std::string& err) {
+        if constexpr (PR)
+            if (L.queue) return launch_queue(k_mega_queue<I, T, M>, L, err);
         /* (an accumulator pass: the same variant with ACC = 1, or 2 with moments, rt_kernels.h) */
         return L.accum == 2 ? launch_one(k_mega<I, T, M, S, 2, PR>, L, err)
                : L.accum    ? launch_one(k_mega<I, T, M, S, 1, PR>, L, err)

@@ -202,6 +202,28 @@ int rtr_test_pair_frames(const rtr_scene_desc* scene, int32_t* shapes, int64_t c
     return rtr_debug_frame_shapes(scene, shapes, cap, n_instances);
 }
 
+int rtr_test_queue_blocks_host(int32_t n_tiles, int32_t spp, int32_t chunks, int32_t n_big, int32_t big_spp, int32_t small_spp,
+                               rtr_queue_block_record* recs, int64_t n) {
+    if (n_tiles < 1 || spp < 1 || chunks < 1 || n < 0 || n > (int64_t)n_tiles * chunks * 4 || (n > 0 && !recs)) return RTR_ERR_INVALID;
+    RenderK P{};
+    P.n_tiles = n_tiles, P.spp = spp, P.chunks = chunks;
+    P.n_big = n_big, P.big_spp = big_spp, P.small_spp = small_spp;
+    for (int64_t b = 0; b < n; ++b) {
+        const QueueBlock q = queue_block(P, (int)b);
+        rtr_queue_block_record& r = recs[b];
+        r.slot = q.slot, r.quarter = q.quarter, r.chunk = q.chunk, r.s0 = q.s0, r.s1 = q.s1, r.pad = 0;
+        chunk_range(P, q.chunk, r.ref_s0, r.ref_s1);
+    }
+    return RTR_OK;
+}
+
+int rtr_test_queue_pack_host(int32_t i, int32_t j, int32_t s_end, uint32_t* lo, uint32_t* hi, int32_t* out) {
+    if (!lo || !hi || !out) return RTR_ERR_INVALID;
+    queue_pack(i, j, s_end, *lo, *hi);
+    queue_unpack(*lo, *hi, out[0], out[1], out[2]);
+    return RTR_OK;
+}
+
 int rtr_test_pair_frame_host(int32_t shape, const double* ops, rtr_pair_frame_record* recs, int64_t n) {
     if (shape < RT_SHAPE_NONE || shape > RT_SHAPE_RT || !ops || n < 0 || (n > 0 && !recs)) return RTR_ERR_INVALID;
     /* the chain op by op, as hittable.h:53,128-138 pass a ray down: 1 = translate, 2 = rotate_y */

@@ -35,7 +35,7 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
-                "rtr_test_pair_frame_host", "rtr_test_pair_cast")
+                "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host")
 _TEST_LIB = None
 
 
@@ -72,6 +72,7 @@ PAIR_FRAME_DTYPE = np.dtype([("ao", "<f8", (3,)), ("ad", "<f8", (3,)), ("bo", "<
 PAIR_DTYPE = np.dtype([("ao", "<f8", (3,)), ("ad", "<f8", (3,)), ("a_tmax", "<f8"), ("bo", "<f8", (3,)), ("bd", "<f8", (3,)),
                        ("b_tmax", "<f8"), ("a_t", "<f8"), ("s_a_t", "<f8"), ("a_ref", "<i4"), ("a_inst", "<i4"),
                        ("b_hit", "<i4"), ("s_a_ref", "<i4"), ("s_a_inst", "<i4"), ("s_b_hit", "<i4")])
+QUEUE_BLOCK_DTYPE = np.dtype([(name, "<i4") for name in ("slot", "quarter", "chunk", "s0", "s1", "ref_s0", "ref_s1", "pad")])
 FRAME_SHAPES = ("none", "T", "R", "TR", "RT", "other")  # FInst::shape (csrc/rt_device.h: RT_SHAPE_*)
 
 
@@ -197,6 +198,8 @@ def test_lib():
     T.rtr_test_pair_frames.argtypes = [C.POINTER(A.SceneDescC), vp, C.c_int64, C.POINTER(C.c_int32)]
     T.rtr_test_pair_frame_host.argtypes = [C.c_int32, vp, vp, C.c_int64]
     T.rtr_test_pair_cast.argtypes = [vp, vp, C.c_int64]
+    T.rtr_test_queue_blocks_host.argtypes = [C.c_int32] * 6 + [vp, C.c_int64]
+    T.rtr_test_queue_pack_host.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     _TEST_LIB = T
     return T
 
@@ -263,6 +266,28 @@ def pair_frame_host(shape, ops, ao, ad, bo, bd):
     if rc != 0:
         raise RtrError(rc, "rtr_test_pair_frame_host")
     return recs
+
+
+def queue_blocks_host(n_tiles, spp, chunks, guided=(0, 0, 0)):
+    """rtr_test_queue_blocks_host (include/rtr_hip_test.h; no GPU needed): the host build of the job queue's block decode
+    for every block of a launch over ``n_tiles`` tiles, ``chunks`` partial sums of ``spp`` samples, ``guided`` = (n_big,
+    big_spp, small_spp) of a guided split.  Returns the ``QUEUE_BLOCK_DTYPE`` records, one per block id."""
+    recs = np.zeros(n_tiles * chunks * 4, dtype=QUEUE_BLOCK_DTYPE)
+    rc = test_lib().rtr_test_queue_blocks_host(n_tiles, spp, chunks, *[int(g) for g in guided], recs.ctypes.data, len(recs))
+    if rc != 0:
+        raise RtrError(rc, "rtr_test_queue_blocks_host")
+    return recs
+
+
+def queue_pack_host(i, j, s_end):
+    """rtr_test_queue_pack_host: (lo, hi) halves of the parked word for pixel (i, j) and ``s_end``, and what unpacking
+    them gives back, as ((lo, hi), (i, j, s_end))."""
+    lo, hi = C.c_uint32(0), C.c_uint32(0)
+    out = np.zeros(3, dtype=np.int32)
+    rc = test_lib().rtr_test_queue_pack_host(int(i), int(j), int(s_end), C.byref(lo), C.byref(hi), out.ctypes.data)
+    if rc != 0:
+        raise RtrError(rc, "rtr_test_queue_pack_host")
+    return (lo.value, hi.value), tuple(int(v) for v in out)
 
 
 def denoise_defaults(**overrides):
