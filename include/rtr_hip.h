@@ -781,6 +781,83 @@ int rtr_display_device(rtr_context* ctx, const rtr_display_params* params, int32
                        const double* d_linear, int64_t row_stride, uint8_t* d_rgb8, double* d_mapped,
                        rtr_display_result* h_result, int blocking);
 
+/* ---- hemisphere gathers: ambient occlusion and mean radiance at caller-given surface points ----
+ * For each of `n` points (position p, normal n) the library makes N = params->samples rays over the hemisphere about n in
+ * registers, casts them with the traversal a render walks and reduces them to one 32-byte record: nothing per ray ever
+ * visits memory.  Every output bit is defined here; only + - * / sqrt and compares are used on the way to a ray, so a
+ * host, numpy and the device give the same bits (rtr_gather_ray is the host form).
+ *
+ * RAY s (0 <= s < N) of point k (k = its index in the call + params->point_base, taken modulo 2^32):
+ *   state = rtr_sample_seed_inline(seed, 1, 0, (int32_t)k, s)                  (rtr_seed.h)
+ *   w  = unit(n)                               unit(v) = (1 / sqrt(v.x*v.x + v.y*v.y + v.z*v.z)) * v   (core/vec3.h:208-224)
+ *   u  = random_unit_vector(state)             the rejection loop of core/vec3.h:226-237: draws z, y, x, each
+ *                                              -1 + state' * 2^-31 after one xorshift32 step (13, 17, 5), until
+ *                                              x*x + y*y + z*z < 1; then unit
+ *   sd = w + u;  if every |component| of sd is < 1e-8 (near_zero, core/vec3.h:81-85): sd = w
+ *   d  = unit(sd)
+ * The ray is (origin p, direction d, time, [t_min, t_max]) with the state left after the draws: the direction of the
+ * reference's lambertian scatter, cosine-distributed about n and of unit length, so t_max is a distance.
+ *
+ * REDUCTION (part of the contract: v is FP64).  G = min(64, bit_ceil(N)).  Lane l (0 <= l < G) takes the samples
+ * s = l, l + G, l + 2G, ... < N in increasing order into a = +0.0; a = a + x_s, per component.  Then for
+ * off = G/2, ..., 1: a[l] = a[l] + a[l xor off], all lanes at once.  Then v = (1.0 / N) * a[0].  Counts the same way.
+ *
+ * rtr_gather_occlusion: a sample is BLOCKED when the any-hit cast of the integrators' shadow rays finds something in
+ * [t_min, t_max] -- rtr_query_occluded of that ray, draws inside media included.  x_s = d for an unblocked sample; a
+ * blocked one adds nothing.  count = unblocked samples, v = the unnormalised bent normal, count / N = ambient occlusion.
+ * rtr_gather_radiance: x_s = Integrator::Li of that ray with that state under render->integrator, max_depth,
+ * rr_start_depth and flags -- what rtr_li_rays returns for it (t_min and t_max do not apply).  count = N; v = the mean
+ * radiance over cosine-distributed directions: irradiance is pi * v.
+ *
+ * A point is BAD if a component of p or n is not finite or sqrt(n.n) as computed above is not in (0, +inf).  The host
+ * entries reject the whole batch with RTR_ERR_INVALID, name the first bad index in rtr_last_error and leave the outputs
+ * untouched; the device entries cannot see the data: there the kernel writes {0, 0, 0, count 0, valid 0} for such a
+ * point without casting, and every other point gets valid = 1 and its value.
+ *
+ * params: 1 <= samples <= 2^20; flags 0 or RTR_FLAG_REFERENCE_ORDER; time and t_min finite (any finite t_min, 0 and
+ * negative included: below 2^-100 the launch takes the plain IEEE divisions); t_max not NaN; reserved 0.  Anything else,
+ * n < 0 or a NULL array is RTR_ERR_INVALID; a call before rtr_upload_scene is RTR_ERR_NO_SCENE -- all before any device
+ * work.  n == 0 is RTR_OK without a launch.
+ *
+ * The host entries take host arrays and block; they go through a buffer of the context nothing else uses, in slices of
+ * at most 2^20 points, and advance point_base per slice.  The device entries take device pointers (8-byte aligned; in and
+ * out must not overlap), run on the context stream behind whatever is queued there and return at once unless `blocking`.
+ * Neither touches anything a queued render or accumulator pass uses, nor the statistics of rtr_get_stats; rtr_cancel
+ * does not apply.  Points can be sharded over contexts: shard j passes point_base = its first point's index. */
+typedef struct rtr_gather_point {   /* 48 bytes */
+    double p[3], n[3];              /* n need not be normalised */
+} rtr_gather_point;
+
+typedef struct rtr_gather_params {  /* 56 bytes */
+    int32_t samples;
+    uint32_t seed, point_base;
+    int32_t flags;
+    double time, t_min, t_max;
+    double reserved[2];
+} rtr_gather_params;
+
+typedef struct rtr_gather_out {     /* 32 bytes */
+    double v[3];
+    int32_t count, valid;
+} rtr_gather_out;
+
+/* samples 64, seed 0, point_base 0, flags 0, time 0, t_min 0.001, t_max +inf */
+void rtr_gather_defaults(rtr_gather_params* p);
+
+int rtr_gather_occlusion(rtr_context* ctx, const rtr_gather_params* params, const rtr_gather_point* points,
+                         rtr_gather_out* out, int64_t n);
+int rtr_gather_radiance(rtr_context* ctx, const rtr_render_params* render, const rtr_gather_params* params,
+                        const rtr_gather_point* points, rtr_gather_out* out, int64_t n);
+int rtr_gather_occlusion_device(rtr_context* ctx, const rtr_gather_params* params, const rtr_gather_point* d_points,
+                                rtr_gather_out* d_out, int64_t n, int blocking);
+int rtr_gather_radiance_device(rtr_context* ctx, const rtr_render_params* render, const rtr_gather_params* params,
+                               const rtr_gather_point* d_points, rtr_gather_out* d_out, int64_t n, int blocking);
+
+/* Host-only, needs no context: ray s of the point at `index_in_call` (the definition above; `point` is that point's
+ * record, not an array).  RTR_ERR_INVALID for a bad point, bad params, a negative index or s outside [0, samples). */
+int rtr_gather_ray(const rtr_gather_params* params, const rtr_gather_point* point, int64_t index_in_call, int32_t s,
+                   rtr_ray* out);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

@@ -13,7 +13,7 @@ Layout:
 """
 from . import _abi  # noqa: F401
 from ._abi import (INTEGRATOR_MIS, INTEGRATOR_RR, PIPELINE_AUTO, PIPELINE_MEGAKERNEL,  # noqa: F401
-                   PIPELINE_WAVEFRONT, RAY_DTYPE, RAY_HIT_DTYPE, make_params)
+                   PIPELINE_WAVEFRONT, RAY_DTYPE, RAY_HIT_DTYPE, GATHER_POINT_DTYPE, GATHER_OUT_DTYPE, make_params)
 from .scene import Scene  # noqa: F401
 
 
@@ -23,7 +23,7 @@ def __getattr__(name):
         import importlib
         return importlib.import_module(__name__ + "." + name)
     if name in ("Context", "RtrError", "library_path", "denoise_defaults", "denoise_host", "temporal_defaults",
-                "History", "display_defaults", "srgb_thresholds"):
+                "History", "display_defaults", "srgb_thresholds", "gather_defaults", "gather_rays"):
         from . import native
         return getattr(native, name)
     if name in ("Renderer", "RenderBuffer", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):

@@ -53,6 +53,11 @@ RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("tim
 RAY_HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("n", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
                           ("hit", "<i4"), ("front_face", "<i4"), ("material", "<i4"), ("rng_out", "<u4")])
 assert RAY_DTYPE.itemsize == 80 and RAY_HIT_DTYPE.itemsize == 88
+# hemisphere gathers (rtr_gather_*): rtr_gather_point in, rtr_gather_out out
+GATHER_POINT_DTYPE = np.dtype([("p", "<f8", (3,)), ("n", "<f8", (3,))])
+GATHER_OUT_DTYPE = np.dtype([("v", "<f8", (3,)), ("count", "<i4"), ("valid", "<i4")])
+assert GATHER_POINT_DTYPE.itemsize == 48 and GATHER_OUT_DTYPE.itemsize == 32
+GATHER_MAX_SAMPLES = 1 << 20
 
 # golden-vector records (rtr_testrec.h, packed)
 LI_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("s", "<i4"), ("rng_exit", "<u4"), ("L", "<f8", (3,)),
@@ -118,6 +123,16 @@ class RayHitC(C.Structure):
 
 
 assert C.sizeof(RayC) == RAY_DTYPE.itemsize and C.sizeof(RayHitC) == RAY_HIT_DTYPE.itemsize
+
+
+class GatherParamsC(C.Structure):
+    """rtr_gather_params (include/rtr_hip.h): the hemisphere gathers rtr_gather_occlusion / rtr_gather_radiance"""
+    _fields_ = [("samples", C.c_int32), ("seed", C.c_uint32), ("point_base", C.c_uint32), ("flags", C.c_int32),
+                ("time", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double), ("reserved", C.c_double * 2)]
+
+
+GATHER_PARAMS_SIZE = 56
+assert C.sizeof(GatherParamsC) == GATHER_PARAMS_SIZE
 
 
 class DenoiseParamsC(C.Structure):

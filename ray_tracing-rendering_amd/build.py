@@ -52,7 +52,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # translation units of librtr_hip.so: (object name, source, extra defines); compiled in parallel
 HIP_UNITS = [("capi", "rtr_capi.hip", []), ("mega_mis", "rtr_mega.hip", ["-DRTR_MEGA_GROUP=0"]),
              ("mega_rr_path", "rtr_mega.hip", ["-DRTR_MEGA_GROUP=1"]), ("mega_pbr_nee", "rtr_mega.hip", ["-DRTR_MEGA_GROUP=2"]),
-             ("wavefront", "rtr_wavefront.hip", []), ("test", "rtr_test.hip", [])]
+             ("wavefront", "rtr_wavefront.hip", []), ("gather", "rtr_gather.hip", []), ("test", "rtr_test.hip", [])]
 
 
 def build_hip(force=False, verbose=False, extra_flags=()):

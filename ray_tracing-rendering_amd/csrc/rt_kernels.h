@@ -13,6 +13,8 @@
  *  k_resolve   adds the per-chunk partial sums of a pixel in chunk order, scales by 1/spp
  *              (renderer.h:131) and stores linear mean radiance.
  *  k_li        Integrator::Li of single camera samples or caller-given rays, one lane each (rtr_li_samples / rtr_li_rays).
+ *  k_gather_any / k_gather_li   hemisphere gathers (rtr_gather_*): a group of up to 64 lanes per point makes its samples'
+ *              rays in registers, casts them (any-hit / Integrator::Li) and reduces them inside the wave.
  *  k_accum_commit / k_accum_resolve   progressive accumulators (rtr_accum_*): keep the sums of the tiles a pass
  *              finished, and turn sums + per-tile sample counts into linear mean radiance and the 8-bit store.
  *  k_accum_errors / k_accum_plan   adaptive sampling: per-tile noise estimates from sums + second moments, and the
@@ -1121,6 +1123,100 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_query_any(DScene sc, const rtr_ra
     }
     occluded[k] = blocked ? 1 : 0;
     if (rng_out) rng_out[k] = rng;
+}
+
+/* rtr_gather_occlusion / rtr_gather_radiance: N hemisphere samples per point, made in registers, cast, and reduced inside
+ * the wave (include/rtr_hip.h has the contract: ray, reduction order, bad points).  Global lane g = block * RTR_BLOCK +
+ * thread serves point g / G as lane g % G of its group (G = 1 << K.lg <= 64, so a group never leaves its wave and a wave
+ * holds 64 / G points).  A lane takes the samples l, l + G, ... in order; the casts run under divergent EXEC like the
+ * queries'.  The butterfly does not: lanes without a sample, of a bad point or of a point past the end carry +0.0 / 0 and
+ * reach every __shfl_xor; only a wave whose first point is past the end returns.  Lane 0 of a group stores the record.
+ * BCAST: lane 0 of the group loads the point and the group reads it from that lane, instead of every lane loading the
+ * same 48 bytes (tools/time_gather.py measures both: DESIGN.md 4.8). */
+#ifndef RTR_GATHER_BROADCAST_DEFAULT
+#define RTR_GATHER_BROADCAST_DEFAULT 0 /* which form the library launches (RTR_GATHER_BROADCAST=0/1 overrides it) */
+#endif
+struct GatherLane {
+    long long k; /* point of this lane's group */
+    int l;       /* lane in the group */
+    bool cast;   /* the point exists and is not bad */
+    V3 p, w;
+};
+template <bool BCAST>
+RT_DEV bool gather_begin(const GatherK& K, GatherLane& L) {
+    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (((g & ~63ll) >> K.lg) >= K.n) return false; /* the whole wave is past the end */
+    L.k = g >> K.lg, L.l = (int)(g & ((1 << K.lg) - 1));
+    const bool live = L.k < K.n;
+    rtr_gather_point q;
+    for (int a = 0; a < 3; ++a) q.p[a] = 0.0, q.n[a] = 0.0;
+    if (BCAST) {
+        if (live && L.l == 0) q = K.pts[L.k];
+        const int src = (int)(threadIdx.x & 63) - L.l;
+        for (int a = 0; a < 3; ++a) q.p[a] = __shfl(q.p[a], src, 64), q.n[a] = __shfl(q.n[a], src, 64);
+    } else if (live) {
+        q = K.pts[L.k];
+    }
+    double nlen;
+    L.cast = !gather_point_bad(q, nlen) && live;
+    L.p = ld3(q.p);
+    L.w = scl(1 / nlen, ld3(q.n));
+    return true;
+}
+RT_DEV uint32_t gather_ray(const GatherK& K, const GatherLane& L, int s, V3& d) {
+    uint32_t rng = rtr_sample_seed_inline(K.seed, 1, 0, (int32_t)((uint32_t)L.k + K.point_base), s);
+    gather_direction(L.w.x, L.w.y, L.w.z, rng, d.x, d.y, d.z);
+    return rng;
+}
+RT_DEV void gather_end(const GatherK& K, const GatherLane& L, V3 a, int count) {
+    for (int off = (1 << K.lg) >> 1; off > 0; off >>= 1) {
+        a.x = a.x + __shfl_xor(a.x, off, 64), a.y = a.y + __shfl_xor(a.y, off, 64), a.z = a.z + __shfl_xor(a.z, off, 64);
+        count = count + __shfl_xor(count, off, 64);
+    }
+    if (L.l != 0 || L.k >= K.n) return;
+    rtr_gather_out o;
+    const double scale = 1.0 / K.samples;
+    o.v[0] = L.cast ? scale * a.x : 0.0, o.v[1] = L.cast ? scale * a.y : 0.0, o.v[2] = L.cast ? scale * a.z : 0.0;
+    o.count = L.cast ? count : 0, o.valid = L.cast ? 1 : 0;
+    K.out[L.k] = o;
+}
+template <int TRAV, bool BCAST>
+__global__ void __launch_bounds__(RTR_BLOCK) k_gather_any(const DScene sc, const GatherK K) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    GatherLane L;
+    if (!gather_begin<BCAST>(K, L)) return;
+    V3 a = mk(0.0, 0.0, 0.0);
+    int count = 0;
+    if (L.cast)
+        for (int s = L.l; s < K.samples; s += 1 << K.lg) {
+            V3 d;
+            uint32_t rng = gather_ray(K, L, s, d);
+            if (!cast_shadow<TRAV>(sc, L.p, d, K.t_max, rng, st, K.time, K.t_min)) a = add(a, d), ++count;
+        }
+    gather_end(K, L, a, count);
+}
+template <int INTEG, int TRAV>
+__global__ void __launch_bounds__(RTR_BLOCK) k_gather_li(const DScene sc, const GatherK K) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    GatherLane L;
+    if (!gather_begin<false>(K, L)) return;
+    V3 a = mk(0.0, 0.0, 0.0);
+    int count = 0;
+    if (L.cast)
+        for (int s = L.l; s < K.samples; s += 1 << K.lg) {
+            V3 d;
+            uint32_t rng = gather_ray(K, L, s, d);
+            PathState ps;
+            path_begin(ps, L.p, d, K.time);
+            PathCounters cnt;
+            cnt.closest = 0, cnt.shadow = 0;
+            while (bounce<INTEG, TRAV>(sc, ps, rng, st, K.max_depth, K.rr_start, cnt)) {
+            }
+            a = add(a, ps.L), ++count;
+        }
+    gather_end(K, L, a, count);
 }
 
 #ifdef RTR_TU_CAPI /* non-template kernels live in one translation unit */

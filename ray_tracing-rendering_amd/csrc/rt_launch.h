@@ -1,8 +1,8 @@
 /*
  * rt_launch.h -- host-side seams between the translation units of librtr_hip.so.  The kernels are
  * compiled in parallel: rtr_capi.hip (C ABI, scene lowering and upload, per-ray kernels, k_resolve), rtr_mega.hip
- * three times (one integrator group each: RTR_MEGA_GROUP 0 = MIS, 1 = RR + path, 2 = PBR + NEE) and
- * rtr_wavefront.hip (stage kernels + their host driver).
+ * three times (one integrator group each: RTR_MEGA_GROUP 0 = MIS, 1 = RR + path, 2 = PBR + NEE),
+ * rtr_wavefront.hip (stage kernels + their host driver) and rtr_gather.hip (the hemisphere-gather kernels + their launcher).
  *
  * Which k_mega instantiation a render runs is decided once, by mega_variant() in rtr_capi.hip from the
  * SceneFacts of rt_lower.h (which only that unit includes); the MegaVariant travels in MegaLaunch to the group's unit, which looks it up in its explicit list of
@@ -56,6 +56,20 @@ int rtr_mega_launch_rr_path(const MegaLaunch& L, std::string& err);
 int rtr_mega_launch_pbr_nee(const MegaLaunch& L, std::string& err);
 
 void rtr_launch_resolve(const ResolveK& R, hipStream_t stream);
+
+/* one hemisphere-gather launch (rtr_gather.hip holds the k_gather_* instantiations) */
+struct GatherLaunch {
+    DScene ds;      /* the launch's copy: shared_div cleared for t_min < 2^-100 */
+    GatherK K;
+    int integ;      /* RTR_INTEGRATOR_* of a radiance gather, -1: occlusion */
+    int trav;       /* per_ray_trav(..., top = integ < 0), before the EXACT -> MEDIA substitution of li_run */
+    size_t lds;     /* traversal stack, bytes per workgroup */
+    bool broadcast; /* occlusion: k_gather_any<T, true> */
+    hipStream_t stream;
+};
+int rtr_gather_launch(const GatherLaunch& L, std::string& err);
+/* RTR_OK, or RTR_ERR_INVALID with the reason in `err` */
+int rtr_gather_params_check(const rtr_gather_params* p, std::string& err);
 
 /* The per-lane traversal stack lives in LDS: a graph that needs more than the CU has (e.g. the reference-order walk
  * of a hittable_list with thousands of direct children) cannot run that way.  `static_bytes`: the kernel's own static

@@ -121,6 +121,48 @@ RT_DEV unsigned long long wave_sum(unsigned long long v) {
     return v;
 }
 
+/* ---- hemisphere gathers (include/rtr_hip.h: rtr_gather_*) ----
+ * The arithmetic of the contract, written once for host (rtr_gather_ray, the host entries' checks) and device
+ * (k_gather_*): + - * / sqrt and compares only, no libm, the operation order of core/vec3.h. */
+struct GatherK {
+    const rtr_gather_point* pts;
+    rtr_gather_out* out;
+    long long n;
+    int samples, lg;            /* N; log2 of the group size G = min(64, bit_ceil(N)) */
+    uint32_t seed, point_base;
+    double time, t_min, t_max;
+    int max_depth, rr_start;    /* radiance only */
+};
+RT_HD int gather_lg(int samples) {
+    int lg = 0;
+    while (lg < 6 && (1 << lg) < samples) ++lg;
+    return lg;
+}
+RT_HD bool gather_point_bad(const rtr_gather_point& q, double& nlen) {
+    bool ok = true;
+    for (int a = 0; a < 3; ++a) ok = ok && __builtin_isfinite(q.p[a]) && __builtin_isfinite(q.n[a]);
+    nlen = __builtin_sqrt(q.n[0] * q.n[0] + q.n[1] * q.n[1] + q.n[2] * q.n[2]);
+    return !(ok && nlen > 0.0 && nlen < __builtin_huge_val());
+}
+/* direction of the sample whose generator is `rng` about the unit normal w; rng is left behind the draws */
+RT_HD void gather_direction(double wx, double wy, double wz, uint32_t& rng, double& dx, double& dy, double& dz) {
+    double x, y, z;
+    for (;;) { /* vec3.h:226-233: z takes the first draw */
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        z = -1.0 + rng * 4.656612873077392578125e-10;
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        y = -1.0 + rng * 4.656612873077392578125e-10;
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        x = -1.0 + rng * 4.656612873077392578125e-10;
+        if (!(x * x + y * y + z * z >= 1)) break;
+    }
+    const double ru = 1 / __builtin_sqrt(x * x + y * y + z * z);
+    double sx = wx + ru * x, sy = wy + ru * y, sz = wz + ru * z;
+    if (__builtin_fabs(sx) < 1e-8 && __builtin_fabs(sy) < 1e-8 && __builtin_fabs(sz) < 1e-8) sx = wx, sy = wy, sz = wz;
+    const double rs = 1 / __builtin_sqrt(sx * sx + sy * sy + sz * sz);
+    dx = rs * sx, dy = rs * sy, dz = rs * sz;
+}
+
 struct ResolveK {
     RenderK r;
     double* out; /* linear mean radiance, 3 doubles per pixel */

@@ -56,6 +56,7 @@ struct rtr_context {
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
     DevBuf b_query; /* rtr_query_closest / rtr_query_occluded: one slice of rays and its results (nothing else uses it) */
+    DevBuf b_gather; /* rtr_gather_occlusion / rtr_gather_radiance: one slice of points and its results (nothing else uses it) */
     DevBuf b_display;    /* rtr_display_*: the sRGB thresholds (uploaded by rtr_create), the histogram, the DisplayRec */
     DevBuf b_display_io; /* rtr_display_host / _histogram: the image and its outputs (nothing else uses it) */
     std::vector<int> last_tiles; /* what b_tiles holds */
@@ -854,7 +855,7 @@ void rtr_destroy(rtr_context* c) {
     for (DevBuf& b : c->sb)
         if (b.p) hipFree(b.p);
     DevBuf* bufs[] = {&c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise,
-                      &c->b_query, &c->b_display, &c->b_display_io};
+                      &c->b_query, &c->b_gather, &c->b_display, &c->b_display_io};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     c->pool.release();
@@ -2040,6 +2041,119 @@ int rtr_query_occluded_device(rtr_context* c, const rtr_ray* d_rays, uint8_t* d_
     if (int rc = query_check(c, d_rays, d_occluded, n, flags)) return rc;
     if (n == 0) return RTR_OK;
     return query_device(c, d_rays, nullptr, d_occluded, d_rng_out, n, flags, blocking);
+}
+
+} /* extern "C" */
+
+/* ---- hemisphere gathers: occlusion and radiance over the hemisphere at caller-given points (kernels: rtr_gather.hip) -- */
+namespace {
+
+constexpr int64_t kGatherSlice = (int64_t)1 << 20; /* points per slice of the host entries */
+
+/* what every gather entry checks before any device work; `radiance`: rp is checked too (a NULL one is invalid) */
+int gather_check(rtr_context* c, const rtr_render_params* rp, bool radiance, const rtr_gather_params* gp, const void* pts,
+                 const void* out, int64_t n) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = rtr_gather_params_check(gp, c->err)) return rc;
+    if (n < 0 || (n > 0 && (!pts || !out))) return fail(c, RTR_ERR_INVALID, "rtr_gather_*: negative n or NULL array");
+    if (radiance)
+        if (int rc = params_check(c, rp)) return rc;
+    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_gather_* before rtr_upload_scene");
+    return RTR_OK;
+}
+int gather_check_points(rtr_context* c, const rtr_gather_point* pts, int64_t n) {
+    for (int64_t k = 0; k < n; ++k) {
+        double nlen;
+        if (gather_point_bad(pts[k], nlen))
+            return fail(c, RTR_ERR_INVALID, "rtr_gather_*: bad point at index " + std::to_string(k) +
+                                                " (non-finite position / normal, or a normal whose length is not in (0, inf))");
+    }
+    return RTR_OK;
+}
+
+/* every lane of a group loads its point (k_gather_any<T, false>) unless RTR_GATHER_BROADCAST=1 asks for one load per group
+ * and a broadcast (tools/time_gather.py measures both forms: DESIGN.md 4.8) */
+bool gather_broadcast() {
+    const char* e = getenv("RTR_GATHER_BROADCAST");
+    return e ? e[0] != '0' : RTR_GATHER_BROADCAST_DEFAULT != 0;
+}
+
+/* launches over device arrays on the context stream */
+int gather_launch(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, uint32_t point_base,
+                  const rtr_gather_point* d_pts, rtr_gather_out* d_out, int64_t n) {
+    GatherLaunch L;
+    L.ds = c->ds;
+    L.integ = rp ? rp->integrator : -1;
+    L.trav = per_ray_trav(c->facts, c->info, rp ? rp->flags : gp->flags, !rp);
+    L.lds = stack_bytes(c->facts, c->info, L.trav);
+    L.broadcast = gather_broadcast();
+    L.stream = c->stream;
+    if (!rp && !(gp->t_min >= 0x1p-100)) L.ds.shared_div = 0; /* the plain divisions, as k_query_* per wave */
+    L.K = GatherK{d_pts, d_out, (long long)n, gp->samples, gather_lg(gp->samples), gp->seed, point_base, gp->time, gp->t_min,
+                  gp->t_max, rp ? rp->max_depth : 0, rp ? rp->rr_start_depth : 0};
+    return rtr_gather_launch(L, c->err);
+}
+
+int gather_host(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_gather_point* pts,
+                rtr_gather_out* out, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError(); /* a launch error of an earlier call is not this call's */
+    const int64_t slice = std::min(n, kGatherSlice);
+    const size_t in_bytes = (size_t)slice * sizeof(rtr_gather_point);
+    if (int rc = ensure(c, c->b_gather, in_bytes + (size_t)slice * sizeof(rtr_gather_out))) return rc;
+    rtr_gather_point* d_pts = static_cast<rtr_gather_point*>(c->b_gather.p);
+    rtr_gather_out* d_out = reinterpret_cast<rtr_gather_out*>(static_cast<char*>(c->b_gather.p) + in_bytes);
+    for (int64_t k0 = 0; k0 < n; k0 += slice) {
+        const int64_t m = std::min(slice, n - k0);
+        HIPCHK(c, hipMemcpyAsync(d_pts, pts + k0, (size_t)m * sizeof(rtr_gather_point), hipMemcpyHostToDevice, c->stream));
+        if (int rc = gather_launch(c, rp, gp, gp->point_base + (uint32_t)k0, d_pts, d_out, m)) return rc;
+        HIPCHK(c, hipMemcpyAsync(out + k0, d_out, (size_t)m * sizeof(rtr_gather_out), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); /* the next slice reuses the buffer */
+    }
+    return RTR_OK;
+}
+
+int gather_device(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_gather_point* d_pts,
+                  rtr_gather_out* d_out, int64_t n, int blocking) {
+    if (((uintptr_t)d_pts | (uintptr_t)d_out) & 7) return fail(c, RTR_ERR_INVALID, "rtr_gather_*_device: pointers must be 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    if (int rc = gather_launch(c, rp, gp, gp->point_base, d_pts, d_out, n)) return rc;
+    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rtr_gather_occlusion(rtr_context* c, const rtr_gather_params* gp, const rtr_gather_point* pts, rtr_gather_out* out, int64_t n) {
+    if (int rc = gather_check(c, nullptr, false, gp, pts, out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    if (int rc = gather_check_points(c, pts, n)) return rc;
+    return gather_host(c, nullptr, gp, pts, out, n);
+}
+
+int rtr_gather_radiance(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_gather_point* pts,
+                        rtr_gather_out* out, int64_t n) {
+    if (int rc = gather_check(c, rp, true, gp, pts, out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    if (int rc = gather_check_points(c, pts, n)) return rc;
+    return gather_host(c, rp, gp, pts, out, n);
+}
+
+int rtr_gather_occlusion_device(rtr_context* c, const rtr_gather_params* gp, const rtr_gather_point* d_pts, rtr_gather_out* d_out,
+                                int64_t n, int blocking) {
+    if (int rc = gather_check(c, nullptr, false, gp, d_pts, d_out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    return gather_device(c, nullptr, gp, d_pts, d_out, n, blocking);
+}
+
+int rtr_gather_radiance_device(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp,
+                               const rtr_gather_point* d_pts, rtr_gather_out* d_out, int64_t n, int blocking) {
+    if (int rc = gather_check(c, rp, true, gp, d_pts, d_out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    return gather_device(c, rp, gp, d_pts, d_out, n, blocking);
 }
 
 } /* extern "C" */

@@ -25,6 +25,10 @@
  *           [--pick i,j]   nothing is rendered: the closest hit of pixel (i, j)'s centre ray -- u = (i + 0.5) / (W - 1),
  *                                   v = (j + 0.5) / (H - 1), no lens offset, time0 -- through Renderer::closest_hits, as one line
  *                                   `hit front_face material t p n` with the doubles as %.17g
+ *           [--ao N [--ao-distance D]]   nothing is path-traced: the pixel-centre ray of every pixel (the ray of --pick) goes
+ *                                   through Renderer::closest_hits, then Renderer::ambient_occlusion casts N hemisphere rays
+ *                                   of length D (default: unbounded) at every hit's (p, n); a pixel is count / N grey, 1.0
+ *                                   where the centre ray misses, stored like a render.  Not with --pick, --adaptive, --turntable
  *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
  *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
  *                                   rtr_display_host through Renderer::display; with --turntable rtr_display_device on
@@ -168,8 +172,8 @@ int main(int argc, char** argv) {
     rtr_display_defaults(&dp);
     int turntable_frames = 0;
     int pick_i = 0, pick_j = 0;
-    int denoise_iter = -1;
-    double threshold = 0.0;
+    int denoise_iter = -1, ao_samples = 0;
+    double threshold = 0.0, ao_distance = 0.0; /* 0: unbounded */
     std::vector<int> devices{0}, passes;
     unsigned seed = 1;
     std::string out;
@@ -239,6 +243,22 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (!std::strcmp(argv[k], "--ao") && k + 1 < argc) {
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (end == argv[k] || *end != '\0' || v < 1 || v > (1 << 20)) {
+                std::cerr << "--ao: N must be an integer in 1..1048576, not " << argv[k] << "\n";
+                return 2;
+            }
+            ao_samples = (int)v;
+        }
+        else if (!std::strcmp(argv[k], "--ao-distance") && k + 1 < argc) {
+            if (!parse_positive(argv[k + 1], ao_distance)) {
+                std::cerr << "--ao-distance takes a finite number > 0, not " << argv[k + 1] << "\n";
+                return 2;
+            }
+            ++k;
+        }
         else if (!std::strcmp(argv[k], "--spp-min") && k + 1 < argc) {
             spp_min = std::atoi(argv[++k]);
             if (spp_min < 1) {
@@ -288,6 +308,14 @@ int main(int argc, char** argv) {
     }
     if (turntable_frames && (adaptive || repeat != 1 || pick)) {
         std::cerr << "--turntable excludes --adaptive, --repeat and --pick\n";
+        return 2;
+    }
+    if (ao_distance > 0.0 && !ao_samples) {
+        std::cerr << "--ao-distance goes with --ao\n";
+        return 2;
+    }
+    if (ao_samples && (pick || adaptive || turntable_frames)) {
+        std::cerr << "--ao excludes --pick, --adaptive and --turntable\n";
         return 2;
     }
     if (display && pick) {
@@ -352,6 +380,47 @@ int main(int argc, char** argv) {
         const rtr_ray_hit& h = hits[0];
         std::printf("%d %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", h.hit, h.front_face, h.material, h.t, h.p[0], h.p[1],
                     h.p[2], h.n[0], h.n[1], h.n[2]);
+        return 0;
+    }
+    if (ao_samples) {
+        if (renderer.upload_scene(config.world, cam, config.background, config.lights) != RTR_OK) {
+            std::cerr << "upload failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        std::vector<ray> centres;
+        centres.reserve((size_t)W * H);
+        for (int j = 0; j < H; ++j)
+            for (int i = 0; i < W; ++i) {
+                const double u = (i + 0.5) / (W - 1), v = (j + 0.5) / (H - 1);
+                centres.emplace_back(cam->origin, cam->lower_left_corner + u * cam->horizontal + v * cam->vertical - cam->origin, cam->time0);
+            }
+        const std::vector<rtr_ray_hit> hits = renderer.closest_hits(centres);
+        if (hits.size() != centres.size()) {
+            std::cerr << "query failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        std::vector<point3> points;
+        std::vector<vec3> normals;
+        for (const rtr_ray_hit& h : hits)
+            if (h.hit) points.emplace_back(h.p[0], h.p[1], h.p[2]), normals.emplace_back(h.n[0], h.n[1], h.n[2]);
+        const std::vector<rtr_gather_out> ao = renderer.ambient_occlusion(points, normals, ao_samples, ao_distance > 0.0 ? ao_distance : infinity);
+        if (ao.size() != points.size()) {
+            std::cerr << "ambient occlusion failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        std::vector<double> lin((size_t)W * H * 3);
+        size_t next = 0;
+        for (size_t k = 0; k < hits.size(); ++k) {
+            const double g = hits[k].hit ? (double)ao[next++].count / ao_samples : 1.0;
+            lin[3 * k] = lin[3 * k + 1] = lin[3 * k + 2] = g;
+        }
+        buffer.store_linear_rows(lin.data(), 0, H, W);
+        std::cout << "ambient occlusion: " << points.size() << " points x " << ao_samples << " samples\n";
+        const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0;
+        if (!out.empty() && !(png ? buffer.save_to_png(out) : buffer.save_to_ppm(out))) {
+            std::cerr << "Failed to save image to " << out << "\n";
+            return 1;
+        }
         return 0;
     }
     renderer.set_samples(config.samples_per_pixel);

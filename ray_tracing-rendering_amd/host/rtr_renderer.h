@@ -410,6 +410,20 @@ class Renderer {
         return occ;
     }
 
+    /* Hemisphere gathers (include/rtr_hip.h: rtr_gather_*), on the first context and the scene uploaded there, like the
+     * queries.  ambient_occlusion: `samples` cosine-distributed rays about every normal, cast up to the distance t_max;
+     * count / samples of a record is the unoccluded fraction, v the unnormalised bent normal.  gather_radiance: the mean of
+     * Integrator::Li over those rays under the integrator set on this renderer (irradiance = pi * v).  An empty vector and
+     * last_status() / last_error() on failure. */
+    std::vector<rtr_gather_out> ambient_occlusion(const std::vector<point3>& points, const std::vector<vec3>& normals, int samples = 64,
+                                                  double t_max = infinity, unsigned seed = 0) {
+        return gather(points, normals, samples, t_max, seed, false);
+    }
+    std::vector<rtr_gather_out> gather_radiance(const std::vector<point3>& points, const std::vector<vec3>& normals, int samples = 64,
+                                                unsigned seed = 0) {
+        return gather(points, normals, samples, infinity, seed, true);
+    }
+
     /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
      * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
      * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */
@@ -439,6 +453,32 @@ class Renderer {
             q[k].rng_state = 1u, q[k].pad = 0;
         }
         return q;
+    }
+    std::vector<rtr_gather_out> gather(const std::vector<point3>& points, const std::vector<vec3>& normals, int samples, double t_max,
+                                       unsigned seed, bool radiance) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if (points.size() != normals.size()) m_error = "one normal per point", m_status = RTR_ERR_INVALID;
+        else if (radiance && !m_integrator) m_error = "no integrator set", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_gather_out> out(points.size());
+        if (m_status == RTR_OK) {
+            std::vector<rtr_gather_point> pts(points.size());
+            for (size_t k = 0; k < points.size(); ++k)
+                for (int a = 0; a < 3; ++a) pts[k].p[a] = points[k][a], pts[k].n[a] = normals[k][a];
+            rtr_gather_params gp;
+            rtr_gather_defaults(&gp);
+            gp.samples = samples, gp.seed = seed, gp.t_max = t_max;
+            if (radiance) {
+                const rtr_render_params rp = base_params(2, 2); /* integrator and depths; no image is involved */
+                m_status = rtr_gather_radiance(m_ctx[0], &rp, &gp, pts.data(), out.data(), (int64_t)pts.size());
+            } else {
+                m_status = rtr_gather_occlusion(m_ctx[0], &gp, pts.data(), out.data(), (int64_t)pts.size());
+            }
+            if (m_status != RTR_OK) m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
     }
     /* what render(), render_progressive() and render_adaptive() check and upload before they render */
     int prepare(const hittable& world, const camera& cam, const color& background, const std::vector<shared_ptr<Light>>& lights,

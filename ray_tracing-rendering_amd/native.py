@@ -30,7 +30,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_history_clear", "rtr_history_destroy", "rtr_history_planes", "rtr_accum_denoise_temporal",
            "rtr_display_defaults", "rtr_display_srgb_thresholds", "rtr_display_histogram", "rtr_display_host",
            "rtr_display_device", "rtr_accum_resolve_device", "rtr_accum_features_device", "rtr_accum_denoise_device",
-           "rtr_accum_denoise_temporal_device")
+           "rtr_accum_denoise_temporal_device", "rtr_gather_defaults", "rtr_gather_occlusion", "rtr_gather_radiance",
+           "rtr_gather_occlusion_device", "rtr_gather_radiance_device", "rtr_gather_ray")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
@@ -161,6 +162,13 @@ def lib():
                                      P(A.DisplayResultC), C.c_int]
     for name, argtypes in A.DEVICE_OUTPUT_SIGNATURES.items():
         getattr(L, name).argtypes = argtypes
+    L.rtr_gather_defaults.argtypes = [P(A.GatherParamsC)]
+    L.rtr_gather_defaults.restype = None
+    L.rtr_gather_occlusion.argtypes = [vp, P(A.GatherParamsC), vp, vp, C.c_int64]
+    L.rtr_gather_radiance.argtypes = [vp, P(A.RenderParamsC), P(A.GatherParamsC), vp, vp, C.c_int64]
+    L.rtr_gather_occlusion_device.argtypes = [vp, P(A.GatherParamsC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_gather_radiance_device.argtypes = [vp, P(A.RenderParamsC), P(A.GatherParamsC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_gather_ray.argtypes = [P(A.GatherParamsC), vp, C.c_int64, C.c_int32, vp]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -321,6 +329,49 @@ def display_defaults(**overrides):
             raise TypeError("no display parameter %r" % k)
         setattr(p, k, v)
     return p
+
+
+def gather_defaults(**overrides):
+    """rtr_gather_params with the library's defaults (rtr_gather_defaults: samples 64, seed 0, point_base 0, flags 0, time 0,
+    t_min 0.001, t_max inf), fields replaced by ``overrides``; ``reference_order=True`` sets RTR_FLAG_REFERENCE_ORDER."""
+    p = A.GatherParamsC()
+    lib().rtr_gather_defaults(C.byref(p))
+    if overrides.pop("reference_order", False):
+        p.flags |= A.FLAG_REFERENCE_ORDER
+    for k, v in overrides.items():
+        if k not in ("samples", "seed", "point_base", "flags", "time", "t_min", "t_max"):
+            raise TypeError("no gather parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def gather_points(points, normals):
+    """A ``GATHER_POINT_DTYPE`` array from (n, 3) positions and normals (or ``points`` already such an array)."""
+    if isinstance(points, np.ndarray) and points.dtype == A.GATHER_POINT_DTYPE:
+        return np.ascontiguousarray(points)
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    pts = np.zeros(len(p), dtype=A.GATHER_POINT_DTYPE)
+    pts["p"], pts["n"] = p, np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    return pts
+
+
+def gather_rays(points, normals=None, params=None, **overrides):
+    """rtr_gather_ray for every sample of every point (host only, no context): the ``RAY_DTYPE`` rays [n, samples] the
+    gathers cast, with the generator state after the direction's draws.  Raises RtrError for a bad point or bad params."""
+    L = lib()
+    gp = params if params is not None else gather_defaults(**overrides)
+    pts = gather_points(points, normals)
+    n_s = int(gp.samples)
+    if not 1 <= n_s <= A.GATHER_MAX_SAMPLES:
+        raise RtrError(A.RTR_ERR_INVALID, "rtr_gather_ray: samples outside 1 .. 2^20")
+    rays = np.zeros((len(pts), n_s), dtype=A.RAY_DTYPE)
+    base, stride, size = pts.ctypes.data, A.GATHER_POINT_DTYPE.itemsize, A.RAY_DTYPE.itemsize
+    for k in range(len(pts)):
+        for s in range(n_s):
+            rc = L.rtr_gather_ray(C.byref(gp), base + k * stride, k, s, rays.ctypes.data + (k * n_s + s) * size)
+            if rc != 0:
+                raise RtrError(rc, "rtr_gather_ray: bad params or bad point at index %d" % k)
+    return rays
 
 
 def srgb_thresholds():
@@ -544,6 +595,58 @@ class Context:
         self._chk(self._L.rtr_query_occluded_device(self._h, C.c_void_p(rays_ptr), C.c_void_p(occluded_ptr),
                                                     C.c_void_p(rng_out_ptr or None), int(n),
                                                     A.FLAG_REFERENCE_ORDER if reference_order else 0, 1 if blocking else 0))
+
+    # hemisphere gathers (include/rtr_hip.h: rtr_gather_*)
+    @staticmethod
+    def _gather_out(out, n):
+        if out is None:
+            return np.zeros(n, dtype=A.GATHER_OUT_DTYPE)
+        if out.dtype != A.GATHER_OUT_DTYPE or len(out) < n or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous GATHER_OUT_DTYPE array of at least %d records" % n)
+        return out
+
+    def gather_occlusion(self, points, normals=None, samples=64, seed=0, t_max=np.inf, t_min=0.001, time=0.0, point_base=0,
+                         reference_order=False, params=None, out=None):
+        """rtr_gather_occlusion: ``samples`` cosine-distributed rays about every normal, any-hit cast in [t_min, t_max] and
+        reduced on the device.  Returns a ``GATHER_OUT_DTYPE`` array: ``count`` unblocked samples (count / samples is the
+        ambient occlusion), ``v`` the unnormalised bent normal, ``valid`` 1.  ``points`` may be a ready
+        ``GATHER_POINT_DTYPE`` array; ``params`` a ready rtr_gather_params (the keyword values are then ignored).
+        Blocking; raises RtrError (RTR_ERR_INVALID) naming the first bad point, with ``out`` untouched."""
+        gp = params if params is not None else gather_defaults(
+            samples=samples, seed=seed, t_max=t_max, t_min=t_min, time=time, point_base=point_base, reference_order=reference_order)
+        pts = gather_points(points, normals)
+        out = self._gather_out(out, len(pts))
+        self._chk(self._L.rtr_gather_occlusion(self._h, C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
+        return out
+
+    def gather_radiance(self, params, points, normals=None, samples=64, seed=0, time=0.0, point_base=0, gather_params=None,
+                        out=None):
+        """rtr_gather_radiance: the mean of ``Integrator::Li`` over ``samples`` cosine-distributed rays about every normal
+        under ``params`` (an rtr_render_params: integrator, max_depth, rr_start_depth, flags); irradiance is pi * v."""
+        gp = gather_params if gather_params is not None else gather_defaults(samples=samples, seed=seed, time=time,
+                                                                             point_base=point_base)
+        pts = gather_points(points, normals)
+        out = self._gather_out(out, len(pts))
+        self._chk(self._L.rtr_gather_radiance(self._h, C.byref(params), C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
+        return out
+
+    def gather_occlusion_into(self, points_ptr, out_ptr, n, params=None, blocking=False, **overrides):
+        """rtr_gather_occlusion_device: n ``GATHER_POINT_DTYPE`` records at device pointer ``points_ptr`` ->
+        ``GATHER_OUT_DTYPE`` records at ``out_ptr``, on the context stream behind what is queued there."""
+        gp = params if params is not None else gather_defaults(**overrides)
+        self._chk(self._L.rtr_gather_occlusion_device(self._h, C.byref(gp), C.c_void_p(points_ptr), C.c_void_p(out_ptr), int(n),
+                                                      1 if blocking else 0))
+
+    def gather_radiance_into(self, params, points_ptr, out_ptr, n, gather_params=None, blocking=False, **overrides):
+        """rtr_gather_radiance_device: the device-pointer form of ``gather_radiance``."""
+        gp = gather_params if gather_params is not None else gather_defaults(**overrides)
+        self._chk(self._L.rtr_gather_radiance_device(self._h, C.byref(params), C.byref(gp), C.c_void_p(points_ptr),
+                                                     C.c_void_p(out_ptr), int(n), 1 if blocking else 0))
+
+    @staticmethod
+    def gather_rays(points, normals=None, params=None, **overrides):
+        """The rays the gathers cast, ``RAY_DTYPE`` [n, samples], through rtr_gather_ray (``native.gather_rays``)."""
+        return gather_rays(points, normals, params, **overrides)
 
     # display transform (include/rtr_hip.h: rtr_display_*)
     @staticmethod
