@@ -30,17 +30,29 @@ int rtr_test_li(rtr_context* ctx, const rtr_render_params* params, rtr_li_record
 int rtr_test_flat_hits(rtr_context* ctx, rtr_hit_record* recs, int64_t n, int with_uv, int32_t* used_finish);
 
 /* Which kernel instantiation the context's last render call launched, recorded on the host as it was enqueued.
- * Megakernel: k_mega<integrator, trav, ms, sorted, accum> (accum: 0 one-shot, 1 accumulator pass, 2 accumulator pass
- * with moments); wavefront: the plan (lean / quadlit / sort / media / machine /
+ * Megakernel: k_mega<integrator, trav, ms, sorted, accum, pair> (accum: 0 one-shot, 1 accumulator pass, 2 accumulator pass
+ * with moments), or with queue set k_mega_queue<integrator, trav, ms>; wavefront: the plan (lean / quadlit / sort / media / machine /
  * trav) and wf_shade<integrator, PH, ms, sorted> for every PH bit of shade_phases.  trav and ms are the RT_TRAV_* and
  * RT_MS_* values of csrc/rt_device.h.  pipeline = -1: no render of this context has launched anything yet. */
 typedef struct rtr_kernel_record {
     int32_t pipeline, integrator, trav, ms, sorted, shade_phases;
     int32_t lean, quadlit, sort, media, machine;
     int32_t accum;
+    int32_t pair, queue; /* megakernel: the pair-cast instantiation k_mega<..., accum, true> / its job-queue twin
+                            k_mega_queue<integrator, trav, ms> ran in its place (one-shot renders only) */
 } rtr_kernel_record;
 /* size_of_out must be sizeof(rtr_kernel_record) */
 int rtr_test_last_kernel(rtr_context* ctx, rtr_kernel_record* out, size_t size_of_out);
+
+/* Which gather kernel the context's last rtr_gather_* call launched (of its last slice), recorded on the host as it was
+ * enqueued: k_gather_li<integ, trav> of a radiance gather, or with integ = -1 k_gather_any<trav, broadcast> of an occlusion
+ * gather.  trav is the RT_TRAV_* template value, after the substitution of the media kernel for the reference-order walk
+ * of integrators 0, 2 and 3; lg is log2 of the lanes that share a point.  trav = -1: no gather has launched anything yet. */
+typedef struct rtr_gather_record {
+    int32_t integ, trav, broadcast, lg;
+} rtr_gather_record;
+/* size_of_out must be sizeof(rtr_gather_record) */
+int rtr_test_last_gather(rtr_context* ctx, rtr_gather_record* out, size_t size_of_out);
 
 /* What the library makes of a scene before anything reaches a device: the validator, the host-only lowering
  * (csrc/rt_lower.h: lower_scene) and the two decisions every launch hangs on -- pick_trav and, for `integrator` and the

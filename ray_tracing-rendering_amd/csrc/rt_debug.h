@@ -28,6 +28,15 @@ struct rtr_debug_kernel {
     int shade_phases; /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched; 0 for the megakernel */
     int lean, quadlit, sort, media, machine; /* wavefront: the WavefrontPlan fields; 0 for the megakernel */
     int accum;      /* megakernel: the ACC template value of k_mega (0 one-shot, 1 accumulator pass, 2 with moments) */
+    int pair;       /* megakernel: k_mega's pair-cast instantiation (PAIR = true) */
+    int queue;      /* megakernel: k_mega_queue<integrator, trav, ms>, the job-queue twin of the pair-cast kernel, ran instead */
+};
+/* the gather kernel the last rtr_gather_* call launched (of its last slice), recorded on the host when it is enqueued */
+struct rtr_debug_gather {
+    int integ;     /* k_gather_li<integ, trav>; -1: occlusion, k_gather_any<trav, broadcast> */
+    int trav;      /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of rtr_gather_launch; -1: no gather yet */
+    int broadcast; /* k_gather_any<T, true> */
+    int lg;        /* log2 of the lanes that share a point (gather_lg of the samples) */
 };
 struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     double L[3];
@@ -53,6 +62,7 @@ int rtr_debug_scene_plan(const rtr_scene_desc* scene, int integrator, int flags,
 int rtr_debug_frame_shapes(const rtr_scene_desc* scene, int32_t* shapes, int64_t cap, int32_t* n_inst);
 int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t size_of_view);
 int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
+int rtr_debug_last_gather(rtr_context* ctx, rtr_debug_gather* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);
 void rtr_debug_set_error(rtr_context* ctx, const char* msg); /* rtr_last_error() of a failing rtr_test_* call */
 }

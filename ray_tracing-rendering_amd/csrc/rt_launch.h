@@ -23,6 +23,15 @@ struct LaunchedKernel {
     int ms = -1;     /* RT_MS_* of k_mega / of the wf_shade stage */
     int sorted = 0;  /* k_mega's sorted instantiation / wf_shade<..., true> */
     int phases = 0;  /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched */
+    int pair = 0;    /* k_mega's pair-cast instantiation (MegaVariant::pair) */
+    int queue = 0;   /* k_mega_queue, the job-queue twin, ran in place of k_mega (MegaLaunch::queue) */
+};
+/* which gather kernel a launch ran, recorded on the host (rtr_debug_last_gather) */
+struct LaunchedGather {
+    int integ = -1;    /* k_gather_li<integ, trav>; -1: k_gather_any<trav, broadcast> */
+    int trav = -1;     /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution; -1: nothing launched yet */
+    int broadcast = 0; /* k_gather_any<T, true> */
+    int lg = 0;        /* GatherK::lg: log2 of the lanes that share a point */
 };
 
 /* the k_mega<integ, trav, ms, sorted, ACC, pair> a render runs (ACC follows from the call: MegaLaunch::accum; a one-shot
@@ -67,7 +76,7 @@ struct GatherLaunch {
     bool broadcast; /* occlusion: k_gather_any<T, true> */
     hipStream_t stream;
 };
-int rtr_gather_launch(const GatherLaunch& L, std::string& err);
+int rtr_gather_launch(const GatherLaunch& L, LaunchedGather* launched, std::string& err);
 /* RTR_OK, or RTR_ERR_INVALID with the reason in `err` */
 int rtr_gather_params_check(const rtr_gather_params* p, std::string& err);
 

@@ -68,6 +68,7 @@ struct rtr_context {
     bool in_flight = false; /* stream-ordered work of a render call is queued whose statistics are not pending (an error return) */
     rtr_render_stats stats{};
     rtr_debug_kernel last_kernel{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0}; /* rtr_debug_last_kernel */
+    LaunchedGather last_gather{};                                       /* rtr_debug_last_gather */
     /* Cancel.  Renders are numbered; rtr_cancel() covers every render issued so far: it stores the newest
      * id in `cancelled_upto` and in the device word the kernels poll.  A render issued afterwards carries a
      * larger id, so nothing has to be reset between renders and a cancel that arrives while a render waits
@@ -569,7 +570,8 @@ int launch_mega(rtr_context* c, const RenderK& P, int integrator, int trav_in, b
     case RTR_INTEGRATOR_PATH: rc = rtr_mega_launch_rr_path(L, c->err); break;
     default: rc = rtr_mega_launch_pbr_nee(L, c->err); break;
     }
-    if (rc == RTR_OK && !dry && launched) launched->trav = v.trav, launched->ms = v.ms, launched->sorted = v.sorted;
+    if (rc == RTR_OK && !dry && launched)
+        launched->trav = v.trav, launched->ms = v.ms, launched->sorted = v.sorted, launched->pair = v.pair, launched->queue = L.queue;
     return rc;
 }
 
@@ -1079,7 +1081,7 @@ static int render_core(rtr_context* c, const rtr_render_params* p, double* d_rgb
             HIPCHK(c, hipMemsetAsync(c->b_done.p, 0, done_bytes, c->stream));
         if ((rc = launch_mega(c, P, p->integrator, trav, false, nullptr, p->flags, &c->stats.flags_in_effect, &launched))) return rc;
         c->last_kernel = rtr_debug_kernel{pipeline, p->integrator, launched.trav, launched.ms, launched.sorted, 0, 0, 0, 0, 0, 0,
-                                          acc ? (acc->moments ? 2 : 1) : 0};
+                                          acc ? (acc->moments ? 2 : 1) : 0, launched.pair, launched.queue};
         if (acc) {
             hipLaunchKernelGGL(k_accum_commit, dim3((unsigned)P.n_tiles), dim3(RTR_BLOCK), 0, c->stream, P,
                                static_cast<double*>(acc->d_sum.p), static_cast<double*>(acc->moments ? acc->d_q.p : nullptr),
@@ -1894,6 +1896,11 @@ int rtr_debug_frame_shapes(const rtr_scene_desc* s, int32_t* shapes, int64_t cap
     for (int k = 0; k < L.ds.n_finst && k < cap; ++k) shapes[k] = L.cs.inst[(size_t)k].shape;
     return RTR_OK;
 }
+int rtr_debug_last_gather(rtr_context* c, rtr_debug_gather* out, size_t size) {
+    if (!c || !out || size != sizeof(rtr_debug_gather)) return RTR_ERR_INVALID;
+    *out = rtr_debug_gather{c->last_gather.integ, c->last_gather.trav, c->last_gather.broadcast, c->last_gather.lg};
+    return RTR_OK;
+}
 int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {
     if (!c || !out || size != sizeof(rtr_debug_kernel)) return RTR_ERR_INVALID;
     *out = c->last_kernel;
@@ -2091,7 +2098,7 @@ int gather_launch(rtr_context* c, const rtr_render_params* rp, const rtr_gather_
     if (!rp && !(gp->t_min >= 0x1p-100)) L.ds.shared_div = 0; /* the plain divisions, as k_query_* per wave */
     L.K = GatherK{d_pts, d_out, (long long)n, gp->samples, gather_lg(gp->samples), gp->seed, point_base, gp->time, gp->t_min,
                   gp->t_max, rp ? rp->max_depth : 0, rp ? rp->rr_start_depth : 0};
-    return rtr_gather_launch(L, c->err);
+    return rtr_gather_launch(L, &c->last_gather, c->err);
 }
 
 int gather_host(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_gather_point* pts,

@@ -1,7 +1,7 @@
 /*
  * rtr_gather.hip -- hemisphere gathers (include/rtr_hip.h: rtr_gather_*): the k_gather_any / k_gather_li instantiations and
  * their launcher, and the host-only pieces that need no context (rtr_gather_defaults, rtr_gather_ray, the parameter
- * check).  A translation unit of its own so that the 22 kernels compile beside rtr_capi.hip, which holds the entries.
+ * check).  A translation unit of its own so that the 27 kernels (10 k_gather_any, 17 k_gather_li) compile beside rtr_capi.hip, which holds the entries.
  */
 #include "rt_kernels.h"
 #include "rt_launch.h"
@@ -39,7 +39,7 @@ bool launch_li(Travs travs, int trav, const GatherLaunch& L, std::string& err, i
 
 } // namespace
 
-int rtr_gather_launch(const GatherLaunch& L, std::string& err) {
+int rtr_gather_launch(const GatherLaunch& L, LaunchedGather* launched, std::string& err) {
     int rc = RTR_OK, trav = L.trav;
     bool found;
     if (L.integ < 0) {
@@ -63,6 +63,7 @@ int rtr_gather_launch(const GatherLaunch& L, std::string& err) {
         err = "no gather kernel for traversal " + std::to_string(trav);
         return RTR_ERR_UNSUPPORTED;
     }
+    if (rc == RTR_OK && launched) *launched = LaunchedGather{L.integ < 0 ? -1 : L.integ, trav, L.integ < 0 && L.broadcast, L.K.lg};
     return rc;
 }
 

@@ -3,8 +3,9 @@
  * times with -DRTR_MEGA_GROUP=0/1/2 so the variants build in parallel.
  *
  * Each group dispatches over the explicit list of its instantiations at the end of this file, one Row per
- * (I, T, M[, S][, PAIR]); every row stands for its three ACC twins, a PAIR row also for its job-queue twin k_mega_queue.  tests/test_kernel_variants.py holds the same
- * table and renders each row against the oracle: a variant added or removed here goes into that table too.
+ * (I, T, M[, S][, PAIR]); every row stands for its three ACC twins, a PAIR row also for its job-queue twin k_mega_queue:
+ * 46 rows (22 + 16 + 8), so 138 k_mega and 3 k_mega_queue, 141 kernels.  tests/test_kernel_variants.py holds the same
+ * table and renders each of the 141 against the oracle: a variant added or removed here goes into that table too.
  */
 #include "rt_kernels.h"
 #include "rt_launch.h"

@@ -35,6 +35,7 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
+                "rtr_test_last_gather",
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
                 "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host")
 _TEST_LIB = None
@@ -50,7 +51,12 @@ class SceneInfoC(C.Structure):
 class KernelRecordC(C.Structure):
     """rtr_kernel_record of include/rtr_hip_test.h"""
     _fields_ = [(name, C.c_int32) for name in ("pipeline", "integrator", "trav", "ms", "sorted", "shade_phases", "lean",
-                                               "quadlit", "sort", "media", "machine", "accum")]
+                                               "quadlit", "sort", "media", "machine", "accum", "pair", "queue")]
+
+
+class GatherRecordC(C.Structure):
+    """rtr_gather_record of include/rtr_hip_test.h"""
+    _fields_ = [(name, C.c_int32) for name in ("integ", "trav", "broadcast", "lg")]
 
 
 class ScenePlanC(C.Structure):
@@ -198,6 +204,7 @@ def test_lib():
     T.rtr_test_issue_rates.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     T.rtr_test_shared_division.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
+    T.rtr_test_last_gather.argtypes = [vp, C.POINTER(GatherRecordC), C.c_size_t]
     T.rtr_test_temporal_planes.argtypes = [vp] + [C.c_int32] * 6 + [C.POINTER(A.CameraC), C.POINTER(A.CameraC), C.c_int,
                                                                     C.POINTER(A.TemporalParamsC)] + [vp] * 8
     T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64,
@@ -739,6 +746,15 @@ class Context:
         if r.pipeline < 0:
             return None
         return {name: int(getattr(r, name)) for name, _ in KernelRecordC._fields_}
+
+    def last_gather(self):
+        """The gather kernel the last gather call launched (include/rtr_hip_test.h: rtr_gather_record), as a dict; None
+        before any gather of this context launched one."""
+        r = GatherRecordC()
+        self._chk(test_lib().rtr_test_last_gather(self._h, C.byref(r), C.sizeof(r)))
+        if r.trav < 0:
+            return None
+        return {name: int(getattr(r, name)) for name, _ in GatherRecordC._fields_}
 
     def reference_order(self, on):
         """Force the reference-order traversal for rtr_test_hits (renders use params.flags)."""

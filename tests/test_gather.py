@@ -3,7 +3,12 @@ GPU.  Occlusion counts are held to the pinned CPU oracle (rto_hits on the rays o
 tests/_gather_ref.py) exactly and the bent normal to the restatement's reduction bit for bit; scenes with media to the
 library's own any-hit query on the same rays; radiance to the reduction of rtr_li_rays on the same rays and states.  Batch
 shapes, bad points, the device entries behind a queued render, renders and accumulator passes around a gather, the
-parameter checks and the command-line driver complete the contract."""
+parameter checks and the command-line driver complete the contract.
+
+csrc/rtr_gather.hip holds 10 k_gather_any<traversal, broadcast> and 17 k_gather_li<integrator, traversal> (GATHER_TABLE
+below restates its lists); which one a call launched, and over how many lanes per point, the context records on the host
+(Context.last_gather).  The last test asserts that the tests of this module launched, and compared, every one of them:
+run the module as a whole."""
 import ctypes as C
 import os
 import subprocess
@@ -22,6 +27,44 @@ pytestmark = pytest.mark.gpu
 
 SEED = 7
 SAMPLES = (1, 5, 64, 100)
+# lanes per point 2, 4, 16 and 32 (the xor butterfly of gather_end over a part of a wave), each full and with a ragged
+# last round, and a second and a third round at 64
+WIDTH_SAMPLES = (2, 3, 4, 9, 16, 17, 32, 33, 65, 129)
+
+# RT_TRAV_* of csrc/rt_device.h
+EXACT, MEDIA, FAST, PROGRAM, FLAT, TOP, PROGRAM_EXT, FLAT_GUARD = range(8)
+TRAV_NAME = ["EXACT", "MEDIA", "FAST", "PROGRAM", "FLAT", "TOP", "PROGRAM_EXT", "FLAT_GUARD"]
+# the TravSets of csrc/rtr_gather.hip: TravsTop (k_gather_any, both forms), TravsLi (MIS = 4, RR = 1), TravsN1 (0, 2, 3)
+TRAVS_TOP = (FAST, TOP, PROGRAM_EXT, MEDIA, EXACT)
+TRAVS_LI = (FAST, PROGRAM_EXT, MEDIA, EXACT)
+TRAVS_N1 = (FAST, PROGRAM_EXT, MEDIA)
+# (integrator or -1 for k_gather_any, traversal, broadcast)
+GATHER_TABLE = {(-1, t, b) for t in TRAVS_TOP for b in (0, 1)} | {(i, t, 0) for i in (4, 1) for t in TRAVS_LI} | \
+               {(i, t, 0) for i in (0, 2, 3) for t in TRAVS_N1}
+assert len(GATHER_TABLE) == 10 + 17
+SEEN = set()  # what the tests of this module launched
+
+
+def gather_name(g):
+    i, t, b = g
+    return "k_gather_any<%s, %s>" % (TRAV_NAME[t], "true" if b else "false") if i < 0 else "k_gather_li<%d, %s>" % (i, TRAV_NAME[t])
+
+
+def _note(ctx, samples, radiance=None):
+    """Enters the gather kernel the last call launched into SEEN and returns (integrator, traversal, broadcast).  The lanes
+    per point are min(64, the next power of two >= samples) (include/rtr_hip.h), restated here."""
+    g = ctx.last_gather()
+    assert g is not None
+    width = 1
+    while width < samples and width < 64:
+        width *= 2
+    assert 1 << g["lg"] == width, (samples, g)
+    if radiance is not None:
+        assert (g["integ"] >= 0) == radiance and (radiance or g["integ"] == -1), g
+    assert not (g["broadcast"] and g["integ"] >= 0), g
+    name = (g["integ"], g["trav"], g["broadcast"])
+    SEEN.add(name)
+    return name
 
 
 @pytest.fixture(scope="module")
@@ -70,7 +113,13 @@ def test_occlusion_equals_the_oracle(ctx, sid, t_max, samples):
     count, v = _oracle(sid, samples, t_max)
     for order in (False, True):
         out = ctx.gather_occlusion(p, n, samples=samples, seed=SEED, t_max=t_max, reference_order=order)
+        assert _note(ctx, samples, False) == (-1, EXACT if order else FAST, 0)
         _assert_occlusion(out, count, v, (sid, t_max, samples, order))
+
+
+@pytest.mark.parametrize("samples", WIDTH_SAMPLES)
+def test_occlusion_equals_the_oracle_at_every_group_width(ctx, samples):
+    test_occlusion_equals_the_oracle(ctx, 21, np.inf, samples)
 
 
 @pytest.mark.parametrize("t_min", (0.0, -1.0))
@@ -96,6 +145,7 @@ def test_scene_with_media_equals_the_any_hit_query(ctx):
         count, v = GR.occlusion(rays["direction"], occ.reshape(rays.shape))
         assert ((count > 0) & (count < 64)).any()
         out = ctx.gather_occlusion(p, n, samples=64, seed=SEED, reference_order=order)
+        assert _note(ctx, 64, False) == (-1, MEDIA if order else PROGRAM_EXT, 0)
         _assert_occlusion(out, count, v, order)
 
 
@@ -113,7 +163,49 @@ def test_random_scenes_equal_the_oracle(ctx, seed, kw, what):
     ctx.upload(sc)
     for order in (False, True):
         out = ctx.gather_occlusion(p, n, samples=64, seed=SEED, reference_order=order)
+        want = {("top_trees", False): TOP, ("top_trees", True): EXACT, ("inverted_boxes", False): PROGRAM_EXT,
+                ("inverted_boxes", True): MEDIA}[what, order]  # (a guarded hollow sphere: a step program / the media walk)
+        assert _note(ctx, 64, False) == (-1, want, 0)
         _assert_occlusion(out, count, v, (seed, order))
+
+
+_SCENES = {}
+
+
+def _scene_points(key, m):
+    """(scene, p, n) with ``m`` surface points: golden scene ``key``, or the random scenes "top" (200 objects under a top
+    tree) and "hollow" (a guarded hollow sphere) with the oracle's hits of random rays"""
+    if key not in _SCENES:
+        if isinstance(key, int):
+            _SCENES[key] = (G.scene(key), None)
+        else:
+            seed, kw, what = {"top": (19, dict(n_objects=200), "top_trees"), "hollow": (16, dict(hollow=True), "inverted_boxes")}[key]
+            sc = R.random_scene(seed, **kw)
+            assert rtr.native.validate_scene(sc)[what] > 0
+            hits = G.oracle_records(sc, "rto_hits", R.random_rays(seed, 512))
+            _SCENES[key] = (sc, hits[hits["hit"] == 1])
+    sc, hits = _SCENES[key]
+    if hits is None:
+        return (sc,) + GR.golden_points(key, m)
+    assert len(hits) >= m
+    return sc, hits["p"][:m].copy(), hits["n"][:m].copy()
+
+
+def _radiance_case(ctx, key, integrator, samples, order, m=16):
+    """one radiance gather against the contract's own reference: GR.reduce of rtr_li_rays on the rays of rtr_gather_ray with
+    the same render params, flags included.  Returns (the kernel's name, the output records)."""
+    sc, p, n = _scene_points(key, m)
+    ctx.upload(sc)
+    prm = A.make_params(64, 64, 1, integrator=integrator, flags=A.FLAG_REFERENCE_ORDER if order else 0)
+    rays = ctx.gather_rays(p, n, samples=samples, seed=SEED, time=0.25).reshape(-1)
+    L = ctx.li_rays(prm, rays["origin"], rays["direction"], rays["time"], rays["rng_state"]).reshape(m, samples, 3)
+    # (scene 9 has no light list and a black background: five samples at sixteen points can all miss its one emitter)
+    assert (L != 0).any() or (key == 9 and samples < 64), (key, integrator, samples)
+    out = ctx.gather_radiance(prm, p, n, samples=samples, seed=SEED, time=0.25)
+    name = _note(ctx, samples, True)
+    assert np.array_equal(_bits(out["v"]), _bits(GR.reduce(L))), (key, integrator, samples, order)
+    assert (out["count"] == samples).all() and (out["valid"] == 1).all()
+    return name, out
 
 
 @pytest.mark.parametrize("samples", (5, 64))
@@ -126,8 +218,40 @@ def test_radiance_equals_the_reduction_of_li_rays(ctx, sid, integrator, samples)
     L = ctx.li_rays(prm, rays["origin"], rays["direction"], rays["time"], rays["rng_state"]).reshape(16, samples, 3)
     assert (L != 0).any()
     out = ctx.gather_radiance(prm, p, n, samples=samples, seed=SEED, time=0.25)
+    assert _note(ctx, samples, True) == (integrator, PROGRAM_EXT if sid == 9 else FAST, 0)
     assert np.array_equal(_bits(out["v"]), _bits(GR.reduce(L))), (sid, integrator, samples)
     assert (out["count"] == samples).all() and (out["valid"] == 1).all()
+
+
+@pytest.mark.parametrize("samples", (5, 64))
+@pytest.mark.parametrize("order", (False, True))
+@pytest.mark.parametrize("integrator", range(5))
+@pytest.mark.parametrize("key", (9, "hollow"))
+def test_radiance_with_media_and_guarded_steps(ctx, key, integrator, order, samples):
+    """Every integrator on a scene with media and on one with a guarded hollow sphere: the general program kernel, and with
+    FLAG_REFERENCE_ORDER in the render params the media walk (k_gather_li<I, PROGRAM_EXT> / <I, MEDIA>)."""
+    name, _ = _radiance_case(ctx, key, integrator, samples, order)
+    assert name == (integrator, MEDIA if order else PROGRAM_EXT, 0)
+
+
+@pytest.mark.parametrize("samples", (5, 64))
+@pytest.mark.parametrize("sid,integrator", [(21, 0), (21, 1), (21, 2), (21, 3), (21, 4), (23, 1), (23, 4)])
+def test_radiance_in_reference_order(ctx, sid, integrator, samples):
+    """FLAG_REFERENCE_ORDER on scenes without media: k_gather_li<I, EXACT> for MIS and RR; integrators 0, 2 and 3 have no
+    such kernel and take the media kernel in its place (rtr_gather_launch).  On scene 21 the walk in reference order and
+    the compiled traversal give the same bits (tests/test_gpu_parity.py holds the two to each other there)."""
+    name, out = _radiance_case(ctx, sid, integrator, samples, True)
+    assert name == (integrator, EXACT if integrator in (1, 4) else MEDIA, 0)
+    if sid == 21:
+        plain_name, plain = _radiance_case(ctx, sid, integrator, samples, False)
+        assert plain_name == (integrator, FAST, 0)
+        assert _same_bits(out, plain), (integrator, samples)
+
+
+@pytest.mark.parametrize("samples", (2, 3, 4, 9, 16, 17, 32, 33))
+def test_radiance_at_every_group_width(ctx, samples):
+    """2, 4, 16 and 32 lanes per point, each full and with a ragged last round"""
+    assert _radiance_case(ctx, 21, 4, samples, False)[0] == (4, FAST, 0)
 
 
 def test_a_point_facing_away_from_the_scene_sees_the_background(ctx):
@@ -173,6 +297,46 @@ def test_batch_shapes(ctx, samples):
         assert _same_bits(split, whole), cut
     assert not _same_bits(ctx.gather_occlusion(pts[64:].copy(), samples=samples, seed=SEED), whole[64:])  # (base matters)
     assert _same_bits(pts, keep)
+
+
+@pytest.mark.parametrize("samples", (3, 17))  # G = 4: sixteen points per wave; G = 32: two
+def test_batch_shapes_with_several_points_per_wave(ctx, samples):
+    """Batches that end inside a wave, at its end and just behind it, through the device entries (the host entries refuse
+    a bad point; the kernels answer it with valid = 0): a bad point in a group that shares its wave with good ones."""
+    import torch
+    ctx.upload(G.scene(21))
+    p, n = GR.golden_points(21)
+    count, v = _oracle(21, samples, np.inf)
+    pts = _points(p, n)[:33]
+    whole = ctx.gather_occlusion(pts, samples=samples, seed=SEED)
+    assert _note(ctx, samples, False) == (-1, FAST, 0)
+    _assert_occlusion(whole, count[:33], v[:33], samples)
+    prm = A.make_params(64, 64, 1)
+    whole_rad = ctx.gather_radiance(prm, pts, samples=samples, seed=SEED)
+    assert _note(ctx, samples, True) == (4, FAST, 0)
+    rays = ctx.gather_rays(pts, samples=samples, seed=SEED).reshape(-1)
+    L = ctx.li_rays(prm, rays["origin"], rays["direction"], rays["time"], rays["rng_state"]).reshape(33, samples, 3)
+    assert np.array_equal(_bits(whole_rad["v"]), _bits(GR.reduce(L)))
+    bad = pts.copy()
+    bad["n"][5] = 0.0          # wave 0 at both widths
+    bad["p"][16, 1] = np.nan   # G = 4: wave 1 (its first group); G = 32: wave 8
+    d_pts = torch.from_numpy(bad.view(np.uint8).copy()).cuda()
+    size = A.GATHER_OUT_DTYPE.itemsize
+    for m in (0, 1, 15, 16, 17, 31, 32, 33):
+        ok = ~np.isin(np.arange(m), (5, 16))
+        for radiance, want in ((False, whole), (True, whole_rad)):
+            d_out = torch.full(((m + 1) * size,), 0xA5, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            if radiance:
+                ctx.gather_radiance_into(prm, d_pts.data_ptr(), d_out.data_ptr(), m, samples=samples, seed=SEED, blocking=True)
+            else:
+                ctx.gather_occlusion_into(d_pts.data_ptr(), d_out.data_ptr(), m, samples=samples, seed=SEED, blocking=True)
+            raw = d_out.cpu().numpy()
+            got = raw[:m * size].view(A.GATHER_OUT_DTYPE)
+            assert (raw[m * size:] == 0xA5).all(), (m, radiance)  # nothing behind the batch is written
+            assert _same_bits(got[ok], want[:m][ok]), (m, radiance)
+            assert _same_bits(got[~ok], np.zeros(int((~ok).sum()), dtype=A.GATHER_OUT_DTYPE)), (m, radiance)
+    assert _same_bits(d_pts.cpu().numpy(), bad.view(np.uint8))
 
 
 def test_bad_points(ctx):
@@ -333,23 +497,50 @@ def test_cli_ao_equals_the_python_route(ctx, tmp_path):
         assert r.returncode == 2, extra
 
 
+# (scene, reference order) -> the traversal of k_gather_any: all five of its list
+BROADCAST_CASES = [(21, False, FAST), (9, False, PROGRAM_EXT), ("top", False, TOP), ("hollow", False, PROGRAM_EXT),
+                   (21, True, EXACT), (9, True, MEDIA)]
+
+
 def test_broadcast_form_gives_the_same_bits(ctx, monkeypatch):
     """k_gather_any<T, true> (RTR_GATHER_BROADCAST=1: one load per group and a broadcast), the form tools/time_gather.py
-    measures against the one the library launches; bad points and a ragged last wave included."""
+    measures against the one the library launches, for every traversal; bad points and a ragged last wave included.  The
+    form the library launches is held to the oracle (or, with media, to the any-hit query) on the same points first."""
     import torch
-    ctx.upload(G.scene(21))
-    p, n = GR.golden_points(21, 257)
-    pts = _points(p, n)
-    pts["n"][9] = 0.0
-    pts["p"][130, 2] = np.nan
-    d_pts = torch.from_numpy(pts.view(np.uint8).copy()).cuda()
-    for samples in (5, 100):
-        got = []
-        for form in ("0", "1"):
-            monkeypatch.setenv("RTR_GATHER_BROADCAST", form)
-            d_out = torch.full((257 * A.GATHER_OUT_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            ctx.gather_occlusion_into(d_pts.data_ptr(), d_out.data_ptr(), 257, samples=samples, seed=SEED, blocking=True)
-            got.append(d_out.cpu().numpy().view(A.GATHER_OUT_DTYPE))
-        assert _same_bits(got[0], got[1]), samples
-        assert got[0]["valid"].sum() == 255 and got[0]["valid"][9] == 0 and got[0]["valid"][130] == 0
+    for key, order, trav in BROADCAST_CASES:
+        sc, p, n = _scene_points(key, 257)
+        ctx.upload(sc)
+        pts = _points(p, n)
+        rays = ctx.gather_rays(pts, samples=5, seed=SEED)
+        if key == 9:
+            occ = ctx.query_occluded(rays.reshape(-1), reference_order=order).reshape(rays.shape) != 0
+        else:
+            _, occ = GR.oracle_blocked(sc, p, n, 5, seed=SEED)
+        want5 = GR.occlusion(rays["direction"], occ)
+        pts["n"][9] = 0.0
+        pts["p"][130, 2] = np.nan
+        good = ~np.isin(np.arange(257), (9, 130))
+        d_pts = torch.from_numpy(pts.view(np.uint8).copy()).cuda()
+        for samples in (5, 100):
+            got = []
+            for form in ("0", "1"):
+                monkeypatch.setenv("RTR_GATHER_BROADCAST", form)
+                d_out = torch.full((257 * A.GATHER_OUT_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                ctx.gather_occlusion_into(d_pts.data_ptr(), d_out.data_ptr(), 257, samples=samples, seed=SEED,
+                                          reference_order=order, blocking=True)
+                assert _note(ctx, samples, False) == (-1, trav, int(form)), (key, order)
+                got.append(d_out.cpu().numpy().view(A.GATHER_OUT_DTYPE))
+            assert _same_bits(got[0], got[1]), (key, order, samples)
+            assert got[0]["valid"].sum() == 255 and got[0]["valid"][9] == 0 and got[0]["valid"][130] == 0
+            if samples == 5:
+                _assert_occlusion(got[0][good], want5[0][good], want5[1][good], (key, order))
+
+
+def test_every_gather_kernel_ran_and_was_compared():
+    """The union of what the tests above launched is the whole of GATHER_TABLE: every k_gather_any<T, broadcast> and every
+    k_gather_li<I, T> of csrc/rtr_gather.hip ran under a test that compares its output."""
+    missing = sorted(map(gather_name, GATHER_TABLE - SEEN))
+    extra = sorted(map(gather_name, SEEN - GATHER_TABLE))
+    print("gather kernels: %d / %d" % (len(SEEN & GATHER_TABLE), len(GATHER_TABLE)))
+    assert not missing and not extra, "gather kernels not launched: %s; launched but not in the table: %s" % (missing, extra)

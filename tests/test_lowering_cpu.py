@@ -278,7 +278,7 @@ def test_variant_scenes_get_the_kernel_they_aim_at(name):
     sc = KV._scene(name)
     p = plan_of(sc, integrator=KV.I_MIS)
     assert plan_class(p) == KV.material_class(sc) == KV.SCENES[name][1]
-    assert (KV.I_MIS, p["mega_trav"], p["mega_ms"], p["mega_sorted"]) in KV.MEGA_TABLE
+    assert (KV.I_MIS, p["mega_trav"], p["mega_ms"], p["mega_sorted"], p["mega_pair"]) in KV.MEGA_ROWS
     want = _mis_trav_by_name(name)
     if want is not None:
         assert p["mega_trav"] == want, (KV.TRAV_NAME[p["mega_trav"]], KV.TRAV_NAME[want])
@@ -286,6 +286,51 @@ def test_variant_scenes_get_the_kernel_they_aim_at(name):
     assert p["fast_ok"] == info["fast_ok"] and p["has_media"] == info["has_media"] and p["fast_stack_words"] == info["fast_stack_words"]
     assert p["top_tree"] == (info["top_trees"] > 0 and info["fast_ok"])
     assert p["n_steps"] == (info["program_steps"] or int(info["fast_ok"])) and p["n_refs"] == info["fast_refs"]
+
+
+@pytest.mark.parametrize("name", sorted(KV.PAIRED))
+def test_flat_mis_scenes_with_and_without_the_pair_cast(name):
+    """Every flat MIS class has a pair-cast scene and one that is not (KV.PAIRED), and each flag moves a MIS render to the
+    kernel the matrix expects: FLAG_SPLIT_CASTS to the row without the pair cast, FLAG_SORTED_SHADING to the sorted row
+    where there is one (QuadLights-only: sorted kernels do not pair), FLAG_STATIC_GRID to no other row."""
+    sc = KV._scene(name)
+    ms = {"lean": KV.LEAN, "quadlit": KV.QUADLIT, "full": KV.FULL}[KV.SCENES[name][1]]
+    pair = int(KV.PAIRED[name])
+    sortable = ms == KV.QUADLIT  # the one sorted row of the flat kernels: Row<MIS, RT_TRAV_FLAT, RT_MS_QUADLIT, true>
+    want = {0: (0, pair), A.FLAG_STATIC_GRID: (0, pair), A.FLAG_SPLIT_CASTS: (0, 0),
+            A.FLAG_SORTED_SHADING: (1, 0) if sortable else (0, pair)}
+    for flags, (srt, pr) in want.items():
+        p = plan_of(sc, integrator=KV.I_MIS, flags=flags)
+        assert plan_class(p) == KV.SCENES[name][1] and p["pair_cast"] == pair, (name, flags)
+        assert (p["mega_trav"], p["mega_ms"], p["mega_sorted"], p["mega_pair"]) == (FLAT, ms, srt, pr), (name, flags, p)
+    for integ in (KV.I_PATH, KV.I_RR, KV.I_PBR, KV.I_NEE):  # only MIS casts a shadow ray and a closest-hit ray together
+        assert not plan_of(sc, integrator=integ)["mega_pair"], (name, integ)
+    n_moving = int((sc.nodes["type"] == A.NODE_MOVING_SPHERE).sum())
+    n_inst = len(KV.instance_refs(sc))
+    if pair:
+        assert n_moving == 0 and n_inst <= NO_BOX_MAX, (name, n_moving, n_inst)  # (the rule of pair_cast_allowed)
+    else:
+        assert n_moving > 0 or n_inst > NO_BOX_MAX, (name, n_moving, n_inst)
+
+
+def test_the_variant_matrix_reaches_every_megakernel_by_name(monkeypatch):
+    """What tests/test_kernel_variants.py will launch on a GPU, computed here from native.scene_plan alone: every scene,
+    every integrator, every flag set, one-shot and as an accumulator without and with moments (KV.planned_mega_names; the
+    GPU matrix asserts per scene that exactly these ran).  The union is the whole table of 141 names, so a scene change
+    that stops reaching a kernel fails here, by name, before anyone has a GPU."""
+    names = set()
+    for name in sorted(KV.SCENES):
+        names |= KV.planned_mega_names(KV._scene(name))
+    flat = len(names)
+    monkeypatch.setenv("RTR_TOP_MIN", "2")  # read at every lowering: the RT_TRAV_TOP rows
+    for name in KV.TOP_SCENES:
+        names |= KV.planned_mega_names(KV._scene(name))
+    monkeypatch.delenv("RTR_TOP_MIN")
+    missing = sorted(map(KV.mega_name, KV.MEGA_TABLE - names))
+    extra = sorted(map(KV.mega_name, names - KV.MEGA_TABLE))
+    print("planned megakernel names: %d / %d (%d without the forced top trees)" % (len(names & KV.MEGA_TABLE), len(KV.MEGA_TABLE), flat))
+    assert len(KV.MEGA_TABLE) == 141
+    assert not missing and not extra, "no scene of the matrix reaches: %s; not in the table: %s" % (missing, extra)
 
 
 def test_scene_plan_rejects_what_the_validator_rejects():
