@@ -56,7 +56,7 @@ int rtr_test_last_gather(rtr_context* ctx, rtr_gather_record* out, size_t size_o
 
 /* What the library makes of a scene before anything reaches a device: the validator, the host-only lowering
  * (csrc/rt_lower.h: lower_scene) and the two decisions every launch hangs on -- pick_trav and, for `integrator` and the
- * render `flags`, mega_variant (csrc/rtr_capi.hip).  Needs no context and no GPU.  RT_TRAV_*, RT_MS_*, RT_TIE_FLAG and
+ * render `flags`, mega_variant (csrc/rt_select.h).  Needs no context and no GPU.  RT_TRAV_*, RT_MS_*, RT_TIE_FLAG and
  * RT_GUARD_FLAG are those of csrc/rt_device.h. */
 typedef struct rtr_scene_plan {
     int32_t fast_ok, has_media;                /* rtr_scene_info */

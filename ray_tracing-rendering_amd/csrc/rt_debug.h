@@ -13,7 +13,7 @@ struct rtr_debug_view {
     DScene ds;          /* device pointers of the uploaded scene */
     hipStream_t stream; /* the context's stream */
     int device, n_cus, n_materials;
-    int trav;           /* RT_TRAV_* template value of the per-ray kernels for a call with `flags` (per_ray_trav, rtr_capi.hip) */
+    int trav;           /* RT_TRAV_* template value of the per-ray kernels for a call with `flags` (per_ray_trav, rt_select.h) */
     size_t stack_bytes; /* LDS traversal stack per workgroup of that traversal */
     int flat_trav;      /* RT_TRAV_FLAT / RT_TRAV_FLAT_GUARD where the megakernel of such a call runs a flat kernel, else -1 */
 };
@@ -34,7 +34,7 @@ struct rtr_debug_kernel {
 /* the gather kernel the last rtr_gather_* call launched (of its last slice), recorded on the host when it is enqueued */
 struct rtr_debug_gather {
     int integ;     /* k_gather_li<integ, trav>; -1: occlusion, k_gather_any<trav, broadcast> */
-    int trav;      /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of rtr_gather_launch; -1: no gather yet */
+    int trav;      /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no gather yet */
     int broadcast; /* k_gather_any<T, true> */
     int lg;        /* log2 of the lanes that share a point (gather_lg of the samples) */
 };
@@ -43,7 +43,7 @@ struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     uint32_t rng_exit;
     int32_t n_closest, n_shadow, pad;
 };
-/* what lowering (rt_lower.h) and the variant decisions of rtr_capi.hip make of a scene, without a device; the layout of
+/* what lowering (rt_lower.h) and the variant decisions of rt_select.h make of a scene, without a device; the layout of
  * rtr_scene_plan (include/rtr_hip_test.h), which documents the members */
 struct rtr_debug_plan {
     int32_t fast_ok, has_media, flat_scene, flat_guarded, lean_materials, quad_lights_only, uv_order_dependent, machine_ok;

@@ -519,7 +519,7 @@ struct Stack {
     RT_DEV Real getd(int k) const { return __hiloint2double(get(k + 1), get(k)); }
 };
 
-/* stack words used by the wrapper frames (must match the analysis in rtr_capi.hip) */
+/* stack words used by the wrapper frames (must match the analysis in rt_validate.h) */
 #define RT_FRAME_TRANSLATE 8 /* o.xyz (6) + hits + marker */
 #define RT_FRAME_ROTATE 14   /* o.x o.z d.x d.z inv.x inv.z (12) + hits + marker */
 #define RT_FRAME_FLIP 2      /* hits + marker */

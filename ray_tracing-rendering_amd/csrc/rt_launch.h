@@ -1,13 +1,14 @@
 /*
- * rt_launch.h -- host-side seams between the translation units of librtr_hip.so.  The kernels are
- * compiled in parallel: rtr_capi.hip (C ABI, scene lowering and upload, per-ray kernels, k_resolve), rtr_mega.hip
- * three times (one integrator group each: RTR_MEGA_GROUP 0 = MIS, 1 = RR + path, 2 = PBR + NEE),
- * rtr_wavefront.hip (stage kernels + their host driver) and rtr_gather.hip (the hemisphere-gather kernels + their launcher).
+ * rt_launch.h -- host-side seams between the translation units of librtr_hip.so that launch for one another.  The
+ * units are compiled in parallel: rtr_capi.hip (context, scene upload, renders, k_li), rtr_accum.hip, rtr_image.hip,
+ * rtr_query.hip and rtr_gather.hip (one subject of include/rtr_hip.h each, with its kernels), rtr_mega.hip three times
+ * (one integrator group each: RTR_MEGA_GROUP 0 = MIS, 1 = RR + path, 2 = PBR + NEE) and rtr_wavefront.hip (stage
+ * kernels + their host driver).
  *
- * Which k_mega instantiation a render runs is decided once, by mega_variant() in rtr_capi.hip from the
- * SceneFacts of rt_lower.h (which only that unit includes); the MegaVariant travels in MegaLaunch to the group's unit, which looks it up in its explicit list of
- * instantiations.  kernel_lds() is the one LDS-limit check of every launcher, and dispatch_trav() the
- * one place a runtime RT_TRAV_* becomes a template argument of the per-ray kernels.
+ * Which k_mega instantiation a render runs is decided once, by mega_plan() of rt_select.h; the MegaVariant travels in
+ * MegaLaunch to the group's unit, which looks it up in its explicit list of instantiations.  kernel_lds() is the one
+ * LDS-limit check of every launcher, and dispatch_trav() the one place a runtime RT_TRAV_* becomes a template argument
+ * of the per-ray kernels.
  */
 #pragma once
 
@@ -17,21 +18,13 @@
 #include <string>
 #include <utility>
 
-/* which instantiation a launch actually ran, recorded on the host (rtr_debug_last_kernel) */
+/* which stage instantiations a wavefront render actually ran, recorded on the host (rtr_debug_last_kernel; a megakernel
+ * render records its MegaLaunch) */
 struct LaunchedKernel {
-    int trav = -1;   /* RT_TRAV_* template value of k_mega (RT_TRAV_FLAT_GUARD, RT_TRAV_PROGRAM_EXT included) / WavefrontPlan::trav */
-    int ms = -1;     /* RT_MS_* of k_mega / of the wf_shade stage */
-    int sorted = 0;  /* k_mega's sorted instantiation / wf_shade<..., true> */
-    int phases = 0;  /* wavefront: bit PH set for every wf_shade<I, PH, ...> launched */
-    int pair = 0;    /* k_mega's pair-cast instantiation (MegaVariant::pair) */
-    int queue = 0;   /* k_mega_queue, the job-queue twin, ran in place of k_mega (MegaLaunch::queue) */
-};
-/* which gather kernel a launch ran, recorded on the host (rtr_debug_last_gather) */
-struct LaunchedGather {
-    int integ = -1;    /* k_gather_li<integ, trav>; -1: k_gather_any<trav, broadcast> */
-    int trav = -1;     /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution; -1: nothing launched yet */
-    int broadcast = 0; /* k_gather_any<T, true> */
-    int lg = 0;        /* GatherK::lg: log2 of the lanes that share a point */
+    int trav = -1;   /* WavefrontPlan::trav */
+    int ms = -1;     /* RT_MS_* of the wf_shade stage */
+    int sorted = 0;  /* wf_shade<..., true> */
+    int phases = 0;  /* bit PH set for every wf_shade<I, PH, ...> launched */
 };
 
 /* the k_mega<integ, trav, ms, sorted, ACC, pair> a render runs (ACC follows from the call: MegaLaunch::accum; a one-shot
@@ -41,44 +34,34 @@ struct MegaVariant {
     bool sorted, pair;   /* the sorted instantiation (RTR_FLAG_SORTED_SHADING) / the pair-cast twin of a flat MIS kernel */
 };
 
-/* one megakernel launch */
+/* one megakernel launch: the plan of rt_select.h (mega_plan), then the call's own part */
 struct MegaLaunch {
     MegaVariant variant;
     int accum;          /* 0, or an accumulator pass: the k_mega<..., ACC = 1> twin of the variant, 2 with moments */
     size_t lds;         /* traversal stack + parked path state, bytes per workgroup */
     int stack_words;
-    hipStream_t stream;
-    const DScene* dsc;
-    RenderK P;
-    bool dry;           /* only what can fail without touching the stream: LDS attribute, occupancy query */
-    int* blocks_per_cu; /* dry: resident workgroups per CU of the variant that would run */
+    int n_cus, grid_cap;
+    int flags_in_effect; /* the render flags that changed the choice */
     /* the job-queue twin of a pair-cast variant (rt_kernels.h: k_mega_queue; accum = 0 only): a persistent grid of the
-     * workgroups the chip holds -- occupancy x n_cus, at most one per (tile, chunk), at most grid_cap if that is > 0 --
+     * workgroups the chip holds -- per_cu x n_cus, at most one per (tile, chunk), at most grid_cap if that is > 0 --
      * whose waves pull blocks of jobs through the counter behind the completion words, P.done[n_tiles * chunks];
      * the caller zeroes the words and the counter on the stream before the launch */
     bool queue;
-    int n_cus, grid_cap;
+    /* A kernel is PREPARED once per render, without touching the stream: its LDS checked and the attribute raised, and
+     * with `occupancy` -- auto chunking and the queue's grid need it -- per_cu, the resident workgroups per CU, queried.
+     * The launch proper (prepare = false) checks and queries nothing: per_cu travels here. */
+    bool prepare, occupancy;
+    int per_cu;
+    hipStream_t stream;
+    const DScene* dsc;
+    RenderK P;
 };
 /* return an rtr_status; `err` receives the text of a failure */
-int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err);
-int rtr_mega_launch_rr_path(const MegaLaunch& L, std::string& err);
-int rtr_mega_launch_pbr_nee(const MegaLaunch& L, std::string& err);
+int rtr_mega_launch_mis(MegaLaunch& L, std::string& err);
+int rtr_mega_launch_rr_path(MegaLaunch& L, std::string& err);
+int rtr_mega_launch_pbr_nee(MegaLaunch& L, std::string& err);
 
 void rtr_launch_resolve(const ResolveK& R, hipStream_t stream);
-
-/* one hemisphere-gather launch (rtr_gather.hip holds the k_gather_* instantiations) */
-struct GatherLaunch {
-    DScene ds;      /* the launch's copy: shared_div cleared for t_min < 2^-100 */
-    GatherK K;
-    int integ;      /* RTR_INTEGRATOR_* of a radiance gather, -1: occlusion */
-    int trav;       /* per_ray_trav(..., top = integ < 0), before the EXACT -> MEDIA substitution of li_run */
-    size_t lds;     /* traversal stack, bytes per workgroup */
-    bool broadcast; /* occlusion: k_gather_any<T, true> */
-    hipStream_t stream;
-};
-int rtr_gather_launch(const GatherLaunch& L, LaunchedGather* launched, std::string& err);
-/* RTR_OK, or RTR_ERR_INVALID with the reason in `err` */
-int rtr_gather_params_check(const rtr_gather_params* p, std::string& err);
 
 /* The per-lane traversal stack lives in LDS: a graph that needs more than the CU has (e.g. the reference-order walk
  * of a hittable_list with thousands of direct children) cannot run that way.  `static_bytes`: the kernel's own static

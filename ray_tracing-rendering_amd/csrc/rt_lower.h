@@ -2,8 +2,8 @@
  * rt_lower.h -- host side, no HIP call: the second half of scene compilation.  rt_compile.h lowers a validated hittable
  * graph to a CompiledScene; lower_scene() below turns that into every array the device reads (step program, instance
  * visits, per-reference records with their tie and guard flags, leaf records, scan runs, FMat) and into the facts every
- * kernel-variant decision hangs on (SceneFacts: pick_trav, mega_variant and the wavefront plan of rtr_capi.hip read
- * nothing else).  rtr_upload_scene only copies what comes out of here.  Included by the C-ABI unit alone: the megakernel
+ * kernel-variant decision hangs on (SceneFacts: pick_trav, mega_variant and the wavefront plan of rt_select.h read
+ * nothing else).  rtr_upload_scene only copies what comes out of here.  Included through rt_select.h / rt_context.h by the units of the C ABI: the megakernel
  * and wavefront units do not see it.
  */
 #pragma once

@@ -21,52 +21,47 @@ int mega_fail(std::string& err, int code, const std::string& m) {
     return code;
 }
 
+int mega_status(hipError_t e, std::string& err) {
+    return e == hipSuccess ? RTR_OK : mega_fail(err, RTR_ERR_DEVICE, std::string("megakernel launch: ") + hipGetErrorString(e));
+}
+
+/* MegaLaunch::prepare: what can fail without touching the stream, once per render; the kernel's own static LDS (a few
+ * words of the workgroup vote) counts against the same 160 KiB */
 template <typename K>
-int launch_one(K kernel, const MegaLaunch& L, std::string& err) {
+int prepare(K kernel, MegaLaunch& L, std::string& err) {
     hipFuncAttributes fa{};
     hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
-    /* the kernel's own static LDS (a few words of the workgroup vote) counts against the same 160 KiB */
     if (e == hipSuccess)
         if (int rc = kernel_lds(kernel, L.lds, fa.sharedSizeBytes, err)) return rc;
-    if (e == hipSuccess && L.dry && L.blocks_per_cu)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(L.blocks_per_cu, kernel, RTR_BLOCK, L.lds);
-    if (e == hipSuccess && !L.dry) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(L.P.n_tiles * L.P.chunks)), dim3(RTR_BLOCK), L.lds, L.stream, L.dsc, L.P,
-                           L.stack_words);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return mega_fail(err, RTR_ERR_DEVICE, std::string("megakernel launch: ") + hipGetErrorString(e));
-    return RTR_OK;
+    if (e == hipSuccess && L.occupancy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&L.per_cu, kernel, RTR_BLOCK, L.lds);
+    return mega_status(e, err);
+}
+
+template <typename K>
+int launch_one(K kernel, MegaLaunch& L, std::string& err) {
+    if (L.prepare) return prepare(kernel, L, err);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(L.P.n_tiles * L.P.chunks)), dim3(RTR_BLOCK), L.lds, L.stream, L.dsc, L.P, L.stack_words);
+    return mega_status(hipGetLastError(), err);
 }
 
 /* the job-queue twin of a pair-cast variant: a persistent grid (MegaLaunch::queue) */
 template <typename K>
-int launch_queue(K kernel, const MegaLaunch& L, std::string& err) {
-    hipFuncAttributes fa{};
-    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
-    if (e == hipSuccess)
-        if (int rc = kernel_lds(kernel, L.lds, fa.sharedSizeBytes, err)) return rc;
-    int per_cu = 0;
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RTR_BLOCK, L.lds);
-    if (e == hipSuccess && L.dry && L.blocks_per_cu) *L.blocks_per_cu = per_cu;
-    if (e == hipSuccess && !L.dry) {
-        const long long cells = (long long)L.P.n_tiles * L.P.chunks; /* four blocks each */
-        long long grid = (long long)(per_cu > 0 ? per_cu : 1) * (L.n_cus > 0 ? L.n_cus : 1);
-        if (grid > cells) grid = cells;
-        if (L.grid_cap > 0 && grid > L.grid_cap) grid = L.grid_cap;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(RTR_BLOCK), L.lds, L.stream, L.dsc, L.P, L.stack_words,
-                           reinterpret_cast<uint32_t*>(L.P.done + cells), (int)(cells * 4));
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return mega_fail(err, RTR_ERR_DEVICE, std::string("megakernel launch: ") + hipGetErrorString(e));
-    return RTR_OK;
+int launch_queue(K kernel, MegaLaunch& L, std::string& err) {
+    if (L.prepare) return prepare(kernel, L, err);
+    const long long cells = (long long)L.P.n_tiles * L.P.chunks; /* four blocks each */
+    long long grid = (long long)(L.per_cu > 0 ? L.per_cu : 1) * (L.n_cus > 0 ? L.n_cus : 1);
+    if (grid > cells) grid = cells;
+    if (L.grid_cap > 0 && grid > L.grid_cap) grid = L.grid_cap;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(RTR_BLOCK), L.lds, L.stream, L.dsc, L.P, L.stack_words,
+                       reinterpret_cast<uint32_t*>(L.P.done + cells), (int)(cells * 4));
+    return mega_status(hipGetLastError(), err);
 }
 
 /* one line of a group's list: k_mega<I, T, M, S, ACC, PR> for ACC = 0, 1, 2 */
 template <int I, int T, int M, bool S = false, bool PR = false>
 struct Row {
     static bool is(const MegaVariant& v) { return v.integ == I && v.trav == T && v.ms == M && v.sorted == S && v.pair == PR; }
-    static int launch(const MegaLaunch& L, std::string& err) {
+    static int launch(MegaLaunch& L, std::string& err) {
         if constexpr (PR)
             if (L.queue) return launch_queue(k_mega_queue<I, T, M>, L, err);
         /* (an accumulator pass: the same variant with ACC = 1, or 2 with moments, rt_kernels.h) */
@@ -77,7 +72,7 @@ struct Row {
 };
 /* the row that is MegaLaunch::variant, or RTR_ERR_UNSUPPORTED: never another kernel in its place */
 template <typename... Rows>
-int launch_from(const MegaLaunch& L, std::string& err) {
+int launch_from(MegaLaunch& L, std::string& err) {
     int rc = RTR_OK;
     if (((Rows::is(L.variant) && (rc = Rows::launch(L, err), true)) || ...)) return rc;
     const MegaVariant& v = L.variant;
@@ -91,7 +86,7 @@ int launch_from(const MegaLaunch& L, std::string& err) {
 #if RTR_MEGA_GROUP == 0
 /* MIS: every traversal; lean / QuadLights-only / full material sets; the flat kernels have a pair-cast twin and the
  * flat QuadLights-only one a sorted twin */
-int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err) {
+int rtr_mega_launch_mis(MegaLaunch& L, std::string& err) {
     constexpr int I = RTR_INTEGRATOR_MIS;
     return launch_from<
         Row<I, RT_TRAV_FLAT, RT_MS_LEAN>,
@@ -121,7 +116,7 @@ int rtr_mega_launch_mis(const MegaLaunch& L, std::string& err) {
 /* RR: every traversal, lean / full (it has no light code).  Path (like PBR and NEE): the generic
  * material set, one program kernel -- the general one --, and the media kernel, which also serves the reference-order
  * traversal of scenes without media */
-int rtr_mega_launch_rr_path(const MegaLaunch& L, std::string& err) {
+int rtr_mega_launch_rr_path(MegaLaunch& L, std::string& err) {
     constexpr int R = RTR_INTEGRATOR_RR, P = RTR_INTEGRATOR_PATH;
     return launch_from<
         Row<R, RT_TRAV_FLAT, RT_MS_LEAN>,
@@ -142,7 +137,7 @@ int rtr_mega_launch_rr_path(const MegaLaunch& L, std::string& err) {
         Row<P, RT_TRAV_MEDIA, RT_MS_FULL>>(L, err);
 }
 #else
-int rtr_mega_launch_pbr_nee(const MegaLaunch& L, std::string& err) {
+int rtr_mega_launch_pbr_nee(MegaLaunch& L, std::string& err) {
     constexpr int B = RTR_INTEGRATOR_PBR, N = RTR_INTEGRATOR_NEE;
     return launch_from<
         Row<B, RT_TRAV_FAST, RT_MS_FULL>,

@@ -2,10 +2,9 @@
  * rtr_test.hip -- librtr_hip_test.so: the entry points of include/rtr_hip_test.h.  Test infrastructure, built next to
  * librtr_hip.so and linked against it; it reaches a context only through the seam of csrc/rt_debug.h.
  */
-/* this library is a link unit of its own: it takes its own copy of the non-template kernels of rt_kernels.h, which
- * inside librtr_hip.so live in rtr_capi.hip alone (rtr_test_temporal_planes launches k_temporal_blend / _store) */
-#define RTR_TU_CAPI
+/* (a link unit of its own: rtr_test_temporal_planes launches its own copy of k_temporal_blend / _store) */
 #include "rt_debug.h"
+#include "rt_image_kernels.h"
 #include "rt_launch.h"
 #include "rt_test_kernels.h"
 #include "rtr_hip_test.h"
@@ -104,7 +103,7 @@ int rtr_test_hits(rtr_context* c, rtr_hit_record* recs, int64_t n) {
     ds.needs_uv = 1; /* the vectors pin u,v although no flattened texture of these scenes reads them */
     auto* d = static_cast<rtr_hit_record*>(t->buf);
     const size_t lds = v.stack_bytes;
-    /* (rtr_debug_view::trav is a template value already: per_ray_trav of rtr_capi.hip) */
+    /* (rtr_debug_view::trav is a template value already: per_ray_trav of rt_select.h) */
     if (!dispatch_trav(TravSet<RT_TRAV_FAST, RT_TRAV_TOP, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA, RT_TRAV_EXACT>{}, v.trav, [&](auto t) {
             constexpr int T = decltype(t)::value;
             if ((rc = set_lds(c, k_test_hits<T>, lds))) return;
@@ -369,7 +368,7 @@ int rtr_test_shared_division(rtr_context* c, uint64_t* mismatches, uint64_t* tes
 }
 
 /* k_temporal_blend and k_temporal_store of the product on caller-given planes: the planes they touch in the test buffer,
- * the grids of denoise_run (rtr_capi.hip) */
+ * the grids of denoise_run (rtr_image.hip) */
 int rtr_test_temporal_planes(rtr_context* c, int32_t width, int32_t height, int32_t image_width, int32_t image_height, int32_t x0,
                              int32_t y0, const rtr_camera* cam, const rtr_camera* prev, int have, const rtr_temporal_params* tp,
                              const double* h_color, const double* h_q, const int32_t* h_count, const double* h_feat,

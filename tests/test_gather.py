@@ -238,7 +238,7 @@ def test_radiance_with_media_and_guarded_steps(ctx, key, integrator, order, samp
 @pytest.mark.parametrize("sid,integrator", [(21, 0), (21, 1), (21, 2), (21, 3), (21, 4), (23, 1), (23, 4)])
 def test_radiance_in_reference_order(ctx, sid, integrator, samples):
     """FLAG_REFERENCE_ORDER on scenes without media: k_gather_li<I, EXACT> for MIS and RR; integrators 0, 2 and 3 have no
-    such kernel and take the media kernel in its place (rtr_gather_launch).  On scene 21 the walk in reference order and
+    such kernel and take the media kernel in its place (csrc/rt_select.h: li_trav).  On scene 21 the walk in reference order and
     the compiled traversal give the same bits (tests/test_gpu_parity.py holds the two to each other there)."""
     name, out = _radiance_case(ctx, sid, integrator, samples, True)
     assert name == (integrator, EXACT if integrator in (1, 4) else MEDIA, 0)

@@ -30,7 +30,7 @@ def chunk_range(spp, chunks, guided, c):
 
 
 def guided_split(spp, chunks):
-    """the split choose_chunks (csrc/rtr_capi.hip) makes of `chunks` equal parts: (chunks, (n_big, big_spp, small_spp))"""
+    """the split choose_chunks (csrc/rt_select.h) makes of `chunks` equal parts: (chunks, (n_big, big_spp, small_spp))"""
     n_big = max(1, chunks * 6 // 8)
     big = int((0.90 * spp + n_big - 1) / n_big)
     rem = spp - n_big * big

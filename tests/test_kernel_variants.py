@@ -254,7 +254,7 @@ def mega_flag_sets(sc, integ):
 
 def planned_mega_names(sc):
     """The full names _render_matrix will launch on ``sc``, from native.scene_plan alone (no GPU): every integrator with
-    every flag set one-shot -- the job queue runs a pair variant unless FLAG_STATIC_GRID is set (csrc/rtr_capi.hip:
+    every flag set one-shot -- the job queue runs a pair variant unless FLAG_STATIC_GRID is set (csrc/rt_select.h:
     mega_queue) --, and every row so reached once more as an accumulator pass without and with moments."""
     names = set()
     for integ in (I_PATH, I_RR, I_PBR, I_NEE, I_MIS):
