@@ -22,6 +22,24 @@ int rtr_test_hits(rtr_context* ctx, rtr_hit_record* recs, int64_t n);
 int rtr_test_materials(rtr_context* ctx, rtr_mat_record* recs, int64_t n);
 int rtr_test_lights(rtr_context* ctx, rtr_light_record* recs, int64_t n);
 int rtr_test_li(rtr_context* ctx, const rtr_render_params* params, rtr_li_record* recs, int64_t n);
+/* rtr_test_materials runs mat_prepare, mat_sample, mat_eval, mat_pdf and mat_emitted, and then the fused mat_eval_pdf the MIS
+ * kernels call for the light sample, on (wo, wi_in): the record's `pad` gets bit 0 where its f differs from mat_eval in any
+ * bit and bit 1 where its pdf differs from mat_pdf (a NaN equals a NaN), so 0 means the fused form is the separate ones.
+ * rtr_test_scatter: mat_prepare + the legacy mat_scatter of integrators 0 and 1 with r_in.direction() = wo (not normalised)
+ * in the same record: sample_ok the return value, s_wi the scattered direction, s_f the attenuation, rng_out the state
+ * after the call; every other output is zero. */
+int rtr_test_scatter(rtr_context* ctx, rtr_mat_record* recs, int64_t n);
+/* The same kernels instantiated for material set ms (RT_MS_LEAN 0, RT_MS_FULL 1, RT_MS_QUADLIT 2 of csrc/rt_device.h) as the
+ * render kernels are: mat_prepare<ms>, mat_sample<ms>, ..., light_sample<ms>, light_pdf<ms>.  RTR_ERR_UNSUPPORTED, the records
+ * untouched, where the uploaded scene is not of that class by the predicates of mega_variant (rtr_scene_plan::lean_materials;
+ * quad_lights_only and no texture that reads (u, v)).  The entries without _ms are ms = RT_MS_FULL. */
+int rtr_test_materials_ms(rtr_context* ctx, rtr_mat_record* recs, int64_t n, int32_t ms);
+int rtr_test_scatter_ms(rtr_context* ctx, rtr_mat_record* recs, int64_t n, int32_t ms);
+int rtr_test_lights_ms(rtr_context* ctx, rtr_light_record* recs, int64_t n, int32_t ms);
+/* pow5 of csrc/rt_device.h (the device's pow(x, 5.0): x^5 in double-double arithmetic) over a host array, on the device and
+ * as a host build of the same function (no context, no GPU).  Both are the same fused multiply-adds without contraction. */
+int rtr_test_pow5(rtr_context* ctx, const double* x, double* out, int64_t n);
+int rtr_test_pow5_host(const double* x, double* out, int64_t n);
 /* rtr_test_hits through the closest-hit cast of the FLAT kernels (cast_closest<RT_TRAV_FLAT> or, in a scene with guarded
  * references, <RT_TRAV_FLAT_GUARD>), which the megakernel runs on flat scenes and no query or per-ray kernel does: the flat
  * scan, then the hit record from the scene's finish records (rtr_finish_record) where it has them.  with_uv: compute

@@ -195,7 +195,89 @@ def tie_fixtures(note):
         note(name, cmd, info, scene=sid)
 
 
+def write_earthmap(td):
+    """the synthetic 96x48 picture of scene 4 (binary PPM under the name the reference asks for)"""
+    w, h = 96, 48
+    px = bytearray()
+    for j in range(h):
+        for i in range(w):
+            px += bytes(((i * 5 + j * 3) % 256, (i * i + 7 * j) % 256, (i ^ (3 * j)) % 256))
+    with open(os.path.join(td, "earthmap.jpg"), "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (w, h) + bytes(px))
+
+
+POW5_PARTS = 7
+SHADING_EDGE_SCENE = 1014  # harness scene: one sphere per material class / texture class / roughness clamp end
+
+
+def pow5_differences(path):
+    """how many of the values of a pow5_*.bin the library's double-double x^5 (rtr_test_pow5_host, the host build of
+    rt_device.h: pow5) does not reproduce bit for bit; all of them by one ulp (tests/test_oracle_golden.py)"""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    native = importlib.import_module("ray_tracing-rendering_amd").native
+    xy = np.fromfile(path, dtype="<f8").reshape(-1, 2)
+    return int((native.pow5_host(xy[:, 0]).view(np.uint64) != np.ascontiguousarray(xy[:, 1]).view(np.uint64)).sum())
+
+
+def shading_edge_fixtures(note):
+    """Vectors built ON the decisions of the shading functions (NaN operands, signed zeros, the two sides of every
+    compare, index edges of the textures and of the environment map tables) instead of beside them, plus the legacy
+    material::scatter and glibc's pow(x, 5)."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        write_earthmap(td)
+        write_pbr_textures(td)
+        for fname, w, h, sun in HDR_ASSETS.values():
+            write_hdr(os.path.join(td, fname), w, h, sun)
+        sid = SHADING_EDGE_SCENE
+        name = "scene%d.rtrs" % sid
+        cmd, info = run("dump-scene", sid, SCENE_SEED, os.path.join(GOLD, name), cwd=td)
+        note(name, cmd, info, raw_sha256=sha(os.path.join(GOLD, name)),
+             asset="synthetic 96x48 PPM as earthmap.jpg, synthetic PNG as tex/oak/oak_veneer_01_nor_dx_1k.png")
+        for sid in (SHADING_EDGE_SCENE, 21, 23, 35):
+            name = "materials_edge_scene%02d.bin" % sid
+            cmd, info = run("materials-edge", sid, SCENE_SEED, os.path.join(GOLD, name), cwd=td)
+            note(name, cmd, info, scene=sid)
+        for sid, n in ((9, SCATTER_N_PER[9]), (SHADING_EDGE_SCENE, SCATTER_N_PER[SHADING_EDGE_SCENE])):
+            name = "scatter_scene%02d.bin" % sid
+            # (scene 9 as scene09.rtrs has it: without the picture its earth sphere asks for)
+            cmd, info = run("scatter", sid, SCENE_SEED, n, 4400 + sid, os.path.join(GOLD, name), cwd=td if sid > 1000 else None)
+            note(name, cmd, info, scene=sid)
+        name = "scatter_edge_scene%d.bin" % SHADING_EDGE_SCENE
+        cmd, info = run("scatter-edge", SHADING_EDGE_SCENE, SCENE_SEED, os.path.join(GOLD, name), cwd=td)
+        note(name, cmd, info, scene=SHADING_EDGE_SCENE)
+        for sid in (21, 23, 15, 17, 18, 19, 24, 26):
+            name = "lights_edge_scene%02d.bin" % sid
+            cmd, info = run("lights-edge", sid, SCENE_SEED, os.path.join(GOLD, name), cwd=td)
+            note(name, cmd, info, scene=sid)
+    for part in range(POW5_PARTS):  # 65536 pairs of doubles are 1 MiB: seven files below 160 KB each
+        name = "pow5_%d.bin" % part
+        cmd, info = run("pow5", part, POW5_PARTS, os.path.join(GOLD, name))
+        info["differs_from_pow5_host"] = pow5_differences(os.path.join(GOLD, name))
+        note(name, cmd, info)
+
+
+# records per material of the random scatter vectors, chosen so that each file stays below 160 KB (640 records)
+SCATTER_N_PER = {9: 48, SHADING_EDGE_SCENE: 28}
+
+
 def main():
+    if "--add-shading-edges" in sys.argv:  # only the shading-edge fixtures, into the existing manifest
+        subprocess.run(["make", "-C", HERE, "_ref/ref_harness"], check=True)
+        with open(os.path.join(GOLD, "manifest.json")) as f:
+            manifest = json.load(f)
+
+        def note(name, cmd, info, **extra):
+            p = os.path.join(GOLD, name)
+            assert os.path.getsize(p) <= 160 * 1024, (name, os.path.getsize(p))
+            manifest["files"][name] = {"argv": [os.path.basename(cmd[0])] + cmd[1:-1] + [name], "info": info,
+                                       "sha256": sha(p), "bytes": os.path.getsize(p), **extra}
+        shading_edge_fixtures(note)
+        with open(os.path.join(GOLD, "manifest.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        return 0
     if "--add-ties" in sys.argv:  # only the tie fixtures, into the existing manifest
         subprocess.run(["make", "-C", HERE, "_ref/ref_harness"], check=True)
         with open(os.path.join(GOLD, "manifest.json")) as f:
@@ -406,6 +488,7 @@ def main():
 
     png_fixtures(manifest, note)
     tie_fixtures(note)
+    shading_edge_fixtures(note)
 
     with open(os.path.join(GOLD, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)

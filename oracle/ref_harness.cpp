@@ -16,6 +16,10 @@
  *   hits        <scene> <scene_seed> <n> <gen_seed> <out.bin>
  *   materials   <scene> <scene_seed> <n_per_material> <gen_seed> <out.bin>
  *   lights      <scene> <scene_seed> <n_per_light> <gen_seed> <out.bin>
+ *   scatter     <scene> <scene_seed> <n_per_material> <gen_seed> <out.bin>   legacy material::scatter, rtr_mat_record layout
+ *   materials-edge / scatter-edge / lights-edge <scene> <scene_seed> <out.bin>  constructed records on the branch edges
+ *                                                          of the shading functions; per-case record counts in the JSON
+ *   pow5        <part> <parts> <out.bin>                   pairs (x, glibc pow(x, 5.0)), one slice of 65536
  *   rng         <out.bin>
  *   time        <scene> <integ> <W> <spp>                  unseeded Renderer::render timing
  *   png         <in.f64> <W> <H> <out.rgb8>                the reference's own output stage on a linear image:
@@ -393,6 +397,28 @@ static SceneConfig primitive_scene(int id) {
             c.world = make_shared<hittable_list>(w);
         else
             c.world = make_shared<bvh_node>(w, 0, 1); /* split axes drawn from the scene seed (bvh.h:61-63) */
+        break;
+    }
+    case 1014: { /* the "shading edge" scene: one small sphere per material, for materials-edge / scatter-edge.  Needs the
+                    synthetic earthmap.jpg of scene 4 and the synthetic PNGs of scene 35 in the working directory */
+        hittable_list w;
+        int k = 0;
+        auto put = [&](shared_ptr<material> m) { w.add(make_shared<sphere>(point3(-4.0 + 0.4 * k, 0.0, 0.05 * k), 0.15, m)), ++k; };
+        auto solid = [](double v) { return make_shared<solid_color>(v, v, v); };
+        put(make_shared<lambertian>(color(0.73, 0.2, 0.5)));
+        auto inner = make_shared<checker_texture>(color(0.2, 0.3, 0.1), color(0.9, 0.9, 0.9));
+        put(make_shared<lambertian>(make_shared<checker_texture>(make_shared<solid_color>(0.1, 0.2, 0.8), inner))); /* odd child: a checker */
+        put(make_shared<lambertian>(make_shared<noise_texture>(4.0)));
+        put(make_shared<lambertian>(make_shared<image_texture>("earthmap.jpg")));
+        for (double fuzz : {0.0, 0.3, 1.0}) put(make_shared<metal>(color(0.8, 0.6, 0.2), fuzz));
+        for (double ir : {1.5, 1.0, 0.8}) put(make_shared<dielectric>(ir));
+        put(make_shared<diffuse_light>(color(4, 3, 2)));
+        for (double r : {0.0, 0.01, 1.0, 2.0}) /* the clamp of roughness to [0.01, 1] at both ends */
+            for (double m : {0.0, 1.0}) put(make_shared<PBRMaterial>(make_shared<solid_color>(0.9, 0.5, 0.3), solid(r), solid(m)));
+        put(make_shared<PBRMaterial>(make_shared<solid_color>(0.6, 0.7, 0.8), solid(0.3), solid(0.5),
+                                     make_shared<image_texture>("tex/oak/oak_veneer_01_nor_dx_1k.png")));
+        w.add(make_shared<constant_medium>(make_shared<sphere>(point3(0, 1.5, 0), 0.4, white), 0.9, smoke)); /* an isotropic material */
+        c.world = make_shared<bvh_node>(w, 0, 1);
         break;
     }
     default: die("unknown primitive scene id");
@@ -933,7 +959,68 @@ static int cmd_hits(int scene_id, uint32_t scene_seed, int n, uint64_t gen_seed,
     return 0;
 }
 
-static int cmd_materials(int scene_id, uint32_t scene_seed, int n_per, uint64_t gen_seed, const char* path) {
+/* material::sample / eval / pdf / emitted of `mat` on the inputs of one record */
+static void eval_material(const material* mat, MatRecordOut& o) {
+    hit_record rec;
+    rec.normal = vec3(o.n[0], o.n[1], o.n[2]);
+    rec.p = vec3(o.p[0], o.p[1], o.p[2]);
+    rec.u = o.u, rec.v = o.v;
+    rec.t = 1.0;
+    rec.front_face = o.front_face != 0;
+    rec.mat_ptr = const_cast<material*>(mat);
+    const vec3 wo(o.wo[0], o.wo[1], o.wo[2]), wi(o.wi_in[0], o.wi_in[1], o.wi_in[2]);
+    set_rng(o.rng_in);
+    BSDFSample bs;
+    bs.wi = vec3(0, 0, 0);
+    bs.f = color(0, 0, 0);
+    bs.pdf = 0;
+    bs.is_specular = false;
+    bool ok = mat->sample(rec, wo, bs);
+    o.rng_out = get_rng();
+    o.sample_ok = ok;
+    o.is_specular = bs.is_specular;
+    o.is_transmission = bs.is_transmission;
+    Flattener::put3(o.s_wi, bs.wi);
+    Flattener::put3(o.s_f, bs.f);
+    o.s_pdf = bs.pdf;
+    color e = mat->eval(rec, wo, wi);
+    Flattener::put3(o.eval, e);
+    o.pdf = mat->pdf(rec, wo, wi);
+    color em = mat->emitted(rec, wo);
+    Flattener::put3(o.emitted, em);
+}
+
+/* the legacy material::scatter(r_in, rec, attenuation, scattered) of integrators 0 and 1 in the same record: wo holds
+ * r_in.direction() (not normalised), sample_ok the return value, s_wi scattered.direction(), s_f the attenuation,
+ * rng_out the state after the call; every other output stays zero */
+static void eval_scatter(const material* mat, MatRecordOut& o) {
+    hit_record rec;
+    rec.normal = vec3(o.n[0], o.n[1], o.n[2]);
+    rec.p = vec3(o.p[0], o.p[1], o.p[2]);
+    rec.u = o.u, rec.v = o.v;
+    rec.t = 1.0;
+    rec.front_face = o.front_face != 0;
+    rec.mat_ptr = const_cast<material*>(mat);
+    ray r_in(rec.p, vec3(o.wo[0], o.wo[1], o.wo[2]), 0.0);
+    set_rng(o.rng_in);
+    color attenuation(0, 0, 0);
+    ray scattered(point3(0, 0, 0), vec3(0, 0, 0), 0.0);
+    bool ok = mat->scatter(r_in, rec, attenuation, scattered);
+    o.rng_out = get_rng();
+    o.sample_ok = ok;
+    Flattener::put3(o.s_wi, scattered.direction());
+    Flattener::put3(o.s_f, attenuation);
+}
+
+static void write_mat_records(const char* path, const std::vector<MatRecordOut>& recs) {
+    FILE* fo = std::fopen(path, "wb");
+    if (!fo) die("cannot open output");
+    std::fwrite(recs.data(), sizeof(MatRecordOut), recs.size(), fo);
+    std::fclose(fo);
+}
+
+/* `materials` and, with scatter set, `scatter`: the same random inputs through either interface */
+static int cmd_materials(int scene_id, uint32_t scene_seed, int n_per, uint64_t gen_seed, const char* path, bool scatter) {
     Loaded l = load_scene(scene_id, scene_seed);
     Flattener f = flatten(l);
     std::mt19937_64 g(gen_seed);
@@ -952,7 +1039,6 @@ static int cmd_materials(int scene_id, uint32_t scene_seed, int n_per, uint64_t 
             rec.v = U01(g);
             rec.t = 1.0 + 10 * U01(g);
             rec.front_face = (k % 3) != 0;
-            rec.mat_ptr = const_cast<material*>(mat);
             vec3 wo = gen_unit(g);
             if ((k % 4) != 3 && dot(wo, rec.normal) < 0) wo = -wo; /* mostly the upper hemisphere */
             vec3 wi = gen_unit(g);
@@ -965,33 +1051,522 @@ static int cmd_materials(int scene_id, uint32_t scene_seed, int n_per, uint64_t 
             Flattener::put3(o.wo, wo);
             Flattener::put3(o.wi_in, wi);
             o.rng_in = (uint32_t)g() | 1u;
-            set_rng(o.rng_in);
-            BSDFSample bs;
-            bs.wi = vec3(0, 0, 0);
-            bs.f = color(0, 0, 0);
-            bs.pdf = 0;
-            bs.is_specular = false;
-            bool ok = mat->sample(rec, wo, bs);
-            o.rng_out = get_rng();
-            o.sample_ok = ok;
-            o.is_specular = bs.is_specular;
-            o.is_transmission = bs.is_transmission;
-            Flattener::put3(o.s_wi, bs.wi);
-            Flattener::put3(o.s_f, bs.f);
-            o.s_pdf = bs.pdf;
-            color e = mat->eval(rec, wo, wi);
-            Flattener::put3(o.eval, e);
-            o.pdf = mat->pdf(rec, wo, wi);
-            color em = mat->emitted(rec, wo);
-            Flattener::put3(o.emitted, em);
+            if (scatter) { /* the incoming ray: towards the surface where wo left it, every fourth one unnormalised */
+                Flattener::put3(o.wo, (k % 4) == 1 ? -wo * (0.25 + 4.0 * U01(g)) : -wo);
+                eval_scatter(mat, o);
+            } else {
+                eval_material(mat, o);
+            }
             recs.push_back(o);
         }
     }
+    write_mat_records(path, recs);
+    std::printf("{\"scene\": %d, \"materials\": %zu, \"n\": %zu}\n", scene_id, f.mats.size(), recs.size());
+    return 0;
+}
+
+/* ---- vectors built ON the decisions of the shading functions (materials-edge, scatter-edge, lights-edge) ---------- */
+/* Every record belongs to a named case; a case counts a record only where its condition holds, evaluated here with the
+ * reference's own expressions, and the counts go into the command's JSON line (and from there into the manifest). */
+typedef std::map<std::string, int> CaseCounts;
+static void print_counts(const CaseCounts& c) {
+    std::printf("\"cases\": {");
+    bool first = true;
+    for (const auto& kv : c) {
+        std::printf("%s\"%s\": %d", first ? "" : ", ", kv.first.c_str(), kv.second);
+        first = false;
+    }
+    std::printf("}");
+}
+static double up(double x) { return std::nextafter(x, infinity); }
+static double down(double x) { return std::nextafter(x, -infinity); }
+/* the state whose NEXT random_double() is draw * 2^-32: one xorshift32 step (rtweekend.h:29-33) is a bijection */
+static uint32_t state_before_draw(uint32_t draw) {
+    uint32_t s = draw;
+    s ^= s << 5, s ^= s << 10, s ^= s << 20; /* undo s ^= s << 5 */
+    s ^= s >> 17;                            /* undo s ^= s >> 17 */
+    s ^= s << 13, s ^= s << 26;              /* undo s ^= s << 13 */
+    set_rng(s);
+    if (random_double() != draw * 2.3283064365386963e-10 || s == 0) die("state_before_draw: inversion failed");
+    return s;
+}
+/* x with |x| = 1 after normalisation is wanted at an exact value: a unit vector (x, y, 0) (or (y, x, 0) with swap)
+ * whose length_squared() rounds to exactly 1, so that unit_vector() leaves x as it is */
+static vec3 exact_unit_xy(double x, bool swap) {
+    double y = std::sqrt(1.0 - x * x);
+    for (int k = 0; k < 200; ++k) {
+        for (double c : {y + k * 1.1102230246251565e-16, y - k * 1.1102230246251565e-16}) {
+            vec3 v = swap ? vec3(c, x, 0) : vec3(x, c, 0);
+            if (v.length_squared() == 1.0) return v;
+        }
+    }
+    die("exact_unit_xy: no exact unit vector found");
+    return vec3(0, 0, 0);
+}
+
+struct MatEdgeGen {
+    bool scatter;
+    std::vector<MatRecordOut> recs;
+    CaseCounts counts;
+    int m = 0; /* current material */
+    const vec3 P0{0.37, -1.25, 2.5};
+
+    /* wo is the direction AWAY from the surface; scatter records store the incoming direction -wo unless raw */
+    void emit(const std::string& name, bool cond, vec3 n, vec3 wo, vec3 wi, bool front = true, double u = 0.3, double v = 0.6,
+              vec3 p = vec3(0.37, -1.25, 2.5), uint32_t rng = 0, bool raw_wo = false) {
+        MatRecordOut o;
+        std::memset(&o, 0, sizeof o);
+        o.material = m, o.front_face = front;
+        o.rng_in = rng ? rng : ((0x9E3779B9u ^ (uint32_t)(recs.size() * 2654435761u)) | 1u);
+        Flattener::put3(o.p, p), Flattener::put3(o.n, n);
+        o.u = u, o.v = v;
+        Flattener::put3(o.wo, (scatter && !raw_wo) ? -wo : wo);
+        Flattener::put3(o.wi_in, wi);
+        recs.push_back(o);
+        counts[name] += cond ? 1 : 0;
+    }
+    /* dielectric::sample (material.h:158-163) / ::scatter (:179-183): which side of `refraction_ratio * sin_theta > 1.0`
+     * the stored direction d is on */
+    bool cannot_refract(vec3 d, vec3 n, double refraction_ratio) const {
+        vec3 unit_direction = scatter ? unit_vector(d) : -d;
+        double cos_theta = fmin(dot(-unit_direction, n), 1.0);
+        double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
+        return refraction_ratio * sin_theta > 1.0;
+    }
+    double cos_of(vec3 d, vec3 n) const {
+        vec3 unit_direction = scatter ? unit_vector(d) : -d;
+        return fmin(dot(-unit_direction, n), 1.0);
+    }
+
+    void material_cases(const material* mat) {
+        const vec3 X(1, 0, 0), Y(0, 1, 0), Z(0, 0, 1);
+        const vec3 ta(0.3, -0.2, 0.4), tb(-0.5, 0.1, 0.2);
+        auto above = [&](vec3 n, vec3 t) { return unit_vector(n + t); };
+        const vec3 wo0 = above(Z, ta), wi0 = above(Z, tb);
+        const double tiny = std::numeric_limits<double>::denorm_min();
+        auto lam = dynamic_cast<const lambertian*>(mat);
+        auto die_ = dynamic_cast<const dielectric*>(mat);
+        auto pbr = dynamic_cast<const PBRMaterial*>(mat);
+        auto lit = dynamic_cast<const diffuse_light*>(mat);
+        auto iso = dynamic_cast<const isotropic*>(mat);
+
+        /* n on each axis and on a generic unit vector */
+        const vec3 ng = unit_vector(vec3(0.48, -0.6, 0.64));
+        for (vec3 n : {X, Y, Z, ng}) emit("n_axes_and_generic", true, n, above(n, ta), above(n, tb));
+        /* wo perpendicular to n, below the surface, the zero vector */
+        emit("wo_perp", dot(Z, vec3(0.6, 0.8, 0.0)) == 0, Z, vec3(0.6, 0.8, 0.0), wi0);
+        emit("wo_below", dot(Z, -wo0) < 0, Z, -wo0, wi0);
+        emit("wo_zero", true, Z, vec3(0, 0, 0), wi0);
+        /* wi only reaches eval() and pdf() of lambertian and PBRMaterial (the base class returns 0 without reading it): the
+         * other classes get the -0 record alone */
+        emit("wi_perp_dot_minus_zero", std::signbit(dot(Z, unit_vector(vec3(-0.6, -0.8, -0.0)))) && dot(Z, unit_vector(vec3(-0.6, -0.8, -0.0))) == 0, Z,
+             wo0, vec3(-0.6, -0.8, -0.0));
+        if (lam || pbr) {
+            /* wi exactly perpendicular to n: dot +0, dot -0 (every product a negative zero), one step to either side */
+            emit("wi_perp_dot_plus_zero", dot(Z, vec3(0.6, 0.8, 0.0)) == 0 && !std::signbit(dot(Z, unit_vector(vec3(0.6, 0.8, 0.0)))), Z, wo0,
+                 vec3(0.6, 0.8, 0.0));
+            emit("wi_perp_one_step_above", dot(Z, vec3(0.6, 0.8, tiny)) > 0, Z, wo0, vec3(0.6, 0.8, tiny));
+            emit("wi_perp_one_step_below", dot(Z, vec3(0.6, 0.8, -tiny)) < 0, Z, wo0, vec3(0.6, 0.8, -tiny));
+            emit("wi_perp_one_ulp_of_one_above", dot(Z, vec3(0.6, 0.8, 2.220446049250313e-16)) > 0, Z, wo0, vec3(0.6, 0.8, 2.220446049250313e-16));
+            emit("wi_perp_one_ulp_of_one_below", dot(Z, vec3(0.6, 0.8, -2.220446049250313e-16)) < 0, Z, wo0, vec3(0.6, 0.8, -2.220446049250313e-16));
+            /* wi = -wo (the half vector is unit(0)), wi = 0 */
+            emit("wi_minus_wo", (wo0 + (-wo0)).length_squared() == 0, Z, wo0, -wo0);
+            /* the same with wo below and wi above the surface: PBRMaterial::pdf passes its NdotL test and meets the NaN half
+             * vector (eval cannot: it wants NdotL > 0 and NdotV > 0, which wi = -wo never gives) */
+            emit("wi_minus_wo_from_below", dot(Z, wo0) > 0 && ((-wo0) + wo0).length_squared() == 0, Z, -wo0, wo0);
+            emit("wi_zero", true, Z, wo0, vec3(0, 0, 0));
+            /* wi the exact mirror of wo about n; wi unnormalised */
+            emit("wi_mirror_of_wo", true, Z, vec3(0.6, 0.0, 0.8), vec3(-0.6, 0.0, 0.8));
+            emit("wi_scaled_down", true, Z, wo0, wi0 * 0.0009765625);
+            emit("wi_scaled_up", true, Z, wo0, wi0 * 1024.0);
+        }
+        /* wo = n (1 + 2^-52): dot(wo, n) > 1, the dielectric's fmin(cos, 1) acts */
+        emit("wo_longer_than_n", dot(Z * (1.0 + 2.220446049250313e-16), Z) > 1.0, Z, Z * (1.0 + 2.220446049250313e-16), wi0);
+        /* both faces */
+        emit("front_face", true, ng, above(ng, ta), above(ng, tb), true);
+        emit("back_face", true, ng, above(ng, ta), above(ng, tb), false);
+
+        /* textures: (u, v) on and beyond the ends of [0, 1], p at the origin, at negative and integer coordinates, far out */
+        const double uvs[6] = {0.0, 1.0, down(1.0), -0.25, 1.5, 0.5};
+        const vec3 ps[6] = {vec3(0, 0, 0), vec3(-0.0, -0.0, -0.0), vec3(-3, 0, 255), vec3(-0.5, 7, -255.5), vec3(4, -7, 12), vec3(1e5, -1e5, 0.1)};
+        const texture* t0 = lam ? lam->albedo.get() : lit ? lit->emit.get() : iso ? iso->albedo.get() : pbr ? pbr->albedo.get() : nullptr;
+        const bool image = dynamic_cast<const image_texture*>(t0) || (pbr && pbr->normal_map);
+        const bool procedural = dynamic_cast<const checker_texture*>(t0) || dynamic_cast<const noise_texture*>(t0);
+        if (image) {
+            int k = 0;
+            for (double u : uvs)
+                for (double v : uvs) {
+                    if (pbr && u != 0.0 && u != 1.0 && v != 0.0 && v != 1.0 && u != v) continue; /* the normal map: ends and diagonal */
+                    emit("uv_ends_and_beyond", true, ng, above(ng, ta), above(ng, tb), true, u, v, ps[k++ % 6]);
+                }
+        }
+        if (image || procedural)
+            for (const vec3& p : ps) emit("p_zero_negative_integer_far", true, ng, above(ng, ta), above(ng, tb), true, 0.3, 0.6, p);
+
+        if (die_) {
+            /* refraction_ratio * sin_theta straddling 1.0: two neighbouring doubles in one component of the direction, one
+             * on each side of the reference's own compare; the first draw is 0.5, far above the reflectance there, so the
+             * refracting side transmits.  Back face with ir > 1, front face with ir < 1; none for ir = 1 */
+            const bool front = die_->ir < 1.0;
+            const double rr = front ? 1.0 / die_->ir : die_->ir;
+            const uint32_t half = state_before_draw(0x80000000u);
+            for (int k = 0; k < 8 && die_->ir != 1.0; ++k) {
+                const double az = 0.3 + 0.7 * k, s = 1.0 / rr;
+                /* the direction away from the surface at the critical angle, its component along n to be bisected */
+                const double x = s * std::cos(az), y = s * std::sin(az), z0 = std::sqrt(1.0 - s * s);
+                auto dir = [&](double z) { return scatter ? -vec3(x, y, z) : vec3(x, y, z); };
+                double lo = z0 * 1.01, hi = z0 * 0.99; /* steeper: refracts; flatter: cannot */
+                if (cannot_refract(dir(lo), Z, rr) || !cannot_refract(dir(hi), Z, rr)) die("dielectric straddle: bad bracket");
+                for (;;) {
+                    const double mid = lo + (hi - lo) / 2;
+                    if (mid == lo || mid == hi) break;
+                    (cannot_refract(dir(mid), Z, rr) ? hi : lo) = mid;
+                }
+                const bool adjacent = std::nextafter(lo, hi) == hi;
+                emit("dielectric_straddle_refracts", adjacent && !cannot_refract(dir(lo), Z, rr), Z, dir(lo), wi0, front, 0.3, 0.6, P0, half, true);
+                emit("dielectric_straddle_cannot_refract", adjacent && cannot_refract(dir(hi), Z, rr), Z, dir(hi), wi0, front, 0.3, 0.6, P0, half, true);
+            }
+            /* the first draw the nearest multiple of 2^-32 below and above the reference's reflectance (material.h:165-166);
+             * where the reflectance lies within 2^-40 of a multiple, the next one out is taken, so that the one-ulp
+             * difference between a device pow5 and glibc's pow cannot change the side */
+            for (vec3 w : {wo0, above(Z, vec3(0.9, 0.3, -0.6))})
+                for (int face = 0; face < 2; ++face) {
+                    const double ratio = face ? 1.0 / die_->ir : die_->ir;
+                    const vec3 d = scatter ? -w : w;
+                    if (cannot_refract(d, Z, ratio)) continue;
+                    const double R = dielectric::reflectance(cos_of(d, Z), ratio) * 4294967296.0;
+                    double below = std::floor(R), abv = std::ceil(R);
+                    if (R - below < 0.00390625) below -= 1; /* 2^-40 of the draw's scale */
+                    if (abv - R < 0.00390625) abv += 1;
+                    if (below < 1 || abv > 4294967295.0) continue;
+                    emit("dielectric_draw_below_reflectance", dielectric::reflectance(cos_of(d, Z), ratio) > below * 2.3283064365386963e-10, Z, d, wi0,
+                         face != 0, 0.3, 0.6, P0, state_before_draw((uint32_t)below), true);
+                    emit("dielectric_draw_above_reflectance", !(dielectric::reflectance(cos_of(d, Z), ratio) > abv * 2.3283064365386963e-10), Z, d, wi0,
+                         face != 0, 0.3, 0.6, P0, state_before_draw((uint32_t)abv), true);
+                }
+        }
+        if (lam) {
+            /* n = -random_unit_vector() of the record's own generator: rec.normal + random_unit_vector() is the zero vector
+             * and near_zero() fires (material.h:81-84, :105-108); with 2e-8 added to one component it does not */
+            const uint32_t rng = 0x1234567u + 977u * (uint32_t)m;
+            set_rng(rng);
+            const vec3 n = -random_unit_vector();
+            set_rng(rng);
+            const bool fires = (n + random_unit_vector()).near_zero();
+            emit("lambertian_near_zero_fires", fires, n, wo0, wi0, true, 0.3, 0.6, P0, rng);
+            const vec3 n2 = n + vec3(2e-8, 0, 0);
+            set_rng(rng);
+            emit("lambertian_near_zero_just_not", !(n2 + random_unit_vector()).near_zero(), n2, wo0, wi0, true, 0.3, 0.6, P0, rng);
+        }
+        if (pbr && (pbr->normal_map || (pbr_ordinal++ % 3) == 0)) {
+            /* frames: onb::build_from_w's fabs(w.x) > 0.9 (onb.h:32-37) through both sampling branches, and the
+             * fabs(N.y) > 0.999 of the normal-mapped TBN (material.h:252) */
+            const uint32_t ggx = state_before_draw(0x40000000u), cosine = state_before_draw(0xC0000000u);
+            std::vector<std::pair<std::string, vec3>> ns;
+            ns.push_back({"frame_nx_at_0.9", exact_unit_xy(0.9, false)});
+            ns.push_back({"frame_nx_one_ulp_above_0.9", exact_unit_xy(up(0.9), false)});
+            ns.push_back({"frame_nx_0.95", exact_unit_xy(0.95, false)});
+            ns.push_back({"frame_nx_negative", exact_unit_xy(-up(0.9), false)});
+            ns.push_back({"frame_ny_at_0.999", exact_unit_xy(0.999, true)});
+            ns.push_back({"frame_ny_one_ulp_above_0.999", exact_unit_xy(up(0.999), true)});
+            ns.push_back({"frame_ny_1", Y});
+            /* a normal along y that is too short for the fabs(N.y) > 0.999 test: the tangent of the normal-mapped TBN is
+             * unit(cross(N, y)) = unit(0), N becomes NaN and passes every `<= 0` test of eval and pdf */
+            if (pbr->normal_map) ns.push_back({"frame_tbn_tangent_is_nan", vec3(0, 0.5, 0)});
+            for (const auto& c : ns) {
+                const vec3 n = c.second, w = unit_vector(n);
+                bool cond = true;
+                if (c.first == "frame_nx_at_0.9") cond = w.x() == 0.9 && !(fabs(w.x()) > 0.9);
+                if (c.first == "frame_nx_one_ulp_above_0.9") cond = w.x() == up(0.9) && fabs(w.x()) > 0.9;
+                if (c.first == "frame_nx_negative") cond = w.x() < 0 && fabs(w.x()) > 0.9;
+                if (c.first == "frame_ny_at_0.999") cond = n.y() == 0.999 && !(fabs(n.y()) > 0.999);
+                if (c.first == "frame_ny_one_ulp_above_0.999") cond = n.y() == up(0.999) && fabs(n.y()) > 0.999;
+                if (c.first == "frame_tbn_tangent_is_nan") cond = !(fabs(n.y()) > 0.999) && std::isnan(unit_vector(cross(n, vec3(0, 1, 0))).x());
+                emit(c.first, cond, n, above(n, ta), above(n, tb), true, 0.3, 0.6, P0, ggx);
+                emit(c.first, cond, n, above(n, ta), above(n, tb), true, 0.3, 0.6, P0, cosine);
+            }
+        }
+    }
+    int pbr_ordinal = 0;
+};
+
+static int cmd_materials_edge(int scene_id, uint32_t scene_seed, const char* path, bool scatter) {
+    Loaded l = load_scene(scene_id, scene_seed);
+    Flattener f = flatten(l);
+    MatEdgeGen gen;
+    gen.scatter = scatter;
+    for (size_t m = 0; m < f.mats.size(); ++m) {
+        gen.m = (int)m;
+        gen.material_cases(f.mats[m]);
+    }
+    for (MatRecordOut& o : gen.recs) {
+        if (scatter)
+            eval_scatter(f.mats[o.material], o);
+        else
+            eval_material(f.mats[o.material], o);
+    }
+    if (gen.recs.size() > 640) die("materials-edge: " + std::to_string(gen.recs.size()) + " records, more than 640; trim the lists");
+    write_mat_records(path, gen.recs);
+    std::printf("{\"scene\": %d, \"materials\": %zu, \"n\": %zu, ", scene_id, f.mats.size(), gen.recs.size());
+    print_counts(gen.counts);
+    std::printf("}\n");
+    return 0;
+}
+
+struct LightEdgeGen {
+    std::vector<LightRecordOut> recs;
+    CaseCounts counts;
+    int li = 0;
+    void emit(const std::string& name, bool cond, vec3 p, vec2 u, vec3 dir) {
+        LightRecordOut o;
+        std::memset(&o, 0, sizeof o);
+        o.light = li;
+        Flattener::put3(o.p, p);
+        o.u[0] = u.x(), o.u[1] = u.y();
+        Flattener::put3(o.dir, dir);
+        recs.push_back(o);
+        counts[name] += cond ? 1 : 0;
+    }
+    static int major_axis(vec3 n) { return fabs(n.x()) > fabs(n.y()) ? (fabs(n.x()) > fabs(n.z()) ? 0 : 2) : (fabs(n.y()) > fabs(n.z()) ? 1 : 2); }
+    static bool is_int(vec3 v) { return v.x() == std::floor(v.x()) && v.y() == std::floor(v.y()) && v.z() == std::floor(v.z()); }
+
+    void quad(const QuadLight* q) {
+        const vec2 mid(0.5, 0.5);
+        const vec3 g(0.3, -0.5, 0.8);
+        const vec3 n = q->normal, c = q->Q + 0.5 * q->u + 0.5 * q->v;
+        const int ax = major_axis(n);
+        auto cos_at = [&](vec3 p, vec2 u) { /* quad_light.h:22-31 */
+            point3 light_point = q->Q + u.x() * q->u + u.y() * q->v;
+            vec3 d = light_point - p;
+            vec3 wi = d / sqrt(d.length_squared());
+            return dot(-wi, n);
+        };
+        /* sample(): p in the light's plane, one step to either side along the normal, behind, in front, far away, at the
+         * sampled point itself (dist 0, wi NaN), u at the corners */
+        vec3 inplane = q->Q + 1.75 * q->u + 0.25 * q->v;
+        emit("quad_sample_p_in_plane", cos_at(inplane, mid) == 0, inplane, mid, g);
+        vec3 a = inplane, b = inplane;
+        a[ax] = n[ax] > 0 ? up(a[ax]) : down(a[ax]);
+        b[ax] = n[ax] > 0 ? down(b[ax]) : up(b[ax]);
+        emit("quad_sample_p_one_step_in_front", cos_at(a, mid) > 0, a, mid, g);
+        emit("quad_sample_p_one_step_behind", cos_at(b, mid) < 0, b, mid, g);
+        emit("quad_sample_p_behind", cos_at(c - 50.0 * n, mid) < 0, c - 50.0 * n, mid, g);
+        emit("quad_sample_p_far", cos_at(c + 1e6 * n, mid) > 0, c + 1e6 * n, mid, g);
+        const vec2 uu(0.25, 0.75);
+        const point3 lp = q->Q + uu.x() * q->u + uu.y() * q->v;
+        emit("quad_sample_p_is_the_light_point", (lp - lp).length_squared() == 0 && std::isnan(cos_at(lp, uu)), lp, uu, g);
+        for (int k = 0; k < 4; ++k) emit("quad_sample_u_corners", true, c + 80.0 * n + 30.0 * unit_vector(q->u), vec2(k & 1, k >> 1), g);
+        /* pdf(): a direction leaving the front and one leaving the back, the zero direction, scaled directions */
+        const vec3 o1 = c + 100.0 * n;
+        emit("quad_pdf_from_the_front", q->pdf(o1, -n) > 0, o1, mid, -n);
+        emit("quad_pdf_from_the_back", dot(n, n) > 0 && q->pdf(c - 100.0 * n, n) == 0, c - 100.0 * n, mid, n);
+        emit("quad_pdf_dir_zero", true, o1, mid, vec3(0, 0, 0));
+        const vec3 slanted = (c + 0.2 * q->u) - o1;
+        emit("quad_pdf_dir_scaled_down", q->pdf(o1, slanted * 1e-3) > 0, o1, mid, slanted * 1e-3);
+        emit("quad_pdf_dir_scaled_up", q->pdf(o1, slanted * 1e3) > 0, o1, mid, slanted * 1e3);
+        /* exact arithmetic: an axis-aligned light with integer corners (the Cornell lights) */
+        if (!(fabs(n[ax]) == 1.0 && is_int(q->Q) && is_int(q->u) && is_int(q->v))) return;
+        const vec3 o2 = c + n; /* one unit in front: dot(Q - origin, normal) == -1 */
+        auto t_of = [&](vec3 o, vec3 d) { return dot(q->Q - o, n) / dot(d, n); };
+        for (double s : {1e-6, down(1e-6), up(1e-6)}) {
+            const double denom = dot(-n * s, n);
+            emit(denom == -1e-6 ? "quad_pdf_denom_at_minus_1e-6" : denom > -1e-6 ? "quad_pdf_denom_one_ulp_above" : "quad_pdf_denom_one_ulp_below",
+                 dot(q->Q - o2, n) == -1.0, o2, mid, -n * s);
+        }
+        double s_above = down(1000.0); /* 1 / s rounds to 0.001 for the nearest neighbours of 1000 */
+        while (t_of(o2, -n * s_above) == 0.001) s_above = down(s_above);
+        for (double s : {1000.0, s_above, up(1000.0)}) {
+            const double t = t_of(o2, -n * s);
+            emit(t == 0.001 ? "quad_pdf_t_at_0.001" : t < 0.001 ? "quad_pdf_t_below_0.001" : "quad_pdf_t_above_0.001", true, o2, mid, -n * s);
+        }
+        auto ab = [&](vec3 o, double& alpha, double& beta) { /* quad_light.h:58-67 with direction = -n */
+            double t = t_of(o, -n);
+            point3 intersection = o + t * (-n);
+            vec3 pl = intersection - q->Q;
+            alpha = dot(pl, q->u) / q->u.length_squared();
+            beta = dot(pl, q->v) / q->v.length_squared();
+        };
+        const int ua = major_axis(q->u), va = major_axis(q->v);
+        for (int k = 0; k < 9; ++k) { /* alpha, beta from {0, 0.5, 1}: edges, corners, the centre */
+            const vec3 o = q->Q + 0.5 * (k % 3) * q->u + 0.5 * (k / 3) * q->v + n;
+            double al, be;
+            ab(o, al, be);
+            emit("quad_pdf_alpha_beta_on_0_and_1", al == 0.5 * (k % 3) && be == 0.5 * (k / 3) && q->pdf(o, -n) > 0, o, mid, -n);
+        }
+        for (int k = 0; k < 4; ++k) { /* one ulp outside each edge */
+            vec3 o = q->Q + 0.5 * q->u + 0.5 * q->v + n;
+            const bool hi = k & 1;
+            const int axis = k < 2 ? ua : va;
+            const vec3& e = k < 2 ? q->u : q->v;
+            o[axis] = q->Q[axis] + (hi ? e[axis] : 0.0);
+            o[axis] = ((e[axis] > 0) == hi) ? up(o[axis]) : down(o[axis]);
+            double al, be;
+            ab(o, al, be);
+            emit("quad_pdf_alpha_beta_one_ulp_outside", (al < 0 || al > 1 || be < 0 || be > 1) && q->pdf(o, -n) == 0, o, mid, -n);
+        }
+    }
+    void spot(const SpotLight* s) {
+        const vec2 mid(0.5, 0.5);
+        const vec3 g(0.3, -0.5, 0.8);
+        auto lit = [&](vec3 p) { return s->sample(p, mid).Li.length_squared() > 0; };
+        onb f;
+        f.build_from_w(s->direction);
+        const double th = std::acos(s->cos_cutoff);
+        for (int k = 0; k < 8; ++k) { /* cos_theta straddling cos_cutoff: neighbouring doubles in one component of p */
+            const double az = 0.4 + 0.8 * k, dist = 3.0 + 17.0 * k;
+            auto at = [&](double ang) { return s->position + dist * (std::cos(ang) * f.w() + std::sin(ang) * (std::cos(az) * f.u() + std::sin(az) * f.v())); };
+            vec3 in = at(th * 0.999), out = at(th * 1.001);
+            if (!lit(in) || lit(out)) die("spot straddle: bad bracket");
+            int ax = 0; /* bisect along the component in which the two differ most, the others taken from `in` */
+            for (int c = 1; c < 3; ++c)
+                if (fabs(out[c] - in[c]) > fabs(out[ax] - in[ax])) ax = c;
+            vec3 far = in;
+            far[ax] = out[ax];
+            for (int step = 0; lit(far) && step < 60; ++step) far[ax] += out[ax] - in[ax];
+            if (lit(far)) die("spot straddle: no dark end");
+            double lo = in[ax], hi = far[ax];
+            for (;;) {
+                const double m = lo + (hi - lo) / 2;
+                if (m == lo || m == hi) break;
+                vec3 p = in;
+                p[ax] = m;
+                (lit(p) ? lo : hi) = m;
+            }
+            vec3 p0 = in, p1 = in;
+            p0[ax] = lo, p1[ax] = hi;
+            const bool adjacent = std::nextafter(lo, hi) == hi;
+            emit("spot_straddle_lit", adjacent && lit(p0), p0, mid, g);
+            emit("spot_straddle_dark", adjacent && !lit(p1), p1, mid, g);
+        }
+        emit("spot_p_at_the_position", true, s->position, mid, g);
+        emit("spot_p_on_the_axis", lit(s->position + 7.0 * s->direction), s->position + 7.0 * s->direction, mid, g);
+    }
+    void env(const EnvironmentLight* e) {
+        const vec3 P(0.1, 0.2, 0.3), g(0.3, -0.5, 0.8);
+        const vec2 mid(0.5, 0.5);
+        const int w = e->width, h = e->height;
+        if (w == 0) { /* no map: the uniform sphere */
+            emit("env_uniform", true, P, mid, g);
+            return;
+        }
+        const double ends[3] = {0.0, down(1.0), 0.5};
+        for (double ux : ends)
+            for (double uy : ends) emit("env_sample_u_ends", true, P, vec2(ux, uy), g);
+        const Distribution1D& marg = e->distribution.marginal;
+        for (int k : {1, h / 2, h}) { /* u.y equal to an entry of the marginal cdf */
+            emit("env_sample_uy_on_marginal_cdf", true, P, vec2(0.5, marg.cdf[k]), g);
+        }
+        double pdf_unused;
+        int row;
+        marg.sample(0.5, pdf_unused, row);
+        const Distribution1D& cond = e->distribution.conditional[row];
+        for (int k : {1, w / 2, w}) emit("env_sample_ux_on_row_cdf", true, P, vec2(cond.cdf[k], 0.5), g);
+        if (e->is_light_probe) {
+            auto radius = [&](vec2 u) { /* environmental_light.h:196-210 */
+                double map_pdf;
+                vec2 uv = e->distribution.sample(u, map_pdf);
+                double uc = uv.x() * 2.0 - 1.0;
+                double vc = (1.0 - uv.y()) * 2.0 - 1.0;
+                return map_pdf == 0 ? -1.0 : sqrt(uc * uc + vc * vc);
+            };
+            const vec2 corner(0.001, 0.001);
+            emit("env_probe_outside_the_disc", radius(corner) > 1.0, P, corner, g);
+            /* v = 0.5 from the marginal cdf entry h/2, u = 1 from the last entry of that row's cdf, u = 0.5 from its middle one */
+            const double uy = marg.cdf[h / 2];
+            marg.sample(uy, pdf_unused, row);
+            const Distribution1D& r2 = e->distribution.conditional[row];
+            emit("env_probe_on_the_disc", radius(vec2(r2.cdf[w], uy)) == 1.0, P, vec2(r2.cdf[w], uy), g);
+            emit("env_probe_centre", radius(vec2(r2.cdf[w / 2], uy)) == 0.0, P, vec2(r2.cdf[w / 2], uy), g);
+        }
+        /* pdf(): the axes (the poles of both mappings; d == 0 in the probe), the seam of the equirectangular map where
+         * u = 0 and u = 1 come from the sign of a zero, one step off it, the zero direction */
+        auto seam_index = [&](vec3 d) { /* environmental_light.h:319,334-346: int(u * width) before the clamp */
+            vec3 unit_dir = unit_vector(d);
+            auto phi = atan2(-unit_dir.z(), unit_dir.x()) + pi;
+            return int((phi / (2 * pi)) * w);
+        };
+        const double tiny = std::numeric_limits<double>::denorm_min();
+        for (vec3 d : {vec3(1, 0, 0), vec3(-1, 0, 0), vec3(0, 1, 0), vec3(0, -1, 0), vec3(0, 0, 1), vec3(0, 0, -1)}) emit("env_pdf_axes", true, P, mid, d);
+        emit("env_pdf_seam_plus_zero", e->is_light_probe || seam_index(vec3(-1, 0, 0.0)) == 0, P, mid, vec3(-1, 0, 0.0)); /* atan2(-0, -1) = -pi: u = 0 */
+        emit("env_pdf_seam_minus_zero", e->is_light_probe || seam_index(vec3(-1, 0, -0.0)) == w, P, mid, vec3(-1, 0, -0.0)); /* atan2(+0, -1) = pi: u = 1 */
+        for (double z : {tiny, -tiny, 1e-15, -1e-15}) emit("env_pdf_one_step_off_the_seam", true, P, mid, vec3(-1, 0, z));
+        emit("env_pdf_dir_zero", std::isnan(e->pdf(P, vec3(0, 0, 0))), P, mid, vec3(0, 0, 0));
+    }
+    void light(const Light* L) {
+        const vec2 mid(0.5, 0.5);
+        const vec3 g(0.3, -0.5, 0.8);
+        if (auto q = dynamic_cast<const QuadLight*>(L)) {
+            quad(q);
+        } else if (auto s = dynamic_cast<const SpotLight*>(L)) {
+            spot(s);
+        } else if (auto p = dynamic_cast<const PointLight*>(L)) {
+            emit("point_p_at_the_position", std::isinf(p->sample(p->m_position, mid).Li.x()), p->m_position, mid, g);
+            const vec3 near_ = p->m_position + vec3(1e-150, 0, 0);
+            emit("point_p_offset_1e-150", true, near_, mid, g);
+            emit("point_p_generic", true, p->m_position + vec3(3, -4, 12), mid, g);
+        } else if (dynamic_cast<const DirectionalLight*>(L)) {
+            emit("directional_p_zero", true, vec3(0, 0, 0), mid, g);
+            emit("directional_p_1e300", true, vec3(1e300, -1e300, 1e300), mid, g);
+        } else if (auto e = dynamic_cast<const EnvironmentLight*>(L)) {
+            env(e);
+        } else {
+            die("lights-edge: unknown light class");
+        }
+    }
+};
+
+static int cmd_lights_edge(int scene_id, uint32_t scene_seed, const char* path) {
+    Loaded l = load_scene(scene_id, scene_seed);
+    LightEdgeGen gen;
+    for (size_t li = 0; li < l.cfg.lights.size(); ++li) {
+        gen.li = (int)li;
+        gen.light(l.cfg.lights[li].get());
+    }
+    for (LightRecordOut& o : gen.recs) {
+        const Light* L = l.cfg.lights[o.light].get();
+        const vec3 p(o.p[0], o.p[1], o.p[2]);
+        set_rng(0x2545F491u); /* EnvironmentLight::sample draws from the global generator */
+        LightSample s = L->sample(p, vec2(o.u[0], o.u[1]));
+        Flattener::put3(o.Li, s.Li);
+        Flattener::put3(o.wi, s.wi);
+        o.pdf = s.pdf, o.dist = s.dist, o.is_delta = s.is_delta;
+        o.pdf_dir = L->pdf(p, vec3(o.dir[0], o.dir[1], o.dir[2]));
+    }
     FILE* fo = std::fopen(path, "wb");
     if (!fo) die("cannot open output");
-    std::fwrite(recs.data(), sizeof(MatRecordOut), recs.size(), fo);
+    std::fwrite(gen.recs.data(), sizeof(LightRecordOut), gen.recs.size(), fo);
     std::fclose(fo);
-    std::printf("{\"scene\": %d, \"materials\": %zu, \"n\": %zu}\n", scene_id, f.mats.size(), recs.size());
+    std::printf("{\"scene\": %d, \"lights\": %zu, \"n\": %zu, ", scene_id, l.cfg.lights.size(), gen.recs.size());
+    print_counts(gen.counts);
+    std::printf("}\n");
+    return 0;
+}
+
+/* x and glibc's pow(x, 5.0) (material.h:202,431) as pairs of doubles: 32768 x uniform in [0, 1), 16384 of the form 1 - c
+ * with c uniform (the shape 1 - cosTheta has), 0, 1, 2^-k for k up to 215 with their neighbours, the rest uniform: 65536 in
+ * all, of which this writes slice `part` of `parts` (a fixture file stays below 160 KB) */
+static int cmd_pow5(int part, int parts, const char* path) {
+    if (parts < 1 || part < 0 || part >= parts) die("pow5: bad part");
+    std::mt19937_64 g(5555);
+    auto U = [&]() { return (double)(g() >> 11) * 1.1102230246251565e-16; };
+    std::vector<double> x;
+    for (int k = 0; k < 32768; ++k) x.push_back(U());
+    for (int k = 0; k < 16384; ++k) x.push_back(1.0 - U());
+    x.push_back(0.0), x.push_back(up(0.0)), x.push_back(1.0), x.push_back(down(1.0));
+    for (int k = 1; k <= 215; ++k) {
+        const double p = std::ldexp(1.0, -k);
+        x.push_back(p), x.push_back(up(p)), x.push_back(down(p));
+    }
+    while (x.size() < 65536) x.push_back(U());
+    FILE* fo = std::fopen(path, "wb");
+    if (!fo) die("cannot open output");
+    const size_t k0 = x.size() * part / parts, k1 = x.size() * (part + 1) / parts;
+    for (size_t k = k0; k < k1; ++k) {
+        const double pair[2] = {x[k], pow(x[k], 5)};
+        std::fwrite(pair, sizeof(double), 2, fo);
+    }
+    std::fclose(fo);
+    std::printf("{\"n\": %zu, \"first\": %zu, \"of\": %zu}\n", k1 - k0, k0, x.size());
     return 0;
 }
 
@@ -1148,8 +1723,13 @@ int main(int argc, char** argv) {
     if (c == "li" && argc == 10) return cmd_li(I(2), I(3), I(4), I(5), U(6), U(7), I(8), argv[9]);
     if (c == "hits" && argc == 7) return cmd_hits(I(2), U(3), I(4), std::strtoull(argv[5], nullptr, 0), argv[6]);
     if (c == "materials" && argc == 7)
-        return cmd_materials(I(2), U(3), I(4), std::strtoull(argv[5], nullptr, 0), argv[6]);
+        return cmd_materials(I(2), U(3), I(4), std::strtoull(argv[5], nullptr, 0), argv[6], false);
+    if (c == "scatter" && argc == 7) return cmd_materials(I(2), U(3), I(4), std::strtoull(argv[5], nullptr, 0), argv[6], true);
     if (c == "lights" && argc == 7) return cmd_lights(I(2), U(3), I(4), std::strtoull(argv[5], nullptr, 0), argv[6]);
+    if (c == "materials-edge" && argc == 5) return cmd_materials_edge(I(2), U(3), argv[4], false);
+    if (c == "scatter-edge" && argc == 5) return cmd_materials_edge(I(2), U(3), argv[4], true);
+    if (c == "lights-edge" && argc == 5) return cmd_lights_edge(I(2), U(3), argv[4]);
+    if (c == "pow5" && argc == 5) return cmd_pow5(I(2), I(3), argv[4]);
     if (c == "rng" && argc == 3) return cmd_rng(argv[2]);
     if (c == "wrap-bvh" && argc == 5) return cmd_wrap_bvh(argv[2], U(3), argv[4]);
     if (c == "hits-rtrs" && argc == 5) return cmd_hits_rtrs(argv[2], argv[3], argv[4]);

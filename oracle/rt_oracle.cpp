@@ -1491,6 +1491,34 @@ int rto_materials(const rtr_scene_desc* scene, rtr_mat_record* recs, int64_t n) 
     return RTR_OK;
 }
 
+/* the legacy material::scatter(r_in, rec, attenuation, scattered) in the layout of rto_materials: wo is r_in.direction(),
+ * sample_ok the return value, s_wi scattered.direction(), s_f the attenuation; the other outputs are zero */
+int rto_scatter(const rtr_scene_desc* scene, rtr_mat_record* recs, int64_t n) {
+    if (!scene || !recs) return RTR_ERR_INVALID;
+    Scene sc{scene};
+    for (int64_t k = 0; k < n; ++k) {
+        rtr_mat_record& o = recs[k];
+        if (o.material < 0 || o.material >= scene->n_materials) return RTR_ERR_INVALID;
+        Rec rec;
+        rec.p = ld(o.p), rec.normal = ld(o.n);
+        rec.u = o.u, rec.v = o.v, rec.t = 1.0;
+        rec.front_face = o.front_face != 0;
+        rec.mat = o.material;
+        const Ray r_in = make_ray(rec.p, ld(o.wo), 0.0);
+        Rng g{o.rng_in};
+        V3 attenuation = mk(0, 0, 0);
+        Ray scattered = make_ray(mk(0, 0, 0), mk(0, 0, 0), 0.0);
+        const bool ok = mat_scatter(sc, r_in, rec, attenuation, scattered, g);
+        o.rng_out = g.s;
+        o.sample_ok = ok, o.is_specular = 0, o.is_transmission = 0, o.pad = 0;
+        o.s_wi[0] = scattered.d.x, o.s_wi[1] = scattered.d.y, o.s_wi[2] = scattered.d.z;
+        o.s_f[0] = attenuation.x, o.s_f[1] = attenuation.y, o.s_f[2] = attenuation.z;
+        o.s_pdf = 0, o.pdf = 0;
+        for (int c = 0; c < 3; ++c) o.eval[c] = o.emitted[c] = 0;
+    }
+    return RTR_OK;
+}
+
 int rto_lights(const rtr_scene_desc* scene, rtr_light_record* recs, int64_t n) {
     if (!scene || !recs) return RTR_ERR_INVALID;
     for (int64_t k = 0; k < n; ++k) {

@@ -16,6 +16,8 @@ struct rtr_debug_view {
     int trav;           /* RT_TRAV_* template value of the per-ray kernels for a call with `flags` (per_ray_trav, rt_select.h) */
     size_t stack_bytes; /* LDS traversal stack per workgroup of that traversal */
     int flat_trav;      /* RT_TRAV_FLAT / RT_TRAV_FLAT_GUARD where the megakernel of such a call runs a flat kernel, else -1 */
+    int lean_ok, quadlit_ok; /* mega_variant's predicates for RT_MS_LEAN / RT_MS_QUADLIT kernels (rt_select.h):
+                                SceneFacts::lean_materials; quad_lights_only and no texture that reads (u,v) */
 };
 /* the kernels the last render call launched, recorded on the host when they are enqueued (no device work) */
 struct rtr_debug_kernel {

@@ -8,7 +8,7 @@
  * reference's operation order in IEEE binary64 (division and sqrt correctly rounded), so
  * results are bit-identical to the reference wherever no libm transcendental is involved
  * (all of the Cornell scenes); sin/cos/log/acos/atan2 come from OCML and may differ from
- * glibc in the last ulp (scenes 23, 9, 22); pow(x, 5) is a correctly rounded x^5 (pow5).  RNG draws are sequenced in the order
+ * glibc in the last ulp (scenes 23, 9, 22); pow(x, 5) is x^5 in double-double arithmetic (pow5: within one ulp of glibc's).  RNG draws are sequenced in the order
  * g++ evaluates the reference's argument lists.
  *
  * Citations are reference paths relative to /root/reference/src.
@@ -2227,10 +2227,14 @@ RT_DEV Real geometry_smith(V3 N, V3 V, V3 L, Real roughness) { /* material.h:421
     Real ggx1 = geometry_schlick_ggx(NdotL, roughness);
     return ggx1 * ggx2;
 }
-/* pow(x, 5.0) of the reference (material.h:202,431; glibc: correctly rounded in nearly all cases) as
- * x^5 in double-double arithmetic: the rounded sum is the correctly rounded x^5 up to rare half-way
- * cases -- closer to glibc than OCML's pow, at a tenth of its instructions. */
-RT_DEV Real pow5(Real x) {
+/* pow(x, 5.0) of the reference (material.h:202,431) as x^5 in double-double arithmetic -- closer to glibc's pow than
+ * OCML's, at a tenth of its instructions, but not equal to it: against glibc's pow on the 65 536 values of
+ * tests/golden/pow5_*.bin (uniform x, x = 1 - c, powers of two down to the denormals) it differs on 57, always by one
+ * ulp (about one value in a thousand; harmless at the 1e-11 the PBR and dielectric vectors are held to).  The count per
+ * file is `differs_from_pow5_host` in tests/golden/manifest.json; a CPU test holds a host build of these lines
+ * (rtr_test_pow5_host) to it exactly, and tests/test_shading_edges.py holds the device to the host build bit for bit, so
+ * reordering the low-order terms below does not pass. */
+RT_HD Real pow5(Real x) {
     const Real h2 = x * x, l2 = __builtin_fma(x, x, -h2);
     const Real h4 = h2 * h2, l4 = __builtin_fma(h2, h2, -h4) + 2.0 * h2 * l2;
     const Real h5 = h4 * x, l5 = __builtin_fma(h4, x, -h5) + l4 * x;

@@ -93,6 +93,12 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_pair(const DScene sc, rtr_pa
     recs[k] = r;
 }
 
+/* equal in every bit, a NaN equal to a NaN of any payload */
+RT_DEV bool same_bits(Real a, Real b) { return (a != a && b != b) || __double_as_longlong(a) == __double_as_longlong(b); }
+
+/* mat_prepare + mat_sample / mat_eval / mat_pdf / mat_emitted of the MS instantiation, and the fused mat_eval_pdf the MIS
+ * kernels call for the light sample: pad bit 0 = its f differs from mat_eval, bit 1 = its pdf differs from mat_pdf */
+template <int MS>
 __global__ void __launch_bounds__(RTR_BLOCK) k_test_materials(const DScene sc, rtr_mat_record* recs, long long n) {
     const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
     if (k >= n) return;
@@ -106,34 +112,70 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_materials(const DScene sc, r
     uint32_t rng = r.rng_in;
     BSDFSample bs;
     bs.wi = mk(0, 0, 0), bs.f = mk(0, 0, 0), bs.pdf = 0, bs.is_specular = false, bs.is_transmission = false;
-    const MatCtx mc = mat_prepare(sc, rec);
-    const bool ok = mat_sample(mc, rec, wo, bs, rng);
+    const MatCtx mc = mat_prepare<MS>(sc, rec);
+    const bool ok = mat_sample<MS>(mc, rec, wo, bs, rng);
     r.rng_out = rng;
-    r.sample_ok = ok, r.is_specular = bs.is_specular, r.pad = 0;
+    r.sample_ok = ok, r.is_specular = bs.is_specular;
     r.is_transmission = bs.is_transmission;
     r.s_wi[0] = bs.wi.x, r.s_wi[1] = bs.wi.y, r.s_wi[2] = bs.wi.z;
     r.s_f[0] = bs.f.x, r.s_f[1] = bs.f.y, r.s_f[2] = bs.f.z;
     r.s_pdf = bs.pdf;
-    const V3 e = mat_eval(mc, wo, wi);
+    const V3 e = mat_eval<MS>(mc, wo, wi);
     r.eval[0] = e.x, r.eval[1] = e.y, r.eval[2] = e.z;
-    r.pdf = mat_pdf(mc, rec, wo, wi);
+    r.pdf = mat_pdf<MS>(mc, rec, wo, wi);
     const V3 em = mat_emitted(mc, rec);
     r.emitted[0] = em.x, r.emitted[1] = em.y, r.emitted[2] = em.z;
+    V3 f2;
+    Real pdf2;
+    mat_eval_pdf<MS>(mc, rec, wo, wi, f2, pdf2);
+    r.pad = (same_bits(f2.x, e.x) && same_bits(f2.y, e.y) && same_bits(f2.z, e.z) ? 0 : 1) | (same_bits(pdf2, r.pdf) ? 0 : 2);
     recs[k] = r;
 }
 
+/* mat_prepare + the legacy mat_scatter with rd = wo: sample_ok the return value, s_wi the new direction, s_f the attenuation */
+template <int MS>
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_scatter(const DScene sc, rtr_mat_record* recs, long long n) {
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    rtr_mat_record r = recs[k];
+    Hit rec;
+    rec.p = ld3(r.p), rec.n = ld3(r.n);
+    rec.u = r.u, rec.v = r.v, rec.t = 1.0;
+    rec.front = r.front_face != 0;
+    rec.mat = r.material;
+    uint32_t rng = r.rng_in;
+    V3 attenuation = mk(0, 0, 0), dir = mk(0, 0, 0);
+    const MatCtx mc = mat_prepare<MS>(sc, rec);
+    const bool ok = mat_scatter<MS>(mc, ld3(r.wo), rec, attenuation, dir, rng);
+    r.rng_out = rng;
+    r.sample_ok = ok, r.is_specular = 0, r.is_transmission = 0, r.pad = 0;
+    r.s_wi[0] = dir.x, r.s_wi[1] = dir.y, r.s_wi[2] = dir.z;
+    r.s_f[0] = attenuation.x, r.s_f[1] = attenuation.y, r.s_f[2] = attenuation.z;
+    r.s_pdf = 0, r.pdf = 0;
+    r.eval[0] = r.eval[1] = r.eval[2] = 0;
+    r.emitted[0] = r.emitted[1] = r.emitted[2] = 0;
+    recs[k] = r;
+}
+
+template <int MS>
 __global__ void __launch_bounds__(RTR_BLOCK) k_test_lights(const DScene sc, rtr_light_record* recs, long long n) {
     const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
     if (k >= n) return;
     rtr_light_record r = recs[k];
     const rtr_light l = ld_const(sc.lights, r.light);
     uint32_t rng = 0x2545F491u; /* the uniform environment light draws its direction itself */
-    LightSample s = light_sample(l, ld3(r.p), r.u[0], r.u[1], rng, sc.image_bytes);
+    LightSample s = light_sample<MS>(l, ld3(r.p), r.u[0], r.u[1], rng, sc.image_bytes);
     r.Li[0] = s.Li.x, r.Li[1] = s.Li.y, r.Li[2] = s.Li.z;
     r.wi[0] = s.wi.x, r.wi[1] = s.wi.y, r.wi[2] = s.wi.z;
     r.pdf = s.pdf, r.dist = s.dist, r.is_delta = s.is_delta, r.pad2 = 0;
-    r.pdf_dir = light_pdf(l, ld3(r.p), ld3(r.dir), sc.image_bytes);
+    r.pdf_dir = light_pdf<MS>(l, ld3(r.p), ld3(r.dir), sc.image_bytes);
     recs[k] = r;
+}
+
+/* rtr_test_pow5: pow5 of rt_device.h, one value per lane */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_pow5(const double* __restrict__ x, double* __restrict__ out, long long n) {
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k < n) out[k] = pow5(x[k]);
 }
 
 /* rtr_test_stream8: 8 bytes per lane in, 8 bytes per lane out */

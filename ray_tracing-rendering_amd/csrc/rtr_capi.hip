@@ -735,6 +735,8 @@ int rtr_debug_view_get(rtr_context* c, int flags, rtr_debug_view* v, size_t size
     /* mega_variant's choice for MIS / RR where that is a flat kernel */
     const int mega = mega_variant(c->facts, RTR_INTEGRATOR_MIS, pick_trav(c->facts, c->info, flags), flags, nullptr).trav;
     v->flat_trav = mega == RT_TRAV_FLAT || mega == RT_TRAV_FLAT_GUARD ? mega : -1;
+    v->lean_ok = c->facts.lean_materials;
+    v->quadlit_ok = c->facts.quad_lights_only && !c->facts.needs_uv;
     return RTR_OK;
 }
 int rtr_debug_scene_plan(const rtr_scene_desc* s, int integrator, int flags, rtr_debug_plan* out, size_t size, int32_t* ref_flags,

@@ -137,7 +137,26 @@ int rtr_test_flat_hits(rtr_context* c, rtr_hit_record* recs, int64_t n, int with
     return end(c, v.stream, t, recs, n, sizeof *recs);
 }
 
-int rtr_test_materials(rtr_context* c, rtr_mat_record* recs, int64_t n) {
+/* the unit kernels of the shading functions, instantiated for material set `ms` as the render kernels are; a scene that
+ * mega_variant would not give such a kernel is refused before anything is copied */
+static int ms_refused(rtr_context* c, int ms) {
+    rtr_debug_view v;
+    if (ms != RT_MS_LEAN && ms != RT_MS_FULL && ms != RT_MS_QUADLIT) return fail(c, RTR_ERR_INVALID, "unknown material set");
+    if (int rc = rtr_debug_view_get(c, 0, &v, sizeof v)) return rc;
+    if (ms == RT_MS_LEAN && !v.lean_ok) return fail(c, RTR_ERR_UNSUPPORTED, "the uploaded scene gets no RT_MS_LEAN kernel");
+    if (ms == RT_MS_QUADLIT && !v.quadlit_ok) return fail(c, RTR_ERR_UNSUPPORTED, "the uploaded scene gets no RT_MS_QUADLIT kernel");
+    return RTR_OK;
+}
+#define RTR_LAUNCH_MS(KERNEL, ms, ...)                                                                        \
+    do {                                                                                                       \
+        if ((ms) == RT_MS_LEAN) hipLaunchKernelGGL(KERNEL<RT_MS_LEAN>, __VA_ARGS__);                           \
+        else if ((ms) == RT_MS_QUADLIT) hipLaunchKernelGGL(KERNEL<RT_MS_QUADLIT>, __VA_ARGS__);                \
+        else hipLaunchKernelGGL(KERNEL<RT_MS_FULL>, __VA_ARGS__);                                              \
+    } while (0)
+
+static int mat_records(rtr_context* c, rtr_mat_record* recs, int64_t n, int ms, bool scatter) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = ms_refused(c, ms)) return rc;
     rtr_debug_view v;
     TestState* t;
     int rc = begin(c, recs, n, sizeof *recs, v, t);
@@ -145,12 +164,21 @@ int rtr_test_materials(rtr_context* c, rtr_mat_record* recs, int64_t n) {
     for (int64_t k = 0; k < n; ++k)
         if (recs[k].material < 0 || recs[k].material >= v.n_materials) return fail(c, RTR_ERR_INVALID, "material index out of range");
     TCHK(c, hipSetDevice(v.device));
-    hipLaunchKernelGGL(k_test_materials, grid_of(n), dim3(RTR_BLOCK), 0, v.stream, v.ds, static_cast<rtr_mat_record*>(t->buf),
-                       (long long)n);
+    auto* d = static_cast<rtr_mat_record*>(t->buf);
+    if (scatter)
+        RTR_LAUNCH_MS(k_test_scatter, ms, grid_of(n), dim3(RTR_BLOCK), 0, v.stream, v.ds, d, (long long)n);
+    else
+        RTR_LAUNCH_MS(k_test_materials, ms, grid_of(n), dim3(RTR_BLOCK), 0, v.stream, v.ds, d, (long long)n);
     return end(c, v.stream, t, recs, n, sizeof *recs);
 }
+int rtr_test_materials_ms(rtr_context* c, rtr_mat_record* recs, int64_t n, int32_t ms) { return mat_records(c, recs, n, ms, false); }
+int rtr_test_materials(rtr_context* c, rtr_mat_record* recs, int64_t n) { return mat_records(c, recs, n, RT_MS_FULL, false); }
+int rtr_test_scatter_ms(rtr_context* c, rtr_mat_record* recs, int64_t n, int32_t ms) { return mat_records(c, recs, n, ms, true); }
+int rtr_test_scatter(rtr_context* c, rtr_mat_record* recs, int64_t n) { return mat_records(c, recs, n, RT_MS_FULL, true); }
 
-int rtr_test_lights(rtr_context* c, rtr_light_record* recs, int64_t n) {
+int rtr_test_lights_ms(rtr_context* c, rtr_light_record* recs, int64_t n, int32_t ms) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = ms_refused(c, ms)) return rc;
     rtr_debug_view v;
     TestState* t;
     int rc = begin(c, recs, n, sizeof *recs, v, t);
@@ -158,9 +186,34 @@ int rtr_test_lights(rtr_context* c, rtr_light_record* recs, int64_t n) {
     for (int64_t k = 0; k < n; ++k)
         if (recs[k].light < 0 || recs[k].light >= v.ds.n_lights) return fail(c, RTR_ERR_INVALID, "light index out of range");
     TCHK(c, hipSetDevice(v.device));
-    hipLaunchKernelGGL(k_test_lights, grid_of(n), dim3(RTR_BLOCK), 0, v.stream, v.ds, static_cast<rtr_light_record*>(t->buf),
-                       (long long)n);
+    RTR_LAUNCH_MS(k_test_lights, ms, grid_of(n), dim3(RTR_BLOCK), 0, v.stream, v.ds, static_cast<rtr_light_record*>(t->buf), (long long)n);
     return end(c, v.stream, t, recs, n, sizeof *recs);
+}
+int rtr_test_lights(rtr_context* c, rtr_light_record* recs, int64_t n) { return rtr_test_lights_ms(c, recs, n, RT_MS_FULL); }
+
+int rtr_test_pow5(rtr_context* c, const double* x, double* out, int64_t n) {
+    if (!c) return RTR_ERR_INVALID;
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(c, RTR_ERR_INVALID, "bad array");
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc || n == 0) return rc;
+    if ((rc = ensure(c, *t, (size_t)n * 16))) return rc;
+    double* dx = static_cast<double*>(t->buf);
+    double* dout = dx + n;
+    TCHK(c, hipMemcpy(dx, x, (size_t)n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_test_pow5, grid_of(n), dim3(RTR_BLOCK), 0, stream, dx, dout, (long long)n);
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream));
+    TCHK(c, hipMemcpy(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return RTR_OK;
+}
+
+int rtr_test_pow5_host(const double* x, double* out, int64_t n) {
+    if (n < 0 || (n > 0 && (!x || !out))) return RTR_ERR_INVALID;
+    for (int64_t k = 0; k < n; ++k) out[k] = pow5(x[k]);
+    return RTR_OK;
 }
 
 /* Integrator::Li per camera sample with the RNG state at exit and the segment counts: the product's own per-ray kernel

@@ -37,7 +37,9 @@ TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_t
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
                 "rtr_test_last_gather",
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
-                "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host")
+                "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
+                "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
+                "rtr_test_pow5_host")
 _TEST_LIB = None
 
 
@@ -80,6 +82,7 @@ PAIR_DTYPE = np.dtype([("ao", "<f8", (3,)), ("ad", "<f8", (3,)), ("a_tmax", "<f8
                        ("b_tmax", "<f8"), ("a_t", "<f8"), ("s_a_t", "<f8"), ("a_ref", "<i4"), ("a_inst", "<i4"),
                        ("b_hit", "<i4"), ("s_a_ref", "<i4"), ("s_a_inst", "<i4"), ("s_b_hit", "<i4")])
 QUEUE_BLOCK_DTYPE = np.dtype([(name, "<i4") for name in ("slot", "quarter", "chunk", "s0", "s1", "ref_s0", "ref_s1", "pad")])
+MS_LEAN, MS_FULL, MS_QUADLIT = 0, 1, 2  # RT_MS_* (csrc/rt_device.h): the material-set instantiations of the kernels
 FRAME_SHAPES = ("none", "T", "R", "TR", "RT", "other")  # FInst::shape (csrc/rt_device.h: RT_SHAPE_*)
 
 
@@ -195,8 +198,12 @@ def test_lib():
         raise RtrError(A.RTR_ERR_DEVICE, "test library %s is missing: run __graft_entry__.build()" % path)
     T = C.CDLL(path, mode=C.RTLD_GLOBAL)
     vp = C.c_void_p
-    for name in ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights"):
+    for name in ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_scatter"):
         getattr(T, name).argtypes = [vp, vp, C.c_int64]
+    for name in ("rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms"):
+        getattr(T, name).argtypes = [vp, vp, C.c_int64, C.c_int32]
+    T.rtr_test_pow5.argtypes = [vp, vp, vp, C.c_int64]
+    T.rtr_test_pow5_host.argtypes = [vp, vp, C.c_int64]
     T.rtr_test_li.argtypes = [vp, C.POINTER(A.RenderParamsC), vp, C.c_int64]
     T.rtr_test_reference_order.argtypes = [vp, C.c_int]
     T.rtr_test_stream8.argtypes = [vp, C.c_int64, C.c_int]
@@ -281,6 +288,16 @@ def pair_frame_host(shape, ops, ao, ad, bo, bd):
     if rc != 0:
         raise RtrError(rc, "rtr_test_pair_frame_host")
     return recs
+
+
+def pow5_host(x):
+    """rtr_test_pow5_host (include/rtr_hip_test.h; no GPU needed): the host build of the device's pow5 over an array."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros_like(x)
+    rc = test_lib().rtr_test_pow5_host(x.ctypes.data, out.ctypes.data, x.size)
+    if rc != 0:
+        raise RtrError(rc, "rtr_test_pow5_host")
+    return out
 
 
 def queue_blocks_host(n_tiles, spp, chunks, guided=(0, 0, 0)):
@@ -842,8 +859,20 @@ class Context:
         return recs
 
     # device unit kernels over golden-vector records (include/rtr_hip_test.h)
-    def test_records(self, kind, recs, params=None):
+    def test_records(self, kind, recs, params=None, ms=None):
+        """kind: "hits", "materials", "scatter", "lights", "li" over their record arrays, or "pow5" over an array of
+        doubles.  ms (``MS_LEAN`` / ``MS_FULL`` / ``MS_QUADLIT``; materials, scatter and lights only): the material-set
+        instantiation of the kernels; raises RtrError (RTR_ERR_UNSUPPORTED) where the scene is not of that class."""
         out = np.ascontiguousarray(recs.copy())
+        if kind == "pow5":
+            x = np.ascontiguousarray(recs, dtype=np.float64)
+            out = np.zeros_like(x)
+            self._chk(test_lib().rtr_test_pow5(self._h, x.ctypes.data, out.ctypes.data, x.size))
+            return out
+        if ms is not None:
+            fn = getattr(test_lib(), "rtr_test_%s_ms" % kind)
+            self._chk(fn(self._h, out.ctypes.data, len(out), int(ms)))
+            return out
         fn = getattr(test_lib(), "rtr_test_" + kind)
         if kind == "li":
             self._chk(fn(self._h, C.byref(params), out.ctypes.data, len(out)))

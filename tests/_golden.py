@@ -60,7 +60,7 @@ def oracle():
         P = C.POINTER
         lib.rto_render.argtypes = [P(A.SceneDescC), P(A.RenderParamsC), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         lib.rto_li.argtypes = [P(A.SceneDescC), P(A.RenderParamsC), C.c_void_p, C.c_int64]
-        for fn in (lib.rto_hits, lib.rto_hits_running_guard, lib.rto_materials, lib.rto_lights):
+        for fn in (lib.rto_hits, lib.rto_hits_running_guard, lib.rto_materials, lib.rto_scatter, lib.rto_lights):
             fn.argtypes = [P(A.SceneDescC), C.c_void_p, C.c_int64]
         lib.rto_rng_block.argtypes = [C.c_uint32, C.c_void_p]
         lib.rto_sample_seed.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]

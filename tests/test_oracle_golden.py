@@ -287,3 +287,117 @@ def test_region_matches_full_image():
     full, _ = G.oracle_render(sc, A.make_params(48, 27, 3), threads=2)
     sub, _ = G.oracle_render(sc, A.make_params(48, 27, 3, region=(5, 3, 37, 20)), threads=2)
     assert np.array_equal(sub, full[3:20, 5:37])
+
+
+# ---- vectors built ON the decisions of the shading functions (oracle/ref_harness.cpp: materials-edge, scatter,
+# scatter-edge, lights-edge, pow5; oracle/gen_golden.py --add-shading-edges) ---------------------------------------
+import _shading_edges as E  # noqa: E402
+
+
+def _assert_same(out, gold, fields, mask=None):
+    for f in fields:
+        a, b = (out[f], gold[f]) if mask is None else (out[f][mask], gold[f][mask])
+        assert np.array_equal(np.isnan(a), np.isnan(b)), f
+        assert np.all(E.same(a, b)), f
+
+
+@pytest.mark.parametrize("sid", E.MATERIAL_EDGE_SCENES)
+def test_material_edge_vectors(sid):
+    """material::sample / eval / pdf / emitted on constructed records: NaN operands (wi = -wo, zero vectors), dot
+    products of +0, -0 and one step either side, the dielectric's critical angle and reflectance draw, near_zero,
+    the frame thresholds, the ends of the texture coordinates.  Every output field the reference writes, bit for
+    bit, a NaN equal to a NaN."""
+    sc = G.scene(sid)
+    gold = G.records(E.material_edge_name(sid), A.MAT_DTYPE)
+    out = G.oracle_records(sc, "rto_materials", gold)
+    for f in ("sample_ok", "rng_out", "is_transmission", "pad"):
+        assert np.array_equal(out[f], gold[f]), f
+    _assert_same(out, gold, ("eval", "pdf", "emitted"))
+    ok = E.sample_written(sc, gold)
+    _assert_same(out, gold, ("s_wi", "s_f", "s_pdf"), ok)
+    assert np.array_equal(out["is_specular"][ok], gold["is_specular"][ok])
+
+
+@pytest.mark.parametrize("name", sorted(E.SCATTER_FILES))
+def test_scatter_vectors(name):
+    """The legacy material::scatter of integrators 0 and 1 (material.h:103-112, :133-140, :176-193,
+    constant_medium.h:19-24), random and constructed records: return value, generator state, scattered direction and
+    attenuation where the class writes them; every other output is zero on both sides."""
+    sc = G.scene(E.SCATTER_FILES[name])
+    gold = G.records(name, A.MAT_DTYPE)
+    out = G.oracle_records(sc, "rto_scatter", gold)
+    for f in ("sample_ok", "rng_out", "is_specular", "is_transmission", "pad"):
+        assert np.array_equal(out[f], gold[f]), f
+    _assert_same(out, gold, ("s_wi", "s_f"), E.scatter_written(sc, gold))
+    _assert_same(out, gold, ("s_pdf", "eval", "pdf", "emitted"))
+    types = E.material_types(sc, gold)
+    assert (gold["sample_ok"] == 1).any() and (gold["sample_ok"] == 0).any()
+    assert (gold["sample_ok"][types == A.MAT_METAL] == 0).any()  # a reflection below the surface
+    assert set(np.unique(types)) >= {A.MAT_LAMBERTIAN, A.MAT_METAL, A.MAT_DIELECTRIC, A.MAT_DIFFUSE_LIGHT, A.MAT_ISOTROPIC}
+
+
+@pytest.mark.parametrize("sid", E.LIGHT_EDGE_SCENES)
+def test_light_edge_vectors(sid):
+    """Light::sample / pdf on constructed records (the plane of a QuadLight, its edges and corners, the spot cone, the
+    positions of the delta lights, the cdf entries, the seam and the poles of the environment maps)."""
+    sc = G.scene(sid)
+    gold = G.records(E.light_edge_name(sid), A.LIGHTREC_DTYPE)
+    out = G.oracle_records(sc, "rto_lights", gold)
+    _assert_same(out, gold, E.LIGHT_FLOAT_FIELDS)
+    assert np.array_equal(out["is_delta"], gold["is_delta"])
+
+
+def test_shading_edge_fixtures_hit_what_they_aim_at():
+    """Every named case of every *-edge fixture holds at least one record for which the harness found the case's condition
+    true (with the reference's own expressions), and the reference's outputs show the branches taken."""
+    for name in E.edge_files():
+        cases = G.MANIFEST["files"][name]["info"]["cases"]
+        assert len(cases) >= 1
+        for case, count in cases.items():
+            assert count >= 1, (name, case)
+    sc = G.scene(E.EDGE_SCENE)
+    gold = G.records(E.material_edge_name(E.EDGE_SCENE), A.MAT_DTYPE)
+    types = E.material_types(sc, gold)
+    straddle = E.dielectric_straddle(sc, gold, scatter=False)
+    assert straddle.sum() >= 32 and set(gold["is_transmission"][straddle].tolist()) == {0, 1}
+    lam = types == A.MAT_LAMBERTIAN
+    assert (E.bits(gold["s_wi"][lam]) == E.bits(gold["n"][lam])).all(axis=1).any()  # near_zero fired: wi = unit(n) = n
+    assert ((gold["pdf"] == 0) & np.signbit(gold["pdf"])).any()  # cosine = -0.0 passes `cosine < 0`
+    assert np.isnan(gold["eval"]).any() and np.isnan(gold["pdf"]).any()
+    sgold = G.records("scatter_edge_scene1014.bin", A.MAT_DTYPE)
+    sstraddle = E.dielectric_straddle(sc, sgold, scatter=True)
+    assert sstraddle.sum() >= 32
+    lights = {sid: (G.scene(sid), G.records(E.light_edge_name(sid), A.LIGHTREC_DTYPE)) for sid in E.LIGHT_EDGE_SCENES}
+    assert any(np.isnan(g["wi"]).any() for _, g in lights.values())
+    assert any(np.isnan(g["pdf_dir"]).any() for _, g in lights.values())
+    sc21, g21 = lights[21]
+    edge = E.quad_alpha_beta_edge(sc21, g21)
+    assert edge.sum() >= 8 and (g21["pdf_dir"][edge] == 0).any() and (g21["pdf_dir"][edge] > 0).any()
+    sc18, g18 = lights[18]
+    cone = E.spot_straddle(sc18, g18)
+    li = g18["Li"][cone].sum(axis=1)
+    assert cone.sum() >= 16 and (li == 0).any() and (li > 0).any()
+    assert np.isinf(lights[15][1]["Li"]).any()  # a point light at its own position
+
+
+def test_shading_edge_fixtures_are_small_data_files():
+    names = E.edge_files() + list(E.SCATTER_FILES) + ["scene1014.rtrs"] + E.POW5_FILES
+    for name in names:
+        info = G.MANIFEST["files"][name]
+        assert info["bytes"] == G.os.path.getsize(G.os.path.join(G.GOLD, name))
+        assert info["bytes"] <= 160 * 1024 and info["argv"] and len(info["sha256"]) == 64
+
+
+def test_pow5_host_is_within_one_ulp_of_glibc_pow():
+    """rt_device.h: pow5 (x^5 in double-double arithmetic) against glibc's pow(x, 5.0) as the reference's harness computed it
+    on 65 536 values: never more than one ulp apart, and the number of values that differ at all is the count
+    oracle/gen_golden.py measured and wrote into the manifest -- fixed arithmetic, so a count and not a bound."""
+    xy, committed = E.pow5_pairs()
+    assert len(xy) == 65536 and (xy[:, 0] == 0).any() and (xy[:, 0] == 1).any() and (xy[:, 0] == 2.0 ** -215).any()
+    got = G.rtr.native.pow5_host(xy[:, 0])
+    want = np.ascontiguousarray(xy[:, 1])
+    assert np.all(np.isfinite(got)) and np.all(np.isfinite(want)) and np.all(got >= 0) and np.all(want >= 0)
+    d = got.view(np.int64) - want.view(np.int64)  # same sign, finite: the distance in ulps
+    print("pow5: %d of %d differ, largest distance %d ulp" % ((d != 0).sum(), len(d), np.abs(d).max()))
+    assert np.abs(d).max() <= 1
+    assert int((d != 0).sum()) == committed
