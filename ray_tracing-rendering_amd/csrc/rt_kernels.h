@@ -683,7 +683,9 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
  *
  * State: the pixel (16 bits each) and the job's s_end share PK_PIXEL (queue_pack), read at a sample's end, where the
  * camera ray needs the pixel anyway; the lane's cell lives in its traversal-stack word of LDS, which a flat scan never
- * touches (-1: no job); the wave's block and its cursor are wave-uniform.  Nothing new is live across the pair cast.
+ * touches (-1: no job); the wave's block, its cursor and its sample count are wave-uniform and live in an LDS slot of the
+ * wave (QueueSlot), and the job switch reads the launch's arguments where it needs them (queue_args).  Nothing of the
+ * queue is live across the pair cast.
  *
  * rtr_cancel(): the wave polls as k_mega does.  A wave that takes the cancel drops its jobs -- no lane of it stores or
  * counts again, so their cells stay incomplete and their tiles untouched -- and adds 1 to stats[7]: here that word
@@ -694,12 +696,64 @@ struct QueueWave {
     unsigned long long samples; /* samples of the jobs the wave's lanes have taken (wave-uniform: a lane has no register
                                    to count its own in); a cancel takes back what its dropped jobs had left */
 };
+/* Nothing of the queue is live across the pair cast, where every scalar register that is held is one that the scans
+ * spill (a spilled scalar is a v_writelane and every reload a v_readlane: vector instructions of a kernel the vector
+ * pipe binds).  The wave's QueueWave lives in LDS, one slot per wave of the workgroup, and is read and written only by
+ * the job switch and the cancel path.  Every lane that is there stores the same value and a lane reads after its own
+ * store (a lane that has left the loop never comes back), so no lane depends on another's store; the accesses are
+ * volatile so that none of them is kept in a register across an iteration. */
+__shared__ int rt_queue_waves[(RTR_BLOCK / 64) * 4]; /* [wave]: block, next, samples lo, samples hi (k_mega_queue only) */
+struct QueueSlot {
+    /* (through an LDS pointer: a volatile access through a generic one stays a flat access with a 64-bit address) */
+    RT_DEV static volatile __attribute__((address_space(3))) int& w(int k) {
+        return ((volatile __attribute__((address_space(3))) int*)rt_queue_waves)[(threadIdx.x >> 6) * 4 + k];
+    }
+    RT_DEV static int uni(int v) { return __builtin_amdgcn_readfirstlane(v); } /* every lane read the same word */
+    RT_DEV static QueueWave get() {
+        QueueWave q;
+        q.block = uni(w(0)), q.next = uni(w(1));
+        q.samples = get_samples();
+        return q;
+    }
+    RT_DEV static unsigned long long get_samples() {
+        return (unsigned long long)(uint32_t)uni(w(2)) | ((unsigned long long)(uint32_t)uni(w(3)) << 32);
+    }
+    RT_DEV static void set_samples(unsigned long long n) { w(2) = (int)(uint32_t)n, w(3) = (int)(uint32_t)(n >> 32); }
+    RT_DEV static void set(const QueueWave& q) {
+        w(0) = q.block, w(1) = q.next;
+        set_samples(q.samples);
+    }
+};
+/* The launch's arguments for the same two places, read from the kernel-argument segment where they are used: the
+ * arguments a kernel names are loaded at its entry and would be held, or spilled, through every cast.  The layout is
+ * k_mega_queue's parameter list, each argument at its natural alignment; the pointer passes through an empty asm so
+ * that the loads stay behind it. */
+struct QueueArgs {
+    const DScene* scp;
+    RenderK P;
+    int stack_words;
+    uint32_t* q_counter;
+    int n_blocks;
+};
+RT_DEV QueueArgs queue_args() {
+    unsigned long long p = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ld_const(reinterpret_cast<const QueueArgs*>(p), 0);
+}
+/* P for the camera sample inside the loop: W and H behind an empty asm, so that (W - 1) and (H - 1) are converted where a
+ * sample begins (two instructions) and not carried as doubles through every cast, where the lean kernel spills them */
+RT_DEV RenderK queue_image_size(const RenderK& P) {
+    RenderK B = P;
+    asm volatile("" : "+s"(B.W), "+s"(B.H));
+    return B;
+}
 /* Lanes with `need` take consecutive jobs, by their rank among those lanes, until each has a job with samples or the
  * queue has run out; the wave-uniform loop fetches a block whenever the current one has none left.  true: the lane has a
  * job (PK_PIXEL and *my_cell are set, `s` is its first sample); a lane in need that gets none has *my_cell = -1. */
-RT_DEV bool queue_take(const RenderK& P, uint32_t* __restrict__ q_counter, const int n_blocks, QueueWave& qw, bool need,
+RT_DEV bool queue_take(const RenderK& P, uint32_t* __restrict__ q_counter, const int n_blocks, const QueueSlot slot, bool need,
                        const Park& pk, int* my_cell, int& s) {
     bool got = false;
+    QueueWave qw = slot.get();
     unsigned long long m = __ballot(need);
     while (m) { /* wave-uniform */
         if (qw.block >= 0 && qw.next == RT_QUEUE_JOBS) {
@@ -739,19 +793,21 @@ RT_DEV bool queue_take(const RenderK& P, uint32_t* __restrict__ q_counter, const
         qw.next = taken < RT_QUEUE_JOBS ? taken : RT_QUEUE_JOBS;
         m = __ballot(need);
     }
+    slot.set(qw);
     return got;
 }
 
 template <int INTEG, int TRAV, int MS>
 __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
-    k_mega_queue(const DScene* __restrict__ scp, const RenderK P, const int stack_words, uint32_t* __restrict__ q_counter,
-                 const int n_blocks) {
+    k_mega_queue(const DScene* __restrict__ scp, const RenderK P, const int stack_words, uint32_t* __restrict__ /* q_counter */,
+                 const int /* n_blocks */) { /* (the queue's own arguments: queue_args(), where they are used) */
     static_assert(mega_pairable(INTEG, TRAV), "no pair-cast variant of this kernel");
     extern __shared__ int lds_stack[];
     const DScene& sc = *scp;
     const Stack st{lds_stack + threadIdx.x};
     const Park pk{reinterpret_cast<double*>(lds_stack + stack_words * RTR_BLOCK) + threadIdx.x};
     int* const my_cell = lds_stack + threadIdx.x; /* the lane's cell, in its stack word */
+    const QueueSlot slot; /* the wave's QueueWave, in LDS */
 #ifdef RTR_REGION_PROFILE
     if (threadIdx.x < 4 * 2 * RT_PROF_REGIONS + 8) rt_prof_lds[threadIdx.x] = 0;
     if (threadIdx.x + 256 < 4 * 2 * RT_PROF_REGIONS + 8) rt_prof_lds[threadIdx.x + 256] = 0;
@@ -763,12 +819,19 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     PathState ps;
     uint32_t rng = 1;
     int s = 0;
-    QueueWave qw{0, RT_QUEUE_JOBS, 0ull};
+    slot.set(QueueWave{0, RT_QUEUE_JOBS, 0ull});
     pk.set3(PK_ACC, mk(0.0, 0.0, 0.0));
     pk.set2(PK_NCAST, 0u, 0u);
     pk.set3(PK_L, mk(0.0, 0.0, 0.0));
+    /* ray B's request is always in PK_SWI / PK_STMAX, dead (t_max = 0: no record accepts it) or parked by the shading */
+    pk.set3(PK_SWI, mk(1.0, 1.0, 1.0));
+    pk.set(PK_STMAX, 0.0);
     *my_cell = -1;
-    bool done = !queue_take(P, q_counter, n_blocks, qw, true, pk, my_cell, s);
+    bool done;
+    {
+        const QueueArgs Q = queue_args();
+        done = !queue_take(Q.P, Q.q_counter, Q.n_blocks, slot, true, pk, my_cell, s);
+    }
     if (!done) {
         uint32_t lo, hi;
         int i, j, s_end;
@@ -788,26 +851,29 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         RTR_CLK(other);
         RT_REGION(RG_OTHER);
         const bool cast_a = !done;
-        Real a_tmax = RT_INF, b_tmax = 0.0;
+        Real a_tmax = RT_INF;
         int a_ref, a_inst, b_ref;
-        V3 swi = mk(1.0, 1.0, 1.0);
         RT_REGION(RG_COUNT);
-        {
+        { /* (two ds_add_u32 with a 0 / 1 operand in its place save four instructions and no time: profiles/r17_loopstate.txt) */
             uint32_t n_closest, n_shadow;
             pk.get2(PK_NCAST, n_closest, n_shadow);
             pk.set2(PK_NCAST, n_closest + (cast_a ? 1u : 0u), n_shadow + (pending ? 1u : 0u));
         }
         RT_REGION(RG_OTHER);
+        /* the dummy A of a lane that waits for its job switch is installed here and not where `done` becomes true: held
+         * from there, its seven words would have to survive the other lanes' shading, which has no registers for them */
         if (!cast_a) {
             ps.ro = mk(0.0, 0.0, 0.0), ps.rd = mk(1.0, 1.0, 1.0), ps.tm = 0.0;
             a_tmax = 0.0;
         }
-        if (pending) {
-            swi = pk.get3(PK_SWI);
-            b_tmax = pk.get(PK_STMAX);
-        } else {
-            so = mk(0.0, 0.0, 0.0);
-        }
+        /* B is what the parked words hold, read by every lane alike.  A dead request keeps the direction of the lane's
+         * last one, and `so` its origin: with t_max = 0 no record of the fast or the plain scans accepts it (t_min is
+         * 0.001), and a b_ref it did set would not count, because `lit` asks for `pending`.  A stale direction or origin
+         * that failed rcp_safe or the origin verdict when it was cast fails it again, until the lane parks its next
+         * request, and sends the wave to the plain scans of that frame, which return what the pair scans return: it
+         * costs that frame's time, never a hit. */
+        const V3 swi = pk.get3(PK_SWI);
+        Real b_tmax = pk.get(PK_STMAX);
         trace_pair(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
         RTR_CLK(closest);
         RT_REGION(RG_POLL);
@@ -825,6 +891,12 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             pk.set3(PK_L, L);
         }
         pending = false;
+        { /* the request is cast: the resident one is dead until the shading parks the next (the zero is made here: hoisted
+           * out of the loop it is one more pair of registers that the lean kernel spills) */
+            Real dead = 0.0;
+            asm volatile("" : "+v"(dead));
+            pk.set(PK_STMAX, dead);
+        }
         RTR_CLK(shadow);
         bool begin = false; /* the lane starts sample s at the end of this iteration */
         if (cast_a) {
@@ -870,19 +942,20 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         const bool job_end = !cast_a && *my_cell >= 0;
         if (__ballot(job_end)) { /* wave-uniform */
             RT_REGION(RG_EXCHANGE);
+            const QueueArgs Q = queue_args();
             if (job_end) {
                 uint32_t lo, hi;
                 pk.get2(PK_PIXEL, lo, hi);
                 const V3 acc = pk.get3(PK_ACC);
                 const int cell = *my_cell;
-                double* out = P.partial + (size_t)cell * 3 * RTR_BLOCK + ((lo >> 12) & 0xf0u) + (lo & 0xfu); /* tile_pixel's tid */
+                double* out = Q.P.partial + (size_t)cell * 3 * RTR_BLOCK + ((lo >> 12) & 0xf0u) + (lo & 0xfu); /* tile_pixel's tid */
                 out[0] = acc.x;
                 out[RTR_BLOCK] = acc.y;
                 out[2 * RTR_BLOCK] = acc.z;
-                atomicAdd(&P.done[cell], 1);
+                atomicAdd(&Q.P.done[cell], 1);
                 pk.set3(PK_ACC, mk(0.0, 0.0, 0.0));
             }
-            if (queue_take(P, q_counter, n_blocks, qw, job_end, pk, my_cell, s)) done = false, begin = true;
+            if (queue_take(Q.P, Q.q_counter, Q.n_blocks, slot, job_end, pk, my_cell, s)) done = false, begin = true;
         }
         if (begin) {
             uint32_t lo, hi;
@@ -892,7 +965,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             done = s >= s_end;
             if (!done) {
                 RT_REGION(RG_BEGIN);
-                camera_sample(sc, P, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
+                camera_sample(sc, queue_image_size(P), i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
                 ps.depth = 0, ps.specular_bounce = false;
                 pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
                 pk.set(PK_PDF, 0.0);
@@ -901,15 +974,17 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         RT_REGION(RG_POLL);
         if (__any(cancel_poll_take(P, cancel_word))) { /* wave-uniform: every lane polled the same word */
             const unsigned long long here = __ballot(1);
-            if ((int)__lane_id() == __builtin_ctzll(here)) atomicAdd(&P.stats[7], 1ull);
+            if ((int)__lane_id() == __builtin_ctzll(here)) atomicAdd(&queue_args().P.stats[7], 1ull);
             int left = 0; /* samples of the lane's job that have not ended */
             if (*my_cell >= 0) {
                 uint32_t lo, hi;
                 pk.get2(PK_PIXEL, lo, hi);
                 left = (int)hi - s;
             }
+            unsigned long long dropped = 0;
             for (unsigned long long m = __ballot(left > 0); m; m &= m - 1) /* wave-uniform */
-                qw.samples -= (unsigned long long)__builtin_amdgcn_readlane(left, __builtin_ctzll(m));
+                dropped += (unsigned long long)__builtin_amdgcn_readlane(left, __builtin_ctzll(m));
+            slot.set_samples(slot.get_samples() - dropped);
             *my_cell = -1; /* the wave's jobs are dropped (an ended sample still settles: the loop's condition) */
             done = true;
         }
@@ -926,8 +1001,9 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     }
 #endif
     unsigned long long b = wave_sum(cnt.closest), c = wave_sum(cnt.shadow);
+    const unsigned long long taken = slot.get_samples();
     if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&P.stats[0], qw.samples);
+        atomicAdd(&P.stats[0], taken);
         atomicAdd(&P.stats[1], b);
         atomicAdd(&P.stats[2], c);
     }
