@@ -182,6 +182,20 @@ int rtr_test_issue_rates(rtr_context* ctx, double* cycles_per_inst, int n);
  * *tested: the pairs the kernel compared, 2^32 when every pair drawn was in that range. */
 int rtr_test_shared_division(rtr_context* ctx, uint64_t* mismatches, uint64_t* tested);
 
+/* Shading and the sample start divide by numbers that are the same for a whole scene or launch -- an edge of a quad light,
+ * pi, the image size -- through a reciprocal made once (rt_device.h: udiv).  rtr_test_udiv runs udiv beside the
+ * compiler's n / d for every one of the n numerators against every one of the m divisors, the divisor's record made on
+ * the device as the kernels make theirs.  *mismatches
+ * (quotients that differ in any bit, a NaN equal to a NaN) must be 0; *tested = n * m.  Needs no scene. */
+int rtr_test_udiv(rtr_context* ctx, const double* numerators, int64_t n, const double* divisors, int32_t m,
+                  uint64_t* mismatches, uint64_t* tested);
+/* The uploaded scene's table of shading constants (rt_device.h: SceneConsts, made on the device by rtr_upload_scene) as
+ * 8-byte words -- 1 / n_lights, 0, pi, rcp_refined(pi); then per light len2(U), its refined reciprocal, len2(V), its refined
+ * reciprocal, the `safe` flag in the low half of a word -- into `table`, and a second evaluation of the same expressions
+ * by a kernel of the test library into `again`: 4 + 5 * n_lights words each (cap: the words each array holds; 0 only
+ * asks for *n_lights). */
+int rtr_test_scene_consts(rtr_context* ctx, uint64_t* table, uint64_t* again, int64_t cap, int32_t* n_lights);
+
 /* The temporal stage of rtr_accum_denoise_temporal alone, over HOST planes: the product's k_temporal_blend and
  * k_temporal_store, launched with the grids of a frame, on a width x height region at (x0, y0) of an image_width x
  * image_height image.  h_color, h_q, h_count and h_feat are the planes of rtr_denoise_host, h_hist_in the last frame's

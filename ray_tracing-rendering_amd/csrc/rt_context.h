@@ -24,11 +24,11 @@ struct DevBuf {
  * frees them as an array, so a new one needs its declaration here and its line in rtr_upload_scene, nothing else */
 struct SceneBufs {
     DevBuf nodes, kids, mats, tex, perlin, images, imgbytes, lights;
-    DevBuf finst, fxf, fref, fexit, fbvh, fsub, fscan, fguard, fstep, fvisit, fprim, fleaf, fmat, ffin, dscene;
+    DevBuf finst, fxf, fref, fexit, fbvh, fsub, fscan, fguard, fstep, fvisit, fprim, fleaf, fmat, ffin, sconsts, dscene;
     DevBuf* begin() { return &nodes; }
     DevBuf* end() { return begin() + sizeof(SceneBufs) / sizeof(DevBuf); }
 };
-static_assert(sizeof(SceneBufs) == 23 * sizeof(DevBuf), "SceneBufs holds DevBufs only");
+static_assert(sizeof(SceneBufs) == 24 * sizeof(DevBuf), "SceneBufs holds DevBufs only");
 
 struct rtr_context {
     int device = 0;

@@ -35,15 +35,17 @@ typedef double Real;
  * the region that was current, then makes `id` current.  Counters live in LDS per wave and are added to
  * RenderK::stats[RT_PROF_BASE ...] when the workgroup ends.  The markers cost about a tenth of the wave's time
  * themselves: read the table as proportions.  In product builds RT_REGION() expands to nothing. */
-#define RT_STATS_WORDS 80 /* u64 words of RenderK::stats: 8 of the product + 2 x 32 region words */
+#define RT_STATS_WORDS 80 /* u64 words of RenderK::stats: 8 of the product + 2 x 34 region words, 4 spare */
 #define RT_PROF_BASE 8
-#define RT_PROF_REGIONS 32
+#define RT_PROF_REGIONS 34
 enum { RG_OTHER = 0, RG_SETUP = 1, RG_RECTS = 2, RG_SPHERES = 3, RG_GENERIC = 4, RG_TREE = 5, RG_LEAVES = 6, RG_FINISH = 7,
        RG_SH_SETUP = 8, RG_SH_RECTS = 9, RG_SH_SPHERES = 10, RG_SH_GENERIC = 11, RG_SH_TREE = 12, RG_SH_LEAVES = 13,
        RG_MEDIA = 14, RG_MATPREP = 15, RG_SHADE_A = 16, RG_SHADE_B = 17, RG_MISS = 18, RG_REGEN = 19, RG_SHADE_RR = 20,
        RG_PARK = 21, RG_BARRIER = 22, RG_EXCHANGE = 23, RG_PAIR_SETUP = 24, RG_PAIR_RUNS = 25, RG_PAIR_SPHERES = 26,
        RG_POLL = 27, RG_BEGIN = 28, RG_SETTLE = 29, RG_COUNT = 30, RG_REJECT = 31, /* the sample boundary of the lockstep loops, split */
-       RG_N = 32 };
+       RG_EMIT_MIS = 32, /* shade_a_mis: the MIS weight of a BSDF-sampled ray that reached an emitter (compute_light_pdf) */
+       RG_CAMDIV = 33,   /* camera_sample: the two divisions by the image size */
+       RG_N = 34 };
 #ifdef RTR_REGION_PROFILE
 __shared__ unsigned long long rt_prof_lds[4 * 2 * RT_PROF_REGIONS + 4 * 2]; /* [wave][cycles | visits][region], then [wave][last, current] */
 RT_DEV void rt_region(int id) {
@@ -246,6 +248,35 @@ RT_DEV V3 raydiv_inv(const RayDiv& q, V3 d) {
     return mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
 }
 
+/* n / d for a divisor that is the same in every lane of every wave for a whole scene or launch (an edge of a light, pi,
+ * the image size): d, r = rcp_refined(d) and `safe` = rcp_safe(d) are made once -- the scene's by k_scene_consts at
+ * upload (SceneConsts), the image's in the kernel prologue -- so a division costs div_shared's three instructions and
+ * its guard instead of the compiler's twelve.  The numerator is a lane's own and may be anything: if any lane that is
+ * here holds one outside [2^-300, 2^200] (zero, denormals, inf and NaN included), the whole wave takes the plain
+ * division, so the sign of a zero quotient and every special value are the reference's, and the lanes in range get the
+ * same bits either way; BOUNDED says the caller knows the numerator to be finite and below 2^200.  The guard is a vote
+ * and not a per-lane select on purpose: written per lane, the compiler computes BOTH quotients in every lane and picks
+ * one, which costs more than the plain division alone.  `safe` is wave-uniform as well: an unsafe divisor (a light edge
+ * of length 0, a one-pixel image) is a scalar branch to n / d. */
+struct UDiv {
+    Real d, r;
+    bool safe;
+};
+RT_DEV UDiv udiv_make(Real d) {
+    UDiv u;
+    u.d = d, u.r = rcp_refined(d), u.safe = rcp_safe(d);
+    return u;
+}
+template <bool BOUNDED = false>
+RT_DEV Real udiv(Real n, const UDiv& u) {
+    const Real an = __builtin_fabs(n);
+    const bool in_range = (an >= 0x1p-300) & (BOUNDED || an <= 0x1p200);
+    if (!u.safe || !__all(in_range)) return n / u.d;
+    const Real q = n * u.r;
+    const Real e = __builtin_fma(-u.d, q, n);
+    return __builtin_fma(e, u.r, q);
+}
+
 /* ---- device scene ------------------------------------------------------------------------ */
 /* Scene arrays are immutable during a render.  Reading them through the constant address space
  * tells the compiler so: wave-uniform accesses (instance / reference / primitive loops of the
@@ -309,7 +340,54 @@ struct DScene {
     int32_t n_fvisit;        /* visits of the traversal machine's flattened program (rt_machine.h) */
     const struct FVisit* fvisit;
     const struct FFin* ffin; /* finish record per reference (see FFin); null: the scene has none, fast_finish's own loads */
+    const struct SceneConsts* consts; /* what shading divides by, made on the device at upload (see SceneConsts); never null */
 };
+
+/* Scene constants of the shading code: quotients and divisors that are the same for every lane of every wave as long as
+ * the scene is.  k_scene_consts (one workgroup, enqueued by rtr_upload_scene behind the copies) fills them with the very
+ * functions the render kernels would call -- 1.0 / n, len2, rcp_refined, rcp_safe -- so the bits are this device's by
+ * construction.  A SceneConsts is followed by one LightConsts per light; both are read through scalar loads where they
+ * are used and nowhere held. */
+struct LightConsts {
+    double u2, ru2; /* QuadLight: len2(U) and its refined reciprocal (light_pdf's alpha) */
+    double v2, rv2; /* len2(V) (beta) */
+    int32_t safe;   /* rcp_safe(u2) & rcp_safe(v2): 0 = light_pdf divides plainly (an edge of length 0, a non-finite one) */
+    int32_t pad;
+};
+struct SceneConsts {
+    double inv_n_lights; /* 1.0 / n_lights: light_select_pdf (mis_path_integrator.h:175,196) */
+    double pad;
+    double pi, rcp_pi;   /* RT_PI and rcp_refined(RT_PI), one 16-byte scalar load.  pi comes from here as well: as a literal
+                            the compiler keeps the high word of -pi in a scalar register across the whole loop, and in the
+                            job-queue kernel that register is a spilled one (two lane moves at every use) */
+};
+RT_HD size_t scene_consts_bytes(int n_lights) { return sizeof(SceneConsts) + (size_t)n_lights * sizeof(LightConsts); }
+RT_DEV void scene_consts_fill(const rtr_light* lights, int n_lights, SceneConsts* out, int k) {
+    if (k == 0) {
+        out->inv_n_lights = 1.0 / n_lights;
+        out->pad = 0.0;
+        out->pi = RT_PI;
+        out->rcp_pi = rcp_refined(RT_PI);
+    }
+    if (k < n_lights) {
+        LightConsts c;
+        c.u2 = len2(ld3(lights[k].f + 3)), c.v2 = len2(ld3(lights[k].f + 6));
+        c.ru2 = rcp_refined(c.u2), c.rv2 = rcp_refined(c.v2);
+        c.safe = rcp_safe(c.u2) & rcp_safe(c.v2);
+        c.pad = 0;
+        reinterpret_cast<LightConsts*>(out + 1)[k] = c;
+    }
+}
+RT_DEV Real scene_light_select_pdf(const DScene& sc) { return as_const(sc.consts)->inv_n_lights; }
+/* pi as udiv's divisor */
+RT_DEV UDiv scene_pi(const DScene& sc) {
+    UDiv u;
+    u.d = as_const(sc.consts)->pi, u.r = as_const(sc.consts)->rcp_pi, u.safe = true;
+    return u;
+}
+RT_DEV LightConsts scene_light_consts(const DScene& sc, int k) {
+    return ld_const(reinterpret_cast<const LightConsts*>(sc.consts + 1), k);
+}
 
 /*
  * Compiled scene.  Where no constant_medium exists, a ray cast's result does not depend on
@@ -2268,12 +2346,13 @@ struct MatCtx {
     V3 N;                /* PBR: shading normal (material.h:247-261) */
     Real rough, metal;   /* PBR: roughness clamped to [0.01, 1] (:264,327,368), metallic */
 };
-__device__ __forceinline__ Real pbr_pdf(const MatCtx& c, V3 wo, V3 wi) {
+/* pi: scene_pi, for the divisions by pi */
+__device__ __forceinline__ Real pbr_pdf(const MatCtx& c, V3 wo, V3 wi, const UDiv& pi) {
     /* material.h:305-340 */
     const V3 N = c.N;
     if (dot(N, wi) <= 0) return 0;
     const Real rough = c.rough;
-    Real pdf_diff = dot(N, wi) / RT_PI;
+    Real pdf_diff = udiv(dot(N, wi), pi);
     V3 H = unit(add(wo, wi));
     Real D = distribution_ggx(N, H, rough);
     Real NdotH = maxd(dot(N, H), 0.0);
@@ -2307,7 +2386,7 @@ __device__ __forceinline__ V3 pbr_eval(const MatCtx& c, V3 wo, V3 wi) {
 /* PBRMaterial::eval and ::pdf of the same pair of directions (the light sample of sample_lights_mis, the BSDF sample of
  * PBRMaterial::sample: material.h:296-298, mis_path_integrator.h:215-224): the half vector, D, N.H and H.V are the same
  * expressions in both (material.h:317-331, :356-373) -- computed once here, each result as above */
-__device__ __forceinline__ void pbr_eval_pdf(const MatCtx& c, V3 wo, V3 wi, V3& f, Real& pdf) {
+__device__ __forceinline__ void pbr_eval_pdf(const MatCtx& c, V3 wo, V3 wi, V3& f, Real& pdf, const UDiv& pi) {
     const V3 N = c.N;
     const Real NdotL = dot(N, wi);
     f = mk(0, 0, 0), pdf = 0;
@@ -2317,7 +2396,7 @@ __device__ __forceinline__ void pbr_eval_pdf(const MatCtx& c, V3 wo, V3 wi, V3& 
     const Real D = distribution_ggx(N, H, rough);
     const Real NdotH = maxd(dot(N, H), 0.0);
     const Real HdotV = maxd(dot(H, wo), 0.0);
-    const Real pdf_diff = NdotL / RT_PI;
+    const Real pdf_diff = udiv(NdotL, pi);
     const Real pdf_spec = (D * NdotH) / (4.0 * HdotV + 0.0001);
     pdf = 0.5 * pdf_diff + 0.5 * pdf_spec;
     const Real NdotV = dot(N, wo);
@@ -2380,7 +2459,7 @@ RT_DEV V3 mat_emitted_legacy(const MatCtx& c) {
 }
 
 /* PBRMaterial::sample (material.h:245-303) */
-__device__ __forceinline__ bool pbr_sample(const MatCtx& c, V3 wo, BSDFSample& s, uint32_t& rng) {
+__device__ __forceinline__ bool pbr_sample(const MatCtx& c, V3 wo, BSDFSample& s, uint32_t& rng, const UDiv& pi) {
     const V3 N = c.N;
     const Real rough = c.rough;
     /* Both branches of material.h:263-302 build the same basis around N, draw r1 then r2 and take cos / sin of
@@ -2411,19 +2490,19 @@ __device__ __forceinline__ bool pbr_sample(const MatCtx& c, V3 wo, BSDFSample& s
         s.wi = unit(L);
     }
     s.is_specular = false;
-    pbr_eval_pdf(c, wo, s.wi, s.f, s.pdf);
+    pbr_eval_pdf(c, wo, s.wi, s.f, s.pdf, pi);
     if (s.pdf < 1e-6) return false;
     return true;
 }
 
 template <int MS = RT_MS_FULL>
-__device__ __forceinline__ bool mat_sample(const MatCtx& c, const Hit& rec, V3 wo, BSDFSample& s, uint32_t& rng) {
+__device__ __forceinline__ bool mat_sample(const MatCtx& c, const Hit& rec, V3 wo, BSDFSample& s, uint32_t& rng, const UDiv& pi) {
     const int type = c.type;
     if (type == RTR_MAT_LAMBERTIAN) { /* material.h:79-90 */
         V3 scatter_direction = add(rec.n, random_unit_vector(rng));
         if (near_zero(scatter_direction)) scatter_direction = rec.n;
         s.wi = unit(scatter_direction);
-        s.pdf = dot(rec.n, s.wi) / RT_PI;
+        s.pdf = udiv(dot(rec.n, s.wi), pi);
         s.f = divs(c.albedo, RT_PI);
         s.is_specular = false;
         return true;
@@ -2456,7 +2535,7 @@ __device__ __forceinline__ bool mat_sample(const MatCtx& c, const Hit& rec, V3 w
         }
         return true;
     }
-    if (type == RTR_MAT_PBR) return pbr_sample(c, wo, s, rng);
+    if (type == RTR_MAT_PBR) return pbr_sample(c, wo, s, rng, pi);
     return false; /* diffuse_light (material.h:213-216), isotropic (base class, :42-45) */
 }
 
@@ -2469,23 +2548,23 @@ RT_DEV V3 mat_eval(const MatCtx& c, V3 wo, V3 wi) {
 }
 /* material::pdf: base 0 (material.h:54-57), lambertian (:92-96), PBR (:305) */
 template <int MS = RT_MS_FULL>
-RT_DEV Real mat_pdf(const MatCtx& c, const Hit& rec, V3 wo, V3 wi) {
+RT_DEV Real mat_pdf(const MatCtx& c, const Hit& rec, V3 wo, V3 wi, const UDiv& pi) {
     if (c.type == RTR_MAT_LAMBERTIAN) {
         Real cosine = dot(rec.n, unit(wi));
-        return cosine < 0 ? 0 : cosine / RT_PI;
+        return cosine < 0 ? 0 : udiv(cosine, pi);
     }
-    if (MS != RT_MS_LEAN && c.type == RTR_MAT_PBR) return pbr_pdf(c, wo, wi);
+    if (MS != RT_MS_LEAN && c.type == RTR_MAT_PBR) return pbr_pdf(c, wo, wi, pi);
     return 0.0;
 }
 /* material::eval and material::pdf of one pair of directions */
 template <int MS = RT_MS_FULL>
-RT_DEV void mat_eval_pdf(const MatCtx& c, const Hit& rec, V3 wo, V3 wi, V3& f, Real& pdf) {
+RT_DEV void mat_eval_pdf(const MatCtx& c, const Hit& rec, V3 wo, V3 wi, V3& f, Real& pdf, const UDiv& pi) {
     if (MS != RT_MS_LEAN && c.type == RTR_MAT_PBR) {
-        pbr_eval_pdf(c, wo, wi, f, pdf);
+        pbr_eval_pdf(c, wo, wi, f, pdf, pi);
         return;
     }
     f = mat_eval<MS>(c, wo, wi);
-    pdf = mat_pdf<MS>(c, rec, wo, wi);
+    pdf = mat_pdf<MS>(c, rec, wo, wi, pi);
 }
 /* legacy material::scatter(r_in, rec, attenuation, scattered): new ray = (rec.p, dir, r_in.time) */
 template <int MS = RT_MS_FULL>
@@ -2723,7 +2802,7 @@ RT_DEV LightSample light_sample(const rtr_light& l, V3 p, Real ux, Real uy, uint
     return s;
 }
 template <int MS = RT_MS_FULL>
-RT_DEV Real light_pdf(const rtr_light& l, V3 origin, V3 direction, const uint8_t* blob) {
+RT_DEV Real light_pdf(const rtr_light& l, const LightConsts& lc, V3 origin, V3 direction, const uint8_t* blob) {
     if (MS == RT_MS_FULL) {
         if (l.type == RTR_LIGHT_ENV_UNIFORM) return 1.0 / (4.0 * RT_PI); /* environmental_light.h:293-294 */
         if (l.type == RTR_LIGHT_ENV_MAP) return env_pdf(env_map(l, blob), direction);
@@ -2735,8 +2814,11 @@ RT_DEV Real light_pdf(const rtr_light& l, V3 origin, V3 direction, const uint8_t
     Real t = dot(sub(Q, origin), normal) / denom;
     if (t < 0.001 || t > RT_INF) return 0;
     V3 planar = sub(add(origin, scl(t, direction)), Q);
-    Real alpha = dot(planar, U) / len2(U);
-    Real beta = dot(planar, Vv) / len2(Vv);
+    UDiv du, dv; /* len2(U), len2(Vv): the scene's (LightConsts) */
+    du.d = lc.u2, du.r = lc.ru2, dv.d = lc.v2, dv.r = lc.rv2;
+    du.safe = dv.safe = lc.safe != 0;
+    Real alpha = udiv(dot(planar, U), du);
+    Real beta = udiv(dot(planar, Vv), dv);
     if (alpha < 0 || alpha > 1 || beta < 0 || beta > 1) return 0;
     Real dist_sq = t * t * len2(direction);
     Real cos_theta = -denom / len(direction);
@@ -2772,10 +2854,10 @@ RT_DEV Real power_heuristic(Real pdf_a, Real pdf_b) { /* :165-170 */
 template <int MS = RT_MS_FULL>
 RT_DEV Real compute_light_pdf(const DScene& sc, V3 o, V3 d) { /* :173-188 */
     Real total_pdf = 0.0;
-    Real light_select_pdf = 1.0 / sc.n_lights;
+    Real light_select_pdf = scene_light_select_pdf(sc);
     for (int k = 0; k < sc.n_lights; ++k) {
         const rtr_light l = ld_const(sc.lights, k); /* wave-uniform index: scalar loads */
-        total_pdf += light_pdf<MS>(l, o, d, sc.image_bytes) * light_select_pdf;
+        total_pdf += light_pdf<MS>(l, scene_light_consts(sc, k), o, d, sc.image_bytes) * light_select_pdf;
     }
     return total_pdf;
 }
@@ -2880,7 +2962,9 @@ RT_DEV void shade_a_mis(const DScene& sc, PathState& ps, const Hit& rec, const M
             if (ps.depth == 0 || ps.specular_bounce) {
                 L_emit = mul(ps.thr, emitted);
             } else if (have_lights) {
+                RT_REGION(RG_EMIT_MIS);
                 Real mis_weight = power_heuristic(ps.prev_bsdf_pdf, compute_light_pdf<MS>(sc, ps.ro, ps.rd));
+                RT_REGION(RG_SHADE_A);
                 L_emit = scl(mis_weight, mul(ps.thr, emitted));
             } else {
                 L_emit = mul(ps.thr, emitted);
@@ -2891,7 +2975,7 @@ RT_DEV void shade_a_mis(const DScene& sc, PathState& ps, const Hit& rec, const M
     /* material::is_specular() is never overridden, so NEE runs at every hit */
     if ((PART & 2) && have_lights) {
         const int light_idx = rng_int(rng, 0, sc.n_lights - 1);
-        const Real light_select_pdf = 1.0 / sc.n_lights;
+        const Real light_select_pdf = scene_light_select_pdf(sc);
         const Real uy = rng_next(rng); /* vec2 u(r(), r()): u.y takes the first draw (g++ order) */
         const Real ux = rng_next(rng);
         LightSample ls;
@@ -2906,7 +2990,7 @@ RT_DEV void shade_a_mis(const DScene& sc, PathState& ps, const Hit& rec, const M
             V3 f;
             Real bsdf_pdf = 0;
             if (INTEG == RTR_INTEGRATOR_MIS && !ls.is_delta)
-                mat_eval_pdf<MS>(mc, rec, wo, ls.wi, f, bsdf_pdf); /* mis_path_integrator.h:215, :223 */
+                mat_eval_pdf<MS>(mc, rec, wo, ls.wi, f, bsdf_pdf, scene_pi(sc)); /* mis_path_integrator.h:215, :223 */
             else
                 f = mat_eval<MS>(mc, wo, ls.wi);
             Real cos_theta = __builtin_fabs(dot(ls.wi, rec.n));
@@ -2937,7 +3021,7 @@ RT_DEV bool shade_b_mis(const DScene& sc, PathState& ps, const Hit& rec, const M
                         int rr_start) {
     RT_REGION(RG_SHADE_B);
     BSDFSample bs;
-    if (!mat_sample<MS>(mc, rec, wo, bs, rng)) { /* :106-118 */
+    if (!mat_sample<MS>(mc, rec, wo, bs, rng, scene_pi(sc))) { /* :106-118 */
         if (INTEG != RTR_INTEGRATOR_MIS) return false; /* pbr_path_integrator.h:44-46, direct_light_integrator.h:67-69 */
         V3 attenuation, ndir;
         if (!mat_scatter<MS>(mc, ps.rd, rec, attenuation, ndir, rng)) return false;

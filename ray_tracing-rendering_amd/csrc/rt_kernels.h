@@ -724,6 +724,22 @@ struct QueueSlot {
         set_samples(q.samples);
     }
 };
+/* The image's divisors for camera_sample (CameraDiv), made in the prologue and kept the same way: (W - 1), its refined
+ * reciprocal, (H - 1), its refined reciprocal.  Every lane of the workgroup stores the same four words before its first
+ * sample and reads them back where a sample begins, so they cost no register across the cast and no division there. */
+__shared__ double rt_queue_camera[4];
+struct QueueCamera {
+    RT_DEV static volatile __attribute__((address_space(3))) double& w(int k) {
+        return ((volatile __attribute__((address_space(3))) double*)rt_queue_camera)[k];
+    }
+    RT_DEV static void set(const CameraDiv& c) { w(0) = c.w.d, w(1) = c.w.r, w(2) = c.h.d, w(3) = c.h.r; }
+    RT_DEV static CameraDiv get(int W, int H) {
+        CameraDiv c;
+        c.w.d = w(0), c.w.r = w(1), c.h.d = w(2), c.h.r = w(3);
+        c.w.safe = c.h.safe = (W != 1) & (H != 1);
+        return c;
+    }
+};
 /* The launch's arguments for the same two places, read from the kernel-argument segment where they are used: the
  * arguments a kernel names are loaded at its entry and would be held, or spilled, through every cast.  The layout is
  * k_mega_queue's parameter list, each argument at its natural alignment; the pointer passes through an empty asm so
@@ -827,6 +843,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     pk.set3(PK_SWI, mk(1.0, 1.0, 1.0));
     pk.set(PK_STMAX, 0.0);
     *my_cell = -1;
+    QueueCamera::set(camera_div_make(P.W, P.H));
     bool done;
     {
         const QueueArgs Q = queue_args();
@@ -837,7 +854,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         int i, j, s_end;
         pk.get2(PK_PIXEL, lo, hi);
         queue_unpack(lo, hi, i, j, s_end);
-        camera_sample(sc, P, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
+        camera_sample(sc, QueueCamera::get(P.W, P.H), P.seed, P.W, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
         ps.depth = 0, ps.specular_bounce = false;
         pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
         pk.set(PK_PDF, 0.0);
@@ -965,7 +982,8 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             done = s >= s_end;
             if (!done) {
                 RT_REGION(RG_BEGIN);
-                camera_sample(sc, queue_image_size(P), i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
+                const RenderK B = queue_image_size(P);
+                camera_sample(sc, QueueCamera::get(B.W, B.H), B.seed, B.W, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
                 ps.depth = 0, ps.specular_bounce = false;
                 pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
                 pk.set(PK_PDF, 0.0);

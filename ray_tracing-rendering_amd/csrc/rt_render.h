@@ -59,8 +59,36 @@ RT_DEV void tile_pixel(const RenderK& P, int slot, int tid, int& i, int& j, bool
  * (renderer.h:73-75); rng goes on from its state after get_ray */
 RT_DEV void camera_sample(const DScene& sc, const RenderK& P, int i, int j, int s, uint32_t& rng, V3& ro, V3& rd, Real& tm) {
     rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
+    const int region = RT_REGION_CURRENT();
+    (void)region;
+    RT_REGION(RG_CAMDIV);
     const Real u = (i + rng_next(rng)) / (P.W - 1);
     const Real v = (j + rng_next(rng)) / (P.H - 1);
+    RT_REGION(region);
+    camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+}
+/* The divisors of camera_sample belong to the launch: (double)(W - 1), (double)(H - 1) and their refined reciprocals are
+ * made once in a kernel's prologue (udiv).  The pixel is an int and the jitter below 1, so the numerators are bounded;
+ * i + r = 0 takes udiv's plain division.  `safe` is decided on the integers, in scalar registers: a (double)(W - 1) is
+ * within rcp_safe's range unless it is 0 (a one-pixel-wide image, which params_check refuses anyway). */
+struct CameraDiv {
+    UDiv w, h;
+};
+RT_DEV CameraDiv camera_div_make(int W, int H) {
+    CameraDiv c;
+    c.w = udiv_make((Real)(W - 1)), c.h = udiv_make((Real)(H - 1));
+    c.w.safe = c.h.safe = (W != 1) & (H != 1);
+    return c;
+}
+RT_DEV void camera_sample(const DScene& sc, const CameraDiv& cd, uint32_t seed, int W, int i, int j, int s, uint32_t& rng, V3& ro,
+                          V3& rd, Real& tm) {
+    rng = rtr_sample_seed_inline(seed, W, i, j, s);
+    const int region = RT_REGION_CURRENT();
+    (void)region;
+    RT_REGION(RG_CAMDIV);
+    const Real u = udiv<true>(i + rng_next(rng), cd.w);
+    const Real v = udiv<true>(j + rng_next(rng), cd.h);
+    RT_REGION(region);
     camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
 }
 

@@ -113,7 +113,8 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_materials(const DScene sc, r
     BSDFSample bs;
     bs.wi = mk(0, 0, 0), bs.f = mk(0, 0, 0), bs.pdf = 0, bs.is_specular = false, bs.is_transmission = false;
     const MatCtx mc = mat_prepare<MS>(sc, rec);
-    const bool ok = mat_sample<MS>(mc, rec, wo, bs, rng);
+    const UDiv pi = scene_pi(sc);
+    const bool ok = mat_sample<MS>(mc, rec, wo, bs, rng, pi);
     r.rng_out = rng;
     r.sample_ok = ok, r.is_specular = bs.is_specular;
     r.is_transmission = bs.is_transmission;
@@ -122,12 +123,12 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_materials(const DScene sc, r
     r.s_pdf = bs.pdf;
     const V3 e = mat_eval<MS>(mc, wo, wi);
     r.eval[0] = e.x, r.eval[1] = e.y, r.eval[2] = e.z;
-    r.pdf = mat_pdf<MS>(mc, rec, wo, wi);
+    r.pdf = mat_pdf<MS>(mc, rec, wo, wi, pi);
     const V3 em = mat_emitted(mc, rec);
     r.emitted[0] = em.x, r.emitted[1] = em.y, r.emitted[2] = em.z;
     V3 f2;
     Real pdf2;
-    mat_eval_pdf<MS>(mc, rec, wo, wi, f2, pdf2);
+    mat_eval_pdf<MS>(mc, rec, wo, wi, f2, pdf2, pi);
     r.pad = (same_bits(f2.x, e.x) && same_bits(f2.y, e.y) && same_bits(f2.z, e.z) ? 0 : 1) | (same_bits(pdf2, r.pdf) ? 0 : 2);
     recs[k] = r;
 }
@@ -168,8 +169,37 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_lights(const DScene sc, rtr_
     r.Li[0] = s.Li.x, r.Li[1] = s.Li.y, r.Li[2] = s.Li.z;
     r.wi[0] = s.wi.x, r.wi[1] = s.wi.y, r.wi[2] = s.wi.z;
     r.pdf = s.pdf, r.dist = s.dist, r.is_delta = s.is_delta, r.pad2 = 0;
-    r.pdf_dir = light_pdf<MS>(l, ld3(r.p), ld3(r.dir), sc.image_bytes);
+    r.pdf_dir = light_pdf<MS>(l, scene_light_consts(sc, r.light), ld3(r.p), ld3(r.dir), sc.image_bytes);
     recs[k] = r;
+}
+
+/* rtr_test_udiv: udiv() beside the compiler's n / d, every numerator against every divisor; the divisor's record is
+ * made as the kernels make theirs (udiv_make).  out[0] += quotients that differ in any bit (a NaN equals a NaN), out[1] += pairs compared */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_udiv(const double* __restrict__ num, long long n, const double* __restrict__ div,
+                                                         int m, unsigned long long* out) {
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    unsigned long long bad = 0, tested = 0;
+    if (k < n) {
+        const double x = num[k];
+        for (int j = 0; j < m; ++j) { /* wave-uniform divisor: `safe` is a scalar branch, as in the renders */
+            const double d = as_const(div)[j];
+            const UDiv u = udiv_make(d);
+            const double ref = x / d;
+            bad += !same_bits(udiv(x, u), ref);
+            if (__builtin_fabs(x) <= 0x1p200) bad += !same_bits(udiv<true>(x, u), ref);
+            ++tested;
+        }
+    }
+    bad = wave_sum(bad);
+    tested = wave_sum(tested);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, bad);
+    if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
+}
+
+/* rtr_test_scene_consts: a second evaluation of the scene table (scene_consts_fill) into the test buffer */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_scene_consts(const DScene sc, SceneConsts* out) {
+    for (int k = threadIdx.x; k < (sc.n_lights > 1 ? sc.n_lights : 1); k += RTR_BLOCK)
+        scene_consts_fill(sc.lights, sc.n_lights, out, k);
 }
 
 /* rtr_test_pow5: pow5 of rt_device.h, one value per lane */

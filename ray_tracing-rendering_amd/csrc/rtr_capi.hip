@@ -130,13 +130,14 @@ int finish_stats(rtr_context* c) {
                                           "sorted shading: tickets + exchange / queue: job switch", "pair cast: instance setup",
                                           "pair cast: rect runs", "pair cast: sphere runs", "sample end: cancel poll",
                                           "sample end: begin_sample (camera ray)", "sample end: settle into the pixel sum",
-                                          "cast counters", "random_in_unit_sphere rejection loop"};
+                                          "cast counters", "random_in_unit_sphere rejection loop",
+                                          "shade_a: emitter MIS weight (compute_light_pdf)", "camera_sample: image-size divisions"};
         double total = 0;
         for (int k = 0; k < RG_N; ++k) total += (double)h[RT_PROF_BASE + k];
         std::fprintf(stderr, "[region profile] %.4g wave cycles in all, %llu samples\n", total, h[0]);
         for (int k = 0; k < RG_N; ++k)
             if (h[RT_PROF_BASE + RT_PROF_REGIONS + k])
-                std::fprintf(stderr, "[region profile] %-36s %6.2f %%  %12llu visits  %8.1f cycles/visit\n", names[k],
+                std::fprintf(stderr, "[region profile] %-48s %6.2f %%  %12llu visits  %8.1f cycles/visit\n", names[k],
                              100.0 * (double)h[RT_PROF_BASE + k] / total, h[RT_PROF_BASE + RT_PROF_REGIONS + k],
                              (double)h[RT_PROF_BASE + k] / (double)h[RT_PROF_BASE + RT_PROF_REGIONS + k]);
     }
@@ -448,6 +449,12 @@ int rtr_set_stream(rtr_context* c, void* hip_stream) {
     return RTR_OK;
 }
 
+/* the scene's table of shading constants (rt_device.h: SceneConsts): one workgroup, a lane per light */
+__global__ void __launch_bounds__(RTR_BLOCK) k_scene_consts(const rtr_light* __restrict__ lights, const int n_lights,
+                                                            SceneConsts* __restrict__ out) {
+    for (int k = threadIdx.x; k < (n_lights > 1 ? n_lights : 1); k += RTR_BLOCK) scene_consts_fill(lights, n_lights, out, k);
+}
+
 int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
     if (!c) return RTR_ERR_INVALID;
     Validator v;
@@ -486,6 +493,14 @@ int rtr_upload_scene(rtr_context* c, const rtr_scene_desc* s) {
     if ((rc = put(c, b.fmat, L.mats, d.fmat))) return rc;
     if ((rc = put(c, b.ffin, L.finish, d.ffin))) return rc;
     if (L.finish.empty()) d.ffin = nullptr; /* (an earlier scene's buffer may still be there: null means "no records") */
+    /* the lights are on the device (blocking copies): their table is made there, and is there when this call returns.
+     * Nothing else changes lights, so nothing else makes it */
+    if ((rc = ensure(c, b.sconsts, scene_consts_bytes(s->n_lights)))) return rc;
+    d.consts = static_cast<const SceneConsts*>(b.sconsts.p);
+    hipLaunchKernelGGL(k_scene_consts, dim3(1), dim3(RTR_BLOCK), 0, c->stream, d.lights, (int)s->n_lights,
+                       static_cast<SceneConsts*>(b.sconsts.p));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((rc = upload(c, b.dscene, &d, sizeof(DScene)))) return rc;
     c->info = info;
     c->facts = L.facts;

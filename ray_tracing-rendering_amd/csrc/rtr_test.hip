@@ -420,6 +420,52 @@ int rtr_test_shared_division(rtr_context* c, uint64_t* mismatches, uint64_t* tes
     return RTR_OK;
 }
 
+int rtr_test_udiv(rtr_context* c, const double* num, int64_t n, const double* div, int32_t m, uint64_t* mismatches, uint64_t* tested) {
+    if (!c || !mismatches || !tested) return RTR_ERR_INVALID;
+    if (n < 1 || m < 1 || !num || !div) return fail(c, RTR_ERR_INVALID, "bad array");
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc) return rc;
+    if ((rc = ensure(c, *t, 16 + (size_t)(n + m) * 8))) return rc;
+    auto* counts = static_cast<unsigned long long*>(t->buf);
+    double* dnum = reinterpret_cast<double*>(counts + 2);
+    double* ddiv = dnum + n;
+    TCHK(c, hipMemsetAsync(counts, 0, 16, stream));
+    TCHK(c, hipMemcpy(dnum, num, (size_t)n * 8, hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(ddiv, div, (size_t)m * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_test_udiv, grid_of(n), dim3(RTR_BLOCK), 0, stream, dnum, (long long)n, ddiv, (int)m, counts);
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream));
+    unsigned long long h[2] = {0, 0};
+    TCHK(c, hipMemcpy(h, counts, 16, hipMemcpyDeviceToHost));
+    *mismatches = h[0], *tested = h[1];
+    return RTR_OK;
+}
+
+int rtr_test_scene_consts(rtr_context* c, uint64_t* table, uint64_t* again, int64_t cap, int32_t* n_lights) {
+    static_assert(sizeof(SceneConsts) == 32 && sizeof(LightConsts) == 40, "4 + 5 words per light");
+    rtr_debug_view v;
+    TestState* t;
+    int rc = begin(c, nullptr, 0, 0, v, t);
+    if (rc) return rc;
+    if (!n_lights || cap < 0 || (cap > 0 && (!table || !again))) return fail(c, RTR_ERR_INVALID, "bad array");
+    *n_lights = v.ds.n_lights;
+    const size_t bytes = scene_consts_bytes(v.ds.n_lights);
+    if ((size_t)cap * 8 < bytes) return cap == 0 ? RTR_OK : fail(c, RTR_ERR_INVALID, "table buffer too small");
+    if (!v.ds.consts) return fail(c, RTR_ERR_DEVICE, "the uploaded scene has no table of constants");
+    TCHK(c, hipSetDevice(v.device));
+    if ((rc = ensure(c, *t, bytes))) return rc;
+    TCHK(c, hipMemsetAsync(t->buf, 0, bytes, v.stream));
+    hipLaunchKernelGGL(k_test_scene_consts, dim3(1), dim3(RTR_BLOCK), 0, v.stream, v.ds, static_cast<SceneConsts*>(t->buf));
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(v.stream));
+    TCHK(c, hipMemcpy(again, t->buf, bytes, hipMemcpyDeviceToHost));
+    TCHK(c, hipMemcpy(table, v.ds.consts, bytes, hipMemcpyDeviceToHost));
+    return RTR_OK;
+}
+
 /* k_temporal_blend and k_temporal_store of the product on caller-given planes: the planes they touch in the test buffer,
  * the grids of denoise_run (rtr_image.hip) */
 int rtr_test_temporal_planes(rtr_context* c, int32_t width, int32_t height, int32_t image_width, int32_t image_height, int32_t x0,

@@ -39,7 +39,7 @@ TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_t
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
                 "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
-                "rtr_test_pow5_host")
+                "rtr_test_pow5_host", "rtr_test_udiv", "rtr_test_scene_consts")
 _TEST_LIB = None
 
 
@@ -222,6 +222,8 @@ def test_lib():
     T.rtr_test_pair_cast.argtypes = [vp, vp, C.c_int64]
     T.rtr_test_queue_blocks_host.argtypes = [C.c_int32] * 6 + [vp, C.c_int64]
     T.rtr_test_queue_pack_host.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
+    T.rtr_test_udiv.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    T.rtr_test_scene_consts.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int32)]
     _TEST_LIB = T
     return T
 
@@ -809,6 +811,32 @@ class Context:
         n, tested = C.c_uint64(0), C.c_uint64(0)
         self._chk(test_lib().rtr_test_shared_division(self._h, C.byref(n), C.byref(tested)))
         return int(n.value), int(tested.value)
+
+    def udiv_mismatches(self, numerators, divisors):
+        """rtr_test_udiv (include/rtr_hip_test.h): every numerator over every divisor through udiv and through n / d; (how
+        many quotients differ in any bit, how many pairs were compared)."""
+        num = np.ascontiguousarray(numerators, dtype=np.float64).ravel()
+        div = np.ascontiguousarray(divisors, dtype=np.float64).ravel()
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        self._chk(test_lib().rtr_test_udiv(self._h, num.ctypes.data, len(num), div.ctypes.data, len(div), C.byref(n),
+                                           C.byref(tested)))
+        return int(n.value), int(tested.value)
+
+    def scene_consts(self):
+        """rtr_test_scene_consts (include/rtr_hip_test.h): the uploaded scene's table of shading constants and its second
+        evaluation by the test library, each as a dict: ``inv_n_lights``, ``pi``, ``rcp_pi`` (and all of it as uint64 bits in
+        ``words``), ``lights`` (n, 4) float64 = len2(U), its reciprocal, len2(V), its reciprocal, ``safe`` (n,) int."""
+        nl = C.c_int32(0)
+        self._chk(test_lib().rtr_test_scene_consts(self._h, None, None, 0, C.byref(nl)))
+        words = 4 + 5 * nl.value
+        a, b = np.zeros(words, dtype=np.uint64), np.zeros(words, dtype=np.uint64)
+        self._chk(test_lib().rtr_test_scene_consts(self._h, a.ctypes.data, b.ctypes.data, words, C.byref(nl)))
+
+        def view(w):
+            per = w[4:].reshape(nl.value, 5)
+            return {"words": w, "inv_n_lights": float(w[:1].view(np.float64)[0]), "pi": float(w[2:3].view(np.float64)[0]), "rcp_pi": float(w[3:4].view(np.float64)[0]),
+                    "lights": np.ascontiguousarray(per[:, :4]).view(np.float64), "safe": (per[:, 4] & 0xffffffff).astype(np.int64)}
+        return view(a), view(b)
 
     def shared_division_mismatches(self):
         """2^32 operand pairs: how many quotients of the shared-reciprocal division differ from n / d (include/rtr_hip_test.h)."""
