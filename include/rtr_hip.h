@@ -858,6 +858,110 @@ int rtr_gather_radiance_device(rtr_context* ctx, const rtr_render_params* render
 int rtr_gather_ray(const rtr_gather_params* params, const rtr_gather_point* point, int64_t index_in_call, int32_t s,
                    rtr_ray* out);
 
+/* ---- light probes: second-order spherical harmonics of visibility and radiance at points in space, and their use ----
+ * A probe is a point p in free space, without a normal.  For each of `n` probes the library makes N = params->samples rays
+ * over the whole sphere in registers, casts them, projects every sample onto nine real spherical harmonics and reduces
+ * them inside the wave to one record: directional lighting for objects that move through a baked scene.  rtr_gather_params
+ * is the parameter block, and everything the gathers' contract above says of it holds here.  Every output bit is defined
+ * here; only + - * / sqrt and compares are used, in the order written.
+ *
+ * RAY s (0 <= s < N) of probe k (k = its index in the call + params->point_base, taken modulo 2^32):
+ *   state = rtr_sample_seed_inline(seed, 1, 0, (int32_t)k, s)
+ *   u = random_unit_vector(state)       the rejection loop of the gathers: draws z, y, x until x*x + y*y + z*z < 1
+ *   d = unit(u) = (1 / sqrt(x*x + y*y + z*z)) * (x, y, z)
+ * There is no normal and no near_zero step: d is uniform on the sphere and of unit length, so t_max is a distance.  The
+ * ray is (origin p, direction d, time, [t_min, t_max]) with the state left after the draws (rtr_probe_ray is the host form).
+ *
+ * BASIS: nine functions of d = (x, y, z), in this order and with these literals (rtr_sh_basis is the host form, the same
+ * function the kernels call):
+ *   K0 = 0.28209479177387814  K1 = 0.4886025119029199  K2 = 1.0925484305920792  K3 = 0.31539156525252005
+ *   K4 = 0.5462742152960396
+ *   Y0 = K0          Y1 = K1*y        Y2 = K1*z                       Y3 = K1*x       Y4 = K2*(x*y)
+ *   Y5 = K2*(y*z)    Y6 = K3*(3.0*(z*z) - 1.0)                        Y7 = K2*(x*z)   Y8 = K4*(x*x - y*y)
+ *
+ * REDUCTION: the gathers', word for word, for every component independently: G = min(64, bit_ceil(N)); lane l adds its
+ * samples l, l + G, ... in increasing order into +0.0; then for off = G/2, ..., 1: a[l] = a[l] + a[l xor off]; then
+ * c = (1.0 / N) * a[0].  Counts the same way.
+ *
+ * rtr_probe_visibility: an unblocked sample adds Y_i(d) to component i, a blocked one adds nothing.  BLOCKED is the
+ * gathers' meaning: the any-hit cast of the shadow rays finds something in [t_min, t_max] (rtr_query_occluded of that ray,
+ * draws inside media included).  count = the unblocked samples.
+ * rtr_probe_radiance: sample s adds Y_i(d) * L[ch] to c[i][ch], L = what rtr_li_rays returns for that ray and state under
+ * render->integrator, max_depth, rr_start_depth and flags (t_min and t_max do not apply).  count = N.  c is the mean over
+ * uniform directions: the estimate of the SH coefficients of the radiance field is 4 pi * c (rtr_sh_irradiance applies it).
+ *
+ * A probe is BAD if a component of p is not finite.  The host entries reject the whole batch with RTR_ERR_INVALID, name
+ * the first bad index in rtr_last_error and leave the outputs untouched; the device entries write an all-zero record
+ * (valid 0) for such a probe without casting, and every other probe gets valid = 1.
+ *
+ * Parameter checks, n == 0, RTR_ERR_NO_SCENE, the slices of 2^20 points that advance point_base, the 2^-100 rule of t_min,
+ * stream order (device pointers 8-byte aligned, `blocking`), and what a call leaves alone -- renders, accumulators,
+ * statistics -- are the gathers'.  The host entries go through a buffer of the context nothing else uses. */
+typedef struct rtr_probe_point {    /* 24 bytes */
+    double p[3];
+} rtr_probe_point;
+
+typedef struct rtr_probe_vis {      /* 80 bytes */
+    double c[9];
+    int32_t count, valid;
+} rtr_probe_vis;
+
+typedef struct rtr_probe_sh {       /* 224 bytes */
+    double c[9][3];                 /* [basis function][r, g, b] */
+    int32_t count, valid;
+} rtr_probe_sh;
+
+int rtr_probe_visibility(rtr_context* ctx, const rtr_gather_params* params, const rtr_probe_point* points,
+                         rtr_probe_vis* out, int64_t n);
+int rtr_probe_radiance(rtr_context* ctx, const rtr_render_params* render, const rtr_gather_params* params,
+                       const rtr_probe_point* points, rtr_probe_sh* out, int64_t n);
+int rtr_probe_visibility_device(rtr_context* ctx, const rtr_gather_params* params, const rtr_probe_point* d_points,
+                                rtr_probe_vis* d_out, int64_t n, int blocking);
+int rtr_probe_radiance_device(rtr_context* ctx, const rtr_render_params* render, const rtr_gather_params* params,
+                              const rtr_probe_point* d_points, rtr_probe_sh* d_out, int64_t n, int blocking);
+
+/* Host-only, needs no context: ray s of the probe at `index_in_call`, like rtr_gather_ray.  RTR_ERR_INVALID for a bad
+ * probe, bad params, a negative index or s outside [0, samples). */
+int rtr_probe_ray(const rtr_gather_params* params, const rtr_probe_point* point, int64_t index_in_call, int32_t s,
+                  rtr_ray* out);
+
+/* Host-only: the nine basis functions at d (taken as given: the kernels pass unit vectors). */
+void rtr_sh_basis(const double d[3], double y[9]);
+
+/* Host-only: irradiance E[ch] at a surface with normal n lit by the radiance whose probe record holds c.
+ *   w = unit(n), y = basis(w)
+ *   per channel: e = +0.0; for i = 0..8 in order: e = e + (A[i] * y[i]) * c[i][ch]; E[ch] = 12.566370614359172 * e
+ *   A = {3.141592653589793, 2.0943951023931953 x3, 0.7853981633974483 x5}: the clamped-cosine factors pi, 2 pi / 3, pi / 4
+ * RTR_ERR_INVALID for a NULL pointer or a bad normal (the gathers' rule: a component not finite, or sqrt(n.n) not in (0, inf)). */
+int rtr_sh_irradiance(const double c[9][3], const double n[3], double E[3]);
+
+/* GRID LOOKUP: probes on a regular grid -> irradiance at query points (p, n), trilinear in the coefficients.
+ * Probe (ix, iy, iz) of the grid has index ix + dims[0] * (iy + dims[1] * iz) in the rtr_probe_sh array and stands at
+ * origin + (ix, iy, iz) * spacing.  origin finite; spacing finite and > 0; dims >= 1 with a product <= 2^24; pad 0.
+ * Per axis a:
+ *   f = (p[a] - origin[a]) / spacing[a];  f = min(max(f, 0.0), (double)(dims[a] - 1))     (a query outside is clamped)
+ *   i0 = (int)f;  if i0 > dims[a] - 2: i0 = max(dims[a] - 2, 0)
+ *   t = f - (double)i0, and t = 0 when dims[a] == 1;  w0 = 1.0 - t, w1 = t
+ * The corners are visited with dz outermost, then dy, then dx, each in {0, 1}, every index clipped to dims - 1:
+ *   w = (wx * wy) * wz;  the corner is USED if w > 0 and its probe has valid != 0
+ *   a used corner: wsum = wsum + w and acc[i][ch] = acc[i][ch] + w * probe.c[i][ch]
+ * No used corner: {0, 0, 0, count 0, valid 0}.  Otherwise c = (1.0 / wsum) * acc, v = rtr_sh_irradiance(c, n),
+ * count = the used corners, valid 1.  A BAD query is a bad gather point: the host entry rejects the batch and names the
+ * index, the device entry writes valid 0 for it without reading a probe.  Neither entry needs a scene; n == 0 is RTR_OK. */
+typedef struct rtr_probe_grid {     /* 64 bytes */
+    double origin[3], spacing[3];
+    int32_t dims[3], pad;
+} rtr_probe_grid;
+
+int rtr_probe_lookup(rtr_context* ctx, const rtr_probe_grid* grid, const rtr_probe_sh* probes,
+                     const rtr_gather_point* queries, rtr_gather_out* out, int64_t n);
+int rtr_probe_lookup_device(rtr_context* ctx, const rtr_probe_grid* grid, const rtr_probe_sh* d_probes,
+                            const rtr_gather_point* d_queries, rtr_gather_out* d_out, int64_t n, int blocking);
+/* Host-only, needs no context: the lookup of one query over HOST probes, the same function the kernel calls.
+ * RTR_ERR_INVALID for a bad grid, a bad query or a NULL pointer. */
+int rtr_probe_lookup_one(const rtr_probe_grid* grid, const rtr_probe_sh* probes, const rtr_gather_point* query,
+                         rtr_gather_out* out);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

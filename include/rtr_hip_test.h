@@ -72,6 +72,14 @@ typedef struct rtr_gather_record {
 /* size_of_out must be sizeof(rtr_gather_record) */
 int rtr_test_last_gather(rtr_context* ctx, rtr_gather_record* out, size_t size_of_out);
 
+/* The same for the light probes: k_probe_li<integ, trav> of the last rtr_probe_radiance call, or with integ = -1
+ * k_probe_any<trav> of the last rtr_probe_visibility call; trav = -1: no probe call has launched anything yet. */
+typedef struct rtr_probe_record {
+    int32_t integ, trav, lg;
+} rtr_probe_record;
+/* size_of_out must be sizeof(rtr_probe_record) */
+int rtr_test_last_probe(rtr_context* ctx, rtr_probe_record* out, size_t size_of_out);
+
 /* What the library makes of a scene before anything reaches a device: the validator, the host-only lowering
  * (csrc/rt_lower.h: lower_scene) and the two decisions every launch hangs on -- pick_trav and, for `integrator` and the
  * render `flags`, mega_variant (csrc/rt_select.h).  Needs no context and no GPU.  RT_TRAV_*, RT_MS_*, RT_TIE_FLAG and

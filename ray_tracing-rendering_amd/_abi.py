@@ -58,6 +58,12 @@ GATHER_POINT_DTYPE = np.dtype([("p", "<f8", (3,)), ("n", "<f8", (3,))])
 GATHER_OUT_DTYPE = np.dtype([("v", "<f8", (3,)), ("count", "<i4"), ("valid", "<i4")])
 assert GATHER_POINT_DTYPE.itemsize == 48 and GATHER_OUT_DTYPE.itemsize == 32
 GATHER_MAX_SAMPLES = 1 << 20
+# light probes (rtr_probe_*): rtr_probe_point in, rtr_probe_vis / rtr_probe_sh out
+PROBE_POINT_DTYPE = np.dtype([("p", "<f8", (3,))])
+PROBE_VIS_DTYPE = np.dtype([("c", "<f8", (9,)), ("count", "<i4"), ("valid", "<i4")])
+PROBE_SH_DTYPE = np.dtype([("c", "<f8", (9, 3)), ("count", "<i4"), ("valid", "<i4")])
+assert PROBE_POINT_DTYPE.itemsize == 24 and PROBE_VIS_DTYPE.itemsize == 80 and PROBE_SH_DTYPE.itemsize == 224
+PROBE_GRID_MAX = 1 << 24
 
 # golden-vector records (rtr_testrec.h, packed)
 LI_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("s", "<i4"), ("rng_exit", "<u4"), ("L", "<f8", (3,)),
@@ -133,6 +139,15 @@ class GatherParamsC(C.Structure):
 
 GATHER_PARAMS_SIZE = 56
 assert C.sizeof(GatherParamsC) == GATHER_PARAMS_SIZE
+
+
+class ProbeGridC(C.Structure):
+    """rtr_probe_grid (include/rtr_hip.h): the regular grid of rtr_probe_lookup"""
+    _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("dims", C.c_int32 * 3), ("pad", C.c_int32)]
+
+
+PROBE_GRID_SIZE = 64
+assert C.sizeof(ProbeGridC) == PROBE_GRID_SIZE
 
 
 class DenoiseParamsC(C.Structure):

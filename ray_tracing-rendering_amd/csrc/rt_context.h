@@ -47,6 +47,7 @@ struct rtr_context {
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
     DevBuf b_query; /* rtr_query_closest / rtr_query_occluded: one slice of rays and its results (nothing else uses it) */
     DevBuf b_gather; /* rtr_gather_occlusion / rtr_gather_radiance: one slice of points and its results (nothing else uses it) */
+    DevBuf b_probe; /* rtr_probe_visibility / _radiance / _lookup: one slice of inputs and its results (nothing else uses it) */
     DevBuf b_display;    /* rtr_display_*: the sRGB thresholds (uploaded by rtr_create), the histogram, the DisplayRec */
     DevBuf b_display_io; /* rtr_display_host / _histogram: the image and its outputs (nothing else uses it) */
     std::vector<int> last_tiles; /* what b_tiles holds */
@@ -59,6 +60,7 @@ struct rtr_context {
     rtr_render_stats stats{};
     rtr_debug_kernel last_kernel{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0}; /* rtr_debug_last_kernel */
     rtr_debug_gather last_gather{-1, -1, 0, 0};                         /* rtr_debug_last_gather */
+    rtr_debug_probe last_probe{-1, -1, 0};                              /* rtr_debug_last_probe */
     /* Cancel.  Renders are numbered; rtr_cancel() covers every render issued so far: it stores the newest
      * id in `cancelled_upto` and in the device word the kernels poll.  A render issued afterwards carries a
      * larger id, so nothing has to be reset between renders and a cancel that arrives while a render waits

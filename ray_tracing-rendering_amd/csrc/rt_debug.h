@@ -40,6 +40,12 @@ struct rtr_debug_gather {
     int broadcast; /* k_gather_any<T, true> */
     int lg;        /* log2 of the lanes that share a point (gather_lg of the samples) */
 };
+/* the probe kernel the last rtr_probe_visibility / rtr_probe_radiance call launched (of its last slice), recorded like a gather's */
+struct rtr_debug_probe {
+    int integ; /* k_probe_li<integ, trav>; -1: visibility, k_probe_any<trav> */
+    int trav;  /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no probe call yet */
+    int lg;    /* log2 of the lanes that share a point */
+};
 struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     double L[3];
     uint32_t rng_exit;
@@ -65,6 +71,7 @@ int rtr_debug_frame_shapes(const rtr_scene_desc* scene, int32_t* shapes, int64_t
 int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t size_of_view);
 int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
 int rtr_debug_last_gather(rtr_context* ctx, rtr_debug_gather* out, size_t size_of_out);
+int rtr_debug_last_probe(rtr_context* ctx, rtr_debug_probe* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);
 void rtr_debug_set_error(rtr_context* ctx, const char* msg); /* rtr_last_error() of a failing rtr_test_* call */
 }

@@ -13,6 +13,8 @@
  *  k_li        Integrator::Li of single camera samples or caller-given rays, one lane each (rtr_li_samples / rtr_li_rays).
  *  k_gather_any / k_gather_li   hemisphere gathers (rtr_gather_*): a group of up to 64 lanes per point makes its samples'
  *              rays in registers, casts them (any-hit / Integrator::Li) and reduces them inside the wave.
+ *  k_probe_any / k_probe_li     light probes (rtr_probe_*): the gathers' mapping over the whole sphere, every sample projected
+ *              onto nine spherical harmonics; 9 or 27 sums per point instead of 3.
  *  k_features  first-hit albedo / normal / depth of a pixel's first K camera samples (rtr_accum_features).
  *  k_query_closest / k_query_any   hittable::hit of the scene root for caller-given rays (rtr_query_*).
  * Template kernels only, instantiated by the unit that launches them.  The non-template kernels live in one header per
@@ -1307,4 +1309,134 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_gather_li(const DScene sc, const 
             a = add(a, ps.L), ++count;
         }
     gather_end(K, L, a, count);
+}
+
+/* rtr_probe_visibility / rtr_probe_radiance: N sphere samples per probe, projected onto the nine SH functions of
+ * sh_basis and reduced like a gather (include/rtr_hip.h has the contract).  The mapping is the gathers': global lane g
+ * serves point g / G as lane g % G, lanes without a sample, of a bad point or of a point past the end carry +0.0 / 0
+ * through every __shfl_xor, lane 0 of a group stores the record.  A probe has no normal and the records differ, so the
+ * kernels have a begin and an end of their own and leave gather_begin / gather_end as they are.
+ * k_probe_li keeps its 27 sums per lane in LDS behind the traversal stack (RTR_PROBE_LDS_SUMS): word i of
+ * lane l is sums[i * RTR_BLOCK + l], each lane touches only its own words, so no barrier is needed; the butterfly reads
+ * them back into registers behind the sample loop. */
+#ifndef RTR_PROBE_LDS_SUMS
+#define RTR_PROBE_LDS_SUMS 1 /* 0: the sums of k_probe_li stay in registers across the bounce loop */
+#endif
+constexpr size_t probe_sum_bytes() { return RTR_PROBE_LDS_SUMS ? (size_t)27 * sizeof(double) * RTR_BLOCK : 0; }
+struct ProbeLane {
+    long long k; /* point of this lane's group */
+    int l;       /* lane in the group */
+    bool cast;   /* the point exists and is not bad */
+    V3 p;
+};
+RT_DEV bool probe_begin(const ProbeK& K, ProbeLane& L) {
+    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (((g & ~63ll) >> K.lg) >= K.n) return false; /* the whole wave is past the end */
+    L.k = g >> K.lg, L.l = (int)(g & ((1 << K.lg) - 1));
+    const bool live = L.k < K.n;
+    rtr_probe_point q;
+    for (int a = 0; a < 3; ++a) q.p[a] = 0.0;
+    if (live) q = K.pts[L.k];
+    L.cast = !probe_point_bad(q) && live;
+    L.p = ld3(q.p);
+    return true;
+}
+RT_DEV uint32_t probe_ray(const ProbeK& K, const ProbeLane& L, int s, V3& d) {
+    uint32_t rng = rtr_sample_seed_inline(K.seed, 1, 0, (int32_t)((uint32_t)L.k + K.point_base), s);
+    probe_direction(rng, d.x, d.y, d.z);
+    return rng;
+}
+/* the butterfly over C sums and the count; afterwards lane 0 of a group holds the totals */
+template <int C>
+RT_DEV void probe_reduce(const ProbeK& K, double (&a)[C], int& count) {
+    for (int off = (1 << K.lg) >> 1; off > 0; off >>= 1) {
+#pragma unroll
+        for (int i = 0; i < C; ++i) a[i] = a[i] + __shfl_xor(a[i], off, 64);
+        count = count + __shfl_xor(count, off, 64);
+    }
+}
+template <int TRAV>
+__global__ void __launch_bounds__(RTR_BLOCK) k_probe_any(const DScene sc, const ProbeK K) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    ProbeLane L;
+    if (!probe_begin(K, L)) return;
+    double a[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) a[i] = 0.0;
+    int count = 0;
+    if (L.cast)
+        for (int s = L.l; s < K.samples; s += 1 << K.lg) {
+            V3 d;
+            uint32_t rng = probe_ray(K, L, s, d);
+            if (!cast_shadow<TRAV>(sc, L.p, d, K.t_max, rng, st, K.time, K.t_min)) {
+                double Y[9];
+                sh_basis(d.x, d.y, d.z, Y);
+#pragma unroll
+                for (int i = 0; i < 9; ++i) a[i] = a[i] + Y[i];
+                ++count;
+            }
+        }
+    probe_reduce(K, a, count);
+    if (L.l != 0 || L.k >= K.n) return;
+    rtr_probe_vis o;
+    const double scale = 1.0 / K.samples;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o.c[i] = L.cast ? scale * a[i] : 0.0;
+    o.count = L.cast ? count : 0, o.valid = L.cast ? 1 : 0;
+    static_cast<rtr_probe_vis*>(K.out)[L.k] = o;
+}
+template <int INTEG, int TRAV>
+__global__ void __launch_bounds__(RTR_BLOCK) k_probe_li(const DScene sc, const ProbeK K) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    ProbeLane L;
+    if (!probe_begin(K, L)) return;
+    double a[27];
+#if RTR_PROBE_LDS_SUMS
+    double* sums = reinterpret_cast<double*>(lds_stack + K.sum_word) + threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 27; ++i) sums[i * RTR_BLOCK] = 0.0;
+#else
+#pragma unroll
+    for (int i = 0; i < 27; ++i) a[i] = 0.0;
+#endif
+    int count = 0;
+    if (L.cast)
+        for (int s = L.l; s < K.samples; s += 1 << K.lg) {
+            V3 d;
+            uint32_t rng = probe_ray(K, L, s, d);
+            PathState ps;
+            path_begin(ps, L.p, d, K.time);
+            PathCounters cnt;
+            cnt.closest = 0, cnt.shadow = 0;
+            while (bounce<INTEG, TRAV>(sc, ps, rng, st, K.max_depth, K.rr_start, cnt)) {
+            }
+            double Y[9];
+            sh_basis(d.x, d.y, d.z, Y);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+#if RTR_PROBE_LDS_SUMS
+                sums[(3 * i) * RTR_BLOCK] = sums[(3 * i) * RTR_BLOCK] + Y[i] * ps.L.x;
+                sums[(3 * i + 1) * RTR_BLOCK] = sums[(3 * i + 1) * RTR_BLOCK] + Y[i] * ps.L.y;
+                sums[(3 * i + 2) * RTR_BLOCK] = sums[(3 * i + 2) * RTR_BLOCK] + Y[i] * ps.L.z;
+#else
+                a[3 * i] = a[3 * i] + Y[i] * ps.L.x, a[3 * i + 1] = a[3 * i + 1] + Y[i] * ps.L.y, a[3 * i + 2] = a[3 * i + 2] + Y[i] * ps.L.z;
+#endif
+            }
+            ++count;
+        }
+#if RTR_PROBE_LDS_SUMS
+#pragma unroll
+    for (int i = 0; i < 27; ++i) a[i] = sums[i * RTR_BLOCK];
+#endif
+    probe_reduce(K, a, count);
+    if (L.l != 0 || L.k >= K.n) return;
+    rtr_probe_sh o;
+    const double scale = 1.0 / K.samples;
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+        for (int ch = 0; ch < 3; ++ch) o.c[i][ch] = L.cast ? scale * a[3 * i + ch] : 0.0;
+    o.count = L.cast ? count : 0, o.valid = L.cast ? 1 : 0;
+    static_cast<rtr_probe_sh*>(K.out)[L.k] = o;
 }

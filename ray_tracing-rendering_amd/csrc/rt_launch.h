@@ -1,7 +1,7 @@
 /*
  * rt_launch.h -- host-side seams between the translation units of librtr_hip.so that launch for one another.  The
  * units are compiled in parallel: rtr_capi.hip (context, scene upload, renders, k_li), rtr_accum.hip, rtr_image.hip,
- * rtr_query.hip and rtr_gather.hip (one subject of include/rtr_hip.h each, with its kernels), rtr_mega.hip three times
+ * rtr_query.hip, rtr_gather.hip and rtr_probe.hip (one subject of include/rtr_hip.h each, with its kernels), rtr_mega.hip three times
  * (one integrator group each: RTR_MEGA_GROUP 0 = MIS, 1 = RR + path, 2 = PBR + NEE) and rtr_wavefront.hip (stage
  * kernels + their host driver).
  *

@@ -161,6 +161,16 @@ struct GatherK {
     double time, t_min, t_max;
     int max_depth, rr_start;    /* radiance only */
 };
+/* why `p` is no valid parameter block, or nullptr: the rules of the gathers, which the probes share with the block */
+inline const char* gather_params_why(const rtr_gather_params* p) {
+    if (!p) return "null gather params";
+    if (p->samples < 1 || p->samples > (1 << 20)) return "samples outside 1 .. 2^20";
+    if (p->flags & ~RTR_FLAG_REFERENCE_ORDER) return "unknown flag bits";
+    if (!__builtin_isfinite(p->time) || !__builtin_isfinite(p->t_min)) return "time or t_min not finite";
+    if (p->t_max != p->t_max) return "t_max is NaN";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return "reserved must be 0";
+    return nullptr;
+}
 RT_HD int gather_lg(int samples) {
     int lg = 0;
     while (lg < 6 && (1 << lg) < samples) ++lg;
@@ -189,6 +199,110 @@ RT_HD void gather_direction(double wx, double wy, double wz, uint32_t& rng, doub
     if (__builtin_fabs(sx) < 1e-8 && __builtin_fabs(sy) < 1e-8 && __builtin_fabs(sz) < 1e-8) sx = wx, sy = wy, sz = wz;
     const double rs = 1 / __builtin_sqrt(sx * sx + sy * sy + sz * sz);
     dx = rs * sx, dy = rs * sy, dz = rs * sz;
+}
+
+/* ---- light probes (include/rtr_hip.h: rtr_probe_*, rtr_sh_*) ----
+ * The arithmetic of that contract, written once for host (rtr_probe_ray, rtr_sh_basis, rtr_sh_irradiance, the entries'
+ * checks) and device (k_probe_*): the same rules as the gathers' above. */
+struct ProbeK {
+    const rtr_probe_point* pts;
+    void* out;                  /* rtr_probe_vis (k_probe_any) or rtr_probe_sh (k_probe_li) records */
+    long long n;
+    int samples, lg;            /* N; log2 of the group size, the gathers' gather_lg */
+    uint32_t seed, point_base;
+    double time, t_min, t_max;
+    int max_depth, rr_start;    /* radiance only */
+    int sum_word;               /* radiance only: the word of the dynamic LDS at which the per-lane sums start */
+};
+RT_HD bool probe_point_bad(const rtr_probe_point& q) {
+    return !(__builtin_isfinite(q.p[0]) && __builtin_isfinite(q.p[1]) && __builtin_isfinite(q.p[2]));
+}
+/* uniform on the sphere: the rejection loop of gather_direction, then unit; rng is left behind the draws */
+RT_HD void probe_direction(uint32_t& rng, double& dx, double& dy, double& dz) {
+    double x, y, z;
+    for (;;) {
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        z = -1.0 + rng * 4.656612873077392578125e-10;
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        y = -1.0 + rng * 4.656612873077392578125e-10;
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        x = -1.0 + rng * 4.656612873077392578125e-10;
+        if (!(x * x + y * y + z * z >= 1)) break;
+    }
+    const double ru = 1 / __builtin_sqrt(x * x + y * y + z * z);
+    dx = ru * x, dy = ru * y, dz = ru * z;
+}
+/* the nine real spherical harmonics of bands 0..2 at the unit vector (x, y, z), in the header's order */
+RT_HD void sh_basis(double x, double y, double z, double* Y) {
+    const double K0 = 0.28209479177387814, K1 = 0.4886025119029199, K2 = 1.0925484305920792, K3 = 0.31539156525252005,
+                 K4 = 0.5462742152960396;
+    Y[0] = K0;
+    Y[1] = K1 * y;
+    Y[2] = K1 * z;
+    Y[3] = K1 * x;
+    Y[4] = K2 * (x * y);
+    Y[5] = K2 * (y * z);
+    Y[6] = K3 * (3.0 * (z * z) - 1.0);
+    Y[7] = K2 * (x * z);
+    Y[8] = K4 * (x * x - y * y);
+}
+/* irradiance E of the normal n (nlen = sqrt(n.n), in (0, inf): gather_point_bad) under the radiance coefficients c */
+RT_HD void sh_irradiance(const double (*c)[3], const double* n, double nlen, double* E) {
+    const double r = 1 / nlen;
+    double y[9];
+    sh_basis(r * n[0], r * n[1], r * n[2], y);
+    const double A1 = 2.0943951023931953, A2 = 0.7853981633974483;
+    const double A[9] = {3.141592653589793, A1, A1, A1, A2, A2, A2, A2, A2};
+    for (int ch = 0; ch < 3; ++ch) {
+        double e = 0.0;
+        for (int i = 0; i < 9; ++i) e = e + (A[i] * y[i]) * c[i][ch];
+        E[ch] = 12.566370614359172 * e;
+    }
+}
+/* one axis of the grid lookup: the lower corner i0 and the weights of it and of its neighbour */
+RT_HD void probe_axis(double p, double origin, double spacing, int dim, int& i0, double& w0, double& w1) {
+    double f = (p - origin) / spacing;
+    const double hi = (double)(dim - 1);
+    f = f > 0.0 ? f : 0.0;
+    f = f < hi ? f : hi;
+    i0 = (int)f;
+    if (i0 > dim - 2) i0 = dim - 2 > 0 ? dim - 2 : 0;
+    const double t = dim == 1 ? 0.0 : f - (double)i0;
+    w0 = 1.0 - t, w1 = t;
+}
+/* rtr_probe_lookup of one query that is not bad; probes: the grid's records */
+RT_HD rtr_gather_out probe_lookup_one(const rtr_probe_grid& g, const rtr_probe_sh* __restrict__ probes, const rtr_gather_point& q,
+                                      double nlen) {
+    int i0[3];
+    double w[3][2];
+    for (int a = 0; a < 3; ++a) probe_axis(q.p[a], g.origin[a], g.spacing[a], g.dims[a], i0[a], w[a][0], w[a][1]);
+    double acc[9][3];
+    for (int i = 0; i < 9; ++i) acc[i][0] = acc[i][1] = acc[i][2] = 0.0;
+    double wsum = 0.0;
+    int used = 0;
+    for (int dz = 0; dz < 2; ++dz)
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ix = i0[0] + dx < g.dims[0] - 1 ? i0[0] + dx : g.dims[0] - 1;
+                const int iy = i0[1] + dy < g.dims[1] - 1 ? i0[1] + dy : g.dims[1] - 1;
+                const int iz = i0[2] + dz < g.dims[2] - 1 ? i0[2] + dz : g.dims[2] - 1;
+                const double wc = (w[0][dx] * w[1][dy]) * w[2][dz];
+                const rtr_probe_sh& pr = probes[ix + (long long)g.dims[0] * (iy + (long long)g.dims[1] * iz)];
+                if (wc > 0 && pr.valid != 0) {
+                    wsum = wsum + wc, ++used;
+                    for (int i = 0; i < 9; ++i)
+                        for (int ch = 0; ch < 3; ++ch) acc[i][ch] = acc[i][ch] + wc * pr.c[i][ch];
+                }
+            }
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    if (used == 0) return o;
+    const double rw = 1.0 / wsum;
+    for (int i = 0; i < 9; ++i)
+        for (int ch = 0; ch < 3; ++ch) acc[i][ch] = rw * acc[i][ch];
+    sh_irradiance(acc, q.n, nlen, o.v);
+    o.count = used, o.valid = 1;
+    return o;
 }
 
 struct ResolveK {

@@ -2,7 +2,7 @@
  * rt_select.h -- from what is known about a scene and a call to the kernel that runs: THE place of every rule that
  * turns (SceneFacts, rtr_scene_info, integrator, flags) into a traversal, a k_mega instantiation, a k_li-shaped kernel,
  * a wavefront plan or a chunk count.  Host side, no HIP call, nothing else: a sibling of rt_lower.h, which finds the
- * facts out.  The units that launch (rtr_capi.hip, rtr_accum.hip, rtr_query.hip, rtr_gather.hip) ask here.
+ * facts out.  The units that launch (rtr_capi.hip, rtr_accum.hip, rtr_query.hip, rtr_gather.hip, rtr_probe.hip) ask here.
  */
 #pragma once
 
@@ -38,10 +38,10 @@ inline int per_ray_trav(const SceneFacts& f, const rtr_scene_info& info, int fla
     return trav == RT_TRAV_PROGRAM ? RT_TRAV_PROGRAM_EXT : trav;
 }
 
-/* ---- the k_li family: k_li and k_gather_li<INTEG, TRAV> ----
+/* ---- the k_li family: k_li, k_gather_li and k_probe_li<INTEG, TRAV> ----
  * The traversals the per-ray kernels are instantiated for: TravsLi those of k_features and of the k_li-shaped kernels of
  * MIS and RR, TravsN1 those of path, PBR and NEE (the media kernel also serves the reference-order walk),
- * TravsTop those of the kernels that also walk a top tree (k_query_*, k_gather_any). */
+ * TravsTop those of the kernels that also walk a top tree (k_query_*, k_gather_any, k_probe_any). */
 using TravsLi = TravSet<RT_TRAV_FAST, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA, RT_TRAV_EXACT>;
 using TravsN1 = TravSet<RT_TRAV_FAST, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA>;
 using TravsTop = TravSet<RT_TRAV_FAST, RT_TRAV_TOP, RT_TRAV_PROGRAM_EXT, RT_TRAV_MEDIA, RT_TRAV_EXACT>;

@@ -429,7 +429,7 @@ void rtr_destroy(rtr_context* c) {
     for (DevBuf& b : c->sb)
         if (b.p) hipFree(b.p);
     DevBuf* bufs[] = {&c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise,
-                      &c->b_query, &c->b_gather, &c->b_display, &c->b_display_io};
+                      &c->b_query, &c->b_gather, &c->b_probe, &c->b_display, &c->b_display_io};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     c->pool.release();

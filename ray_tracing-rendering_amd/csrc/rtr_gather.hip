@@ -27,13 +27,7 @@ int launch_gather(rtr_context* c, Kern kernel, const DScene& ds, const GatherK& 
 
 /* RTR_OK, or RTR_ERR_INVALID with the reason in `err` */
 int gather_params_check(const rtr_gather_params* p, std::string& err) {
-    const char* why = nullptr;
-    if (!p) why = "null gather params";
-    else if (p->samples < 1 || p->samples > (1 << 20)) why = "samples outside 1 .. 2^20";
-    else if (p->flags & ~RTR_FLAG_REFERENCE_ORDER) why = "unknown flag bits";
-    else if (!__builtin_isfinite(p->time) || !__builtin_isfinite(p->t_min)) why = "time or t_min not finite";
-    else if (p->t_max != p->t_max) why = "t_max is NaN";
-    else if (p->reserved[0] != 0 || p->reserved[1] != 0) why = "reserved must be 0";
+    const char* why = gather_params_why(p);
     if (!why) return RTR_OK;
     err = std::string("rtr_gather_*: ") + why;
     return RTR_ERR_INVALID;

@@ -29,6 +29,11 @@
  *                                   through Renderer::closest_hits, then Renderer::ambient_occlusion casts N hemisphere rays
  *                                   of length D (default: unbounded) at every hit's (p, n); a pixel is count / N grey, 1.0
  *                                   where the centre ray misses, stored like a render.  Not with --pick, --adaptive, --turntable
+ *           [--probes NX,NY,NZ --probe-box x0,y0,z0,x1,y1,z1 [--probe-samples N]]   nothing is path-traced per pixel: a grid of
+ *                                   NX x NY x NZ light probes whose first and last stand on the box corners (an axis with one
+ *                                   probe: at the lower corner) goes through Renderer::light_probes with N (default 64) sphere
+ *                                   samples each under the integrator and --seed; one line per probe, x fastest: `valid count`
+ *                                   and the 27 coefficients c[i][channel] as %.17g.  Not with --pick, --ao, --adaptive, --turntable
  *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
  *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
  *                                   rtr_display_host through Renderer::display; with --turntable rtr_display_device on
@@ -174,6 +179,9 @@ int main(int argc, char** argv) {
     int pick_i = 0, pick_j = 0;
     int denoise_iter = -1, ao_samples = 0;
     double threshold = 0.0, ao_distance = 0.0; /* 0: unbounded */
+    int probe_dims[3] = {0, 0, 0}, probe_samples = 64;
+    double probe_box[6];
+    bool probes = false, probe_boxed = false, probe_sampled = false;
     std::vector<int> devices{0}, passes;
     unsigned seed = 1;
     std::string out;
@@ -259,6 +267,34 @@ int main(int argc, char** argv) {
             }
             ++k;
         }
+        else if (!std::strcmp(argv[k], "--probes") && k + 1 < argc) {
+            char tail = 0;
+            probes = std::sscanf(argv[++k], "%d,%d,%d%c", &probe_dims[0], &probe_dims[1], &probe_dims[2], &tail) == 3;
+            if (!probes || probe_dims[0] < 1 || probe_dims[1] < 1 || probe_dims[2] < 1 ||
+                (long long)probe_dims[0] * probe_dims[1] * probe_dims[2] > (1ll << 24)) {
+                std::cerr << "--probes takes NX,NY,NZ, each >= 1 with a product <= 16777216, not " << argv[k] << "\n";
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--probe-box") && k + 1 < argc) {
+            char tail = 0;
+            double* b = probe_box;
+            probe_boxed = std::sscanf(argv[++k], "%lf,%lf,%lf,%lf,%lf,%lf%c", b, b + 1, b + 2, b + 3, b + 4, b + 5, &tail) == 6;
+            for (int a = 0; a < 6; ++a) probe_boxed = probe_boxed && std::isfinite(b[a]);
+            if (!probe_boxed) {
+                std::cerr << "--probe-box takes six finite numbers x0,y0,z0,x1,y1,z1, not " << argv[k] << "\n";
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--probe-samples") && k + 1 < argc) {
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (end == argv[k] || *end != '\0' || v < 1 || v > (1 << 20)) {
+                std::cerr << "--probe-samples: N must be an integer in 1..1048576, not " << argv[k] << "\n";
+                return 2;
+            }
+            probe_samples = (int)v, probe_sampled = true;
+        }
         else if (!std::strcmp(argv[k], "--spp-min") && k + 1 < argc) {
             spp_min = std::atoi(argv[++k]);
             if (spp_min < 1) {
@@ -318,6 +354,24 @@ int main(int argc, char** argv) {
         std::cerr << "--ao excludes --pick, --adaptive and --turntable\n";
         return 2;
     }
+    if ((probe_boxed || probe_sampled) && !probes) {
+        std::cerr << "--probe-box and --probe-samples go with --probes\n";
+        return 2;
+    }
+    if (probes && !probe_boxed) {
+        std::cerr << "--probes needs --probe-box\n";
+        return 2;
+    }
+    if (probes && (pick || ao_samples || adaptive || turntable_frames)) {
+        std::cerr << "--probes excludes --pick, --ao, --adaptive and --turntable\n";
+        return 2;
+    }
+    if (probes)
+        for (int a = 0; a < 3; ++a)
+            if (probe_dims[a] > 1 && !(probe_box[3 + a] > probe_box[a])) {
+                std::cerr << "--probe-box: the upper corner must lie above the lower one on every axis with more than one probe\n";
+                return 2;
+            }
     if (display && pick) {
         std::cerr << "the display options exclude --pick\n";
         return 2;
@@ -434,6 +488,36 @@ int main(int argc, char** argv) {
     renderer.set_max_depth(50); /* main.cpp:102 */
     renderer.set_seed(seed);
     renderer.set_progress_bands(bands);
+    if (probes) {
+        if (renderer.upload_scene(config.world, cam, config.background, config.lights) != RTR_OK) {
+            std::cerr << "upload failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        std::vector<point3> points;
+        for (int iz = 0; iz < probe_dims[2]; ++iz)
+            for (int iy = 0; iy < probe_dims[1]; ++iy)
+                for (int ix = 0; ix < probe_dims[0]; ++ix) {
+                    const int idx[3] = {ix, iy, iz};
+                    double p[3];
+                    for (int a = 0; a < 3; ++a) {
+                        const double sp = probe_dims[a] > 1 ? (probe_box[3 + a] - probe_box[a]) / (double)(probe_dims[a] - 1) : 1.0;
+                        p[a] = probe_box[a] + (double)idx[a] * sp;
+                    }
+                    points.emplace_back(p[0], p[1], p[2]);
+                }
+        const std::vector<rtr_probe_sh> sh = renderer.light_probes(points, probe_samples, seed);
+        if (sh.size() != points.size()) {
+            std::cerr << "light probes failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        for (const rtr_probe_sh& r : sh) {
+            std::printf("%d %d", r.valid, r.count);
+            for (int i = 0; i < 9; ++i)
+                for (int ch = 0; ch < 3; ++ch) std::printf(" %.17g", r.c[i][ch]);
+            std::printf("\n");
+        }
+        return 0;
+    }
     for (int r = 0; r < repeat; ++r) { /* a second call finds the flattened scene on the GPUs */
         if (adaptive) {
             auto t = std::chrono::high_resolution_clock::now();

@@ -424,6 +424,52 @@ class Renderer {
         return gather(points, normals, samples, infinity, seed, true);
     }
 
+    /* Light probes (include/rtr_hip.h: rtr_probe_*), on the first context and the scene uploaded there.  light_probes:
+     * Integrator::Li of `samples` rays uniform over the sphere from every point under the integrator set on this renderer,
+     * as nine spherical-harmonic coefficients per channel.  probe_irradiance: irradiance at (points, normals) from such
+     * records on a regular grid (rtr_probe_lookup; needs no scene).  An empty vector and last_status() / last_error() on
+     * failure. */
+    std::vector<rtr_probe_sh> light_probes(const std::vector<point3>& points, int samples = 64, unsigned seed = 0) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if (!m_integrator) m_error = "no integrator set", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_probe_sh> out(points.size());
+        if (m_status == RTR_OK) {
+            std::vector<rtr_probe_point> pts(points.size());
+            for (size_t k = 0; k < points.size(); ++k)
+                for (int a = 0; a < 3; ++a) pts[k].p[a] = points[k][a];
+            rtr_gather_params gp;
+            rtr_gather_defaults(&gp);
+            gp.samples = samples, gp.seed = seed;
+            const rtr_render_params rp = base_params(2, 2); /* integrator and depths; no image is involved */
+            if ((m_status = rtr_probe_radiance(m_ctx[0], &rp, &gp, pts.data(), out.data(), (int64_t)pts.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+    std::vector<rtr_gather_out> probe_irradiance(const rtr_probe_grid& grid, const std::vector<rtr_probe_sh>& probes,
+                                                 const std::vector<point3>& points, const std::vector<vec3>& normals) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if (points.size() != normals.size()) m_error = "one normal per point", m_status = RTR_ERR_INVALID;
+        else if (grid.dims[0] < 1 || grid.dims[1] < 1 || grid.dims[2] < 1 ||
+                 (long long)grid.dims[0] * grid.dims[1] * grid.dims[2] != (long long)probes.size())
+            m_error = "one probe record per grid point", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_gather_out> out(points.size());
+        if (m_status == RTR_OK) {
+            std::vector<rtr_gather_point> q(points.size());
+            for (size_t k = 0; k < points.size(); ++k)
+                for (int a = 0; a < 3; ++a) q[k].p[a] = points[k][a], q[k].n[a] = normals[k][a];
+            if ((m_status = rtr_probe_lookup(m_ctx[0], &grid, probes.data(), q.data(), out.data(), (int64_t)q.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+
     /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
      * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
      * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */

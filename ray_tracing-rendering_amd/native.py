@@ -31,11 +31,14 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_display_defaults", "rtr_display_srgb_thresholds", "rtr_display_histogram", "rtr_display_host",
            "rtr_display_device", "rtr_accum_resolve_device", "rtr_accum_features_device", "rtr_accum_denoise_device",
            "rtr_accum_denoise_temporal_device", "rtr_gather_defaults", "rtr_gather_occlusion", "rtr_gather_radiance",
-           "rtr_gather_occlusion_device", "rtr_gather_radiance_device", "rtr_gather_ray")
+           "rtr_gather_occlusion_device", "rtr_gather_radiance_device", "rtr_gather_ray",
+           "rtr_probe_visibility", "rtr_probe_radiance", "rtr_probe_visibility_device", "rtr_probe_radiance_device",
+           "rtr_probe_ray", "rtr_sh_basis", "rtr_sh_irradiance", "rtr_probe_lookup", "rtr_probe_lookup_device",
+           "rtr_probe_lookup_one")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
-                "rtr_test_last_gather",
+                "rtr_test_last_gather", "rtr_test_last_probe",
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
                 "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
@@ -59,6 +62,11 @@ class KernelRecordC(C.Structure):
 class GatherRecordC(C.Structure):
     """rtr_gather_record of include/rtr_hip_test.h"""
     _fields_ = [(name, C.c_int32) for name in ("integ", "trav", "broadcast", "lg")]
+
+
+class ProbeRecordC(C.Structure):
+    """rtr_probe_record of include/rtr_hip_test.h"""
+    _fields_ = [(name, C.c_int32) for name in ("integ", "trav", "lg")]
 
 
 class ScenePlanC(C.Structure):
@@ -178,6 +186,17 @@ def lib():
     L.rtr_gather_occlusion_device.argtypes = [vp, P(A.GatherParamsC), vp, vp, C.c_int64, C.c_int]
     L.rtr_gather_radiance_device.argtypes = [vp, P(A.RenderParamsC), P(A.GatherParamsC), vp, vp, C.c_int64, C.c_int]
     L.rtr_gather_ray.argtypes = [P(A.GatherParamsC), vp, C.c_int64, C.c_int32, vp]
+    L.rtr_probe_visibility.argtypes = [vp, P(A.GatherParamsC), vp, vp, C.c_int64]
+    L.rtr_probe_radiance.argtypes = [vp, P(A.RenderParamsC), P(A.GatherParamsC), vp, vp, C.c_int64]
+    L.rtr_probe_visibility_device.argtypes = [vp, P(A.GatherParamsC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_probe_radiance_device.argtypes = [vp, P(A.RenderParamsC), P(A.GatherParamsC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_probe_ray.argtypes = [P(A.GatherParamsC), vp, C.c_int64, C.c_int32, vp]
+    L.rtr_sh_basis.argtypes = [vp, vp]
+    L.rtr_sh_basis.restype = None
+    L.rtr_sh_irradiance.argtypes = [vp, vp, vp]
+    L.rtr_probe_lookup.argtypes = [vp, P(A.ProbeGridC), vp, vp, vp, C.c_int64]
+    L.rtr_probe_lookup_device.argtypes = [vp, P(A.ProbeGridC), vp, vp, vp, C.c_int64, C.c_int]
+    L.rtr_probe_lookup_one.argtypes = [P(A.ProbeGridC), vp, vp, vp]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -212,6 +231,7 @@ def test_lib():
     T.rtr_test_shared_division.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
     T.rtr_test_last_gather.argtypes = [vp, C.POINTER(GatherRecordC), C.c_size_t]
+    T.rtr_test_last_probe.argtypes = [vp, C.POINTER(ProbeRecordC), C.c_size_t]
     T.rtr_test_temporal_planes.argtypes = [vp] + [C.c_int32] * 6 + [C.POINTER(A.CameraC), C.POINTER(A.CameraC), C.c_int,
                                                                     C.POINTER(A.TemporalParamsC)] + [vp] * 8
     T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64,
@@ -398,6 +418,87 @@ def gather_rays(points, normals=None, params=None, **overrides):
             if rc != 0:
                 raise RtrError(rc, "rtr_gather_ray: bad params or bad point at index %d" % k)
     return rays
+
+
+def probe_points(points):
+    """A ``PROBE_POINT_DTYPE`` array from (n, 3) positions (or ``points`` already such an array)."""
+    if isinstance(points, np.ndarray) and points.dtype == A.PROBE_POINT_DTYPE:
+        return np.ascontiguousarray(points)
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    pts = np.zeros(len(p), dtype=A.PROBE_POINT_DTYPE)
+    pts["p"] = p
+    return pts
+
+
+def probe_rays(points, params=None, **overrides):
+    """rtr_probe_ray for every sample of every probe (host only, no context): the ``RAY_DTYPE`` rays [n, samples] the probe
+    kernels cast, uniform over the sphere, with the generator state after the direction's draws."""
+    L = lib()
+    gp = params if params is not None else gather_defaults(**overrides)
+    pts = probe_points(points)
+    n_s = int(gp.samples)
+    if not 1 <= n_s <= A.GATHER_MAX_SAMPLES:
+        raise RtrError(A.RTR_ERR_INVALID, "rtr_probe_ray: samples outside 1 .. 2^20")
+    rays = np.zeros((len(pts), n_s), dtype=A.RAY_DTYPE)
+    base, stride, size = pts.ctypes.data, A.PROBE_POINT_DTYPE.itemsize, A.RAY_DTYPE.itemsize
+    for k in range(len(pts)):
+        for s in range(n_s):
+            rc = L.rtr_probe_ray(C.byref(gp), base + k * stride, k, s, rays.ctypes.data + (k * n_s + s) * size)
+            if rc != 0:
+                raise RtrError(rc, "rtr_probe_ray: bad params or bad point at index %d" % k)
+    return rays
+
+
+def sh_basis(directions):
+    """rtr_sh_basis: the nine basis functions [..., 9] at the directions [..., 3] (taken as given: pass unit vectors)."""
+    d = np.ascontiguousarray(directions, dtype=np.float64)
+    flat = d.reshape(-1, 3)
+    y = np.zeros((len(flat), 9))
+    L = lib()
+    for k in range(len(flat)):
+        L.rtr_sh_basis(flat.ctypes.data + 24 * k, y.ctypes.data + 72 * k)
+    return y.reshape(d.shape[:-1] + (9,))
+
+
+def sh_irradiance(c, normals):
+    """rtr_sh_irradiance: irradiance [..., 3] of the normals [..., 3] under the coefficients ``c`` ([9, 3], the ``c`` of a
+    ``PROBE_SH_DTYPE`` record).  Raises RtrError for a bad normal."""
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if c.shape != (9, 3):
+        raise ValueError("c must be [9, 3]")
+    n = np.ascontiguousarray(normals, dtype=np.float64)
+    flat = n.reshape(-1, 3)
+    E = np.zeros((len(flat), 3))
+    L = lib()
+    for k in range(len(flat)):
+        rc = L.rtr_sh_irradiance(c.ctypes.data, flat.ctypes.data + 24 * k, E.ctypes.data + 24 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_sh_irradiance: bad normal at index %d" % k)
+    return E.reshape(n.shape)
+
+
+def probe_grid(origin, spacing, dims):
+    """An rtr_probe_grid: probe (ix, iy, iz) stands at origin + (ix, iy, iz) * spacing, index ix + dims[0] * (iy + dims[1] * iz)."""
+    g = A.ProbeGridC()
+    for a in range(3):
+        g.origin[a], g.spacing[a], g.dims[a] = float(origin[a]), float(spacing[a]), int(dims[a])
+    return g
+
+
+def probe_lookup_host(grid, probes, points, normals=None):
+    """rtr_probe_lookup_one for every query (host only, no context): a ``GATHER_OUT_DTYPE`` array.  Raises RtrError for a bad
+    grid or a bad query."""
+    L = lib()
+    probes = np.ascontiguousarray(probes, dtype=A.PROBE_SH_DTYPE)
+    if len(probes) != grid.dims[0] * grid.dims[1] * grid.dims[2]:
+        raise ValueError("probes must hold dims[0] * dims[1] * dims[2] records")
+    q = gather_points(points, normals)
+    out = np.zeros(len(q), dtype=A.GATHER_OUT_DTYPE)
+    for k in range(len(q)):
+        rc = L.rtr_probe_lookup_one(C.byref(grid), probes.ctypes.data, q.ctypes.data + 48 * k, out.ctypes.data + 32 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_probe_lookup_one: bad grid, or bad query at index %d" % k)
+    return out
 
 
 def srgb_thresholds():
@@ -674,6 +775,74 @@ class Context:
         """The rays the gathers cast, ``RAY_DTYPE`` [n, samples], through rtr_gather_ray (``native.gather_rays``)."""
         return gather_rays(points, normals, params, **overrides)
 
+    # light probes (include/rtr_hip.h: rtr_probe_*)
+    @staticmethod
+    def _probe_out(out, n, dtype):
+        if out is None:
+            return np.zeros(n, dtype=dtype)
+        if out.dtype != dtype or len(out) < n or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous array of at least %d probe records" % n)
+        return out
+
+    def probe_visibility(self, points, samples=64, seed=0, t_max=np.inf, t_min=0.001, time=0.0, point_base=0,
+                         reference_order=False, params=None, out=None):
+        """rtr_probe_visibility: ``samples`` rays uniform over the sphere from every point, any-hit cast in [t_min, t_max],
+        the unblocked ones projected onto nine spherical harmonics and reduced on the device.  Returns a ``PROBE_VIS_DTYPE``
+        array (``c`` [9], ``count`` unblocked samples, ``valid`` 1).  Blocking; raises RtrError (RTR_ERR_INVALID) naming the
+        first bad point, with ``out`` untouched."""
+        gp = params if params is not None else gather_defaults(
+            samples=samples, seed=seed, t_max=t_max, t_min=t_min, time=time, point_base=point_base, reference_order=reference_order)
+        pts = probe_points(points)
+        out = self._probe_out(out, len(pts), A.PROBE_VIS_DTYPE)
+        self._chk(self._L.rtr_probe_visibility(self._h, C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
+        return out
+
+    def probe_radiance(self, params, points, samples=64, seed=0, time=0.0, point_base=0, gather_params=None, out=None):
+        """rtr_probe_radiance: ``Integrator::Li`` of ``samples`` rays uniform over the sphere from every point under
+        ``params`` (an rtr_render_params), projected onto nine spherical harmonics per channel.  Returns a
+        ``PROBE_SH_DTYPE`` array (``c`` [9, 3]); the coefficient estimate is 4 pi * c (``sh_irradiance`` applies it)."""
+        gp = gather_params if gather_params is not None else gather_defaults(samples=samples, seed=seed, time=time,
+                                                                             point_base=point_base)
+        pts = probe_points(points)
+        out = self._probe_out(out, len(pts), A.PROBE_SH_DTYPE)
+        self._chk(self._L.rtr_probe_radiance(self._h, C.byref(params), C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
+        return out
+
+    def probe_visibility_into(self, points_ptr, out_ptr, n, params=None, blocking=False, **overrides):
+        """rtr_probe_visibility_device: n ``PROBE_POINT_DTYPE`` records at device pointer ``points_ptr`` ->
+        ``PROBE_VIS_DTYPE`` records at ``out_ptr``, on the context stream behind what is queued there."""
+        gp = params if params is not None else gather_defaults(**overrides)
+        self._chk(self._L.rtr_probe_visibility_device(self._h, C.byref(gp), C.c_void_p(points_ptr), C.c_void_p(out_ptr), int(n),
+                                                      1 if blocking else 0))
+
+    def probe_radiance_into(self, params, points_ptr, out_ptr, n, gather_params=None, blocking=False, **overrides):
+        """rtr_probe_radiance_device: the device-pointer form of ``probe_radiance``."""
+        gp = gather_params if gather_params is not None else gather_defaults(**overrides)
+        self._chk(self._L.rtr_probe_radiance_device(self._h, C.byref(params), C.byref(gp), C.c_void_p(points_ptr),
+                                                    C.c_void_p(out_ptr), int(n), 1 if blocking else 0))
+
+    @staticmethod
+    def probe_rays(points, params=None, **overrides):
+        """The rays the probe kernels cast, ``RAY_DTYPE`` [n, samples], through rtr_probe_ray (``native.probe_rays``)."""
+        return probe_rays(points, params, **overrides)
+
+    def probe_lookup(self, grid, probes, points, normals=None, out=None):
+        """rtr_probe_lookup: irradiance at the queries (points, normals) from the ``PROBE_SH_DTYPE`` records of ``grid`` (an
+        rtr_probe_grid: ``native.probe_grid``), trilinear in the coefficients.  Returns a ``GATHER_OUT_DTYPE`` array
+        (``v`` the irradiance, ``count`` the corners used, ``valid``).  Blocking; needs no scene."""
+        probes = np.ascontiguousarray(probes, dtype=A.PROBE_SH_DTYPE)
+        if len(probes) != grid.dims[0] * grid.dims[1] * grid.dims[2]:
+            raise ValueError("probes must hold dims[0] * dims[1] * dims[2] records")
+        q = gather_points(points, normals)
+        out = self._gather_out(out, len(q))
+        self._chk(self._L.rtr_probe_lookup(self._h, C.byref(grid), probes.ctypes.data, q.ctypes.data, out.ctypes.data, len(q)))
+        return out
+
+    def probe_lookup_into(self, grid, probes_ptr, queries_ptr, out_ptr, n, blocking=False):
+        """rtr_probe_lookup_device: the same over device pointers, on the context stream behind what is queued there."""
+        self._chk(self._L.rtr_probe_lookup_device(self._h, C.byref(grid), C.c_void_p(probes_ptr), C.c_void_p(queries_ptr),
+                                                  C.c_void_p(out_ptr), int(n), 1 if blocking else 0))
+
     # display transform (include/rtr_hip.h: rtr_display_*)
     @staticmethod
     def _linear_image(linear):
@@ -774,6 +943,15 @@ class Context:
         if r.trav < 0:
             return None
         return {name: int(getattr(r, name)) for name, _ in GatherRecordC._fields_}
+
+    def last_probe(self):
+        """The probe kernel the last probe_visibility / probe_radiance call launched (include/rtr_hip_test.h:
+        rtr_probe_record), as a dict; None before any such call of this context launched one."""
+        r = ProbeRecordC()
+        self._chk(test_lib().rtr_test_last_probe(self._h, C.byref(r), C.sizeof(r)))
+        if r.trav < 0:
+            return None
+        return {name: int(getattr(r, name)) for name, _ in ProbeRecordC._fields_}
 
     def reference_order(self, on):
         """Force the reference-order traversal for rtr_test_hits (renders use params.flags)."""

@@ -356,6 +356,59 @@ class Renderer:
         return denoise_host(self._ctx, *summed, params=params, out=target_buffer.linear.copy())
 
 
+class ProbeGrid:
+    """A regular grid of radiance probes (include/rtr_hip.h: rtr_probe_grid and rtr_probe_sh records): ``dims`` probes from
+    ``origin`` every ``spacing``, probe (ix, iy, iz) at index ix + dims[0] * (iy + dims[1] * iz).  ``bake`` fills the
+    coefficients with rtr_probe_radiance, ``irradiance`` reads them with rtr_probe_lookup."""
+
+    def __init__(self, origin, spacing, dims, coefficients=None):
+        self.origin = np.asarray(origin, dtype=np.float64).reshape(3)
+        self.spacing = np.asarray(spacing, dtype=np.float64).reshape(3)
+        self.dims = tuple(int(d) for d in dims)
+        n = self.dims[0] * self.dims[1] * self.dims[2]
+        if len(self.dims) != 3 or min(self.dims) < 1 or n > A.PROBE_GRID_MAX:
+            raise ValueError("dims must be three counts >= 1 with a product <= 2^24")
+        if not (np.isfinite(self.origin).all() and np.isfinite(self.spacing).all() and (self.spacing > 0).all()):
+            raise ValueError("origin must be finite, spacing finite and > 0")
+        self.coefficients = np.zeros(n, dtype=A.PROBE_SH_DTYPE) if coefficients is None else \
+            np.ascontiguousarray(coefficients, dtype=A.PROBE_SH_DTYPE)
+        if len(self.coefficients) != n:
+            raise ValueError("coefficients must hold %d records" % n)
+        self._ctx = None
+
+    @classmethod
+    def in_box(cls, lo, hi, dims):
+        """The grid whose first and last probes stand on the corners ``lo`` and ``hi`` (an axis with one probe: at ``lo``)."""
+        lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+        steps = np.maximum(np.asarray(dims, dtype=np.float64) - 1.0, 1.0)
+        spacing = (hi - lo) / steps
+        return cls(lo, np.where(spacing > 0, spacing, 1.0), dims)
+
+    def positions(self):
+        """[n, 3] probe positions in index order: origin + (ix, iy, iz) * spacing"""
+        iz, iy, ix = np.meshgrid(*(np.arange(d, dtype=np.float64) for d in self.dims[::-1]), indexing="ij")
+        idx = np.stack([ix, iy, iz], axis=-1).reshape(-1, 3)
+        return self.origin + idx * self.spacing
+
+    def grid(self):
+        from . import native
+        return native.probe_grid(self.origin, self.spacing, self.dims)
+
+    def bake(self, ctx, params, samples=64, seed=0, time=0.0):
+        """rtr_probe_radiance at every probe under ``params`` (an rtr_render_params) on the scene ``ctx`` holds."""
+        self.coefficients = ctx.probe_radiance(params, self.positions(), samples=samples, seed=seed, time=time)
+        self._ctx = ctx
+        return self
+
+    def irradiance(self, points, normals, ctx=None):
+        """rtr_probe_lookup: [n, 3] irradiance at the queries; rows whose eight corners are all invalid are zero.  ``ctx``:
+        the context that runs it (default: the one that baked)."""
+        ctx = ctx if ctx is not None else self._ctx
+        if ctx is None:
+            raise ValueError("irradiance needs a context: bake first or pass ctx")
+        return ctx.probe_lookup(self.grid(), self.coefficients, points, normals)["v"]
+
+
 def check_denoise(params):
     """ValueError unless ``params`` is None or valid rtr_denoise_params (the checks of rtr_accum_denoise)."""
     import math
