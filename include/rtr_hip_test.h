@@ -2,8 +2,9 @@
  * rtr_hip_test.h -- entry points of librtr_hip_test.so, a SEPARATE library next to librtr_hip.so (it links against
  * it): device unit kernels that run the product's own device functions (csrc/rt_device.h) over golden-vector records
  * (include/rtr_testrec.h), one lane per record, plus counter-calibration and instruction-level checks, a unit
- * entry that runs the temporal kernels of the denoiser over caller-given planes (rtr_test_temporal_planes), and a
- * host-only entry that says what lowering makes of a scene and which kernel it would get (rtr_test_scene_plan).  They
+ * entry that runs the temporal kernels of the denoiser over caller-given planes (rtr_test_temporal_planes), three that
+ * hold the accumulator kernels to synthetic tile state (rtr_test_accum_load / _plan / _commit), and a host-only entry
+ * that says what lowering makes of a scene and which kernel it would get (rtr_test_scene_plan).  They
  * exist so tests can compare the HIP path with the oracle below the whole-image level; none of this code is in the
  * product library, and a renderer integration only needs rtr_hip.h.
  */
@@ -217,6 +218,42 @@ int rtr_test_temporal_planes(rtr_context* ctx, int32_t width, int32_t height, in
                              const rtr_temporal_params* tp, const double* h_color, const double* h_q,
                              const int32_t* h_count, const double* h_feat, const double* h_hist_in,
                              double* h_c, double* h_var, double* h_hist_out);
+
+/* ---- the accumulator kernels (csrc/rt_accum_kernels.h) on synthetic tile state ----
+ *
+ * rtr_test_accum_load puts caller-given state into an accumulator of the product, so that its own binaries --
+ * k_accum_errors behind rtr_accum_errors, k_accum_resolve and the host scatter loops behind rtr_accum_resolve / _moments,
+ * k_accum_resolve_scatter behind rtr_accum_resolve_device, and k_accum_plan / k_accum_commit inside rtr_accum_refine -- run
+ * on sums, moments and counts no render produces:
+ *   sum    [n][3][256] doubles: per owned tile (order of rtr_accum_tiles) the three channel planes, lane = 16 * row + column
+ *          of the tile, row 0 its lowest; EVERY lane is given, those outside the region included
+ *   q      [n][256] doubles, same lanes; required exactly when the accumulator keeps moments (else NULL)
+ *   count  [n] ints >= 0
+ *   n      the number of owned tiles
+ * Waits for the context's stream, copies, and sets the library's host copy of the counts; runs no kernel.  The state is
+ * what the next rtr_accum_* call sees; a pass continues the loaded sums.  RTR_ERR_INVALID, before any device work, for a
+ * NULL array, a wrong n, a negative count, or a q that does not match the moments flag. */
+int rtr_test_accum_load(rtr_context* ctx, rtr_accum* acc, const double* sum, const double* q, const int32_t* count, int64_t n);
+
+/* k_accum_plan alone, launched as a pass launches it (one workgroup of 1024 threads), over HOST arrays of n tiles:
+ * count[n], err[n] (read in mode 2 only) and tile_s1[n] (in: the targets of mode 0; out: the targets of every mode).
+ * mode 0: targets as given; 1: max(count, spp); 2: the refinement rule of rtr_accum_refine with spp_min, spp_max and
+ * threshold.  active[n] receives the list of the slots with target > count -- its first *n_active entries, the most
+ * pending samples first by floor(log2(target - count)), any order inside such a bucket; the entry fills the list with -1
+ * before the launch, so the entries from *n_active on read -1.  Nothing is rendered: counts and targets may be as large
+ * as INT32_MAX.  Needs no scene.  Blocking.  RTR_ERR_INVALID for a NULL pointer, n < 1 or an unknown mode. */
+int rtr_test_accum_plan(rtr_context* ctx, int64_t n, int32_t mode, int32_t spp, int32_t spp_min, int32_t spp_max,
+                        double threshold, const int32_t* count, const double* err, int32_t* tile_s1, int32_t* active,
+                        int32_t* n_active);
+
+/* k_accum_commit alone, one workgroup per tile as behind a pass, over HOST arrays of n tiles: workgroup b < n_active takes
+ * the slot active[b] and, where done[slot] is nonzero, copies partial[slot] ([n][3][256]) into sum, q_part[slot] ([n][256])
+ * into q and tile_s1[slot] into count[slot]; every other slot of sum, q and count keeps every byte.  q and q_part are both
+ * NULL (an accumulator without moments) or both given.  Needs no scene.  Blocking.  RTR_ERR_INVALID for a NULL pointer,
+ * n < 1, n_active outside [0, n] or an entry of active[0 .. n) outside [0, n). */
+int rtr_test_accum_commit(rtr_context* ctx, int64_t n, const int32_t* active, int32_t n_active, const int32_t* done,
+                          const int32_t* tile_s1, const double* partial, const double* q_part, double* sum, double* q,
+                          int32_t* count);
 
 #ifdef __cplusplus
 }

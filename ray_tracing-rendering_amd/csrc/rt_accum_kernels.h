@@ -1,6 +1,6 @@
 /*
  * rt_accum_kernels.h -- the non-template kernels of the progressive accumulators (rtr_accum_*); rtr_accum.hip includes
- * them, and no other unit.
+ * them for the product, and rtr_test.hip for the test library's own copies of k_accum_plan and k_accum_commit.
  *  k_accum_commit / k_accum_resolve(_scatter)   keep the sums of the tiles a pass finished, and turn sums + per-tile
  *                  sample counts into linear mean radiance and the 8-bit store.
  *  k_accum_errors / k_accum_plan   adaptive sampling: per-tile noise estimates from sums + second moments, and the
@@ -29,7 +29,10 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_accum_commit(const RenderK P, dou
 
 /* rtr_accum_errors / rtr_accum_refine: one workgroup per owned tile, the largest per-pixel error of the tile's pixels
  * inside the region (include/rtr_hip.h); +inf below 2 samples.  Only + - * / sqrt max: a numpy restatement gives the
- * same bits. */
+ * same bits.  The header's max(a, b) is `a > b ? a : b` with the varying operand as a: a NaN difference gives var = 0 and
+ * a NaN or negative y_m the floor 1e-4, so no pixel's error is NaN whatever the sums hold (+inf where Q is +inf over finite
+ * sums) and the `>` folds below are a plain maximum; a tile whose pixels all have error 0 reports +0.0.  What the lanes
+ * outside the region hold is never read. */
 __global__ void __launch_bounds__(RTR_BLOCK) k_accum_errors(const AccumResolveK R, const double* __restrict__ q,
                                                             double* __restrict__ err) {
     __shared__ double wmax[RTR_BLOCK / 64];
@@ -71,7 +74,10 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_accum_errors(const AccumResolveK 
  *   mode 0  tile_s1 as given (rtr_accum_render_tiles uploaded it)
  *   mode 1  max(count, spp) (rtr_accum_render)
  *   mode 2  the refinement rule of rtr_accum_refine on err: count < spp_min -> spp_min; err > threshold and count <
- *           spp_max -> min(spp_max, 2 * count); else count */
+ *           spp_max -> min(spp_max, 2 * count); else count.  `err > threshold` is false at equality and for a NaN err
+ *           (such a tile stops once it holds spp_min), true for +inf; the minimum is exact up to spp_max = INT32_MAX; a
+ *           count above spp_max stays.
+ * The slots of `active` from *n_active on are not written. */
 struct AccumPlanK {
     int n_tiles, mode;
     const int* count;
@@ -119,7 +125,9 @@ __global__ void __launch_bounds__(1024) k_accum_plan(const AccumPlanK K) {
 }
 
 /* rtr_accum_resolve: (1 / count) * sum, the expression of k_resolve, and the reference's store of it
- * (renderer.h:126-140: sqrt gamma, clamp to [0, 1]; render_buffer.h:35-55: uchar(c * 255) truncation) */
+ * (renderer.h:126-140: sqrt gamma, clamp to [0, 1]; render_buffer.h:35-55: uchar(c * 255) truncation).  A mean above 1
+ * or +inf stores 255 and -0.0 stores 0; the byte of a NaN or negative mean (sqrt: NaN) is unspecified, as the reference's
+ * cast of a NaN is, but the same here and in k_accum_resolve_scatter */
 __global__ void __launch_bounds__(RTR_BLOCK) k_accum_resolve(const AccumResolveK R) {
     const int n = R.count[blockIdx.x];
     if (n == 0) return; /* wave-uniform: the host leaves such a tile alone */

@@ -74,4 +74,11 @@ int rtr_debug_last_gather(rtr_context* ctx, rtr_debug_gather* out, size_t size_o
 int rtr_debug_last_probe(rtr_context* ctx, rtr_debug_probe* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);
 void rtr_debug_set_error(rtr_context* ctx, const char* msg); /* rtr_last_error() of a failing rtr_test_* call */
+/* Synthetic state into an accumulator, so that the product's own k_accum_errors / _plan / _commit / _resolve(_scatter) run on
+ * sums, moments and counts no render produces: sum [n][3][RTR_BLOCK] and q [n][RTR_BLOCK] doubles in the tile layout of
+ * d_sum / d_q (every lane of a tile, those outside the region included), count [n] ints >= 0, n the number of owned
+ * tiles; q exactly when the accumulator keeps moments.  Waits for the context's stream, copies the arrays and sets the
+ * host copy of the counts; no kernel.  RTR_ERR_INVALID, before any device work, for a NULL array, a wrong n, a negative
+ * count or a q that does not match the moments flag. */
+int rtr_debug_accum_load(rtr_context* ctx, rtr_accum* acc, const double* sum, const double* q, const int32_t* count, int64_t n);
 }

@@ -159,6 +159,28 @@ int accum_clear(rtr_context* c, rtr_accum* a) {
 
 extern "C" {
 
+/* the seam of rt_debug.h: caller-given sums, moments and counts in place of what accum_clear zeroes */
+int rtr_debug_accum_load(rtr_context* c, rtr_accum* a, const double* sum, const double* q, const int32_t* count, int64_t n) {
+    if (!c) return RTR_ERR_INVALID;
+    if (int rc = accum_check(c, a)) return rc;
+    if (!sum || !count) return fail(c, RTR_ERR_INVALID, "null sum or count");
+    if ((q != nullptr) != a->moments) return fail(c, RTR_ERR_INVALID, "q must be given exactly when the accumulator keeps moments");
+    if (n != (int64_t)a->tiles.size()) return fail(c, RTR_ERR_INVALID, "n is not the number of owned tiles");
+    for (int64_t k = 0; k < n; ++k)
+        if (count[k] < 0) return fail(c, RTR_ERR_INVALID, "negative sample count");
+    if (n == 0) return RTR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* its queued passes */
+    const size_t m = (size_t)n;
+    HIPCHK(c, hipMemcpyAsync(a->d_sum.p, sum, m * 3 * RTR_BLOCK * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (q) HIPCHK(c, hipMemcpyAsync(a->d_q.p, q, m * RTR_BLOCK * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(a->d_count.p, count, m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the arrays are the caller's */
+    a->h_counts.assign(count, count + m);
+    a->counts_stale = false;
+    return RTR_OK;
+}
+
 int rtr_accum_create(rtr_context* c, const rtr_render_params* p, rtr_accum** out) { return rtr_accum_create_ex(c, p, 0, out); }
 
 int rtr_accum_create_ex(rtr_context* c, const rtr_render_params* p, uint32_t accum_flags, rtr_accum** out) {

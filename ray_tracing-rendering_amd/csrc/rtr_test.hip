@@ -2,7 +2,9 @@
  * rtr_test.hip -- librtr_hip_test.so: the entry points of include/rtr_hip_test.h.  Test infrastructure, built next to
  * librtr_hip.so and linked against it; it reaches a context only through the seam of csrc/rt_debug.h.
  */
-/* (a link unit of its own: rtr_test_temporal_planes launches its own copy of k_temporal_blend / _store) */
+/* (a link unit of its own: rtr_test_temporal_planes launches its own copy of k_temporal_blend / _store, rtr_test_accum_plan
+ * and rtr_test_accum_commit theirs of k_accum_plan and k_accum_commit) */
+#include "rt_accum_kernels.h"
 #include "rt_debug.h"
 #include "rt_image_kernels.h"
 #include "rt_launch.h"
@@ -538,6 +540,97 @@ int rtr_test_temporal_planes(rtr_context* c, int32_t width, int32_t height, int3
         for (int k = 0; k < 3; ++k) h_c[3 * p + k] = cc[p + k * np];
         h_var[p] = vv[p];
     }
+    return RTR_OK;
+}
+
+int rtr_test_accum_load(rtr_context* c, rtr_accum* acc, const double* sum, const double* q, const int32_t* count, int64_t n) {
+    return rtr_debug_accum_load(c, acc, sum, q, count, n);
+}
+
+/* k_accum_plan of the product on caller-given counts, errors and targets: the launch of accum_pass_plan (rtr_accum.hip) */
+int rtr_test_accum_plan(rtr_context* c, int64_t n, int32_t mode, int32_t spp, int32_t spp_min, int32_t spp_max, double threshold,
+                        const int32_t* count, const double* err, int32_t* tile_s1, int32_t* active, int32_t* n_active) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!count || !err || !tile_s1 || !active || !n_active) return fail(c, RTR_ERR_INVALID, "null argument");
+    if (n < 1 || n > ((int64_t)1 << 24)) return fail(c, RTR_ERR_INVALID, "need 1 <= n <= 2^24 tiles");
+    if (mode < 0 || mode > 2) return fail(c, RTR_ERR_INVALID, "unknown plan mode");
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc) return rc;
+    const size_t m = (size_t)n;
+    if ((rc = ensure(c, *t, m * sizeof(double) + (3 * m + 1) * sizeof(int)))) return rc;
+    double* d_err = static_cast<double*>(t->buf);
+    int* d_count = reinterpret_cast<int*>(d_err + m);
+    int* d_s1 = d_count + m;
+    int* d_active = d_s1 + m;
+    int* d_nactive = d_active + m;
+    std::vector<int> minus(m + 1, -1); /* the slots of the list the kernel does not write stay -1 */
+    TCHK(c, hipMemcpy(d_err, err, m * sizeof(double), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_count, count, m * sizeof(int), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_s1, tile_s1, m * sizeof(int), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_active, minus.data(), (m + 1) * sizeof(int), hipMemcpyHostToDevice));
+    AccumPlanK K{};
+    K.n_tiles = (int)n, K.mode = mode;
+    K.count = d_count, K.err = d_err, K.tile_s1 = d_s1, K.active = d_active, K.n_active = d_nactive;
+    K.spp = spp, K.spp_min = spp_min, K.spp_max = spp_max, K.threshold = threshold;
+    hipLaunchKernelGGL(k_accum_plan, dim3(1), dim3(1024), 0, stream, K);
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream));
+    TCHK(c, hipMemcpy(tile_s1, d_s1, m * sizeof(int), hipMemcpyDeviceToHost));
+    TCHK(c, hipMemcpy(active, d_active, m * sizeof(int), hipMemcpyDeviceToHost));
+    TCHK(c, hipMemcpy(n_active, d_nactive, sizeof(int), hipMemcpyDeviceToHost));
+    return RTR_OK;
+}
+
+/* k_accum_commit of the product over caller-given pass results: the launch of accum_pass_commit (rtr_accum.hip) */
+int rtr_test_accum_commit(rtr_context* c, int64_t n, const int32_t* active, int32_t n_active, const int32_t* done,
+                          const int32_t* tile_s1, const double* partial, const double* q_part, double* sum, double* q, int32_t* count) {
+    if (!c) return RTR_ERR_INVALID;
+    if (!active || !done || !tile_s1 || !partial || !sum || !count) return fail(c, RTR_ERR_INVALID, "null argument");
+    if ((q == nullptr) != (q_part == nullptr)) return fail(c, RTR_ERR_INVALID, "q and q_part go together");
+    if (n < 1 || n > ((int64_t)1 << 20)) return fail(c, RTR_ERR_INVALID, "need 1 <= n <= 2^20 tiles");
+    if (n_active < 0 || n_active > n) return fail(c, RTR_ERR_INVALID, "need 0 <= n_active <= n");
+    for (int64_t k = 0; k < n; ++k)
+        if (active[k] < 0 || active[k] >= n) return fail(c, RTR_ERR_INVALID, "active slot out of range");
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc) return rc;
+    const size_t m = (size_t)n, ns = m * 3 * RTR_BLOCK, nq = m * RTR_BLOCK;
+    if ((rc = ensure(c, *t, (2 * ns + 2 * nq) * sizeof(double) + (4 * m + 1) * sizeof(int)))) return rc;
+    double* d_partial = static_cast<double*>(t->buf);
+    double* d_qpart = d_partial + ns;
+    double* d_sum = d_qpart + nq;
+    double* d_q = d_sum + ns;
+    int* d_active = reinterpret_cast<int*>(d_q + nq);
+    int* d_done = d_active + m;
+    int* d_s1 = d_done + m;
+    int* d_count = d_s1 + m;
+    int* d_nactive = d_count + m;
+    TCHK(c, hipMemcpy(d_partial, partial, ns * sizeof(double), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_sum, sum, ns * sizeof(double), hipMemcpyHostToDevice));
+    if (q) {
+        TCHK(c, hipMemcpy(d_qpart, q_part, nq * sizeof(double), hipMemcpyHostToDevice));
+        TCHK(c, hipMemcpy(d_q, q, nq * sizeof(double), hipMemcpyHostToDevice));
+    }
+    TCHK(c, hipMemcpy(d_active, active, m * sizeof(int), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_done, done, m * sizeof(int), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_s1, tile_s1, m * sizeof(int), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_count, count, m * sizeof(int), hipMemcpyHostToDevice));
+    TCHK(c, hipMemcpy(d_nactive, &n_active, sizeof(int), hipMemcpyHostToDevice));
+    RenderK P{};
+    P.n_tiles = (int)n, P.chunks = 1;
+    P.partial = d_partial, P.q_part = q ? d_qpart : nullptr;
+    P.done = d_done, P.tile_s1 = d_s1, P.active = d_active, P.n_active = d_nactive;
+    hipLaunchKernelGGL(k_accum_commit, dim3((unsigned)n), dim3(RTR_BLOCK), 0, stream, P, d_sum, q ? d_q : nullptr, d_count);
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream));
+    TCHK(c, hipMemcpy(sum, d_sum, ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (q) TCHK(c, hipMemcpy(q, d_q, nq * sizeof(double), hipMemcpyDeviceToHost));
+    TCHK(c, hipMemcpy(count, d_count, m * sizeof(int), hipMemcpyDeviceToHost));
     return RTR_OK;
 }
 

@@ -42,7 +42,8 @@ TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_t
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
                 "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
-                "rtr_test_pow5_host", "rtr_test_udiv", "rtr_test_scene_consts")
+                "rtr_test_pow5_host", "rtr_test_udiv", "rtr_test_scene_consts", "rtr_test_accum_load",
+                "rtr_test_accum_plan", "rtr_test_accum_commit")
 _TEST_LIB = None
 
 
@@ -244,6 +245,9 @@ def test_lib():
     T.rtr_test_queue_pack_host.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     T.rtr_test_udiv.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_scene_consts.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int32)]
+    T.rtr_test_accum_load.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
+    T.rtr_test_accum_plan.argtypes = [vp, C.c_int64] + [C.c_int32] * 4 + [C.c_double, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+    T.rtr_test_accum_commit.argtypes = [vp, C.c_int64, vp, C.c_int32] + [vp] * 7
     _TEST_LIB = T
     return T
 
@@ -1047,6 +1051,44 @@ class Context:
             hist.ctypes.data, c.ctypes.data, var.ctypes.data, new.ctypes.data))
         return c, var, new
 
+    def accum_plan(self, count, err, tile_s1, mode, spp=0, spp_min=1, spp_max=1, threshold=1.0):
+        """rtr_test_accum_plan (include/rtr_hip_test.h): k_accum_plan alone over n tiles.  Returns (targets (n,) int32, the
+        active list (n,) int32 with -1 from ``n_active`` on, n_active)."""
+        count = np.ascontiguousarray(count, dtype=np.int32)
+        err = np.ascontiguousarray(err, dtype=np.float64)
+        s1 = np.array(tile_s1, dtype=np.int32, order="C")
+        if count.ndim != 1 or err.shape != count.shape or s1.shape != count.shape:
+            raise ValueError("count, err and tile_s1 of one shape (n,) expected")
+        active = np.full(len(count), -1, dtype=np.int32)
+        na = C.c_int32(-1)
+        self._chk(test_lib().rtr_test_accum_plan(self._h, len(count), int(mode), int(spp), int(spp_min), int(spp_max),
+                                                 float(threshold), count.ctypes.data, err.ctypes.data, s1.ctypes.data,
+                                                 active.ctypes.data, C.byref(na)))
+        return s1, active, int(na.value)
+
+    def accum_commit(self, active, n_active, done, tile_s1, partial, q_part, sum, q, count):
+        """rtr_test_accum_commit (include/rtr_hip_test.h): k_accum_commit alone over n tiles; ``partial`` and ``sum`` (n, 3,
+        256), ``q_part`` and ``q`` (n, 256) or both None.  Returns (sum, q, count) after the kernel, as new arrays."""
+        ints = [np.ascontiguousarray(a, dtype=np.int32) for a in (active, done, tile_s1)]
+        n = len(ints[0])
+        partial = np.ascontiguousarray(partial, dtype=np.float64)
+        sum_ = np.array(sum, dtype=np.float64, order="C")
+        cnt = np.array(count, dtype=np.int32, order="C")
+        if any(a.shape != (n,) for a in ints) or cnt.shape != (n,) or partial.shape != (n, 3, 256) or sum_.shape != (n, 3, 256):
+            raise ValueError("n tiles: int arrays (n,), partial and sum (n, 3, 256) expected")
+        if (q is None) != (q_part is None):
+            raise ValueError("q and q_part go together")
+        qq = qp = None
+        if q is not None:
+            qp = np.ascontiguousarray(q_part, dtype=np.float64)
+            qq = np.array(q, dtype=np.float64, order="C")
+            if qp.shape != (n, 256) or qq.shape != (n, 256):
+                raise ValueError("q_part and q of shape (n, 256) expected")
+        self._chk(test_lib().rtr_test_accum_commit(
+            self._h, n, ints[0].ctypes.data, int(n_active), ints[1].ctypes.data, ints[2].ctypes.data, partial.ctypes.data,
+            None if qp is None else qp.ctypes.data, sum_.ctypes.data, None if qq is None else qq.ctypes.data, cnt.ctypes.data))
+        return sum_, qq, cnt
+
     def flat_hits(self, recs, with_uv=True):
         """rtr_test_flat_hits (include/rtr_hip_test.h): ``HIT_DTYPE`` records through the closest-hit cast of the flat
         kernels.  Returns (records, whether the scene has finish records); RtrError where no flat kernel runs the scene."""
@@ -1111,6 +1153,22 @@ class Accumulator:
         """One pass: every owned tile continues to ``spp_target`` samples (raises RtrError, RTR_ERR_CANCELLED
         after rtr_cancel: the tiles then hold their old or their new samples)."""
         self._ctx._chk(self._L.rtr_accum_render(self._ctx._h, self._handle(), int(spp_target), 1 if blocking else 0))
+
+    def load_state(self, sum, q, count):
+        """rtr_test_accum_load (include/rtr_hip_test.h, the test library): synthetic state into the accumulator -- ``sum``
+        (n, 3, 256) and ``q`` (n, 256; None without moments) float64 in the tile layout, every lane given, ``count`` (n,)
+        int32, n the owned tiles in the order of ``tiles()``."""
+        sum = np.ascontiguousarray(sum, dtype=np.float64)
+        count = np.ascontiguousarray(count, dtype=np.int32)
+        n = len(count)
+        if sum.shape != (n, 3, 256) or count.shape != (n,):
+            raise ValueError("sum of shape (n, 3, 256) and count of shape (n,) expected")
+        if q is not None:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            if q.shape != (n, 256):
+                raise ValueError("q of shape (n, 256) expected")
+        self._ctx._chk(test_lib().rtr_test_accum_load(self._ctx._h, self._handle(), sum.ctypes.data,
+                                                      None if q is None else q.ctypes.data, count.ctypes.data, n))
 
     def _out(self, out, dtype):
         h, w = self.shape
