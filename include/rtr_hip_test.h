@@ -198,6 +198,25 @@ int rtr_test_shared_division(rtr_context* ctx, uint64_t* mismatches, uint64_t* t
  * (quotients that differ in any bit, a NaN equal to a NaN) must be 0; *tested = n * m.  Needs no scene. */
 int rtr_test_udiv(rtr_context* ctx, const double* numerators, int64_t n, const double* divisors, int32_t m,
                   uint64_t* mismatches, uint64_t* tested);
+/* Shading takes 1.0 / d and sqrt(x) of a lane's own numbers through short forms when every lane of the wave holds an
+ * operand in the ordinary range, and through the compiler's expansion otherwise (rt_device.h: rcp_lane; sqrt_lane and
+ * sqrt_rcp_lane).  Each entry runs one kernel over 2^26 operands made from a counter -- random mantissas under every
+ * exponent of the accepted window, and in every fourth wave one lane with a value of rtr_test_lane_specials -- beside the
+ * compiler's result.  *mismatches (operands with a result that differs in any bit, NaN payloads included) must be 0;
+ * *tested = 2^26; *short_sets: how many operands sat in a wave that voted for the short form; first[0 .. 4): a mismatching
+ * operand, 0, its result and the expected result as bits, zeros when there is none.  Needs no scene. */
+int rtr_test_rcp_lane(rtr_context* ctx, uint64_t* mismatches, uint64_t* tested, uint64_t* short_sets, uint64_t* first);
+int rtr_test_sqrt_lane(rtr_context* ctx, uint64_t* mismatches, uint64_t* tested, uint64_t* short_sets, uint64_t* first);
+/* The edge values of those kernels as bits: every window bound, the smallest normal number and 2^1023 with their
+ * neighbours, zero, denormals, infinity, NaNs, the largest finite number and 1, each with both signs.  Fills out[0 .. min(cap,
+ * count)) and returns the count.  No GPU needed. */
+int rtr_test_lane_specials(uint64_t* out, int64_t cap);
+/* The host build of the short forms' arithmetic, the vote replaced by a flag per element: op 0: 1.0 / a, 1: sqrt(a).
+ * took_short[k] = the element was inside the window and went through the short form; the seeds of the host build are the
+ * correctly rounded reciprocal and reciprocal square root with their low coarse_bits bits cleared (0 .. 40; 29 is the
+ * accuracy the ISA manual gives v_rcp_f64 and v_rsq_f64).  Not thread-safe.  No GPU needed. */
+int rtr_test_lane_host(int32_t op, int32_t coarse_bits, const double* a, double* out, int32_t* took_short, int64_t n);
+
 /* The uploaded scene's table of shading constants (rt_device.h: SceneConsts, made on the device by rtr_upload_scene) as
  * 8-byte words -- 1 / n_lights, 0, pi, rcp_refined(pi); then per light len2(U), its refined reciprocal, len2(V), its refined
  * reciprocal, the `safe` flag in the low half of a word -- into `table`, and a second evaluation of the same expressions

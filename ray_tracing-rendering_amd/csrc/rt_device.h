@@ -35,9 +35,9 @@ typedef double Real;
  * the region that was current, then makes `id` current.  Counters live in LDS per wave and are added to
  * RenderK::stats[RT_PROF_BASE ...] when the workgroup ends.  The markers cost about a tenth of the wave's time
  * themselves: read the table as proportions.  In product builds RT_REGION() expands to nothing. */
-#define RT_STATS_WORDS 80 /* u64 words of RenderK::stats: 8 of the product + 2 x 34 region words, 4 spare */
+#define RT_STATS_WORDS 80 /* u64 words of RenderK::stats: 8 of the product + 2 x 36 region words */
 #define RT_PROF_BASE 8
-#define RT_PROF_REGIONS 34
+#define RT_PROF_REGIONS 36
 enum { RG_OTHER = 0, RG_SETUP = 1, RG_RECTS = 2, RG_SPHERES = 3, RG_GENERIC = 4, RG_TREE = 5, RG_LEAVES = 6, RG_FINISH = 7,
        RG_SH_SETUP = 8, RG_SH_RECTS = 9, RG_SH_SPHERES = 10, RG_SH_GENERIC = 11, RG_SH_TREE = 12, RG_SH_LEAVES = 13,
        RG_MEDIA = 14, RG_MATPREP = 15, RG_SHADE_A = 16, RG_SHADE_B = 17, RG_MISS = 18, RG_REGEN = 19, RG_SHADE_RR = 20,
@@ -45,7 +45,9 @@ enum { RG_OTHER = 0, RG_SETUP = 1, RG_RECTS = 2, RG_SPHERES = 3, RG_GENERIC = 4,
        RG_POLL = 27, RG_BEGIN = 28, RG_SETTLE = 29, RG_COUNT = 30, RG_REJECT = 31, /* the sample boundary of the lockstep loops, split */
        RG_EMIT_MIS = 32, /* shade_a_mis: the MIS weight of a BSDF-sampled ray that reached an emitter (compute_light_pdf) */
        RG_CAMDIV = 33,   /* camera_sample: the two divisions by the image size */
-       RG_N = 34 };
+       RG_LANE_DIV = 34,  /* shading: 1 / x of a lane's own divisor (rcp_lane and the reciprocal of sqrt_rcp_lane) */
+       RG_LANE_SQRT = 35, /* shading: square roots of a lane's own number (sqrt_lane; with its vote where one covers both) */
+       RG_N = 36 };
 #ifdef RTR_REGION_PROFILE
 __shared__ unsigned long long rt_prof_lds[4 * 2 * RT_PROF_REGIONS + 4 * 2]; /* [wave][cycles | visits][region], then [wave][last, current] */
 RT_DEV void rt_region(int id) {
@@ -72,6 +74,145 @@ RT_DEV int rt_region_current() { return (int)rt_prof_lds[4 * 2 * RT_PROF_REGIONS
 #define RT_INF (__builtin_huge_val())
 #define RT_PI 3.1415926535897932385 /* core/rtweekend.h:18 */
 
+/* ---- 1 / d and sqrt(x) of a lane's own numbers: short forms under a vote of the wave --------------------------------
+ * hipcc expands 1.0 / d into v_div_scale x 2, v_rcp_f64, four fma, a multiply, an fma, v_div_fmas and v_div_fixup, and
+ * __builtin_sqrt(x) into a compare, a select and v_ldexp before v_rsq_f64, two multiplies and seven fma, then a v_ldexp, a
+ * class compare and two selects.  For operands in the ordinary range the scales, the fixup and the rescale return their
+ * operand unchanged (see "IEEE division with a shared divisor" below), so the core alone gives the same bits:
+ *     rcp_short   rcp_refined(d), then fma(fma(-d, r, 1), r, r): the division's tail with the numerator 1, whose
+ *                 product 1 * r is r                                                   |d| in [2^-100, 2^100)
+ *     sqrt_short  the compiler's core, operand for operand and in its order.  It rescales x < 2^-767 (the literal of
+ *                 its first compare, 0x1000000000000000) and passes +-0 and +inf through (class mask 0x260); a negative
+ *                 x or a NaN goes through the core to a NaN.                            x in [2^-767, inf), x > 0
+ * Whether a wave may take the short form is a VOTE of the lanes that are there (rcp_lane, sqrt_lane, sqrt_rcp_lane): one
+ * lane outside the window sends the whole wave to the compiler's expansion, so zeros, denormals, infinities and NaNs
+ * (payloads included) get the plain result and lanes in range get the same bits either way.  Written per lane the compiler
+ * would compute both forms in every lane and select (profiles/r18_uniform_div.txt, (a)).  The windows are tested on the
+ * high dword with integer instructions -- an add and an unsigned compare against 32-bit numbers, and an `and` before them
+ * where either sign is allowed -- so no bound lives in a scalar register pair across the loop; the upper edge itself
+ * (2^100, 2^200) counts as outside.  A vote costs those two or three vector instructions and a scalar compare and branch,
+ * so a site gets one only where the short arm saves more.  The general quotient n / d does not: its short form saves three
+ * instructions and its two windows cost four to six; built into power_heuristic's blocks it measured x1.001, inside the
+ * spread, and was taken out again (profiles/r20_lane_div.txt).
+ * -DRTR_PLAIN_LANE_DIV gives the compiler's expansions everywhere; -DRTR_LANE_RCP=0 and -DRTR_LANE_SQRT=0 switch one
+ * kind off. */
+#ifdef RTR_PLAIN_LANE_DIV
+#define RTR_LANE_RCP 0
+#define RTR_LANE_SQRT 0
+#endif
+#ifndef RTR_LANE_RCP
+#define RTR_LANE_RCP 1
+#endif
+#ifndef RTR_LANE_SQRT
+#define RTR_LANE_SQRT 1
+#endif
+/* The seeds.  The host build (tests/test_lane_division_cpu.py) has no v_rcp_f64 / v_rsq_f64: it takes the correctly
+ * rounded value, with its low rt_host_seed_coarse bits cleared (0: as it is; 29: an error of up to 2^29 ulp, the accuracy
+ * the ISA manual gives both instructions). */
+inline int rt_host_seed_coarse = 0; /* host code only */
+RT_HD Real lane_seed_host(Real v) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, 8);
+    b &= ~((1ull << rt_host_seed_coarse) - 1);
+    __builtin_memcpy(&v, &b, 8);
+#endif
+    return v;
+}
+RT_HD Real rcp_seed(Real d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcp(d);
+#else
+    return lane_seed_host(1.0 / d);
+#endif
+}
+RT_HD Real rsq_seed(Real x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rsq(x);
+#else
+    return lane_seed_host(1.0 / __builtin_sqrt(x));
+#endif
+}
+RT_HD Real rcp_refined(Real d) {
+    Real r = rcp_seed(d);
+    Real e = __builtin_fma(-d, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-d, r, 1.0);
+    return __builtin_fma(r, e, r);
+}
+RT_HD Real rcp_short(Real d) {
+    const Real r = rcp_refined(d);
+    return __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+}
+RT_HD Real sqrt_short(Real x) {
+    const Real y = rsq_seed(x);
+    Real g = x * y;
+    Real h = y * 0.5;
+    const Real e = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, e, g);
+    h = __builtin_fma(h, e, h);
+    Real d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    return __builtin_fma(d, h, g);
+}
+/* x in [2^EMIN, 2^EMAX) in magnitude, decided on the high dword: zeros and denormals lie below every window, infinities
+ * and NaNs above.  SIGN 0: either sign; +1 / -1: only a positive / negative x is inside, which saves the `and` */
+template <int EMIN, int EMAX, int SIGN = 0>
+RT_HD bool lane_window(Real x) {
+    unsigned long long b;
+    __builtin_memcpy(&b, &x, 8);
+    const uint32_t hi = (uint32_t)(b >> 32) & (SIGN == 0 ? 0x7fffffffu : 0xffffffffu);
+    return hi - (((uint32_t)(1023 + EMIN) << 20) | (SIGN < 0 ? 0x80000000u : 0u)) < ((uint32_t)(EMAX - EMIN) << 20);
+}
+#define RT_SQRT_WINDOW(x) lane_window<-767, 1024, 1>(x)
+#define RT_UNIT_WINDOW(x) lane_window<-200, 200, 1>(x) /* sqrt(x) is then inside the reciprocal's window: one vote for both */
+/* 1.0 / d */
+template <int SIGN = 0>
+RT_DEV Real rcp_lane(Real d) {
+    const int region = RT_REGION_CURRENT();
+    RT_REGION(RG_LANE_DIV);
+    Real r;
+    if (RTR_LANE_RCP && __all(lane_window<-100, 100, SIGN>(d)))
+        r = rcp_short(d);
+    else
+        r = 1.0 / d;
+    RT_REGION(region);
+    return r;
+}
+RT_DEV Real sqrt_lane(Real x) {
+    const int region = RT_REGION_CURRENT();
+    RT_REGION(RG_LANE_SQRT);
+    Real s;
+    if (RTR_LANE_SQRT && __all(RT_SQRT_WINDOW(x)))
+        s = sqrt_short(x);
+    else
+        s = __builtin_sqrt(x);
+    RT_REGION(region);
+    return s;
+}
+/* root = sqrt(x), returns 1.0 / root: a length and the factor that normalises by it, under one vote */
+RT_DEV Real sqrt_rcp_lane(Real x, Real& root) {
+    if (!(RTR_LANE_SQRT && RTR_LANE_RCP)) {
+        root = sqrt_lane(x);
+        return rcp_lane<1>(root);
+    }
+    const int region = RT_REGION_CURRENT();
+    RT_REGION(RG_LANE_SQRT);
+    Real r;
+    if (__all(RT_UNIT_WINDOW(x))) {
+        root = sqrt_short(x);
+        RT_REGION(RG_LANE_DIV);
+        r = rcp_short(root);
+    } else {
+        root = __builtin_sqrt(x);
+        RT_REGION(RG_LANE_DIV);
+        r = 1.0 / root;
+    }
+    RT_REGION(region);
+    return r;
+}
+
 /* ---- core/vec3.h:12-224 --------------------------------------------------------------- */
 struct V3 {
     Real x, y, z;
@@ -87,12 +228,33 @@ RT_DEV V3 add(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 RT_DEV V3 sub(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 RT_DEV V3 mul(V3 a, V3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
 RT_DEV V3 scl(Real t, V3 v) { return mk(t * v.x, t * v.y, t * v.z); }
-RT_DEV V3 divs(V3 v, Real t) { return scl(1 / t, v); } /* vec3.h:208-210: multiply by 1/t */
+/* vec3.h:208-210: multiply by 1/t.  LANE: t is a lane's own number on a path every bounce runs (rcp_lane); the default is
+ * the compiler's division, which folds for a constant t.  The lane form's window holds positive numbers only: pdfs, the
+ * roulette's probability */
+template <bool LANE = false>
+RT_DEV V3 divs(V3 v, Real t) { return scl(LANE ? rcp_lane<1>(t) : 1 / t, v); }
 RT_DEV Real dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 RT_DEV V3 cross(V3 u, V3 v) { return mk(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x); }
 RT_DEV Real len2(V3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
-RT_DEV Real len(V3 a) { return __builtin_sqrt(len2(a)); }
-RT_DEV V3 unit(V3 v) { return divs(v, len(v)); }
+/* LANE (here, in divs and in the shading functions below): the caller is on the path every bounce of a lean MIS kernel
+ * runs and takes the wave-voted short forms; everything else keeps the compiler's expansions, and with them its registers
+ * (profiles/r20_kres.txt: given to every caller, the two arms cost the other kernels of the benchmark scratch) */
+#define RT_LANE_MS(MS) ((MS) == RT_MS_LEAN)
+/* root = sqrt(x), returns 1.0 / root */
+template <bool LANE>
+RT_DEV Real sqrt_rcp(Real x, Real& root) {
+    if (LANE) return sqrt_rcp_lane(x, root);
+    root = __builtin_sqrt(x);
+    return 1 / root;
+}
+template <bool LANE = false>
+RT_DEV Real len(V3 a) { return LANE ? sqrt_lane(len2(a)) : __builtin_sqrt(len2(a)); }
+template <bool LANE = false>
+RT_DEV V3 unit(V3 v) { /* v / v.length() = (1 / length) * v; LANE: the root and its reciprocal under one vote */
+    Real l;
+    const Real r = sqrt_rcp<LANE>(len2(v), l);
+    return scl(r, v);
+}
 RT_DEV bool near_zero(V3 a) { /* vec3.h:81-85 */
     const Real s = 1e-8;
     return (__builtin_fabs(a.x) < s) && (__builtin_fabs(a.y) < s) && (__builtin_fabs(a.z) < s);
@@ -150,7 +312,8 @@ RT_DEV V3 random_in_unit_sphere(uint32_t& s) {
         return p;
     }
 }
-RT_DEV V3 random_unit_vector(uint32_t& s) { return unit(random_in_unit_sphere(s)); }
+template <bool LANE = false>
+RT_DEV V3 random_unit_vector(uint32_t& s) { return unit<LANE>(random_in_unit_sphere(s)); }
 RT_DEV V3 random_in_unit_disk(uint32_t& s) { /* vec3.h:250-257; y first */
     for (;;) {
         Real y = rng_sym(s);
@@ -190,13 +353,7 @@ RT_DEV V3 random_cosine_direction(uint32_t& s) { /* vec3.h:261-269 */
  * divisions (`fast`, wave-uniform); a numerator below 2^-300 (zero included: the sign of a zero quotient) gives a
  * quotient below 2^-200 either way, which every caller with t_min >= 2^-100 rejects by `t < t_min` -- the
  * others (medium boundaries: t_min = -inf) take the plain division for such numerators (`guard`). */
-RT_DEV Real rcp_refined(Real d) {
-    Real r = __builtin_amdgcn_rcp(d);
-    Real e = __builtin_fma(-d, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-d, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
+/* (rcp_refined: with the lane forms above) */
 RT_DEV bool rcp_safe(Real d) { return (__builtin_fabs(d) >= 0x1p-100) & (__builtin_fabs(d) <= 0x1p100); }
 /* n / d given r = rcp_refined(d).  SHARED is decided once per ray and frame (RayDiv::fast, wave-uniform), outside the
  * loops over primitives: every instruction counts in them, a scalar branch as much as an FP64 one */
@@ -2499,9 +2656,9 @@ template <int MS = RT_MS_FULL>
 __device__ __forceinline__ bool mat_sample(const MatCtx& c, const Hit& rec, V3 wo, BSDFSample& s, uint32_t& rng, const UDiv& pi) {
     const int type = c.type;
     if (type == RTR_MAT_LAMBERTIAN) { /* material.h:79-90 */
-        V3 scatter_direction = add(rec.n, random_unit_vector(rng));
+        V3 scatter_direction = add(rec.n, random_unit_vector<RT_LANE_MS(MS)>(rng));
         if (near_zero(scatter_direction)) scatter_direction = rec.n;
-        s.wi = unit(scatter_direction);
+        s.wi = unit<RT_LANE_MS(MS)>(scatter_direction);
         s.pdf = udiv(dot(rec.n, s.wi), pi);
         s.f = divs(c.albedo, RT_PI);
         s.is_specular = false;
@@ -2550,7 +2707,7 @@ RT_DEV V3 mat_eval(const MatCtx& c, V3 wo, V3 wi) {
 template <int MS = RT_MS_FULL>
 RT_DEV Real mat_pdf(const MatCtx& c, const Hit& rec, V3 wo, V3 wi, const UDiv& pi) {
     if (c.type == RTR_MAT_LAMBERTIAN) {
-        Real cosine = dot(rec.n, unit(wi));
+        Real cosine = dot(rec.n, unit<RT_LANE_MS(MS)>(wi));
         return cosine < 0 ? 0 : udiv(cosine, pi);
     }
     if (MS != RT_MS_LEAN && c.type == RTR_MAT_PBR) return pbr_pdf(c, wo, wi, pi);
@@ -2789,8 +2946,7 @@ RT_DEV LightSample light_sample(const rtr_light& l, V3 p, Real ux, Real uy, uint
     V3 light_point = add(add(ld3(l.f), scl(ux, ld3(l.f + 3))), scl(uy, ld3(l.f + 6)));
     V3 d = sub(light_point, p);
     Real dist_sq = len2(d);
-    s.dist = __builtin_sqrt(dist_sq);
-    s.wi = divs(d, s.dist);
+    s.wi = scl(sqrt_rcp<RT_LANE_MS(MS)>(dist_sq, s.dist), d); /* dist = sqrt(dist_sq), wi = d / dist (vec3.h:208-210) */
     Real cos_theta = dot(neg(s.wi), ld3(l.f + 12));
     if (cos_theta <= 0) {
         s.Li = mk(0, 0, 0);
@@ -2801,8 +2957,10 @@ RT_DEV LightSample light_sample(const rtr_light& l, V3 p, Real ux, Real uy, uint
     s.pdf = dist_sq / (l.f[15] * cos_theta);
     return s;
 }
+/* dir_len (lane kernels only) = len(direction): the same for every light, so compute_light_pdf takes the root and its vote
+ * once, outside its loop over the lights -- inside it the compiler hoists both arms of the vote and runs both */
 template <int MS = RT_MS_FULL>
-RT_DEV Real light_pdf(const rtr_light& l, const LightConsts& lc, V3 origin, V3 direction, const uint8_t* blob) {
+RT_DEV Real light_pdf(const rtr_light& l, const LightConsts& lc, V3 origin, V3 direction, Real dir_len, const uint8_t* blob) {
     if (MS == RT_MS_FULL) {
         if (l.type == RTR_LIGHT_ENV_UNIFORM) return 1.0 / (4.0 * RT_PI); /* environmental_light.h:293-294 */
         if (l.type == RTR_LIGHT_ENV_MAP) return env_pdf(env_map(l, blob), direction);
@@ -2821,7 +2979,7 @@ RT_DEV Real light_pdf(const rtr_light& l, const LightConsts& lc, V3 origin, V3 d
     Real beta = udiv(dot(planar, Vv), dv);
     if (alpha < 0 || alpha > 1 || beta < 0 || beta > 1) return 0;
     Real dist_sq = t * t * len2(direction);
-    Real cos_theta = -denom / len(direction);
+    Real cos_theta = -denom / (RT_LANE_MS(MS) ? dir_len : len(direction));
     return dist_sq / (l.f[15] * cos_theta);
 }
 
@@ -2855,9 +3013,10 @@ template <int MS = RT_MS_FULL>
 RT_DEV Real compute_light_pdf(const DScene& sc, V3 o, V3 d) { /* :173-188 */
     Real total_pdf = 0.0;
     Real light_select_pdf = scene_light_select_pdf(sc);
+    const Real dir_len = RT_LANE_MS(MS) ? len<true>(d) : 0.0;
     for (int k = 0; k < sc.n_lights; ++k) {
         const rtr_light l = ld_const(sc.lights, k); /* wave-uniform index: scalar loads */
-        total_pdf += light_pdf<MS>(l, scene_light_consts(sc, k), o, d, sc.image_bytes) * light_select_pdf;
+        total_pdf += light_pdf<MS>(l, scene_light_consts(sc, k), o, d, dir_len, sc.image_bytes) * light_select_pdf;
     }
     return total_pdf;
 }
@@ -3006,7 +3165,7 @@ RT_DEV void shade_a_mis(const DScene& sc, PathState& ps, const Hit& rec, const M
             } else { /* mis_path_integrator.h:222-229 */
                 Real lpdf = ls.pdf * light_select_pdf;
                 Real mis_weight = power_heuristic(lpdf, bsdf_pdf);
-                L_direct = divs(scl(mis_weight, scl(cos_theta, mul(f, ls.Li))), lpdf);
+                L_direct = divs<RT_LANE_MS(MS)>(scl(mis_weight, scl(cos_theta, mul(f, ls.Li))), lpdf);
             }
             rq.put(ls.wi, ls.dist - 0.001,
                    INTEG == RTR_INTEGRATOR_NEE ? mul(ps.thr, L_direct) : clamp_radiance(mul(ps.thr, L_direct)));
@@ -3037,13 +3196,13 @@ RT_DEV bool shade_b_mis(const DScene& sc, PathState& ps, const Hit& rec, const M
         if (bs.is_specular)
             ps.thr = mul(ps.thr, bs.f);
         else
-            ps.thr = mul(ps.thr, divs(scl(cos_theta, bs.f), bs.pdf));
+            ps.thr = mul(ps.thr, divs<RT_LANE_MS(MS)>(scl(cos_theta, bs.f), bs.pdf));
         ps.ro = rec.p, ps.rd = bs.wi;
     }
     if (ps.depth >= rr_start) { /* :137-146 */
         Real p_survive = clampd(max3(ps.thr), 0.05, 0.95);
         if (rng_next(rng) > p_survive) return false;
-        ps.thr = divs(ps.thr, p_survive);
+        ps.thr = divs<RT_LANE_MS(MS)>(ps.thr, p_survive);
     }
     return true;
 }

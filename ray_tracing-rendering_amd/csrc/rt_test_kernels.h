@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_lights(const DScene sc, rtr_
     r.Li[0] = s.Li.x, r.Li[1] = s.Li.y, r.Li[2] = s.Li.z;
     r.wi[0] = s.wi.x, r.wi[1] = s.wi.y, r.wi[2] = s.wi.z;
     r.pdf = s.pdf, r.dist = s.dist, r.is_delta = s.is_delta, r.pad2 = 0;
-    r.pdf_dir = light_pdf<MS>(l, scene_light_consts(sc, r.light), ld3(r.p), ld3(r.dir), sc.image_bytes);
+    r.pdf_dir = light_pdf<MS>(l, scene_light_consts(sc, r.light), ld3(r.p), ld3(r.dir), RT_LANE_MS(MS) ? len<true>(ld3(r.dir)) : 0.0, sc.image_bytes);
     recs[k] = r;
 }
 
@@ -194,6 +194,78 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_udiv(const double* __restric
     tested = wave_sum(tested);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, bad);
     if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
+}
+
+/* rtr_test_rcp_lane / rtr_test_sqrt_lane: the wave-voted short forms of rt_device.h beside the compiler's 1.0 / d and
+ * __builtin_sqrt(x), bit for bit (NaN payloads too).
+ * The edge values every wave class gets: each window bound of the short forms (and 2^-300, 2^200), the smallest normal
+ * number and the exponent of the largest, each with the value one ulp below and above it; zero, denormals, infinity, NaNs
+ * (quiet, with a payload, signalling), the largest finite number and 1 -- all of them with both signs. */
+#define RT_LANE_SPECIALS 68
+RT_HD unsigned long long lane_special(unsigned k) {
+    const unsigned long long sign = (unsigned long long)(k & 1) << 63;
+    k >>= 1;
+    if (k < 24) {
+        const int e[8] = {-1022, -767, -300, -200, -100, 100, 200, 1023};
+        return sign | ((((unsigned long long)(1023 + e[k / 3])) << 52) + (k % 3) - 1);
+    }
+    const unsigned long long other[10] = {0ull, 1ull, 0x0008000000000000ull, 1ull << 44, 0x7ff0000000000000ull, 0x7ff8000000000000ull,
+                                          0x7ff8000000001234ull, 0x7ff0000000000001ull, 0x7fefffffffffffffull, 0x3ff0000000000000ull};
+    return sign | other[(k - 24) % 10];
+}
+RT_DEV unsigned long long lane_mix(unsigned long long z) { /* splitmix64's finaliser */
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+/* OP 0: rcp_lane in its two windows (either sign; positive divisors only, the callers'), 1: sqrt_lane and sqrt_rcp_lane.
+ * Operand set g of gridDim.x * RTR_BLOCK * per_thread comes from the counter alone: a random mantissa (OP 0: and sign) under
+ * every exponent of the accepted window in turn, lane after lane, so a wave of such sets votes for the short form.  Every
+ * fourth wave gets one edge value: in lane (w / 4) % 64, value (w / 256) % 68, so every value meets every lane position,
+ * and waves that vote for the plain form carry 63 lanes in range through it.
+ * out[0] += sets with a result that differs, out[1] += sets compared, out[2]: a mismatch was recorded in out[3..6] =
+ * operand, 0, result, expected (bits), out[7] += sets whose wave had every lane inside the form's widest window. */
+template <int OP>
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_lane(unsigned long long* out, unsigned per_thread) {
+    const unsigned long long threads = (unsigned long long)gridDim.x * RTR_BLOCK, tid = (unsigned long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    unsigned long long bad = 0, tested = 0, in_short = 0;
+    for (unsigned it = 0; it < per_thread; ++it) {
+        const unsigned long long g = (unsigned long long)it * threads + tid, w = g >> 6;
+        const unsigned long long h = lane_mix(g);
+        const int e = OP == 1 ? -767 + (int)(g % 1791) : -100 + (int)(g % 200);
+        Real a = __longlong_as_double((long long)((h & (OP == 1 ? 0x000FFFFFFFFFFFFFull : 0x800FFFFFFFFFFFFFull)) |
+                                                  ((unsigned long long)(1023 + e) << 52)));
+        if ((w & 3) == 3 && (g & 63) == ((w >> 2) & 63)) a = __longlong_as_double((long long)lane_special((unsigned)(w >> 8) % RT_LANE_SPECIALS));
+        Real got, want;
+        bool differs = false, all_in;
+        auto check = [&](Real g_, Real w_) {
+            if (!differs && __double_as_longlong(g_) != __double_as_longlong(w_)) differs = true, got = g_, want = w_;
+        };
+        if (OP == 0) {
+            all_in = __all(lane_window<-100, 100>(a));
+            check(rcp_lane(a), 1.0 / a);
+            check(rcp_lane<1>(a), 1.0 / a);
+            check(rcp_lane<1>(__builtin_fabs(a)), 1.0 / __builtin_fabs(a));
+        } else {
+            all_in = __all(RT_SQRT_WINDOW(a));
+            const Real s = __builtin_sqrt(a);
+            check(sqrt_lane(a), s);
+            Real root;
+            const Real r = sqrt_rcp_lane(a, root);
+            check(root, s);
+            check(r, 1.0 / s);
+        }
+        if (differs && atomicCAS(out + 2, 0ull, 1ull) == 0ull) {
+            out[3] = (unsigned long long)__double_as_longlong(a), out[4] = 0;
+            out[5] = (unsigned long long)__double_as_longlong(got), out[6] = (unsigned long long)__double_as_longlong(want);
+        }
+        bad += differs, in_short += all_in, ++tested;
+    }
+    bad = wave_sum(bad), tested = wave_sum(tested), in_short = wave_sum(in_short);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, bad);
+    if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
+    if ((threadIdx.x & 63) == 0 && in_short) atomicAdd(out + 7, in_short);
 }
 
 /* rtr_test_scene_consts: a second evaluation of the scene table (scene_consts_fill) into the test buffer */

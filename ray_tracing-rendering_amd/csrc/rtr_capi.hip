@@ -131,7 +131,8 @@ int finish_stats(rtr_context* c) {
                                           "pair cast: rect runs", "pair cast: sphere runs", "sample end: cancel poll",
                                           "sample end: begin_sample (camera ray)", "sample end: settle into the pixel sum",
                                           "cast counters", "random_in_unit_sphere rejection loop",
-                                          "shade_a: emitter MIS weight (compute_light_pdf)", "camera_sample: image-size divisions"};
+                                          "shade_a: emitter MIS weight (compute_light_pdf)", "camera_sample: image-size divisions",
+                                          "shading: lane-varying 1 / x and n / d", "shading: lane-varying sqrt"};
         double total = 0;
         for (int k = 0; k < RG_N; ++k) total += (double)h[RT_PROF_BASE + k];
         std::fprintf(stderr, "[region profile] %.4g wave cycles in all, %llu samples\n", total, h[0]);

@@ -91,6 +91,27 @@ int bare(rtr_context* c, hipStream_t& stream, int& n_cus, TestState*& t) {
     return RTR_OK;
 }
 
+/* 2^26 operand sets through k_test_lane<OP>: 1024 workgroups, 256 sets per lane */
+template <int OP>
+int lane_test(rtr_context* c, uint64_t* mismatches, uint64_t* tested, uint64_t* short_sets, uint64_t* first) {
+    if (!c || !mismatches || !tested || !short_sets || !first) return RTR_ERR_INVALID;
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc) return rc;
+    if ((rc = ensure(c, *t, 64))) return rc;
+    TCHK(c, hipMemsetAsync(t->buf, 0, 64, stream));
+    const unsigned blocks = 1024, per_thread = (unsigned)((1ull << 26) / ((unsigned long long)blocks * RTR_BLOCK));
+    hipLaunchKernelGGL(k_test_lane<OP>, dim3(blocks), dim3(RTR_BLOCK), 0, stream, static_cast<unsigned long long*>(t->buf), per_thread);
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream)); /* the kernel's stream, before the counters are read */
+    unsigned long long h[8] = {0};
+    TCHK(c, hipMemcpy(h, t->buf, sizeof h, hipMemcpyDeviceToHost));
+    *mismatches = h[0], *tested = h[1], *short_sets = h[7];
+    for (int k = 0; k < 4; ++k) first[k] = h[2] ? h[3 + k] : 0;
+    return RTR_OK;
+}
 } // namespace
 
 extern "C" {
@@ -449,6 +470,34 @@ int rtr_test_udiv(rtr_context* c, const double* num, int64_t n, const double* di
     unsigned long long h[2] = {0, 0};
     TCHK(c, hipMemcpy(h, counts, 16, hipMemcpyDeviceToHost));
     *mismatches = h[0], *tested = h[1];
+    return RTR_OK;
+}
+
+int rtr_test_rcp_lane(rtr_context* c, uint64_t* mismatches, uint64_t* tested, uint64_t* short_sets, uint64_t* first) {
+    return lane_test<0>(c, mismatches, tested, short_sets, first);
+}
+int rtr_test_sqrt_lane(rtr_context* c, uint64_t* mismatches, uint64_t* tested, uint64_t* short_sets, uint64_t* first) {
+    return lane_test<1>(c, mismatches, tested, short_sets, first);
+}
+
+int rtr_test_lane_specials(uint64_t* out, int64_t cap) {
+    if (cap < 0 || (cap > 0 && !out)) return -1;
+    for (int64_t k = 0; k < cap && k < RT_LANE_SPECIALS; ++k) out[k] = lane_special((unsigned)k);
+    return RT_LANE_SPECIALS;
+}
+
+int rtr_test_lane_host(int32_t op, int32_t coarse_bits, const double* a, double* out, int32_t* took_short, int64_t n) {
+    if (coarse_bits < 0 || coarse_bits > 40) return RTR_ERR_INVALID;
+    rt_host_seed_coarse = coarse_bits;
+    if (op < 0 || op > 1 || n < 0 || (n > 0 && (!a || !out || !took_short))) return RTR_ERR_INVALID;
+    for (int64_t k = 0; k < n; ++k) {
+        const bool s = op == 0 ? lane_window<-100, 100>(a[k]) : RT_SQRT_WINDOW(a[k]);
+        if (op == 0)
+            out[k] = s ? rcp_short(a[k]) : 1.0 / a[k];
+        else
+            out[k] = s ? sqrt_short(a[k]) : __builtin_sqrt(a[k]);
+        took_short[k] = s;
+    }
     return RTR_OK;
 }
 

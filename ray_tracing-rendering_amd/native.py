@@ -43,7 +43,8 @@ TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_t
                 "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
                 "rtr_test_pow5_host", "rtr_test_udiv", "rtr_test_scene_consts", "rtr_test_accum_load",
-                "rtr_test_accum_plan", "rtr_test_accum_commit")
+                "rtr_test_accum_plan", "rtr_test_accum_commit", "rtr_test_rcp_lane", "rtr_test_sqrt_lane",
+                "rtr_test_lane_specials", "rtr_test_lane_host")
 _TEST_LIB = None
 
 
@@ -245,6 +246,10 @@ def test_lib():
     T.rtr_test_queue_pack_host.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     T.rtr_test_udiv.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_scene_consts.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int32)]
+    for name in ("rtr_test_rcp_lane", "rtr_test_sqrt_lane"):
+        getattr(T, name).argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3 + [vp]
+    T.rtr_test_lane_specials.argtypes = [vp, C.c_int64]
+    T.rtr_test_lane_host.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, C.c_int64]
     T.rtr_test_accum_load.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
     T.rtr_test_accum_plan.argtypes = [vp, C.c_int64] + [C.c_int32] * 4 + [C.c_double, vp, vp, vp, vp, C.POINTER(C.c_int32)]
     T.rtr_test_accum_commit.argtypes = [vp, C.c_int64, vp, C.c_int32] + [vp] * 7
@@ -324,6 +329,29 @@ def pow5_host(x):
     if rc != 0:
         raise RtrError(rc, "rtr_test_pow5_host")
     return out
+
+
+def lane_specials():
+    """rtr_test_lane_specials (include/rtr_hip_test.h; no GPU needed): the edge values of the lane-division kernels, float64."""
+    n = test_lib().rtr_test_lane_specials(None, 0)
+    out = np.zeros(n, dtype=np.uint64)
+    test_lib().rtr_test_lane_specials(out.ctypes.data, n)
+    return out.view(np.float64)
+
+
+LANE_OPS = ("rcp", "sqrt")
+
+
+def lane_host(op, a, coarse_bits=0):
+    """rtr_test_lane_host (include/rtr_hip_test.h; no GPU needed): 1.0 / a (``op`` "rcp") or sqrt(a) ("sqrt") through the
+    host build of the short forms, element by element, the seeds' low ``coarse_bits`` bits cleared.  Returns (results,
+    took_short)."""
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    out, took = np.zeros_like(a), np.zeros(a.size, dtype=np.int32)
+    rc = test_lib().rtr_test_lane_host(LANE_OPS.index(op), int(coarse_bits), a.ctypes.data, out.ctypes.data, took.ctypes.data, a.size)
+    if rc != 0:
+        raise RtrError(rc, "rtr_test_lane_host")
+    return out, took.astype(bool)
 
 
 def queue_blocks_host(n_tiles, spp, chunks, guided=(0, 0, 0)):
@@ -1003,6 +1031,16 @@ class Context:
         self._chk(test_lib().rtr_test_udiv(self._h, num.ctypes.data, len(num), div.ctypes.data, len(div), C.byref(n),
                                            C.byref(tested)))
         return int(n.value), int(tested.value)
+
+    def lane_mismatches(self, op):
+        """rtr_test_rcp_lane / _sqrt_lane (include/rtr_hip_test.h; ``op`` one of LANE_OPS): (operands whose result differs
+        from the compiler's, operands compared, operands in waves that voted for the short form, a mismatch as four uint64:
+        operand, 0, result, expected)."""
+        n, tested, short = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        first = np.zeros(4, dtype=np.uint64)
+        fn = getattr(test_lib(), "rtr_test_%s_lane" % op)
+        self._chk(fn(self._h, C.byref(n), C.byref(tested), C.byref(short), first.ctypes.data))
+        return int(n.value), int(tested.value), int(short.value), first
 
     def scene_consts(self):
         """rtr_test_scene_consts (include/rtr_hip_test.h): the uploaded scene's table of shading constants and its second
