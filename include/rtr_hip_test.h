@@ -217,6 +217,23 @@ int rtr_test_lane_specials(uint64_t* out, int64_t cap);
  * accuracy the ISA manual gives v_rcp_f64 and v_rsq_f64).  Not thread-safe.  No GPU needed. */
 int rtr_test_lane_host(int32_t op, int32_t coarse_bits, const double* a, double* out, int32_t* took_short, int64_t n);
 
+/* A random draw in (-1, 1) is the generator's 32-bit state s as the double -1 + s * 2^-31; the lean kernels make it with
+ * one addition from a double whose low word is s (rt_device.h: draw_sym_join).  rtr_test_draw_forms walks ALL 2^32 states
+ * on the device and counts those where the joined form and the plain text differ in any bit: *mismatches must be 0,
+ * *tested 2^32; *first: such a state + 1, or 0.  Needs no scene. */
+int rtr_test_draw_forms(rtr_context* ctx, uint64_t* mismatches, uint64_t* tested, uint64_t* first);
+/* The functions that draw -- random_in_unit_sphere, random_in_unit_disk, random_cosine_direction, rng_range(0.25, 7.5),
+ * rng_int(0, 6), one after the other -- from n states seeded by `seed`, one per lane, with the joined form and in the
+ * plain text (a second instantiation in this library).  *mismatches: lanes where an output bit or the
+ * state after a call differs, must be 0; *tested = n; *first: such a lane's starting state, or 0.  Needs no scene. */
+int rtr_test_draw_callers(rtr_context* ctx, uint64_t seed, int64_t n, uint64_t* mismatches, uint64_t* tested, uint64_t* first);
+/* The host build of the joined form: out[k] = draw_sym_join(s[k]).  No GPU needed. */
+int rtr_test_draw_host(const uint32_t* s, double* out, int64_t n);
+/* The host build of the joined form beside the plain text on the states first, first + stride, ... (count of them, all
+ * below 2^32), split over `threads` threads: *mismatches = states where it differs in any bit, *tested = count.
+ * first 0, count 2^32, stride 1 is every state.  No GPU needed. */
+int rtr_test_draw_host_range(uint64_t first, uint64_t count, uint64_t stride, int32_t threads, uint64_t* mismatches, uint64_t* tested);
+
 /* The uploaded scene's table of shading constants (rt_device.h: SceneConsts, made on the device by rtr_upload_scene) as
  * 8-byte words -- 1 / n_lights, 0, pi, rcp_refined(pi); then per light len2(U), its refined reciprocal, len2(V), its refined
  * reciprocal, the `safe` flag in the low half of a word -- into `table`, and a second evaluation of the same expressions

@@ -280,44 +280,82 @@ RT_DEV Real max3(V3 a) { /* std::max({x,y,z}) */
 RT_DEV Real maxd(Real a, Real b) { return a < b ? b : a; } /* std::max(a,b) */
 
 /* ---- core/rtweekend.h:24-50 ------------------------------------------------------------ */
-RT_DEV Real rng_next(uint32_t& s) {
+RT_HD void xorshift32(uint32_t& s) {
     s ^= s << 13;
     s ^= s >> 17;
     s ^= s << 5;
+}
+RT_DEV Real rng_next(uint32_t& s) {
+    xorshift32(s);
     return s * 2.3283064365386963e-10;
 }
 RT_DEV Real rng_range(uint32_t& s, Real lo, Real hi) { return lo + (hi - lo) * rng_next(s); }
 RT_DEV int rng_int(uint32_t& s, int lo, int hi) { return (int)rng_range(s, lo, hi + 1); }
 
-/* random_double(-1, 1) = -1 + (1 - -1) * (s * 2^-32) (rtweekend.h:36-38).  Doubling is exact, so
- * this equals -1 + s * 2^-31 bit for bit, with one multiply less. */
-RT_DEV Real rng_sym(uint32_t& s) {
-    s ^= s << 13;
-    s ^= s >> 17;
-    s ^= s << 5;
-    return -1.0 + s * 4.656612873077392578125e-10;
+/* random_double(-1, 1) = -1 + (1 - -1) * (s * 2^-32) (rtweekend.h:36-38), s the generator's 32-bit state.  Doubling is
+ * exact, so this equals -1 + s * 2^-31 bit for bit, with one multiply less (draw_sym_plain).  Written so, hipcc converts
+ * (v_cvt_f64_u32), scales (v_ldexp_f64) and adds: three FP64-rate instructions.  The same double comes out of ONE addition
+ * when s is placed in the low word of a double whose high word is a constant (draw_sym_join):
+ *     { 0x41400000, s } = 2^21 + s * 2^-31,          minus (2^21 + 1)  = s * 2^-31 - 1
+ * Both operands and the difference are representable (multiples of 2^-31 of at most 53 bits), so nothing rounds and the
+ * result is the plain text's bit for bit, +0 at s = 2^31 included (x - x is +0 to nearest).  Checked over all 2^32 states on
+ * the host (tests/test_draw_forms_cpu.py) and on the device (rtr_test_draw_forms).
+ * JOIN is a template policy like the short forms above, plain by default: the kernels of the lean material set pass
+ * RT_DRAW_MS(MS), every other kernel compiles the plain text and keeps its registers (profiles/r21_kres.txt: given to every
+ * caller, the joined form cost 85 of 339 kernels scratch or spilled VGPRs, final_mis's among them).  -DRTR_PLAIN_DRAWS
+ * restores the plain text everywhere.  The same device for rng_next ({ 0x41300000, s } - 2^20 = s * 2^-32, as exact) saves
+ * one v_ldexp_f64 per draw; it measured x1.002, half the run-to-run spread, and was taken out again
+ * (profiles/r21_draws.txt). */
+#ifdef RTR_PLAIN_DRAWS
+#define RT_DRAW_MS(MS) false
+#else
+#define RT_DRAW_MS(MS) RT_LANE_MS(MS)
+#endif
+RT_HD Real draw_sym_plain(uint32_t s) { return -1.0 + s * 4.656612873077392578125e-10; }
+/* hi: the constant high word, which a loop over several draws holds in one register (rng_hi) */
+RT_HD Real draw_sym_join(uint32_t s, uint32_t hi = 0x41400000u) {
+    const unsigned long long b = ((unsigned long long)hi << 32) | s;
+    Real v;
+    __builtin_memcpy(&v, &b, 8);
+    return v - 2097153.0;
+}
+template <bool JOIN = false>
+RT_DEV Real rng_sym(uint32_t& s, uint32_t hi = 0x41400000u) {
+    xorshift32(s);
+    return JOIN ? draw_sym_join(s, hi) : draw_sym_plain(s);
+}
+/* the high word as a value the compiler cannot see through: the rejection loops make it once and every draw of every trip
+ * pairs the state with that one register */
+RT_DEV uint32_t rng_hi() {
+    uint32_t hi = 0x41400000u;
+    asm("" : "+v"(hi));
+    return hi;
 }
 
 /* vec3::random(-1,1) accepted into the unit ball (vec3.h:226-233); z takes the first draw */
+template <bool JOIN = false>
 RT_DEV V3 random_in_unit_sphere(uint32_t& s) {
     const int region = RT_REGION_CURRENT();
     RT_REGION(RG_REJECT);
+    const uint32_t hi = JOIN ? rng_hi() : 0u;
     for (;;) {
-        Real z = rng_sym(s);
-        Real y = rng_sym(s);
-        Real x = rng_sym(s);
+        Real z = rng_sym<JOIN>(s, hi);
+        Real y = rng_sym<JOIN>(s, hi);
+        Real x = rng_sym<JOIN>(s, hi);
         V3 p = mk(x, y, z);
         if (len2(p) >= 1) continue;
         RT_REGION(region);
         return p;
     }
 }
-template <bool LANE = false>
-RT_DEV V3 random_unit_vector(uint32_t& s) { return unit<LANE>(random_in_unit_sphere(s)); }
+template <bool LANE = false, bool JOIN = false>
+RT_DEV V3 random_unit_vector(uint32_t& s) { return unit<LANE>(random_in_unit_sphere<JOIN>(s)); }
+template <bool JOIN = false>
 RT_DEV V3 random_in_unit_disk(uint32_t& s) { /* vec3.h:250-257; y first */
+    const uint32_t hi = JOIN ? rng_hi() : 0u;
     for (;;) {
-        Real y = rng_sym(s);
-        Real x = rng_sym(s);
+        Real y = rng_sym<JOIN>(s, hi);
+        Real x = rng_sym<JOIN>(s, hi);
         V3 p = mk(x, y, 0);
         if (len2(p) >= 1) continue;
         return p;
@@ -2656,7 +2694,7 @@ template <int MS = RT_MS_FULL>
 __device__ __forceinline__ bool mat_sample(const MatCtx& c, const Hit& rec, V3 wo, BSDFSample& s, uint32_t& rng, const UDiv& pi) {
     const int type = c.type;
     if (type == RTR_MAT_LAMBERTIAN) { /* material.h:79-90 */
-        V3 scatter_direction = add(rec.n, random_unit_vector<RT_LANE_MS(MS)>(rng));
+        V3 scatter_direction = add(rec.n, random_unit_vector<RT_LANE_MS(MS), RT_DRAW_MS(MS)>(rng));
         if (near_zero(scatter_direction)) scatter_direction = rec.n;
         s.wi = unit<RT_LANE_MS(MS)>(scatter_direction);
         s.pdf = udiv(dot(rec.n, s.wi), pi);
@@ -2729,7 +2767,7 @@ __device__ __forceinline__ bool mat_scatter(const MatCtx& c, V3 rd, const Hit& r
                                             uint32_t& rng) {
     const int type = c.type;
     if (type == RTR_MAT_LAMBERTIAN) { /* material.h:103-112 */
-        V3 scatter_direction = add(rec.n, random_unit_vector(rng));
+        V3 scatter_direction = add(rec.n, random_unit_vector<false, RT_DRAW_MS(MS)>(rng));
         if (near_zero(scatter_direction)) scatter_direction = rec.n;
         out_dir = scatter_direction;
         attenuation = c.albedo;
@@ -2984,8 +3022,9 @@ RT_DEV Real light_pdf(const rtr_light& l, const LightConsts& lc, V3 origin, V3 d
 }
 
 /* ---- renderer/camera.h:32-40 --------------------------------------------------------------------------------- */
+template <bool JOIN = false>
 RT_DEV void camera_get_ray(const rtr_camera& c, Real s, Real t, uint32_t& rng, V3& o, V3& d, Real& tm) {
-    V3 rd = scl(c.lens_radius, random_in_unit_disk(rng));
+    V3 rd = scl(c.lens_radius, random_in_unit_disk<JOIN>(rng));
     V3 offset = add(scl(rd.x, ld3(c.u)), scl(rd.y, ld3(c.v)));
     V3 origin = ld3(c.origin);
     d = sub(sub(add(add(ld3(c.lower_left_corner), scl(s, ld3(c.horizontal))), scl(t, ld3(c.vertical))), origin),

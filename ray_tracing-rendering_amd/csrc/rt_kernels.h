@@ -171,7 +171,7 @@ RT_DEV bool cancel_poll_take(const RenderK& P, uint32_t word) { return word >= P
 /* renderer.h:73-75 under the per-sample seed: the camera ray of sample s of the lane's pixel and the parked words of a
  * new path.  K_* : the variant's parked words (PK_* / SK_*); K_L < 0: the loop clears the radiance word itself (the
  * pair cast, step (3)); K_PIX >= 0: the word that holds the lane's pixel (PK_PIXEL), else it is worked out again */
-template <int K_THR, int K_L, int K_PDF, int K_PIX = -1>
+template <int K_THR, int K_L, int K_PDF, int K_PIX = -1, bool JOIN = false>
 RT_DEV void begin_sample(const DScene& sc, const RenderK& P, const Park& pk, int slot, int s, uint32_t& rng, PathState& ps) {
     int pi, pj;
     if (K_PIX >= 0) {
@@ -182,7 +182,7 @@ RT_DEV void begin_sample(const DScene& sc, const RenderK& P, const Park& pk, int
         bool in_region;
         tile_pixel(P, slot, threadIdx.x, pi, pj, in_region); /* recomputed: not worth two live registers */
     }
-    camera_sample(sc, P, pi, pj, s, rng, ps.ro, ps.rd, ps.tm);
+    camera_sample<JOIN>(sc, P, pi, pj, s, rng, ps.ro, ps.rd, ps.tm);
     ps.depth = 0, ps.specular_bounce = false;
     pk.set3(K_THR, mk(1.0, 1.0, 1.0));
     if (K_L >= 0) pk.set3(K_L, mk(0.0, 0.0, 0.0));
@@ -250,7 +250,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
         pk.set(SK_NCLOSEST, 0.0);
         pk.set(SK_NSHADOW, 0.0);
-        if (!done) begin_sample<SK_THR, SK_L, SK_PDF>(sc, P, pk, slot, s, rng, ps);
+        if (!done) begin_sample<SK_THR, SK_L, SK_PDF, -1, RT_DRAW_MS(MS)>(sc, P, pk, slot, s, rng, ps);
         __syncthreads();
         for (;;) {
             bool pending = false, ended = false, shade_me = false;
@@ -381,7 +381,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 ++n_samples;
                 ++s;
                 done = s >= s_end || ((s & 7) == 0 && render_cancelled(P));
-                if (!done) begin_sample<SK_THR, SK_L, SK_PDF>(sc, P, pk, slot, s, rng, ps);
+                if (!done) begin_sample<SK_THR, SK_L, SK_PDF, -1, RT_DRAW_MS(MS)>(sc, P, pk, slot, s, rng, ps);
             }
         }
         cnt.closest = (uint32_t)pk.get(SK_NCLOSEST);
@@ -394,7 +394,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 if ((s & 7) == 0 && render_cancelled(P)) break;
                 V3 ro, rd;
                 Real tm;
-                camera_sample(sc, P, i, j, s, rng, ro, rd, tm);
+                camera_sample<RT_DRAW_MS(MS)>(sc, P, i, j, s, rng, ro, rd, tm);
                 path_begin(ps, ro, rd, tm);
                 fresh = false;
             }
@@ -424,7 +424,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         pk.set2(PK_NCAST, 0u, 0u);
         pk.set2(PK_PIXEL, (uint32_t)i, (uint32_t)j);
         pk.set3(PK_L, mk(0.0, 0.0, 0.0));
-        if (!done) begin_sample<PK_THR, -1, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
+        if (!done) begin_sample<PK_THR, -1, PK_PDF, PK_PIXEL, RT_DRAW_MS(MS)>(sc, P, pk, slot, s, rng, ps);
         uint32_t it = 0; /* iterations of the wave: wave-uniform */
         bool pending = false; /* a shadow request is parked: PK_SWI, PK_STMAX, PK_CONTRIB, origin `so` */
         bool settle = false;  /* the sample in PK_L has ended: add it to the pixel sum once its shadow ray is resolved */
@@ -516,7 +516,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                     ++s;
                     done = s >= s_end;
                     RT_REGION(RG_BEGIN);
-                    if (!done) begin_sample<PK_THR, -1, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
+                    if (!done) begin_sample<PK_THR, -1, PK_PDF, PK_PIXEL, RT_DRAW_MS(MS)>(sc, P, pk, slot, s, rng, ps);
                 }
             }
             RT_REGION(RG_POLL);
@@ -533,7 +533,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         /* cast counters live in LDS as well */
         pk.set2(PK_NCAST, 0u, 0u);
         pk.set2(PK_PIXEL, (uint32_t)i, (uint32_t)j);
-        if (!done) begin_sample<PK_THR, PK_L, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
+        if (!done) begin_sample<PK_THR, PK_L, PK_PDF, PK_PIXEL, RT_DRAW_MS(MS)>(sc, P, pk, slot, s, rng, ps);
         PhaseClocks clk;
         uint32_t it = 0; /* iterations of the wave: wave-uniform */
         while (!done) {
@@ -617,7 +617,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
                 ++s;
                 done = s >= s_end;
                 RT_REGION(RG_BEGIN);
-                if (!done) begin_sample<PK_THR, PK_L, PK_PDF, PK_PIXEL>(sc, P, pk, slot, s, rng, ps);
+                if (!done) begin_sample<PK_THR, PK_L, PK_PDF, PK_PIXEL, RT_DRAW_MS(MS)>(sc, P, pk, slot, s, rng, ps);
             }
             RT_REGION(RG_COUNT);
             { /* one closest-hit cast per iteration of a live lane, and its shadow ray if it cast one */
@@ -856,7 +856,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         int i, j, s_end;
         pk.get2(PK_PIXEL, lo, hi);
         queue_unpack(lo, hi, i, j, s_end);
-        camera_sample(sc, QueueCamera::get(P.W, P.H), P.seed, P.W, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
+        camera_sample<RT_DRAW_MS(MS)>(sc, QueueCamera::get(P.W, P.H), P.seed, P.W, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
         ps.depth = 0, ps.specular_bounce = false;
         pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
         pk.set(PK_PDF, 0.0);
@@ -985,7 +985,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             if (!done) {
                 RT_REGION(RG_BEGIN);
                 const RenderK B = queue_image_size(P);
-                camera_sample(sc, QueueCamera::get(B.W, B.H), B.seed, B.W, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
+                camera_sample<RT_DRAW_MS(MS)>(sc, QueueCamera::get(B.W, B.H), B.seed, B.W, i, j, s, rng, ps.ro, ps.rd, ps.tm); /* begin_sample */
                 ps.depth = 0, ps.specular_bounce = false;
                 pk.set3(PK_THR, mk(1.0, 1.0, 1.0));
                 pk.set(PK_PDF, 0.0);

@@ -57,6 +57,7 @@ RT_DEV void tile_pixel(const RenderK& P, int slot, int tid, int& i, int& j, bool
 
 /* sample s of pixel (i, j): the generator under the per-sample seed, its two jitter draws and the camera ray
  * (renderer.h:73-75); rng goes on from its state after get_ray */
+template <bool JOIN = false>
 RT_DEV void camera_sample(const DScene& sc, const RenderK& P, int i, int j, int s, uint32_t& rng, V3& ro, V3& rd, Real& tm) {
     rng = rtr_sample_seed_inline(P.seed, P.W, i, j, s);
     const int region = RT_REGION_CURRENT();
@@ -65,7 +66,7 @@ RT_DEV void camera_sample(const DScene& sc, const RenderK& P, int i, int j, int 
     const Real u = (i + rng_next(rng)) / (P.W - 1);
     const Real v = (j + rng_next(rng)) / (P.H - 1);
     RT_REGION(region);
-    camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+    camera_get_ray<JOIN>(sc.camera, u, v, rng, ro, rd, tm);
 }
 /* The divisors of camera_sample belong to the launch: (double)(W - 1), (double)(H - 1) and their refined reciprocals are
  * made once in a kernel's prologue (udiv).  The pixel is an int and the jitter below 1, so the numerators are bounded;
@@ -80,6 +81,7 @@ RT_DEV CameraDiv camera_div_make(int W, int H) {
     c.w.safe = c.h.safe = (W != 1) & (H != 1);
     return c;
 }
+template <bool JOIN = false>
 RT_DEV void camera_sample(const DScene& sc, const CameraDiv& cd, uint32_t seed, int W, int i, int j, int s, uint32_t& rng, V3& ro,
                           V3& rd, Real& tm) {
     rng = rtr_sample_seed_inline(seed, W, i, j, s);
@@ -89,7 +91,7 @@ RT_DEV void camera_sample(const DScene& sc, const CameraDiv& cd, uint32_t seed, 
     const Real u = udiv<true>(i + rng_next(rng), cd.w);
     const Real v = udiv<true>(j + rng_next(rng), cd.h);
     RT_REGION(region);
-    camera_get_ray(sc.camera, u, v, rng, ro, rd, tm);
+    camera_get_ray<JOIN>(sc.camera, u, v, rng, ro, rd, tm);
 }
 
 /* samples [s0, s1) of chunk c of a pixel */

@@ -299,6 +299,66 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_sincos(unsigned long long* o
     if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
 }
 
+/* rtr_test_draw_forms: the joined form of a draw in (-1, 1) (rt_device.h: draw_sym_join, with its own high word and with
+ * the one from rng_hi(), as the rejection loops hold it) beside the plain text, for all 2^32 states.
+ * out[0] += states where it differs in any bit; out[1] += states tested; out[2]: one such state + 1 */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_draw_forms(unsigned long long* out) {
+    unsigned long long bad = 0, tested = 0;
+    const unsigned long long stride = (unsigned long long)gridDim.x * RTR_BLOCK;
+    const uint32_t hi = rng_hi();
+    for (unsigned long long k = (unsigned long long)blockIdx.x * RTR_BLOCK + threadIdx.x; k < (1ull << 32); k += stride) {
+        const uint32_t s = (uint32_t)k;
+        const bool differs = (__double_as_longlong(draw_sym_join(s)) != __double_as_longlong(draw_sym_plain(s))) |
+                             (__double_as_longlong(draw_sym_join(s, hi)) != __double_as_longlong(draw_sym_plain(s)));
+        if (differs) out[2] = k + 1;
+        bad += differs;
+        ++tested;
+    }
+    bad = wave_sum(bad);
+    tested = wave_sum(tested);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, bad);
+    if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
+}
+
+/* rtr_test_draw_callers: the functions that draw, with the joined form (JOIN) and in the plain text (this library's second
+ * instantiation), lane by lane from the same seeded state: random_in_unit_sphere, random_in_unit_disk,
+ * random_cosine_direction, rng_range(0.25, 7.5), rng_int(0, 6), in that order, the state carried from call to call (the
+ * last three draw through rng_next, which has one form).
+ * out[0] += lanes with an output bit or an exit state that differs; out[1] += lanes tested; out[2]: one such lane's seed
+ * state */
+#define RT_DRAW_WORDS 11
+template <bool JOIN>
+RT_DEV void draw_callers(uint32_t& s, long long* w, uint32_t* exits) {
+    V3 p = random_in_unit_sphere<JOIN>(s);
+    w[0] = __double_as_longlong(p.x), w[1] = __double_as_longlong(p.y), w[2] = __double_as_longlong(p.z), exits[0] = s;
+    p = random_in_unit_disk<JOIN>(s);
+    w[3] = __double_as_longlong(p.x), w[4] = __double_as_longlong(p.y), w[5] = __double_as_longlong(p.z), exits[1] = s;
+    p = random_cosine_direction(s);
+    w[6] = __double_as_longlong(p.x), w[7] = __double_as_longlong(p.y), w[8] = __double_as_longlong(p.z), exits[2] = s;
+    w[9] = __double_as_longlong(rng_range(s, 0.25, 7.5)), exits[3] = s;
+    w[10] = rng_int(s, 0, 6), exits[4] = s;
+}
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_draw_callers(unsigned long long* out, unsigned long long seed, long long n) {
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    unsigned long long bad = 0, tested = 0;
+    if (k < n) {
+        uint32_t s0 = (uint32_t)lane_mix(seed + (unsigned long long)k);
+        if (s0 == 0) s0 = 0x2545F491u; /* xorshift32 has no state 0 */
+        uint32_t a = s0, b = s0, ea[5], eb[5];
+        long long wa[RT_DRAW_WORDS], wb[RT_DRAW_WORDS];
+        draw_callers<true>(a, wa, ea);
+        draw_callers<false>(b, wb, eb);
+        bool differs = false;
+        for (int j = 0; j < RT_DRAW_WORDS; ++j) differs |= wa[j] != wb[j];
+        for (int j = 0; j < 5; ++j) differs |= ea[j] != eb[j];
+        if (differs) out[2] = s0;
+        bad = differs, tested = 1;
+    }
+    bad = wave_sum(bad), tested = wave_sum(tested);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, bad);
+    if ((threadIdx.x & 63) == 0 && tested) atomicAdd(out + 1, tested);
+}
+
 /* rtr_test_shared_division: div_shared() against the compiler's n / d on 2^32 operand pairs.  Three quarters of them
  * take both operands from the whole range the short form is used in (|d| in [2^-100, 2^100), |n| in [2^-300, 2^200),
  * random mantissas and signs); the rest are shaped like the rectangle test's (k - o) / d: a difference of two

@@ -15,6 +15,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace {
@@ -498,6 +499,75 @@ int rtr_test_lane_host(int32_t op, int32_t coarse_bits, const double* a, double*
             out[k] = s ? sqrt_short(a[k]) : __builtin_sqrt(a[k]);
         took_short[k] = s;
     }
+    return RTR_OK;
+}
+
+int rtr_test_draw_forms(rtr_context* c, uint64_t* mismatches, uint64_t* tested, uint64_t* first) {
+    if (!c || !mismatches || !tested || !first) return RTR_ERR_INVALID;
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc) return rc;
+    if ((rc = ensure(c, *t, 32))) return rc;
+    TCHK(c, hipMemsetAsync(t->buf, 0, 32, stream));
+    hipLaunchKernelGGL(k_test_draw_forms, dim3((unsigned)(n_cus * 16)), dim3(RTR_BLOCK), 0, stream, static_cast<unsigned long long*>(t->buf));
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream)); /* the kernel's stream, before the counters are read */
+    unsigned long long h[4] = {0};
+    TCHK(c, hipMemcpy(h, t->buf, sizeof h, hipMemcpyDeviceToHost));
+    *mismatches = h[0], *tested = h[1], *first = h[2];
+    return RTR_OK;
+}
+
+int rtr_test_draw_callers(rtr_context* c, uint64_t seed, int64_t n, uint64_t* mismatches, uint64_t* tested, uint64_t* first) {
+    if (!c || !mismatches || !tested || !first) return RTR_ERR_INVALID;
+    if (n < 1 || n > (1ll << 30)) return fail(c, RTR_ERR_INVALID, "bad lane count");
+    hipStream_t stream;
+    int n_cus;
+    TestState* t;
+    int rc = bare(c, stream, n_cus, t);
+    if (rc) return rc;
+    if ((rc = ensure(c, *t, 32))) return rc;
+    TCHK(c, hipMemsetAsync(t->buf, 0, 32, stream));
+    hipLaunchKernelGGL(k_test_draw_callers, grid_of(n), dim3(RTR_BLOCK), 0, stream, static_cast<unsigned long long*>(t->buf),
+                       (unsigned long long)seed, (long long)n);
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(stream));
+    unsigned long long h[4] = {0};
+    TCHK(c, hipMemcpy(h, t->buf, sizeof h, hipMemcpyDeviceToHost));
+    *mismatches = h[0], *tested = h[1], *first = h[2];
+    return RTR_OK;
+}
+
+int rtr_test_draw_host(const uint32_t* s, double* out, int64_t n) {
+    if (n < 0 || (n > 0 && (!s || !out))) return RTR_ERR_INVALID;
+    for (int64_t k = 0; k < n; ++k) out[k] = draw_sym_join(s[k]);
+    return RTR_OK;
+}
+
+int rtr_test_draw_host_range(uint64_t first, uint64_t count, uint64_t stride, int32_t threads, uint64_t* mismatches, uint64_t* tested) {
+    if (!mismatches || !tested || stride == 0 || threads < 1 || threads > 256) return RTR_ERR_INVALID;
+    if (first >= (1ull << 32) || count > (1ull << 32) || (count && first + (count - 1) * stride >= (1ull << 32))) return RTR_ERR_INVALID;
+    std::vector<uint64_t> bad((size_t)threads, 0), done((size_t)threads, 0);
+    auto work = [&](int w) {
+        const uint64_t k0 = count * (uint64_t)w / (uint64_t)threads, k1 = count * (uint64_t)(w + 1) / (uint64_t)threads;
+        uint64_t b = 0;
+        for (uint64_t k = k0; k < k1; ++k) {
+            const uint32_t v = (uint32_t)(first + k * stride);
+            const double y = draw_sym_join(v), y0 = draw_sym_plain(v);
+            uint64_t by, by0;
+            memcpy(&by, &y, 8), memcpy(&by0, &y0, 8);
+            b += by != by0;
+        }
+        bad[(size_t)w] = b, done[(size_t)w] = k1 - k0;
+    };
+    std::vector<std::thread> pool;
+    for (int w = 1; w < threads; ++w) pool.emplace_back(work, w);
+    work(0);
+    for (auto& th : pool) th.join();
+    *mismatches = 0, *tested = 0;
+    for (int w = 0; w < threads; ++w) *mismatches += bad[(size_t)w], *tested += done[(size_t)w];
     return RTR_OK;
 }
 

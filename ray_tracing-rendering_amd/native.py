@@ -44,7 +44,8 @@ TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_t
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
                 "rtr_test_pow5_host", "rtr_test_udiv", "rtr_test_scene_consts", "rtr_test_accum_load",
                 "rtr_test_accum_plan", "rtr_test_accum_commit", "rtr_test_rcp_lane", "rtr_test_sqrt_lane",
-                "rtr_test_lane_specials", "rtr_test_lane_host")
+                "rtr_test_lane_specials", "rtr_test_lane_host", "rtr_test_draw_forms", "rtr_test_draw_callers",
+                "rtr_test_draw_host", "rtr_test_draw_host_range")
 _TEST_LIB = None
 
 
@@ -250,6 +251,10 @@ def test_lib():
         getattr(T, name).argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3 + [vp]
     T.rtr_test_lane_specials.argtypes = [vp, C.c_int64]
     T.rtr_test_lane_host.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, C.c_int64]
+    T.rtr_test_draw_forms.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
+    T.rtr_test_draw_callers.argtypes = [vp, C.c_uint64, C.c_int64] + [C.POINTER(C.c_uint64)] * 3
+    T.rtr_test_draw_host.argtypes = [vp, vp, C.c_int64]
+    T.rtr_test_draw_host_range.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     T.rtr_test_accum_load.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
     T.rtr_test_accum_plan.argtypes = [vp, C.c_int64] + [C.c_int32] * 4 + [C.c_double, vp, vp, vp, vp, C.POINTER(C.c_int32)]
     T.rtr_test_accum_commit.argtypes = [vp, C.c_int64, vp, C.c_int32] + [vp] * 7
@@ -352,6 +357,27 @@ def lane_host(op, a, coarse_bits=0):
     if rc != 0:
         raise RtrError(rc, "rtr_test_lane_host")
     return out, took.astype(bool)
+
+
+def draw_host(s):
+    """rtr_test_draw_host (include/rtr_hip_test.h; no GPU needed): the host build of the joined form of a draw in (-1, 1)
+    over the states ``s`` (uint32): -1 + s * 2^-31, float64."""
+    s = np.ascontiguousarray(s, dtype=np.uint32).ravel()
+    out = np.zeros(s.size, dtype=np.float64)
+    rc = test_lib().rtr_test_draw_host(s.ctypes.data, out.ctypes.data, s.size)
+    if rc != 0:
+        raise RtrError(rc, "rtr_test_draw_host")
+    return out
+
+
+def draw_host_range(first, count, stride=1, threads=1):
+    """rtr_test_draw_host_range (include/rtr_hip_test.h; no GPU needed): the joined form beside the plain text on the
+    states first, first + stride, ... (``count`` of them), over ``threads`` threads.  Returns (mismatches, tested)."""
+    bad, tested = C.c_uint64(0), C.c_uint64(0)
+    rc = test_lib().rtr_test_draw_host_range(int(first), int(count), int(stride), int(threads), C.byref(bad), C.byref(tested))
+    if rc != 0:
+        raise RtrError(rc, "rtr_test_draw_host_range")
+    return bad.value, tested.value
 
 
 def queue_blocks_host(n_tiles, spp, chunks, guided=(0, 0, 0)):
@@ -999,6 +1025,21 @@ class Context:
         n, tested = C.c_uint64(0), C.c_uint64(0)
         self._chk(test_lib().rtr_test_sincos_exhaustive(self._h, C.byref(n), C.byref(tested)))
         return int(n.value), int(tested.value)
+
+    def draw_forms(self):
+        """rtr_test_draw_forms (include/rtr_hip_test.h): all 2^32 generator states through the joined form of a draw in
+        (-1, 1) and the plain text: (states where it differs in some bit, states compared, such a state + 1 or 0)."""
+        n, tested, first = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(test_lib().rtr_test_draw_forms(self._h, C.byref(n), C.byref(tested), C.byref(first)))
+        return int(n.value), int(tested.value), int(first.value)
+
+    def draw_callers(self, seed, n):
+        """rtr_test_draw_callers (include/rtr_hip_test.h): every function that draws, with the joined form and in the plain
+        text, from ``n`` states seeded by ``seed``: (lanes where an output bit or an exit state differs, lanes compared,
+        such a lane's starting state or 0)."""
+        bad, tested, first = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(test_lib().rtr_test_draw_callers(self._h, int(seed), int(n), C.byref(bad), C.byref(tested), C.byref(first)))
+        return int(bad.value), int(tested.value), int(first.value)
 
     def sincos_mismatches(self):
         """All 2^32 sampler angles: how many give sincos(phi) != (sin(phi), cos(phi)) in some bit (include/rtr_hip_test.h)."""
