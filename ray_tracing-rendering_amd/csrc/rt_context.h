@@ -45,9 +45,10 @@ struct rtr_context {
     /* per-render workspace */
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
-    DevBuf b_query; /* rtr_query_closest / rtr_query_occluded: one slice of rays and its results (nothing else uses it) */
-    DevBuf b_gather; /* rtr_gather_occlusion / rtr_gather_radiance: one slice of points and its results (nothing else uses it) */
-    DevBuf b_probe; /* rtr_probe_visibility / _radiance / _lookup: one slice of inputs and its results (nothing else uses it) */
+    /* the host entries of rtr_query_*, rtr_gather_*, rtr_probe_*: one slice of inputs and its results (staged_slices of
+     * rt_batch.h).  One buffer serves them all: each returns only behind its last slice's wait, and the device entries
+     * never touch it */
+    DevBuf b_batch;
     DevBuf b_display;    /* rtr_display_*: the sRGB thresholds (uploaded by rtr_create), the histogram, the DisplayRec */
     DevBuf b_display_io; /* rtr_display_host / _histogram: the image and its outputs (nothing else uses it) */
     std::vector<int> last_tiles; /* what b_tiles holds */

@@ -430,7 +430,7 @@ void rtr_destroy(rtr_context* c) {
     for (DevBuf& b : c->sb)
         if (b.p) hipFree(b.p);
     DevBuf* bufs[] = {&c->b_tiles, &c->b_partial, &c->b_done, &c->b_stats, &c->b_cancel, &c->b_test, &c->b_stage, &c->b_denoise,
-                      &c->b_query, &c->b_gather, &c->b_probe, &c->b_display, &c->b_display_io};
+                      &c->b_batch, &c->b_display, &c->b_display_io};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     c->pool.release();
@@ -790,11 +790,6 @@ int rtr_debug_frame_shapes(const rtr_scene_desc* s, int32_t* shapes, int64_t cap
     const LoweredScene L = lower_scene(s, info);
     *n_inst = L.ds.n_finst;
     for (int k = 0; k < L.ds.n_finst && k < cap; ++k) shapes[k] = L.cs.inst[(size_t)k].shape;
-    return RTR_OK;
-}
-int rtr_debug_last_gather(rtr_context* c, rtr_debug_gather* out, size_t size) {
-    if (!c || !out || size != sizeof(rtr_debug_gather)) return RTR_ERR_INVALID;
-    *out = c->last_gather;
     return RTR_OK;
 }
 int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {

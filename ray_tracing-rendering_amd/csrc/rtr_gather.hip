@@ -1,50 +1,22 @@
 /*
- * rtr_gather.hip -- hemisphere gathers (include/rtr_hip.h: rtr_gather_*): the entries, their checks, the launcher and the
- * 27 kernels it picks from (10 k_gather_any, 17 k_gather_li), and the host-only pieces that need no context
+ * rtr_gather.hip -- hemisphere gathers (include/rtr_hip.h: rtr_gather_*): the point check, the kernel choice among the
+ * 27 kernels held here (10 k_gather_any, 17 k_gather_li), the entries, and the host-only pieces that need no context
  * (rtr_gather_defaults, rtr_gather_ray).  Which k_gather_li a radiance gather runs is the k_li family rule of rt_select.h.
+ * The entries' common checks, the staging of the host entries, the body of the device entries, the launch set-up and the
+ * chunked launcher are rt_batch.h's, shared with the probes.
  */
-#include "rt_context.h"
+#include "rt_batch.h"
 
 using namespace rtr;
 
 namespace {
-
-constexpr long long kLaunchPoints = 1ll << 24; /* points per launch: at most 2^22 workgroups */
-
-template <typename Kern>
-int launch_gather(rtr_context* c, Kern kernel, const DScene& ds, const GatherK& all, size_t lds) {
-    if (int rc = set_lds(c, kernel, lds)) return rc;
-    for (long long k0 = 0; k0 < all.n; k0 += kLaunchPoints) {
-        GatherK K = all;
-        K.pts += k0, K.out += k0, K.point_base += (uint32_t)k0;
-        K.n = all.n - k0 < kLaunchPoints ? all.n - k0 : kLaunchPoints;
-        const long long lanes = K.n << K.lg;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), lds, c->stream, ds, K);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("gather launch: ") + hipGetErrorString(e));
-}
-
-/* RTR_OK, or RTR_ERR_INVALID with the reason in `err` */
-int gather_params_check(const rtr_gather_params* p, std::string& err) {
-    const char* why = gather_params_why(p);
-    if (!why) return RTR_OK;
-    err = std::string("rtr_gather_*: ") + why;
-    return RTR_ERR_INVALID;
-}
 
 constexpr int64_t kGatherSlice = (int64_t)1 << 20; /* points per slice of the host entries */
 
 /* what every gather entry checks before any device work; `radiance`: rp is checked too (a NULL one is invalid) */
 int gather_check(rtr_context* c, const rtr_render_params* rp, bool radiance, const rtr_gather_params* gp, const void* pts,
                  const void* out, int64_t n) {
-    if (!c) return RTR_ERR_INVALID;
-    if (int rc = gather_params_check(gp, c->err)) return rc;
-    if (n < 0 || (n > 0 && (!pts || !out))) return fail(c, RTR_ERR_INVALID, "rtr_gather_*: negative n or NULL array");
-    if (radiance)
-        if (int rc = params_check(c, rp)) return rc;
-    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_gather_* before rtr_upload_scene");
-    return RTR_OK;
+    return points_check(c, "rtr_gather_*", rp, radiance, gp, n, pts && out);
 }
 int gather_check_points(rtr_context* c, const rtr_gather_point* pts, int64_t n) {
     for (int64_t k = 0; k < n; ++k) {
@@ -66,54 +38,36 @@ bool gather_broadcast() {
 /* launches over device arrays on the context stream; rp: a radiance gather (k_gather_li), else occlusion (k_gather_any) */
 int gather_launch(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, uint32_t point_base,
                   const rtr_gather_point* d_pts, rtr_gather_out* d_out, int64_t n) {
-    const int integ = rp ? rp->integrator : -1;
-    const int per_ray = per_ray_trav(c->facts, c->info, rp ? rp->flags : gp->flags, !rp);
-    const int trav = rp ? li_trav(integ, per_ray) : per_ray;
-    const size_t lds = stack_bytes(c->facts, c->info, per_ray);
+    PointLaunch<GatherK> L = point_launch<GatherK>(c, rp, gp);
+    L.k.pts = d_pts, L.k.out = d_out, L.k.n = (long long)n, L.k.point_base = point_base;
     const bool broadcast = !rp && gather_broadcast();
-    DScene ds = c->ds;
-    if (!rp && !(gp->t_min >= 0x1p-100)) ds.shared_div = 0; /* the plain divisions, as k_query_* per wave */
-    const GatherK K{d_pts, d_out, (long long)n, gp->samples, gather_lg(gp->samples), gp->seed, point_base, gp->time, gp->t_min,
-                    gp->t_max, rp ? rp->max_depth : 0, rp ? rp->rr_start_depth : 0};
+    const size_t rec = sizeof(rtr_gather_out), lds = L.stack;
     int rc = RTR_OK;
     const bool found =
-        rp ? dispatch_li(integ, trav, [&](auto i, auto t) { rc = launch_gather(c, k_gather_li<decltype(i)::value, decltype(t)::value>, ds, K, lds); })
-           : dispatch_trav(TravsTop{}, trav, [&](auto t) {
+        rp ? dispatch_li(L.integ, L.trav, [&](auto i, auto t) { rc = launch_points(c, k_gather_li<decltype(i)::value, decltype(t)::value>, L.ds, L.k, rec, lds); })
+           : dispatch_trav(TravsTop{}, L.trav, [&](auto t) {
                  constexpr int T = decltype(t)::value;
-                 rc = broadcast ? launch_gather(c, k_gather_any<T, true>, ds, K, lds) : launch_gather(c, k_gather_any<T, false>, ds, K, lds);
+                 rc = broadcast ? launch_points(c, k_gather_any<T, true>, L.ds, L.k, rec, lds) : launch_points(c, k_gather_any<T, false>, L.ds, L.k, rec, lds);
              });
-    if (!found) return fail(c, RTR_ERR_UNSUPPORTED, "no gather kernel for traversal " + std::to_string(trav));
-    if (rc == RTR_OK) c->last_gather = rtr_debug_gather{integ, trav, broadcast, K.lg};
+    if (!found) return fail(c, RTR_ERR_UNSUPPORTED, "no gather kernel for traversal " + std::to_string(L.trav));
+    if (rc == RTR_OK) c->last_gather = rtr_debug_gather{L.integ, L.trav, broadcast, L.k.lg};
     return rc;
 }
 
+/* slices of at most kGatherSlice points (staged_slices of rt_batch.h), each at its point_base */
 int gather_host(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_gather_point* pts,
                 rtr_gather_out* out, int64_t n) {
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError(); /* a launch error of an earlier call is not this call's */
-    const int64_t slice = std::min(n, kGatherSlice);
-    const size_t in_bytes = (size_t)slice * sizeof(rtr_gather_point);
-    if (int rc = ensure(c, c->b_gather, in_bytes + (size_t)slice * sizeof(rtr_gather_out))) return rc;
-    rtr_gather_point* d_pts = static_cast<rtr_gather_point*>(c->b_gather.p);
-    rtr_gather_out* d_out = reinterpret_cast<rtr_gather_out*>(static_cast<char*>(c->b_gather.p) + in_bytes);
-    for (int64_t k0 = 0; k0 < n; k0 += slice) {
-        const int64_t m = std::min(slice, n - k0);
-        HIPCHK(c, hipMemcpyAsync(d_pts, pts + k0, (size_t)m * sizeof(rtr_gather_point), hipMemcpyHostToDevice, c->stream));
-        if (int rc = gather_launch(c, rp, gp, gp->point_base + (uint32_t)k0, d_pts, d_out, m)) return rc;
-        HIPCHK(c, hipMemcpyAsync(out + k0, d_out, (size_t)m * sizeof(rtr_gather_out), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream)); /* the next slice reuses the buffer */
-    }
-    return RTR_OK;
+    const StagedIO io{0, sizeof(rtr_gather_point), pts, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
+    return staged_slices(c, n, kGatherSlice, io, [&](const Slice& s) {
+        return gather_launch(c, rp, gp, gp->point_base + (uint32_t)s.k0, static_cast<const rtr_gather_point*>(s.in),
+                             static_cast<rtr_gather_out*>(s.out[0]), s.m);
+    });
 }
 
 int gather_device(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_gather_point* d_pts,
                   rtr_gather_out* d_out, int64_t n, int blocking) {
-    if (((uintptr_t)d_pts | (uintptr_t)d_out) & 7) return fail(c, RTR_ERR_INVALID, "rtr_gather_*_device: pointers must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError();
-    if (int rc = gather_launch(c, rp, gp, gp->point_base, d_pts, d_out, n)) return rc;
-    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return device_entry(c, "rtr_gather_*_device", (uintptr_t)d_pts | (uintptr_t)d_out, blocking,
+                        [&] { return gather_launch(c, rp, gp, gp->point_base, d_pts, d_out, n); });
 }
 
 } // namespace
@@ -158,19 +112,18 @@ void rtr_gather_defaults(rtr_gather_params* p) {
 
 int rtr_gather_ray(const rtr_gather_params* params, const rtr_gather_point* point, int64_t index_in_call, int32_t s,
                    rtr_ray* out) {
-    std::string err;
-    if (gather_params_check(params, err) || !point || !out || index_in_call < 0 || s < 0 || s >= params->samples)
-        return RTR_ERR_INVALID;
-    double nlen;
-    if (gather_point_bad(*point, nlen)) return RTR_ERR_INVALID;
-    const double r = 1 / nlen;
-    uint32_t rng = rtr_sample_seed_inline(params->seed, 1, 0, (int32_t)((uint32_t)index_in_call + params->point_base), s);
-    rtr_ray ray{};
-    gather_direction(r * point->n[0], r * point->n[1], r * point->n[2], rng, ray.direction[0], ray.direction[1], ray.direction[2]);
-    for (int a = 0; a < 3; ++a) ray.origin[a] = point->p[a];
-    ray.time = params->time, ray.t_min = params->t_min, ray.t_max = params->t_max;
-    ray.rng_state = rng;
-    *out = ray;
+    return sample_ray(params, point ? point->p : nullptr, index_in_call, s, out, [&](uint32_t& rng, double* d) {
+        double nlen;
+        if (gather_point_bad(*point, nlen)) return false;
+        const double r = 1 / nlen;
+        gather_direction(r * point->n[0], r * point->n[1], r * point->n[2], rng, d[0], d[1], d[2]);
+        return true;
+    });
+}
+
+int rtr_debug_last_gather(rtr_context* c, rtr_debug_gather* out, size_t size) {
+    if (!c || !out || size != sizeof(rtr_debug_gather)) return RTR_ERR_INVALID;
+    *out = c->last_gather;
     return RTR_OK;
 }
 

@@ -1,10 +1,12 @@
 /*
- * rtr_probe.hip -- light probes (include/rtr_hip.h: rtr_probe_*, rtr_sh_*): the entries, their checks, the launcher and
- * the 22 kernels it picks from (5 k_probe_any, 17 k_probe_li), k_probe_lookup, and the host-only pieces that need no
- * context (rtr_probe_ray, rtr_sh_basis, rtr_sh_irradiance).  Which k_probe_li a radiance call runs is the k_li family
- * rule of rt_select.h, like the gathers'.
+ * rtr_probe.hip -- light probes (include/rtr_hip.h: rtr_probe_*, rtr_sh_*): the point and grid checks, the kernel choice
+ * among the 22 kernels held here (5 k_probe_any, 17 k_probe_li), k_probe_lookup and its launch, the entries, and the
+ * host-only pieces that need no context (rtr_probe_ray, rtr_sh_basis, rtr_sh_irradiance, rtr_probe_lookup_one).  Which
+ * k_probe_li a radiance call runs is the k_li family rule of rt_select.h, like the gathers'.  The entries' common checks,
+ * the staging of the host entries, the body of the device entries, the launch set-up and the chunked launcher are
+ * rt_batch.h's, shared with the gathers.
  */
-#include "rt_context.h"
+#include "rt_batch.h"
 
 using namespace rtr;
 
@@ -24,41 +26,12 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_probe_lookup(const rtr_probe_grid
 
 namespace {
 
-constexpr long long kLaunchPoints = 1ll << 24; /* points per launch: at most 2^22 workgroups */
 constexpr int64_t kProbeSlice = (int64_t)1 << 20; /* points per slice of the host entries */
-
-template <typename Kern>
-int launch_probe(rtr_context* c, Kern kernel, const DScene& ds, const ProbeK& all, size_t rec, size_t lds) {
-    if (int rc = set_lds(c, kernel, lds)) return rc;
-    for (long long k0 = 0; k0 < all.n; k0 += kLaunchPoints) {
-        ProbeK K = all;
-        K.pts += k0, K.out = static_cast<char*>(all.out) + (size_t)k0 * rec, K.point_base += (uint32_t)k0;
-        K.n = all.n - k0 < kLaunchPoints ? all.n - k0 : kLaunchPoints;
-        const long long lanes = K.n << K.lg;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), lds, c->stream, ds, K);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("probe launch: ") + hipGetErrorString(e));
-}
-
-/* the gathers' parameter rules (rtr_gather_params is the block): RTR_OK, or RTR_ERR_INVALID with the reason in `err` */
-int probe_params_check(const rtr_gather_params* p, std::string& err) {
-    const char* why = gather_params_why(p);
-    if (!why) return RTR_OK;
-    err = std::string("rtr_probe_*: ") + why;
-    return RTR_ERR_INVALID;
-}
 
 /* what every probe entry checks before any device work; `radiance`: rp is checked too (a NULL one is invalid) */
 int probe_check(rtr_context* c, const rtr_render_params* rp, bool radiance, const rtr_gather_params* gp, const void* pts,
                 const void* out, int64_t n) {
-    if (!c) return RTR_ERR_INVALID;
-    if (int rc = probe_params_check(gp, c->err)) return rc;
-    if (n < 0 || (n > 0 && (!pts || !out))) return fail(c, RTR_ERR_INVALID, "rtr_probe_*: negative n or NULL array");
-    if (radiance)
-        if (int rc = params_check(c, rp)) return rc;
-    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_probe_* before rtr_upload_scene");
-    return RTR_OK;
+    return points_check(c, "rtr_probe_*", rp, radiance, gp, n, pts && out);
 }
 int probe_check_points(rtr_context* c, const rtr_probe_point* pts, int64_t n) {
     for (int64_t k = 0; k < n; ++k)
@@ -67,62 +40,40 @@ int probe_check_points(rtr_context* c, const rtr_probe_point* pts, int64_t n) {
     return RTR_OK;
 }
 
-size_t probe_record(bool radiance) { return radiance ? sizeof(rtr_probe_sh) : sizeof(rtr_probe_vis); }
-
 /* launches over device arrays on the context stream; rp: radiance probes (k_probe_li), else visibility (k_probe_any) */
 int probe_launch(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, uint32_t point_base,
                  const rtr_probe_point* d_pts, void* d_out, int64_t n) {
-    const int integ = rp ? rp->integrator : -1;
-    const int per_ray = per_ray_trav(c->facts, c->info, rp ? rp->flags : gp->flags, !rp);
-    const int trav = rp ? li_trav(integ, per_ray) : per_ray;
+    PointLaunch<ProbeK> L = point_launch<ProbeK>(c, rp, gp);
+    L.k.pts = d_pts, L.k.out = d_out, L.k.n = (long long)n, L.k.point_base = point_base;
     /* the traversal stack, and behind it the per-lane sums of k_probe_li (rt_kernels.h: ProbeSums) */
-    const size_t stack = stack_bytes(c->facts, c->info, per_ray);
-    const size_t lds = stack + (rp ? probe_sum_bytes() : 0);
-    DScene ds = c->ds;
-    if (!rp && !(gp->t_min >= 0x1p-100)) ds.shared_div = 0; /* the plain divisions, as the gathers */
-    const ProbeK K{d_pts, d_out, (long long)n, gp->samples, gather_lg(gp->samples), gp->seed, point_base, gp->time, gp->t_min,
-                   gp->t_max, rp ? rp->max_depth : 0, rp ? rp->rr_start_depth : 0, (int)(stack / sizeof(int))};
+    L.k.sum_word = (int)(L.stack / sizeof(int));
+    const size_t lds = L.stack + (rp ? probe_sum_bytes() : 0);
     int rc = RTR_OK;
     const bool found =
-        rp ? dispatch_li(integ, trav, [&](auto i, auto t) {
-                 rc = launch_probe(c, k_probe_li<decltype(i)::value, decltype(t)::value>, ds, K, sizeof(rtr_probe_sh), lds);
+        rp ? dispatch_li(L.integ, L.trav, [&](auto i, auto t) {
+                 rc = launch_points(c, k_probe_li<decltype(i)::value, decltype(t)::value>, L.ds, L.k, sizeof(rtr_probe_sh), lds);
              })
-           : dispatch_trav(TravsTop{}, trav, [&](auto t) {
-                 rc = launch_probe(c, k_probe_any<decltype(t)::value>, ds, K, sizeof(rtr_probe_vis), lds);
+           : dispatch_trav(TravsTop{}, L.trav, [&](auto t) {
+                 rc = launch_points(c, k_probe_any<decltype(t)::value>, L.ds, L.k, sizeof(rtr_probe_vis), lds);
              });
-    if (!found) return fail(c, RTR_ERR_UNSUPPORTED, "no probe kernel for traversal " + std::to_string(trav));
-    if (rc == RTR_OK) c->last_probe = rtr_debug_probe{integ, trav, K.lg};
+    if (!found) return fail(c, RTR_ERR_UNSUPPORTED, "no probe kernel for traversal " + std::to_string(L.trav));
+    if (rc == RTR_OK) c->last_probe = rtr_debug_probe{L.integ, L.trav, L.k.lg};
     return rc;
 }
 
+/* slices of at most kProbeSlice points (staged_slices of rt_batch.h), each at its point_base */
 int probe_host(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_probe_point* pts, void* out,
                int64_t n) {
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError(); /* a launch error of an earlier call is not this call's */
-    const size_t rec = probe_record(rp != nullptr);
-    const int64_t slice = std::min(n, kProbeSlice);
-    const size_t in_bytes = (size_t)slice * sizeof(rtr_probe_point);
-    if (int rc = ensure(c, c->b_probe, in_bytes + (size_t)slice * rec)) return rc;
-    rtr_probe_point* d_pts = static_cast<rtr_probe_point*>(c->b_probe.p);
-    char* d_out = static_cast<char*>(c->b_probe.p) + in_bytes;
-    for (int64_t k0 = 0; k0 < n; k0 += slice) {
-        const int64_t m = std::min(slice, n - k0);
-        HIPCHK(c, hipMemcpyAsync(d_pts, pts + k0, (size_t)m * sizeof(rtr_probe_point), hipMemcpyHostToDevice, c->stream));
-        if (int rc = probe_launch(c, rp, gp, gp->point_base + (uint32_t)k0, d_pts, d_out, m)) return rc;
-        HIPCHK(c, hipMemcpyAsync(static_cast<char*>(out) + (size_t)k0 * rec, d_out, (size_t)m * rec, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream)); /* the next slice reuses the buffer */
-    }
-    return RTR_OK;
+    const StagedIO io{0, sizeof(rtr_probe_point), pts, {rp ? sizeof(rtr_probe_sh) : sizeof(rtr_probe_vis), 0}, {out, nullptr}};
+    return staged_slices(c, n, kProbeSlice, io, [&](const Slice& s) {
+        return probe_launch(c, rp, gp, gp->point_base + (uint32_t)s.k0, static_cast<const rtr_probe_point*>(s.in), s.out[0], s.m);
+    });
 }
 
 int probe_device(rtr_context* c, const rtr_render_params* rp, const rtr_gather_params* gp, const rtr_probe_point* d_pts, void* d_out,
                  int64_t n, int blocking) {
-    if (((uintptr_t)d_pts | (uintptr_t)d_out) & 7) return fail(c, RTR_ERR_INVALID, "rtr_probe_*_device: pointers must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError();
-    if (int rc = probe_launch(c, rp, gp, gp->point_base, d_pts, d_out, n)) return rc;
-    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return device_entry(c, "rtr_probe_*_device", (uintptr_t)d_pts | (uintptr_t)d_out, blocking,
+                        [&] { return probe_launch(c, rp, gp, gp->point_base, d_pts, d_out, n); });
 }
 
 bool probe_grid_ok(const rtr_probe_grid* g, std::string& why) {
@@ -139,13 +90,12 @@ bool probe_grid_ok(const rtr_probe_grid* g, std::string& why) {
     return true;
 }
 
-/* what both lookup entries check before any device work */
+/* what both lookup entries check before any device work, in this order: context, grid, n / NULL; no scene is needed */
 int lookup_check(rtr_context* c, const rtr_probe_grid* g, const void* probes, const void* q, const void* out, int64_t n) {
     if (!c) return RTR_ERR_INVALID;
     std::string why;
     if (!probe_grid_ok(g, why)) return fail(c, RTR_ERR_INVALID, "rtr_probe_lookup: " + why);
-    if (n < 0 || (n > 0 && (!probes || !q || !out))) return fail(c, RTR_ERR_INVALID, "rtr_probe_lookup: negative n or NULL array");
-    return RTR_OK;
+    return batch_check(c, "rtr_probe_lookup", n, probes && q && out);
 }
 int lookup_launch(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_sh* d_probes, const rtr_gather_point* d_q,
                   rtr_gather_out* d_out, int64_t n) {
@@ -192,18 +142,11 @@ int rtr_probe_radiance_device(rtr_context* c, const rtr_render_params* rp, const
 }
 
 int rtr_probe_ray(const rtr_gather_params* params, const rtr_probe_point* point, int64_t index_in_call, int32_t s, rtr_ray* out) {
-    std::string err;
-    if (probe_params_check(params, err) || !point || !out || index_in_call < 0 || s < 0 || s >= params->samples)
-        return RTR_ERR_INVALID;
-    if (probe_point_bad(*point)) return RTR_ERR_INVALID;
-    uint32_t rng = rtr_sample_seed_inline(params->seed, 1, 0, (int32_t)((uint32_t)index_in_call + params->point_base), s);
-    rtr_ray ray{};
-    probe_direction(rng, ray.direction[0], ray.direction[1], ray.direction[2]);
-    for (int a = 0; a < 3; ++a) ray.origin[a] = point->p[a];
-    ray.time = params->time, ray.t_min = params->t_min, ray.t_max = params->t_max;
-    ray.rng_state = rng;
-    *out = ray;
-    return RTR_OK;
+    return sample_ray(params, point ? point->p : nullptr, index_in_call, s, out, [&](uint32_t& rng, double* d) {
+        if (probe_point_bad(*point)) return false;
+        probe_direction(rng, d[0], d[1], d[2]);
+        return true;
+    });
 }
 
 void rtr_sh_basis(const double d[3], double y[9]) {
@@ -238,38 +181,23 @@ int rtr_probe_lookup(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_sh
             return fail(c, RTR_ERR_INVALID, "rtr_probe_lookup: bad query at index " + std::to_string(k) +
                                                 " (non-finite position / normal, or a normal whose length is not in (0, inf))");
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError();
+    /* the grid stays at the head of the staging buffer for all slices: the first one brings it */
+    static_assert(sizeof(rtr_probe_sh) % 16 == 0, "StagedIO::head_bytes");
     const size_t grid_bytes = (size_t)g->dims[0] * g->dims[1] * g->dims[2] * sizeof(rtr_probe_sh);
-    const int64_t slice = std::min(n, kProbeSlice);
-    const size_t in_bytes = (size_t)slice * sizeof(rtr_gather_point);
-    if (int rc = ensure(c, c->b_probe, grid_bytes + in_bytes + (size_t)slice * sizeof(rtr_gather_out))) return rc;
-    char* base = static_cast<char*>(c->b_probe.p);
-    rtr_probe_sh* d_probes = reinterpret_cast<rtr_probe_sh*>(base);
-    rtr_gather_point* d_q = reinterpret_cast<rtr_gather_point*>(base + grid_bytes);
-    rtr_gather_out* d_out = reinterpret_cast<rtr_gather_out*>(base + grid_bytes + in_bytes);
-    HIPCHK(c, hipMemcpyAsync(d_probes, probes, grid_bytes, hipMemcpyHostToDevice, c->stream));
-    for (int64_t k0 = 0; k0 < n; k0 += slice) {
-        const int64_t m = std::min(slice, n - k0);
-        HIPCHK(c, hipMemcpyAsync(d_q, q + k0, (size_t)m * sizeof(rtr_gather_point), hipMemcpyHostToDevice, c->stream));
-        if (int rc = lookup_launch(c, g, d_probes, d_q, d_out, m)) return rc;
-        HIPCHK(c, hipMemcpyAsync(out + k0, d_out, (size_t)m * sizeof(rtr_gather_out), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return RTR_OK;
+    const StagedIO io{grid_bytes, sizeof(rtr_gather_point), q, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
+    return staged_slices(c, n, kProbeSlice, io, [&](const Slice& s) {
+        if (s.k0 == 0) HIPCHK(c, hipMemcpyAsync(s.head, probes, grid_bytes, hipMemcpyHostToDevice, c->stream));
+        return lookup_launch(c, g, static_cast<const rtr_probe_sh*>(s.head), static_cast<const rtr_gather_point*>(s.in),
+                             static_cast<rtr_gather_out*>(s.out[0]), s.m);
+    });
 }
 
 int rtr_probe_lookup_device(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_sh* d_probes, const rtr_gather_point* d_q,
                             rtr_gather_out* d_out, int64_t n, int blocking) {
     if (int rc = lookup_check(c, g, d_probes, d_q, d_out, n)) return rc;
     if (n == 0) return RTR_OK;
-    if (((uintptr_t)d_probes | (uintptr_t)d_q | (uintptr_t)d_out) & 7)
-        return fail(c, RTR_ERR_INVALID, "rtr_probe_lookup_device: pointers must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError();
-    if (int rc = lookup_launch(c, g, d_probes, d_q, d_out, n)) return rc;
-    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return device_entry(c, "rtr_probe_lookup_device", (uintptr_t)d_probes | (uintptr_t)d_q | (uintptr_t)d_out, blocking,
+                        [&] { return lookup_launch(c, g, d_probes, d_q, d_out, n); });
 }
 
 int rtr_debug_last_probe(rtr_context* c, rtr_debug_probe* out, size_t size) {

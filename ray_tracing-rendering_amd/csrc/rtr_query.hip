@@ -1,8 +1,10 @@
 /*
  * rtr_query.hip -- ray queries (include/rtr_hip.h: rtr_query_*): hittable::hit of the scene root for caller-given rays,
- * closest hit and occlusion, from host or device arrays.  Holds the k_query_closest / k_query_any instantiations.
+ * closest hit and occlusion, from host or device arrays: the ray check, the launch and the k_query_closest / k_query_any
+ * instantiations it picks from.  The entries' common checks, the staging of the host entries and the body of the device
+ * entries are rt_batch.h's.
  */
-#include "rt_context.h"
+#include "rt_batch.h"
 
 using namespace rtr;
 
@@ -10,13 +12,12 @@ namespace {
 
 constexpr int64_t kQuerySlice = (int64_t)1 << 22; /* rays per slice of the host entries */
 
-/* what every query entry checks before any device work */
+/* what every query entry checks before any device work, in this order: context, flags, n / NULL, scene */
 int query_check(rtr_context* c, const void* rays, const void* out, int64_t n, int32_t flags) {
     if (!c) return RTR_ERR_INVALID;
     if (flags & ~RTR_FLAG_REFERENCE_ORDER) return fail(c, RTR_ERR_INVALID, "rtr_query_*: unknown flag bits");
-    if (n < 0 || (n > 0 && (!rays || !out))) return fail(c, RTR_ERR_INVALID, "rtr_query_*: negative n or NULL array");
-    if (!c->has_scene) return fail(c, RTR_ERR_NO_SCENE, "rtr_query_* before rtr_upload_scene");
-    return RTR_OK;
+    if (int rc = batch_check(c, "rtr_query_*", n, rays && out)) return rc;
+    return scene_check(c, "rtr_query_*");
 }
 int query_check_rays(rtr_context* c, const rtr_ray* rays, int64_t n) {
     const bool media = c->info.has_media != 0;
@@ -68,43 +69,21 @@ int query_launch(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, uin
     return RTR_OK;
 }
 
-/* the host entries: slices of at most kQuerySlice rays through c->b_query, everything stream-ordered on the context
- * stream (behind a render that is still running; its workspace, statistics and events are not touched) */
+/* the host entries: slices of at most kQuerySlice rays (staged_slices of rt_batch.h); closest hit has one output stream,
+ * occlusion two, of which rng_out may be NULL */
 int query_host(rtr_context* c, const rtr_ray* rays, rtr_ray_hit* hits, uint8_t* occ, uint32_t* rng_out, int64_t n, int flags) {
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError(); /* a launch error of an earlier call is not this call's */
-    const int64_t slice = std::min(n, kQuerySlice);
-    const size_t in_bytes = (size_t)slice * sizeof(rtr_ray);
-    const size_t out_bytes = hits ? (size_t)slice * sizeof(rtr_ray_hit) : (size_t)slice * sizeof(uint32_t);
-    const size_t occ_bytes = hits ? 0 : (((size_t)slice + 15) & ~(size_t)15);
-    if (int rc = ensure(c, c->b_query, in_bytes + out_bytes + occ_bytes)) return rc;
-    char* base = static_cast<char*>(c->b_query.p);
-    rtr_ray* d_rays = reinterpret_cast<rtr_ray*>(base);
-    rtr_ray_hit* d_hits = hits ? reinterpret_cast<rtr_ray_hit*>(base + in_bytes) : nullptr;
-    uint32_t* d_rng = hits ? nullptr : reinterpret_cast<uint32_t*>(base + in_bytes);
-    uint8_t* d_occ = hits ? nullptr : reinterpret_cast<uint8_t*>(base + in_bytes + out_bytes);
-    for (int64_t k0 = 0; k0 < n; k0 += slice) {
-        const int64_t m = std::min(slice, n - k0);
-        HIPCHK(c, hipMemcpyAsync(d_rays, rays + k0, (size_t)m * sizeof(rtr_ray), hipMemcpyHostToDevice, c->stream));
-        if (int rc = query_launch(c, d_rays, d_hits, d_occ, d_rng, m, flags)) return rc;
-        if (hits) {
-            HIPCHK(c, hipMemcpyAsync(hits + k0, d_hits, (size_t)m * sizeof(rtr_ray_hit), hipMemcpyDeviceToHost, c->stream));
-        } else {
-            HIPCHK(c, hipMemcpyAsync(occ + k0, d_occ, (size_t)m, hipMemcpyDeviceToHost, c->stream));
-            if (rng_out) HIPCHK(c, hipMemcpyAsync(rng_out + k0, d_rng, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream)); /* the next slice reuses the buffer */
-    }
-    return RTR_OK;
+    const StagedIO io = hits ? StagedIO{0, sizeof(rtr_ray), rays, {sizeof(rtr_ray_hit), 0}, {hits, nullptr}}
+                             : StagedIO{0, sizeof(rtr_ray), rays, {sizeof(uint8_t), sizeof(uint32_t)}, {occ, rng_out}};
+    return staged_slices(c, n, kQuerySlice, io, [&](const Slice& s) {
+        const rtr_ray* d_rays = static_cast<const rtr_ray*>(s.in);
+        return hits ? query_launch(c, d_rays, static_cast<rtr_ray_hit*>(s.out[0]), nullptr, nullptr, s.m, flags)
+                    : query_launch(c, d_rays, nullptr, static_cast<uint8_t*>(s.out[0]), static_cast<uint32_t*>(s.out[1]), s.m, flags);
+    });
 }
 
 int query_device(rtr_context* c, const rtr_ray* d_rays, rtr_ray_hit* d_hits, uint8_t* d_occ, uint32_t* d_rng, int64_t n, int flags,
                  int blocking) {
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)hipGetLastError();
-    if (int rc = query_launch(c, d_rays, d_hits, d_occ, d_rng, n, flags)) return rc;
-    if (blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return device_entry(c, nullptr, 0, blocking, [&] { return query_launch(c, d_rays, d_hits, d_occ, d_rng, n, flags); });
 }
 
 } // namespace

@@ -402,51 +402,42 @@ def queue_pack_host(i, j, s_end):
     return (lo.value, hi.value), tuple(int(v) for v in out)
 
 
-def denoise_defaults(**overrides):
-    """rtr_denoise_params with the library's defaults (rtr_denoise_defaults), fields replaced by ``overrides``."""
-    p = A.DenoiseParamsC()
-    lib().rtr_denoise_defaults(C.byref(p))
+def _defaults(struct, c_function, allowed_fields, overrides):
+    """A ``struct`` filled by the library's ``c_function`` (rtr_*_defaults), then the ``allowed_fields`` that ``overrides``
+    names replaced; TypeError for any other name.  The subject in the message is the middle of the function's name."""
+    p = struct()
+    getattr(lib(), c_function)(C.byref(p))
     for k, v in overrides.items():
-        if k not in ("iterations", "feature_spp", "sigma_l", "sigma_n", "sigma_a", "sigma_z"):
-            raise TypeError("no denoise parameter %r" % k)
+        if k not in allowed_fields:
+            raise TypeError("no %s parameter %r" % (c_function.split("_")[1], k))
         setattr(p, k, v)
     return p
+
+
+def denoise_defaults(**overrides):
+    """rtr_denoise_params with the library's defaults (rtr_denoise_defaults), fields replaced by ``overrides``."""
+    return _defaults(A.DenoiseParamsC, "rtr_denoise_defaults",
+                     ("iterations", "feature_spp", "sigma_l", "sigma_n", "sigma_a", "sigma_z"), overrides)
 
 
 def temporal_defaults(**overrides):
     """rtr_temporal_params with the library's defaults (rtr_temporal_defaults), fields replaced by ``overrides``."""
-    p = A.TemporalParamsC()
-    lib().rtr_temporal_defaults(C.byref(p))
-    for k, v in overrides.items():
-        if k not in ("alpha_min", "tau_z", "tau_n", "min_weight"):
-            raise TypeError("no temporal parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _defaults(A.TemporalParamsC, "rtr_temporal_defaults", ("alpha_min", "tau_z", "tau_n", "min_weight"), overrides)
 
 
 def display_defaults(**overrides):
     """rtr_display_params with the library's defaults (rtr_display_defaults), fields replaced by ``overrides``."""
-    p = A.DisplayParamsC()
-    lib().rtr_display_defaults(C.byref(p))
-    for k, v in overrides.items():
-        if k not in ("auto_exposure", "meter_permille", "tone_curve", "encoding", "exposure", "key", "white"):
-            raise TypeError("no display parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _defaults(A.DisplayParamsC, "rtr_display_defaults",
+                     ("auto_exposure", "meter_permille", "tone_curve", "encoding", "exposure", "key", "white"), overrides)
 
 
 def gather_defaults(**overrides):
     """rtr_gather_params with the library's defaults (rtr_gather_defaults: samples 64, seed 0, point_base 0, flags 0, time 0,
     t_min 0.001, t_max inf), fields replaced by ``overrides``; ``reference_order=True`` sets RTR_FLAG_REFERENCE_ORDER."""
-    p = A.GatherParamsC()
-    lib().rtr_gather_defaults(C.byref(p))
     if overrides.pop("reference_order", False):
-        p.flags |= A.FLAG_REFERENCE_ORDER
-    for k, v in overrides.items():
-        if k not in ("samples", "seed", "point_base", "flags", "time", "t_min", "t_max"):
-            raise TypeError("no gather parameter %r" % k)
-        setattr(p, k, v)
-    return p
+        overrides.setdefault("flags", A.FLAG_REFERENCE_ORDER)  # onto the default flags, 0; an explicit flags= replaces them
+    return _defaults(A.GatherParamsC, "rtr_gather_defaults", ("samples", "seed", "point_base", "flags", "time", "t_min", "t_max"),
+                     overrides)
 
 
 def gather_points(points, normals):
@@ -462,19 +453,23 @@ def gather_points(points, normals):
 def gather_rays(points, normals=None, params=None, **overrides):
     """rtr_gather_ray for every sample of every point (host only, no context): the ``RAY_DTYPE`` rays [n, samples] the
     gathers cast, with the generator state after the direction's draws.  Raises RtrError for a bad point or bad params."""
-    L = lib()
+    return _ray_table("rtr_gather_ray", gather_points(points, normals), params, overrides)
+
+
+def _ray_table(c_function, pts, params, overrides):
+    """``c_function`` (rtr_gather_ray / rtr_probe_ray) for every sample of every record of ``pts``: ``RAY_DTYPE`` [n, samples]"""
+    ray_of = getattr(lib(), c_function)
     gp = params if params is not None else gather_defaults(**overrides)
-    pts = gather_points(points, normals)
     n_s = int(gp.samples)
     if not 1 <= n_s <= A.GATHER_MAX_SAMPLES:
-        raise RtrError(A.RTR_ERR_INVALID, "rtr_gather_ray: samples outside 1 .. 2^20")
+        raise RtrError(A.RTR_ERR_INVALID, "%s: samples outside 1 .. 2^20" % c_function)
     rays = np.zeros((len(pts), n_s), dtype=A.RAY_DTYPE)
-    base, stride, size = pts.ctypes.data, A.GATHER_POINT_DTYPE.itemsize, A.RAY_DTYPE.itemsize
+    base, stride, size = pts.ctypes.data, pts.dtype.itemsize, A.RAY_DTYPE.itemsize
     for k in range(len(pts)):
         for s in range(n_s):
-            rc = L.rtr_gather_ray(C.byref(gp), base + k * stride, k, s, rays.ctypes.data + (k * n_s + s) * size)
+            rc = ray_of(C.byref(gp), base + k * stride, k, s, rays.ctypes.data + (k * n_s + s) * size)
             if rc != 0:
-                raise RtrError(rc, "rtr_gather_ray: bad params or bad point at index %d" % k)
+                raise RtrError(rc, "%s: bad params or bad point at index %d" % (c_function, k))
     return rays
 
 
@@ -491,20 +486,7 @@ def probe_points(points):
 def probe_rays(points, params=None, **overrides):
     """rtr_probe_ray for every sample of every probe (host only, no context): the ``RAY_DTYPE`` rays [n, samples] the probe
     kernels cast, uniform over the sphere, with the generator state after the direction's draws."""
-    L = lib()
-    gp = params if params is not None else gather_defaults(**overrides)
-    pts = probe_points(points)
-    n_s = int(gp.samples)
-    if not 1 <= n_s <= A.GATHER_MAX_SAMPLES:
-        raise RtrError(A.RTR_ERR_INVALID, "rtr_probe_ray: samples outside 1 .. 2^20")
-    rays = np.zeros((len(pts), n_s), dtype=A.RAY_DTYPE)
-    base, stride, size = pts.ctypes.data, A.PROBE_POINT_DTYPE.itemsize, A.RAY_DTYPE.itemsize
-    for k in range(len(pts)):
-        for s in range(n_s):
-            rc = L.rtr_probe_ray(C.byref(gp), base + k * stride, k, s, rays.ctypes.data + (k * n_s + s) * size)
-            if rc != 0:
-                raise RtrError(rc, "rtr_probe_ray: bad params or bad point at index %d" % k)
-    return rays
+    return _ray_table("rtr_probe_ray", probe_points(points), params, overrides)
 
 
 def sh_basis(directions):
@@ -609,6 +591,21 @@ def denoise_host(ctx, color, q, count, feat, params=None, rgb8=False, out=None):
     ctx._chk(ctx._L.rtr_denoise_host(ctx._h, C.byref(prm), w, h, color.ctypes.data, q.ctypes.data, count.ctypes.data,
                                      feat.ctypes.data, None if rgb8 else out.ctypes.data, out.ctypes.data if rgb8 else None))
     return out
+
+
+def _records_out(out, n, dtype):
+    """The output array of a query, gather or probe entry: ``out`` if it can take ``n`` records of ``dtype``, a zeroed
+    array when it is None."""
+    if out is None:
+        return np.zeros(n, dtype=dtype)
+    if out.dtype != dtype or len(out) < n or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous array of at least %d records of the entry's output dtype" % n)
+    return out
+
+
+def _into_tail(in_ptr, out_ptr, n, blocking):
+    """The last four arguments of a gather, probe or lookup device entry"""
+    return C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(n), 1 if blocking else 0
 
 
 class Context:
@@ -749,10 +746,7 @@ class Context:
         ``RAY_HIT_DTYPE`` array.  ``origins`` may be a ready ``RAY_DTYPE`` array (the other ray arguments are then
         ignored).  Blocking; raises RtrError (RTR_ERR_INVALID) naming the first bad ray, with ``out`` untouched."""
         rays = self._rays(origins, directions, times, t_min, t_max, rng_states)
-        if out is None:
-            out = np.zeros(len(rays), dtype=A.RAY_HIT_DTYPE)
-        elif out.dtype != A.RAY_HIT_DTYPE or len(out) < len(rays) or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous RAY_HIT_DTYPE array of at least %d records" % len(rays))
+        out = _records_out(out, len(rays), A.RAY_HIT_DTYPE)
         flags = A.FLAG_REFERENCE_ORDER if reference_order else 0
         self._chk(self._L.rtr_query_closest(self._h, rays.ctypes.data, out.ctypes.data, len(rays), flags))
         return out
@@ -782,14 +776,6 @@ class Context:
                                                     A.FLAG_REFERENCE_ORDER if reference_order else 0, 1 if blocking else 0))
 
     # hemisphere gathers (include/rtr_hip.h: rtr_gather_*)
-    @staticmethod
-    def _gather_out(out, n):
-        if out is None:
-            return np.zeros(n, dtype=A.GATHER_OUT_DTYPE)
-        if out.dtype != A.GATHER_OUT_DTYPE or len(out) < n or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous GATHER_OUT_DTYPE array of at least %d records" % n)
-        return out
-
     def gather_occlusion(self, points, normals=None, samples=64, seed=0, t_max=np.inf, t_min=0.001, time=0.0, point_base=0,
                          reference_order=False, params=None, out=None):
         """rtr_gather_occlusion: ``samples`` cosine-distributed rays about every normal, any-hit cast in [t_min, t_max] and
@@ -800,7 +786,7 @@ class Context:
         gp = params if params is not None else gather_defaults(
             samples=samples, seed=seed, t_max=t_max, t_min=t_min, time=time, point_base=point_base, reference_order=reference_order)
         pts = gather_points(points, normals)
-        out = self._gather_out(out, len(pts))
+        out = _records_out(out, len(pts), A.GATHER_OUT_DTYPE)
         self._chk(self._L.rtr_gather_occlusion(self._h, C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
         return out
 
@@ -811,7 +797,7 @@ class Context:
         gp = gather_params if gather_params is not None else gather_defaults(samples=samples, seed=seed, time=time,
                                                                              point_base=point_base)
         pts = gather_points(points, normals)
-        out = self._gather_out(out, len(pts))
+        out = _records_out(out, len(pts), A.GATHER_OUT_DTYPE)
         self._chk(self._L.rtr_gather_radiance(self._h, C.byref(params), C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
         return out
 
@@ -819,14 +805,13 @@ class Context:
         """rtr_gather_occlusion_device: n ``GATHER_POINT_DTYPE`` records at device pointer ``points_ptr`` ->
         ``GATHER_OUT_DTYPE`` records at ``out_ptr``, on the context stream behind what is queued there."""
         gp = params if params is not None else gather_defaults(**overrides)
-        self._chk(self._L.rtr_gather_occlusion_device(self._h, C.byref(gp), C.c_void_p(points_ptr), C.c_void_p(out_ptr), int(n),
-                                                      1 if blocking else 0))
+        self._chk(self._L.rtr_gather_occlusion_device(self._h, C.byref(gp), *_into_tail(points_ptr, out_ptr, n, blocking)))
 
     def gather_radiance_into(self, params, points_ptr, out_ptr, n, gather_params=None, blocking=False, **overrides):
         """rtr_gather_radiance_device: the device-pointer form of ``gather_radiance``."""
         gp = gather_params if gather_params is not None else gather_defaults(**overrides)
-        self._chk(self._L.rtr_gather_radiance_device(self._h, C.byref(params), C.byref(gp), C.c_void_p(points_ptr),
-                                                     C.c_void_p(out_ptr), int(n), 1 if blocking else 0))
+        self._chk(self._L.rtr_gather_radiance_device(self._h, C.byref(params), C.byref(gp),
+                                                     *_into_tail(points_ptr, out_ptr, n, blocking)))
 
     @staticmethod
     def gather_rays(points, normals=None, params=None, **overrides):
@@ -834,14 +819,6 @@ class Context:
         return gather_rays(points, normals, params, **overrides)
 
     # light probes (include/rtr_hip.h: rtr_probe_*)
-    @staticmethod
-    def _probe_out(out, n, dtype):
-        if out is None:
-            return np.zeros(n, dtype=dtype)
-        if out.dtype != dtype or len(out) < n or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous array of at least %d probe records" % n)
-        return out
-
     def probe_visibility(self, points, samples=64, seed=0, t_max=np.inf, t_min=0.001, time=0.0, point_base=0,
                          reference_order=False, params=None, out=None):
         """rtr_probe_visibility: ``samples`` rays uniform over the sphere from every point, any-hit cast in [t_min, t_max],
@@ -851,7 +828,7 @@ class Context:
         gp = params if params is not None else gather_defaults(
             samples=samples, seed=seed, t_max=t_max, t_min=t_min, time=time, point_base=point_base, reference_order=reference_order)
         pts = probe_points(points)
-        out = self._probe_out(out, len(pts), A.PROBE_VIS_DTYPE)
+        out = _records_out(out, len(pts), A.PROBE_VIS_DTYPE)
         self._chk(self._L.rtr_probe_visibility(self._h, C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
         return out
 
@@ -862,7 +839,7 @@ class Context:
         gp = gather_params if gather_params is not None else gather_defaults(samples=samples, seed=seed, time=time,
                                                                              point_base=point_base)
         pts = probe_points(points)
-        out = self._probe_out(out, len(pts), A.PROBE_SH_DTYPE)
+        out = _records_out(out, len(pts), A.PROBE_SH_DTYPE)
         self._chk(self._L.rtr_probe_radiance(self._h, C.byref(params), C.byref(gp), pts.ctypes.data, out.ctypes.data, len(pts)))
         return out
 
@@ -870,14 +847,13 @@ class Context:
         """rtr_probe_visibility_device: n ``PROBE_POINT_DTYPE`` records at device pointer ``points_ptr`` ->
         ``PROBE_VIS_DTYPE`` records at ``out_ptr``, on the context stream behind what is queued there."""
         gp = params if params is not None else gather_defaults(**overrides)
-        self._chk(self._L.rtr_probe_visibility_device(self._h, C.byref(gp), C.c_void_p(points_ptr), C.c_void_p(out_ptr), int(n),
-                                                      1 if blocking else 0))
+        self._chk(self._L.rtr_probe_visibility_device(self._h, C.byref(gp), *_into_tail(points_ptr, out_ptr, n, blocking)))
 
     def probe_radiance_into(self, params, points_ptr, out_ptr, n, gather_params=None, blocking=False, **overrides):
         """rtr_probe_radiance_device: the device-pointer form of ``probe_radiance``."""
         gp = gather_params if gather_params is not None else gather_defaults(**overrides)
-        self._chk(self._L.rtr_probe_radiance_device(self._h, C.byref(params), C.byref(gp), C.c_void_p(points_ptr),
-                                                    C.c_void_p(out_ptr), int(n), 1 if blocking else 0))
+        self._chk(self._L.rtr_probe_radiance_device(self._h, C.byref(params), C.byref(gp),
+                                                    *_into_tail(points_ptr, out_ptr, n, blocking)))
 
     @staticmethod
     def probe_rays(points, params=None, **overrides):
@@ -892,14 +868,14 @@ class Context:
         if len(probes) != grid.dims[0] * grid.dims[1] * grid.dims[2]:
             raise ValueError("probes must hold dims[0] * dims[1] * dims[2] records")
         q = gather_points(points, normals)
-        out = self._gather_out(out, len(q))
+        out = _records_out(out, len(q), A.GATHER_OUT_DTYPE)
         self._chk(self._L.rtr_probe_lookup(self._h, C.byref(grid), probes.ctypes.data, q.ctypes.data, out.ctypes.data, len(q)))
         return out
 
     def probe_lookup_into(self, grid, probes_ptr, queries_ptr, out_ptr, n, blocking=False):
         """rtr_probe_lookup_device: the same over device pointers, on the context stream behind what is queued there."""
-        self._chk(self._L.rtr_probe_lookup_device(self._h, C.byref(grid), C.c_void_p(probes_ptr), C.c_void_p(queries_ptr),
-                                                  C.c_void_p(out_ptr), int(n), 1 if blocking else 0))
+        self._chk(self._L.rtr_probe_lookup_device(self._h, C.byref(grid), C.c_void_p(probes_ptr),
+                                                  *_into_tail(queries_ptr, out_ptr, n, blocking)))
 
     # display transform (include/rtr_hip.h: rtr_display_*)
     @staticmethod
