@@ -962,6 +962,113 @@ int rtr_probe_lookup_device(rtr_context* ctx, const rtr_probe_grid* grid, const 
 int rtr_probe_lookup_one(const rtr_probe_grid* grid, const rtr_probe_sh* probes, const rtr_gather_point* query,
                          rtr_gather_out* out);
 
+/* ---- environment captures: cube maps of radiance about points in space, their lookup, and Radiance .hdr output ----
+ * Gathers and probes reduce what arrives at a point to one normal or to nine coefficients.  A capture keeps the directions:
+ * for each of `n` centres (rtr_probe_point) six faces of S x S texels, each texel the mean of Integrator::Li over
+ * N = params->samples rays through it, made in registers and reduced inside the wave like a gather.  The texel record is
+ * rtr_gather_out (v = mean radiance, count = N, valid); the records are laid out [centre][face f][row b][column a], so a
+ * call writes n * 6 * S * S of them.  Texels are indexed in 64 bits; 1 <= S <= 4096 (6 S^2 and a centre's texel index fit
+ * an int32).  Every output bit is defined here; only + - * / sqrt and compares are used on the way to a ray, in the order
+ * written, so a host, numpy and the device give the same bits (rtr_capture_ray is the host form).
+ *
+ * RAY s (0 <= s < N) of texel e = (f * S + b) * S + a of centre k (k = its index in the call + params->point_base, taken
+ * modulo 2^32):
+ *   state = rtr_sample_seed_inline(seed, 6 * S * S, e, (int32_t)k, s)            (rtr_seed.h)
+ *   jitter = 1: two draws of the reference's random_double (core/rtweekend.h:24-34), each one xorshift32 step (13, 17, 5)
+ *               and then state * 2^-32: ju first, then jv.  jitter = 0: ju = jv = 0.5 and nothing is drawn.
+ *   u = (2.0 * (a + ju)) / S - 1.0;  v = (2.0 * (b + jv)) / S - 1.0               (a, b and S converted to double)
+ *   d0 by face:  0 (+x): ( 1, -v, -u)    1 (-x): (-1, -v,  u)    2 (+y): ( u,  1,  v)
+ *                3 (-y): ( u, -1, -v)    4 (+z): ( u, -v,  1)    5 (-z): (-u, -v, -1)
+ *   d = unit(d0)                    unit(w) = (1 / sqrt(w.x*w.x + w.y*w.y + w.z*w.z)) * w, the gathers'
+ * The ray is (origin = the centre, direction d, time) and the state left after the draws enters Li: x_s = what rtr_li_rays
+ * returns for that ray and state under render->integrator, max_depth, rr_start_depth and flags, exactly as for
+ * rtr_gather_radiance.  Face f looks down its axis with u to the right and v downwards as seen from the centre (the usual
+ * cube-map table): row 0 is the top row of a face.
+ *
+ * REDUCTION: the gathers', word for word: G = min(64, bit_ceil(N)); lane l adds its samples l, l + G, ... in increasing
+ * order into +0.0; then for off = G/2, ..., 1: a[l] = a[l] + a[l xor off]; then v = (1.0 / N) * a[0].  count = N.
+ *
+ * A centre is BAD if a component of p is not finite.  The host entry rejects the whole batch with RTR_ERR_INVALID, names
+ * the first bad index in rtr_last_error and leaves the outputs untouched; the device entry writes an all-zero record
+ * (valid 0) for every texel of such a centre without casting, and every other texel gets valid = 1.
+ *
+ * params: face_size and samples as above; jitter 0 or 1; time finite; reserved 0.  Anything else, a NULL render, n < 0 or
+ * a NULL array is RTR_ERR_INVALID; a call before rtr_upload_scene is RTR_ERR_NO_SCENE -- all before any device work, in
+ * the gathers' order.  n == 0 is RTR_OK without a launch.  The host entry takes host arrays and blocks; it stages the
+ * centres once in the buffer of the gathers' host entries and brings the records back in slices of at most 2^20 texels.
+ * The device entry takes device pointers (8-byte aligned; in and out must not overlap), runs on the context stream behind
+ * whatever is queued there and returns at once unless `blocking`.  Neither touches anything a queued render or accumulator
+ * pass uses, nor the statistics of rtr_get_stats; rtr_cancel does not apply.  Centres can be sharded over contexts: shard
+ * j passes point_base = its first centre's index. */
+typedef struct rtr_capture_params { /* 48 bytes */
+    int32_t face_size, samples;
+    uint32_t seed, point_base;
+    int32_t jitter, pad;            /* pad must be 0 */
+    double time;
+    double reserved[2];
+} rtr_capture_params;
+
+/* face_size 32, samples 16, seed 0, point_base 0, jitter 1, time 0 */
+void rtr_capture_defaults(rtr_capture_params* p);
+
+int rtr_capture_cube(rtr_context* ctx, const rtr_render_params* render, const rtr_capture_params* params,
+                     const rtr_probe_point* centres, rtr_gather_out* out, int64_t n);
+int rtr_capture_cube_device(rtr_context* ctx, const rtr_render_params* render, const rtr_capture_params* params,
+                            const rtr_probe_point* d_centres, rtr_gather_out* d_out, int64_t n, int blocking);
+
+/* Host-only, needs no context: ray s of texel (a, b) of face `face` of the centre at `index_in_call` (the definition
+ * above; `point` is that centre's record, not an array).  out->t_min = 0.001 and out->t_max = +inf, the defaults of the
+ * queries: Li does not read them.  RTR_ERR_INVALID for a bad centre, bad params, a negative index, a face outside 0..5,
+ * a or b outside [0, S) or s outside [0, samples). */
+int rtr_capture_ray(const rtr_capture_params* params, const rtr_probe_point* point, int64_t index_in_call, int32_t face,
+                    int32_t a, int32_t b, int32_t s, rtr_ray* out);
+
+/* CUBE LOOKUP: the radiance of ONE capture (`texels`: its 6 S^2 records, 1 <= face_size <= 4096) along caller-given
+ * directions; an rtr_probe_point holds a direction (x, y, z) here, which need not be normalised.
+ *   major axis: the one of largest |component|; on a tie x wins over y and y over z.  m = that |component|.
+ *   face and (u, v), the inverse of the table above, one division each:
+ *     x major: x > 0: face 0, u = -z / m   else face 1, u =  z / m;   v = -y / m
+ *     y major: y > 0: face 2, v =  z / m   else face 3, v = -z / m;   u =  x / m
+ *     z major: z > 0: face 4, u =  x / m   else face 5, u = -x / m;   v = -y / m
+ *   per axis, with c = u for the columns and c = v for the rows:
+ *     g = ((c + 1.0) * S) * 0.5 - 0.5;  g = min(max(g, 0.0), (double)(S - 1))      (clamped to the face)
+ *     i0 = (int)g;  if i0 > S - 2: i0 = max(S - 2, 0);   t = g - (double)i0, and t = 0 when S == 1;  w0 = 1.0 - t, w1 = t
+ *   the four texels are visited with the row offset db outermost, then the column offset da, each in {0, 1}, indices
+ *   clipped to S - 1:  w = wa[da] * wb[db];  a texel is USED if w > 0;  acc = +0.0;  acc[ch] = acc[ch] + w * texel.v[ch]
+ * The filter is bilinear inside the face only: there is NO filtering across faces, a direction near a cube edge reads
+ * the clamped texels of its own face.  Result: v = acc, count = the texels used, valid 1.  {0, 0, 0, count 0, valid 0}
+ * when a component of the direction is not finite, sqrt(x*x + y*y + z*z) is not in (0, +inf), or a used texel has
+ * valid == 0 -- the entries reject nothing per direction.  face_size outside 1 .. 4096, n < 0 or a NULL array is
+ * RTR_ERR_INVALID; n == 0 is RTR_OK; no scene is needed.  The host entry stages the texels once and the directions in
+ * slices of 2^20; the device entry is stream-ordered like the gathers' (8-byte aligned pointers, `blocking`). */
+int rtr_cube_lookup(rtr_context* ctx, int32_t face_size, const rtr_gather_out* texels, const rtr_probe_point* directions,
+                    rtr_gather_out* out, int64_t n);
+int rtr_cube_lookup_device(rtr_context* ctx, int32_t face_size, const rtr_gather_out* d_texels,
+                           const rtr_probe_point* d_directions, rtr_gather_out* d_out, int64_t n, int blocking);
+/* Host-only, needs no context: the lookup of one direction over HOST texels, the same function the kernel calls. */
+int rtr_cube_lookup_one(int32_t face_size, const rtr_gather_out* texels, const rtr_probe_point* direction,
+                        rtr_gather_out* out);
+
+/* Host-only (uses libm): the direction of the centre of texel (i, j) of a W x H equirectangular map under the
+ * reference's mapping (lighting/environmental_light.h:225-232): u = (i + 0.5) / W, v = (j + 0.5) / H,
+ * phi = 2 pi u - pi, theta = pi v, d = (sin(theta) * cos(phi), cos(theta), -sin(theta) * sin(phi)).  Row 0 is the top.
+ * RTR_ERR_INVALID for W or H < 1, a texel outside the map or a NULL d. */
+int rtr_latlong_direction(int32_t W, int32_t H, int32_t i, int32_t j, double d[3]);
+
+/* Host-only: out_rgb[(j * W + i) * 3 + ch] = rtr_cube_lookup_one(face_size, texels, rtr_latlong_direction(W, H, i, j)).v[ch],
+ * and nothing else (an invalid lookup gives 0).  RTR_ERR_INVALID for a bad size or a NULL pointer. */
+int rtr_cube_to_latlong(int32_t face_size, const rtr_gather_out* texels, int32_t W, int32_t H, double* out_rgb);
+
+/* Host-only: writes H rows (row 0 first: the top) of W texels, 3 doubles each, as a Radiance picture with flat
+ * scanlines: the header "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y H +X W\n", then 4 bytes per texel.  A negative or NaN
+ * channel counts as 0; m = the largest channel.  m < 1e-32: four zero bytes.  Otherwise (f, e) = frexp(m),
+ * scale = (f * 256.0) / m, each of the three bytes is (int)(c * scale), at most 255, and the fourth is e + 128 (m above
+ * 2^127 is stored as four bytes 255: the format ends there).  A reader's texel is byte * 2^(e - 136): never above the
+ * input, and below it by less than 2^(e - 136).  (Inherent to flat files: readers take a file of 8 <= W < 32768 whose
+ * very first texel is the bytes 2, 2, b < 128 for run-length encoded.)  RTR_ERR_INVALID for W or H < 1 or a NULL pointer,
+ * RTR_ERR_DEVICE when the file cannot be written. */
+int rtr_write_rgbe(const char* path, int32_t W, int32_t H, const double* rgb);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

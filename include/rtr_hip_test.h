@@ -81,6 +81,13 @@ typedef struct rtr_probe_record {
 /* size_of_out must be sizeof(rtr_probe_record) */
 int rtr_test_last_probe(rtr_context* ctx, rtr_probe_record* out, size_t size_of_out);
 
+/* And for the environment captures: k_capture_li<integ, trav> of the last rtr_capture_cube call; trav = -1: none yet. */
+typedef struct rtr_capture_record {
+    int32_t integ, trav, lg;
+} rtr_capture_record;
+/* size_of_out must be sizeof(rtr_capture_record) */
+int rtr_test_last_capture(rtr_context* ctx, rtr_capture_record* out, size_t size_of_out);
+
 /* What the library makes of a scene before anything reaches a device: the validator, the host-only lowering
  * (csrc/rt_lower.h: lower_scene) and the two decisions every launch hangs on -- pick_trav and, for `integrator` and the
  * render `flags`, mega_variant (csrc/rt_select.h).  Needs no context and no GPU.  RT_TRAV_*, RT_MS_*, RT_TIE_FLAG and

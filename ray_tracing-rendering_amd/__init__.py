@@ -24,10 +24,11 @@ def __getattr__(name):
         return importlib.import_module(__name__ + "." + name)
     if name in ("Context", "RtrError", "library_path", "denoise_defaults", "denoise_host", "temporal_defaults",
                 "History", "display_defaults", "srgb_thresholds", "gather_defaults", "gather_rays",
-                "probe_rays", "sh_basis", "sh_irradiance", "probe_grid"):
+                "probe_rays", "sh_basis", "sh_irradiance", "probe_grid", "capture_defaults", "capture_ray", "capture_rays",
+                "cube_lookup_host", "latlong_direction", "cube_to_latlong", "write_rgbe"):
         from . import native
         return getattr(native, name)
-    if name in ("Renderer", "RenderBuffer", "ProbeGrid", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):
+    if name in ("Renderer", "RenderBuffer", "ProbeGrid", "Cubemap", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):
         from . import renderer
         return getattr(renderer, name)
     raise AttributeError(name)

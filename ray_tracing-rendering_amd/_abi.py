@@ -64,6 +64,7 @@ PROBE_VIS_DTYPE = np.dtype([("c", "<f8", (9,)), ("count", "<i4"), ("valid", "<i4
 PROBE_SH_DTYPE = np.dtype([("c", "<f8", (9, 3)), ("count", "<i4"), ("valid", "<i4")])
 assert PROBE_POINT_DTYPE.itemsize == 24 and PROBE_VIS_DTYPE.itemsize == 80 and PROBE_SH_DTYPE.itemsize == 224
 PROBE_GRID_MAX = 1 << 24
+CAPTURE_MAX_FACE = 4096  # rtr_capture_cube / rtr_cube_lookup: the largest face_size
 
 # golden-vector records (rtr_testrec.h, packed)
 LI_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("s", "<i4"), ("rng_exit", "<u4"), ("L", "<f8", (3,)),
@@ -148,6 +149,16 @@ class ProbeGridC(C.Structure):
 
 PROBE_GRID_SIZE = 64
 assert C.sizeof(ProbeGridC) == PROBE_GRID_SIZE
+
+
+class CaptureParamsC(C.Structure):
+    """rtr_capture_params (include/rtr_hip.h): the environment captures of rtr_capture_cube"""
+    _fields_ = [("face_size", C.c_int32), ("samples", C.c_int32), ("seed", C.c_uint32), ("point_base", C.c_uint32),
+                ("jitter", C.c_int32), ("pad", C.c_int32), ("time", C.c_double), ("reserved", C.c_double * 2)]
+
+
+CAPTURE_PARAMS_SIZE = 48
+assert C.sizeof(CaptureParamsC) == CAPTURE_PARAMS_SIZE
 
 
 class DenoiseParamsC(C.Structure):

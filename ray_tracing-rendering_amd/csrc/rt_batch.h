@@ -1,6 +1,6 @@
 /*
  * rt_batch.h -- host only: what the units that answer a batch of caller records share (rtr_query.hip, rtr_gather.hip,
- * rtr_probe.hip).  The entry checks they have in common, the one path of a host entry from the caller's array to the
+ * rtr_probe.hip, rtr_capture.hip).  The entry checks they have in common, the one path of a host entry from the caller's array to the
  * kernel and back (staged_slices), the body of a device-pointer entry (device_entry), and for the gathers and probes the
  * launch set-up, the chunked launcher and the single-ray entry.  No device code; the kernels and which one a call runs
  * stay with the units.
@@ -47,8 +47,10 @@ inline int points_check(rtr_context* c, const char* who, const rtr_render_params
  * next slice reuses the buffer; so the call returns with nothing of its own queued.  All record checks are the caller's
  * and come before this: a failing entry leaves the outputs untouched. */
 struct StagedIO {
-    size_t head_bytes;  /* kept at the head of the buffer for the caller (the grid of rtr_probe_lookup), a multiple of 16 */
-    size_t in_rec;      /* bytes per input record */
+    size_t head_bytes;  /* kept at the head of the buffer for the caller (the grid of rtr_probe_lookup, the centres of
+                           rtr_capture_cube), a multiple of 16 */
+    size_t in_rec;      /* bytes per input record; 0: the slices have no input of their own (rtr_capture_cube: a record is
+                           a texel, and its input is the centre at the head) */
     const void* in;
     size_t out_rec[2];  /* bytes per record of each output stream; 0: no such stream */
     void* out[2];       /* nullptr: the stream is staged for the kernel but not copied back (rng_out of rtr_query_occluded) */
@@ -73,8 +75,9 @@ int staged_slices(rtr_context* c, int64_t n, int64_t slice_len, const StagedIO& 
         if (io.out_rec[o]) s.out[o] = next, next += room(io.out_rec[o]);
     for (s.k0 = 0; s.k0 < n; s.k0 += slice) {
         s.m = std::min(slice, n - s.k0);
-        HIPCHK(c, hipMemcpyAsync(s.in, static_cast<const char*>(io.in) + (size_t)s.k0 * io.in_rec, (size_t)s.m * io.in_rec,
-                                 hipMemcpyHostToDevice, c->stream));
+        if (io.in_rec)
+            HIPCHK(c, hipMemcpyAsync(s.in, static_cast<const char*>(io.in) + (size_t)s.k0 * io.in_rec, (size_t)s.m * io.in_rec,
+                                     hipMemcpyHostToDevice, c->stream));
         if (int rc = launch(s)) return rc;
         for (int o = 0; o < 2; ++o)
             if (io.out_rec[o] && io.out[o])
@@ -137,6 +140,21 @@ int launch_points(rtr_context* c, Kern kernel, const DScene& ds, const K& all, s
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("point kernel launch: ") + hipGetErrorString(e));
+}
+
+/* The same for the captures, whose records are texels: the launches split on the record of all.out (CaptureK::k0, n), the
+ * centre array stays where it is */
+template <typename Kern>
+int launch_texels(rtr_context* c, Kern kernel, const DScene& ds, const CaptureK& all, size_t lds) {
+    if (int rc = set_lds(c, kernel, lds)) return rc;
+    for (long long k0 = all.k0; k0 < all.n; k0 += kLaunchPoints) {
+        CaptureK k = all;
+        k.k0 = k0, k.n = all.n - k0 < kLaunchPoints ? all.n : k0 + kLaunchPoints;
+        const long long lanes = (k.n - k.k0) << k.lg;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), lds, c->stream, ds, k);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("capture kernel launch: ") + hipGetErrorString(e));
 }
 
 /* rtr_gather_ray / rtr_probe_ray: sample `s` of the point at `origin`, record `index_in_call` of a call with `params`.

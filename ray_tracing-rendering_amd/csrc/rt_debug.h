@@ -46,6 +46,12 @@ struct rtr_debug_probe {
     int trav;  /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no probe call yet */
     int lg;    /* log2 of the lanes that share a point */
 };
+/* the capture kernel the last rtr_capture_cube call launched (of its last slice), recorded like a gather's */
+struct rtr_debug_capture {
+    int integ; /* k_capture_li<integ, trav> */
+    int trav;  /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no capture yet */
+    int lg;    /* log2 of the lanes that share a texel */
+};
 struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     double L[3];
     uint32_t rng_exit;
@@ -72,6 +78,7 @@ int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t
 int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
 int rtr_debug_last_gather(rtr_context* ctx, rtr_debug_gather* out, size_t size_of_out);
 int rtr_debug_last_probe(rtr_context* ctx, rtr_debug_probe* out, size_t size_of_out);
+int rtr_debug_last_capture(rtr_context* ctx, rtr_debug_capture* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);
 void rtr_debug_set_error(rtr_context* ctx, const char* msg); /* rtr_last_error() of a failing rtr_test_* call */
 /* Synthetic state into an accumulator, so that the product's own k_accum_errors / _plan / _commit / _resolve(_scatter) run on

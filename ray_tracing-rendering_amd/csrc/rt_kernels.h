@@ -15,6 +15,7 @@
  *              rays in registers, casts them (any-hit / Integrator::Li) and reduces them inside the wave.
  *  k_probe_any / k_probe_li     light probes (rtr_probe_*): the gathers' mapping over the whole sphere, every sample projected
  *              onto nine spherical harmonics; 9 or 27 sums per point instead of 3.
+ *  k_capture_li   environment captures (rtr_capture_cube): the gathers' mapping with a cube-map texel as the point.
  *  k_features  first-hit albedo / normal / depth of a pixel's first K camera samples (rtr_accum_features).
  *  k_query_closest / k_query_any   hittable::hit of the scene root for caller-given rays (rtr_query_*).
  * Template kernels only, instantiated by the unit that launches them.  The non-template kernels live in one header per
@@ -1260,7 +1261,9 @@ RT_DEV uint32_t gather_ray(const GatherK& K, const GatherLane& L, int s, V3& d) 
     gather_direction(L.w.x, L.w.y, L.w.z, rng, d.x, d.y, d.z);
     return rng;
 }
-RT_DEV void gather_end(const GatherK& K, const GatherLane& L, V3 a, int count) {
+/* (K, L: GatherK and GatherLane, or the capture's CaptureK and CaptureLane, which have the members this reads) */
+template <typename KT, typename LT>
+RT_DEV void gather_end(const KT& K, const LT& L, V3 a, int count) {
     for (int off = (1 << K.lg) >> 1; off > 0; off >>= 1) {
         a.x = a.x + __shfl_xor(a.x, off, 64), a.y = a.y + __shfl_xor(a.y, off, 64), a.z = a.z + __shfl_xor(a.z, off, 64);
         count = count + __shfl_xor(count, off, 64);
@@ -1439,4 +1442,65 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_probe_li(const DScene sc, const P
         for (int ch = 0; ch < 3; ++ch) o.c[i][ch] = L.cast ? scale * a[3 * i + ch] : 0.0;
     o.count = L.cast ? count : 0, o.valid = L.cast ? 1 : 0;
     static_cast<rtr_probe_sh*>(K.out)[L.k] = o;
+}
+
+/* rtr_capture_cube: a cube map of mean radiance about each centre, N rays through every texel (include/rtr_hip.h has the
+ * contract).  A texel is a "point" of the gathers' mapping: global lane g serves record K.k0 + g / G of K.out as lane g % G,
+ * a group never leaves its wave, lanes without a sample, of a bad centre or past the end carry +0.0 / 0 through every
+ * __shfl_xor, lane 0 of a group stores the record: gather_end as it is.  Begin and ray are the capture's own: the texel
+ * number of the call (K.first + record) gives the centre (texel / 6 S^2) and (face, row, column), capture_direction of
+ * rt_render.h the direction. */
+struct CaptureLane {
+    long long k; /* record of K.out of this lane's group */
+    int l;       /* lane in the group */
+    bool cast;   /* the texel exists and its centre is not bad */
+    V3 p;
+    int e, f, a, b;   /* texel of the centre's capture: e = (f * S + b) * S + a */
+    uint32_t centre;  /* the centre's number under the seed: its index in the call + point_base */
+};
+RT_DEV bool capture_begin(const CaptureK& K, CaptureLane& L) {
+    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (K.k0 + ((g & ~63ll) >> K.lg) >= K.n) return false; /* the whole wave is past the end */
+    L.k = K.k0 + (g >> K.lg), L.l = (int)(g & ((1 << K.lg) - 1));
+    const bool live = L.k < K.n;
+    const long long texel = K.first + (live ? L.k : K.k0);
+    const long long c = texel / K.F;
+    L.e = (int)(texel - c * K.F);
+    L.f = L.e / K.SS;
+    const int r = L.e - L.f * K.SS;
+    L.b = r / K.S, L.a = r - L.b * K.S;
+    L.centre = (uint32_t)c + K.point_base;
+    rtr_probe_point q;
+    for (int i = 0; i < 3; ++i) q.p[i] = 0.0;
+    if (live) q = K.pts[c];
+    L.cast = !probe_point_bad(q) && live;
+    L.p = ld3(q.p);
+    return true;
+}
+RT_DEV uint32_t capture_ray(const CaptureK& K, const CaptureLane& L, int s, V3& d) {
+    uint32_t rng = rtr_sample_seed_inline(K.seed, K.F, L.e, (int32_t)L.centre, s);
+    capture_direction(K.S, L.f, L.a, L.b, K.jitter, rng, d.x, d.y, d.z);
+    return rng;
+}
+template <int INTEG, int TRAV>
+__global__ void __launch_bounds__(RTR_BLOCK) k_capture_li(const DScene sc, const CaptureK K) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    CaptureLane L;
+    if (!capture_begin(K, L)) return;
+    V3 a = mk(0.0, 0.0, 0.0);
+    int count = 0;
+    if (L.cast)
+        for (int s = L.l; s < K.samples; s += 1 << K.lg) {
+            V3 d;
+            uint32_t rng = capture_ray(K, L, s, d);
+            PathState ps;
+            path_begin(ps, L.p, d, K.time);
+            PathCounters cnt;
+            cnt.closest = 0, cnt.shadow = 0;
+            while (bounce<INTEG, TRAV>(sc, ps, rng, st, K.max_depth, K.rr_start, cnt)) {
+            }
+            a = add(a, ps.L), ++count;
+        }
+    gather_end(K, L, a, count);
 }

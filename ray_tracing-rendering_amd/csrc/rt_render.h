@@ -307,6 +307,101 @@ RT_HD rtr_gather_out probe_lookup_one(const rtr_probe_grid& g, const rtr_probe_s
     return o;
 }
 
+/* ---- environment captures (include/rtr_hip.h: rtr_capture_*, rtr_cube_*) ----
+ * The arithmetic of that contract, written once for host (rtr_capture_ray, rtr_cube_lookup_one, the entries' checks) and
+ * device (k_capture_li, k_cube_lookup): the same rules as the gathers' above. */
+#define RTR_CAPTURE_MAX_FACE 4096 /* rtr_hip.h: 6 S^2 and every texel of one centre fit an int32 */
+struct CaptureK {
+    const rtr_probe_point* pts; /* the centres of the whole call */
+    rtr_gather_out* out;        /* out[0] is the record of texel `first` of the call */
+    long long first;            /* texels are numbered through the call: centre * 6 S^2 + e */
+    long long k0, n;            /* this launch serves the records [k0, n) of `out` */
+    int S, SS, F;               /* face size, S^2, 6 S^2 */
+    int samples, lg;            /* N; log2 of the group size, the gathers' gather_lg */
+    uint32_t seed, point_base;
+    int jitter;
+    double time;
+    int max_depth, rr_start;
+};
+/* why `p` is no valid parameter block, or nullptr */
+inline const char* capture_params_why(const rtr_capture_params* p) {
+    if (!p) return "null capture params";
+    if (p->face_size < 1 || p->face_size > RTR_CAPTURE_MAX_FACE) return "face_size outside 1 .. 4096";
+    if (p->samples < 1 || p->samples > (1 << 20)) return "samples outside 1 .. 2^20";
+    if (p->jitter != 0 && p->jitter != 1) return "jitter must be 0 or 1";
+    if (!__builtin_isfinite(p->time)) return "time not finite";
+    if (p->pad != 0 || p->reserved[0] != 0 || p->reserved[1] != 0) return "pad and reserved must be 0";
+    return nullptr;
+}
+/* direction of the ray through texel (a, b) of face f of an S x S cube map whose generator is `rng`; rng is left
+ * behind the jitter's draws (none without jitter) */
+RT_HD void capture_direction(int S, int f, int a, int b, int jitter, uint32_t& rng, double& dx, double& dy, double& dz) {
+    double ju = 0.5, jv = 0.5;
+    if (jitter) { /* random_double, core/rtweekend.h:24-34: one step, then state * 2^-32 */
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        ju = rng * 2.3283064365386962890625e-10;
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        jv = rng * 2.3283064365386962890625e-10;
+    }
+    const double u = (2.0 * (a + ju)) / S - 1.0;
+    const double v = (2.0 * (b + jv)) / S - 1.0;
+    double x, y, z;
+    switch (f) {
+    case 0: x = 1.0, y = -v, z = -u; break;
+    case 1: x = -1.0, y = -v, z = u; break;
+    case 2: x = u, y = 1.0, z = v; break;
+    case 3: x = u, y = -1.0, z = -v; break;
+    case 4: x = u, y = -v, z = 1.0; break;
+    default: x = -u, y = -v, z = -1.0; break;
+    }
+    const double r = 1 / __builtin_sqrt(x * x + y * y + z * z);
+    dx = r * x, dy = r * y, dz = r * z;
+}
+/* rtr_cube_lookup of one direction over the 6 S^2 records of one capture */
+RT_HD rtr_gather_out cube_lookup_one(int S, const rtr_gather_out* __restrict__ texels, const rtr_probe_point& q) {
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    const double x = q.p[0], y = q.p[1], z = q.p[2];
+    const double len = __builtin_sqrt(x * x + y * y + z * z);
+    if (probe_point_bad(q) || !(len > 0.0 && len < __builtin_huge_val())) return o;
+    const double ax = __builtin_fabs(x), ay = __builtin_fabs(y), az = __builtin_fabs(z);
+    int f;
+    double u, v;
+    if (ax >= ay && ax >= az) {
+        f = x > 0 ? 0 : 1;
+        u = (x > 0 ? -z : z) / ax, v = -y / ax;
+    } else if (ay >= az) {
+        f = y > 0 ? 2 : 3;
+        u = x / ay, v = (y > 0 ? z : -z) / ay;
+    } else {
+        f = z > 0 ? 4 : 5;
+        u = (z > 0 ? x : -x) / az, v = -y / az;
+    }
+    int i0[2];
+    double w[2][2];
+    probe_axis(((u + 1.0) * S) * 0.5 - 0.5, 0.0, 1.0, S, i0[0], w[0][0], w[0][1]);
+    probe_axis(((v + 1.0) * S) * 0.5 - 0.5, 0.0, 1.0, S, i0[1], w[1][0], w[1][1]);
+    double acc[3] = {0.0, 0.0, 0.0};
+    int used = 0;
+    bool ok = true;
+    for (int db = 0; db < 2; ++db)
+        for (int da = 0; da < 2; ++da) {
+            const int ia = i0[0] + da < S - 1 ? i0[0] + da : S - 1;
+            const int ib = i0[1] + db < S - 1 ? i0[1] + db : S - 1;
+            const double wc = w[0][da] * w[1][db];
+            if (wc > 0) {
+                const rtr_gather_out& t = texels[((long long)f * S + ib) * S + ia];
+                ok = ok && t.valid != 0;
+                ++used;
+                for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + wc * t.v[ch];
+            }
+        }
+    if (!ok) return o;
+    o.v[0] = acc[0], o.v[1] = acc[1], o.v[2] = acc[2];
+    o.count = used, o.valid = 1;
+    return o;
+}
+
 struct ResolveK {
     RenderK r;
     double* out; /* linear mean radiance, 3 doubles per pixel */

@@ -29,6 +29,11 @@
  *                                   through Renderer::closest_hits, then Renderer::ambient_occlusion casts N hemisphere rays
  *                                   of length D (default: unbounded) at every hit's (p, n); a pixel is count / N grey, 1.0
  *                                   where the centre ray misses, stored like a render.  Not with --pick, --adaptive, --turntable
+ *           [--capture x,y,z --capture-out file.hdr [--face S] [--capture-spp N] [--latlong W,H]]   nothing is path-traced per
+ *                                   pixel: Renderer::capture_cube makes a cube map of 6 x S x S texels (default 32), N
+ *                                   (default 16) jittered rays each, of what surrounds the point under the integrator
+ *                                   and --seed, and Renderer::save_environment writes it as a W x H (default 4S x 2S)
+ *                                   equirectangular Radiance .hdr file, the map an EnvironmentLight reads
  *           [--probes NX,NY,NZ --probe-box x0,y0,z0,x1,y1,z1 [--probe-samples N]]   nothing is path-traced per pixel: a grid of
  *                                   NX x NY x NZ light probes whose first and last stand on the box corners (an axis with one
  *                                   probe: at the lower corner) goes through Renderer::light_probes with N (default 64) sphere
@@ -182,6 +187,10 @@ int main(int argc, char** argv) {
     int probe_dims[3] = {0, 0, 0}, probe_samples = 64;
     double probe_box[6];
     bool probes = false, probe_boxed = false, probe_sampled = false;
+    double capture_at[3] = {0, 0, 0};
+    int capture_face = 32, capture_spp = 16, latlong[2] = {0, 0};
+    bool capture = false, capture_face_set = false, capture_spp_set = false, latlong_set = false;
+    std::string capture_out;
     std::vector<int> devices{0}, passes;
     unsigned seed = 1;
     std::string out;
@@ -273,6 +282,36 @@ int main(int argc, char** argv) {
             if (!probes || probe_dims[0] < 1 || probe_dims[1] < 1 || probe_dims[2] < 1 ||
                 (long long)probe_dims[0] * probe_dims[1] * probe_dims[2] > (1ll << 24)) {
                 std::cerr << "--probes takes NX,NY,NZ, each >= 1 with a product <= 16777216, not " << argv[k] << "\n";
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--capture") && k + 1 < argc) {
+            char tail;
+            capture = std::sscanf(argv[++k], "%lf,%lf,%lf%c", &capture_at[0], &capture_at[1], &capture_at[2], &tail) == 3;
+            for (int a = 0; a < 3; ++a) capture = capture && std::isfinite(capture_at[a]);
+            if (!capture) {
+                std::cerr << "--capture takes three finite numbers x,y,z, not " << argv[k] << "\n";
+                return 2;
+            }
+        }
+        else if ((!std::strcmp(argv[k], "--face") || !std::strcmp(argv[k], "--capture-spp")) && k + 1 < argc) {
+            const bool face = !std::strcmp(argv[k], "--face");
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (!end || *end || v < 1 || v > (face ? 4096 : 1 << 20)) {
+                std::cerr << argv[k - 1] << ": an integer in 1.." << (face ? 4096 : 1 << 20) << ", not " << argv[k] << "\n";
+                return 2;
+            }
+            if (face) capture_face = (int)v, capture_face_set = true;
+            else capture_spp = (int)v, capture_spp_set = true;
+        }
+        else if (!std::strcmp(argv[k], "--capture-out") && k + 1 < argc) capture_out = argv[++k];
+        else if (!std::strcmp(argv[k], "--latlong") && k + 1 < argc) {
+            char tail;
+            latlong_set = std::sscanf(argv[++k], "%d,%d%c", &latlong[0], &latlong[1], &tail) == 2 && latlong[0] >= 1 &&
+                          latlong[1] >= 1 && latlong[0] <= 65536 && latlong[1] <= 65536;
+            if (!latlong_set) {
+                std::cerr << "--latlong takes W,H, each in 1..65536, not " << argv[k] << "\n";
                 return 2;
             }
         }
@@ -372,6 +411,19 @@ int main(int argc, char** argv) {
                 std::cerr << "--probe-box: the upper corner must lie above the lower one on every axis with more than one probe\n";
                 return 2;
             }
+    if ((capture_face_set || capture_spp_set || !capture_out.empty() || latlong_set) && !capture) {
+        std::cerr << "--face, --capture-spp, --capture-out and --latlong go with --capture\n";
+        return 2;
+    }
+    if (capture && capture_out.empty()) {
+        std::cerr << "--capture needs --capture-out file.hdr\n";
+        return 2;
+    }
+    if (capture && (probes || pick || ao_samples || adaptive || turntable_frames)) {
+        std::cerr << "--capture excludes --probes, --pick, --ao, --adaptive and --turntable\n";
+        return 2;
+    }
+    if (capture && !latlong_set) latlong[0] = 4 * capture_face, latlong[1] = 2 * capture_face;
     if (display && pick) {
         std::cerr << "the display options exclude --pick\n";
         return 2;
@@ -488,6 +540,21 @@ int main(int argc, char** argv) {
     renderer.set_max_depth(50); /* main.cpp:102 */
     renderer.set_seed(seed);
     renderer.set_progress_bands(bands);
+    if (capture) {
+        if (renderer.upload_scene(config.world, cam, config.background, config.lights) != RTR_OK) {
+            std::cerr << "upload failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        const std::vector<rtr_gather_out> cube =
+            renderer.capture_cube({point3(capture_at[0], capture_at[1], capture_at[2])}, capture_face, capture_spp, seed);
+        if (cube.empty() || !renderer.save_environment(capture_out, cube, capture_face, latlong[0], latlong[1])) {
+            std::cerr << "capture failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        std::cout << "capture: 6 x " << capture_face << " x " << capture_face << " texels x " << capture_spp << " samples -> "
+                  << capture_out << " (" << latlong[0] << " x " << latlong[1] << ")\n";
+        return 0;
+    }
     if (probes) {
         if (renderer.upload_scene(config.world, cam, config.background, config.lights) != RTR_OK) {
             std::cerr << "upload failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";

@@ -254,6 +254,18 @@ int rtr_host_save_jpg(int width, int height, const char* path) {
     return buf.save_to_jpg(path) ? 1 : 0;
 }
 
+/* The Radiance RGBE reader of EnvironmentLight (host/rtr_scene_api.h) on the file at `path`: *width and *height, and
+ * when `texels` holds at least width * height * 3 floats (`cap`), the texels as the light keeps them, row 0 first.
+ * Returns RTR_OK, or RTR_ERR_INVALID when the file cannot be read as such a picture. */
+int rtr_host_read_hdr(const char* path, int32_t* width, int32_t* height, float* texels, int64_t cap) {
+    if (!path || !width || !height) return RTR_ERR_INVALID;
+    const EnvironmentLight light(path);
+    if (light.width <= 0 || light.height <= 0) return RTR_ERR_INVALID;
+    *width = light.width, *height = light.height;
+    if (texels && cap >= (int64_t)light.hdr_data.size()) std::memcpy(texels, light.hdr_data.data(), light.hdr_data.size() * sizeof(float));
+    return RTR_OK;
+}
+
 /* tile bookkeeping of the multi-context Renderer (host/rtr_renderer.h), for the CPU tests */
 int rtr_host_tile_owner(int width, int height, int i, int j, int n_workers) { return rtr::tile_owner(width, height, i, j, n_workers); }
 

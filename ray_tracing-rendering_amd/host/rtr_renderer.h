@@ -470,6 +470,48 @@ class Renderer {
         return out;
     }
 
+    /* Environment captures (include/rtr_hip.h: rtr_capture_cube), on the first context and the scene uploaded there.
+     * capture_cube: for every centre six faces of face_size x face_size texels, each the mean of Integrator::Li over
+     * `samples` jittered rays through it under the integrator set on this renderer; 6 * face_size^2 records per centre,
+     * [centre][face][row][column].  save_environment: one capture (6 * face_size^2 records) resampled to a width x height
+     * equirectangular map (rtr_cube_to_latlong) and written as a Radiance .hdr file an EnvironmentLight reads
+     * (rtr_write_rgbe).  An empty vector / false and last_status() / last_error() on failure. */
+    std::vector<rtr_gather_out> capture_cube(const std::vector<point3>& centres, int face_size = 32, int samples = 16, unsigned seed = 0) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if (!m_integrator) m_error = "no integrator set", m_status = RTR_ERR_INVALID;
+        else if (face_size < 1 || face_size > 4096) m_error = "face_size outside 1 .. 4096", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_gather_out> out;
+        if (m_status == RTR_OK) {
+            out.resize(centres.size() * 6 * (size_t)face_size * face_size);
+            std::vector<rtr_probe_point> pts(centres.size());
+            for (size_t k = 0; k < centres.size(); ++k)
+                for (int a = 0; a < 3; ++a) pts[k].p[a] = centres[k][a];
+            rtr_capture_params cp;
+            rtr_capture_defaults(&cp);
+            cp.face_size = face_size, cp.samples = samples, cp.seed = seed;
+            const rtr_render_params rp = base_params(2, 2); /* integrator and depths; no image is involved */
+            if ((m_status = rtr_capture_cube(m_ctx[0], &rp, &cp, pts.data(), out.data(), (int64_t)pts.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+    bool save_environment(const std::string& path, const std::vector<rtr_gather_out>& texels, int face_size, int width, int height) {
+        m_status = RTR_OK;
+        if (face_size < 1 || texels.size() != 6 * (size_t)face_size * face_size || width < 1 || height < 1)
+            m_error = "a capture of 6 * face_size^2 records and a map of at least 1 x 1 expected", m_status = RTR_ERR_INVALID;
+        if (m_status == RTR_OK) {
+            std::vector<double> rgb((size_t)width * height * 3);
+            if ((m_status = rtr_cube_to_latlong(face_size, texels.data(), width, height, rgb.data())))
+                m_error = "rtr_cube_to_latlong failed";
+            else if ((m_status = rtr_write_rgbe(path.c_str(), width, height, rgb.data())))
+                m_error = "cannot write " + path;
+        }
+        return m_status == RTR_OK;
+    }
+
     /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
      * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
      * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */

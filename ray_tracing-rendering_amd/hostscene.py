@@ -29,8 +29,23 @@ def lib():
                                            C.POINTER(C.c_size_t), C.POINTER(_Info), C.c_char_p, C.c_size_t]
         L.rtr_host_free.argtypes = [C.POINTER(C.c_uint8)]
         L.rtr_host_free.restype = None
+        L.rtr_host_read_hdr.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int64]
         _LIB = L
     return _LIB
+
+
+def read_hdr(path):
+    """The texels float32 [H, W, 3] (row 0 the top) the host layer's EnvironmentLight reads from the Radiance .hdr file at
+    ``path``, through its own RGBE reader."""
+    import numpy as np
+    L = lib()
+    w, h = C.c_int32(), C.c_int32()
+    p = os.fsencode(path)
+    if L.rtr_host_read_hdr(p, C.byref(w), C.byref(h), None, 0) != 0:
+        raise OSError("%s cannot be read as a Radiance picture" % path)
+    out = np.zeros((h.value, w.value, 3), dtype=np.float32)
+    L.rtr_host_read_hdr(p, C.byref(w), C.byref(h), out.ctypes.data, out.size)
+    return out
 
 
 def build_scene(scene_id, scene_seed=SCENE_SEED, with_defaults=False):

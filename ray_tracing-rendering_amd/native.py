@@ -34,11 +34,13 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_gather_occlusion_device", "rtr_gather_radiance_device", "rtr_gather_ray",
            "rtr_probe_visibility", "rtr_probe_radiance", "rtr_probe_visibility_device", "rtr_probe_radiance_device",
            "rtr_probe_ray", "rtr_sh_basis", "rtr_sh_irradiance", "rtr_probe_lookup", "rtr_probe_lookup_device",
-           "rtr_probe_lookup_one")
+           "rtr_probe_lookup_one", "rtr_capture_defaults", "rtr_capture_cube", "rtr_capture_cube_device", "rtr_capture_ray",
+           "rtr_cube_lookup", "rtr_cube_lookup_device", "rtr_cube_lookup_one", "rtr_latlong_direction",
+           "rtr_cube_to_latlong", "rtr_write_rgbe")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
-                "rtr_test_last_gather", "rtr_test_last_probe",
+                "rtr_test_last_gather", "rtr_test_last_probe", "rtr_test_last_capture",
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
                 "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
@@ -69,6 +71,11 @@ class GatherRecordC(C.Structure):
 
 class ProbeRecordC(C.Structure):
     """rtr_probe_record of include/rtr_hip_test.h"""
+    _fields_ = [(name, C.c_int32) for name in ("integ", "trav", "lg")]
+
+
+class CaptureRecordC(C.Structure):
+    """rtr_capture_record of include/rtr_hip_test.h"""
     _fields_ = [(name, C.c_int32) for name in ("integ", "trav", "lg")]
 
 
@@ -200,6 +207,17 @@ def lib():
     L.rtr_probe_lookup.argtypes = [vp, P(A.ProbeGridC), vp, vp, vp, C.c_int64]
     L.rtr_probe_lookup_device.argtypes = [vp, P(A.ProbeGridC), vp, vp, vp, C.c_int64, C.c_int]
     L.rtr_probe_lookup_one.argtypes = [P(A.ProbeGridC), vp, vp, vp]
+    L.rtr_capture_defaults.argtypes = [P(A.CaptureParamsC)]
+    L.rtr_capture_defaults.restype = None
+    L.rtr_capture_cube.argtypes = [vp, P(A.RenderParamsC), P(A.CaptureParamsC), vp, vp, C.c_int64]
+    L.rtr_capture_cube_device.argtypes = [vp, P(A.RenderParamsC), P(A.CaptureParamsC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_capture_ray.argtypes = [P(A.CaptureParamsC), vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rtr_cube_lookup.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int64]
+    L.rtr_cube_lookup_device.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int64, C.c_int]
+    L.rtr_cube_lookup_one.argtypes = [C.c_int32, vp, vp, vp]
+    L.rtr_latlong_direction.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rtr_cube_to_latlong.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, vp]
+    L.rtr_write_rgbe.argtypes = [C.c_char_p, C.c_int32, C.c_int32, vp]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -235,6 +253,7 @@ def test_lib():
     T.rtr_test_last_kernel.argtypes = [vp, C.POINTER(KernelRecordC), C.c_size_t]
     T.rtr_test_last_gather.argtypes = [vp, C.POINTER(GatherRecordC), C.c_size_t]
     T.rtr_test_last_probe.argtypes = [vp, C.POINTER(ProbeRecordC), C.c_size_t]
+    T.rtr_test_last_capture.argtypes = [vp, C.POINTER(CaptureRecordC), C.c_size_t]
     T.rtr_test_temporal_planes.argtypes = [vp] + [C.c_int32] * 6 + [C.POINTER(A.CameraC), C.POINTER(A.CameraC), C.c_int,
                                                                     C.POINTER(A.TemporalParamsC)] + [vp] * 8
     T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64,
@@ -539,6 +558,99 @@ def probe_lookup_host(grid, probes, points, normals=None):
         if rc != 0:
             raise RtrError(rc, "rtr_probe_lookup_one: bad grid, or bad query at index %d" % k)
     return out
+
+
+def capture_defaults(**overrides):
+    """rtr_capture_params with the library's defaults (rtr_capture_defaults: face_size 32, samples 16, seed 0, point_base 0,
+    jitter 1, time 0), fields replaced by ``overrides``."""
+    return _defaults(A.CaptureParamsC, "rtr_capture_defaults", ("face_size", "samples", "seed", "point_base", "jitter", "time"),
+                     overrides)
+
+
+def capture_ray(point, face, a, b, s=0, index_in_call=0, params=None, **overrides):
+    """rtr_capture_ray (host only, no context): ray ``s`` through texel (``a``, ``b``) of face ``face`` of the centre
+    ``point`` ([3]) at ``index_in_call``, as a one-element ``RAY_DTYPE`` array with the generator state after the jitter's
+    draws.  Raises RtrError for a bad centre, bad params or an index outside the capture."""
+    cp = params if params is not None else capture_defaults(**overrides)
+    pt = probe_points(np.asarray(point, dtype=np.float64).reshape(1, 3))
+    ray = np.zeros(1, dtype=A.RAY_DTYPE)
+    rc = lib().rtr_capture_ray(C.byref(cp), pt.ctypes.data, int(index_in_call), int(face), int(a), int(b), int(s), ray.ctypes.data)
+    if rc != 0:
+        raise RtrError(rc, "rtr_capture_ray: bad params, bad centre or an index outside the capture")
+    return ray
+
+
+def capture_rays(points, params=None, **overrides):
+    """rtr_capture_ray for every sample of every texel of every centre: ``RAY_DTYPE`` [n, 6, S, S, samples] (row b, then
+    column a), the rays rtr_capture_cube casts."""
+    cp = params if params is not None else capture_defaults(**overrides)
+    pts = probe_points(points)
+    S, N = int(cp.face_size), int(cp.samples)
+    if not (1 <= S <= A.CAPTURE_MAX_FACE and 1 <= N <= A.GATHER_MAX_SAMPLES):
+        raise RtrError(A.RTR_ERR_INVALID, "rtr_capture_ray: face_size or samples out of range")
+    rays = np.zeros((len(pts), 6, S, S, N), dtype=A.RAY_DTYPE)
+    ray_of, size, flat = lib().rtr_capture_ray, A.RAY_DTYPE.itemsize, 0
+    for k in range(len(pts)):
+        for f in range(6):
+            for b in range(S):
+                for a in range(S):
+                    for s in range(N):
+                        rc = ray_of(C.byref(cp), pts.ctypes.data + 24 * k, k, f, a, b, s, rays.ctypes.data + flat * size)
+                        if rc != 0:
+                            raise RtrError(rc, "rtr_capture_ray: bad params or bad centre at index %d" % k)
+                        flat += 1
+    return rays
+
+
+def _cube_texels(texels, face_size=None):
+    """(face size, the 6 S^2 ``GATHER_OUT_DTYPE`` records) of one capture given as records or as a [6, S, S] array of them"""
+    t = np.ascontiguousarray(texels, dtype=A.GATHER_OUT_DTYPE)
+    S = int(face_size) if face_size is not None else (t.shape[-1] if t.ndim == 3 else int(round((t.size / 6) ** 0.5)))
+    if not 1 <= S <= A.CAPTURE_MAX_FACE or t.size != 6 * S * S:
+        raise ValueError("a capture holds 6 * S * S records, 1 <= S <= %d" % A.CAPTURE_MAX_FACE)
+    return S, t.reshape(-1)
+
+
+def cube_lookup_host(texels, directions, face_size=None):
+    """rtr_cube_lookup_one for every direction ([n, 3]; host only, no context): a ``GATHER_OUT_DTYPE`` array."""
+    S, t = _cube_texels(texels, face_size)
+    q = probe_points(directions)
+    out = np.zeros(len(q), dtype=A.GATHER_OUT_DTYPE)
+    L = lib()
+    for k in range(len(q)):
+        rc = L.rtr_cube_lookup_one(S, t.ctypes.data, q.ctypes.data + 24 * k, out.ctypes.data + 32 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_cube_lookup_one")
+    return out
+
+
+def latlong_direction(width, height, i, j):
+    """rtr_latlong_direction: the direction [3] of the centre of texel (i, j) of a width x height equirectangular map."""
+    d = np.zeros(3)
+    rc = lib().rtr_latlong_direction(int(width), int(height), int(i), int(j), d.ctypes.data)
+    if rc != 0:
+        raise RtrError(rc, "rtr_latlong_direction: bad size or texel outside the map")
+    return d
+
+
+def cube_to_latlong(texels, width, height, face_size=None):
+    """rtr_cube_to_latlong: the capture resampled to an equirectangular image [height, width, 3], row 0 the top."""
+    S, t = _cube_texels(texels, face_size)
+    out = np.zeros((int(height), int(width), 3))
+    rc = lib().rtr_cube_to_latlong(S, t.ctypes.data, int(width), int(height), out.ctypes.data)
+    if rc != 0:
+        raise RtrError(rc, "rtr_cube_to_latlong: bad size")
+    return out
+
+
+def write_rgbe(path, rgb):
+    """rtr_write_rgbe: the image ``rgb`` [H, W, 3] (row 0 the top) as a flat-scanline Radiance .hdr file at ``path``."""
+    a = np.ascontiguousarray(rgb, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("an (H, W, 3) image expected")
+    rc = lib().rtr_write_rgbe(os.fsencode(path), a.shape[1], a.shape[0], a.ctypes.data)
+    if rc != 0:
+        raise RtrError(rc, "rtr_write_rgbe: bad size, or %s cannot be written" % path)
 
 
 def srgb_thresholds():
@@ -877,6 +989,50 @@ class Context:
         self._chk(self._L.rtr_probe_lookup_device(self._h, C.byref(grid), C.c_void_p(probes_ptr),
                                                   *_into_tail(queries_ptr, out_ptr, n, blocking)))
 
+    # environment captures (include/rtr_hip.h: rtr_capture_*, rtr_cube_*)
+    def capture_cube_records(self, params, points, capture_params=None, out=None, **overrides):
+        """rtr_capture_cube: the ``GATHER_OUT_DTYPE`` records [n, 6, S, S] (face, row, column) of the cube maps about the
+        centres ``points`` under ``params`` (an rtr_render_params).  Blocking; raises RtrError (RTR_ERR_INVALID) naming the
+        first bad centre, with ``out`` untouched."""
+        cp = capture_params if capture_params is not None else capture_defaults(**overrides)
+        pts = probe_points(points)
+        S = int(cp.face_size)
+        flat = _records_out(None if out is None else out.reshape(-1), len(pts) * 6 * S * S, A.GATHER_OUT_DTYPE)
+        self._chk(self._L.rtr_capture_cube(self._h, C.byref(params), C.byref(cp), pts.ctypes.data, flat.ctypes.data, len(pts)))
+        return flat[:len(pts) * 6 * S * S].reshape(len(pts), 6, S, S)
+
+    def capture_cube(self, params, points, face_size=32, samples=16, seed=0, jitter=1, time=0.0, point_base=0):
+        """The mean radiance float64 [n, 6, S, S, 3] of ``capture_cube_records`` and its valid mask, bool [n, 6, S, S]."""
+        rec = self.capture_cube_records(params, points, face_size=face_size, samples=samples, seed=seed, jitter=jitter,
+                                        time=time, point_base=point_base)
+        return np.ascontiguousarray(rec["v"]), rec["valid"] != 0
+
+    def capture_cube_into(self, params, points_ptr, out_ptr, n, capture_params=None, blocking=False, **overrides):
+        """rtr_capture_cube_device: n ``PROBE_POINT_DTYPE`` centres at device pointer ``points_ptr`` -> n * 6 * S * S
+        ``GATHER_OUT_DTYPE`` records at ``out_ptr``, on the context stream behind what is queued there."""
+        cp = capture_params if capture_params is not None else capture_defaults(**overrides)
+        self._chk(self._L.rtr_capture_cube_device(self._h, C.byref(params), C.byref(cp),
+                                                  *_into_tail(points_ptr, out_ptr, n, blocking)))
+
+    @staticmethod
+    def capture_rays(points, params=None, **overrides):
+        """The rays a capture casts, ``RAY_DTYPE`` [n, 6, S, S, samples], through rtr_capture_ray (``native.capture_rays``)."""
+        return capture_rays(points, params, **overrides)
+
+    def cube_lookup(self, texels, directions, face_size=None, out=None):
+        """rtr_cube_lookup: the radiance of one capture (6 * S * S records, or [6, S, S]) along the directions [n, 3],
+        bilinear inside a face.  Returns a ``GATHER_OUT_DTYPE`` array (``count`` the texels used).  Blocking; needs no scene."""
+        S, t = _cube_texels(texels, face_size)
+        q = probe_points(directions)
+        out = _records_out(out, len(q), A.GATHER_OUT_DTYPE)
+        self._chk(self._L.rtr_cube_lookup(self._h, S, t.ctypes.data, q.ctypes.data, out.ctypes.data, len(q)))
+        return out
+
+    def cube_lookup_into(self, face_size, texels_ptr, directions_ptr, out_ptr, n, blocking=False):
+        """rtr_cube_lookup_device: the same over device pointers, on the context stream behind what is queued there."""
+        self._chk(self._L.rtr_cube_lookup_device(self._h, int(face_size), C.c_void_p(texels_ptr),
+                                                 *_into_tail(directions_ptr, out_ptr, n, blocking)))
+
     # display transform (include/rtr_hip.h: rtr_display_*)
     @staticmethod
     def _linear_image(linear):
@@ -986,6 +1142,15 @@ class Context:
         if r.trav < 0:
             return None
         return {name: int(getattr(r, name)) for name, _ in ProbeRecordC._fields_}
+
+    def last_capture(self):
+        """The capture kernel the last capture_cube call launched (include/rtr_hip_test.h: rtr_capture_record), as a dict;
+        None before any such call of this context launched one."""
+        r = CaptureRecordC()
+        self._chk(test_lib().rtr_test_last_capture(self._h, C.byref(r), C.sizeof(r)))
+        if r.trav < 0:
+            return None
+        return {name: int(getattr(r, name)) for name, _ in CaptureRecordC._fields_}
 
     def reference_order(self, on):
         """Force the reference-order traversal for rtr_test_hits (renders use params.flags)."""

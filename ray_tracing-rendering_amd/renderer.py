@@ -321,6 +321,15 @@ class Renderer:
         that holds the gathered image."""
         return self._ctx.display(target_buffer.linear, params)[0]
 
+    def capture_environment(self, scene, centre, face_size=32, samples=16, seed=None, jitter=1, time=0.0):
+        """A ``Cubemap`` of what surrounds ``centre`` ([3]) in ``scene`` under this renderer's integrator and depth
+        (include/rtr_hip.h: rtr_capture_cube): mean radiance of ``samples`` rays through every texel of six faces."""
+        self._scene_on_device(scene, own_camera=False)
+        p = A.make_params(2, 2, 1, integrator=self._integrator, seed=self.seed, max_depth=self._max_depth)
+        rec = self._ctx.capture_cube_records(p, np.asarray(centre, dtype=np.float64).reshape(1, 3), face_size=face_size,
+                                             samples=samples, seed=self.seed if seed is None else seed, jitter=jitter, time=time)
+        return Cubemap(rec[0])
+
     def _scene_on_device(self, scene, own_camera=True):
         """Upload ``scene`` unless the context holds it already.  ``own_camera``: a scene that is there but is seen from
         another camera since ``Context.set_camera`` (a ``render_sequence``) gets its own camera back, so a render of
@@ -407,6 +416,43 @@ class ProbeGrid:
         if ctx is None:
             raise ValueError("irradiance needs a context: bake first or pass ctx")
         return ctx.probe_lookup(self.grid(), self.coefficients, points, normals)["v"]
+
+
+class Cubemap:
+    """One environment capture (include/rtr_hip.h: rtr_capture_cube): ``texels``, ``GATHER_OUT_DTYPE`` records [6, S, S]
+    (face, row, column).  ``lookup`` reads it along directions (rtr_cube_lookup_one, or rtr_cube_lookup on a context),
+    ``to_latlong`` resamples it to the equirectangular layout of the reference's EnvironmentLight, ``save_hdr`` writes that
+    as a Radiance .hdr file an EnvironmentLight can read."""
+
+    def __init__(self, texels):
+        t = np.ascontiguousarray(texels, dtype=A.GATHER_OUT_DTYPE)
+        if t.ndim != 3 or t.shape[0] != 6 or t.shape[1] != t.shape[2] or not 1 <= t.shape[1] <= A.CAPTURE_MAX_FACE:
+            raise ValueError("texels must be [6, S, S] records, 1 <= S <= %d" % A.CAPTURE_MAX_FACE)
+        self.texels = t
+        self.face_size = int(t.shape[1])
+
+    @property
+    def radiance(self):
+        """[6, S, S, 3] mean radiance"""
+        return self.texels["v"]
+
+    def lookup(self, directions, ctx=None):
+        """[n, 3] radiance along the directions [n, 3], bilinear inside a face; zero where the lookup is invalid.
+        ``ctx``: a context to run it on the device (default: on the host)."""
+        from . import native
+        if ctx is not None:
+            return ctx.cube_lookup(self.texels, directions)["v"]
+        return native.cube_lookup_host(self.texels, directions)["v"]
+
+    def to_latlong(self, width, height):
+        """rtr_cube_to_latlong: [height, width, 3], row 0 the top (+y), the centre column towards +x."""
+        from . import native
+        return native.cube_to_latlong(self.texels, width, height)
+
+    def save_hdr(self, path, width, height):
+        """``to_latlong(width, height)`` written with rtr_write_rgbe."""
+        from . import native
+        native.write_rgbe(path, self.to_latlong(width, height))
 
 
 def check_denoise(params):
