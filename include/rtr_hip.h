@@ -1069,6 +1069,121 @@ int rtr_cube_to_latlong(int32_t face_size, const rtr_gather_out* texels, int32_t
  * RTR_ERR_DEVICE when the file cannot be written. */
 int rtr_write_rgbe(const char* path, int32_t W, int32_t H, const double* rgb);
 
+/* ---- filtered cube maps: a GGX-filtered level made on the device from a capture, and a seam-aware lookup that blends two
+ * levels by roughness ----
+ * A glossy object needs the capture convolved with its specular lobe at several roughnesses.  rtr_cube_filter makes one
+ * such level: every texel of an output cube of face size face_out is a DEFINED SUM over all 6 face_in^2 texels of the
+ * source cube (brute force, no Monte-Carlo prefilter: no noise, no sin / cos, a definition independent of the
+ * implementation).  Only + - * / sqrt and compares, no fused multiply-add: every product is rounded before its add, so a
+ * host (rtr_cube_filter_one), numpy and the device give the same bits.  Records are rtr_gather_out, cubes are laid out
+ * [cube][face][row][column] as the captures': texels holds n_cubes * 6 face_in^2 records, out n_cubes * 6 face_out^2.
+ *
+ * FILTER: output texel (f, b, a) of cube k.
+ *   R = its unit centre direction: the capture's RAY above with jitter 0 (ju = jv = 0.5) at S = face_out: d0 by the face
+ *       table, R = unit(d0).
+ *   Source texel j (0 <= j < 6 face_in^2, the record order [face][row][column]): d0 the same way at S = face_in,
+ *       r2 = d0.x*d0.x + d0.y*d0.y + d0.z*d0.z,  L = unit(d0) = (1 / sqrt(r2)) * d0,
+ *       dw = 1.0 / (r2 * sqrt(r2))                  (its solid angle; the common factor 4 / S^2 cancels)
+ *   c = (R.x*L.x + R.y*L.y) + R.z*L.z               texel j is USED iff c > cos_cut
+ *   h2 = (1.0 + c) * 0.5                            ((n.h)^2 for n = v = R)
+ *   den = h2 * (alpha*alpha - 1.0) + 1.0
+ *   w = (c * dw) / (den * den)                      (GGX D times n.l times dw; the numerator alpha^2 and the pi of D cancel
+ *                                                    in the normalisation and are left out)
+ * REDUCTION: the gathers' with G = 64 fixed.  Lane l visits j = l, l + 64, ... in increasing order and for each USED texel
+ * does acc[ch] = acc[ch] + w * v[ch] (ch = 0, 1, 2) and wsum = wsum + w, all from +0.0, counts the texel and remembers
+ * whether it had valid == 0.  Then for off = 32, 16, ..., 1: x[l] = x[l] + x[l xor off] on the four sums and the count.
+ * Result: v = (1.0 / wsum) * acc, count = the texels used, valid 1.  The all-zero record (valid 0) is written when count
+ * is 0, when a USED texel is invalid, or when wsum is not in (0, +inf).  Skipping texels that are not USED, or whole
+ * blocks of them, changes no bit: an implementation may cull.
+ *
+ * params: 1 <= face_in, face_out <= 512; 2^-20 <= alpha <= 1 (alpha = roughness^2, the reference's a,
+ * materials/material.h:399); 0 <= cos_cut < 1 written with a clear sign bit (-0.0 is rejected: one spelling per filter);
+ * pad 0.  Bad params, n_cubes < 0 or a NULL array is RTR_ERR_INVALID, before any device work, context first as for the
+ * captures; n_cubes == 0 is RTR_OK without a launch; no scene is needed.  The host entry takes host arrays and blocks: it
+ * stages the source cubes once at the head of the buffer of the gathers' host entries and brings the records back in
+ * slices of at most 2^20.  The device entry takes device pointers (8-byte aligned; texels and out must not overlap: both
+ * RTR_ERR_INVALID before any launch), runs on the context stream behind whatever is queued there -- a
+ * rtr_capture_cube_device, say -- needs no scratch memory and returns at once unless `blocking`.  A call is split into
+ * launches over output texels so that no launch exceeds a fixed number of (output, source) pairs; the environment variable
+ * RTR_FILTER_PAIRS=n, read at every call, lowers that cap (a test hook: the bits do not depend on it). */
+typedef struct rtr_cube_filter_params { /* 32 bytes */
+    int32_t face_in, face_out;
+    double alpha;
+    double cos_cut;
+    int32_t pad[2];                 /* must be 0 */
+} rtr_cube_filter_params;
+
+/* face_in 32, face_out 16, alpha 0.25, cos_cut 0.0 */
+void rtr_cube_filter_defaults(rtr_cube_filter_params* p);
+
+int rtr_cube_filter(rtr_context* ctx, const rtr_cube_filter_params* params, const rtr_gather_out* texels,
+                    rtr_gather_out* out, int64_t n_cubes);
+int rtr_cube_filter_device(rtr_context* ctx, const rtr_cube_filter_params* params, const rtr_gather_out* d_texels,
+                           rtr_gather_out* d_out, int64_t n_cubes, int blocking);
+/* Host-only, needs no context: output texel (a, b) of face `face` from the 6 face_in^2 HOST records of one cube, the
+ * arithmetic the kernel runs in the lane order above.  RTR_ERR_INVALID for bad params, a NULL pointer, a face outside
+ * 0..5 or a, b outside [0, face_out). */
+int rtr_cube_filter_one(const rtr_cube_filter_params* params, const rtr_gather_out* cube_texels, int32_t face, int32_t a,
+                        int32_t b, rtr_gather_out* out);
+
+/* A CHAIN is a set of 1 <= n_levels <= 13 cubes of one environment in one array of `n_records` records: level i has face
+ * size levels[i].face_size (1 .. 4096), starts at record levels[i].offset and was filtered with levels[i].alpha.  The
+ * alphas are finite and strictly increasing, offsets are >= 0, every level lies inside n_records, pads are 0: anything
+ * else is RTR_ERR_INVALID in every entry below.
+ *
+ * PLAN (host only): the usual chain for a capture of face size S (1 .. 4096): level i has face_size = max(S >> i, 1),
+ * offset = the records of the levels before it, alpha = r * r with r = (double)i / (n_levels - 1) (r = 0 for one level):
+ * level 0 has alpha 0 and is the capture itself, level i > 0 is rtr_cube_filter of level 0 with that alpha (the caller
+ * runs it: face_out > 512 is outside the filter).  *n_records = the records of all levels.  levels may be NULL to ask for
+ * n_records alone. */
+typedef struct rtr_cube_level {     /* 24 bytes */
+    int32_t face_size, pad;
+    int64_t offset;                 /* in records */
+    double alpha;
+} rtr_cube_level;
+typedef struct rtr_cube_query {     /* 32 bytes */
+    double d[3];                    /* direction, need not be normalised */
+    double alpha;                   /* roughness^2 */
+} rtr_cube_query;
+int rtr_cube_chain_plan(int32_t face_size, int32_t n_levels, rtr_cube_level* levels, int64_t* n_records);
+
+/* CHAIN LOOKUP of one query:
+ *   a = min(max(q.alpha, alpha_0), alpha_last)
+ *   i = the largest level with alpha_i <= a, capped at n_levels - 2 when there are two or more levels
+ *   t = (a - alpha_i) / (alpha_{i+1} - alpha_i);  with one level t = 0
+ *   t == 0: the result is X_i, and level i + 1 is not read.  Otherwise v = (1.0 - t) * X_i.v + t * X_{i+1}.v per channel,
+ *   count = X_i.count + X_{i+1}.count, valid 1 -- and the zero record if either X is invalid.
+ * A non-finite q.alpha, or a direction rtr_cube_lookup would reject, gives the zero record.
+ *
+ * X = the SEAM-AWARE LOOKUP of q.d in one level (S = its face size, its 6 S^2 records):
+ *   face and (u, v) exactly as rtr_cube_lookup.
+ *   per axis (c = u: columns, c = v: rows): g = ((c + 1.0) * S) * 0.5 - 0.5, NOT clamped;  i0 = floor(g), -1 .. S - 1;
+ *     t = g - (double)i0;  w0 = 1.0 - t, w1 = t
+ *   taps as there: db outermost, then da, each in {0, 1}: ia = i0a + da, ib = i0b + db, w = wa[da] * wb[db], USED iff w > 0,
+ *     acc[ch] = acc[ch] + w * texel.v[ch] from +0.0
+ *   a tap inside [0, S)^2 reads texel (ib, ia) of its own face.  Any other tap: u' = (2.0 * (ia + 0.5)) / S - 1.0 and v'
+ *     likewise from ib; d0 = the face table at (u', v'), un-normalised; the major-axis rule of rtr_cube_lookup applied to d0
+ *     gives (f'', u'', v''); the tap reads texel min(max((int)(((c'' + 1.0) * S) * 0.5), 0), S - 1) per axis of face f''.
+ *     A corner tap, outside on both axes, resolves by the tie rule: x over y over z.
+ *   v = acc, count = the taps used, valid 1; the zero record if a used texel has valid == 0.
+ * This holds for S = 1 too, where it blends the six texels.  The filter is continuous across cube edges: a tap beyond an
+ * edge lands on the neighbouring face's edge texel, and that texel's outward tap comes back.  It is NOT a true three-face
+ * filter at the corners, where the fourth tap is one of the three texels that meet there.  rtr_cube_lookup itself stays
+ * unfiltered across faces and keeps its bits.
+ *
+ * n < 0 or a NULL array is RTR_ERR_INVALID, n == 0 is RTR_OK, no scene is needed.  The host entry stages the n_records
+ * texels once and the queries in slices of 2^20; the device entry (levels is a HOST array, copied at the call) is
+ * stream-ordered like the gathers' (8-byte aligned pointers, `blocking`). */
+int rtr_cube_chain_lookup(rtr_context* ctx, const rtr_cube_level* levels, int32_t n_levels, const rtr_gather_out* texels,
+                          int64_t n_records, const rtr_cube_query* queries, rtr_gather_out* out, int64_t n);
+int rtr_cube_chain_lookup_device(rtr_context* ctx, const rtr_cube_level* levels, int32_t n_levels,
+                                 const rtr_gather_out* d_texels, int64_t n_records, const rtr_cube_query* d_queries,
+                                 rtr_gather_out* d_out, int64_t n, int blocking);
+/* Host-only, needs no context: one query over HOST records, the same function the kernel calls.  RTR_ERR_INVALID for a bad
+ * chain (checked against the level ends: there is no n_records here) or a NULL pointer. */
+int rtr_cube_chain_lookup_one(const rtr_cube_level* levels, int32_t n_levels, const rtr_gather_out* texels,
+                              const rtr_cube_query* query, rtr_gather_out* out);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

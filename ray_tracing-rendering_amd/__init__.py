@@ -25,10 +25,11 @@ def __getattr__(name):
     if name in ("Context", "RtrError", "library_path", "denoise_defaults", "denoise_host", "temporal_defaults",
                 "History", "display_defaults", "srgb_thresholds", "gather_defaults", "gather_rays",
                 "probe_rays", "sh_basis", "sh_irradiance", "probe_grid", "capture_defaults", "capture_ray", "capture_rays",
-                "cube_lookup_host", "latlong_direction", "cube_to_latlong", "write_rgbe"):
+                "cube_lookup_host", "latlong_direction", "cube_to_latlong", "write_rgbe", "cube_filter_defaults",
+                "cube_filter_host", "cube_chain_plan", "cube_chain_lookup_host", "cube_queries"):
         from . import native
         return getattr(native, name)
-    if name in ("Renderer", "RenderBuffer", "ProbeGrid", "Cubemap", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):
+    if name in ("Renderer", "RenderBuffer", "ProbeGrid", "Cubemap", "CubeChain", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):
         from . import renderer
         return getattr(renderer, name)
     raise AttributeError(name)

@@ -161,6 +161,24 @@ CAPTURE_PARAMS_SIZE = 48
 assert C.sizeof(CaptureParamsC) == CAPTURE_PARAMS_SIZE
 
 
+class CubeFilterParamsC(C.Structure):
+    """rtr_cube_filter_params (include/rtr_hip.h): one GGX-filtered level of rtr_cube_filter"""
+    _fields_ = [("face_in", C.c_int32), ("face_out", C.c_int32), ("alpha", C.c_double), ("cos_cut", C.c_double),
+                ("pad", C.c_int32 * 2)]
+
+
+class CubeLevelC(C.Structure):
+    """rtr_cube_level (include/rtr_hip.h): one level of a chain of filtered cubes"""
+    _fields_ = [("face_size", C.c_int32), ("pad", C.c_int32), ("offset", C.c_int64), ("alpha", C.c_double)]
+
+
+CUBE_FILTER_PARAMS_SIZE, CUBE_LEVEL_SIZE = 32, 24
+assert C.sizeof(CubeFilterParamsC) == CUBE_FILTER_PARAMS_SIZE and C.sizeof(CubeLevelC) == CUBE_LEVEL_SIZE
+CUBE_QUERY_DTYPE = np.dtype([("d", "<f8", (3,)), ("alpha", "<f8")])  # rtr_cube_query
+assert CUBE_QUERY_DTYPE.itemsize == 32
+CUBE_FILTER_MAX_FACE, CUBE_CHAIN_MAX_LEVELS = 512, 13
+
+
 class DenoiseParamsC(C.Structure):
     """rtr_denoise_params (include/rtr_hip.h): the a-trous denoiser of rtr_accum_denoise / rtr_denoise_host"""
     _fields_ = [("iterations", C.c_int32), ("feature_spp", C.c_int32), ("sigma_l", C.c_double),

@@ -402,6 +402,192 @@ RT_HD rtr_gather_out cube_lookup_one(int S, const rtr_gather_out* __restrict__ t
     return o;
 }
 
+/* ---- filtered cube maps (include/rtr_hip.h: rtr_cube_filter*, rtr_cube_chain_*) ----
+ * The arithmetic of that contract, written once for host (the _one forms, the entries' checks) and device (k_cube_filter
+ * and k_cube_chain_lookup of rt_cube.h). */
+#define RTR_FILTER_MAX_FACE 512
+#define RTR_CHAIN_MAX_LEVELS 13
+inline const char* cube_filter_params_why(const rtr_cube_filter_params* p) {
+    if (!p) return "null filter params";
+    if (p->face_in < 1 || p->face_in > RTR_FILTER_MAX_FACE) return "face_in outside 1 .. 512";
+    if (p->face_out < 1 || p->face_out > RTR_FILTER_MAX_FACE) return "face_out outside 1 .. 512";
+    if (!(p->alpha >= 0x1p-20 && p->alpha <= 1.0)) return "alpha outside 2^-20 .. 1";
+    if (!(p->cos_cut >= 0.0 && p->cos_cut < 1.0) || __builtin_signbit(p->cos_cut)) return "cos_cut outside [+0, 1)";
+    if (p->pad[0] != 0 || p->pad[1] != 0) return "pad must be 0";
+    return nullptr;
+}
+/* why the chain is none, or nullptr; n_records < 0: the levels' own ends are the only bound (rtr_cube_chain_lookup_one) */
+inline const char* cube_chain_why(const rtr_cube_level* lv, int n_levels, long long n_records) {
+    if (!lv) return "null levels";
+    if (n_levels < 1 || n_levels > RTR_CHAIN_MAX_LEVELS) return "n_levels outside 1 .. 13";
+    for (int i = 0; i < n_levels; ++i) {
+        if (lv[i].face_size < 1 || lv[i].face_size > RTR_CAPTURE_MAX_FACE || lv[i].pad != 0) return "level face_size outside 1 .. 4096 or pad not 0";
+        const long long recs = 6ll * lv[i].face_size * lv[i].face_size;
+        if (lv[i].offset < 0 || (n_records >= 0 && (lv[i].offset > n_records || recs > n_records - lv[i].offset)))
+            return "a level lies outside n_records";
+        if (!__builtin_isfinite(lv[i].alpha) || (i > 0 && !(lv[i].alpha > lv[i - 1].alpha))) return "level alphas must be finite and strictly increasing";
+    }
+    return nullptr;
+}
+/* the face table of the captures: the un-normalised direction of (u, v) on face f */
+RT_HD void cube_face_d0(int f, double u, double v, double& x, double& y, double& z) {
+    switch (f) {
+    case 0: x = 1.0, y = -v, z = -u; break;
+    case 1: x = -1.0, y = -v, z = u; break;
+    case 2: x = u, y = 1.0, z = v; break;
+    case 3: x = u, y = -1.0, z = -v; break;
+    case 4: x = u, y = -v, z = 1.0; break;
+    default: x = -u, y = -v, z = -1.0; break;
+    }
+}
+/* the centre of texel (a, b) of face f of an S x S cube: capture_direction without jitter, and the texel's solid-angle
+ * weight dw = 1 / (r2 sqrt(r2)) beside the unit direction */
+RT_HD void cube_texel_centre(int S, int f, int a, int b, double& lx, double& ly, double& lz, double& dw) {
+    const double u = (2.0 * (a + 0.5)) / S - 1.0;
+    const double v = (2.0 * (b + 0.5)) / S - 1.0;
+    double x, y, z;
+    cube_face_d0(f, u, v, x, y, z);
+    const double r2 = x * x + y * y + z * z;
+    const double root = __builtin_sqrt(r2);
+    const double r = 1 / root;
+    lx = r * x, ly = r * y, lz = r * z;
+    dw = 1.0 / (r2 * root);
+}
+/* n / d of the filter's weight.  The device takes the short form of "IEEE division with a shared divisor" (rt_device.h):
+ * the compiler's own sequence without the scales and the fixup, the same bits while |d| is in [2^-100, 2^100] and |n| in
+ * [2^-300, 2^200].  Both hold for every USED pair: d = den * den with den = h2 (alpha^2 - 1) + 1, h2 within an ulp of
+ * (1/2, 1] and alpha^2 in [2^-40, 1], so d is in [2^-84, 4]; n = c * dw with dw in [0.19, 1] and c > 0 a sum of three
+ * products of components that are each at least 2^-10.5 or zero, hence a multiple of 2^-74 and at most 1 + 2^-50.  The
+ * host divides. */
+RT_HD double filter_quotient(double n, double d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double r = rcp_refined(d);
+    const double q = n * r;
+    return __builtin_fma(__builtin_fma(-d, q, n), r, q);
+#else
+    return n / d;
+#endif
+}
+/* the running sums of one lane for one output texel */
+struct FilterAcc {
+    double v[3], wsum;
+    int count, bad;
+};
+RT_HD void filter_acc_zero(FilterAcc& s) { s.v[0] = s.v[1] = s.v[2] = s.wsum = 0.0, s.count = 0, s.bad = 0; }
+/* w of the pair whose cosine c is USED */
+RT_HD double filter_weight(double c, double dw, double a2m1) {
+    const double h2 = (1.0 + c) * 0.5;
+    const double den = h2 * a2m1 + 1.0;
+    return filter_quotient(c * dw, den * den);
+}
+RT_HD void filter_add(FilterAcc& s, double w, double v0, double v1, double v2, int valid) {
+    s.v[0] = s.v[0] + w * v0, s.v[1] = s.v[1] + w * v1, s.v[2] = s.v[2] + w * v2;
+    s.wsum = s.wsum + w;
+    s.count += 1, s.bad += valid == 0;
+}
+/* the record of the sums of all 64 lanes */
+RT_HD rtr_gather_out filter_result(const FilterAcc& s) {
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    if (s.count == 0 || s.bad != 0 || !(s.wsum > 0.0 && s.wsum < __builtin_huge_val())) return o;
+    const double r = 1.0 / s.wsum;
+    o.v[0] = r * s.v[0], o.v[1] = r * s.v[1], o.v[2] = r * s.v[2];
+    o.count = s.count, o.valid = 1;
+    return o;
+}
+
+/* face and (u, v) of a direction with a major axis: the rule of cube_lookup_one (x over y over z on a tie), which keeps
+ * its own lines so that k_cube_lookup stays the text it was */
+RT_HD void cube_face_uv(double x, double y, double z, int& f, double& u, double& v) {
+    const double ax = __builtin_fabs(x), ay = __builtin_fabs(y), az = __builtin_fabs(z);
+    if (ax >= ay && ax >= az) {
+        f = x > 0 ? 0 : 1;
+        u = (x > 0 ? -z : z) / ax, v = -y / ax;
+    } else if (ay >= az) {
+        f = y > 0 ? 2 : 3;
+        u = x / ay, v = (y > 0 ? z : -z) / ay;
+    } else {
+        f = z > 0 ? 4 : 5;
+        u = (z > 0 ? x : -x) / az, v = -y / az;
+    }
+}
+RT_HD int cube_texel_of(double c, int S) {
+    const int i = (int)(((c + 1.0) * S) * 0.5);
+    return i < 0 ? 0 : (i > S - 1 ? S - 1 : i);
+}
+/* the seam-aware lookup of one level: its 6 S^2 records */
+RT_HD rtr_gather_out cube_seam_lookup(int S, const rtr_gather_out* __restrict__ texels, double x, double y, double z) {
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    int f;
+    double uv[2];
+    cube_face_uv(x, y, z, f, uv[0], uv[1]);
+    int i0[2];
+    double w[2][2];
+    for (int k = 0; k < 2; ++k) {
+        const double g = ((uv[k] + 1.0) * S) * 0.5 - 0.5;
+        const double fl = __builtin_floor(g);
+        i0[k] = (int)fl;
+        const double t = g - fl;
+        w[k][0] = 1.0 - t, w[k][1] = t;
+    }
+    double acc[3] = {0.0, 0.0, 0.0};
+    int used = 0;
+    bool ok = true;
+    for (int db = 0; db < 2; ++db)
+        for (int da = 0; da < 2; ++da) {
+            const double wc = w[0][da] * w[1][db];
+            if (wc > 0) {
+                int ia = i0[0] + da, ib = i0[1] + db, ft = f;
+                if (ia < 0 || ia >= S || ib < 0 || ib >= S) {
+                    const double u1 = (2.0 * (ia + 0.5)) / S - 1.0, v1 = (2.0 * (ib + 0.5)) / S - 1.0;
+                    double dx, dy, dz, u2, v2;
+                    cube_face_d0(f, u1, v1, dx, dy, dz);
+                    cube_face_uv(dx, dy, dz, ft, u2, v2);
+                    ia = cube_texel_of(u2, S), ib = cube_texel_of(v2, S);
+                }
+                const rtr_gather_out& t = texels[((long long)ft * S + ib) * S + ia];
+                ok = ok && t.valid != 0;
+                ++used;
+                for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + wc * t.v[ch];
+            }
+        }
+    if (!ok) return o;
+    o.v[0] = acc[0], o.v[1] = acc[1], o.v[2] = acc[2];
+    o.count = used, o.valid = 1;
+    return o;
+}
+/* the levels of a chain as a kernel argument */
+struct ChainK {
+    rtr_cube_level lv[RTR_CHAIN_MAX_LEVELS];
+    int n;
+};
+/* rtr_cube_chain_lookup of one query over the records of a valid chain */
+RT_HD rtr_gather_out cube_chain_lookup_one(const rtr_cube_level* lv, int n, const rtr_gather_out* __restrict__ texels,
+                                           const rtr_cube_query& q) {
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    const double x = q.d[0], y = q.d[1], z = q.d[2];
+    rtr_probe_point p;
+    p.p[0] = x, p.p[1] = y, p.p[2] = z;
+    const double len = __builtin_sqrt(x * x + y * y + z * z);
+    if (probe_point_bad(p) || !(len > 0.0 && len < __builtin_huge_val()) || !__builtin_isfinite(q.alpha)) return o;
+    double a = q.alpha > lv[0].alpha ? q.alpha : lv[0].alpha;
+    a = a < lv[n - 1].alpha ? a : lv[n - 1].alpha;
+    int i = 0;
+    for (int k = 1; k < n; ++k)
+        if (lv[k].alpha <= a) i = k;
+    if (n >= 2 && i > n - 2) i = n - 2;
+    const double t = n >= 2 ? (a - lv[i].alpha) / (lv[i + 1].alpha - lv[i].alpha) : 0.0;
+    const rtr_gather_out x0 = cube_seam_lookup(lv[i].face_size, texels + lv[i].offset, x, y, z);
+    if (t == 0) return x0;
+    const rtr_gather_out x1 = cube_seam_lookup(lv[i + 1].face_size, texels + lv[i + 1].offset, x, y, z);
+    if (!x0.valid || !x1.valid) return o;
+    for (int ch = 0; ch < 3; ++ch) o.v[ch] = (1.0 - t) * x0.v[ch] + t * x1.v[ch];
+    o.count = x0.count + x1.count, o.valid = 1;
+    return o;
+}
+
 struct ResolveK {
     RenderK r;
     double* out; /* linear mean radiance, 3 doubles per pixel */

@@ -29,11 +29,14 @@
  *                                   through Renderer::closest_hits, then Renderer::ambient_occlusion casts N hemisphere rays
  *                                   of length D (default: unbounded) at every hit's (p, n); a pixel is count / N grey, 1.0
  *                                   where the centre ray misses, stored like a render.  Not with --pick, --adaptive, --turntable
- *           [--capture x,y,z --capture-out file.hdr [--face S] [--capture-spp N] [--latlong W,H]]   nothing is path-traced per
+ *           [--capture x,y,z --capture-out file.hdr [--face S] [--capture-spp N] [--latlong W,H] [--capture-levels L]]   nothing is path-traced per
  *                                   pixel: Renderer::capture_cube makes a cube map of 6 x S x S texels (default 32), N
  *                                   (default 16) jittered rays each, of what surrounds the point under the integrator
  *                                   and --seed, and Renderer::save_environment writes it as a W x H (default 4S x 2S)
- *                                   equirectangular Radiance .hdr file, the map an EnvironmentLight reads
+ *                                   equirectangular Radiance .hdr file, the map an EnvironmentLight reads.  With
+ *                                   --capture-levels L (1..13) Renderer::prefilter_cube makes the chain of L GGX-filtered
+ *                                   levels (S <= 512 for L > 1) and every level is written at W x H: file.hdr is level 0,
+ *                                   file.L<i>.hdr level i
  *           [--probes NX,NY,NZ --probe-box x0,y0,z0,x1,y1,z1 [--probe-samples N]]   nothing is path-traced per pixel: a grid of
  *                                   NX x NY x NZ light probes whose first and last stand on the box corners (an axis with one
  *                                   probe: at the lower corner) goes through Renderer::light_probes with N (default 64) sphere
@@ -188,7 +191,7 @@ int main(int argc, char** argv) {
     double probe_box[6];
     bool probes = false, probe_boxed = false, probe_sampled = false;
     double capture_at[3] = {0, 0, 0};
-    int capture_face = 32, capture_spp = 16, latlong[2] = {0, 0};
+    int capture_face = 32, capture_spp = 16, latlong[2] = {0, 0}, capture_levels = 0;
     bool capture = false, capture_face_set = false, capture_spp_set = false, latlong_set = false;
     std::string capture_out;
     std::vector<int> devices{0}, passes;
@@ -306,6 +309,15 @@ int main(int argc, char** argv) {
             else capture_spp = (int)v, capture_spp_set = true;
         }
         else if (!std::strcmp(argv[k], "--capture-out") && k + 1 < argc) capture_out = argv[++k];
+        else if (!std::strcmp(argv[k], "--capture-levels") && k + 1 < argc) {
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (!end || *end || v < 1 || v > 13) {
+                std::cerr << "--capture-levels: an integer in 1..13, not " << argv[k] << "\n";
+                return 2;
+            }
+            capture_levels = (int)v;
+        }
         else if (!std::strcmp(argv[k], "--latlong") && k + 1 < argc) {
             char tail;
             latlong_set = std::sscanf(argv[++k], "%d,%d%c", &latlong[0], &latlong[1], &tail) == 2 && latlong[0] >= 1 &&
@@ -411,8 +423,12 @@ int main(int argc, char** argv) {
                 std::cerr << "--probe-box: the upper corner must lie above the lower one on every axis with more than one probe\n";
                 return 2;
             }
-    if ((capture_face_set || capture_spp_set || !capture_out.empty() || latlong_set) && !capture) {
-        std::cerr << "--face, --capture-spp, --capture-out and --latlong go with --capture\n";
+    if ((capture_face_set || capture_spp_set || !capture_out.empty() || latlong_set || capture_levels) && !capture) {
+        std::cerr << "--face, --capture-spp, --capture-out, --latlong and --capture-levels go with --capture\n";
+        return 2;
+    }
+    if (capture_levels > 1 && capture_face > 512) {
+        std::cerr << "--capture-levels above 1 needs --face of at most 512\n";
         return 2;
     }
     if (capture && capture_out.empty()) {
@@ -553,6 +569,26 @@ int main(int argc, char** argv) {
         }
         std::cout << "capture: 6 x " << capture_face << " x " << capture_face << " texels x " << capture_spp << " samples -> "
                   << capture_out << " (" << latlong[0] << " x " << latlong[1] << ")\n";
+        if (capture_levels > 1) { /* level 0 is written above; the filtered levels go beside it */
+            std::vector<rtr_cube_level> plan;
+            const std::vector<rtr_gather_out> chain = renderer.prefilter_cube(cube, capture_face, capture_levels, plan);
+            const size_t dot = capture_out.rfind(".hdr");
+            const std::string stem = dot != std::string::npos && dot + 4 == capture_out.size() ? capture_out.substr(0, dot) : capture_out;
+            for (int i = 1; i < capture_levels && !chain.empty(); ++i) {
+                const size_t recs = 6 * (size_t)plan[i].face_size * plan[i].face_size;
+                const std::vector<rtr_gather_out> level(chain.begin() + plan[i].offset, chain.begin() + plan[i].offset + recs);
+                const std::string path = stem + ".L" + std::to_string(i) + ".hdr";
+                if (!renderer.save_environment(path, level, plan[i].face_size, latlong[0], latlong[1])) {
+                    std::cerr << "cannot write " << path << " (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+                    return 1;
+                }
+                std::cout << "level " << i << ": face " << plan[i].face_size << ", alpha " << plan[i].alpha << " -> " << path << "\n";
+            }
+            if (chain.empty()) {
+                std::cerr << "prefilter failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+                return 1;
+            }
+        }
         return 0;
     }
     if (probes) {

@@ -512,6 +512,53 @@ class Renderer {
         return m_status == RTR_OK;
     }
 
+    /* Filtered cube maps (include/rtr_hip.h: rtr_cube_filter, rtr_cube_chain_*), on the first context; no scene is needed.
+     * prefilter_cube: the chain rtr_cube_chain_plan lays out for one capture (6 * face_size^2 records) -- `plan` receives
+     * its levels --, level 0 the capture itself, every further level its GGX filter at the plan's alpha and face size; the
+     * records of all levels in one vector.  chain_lookup: the seam-aware lookup of the queries in such a chain, two levels
+     * blended by alpha.  An empty vector and last_status() / last_error() on failure. */
+    std::vector<rtr_gather_out> prefilter_cube(const std::vector<rtr_gather_out>& texels, int face_size, int levels,
+                                               std::vector<rtr_cube_level>& plan, double cos_cut = 0.0) {
+        m_status = RTR_OK;
+        int64_t n_records = 0;
+        plan.assign(levels > 0 ? (size_t)levels : 0, rtr_cube_level{});
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if ((m_status = rtr_cube_chain_plan(face_size, levels, plan.data(), &n_records)))
+            m_error = "face_size outside 1 .. 4096 or levels outside 1 .. 13";
+        else if (texels.size() != 6 * (size_t)face_size * face_size)
+            m_error = "a capture of 6 * face_size^2 records expected", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_gather_out> out;
+        if (m_status == RTR_OK) {
+            out.resize((size_t)n_records);
+            std::copy(texels.begin(), texels.end(), out.begin());
+            for (int i = 1; i < levels && m_status == RTR_OK; ++i) {
+                rtr_cube_filter_params fp;
+                rtr_cube_filter_defaults(&fp);
+                fp.face_in = face_size, fp.face_out = plan[i].face_size, fp.alpha = plan[i].alpha, fp.cos_cut = cos_cut;
+                if ((m_status = rtr_cube_filter(m_ctx[0], &fp, texels.data(), out.data() + plan[i].offset, 1)))
+                    m_error = rtr_last_error(m_ctx[0]);
+            }
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+    std::vector<rtr_gather_out> chain_lookup(const std::vector<rtr_cube_level>& plan, const std::vector<rtr_gather_out>& records,
+                                             const std::vector<rtr_cube_query>& queries) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        std::vector<rtr_gather_out> out;
+        if (m_status == RTR_OK) {
+            out.resize(queries.size());
+            if ((m_status = rtr_cube_chain_lookup(m_ctx[0], plan.data(), (int32_t)plan.size(), records.data(), (int64_t)records.size(),
+                                                  queries.data(), out.data(), (int64_t)queries.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+
     /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
      * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
      * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */

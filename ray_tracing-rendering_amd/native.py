@@ -36,7 +36,9 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_probe_ray", "rtr_sh_basis", "rtr_sh_irradiance", "rtr_probe_lookup", "rtr_probe_lookup_device",
            "rtr_probe_lookup_one", "rtr_capture_defaults", "rtr_capture_cube", "rtr_capture_cube_device", "rtr_capture_ray",
            "rtr_cube_lookup", "rtr_cube_lookup_device", "rtr_cube_lookup_one", "rtr_latlong_direction",
-           "rtr_cube_to_latlong", "rtr_write_rgbe")
+           "rtr_cube_to_latlong", "rtr_write_rgbe", "rtr_cube_filter_defaults", "rtr_cube_filter", "rtr_cube_filter_device",
+           "rtr_cube_filter_one", "rtr_cube_chain_plan", "rtr_cube_chain_lookup", "rtr_cube_chain_lookup_device",
+           "rtr_cube_chain_lookup_one")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
@@ -218,6 +220,15 @@ def lib():
     L.rtr_latlong_direction.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
     L.rtr_cube_to_latlong.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, vp]
     L.rtr_write_rgbe.argtypes = [C.c_char_p, C.c_int32, C.c_int32, vp]
+    L.rtr_cube_filter_defaults.argtypes = [P(A.CubeFilterParamsC)]
+    L.rtr_cube_filter_defaults.restype = None
+    L.rtr_cube_filter.argtypes = [vp, P(A.CubeFilterParamsC), vp, vp, C.c_int64]
+    L.rtr_cube_filter_device.argtypes = [vp, P(A.CubeFilterParamsC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_cube_filter_one.argtypes = [P(A.CubeFilterParamsC), vp, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rtr_cube_chain_plan.argtypes = [C.c_int32, C.c_int32, vp, P(C.c_int64)]
+    L.rtr_cube_chain_lookup.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64]
+    L.rtr_cube_chain_lookup_device.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, C.c_int]
+    L.rtr_cube_chain_lookup_one.argtypes = [vp, C.c_int32, vp, vp, vp]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -653,6 +664,88 @@ def write_rgbe(path, rgb):
         raise RtrError(rc, "rtr_write_rgbe: bad size, or %s cannot be written" % path)
 
 
+def cube_filter_defaults(**overrides):
+    """rtr_cube_filter_params with the library's defaults (rtr_cube_filter_defaults: face_in 32, face_out 16, alpha 0.25,
+    cos_cut 0), fields replaced by ``overrides``."""
+    return _defaults(A.CubeFilterParamsC, "rtr_cube_filter_defaults", ("face_in", "face_out", "alpha", "cos_cut"), overrides)
+
+
+def _filter_cubes(texels, fp):
+    """The source records of a filter call as a flat array, and how many cubes of 6 * face_in^2 they are"""
+    t = np.ascontiguousarray(texels, dtype=A.GATHER_OUT_DTYPE).reshape(-1)
+    per = 6 * int(fp.face_in) ** 2
+    if per <= 0 or t.size % per:
+        raise ValueError("the source holds whole cubes of 6 * face_in^2 records")
+    return t, t.size // per
+
+
+def cube_filter_host(texels, params=None, **overrides):
+    """rtr_cube_filter_one for every output texel of every cube (host only, no context; a loop for tests): the
+    ``GATHER_OUT_DTYPE`` records [n_cubes, 6, face_out, face_out] of the source ``texels`` ([n_cubes, 6, face_in, face_in]
+    or flat)."""
+    fp = params if params is not None else cube_filter_defaults(**overrides)
+    L = lib()
+    So = int(fp.face_out)
+    if not 1 <= So <= A.CUBE_FILTER_MAX_FACE or not 1 <= int(fp.face_in) <= A.CUBE_FILTER_MAX_FACE:
+        raise RtrError(A.RTR_ERR_INVALID, "rtr_cube_filter_one: face_in or face_out outside 1 .. 512")
+    t, n = _filter_cubes(texels, fp)
+    out = np.zeros((n, 6, So, So), dtype=A.GATHER_OUT_DTYPE)
+    per_in, flat = 6 * int(fp.face_in) ** 2 * 32, 0
+    for k in range(n):
+        for f in range(6):
+            for b in range(So):
+                for a in range(So):
+                    rc = L.rtr_cube_filter_one(C.byref(fp), t.ctypes.data + k * per_in, f, a, b, out.ctypes.data + 32 * flat)
+                    if rc != 0:
+                        raise RtrError(rc, "rtr_cube_filter_one: bad params")
+                    flat += 1
+    return out
+
+
+def cube_chain_plan(face_size, n_levels):
+    """rtr_cube_chain_plan: (levels, n_records) -- a ctypes array of ``n_levels`` rtr_cube_level for a capture of
+    ``face_size`` and the records all levels hold."""
+    levels = (A.CubeLevelC * max(int(n_levels), 1))()
+    n = C.c_int64()
+    rc = lib().rtr_cube_chain_plan(int(face_size), int(n_levels), C.byref(levels), C.byref(n))
+    if rc != 0:
+        raise RtrError(rc, "rtr_cube_chain_plan: face_size outside 1 .. 4096 or n_levels outside 1 .. 13")
+    return levels, int(n.value)
+
+
+def cube_levels(levels):
+    """A ctypes array of rtr_cube_level from ``levels``: such an array, or (face_size, offset, alpha) triples"""
+    if isinstance(levels, C.Array) and levels._type_ is A.CubeLevelC:
+        return levels
+    arr = (A.CubeLevelC * max(len(levels), 1))()
+    for i, (s, o, a) in enumerate(levels):
+        arr[i] = A.CubeLevelC(int(s), 0, int(o), float(a))
+    return arr
+
+
+def cube_queries(directions, alpha):
+    """A ``CUBE_QUERY_DTYPE`` array from (n, 3) directions and alphas (a number or [n])"""
+    d = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+    q = np.zeros(len(d), dtype=A.CUBE_QUERY_DTYPE)
+    q["d"], q["alpha"] = d, alpha
+    return q
+
+
+def cube_chain_lookup_host(levels, texels, queries, n_levels=None):
+    """rtr_cube_chain_lookup_one for every query (``CUBE_QUERY_DTYPE``; host only, no context): a ``GATHER_OUT_DTYPE`` array."""
+    lv = cube_levels(levels)
+    n_levels = len(levels) if n_levels is None else int(n_levels)
+    t = np.ascontiguousarray(texels, dtype=A.GATHER_OUT_DTYPE).reshape(-1)
+    q = np.ascontiguousarray(queries, dtype=A.CUBE_QUERY_DTYPE)
+    out = np.zeros(len(q), dtype=A.GATHER_OUT_DTYPE)
+    L = lib()
+    for k in range(len(q)):
+        rc = L.rtr_cube_chain_lookup_one(C.byref(lv), n_levels, t.ctypes.data, q.ctypes.data + 32 * k, out.ctypes.data + 32 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_cube_chain_lookup_one: bad chain")
+    return out
+
+
 def srgb_thresholds():
     """rtr_display_srgb_thresholds: the 256 doubles S that define RTR_ENCODE_SRGB (code = how many of S[1..255] are <= t)."""
     out = np.zeros(256, dtype=np.float64)
@@ -1032,6 +1125,42 @@ class Context:
         """rtr_cube_lookup_device: the same over device pointers, on the context stream behind what is queued there."""
         self._chk(self._L.rtr_cube_lookup_device(self._h, int(face_size), C.c_void_p(texels_ptr),
                                                  *_into_tail(directions_ptr, out_ptr, n, blocking)))
+
+    # filtered cube maps (include/rtr_hip.h: rtr_cube_filter*, rtr_cube_chain_*)
+    def cube_filter(self, texels, params=None, out=None, **overrides):
+        """rtr_cube_filter: the GGX-filtered records [n_cubes, 6, face_out, face_out] of the source cubes ``texels``
+        ([n_cubes, 6, face_in, face_in] or flat).  Blocking; needs no scene."""
+        fp = params if params is not None else cube_filter_defaults(**overrides)
+        t, n = _filter_cubes(texels, fp)
+        So = int(fp.face_out)
+        flat = _records_out(None if out is None else out.reshape(-1), n * 6 * So * So, A.GATHER_OUT_DTYPE)
+        self._chk(self._L.rtr_cube_filter(self._h, C.byref(fp), t.ctypes.data, flat.ctypes.data, n))
+        return flat[:n * 6 * So * So].reshape(n, 6, So, So)
+
+    def cube_filter_into(self, texels_ptr, out_ptr, n_cubes, params=None, blocking=False, **overrides):
+        """rtr_cube_filter_device: n_cubes * 6 * face_in^2 records at device pointer ``texels_ptr`` -> n_cubes * 6 *
+        face_out^2 at ``out_ptr``, on the context stream behind what is queued there."""
+        fp = params if params is not None else cube_filter_defaults(**overrides)
+        self._chk(self._L.rtr_cube_filter_device(self._h, C.byref(fp), *_into_tail(texels_ptr, out_ptr, n_cubes, blocking)))
+
+    def cube_chain_lookup(self, levels, texels, queries, out=None, n_levels=None):
+        """rtr_cube_chain_lookup: the seam-aware lookup of ``queries`` (``CUBE_QUERY_DTYPE``) in the chain ``levels`` over the
+        records ``texels``, two levels blended by alpha.  Returns a ``GATHER_OUT_DTYPE`` array.  Blocking; needs no scene."""
+        lv = cube_levels(levels)
+        t = np.ascontiguousarray(texels, dtype=A.GATHER_OUT_DTYPE).reshape(-1)
+        q = np.ascontiguousarray(queries, dtype=A.CUBE_QUERY_DTYPE)
+        out = _records_out(out, len(q), A.GATHER_OUT_DTYPE)
+        self._chk(self._L.rtr_cube_chain_lookup(self._h, C.byref(lv), len(levels) if n_levels is None else int(n_levels),
+                                                t.ctypes.data, len(t), q.ctypes.data, out.ctypes.data, len(q)))
+        return out
+
+    def cube_chain_lookup_into(self, levels, texels_ptr, n_records, queries_ptr, out_ptr, n, blocking=False, n_levels=None):
+        """rtr_cube_chain_lookup_device: the same over device pointers (``levels`` stays a host table), on the context
+        stream behind what is queued there."""
+        lv = cube_levels(levels)
+        self._chk(self._L.rtr_cube_chain_lookup_device(self._h, C.byref(lv), len(levels) if n_levels is None else int(n_levels),
+                                                       C.c_void_p(texels_ptr), int(n_records),
+                                                       *_into_tail(queries_ptr, out_ptr, n, blocking)))
 
     # display transform (include/rtr_hip.h: rtr_display_*)
     @staticmethod

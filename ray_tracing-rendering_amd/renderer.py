@@ -422,7 +422,8 @@ class Cubemap:
     """One environment capture (include/rtr_hip.h: rtr_capture_cube): ``texels``, ``GATHER_OUT_DTYPE`` records [6, S, S]
     (face, row, column).  ``lookup`` reads it along directions (rtr_cube_lookup_one, or rtr_cube_lookup on a context),
     ``to_latlong`` resamples it to the equirectangular layout of the reference's EnvironmentLight, ``save_hdr`` writes that
-    as a Radiance .hdr file an EnvironmentLight can read."""
+    as a Radiance .hdr file an EnvironmentLight can read, ``prefilter`` makes the chain of GGX-filtered levels a glossy
+    object reads (``CubeChain``)."""
 
     def __init__(self, texels):
         t = np.ascontiguousarray(texels, dtype=A.GATHER_OUT_DTYPE)
@@ -453,6 +454,61 @@ class Cubemap:
         """``to_latlong(width, height)`` written with rtr_write_rgbe."""
         from . import native
         native.write_rgbe(path, self.to_latlong(width, height))
+
+    def prefilter(self, levels=5, cos_cut=0.0, ctx=None):
+        """A ``CubeChain`` of ``levels`` levels (rtr_cube_chain_plan): level 0 is this capture, level i its GGX filter
+        (rtr_cube_filter) at the plan's alpha and face size.  ``ctx``: a context to filter on the device (default: the
+        host loop of rtr_cube_filter_one, for small cubes)."""
+        from . import native
+        plan, n_records = native.cube_chain_plan(self.face_size, levels)
+        records = np.zeros(n_records, dtype=A.GATHER_OUT_DTYPE)
+        records[:6 * self.face_size ** 2] = self.texels.reshape(-1)
+        for lv in list(plan)[1:]:
+            fp = native.cube_filter_defaults(face_in=self.face_size, face_out=lv.face_size, alpha=lv.alpha, cos_cut=cos_cut)
+            level = ctx.cube_filter(self.texels, fp) if ctx is not None else native.cube_filter_host(self.texels, fp)
+            records[lv.offset:lv.offset + 6 * lv.face_size ** 2] = level.reshape(-1)
+        return CubeChain(plan, records)
+
+
+class CubeChain:
+    """A capture and its filtered levels (include/rtr_hip.h: rtr_cube_chain_*): ``levels``, a ctypes array of
+    rtr_cube_level, and ``records``, the ``GATHER_OUT_DTYPE`` records of all of them."""
+
+    def __init__(self, levels, records):
+        self.levels = levels
+        self.records = np.ascontiguousarray(records, dtype=A.GATHER_OUT_DTYPE).reshape(-1)
+
+    def __len__(self):
+        return len(self.levels)
+
+    def level(self, i):
+        """Level ``i`` as a ``Cubemap``"""
+        lv = self.levels[i]
+        S = lv.face_size
+        return Cubemap(self.records[lv.offset:lv.offset + 6 * S * S].reshape(6, S, S))
+
+    def lookup_records(self, directions, roughness, ctx=None):
+        """The ``GATHER_OUT_DTYPE`` records of the seam-aware lookup along the directions [n, 3] at ``roughness`` (a number
+        or [n]); alpha = roughness squared, the levels around it blended."""
+        from . import native
+        r = np.asarray(roughness, dtype=np.float64)
+        q = native.cube_queries(directions, r * r)
+        if ctx is not None:
+            return ctx.cube_chain_lookup(self.levels, self.records, q)
+        return native.cube_chain_lookup_host(self.levels, self.records, q)
+
+    def lookup(self, directions, roughness, ctx=None):
+        """[n, 3] radiance of ``lookup_records``; zero where the lookup is invalid."""
+        return self.lookup_records(directions, roughness, ctx)["v"]
+
+    def save_hdr(self, prefix, width, height):
+        """Every level as a width x height equirectangular Radiance file: ``prefix``.hdr for level 0, ``prefix``.L<i>.hdr
+        for level i.  Returns the paths."""
+        paths = []
+        for i in range(len(self.levels)):
+            paths.append("%s.hdr" % prefix if i == 0 else "%s.L%d.hdr" % (prefix, i))
+            self.level(i).save_hdr(paths[-1], width, height)
+        return paths
 
 
 def check_denoise(params):
