@@ -962,6 +962,132 @@ int rtr_probe_lookup_device(rtr_context* ctx, const rtr_probe_grid* grid, const 
 int rtr_probe_lookup_one(const rtr_probe_grid* grid, const rtr_probe_sh* probes, const rtr_gather_point* query,
                          rtr_gather_out* out);
 
+/* ---- probe distance maps: how far a probe sees in each direction, and a grid lookup that weighs probes by it ----
+ * The grid lookup above blends the eight probes around a query by distance alone, so a query next to a wall takes light
+ * from the probe behind it.  A distance map records per probe the mean and the mean square of the distance to the nearest
+ * surface over an octahedral map of directions; rtr_probe_lookup_visible weighs every corner by the chance that the query
+ * is no farther from the probe than what the probe sees that way (the Chebyshev test of Majercik et al., "Dynamic Diffuse
+ * Global Illumination with Ray-Traced Irradiance Fields", JCGT 2019).  Every output bit is defined here: only + - * / sqrt,
+ * |x| and compares are used, in the order written, without contraction; x*x + y*y + z*z is (x*x + y*y) + z*z;
+ * unit(w) = (1 / sqrt(w.x*w.x + w.y*w.y + w.z*w.z)) * w is the gathers';  sg(t) = (t >= 0) ? 1.0 : -1.0.
+ *
+ * OCTAHEDRAL MAP: T x T texels, row b, column a, 1 <= T <= 64, over the square (u, v) in [-1, 1]^2.
+ *   DECODE (u, v) -> d:   z = (1.0 - |u|) - |v|
+ *                         z >= 0: x = u, y = v;   else: x = (1.0 - |v|) * sg(u), y = (1.0 - |u|) * sg(v)
+ *                         d = unit(x, y, z)                                           (rtr_octa_decode is the host form)
+ *   ENCODE d -> (ox, oy): s = (|x| + |y|) + |z|, which must be > 0; d need not be unit
+ *                         ox = x / s, oy = y / s
+ *                         z < 0: (ox, oy) = ((1.0 - |oy|) * sg(ox), (1.0 - |ox|) * sg(oy)), both from the old values
+ *                                                                                     (rtr_octa_encode is the host form)
+ *
+ * rtr_probe_depth: for each of `n` probes (rtr_probe_point) a T x T map of rtr_probe_depth_texel records, laid out
+ * [probe][row b][column a], T = params->map_size, each texel reduced from N = params->samples rays.
+ * RAY s (0 <= s < N) of texel e = b * T + a of probe k (k = its index in the call + params->point_base, modulo 2^32):
+ *   state = rtr_sample_seed_inline(seed, T * T, e, (int32_t)k, s)                    (rtr_seed.h)
+ *   jitter = 1: the captures' two draws, ju first, then jv.  jitter = 0: ju = jv = 0.5 and nothing is drawn.
+ *   u = (2.0 * (a + ju)) / T - 1.0;  v = (2.0 * (b + jv)) / T - 1.0                   (a, b and T converted to double)
+ *   d = DECODE(u, v)
+ * The ray is (origin p, direction d, time, [t_min, t_max]) with the state left after the draws (rtr_probe_depth_ray is the
+ * host form).  (hit, t, front_face) = what rtr_query_closest returns for that ray and state, draws inside media included;
+ * d is a unit vector, so t is a distance.  x_s = hit ? t : t_max.  A sample adds x_s to `mean` and x_s * x_s to `mean2`;
+ * a hit adds 1 to `hits`; a hit with front_face == 0 adds 1 to `back` (the probe looks at the inside of a surface;
+ * front_face is the reference's, which translate and rotate_y set again from the normal that already faces the ray: a hit
+ * under a transform always counts as a front face).
+ * REDUCTION: the gathers', word for word, over the two sums and the two counts: G = min(64, bit_ceil(N)); lane l adds its
+ * samples l, l + G, ... in increasing order into +0.0 / 0; then for off = G/2, ..., 1: a[l] = a[l] + a[l xor off]; then
+ * mean = (1.0 / N) * a[0], mean2 likewise.  The counts are not scaled.
+ *
+ * params: 1 <= map_size <= 64; samples as the captures' (1 .. 2^20); jitter 0 or 1; pad 0; time finite; t_min finite (any
+ * finite value: below 2^-100 the launch takes the plain IEEE divisions, the gathers' rule); t_max finite and > t_min --
+ * it has NO default: it is the distance of a miss and bounds what a map can tell apart, so the caller sets it (a grid
+ * wants somewhat more than its cell diagonal).  Everything else is the captures' contract: a probe is BAD if a component
+ * of p is not finite; the host entry rejects the whole batch with RTR_ERR_INVALID, names the first bad index in
+ * rtr_last_error and leaves the outputs untouched; the device entry writes all-zero records (valid 0) for every texel of
+ * such a probe without casting, and every other texel gets valid = 1.  Bad params, n < 0 or a NULL array is
+ * RTR_ERR_INVALID, a call before rtr_upload_scene RTR_ERR_NO_SCENE, in this order: context, params, n / NULL, scene -- all
+ * before any device work.  n == 0 is RTR_OK without a launch.  The host entry stages the probes once in the buffer of the
+ * gathers' host entries and brings the records back in slices of at most 2^20 texels; the device entry takes device
+ * pointers (8-byte aligned; in and out must not overlap), runs on the context stream behind whatever is queued there and
+ * returns at once unless `blocking`.  Neither touches anything a queued render or accumulator pass uses, nor the
+ * statistics of rtr_get_stats; rtr_cancel does not apply.  Probes can be sharded over contexts: shard j passes
+ * point_base = its first probe's index. */
+typedef struct rtr_probe_depth_texel { /* 32 bytes */
+    double mean, mean2;             /* of x_s and of x_s * x_s over the texel's samples */
+    int32_t hits, back, valid, pad; /* pad is written 0 */
+} rtr_probe_depth_texel;
+
+typedef struct rtr_probe_depth_params { /* 48 bytes */
+    int32_t map_size, samples;
+    uint32_t seed, point_base;
+    int32_t jitter, pad;            /* pad must be 0 */
+    double time, t_min, t_max;
+} rtr_probe_depth_params;
+
+/* map_size 16, samples 8, seed 0, point_base 0, jitter 1, time 0, t_min 0.001, t_max 0: t_max must be set by the caller */
+void rtr_probe_depth_defaults(rtr_probe_depth_params* p);
+
+int rtr_probe_depth(rtr_context* ctx, const rtr_probe_depth_params* params, const rtr_probe_point* points,
+                    rtr_probe_depth_texel* out, int64_t n);
+int rtr_probe_depth_device(rtr_context* ctx, const rtr_probe_depth_params* params, const rtr_probe_point* d_points,
+                           rtr_probe_depth_texel* d_out, int64_t n, int blocking);
+
+/* Host-only, needs no context: ray s of texel (a, b) of the probe at `index_in_call` (the definition above; `point` is
+ * that probe's record, not an array).  RTR_ERR_INVALID for a bad probe, bad params, a negative index, a or b outside
+ * [0, T) or s outside [0, samples). */
+int rtr_probe_depth_ray(const rtr_probe_depth_params* params, const rtr_probe_point* point, int64_t index_in_call, int32_t a,
+                        int32_t b, int32_t s, rtr_ray* out);
+
+/* Host-only: ENCODE and DECODE as defined above, the same functions the kernels call; the arguments are taken as given. */
+void rtr_octa_encode(const double d[3], double uv[2]);
+void rtr_octa_decode(const double uv[2], double d[3]);
+
+/* VISIBLE GRID LOOKUP: rtr_probe_lookup with two more inputs, the distance maps of the grid's probes (`depth`:
+ * [probe][b][a], probe indexed like the rtr_probe_sh array, T = params->map_size) and the parameter block below.  The grid
+ * rule is rtr_probe_lookup's, and in addition probes * T * T <= 2^24; the query tests are rtr_probe_lookup's.
+ *   w = unit(n);  pb = p + normal_bias * w                      (the point the visibility is tested at, lifted off the surface)
+ *   axis weights and corner indices from the unbiased p, exactly as above; corners with dz outermost, then dy, then dx
+ * A corner with probe position P[a] = origin[a] + (double)i[a] * spacing[a] (i: the clipped index) and
+ * tri = (wx * wy) * wz is a CANDIDATE if tri > 0 and its rtr_probe_sh has valid != 0.  For a candidate:
+ *   wrap weight:  e = P - p;  el2 = e.e;  cosn = (el2 > 0) ? (e.w) / sqrt(el2) : 0.0;  h = (cosn + 1.0) * 0.5;
+ *                 wb = h * h + 0.2                               (a probe behind the surface still counts a little)
+ *   visibility:   dv = pb - P;  r2 = dv.dv;  !(r2 > 0): c = 1.0.  Otherwise r = sqrt(r2) and (m1, m2, ok) = FETCH(dv) in
+ *                 that probe's map;  !ok or r <= m1: c = 1.0.  Otherwise var = |m2 - m1 * m1|, dd = r - m1,
+ *                 den = var + dd * dd,  c = (den > 0) ? var / den : 0.0,  then c = (c * c) * c
+ *   weight:       wv = wb * c;  if !(wv >= 0x1p-20): wv = 0x1p-20;  wgt = tri * wv
+ *   wsum = wsum + wgt;  acc[i][ch] = acc[i][ch] + wgt * probe.c[i][ch]
+ * (a.b of two vectors is (a.x*b.x + a.y*b.y) + a.z*b.z.)  The ending is rtr_probe_lookup's: no candidate gives
+ * {0, 0, 0, count 0, valid 0}; otherwise c = (1.0 / wsum) * acc, v = rtr_sh_irradiance(c, n), count = the candidates, valid 1.
+ * FETCH(d):  (ox, oy) = ENCODE(d).  Per axis, with c = ox for the columns and c = oy for the rows:
+ *     g = ((c + 1.0) * T) * 0.5 - 0.5;  i0 = (g < 0) ? -1 : (int)g;  t = g - (double)i0;  w0 = 1.0 - t, w1 = t
+ *   There is no clamp: the indices -1 and T fold over the map's edge, where the octahedral square continues in itself.
+ *   The four taps are visited with db outermost, then da, w = wa[da] * wb[db]; a tap is USED if w > 0.  Its index
+ *   (ia, ib) = (i0a + da, i0b + db) is folded in this order:
+ *     if ia < 0: (ia, ib) = (0, T-1-ib);   else if ia > T-1: (ia, ib) = (T-1, T-1-ib)
+ *     then if ib < 0: (ib, ia) = (0, T-1-ia);   else if ib > T-1: (ib, ia) = (T-1, T-1-ia)
+ *   m1 = m1 + w * mean, m2 = m2 + w * mean2, both from +0.0;  ok is false if a used tap has valid == 0.
+ * 0.2, the cube and the floor 2^-20 are the published constants; here they are definitions.  The floor keeps a query that
+ * no corner "can see" normalised, so it never comes out black.  params: 1 <= map_size <= 64; pad 0; normal_bias finite
+ * and >= 0; reserved 0.  Checks in this order: context, grid, params, n / NULL; the host entry then rejects a batch with a
+ * bad query and names the index; the device entry writes valid 0 for it without reading a probe.  No scene is needed;
+ * n == 0 is RTR_OK.  The host entry stages the rtr_probe_sh records and the maps once and the queries in slices of 2^20;
+ * the device entry is stream-ordered like the gathers' (8-byte aligned pointers, `blocking`). */
+typedef struct rtr_probe_visible_params { /* 32 bytes */
+    int32_t map_size, pad;          /* pad must be 0 */
+    double normal_bias;             /* finite, >= 0 */
+    double reserved[2];             /* 0 */
+} rtr_probe_visible_params;
+
+int rtr_probe_lookup_visible(rtr_context* ctx, const rtr_probe_grid* grid, const rtr_probe_sh* probes,
+                             const rtr_probe_depth_texel* depth, const rtr_probe_visible_params* params,
+                             const rtr_gather_point* queries, rtr_gather_out* out, int64_t n);
+int rtr_probe_lookup_visible_device(rtr_context* ctx, const rtr_probe_grid* grid, const rtr_probe_sh* d_probes,
+                                    const rtr_probe_depth_texel* d_depth, const rtr_probe_visible_params* params,
+                                    const rtr_gather_point* d_queries, rtr_gather_out* d_out, int64_t n, int blocking);
+/* Host-only, needs no context: the lookup of one query over HOST records, the same function the kernel calls.
+ * RTR_ERR_INVALID for a bad grid, bad params, a bad query or a NULL pointer. */
+int rtr_probe_lookup_visible_one(const rtr_probe_grid* grid, const rtr_probe_sh* probes, const rtr_probe_depth_texel* depth,
+                                 const rtr_probe_visible_params* params, const rtr_gather_point* query, rtr_gather_out* out);
+
 /* ---- environment captures: cube maps of radiance about points in space, their lookup, and Radiance .hdr output ----
  * Gathers and probes reduce what arrives at a point to one normal or to nine coefficients.  A capture keeps the directions:
  * for each of `n` centres (rtr_probe_point) six faces of S x S texels, each texel the mean of Integrator::Li over

@@ -88,6 +88,13 @@ typedef struct rtr_capture_record {
 /* size_of_out must be sizeof(rtr_capture_record) */
 int rtr_test_last_capture(rtr_context* ctx, rtr_capture_record* out, size_t size_of_out);
 
+/* And for the probe distance maps: k_probe_depth<trav> of the last rtr_probe_depth call; trav = -1: none yet. */
+typedef struct rtr_probe_depth_record {
+    int32_t trav, lg;
+} rtr_probe_depth_record;
+/* size_of_out must be sizeof(rtr_probe_depth_record) */
+int rtr_test_last_probe_depth(rtr_context* ctx, rtr_probe_depth_record* out, size_t size_of_out);
+
 /* What the library makes of a scene before anything reaches a device: the validator, the host-only lowering
  * (csrc/rt_lower.h: lower_scene) and the two decisions every launch hangs on -- pick_trav and, for `integrator` and the
  * render `flags`, mega_variant (csrc/rt_select.h).  Needs no context and no GPU.  RT_TRAV_*, RT_MS_*, RT_TIE_FLAG and

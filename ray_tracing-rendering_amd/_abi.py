@@ -151,6 +151,26 @@ PROBE_GRID_SIZE = 64
 assert C.sizeof(ProbeGridC) == PROBE_GRID_SIZE
 
 
+class ProbeDepthParamsC(C.Structure):
+    """rtr_probe_depth_params (include/rtr_hip.h): the distance maps of rtr_probe_depth"""
+    _fields_ = [("map_size", C.c_int32), ("samples", C.c_int32), ("seed", C.c_uint32), ("point_base", C.c_uint32),
+                ("jitter", C.c_int32), ("pad", C.c_int32), ("time", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double)]
+
+
+class ProbeVisibleParamsC(C.Structure):
+    """rtr_probe_visible_params (include/rtr_hip.h): the visibility-weighted grid lookup rtr_probe_lookup_visible"""
+    _fields_ = [("map_size", C.c_int32), ("pad", C.c_int32), ("normal_bias", C.c_double), ("reserved", C.c_double * 2)]
+
+
+PROBE_DEPTH_PARAMS_SIZE, PROBE_VISIBLE_PARAMS_SIZE = 48, 32
+assert C.sizeof(ProbeDepthParamsC) == PROBE_DEPTH_PARAMS_SIZE and C.sizeof(ProbeVisibleParamsC) == PROBE_VISIBLE_PARAMS_SIZE
+# rtr_probe_depth_texel: one texel of a probe's octahedral distance map
+PROBE_DEPTH_DTYPE = np.dtype([("mean", "<f8"), ("mean2", "<f8"), ("hits", "<i4"), ("back", "<i4"), ("valid", "<i4"),
+                              ("pad", "<i4")])
+assert PROBE_DEPTH_DTYPE.itemsize == 32
+PROBE_DEPTH_MAX_MAP = 64
+
+
 class CaptureParamsC(C.Structure):
     """rtr_capture_params (include/rtr_hip.h): the environment captures of rtr_capture_cube"""
     _fields_ = [("face_size", C.c_int32), ("samples", C.c_int32), ("seed", C.c_uint32), ("point_base", C.c_uint32),

@@ -1,6 +1,6 @@
 /*
  * rt_batch.h -- host only: what the units that answer a batch of caller records share (rtr_query.hip, rtr_gather.hip,
- * rtr_probe.hip, rtr_capture.hip, rtr_cube.hip).  The entry checks they have in common, the one path of a host entry from the caller's array to the
+ * rtr_probe.hip, rtr_probe_depth.hip, rtr_capture.hip, rtr_cube.hip).  The entry checks they have in common, the one path of a host entry from the caller's array to the
  * kernel and back (staged_slices), the body of a device-pointer entry (device_entry), and for the gathers and probes the
  * launch set-up, the chunked launcher and the single-ray entry.  No device code; the kernels and which one a call runs
  * stay with the units.
@@ -142,13 +142,13 @@ int launch_points(rtr_context* c, Kern kernel, const DScene& ds, const K& all, s
     return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("point kernel launch: ") + hipGetErrorString(e));
 }
 
-/* The same for the captures, whose records are texels: the launches split on the record of all.out (CaptureK::k0, n), the
- * centre array stays where it is */
-template <typename Kern>
-int launch_texels(rtr_context* c, Kern kernel, const DScene& ds, const CaptureK& all, size_t lds) {
+/* The same for the captures and the probe distance maps, whose records are texels: the launches split on the record of
+ * all.out (k0, n of CaptureK / DepthK), the centre array stays where it is */
+template <typename Kern, typename K>
+int launch_texels(rtr_context* c, Kern kernel, const DScene& ds, const K& all, size_t lds) {
     if (int rc = set_lds(c, kernel, lds)) return rc;
     for (long long k0 = all.k0; k0 < all.n; k0 += kLaunchPoints) {
-        CaptureK k = all;
+        K k = all;
         k.k0 = k0, k.n = all.n - k0 < kLaunchPoints ? all.n : k0 + kLaunchPoints;
         const long long lanes = (k.n - k.k0) << k.lg;
         hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), lds, c->stream, ds, k);

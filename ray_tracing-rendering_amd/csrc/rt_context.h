@@ -45,7 +45,7 @@ struct rtr_context {
     /* per-render workspace */
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
-    /* the host entries of rtr_query_*, rtr_gather_*, rtr_probe_*, rtr_capture_cube, rtr_cube_lookup: one slice of inputs and its results (staged_slices of
+    /* the host entries of rtr_query_*, rtr_gather_*, rtr_probe_*, rtr_capture_cube, rtr_cube_lookup, rtr_probe_depth, rtr_probe_lookup_visible: one slice of inputs and its results (staged_slices of
      * rt_batch.h).  One buffer serves them all: each returns only behind its last slice's wait, and the device entries
      * never touch it */
     DevBuf b_batch;
@@ -63,6 +63,7 @@ struct rtr_context {
     rtr_debug_gather last_gather{-1, -1, 0, 0};                         /* rtr_debug_last_gather */
     rtr_debug_probe last_probe{-1, -1, 0};                              /* rtr_debug_last_probe */
     rtr_debug_capture last_capture{-1, -1, 0};                          /* rtr_debug_last_capture */
+    rtr_debug_probe_depth last_probe_depth{-1, 0};                      /* rtr_debug_last_probe_depth */
     /* Cancel.  Renders are numbered; rtr_cancel() covers every render issued so far: it stores the newest
      * id in `cancelled_upto` and in the device word the kernels poll.  A render issued afterwards carries a
      * larger id, so nothing has to be reset between renders and a cancel that arrives while a render waits

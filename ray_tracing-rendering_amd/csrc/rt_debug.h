@@ -52,6 +52,11 @@ struct rtr_debug_capture {
     int trav;  /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no capture yet */
     int lg;    /* log2 of the lanes that share a texel */
 };
+/* the distance-map kernel the last rtr_probe_depth call launched (of its last slice), recorded like a gather's */
+struct rtr_debug_probe_depth {
+    int trav; /* k_probe_depth<trav>: the RT_TRAV_* template value; -1: no such call yet */
+    int lg;   /* log2 of the lanes that share a texel */
+};
 struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     double L[3];
     uint32_t rng_exit;
@@ -79,6 +84,7 @@ int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_o
 int rtr_debug_last_gather(rtr_context* ctx, rtr_debug_gather* out, size_t size_of_out);
 int rtr_debug_last_probe(rtr_context* ctx, rtr_debug_probe* out, size_t size_of_out);
 int rtr_debug_last_capture(rtr_context* ctx, rtr_debug_capture* out, size_t size_of_out);
+int rtr_debug_last_probe_depth(rtr_context* ctx, rtr_debug_probe_depth* out, size_t size_of_out);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);
 void rtr_debug_set_error(rtr_context* ctx, const char* msg); /* rtr_last_error() of a failing rtr_test_* call */
 /* Synthetic state into an accumulator, so that the product's own k_accum_errors / _plan / _commit / _resolve(_scatter) run on

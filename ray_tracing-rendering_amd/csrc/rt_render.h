@@ -307,6 +307,167 @@ RT_HD rtr_gather_out probe_lookup_one(const rtr_probe_grid& g, const rtr_probe_s
     return o;
 }
 
+/* ---- probe distance maps (include/rtr_hip.h: rtr_probe_depth*, rtr_octa_*, rtr_probe_lookup_visible*) ----
+ * The arithmetic of that contract, written once for host (rtr_probe_depth_ray, rtr_octa_*, rtr_probe_lookup_visible_one,
+ * the entries' checks) and device (k_probe_depth, k_probe_lookup_visible): the same rules as the gathers' above. */
+#define RTR_DEPTH_MAX_MAP 64
+struct DepthK {
+    const rtr_probe_point* pts; /* the probes of the whole call */
+    rtr_probe_depth_texel* out; /* out[0] is the record of texel `first` of the call */
+    long long first;            /* texels are numbered through the call: probe * T^2 + e */
+    long long k0, n;            /* this launch serves the records [k0, n) of `out` */
+    int T, TT;                  /* map size, T^2 */
+    int samples, lg;            /* N; log2 of the group size, the gathers' gather_lg */
+    uint32_t seed, point_base;
+    int jitter;
+    double time, t_min, t_max;
+};
+/* why `p` is no valid parameter block, or nullptr */
+inline const char* probe_depth_params_why(const rtr_probe_depth_params* p) {
+    if (!p) return "null probe depth params";
+    if (p->map_size < 1 || p->map_size > RTR_DEPTH_MAX_MAP) return "map_size outside 1 .. 64";
+    if (p->samples < 1 || p->samples > (1 << 20)) return "samples outside 1 .. 2^20";
+    if (p->jitter != 0 && p->jitter != 1) return "jitter must be 0 or 1";
+    if (p->pad != 0) return "pad must be 0";
+    if (!__builtin_isfinite(p->time) || !__builtin_isfinite(p->t_min)) return "time or t_min not finite";
+    if (!(__builtin_isfinite(p->t_max) && p->t_max > p->t_min)) return "t_max must be finite and > t_min";
+    return nullptr;
+}
+inline const char* probe_visible_params_why(const rtr_probe_visible_params* p) {
+    if (!p) return "null visible params";
+    if (p->map_size < 1 || p->map_size > RTR_DEPTH_MAX_MAP) return "map_size outside 1 .. 64";
+    if (p->pad != 0 || p->reserved[0] != 0 || p->reserved[1] != 0) return "pad and reserved must be 0";
+    if (!(__builtin_isfinite(p->normal_bias) && p->normal_bias >= 0)) return "normal_bias must be finite and >= 0";
+    return nullptr;
+}
+RT_HD double octa_sg(double t) { return t >= 0 ? 1.0 : -1.0; }
+/* DECODE: the unit direction of the point (u, v) of the octahedral square */
+RT_HD void octa_decode(double u, double v, double& dx, double& dy, double& dz) {
+    const double z = (1.0 - __builtin_fabs(u)) - __builtin_fabs(v);
+    double x = u, y = v;
+    if (!(z >= 0)) x = (1.0 - __builtin_fabs(v)) * octa_sg(u), y = (1.0 - __builtin_fabs(u)) * octa_sg(v);
+    const double r = 1 / __builtin_sqrt(x * x + y * y + z * z);
+    dx = r * x, dy = r * y, dz = r * z;
+}
+/* ENCODE: the point of the square of a direction that need not be unit */
+RT_HD void octa_encode(double x, double y, double z, double& ox, double& oy) {
+    const double s = (__builtin_fabs(x) + __builtin_fabs(y)) + __builtin_fabs(z);
+    ox = x / s, oy = y / s;
+    if (z < 0) {
+        const double fx = (1.0 - __builtin_fabs(oy)) * octa_sg(ox), fy = (1.0 - __builtin_fabs(ox)) * octa_sg(oy);
+        ox = fx, oy = fy;
+    }
+}
+/* direction of the ray through texel (a, b) of a T x T octahedral map whose generator is `rng`; rng is left behind the
+ * jitter's draws (none without jitter), which are the captures' */
+RT_HD void depth_direction(int T, int a, int b, int jitter, uint32_t& rng, double& dx, double& dy, double& dz) {
+    double ju = 0.5, jv = 0.5;
+    if (jitter) {
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        ju = rng * 2.3283064365386962890625e-10;
+        rng ^= rng << 13, rng ^= rng >> 17, rng ^= rng << 5;
+        jv = rng * 2.3283064365386962890625e-10;
+    }
+    const double u = (2.0 * (a + ju)) / T - 1.0;
+    const double v = (2.0 * (b + jv)) / T - 1.0;
+    octa_decode(u, v, dx, dy, dz);
+}
+/* one axis of FETCH: no clamp, i0 in [-1, T - 1] */
+RT_HD void octa_axis(double c, int T, int& i0, double& w0, double& w1) {
+    const double g = ((c + 1.0) * T) * 0.5 - 0.5;
+    i0 = g < 0 ? -1 : (int)g;
+    const double t = g - (double)i0;
+    w0 = 1.0 - t, w1 = t;
+}
+/* FETCH: the bilinear mean and mean of squares of one probe's T x T map along d, folded over the map's edge; false: a
+ * used tap is not valid.  A tap is read only if its weight is > 0 (a NaN weight reads nothing). */
+RT_HD bool octa_fetch(int T, const rtr_probe_depth_texel* __restrict__ map, double dx, double dy, double dz, double& m1, double& m2) {
+    double ox, oy;
+    octa_encode(dx, dy, dz, ox, oy);
+    int i0[2];
+    double w[2][2];
+    octa_axis(ox, T, i0[0], w[0][0], w[0][1]);
+    octa_axis(oy, T, i0[1], w[1][0], w[1][1]);
+    m1 = 0.0, m2 = 0.0;
+    bool ok = true;
+    for (int db = 0; db < 2; ++db)
+        for (int da = 0; da < 2; ++da) {
+            const double wc = w[0][da] * w[1][db];
+            if (!(wc > 0)) continue;
+            int ia = i0[0] + da, ib = i0[1] + db;
+            if (ia < 0) ia = 0, ib = T - 1 - ib;
+            else if (ia > T - 1) ia = T - 1, ib = T - 1 - ib;
+            if (ib < 0) ib = 0, ia = T - 1 - ia;
+            else if (ib > T - 1) ib = T - 1, ia = T - 1 - ia;
+            const rtr_probe_depth_texel& t = map[ib * T + ia];
+            ok = ok && t.valid != 0;
+            m1 = m1 + wc * t.mean, m2 = m2 + wc * t.mean2;
+        }
+    return ok;
+}
+/* rtr_probe_lookup_visible of one query that is not bad; probes, depth: the grid's records and their maps */
+RT_HD rtr_gather_out probe_lookup_visible_one(const rtr_probe_grid& g, const rtr_probe_sh* __restrict__ probes,
+                                              const rtr_probe_depth_texel* __restrict__ depth, int T, double normal_bias,
+                                              const rtr_gather_point& q, double nlen) {
+    int i0[3];
+    double w[3][2];
+    for (int a = 0; a < 3; ++a) probe_axis(q.p[a], g.origin[a], g.spacing[a], g.dims[a], i0[a], w[a][0], w[a][1]);
+    const double rn = 1 / nlen;
+    const double wn[3] = {rn * q.n[0], rn * q.n[1], rn * q.n[2]};
+    const double pb[3] = {q.p[0] + normal_bias * wn[0], q.p[1] + normal_bias * wn[1], q.p[2] + normal_bias * wn[2]};
+    double acc[9][3];
+    for (int i = 0; i < 9; ++i) acc[i][0] = acc[i][1] = acc[i][2] = 0.0;
+    double wsum = 0.0;
+    int used = 0;
+    for (int dz = 0; dz < 2; ++dz)
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ix = i0[0] + dx < g.dims[0] - 1 ? i0[0] + dx : g.dims[0] - 1;
+                const int iy = i0[1] + dy < g.dims[1] - 1 ? i0[1] + dy : g.dims[1] - 1;
+                const int iz = i0[2] + dz < g.dims[2] - 1 ? i0[2] + dz : g.dims[2] - 1;
+                const double tri = (w[0][dx] * w[1][dy]) * w[2][dz];
+                const long long pi = ix + (long long)g.dims[0] * (iy + (long long)g.dims[1] * iz);
+                const rtr_probe_sh& pr = probes[pi];
+                if (!(tri > 0 && pr.valid != 0)) continue;
+                const double P[3] = {g.origin[0] + (double)ix * g.spacing[0], g.origin[1] + (double)iy * g.spacing[1],
+                                     g.origin[2] + (double)iz * g.spacing[2]};
+                const double e[3] = {P[0] - q.p[0], P[1] - q.p[1], P[2] - q.p[2]};
+                const double el2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
+                const double cosn = el2 > 0 ? (e[0] * wn[0] + e[1] * wn[1] + e[2] * wn[2]) / __builtin_sqrt(el2) : 0.0;
+                const double h = (cosn + 1.0) * 0.5;
+                const double wb = h * h + 0.2;
+                const double dv[3] = {pb[0] - P[0], pb[1] - P[1], pb[2] - P[2]};
+                const double r2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+                double c = 1.0;
+                if (r2 > 0) {
+                    const double r = __builtin_sqrt(r2);
+                    double m1, m2;
+                    const bool ok = octa_fetch(T, depth + pi * T * T, dv[0], dv[1], dv[2], m1, m2);
+                    if (ok && !(r <= m1)) {
+                        const double var = __builtin_fabs(m2 - m1 * m1), dd = r - m1;
+                        const double den = var + dd * dd;
+                        c = den > 0 ? var / den : 0.0;
+                        c = (c * c) * c;
+                    }
+                }
+                double wv = wb * c;
+                if (!(wv >= 0x1p-20)) wv = 0x1p-20;
+                const double wgt = tri * wv;
+                wsum = wsum + wgt, ++used;
+                for (int i = 0; i < 9; ++i)
+                    for (int ch = 0; ch < 3; ++ch) acc[i][ch] = acc[i][ch] + wgt * pr.c[i][ch];
+            }
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    if (used == 0) return o;
+    const double rw = 1.0 / wsum;
+    for (int i = 0; i < 9; ++i)
+        for (int ch = 0; ch < 3; ++ch) acc[i][ch] = rw * acc[i][ch];
+    sh_irradiance(acc, q.n, nlen, o.v);
+    o.count = used, o.valid = 1;
+    return o;
+}
+
 /* ---- environment captures (include/rtr_hip.h: rtr_capture_*, rtr_cube_*) ----
  * The arithmetic of that contract, written once for host (rtr_capture_ray, rtr_cube_lookup_one, the entries' checks) and
  * device (k_capture_li, k_cube_lookup): the same rules as the gathers' above. */

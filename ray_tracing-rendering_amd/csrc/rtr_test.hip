@@ -284,6 +284,12 @@ int rtr_test_last_capture(rtr_context* c, rtr_capture_record* out, size_t size) 
     return rtr_debug_last_capture(c, reinterpret_cast<rtr_debug_capture*>(out), sizeof(rtr_debug_capture));
 }
 
+int rtr_test_last_probe_depth(rtr_context* c, rtr_probe_depth_record* out, size_t size) {
+    static_assert(sizeof(rtr_probe_depth_record) == sizeof(rtr_debug_probe_depth), "one layout");
+    if (size != sizeof(rtr_probe_depth_record)) return RTR_ERR_INVALID;
+    return rtr_debug_last_probe_depth(c, reinterpret_cast<rtr_debug_probe_depth*>(out), sizeof(rtr_debug_probe_depth));
+}
+
 int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t flags, rtr_scene_plan* out, int32_t* ref_flags,
                         int64_t cap, rtr_finish_record* finish, int64_t finish_cap) {
     static_assert(sizeof(rtr_scene_plan) == sizeof(rtr_debug_plan), "one layout");

@@ -42,6 +42,10 @@
  *                                   probe: at the lower corner) goes through Renderer::light_probes with N (default 64) sphere
  *                                   samples each under the integrator and --seed; one line per probe, x fastest: `valid count`
  *                                   and the 27 coefficients c[i][channel] as %.17g.  Not with --pick, --ao, --adaptive, --turntable
+ *           [--probe-depth T [--probe-depth-samples N] --probe-depth-out FILE]   with --probes: the probes' octahedral distance
+ *                                   maps of T x T texels (1..64) go through Renderer::probe_depth with N (default 8) rays per
+ *                                   texel under --seed, misses at 1.5 x the length of the grid's spacing; FILE receives the raw
+ *                                   rtr_probe_depth_texel records, [probe][row][column].  What is printed does not change
  *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
  *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
  *                                   rtr_display_host through Renderer::display; with --turntable rtr_display_device on
@@ -190,6 +194,9 @@ int main(int argc, char** argv) {
     int probe_dims[3] = {0, 0, 0}, probe_samples = 64;
     double probe_box[6];
     bool probes = false, probe_boxed = false, probe_sampled = false;
+    int probe_depth = 0, probe_depth_samples = 8;
+    bool probe_depth_set = false, probe_depth_sampled = false;
+    std::string probe_depth_out;
     double capture_at[3] = {0, 0, 0};
     int capture_face = 32, capture_spp = 16, latlong[2] = {0, 0}, capture_levels = 0;
     bool capture = false, capture_face_set = false, capture_spp_set = false, latlong_set = false;
@@ -346,6 +353,19 @@ int main(int argc, char** argv) {
             }
             probe_samples = (int)v, probe_sampled = true;
         }
+        else if ((!std::strcmp(argv[k], "--probe-depth") || !std::strcmp(argv[k], "--probe-depth-samples")) && k + 1 < argc) {
+            const bool size = !std::strcmp(argv[k], "--probe-depth");
+            const long most = size ? 64 : (1 << 20);
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (end == argv[k] || *end != '\0' || v < 1 || v > most) {
+                std::cerr << argv[k - 1] << " takes an integer in 1.." << most << ", not " << argv[k] << "\n";
+                return 2;
+            }
+            if (size) probe_depth = (int)v, probe_depth_set = true;
+            else probe_depth_samples = (int)v, probe_depth_sampled = true;
+        }
+        else if (!std::strcmp(argv[k], "--probe-depth-out") && k + 1 < argc) probe_depth_out = argv[++k];
         else if (!std::strcmp(argv[k], "--spp-min") && k + 1 < argc) {
             spp_min = std::atoi(argv[++k]);
             if (spp_min < 1) {
@@ -411,6 +431,14 @@ int main(int argc, char** argv) {
     }
     if (probes && !probe_boxed) {
         std::cerr << "--probes needs --probe-box\n";
+        return 2;
+    }
+    if ((probe_depth_set || probe_depth_sampled || !probe_depth_out.empty()) && !probes) {
+        std::cerr << "--probe-depth, --probe-depth-samples and --probe-depth-out go with --probes\n";
+        return 2;
+    }
+    if (probe_depth_set != !probe_depth_out.empty() || (probe_depth_sampled && !probe_depth_set)) {
+        std::cerr << "--probe-depth T and --probe-depth-out FILE go together; --probe-depth-samples goes with them\n";
         return 2;
     }
     if (probes && (pick || ao_samples || adaptive || turntable_frames)) {
@@ -612,6 +640,23 @@ int main(int argc, char** argv) {
         if (sh.size() != points.size()) {
             std::cerr << "light probes failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
             return 1;
+        }
+        if (probe_depth_set) {
+            double sp[3];
+            for (int a = 0; a < 3; ++a)
+                sp[a] = probe_dims[a] > 1 ? (probe_box[3 + a] - probe_box[a]) / (double)(probe_dims[a] - 1) : 1.0;
+            const double reach = 1.5 * std::sqrt((sp[0] * sp[0] + sp[1] * sp[1]) + sp[2] * sp[2]);
+            const std::vector<rtr_probe_depth_texel> maps = renderer.probe_depth(points, probe_depth, reach, probe_depth_samples, seed);
+            if (maps.size() != points.size() * (size_t)probe_depth * probe_depth) {
+                std::cerr << "probe depth failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+                return 1;
+            }
+            std::FILE* f = std::fopen(probe_depth_out.c_str(), "wb");
+            const bool ok = f && std::fwrite(maps.data(), sizeof(rtr_probe_depth_texel), maps.size(), f) == maps.size();
+            if (!(f && std::fclose(f) == 0 && ok)) {
+                std::cerr << "cannot write " << probe_depth_out << "\n";
+                return 1;
+            }
         }
         for (const rtr_probe_sh& r : sh) {
             std::printf("%d %d", r.valid, r.count);

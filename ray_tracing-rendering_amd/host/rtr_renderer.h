@@ -470,6 +470,61 @@ class Renderer {
         return out;
     }
 
+    /* Probe distance maps (include/rtr_hip.h: rtr_probe_depth, rtr_probe_lookup_visible), on the first context.
+     * probe_depth: for every point an octahedral map of map_size x map_size texels, each the mean and mean square of the
+     * distance to the nearest surface over `samples` jittered rays through it, misses counted at max_distance;
+     * map_size^2 records per point, [point][row][column].  probe_irradiance_visible: probe_irradiance with every corner
+     * weighed by what its probe's map says of the way to the query, tested normal_bias off the surface (needs no scene).
+     * An empty vector and last_status() / last_error() on failure. */
+    std::vector<rtr_probe_depth_texel> probe_depth(const std::vector<point3>& points, int map_size, double max_distance,
+                                                   int samples = 8, unsigned seed = 0) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if (map_size < 1 || map_size > 64) m_error = "map_size outside 1 .. 64", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_probe_depth_texel> out;
+        if (m_status == RTR_OK) {
+            out.resize(points.size() * (size_t)map_size * map_size);
+            std::vector<rtr_probe_point> pts(points.size());
+            for (size_t k = 0; k < points.size(); ++k)
+                for (int a = 0; a < 3; ++a) pts[k].p[a] = points[k][a];
+            rtr_probe_depth_params dp;
+            rtr_probe_depth_defaults(&dp);
+            dp.map_size = map_size, dp.samples = samples, dp.seed = seed, dp.t_max = max_distance;
+            if ((m_status = rtr_probe_depth(m_ctx[0], &dp, pts.data(), out.data(), (int64_t)pts.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+    std::vector<rtr_gather_out> probe_irradiance_visible(const rtr_probe_grid& grid, const std::vector<rtr_probe_sh>& probes,
+                                                         const std::vector<rtr_probe_depth_texel>& depth, int map_size,
+                                                         double normal_bias, const std::vector<point3>& points,
+                                                         const std::vector<vec3>& normals) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if (points.size() != normals.size()) m_error = "one normal per point", m_status = RTR_ERR_INVALID;
+        else if (grid.dims[0] < 1 || grid.dims[1] < 1 || grid.dims[2] < 1 ||
+                 (long long)grid.dims[0] * grid.dims[1] * grid.dims[2] != (long long)probes.size())
+            m_error = "one probe record per grid point", m_status = RTR_ERR_INVALID;
+        else if (map_size < 1 || map_size > 64 || depth.size() != probes.size() * (size_t)map_size * map_size)
+            m_error = "map_size^2 depth records per grid point, 1 <= map_size <= 64", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_gather_out> out(points.size());
+        if (m_status == RTR_OK) {
+            std::vector<rtr_gather_point> q(points.size());
+            for (size_t k = 0; k < points.size(); ++k)
+                for (int a = 0; a < 3; ++a) q[k].p[a] = points[k][a], q[k].n[a] = normals[k][a];
+            rtr_probe_visible_params vp{};
+            vp.map_size = map_size, vp.normal_bias = normal_bias;
+            if ((m_status = rtr_probe_lookup_visible(m_ctx[0], &grid, probes.data(), depth.data(), &vp, q.data(), out.data(),
+                                                     (int64_t)q.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+
     /* Environment captures (include/rtr_hip.h: rtr_capture_cube), on the first context and the scene uploaded there.
      * capture_cube: for every centre six faces of face_size x face_size texels, each the mean of Integrator::Li over
      * `samples` jittered rays through it under the integrator set on this renderer; 6 * face_size^2 records per centre,

@@ -38,11 +38,13 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_cube_lookup", "rtr_cube_lookup_device", "rtr_cube_lookup_one", "rtr_latlong_direction",
            "rtr_cube_to_latlong", "rtr_write_rgbe", "rtr_cube_filter_defaults", "rtr_cube_filter", "rtr_cube_filter_device",
            "rtr_cube_filter_one", "rtr_cube_chain_plan", "rtr_cube_chain_lookup", "rtr_cube_chain_lookup_device",
-           "rtr_cube_chain_lookup_one")
+           "rtr_cube_chain_lookup_one", "rtr_probe_depth_defaults", "rtr_probe_depth", "rtr_probe_depth_device",
+           "rtr_probe_depth_ray", "rtr_octa_encode", "rtr_octa_decode", "rtr_probe_lookup_visible",
+           "rtr_probe_lookup_visible_device", "rtr_probe_lookup_visible_one")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
-                "rtr_test_last_gather", "rtr_test_last_probe", "rtr_test_last_capture",
+                "rtr_test_last_gather", "rtr_test_last_probe", "rtr_test_last_capture", "rtr_test_last_probe_depth",
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
                 "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
@@ -79,6 +81,11 @@ class ProbeRecordC(C.Structure):
 class CaptureRecordC(C.Structure):
     """rtr_capture_record of include/rtr_hip_test.h"""
     _fields_ = [(name, C.c_int32) for name in ("integ", "trav", "lg")]
+
+
+class ProbeDepthRecordC(C.Structure):
+    """rtr_probe_depth_record of include/rtr_hip_test.h"""
+    _fields_ = [(name, C.c_int32) for name in ("trav", "lg")]
 
 
 class ScenePlanC(C.Structure):
@@ -209,6 +216,19 @@ def lib():
     L.rtr_probe_lookup.argtypes = [vp, P(A.ProbeGridC), vp, vp, vp, C.c_int64]
     L.rtr_probe_lookup_device.argtypes = [vp, P(A.ProbeGridC), vp, vp, vp, C.c_int64, C.c_int]
     L.rtr_probe_lookup_one.argtypes = [P(A.ProbeGridC), vp, vp, vp]
+    L.rtr_probe_depth_defaults.argtypes = [P(A.ProbeDepthParamsC)]
+    L.rtr_probe_depth_defaults.restype = None
+    L.rtr_probe_depth.argtypes = [vp, P(A.ProbeDepthParamsC), vp, vp, C.c_int64]
+    L.rtr_probe_depth_device.argtypes = [vp, P(A.ProbeDepthParamsC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_probe_depth_ray.argtypes = [P(A.ProbeDepthParamsC), vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rtr_octa_encode.argtypes = [vp, vp]
+    L.rtr_octa_encode.restype = None
+    L.rtr_octa_decode.argtypes = [vp, vp]
+    L.rtr_octa_decode.restype = None
+    L.rtr_probe_lookup_visible.argtypes = [vp, P(A.ProbeGridC), vp, vp, P(A.ProbeVisibleParamsC), vp, vp, C.c_int64]
+    L.rtr_probe_lookup_visible_device.argtypes = [vp, P(A.ProbeGridC), vp, vp, P(A.ProbeVisibleParamsC), vp, vp, C.c_int64,
+                                                  C.c_int]
+    L.rtr_probe_lookup_visible_one.argtypes = [P(A.ProbeGridC), vp, vp, P(A.ProbeVisibleParamsC), vp, vp]
     L.rtr_capture_defaults.argtypes = [P(A.CaptureParamsC)]
     L.rtr_capture_defaults.restype = None
     L.rtr_capture_cube.argtypes = [vp, P(A.RenderParamsC), P(A.CaptureParamsC), vp, vp, C.c_int64]
@@ -265,6 +285,7 @@ def test_lib():
     T.rtr_test_last_gather.argtypes = [vp, C.POINTER(GatherRecordC), C.c_size_t]
     T.rtr_test_last_probe.argtypes = [vp, C.POINTER(ProbeRecordC), C.c_size_t]
     T.rtr_test_last_capture.argtypes = [vp, C.POINTER(CaptureRecordC), C.c_size_t]
+    T.rtr_test_last_probe_depth.argtypes = [vp, C.POINTER(ProbeDepthRecordC), C.c_size_t]
     T.rtr_test_temporal_planes.argtypes = [vp] + [C.c_int32] * 6 + [C.POINTER(A.CameraC), C.POINTER(A.CameraC), C.c_int,
                                                                     C.POINTER(A.TemporalParamsC)] + [vp] * 8
     T.rtr_test_scene_plan.argtypes = [C.POINTER(A.SceneDescC), C.c_int32, C.c_int32, C.POINTER(ScenePlanC), vp, C.c_int64,
@@ -568,6 +589,93 @@ def probe_lookup_host(grid, probes, points, normals=None):
         rc = L.rtr_probe_lookup_one(C.byref(grid), probes.ctypes.data, q.ctypes.data + 48 * k, out.ctypes.data + 32 * k)
         if rc != 0:
             raise RtrError(rc, "rtr_probe_lookup_one: bad grid, or bad query at index %d" % k)
+    return out
+
+
+def probe_depth_defaults(**overrides):
+    """rtr_probe_depth_params with the library's defaults (rtr_probe_depth_defaults: map_size 16, samples 8, seed 0,
+    point_base 0, jitter 1, time 0, t_min 0.001), fields replaced by ``overrides``.  ``t_max`` has no default: a block
+    without it is rejected by every entry."""
+    return _defaults(A.ProbeDepthParamsC, "rtr_probe_depth_defaults",
+                     ("map_size", "samples", "seed", "point_base", "jitter", "time", "t_min", "t_max"), overrides)
+
+
+def probe_depth_rays(points, params=None, **overrides):
+    """rtr_probe_depth_ray for every sample of every texel of every probe (host only, no context): ``RAY_DTYPE``
+    [n, T, T, samples] (row b, then column a), the rays rtr_probe_depth casts."""
+    dp = params if params is not None else probe_depth_defaults(**overrides)
+    pts = probe_points(points)
+    T, N = int(dp.map_size), int(dp.samples)
+    if not (1 <= T <= A.PROBE_DEPTH_MAX_MAP and 1 <= N <= A.GATHER_MAX_SAMPLES):
+        raise RtrError(A.RTR_ERR_INVALID, "rtr_probe_depth_ray: map_size or samples out of range")
+    rays = np.zeros((len(pts), T, T, N), dtype=A.RAY_DTYPE)
+    ray_of, size, flat = lib().rtr_probe_depth_ray, A.RAY_DTYPE.itemsize, 0
+    for k in range(len(pts)):
+        for b in range(T):
+            for a in range(T):
+                for s in range(N):
+                    rc = ray_of(C.byref(dp), pts.ctypes.data + 24 * k, k, a, b, s, rays.ctypes.data + flat * size)
+                    if rc != 0:
+                        raise RtrError(rc, "rtr_probe_depth_ray: bad params or bad probe at index %d" % k)
+                    flat += 1
+    return rays
+
+
+def octa_encode(directions):
+    """rtr_octa_encode: the points [..., 2] of the octahedral square of the directions [..., 3] (need not be unit)."""
+    d = np.ascontiguousarray(directions, dtype=np.float64)
+    flat = d.reshape(-1, 3)
+    uv = np.zeros((len(flat), 2))
+    L = lib()
+    for k in range(len(flat)):
+        L.rtr_octa_encode(flat.ctypes.data + 24 * k, uv.ctypes.data + 16 * k)
+    return uv.reshape(d.shape[:-1] + (2,))
+
+
+def octa_decode(uv):
+    """rtr_octa_decode: the unit directions [..., 3] of the points [..., 2] of the octahedral square."""
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    flat = uv.reshape(-1, 2)
+    d = np.zeros((len(flat), 3))
+    L = lib()
+    for k in range(len(flat)):
+        L.rtr_octa_decode(flat.ctypes.data + 16 * k, d.ctypes.data + 24 * k)
+    return d.reshape(uv.shape[:-1] + (3,))
+
+
+def probe_visible_params(map_size, normal_bias=0.0):
+    """An rtr_probe_visible_params"""
+    vp = A.ProbeVisibleParamsC()
+    vp.map_size, vp.normal_bias = int(map_size), float(normal_bias)
+    return vp
+
+
+def _visible_inputs(grid, probes, depth, map_size):
+    """(SH records, depth records [probes * T * T], T) of a visible lookup; ``depth`` may be [probes, T, T]"""
+    probes = np.ascontiguousarray(probes, dtype=A.PROBE_SH_DTYPE)
+    n = grid.dims[0] * grid.dims[1] * grid.dims[2]
+    if len(probes) != n:
+        raise ValueError("probes must hold dims[0] * dims[1] * dims[2] records")
+    depth = np.ascontiguousarray(depth, dtype=A.PROBE_DEPTH_DTYPE)
+    T = int(map_size) if map_size is not None else (depth.shape[-1] if depth.ndim == 3 else int(round((depth.size / max(n, 1)) ** 0.5)))
+    if depth.size != n * T * T:
+        raise ValueError("depth must hold T * T records per probe")
+    return probes, depth.reshape(-1), T
+
+
+def probe_lookup_visible_host(grid, probes, depth, points, normals=None, normal_bias=0.0, map_size=None, params=None):
+    """rtr_probe_lookup_visible_one for every query (host only, no context): a ``GATHER_OUT_DTYPE`` array.  Raises RtrError
+    for a bad grid, bad params or a bad query."""
+    L = lib()
+    probes, depth, T = _visible_inputs(grid, probes, depth, map_size if params is None else params.map_size)
+    vp = params if params is not None else probe_visible_params(T, normal_bias)
+    q = gather_points(points, normals)
+    out = np.zeros(len(q), dtype=A.GATHER_OUT_DTYPE)
+    for k in range(len(q)):
+        rc = L.rtr_probe_lookup_visible_one(C.byref(grid), probes.ctypes.data, depth.ctypes.data, C.byref(vp),
+                                            q.ctypes.data + 48 * k, out.ctypes.data + 32 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_probe_lookup_visible_one: bad grid or params, or bad query at index %d" % k)
     return out
 
 
@@ -1082,6 +1190,48 @@ class Context:
         self._chk(self._L.rtr_probe_lookup_device(self._h, C.byref(grid), C.c_void_p(probes_ptr),
                                                   *_into_tail(queries_ptr, out_ptr, n, blocking)))
 
+    # probe distance maps (include/rtr_hip.h: rtr_probe_depth*, rtr_probe_lookup_visible*)
+    def probe_depth(self, points, depth_params=None, out=None, **overrides):
+        """rtr_probe_depth: the ``PROBE_DEPTH_DTYPE`` records [n, T, T] (row, column) of the octahedral distance maps of
+        the probes ``points``; ``t_max`` must be given.  Blocking; raises RtrError (RTR_ERR_INVALID) naming the first bad
+        probe, with ``out`` untouched."""
+        dp = depth_params if depth_params is not None else probe_depth_defaults(**overrides)
+        pts = probe_points(points)
+        T = int(dp.map_size)
+        flat = _records_out(None if out is None else out.reshape(-1), len(pts) * T * T, A.PROBE_DEPTH_DTYPE)
+        self._chk(self._L.rtr_probe_depth(self._h, C.byref(dp), pts.ctypes.data, flat.ctypes.data, len(pts)))
+        return flat[:len(pts) * T * T].reshape(len(pts), T, T)
+
+    def probe_depth_into(self, points_ptr, out_ptr, n, depth_params=None, blocking=False, **overrides):
+        """rtr_probe_depth_device: n ``PROBE_POINT_DTYPE`` probes at device pointer ``points_ptr`` -> n * T * T
+        ``PROBE_DEPTH_DTYPE`` records at ``out_ptr``, on the context stream behind what is queued there."""
+        dp = depth_params if depth_params is not None else probe_depth_defaults(**overrides)
+        self._chk(self._L.rtr_probe_depth_device(self._h, C.byref(dp), *_into_tail(points_ptr, out_ptr, n, blocking)))
+
+    @staticmethod
+    def probe_depth_rays(points, params=None, **overrides):
+        """The rays rtr_probe_depth casts, ``RAY_DTYPE`` [n, T, T, samples], through rtr_probe_depth_ray
+        (``native.probe_depth_rays``)."""
+        return probe_depth_rays(points, params, **overrides)
+
+    def probe_lookup_visible(self, grid, probes, depth, points, normals=None, normal_bias=0.0, map_size=None, params=None,
+                             out=None):
+        """rtr_probe_lookup_visible: ``probe_lookup`` with every corner weighed by what its probe's distance map
+        (``depth``: ``PROBE_DEPTH_DTYPE`` [probes, T, T]) says of the way to the query.  Blocking; needs no scene."""
+        probes, depth, T = _visible_inputs(grid, probes, depth, map_size if params is None else params.map_size)
+        vp = params if params is not None else probe_visible_params(T, normal_bias)
+        q = gather_points(points, normals)
+        out = _records_out(out, len(q), A.GATHER_OUT_DTYPE)
+        self._chk(self._L.rtr_probe_lookup_visible(self._h, C.byref(grid), probes.ctypes.data, depth.ctypes.data, C.byref(vp),
+                                                   q.ctypes.data, out.ctypes.data, len(q)))
+        return out
+
+    def probe_lookup_visible_into(self, grid, probes_ptr, depth_ptr, params, queries_ptr, out_ptr, n, blocking=False):
+        """rtr_probe_lookup_visible_device: the same over device pointers, on the context stream behind what is queued
+        there; ``params`` is an rtr_probe_visible_params (``native.probe_visible_params``)."""
+        self._chk(self._L.rtr_probe_lookup_visible_device(self._h, C.byref(grid), C.c_void_p(probes_ptr), C.c_void_p(depth_ptr),
+                                                          C.byref(params), *_into_tail(queries_ptr, out_ptr, n, blocking)))
+
     # environment captures (include/rtr_hip.h: rtr_capture_*, rtr_cube_*)
     def capture_cube_records(self, params, points, capture_params=None, out=None, **overrides):
         """rtr_capture_cube: the ``GATHER_OUT_DTYPE`` records [n, 6, S, S] (face, row, column) of the cube maps about the
@@ -1271,6 +1421,15 @@ class Context:
         if r.trav < 0:
             return None
         return {name: int(getattr(r, name)) for name, _ in ProbeRecordC._fields_}
+
+    def last_probe_depth(self):
+        """The distance-map kernel the last probe_depth call launched (include/rtr_hip_test.h: rtr_probe_depth_record), as
+        a dict; None before any such call of this context launched one."""
+        r = ProbeDepthRecordC()
+        self._chk(test_lib().rtr_test_last_probe_depth(self._h, C.byref(r), C.sizeof(r)))
+        if r.trav < 0:
+            return None
+        return {name: int(getattr(r, name)) for name, _ in ProbeDepthRecordC._fields_}
 
     def last_capture(self):
         """The capture kernel the last capture_cube call launched (include/rtr_hip_test.h: rtr_capture_record), as a dict;

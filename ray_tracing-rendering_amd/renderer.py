@@ -383,6 +383,7 @@ class ProbeGrid:
             np.ascontiguousarray(coefficients, dtype=A.PROBE_SH_DTYPE)
         if len(self.coefficients) != n:
             raise ValueError("coefficients must hold %d records" % n)
+        self.depth = None  # ``bake(depth=T)``: PROBE_DEPTH_DTYPE [n, T, T]
         self._ctx = None
 
     @classmethod
@@ -403,19 +404,51 @@ class ProbeGrid:
         from . import native
         return native.probe_grid(self.origin, self.spacing, self.dims)
 
-    def bake(self, ctx, params, samples=64, seed=0, time=0.0):
-        """rtr_probe_radiance at every probe under ``params`` (an rtr_render_params) on the scene ``ctx`` holds."""
+    def bake(self, ctx, params, samples=64, seed=0, time=0.0, depth=None, depth_samples=8, max_distance=None, classify=None):
+        """rtr_probe_radiance at every probe under ``params`` (an rtr_render_params) on the scene ``ctx`` holds.
+        ``depth``: the size T of an octahedral distance map per probe (rtr_probe_depth with ``depth_samples`` rays per
+        texel, misses at ``max_distance``: by default 1.5 x the length of ``spacing``), kept in ``self.depth`` as
+        ``PROBE_DEPTH_DTYPE`` [n, T, T]; None bakes none.  ``classify``: with a map, ``self.classify`` afterwards (True: its
+        default fraction; a number: that fraction)."""
         self.coefficients = ctx.probe_radiance(params, self.positions(), samples=samples, seed=seed, time=time)
+        self.depth = None
+        if depth is not None:
+            t_max = float(max_distance) if max_distance is not None else 1.5 * float(np.sqrt((self.spacing * self.spacing).sum()))
+            self.depth = ctx.probe_depth(self.positions(), map_size=int(depth), samples=int(depth_samples), seed=seed, time=time,
+                                         t_max=t_max)
+            if classify is not None and classify is not False:
+                self.classify() if classify is True else self.classify(float(classify))
         self._ctx = ctx
         return self
 
-    def irradiance(self, points, normals, ctx=None):
+    def classify(self, back_fraction=0.25):
+        """Sets ``valid = 0`` on every probe whose distance map saw the inside of surfaces on more than ``back_fraction`` of
+        its hits (sum(back) > back_fraction * sum(hits)): a probe inside geometry, which no lookup should use.  Returns the
+        bool mask [n] of the probes it invalidated."""
+        if self.depth is None:
+            raise ValueError("classify needs distance maps: bake with depth=T first")
+        back = self.depth["back"].reshape(len(self.depth), -1).sum(axis=1, dtype=np.int64)
+        hits = self.depth["hits"].reshape(len(self.depth), -1).sum(axis=1, dtype=np.int64)
+        inside = back > back_fraction * hits
+        self.coefficients["valid"][inside] = 0
+        return inside
+
+    def irradiance(self, points, normals, ctx=None, visible=None, normal_bias=None):
         """rtr_probe_lookup: [n, 3] irradiance at the queries; rows whose eight corners are all invalid are zero.  ``ctx``:
-        the context that runs it (default: the one that baked)."""
+        the context that runs it (default: the one that baked).  ``visible`` (default: distance maps were baked):
+        rtr_probe_lookup_visible, every corner weighed by its probe's distance map, tested ``normal_bias`` off the surface
+        (default 0.25 x the smallest spacing)."""
         ctx = ctx if ctx is not None else self._ctx
         if ctx is None:
             raise ValueError("irradiance needs a context: bake first or pass ctx")
-        return ctx.probe_lookup(self.grid(), self.coefficients, points, normals)["v"]
+        if visible is None:
+            visible = self.depth is not None
+        if not visible:
+            return ctx.probe_lookup(self.grid(), self.coefficients, points, normals)["v"]
+        if self.depth is None:
+            raise ValueError("a visible lookup needs distance maps: bake with depth=T first")
+        bias = float(normal_bias) if normal_bias is not None else 0.25 * float(self.spacing.min())
+        return ctx.probe_lookup_visible(self.grid(), self.coefficients, self.depth, points, normals, normal_bias=bias)["v"]
 
 
 class Cubemap:
