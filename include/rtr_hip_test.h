@@ -159,8 +159,19 @@ typedef struct rtr_pair_record {
     double a_t, s_a_t;                                  /* out: t of A's hit (a_tmax without one), pair / single */
     int32_t a_ref, a_inst, b_hit;                       /* out, pair cast: A's reference and instance (-1: none), B hit */
     int32_t s_a_ref, s_a_inst, s_b_hit;                 /* out, single casts */
-} rtr_pair_record; /* 152 bytes */
+    int32_t recasts, pad;                               /* out: casts of the lane's wave that failed a vote of the pair
+                                                           path and were cast again through the single casts */
+} rtr_pair_record; /* 160 bytes */
 int rtr_test_pair_cast(rtr_context* ctx, rtr_pair_record* recs, int64_t n);
+/* The same with the choice between the product's two texts of the pair cast: recast != 0 (what rtr_test_pair_cast runs):
+ * the lean material set's kernels' -- the pair path alone, and both rays again through the single casts where a vote
+ * fails --; recast == 0: the per-frame fallback of every other pair-cast kernel (`recasts` stays 0). */
+int rtr_test_pair_cast_text(rtr_context* ctx, rtr_pair_record* recs, int64_t n, int32_t recast);
+/* The resident shadow request of the job-queue kernel (k_mega_queue) over `casts` >= 1 pair casts of every lane, with that
+ * kernel's own steps around trace_pair: ray B of the record is parked as the request of the first cast and is dead (t_max
+ * 0, direction and origin left where they are) in every later one; ray A is cast every time.  The pair-cast columns are
+ * those of the first cast, `recasts` counts over all of them.  Errors as rtr_test_pair_cast. */
+int rtr_test_pair_resident(rtr_context* ctx, rtr_pair_record* recs, int64_t n, int32_t casts);
 
 /* Host builds of the job queue's own device functions (csrc/rt_render.h: queue_block, queue_pack / queue_unpack), which
  * k_mega_queue -- the persistent-grid twin of the pair-cast kernels -- decodes block ids and keeps its per-lane job with.

@@ -35,9 +35,9 @@ typedef double Real;
  * the region that was current, then makes `id` current.  Counters live in LDS per wave and are added to
  * RenderK::stats[RT_PROF_BASE ...] when the workgroup ends.  The markers cost about a tenth of the wave's time
  * themselves: read the table as proportions.  In product builds RT_REGION() expands to nothing. */
-#define RT_STATS_WORDS 80 /* u64 words of RenderK::stats: 8 of the product + 2 x 36 region words */
+#define RT_STATS_WORDS 82 /* u64 words of RenderK::stats: 8 of the product + 2 x 37 region words */
 #define RT_PROF_BASE 8
-#define RT_PROF_REGIONS 36
+#define RT_PROF_REGIONS 37
 enum { RG_OTHER = 0, RG_SETUP = 1, RG_RECTS = 2, RG_SPHERES = 3, RG_GENERIC = 4, RG_TREE = 5, RG_LEAVES = 6, RG_FINISH = 7,
        RG_SH_SETUP = 8, RG_SH_RECTS = 9, RG_SH_SPHERES = 10, RG_SH_GENERIC = 11, RG_SH_TREE = 12, RG_SH_LEAVES = 13,
        RG_MEDIA = 14, RG_MATPREP = 15, RG_SHADE_A = 16, RG_SHADE_B = 17, RG_MISS = 18, RG_REGEN = 19, RG_SHADE_RR = 20,
@@ -47,7 +47,8 @@ enum { RG_OTHER = 0, RG_SETUP = 1, RG_RECTS = 2, RG_SPHERES = 3, RG_GENERIC = 4,
        RG_CAMDIV = 33,   /* camera_sample: the two divisions by the image size */
        RG_LANE_DIV = 34,  /* shading: 1 / x of a lane's own divisor (rcp_lane and the reciprocal of sqrt_rcp_lane) */
        RG_LANE_SQRT = 35, /* shading: square roots of a lane's own number (sqrt_lane; with its vote where one covers both) */
-       RG_N = 36 };
+       RG_PAIR_RECAST = 36, /* pair cast: a vote failed, both rays again through the single casts (pair_recast) */
+       RG_N = 37 };
 #ifdef RTR_REGION_PROFILE
 __shared__ unsigned long long rt_prof_lds[4 * 2 * RT_PROF_REGIONS + 4 * 2]; /* [wave][cycles | visits][region], then [wave][last, current] */
 RT_DEV void rt_region(int id) {
@@ -1754,8 +1755,10 @@ __device__ __forceinline__ bool trace_fast(const DScene& sc, const FSub sub, V3 
  * every reference with the arithmetic of trace_fast<false> / trace_fast<true> and the same `t == t_max` rule, so
  * hit_ref, hit_inst and t of A and "occluded" of B are those of the two single casts bit for bit (B tests on after its
  * first hit, which changes nothing but its t).  A ray that a lane does not cast arrives as the dummy (0, 0, 0) + t (1, 1, 1)
- * with t_max = 0: no record accepts it and it keeps the shared-division checks (wave-level votes) true.  A frame where
- * either ray needs the plain divisions (RayDiv::fast, wave-uniform) runs the two single-ray scans of trace_fast. */
+ * with t_max = 0: no record accepts it and it keeps the shared-division checks (wave-level votes) true.  Where either
+ * ray needs the plain divisions (RayDiv::fast, wave-uniform), the kernels of the lean material set cast both rays again
+ * through the single casts (trace_pair_recast, pair_recast); the others run the two single-ray scans of trace_fast for
+ * that frame (trace_pair_frames). */
 /* the rectangle test of run_rect_test_x for two rays: both t first (interleaved), A's in-plane coordinates under the full
  * mask, then A's acceptance block and B's with its wave-level exit, EXEC saved once and put back after each block */
 template <int TYPE>
@@ -1834,7 +1837,10 @@ RT_DEV void pair_rects(const RT_CONST_AS double* p, int cnt, int ref, const Pair
     }
     if (k < cnt) pair_rect<TYPE>(p[0], p[1], p[2], p[3], p[4], ref + k, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
 }
-/* the runs of one instance (scan_runs) for both rays: every record is fetched once */
+/* the runs of one instance (scan_runs) for both rays: every record is fetched once.  SPHERES = false: the instance holds
+ * no sphere (RT_INST_SPHERES clear, wave-uniform), and the copy carries no sphere loop, whose selects would otherwise
+ * hand the hit state back through a second set of registers at every run */
+template <bool SPHERES = true>
 RT_DEV void pair_runs(const DScene& sc, const FInst& I, const PairRay& A, Real time, Real& tmaxA, int& hitA, const PairRay& B,
                       Real& tmaxB, int& hitB) {
     const RT_CONST_AS double* p = as_const(sc.fscan) + I.scan_first;
@@ -1863,7 +1869,7 @@ RT_DEV void pair_runs(const DScene& sc, const FInst& I, const PairRay& A, Real t
                 pair_rect<RTR_NODE_YZ_RECT>(y0, y1, z0, z1, x0, r + 5, A.o, A.d, A.q, tmaxA, hitA, B.o, B.d, B.q, tmaxB, hitB);
             }
             ref += 5 * cnt; /* six references per box */
-        } else { /* RTR_NODE_SPHERE (upload leaves moving spheres out of pair_cast scenes) */
+        } else if (SPHERES) { /* RTR_NODE_SPHERE (upload leaves moving spheres out of pair_cast scenes) */
             for (int k = 0; k < cnt; ++k, p += 4) {
                 const V3 c = mk(p[0], p[1], p[2]);
                 const Real r = p[3];
@@ -1936,9 +1942,12 @@ RT_HD PairFrame pair_frame(int shape, const double* f0, const double* f1, V3 ao,
  * (RT_INST_KEEP_Y: the same operand); x and z are made per frame (carrying them for the frames without a rotate_y put
  * ten VGPRs of the lean kernel back into scratch).  RayDiv::fast of a ray in a frame is origin_ok && __all(every lane's
  * verdicts), and __all(p) && __all(q) == __all(p & q): the per-lane verdicts are combined first and voted on once per
- * frame for both rays, and only a frame that fails that vote votes per ray to choose the single-ray scans. */
-__device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
-                                           V3 bo, V3 bd, Real& b_tmax, int& b_ref, const Stack st) {
+ * frame for both rays, and only a frame that fails that vote votes per ray to choose the single-ray scans.
+ * Always returns true: the cast is complete.  This is the pair cast of every pair-cast kernel outside the lean material
+ * set in the product build (pair_recasts(), rt_kernels.h) -- live code, not a measurement aid; -DRTR_PAIR_FRAME_FALLBACK
+ * gives it to the lean kernels as well. */
+__device__ __forceinline__ bool trace_pair_frames(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
+                                                  V3 bo, V3 bd, Real& b_tmax, int& b_ref, const Stack st) {
     a_ref = -1, a_inst = -1, b_ref = -1;
 #ifndef RTR_NO_SHARED_DIV
     const bool ok_a = raydiv_origin_ok(ao), ok_b = raydiv_origin_ok(bo); /* (pair_cast implies shared_div) */
@@ -1999,6 +2008,125 @@ __device__ __forceinline__ void trace_pair(const DScene& sc, V3 ao, V3 ad, Real 
         RT_REGION(RG_PAIR_SETUP);
         if (a_ref >= I.ref_first) a_inst = ii;
     }
+    return true;
+}
+/* A failed vote recasts.  trace_pair_recast holds the pair path alone: at the first frame where some lane's divisor, |d|^2 or
+ * origin is outside div_shared's range it returns false, and whatever it wrote until then does not count.  The caller
+ * then casts both rays from scratch through pair_recast -- the single casts of the split-cast kernels -- after putting
+ * both t_max back to what they were (the hot loop keeps no copy of them).  Per frame the pair scans return the bits of
+ * the single scans (tests/test_pair_shapes.py), so a whole cast through the single scans returns the bits of a cast
+ * through any mixture of the two.  (The copies of the hit state -- a_tmax, a_ref, b_tmax, b_ref -- at every run entry and
+ * back edge of pair_runs are not the scans' doing: they are still emitted with the scans gone) */
+/* The votes of the pair path are taken from the compares' own masks: a verdict is the 64-bit lane mask its v_cmp wrote,
+ * verdicts are combined as wave-uniform integers on the scalar unit, and a vote passes when the combined mask is EXEC (a
+ * v_cmp writes 0 for a lane that is not here).  Written through __all or a ballot of the combined bool, every vote costs
+ * a v_cndmask and a v_cmp_ne on top of its compares.  (volatile: a mask belongs to the EXEC it was made under, so the
+ * compares stay where they are written; every branch between them and their vote is wave-uniform.) */
+typedef unsigned long long PairMask;
+/* lanes with lo <= |x| <= hi (NaN: out, as in rcp_safe) */
+RT_DEV PairMask pair_within(Real x, Real lo, Real hi) {
+    PairMask a, b;
+    asm volatile("v_cmp_ge_f64_e64 %0, |%2|, %3\n\tv_cmp_le_f64_e64 %1, |%2|, %4" : "=&s"(a), "=&s"(b) : "v"(x), "s"(lo), "s"(hi));
+    return a & b;
+}
+RT_DEV PairMask pair_safe(Real d) { return pair_within(d, 0x1p-100, 0x1p100); } /* rcp_safe */
+RT_DEV PairMask pair_below(Real x, Real hi) {
+    PairMask a;
+    asm volatile("v_cmp_le_f64_e64 %0, |%1|, %2" : "=s"(a) : "v"(x), "s"(hi));
+    return a;
+}
+RT_DEV PairMask pair_origin_in(V3 o) { return pair_below(o.x, 0x1p80) & pair_below(o.y, 0x1p80) & pair_below(o.z, 0x1p80); } /* raydiv_origin_ok */
+RT_DEV bool pair_vote(PairMask m) { return m == __builtin_amdgcn_read_exec(); }
+/* One frame of the cast from both rays IN that frame (d.y: the world rays'): the frame's reciprocals, its one vote and
+ * the runs.  `sy`: the verdicts on both d.y.  false: the vote failed, nothing of the frame was scanned. */
+RT_DEV bool pair_scan(const DScene& sc, const FInst& I, V3 ao, Real adx, Real ady, Real adz, Real way, V3 bo, Real bdx, Real bdy,
+                      Real bdz, Real wby, PairMask sy, Real atime, Real& a_tmax, int& a_ref, Real& b_tmax, int& b_ref) {
+    PairRay A, B;
+    A.o = ao, B.o = bo;
+    A.d = mk(adx, ady, adz), B.d = mk(bdx, bdy, bdz);
+    A.q.guard = B.q.guard = false; /* t_min = 0.001 */
+    A.q.fast = B.q.fast = true;
+    A.q.rx = rcp_refined(adx), A.q.rz = rcp_refined(adz);
+    B.q.rx = rcp_refined(bdx), B.q.rz = rcp_refined(bdz);
+    A.q.ry = way, B.q.ry = wby;
+    A.q.a = A.q.ra = B.q.a = B.q.ra = 0;
+    const PairMask s = pair_safe(adx) & pair_safe(adz) & pair_safe(bdx) & pair_safe(bdz) & sy; /* every divisor of both rays */
+    if (I.flags & RT_INST_SPHERES) { /* raydiv_spheres; d.y^2 is made here, in the frames that need it, and not once
+                                      * per cast of a scene without spheres, where a plain product is hoisted to */
+        Real ayy, byy;
+        asm volatile("v_mul_f64 %0, %2, %2\n\tv_mul_f64 %1, %3, %3" : "=&v"(ayy), "=&v"(byy) : "v"(ady), "v"(bdy));
+        A.q.a = adx * adx + ayy + adz * adz, B.q.a = bdx * bdx + byy + bdz * bdz; /* len2 */
+        A.q.ra = rcp_refined(A.q.a), B.q.ra = rcp_refined(B.q.a);
+        if (!pair_vote(s & pair_safe(A.q.a) & pair_safe(B.q.a))) return false;
+        pair_runs<true>(sc, I, A, atime, a_tmax, a_ref, B, b_tmax, b_ref);
+    } else {
+        if (!pair_vote(s)) return false;
+        pair_runs<false>(sc, I, A, atime, a_tmax, a_ref, B, b_tmax, b_ref);
+    }
+    return true;
+}
+__device__ __forceinline__ bool trace_pair_recast(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
+                                                  V3 bo, V3 bd, Real& b_tmax, int& b_ref) {
+    a_ref = -1, a_inst = -1, b_ref = -1;
+#ifdef RTR_NO_SHARED_DIV /* experiments without the shared reciprocals: every cast is the two single casts */
+    return false;
+#endif
+    if (!pair_vote(pair_origin_in(ao) & pair_origin_in(bo))) return false; /* (pair_cast implies shared_div) */
+    const Real way = rcp_refined(ad.y), wby = rcp_refined(bd.y);
+    const PairMask sy = pair_safe(ad.y) & pair_safe(bd.y);
+    for (int ii = 0; ii < sc.n_finst; ++ii) {
+        RT_REGION(RG_PAIR_SETUP);
+        const FInst I = ld_const(sc.finst, ii);
+        PairFrame F;
+        if (I.shape != RT_SHAPE_OTHER) {
+            F = pair_frame(I.shape, I.xf_f[0], I.xf_f[1], ao, ad, bo, bd);
+        } else { /* the generic loop over the ops (none of them touches d.y) */
+            V3 fad = ad, fbd = bd;
+            F.ao = ao, F.bo = bo;
+            wrapper_enter(I.xf_type[0], I.xf_f[0], F.ao, fad);
+            wrapper_enter(I.xf_type[0], I.xf_f[0], F.bo, fbd);
+            if (I.n_xf > 1) {
+                wrapper_enter(I.xf_type[1], I.xf_f[1], F.ao, fad);
+                wrapper_enter(I.xf_type[1], I.xf_f[1], F.bo, fbd);
+            }
+            for (int k = RT_INST_XF_INLINE; k < I.n_xf; ++k) {
+                const FXf x = ld_const(sc.fxf, I.xf_first + k);
+                wrapper_enter(x.type, x.f, F.ao, fad);
+                wrapper_enter(x.type, x.f, F.bo, fbd);
+            }
+            F.adx = fad.x, F.adz = fad.z, F.bdx = fbd.x, F.bdz = fbd.z;
+        }
+        /* (one call for every shape: a second one fed from the world rays' own registers saves the world frame's ten
+         * copies and costs the lean job-queue kernel two spilled VGPRs) */
+        if (!pair_scan(sc, I, F.ao, F.adx, ad.y, F.adz, way, F.bo, F.bdx, bd.y, F.bdz, wby, sy, atime, a_tmax, a_ref, b_tmax, b_ref))
+            return false;
+        RT_REGION(RG_PAIR_SETUP);
+        if (a_ref >= I.ref_first) a_inst = ii;
+    }
+    return true;
+}
+/* The pair cast of a kernel.  RECAST: trace_pair_recast, and the caller runs pair_recast when it returns false; otherwise
+ * the per-frame fallback, which always returns true.  Which kernel takes which is pair_recasts() (rt_kernels.h);
+ * -DRTR_PAIR_FRAME_FALLBACK gives every kernel the fallback: the stand-in for the tree before the recast in before /
+ * after measurements. */
+template <bool RECAST = true>
+__device__ __forceinline__ bool trace_pair(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
+                                           V3 bo, V3 bd, Real& b_tmax, int& b_ref, const Stack st) {
+#ifndef RTR_PAIR_FRAME_FALLBACK
+    if (RECAST) return trace_pair_recast(sc, ao, ad, atime, a_tmax, a_ref, a_inst, bo, bd, b_tmax, b_ref);
+#endif
+    return trace_pair_frames(sc, ao, ad, atime, a_tmax, a_ref, a_inst, bo, bd, b_tmax, b_ref, st);
+}
+/* What a caller of trace_pair does when it returns false: both rays from scratch through the single casts of the
+ * split-cast kernels (cast_closest / cast_any<RT_TRAV_FLAT>'s trace_fast instantiations).  a_tmax and b_tmax arrive
+ * re-materialised from where the caller had them before the cast. */
+RT_DEV void pair_recast(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst, V3 bo, V3 bd,
+                        Real& b_tmax, int& b_ref, const Stack st) {
+    RT_REGION(RG_PAIR_RECAST);
+    int b_inst;
+    const FSub sub = sub_scene0(sc);
+    trace_fast<false, false, false, false, false>(sc, sub, ao, ad, atime, 0.001, a_tmax, a_ref, a_inst, st, 0);
+    trace_fast<true, false, true, false, false>(sc, sub, bo, bd, 0.0, 0.001, b_tmax, b_ref, b_inst, st, 0);
 }
 
 /* Build the reference's hit_record for (reference, instance, t): the primitive's own hit()

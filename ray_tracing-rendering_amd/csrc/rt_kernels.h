@@ -44,6 +44,13 @@ constexpr int mega_waves(int integ, int trav, int ms) {
     return 2;
 }
 
+/* Which pair-cast kernels recast after a failed vote (trace_pair<true>, rt_device.h) and which keep the per-frame fallback
+ * inside the instance loop: the lean material set's, whose kernels are bound by the vector instructions they issue
+ * (cornell_mis x1.023, c5_shard x1.025).  With the recast in the kernels of the other sets mis_spheres lost 0.9 %
+ * (k_mega_queue<4,4,2>: eight more spilled SGPRs) and four of their accumulator-pass kernels spilled two to four more
+ * VGPRs: they compile the fallback's text, as before (profiles/r24_recast.txt). */
+constexpr bool pair_recasts(int ms) { return ms == RT_MS_LEAN; }
+
 /* Per-lane path state that the ray casts do not touch lives in LDS between shading steps
  * ("parked"), so it does not occupy VGPRs across the traversal loops: throughput, radiance of
  * the sample, pixel sum, previous BSDF pdf and the pending light contribution.  Word k of lane l
@@ -455,7 +462,13 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             } else {
                 so = mk(0.0, 0.0, 0.0);
             }
-            trace_pair(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
+            if (!trace_pair<pair_recasts(MS)>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st)) {
+                /* a vote failed (cold): the two single casts, both t_max from where they came (a request that is not
+                 * pending is the dummy already: nothing stale to replace) */
+                a_tmax = cast_a ? RT_INF : 0.0;
+                b_tmax = pending ? pk.get(PK_STMAX) : 0.0;
+                pair_recast(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
+            }
             RTR_CLK(closest);
             RT_REGION(RG_POLL);
             const uint32_t cancel_word = cancel_poll_issue(P, it++);
@@ -816,6 +829,13 @@ RT_DEV bool queue_take(const RenderK& P, uint32_t* __restrict__ q_counter, const
     return got;
 }
 
+/* After a recast (pair_recast) of a kernel whose request B stays resident in PK_SWI / `so` while it is dead: the request is
+ * dead after its cast, and gets the prologue's direction and a zero origin, which pass every vote */
+RT_DEV void pair_retire(const Park& pk, V3& so) {
+    pk.set3(PK_SWI, mk(1.0, 1.0, 1.0));
+    so = mk(0.0, 0.0, 0.0);
+}
+
 template <int INTEG, int TRAV, int MS>
 __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
     k_mega_queue(const DScene* __restrict__ scp, const RenderK P, const int stack_words, uint32_t* __restrict__ /* q_counter */,
@@ -888,13 +908,21 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
         }
         /* B is what the parked words hold, read by every lane alike.  A dead request keeps the direction of the lane's
          * last one, and `so` its origin: with t_max = 0 no record of the fast or the plain scans accepts it (t_min is
-         * 0.001), and a b_ref it did set would not count, because `lit` asks for `pending`.  A stale direction or origin
-         * that failed rcp_safe or the origin verdict when it was cast fails it again, until the lane parks its next
-         * request, and sends the wave to the plain scans of that frame, which return what the pair scans return: it
-         * costs that frame's time, never a hit. */
+         * 0.001), and a b_ref it did set would not count, because `lit` asks for `pending`.  A direction or origin that
+         * failed rcp_safe or the origin verdict sent its cast to the recast below, which replaces it (pair_retire): what
+         * stays resident has passed every vote once. */
         const V3 swi = pk.get3(PK_SWI);
         Real b_tmax = pk.get(PK_STMAX);
-        trace_pair(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
+        if (!trace_pair<pair_recasts(MS)>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st)) {
+            /* a vote failed (cold): both rays again through the single casts, their t_max from where they came (the
+             * request is not yet marked dead).  After this cast the resident request is dead in every lane, and takes
+             * the prologue's direction and a zero origin: a stale direction or origin that failed its verdict would fail
+             * it again in every later iteration and pin the wave to this block. */
+            a_tmax = cast_a ? RT_INF : 0.0;
+            b_tmax = pk.get(PK_STMAX);
+            pair_recast(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st);
+            pair_retire(pk, so);
+        }
         RTR_CLK(closest);
         RT_REGION(RG_POLL);
         const uint32_t cancel_word = cancel_poll_issue(P, it++);

@@ -73,7 +73,9 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_flat_hits(const DScene sc, r
 }
 
 /* trace_pair on one ray pair per lane, and the single casts of the flat kernels (cast_closest / cast_any<RT_TRAV_FLAT>'s
- * trace_fast instantiations) for the same lanes */
+ * trace_fast instantiations) for the same lanes.  RECAST: which of the product's two texts runs -- true: the lean kernels'
+ * (trace_pair_recast + pair_recast), false: the per-frame fallback of every other pair-cast kernel (trace_pair_frames) */
+template <bool RECAST>
 __global__ void __launch_bounds__(RTR_BLOCK) k_test_pair(const DScene sc, rtr_pair_record* recs, long long n) {
     extern __shared__ int lds_stack[];
     const Stack st{lds_stack + threadIdx.x};
@@ -82,13 +84,60 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_test_pair(const DScene sc, rtr_pa
     rtr_pair_record r = recs[k];
     Real a_t = r.a_tmax, b_t = r.b_tmax;
     int a_ref, a_inst, b_ref;
-    trace_pair(sc, ld3(r.ao), ld3(r.ad), 0.0, a_t, a_ref, a_inst, ld3(r.bo), ld3(r.bd), b_t, b_ref, st);
+    r.recasts = 0, r.pad = 0;
+    if (!trace_pair<RECAST>(sc, ld3(r.ao), ld3(r.ad), 0.0, a_t, a_ref, a_inst, ld3(r.bo), ld3(r.bd), b_t, b_ref, st)) {
+        a_t = r.a_tmax, b_t = r.b_tmax;
+        pair_recast(sc, ld3(r.ao), ld3(r.ad), 0.0, a_t, a_ref, a_inst, ld3(r.bo), ld3(r.bd), b_t, b_ref, st);
+        r.recasts = 1;
+    }
     Real s_t = r.a_tmax, sb_t = r.b_tmax;
     int s_ref, s_inst, sb_ref, sb_inst;
     trace_fast<false, false, false, false, false>(sc, sub_scene0(sc), ld3(r.ao), ld3(r.ad), 0.0, 0.001, s_t, s_ref, s_inst, st, 0);
     trace_fast<true, false, true, false, false>(sc, sub_scene0(sc), ld3(r.bo), ld3(r.bd), 0.0, 0.001, sb_t, sb_ref, sb_inst, st, 0);
     r.a_t = a_t, r.s_a_t = s_t;
     r.a_ref = a_ref, r.a_inst = a_inst, r.b_hit = b_ref >= 0;
+    r.s_a_ref = s_ref, r.s_a_inst = s_inst, r.s_b_hit = sb_ref >= 0;
+    recs[k] = r;
+}
+
+/* rtr_test_pair_resident: k_mega_queue's steps around its pair cast, `casts` times (wave-uniform) -- the request read from
+ * its parked words and `so`, the cast, the recast with pair_retire where a vote failed, the request marked dead */
+__global__ void __launch_bounds__(RTR_BLOCK) k_test_pair_resident(const DScene sc, rtr_pair_record* recs, long long n,
+                                                                  const int stack_words, const int casts) {
+    extern __shared__ int lds_stack[];
+    const Stack st{lds_stack + threadIdx.x};
+    const Park pk{reinterpret_cast<double*>(lds_stack + stack_words * RTR_BLOCK) + threadIdx.x};
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    rtr_pair_record r = recs[k];
+    const V3 ao = ld3(r.ao), ad = ld3(r.ad);
+    V3 so = ld3(r.bo);
+    pk.set3(PK_SWI, ld3(r.bd));
+    pk.set(PK_STMAX, r.b_tmax);
+    r.recasts = 0, r.pad = 0;
+    for (int c = 0; c < casts; ++c) {
+        Real a_t = r.a_tmax;
+        int a_ref, a_inst, b_ref;
+        const V3 swi = pk.get3(PK_SWI);
+        Real b_t = pk.get(PK_STMAX);
+        if (!trace_pair(sc, ao, ad, 0.0, a_t, a_ref, a_inst, so, swi, b_t, b_ref, st)) {
+            a_t = r.a_tmax;
+            b_t = pk.get(PK_STMAX);
+            pair_recast(sc, ao, ad, 0.0, a_t, a_ref, a_inst, so, swi, b_t, b_ref, st);
+            pair_retire(pk, so);
+            ++r.recasts;
+        }
+        pk.set(PK_STMAX, 0.0);
+        if (c == 0) {
+            r.a_t = a_t;
+            r.a_ref = a_ref, r.a_inst = a_inst, r.b_hit = b_ref >= 0;
+        }
+    }
+    Real s_t = r.a_tmax, sb_t = r.b_tmax;
+    int s_ref, s_inst, sb_ref, sb_inst;
+    trace_fast<false, false, false, false, false>(sc, sub_scene0(sc), ao, ad, 0.0, 0.001, s_t, s_ref, s_inst, st, 0);
+    trace_fast<true, false, true, false, false>(sc, sub_scene0(sc), ld3(r.bo), ld3(r.bd), 0.0, 0.001, sb_t, sb_ref, sb_inst, st, 0);
+    r.s_a_t = s_t;
     r.s_a_ref = s_ref, r.s_a_inst = s_inst, r.s_b_hit = sb_ref >= 0;
     recs[k] = r;
 }

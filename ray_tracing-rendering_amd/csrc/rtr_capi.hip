@@ -132,7 +132,8 @@ int finish_stats(rtr_context* c) {
                                           "sample end: begin_sample (camera ray)", "sample end: settle into the pixel sum",
                                           "cast counters", "random_in_unit_sphere rejection loop",
                                           "shade_a: emitter MIS weight (compute_light_pdf)", "camera_sample: image-size divisions",
-                                          "shading: lane-varying 1 / x and n / d", "shading: lane-varying sqrt"};
+                                          "shading: lane-varying 1 / x and n / d", "shading: lane-varying sqrt",
+                                          "pair cast: recast through the single casts"};
         double total = 0;
         for (int k = 0; k < RG_N; ++k) total += (double)h[RT_PROF_BASE + k];
         std::fprintf(stderr, "[region profile] %.4g wave cycles in all, %llu samples\n", total, h[0]);

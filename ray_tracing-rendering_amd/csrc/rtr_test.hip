@@ -357,7 +357,7 @@ int rtr_test_pair_frame_host(int32_t shape, const double* ops, rtr_pair_frame_re
     return RTR_OK;
 }
 
-int rtr_test_pair_cast(rtr_context* c, rtr_pair_record* recs, int64_t n) {
+int rtr_test_pair_cast_text(rtr_context* c, rtr_pair_record* recs, int64_t n, int32_t recast) {
     rtr_debug_view v;
     TestState* t;
     int rc = begin(c, recs, n, sizeof *recs, v, t);
@@ -366,8 +366,33 @@ int rtr_test_pair_cast(rtr_context* c, rtr_pair_record* recs, int64_t n) {
     if (n == 0) return RTR_OK;
     TCHK(c, hipSetDevice(v.device));
     const size_t lds = v.stack_bytes;
-    if ((rc = set_lds(c, k_test_pair, lds))) return rc;
-    hipLaunchKernelGGL(k_test_pair, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, v.ds, static_cast<rtr_pair_record*>(t->buf), (long long)n);
+    rtr_pair_record* d = static_cast<rtr_pair_record*>(t->buf);
+    if (recast) {
+        if ((rc = set_lds(c, k_test_pair<true>, lds))) return rc;
+        hipLaunchKernelGGL(k_test_pair<true>, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, v.ds, d, (long long)n);
+    } else {
+        if ((rc = set_lds(c, k_test_pair<false>, lds))) return rc;
+        hipLaunchKernelGGL(k_test_pair<false>, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, v.ds, d, (long long)n);
+    }
+    return end(c, v.stream, t, recs, n, sizeof *recs);
+}
+
+int rtr_test_pair_cast(rtr_context* c, rtr_pair_record* recs, int64_t n) { return rtr_test_pair_cast_text(c, recs, n, 1); }
+
+int rtr_test_pair_resident(rtr_context* c, rtr_pair_record* recs, int64_t n, int32_t casts) {
+    rtr_debug_view v;
+    TestState* t;
+    int rc = begin(c, recs, n, sizeof *recs, v, t);
+    if (rc) return rc;
+    if (casts < 1) return fail(c, RTR_ERR_INVALID, "casts < 1");
+    if (!v.ds.pair_cast) return fail(c, RTR_ERR_UNSUPPORTED, "the uploaded scene is no pair-cast scene");
+    if (n == 0) return RTR_OK;
+    TCHK(c, hipSetDevice(v.device));
+    const int stack_words = (int)(v.stack_bytes / (RTR_BLOCK * sizeof(int)));
+    const size_t lds = (size_t)stack_words * RTR_BLOCK * sizeof(int) + (size_t)RT_PARK_WORDS * RTR_BLOCK * sizeof(double);
+    if ((rc = set_lds(c, k_test_pair_resident, lds))) return rc;
+    hipLaunchKernelGGL(k_test_pair_resident, grid_of(n), dim3(RTR_BLOCK), lds, v.stream, v.ds, static_cast<rtr_pair_record*>(t->buf),
+                       (long long)n, stack_words, (int)casts);
     return end(c, v.stream, t, recs, n, sizeof *recs);
 }
 

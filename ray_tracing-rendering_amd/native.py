@@ -46,7 +46,7 @@ TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_t
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
                 "rtr_test_last_gather", "rtr_test_last_probe", "rtr_test_last_capture", "rtr_test_last_probe_depth",
                 "rtr_test_temporal_planes", "rtr_test_scene_plan", "rtr_test_flat_hits", "rtr_test_pair_frames",
-                "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
+                "rtr_test_pair_frame_host", "rtr_test_pair_cast", "rtr_test_pair_cast_text", "rtr_test_pair_resident", "rtr_test_queue_blocks_host", "rtr_test_queue_pack_host",
                 "rtr_test_scatter", "rtr_test_materials_ms", "rtr_test_scatter_ms", "rtr_test_lights_ms", "rtr_test_pow5",
                 "rtr_test_pow5_host", "rtr_test_udiv", "rtr_test_scene_consts", "rtr_test_accum_load",
                 "rtr_test_accum_plan", "rtr_test_accum_commit", "rtr_test_rcp_lane", "rtr_test_sqrt_lane",
@@ -107,7 +107,9 @@ PAIR_FRAME_DTYPE = np.dtype([("ao", "<f8", (3,)), ("ad", "<f8", (3,)), ("bo", "<
                              ("fo", "<f8", (3,)), ("fd", "<f8", (3,)), ("same_frame", "<i4"), ("pad", "<i4")])
 PAIR_DTYPE = np.dtype([("ao", "<f8", (3,)), ("ad", "<f8", (3,)), ("a_tmax", "<f8"), ("bo", "<f8", (3,)), ("bd", "<f8", (3,)),
                        ("b_tmax", "<f8"), ("a_t", "<f8"), ("s_a_t", "<f8"), ("a_ref", "<i4"), ("a_inst", "<i4"),
-                       ("b_hit", "<i4"), ("s_a_ref", "<i4"), ("s_a_inst", "<i4"), ("s_b_hit", "<i4")])
+                       ("b_hit", "<i4"), ("s_a_ref", "<i4"), ("s_a_inst", "<i4"), ("s_b_hit", "<i4"), ("recasts", "<i4"),
+                       ("pad", "<i4")])
+assert PAIR_DTYPE.itemsize == 160
 QUEUE_BLOCK_DTYPE = np.dtype([(name, "<i4") for name in ("slot", "quarter", "chunk", "s0", "s1", "ref_s0", "ref_s1", "pad")])
 MS_LEAN, MS_FULL, MS_QUADLIT = 0, 1, 2  # RT_MS_* (csrc/rt_device.h): the material-set instantiations of the kernels
 FRAME_SHAPES = ("none", "T", "R", "TR", "RT", "other")  # FInst::shape (csrc/rt_device.h: RT_SHAPE_*)
@@ -294,6 +296,8 @@ def test_lib():
     T.rtr_test_pair_frames.argtypes = [C.POINTER(A.SceneDescC), vp, C.c_int64, C.POINTER(C.c_int32)]
     T.rtr_test_pair_frame_host.argtypes = [C.c_int32, vp, vp, C.c_int64]
     T.rtr_test_pair_cast.argtypes = [vp, vp, C.c_int64]
+    T.rtr_test_pair_cast_text.argtypes = [vp, vp, C.c_int64, C.c_int32]
+    T.rtr_test_pair_resident.argtypes = [vp, vp, C.c_int64, C.c_int32]
     T.rtr_test_queue_blocks_host.argtypes = [C.c_int32] * 6 + [vp, C.c_int64]
     T.rtr_test_queue_pack_host.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     T.rtr_test_udiv.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1605,13 +1609,23 @@ class Context:
         self._chk(test_lib().rtr_test_flat_hits(self._h, out.ctypes.data, len(out), 1 if with_uv else 0, C.byref(used)))
         return out, bool(used.value)
 
-    def pair_cast(self, ao, ad, bo, bd, a_tmax=np.inf, b_tmax=np.inf):
-        """rtr_test_pair_cast (include/rtr_hip_test.h): trace_pair on n ray pairs ((n, 3) arrays; t_max scalars or (n,))
-        next to the two single casts of the flat kernels.  Returns the ``PAIR_DTYPE`` records."""
+    def pair_cast(self, ao, ad, bo, bd, a_tmax=np.inf, b_tmax=np.inf, recast=True):
+        """rtr_test_pair_cast_text (include/rtr_hip_test.h): trace_pair on n ray pairs ((n, 3) arrays; t_max scalars or (n,))
+        next to the two single casts of the flat kernels.  ``recast``: the lean kernels' text (True) or the per-frame
+        fallback of the other pair-cast kernels.  Returns the ``PAIR_DTYPE`` records."""
         recs = np.zeros(len(ao), dtype=PAIR_DTYPE)
         recs["ao"], recs["ad"], recs["bo"], recs["bd"] = ao, ad, bo, bd
         recs["a_tmax"], recs["b_tmax"] = a_tmax, b_tmax
-        self._chk(test_lib().rtr_test_pair_cast(self._h, recs.ctypes.data, len(recs)))
+        self._chk(test_lib().rtr_test_pair_cast_text(self._h, recs.ctypes.data, len(recs), 1 if recast else 0))
+        return recs
+
+    def pair_resident(self, ao, ad, bo, bd, a_tmax=np.inf, b_tmax=np.inf, casts=1):
+        """rtr_test_pair_resident (include/rtr_hip_test.h): ``casts`` pair casts of every lane with the job-queue kernel's
+        resident shadow request, B parked for the first cast only.  Returns the ``PAIR_DTYPE`` records."""
+        recs = np.zeros(len(ao), dtype=PAIR_DTYPE)
+        recs["ao"], recs["ad"], recs["bo"], recs["bd"] = ao, ad, bo, bd
+        recs["a_tmax"], recs["b_tmax"] = a_tmax, b_tmax
+        self._chk(test_lib().rtr_test_pair_resident(self._h, recs.ctypes.data, len(recs), casts))
         return recs
 
     # device unit kernels over golden-vector records (include/rtr_hip_test.h)
