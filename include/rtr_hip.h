@@ -1310,6 +1310,124 @@ int rtr_cube_chain_lookup_device(rtr_context* ctx, const rtr_cube_level* levels,
 int rtr_cube_chain_lookup_one(const rtr_cube_level* levels, int32_t n_levels, const rtr_gather_out* texels,
                               const rtr_cube_query* query, rtr_gather_out* out);
 
+/* ---- image-based shading: the environment BRDF table of the split-sum approximation, and one fused call that turns a
+ * probe grid, a filtered cube chain and that table into the radiance a PBRMaterial surface sends to a viewer ----
+ * rtr_probe_lookup(_visible) gives an irradiance E, rtr_cube_chain_lookup a prefiltered radiance X.  The third factor of
+ * the split sum is the directional albedo of the specular lobe, int f_spec cos dw ~ F0 * a + b, tabulated over
+ * (mu = n.v, roughness) for the reference's D, G, F and its + 0.0001 (materials/material.h:372-432).  Everything below
+ * is FP64 with + - * / sqrt and compares only, no libm and no fused multiply-add: every product is rounded before its
+ * add, so a host (the _one forms), numpy and the device give the same bits.
+ *
+ * TABLE: n_rough x n_mu records {a, b}, row = roughness: record r * n_mu + c is ENTRY (r, c).
+ *   rough = (r + 0.5) / n_rough,  mu = (c + 0.5) / n_mu,  alpha = rough * rough,  a2 = alpha * alpha,
+ *   k = alpha * 0.5                                 (GeometrySchlickGGX, whose k is roughness^2 / 2),   omk = 1.0 - k
+ *   Vx = sqrt(1.0 - mu * mu),  Vz = mu,  g1v = mu / (mu * omk + k)
+ * A defined quadrature with M = `nodes` over the half vector, in the coordinates in which GGX importance sampling is
+ * uniform (D cancels; the sharp lobe of a low roughness needs no fine grid), the azimuth through the rational
+ * parametrisation of the circle (no sin / cos).  NODE j, 0 <= j < 2 M^2:
+ *   sx = +1.0 for j < M^2, else -1.0;  jj = j mod M^2;  s = (jj / M + 0.5) / M  (integer jj / M),  t = (jj mod M + 0.5) / M
+ *   den = a2 + (1.0 - a2) * (s * s),  c2 = (s * s) / den,  Hz = sqrt(c2),  sh = sqrt(max(1.0 - c2, 0.0))
+ *   q = 1.0 + t * t,  Hx = sh * (sx * ((1.0 - t * t) / q)),  wphi = 1.0 / q
+ *   vh = Vx * Hx + Vz * Hz,  nl = (2.0 * vh) * Hz - Vz       (Vy = 0: Hy never enters)
+ *   every node:  W = W + wphi * s.     The node is USED iff nl > 0 and vh > 0; a USED node also does
+ *   g = g1v * (nl / (nl * omk + k))
+ *   e = (((g * nl) * (4.0 * vh)) * sqrt(den)) / ((4.0 * mu) * nl + 0.0001)
+ *   x = 1.0 - vh,  fc = ((x * x) * (x * x)) * x
+ *   A = A + wphi * (e * (1.0 - fc)),  B = B + wphi * (e * fc)
+ * REDUCTION: the gathers' with G = 64 fixed.  Lane l visits j = l, l + 64, ... in increasing order, W, A, B from +0.0; then
+ * for off = 32, 16, ..., 1: x[l] = x[l] + x[l xor off] on the three sums.  a = (1.0 / W) * A, b = (1.0 / W) * B.
+ *
+ * params: 1 <= n_mu, n_rough, nodes <= 256; pad and reserved 0.  Bad params or a NULL pointer is RTR_ERR_INVALID before
+ * any device work, context first; no scene is needed.  The host entry blocks and brings the records back through the
+ * buffer of the gathers' host entries; the device entry takes a device pointer (8-byte aligned), runs on the context
+ * stream behind whatever is queued there, needs no scratch memory and returns at once unless `blocking`.  A call is split
+ * into launches over runs of entries so that no launch exceeds a fixed number of nodes; the environment variable
+ * RTR_TABLE_NODES=n, read at every call, lowers that cap (a test hook: the bits do not depend on it). */
+typedef struct rtr_brdf_params {    /* 32 bytes */
+    int32_t n_mu, n_rough;
+    int32_t nodes;                  /* M */
+    int32_t pad;                    /* must be 0 */
+    double reserved[2];             /* must be 0 */
+} rtr_brdf_params;
+typedef struct rtr_brdf_entry {     /* 16 bytes */
+    double a, b;
+} rtr_brdf_entry;
+
+int rtr_brdf_table(rtr_context* ctx, const rtr_brdf_params* params, rtr_brdf_entry* out);
+int rtr_brdf_table_device(rtr_context* ctx, const rtr_brdf_params* params, rtr_brdf_entry* d_out, int blocking);
+/* Host-only, needs no context: ENTRY (r, c), the arithmetic the kernel runs in the lane order above.  RTR_ERR_INVALID for
+ * bad params, a NULL pointer, r outside [0, n_rough) or c outside [0, n_mu). */
+int rtr_brdf_entry_one(const rtr_brdf_params* params, int32_t r, int32_t c, rtr_brdf_entry* out);
+/* FETCH (host only, the function the shader calls): bilinear in the table at (mu, rough), texel centres at (i + 0.5) / n.
+ *   per axis (x = mu with n = n_mu: columns; x = rough with n = n_rough: rows): g = x * n - 0.5,
+ *     f = min(max(g, 0), n - 1),  i0 = (int)f capped at max(n - 2, 0),  t = f - (double)i0 (t = 0 for n == 1),
+ *     w0 = 1.0 - t, w1 = t: the per-axis rule of rtr_probe_lookup
+ *   taps: dr outermost, then dc, each in {0, 1}: entry (min(i0r + dr, n_rough - 1), min(i0c + dc, n_mu - 1)),
+ *     w = wc[dc] * wr[dr], read iff w > 0:  a = a + w * entry.a, b = b + w * entry.b from +0.0
+ * RTR_ERR_INVALID for n_mu or n_rough outside 1 .. 256, a NULL pointer or a non-finite mu or rough. */
+int rtr_brdf_fetch_one(int32_t n_mu, int32_t n_rough, const rtr_brdf_entry* table, double mu, double rough,
+                       rtr_brdf_entry* out);
+
+/* SHADE: the radiance of one surface point towards its viewer under an ENVIRONMENT: a probe grid (with its distance maps
+ * and the parameters of rtr_probe_lookup_visible, or both NULL for the plain rtr_probe_lookup), a cube chain and a table.
+ * `parts` selects the terms: RTR_SHADE_DIFFUSE | RTR_SHADE_SPECULAR, at least one.  The arrays of a part that is not
+ * selected (grid, probes, depth, visible / levels, chain) may be NULL and are not read; the table serves both.  The struct
+ * is a HOST struct, copied at the call with the grid, the visible params and the levels it points to; probes, depth, chain
+ * and table are host arrays for the host entry and rtr_shade_ibl_one, device arrays for the device entry.
+ *
+ * A query is BAD when one of its 14 fields is not finite or when n or v has a length outside (0, inf) (the gathers' rule).
+ *   N = (1 / |n|) * n,  Vd = (1 / |v|) * v   with |x| = sqrt(x.x*x.x + x.y*x.y + x.z*x.z)
+ *   mu = (N.x*Vd.x + N.y*Vd.y) + N.z*Vd.z,  muc = max(mu, 0.0)
+ *   rough = min(max(roughness, 0.01), 1.0)          (material.h:368),   alpha = rough * rough
+ *   DIFFUSE:  Erec = rtr_probe_lookup(_visible) of the query (p, n)
+ *   SPECULAR: R = (2.0 * mu) * N - Vd per component,  Xrec = rtr_cube_chain_lookup of (R, alpha)
+ *   (a, b) = FETCH at (muc, rough)
+ *   per channel: F0 = (1.0 - metallic) * 0.04 + metallic * base                  (material.h:375)
+ *     kS = F0 * a + b,  kD = (1.0 - kS) * (1.0 - metallic)
+ *     diffuse = ((kD * base) * Erec.v) / pi,  specular = Xrec.v * kS              (pi = 3.1415926535897932385)
+ *     v = diffuse + specular with both parts, else the selected term alone
+ *   valid = 1 and count = the sum of the selected parts' counts when every selected part's record is valid; the all-zero
+ *   record otherwise (the chain is not read when the diffuse record is invalid).
+ *
+ * Entries: env, its table (1 <= n_mu, n_rough <= 256) and the arrays of the selected parts are checked with the rules of
+ * the lookups they name (grid, visible params, chain against n_records); parts outside 1 .. 3, depth without visible or
+ * visible without depth, n < 0 or a NULL array is RTR_ERR_INVALID, before any device work, context first; n == 0 is
+ * RTR_OK; no scene is needed.  The host entry rejects a batch with a BAD query, naming its index, with `out` untouched; it
+ * stages the records once at the head of the buffer of the gathers' host entries and the queries in slices of 2^20.  The
+ * device entry (8-byte aligned pointers; out must not overlap the queries or any array read: RTR_ERR_INVALID) writes the
+ * all-zero record for a BAD query without reading a record, runs on the context stream behind whatever is queued there --
+ * rtr_cube_filter_device, rtr_probe_radiance_device and rtr_brdf_table_device, say -- and returns at once unless
+ * `blocking`. */
+#define RTR_SHADE_DIFFUSE 1
+#define RTR_SHADE_SPECULAR 2
+typedef struct rtr_shade_env {      /* 80 bytes */
+    int32_t parts;                  /* RTR_SHADE_* */
+    int32_t n_levels;
+    const rtr_probe_grid* grid;     /* host */
+    const rtr_probe_sh* probes;     /* dims[0] * dims[1] * dims[2] records */
+    const rtr_probe_depth_texel* depth;         /* probes * map_size^2 records, or NULL */
+    const rtr_probe_visible_params* visible;    /* host; NULL with depth NULL: the plain lookup */
+    const rtr_cube_level* levels;   /* host, n_levels of them */
+    const rtr_gather_out* chain;    /* n_records records */
+    int64_t n_records;
+    const rtr_brdf_entry* table;    /* n_rough * n_mu records */
+    int32_t n_mu, n_rough;
+} rtr_shade_env;
+typedef struct rtr_shade_query {    /* 112 bytes */
+    double p[3];                    /* position */
+    double n[3];                    /* surface normal, need not be normalised */
+    double v[3];                    /* towards the viewer, need not be normalised */
+    double base[3];                 /* base colour */
+    double roughness, metallic;
+} rtr_shade_query;
+
+int rtr_shade_ibl(rtr_context* ctx, const rtr_shade_env* env, const rtr_shade_query* queries, rtr_gather_out* out, int64_t n);
+int rtr_shade_ibl_device(rtr_context* ctx, const rtr_shade_env* env, const rtr_shade_query* d_queries, rtr_gather_out* d_out,
+                         int64_t n, int blocking);
+/* Host-only, needs no context: one query over HOST arrays, the same function the kernel calls.  RTR_ERR_INVALID for a bad
+ * environment, a NULL pointer or a BAD query. */
+int rtr_shade_ibl_one(const rtr_shade_env* env, const rtr_shade_query* query, rtr_gather_out* out);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

@@ -199,6 +199,29 @@ assert CUBE_QUERY_DTYPE.itemsize == 32
 CUBE_FILTER_MAX_FACE, CUBE_CHAIN_MAX_LEVELS = 512, 13
 
 
+class BrdfParamsC(C.Structure):
+    """rtr_brdf_params (include/rtr_hip.h): the environment BRDF table of rtr_brdf_table"""
+    _fields_ = [("n_mu", C.c_int32), ("n_rough", C.c_int32), ("nodes", C.c_int32), ("pad", C.c_int32),
+                ("reserved", C.c_double * 2)]
+
+
+class ShadeEnvC(C.Structure):
+    """rtr_shade_env (include/rtr_hip.h): what rtr_shade_ibl shades under; every pointer member is a c_void_p"""
+    _fields_ = [("parts", C.c_int32), ("n_levels", C.c_int32), ("grid", C.c_void_p), ("probes", C.c_void_p),
+                ("depth", C.c_void_p), ("visible", C.c_void_p), ("levels", C.c_void_p), ("chain", C.c_void_p),
+                ("n_records", C.c_int64), ("table", C.c_void_p), ("n_mu", C.c_int32), ("n_rough", C.c_int32)]
+
+
+BRDF_PARAMS_SIZE, SHADE_ENV_SIZE = 32, 80
+assert C.sizeof(BrdfParamsC) == BRDF_PARAMS_SIZE and C.sizeof(ShadeEnvC) == SHADE_ENV_SIZE
+BRDF_ENTRY_DTYPE = np.dtype([("a", "<f8"), ("b", "<f8")])  # rtr_brdf_entry
+SHADE_QUERY_DTYPE = np.dtype([("p", "<f8", (3,)), ("n", "<f8", (3,)), ("v", "<f8", (3,)), ("base", "<f8", (3,)),
+                              ("roughness", "<f8"), ("metallic", "<f8")])  # rtr_shade_query
+assert BRDF_ENTRY_DTYPE.itemsize == 16 and SHADE_QUERY_DTYPE.itemsize == 112
+BRDF_MAX = 256
+SHADE_DIFFUSE, SHADE_SPECULAR = 1, 2
+
+
 class DenoiseParamsC(C.Structure):
     """rtr_denoise_params (include/rtr_hip.h): the a-trous denoiser of rtr_accum_denoise / rtr_denoise_host"""
     _fields_ = [("iterations", C.c_int32), ("feature_spp", C.c_int32), ("sigma_l", C.c_double),

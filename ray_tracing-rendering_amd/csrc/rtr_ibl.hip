@@ -1,0 +1,250 @@
+/*
+ * rtr_ibl.hip -- image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*): the parameter and environment checks,
+ * the split of a table call into launches of bounded work, the two kernels of rt_ibl.h and their launches, the entries, and
+ * the host-only pieces that need no context (rtr_brdf_entry_one, rtr_brdf_fetch_one, rtr_shade_ibl_one).  The entries'
+ * common checks, the staging of the host entries and the body of the device entries are rt_batch.h's, shared with the
+ * gathers, probes, captures and cube maps.
+ */
+#include "rt_batch.h"
+#include "rt_ibl.h"
+
+#include <cstdlib>
+
+using namespace rtr;
+
+namespace {
+
+constexpr int64_t kShadeSlice = (int64_t)1 << 20; /* queries (table entries) per slice of the host entries */
+constexpr long long kTableNodes = 1ll << 31;      /* nodes per launch at most */
+
+long long table_node_cap() {
+    long long cap = kTableNodes;
+    if (const char* e = getenv("RTR_TABLE_NODES")) { /* a test hook: lowers the cap */
+        const long long v = std::atoll(e);
+        if (v >= 1 && v < cap) cap = v;
+    }
+    return cap;
+}
+
+/* what both table entries check before any device work: context, params, NULL; no scene is needed */
+int table_check(rtr_context* c, const rtr_brdf_params* bp, const void* out) {
+    if (!c) return RTR_ERR_INVALID;
+    if (const char* why = brdf_params_why(bp)) return fail(c, RTR_ERR_INVALID, std::string("rtr_brdf_table: ") + why);
+    return batch_check(c, "rtr_brdf_table", 1, out != nullptr);
+}
+
+/* the entries [e0, e1) of the table (numbered r * n_mu + c) into d_out, whose record 0 is e0.  No launch holds more than
+ * table_node_cap() nodes: whole rows one above the other while they fit, else one row's columns in runs */
+int table_launch(rtr_context* c, const rtr_brdf_params* bp, rtr_brdf_entry* d_out, long long e0, long long e1) {
+    TableK K{};
+    K.out = d_out, K.out_first = e0;
+    K.n_mu = bp->n_mu, K.n_rough = bp->n_rough, K.M = bp->nodes;
+    const long long per_launch = std::max(1ll, table_node_cap() / (2ll * K.M * K.M)); /* entries */
+    for (long long e = e0; e < e1;) {
+        const int r = (int)(e / K.n_mu), col = (int)(e - (long long)r * K.n_mu);
+        long long rows = 1;
+        K.row0 = r, K.c0 = col;
+        if (col == 0 && e1 - e >= K.n_mu && per_launch >= K.n_mu) {
+            rows = std::min((e1 - e) / K.n_mu, per_launch / K.n_mu);
+            K.c1 = K.n_mu;
+        } else {
+            K.c1 = (int)std::min<long long>(K.n_mu, col + std::min(per_launch, e1 - e));
+        }
+        const int cols = K.c1 - K.c0, per_wg = RTR_BLOCK / 64;
+        hipLaunchKernelGGL(k_brdf_table, dim3((unsigned)((cols + per_wg - 1) / per_wg), (unsigned)rows), dim3(RTR_BLOCK), 0, c->stream, K);
+        e += rows * (long long)cols;
+    }
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("brdf table launch: ") + hipGetErrorString(err));
+}
+
+/* the grid rule of rtr_probe_lookup */
+const char* grid_why(const rtr_probe_grid* g) {
+    if (!g) return "null grid";
+    long long count = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!__builtin_isfinite(g->origin[a])) return "origin not finite";
+        if (!(__builtin_isfinite(g->spacing[a]) && g->spacing[a] > 0)) return "spacing must be finite and > 0";
+        if (g->dims[a] < 1 || g->dims[a] > (1 << 24)) return "dims must be >= 1 and their product <= 2^24";
+        count *= g->dims[a];
+        if (count > (1ll << 24)) return "dims must be >= 1 and their product <= 2^24";
+    }
+    if (g->pad != 0) return "pad must be 0";
+    return nullptr;
+}
+long long grid_probes(const rtr_probe_grid* g) { return (long long)g->dims[0] * g->dims[1] * g->dims[2]; }
+
+/* why `env` is no environment, or nullptr: the rules of the lookups it names, for the selected parts only */
+const char* env_why(const rtr_shade_env* e) {
+    if (!e) return "null environment";
+    if (e->parts < 1 || e->parts > (RTR_SHADE_DIFFUSE | RTR_SHADE_SPECULAR)) return "parts must be RTR_SHADE_DIFFUSE, RTR_SHADE_SPECULAR or both";
+    if (e->n_mu < 1 || e->n_mu > RTR_BRDF_MAX || e->n_rough < 1 || e->n_rough > RTR_BRDF_MAX) return "table n_mu or n_rough outside 1 .. 256";
+    if (!e->table) return "null table";
+    if (e->parts & RTR_SHADE_DIFFUSE) {
+        if (const char* why = grid_why(e->grid)) return why;
+        if (!e->probes) return "null probes";
+        if ((e->depth != nullptr) != (e->visible != nullptr)) return "depth and visible go together";
+        if (e->visible) {
+            if (const char* why = probe_visible_params_why(e->visible)) return why;
+            if (grid_probes(e->grid) * e->visible->map_size * e->visible->map_size > (1ll << 24)) return "probes * map_size^2 must be <= 2^24";
+        }
+    }
+    if (e->parts & RTR_SHADE_SPECULAR) {
+        if (e->n_records < 0) return "negative n_records";
+        if (const char* why = cube_chain_why(e->levels, e->n_levels, e->n_records)) return why;
+        if (!e->chain) return "null chain";
+    }
+    return nullptr;
+}
+
+/* bytes of the arrays of a valid environment: of a part that is not selected 0 */
+struct EnvBytes {
+    size_t probes, depth, chain, table;
+};
+EnvBytes env_bytes(const rtr_shade_env* e) {
+    EnvBytes b{0, 0, 0, (size_t)e->n_mu * e->n_rough * sizeof(rtr_brdf_entry)};
+    if (e->parts & RTR_SHADE_DIFFUSE) {
+        b.probes = (size_t)grid_probes(e->grid) * sizeof(rtr_probe_sh);
+        if (e->visible) b.depth = (size_t)grid_probes(e->grid) * e->visible->map_size * e->visible->map_size * sizeof(rtr_probe_depth_texel);
+    }
+    if (e->parts & RTR_SHADE_SPECULAR) b.chain = (size_t)e->n_records * sizeof(rtr_gather_out);
+    return b;
+}
+/* the kernel's argument of a valid environment whose arrays are at these addresses */
+ShadeK shade_k(const rtr_shade_env* e, const void* probes, const void* depth, const void* chain, const void* table) {
+    ShadeK K{};
+    K.parts = e->parts;
+    if (e->parts & RTR_SHADE_DIFFUSE) {
+        K.grid = *e->grid, K.probes = static_cast<const rtr_probe_sh*>(probes);
+        if (e->visible) {
+            K.visible = 1, K.depth = static_cast<const rtr_probe_depth_texel*>(depth);
+            K.T = e->visible->map_size, K.normal_bias = e->visible->normal_bias;
+        }
+    }
+    if (e->parts & RTR_SHADE_SPECULAR) {
+        for (int i = 0; i < e->n_levels; ++i) K.chain.lv[i] = e->levels[i];
+        K.chain.n = e->n_levels, K.texels = static_cast<const rtr_gather_out*>(chain);
+    }
+    K.n_mu = e->n_mu, K.n_rough = e->n_rough, K.table = static_cast<const rtr_brdf_entry*>(table);
+    return K;
+}
+
+/* what both shader entries check before any device work: context, environment, n / NULL; no scene is needed */
+int shade_check(rtr_context* c, const rtr_shade_env* env, const void* q, const void* out, int64_t n) {
+    if (!c) return RTR_ERR_INVALID;
+    if (const char* why = env_why(env)) return fail(c, RTR_ERR_INVALID, std::string("rtr_shade_ibl: ") + why);
+    return batch_check(c, "rtr_shade_ibl", n, q && out);
+}
+int shade_launch(rtr_context* c, const ShadeK& K, const rtr_shade_query* d_q, rtr_gather_out* d_out, int64_t n) {
+    for (int64_t k0 = 0; k0 < n; k0 += kLaunchPoints) {
+        const long long m = std::min<long long>(n - k0, kLaunchPoints);
+        hipLaunchKernelGGL(k_shade_ibl, dim3((unsigned)((m + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), 0, c->stream, K, d_q + k0,
+                           d_out + k0, m);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("shade launch: ") + hipGetErrorString(e));
+}
+
+} // namespace
+
+extern "C" {
+
+int rtr_brdf_entry_one(const rtr_brdf_params* bp, int32_t r, int32_t c, rtr_brdf_entry* out) {
+    if (brdf_params_why(bp) || !out || r < 0 || r >= bp->n_rough || c < 0 || c >= bp->n_mu) return RTR_ERR_INVALID;
+    const int M = bp->nodes, MM = M * M;
+    const BrdfRow R = brdf_row(r, bp->n_rough);
+    const BrdfCol C = brdf_col(c, bp->n_mu, R);
+    double W[64], A[64], B[64];
+    for (int l = 0; l < 64; ++l) W[l] = A[l] = B[l] = 0.0;
+    for (int j = 0; j < 2 * MM; ++j) { /* lane j % 64 meets its nodes in increasing order */
+        const int jj = j < MM ? j : j - MM;
+        const BrdfS S = brdf_s(jj / M, M, R);
+        const BrdfT T = brdf_t(jj % M, M);
+        W[j & 63] = W[j & 63] + T.wphi * S.s;
+        brdf_node(R, C, S, T, j < MM ? 1.0 : -1.0, A[j & 63], B[j & 63]);
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        for (int l = 0; l < off; ++l) /* lane l of the xor tree; the lanes above it are not read again */
+            W[l] = W[l] + W[l ^ off], A[l] = A[l] + A[l ^ off], B[l] = B[l] + B[l ^ off];
+    *out = brdf_result(W[0], A[0], B[0]);
+    return RTR_OK;
+}
+
+int rtr_brdf_fetch_one(int32_t n_mu, int32_t n_rough, const rtr_brdf_entry* table, double mu, double rough, rtr_brdf_entry* out) {
+    if (n_mu < 1 || n_mu > RTR_BRDF_MAX || n_rough < 1 || n_rough > RTR_BRDF_MAX || !table || !out) return RTR_ERR_INVALID;
+    if (!__builtin_isfinite(mu) || !__builtin_isfinite(rough)) return RTR_ERR_INVALID;
+    *out = brdf_fetch(n_mu, n_rough, table, mu, rough);
+    return RTR_OK;
+}
+
+int rtr_brdf_table(rtr_context* c, const rtr_brdf_params* bp, rtr_brdf_entry* out) {
+    if (int rc = table_check(c, bp, out)) return rc;
+    const StagedIO io{0, 0, nullptr, {sizeof(rtr_brdf_entry), 0}, {out, nullptr}};
+    return staged_slices(c, (int64_t)bp->n_mu * bp->n_rough, kShadeSlice, io, [&](const Slice& s) {
+        return table_launch(c, bp, static_cast<rtr_brdf_entry*>(s.out[0]), s.k0, s.k0 + s.m);
+    });
+}
+
+int rtr_brdf_table_device(rtr_context* c, const rtr_brdf_params* bp, rtr_brdf_entry* d_out, int blocking) {
+    if (int rc = table_check(c, bp, d_out)) return rc;
+    return device_entry(c, "rtr_brdf_table_device", (uintptr_t)d_out, blocking,
+                        [&] { return table_launch(c, bp, d_out, 0, (long long)bp->n_mu * bp->n_rough); });
+}
+
+int rtr_shade_ibl_one(const rtr_shade_env* env, const rtr_shade_query* q, rtr_gather_out* out) {
+    double nlen, vlen;
+    if (env_why(env) || !q || !out || shade_query_bad(*q, nlen, vlen)) return RTR_ERR_INVALID;
+    *out = shade_ibl_one(shade_k(env, env->probes, env->depth, env->chain, env->table), *q, nlen, vlen);
+    return RTR_OK;
+}
+
+int rtr_shade_ibl(rtr_context* c, const rtr_shade_env* env, const rtr_shade_query* q, rtr_gather_out* out, int64_t n) {
+    if (int rc = shade_check(c, env, q, out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    for (int64_t k = 0; k < n; ++k) {
+        double nlen, vlen;
+        if (shade_query_bad(q[k], nlen, vlen))
+            return fail(c, RTR_ERR_INVALID, "rtr_shade_ibl: bad query at index " + std::to_string(k) +
+                                                " (a non-finite field, or a normal or view vector whose length is not in (0, inf))");
+    }
+    /* the environment's records stay at the head of the staging buffer for all slices, SH records, maps, chain, table: the
+     * first slice brings them */
+    static_assert(sizeof(rtr_probe_sh) % 16 == 0 && sizeof(rtr_probe_depth_texel) % 16 == 0 && sizeof(rtr_gather_out) % 16 == 0 &&
+                      sizeof(rtr_brdf_entry) % 16 == 0, "StagedIO::head_bytes");
+    const EnvBytes b = env_bytes(env);
+    const StagedIO io{b.probes + b.depth + b.chain + b.table, sizeof(rtr_shade_query), q, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
+    return staged_slices(c, n, kShadeSlice, io, [&](const Slice& s) {
+        char* probes = static_cast<char*>(s.head);
+        char *depth = probes + b.probes, *chain = depth + b.depth, *table = chain + b.chain;
+        if (s.k0 == 0) {
+            if (b.probes) HIPCHK(c, hipMemcpyAsync(probes, env->probes, b.probes, hipMemcpyHostToDevice, c->stream));
+            if (b.depth) HIPCHK(c, hipMemcpyAsync(depth, env->depth, b.depth, hipMemcpyHostToDevice, c->stream));
+            if (b.chain) HIPCHK(c, hipMemcpyAsync(chain, env->chain, b.chain, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(table, env->table, b.table, hipMemcpyHostToDevice, c->stream));
+        }
+        return shade_launch(c, shade_k(env, probes, depth, chain, table), static_cast<const rtr_shade_query*>(s.in),
+                            static_cast<rtr_gather_out*>(s.out[0]), s.m);
+    });
+}
+
+int rtr_shade_ibl_device(rtr_context* c, const rtr_shade_env* env, const rtr_shade_query* d_q, rtr_gather_out* d_out, int64_t n,
+                         int blocking) {
+    if (int rc = shade_check(c, env, d_q, d_out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    const EnvBytes b = env_bytes(env);
+    const uintptr_t in[5][2] = {{(uintptr_t)d_q, (size_t)n * sizeof(rtr_shade_query)},
+                                {b.probes ? (uintptr_t)env->probes : 0, b.probes},
+                                {b.depth ? (uintptr_t)env->depth : 0, b.depth},
+                                {b.chain ? (uintptr_t)env->chain : 0, b.chain},
+                                {(uintptr_t)env->table, b.table}};
+    const uintptr_t u0 = (uintptr_t)d_out, u1 = u0 + (size_t)n * sizeof(rtr_gather_out);
+    uintptr_t bits = u0;
+    for (const auto& a : in) {
+        if (a[1] && a[0] < u1 && u0 < a[0] + a[1]) return fail(c, RTR_ERR_INVALID, "rtr_shade_ibl_device: out overlaps an input");
+        bits |= a[0];
+    }
+    return device_entry(c, "rtr_shade_ibl_device", bits, blocking,
+                        [&] { return shade_launch(c, shade_k(env, env->probes, env->depth, env->chain, env->table), d_q, d_out, n); });
+}
+
+} /* extern "C" */

@@ -46,6 +46,10 @@
  *                                   maps of T x T texels (1..64) go through Renderer::probe_depth with N (default 8) rays per
  *                                   texel under --seed, misses at 1.5 x the length of the grid's spacing; FILE receives the raw
  *                                   rtr_probe_depth_texel records, [probe][row][column].  What is printed does not change
+ *           [--brdf-table NMU,NROUGH [--brdf-nodes M] --brdf-out FILE]   the environment BRDF table of the split sum
+ *                                   (Renderer::brdf_table: NMU x NROUGH entries, 1..256 each, M = 1..256 quadrature nodes per
+ *                                   axis, default 128); FILE receives little-endian doubles [n_rough][n_mu][2] = (a, b).
+ *                                   Needs no scene and renders nothing; excludes every other mode
  *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
  *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
  *                                   rtr_display_host through Renderer::display; with --turntable rtr_display_device on
@@ -197,6 +201,9 @@ int main(int argc, char** argv) {
     int probe_depth = 0, probe_depth_samples = 8;
     bool probe_depth_set = false, probe_depth_sampled = false;
     std::string probe_depth_out;
+    int brdf_dims[2] = {0, 0}, brdf_nodes = 128;
+    bool brdf = false, brdf_noded = false;
+    std::string brdf_out;
     double capture_at[3] = {0, 0, 0};
     int capture_face = 32, capture_spp = 16, latlong[2] = {0, 0}, capture_levels = 0;
     bool capture = false, capture_face_set = false, capture_spp_set = false, latlong_set = false;
@@ -316,6 +323,25 @@ int main(int argc, char** argv) {
             else capture_spp = (int)v, capture_spp_set = true;
         }
         else if (!std::strcmp(argv[k], "--capture-out") && k + 1 < argc) capture_out = argv[++k];
+        else if (!std::strcmp(argv[k], "--brdf-table") && k + 1 < argc) {
+            char tail;
+            brdf = std::sscanf(argv[++k], "%d,%d%c", &brdf_dims[0], &brdf_dims[1], &tail) == 2 && brdf_dims[0] >= 1 &&
+                   brdf_dims[1] >= 1 && brdf_dims[0] <= 256 && brdf_dims[1] <= 256;
+            if (!brdf) {
+                std::cerr << "--brdf-table takes NMU,NROUGH, each in 1..256, not " << argv[k] << "\n";
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[k], "--brdf-nodes") && k + 1 < argc) {
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (end == argv[k] || *end != '\0' || v < 1 || v > 256) {
+                std::cerr << "--brdf-nodes takes an integer in 1..256, not " << argv[k] << "\n";
+                return 2;
+            }
+            brdf_nodes = (int)v, brdf_noded = true;
+        }
+        else if (!std::strcmp(argv[k], "--brdf-out") && k + 1 < argc) brdf_out = argv[++k];
         else if (!std::strcmp(argv[k], "--capture-levels") && k + 1 < argc) {
             char* end = nullptr;
             const long v = std::strtol(argv[++k], &end, 10);
@@ -468,6 +494,14 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (capture && !latlong_set) latlong[0] = 4 * capture_face, latlong[1] = 2 * capture_face;
+    if (brdf != !brdf_out.empty() || (brdf_noded && !brdf)) {
+        std::cerr << "--brdf-table NMU,NROUGH and --brdf-out FILE go together; --brdf-nodes goes with them\n";
+        return 2;
+    }
+    if (brdf && (capture || probes || pick || ao_samples || adaptive || turntable_frames)) {
+        std::cerr << "--brdf-table excludes --capture, --probes, --pick, --ao, --adaptive and --turntable\n";
+        return 2;
+    }
     if (display && pick) {
         std::cerr << "the display options exclude --pick\n";
         return 2;
@@ -511,6 +545,22 @@ int main(int argc, char** argv) {
     const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);
     RenderBuffer buffer(W, H);
     Renderer renderer(devices);
+    if (brdf) {
+        const std::vector<rtr_brdf_entry> table = renderer.brdf_table(brdf_dims[0], brdf_dims[1], brdf_nodes);
+        if (table.size() != (size_t)brdf_dims[0] * brdf_dims[1]) {
+            std::cerr << "brdf table failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        std::FILE* f = std::fopen(brdf_out.c_str(), "wb");
+        const bool ok = f && std::fwrite(table.data(), sizeof(rtr_brdf_entry), table.size(), f) == table.size();
+        if (!(f && std::fclose(f) == 0 && ok)) {
+            std::cerr << "cannot write " << brdf_out << "\n";
+            return 1;
+        }
+        std::cout << "brdf table: " << brdf_dims[1] << " x " << brdf_dims[0] << " entries, " << brdf_nodes << " nodes per axis -> "
+                  << brdf_out << "\n";
+        return 0;
+    }
     if (pick) {
         if (pick_i < 0 || pick_i >= W || pick_j < 0 || pick_j >= H) {
             std::cerr << "--pick: pixel outside the " << W << " x " << H << " image\n";

@@ -614,6 +614,39 @@ class Renderer {
         return out;
     }
 
+    /* Image-based shading (include/rtr_hip.h: rtr_brdf_table, rtr_shade_ibl), on the first context; no scene is needed.
+     * brdf_table: the environment BRDF table of the split sum, n_rough * n_mu records, row = roughness.  shade_points: the
+     * radiance every query sends to its viewer under `env`, whose pointers are host arrays (those of a part that is not
+     * selected may be NULL).  An empty vector and last_status() / last_error() on failure. */
+    std::vector<rtr_brdf_entry> brdf_table(int n_mu, int n_rough, int nodes = 128) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        else if (n_mu < 1 || n_mu > 256 || n_rough < 1 || n_rough > 256) m_error = "n_mu or n_rough outside 1 .. 256", m_status = RTR_ERR_INVALID;
+        std::vector<rtr_brdf_entry> out;
+        if (m_status == RTR_OK) {
+            out.resize((size_t)n_mu * n_rough);
+            rtr_brdf_params bp{};
+            bp.n_mu = n_mu, bp.n_rough = n_rough, bp.nodes = nodes;
+            if ((m_status = rtr_brdf_table(m_ctx[0], &bp, out.data()))) m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+    std::vector<rtr_gather_out> shade_points(const rtr_shade_env& env, const std::vector<rtr_shade_query>& queries) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        std::vector<rtr_gather_out> out;
+        if (m_status == RTR_OK) {
+            out.resize(queries.size());
+            if ((m_status = rtr_shade_ibl(m_ctx[0], &env, queries.data(), out.data(), (int64_t)queries.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+
     /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
      * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
      * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */

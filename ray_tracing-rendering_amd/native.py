@@ -40,7 +40,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_cube_filter_one", "rtr_cube_chain_plan", "rtr_cube_chain_lookup", "rtr_cube_chain_lookup_device",
            "rtr_cube_chain_lookup_one", "rtr_probe_depth_defaults", "rtr_probe_depth", "rtr_probe_depth_device",
            "rtr_probe_depth_ray", "rtr_octa_encode", "rtr_octa_decode", "rtr_probe_lookup_visible",
-           "rtr_probe_lookup_visible_device", "rtr_probe_lookup_visible_one")
+           "rtr_probe_lookup_visible_device", "rtr_probe_lookup_visible_one", "rtr_brdf_table", "rtr_brdf_table_device",
+           "rtr_brdf_entry_one", "rtr_brdf_fetch_one", "rtr_shade_ibl", "rtr_shade_ibl_device", "rtr_shade_ibl_one")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
@@ -251,6 +252,13 @@ def lib():
     L.rtr_cube_chain_lookup.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64]
     L.rtr_cube_chain_lookup_device.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, C.c_int]
     L.rtr_cube_chain_lookup_one.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.rtr_brdf_table.argtypes = [vp, P(A.BrdfParamsC), vp]
+    L.rtr_brdf_table_device.argtypes = [vp, P(A.BrdfParamsC), vp, C.c_int]
+    L.rtr_brdf_entry_one.argtypes = [P(A.BrdfParamsC), C.c_int32, C.c_int32, vp]
+    L.rtr_brdf_fetch_one.argtypes = [C.c_int32, C.c_int32, vp, C.c_double, C.c_double, vp]
+    L.rtr_shade_ibl.argtypes = [vp, P(A.ShadeEnvC), vp, vp, C.c_int64]
+    L.rtr_shade_ibl_device.argtypes = [vp, P(A.ShadeEnvC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_shade_ibl_one.argtypes = [P(A.ShadeEnvC), vp, vp]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -858,6 +866,114 @@ def cube_chain_lookup_host(levels, texels, queries, n_levels=None):
     return out
 
 
+def brdf_params(n_mu, n_rough, nodes=128):
+    """An rtr_brdf_params"""
+    bp = A.BrdfParamsC()
+    bp.n_mu, bp.n_rough, bp.nodes = int(n_mu), int(n_rough), int(nodes)
+    return bp
+
+
+def brdf_table_host(n_mu, n_rough, nodes=128, params=None):
+    """rtr_brdf_entry_one for every entry (host only, no context; a loop for tests): ``BRDF_ENTRY_DTYPE`` [n_rough, n_mu]."""
+    bp = params if params is not None else brdf_params(n_mu, n_rough, nodes)
+    if not (1 <= bp.n_mu <= A.BRDF_MAX and 1 <= bp.n_rough <= A.BRDF_MAX):
+        raise RtrError(A.RTR_ERR_INVALID, "rtr_brdf_entry_one: n_mu or n_rough outside 1 .. 256")
+    out = np.zeros((bp.n_rough, bp.n_mu), dtype=A.BRDF_ENTRY_DTYPE)
+    L = lib()
+    for r in range(bp.n_rough):
+        for c in range(bp.n_mu):
+            rc = L.rtr_brdf_entry_one(C.byref(bp), r, c, out.ctypes.data + 16 * (r * bp.n_mu + c))
+            if rc != 0:
+                raise RtrError(rc, "rtr_brdf_entry_one: bad params")
+    return out
+
+
+def brdf_fetch_one(table, mu, rough):
+    """rtr_brdf_fetch_one: (a, b) of the bilinear fetch at (mu, rough) in ``table`` (``BRDF_ENTRY_DTYPE`` [n_rough, n_mu])."""
+    t = np.ascontiguousarray(table, dtype=A.BRDF_ENTRY_DTYPE)
+    if t.ndim != 2:
+        raise ValueError("table must be [n_rough, n_mu]")
+    out = np.zeros(1, dtype=A.BRDF_ENTRY_DTYPE)
+    rc = lib().rtr_brdf_fetch_one(t.shape[1], t.shape[0], t.ctypes.data, float(mu), float(rough), out.ctypes.data)
+    if rc != 0:
+        raise RtrError(rc, "rtr_brdf_fetch_one: a table axis outside 1 .. 256 or a non-finite coordinate")
+    return float(out["a"][0]), float(out["b"][0])
+
+
+def shade_queries(points, normals, views, base, roughness, metallic):
+    """A ``SHADE_QUERY_DTYPE`` array from (n, 3) points, normals, view vectors and base colours (or one colour) and
+    roughness / metallic (numbers or [n])"""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    q = np.zeros(len(p), dtype=A.SHADE_QUERY_DTYPE)
+    q["p"], q["n"], q["v"], q["base"] = p, normals, views, base
+    q["roughness"], q["metallic"] = roughness, metallic
+    return q
+
+
+def _address(x, dtype):
+    """(address, object to keep alive, records) of an array member of a shade environment: a device pointer given as an
+    int, or host records"""
+    if x is None:
+        return None, None, 0
+    if isinstance(x, (int, np.integer)):
+        return int(x), None, None
+    a = np.ascontiguousarray(x, dtype=dtype)
+    return a.ctypes.data, a, a.size
+
+
+def shade_env(table, grid=None, probes=None, depth=None, visible=None, levels=None, chain=None, parts=None, n_records=None,
+              n_mu=None, n_rough=None, n_levels=None):
+    """An rtr_shade_env.  ``table``, ``probes``, ``depth`` and ``chain`` are host records (numpy; the table
+    [n_rough, n_mu]) or device pointers (ints; then ``n_mu`` / ``n_rough`` / ``n_records`` say how many); ``grid`` an
+    rtr_probe_grid, ``visible`` an rtr_probe_visible_params (with ``depth``) or None, ``levels`` what ``cube_levels``
+    takes.  ``parts`` defaults to the parts whose arrays are given.  The struct keeps what it points to alive."""
+    e = A.ShadeEnvC()
+    keep = []
+    if parts is None:
+        parts = (A.SHADE_DIFFUSE if probes is not None else 0) | (A.SHADE_SPECULAR if chain is not None else 0)
+    e.parts = int(parts)
+    if not isinstance(table, (int, np.integer)) and table is not None:
+        t = np.ascontiguousarray(table, dtype=A.BRDF_ENTRY_DTYPE)
+        if t.ndim == 2:
+            n_rough, n_mu = (t.shape[0] if n_rough is None else n_rough), (t.shape[1] if n_mu is None else n_mu)
+        table = t
+    e.table, k, _ = _address(table, A.BRDF_ENTRY_DTYPE)
+    keep.append(k)
+    e.n_mu, e.n_rough = int(n_mu or 0), int(n_rough or 0)
+    if grid is not None:
+        keep.append(grid)
+        e.grid = C.addressof(grid)
+    e.probes, k, _ = _address(probes, A.PROBE_SH_DTYPE)
+    keep.append(k)
+    e.depth, k, _ = _address(depth, A.PROBE_DEPTH_DTYPE)
+    keep.append(k)
+    if visible is not None:
+        keep.append(visible)
+        e.visible = C.addressof(visible)
+    if levels is not None:
+        lv = cube_levels(levels)
+        keep.append(lv)
+        e.levels, e.n_levels = C.addressof(lv), len(levels) if n_levels is None else int(n_levels)
+    e.chain, k, records = _address(chain, A.GATHER_OUT_DTYPE)
+    keep.append(k)
+    e.n_records = int(n_records) if n_records is not None else int(records or 0)
+    e._keep = keep
+    return e
+
+
+def shade_ibl_one(env, queries):
+    """rtr_shade_ibl_one for every query (``SHADE_QUERY_DTYPE``; host only, no context) under a ``shade_env`` of host
+    arrays: a ``GATHER_OUT_DTYPE`` array.  Raises RtrError for a bad environment or a bad query."""
+    q = np.ascontiguousarray(queries, dtype=A.SHADE_QUERY_DTYPE).reshape(-1)
+    out = np.zeros(len(q), dtype=A.GATHER_OUT_DTYPE)
+    L = lib()
+    for k in range(len(q)):
+        rc = L.rtr_shade_ibl_one(C.byref(env), q.ctypes.data + 112 * k, out.ctypes.data + 32 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_shade_ibl_one: bad environment, or bad query at index %d" % k)
+    return out
+
+
 def srgb_thresholds():
     """rtr_display_srgb_thresholds: the 256 doubles S that define RTR_ENCODE_SRGB (code = how many of S[1..255] are <= t)."""
     out = np.zeros(256, dtype=np.float64)
@@ -1315,6 +1431,34 @@ class Context:
         self._chk(self._L.rtr_cube_chain_lookup_device(self._h, C.byref(lv), len(levels) if n_levels is None else int(n_levels),
                                                        C.c_void_p(texels_ptr), int(n_records),
                                                        *_into_tail(queries_ptr, out_ptr, n, blocking)))
+
+    # image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*)
+    def brdf_table(self, n_mu, n_rough, nodes=128, params=None, out=None):
+        """rtr_brdf_table: the environment BRDF table, ``BRDF_ENTRY_DTYPE`` [n_rough, n_mu].  Blocking; needs no scene."""
+        bp = params if params is not None else brdf_params(n_mu, n_rough, nodes)
+        n = max(int(bp.n_mu), 0) * max(int(bp.n_rough), 0)
+        flat = _records_out(None if out is None else out.reshape(-1), n, A.BRDF_ENTRY_DTYPE)
+        self._chk(self._L.rtr_brdf_table(self._h, C.byref(bp), flat.ctypes.data))
+        return flat[:n].reshape(int(bp.n_rough), int(bp.n_mu))
+
+    def brdf_table_into(self, out_ptr, n_mu, n_rough, nodes=128, params=None, blocking=False):
+        """rtr_brdf_table_device: n_rough * n_mu ``BRDF_ENTRY_DTYPE`` records at device pointer ``out_ptr``, on the context
+        stream behind what is queued there."""
+        bp = params if params is not None else brdf_params(n_mu, n_rough, nodes)
+        self._chk(self._L.rtr_brdf_table_device(self._h, C.byref(bp), C.c_void_p(out_ptr), 1 if blocking else 0))
+
+    def shade_ibl(self, env, queries, out=None):
+        """rtr_shade_ibl: the radiance of the ``SHADE_QUERY_DTYPE`` queries under ``env`` (``native.shade_env`` of host
+        arrays), a ``GATHER_OUT_DTYPE`` array.  Blocking; needs no scene; raises RtrError naming the first bad query."""
+        q = np.ascontiguousarray(queries, dtype=A.SHADE_QUERY_DTYPE).reshape(-1)
+        out = _records_out(out, len(q), A.GATHER_OUT_DTYPE)
+        self._chk(self._L.rtr_shade_ibl(self._h, C.byref(env), q.ctypes.data, out.ctypes.data, len(q)))
+        return out
+
+    def shade_ibl_into(self, env, queries_ptr, out_ptr, n, blocking=False):
+        """rtr_shade_ibl_device: the same over device pointers (``env``: ``native.shade_env`` of device pointers; the
+        struct, its grid, visible params and levels stay on the host), on the context stream behind what is queued there."""
+        self._chk(self._L.rtr_shade_ibl_device(self._h, C.byref(env), *_into_tail(queries_ptr, out_ptr, n, blocking)))
 
     # display transform (include/rtr_hip.h: rtr_display_*)
     @staticmethod

@@ -544,6 +544,65 @@ class CubeChain:
         return paths
 
 
+class BrdfTable:
+    """The environment BRDF table of the split-sum approximation (include/rtr_hip.h: rtr_brdf_table): ``entries``,
+    ``BRDF_ENTRY_DTYPE`` [n_rough, n_mu]; int f_spec cos dw ~ F0 * a + b at (mu, roughness)."""
+
+    def __init__(self, entries):
+        t = np.ascontiguousarray(entries, dtype=A.BRDF_ENTRY_DTYPE)
+        if t.ndim != 2 or not (1 <= t.shape[0] <= A.BRDF_MAX and 1 <= t.shape[1] <= A.BRDF_MAX):
+            raise ValueError("entries must be [n_rough, n_mu] records, 1 .. %d each" % A.BRDF_MAX)
+        self.entries = t
+
+    @classmethod
+    def make(cls, n_mu=32, n_rough=32, nodes=128, ctx=None):
+        """rtr_brdf_table on ``ctx``; without one the host loop of rtr_brdf_entry_one (for small tables)."""
+        from . import native
+        return cls(ctx.brdf_table(n_mu, n_rough, nodes) if ctx is not None else native.brdf_table_host(n_mu, n_rough, nodes))
+
+    def fetch(self, mu, rough):
+        """(a, b) of rtr_brdf_fetch_one at (mu, rough)"""
+        from . import native
+        return native.brdf_fetch_one(self.entries, mu, rough)
+
+
+class IblEnvironment:
+    """What rtr_shade_ibl shades under: a ``ProbeGrid`` (diffuse; its distance maps select the visible lookup), a
+    ``CubeChain`` (specular) and a ``BrdfTable``.  ``grid`` or ``chain`` may be None: that part is left out."""
+
+    def __init__(self, grid, chain, table, normal_bias=None):
+        if grid is None and chain is None:
+            raise ValueError("an environment needs a grid, a chain or both")
+        self.grid, self.chain, self.table = grid, chain, table
+        self.normal_bias = normal_bias
+
+    def env(self):
+        """The rtr_shade_env over the host arrays"""
+        from . import native
+        kw = {}
+        if self.grid is not None:
+            kw.update(grid=self.grid.grid(), probes=self.grid.coefficients)
+            if self.grid.depth is not None:
+                bias = float(self.normal_bias) if self.normal_bias is not None else 0.25 * float(self.grid.spacing.min())
+                kw.update(depth=self.grid.depth, visible=native.probe_visible_params(self.grid.depth.shape[-1], bias))
+        if self.chain is not None:
+            kw.update(levels=self.chain.levels, chain=self.chain.records)
+        return native.shade_env(self.table.entries, **kw)
+
+    def shade_records(self, points, normals, views, base, roughness, metallic, ctx=None):
+        """The ``GATHER_OUT_DTYPE`` records of rtr_shade_ibl; ``ctx``: the context that runs it (default: the grid's
+        baking context, else the host loop of rtr_shade_ibl_one)."""
+        from . import native
+        q = native.shade_queries(points, normals, views, base, roughness, metallic)
+        ctx = ctx if ctx is not None else (self.grid._ctx if self.grid is not None else None)
+        return ctx.shade_ibl(self.env(), q) if ctx is not None else native.shade_ibl_one(self.env(), q)
+
+    def shade(self, points, normals, views, base, roughness, metallic, ctx=None):
+        """[n, 3] radiance towards the viewers: points, normals and view vectors [n, 3], base colour [n, 3] or one colour,
+        roughness and metallic numbers or [n]; zero where a lookup is invalid."""
+        return self.shade_records(points, normals, views, base, roughness, metallic, ctx)["v"]
+
+
 def check_denoise(params):
     """ValueError unless ``params`` is None or valid rtr_denoise_params (the checks of rtr_accum_denoise)."""
     import math
