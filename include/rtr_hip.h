@@ -1428,6 +1428,84 @@ int rtr_shade_ibl_device(rtr_context* ctx, const rtr_shade_env* env, const rtr_s
  * environment, a NULL pointer or a BAD query. */
 int rtr_shade_ibl_one(const rtr_shade_env* env, const rtr_shade_query* query, rtr_gather_out* out);
 
+/* ---- baked previews: a frame of the uploaded scene shaded from a probe grid, a cube chain and a table ----
+ * One launch per frame: every pixel casts k * k camera rays to their closest hit, turns each hit into an rtr_shade_query by
+ * its material and adds rtr_shade_ibl of it; rays and queries never visit memory.  What an interactive viewer of a baked
+ * scene shows while the path tracer converges.  FP64 throughout with + - * / sqrt and compares only, no fused
+ * multiply-add, plain IEEE divisions for everything stated here (the casts inside use whatever a render of the scene uses):
+ * a host, numpy and the device give the same bits.
+ *
+ * RAY: sample s (0 <= s < k * k) of pixel (i, j) of a W x H image, with a = s % k and b = s / k (b is the outer loop):
+ *   u = (i + (a + 0.5) / k) / (W - 1),   v = (j + (b + 0.5) / k) / (H - 1)            (i, j, a, b, k, W - 1, H - 1 as doubles)
+ *   origin = the camera's origin,  d = ((lower_left_corner + u * horizontal) + v * vertical) - origin per component
+ *   (renderer/camera.h:32-40 without the lens offset),  time = time0,  t_min from the params,  t_max = +inf.
+ * No lens offset and no draw: the picture is that of a pinhole at the lens centre.  For k = 1 these are the pixel-centre
+ * rays of rtr_cli --pick.
+ *
+ * SAMPLE: the ray is cast to its closest hit with the traversal a render with `flags` walks (rtr_query_closest of it).
+ *   miss:  kind = MISS, material = -1; direct = what Integrator::Li of RTR_INTEGRATOR_MIS returns for a camera ray that
+ *     leaves the scene (rtr_li_rays of it): the sum of the environment lights' Le, or else the background.
+ *   a diffuse_light:  kind = EMITTER; direct = the value of tex[0] at the hit on a front face, (0, 0, 0) on a back face.
+ *   any other material:  kind = SURFACE;  q.p = the hit's p,  q.n = the hit record's normal (no normal map is applied, as
+ *     for the feature buffers),  q.v = (-d.x, -d.y, -d.z), and by material
+ *       lambertian   base = tex[0] at the hit   roughness = 1.0              metallic = 0.0
+ *       metal        base = f[0..2]             roughness = f[3] (fuzz)      metallic = 1.0
+ *       dielectric   base = (1, 1, 1)           roughness = 0.0              metallic = 1.0
+ *       PBR          base = tex[0] at the hit   roughness = tex[1] at the hit (as it is: the shader clamps it)
+ *                                               metallic = tex[2] at the hit
+ *     A dielectric is a mirror of the environment: there is no refraction in a preview, a stated limit.
+ *   Members not named are 0: q of a MISS or EMITTER sample, direct of a SURFACE sample.
+ *
+ * PIXEL: s = 0 .. k * k - 1 in order, acc from +0.0 per channel.  A MISS or EMITTER sample adds `direct`; a SURFACE sample
+ * adds rtr_shade_ibl_one(env, q).v when that record is valid and nothing otherwise (a point outside the grid, invalid
+ * probes or texels, a BAD query such as a zero normal).  linear = (1.0 / (k * k)) * acc per channel, like the resolve of a
+ * render; lit = the number of samples that added something (every MISS and EMITTER sample, every valid SURFACE sample).
+ *
+ * Layouts: rtr_preview_samples writes record ((j - y0) * (x1 - x0) + (i - x0)) * k * k + s.  The frame entries write
+ * linear[((j - y0) * row_stride + (i - x0)) * 3 + c] -- the layout of rtr_accum_resolve_device, so rtr_display_device may
+ * follow with no host wait -- and, unless lit is NULL, lit[(j - y0) * row_stride + (i - x0)]; only region pixels are written.
+ *
+ * Checks, all before any device work and with the outputs untouched, context first: RTR_ERR_INVALID for a NULL pointer, W
+ * or H below 2, an empty region or one outside the image, grid outside 1 .. 8, a flag bit other than
+ * RTR_FLAG_REFERENCE_ORDER, a t_min that is not finite or below 2^-100, non-zero reserved; RTR_ERR_NO_SCENE before an
+ * upload; RTR_ERR_UNSUPPORTED for a scene with media (isotropic materials: their free paths need the path's generator).
+ * The frame entries check env with the rules of rtr_shade_ibl, and row_stride below the region's width is
+ * RTR_ERR_INVALID.  The device entries want linear, the samples and the environment's arrays 8-byte aligned and lit 4-byte
+ * aligned, and no output may overlap an array of the environment or the other output: RTR_ERR_INVALID.
+ * The entries use the context's current camera (rtr_set_camera applies); rtr_cancel and rtr_get_stats do not apply.
+ * rtr_preview takes the environment's arrays as HOST arrays, staged like those of rtr_shade_ibl, and blocks;
+ * rtr_preview_device takes them as DEVICE arrays, runs on the context stream behind whatever is queued there -- the bakes
+ * included -- and returns at once unless `blocking`.  The samples entries need no environment. */
+typedef struct rtr_preview_params {   /* 64 bytes */
+    int32_t image_width, image_height;  /* W, H >= 2 */
+    int32_t x0, y0, x1, y1;             /* region, as in rtr_render_params */
+    int32_t grid;                       /* k in 1 .. 8: k * k rays per pixel */
+    int32_t flags;                      /* 0 or RTR_FLAG_REFERENCE_ORDER */
+    double t_min;                       /* finite, >= 2^-100; default 0.001 */
+    double reserved[3];                 /* must be 0 */
+} rtr_preview_params;
+#define RTR_PREVIEW_MISS 0
+#define RTR_PREVIEW_EMITTER 1
+#define RTR_PREVIEW_SURFACE 2
+typedef struct rtr_preview_sample {   /* 144 bytes */
+    rtr_shade_query q;                  /* all 0 unless kind == RTR_PREVIEW_SURFACE */
+    double direct[3];                   /* the value of a MISS / EMITTER sample, else 0 */
+    int32_t kind, material;             /* RTR_PREVIEW_*; material = -1 on a miss */
+} rtr_preview_sample;
+
+/* grid 1, t_min 0.001, everything else 0: the caller sets the image size and the region */
+void rtr_preview_defaults(rtr_preview_params* params);
+/* Host-only, needs no context: RAY of sample s of pixel (i, j), the function the kernel calls; rng_state is 1.
+ * RTR_ERR_INVALID for a NULL pointer, bad params, a pixel outside the image or s outside [0, k * k). */
+int rtr_preview_ray(const rtr_camera* camera, const rtr_preview_params* params, int32_t i, int32_t j, int32_t s, rtr_ray* out);
+/* the G-buffer, for callers who shade themselves */
+int rtr_preview_samples(rtr_context* ctx, const rtr_preview_params* params, rtr_preview_sample* out);
+int rtr_preview_samples_device(rtr_context* ctx, const rtr_preview_params* params, rtr_preview_sample* d_out, int blocking);
+int rtr_preview(rtr_context* ctx, const rtr_preview_params* params, const rtr_shade_env* env, double* h_linear,
+                int64_t row_stride, int32_t* h_lit);
+int rtr_preview_device(rtr_context* ctx, const rtr_preview_params* params, const rtr_shade_env* env, double* d_linear,
+                       int64_t row_stride, int32_t* d_lit, int blocking);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

@@ -222,6 +222,22 @@ BRDF_MAX = 256
 SHADE_DIFFUSE, SHADE_SPECULAR = 1, 2
 
 
+class PreviewParamsC(C.Structure):
+    """rtr_preview_params (include/rtr_hip.h): a frame shaded from a bake, rtr_preview / rtr_preview_samples"""
+    _fields_ = [("image_width", C.c_int32), ("image_height", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("x1", C.c_int32), ("y1", C.c_int32), ("grid", C.c_int32), ("flags", C.c_int32), ("t_min", C.c_double),
+                ("reserved", C.c_double * 3)]
+
+
+PREVIEW_PARAMS_SIZE = 64
+assert C.sizeof(PreviewParamsC) == PREVIEW_PARAMS_SIZE
+PREVIEW_SAMPLE_DTYPE = np.dtype([("q", SHADE_QUERY_DTYPE), ("direct", "<f8", (3,)), ("kind", "<i4"),
+                                 ("material", "<i4")])  # rtr_preview_sample
+assert PREVIEW_SAMPLE_DTYPE.itemsize == 144
+PREVIEW_MISS, PREVIEW_EMITTER, PREVIEW_SURFACE = 0, 1, 2
+PREVIEW_MAX_GRID = 8
+
+
 class DenoiseParamsC(C.Structure):
     """rtr_denoise_params (include/rtr_hip.h): the a-trous denoiser of rtr_accum_denoise / rtr_denoise_host"""
     _fields_ = [("iterations", C.c_int32), ("feature_spp", C.c_int32), ("sigma_l", C.c_double),

@@ -53,7 +53,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 HIP_UNITS = [("mega_mis", "rtr_mega.hip", ["-DRTR_MEGA_GROUP=0"]), ("mega_rr_path", "rtr_mega.hip", ["-DRTR_MEGA_GROUP=1"]),
              ("mega_pbr_nee", "rtr_mega.hip", ["-DRTR_MEGA_GROUP=2"]), ("capi", "rtr_capi.hip", []), ("gather", "rtr_gather.hip", []),
              ("probe", "rtr_probe.hip", []), ("probe_depth", "rtr_probe_depth.hip", []),
-             ("capture", "rtr_capture.hip", []), ("cube", "rtr_cube.hip", []), ("ibl", "rtr_ibl.hip", []),
+             ("capture", "rtr_capture.hip", []), ("cube", "rtr_cube.hip", []), ("ibl", "rtr_ibl.hip", []), ("preview", "rtr_preview.hip", []),
              ("wavefront", "rtr_wavefront.hip", []), ("query", "rtr_query.hip", []), ("accum", "rtr_accum.hip", []),
              ("image", "rtr_image.hip", []), ("test", "rtr_test.hip", [])]
 

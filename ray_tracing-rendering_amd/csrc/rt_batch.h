@@ -1,6 +1,6 @@
 /*
  * rt_batch.h -- host only: what the units that answer a batch of caller records share (rtr_query.hip, rtr_gather.hip,
- * rtr_probe.hip, rtr_probe_depth.hip, rtr_capture.hip, rtr_cube.hip, rtr_ibl.hip).  The entry checks they have in common, the one path of a host entry from the caller's array to the
+ * rtr_probe.hip, rtr_probe_depth.hip, rtr_capture.hip, rtr_cube.hip, rtr_ibl.hip, rtr_preview.hip).  The entry checks they have in common, the one path of a host entry from the caller's array to the
  * kernel and back (staged_slices), the body of a device-pointer entry (device_entry), and for the gathers and probes the
  * launch set-up, the chunked launcher and the single-ray entry.  No device code; the kernels and which one a call runs
  * stay with the units.

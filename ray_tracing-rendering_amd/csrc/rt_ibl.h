@@ -1,7 +1,8 @@
 /*
  * rt_ibl.h -- image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*): the arithmetic of that contract, written
- * once for host (the _one forms, the entries' checks) and device, and the two kernels, instantiated and launched by
- * rtr_ibl.hip.  The lookups the shader composes are rt_render.h's: nothing of them is restated here.
+ * once for host (the _one forms, the entries' checks) and device, and the host-side rules of an rtr_shade_env.  The two
+ * kernels are rt_ibl_kernels.h's; rtr_preview.hip composes shade_ibl_one from here.  The lookups the shader composes are
+ * rt_render.h's: nothing of them is restated here.
  */
 #pragma once
 
@@ -170,60 +171,75 @@ RT_HD rtr_gather_out shade_ibl_one(const ShadeK& K, const rtr_shade_query& q, do
     return o;
 }
 
-/* rtr_brdf_table: a wave owns an entry: lane l carries the contract's lane l of its three sums in registers, and the
- * butterfly ends in one 16-byte store.  The four waves of a workgroup take four neighbouring entries of one row (blockIdx.y)
- * and share the parts of a node that do not depend on mu: thread i works out BrdfS of s_i for the row's roughness (a
- * division, three square roots) and BrdfT of t_i (two divisions) once, into LDS, one array per member (12 KiB; the lanes of
- * a wave read at most two neighbouring s and consecutive t: no bank conflict).  What is left per (node, entry) is
- * brdf_node: two divisions for a USED node. */
-struct TableK {
-    rtr_brdf_entry* out; /* out[0] is entry `out_first` of the table (r * n_mu + c) */
-    long long out_first;
-    int row0;            /* blockIdx.y = 0 serves this row */
-    int c0, c1;          /* the launch serves the columns [c0, c1) of each of its rows */
-    int n_mu, n_rough, M;
-};
-__global__ void __launch_bounds__(RTR_BLOCK) k_brdf_table(const TableK K) {
-    __shared__ double s_s[4][RTR_BRDF_MAX], s_t[2][RTR_BRDF_MAX];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = K.row0 + (int)blockIdx.y;
-    const BrdfRow R = brdf_row(r, K.n_rough);
-    if (tid < K.M) {
-        const BrdfS S = brdf_s(tid, K.M, R);
-        const BrdfT T = brdf_t(tid, K.M);
-        s_s[0][tid] = S.s, s_s[1][tid] = S.hz, s_s[2][tid] = S.sh, s_s[3][tid] = S.rden;
-        s_t[0][tid] = T.cx, s_t[1][tid] = T.wphi;
+/* ---- ENVIRONMENT: host side, what the entries of rtr_ibl.hip and rtr_preview.hip check and build alike ---- */
+
+/* the grid rule of rtr_probe_lookup */
+inline const char* shade_grid_why(const rtr_probe_grid* g) {
+    if (!g) return "null grid";
+    long long count = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!__builtin_isfinite(g->origin[a])) return "origin not finite";
+        if (!(__builtin_isfinite(g->spacing[a]) && g->spacing[a] > 0)) return "spacing must be finite and > 0";
+        if (g->dims[a] < 1 || g->dims[a] > (1 << 24)) return "dims must be >= 1 and their product <= 2^24";
+        count *= g->dims[a];
+        if (count > (1ll << 24)) return "dims must be >= 1 and their product <= 2^24";
     }
-    __syncthreads();
-    const int c = K.c0 + (int)blockIdx.x * (RTR_BLOCK / 64) + wave;
-    if (c >= K.c1) return;
-    const BrdfCol C = brdf_col(c, K.n_mu, R);
-    const int MM = K.M * K.M;
-    double W = 0.0, A = 0.0, B = 0.0;
-    for (int j = lane; j < 2 * MM; j += 64) {
-        const int jj = j < MM ? j : j - MM;
-        const int si = jj / K.M, ti = jj - si * K.M;
-        BrdfS S;
-        BrdfT T;
-        S.s = s_s[0][si], S.hz = s_s[1][si], S.sh = s_s[2][si], S.rden = s_s[3][si];
-        T.cx = s_t[0][ti], T.wphi = s_t[1][ti];
-        W = W + T.wphi * S.s;
-        brdf_node(R, C, S, T, j < MM ? 1.0 : -1.0, A, B);
+    if (g->pad != 0) return "pad must be 0";
+    return nullptr;
+}
+inline long long shade_grid_probes(const rtr_probe_grid* g) { return (long long)g->dims[0] * g->dims[1] * g->dims[2]; }
+
+/* why `env` is no environment, or nullptr: the rules of the lookups it names, for the selected parts only */
+inline const char* env_why(const rtr_shade_env* e) {
+    if (!e) return "null environment";
+    if (e->parts < 1 || e->parts > (RTR_SHADE_DIFFUSE | RTR_SHADE_SPECULAR)) return "parts must be RTR_SHADE_DIFFUSE, RTR_SHADE_SPECULAR or both";
+    if (e->n_mu < 1 || e->n_mu > RTR_BRDF_MAX || e->n_rough < 1 || e->n_rough > RTR_BRDF_MAX) return "table n_mu or n_rough outside 1 .. 256";
+    if (!e->table) return "null table";
+    if (e->parts & RTR_SHADE_DIFFUSE) {
+        if (const char* why = shade_grid_why(e->grid)) return why;
+        if (!e->probes) return "null probes";
+        if ((e->depth != nullptr) != (e->visible != nullptr)) return "depth and visible go together";
+        if (e->visible) {
+            if (const char* why = probe_visible_params_why(e->visible)) return why;
+            if (shade_grid_probes(e->grid) * e->visible->map_size * e->visible->map_size > (1ll << 24)) return "probes * map_size^2 must be <= 2^24";
+        }
     }
-    for (int off = 32; off > 0; off >>= 1)
-        W = W + __shfl_xor(W, off, 64), A = A + __shfl_xor(A, off, 64), B = B + __shfl_xor(B, off, 64);
-    if (lane == 0) K.out[(long long)r * K.n_mu + c - K.out_first] = brdf_result(W, A, B);
+    if (e->parts & RTR_SHADE_SPECULAR) {
+        if (e->n_records < 0) return "negative n_records";
+        if (const char* why = cube_chain_why(e->levels, e->n_levels, e->n_records)) return why;
+        if (!e->chain) return "null chain";
+    }
+    return nullptr;
 }
 
-/* rtr_shade_ibl: one lane per query, straight-line (shade_ibl_one) */
-__global__ void __launch_bounds__(RTR_BLOCK) k_shade_ibl(const ShadeK K, const rtr_shade_query* __restrict__ queries,
-                                                          rtr_gather_out* __restrict__ out, long long n) {
-    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
-    if (k >= n) return;
-    const rtr_shade_query q = queries[k];
-    double nlen, vlen;
-    rtr_gather_out o;
-    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
-    if (!shade_query_bad(q, nlen, vlen)) o = shade_ibl_one(K, q, nlen, vlen);
-    out[k] = o;
+/* bytes of the arrays of a valid environment: of a part that is not selected 0 */
+struct EnvBytes {
+    size_t probes, depth, chain, table;
+};
+inline EnvBytes env_bytes(const rtr_shade_env* e) {
+    EnvBytes b{0, 0, 0, (size_t)e->n_mu * e->n_rough * sizeof(rtr_brdf_entry)};
+    if (e->parts & RTR_SHADE_DIFFUSE) {
+        b.probes = (size_t)shade_grid_probes(e->grid) * sizeof(rtr_probe_sh);
+        if (e->visible) b.depth = (size_t)shade_grid_probes(e->grid) * e->visible->map_size * e->visible->map_size * sizeof(rtr_probe_depth_texel);
+    }
+    if (e->parts & RTR_SHADE_SPECULAR) b.chain = (size_t)e->n_records * sizeof(rtr_gather_out);
+    return b;
+}
+/* the kernel's argument of a valid environment whose arrays are at these addresses */
+inline ShadeK shade_k(const rtr_shade_env* e, const void* probes, const void* depth, const void* chain, const void* table) {
+    ShadeK K{};
+    K.parts = e->parts;
+    if (e->parts & RTR_SHADE_DIFFUSE) {
+        K.grid = *e->grid, K.probes = static_cast<const rtr_probe_sh*>(probes);
+        if (e->visible) {
+            K.visible = 1, K.depth = static_cast<const rtr_probe_depth_texel*>(depth);
+            K.T = e->visible->map_size, K.normal_bias = e->visible->normal_bias;
+        }
+    }
+    if (e->parts & RTR_SHADE_SPECULAR) {
+        for (int i = 0; i < e->n_levels; ++i) K.chain.lv[i] = e->levels[i];
+        K.chain.n = e->n_levels, K.texels = static_cast<const rtr_gather_out*>(chain);
+    }
+    K.n_mu = e->n_mu, K.n_rough = e->n_rough, K.table = static_cast<const rtr_brdf_entry*>(table);
+    return K;
 }

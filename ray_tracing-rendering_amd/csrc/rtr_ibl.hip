@@ -1,12 +1,12 @@
 /*
  * rtr_ibl.hip -- image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*): the parameter and environment checks,
- * the split of a table call into launches of bounded work, the two kernels of rt_ibl.h and their launches, the entries, and
+ * the split of a table call into launches of bounded work, the two kernels of rt_ibl_kernels.h and their launches, the entries, and
  * the host-only pieces that need no context (rtr_brdf_entry_one, rtr_brdf_fetch_one, rtr_shade_ibl_one).  The entries'
  * common checks, the staging of the host entries and the body of the device entries are rt_batch.h's, shared with the
  * gathers, probes, captures and cube maps.
  */
 #include "rt_batch.h"
-#include "rt_ibl.h"
+#include "rt_ibl_kernels.h"
 
 #include <cstdlib>
 
@@ -56,77 +56,6 @@ int table_launch(rtr_context* c, const rtr_brdf_params* bp, rtr_brdf_entry* d_ou
     }
     const hipError_t err = hipGetLastError();
     return err == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("brdf table launch: ") + hipGetErrorString(err));
-}
-
-/* the grid rule of rtr_probe_lookup */
-const char* grid_why(const rtr_probe_grid* g) {
-    if (!g) return "null grid";
-    long long count = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (!__builtin_isfinite(g->origin[a])) return "origin not finite";
-        if (!(__builtin_isfinite(g->spacing[a]) && g->spacing[a] > 0)) return "spacing must be finite and > 0";
-        if (g->dims[a] < 1 || g->dims[a] > (1 << 24)) return "dims must be >= 1 and their product <= 2^24";
-        count *= g->dims[a];
-        if (count > (1ll << 24)) return "dims must be >= 1 and their product <= 2^24";
-    }
-    if (g->pad != 0) return "pad must be 0";
-    return nullptr;
-}
-long long grid_probes(const rtr_probe_grid* g) { return (long long)g->dims[0] * g->dims[1] * g->dims[2]; }
-
-/* why `env` is no environment, or nullptr: the rules of the lookups it names, for the selected parts only */
-const char* env_why(const rtr_shade_env* e) {
-    if (!e) return "null environment";
-    if (e->parts < 1 || e->parts > (RTR_SHADE_DIFFUSE | RTR_SHADE_SPECULAR)) return "parts must be RTR_SHADE_DIFFUSE, RTR_SHADE_SPECULAR or both";
-    if (e->n_mu < 1 || e->n_mu > RTR_BRDF_MAX || e->n_rough < 1 || e->n_rough > RTR_BRDF_MAX) return "table n_mu or n_rough outside 1 .. 256";
-    if (!e->table) return "null table";
-    if (e->parts & RTR_SHADE_DIFFUSE) {
-        if (const char* why = grid_why(e->grid)) return why;
-        if (!e->probes) return "null probes";
-        if ((e->depth != nullptr) != (e->visible != nullptr)) return "depth and visible go together";
-        if (e->visible) {
-            if (const char* why = probe_visible_params_why(e->visible)) return why;
-            if (grid_probes(e->grid) * e->visible->map_size * e->visible->map_size > (1ll << 24)) return "probes * map_size^2 must be <= 2^24";
-        }
-    }
-    if (e->parts & RTR_SHADE_SPECULAR) {
-        if (e->n_records < 0) return "negative n_records";
-        if (const char* why = cube_chain_why(e->levels, e->n_levels, e->n_records)) return why;
-        if (!e->chain) return "null chain";
-    }
-    return nullptr;
-}
-
-/* bytes of the arrays of a valid environment: of a part that is not selected 0 */
-struct EnvBytes {
-    size_t probes, depth, chain, table;
-};
-EnvBytes env_bytes(const rtr_shade_env* e) {
-    EnvBytes b{0, 0, 0, (size_t)e->n_mu * e->n_rough * sizeof(rtr_brdf_entry)};
-    if (e->parts & RTR_SHADE_DIFFUSE) {
-        b.probes = (size_t)grid_probes(e->grid) * sizeof(rtr_probe_sh);
-        if (e->visible) b.depth = (size_t)grid_probes(e->grid) * e->visible->map_size * e->visible->map_size * sizeof(rtr_probe_depth_texel);
-    }
-    if (e->parts & RTR_SHADE_SPECULAR) b.chain = (size_t)e->n_records * sizeof(rtr_gather_out);
-    return b;
-}
-/* the kernel's argument of a valid environment whose arrays are at these addresses */
-ShadeK shade_k(const rtr_shade_env* e, const void* probes, const void* depth, const void* chain, const void* table) {
-    ShadeK K{};
-    K.parts = e->parts;
-    if (e->parts & RTR_SHADE_DIFFUSE) {
-        K.grid = *e->grid, K.probes = static_cast<const rtr_probe_sh*>(probes);
-        if (e->visible) {
-            K.visible = 1, K.depth = static_cast<const rtr_probe_depth_texel*>(depth);
-            K.T = e->visible->map_size, K.normal_bias = e->visible->normal_bias;
-        }
-    }
-    if (e->parts & RTR_SHADE_SPECULAR) {
-        for (int i = 0; i < e->n_levels; ++i) K.chain.lv[i] = e->levels[i];
-        K.chain.n = e->n_levels, K.texels = static_cast<const rtr_gather_out*>(chain);
-    }
-    K.n_mu = e->n_mu, K.n_rough = e->n_rough, K.table = static_cast<const rtr_brdf_entry*>(table);
-    return K;
 }
 
 /* what both shader entries check before any device work: context, environment, n / NULL; no scene is needed */

@@ -50,6 +50,13 @@
  *                                   (Renderer::brdf_table: NMU x NROUGH entries, 1..256 each, M = 1..256 quadrature nodes per
  *                                   axis, default 128); FILE receives little-endian doubles [n_rough][n_mu][2] = (a, b).
  *                                   Needs no scene and renders nothing; excludes every other mode
+ *           [--preview K]           the baked preview (Renderer::render_preview: K x K rays per pixel, 1..8) instead of a path
+ *                                   traced image.  Goes together with --probes NX,NY,NZ --probe-box ... [--probe-depth T],
+ *                                   --capture x,y,z --capture-levels L (L >= 1) and --brdf-table NMU,NROUGH: the three parts are
+ *                                   baked as those options say (nothing of them is printed or written: --capture-out,
+ *                                   --probe-depth-out and --brdf-out are not needed), the frame is shaded from them and stored
+ *                                   to --out like a render.  A missing part is an error.  Not with --pick, --ao, --adaptive,
+ *                                   --turntable
  *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
  *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
  *                                   rtr_display_host through Renderer::display; with --turntable rtr_display_device on
@@ -208,6 +215,7 @@ int main(int argc, char** argv) {
     int capture_face = 32, capture_spp = 16, latlong[2] = {0, 0}, capture_levels = 0;
     bool capture = false, capture_face_set = false, capture_spp_set = false, latlong_set = false;
     std::string capture_out;
+    int preview = 0; /* --preview K */
     std::vector<int> devices{0}, passes;
     unsigned seed = 1;
     std::string out;
@@ -342,6 +350,15 @@ int main(int argc, char** argv) {
             brdf_nodes = (int)v, brdf_noded = true;
         }
         else if (!std::strcmp(argv[k], "--brdf-out") && k + 1 < argc) brdf_out = argv[++k];
+        else if (!std::strcmp(argv[k], "--preview") && k + 1 < argc) {
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (end == argv[k] || *end != '\0' || v < 1 || v > 8) {
+                std::cerr << "--preview takes the rays per pixel axis K, an integer in 1..8, not " << argv[k] << "\n";
+                return 2;
+            }
+            preview = (int)v;
+        }
         else if (!std::strcmp(argv[k], "--capture-levels") && k + 1 < argc) {
             char* end = nullptr;
             const long v = std::strtol(argv[++k], &end, 10);
@@ -463,7 +480,24 @@ int main(int argc, char** argv) {
         std::cerr << "--probe-depth, --probe-depth-samples and --probe-depth-out go with --probes\n";
         return 2;
     }
-    if (probe_depth_set != !probe_depth_out.empty() || (probe_depth_sampled && !probe_depth_set)) {
+    if (preview) { /* the three parts of the bake go together here, and nothing of them is written */
+        const char* missing = !probes ? "--probes NX,NY,NZ --probe-box x0,y0,z0,x1,y1,z1 (the probe grid)"
+                              : !capture || capture_levels < 1 ? "--capture x,y,z --capture-levels L (the cube chain)"
+                              : !brdf ? "--brdf-table NMU,NROUGH (the table)" : nullptr;
+        if (missing) {
+            std::cerr << "--preview needs " << missing << "\n";
+            return 2;
+        }
+        if (pick || ao_samples || adaptive || turntable_frames) {
+            std::cerr << "--preview excludes --pick, --ao, --adaptive and --turntable\n";
+            return 2;
+        }
+        if (out.empty()) {
+            std::cerr << "--preview needs --out FILE\n";
+            return 2;
+        }
+    }
+    if (!preview && (probe_depth_set != !probe_depth_out.empty() || (probe_depth_sampled && !probe_depth_set))) {
         std::cerr << "--probe-depth T and --probe-depth-out FILE go together; --probe-depth-samples goes with them\n";
         return 2;
     }
@@ -485,20 +519,20 @@ int main(int argc, char** argv) {
         std::cerr << "--capture-levels above 1 needs --face of at most 512\n";
         return 2;
     }
-    if (capture && capture_out.empty()) {
+    if (capture && capture_out.empty() && !preview) {
         std::cerr << "--capture needs --capture-out file.hdr\n";
         return 2;
     }
-    if (capture && (probes || pick || ao_samples || adaptive || turntable_frames)) {
+    if (capture && ((probes && !preview) || pick || ao_samples || adaptive || turntable_frames)) {
         std::cerr << "--capture excludes --probes, --pick, --ao, --adaptive and --turntable\n";
         return 2;
     }
     if (capture && !latlong_set) latlong[0] = 4 * capture_face, latlong[1] = 2 * capture_face;
-    if (brdf != !brdf_out.empty() || (brdf_noded && !brdf)) {
+    if ((!preview && brdf != !brdf_out.empty()) || (brdf_noded && !brdf)) {
         std::cerr << "--brdf-table NMU,NROUGH and --brdf-out FILE go together; --brdf-nodes goes with them\n";
         return 2;
     }
-    if (brdf && (capture || probes || pick || ao_samples || adaptive || turntable_frames)) {
+    if (brdf && !preview && (capture || probes || pick || ao_samples || adaptive || turntable_frames)) {
         std::cerr << "--brdf-table excludes --capture, --probes, --pick, --ao, --adaptive and --turntable\n";
         return 2;
     }
@@ -545,7 +579,7 @@ int main(int argc, char** argv) {
     const int W = config.image_width, H = static_cast<int>(W / config.aspect_ratio);
     RenderBuffer buffer(W, H);
     Renderer renderer(devices);
-    if (brdf) {
+    if (brdf && !preview) {
         const std::vector<rtr_brdf_entry> table = renderer.brdf_table(brdf_dims[0], brdf_dims[1], brdf_nodes);
         if (table.size() != (size_t)brdf_dims[0] * brdf_dims[1]) {
             std::cerr << "brdf table failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
@@ -634,6 +668,65 @@ int main(int argc, char** argv) {
     renderer.set_max_depth(50); /* main.cpp:102 */
     renderer.set_seed(seed);
     renderer.set_progress_bands(bands);
+    if (preview) {
+        if (renderer.upload_scene(config.world, cam, config.background, config.lights) != RTR_OK) {
+            std::cerr << "upload failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        }
+        const auto failed = [&](const char* what) {
+            std::cerr << what << " failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";
+            return 1;
+        };
+        /* the grid of --probes: probe (ix, iy, iz) at the lower corner + (ix, iy, iz) * spacing */
+        rtr_probe_grid grid{};
+        for (int a = 0; a < 3; ++a) {
+            grid.origin[a] = probe_box[a], grid.dims[a] = probe_dims[a];
+            grid.spacing[a] = probe_dims[a] > 1 ? (probe_box[3 + a] - probe_box[a]) / (double)(probe_dims[a] - 1) : 1.0;
+        }
+        std::vector<point3> points;
+        for (int iz = 0; iz < probe_dims[2]; ++iz)
+            for (int iy = 0; iy < probe_dims[1]; ++iy)
+                for (int ix = 0; ix < probe_dims[0]; ++ix)
+                    points.emplace_back(grid.origin[0] + (double)ix * grid.spacing[0], grid.origin[1] + (double)iy * grid.spacing[1],
+                                        grid.origin[2] + (double)iz * grid.spacing[2]);
+        const std::vector<rtr_probe_sh> sh = renderer.light_probes(points, probe_samples, seed);
+        if (sh.size() != points.size()) return failed("light probes");
+        const double* sp = grid.spacing;
+        std::vector<rtr_probe_depth_texel> maps;
+        rtr_probe_visible_params vp{};
+        if (probe_depth_set) {
+            const double reach = 1.5 * std::sqrt((sp[0] * sp[0] + sp[1] * sp[1]) + sp[2] * sp[2]);
+            maps = renderer.probe_depth(points, probe_depth, reach, probe_depth_samples, seed);
+            if (maps.size() != points.size() * (size_t)probe_depth * probe_depth) return failed("probe depth");
+            vp.map_size = probe_depth, vp.normal_bias = 0.25 * std::min(sp[0], std::min(sp[1], sp[2]));
+        }
+        const std::vector<rtr_gather_out> cube =
+            renderer.capture_cube({point3(capture_at[0], capture_at[1], capture_at[2])}, capture_face, capture_spp, seed);
+        if (cube.empty()) return failed("capture");
+        std::vector<rtr_cube_level> plan;
+        const std::vector<rtr_gather_out> chain = renderer.prefilter_cube(cube, capture_face, capture_levels, plan);
+        if (chain.empty()) return failed("prefilter");
+        const std::vector<rtr_brdf_entry> table = renderer.brdf_table(brdf_dims[0], brdf_dims[1], brdf_nodes);
+        if (table.size() != (size_t)brdf_dims[0] * brdf_dims[1]) return failed("brdf table");
+        rtr_shade_env env{};
+        env.parts = RTR_SHADE_DIFFUSE | RTR_SHADE_SPECULAR;
+        env.grid = &grid, env.probes = sh.data();
+        if (probe_depth_set) env.depth = maps.data(), env.visible = &vp;
+        env.levels = plan.data(), env.n_levels = (int32_t)plan.size(), env.chain = chain.data(), env.n_records = (int64_t)chain.size();
+        env.table = table.data(), env.n_mu = brdf_dims[0], env.n_rough = brdf_dims[1];
+        if (renderer.render_preview(env, buffer, preview) != RTR_OK) return failed("preview");
+        std::cout << "preview: " << W << " x " << H << " pixels x " << preview * preview << " rays, " << points.size() << " probes, "
+                  << capture_levels << " cube levels of face " << capture_face << ", table " << brdf_dims[1] << " x " << brdf_dims[0] << "\n";
+        std::vector<unsigned char> shown;
+        if (display && renderer.display(buffer, dp, shown) != RTR_OK) return failed("display");
+        const bool png = out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0;
+        const std::vector<unsigned char>* bytes = display ? &shown : nullptr;
+        if (!(png ? buffer.save_to_png(out, bytes) : buffer.save_to_ppm(out, bytes))) {
+            std::cerr << "Failed to save image to " << out << "\n";
+            return 1;
+        }
+        return 0;
+    }
     if (capture) {
         if (renderer.upload_scene(config.world, cam, config.background, config.lights) != RTR_OK) {
             std::cerr << "upload failed (" << renderer.last_status() << "): " << renderer.last_error() << "\n";

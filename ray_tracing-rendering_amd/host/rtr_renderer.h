@@ -647,6 +647,27 @@ class Renderer {
         return out;
     }
 
+    /* Baked previews (include/rtr_hip.h: rtr_preview), on the first context and the scene uploaded there, seen from its
+     * camera: grid x grid pixel-centred rays per pixel, every hit shaded under `env` (host arrays, as for shade_points)
+     * instead of being path traced; the frame goes into `target` like a render.  Returns the status (last_status() /
+     * last_error()). */
+    int render_preview(const rtr_shade_env& env, RenderBuffer& target, int grid = 1) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) return m_error = m_create_error, m_status = m_create_status;
+        if (m_ctx.empty()) return m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        rtr_preview_params pp;
+        rtr_preview_defaults(&pp);
+        pp.image_width = target.width(), pp.image_height = target.height();
+        pp.x1 = target.width(), pp.y1 = target.height();
+        pp.grid = grid;
+        std::vector<double> lin((size_t)target.width() * target.height() * 3);
+        if ((m_status = rtr_preview(m_ctx[0], &pp, &env, lin.data(), target.width(), nullptr)))
+            m_error = rtr_last_error(m_ctx[0]);
+        else
+            target.store_linear_rows(lin.data(), 0, target.height(), target.width());
+        return m_status;
+    }
+
     /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
      * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
      * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */

@@ -41,7 +41,9 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_cube_chain_lookup_one", "rtr_probe_depth_defaults", "rtr_probe_depth", "rtr_probe_depth_device",
            "rtr_probe_depth_ray", "rtr_octa_encode", "rtr_octa_decode", "rtr_probe_lookup_visible",
            "rtr_probe_lookup_visible_device", "rtr_probe_lookup_visible_one", "rtr_brdf_table", "rtr_brdf_table_device",
-           "rtr_brdf_entry_one", "rtr_brdf_fetch_one", "rtr_shade_ibl", "rtr_shade_ibl_device", "rtr_shade_ibl_one")
+           "rtr_brdf_entry_one", "rtr_brdf_fetch_one", "rtr_shade_ibl", "rtr_shade_ibl_device", "rtr_shade_ibl_one",
+           "rtr_preview_defaults", "rtr_preview_ray", "rtr_preview_samples", "rtr_preview_samples_device", "rtr_preview",
+           "rtr_preview_device")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
@@ -259,6 +261,13 @@ def lib():
     L.rtr_shade_ibl.argtypes = [vp, P(A.ShadeEnvC), vp, vp, C.c_int64]
     L.rtr_shade_ibl_device.argtypes = [vp, P(A.ShadeEnvC), vp, vp, C.c_int64, C.c_int]
     L.rtr_shade_ibl_one.argtypes = [P(A.ShadeEnvC), vp, vp]
+    L.rtr_preview_defaults.argtypes = [P(A.PreviewParamsC)]
+    L.rtr_preview_defaults.restype = None
+    L.rtr_preview_ray.argtypes = [P(A.CameraC), P(A.PreviewParamsC), C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rtr_preview_samples.argtypes = [vp, P(A.PreviewParamsC), vp]
+    L.rtr_preview_samples_device.argtypes = [vp, P(A.PreviewParamsC), vp, C.c_int]
+    L.rtr_preview.argtypes = [vp, P(A.PreviewParamsC), P(A.ShadeEnvC), vp, C.c_int64, vp]
+    L.rtr_preview_device.argtypes = [vp, P(A.PreviewParamsC), P(A.ShadeEnvC), vp, C.c_int64, vp, C.c_int]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -974,6 +983,40 @@ def shade_ibl_one(env, queries):
     return out
 
 
+def preview_params(width, height, grid=1, region=None, t_min=None, reference_order=False):
+    """An rtr_preview_params from rtr_preview_defaults: a ``width`` x ``height`` image, ``grid`` x ``grid`` rays per
+    pixel, ``region`` (x0, y0, x1, y1) or the whole image"""
+    p = A.PreviewParamsC()
+    lib().rtr_preview_defaults(C.byref(p))
+    x0, y0, x1, y1 = region if region is not None else (0, 0, width, height)
+    p.image_width, p.image_height = int(width), int(height)
+    p.x0, p.y0, p.x1, p.y1 = int(x0), int(y0), int(x1), int(y1)
+    p.grid = int(grid)
+    if t_min is not None:
+        p.t_min = float(t_min)
+    p.flags = A.FLAG_REFERENCE_ORDER if reference_order else 0
+    return p
+
+
+def preview_rays(camera, params):
+    """The rays of a preview's region through rtr_preview_ray (host only, no context): ``RAY_DTYPE`` [h, w, grid^2] under
+    ``camera`` (what ``camera_struct`` takes).  Raises RtrError for bad params."""
+    cam = camera_struct(camera)
+    h, w, kk = params.y1 - params.y0, params.x1 - params.x0, params.grid * params.grid
+    rays = np.zeros((max(h, 0), max(w, 0), max(kk, 0)), dtype=A.RAY_DTYPE)
+    L = lib()
+    if rays.size == 0 and L.rtr_preview_ray(C.byref(cam), C.byref(params), 0, 0, 0, np.zeros(1, A.RAY_DTYPE).ctypes.data) != 0:
+        raise RtrError(A.RTR_ERR_INVALID, "rtr_preview_ray: bad params")
+    for j in range(h):
+        for i in range(w):
+            for s in range(kk):
+                rc = L.rtr_preview_ray(C.byref(cam), C.byref(params), params.x0 + i, params.y0 + j, s,
+                                       rays.ctypes.data + 80 * ((j * w + i) * kk + s))
+                if rc != 0:
+                    raise RtrError(rc, "rtr_preview_ray: bad params")
+    return rays
+
+
 def srgb_thresholds():
     """rtr_display_srgb_thresholds: the 256 doubles S that define RTR_ENCODE_SRGB (code = how many of S[1..255] are <= t)."""
     out = np.zeros(256, dtype=np.float64)
@@ -1459,6 +1502,49 @@ class Context:
         """rtr_shade_ibl_device: the same over device pointers (``env``: ``native.shade_env`` of device pointers; the
         struct, its grid, visible params and levels stay on the host), on the context stream behind what is queued there."""
         self._chk(self._L.rtr_shade_ibl_device(self._h, C.byref(env), *_into_tail(queries_ptr, out_ptr, n, blocking)))
+
+    # baked previews (include/rtr_hip.h: rtr_preview_*)
+    def preview(self, params, env, out=None, return_lit=False):
+        """rtr_preview: the frame of ``params``' region shaded under ``env`` (``native.shade_env`` of host arrays) from the
+        context's current camera: linear (h, w, 3) float64, row 0 the lowest row, or with ``return_lit`` the pair
+        (linear, lit (h, w) int32).  Blocking.  ``out`` may be a view with strided rows: only region pixels are written."""
+        h, w = params.y1 - params.y0, params.x1 - params.x0
+        if h <= 0 or w <= 0:  # an empty region: the library's error
+            self._chk(self._L.rtr_preview(self._h, C.byref(params), C.byref(env), np.zeros(3).ctypes.data, 1, None))
+        if out is None:
+            out = np.zeros((h, w, 3), dtype=np.float64)
+        if (out.dtype != np.float64 or out.shape != (h, w, 3) or out.strides[2] != 8 or out.strides[1] != 24 or
+                (h > 1 and (out.strides[0] % 24 or out.strides[0] < 24 * w))):
+            raise ValueError("out must be a float64 array of shape (%d, %d, 3) whose rows are whole pixels apart" % (h, w))
+        stride = out.strides[0] // 24 if h > 1 else w
+        lit = np.zeros((max(h, 0), stride), dtype=np.int32) if return_lit else None
+        self._chk(self._L.rtr_preview(self._h, C.byref(params), C.byref(env), out.ctypes.data, stride,
+                                      lit.ctypes.data if return_lit else None))
+        return (out, lit[:, :w]) if return_lit else out
+
+    def preview_into(self, params, env, linear_ptr, row_stride, lit_ptr=None, blocking=False):
+        """rtr_preview_device: the same into device pointers (``env``: ``native.shade_env`` of device pointers), rows
+        ``row_stride`` pixels apart, on the context stream behind what is queued there -- the bakes included; the layout
+        ``display_into`` reads."""
+        self._chk(self._L.rtr_preview_device(self._h, C.byref(params), C.byref(env), C.c_void_p(linear_ptr), int(row_stride),
+                                             C.c_void_p(lit_ptr or None), 1 if blocking else 0))
+
+    def preview_samples(self, params, out=None):
+        """rtr_preview_samples: the G-buffer of a preview, ``PREVIEW_SAMPLE_DTYPE`` [h, w, grid^2].  Blocking."""
+        h, w, kk = params.y1 - params.y0, params.x1 - params.x0, params.grid * params.grid
+        n = max(h, 0) * max(w, 0) * max(kk, 0)
+        flat = _records_out(None if out is None else out.reshape(-1), n, A.PREVIEW_SAMPLE_DTYPE)
+        self._chk(self._L.rtr_preview_samples(self._h, C.byref(params), flat.ctypes.data))
+        return flat[:n].reshape(h, w, kk)
+
+    def preview_samples_into(self, params, out_ptr, blocking=False):
+        """rtr_preview_samples_device: h * w * grid^2 ``PREVIEW_SAMPLE_DTYPE`` records at device pointer ``out_ptr``."""
+        self._chk(self._L.rtr_preview_samples_device(self._h, C.byref(params), C.c_void_p(out_ptr), 1 if blocking else 0))
+
+    def preview_rays(self, params):
+        """The rays a preview casts, ``RAY_DTYPE`` [h, w, grid^2], through rtr_preview_ray under the context's current
+        camera (``native.preview_rays``)."""
+        return preview_rays(self.camera(), params)
 
     # display transform (include/rtr_hip.h: rtr_display_*)
     @staticmethod

@@ -330,6 +330,53 @@ class Renderer:
                                              samples=samples, seed=self.seed if seed is None else seed, jitter=jitter, time=time)
         return Cubemap(rec[0])
 
+    def render_preview(self, scene, env, target_buffer, grid=1, display=None):
+        """The baked preview of ``scene`` under ``env`` (an ``IblEnvironment``) into ``target_buffer``
+        (include/rtr_hip.h: rtr_preview): ``grid`` x ``grid`` pixel-centred rays per pixel, each hit shaded from the
+        probes, the cube chain and the table instead of being path traced.  ``display`` (an rtr_display_params): the
+        environment goes to the device once, rtr_preview_device and rtr_display_device follow each other on the context's
+        stream with no host wait, and the bytes are left in ``target_buffer.display_rgb8`` (top row first) beside the
+        linear image."""
+        from . import native
+        if display is not None and not isinstance(display, A.DisplayParamsC):
+            raise ValueError("display must be None or rtr_display_params (display_defaults())")
+        self._scene_on_device(scene)
+        w, h = target_buffer.width, target_buffer.height
+        p = native.preview_params(w, h, grid)
+        if display is None:
+            target_buffer.store_linear(env.render(self._ctx, p))
+            return target_buffer
+        import torch
+        dev = "cuda:%d" % self._ctx.device
+        host = env.env()
+        keep = []
+
+        def on_device(records):  # the records of one array of the environment as bytes on the device
+            t = torch.from_numpy(np.ascontiguousarray(records).reshape(-1).view(np.uint8).copy()).to(dev)
+            keep.append(t)
+            return t.data_ptr()
+
+        kw = {}
+        if env.grid is not None:
+            kw.update(grid=env.grid.grid(), probes=on_device(np.asarray(env.grid.coefficients, dtype=A.PROBE_SH_DTYPE)))
+            vis = _visible_of(host)
+            if vis is not None:
+                kw.update(depth=on_device(np.asarray(env.grid.depth, dtype=A.PROBE_DEPTH_DTYPE)),
+                          visible=native.probe_visible_params(vis.map_size, vis.normal_bias))
+        if env.chain is not None:
+            kw.update(levels=env.chain.levels, chain=on_device(np.asarray(env.chain.records, dtype=A.GATHER_OUT_DTYPE)),
+                      n_records=host.n_records)
+        d_env = native.shade_env(on_device(env.table.entries), n_mu=host.n_mu, n_rough=host.n_rough, **kw)
+        d_lin = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
+        d_rgb = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(d_lin.device)  # the library works on a stream of its own
+        self._ctx.preview_into(p, d_env, d_lin.data_ptr(), w)
+        self._ctx.display_into(d_lin.data_ptr(), w, w, h, d_rgb.data_ptr(), display)
+        self._ctx.synchronize()
+        target_buffer.store_linear(d_lin.cpu().numpy())
+        target_buffer.display_rgb8 = d_rgb.cpu().numpy()
+        return target_buffer
+
     def _scene_on_device(self, scene, own_camera=True):
         """Upload ``scene`` unless the context holds it already.  ``own_camera``: a scene that is there but is seen from
         another camera since ``Context.set_camera`` (a ``render_sequence``) gets its own camera back, so a render of
@@ -601,6 +648,18 @@ class IblEnvironment:
         """[n, 3] radiance towards the viewers: points, normals and view vectors [n, 3], base colour [n, 3] or one colour,
         roughness and metallic numbers or [n]; zero where a lookup is invalid."""
         return self.shade_records(points, normals, views, base, roughness, metallic, ctx)["v"]
+
+    def render(self, ctx, params, return_lit=False):
+        """rtr_preview: the frame of the scene ``ctx`` holds, seen from its current camera and shaded under this
+        environment; ``params`` from ``native.preview_params``.  Linear (h, w, 3), row 0 the lowest row; with
+        ``return_lit`` also the (h, w) count of samples per pixel that found something to add."""
+        return ctx.preview(params, self.env(), return_lit=return_lit)
+
+
+def _visible_of(env):
+    """The rtr_probe_visible_params an rtr_shade_env points to, or None"""
+    import ctypes
+    return ctypes.cast(env.visible, ctypes.POINTER(A.ProbeVisibleParamsC)).contents if env.visible else None
 
 
 def check_denoise(params):
