@@ -45,9 +45,10 @@ struct rtr_context {
     /* per-render workspace */
     DevBuf b_tiles, b_partial, b_done, b_stats, b_cancel, b_test, b_stage;
     DevBuf b_denoise; /* rtr_accum_denoise / rtr_denoise_host: the planes of DenoiseK */
-    /* the host entries of rtr_query_*, rtr_gather_*, rtr_probe_*, rtr_capture_cube, rtr_cube_lookup, rtr_probe_depth, rtr_probe_lookup_visible: one slice of inputs and its results (staged_slices of
-     * rt_batch.h).  One buffer serves them all: each returns only behind its last slice's wait, and the device entries
-     * never touch it */
+    /* the host entries of every unit that includes rt_batch.h: what stays on the device for the whole call at the head (a
+     * grid, centres, an environment), then one slice of inputs and its results (staged_slices of rt_batch.h; rtr_preview
+     * lays its frame out there itself).  One buffer serves them all: each returns only behind its last slice's wait, and
+     * the device entries never touch it */
     DevBuf b_batch;
     DevBuf b_display;    /* rtr_display_*: the sRGB thresholds (uploaded by rtr_create), the histogram, the DisplayRec */
     DevBuf b_display_io; /* rtr_display_host / _histogram: the image and its outputs (nothing else uses it) */
@@ -60,10 +61,8 @@ struct rtr_context {
     bool in_flight = false; /* stream-ordered work of a render call is queued whose statistics are not pending (an error return) */
     rtr_render_stats stats{};
     rtr_debug_kernel last_kernel{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0, 0}; /* rtr_debug_last_kernel */
-    rtr_debug_gather last_gather{-1, -1, 0, 0};                         /* rtr_debug_last_gather */
-    rtr_debug_probe last_probe{-1, -1, 0};                              /* rtr_debug_last_probe */
-    rtr_debug_capture last_capture{-1, -1, 0};                          /* rtr_debug_last_capture */
-    rtr_debug_probe_depth last_probe_depth{-1, 0};                      /* rtr_debug_last_probe_depth */
+    rtr_debug_batch last_batch[RTR_DEBUG_FAMILIES] = {{-1, -1, 0, 0}, {-1, -1, 0, 0}, {-1, -1, 0, 0}, {-1, -1, 0, 0}}; /* rtr_debug_last_batch */
+    long long last_launches = 0; /* launches of the last launch_records call (rt_batch.h): rtr_debug_last_launches */
     /* Cancel.  Renders are numbered; rtr_cancel() covers every render issued so far: it stores the newest
      * id in `cancelled_upto` and in the device word the kernels poll.  A render issued afterwards carries a
      * larger id, so nothing has to be reset between renders and a cancel that arrives while a render waits

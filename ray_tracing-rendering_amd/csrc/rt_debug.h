@@ -33,29 +33,14 @@ struct rtr_debug_kernel {
     int pair;       /* megakernel: k_mega's pair-cast instantiation (PAIR = true) */
     int queue;      /* megakernel: k_mega_queue<integrator, trav, ms>, the job-queue twin of the pair-cast kernel, ran instead */
 };
-/* the gather kernel the last rtr_gather_* call launched (of its last slice), recorded on the host when it is enqueued */
-struct rtr_debug_gather {
-    int integ;     /* k_gather_li<integ, trav>; -1: occlusion, k_gather_any<trav, broadcast> */
-    int trav;      /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no gather yet */
-    int broadcast; /* k_gather_any<T, true> */
-    int lg;        /* log2 of the lanes that share a point (gather_lg of the samples) */
-};
-/* the probe kernel the last rtr_probe_visibility / rtr_probe_radiance call launched (of its last slice), recorded like a gather's */
-struct rtr_debug_probe {
-    int integ; /* k_probe_li<integ, trav>; -1: visibility, k_probe_any<trav> */
-    int trav;  /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no probe call yet */
-    int lg;    /* log2 of the lanes that share a point */
-};
-/* the capture kernel the last rtr_capture_cube call launched (of its last slice), recorded like a gather's */
-struct rtr_debug_capture {
-    int integ; /* k_capture_li<integ, trav> */
-    int trav;  /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no capture yet */
-    int lg;    /* log2 of the lanes that share a texel */
-};
-/* the distance-map kernel the last rtr_probe_depth call launched (of its last slice), recorded like a gather's */
-struct rtr_debug_probe_depth {
-    int trav; /* k_probe_depth<trav>: the RT_TRAV_* template value; -1: no such call yet */
-    int lg;   /* log2 of the lanes that share a texel */
+/* the kernel the last call of a batch family launched (of its last slice), recorded on the host when it is enqueued: one
+ * record per family.  A family without a member leaves it as it starts */
+enum { RTR_DEBUG_GATHER, RTR_DEBUG_PROBE, RTR_DEBUG_CAPTURE, RTR_DEBUG_PROBE_DEPTH, RTR_DEBUG_FAMILIES };
+struct rtr_debug_batch {
+    int integ;     /* k_gather_li / k_probe_li / k_capture_li<integ, trav>; -1: k_gather_any, k_probe_any, k_probe_depth */
+    int trav;      /* RT_TRAV_* template value, after the EXACT -> MEDIA substitution of li_trav; -1: no such call yet */
+    int broadcast; /* gathers: k_gather_any<T, true> */
+    int lg;        /* log2 of the lanes that share a record (gather_lg of the samples) */
 };
 struct rtr_debug_li_out { /* per camera sample: what rtr_li_samples drops */
     double L[3];
@@ -81,10 +66,10 @@ int rtr_debug_scene_plan(const rtr_scene_desc* scene, int integrator, int flags,
 int rtr_debug_frame_shapes(const rtr_scene_desc* scene, int32_t* shapes, int64_t cap, int32_t* n_inst);
 int rtr_debug_view_get(rtr_context* ctx, int flags, rtr_debug_view* view, size_t size_of_view);
 int rtr_debug_last_kernel(rtr_context* ctx, rtr_debug_kernel* out, size_t size_of_out);
-int rtr_debug_last_gather(rtr_context* ctx, rtr_debug_gather* out, size_t size_of_out);
-int rtr_debug_last_probe(rtr_context* ctx, rtr_debug_probe* out, size_t size_of_out);
-int rtr_debug_last_capture(rtr_context* ctx, rtr_debug_capture* out, size_t size_of_out);
-int rtr_debug_last_probe_depth(rtr_context* ctx, rtr_debug_probe_depth* out, size_t size_of_out);
+int rtr_debug_last_batch(rtr_context* ctx, int family, rtr_debug_batch* out, size_t size_of_out); /* family: RTR_DEBUG_* */
+/* the kernel launches the context's last pass through the chunked launcher made (launch_records of rt_batch.h): 1 unless the
+ * call held more records than the cap, which RTR_LAUNCH_RECORDS lowers; 0: none yet; -1: a NULL context */
+int64_t rtr_debug_last_launches(rtr_context* ctx);
 int rtr_debug_li(rtr_context* ctx, const rtr_render_params* params, const int32_t* ijs, rtr_debug_li_out* out, int64_t n);
 void rtr_debug_set_error(rtr_context* ctx, const char* msg); /* rtr_last_error() of a failing rtr_test_* call */
 /* Synthetic state into an accumulator, so that the product's own k_accum_errors / _plan / _commit / _resolve(_scatter) run on

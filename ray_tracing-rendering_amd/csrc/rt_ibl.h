@@ -1,6 +1,7 @@
 /*
  * rt_ibl.h -- image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*): the arithmetic of that contract, written
- * once for host (the _one forms, the entries' checks) and device, and the host-side rules of an rtr_shade_env.  The two
+ * once for host (the _one forms, the entries' checks) and device, and the host side of an rtr_shade_env: its rules, the
+ * staging of its arrays and the overlap test of the _device forms, which rtr_ibl.hip and rtr_preview.hip share.  The two
  * kernels are rt_ibl_kernels.h's; rtr_preview.hip composes shade_ibl_one from here.  The lookups the shader composes are
  * rt_render.h's: nothing of them is restated here.
  */
@@ -173,22 +174,6 @@ RT_HD rtr_gather_out shade_ibl_one(const ShadeK& K, const rtr_shade_query& q, do
 
 /* ---- ENVIRONMENT: host side, what the entries of rtr_ibl.hip and rtr_preview.hip check and build alike ---- */
 
-/* the grid rule of rtr_probe_lookup */
-inline const char* shade_grid_why(const rtr_probe_grid* g) {
-    if (!g) return "null grid";
-    long long count = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (!__builtin_isfinite(g->origin[a])) return "origin not finite";
-        if (!(__builtin_isfinite(g->spacing[a]) && g->spacing[a] > 0)) return "spacing must be finite and > 0";
-        if (g->dims[a] < 1 || g->dims[a] > (1 << 24)) return "dims must be >= 1 and their product <= 2^24";
-        count *= g->dims[a];
-        if (count > (1ll << 24)) return "dims must be >= 1 and their product <= 2^24";
-    }
-    if (g->pad != 0) return "pad must be 0";
-    return nullptr;
-}
-inline long long shade_grid_probes(const rtr_probe_grid* g) { return (long long)g->dims[0] * g->dims[1] * g->dims[2]; }
-
 /* why `env` is no environment, or nullptr: the rules of the lookups it names, for the selected parts only */
 inline const char* env_why(const rtr_shade_env* e) {
     if (!e) return "null environment";
@@ -196,13 +181,11 @@ inline const char* env_why(const rtr_shade_env* e) {
     if (e->n_mu < 1 || e->n_mu > RTR_BRDF_MAX || e->n_rough < 1 || e->n_rough > RTR_BRDF_MAX) return "table n_mu or n_rough outside 1 .. 256";
     if (!e->table) return "null table";
     if (e->parts & RTR_SHADE_DIFFUSE) {
-        if (const char* why = shade_grid_why(e->grid)) return why;
+        if (const char* why = probe_grid_why(e->grid)) return why;
         if (!e->probes) return "null probes";
         if ((e->depth != nullptr) != (e->visible != nullptr)) return "depth and visible go together";
-        if (e->visible) {
-            if (const char* why = probe_visible_params_why(e->visible)) return why;
-            if (shade_grid_probes(e->grid) * e->visible->map_size * e->visible->map_size > (1ll << 24)) return "probes * map_size^2 must be <= 2^24";
-        }
+        if (e->visible)
+            if (const char* why = probe_maps_why(e->grid, e->visible)) return why;
     }
     if (e->parts & RTR_SHADE_SPECULAR) {
         if (e->n_records < 0) return "negative n_records";
@@ -215,12 +198,13 @@ inline const char* env_why(const rtr_shade_env* e) {
 /* bytes of the arrays of a valid environment: of a part that is not selected 0 */
 struct EnvBytes {
     size_t probes, depth, chain, table;
+    size_t total() const { return probes + depth + chain + table; }
 };
 inline EnvBytes env_bytes(const rtr_shade_env* e) {
     EnvBytes b{0, 0, 0, (size_t)e->n_mu * e->n_rough * sizeof(rtr_brdf_entry)};
     if (e->parts & RTR_SHADE_DIFFUSE) {
-        b.probes = (size_t)shade_grid_probes(e->grid) * sizeof(rtr_probe_sh);
-        if (e->visible) b.depth = (size_t)shade_grid_probes(e->grid) * e->visible->map_size * e->visible->map_size * sizeof(rtr_probe_depth_texel);
+        b.probes = (size_t)grid_probes(e->grid) * sizeof(rtr_probe_sh);
+        if (e->visible) b.depth = (size_t)grid_probes(e->grid) * e->visible->map_size * e->visible->map_size * sizeof(rtr_probe_depth_texel);
     }
     if (e->parts & RTR_SHADE_SPECULAR) b.chain = (size_t)e->n_records * sizeof(rtr_gather_out);
     return b;
@@ -242,4 +226,30 @@ inline ShadeK shade_k(const rtr_shade_env* e, const void* probes, const void* de
     }
     K.n_mu = e->n_mu, K.n_rough = e->n_rough, K.table = static_cast<const rtr_brdf_entry*>(table);
     return K;
+}
+/* The arrays of a valid environment packed behind `base` in the order probes, depth, chain, table, each 16-byte aligned
+ * where base is: K is the kernel's argument of that layout, and with `copy` the arrays' copies from the host are queued on
+ * `stream`.  rtr_shade_ibl and rtr_preview stage an environment this way */
+inline hipError_t env_stage(const rtr_shade_env* e, const EnvBytes& b, char* base, bool copy, hipStream_t stream, ShadeK& K) {
+    static_assert(sizeof(rtr_probe_sh) % 16 == 0 && sizeof(rtr_probe_depth_texel) % 16 == 0 && sizeof(rtr_gather_out) % 16 == 0 &&
+                      sizeof(rtr_brdf_entry) % 16 == 0, "the arrays follow each other 16-byte aligned");
+    char* const at[4] = {base, base + b.probes, base + b.probes + b.depth, base + b.probes + b.depth + b.chain};
+    const void* const from[4] = {e->probes, e->depth, e->chain, e->table};
+    const size_t bytes[4] = {b.probes, b.depth, b.chain, b.table};
+    K = shade_k(e, at[0], at[1], at[2], at[3]);
+    for (int i = 0; copy && i < 4; ++i)
+        if (bytes[i])
+            if (hipError_t err = hipMemcpyAsync(at[i], from[i], bytes[i], hipMemcpyHostToDevice, stream)) return err;
+    return hipSuccess;
+}
+/* the _device forms: do two spans of bytes meet; does the span [o0, o0 + on) meet an array of a valid environment whose
+ * arrays are on the device.  `bits` takes the arrays' addresses for the entry's alignment check */
+inline bool spans_overlap(uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return an && bn && a0 < b0 + bn && b0 < a0 + an; }
+inline bool env_overlaps(const rtr_shade_env* e, const EnvBytes& b, uintptr_t o0, size_t on, uintptr_t& bits) {
+    const uintptr_t a0[4] = {(uintptr_t)e->probes, (uintptr_t)e->depth, (uintptr_t)e->chain, (uintptr_t)e->table};
+    const size_t an[4] = {b.probes, b.depth, b.chain, b.table};
+    bool meets = false;
+    for (int i = 0; i < 4; ++i)
+        if (an[i]) bits |= a0[i], meets = meets || spans_overlap(o0, on, a0[i], an[i]);
+    return meets;
 }

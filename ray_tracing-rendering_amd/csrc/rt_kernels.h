@@ -1257,6 +1257,18 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_query_any(DScene sc, const rtr_ra
 #ifndef RTR_GATHER_BROADCAST_DEFAULT
 #define RTR_GATHER_BROADCAST_DEFAULT 0 /* which form the library launches (RTR_GATHER_BROADCAST=0/1 overrides it) */
 #endif
+/* The lane-to-record map of every kernel that gives a record a group of G = 1 << lg lanes (the gathers, the probes, the
+ * captures, the distance maps): this launch serves the records [k0, n), global lane g record k = k0 + g / G as lane
+ * l = g % G.  false: the whole wave is past the end and returns.  A lane whose k >= n is not live: it stays, and carries
+ * +0.0 / 0 through the butterfly.  The gathers and probes number their records from 0: k0 is the constant 0 there.
+ * `live`, k < n, is a line of each caller: as a reference parameter of this function it makes the compiler associate the
+ * lane predicates the other way round, and the kernels' code differs (profiles/r27_kres.txt). */
+RT_DEV bool group_begin(long long k0, long long n, int lg, long long& k, int& l) {
+    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k0 + ((g & ~63ll) >> lg) >= n) return false;
+    k = k0 + (g >> lg), l = (int)(g & ((1 << lg) - 1));
+    return true;
+}
 struct GatherLane {
     long long k; /* point of this lane's group */
     int l;       /* lane in the group */
@@ -1265,9 +1277,7 @@ struct GatherLane {
 };
 template <bool BCAST>
 RT_DEV bool gather_begin(const GatherK& K, GatherLane& L) {
-    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
-    if (((g & ~63ll) >> K.lg) >= K.n) return false; /* the whole wave is past the end */
-    L.k = g >> K.lg, L.l = (int)(g & ((1 << K.lg) - 1));
+    if (!group_begin(0, K.n, K.lg, L.k, L.l)) return false;
     const bool live = L.k < K.n;
     rtr_gather_point q;
     for (int a = 0; a < 3; ++a) q.p[a] = 0.0, q.n[a] = 0.0;
@@ -1361,9 +1371,7 @@ struct ProbeLane {
     V3 p;
 };
 RT_DEV bool probe_begin(const ProbeK& K, ProbeLane& L) {
-    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
-    if (((g & ~63ll) >> K.lg) >= K.n) return false; /* the whole wave is past the end */
-    L.k = g >> K.lg, L.l = (int)(g & ((1 << K.lg) - 1));
+    if (!group_begin(0, K.n, K.lg, L.k, L.l)) return false;
     const bool live = L.k < K.n;
     rtr_probe_point q;
     for (int a = 0; a < 3; ++a) q.p[a] = 0.0;
@@ -1487,9 +1495,7 @@ struct CaptureLane {
     uint32_t centre;  /* the centre's number under the seed: its index in the call + point_base */
 };
 RT_DEV bool capture_begin(const CaptureK& K, CaptureLane& L) {
-    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
-    if (K.k0 + ((g & ~63ll) >> K.lg) >= K.n) return false; /* the whole wave is past the end */
-    L.k = K.k0 + (g >> K.lg), L.l = (int)(g & ((1 << K.lg) - 1));
+    if (!group_begin(K.k0, K.n, K.lg, L.k, L.l)) return false;
     const bool live = L.k < K.n;
     const long long texel = K.first + (live ? L.k : K.k0);
     const long long c = texel / K.F;

@@ -340,6 +340,27 @@ inline const char* probe_visible_params_why(const rtr_probe_visible_params* p) {
     if (!(__builtin_isfinite(p->normal_bias) && p->normal_bias >= 0)) return "normal_bias must be finite and >= 0";
     return nullptr;
 }
+/* why `g` is no probe grid, or nullptr: the rule of rtr_probe_lookup, which every entry that takes a grid shares */
+inline const char* probe_grid_why(const rtr_probe_grid* g) {
+    if (!g) return "null grid";
+    long long count = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!__builtin_isfinite(g->origin[a])) return "origin not finite";
+        if (!(__builtin_isfinite(g->spacing[a]) && g->spacing[a] > 0)) return "spacing must be finite and > 0";
+        if (g->dims[a] < 1 || g->dims[a] > (1 << 24)) return "dims must be >= 1 and their product <= 2^24";
+        count *= g->dims[a];
+        if (count > (1ll << 24)) return "dims must be >= 1 and their product <= 2^24";
+    }
+    if (g->pad != 0) return "pad must be 0";
+    return nullptr;
+}
+inline long long grid_probes(const rtr_probe_grid* g) { return (long long)g->dims[0] * g->dims[1] * g->dims[2]; }
+/* the maps' rules on top of a valid grid: the parameters, and the bound on the texels of all maps */
+inline const char* probe_maps_why(const rtr_probe_grid* g, const rtr_probe_visible_params* vp) {
+    if (const char* why = probe_visible_params_why(vp)) return why;
+    if (grid_probes(g) * vp->map_size * vp->map_size > (1ll << 24)) return "probes * map_size^2 must be <= 2^24";
+    return nullptr;
+}
 RT_HD double octa_sg(double t) { return t >= 0 ? 1.0 : -1.0; }
 /* DECODE: the unit direction of the point (u, v) of the octahedral square */
 RT_HD void octa_decode(double u, double v, double& dx, double& dy, double& dz) {

@@ -798,6 +798,12 @@ int rtr_debug_last_kernel(rtr_context* c, rtr_debug_kernel* out, size_t size) {
     *out = c->last_kernel;
     return RTR_OK;
 }
+int rtr_debug_last_batch(rtr_context* c, int family, rtr_debug_batch* out, size_t size) {
+    if (!c || !out || size != sizeof(rtr_debug_batch) || family < 0 || family >= RTR_DEBUG_FAMILIES) return RTR_ERR_INVALID;
+    *out = c->last_batch[family];
+    return RTR_OK;
+}
+int64_t rtr_debug_last_launches(rtr_context* c) { return c ? c->last_launches : -1; }
 int rtr_debug_li(rtr_context* c, const rtr_render_params* p, const int32_t* ijs, rtr_debug_li_out* out, int64_t n) {
     static_assert(sizeof(rtr_debug_li_out) == sizeof(LiOut), "one layout");
     if (n < 0 || (n > 0 && (!ijs || !out))) return RTR_ERR_INVALID;

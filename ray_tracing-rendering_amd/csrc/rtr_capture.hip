@@ -3,8 +3,8 @@
  * rtr_write_rgbe): the centre check, the kernel choice among the 17 k_capture_li held here (the k_li family rule of
  * rt_select.h, like the gathers'), k_cube_lookup and its launch, the entries, and the host-only pieces that need no context
  * (rtr_capture_defaults, rtr_capture_ray, rtr_cube_lookup_one, rtr_latlong_direction, rtr_cube_to_latlong,
- * rtr_write_rgbe).  The entries' common checks, the staging of the host entries, the body of the device entries and the
- * chunked launcher are rt_batch.h's, shared with the gathers and probes.
+ * rtr_write_rgbe).  The entries' common checks, the staging of the host entries, the body of the device entries, the
+ * chunked launcher and the single-ray entry are rt_batch.h's, shared with the other batch units.
  */
 #include "rt_batch.h"
 
@@ -53,10 +53,10 @@ int capture_launch(rtr_context* c, const rtr_render_params* rp, const rtr_captur
     K.jitter = cp->jitter, K.time = cp->time, K.max_depth = rp->max_depth, K.rr_start = rp->rr_start_depth;
     int rc = RTR_OK;
     const bool found = dispatch_li(rp->integrator, trav, [&](auto i, auto t) {
-        rc = launch_texels(c, k_capture_li<decltype(i)::value, decltype(t)::value>, c->ds, K, lds);
+        rc = launch_records(c, "rtr_capture_cube", k_capture_li<decltype(i)::value, decltype(t)::value>, lds, K.n, K.lg, texel_args(c->ds, K));
     });
     if (!found) return fail(c, RTR_ERR_UNSUPPORTED, "no capture kernel for traversal " + std::to_string(trav));
-    if (rc == RTR_OK) c->last_capture = rtr_debug_capture{rp->integrator, trav, K.lg};
+    if (rc == RTR_OK) c->last_batch[RTR_DEBUG_CAPTURE] = rtr_debug_batch{rp->integrator, trav, 0, K.lg};
     return rc;
 }
 
@@ -68,13 +68,8 @@ int lookup_check(rtr_context* c, int32_t S, const void* texels, const void* q, c
 }
 int lookup_launch(rtr_context* c, int S, const rtr_gather_out* d_texels, const rtr_probe_point* d_q, rtr_gather_out* d_out,
                   int64_t n) {
-    for (int64_t k0 = 0; k0 < n; k0 += kLaunchPoints) {
-        const long long m = std::min<long long>(n - k0, kLaunchPoints);
-        hipLaunchKernelGGL(k_cube_lookup, dim3((unsigned)((m + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), 0, c->stream, S,
-                           d_texels, d_q + k0, d_out + k0, m);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("cube lookup launch: ") + hipGetErrorString(e));
+    return launch_records(c, "rtr_cube_lookup", k_cube_lookup, 0, n, 0,
+                          [&](long long k0, long long m) { return std::make_tuple(S, d_texels, d_q + k0, d_out + k0, m); });
 }
 
 /* the four bytes of one texel of rtr_write_rgbe */
@@ -108,16 +103,12 @@ int rtr_capture_cube(rtr_context* c, const rtr_render_params* rp, const rtr_capt
                      rtr_gather_out* out, int64_t n) {
     if (int rc = capture_check(c, rp, cp, pts, out, n)) return rc;
     if (n == 0) return RTR_OK;
-    for (int64_t k = 0; k < n; ++k)
-        if (probe_point_bad(pts[k]))
-            return fail(c, RTR_ERR_INVALID, "rtr_capture_cube: bad centre at index " + std::to_string(k) + " (non-finite position)");
-    /* the centres stay at the head of the staging buffer for all slices: the first one brings them; a record is a texel */
-    const size_t head = ((size_t)n * sizeof(rtr_probe_point) + 15) & ~(size_t)15;
-    const StagedIO io{head, 0, nullptr, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
-    return staged_slices(c, n * face_texels(cp->face_size), kCaptureSlice, io, [&](const Slice& s) {
-        if (s.k0 == 0) HIPCHK(c, hipMemcpyAsync(s.head, pts, (size_t)n * sizeof(rtr_probe_point), hipMemcpyHostToDevice, c->stream));
-        return capture_launch(c, rp, cp, static_cast<const rtr_probe_point*>(s.head), static_cast<rtr_gather_out*>(s.out[0]), s.k0, s.m);
-    });
+    if (int rc = records_check(c, "rtr_capture_cube", "centre", kPositionRule, n, [&](int64_t k) { return probe_point_bad(pts[k]); }))
+        return rc;
+    return staged_texels(c, pts, n, face_texels(cp->face_size), sizeof(rtr_gather_out), out, kCaptureSlice,
+                         [&](const rtr_probe_point* d_pts, void* d_out, long long first, long long m) {
+                             return capture_launch(c, rp, cp, d_pts, static_cast<rtr_gather_out*>(d_out), first, m);
+                         });
 }
 
 int rtr_capture_cube_device(rtr_context* c, const rtr_render_params* rp, const rtr_capture_params* cp,
@@ -136,18 +127,15 @@ void rtr_capture_defaults(rtr_capture_params* p) {
 
 int rtr_capture_ray(const rtr_capture_params* cp, const rtr_probe_point* point, int64_t index_in_call, int32_t face, int32_t a,
                     int32_t b, int32_t s, rtr_ray* out) {
-    if (capture_params_why(cp) || !point || !out || index_in_call < 0 || probe_point_bad(*point)) return RTR_ERR_INVALID;
+    if (capture_params_why(cp)) return RTR_ERR_INVALID;
     const int S = cp->face_size;
-    if (face < 0 || face > 5 || a < 0 || a >= S || b < 0 || b >= S || s < 0 || s >= cp->samples) return RTR_ERR_INVALID;
-    const int e = (face * S + b) * S + a;
-    uint32_t rng = rtr_sample_seed_inline(cp->seed, 6 * S * S, e, (int32_t)((uint32_t)index_in_call + cp->point_base), s);
-    rtr_ray ray{};
-    capture_direction(S, face, a, b, cp->jitter, rng, ray.direction[0], ray.direction[1], ray.direction[2]);
-    for (int i = 0; i < 3; ++i) ray.origin[i] = point->p[i];
-    ray.time = cp->time, ray.t_min = 0.001, ray.t_max = __builtin_huge_val();
-    ray.rng_state = rng;
-    *out = ray;
-    return RTR_OK;
+    if (face < 0 || face > 5 || a < 0 || a >= S || b < 0 || b >= S) return RTR_ERR_INVALID;
+    const RaySeed seed{cp->seed, cp->point_base, 6 * S * S, (face * S + b) * S + a, cp->samples, cp->time, 0.001, __builtin_huge_val()};
+    return sample_ray(seed, point ? point->p : nullptr, index_in_call, s, out, [&](uint32_t& rng, double* d) {
+        if (probe_point_bad(*point)) return false;
+        capture_direction(S, face, a, b, cp->jitter, rng, d[0], d[1], d[2]);
+        return true;
+    });
 }
 
 int rtr_cube_lookup_one(int32_t S, const rtr_gather_out* texels, const rtr_probe_point* q, rtr_gather_out* out) {
@@ -212,12 +200,6 @@ int rtr_write_rgbe(const char* path, int32_t W, int32_t H, const double* rgb) {
     }
     ok = (std::fclose(f) == 0) && ok;
     return ok ? RTR_OK : RTR_ERR_DEVICE;
-}
-
-int rtr_debug_last_capture(rtr_context* c, rtr_debug_capture* out, size_t size) {
-    if (!c || !out || size != sizeof(rtr_debug_capture)) return RTR_ERR_INVALID;
-    *out = c->last_capture;
-    return RTR_OK;
 }
 
 } /* extern "C" */

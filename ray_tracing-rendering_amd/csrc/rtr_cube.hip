@@ -2,20 +2,19 @@
  * rtr_cube.hip -- filtered cube maps (include/rtr_hip.h: rtr_cube_filter*, rtr_cube_chain_*): the parameter and chain checks,
  * the split of a filter call into launches of bounded work, the two kernels of rt_cube.h and their launches, the entries,
  * and the host-only pieces that need no context (rtr_cube_filter_defaults, rtr_cube_filter_one, rtr_cube_chain_plan,
- * rtr_cube_chain_lookup_one).  The entries' common checks, the staging of the host entries and the body of the device
- * entries are rt_batch.h's, shared with the gathers, probes and captures.
+ * rtr_cube_chain_lookup_one).  The entries' common checks, the staging of the host entries, the body of the device
+ * entries, the chunked launcher of the chain lookup and the cap hook are rt_batch.h's, shared with the other batch units.
  */
 #include "rt_batch.h"
 #include "rt_cube.h"
-
-#include <cstdlib>
 
 using namespace rtr;
 
 namespace {
 
 constexpr int64_t kCubeSlice = (int64_t)1 << 20; /* output records (queries of a lookup) per slice of the host entries */
-/* (output, source) pairs per launch at most: DESIGN.md 4.11 has the measured time of a launch of this size */
+/* (output, source) pairs per launch at most (RTR_FILTER_PAIRS, a test hook, lowers it): DESIGN.md 4.11 has the measured
+ * time of a launch of this size */
 constexpr long long kFilterPairs = 1ll << 35;
 #ifndef RTR_FILTER_WIDE
 #define RTR_FILTER_WIDE 4 /* output texels per wave of the wide kernel; the narrow one has 1 (experiments: -DRTR_FILTER_WIDE=n) */
@@ -23,15 +22,6 @@ constexpr long long kFilterPairs = 1ll << 35;
 constexpr int kFilterWide = RTR_FILTER_WIDE;
 
 long long face_records(int S) { return 6ll * S * S; }
-
-long long filter_pair_cap() {
-    long long cap = kFilterPairs;
-    if (const char* e = getenv("RTR_FILTER_PAIRS")) { /* a test hook: lowers the cap */
-        const long long v = std::atoll(e);
-        if (v >= 1 && v < cap) cap = v;
-    }
-    return cap;
-}
 
 /* what both filter entries check before any device work: context, params, n / NULL; no scene is needed */
 int filter_check(rtr_context* c, const rtr_cube_filter_params* fp, const void* texels, const void* out, int64_t n) {
@@ -41,7 +31,7 @@ int filter_check(rtr_context* c, const rtr_cube_filter_params* fp, const void* t
 }
 
 /* the output records [o0, o1) of the call (numbered cube * Fout + e) into d_out, whose record 0 is o0.  No launch holds
- * more than filter_pair_cap() pairs: whole cubes side by side while they fit, else one cube's texels in runs.  A launch
+ * more than that many pairs: whole cubes side by side while they fit, else one cube's texels in runs.  A launch
  * with few workgroups takes the kernel with one output texel per wave, which spreads it over four times as many */
 int filter_launch(rtr_context* c, const rtr_cube_filter_params* fp, const rtr_gather_out* d_texels, rtr_gather_out* d_out,
                   long long o0, long long o1) {
@@ -50,7 +40,7 @@ int filter_launch(rtr_context* c, const rtr_cube_filter_params* fp, const rtr_ga
     K.Sin = fp->face_in, K.SSin = K.Sin * K.Sin, K.Fin = 6 * K.SSin;
     K.Sout = fp->face_out, K.SSout = K.Sout * K.Sout, K.Fout = 6 * K.SSout;
     K.a2m1 = fp->alpha * fp->alpha - 1.0, K.cos_cut = fp->cos_cut;
-    const long long per_launch = std::max(1ll, filter_pair_cap() / K.Fin); /* output texels */
+    const long long per_launch = std::max(1ll, env_cap("RTR_FILTER_PAIRS", kFilterPairs) / K.Fin); /* output texels */
     for (long long o = o0; o < o1;) {
         const long long cube = o / K.Fout;
         const int e = (int)(o - cube * K.Fout);
@@ -90,13 +80,8 @@ int chain_launch(rtr_context* c, const rtr_cube_level* lv, int n_levels, const r
     ChainK C{};
     for (int i = 0; i < n_levels; ++i) C.lv[i] = lv[i];
     C.n = n_levels;
-    for (int64_t k0 = 0; k0 < n; k0 += kLaunchPoints) {
-        const long long m = std::min<long long>(n - k0, kLaunchPoints);
-        hipLaunchKernelGGL(k_cube_chain_lookup, dim3((unsigned)((m + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), 0, c->stream, C,
-                           d_texels, d_q + k0, d_out + k0, m);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("cube chain lookup launch: ") + hipGetErrorString(e));
+    return launch_records(c, "rtr_cube_chain_lookup", k_cube_chain_lookup, 0, n, 0,
+                          [&](long long k0, long long m) { return std::make_tuple(C, d_texels, d_q + k0, d_out + k0, m); });
 }
 
 } // namespace

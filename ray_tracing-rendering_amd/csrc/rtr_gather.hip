@@ -2,8 +2,8 @@
  * rtr_gather.hip -- hemisphere gathers (include/rtr_hip.h: rtr_gather_*): the point check, the kernel choice among the
  * 27 kernels held here (10 k_gather_any, 17 k_gather_li), the entries, and the host-only pieces that need no context
  * (rtr_gather_defaults, rtr_gather_ray).  Which k_gather_li a radiance gather runs is the k_li family rule of rt_select.h.
- * The entries' common checks, the staging of the host entries, the body of the device entries, the launch set-up and the
- * chunked launcher are rt_batch.h's, shared with the probes.
+ * The entries' common checks, the staging of the host entries, the body of the device entries, the launch set-up, the
+ * chunked launcher and the single-ray entry are rt_batch.h's, shared with the other batch units.
  */
 #include "rt_batch.h"
 
@@ -19,13 +19,10 @@ int gather_check(rtr_context* c, const rtr_render_params* rp, bool radiance, con
     return points_check(c, "rtr_gather_*", rp, radiance, gp, n, pts && out);
 }
 int gather_check_points(rtr_context* c, const rtr_gather_point* pts, int64_t n) {
-    for (int64_t k = 0; k < n; ++k) {
+    return records_check(c, "rtr_gather_*", "point", kGatherPointRule, n, [&](int64_t k) {
         double nlen;
-        if (gather_point_bad(pts[k], nlen))
-            return fail(c, RTR_ERR_INVALID, "rtr_gather_*: bad point at index " + std::to_string(k) +
-                                                " (non-finite position / normal, or a normal whose length is not in (0, inf))");
-    }
-    return RTR_OK;
+        return gather_point_bad(pts[k], nlen);
+    });
 }
 
 /* every lane of a group loads its point (k_gather_any<T, false>) unless RTR_GATHER_BROADCAST=1 asks for one load per group
@@ -41,16 +38,17 @@ int gather_launch(rtr_context* c, const rtr_render_params* rp, const rtr_gather_
     PointLaunch<GatherK> L = point_launch<GatherK>(c, rp, gp);
     L.k.pts = d_pts, L.k.out = d_out, L.k.n = (long long)n, L.k.point_base = point_base;
     const bool broadcast = !rp && gather_broadcast();
-    const size_t rec = sizeof(rtr_gather_out), lds = L.stack;
     int rc = RTR_OK;
-    const bool found =
-        rp ? dispatch_li(L.integ, L.trav, [&](auto i, auto t) { rc = launch_points(c, k_gather_li<decltype(i)::value, decltype(t)::value>, L.ds, L.k, rec, lds); })
-           : dispatch_trav(TravsTop{}, L.trav, [&](auto t) {
-                 constexpr int T = decltype(t)::value;
-                 rc = broadcast ? launch_points(c, k_gather_any<T, true>, L.ds, L.k, rec, lds) : launch_points(c, k_gather_any<T, false>, L.ds, L.k, rec, lds);
-             });
+    const auto launch = [&](auto kernel) {
+        rc = launch_records(c, "rtr_gather_*", kernel, L.stack, L.k.n, L.k.lg, point_args(L.ds, L.k, sizeof(rtr_gather_out)));
+    };
+    const bool found = rp ? dispatch_li(L.integ, L.trav, [&](auto i, auto t) { launch(k_gather_li<decltype(i)::value, decltype(t)::value>); })
+                          : dispatch_trav(TravsTop{}, L.trav, [&](auto t) {
+                                constexpr int T = decltype(t)::value;
+                                broadcast ? launch(k_gather_any<T, true>) : launch(k_gather_any<T, false>);
+                            });
     if (!found) return fail(c, RTR_ERR_UNSUPPORTED, "no gather kernel for traversal " + std::to_string(L.trav));
-    if (rc == RTR_OK) c->last_gather = rtr_debug_gather{L.integ, L.trav, broadcast, L.k.lg};
+    if (rc == RTR_OK) c->last_batch[RTR_DEBUG_GATHER] = rtr_debug_batch{L.integ, L.trav, broadcast, L.k.lg};
     return rc;
 }
 
@@ -119,12 +117,6 @@ int rtr_gather_ray(const rtr_gather_params* params, const rtr_gather_point* poin
         gather_direction(r * point->n[0], r * point->n[1], r * point->n[2], rng, d[0], d[1], d[2]);
         return true;
     });
-}
-
-int rtr_debug_last_gather(rtr_context* c, rtr_debug_gather* out, size_t size) {
-    if (!c || !out || size != sizeof(rtr_debug_gather)) return RTR_ERR_INVALID;
-    *out = c->last_gather;
-    return RTR_OK;
 }
 
 } /* extern "C" */

@@ -2,29 +2,18 @@
  * rtr_ibl.hip -- image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*): the parameter and environment checks,
  * the split of a table call into launches of bounded work, the two kernels of rt_ibl_kernels.h and their launches, the entries, and
  * the host-only pieces that need no context (rtr_brdf_entry_one, rtr_brdf_fetch_one, rtr_shade_ibl_one).  The entries'
- * common checks, the staging of the host entries and the body of the device entries are rt_batch.h's, shared with the
- * gathers, probes, captures and cube maps.
+ * common checks, the staging of the host entries, the body of the device entries, the chunked launcher of the shader and
+ * the cap hook are rt_batch.h's, shared with the other batch units; the staging of an environment is rt_ibl.h's.
  */
 #include "rt_batch.h"
 #include "rt_ibl_kernels.h"
-
-#include <cstdlib>
 
 using namespace rtr;
 
 namespace {
 
 constexpr int64_t kShadeSlice = (int64_t)1 << 20; /* queries (table entries) per slice of the host entries */
-constexpr long long kTableNodes = 1ll << 31;      /* nodes per launch at most */
-
-long long table_node_cap() {
-    long long cap = kTableNodes;
-    if (const char* e = getenv("RTR_TABLE_NODES")) { /* a test hook: lowers the cap */
-        const long long v = std::atoll(e);
-        if (v >= 1 && v < cap) cap = v;
-    }
-    return cap;
-}
+constexpr long long kTableNodes = 1ll << 31;      /* nodes per launch at most (RTR_TABLE_NODES, a test hook, lowers it) */
 
 /* what both table entries check before any device work: context, params, NULL; no scene is needed */
 int table_check(rtr_context* c, const rtr_brdf_params* bp, const void* out) {
@@ -34,12 +23,12 @@ int table_check(rtr_context* c, const rtr_brdf_params* bp, const void* out) {
 }
 
 /* the entries [e0, e1) of the table (numbered r * n_mu + c) into d_out, whose record 0 is e0.  No launch holds more than
- * table_node_cap() nodes: whole rows one above the other while they fit, else one row's columns in runs */
+ * that many nodes: whole rows one above the other while they fit, else one row's columns in runs */
 int table_launch(rtr_context* c, const rtr_brdf_params* bp, rtr_brdf_entry* d_out, long long e0, long long e1) {
     TableK K{};
     K.out = d_out, K.out_first = e0;
     K.n_mu = bp->n_mu, K.n_rough = bp->n_rough, K.M = bp->nodes;
-    const long long per_launch = std::max(1ll, table_node_cap() / (2ll * K.M * K.M)); /* entries */
+    const long long per_launch = std::max(1ll, env_cap("RTR_TABLE_NODES", kTableNodes) / (2ll * K.M * K.M)); /* entries */
     for (long long e = e0; e < e1;) {
         const int r = (int)(e / K.n_mu), col = (int)(e - (long long)r * K.n_mu);
         long long rows = 1;
@@ -65,13 +54,8 @@ int shade_check(rtr_context* c, const rtr_shade_env* env, const void* q, const v
     return batch_check(c, "rtr_shade_ibl", n, q && out);
 }
 int shade_launch(rtr_context* c, const ShadeK& K, const rtr_shade_query* d_q, rtr_gather_out* d_out, int64_t n) {
-    for (int64_t k0 = 0; k0 < n; k0 += kLaunchPoints) {
-        const long long m = std::min<long long>(n - k0, kLaunchPoints);
-        hipLaunchKernelGGL(k_shade_ibl, dim3((unsigned)((m + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), 0, c->stream, K, d_q + k0,
-                           d_out + k0, m);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("shade launch: ") + hipGetErrorString(e));
+    return launch_records(c, "rtr_shade_ibl", k_shade_ibl, 0, n, 0,
+                          [&](long long k0, long long m) { return std::make_tuple(K, d_q + k0, d_out + k0, m); });
 }
 
 } // namespace
@@ -130,29 +114,19 @@ int rtr_shade_ibl_one(const rtr_shade_env* env, const rtr_shade_query* q, rtr_ga
 int rtr_shade_ibl(rtr_context* c, const rtr_shade_env* env, const rtr_shade_query* q, rtr_gather_out* out, int64_t n) {
     if (int rc = shade_check(c, env, q, out, n)) return rc;
     if (n == 0) return RTR_OK;
-    for (int64_t k = 0; k < n; ++k) {
-        double nlen, vlen;
-        if (shade_query_bad(q[k], nlen, vlen))
-            return fail(c, RTR_ERR_INVALID, "rtr_shade_ibl: bad query at index " + std::to_string(k) +
-                                                " (a non-finite field, or a normal or view vector whose length is not in (0, inf))");
-    }
-    /* the environment's records stay at the head of the staging buffer for all slices, SH records, maps, chain, table: the
-     * first slice brings them */
-    static_assert(sizeof(rtr_probe_sh) % 16 == 0 && sizeof(rtr_probe_depth_texel) % 16 == 0 && sizeof(rtr_gather_out) % 16 == 0 &&
-                      sizeof(rtr_brdf_entry) % 16 == 0, "StagedIO::head_bytes");
+    if (int rc = records_check(c, "rtr_shade_ibl", "query", "a non-finite field, or a normal or view vector whose length is not in (0, inf)",
+                               n, [&](int64_t k) {
+                                   double nlen, vlen;
+                                   return shade_query_bad(q[k], nlen, vlen);
+                               }))
+        return rc;
+    /* the environment's arrays stay at the head of the staging buffer for all slices: the first slice brings them */
     const EnvBytes b = env_bytes(env);
-    const StagedIO io{b.probes + b.depth + b.chain + b.table, sizeof(rtr_shade_query), q, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
+    const StagedIO io{b.total(), sizeof(rtr_shade_query), q, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
     return staged_slices(c, n, kShadeSlice, io, [&](const Slice& s) {
-        char* probes = static_cast<char*>(s.head);
-        char *depth = probes + b.probes, *chain = depth + b.depth, *table = chain + b.chain;
-        if (s.k0 == 0) {
-            if (b.probes) HIPCHK(c, hipMemcpyAsync(probes, env->probes, b.probes, hipMemcpyHostToDevice, c->stream));
-            if (b.depth) HIPCHK(c, hipMemcpyAsync(depth, env->depth, b.depth, hipMemcpyHostToDevice, c->stream));
-            if (b.chain) HIPCHK(c, hipMemcpyAsync(chain, env->chain, b.chain, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(table, env->table, b.table, hipMemcpyHostToDevice, c->stream));
-        }
-        return shade_launch(c, shade_k(env, probes, depth, chain, table), static_cast<const rtr_shade_query*>(s.in),
-                            static_cast<rtr_gather_out*>(s.out[0]), s.m);
+        ShadeK K;
+        HIPCHK(c, env_stage(env, b, static_cast<char*>(s.head), s.k0 == 0, c->stream, K));
+        return shade_launch(c, K, static_cast<const rtr_shade_query*>(s.in), static_cast<rtr_gather_out*>(s.out[0]), s.m);
     });
 }
 
@@ -161,17 +135,11 @@ int rtr_shade_ibl_device(rtr_context* c, const rtr_shade_env* env, const rtr_sha
     if (int rc = shade_check(c, env, d_q, d_out, n)) return rc;
     if (n == 0) return RTR_OK;
     const EnvBytes b = env_bytes(env);
-    const uintptr_t in[5][2] = {{(uintptr_t)d_q, (size_t)n * sizeof(rtr_shade_query)},
-                                {b.probes ? (uintptr_t)env->probes : 0, b.probes},
-                                {b.depth ? (uintptr_t)env->depth : 0, b.depth},
-                                {b.chain ? (uintptr_t)env->chain : 0, b.chain},
-                                {(uintptr_t)env->table, b.table}};
-    const uintptr_t u0 = (uintptr_t)d_out, u1 = u0 + (size_t)n * sizeof(rtr_gather_out);
-    uintptr_t bits = u0;
-    for (const auto& a : in) {
-        if (a[1] && a[0] < u1 && u0 < a[0] + a[1]) return fail(c, RTR_ERR_INVALID, "rtr_shade_ibl_device: out overlaps an input");
-        bits |= a[0];
-    }
+    const uintptr_t u0 = (uintptr_t)d_out;
+    const size_t un = (size_t)n * sizeof(rtr_gather_out);
+    uintptr_t bits = u0 | (uintptr_t)d_q;
+    if (spans_overlap(u0, un, (uintptr_t)d_q, (size_t)n * sizeof(rtr_shade_query)) || env_overlaps(env, b, u0, un, bits))
+        return fail(c, RTR_ERR_INVALID, "rtr_shade_ibl_device: out overlaps an input");
     return device_entry(c, "rtr_shade_ibl_device", bits, blocking,
                         [&] { return shade_launch(c, shade_k(env, env->probes, env->depth, env->chain, env->table), d_q, d_out, n); });
 }

@@ -2,8 +2,8 @@
  * rtr_preview.hip -- baked previews (include/rtr_hip.h: rtr_preview_*): a frame shaded from a probe grid, a cube chain and
  * a BRDF table in one launch.  The parameter and region checks, the k_preview instantiations of rt_preview.h and the launch
  * that picks among them (the traversal rule of rt_select.h, as for k_query_closest), the entries, and the host-only
- * rtr_preview_ray.  The environment's rules are rt_ibl.h's, the staging of the host entries and the body of the device
- * entries rt_batch.h's.
+ * rtr_preview_ray.  The environment's rules, its staging and its overlap test are rt_ibl.h's, the staging of the host
+ * entries and the body of the device entries rt_batch.h's.
  */
 #include "rt_batch.h"
 #include "rt_preview.h"
@@ -67,8 +67,6 @@ int preview_launch(rtr_context* c, const rtr_preview_params* p, int y0, int y1, 
     return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("preview launch: ") + hipGetErrorString(e));
 }
 
-bool overlaps(uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return an && bn && a0 < b0 + bn && b0 < a0 + an; }
-
 } // namespace
 
 extern "C" {
@@ -114,24 +112,18 @@ int rtr_preview(rtr_context* c, const rtr_preview_params* p, const rtr_shade_env
                 int32_t* h_lit) {
     if (int rc = preview_check(c, "rtr_preview", p, h_linear != nullptr)) return rc;
     if (int rc = frame_check(c, "rtr_preview", p, env, row_stride)) return rc;
-    /* the environment's records, then the frame and the counts, rows packed: one buffer, the gathers' */
-    static_assert(sizeof(rtr_probe_sh) % 16 == 0 && sizeof(rtr_probe_depth_texel) % 16 == 0 && sizeof(rtr_gather_out) % 16 == 0 &&
-                      sizeof(rtr_brdf_entry) % 16 == 0, "the arrays follow each other 16-byte aligned");
+    /* the environment's arrays, then the frame and the counts, rows packed: one buffer, the gathers' */
     const Region R = region_of(p);
     const EnvBytes b = env_bytes(env);
     const size_t frame_bytes = ((size_t)R.pixels * 3 * sizeof(double) + 15) & ~(size_t)15;
     HIPCHK(c, hipSetDevice(c->device));
     (void)hipGetLastError(); /* a launch error of an earlier call is not this call's */
-    if (int rc = ensure(c, c->b_batch, b.probes + b.depth + b.chain + b.table + frame_bytes + (size_t)R.pixels * sizeof(int32_t))) return rc;
-    char* probes = static_cast<char*>(c->b_batch.p);
-    char *depth = probes + b.probes, *chain = depth + b.depth, *table = chain + b.chain;
-    double* d_linear = reinterpret_cast<double*>(table + b.table);
-    int32_t* d_lit = reinterpret_cast<int32_t*>(table + b.table + frame_bytes);
-    if (b.probes) HIPCHK(c, hipMemcpyAsync(probes, env->probes, b.probes, hipMemcpyHostToDevice, c->stream));
-    if (b.depth) HIPCHK(c, hipMemcpyAsync(depth, env->depth, b.depth, hipMemcpyHostToDevice, c->stream));
-    if (b.chain) HIPCHK(c, hipMemcpyAsync(chain, env->chain, b.chain, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(table, env->table, b.table, hipMemcpyHostToDevice, c->stream));
-    const ShadeK E = shade_k(env, probes, depth, chain, table);
+    if (int rc = ensure(c, c->b_batch, b.total() + frame_bytes + (size_t)R.pixels * sizeof(int32_t))) return rc;
+    char* base = static_cast<char*>(c->b_batch.p);
+    double* d_linear = reinterpret_cast<double*>(base + b.total());
+    int32_t* d_lit = reinterpret_cast<int32_t*>(base + b.total() + frame_bytes);
+    ShadeK E;
+    HIPCHK(c, env_stage(env, b, base, true, c->stream, E));
     if (int rc = preview_launch(c, p, p->y0, p->y1, &E, nullptr, d_linear, h_lit ? d_lit : nullptr, R.w)) return rc;
     HIPCHK(c, hipMemcpy2DAsync(h_linear, (size_t)row_stride * 3 * sizeof(double), d_linear, (size_t)R.w * 3 * sizeof(double),
                                (size_t)R.w * 3 * sizeof(double), R.h, hipMemcpyDeviceToHost, c->stream));
@@ -148,19 +140,12 @@ int rtr_preview_device(rtr_context* c, const rtr_preview_params* p, const rtr_sh
     if (int rc = frame_check(c, "rtr_preview_device", p, env, row_stride)) return rc;
     const Region R = region_of(p);
     const EnvBytes b = env_bytes(env);
-    const uintptr_t in[4][2] = {{b.probes ? (uintptr_t)env->probes : 0, b.probes},
-                                {b.depth ? (uintptr_t)env->depth : 0, b.depth},
-                                {b.chain ? (uintptr_t)env->chain : 0, b.chain},
-                                {(uintptr_t)env->table, b.table}};
     const size_t span = (size_t)(R.h - 1) * (size_t)row_stride + R.w; /* pixels from the first to behind the last one written */
     uintptr_t bits = (uintptr_t)d_linear | ((uintptr_t)d_lit << 1); /* the counts are 4-byte records */
-    for (const auto& a : in) {
-        if (overlaps((uintptr_t)d_linear, span * 3 * sizeof(double), a[0], a[1]) ||
-            (d_lit && overlaps((uintptr_t)d_lit, span * sizeof(int32_t), a[0], a[1])))
-            return fail(c, RTR_ERR_INVALID, "rtr_preview_device: an output overlaps an array of the environment");
-        bits |= a[0];
-    }
-    if (d_lit && overlaps((uintptr_t)d_linear, span * 3 * sizeof(double), (uintptr_t)d_lit, span * sizeof(int32_t)))
+    if (env_overlaps(env, b, (uintptr_t)d_linear, span * 3 * sizeof(double), bits) ||
+        (d_lit && env_overlaps(env, b, (uintptr_t)d_lit, span * sizeof(int32_t), bits)))
+        return fail(c, RTR_ERR_INVALID, "rtr_preview_device: an output overlaps an array of the environment");
+    if (d_lit && spans_overlap((uintptr_t)d_linear, span * 3 * sizeof(double), (uintptr_t)d_lit, span * sizeof(int32_t)))
         return fail(c, RTR_ERR_INVALID, "rtr_preview_device: linear overlaps lit");
     const ShadeK E = shade_k(env, env->probes, env->depth, env->chain, env->table);
     return device_entry(c, "rtr_preview_device", bits, blocking,

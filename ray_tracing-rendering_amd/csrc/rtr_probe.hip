@@ -1,10 +1,10 @@
 /*
- * rtr_probe.hip -- light probes (include/rtr_hip.h: rtr_probe_*, rtr_sh_*): the point and grid checks, the kernel choice
+ * rtr_probe.hip -- light probes (include/rtr_hip.h: rtr_probe_*, rtr_sh_*): the point checks, the kernel choice
  * among the 22 kernels held here (5 k_probe_any, 17 k_probe_li), k_probe_lookup and its launch, the entries, and the
  * host-only pieces that need no context (rtr_probe_ray, rtr_sh_basis, rtr_sh_irradiance, rtr_probe_lookup_one).  Which
- * k_probe_li a radiance call runs is the k_li family rule of rt_select.h, like the gathers'.  The entries' common checks,
- * the staging of the host entries, the body of the device entries, the launch set-up and the chunked launcher are
- * rt_batch.h's, shared with the gathers.
+ * k_probe_li a radiance call runs is the k_li family rule of rt_select.h, like the gathers'.  The grid rule is
+ * rt_render.h's.  The entries' common checks, the staging of the host entries, the body of the device entries, the launch
+ * set-up, the chunked launcher and the single-ray entry are rt_batch.h's, shared with the other batch units.
  */
 #include "rt_batch.h"
 
@@ -34,10 +34,7 @@ int probe_check(rtr_context* c, const rtr_render_params* rp, bool radiance, cons
     return points_check(c, "rtr_probe_*", rp, radiance, gp, n, pts && out);
 }
 int probe_check_points(rtr_context* c, const rtr_probe_point* pts, int64_t n) {
-    for (int64_t k = 0; k < n; ++k)
-        if (probe_point_bad(pts[k]))
-            return fail(c, RTR_ERR_INVALID, "rtr_probe_*: bad point at index " + std::to_string(k) + " (non-finite position)");
-    return RTR_OK;
+    return records_check(c, "rtr_probe_*", "point", kPositionRule, n, [&](int64_t k) { return probe_point_bad(pts[k]); });
 }
 
 /* launches over device arrays on the context stream; rp: radiance probes (k_probe_li), else visibility (k_probe_any) */
@@ -49,15 +46,14 @@ int probe_launch(rtr_context* c, const rtr_render_params* rp, const rtr_gather_p
     L.k.sum_word = (int)(L.stack / sizeof(int));
     const size_t lds = L.stack + (rp ? probe_sum_bytes() : 0);
     int rc = RTR_OK;
+    const auto launch = [&](auto kernel, size_t out_rec) {
+        rc = launch_records(c, "rtr_probe_*", kernel, lds, L.k.n, L.k.lg, point_args(L.ds, L.k, out_rec));
+    };
     const bool found =
-        rp ? dispatch_li(L.integ, L.trav, [&](auto i, auto t) {
-                 rc = launch_points(c, k_probe_li<decltype(i)::value, decltype(t)::value>, L.ds, L.k, sizeof(rtr_probe_sh), lds);
-             })
-           : dispatch_trav(TravsTop{}, L.trav, [&](auto t) {
-                 rc = launch_points(c, k_probe_any<decltype(t)::value>, L.ds, L.k, sizeof(rtr_probe_vis), lds);
-             });
+        rp ? dispatch_li(L.integ, L.trav, [&](auto i, auto t) { launch(k_probe_li<decltype(i)::value, decltype(t)::value>, sizeof(rtr_probe_sh)); })
+           : dispatch_trav(TravsTop{}, L.trav, [&](auto t) { launch(k_probe_any<decltype(t)::value>, sizeof(rtr_probe_vis)); });
     if (!found) return fail(c, RTR_ERR_UNSUPPORTED, "no probe kernel for traversal " + std::to_string(L.trav));
-    if (rc == RTR_OK) c->last_probe = rtr_debug_probe{L.integ, L.trav, L.k.lg};
+    if (rc == RTR_OK) c->last_batch[RTR_DEBUG_PROBE] = rtr_debug_batch{L.integ, L.trav, 0, L.k.lg};
     return rc;
 }
 
@@ -76,36 +72,16 @@ int probe_device(rtr_context* c, const rtr_render_params* rp, const rtr_gather_p
                         [&] { return probe_launch(c, rp, gp, gp->point_base, d_pts, d_out, n); });
 }
 
-bool probe_grid_ok(const rtr_probe_grid* g, std::string& why) {
-    if (!g) return (why = "null grid", false);
-    long long count = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (!__builtin_isfinite(g->origin[a])) return (why = "origin not finite", false);
-        if (!(__builtin_isfinite(g->spacing[a]) && g->spacing[a] > 0)) return (why = "spacing must be finite and > 0", false);
-        if (g->dims[a] < 1 || g->dims[a] > (1 << 24)) return (why = "dims must be >= 1 and their product <= 2^24", false);
-        count *= g->dims[a];
-        if (count > (1ll << 24)) return (why = "dims must be >= 1 and their product <= 2^24", false);
-    }
-    if (g->pad != 0) return (why = "pad must be 0", false);
-    return true;
-}
-
 /* what both lookup entries check before any device work, in this order: context, grid, n / NULL; no scene is needed */
 int lookup_check(rtr_context* c, const rtr_probe_grid* g, const void* probes, const void* q, const void* out, int64_t n) {
     if (!c) return RTR_ERR_INVALID;
-    std::string why;
-    if (!probe_grid_ok(g, why)) return fail(c, RTR_ERR_INVALID, "rtr_probe_lookup: " + why);
+    if (const char* why = probe_grid_why(g)) return fail(c, RTR_ERR_INVALID, std::string("rtr_probe_lookup: ") + why);
     return batch_check(c, "rtr_probe_lookup", n, probes && q && out);
 }
 int lookup_launch(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_sh* d_probes, const rtr_gather_point* d_q,
                   rtr_gather_out* d_out, int64_t n) {
-    for (int64_t k0 = 0; k0 < n; k0 += kLaunchPoints) {
-        const long long m = std::min<long long>(n - k0, kLaunchPoints);
-        hipLaunchKernelGGL(k_probe_lookup, dim3((unsigned)((m + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), 0, c->stream, *g,
-                           d_probes, d_q + k0, d_out + k0, m);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("probe lookup launch: ") + hipGetErrorString(e));
+    return launch_records(c, "rtr_probe_lookup", k_probe_lookup, 0, n, 0,
+                          [&](long long k0, long long m) { return std::make_tuple(*g, d_probes, d_q + k0, d_out + k0, m); });
 }
 
 } // namespace
@@ -164,9 +140,8 @@ int rtr_sh_irradiance(const double c[9][3], const double n[3], double E[3]) {
 }
 
 int rtr_probe_lookup_one(const rtr_probe_grid* g, const rtr_probe_sh* probes, const rtr_gather_point* query, rtr_gather_out* out) {
-    std::string why;
     double nlen;
-    if (!probe_grid_ok(g, why) || !probes || !query || !out || gather_point_bad(*query, nlen)) return RTR_ERR_INVALID;
+    if (probe_grid_why(g) || !probes || !query || !out || gather_point_bad(*query, nlen)) return RTR_ERR_INVALID;
     *out = probe_lookup_one(*g, probes, *query, nlen);
     return RTR_OK;
 }
@@ -175,15 +150,14 @@ int rtr_probe_lookup(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_sh
                      rtr_gather_out* out, int64_t n) {
     if (int rc = lookup_check(c, g, probes, q, out, n)) return rc;
     if (n == 0) return RTR_OK;
-    for (int64_t k = 0; k < n; ++k) {
-        double nlen;
-        if (gather_point_bad(q[k], nlen))
-            return fail(c, RTR_ERR_INVALID, "rtr_probe_lookup: bad query at index " + std::to_string(k) +
-                                                " (non-finite position / normal, or a normal whose length is not in (0, inf))");
-    }
+    if (int rc = records_check(c, "rtr_probe_lookup", "query", kGatherPointRule, n, [&](int64_t k) {
+            double nlen;
+            return gather_point_bad(q[k], nlen);
+        }))
+        return rc;
     /* the grid stays at the head of the staging buffer for all slices: the first one brings it */
     static_assert(sizeof(rtr_probe_sh) % 16 == 0, "StagedIO::head_bytes");
-    const size_t grid_bytes = (size_t)g->dims[0] * g->dims[1] * g->dims[2] * sizeof(rtr_probe_sh);
+    const size_t grid_bytes = (size_t)grid_probes(g) * sizeof(rtr_probe_sh);
     const StagedIO io{grid_bytes, sizeof(rtr_gather_point), q, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
     return staged_slices(c, n, kProbeSlice, io, [&](const Slice& s) {
         if (s.k0 == 0) HIPCHK(c, hipMemcpyAsync(s.head, probes, grid_bytes, hipMemcpyHostToDevice, c->stream));
@@ -198,12 +172,6 @@ int rtr_probe_lookup_device(rtr_context* c, const rtr_probe_grid* g, const rtr_p
     if (n == 0) return RTR_OK;
     return device_entry(c, "rtr_probe_lookup_device", (uintptr_t)d_probes | (uintptr_t)d_q | (uintptr_t)d_out, blocking,
                         [&] { return lookup_launch(c, g, d_probes, d_q, d_out, n); });
-}
-
-int rtr_debug_last_probe(rtr_context* c, rtr_debug_probe* out, size_t size) {
-    if (!c || !out || size != sizeof(rtr_debug_probe)) return RTR_ERR_INVALID;
-    *out = c->last_probe;
-    return RTR_OK;
 }
 
 } /* extern "C" */

@@ -3,8 +3,9 @@
  * k_probe_depth over TravsTop (the set k_query_closest has: a map is a batch of closest-hit queries made in registers),
  * k_probe_lookup_visible and its launch, the entries, and the host-only pieces that need no context
  * (rtr_probe_depth_defaults, rtr_probe_depth_ray, rtr_octa_encode / _decode, rtr_probe_lookup_visible_one).  The arithmetic
- * is rt_render.h's, written once for host and device.  The entries' common checks, the staging of the host entries, the
- * body of the device entries and the chunked launcher are rt_batch.h's, shared with the gathers, probes and captures.
+ * and the grid rule are rt_render.h's, written once for host and device; the lane-to-record map is group_begin of
+ * rt_kernels.h.  The entries' common checks, the staging of the host entries, the body of the device entries, the chunked
+ * launcher and the single-ray entry are rt_batch.h's, shared with the other batch units.
  */
 #include "rt_batch.h"
 
@@ -23,9 +24,7 @@ struct DepthLane {
     uint32_t probe; /* the probe's number under the seed: its index in the call + point_base */
 };
 RT_DEV bool depth_begin(const DepthK& K, DepthLane& L) {
-    const long long g = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
-    if (K.k0 + ((g & ~63ll) >> K.lg) >= K.n) return false; /* the whole wave is past the end */
-    L.k = K.k0 + (g >> K.lg), L.l = (int)(g & ((1 << K.lg) - 1));
+    if (!group_begin(K.k0, K.n, K.lg, L.k, L.l)) return false;
     const bool live = L.k < K.n;
     const long long texel = K.first + (live ? L.k : K.k0);
     const long long c = texel / K.TT;
@@ -115,29 +114,19 @@ int depth_launch(rtr_context* c, const rtr_probe_depth_params* dp, const rtr_pro
     K.samples = dp->samples, K.lg = gather_lg(dp->samples), K.seed = dp->seed, K.point_base = dp->point_base;
     K.jitter = dp->jitter, K.time = dp->time, K.t_min = dp->t_min, K.t_max = dp->t_max;
     int rc = RTR_OK;
-    if (!dispatch_trav(TravsTop{}, trav, [&](auto t) { rc = launch_texels(c, k_probe_depth<decltype(t)::value>, ds, K, lds); }))
+    if (!dispatch_trav(TravsTop{}, trav, [&](auto t) {
+            rc = launch_records(c, "rtr_probe_depth", k_probe_depth<decltype(t)::value>, lds, K.n, K.lg, texel_args(ds, K));
+        }))
         return no_per_ray_kernel(c, trav);
-    if (rc == RTR_OK) c->last_probe_depth = rtr_debug_probe_depth{trav, K.lg};
+    if (rc == RTR_OK) c->last_batch[RTR_DEBUG_PROBE_DEPTH] = rtr_debug_batch{-1, trav, 0, K.lg};
     return rc;
 }
 
-/* the grid rule of rtr_probe_lookup, and the maps' bound on top of it */
+/* the grid rule of rtr_probe_lookup, and the maps' rules on top of it */
 const char* visible_grid_why(const rtr_probe_grid* g, const rtr_probe_visible_params* vp) {
-    if (!g) return "null grid";
-    long long count = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (!__builtin_isfinite(g->origin[a])) return "origin not finite";
-        if (!(__builtin_isfinite(g->spacing[a]) && g->spacing[a] > 0)) return "spacing must be finite and > 0";
-        if (g->dims[a] < 1 || g->dims[a] > (1 << 24)) return "dims must be >= 1 and their product <= 2^24";
-        count *= g->dims[a];
-        if (count > (1ll << 24)) return "dims must be >= 1 and their product <= 2^24";
-    }
-    if (g->pad != 0) return "pad must be 0";
-    if (const char* why = probe_visible_params_why(vp)) return why;
-    if (count * vp->map_size * vp->map_size > (1ll << 24)) return "probes * map_size^2 must be <= 2^24";
-    return nullptr;
+    const char* why = probe_grid_why(g);
+    return why ? why : probe_maps_why(g, vp);
 }
-long long grid_probes(const rtr_probe_grid* g) { return (long long)g->dims[0] * g->dims[1] * g->dims[2]; }
 
 /* what the lookup entries check before any device work, in this order: context, grid, params, n / NULL; no scene is needed */
 int visible_check(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_visible_params* vp, bool arrays, int64_t n) {
@@ -147,13 +136,9 @@ int visible_check(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_visib
 }
 int visible_launch(rtr_context* c, const rtr_probe_grid* g, const rtr_probe_visible_params* vp, const rtr_probe_sh* d_probes,
                    const rtr_probe_depth_texel* d_depth, const rtr_gather_point* d_q, rtr_gather_out* d_out, int64_t n) {
-    for (int64_t k0 = 0; k0 < n; k0 += kLaunchPoints) {
-        const long long m = std::min<long long>(n - k0, kLaunchPoints);
-        hipLaunchKernelGGL(k_probe_lookup_visible, dim3((unsigned)((m + RTR_BLOCK - 1) / RTR_BLOCK)), dim3(RTR_BLOCK), 0, c->stream,
-                           *g, d_probes, d_depth, vp->map_size, vp->normal_bias, d_q + k0, d_out + k0, m);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RTR_OK : fail(c, RTR_ERR_DEVICE, std::string("visible lookup launch: ") + hipGetErrorString(e));
+    return launch_records(c, "rtr_probe_lookup_visible", k_probe_lookup_visible, 0, n, 0, [&](long long k0, long long m) {
+        return std::make_tuple(*g, d_probes, d_depth, vp->map_size, vp->normal_bias, d_q + k0, d_out + k0, m);
+    });
 }
 
 } // namespace
@@ -170,16 +155,12 @@ int rtr_probe_depth(rtr_context* c, const rtr_probe_depth_params* dp, const rtr_
                     int64_t n) {
     if (int rc = depth_check(c, dp, pts, out, n)) return rc;
     if (n == 0) return RTR_OK;
-    for (int64_t k = 0; k < n; ++k)
-        if (probe_point_bad(pts[k]))
-            return fail(c, RTR_ERR_INVALID, "rtr_probe_depth: bad probe at index " + std::to_string(k) + " (non-finite position)");
-    /* the probes stay at the head of the staging buffer for all slices: the first one brings them; a record is a texel */
-    const size_t head = ((size_t)n * sizeof(rtr_probe_point) + 15) & ~(size_t)15;
-    const StagedIO io{head, 0, nullptr, {sizeof(rtr_probe_depth_texel), 0}, {out, nullptr}};
-    return staged_slices(c, n * dp->map_size * dp->map_size, kDepthSlice, io, [&](const Slice& s) {
-        if (s.k0 == 0) HIPCHK(c, hipMemcpyAsync(s.head, pts, (size_t)n * sizeof(rtr_probe_point), hipMemcpyHostToDevice, c->stream));
-        return depth_launch(c, dp, static_cast<const rtr_probe_point*>(s.head), static_cast<rtr_probe_depth_texel*>(s.out[0]), s.k0, s.m);
-    });
+    if (int rc = records_check(c, "rtr_probe_depth", "probe", kPositionRule, n, [&](int64_t k) { return probe_point_bad(pts[k]); }))
+        return rc;
+    return staged_texels(c, pts, n, (long long)dp->map_size * dp->map_size, sizeof(rtr_probe_depth_texel), out, kDepthSlice,
+                         [&](const rtr_probe_point* d_pts, void* d_out, long long first, long long m) {
+                             return depth_launch(c, dp, d_pts, static_cast<rtr_probe_depth_texel*>(d_out), first, m);
+                         });
 }
 
 int rtr_probe_depth_device(rtr_context* c, const rtr_probe_depth_params* dp, const rtr_probe_point* d_pts,
@@ -192,17 +173,15 @@ int rtr_probe_depth_device(rtr_context* c, const rtr_probe_depth_params* dp, con
 
 int rtr_probe_depth_ray(const rtr_probe_depth_params* dp, const rtr_probe_point* point, int64_t index_in_call, int32_t a, int32_t b,
                         int32_t s, rtr_ray* out) {
-    if (probe_depth_params_why(dp) || !point || !out || index_in_call < 0 || probe_point_bad(*point)) return RTR_ERR_INVALID;
+    if (probe_depth_params_why(dp)) return RTR_ERR_INVALID;
     const int T = dp->map_size;
-    if (a < 0 || a >= T || b < 0 || b >= T || s < 0 || s >= dp->samples) return RTR_ERR_INVALID;
-    uint32_t rng = rtr_sample_seed_inline(dp->seed, T * T, b * T + a, (int32_t)((uint32_t)index_in_call + dp->point_base), s);
-    rtr_ray ray{};
-    depth_direction(T, a, b, dp->jitter, rng, ray.direction[0], ray.direction[1], ray.direction[2]);
-    for (int i = 0; i < 3; ++i) ray.origin[i] = point->p[i];
-    ray.time = dp->time, ray.t_min = dp->t_min, ray.t_max = dp->t_max;
-    ray.rng_state = rng;
-    *out = ray;
-    return RTR_OK;
+    if (a < 0 || a >= T || b < 0 || b >= T) return RTR_ERR_INVALID;
+    const RaySeed seed{dp->seed, dp->point_base, T * T, b * T + a, dp->samples, dp->time, dp->t_min, dp->t_max};
+    return sample_ray(seed, point ? point->p : nullptr, index_in_call, s, out, [&](uint32_t& rng, double* d) {
+        if (probe_point_bad(*point)) return false;
+        depth_direction(T, a, b, dp->jitter, rng, d[0], d[1], d[2]);
+        return true;
+    });
 }
 
 void rtr_octa_encode(const double d[3], double uv[2]) {
@@ -225,12 +204,11 @@ int rtr_probe_lookup_visible(rtr_context* c, const rtr_probe_grid* g, const rtr_
                              const rtr_probe_visible_params* vp, const rtr_gather_point* q, rtr_gather_out* out, int64_t n) {
     if (int rc = visible_check(c, g, vp, probes && depth && q && out, n)) return rc;
     if (n == 0) return RTR_OK;
-    for (int64_t k = 0; k < n; ++k) {
-        double nlen;
-        if (gather_point_bad(q[k], nlen))
-            return fail(c, RTR_ERR_INVALID, "rtr_probe_lookup_visible: bad query at index " + std::to_string(k) +
-                                                " (non-finite position / normal, or a normal whose length is not in (0, inf))");
-    }
+    if (int rc = records_check(c, "rtr_probe_lookup_visible", "query", kGatherPointRule, n, [&](int64_t k) {
+            double nlen;
+            return gather_point_bad(q[k], nlen);
+        }))
+        return rc;
     /* the SH records and behind them the maps stay at the head of the staging buffer for all slices: the first one brings them */
     static_assert(sizeof(rtr_probe_sh) % 16 == 0 && sizeof(rtr_probe_depth_texel) % 16 == 0, "StagedIO::head_bytes");
     const size_t sh_bytes = (size_t)grid_probes(g) * sizeof(rtr_probe_sh);
@@ -256,12 +234,6 @@ int rtr_probe_lookup_visible_device(rtr_context* c, const rtr_probe_grid* g, con
     return device_entry(c, "rtr_probe_lookup_visible_device",
                         (uintptr_t)d_probes | (uintptr_t)d_depth | (uintptr_t)d_q | (uintptr_t)d_out, blocking,
                         [&] { return visible_launch(c, g, vp, d_probes, d_depth, d_q, d_out, n); });
-}
-
-int rtr_debug_last_probe_depth(rtr_context* c, rtr_debug_probe_depth* out, size_t size) {
-    if (!c || !out || size != sizeof(rtr_debug_probe_depth)) return RTR_ERR_INVALID;
-    *out = c->last_probe_depth;
-    return RTR_OK;
 }
 
 } /* extern "C" */

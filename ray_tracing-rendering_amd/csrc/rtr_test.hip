@@ -266,28 +266,34 @@ int rtr_test_last_kernel(rtr_context* c, rtr_kernel_record* out, size_t size) {
     return rtr_debug_last_kernel(c, reinterpret_cast<rtr_debug_kernel*>(out), sizeof(rtr_debug_kernel));
 }
 
+/* the four records of the batch families are views of the one rtr_debug_batch */
+static int last_batch(rtr_context* c, int family, const void* out, size_t size, size_t record_size, rtr_debug_batch& b) {
+    if (!out || size != record_size) return RTR_ERR_INVALID;
+    return rtr_debug_last_batch(c, family, &b, sizeof b);
+}
 int rtr_test_last_gather(rtr_context* c, rtr_gather_record* out, size_t size) {
-    static_assert(sizeof(rtr_gather_record) == sizeof(rtr_debug_gather), "one layout");
-    if (size != sizeof(rtr_gather_record)) return RTR_ERR_INVALID;
-    return rtr_debug_last_gather(c, reinterpret_cast<rtr_debug_gather*>(out), sizeof(rtr_debug_gather));
+    rtr_debug_batch b;
+    if (int rc = last_batch(c, RTR_DEBUG_GATHER, out, size, sizeof *out, b)) return rc;
+    *out = rtr_gather_record{b.integ, b.trav, b.broadcast, b.lg};
+    return RTR_OK;
 }
-
 int rtr_test_last_probe(rtr_context* c, rtr_probe_record* out, size_t size) {
-    static_assert(sizeof(rtr_probe_record) == sizeof(rtr_debug_probe), "one layout");
-    if (size != sizeof(rtr_probe_record)) return RTR_ERR_INVALID;
-    return rtr_debug_last_probe(c, reinterpret_cast<rtr_debug_probe*>(out), sizeof(rtr_debug_probe));
+    rtr_debug_batch b;
+    if (int rc = last_batch(c, RTR_DEBUG_PROBE, out, size, sizeof *out, b)) return rc;
+    *out = rtr_probe_record{b.integ, b.trav, b.lg};
+    return RTR_OK;
 }
-
 int rtr_test_last_capture(rtr_context* c, rtr_capture_record* out, size_t size) {
-    static_assert(sizeof(rtr_capture_record) == sizeof(rtr_debug_capture), "one layout");
-    if (size != sizeof(rtr_capture_record)) return RTR_ERR_INVALID;
-    return rtr_debug_last_capture(c, reinterpret_cast<rtr_debug_capture*>(out), sizeof(rtr_debug_capture));
+    rtr_debug_batch b;
+    if (int rc = last_batch(c, RTR_DEBUG_CAPTURE, out, size, sizeof *out, b)) return rc;
+    *out = rtr_capture_record{b.integ, b.trav, b.lg};
+    return RTR_OK;
 }
-
 int rtr_test_last_probe_depth(rtr_context* c, rtr_probe_depth_record* out, size_t size) {
-    static_assert(sizeof(rtr_probe_depth_record) == sizeof(rtr_debug_probe_depth), "one layout");
-    if (size != sizeof(rtr_probe_depth_record)) return RTR_ERR_INVALID;
-    return rtr_debug_last_probe_depth(c, reinterpret_cast<rtr_debug_probe_depth*>(out), sizeof(rtr_debug_probe_depth));
+    rtr_debug_batch b;
+    if (int rc = last_batch(c, RTR_DEBUG_PROBE_DEPTH, out, size, sizeof *out, b)) return rc;
+    *out = rtr_probe_depth_record{b.trav, b.lg};
+    return RTR_OK;
 }
 
 int rtr_test_scene_plan(const rtr_scene_desc* scene, int32_t integrator, int32_t flags, rtr_scene_plan* out, int32_t* ref_flags,
