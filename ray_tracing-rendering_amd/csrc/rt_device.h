@@ -1881,6 +1881,159 @@ RT_DEV void pair_runs(const DScene& sc, const FInst& I, const PairRay& A, Real t
         ref += cnt;
     }
 }
+/* pair_runs<false> as ONE assembly statement: the run loop of one instance without spheres for both rays, with its own
+ * loops and labels.  The four hit-state values are read-write operands that the statement updates in place from entry to
+ * exit, so no register copy of them exists at a run's entry or at a back edge (the allocator emitted about fifteen moves
+ * per run around pair_rect's statements).  A side is pair_rect's text instruction for instruction; around it:
+ *   EXEC      saved once at entry -- the mask the routine is entered with, the same for every record -- and put back from
+ *             that pair after A's block and after B's block of every side; lanes that are off at entry are never written.
+ *   reference one scalar, incremented behind every side (rect runs: ref + k; boxes: r .. r + 5, six per box).
+ *   records   fetched into s[16:35], named in the text: an assembly operand cannot name a part of a wide register, and
+ *             s_load_dwordx16 wants its destination in one aligned piece (early-clobber outputs bound to those registers;
+ *             with this block the job-queue kernel spills the SGPRs it spilled before, with s[64:83] eighteen more).
+ *             Two rect records per trip (x16 + x4), the odd record (x8 + x2), a box (x8 + x4); one lgkmcnt(0) behind each
+ *             fetch and before its first use, nothing outstanding at exit.  The array is padded (rt_lower.h) and lowering
+ *             emits no run with count 0, so the box loop tests at its bottom.
+ *   run word  two 32-bit halves: the low one is shifted run by run and refilled from the high one when it is empty (a run's
+ *             byte is never 0).  A type other than XY / XZ / YZ / box ends the routine.
+ *   waits     the compiler's hazard recogniser sees nothing in here.  Its own output for pair_rect has one wait state
+ *             between a side's last v_add_f64 and the scalar read of EXEC, and one behind the s_mov_b64 to EXEC that ends
+ *             a side; both distances are kept, each filled with a scalar instruction that the loop needs anyway or with
+ *             s_nop 0 (DESIGN 4.2 says what is known about why).
+ * N: a number unique within the statement; W1: the instruction of the first wait state. */
+#define RT_PL_SIDE(N, W1, A0, A1, B0, B1, K, OK, DK, RK, OA, DA, OB, DB)                                                       \
+    "v_add_f64 %[nA], " K ", -%[a" OK "]\n\t"                                                                                   \
+    "v_add_f64 %[nB], " K ", -%[b" OK "]\n\t"                                                                                   \
+    "v_mul_f64 %[tA], %[nA], %[a" RK "]\n\t"                                                                                    \
+    "v_mul_f64 %[tB], %[nB], %[b" RK "]\n\t"                                                                                    \
+    "v_fma_f64 %[nA], -%[a" DK "], %[tA], %[nA]\n\t"                                                                            \
+    "v_fma_f64 %[nB], -%[b" DK "], %[tB], %[nB]\n\t"                                                                            \
+    "v_fma_f64 %[tA], %[nA], %[a" RK "], %[tA]\n\t"                                                                             \
+    "v_fma_f64 %[tB], %[nB], %[b" RK "], %[tB]\n\t"                                                                             \
+    "v_mul_f64 %[uA], %[tA], %[a" DA "]\n\t"                                                                                    \
+    "v_mul_f64 %[wA], %[tA], %[a" DB "]\n\t"                                                                                    \
+    "v_add_f64 %[uA], %[a" OA "], %[uA]\n\t"                                                                                    \
+    "v_add_f64 %[wA], %[a" OB "], %[wA]\n\t" W1 "\n\t"                                                                          \
+    "v_cmpx_ngt_f64 vcc, %[tmin], %[tA]\n\t"                                                                                    \
+    "v_cmpx_ngt_f64 vcc, %[tA], %[tmaxA]\n\t"                                                                                   \
+    "v_cmpx_ngt_f64 vcc, " A0 ", %[uA]\n\t"                                                                                     \
+    "v_cmpx_nlt_f64 vcc, " A1 ", %[uA]\n\t"                                                                                     \
+    "v_cmpx_ngt_f64 vcc, " B0 ", %[wA]\n\t"                                                                                     \
+    "v_cmpx_nlt_f64 vcc, " B1 ", %[wA]\n\t"                                                                                     \
+    "v_mov_b64 %[tmaxA], %[tA]\n\t"                                                                                             \
+    "v_mov_b32 %[hitA], %[ref]\n\t"                                                                                             \
+    "s_mov_b64 exec, %[save]\n\t"                                                                                               \
+    "v_cmpx_ngt_f64 vcc, %[tmin], %[tB]\n\t"                                                                                    \
+    "v_cmpx_ngt_f64 vcc, %[tB], %[tmaxB]\n\t"                                                                                   \
+    "s_cbranch_execz .Lplx%=_" #N "\n\t"                                                                                        \
+    "v_mul_f64 %[u], %[tB], %[b" DA "]\n\t"                                                                                     \
+    "v_add_f64 %[u], %[b" OA "], %[u]\n\t"                                                                                      \
+    "v_cmpx_ngt_f64 vcc, " A0 ", %[u]\n\t"                                                                                      \
+    "v_cmpx_nlt_f64 vcc, " A1 ", %[u]\n\t"                                                                                      \
+    "v_mul_f64 %[u], %[tB], %[b" DB "]\n\t"                                                                                     \
+    "v_add_f64 %[u], %[b" OB "], %[u]\n\t"                                                                                      \
+    "v_cmpx_ngt_f64 vcc, " B0 ", %[u]\n\t"                                                                                      \
+    "v_cmpx_nlt_f64 vcc, " B1 ", %[u]\n\t"                                                                                      \
+    "v_mov_b64 %[tmaxB], %[tB]\n\t"                                                                                             \
+    "v_mov_b32 %[hitB], %[ref]\n"                                                                                               \
+    ".Lplx%=_" #N ":\n\t"                                                                                                       \
+    "s_mov_b64 exec, %[save]\n\t"                                                                                               \
+    "s_add_u32 %[ref], %[ref], 1\n\t" /* the second wait state */
+#define RT_PL_XY(N, W1, A0, A1, B0, B1, K) RT_PL_SIDE(N, W1, A0, A1, B0, B1, K, "oz", "dz", "rz", "ox", "dx", "oy", "dy")
+#define RT_PL_XZ(N, W1, A0, A1, B0, B1, K) RT_PL_SIDE(N, W1, A0, A1, B0, B1, K, "oy", "dy", "ry", "ox", "dx", "oz", "dz")
+#define RT_PL_YZ(N, W1, A0, A1, B0, B1, K) RT_PL_SIDE(N, W1, A0, A1, B0, B1, K, "ox", "dx", "rx", "oy", "dy", "oz", "dz")
+/* a rect run of one type: two records per trip while two are left, then the odd one.  T: the type's side, L: its label */
+#define RT_PL_RECTS(T, L, N0, N1, N2)                                                                                           \
+    ".Lpl" L "%=:\n\t"                                                                                                          \
+    "s_cmp_lt_u32 %[cnt], 2\n\t"                                                                                                \
+    "s_cbranch_scc1 .Lpl" L "1%=\n"                                                                                             \
+    ".Lpl" L "2%=:\n\t"                                                                                                         \
+    "s_load_dwordx16 s[16:31], %[p], %[off]\n\t"                                                                                \
+    "s_load_dwordx4 s[32:35], %[p], %[off] offset:64\n\t"                                                                       \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                                  \
+    T(N0, "s_sub_u32 %[cnt], %[cnt], 2", "s[16:17]", "s[18:19]", "s[20:21]", "s[22:23]", "s[24:25]")                           \
+    T(N1, "s_add_u32 %[off], %[off], 80", "s[26:27]", "s[28:29]", "s[30:31]", "s[32:33]", "s[34:35]")                          \
+    "s_cmp_gt_u32 %[cnt], 1\n\t"                                                                                                \
+    "s_cbranch_scc1 .Lpl" L "2%=\n"                                                                                             \
+    ".Lpl" L "1%=:\n\t"                                                                                                         \
+    "s_cmp_eq_u32 %[cnt], 0\n\t"                                                                                                \
+    "s_cbranch_scc1 .Lplrun%=\n\t"                                                                                              \
+    "s_load_dwordx8 s[16:23], %[p], %[off]\n\t"                                                                                 \
+    "s_load_dwordx2 s[24:25], %[p], %[off] offset:32\n\t"                                                                       \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                                  \
+    T(N2, "s_add_u32 %[off], %[off], 40", "s[16:17]", "s[18:19]", "s[20:21]", "s[22:23]", "s[24:25]")                          \
+    "s_branch .Lplrun%=\n"
+typedef unsigned PairRegs16 __attribute__((ext_vector_type(16)));
+typedef unsigned PairRegs4 __attribute__((ext_vector_type(4)));
+RT_DEV void pair_runs_lean(const DScene& sc, const FInst& I, const PairRay& A, Real& tmaxA, int& hitA, const PairRay& B, Real& tmaxB,
+                           int& hitB) {
+    const RT_CONST_AS double* p = as_const(sc.fscan) + I.scan_first;
+    const Real tmin = 0.001;
+    unsigned lo = (unsigned)I.runs, hi = (unsigned)(I.runs >> 32);
+    int ref = I.ref_first;
+    Real nA, nB, tA, tB, uA, wA, u;
+    unsigned long long save;
+    unsigned off, cnt, typ;
+    PairRegs16 r16;
+    PairRegs4 r4;
+    static_assert(RT_RUN_BITS == 8 && RT_RUN_COUNT_BITS == 5 && RT_RUN_COUNT_MAX == 31 && RT_RUN_BOX == 5 &&
+                      RTR_NODE_XY_RECT - RTR_NODE_SPHERE == 2 && RTR_NODE_XZ_RECT - RTR_NODE_SPHERE == 3 &&
+                      RTR_NODE_YZ_RECT - RTR_NODE_SPHERE == 4,
+                  "pair_runs_lean decodes the run word with these numbers");
+    RT_REGION(RG_PAIR_RUNS);
+    asm volatile("s_mov_b64 %[save], exec\n\t"
+                 "s_mov_b32 %[off], 0\n"
+                 ".Lplrun%=:\n\t"
+                 "s_cmp_lg_u32 %[lo], 0\n\t"
+                 "s_cbranch_scc1 .Lpldec%=\n\t"
+                 "s_mov_b32 %[lo], %[hi]\n\t" /* the low half is empty: on with the high one, or done */
+                 "s_mov_b32 %[hi], 0\n\t"
+                 "s_cmp_eq_u32 %[lo], 0\n\t"
+                 "s_cbranch_scc1 .Lplend%=\n"
+                 ".Lpldec%=:\n\t"
+                 "s_and_b32 %[cnt], %[lo], 31\n\t"
+                 "s_bfe_u32 %[typ], %[lo], 0x30005\n\t" /* three bits from bit 5 */
+                 "s_lshr_b32 %[lo], %[lo], 8\n\t"
+                 "s_cmp_eq_u32 %[typ], 5\n\t"
+                 "s_cbranch_scc1 .Lplbox%=\n\t"
+                 "s_cmp_eq_u32 %[typ], 4\n\t"
+                 "s_cbranch_scc1 .Lplyz%=\n\t"
+                 "s_cmp_eq_u32 %[typ], 3\n\t"
+                 "s_cbranch_scc1 .Lplxz%=\n\t"
+                 "s_cmp_eq_u32 %[typ], 2\n\t"
+                 "s_cbranch_scc0 .Lplend%=\n" /* not a run of this routine */
+                 RT_PL_RECTS(RT_PL_XY, "xy", 0, 1, 2)
+                 RT_PL_RECTS(RT_PL_XZ, "xz", 3, 4, 5)
+                 RT_PL_RECTS(RT_PL_YZ, "yz", 6, 7, 8)
+                 ".Lplbox%=:\n\t" /* x0 x1 y0 y1 z0 z1; the six sides in list order z1 z0 y1 y0 x1 x0 */
+                 "s_load_dwordx8 s[16:23], %[p], %[off]\n\t"
+                 "s_load_dwordx4 s[24:27], %[p], %[off] offset:32\n\t"
+                 "s_waitcnt lgkmcnt(0)\n\t"
+                 RT_PL_XY(9, "s_add_u32 %[off], %[off], 48", "s[16:17]", "s[18:19]", "s[20:21]", "s[22:23]", "s[26:27]")
+                 RT_PL_XY(10, "s_sub_u32 %[cnt], %[cnt], 1", "s[16:17]", "s[18:19]", "s[20:21]", "s[22:23]", "s[24:25]")
+                 RT_PL_XZ(11, "s_nop 0", "s[16:17]", "s[18:19]", "s[24:25]", "s[26:27]", "s[22:23]")
+                 RT_PL_XZ(12, "s_nop 0", "s[16:17]", "s[18:19]", "s[24:25]", "s[26:27]", "s[20:21]")
+                 RT_PL_YZ(13, "s_nop 0", "s[20:21]", "s[22:23]", "s[24:25]", "s[26:27]", "s[18:19]")
+                 RT_PL_YZ(14, "s_nop 0", "s[20:21]", "s[22:23]", "s[24:25]", "s[26:27]", "s[16:17]")
+                 "s_cmp_lg_u32 %[cnt], 0\n\t"
+                 "s_cbranch_scc1 .Lplbox%=\n\t"
+                 "s_branch .Lplrun%=\n"
+                 ".Lplend%=:"
+                 : [tmaxA] "+v"(tmaxA), [hitA] "+v"(hitA), [tmaxB] "+v"(tmaxB), [hitB] "+v"(hitB), [lo] "+s"(lo), [hi] "+s"(hi),
+                   [ref] "+s"(ref), [nA] "=&v"(nA), [nB] "=&v"(nB), [tA] "=&v"(tA), [tB] "=&v"(tB), [uA] "=&v"(uA), [wA] "=&v"(wA),
+                   [u] "=&v"(u), [save] "=&s"(save), [off] "=&s"(off), [cnt] "=&s"(cnt), [typ] "=&s"(typ), "=&{s[16:31]}"(r16),
+                   "=&{s[32:35]}"(r4)
+                 : [aox] "v"(A.o.x), [aoy] "v"(A.o.y), [aoz] "v"(A.o.z), [adx] "v"(A.d.x), [ady] "v"(A.d.y), [adz] "v"(A.d.z),
+                   [arx] "v"(A.q.rx), [ary] "v"(A.q.ry), [arz] "v"(A.q.rz), [box] "v"(B.o.x), [boy] "v"(B.o.y), [boz] "v"(B.o.z),
+                   [bdx] "v"(B.d.x), [bdy] "v"(B.d.y), [bdz] "v"(B.d.z), [brx] "v"(B.q.rx), [bry] "v"(B.q.ry), [brz] "v"(B.q.rz),
+                   [p] "s"(p), [tmin] "s"(tmin)
+                 : "vcc", "scc"); /* (the records are read-only for the whole launch: no memory clobber) */
+}
+#undef RT_PL_RECTS
+#undef RT_PL_XY
+#undef RT_PL_XZ
+#undef RT_PL_YZ
+#undef RT_PL_SIDE
 /* ---- frames of the pair cast -----------------------------------------------------------------------------------------
  * Both rays of a pair into the frame of an instance whose chain has one of the shapes RT_SHAPE_NONE .. RT_SHAPE_RT, as
  * ONE straight-line block per shape: the shape is wave-uniform and decided once, A and B go through the block together,
@@ -2016,7 +2169,8 @@ __device__ __forceinline__ bool trace_pair_frames(const DScene& sc, V3 ao, V3 ad
  * both t_max back to what they were (the hot loop keeps no copy of them).  Per frame the pair scans return the bits of
  * the single scans (tests/test_pair_shapes.py), so a whole cast through the single scans returns the bits of a cast
  * through any mixture of the two.  (The copies of the hit state -- a_tmax, a_ref, b_tmax, b_ref -- at every run entry and
- * back edge of pair_runs are not the scans' doing: they are still emitted with the scans gone) */
+ * back edge of pair_runs are not the scans' doing: pair_runs<...> still has them, about fifteen moves per run, in every
+ * kernel that compiles it.  The kernels of this path run pair_runs_lean, which has none: DESIGN 4.2.) */
 /* The votes of the pair path are taken from the compares' own masks: a verdict is the 64-bit lane mask its v_cmp wrote,
  * verdicts are combined as wave-uniform integers on the scalar unit, and a vote passes when the combined mask is EXEC (a
  * v_cmp writes 0 for a lane that is not here).  Written through __all or a ballot of the combined bool, every vote costs
@@ -2039,6 +2193,7 @@ RT_DEV PairMask pair_origin_in(V3 o) { return pair_below(o.x, 0x1p80) & pair_bel
 RT_DEV bool pair_vote(PairMask m) { return m == __builtin_amdgcn_read_exec(); }
 /* One frame of the cast from both rays IN that frame (d.y: the world rays'): the frame's reciprocals, its one vote and
  * the runs.  `sy`: the verdicts on both d.y.  false: the vote failed, nothing of the frame was scanned. */
+template <bool ROUTINE>
 RT_DEV bool pair_scan(const DScene& sc, const FInst& I, V3 ao, Real adx, Real ady, Real adz, Real way, V3 bo, Real bdx, Real bdy,
                       Real bdz, Real wby, PairMask sy, Real atime, Real& a_tmax, int& a_ref, Real& b_tmax, int& b_ref) {
     PairRay A, B;
@@ -2061,10 +2216,14 @@ RT_DEV bool pair_scan(const DScene& sc, const FInst& I, V3 ao, Real adx, Real ad
         pair_runs<true>(sc, I, A, atime, a_tmax, a_ref, B, b_tmax, b_ref);
     } else {
         if (!pair_vote(s)) return false;
-        pair_runs<false>(sc, I, A, atime, a_tmax, a_ref, B, b_tmax, b_ref);
+        if (ROUTINE)
+            pair_runs_lean(sc, I, A, a_tmax, a_ref, B, b_tmax, b_ref);
+        else
+            pair_runs<false>(sc, I, A, atime, a_tmax, a_ref, B, b_tmax, b_ref);
     }
     return true;
 }
+template <bool ROUTINE>
 __device__ __forceinline__ bool trace_pair_recast(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
                                                   V3 bo, V3 bd, Real& b_tmax, int& b_ref) {
     a_ref = -1, a_inst = -1, b_ref = -1;
@@ -2098,7 +2257,7 @@ __device__ __forceinline__ bool trace_pair_recast(const DScene& sc, V3 ao, V3 ad
         }
         /* (one call for every shape: a second one fed from the world rays' own registers saves the world frame's ten
          * copies and costs the lean job-queue kernel two spilled VGPRs) */
-        if (!pair_scan(sc, I, F.ao, F.adx, ad.y, F.adz, way, F.bo, F.bdx, bd.y, F.bdz, wby, sy, atime, a_tmax, a_ref, b_tmax, b_ref))
+        if (!pair_scan<ROUTINE>(sc, I, F.ao, F.adx, ad.y, F.adz, way, F.bo, F.bdx, bd.y, F.bdz, wby, sy, atime, a_tmax, a_ref, b_tmax, b_ref))
             return false;
         RT_REGION(RG_PAIR_SETUP);
         if (a_ref >= I.ref_first) a_inst = ii;
@@ -2108,12 +2267,18 @@ __device__ __forceinline__ bool trace_pair_recast(const DScene& sc, V3 ao, V3 ad
 /* The pair cast of a kernel.  RECAST: trace_pair_recast, and the caller runs pair_recast when it returns false; otherwise
  * the per-frame fallback, which always returns true.  Which kernel takes which is pair_recasts() (rt_kernels.h);
  * -DRTR_PAIR_FRAME_FALLBACK gives every kernel the fallback: the stand-in for the tree before the recast in before /
- * after measurements. */
-template <bool RECAST = true>
+ * after measurements.  ROUTINE: the runs of a frame without spheres go through pair_runs_lean and not pair_runs<false>
+ * (pair_runs_routine(), rt_kernels.h; recasting kernels only); -DRTR_PAIR_RUNS_PLAIN gives every kernel pair_runs<false>:
+ * the stand-in for the tree before the routine. */
+template <bool RECAST = true, bool ROUTINE = RECAST>
 __device__ __forceinline__ bool trace_pair(const DScene& sc, V3 ao, V3 ad, Real atime, Real& a_tmax, int& a_ref, int& a_inst,
                                            V3 bo, V3 bd, Real& b_tmax, int& b_ref, const Stack st) {
 #ifndef RTR_PAIR_FRAME_FALLBACK
-    if (RECAST) return trace_pair_recast(sc, ao, ad, atime, a_tmax, a_ref, a_inst, bo, bd, b_tmax, b_ref);
+#ifdef RTR_PAIR_RUNS_PLAIN
+    if (RECAST) return trace_pair_recast<false>(sc, ao, ad, atime, a_tmax, a_ref, a_inst, bo, bd, b_tmax, b_ref);
+#else
+    if (RECAST) return trace_pair_recast<ROUTINE>(sc, ao, ad, atime, a_tmax, a_ref, a_inst, bo, bd, b_tmax, b_ref);
+#endif
 #endif
     return trace_pair_frames(sc, ao, ad, atime, a_tmax, a_ref, a_inst, bo, bd, b_tmax, b_ref, st);
 }

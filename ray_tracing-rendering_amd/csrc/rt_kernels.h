@@ -50,6 +50,10 @@ constexpr int mega_waves(int integ, int trav, int ms) {
  * (k_mega_queue<4,4,2>: eight more spilled SGPRs) and four of their accumulator-pass kernels spilled two to four more
  * VGPRs: they compile the fallback's text, as before (profiles/r24_recast.txt). */
 constexpr bool pair_recasts(int ms) { return ms == RT_MS_LEAN; }
+/* Which of them run the rect and box runs of a frame as the one hand-placed routine (pair_runs_lean, rt_device.h): the same
+ * set, whose kernels are bound by instruction issue and whose scenes hold no sphere.  Every other pair-cast kernel keeps
+ * pair_runs<...>, and so does every kernel of a -DRTR_PAIR_RUNS_PLAIN build. */
+constexpr bool pair_runs_routine(int ms) { return ms == RT_MS_LEAN; }
 
 /* Per-lane path state that the ray casts do not touch lives in LDS between shading steps
  * ("parked"), so it does not occupy VGPRs across the traversal loops: throughput, radiance of
@@ -462,7 +466,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
             } else {
                 so = mk(0.0, 0.0, 0.0);
             }
-            if (!trace_pair<pair_recasts(MS)>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st)) {
+            if (!trace_pair<pair_recasts(MS), pair_runs_routine(MS)>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st)) {
                 /* a vote failed (cold): the two single casts, both t_max from where they came (a request that is not
                  * pending is the dummy already: nothing stale to replace) */
                 a_tmax = cast_a ? RT_INF : 0.0;
@@ -913,7 +917,7 @@ __global__ void __launch_bounds__(RTR_BLOCK, mega_waves(INTEG, TRAV, MS))
          * stays resident has passed every vote once. */
         const V3 swi = pk.get3(PK_SWI);
         Real b_tmax = pk.get(PK_STMAX);
-        if (!trace_pair<pair_recasts(MS)>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st)) {
+        if (!trace_pair<pair_recasts(MS), pair_runs_routine(MS)>(sc, ps.ro, ps.rd, ps.tm, a_tmax, a_ref, a_inst, so, swi, b_tmax, b_ref, st)) {
             /* a vote failed (cold): both rays again through the single casts, their t_max from where they came (the
              * request is not yet marked dead).  After this cast the resident request is dead in every lane, and takes
              * the prologue's direction and a zero origin: a stale direction or origin that failed its verdict would fail
