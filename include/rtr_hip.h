@@ -1506,6 +1506,93 @@ int rtr_preview(rtr_context* ctx, const rtr_preview_params* params, const rtr_sh
 int rtr_preview_device(rtr_context* ctx, const rtr_preview_params* params, const rtr_shade_env* env, double* d_linear,
                        int64_t row_stride, int32_t* d_lit, int blocking);
 
+/* ---- capture sets: several captures of one scene, each with the box it was taken in, read with parallax correction ----
+ * rtr_shade_ibl reads its one chain along R as if the environment were infinitely far away, which is right only at the
+ * capture's centre.  A CAPTURE SET holds 1 <= C <= 16 captures.  Capture k has a VOLUME: the point `centre` it was taken
+ * from, the PROXY box its reflections are projected onto (the room), the REACH box of points it serves and the width `fade`
+ * of the band inside the reach box over which its weight rises from 0 to 1.  A lookup at a point p along d intersects the
+ * ray (p, d) with the proxy box of every capture that reaches p, reads that capture towards the intersection as seen from
+ * its centre (box projection), and blends the captures by their weights.  Everything below is FP64 with + - * / and
+ * compares only, no fused multiply-add (every product is rounded before its add), plain IEEE divisions; min(a, b) is b when
+ * b < a and a otherwise.  A host (the _one forms), numpy and the device give the same bits.
+ *
+ * Rules of a set, RTR_ERR_INVALID in every entry below, before any device work, context first: n_captures in 1 .. 16;
+ * fallback -1 or in 0 .. n_captures - 1; volumes not NULL; every number of every volume finite; per axis
+ * proxy_lo < centre < proxy_hi strictly and proxy_lo <= reach_lo <= reach_hi <= proxy_hi; fade >= 0 with a clear sign bit
+ * (-0.0 is rejected: one spelling per set, like cos_cut).  The struct and its volumes are HOST data, copied at the call;
+ * the cap of 16 lets the set travel as a kernel argument.
+ *
+ * LAYOUT: `levels`, `n_levels` and `n_records` describe the chain of ONE capture, exactly as for rtr_cube_chain_lookup, and
+ * every capture of a set has that plan.  The set's array holds C * n_records records level-major: cube k of level i
+ * (S_i = its face size) starts at record levels[i].offset * C + k * 6 * S_i^2.  Level i of all captures is therefore
+ * contiguous in the [cube][face][row][column] order that rtr_capture_cube(_device) with n = C and
+ * rtr_cube_filter(_device) with n_cubes = C write: a set is baked in place with one capture call, and one filter call per
+ * further level, and no copy.  With C = 1 it is the chain layout.
+ *
+ * SET LOOKUP of one query (p, d, alpha).  The query is BAD when one of its seven numbers is not finite or when
+ * sqrt((d.x*d.x + d.y*d.y) + d.z*d.z) is not in (0, inf); a BAD query gives the zero record; pad is not read.
+ * For k = 0 .. C - 1 in order, from acc = +0.0 per channel, wsum = +0.0, count = 0, used = 0:
+ *   m = p[0] - reach_lo[0];  m = min(m, reach_hi[0] - p[0]);  then for a = 1, 2:  m = min(m, p[a] - reach_lo[a]),
+ *     m = min(m, reach_hi[a] - p[a])
+ *   m < 0: capture k does not reach p.
+ *   w = 1.0 when fade == 0, else min(m / fade, 1.0).   Not w > 0: capture k does not reach p (a point on the face of a
+ *     faded reach box is outside, on the face of an unfaded one inside).
+ *   box projection: t = +inf;  for a = 0, 1, 2:  d[a] > 0: ta = (proxy_hi[a] - p[a]) / d[a];  d[a] < 0:
+ *     ta = (proxy_lo[a] - p[a]) / d[a];  a zero component of either sign takes no part;  t = min(t, ta)
+ *     x[a] = p[a] + t * d[a],   dk[a] = x[a] - centre[a]
+ *   Xk = the CHAIN LOOKUP of (dk, alpha) in cube k (rtr_cube_chain_lookup's function over the level starts above).
+ *     Xk invalid: the whole result is the zero record.
+ *   acc[ch] = acc[ch] + w * Xk.v[ch];  wsum = wsum + w;  count += Xk.count;  used += 1
+ * Then  used > 0: v = (1.0 / wsum) * acc per channel, that count, valid 1.
+ *       used == 0 and fallback >= 0: the CHAIN LOOKUP of (d, alpha) in cube `fallback`, its record as it is -- no projection,
+ *         no weight: the "sky" capture, and rtr_cube_chain_lookup / rtr_shade_ibl as a special case.
+ *       used == 0 and fallback < 0: the zero record.
+ * A lane whose point no capture reaches reads no record but the fallback's.  Stated limit: the lobe is not widened with
+ * the distance to the proxy; alpha is used as given.
+ *
+ * rtr_capture_set_lookup: set, levels (against n_records) and n < 0 / NULL arrays as above; n == 0 is RTR_OK; no scene is
+ * needed.  The host entry stages the C * n_records records once at the head of the buffer of the gathers' host entries and
+ * the queries in slices of 2^20 (RTR_SET_SLICE=n, read at every call, lowers that: a test hook, the bits do not depend on
+ * it); the device entry is stream-ordered behind the bakes (8-byte aligned pointers, out must not overlap an input,
+ * `blocking`).  rtr_capture_set_lookup_one is host only, the function the kernel calls; RTR_ERR_INVALID for a bad set or
+ * chain (checked against the level ends) or a NULL pointer, RTR_OK and the zero record for a BAD query.
+ *
+ * rtr_shade_ibl_set(_device, _one) is rtr_shade_ibl word for word, except that the SPECULAR record is the SET LOOKUP of
+ * (q.p, R, alpha): env->chain is the set's array, env->levels / n_levels / n_records describe one capture, and the size and
+ * overlap rules use C * n_records.  rtr_preview_set(_device) is rtr_preview with that shader.  `set` is not checked, and
+ * may be NULL, when SPECULAR is not selected. */
+typedef struct rtr_capture_volume {   /* 128 bytes */
+    double centre[3];                 /* where the capture was taken */
+    double proxy_lo[3], proxy_hi[3];  /* the box reflections are projected onto (the room) */
+    double reach_lo[3], reach_hi[3];  /* the box of points this capture serves */
+    double fade;                      /* width of the band inside `reach` over which the weight rises from 0 to 1 */
+} rtr_capture_volume;
+typedef struct rtr_capture_set {      /* host struct, copied at the call */
+    int32_t n_captures, fallback;     /* 1 .. 16;  -1 or 0 .. n_captures - 1 */
+    const rtr_capture_volume* volumes;/* host */
+} rtr_capture_set;
+typedef struct rtr_capture_query {    /* 64 bytes */
+    double p[3], d[3], alpha, pad;    /* d need not be normalised; alpha = roughness^2; pad 0 */
+} rtr_capture_query;
+
+int rtr_capture_set_lookup(rtr_context* ctx, const rtr_capture_set* set, const rtr_cube_level* levels, int32_t n_levels,
+                           const rtr_gather_out* records, int64_t n_records, const rtr_capture_query* queries,
+                           rtr_gather_out* out, int64_t n);
+int rtr_capture_set_lookup_device(rtr_context* ctx, const rtr_capture_set* set, const rtr_cube_level* levels, int32_t n_levels,
+                                  const rtr_gather_out* d_records, int64_t n_records, const rtr_capture_query* d_queries,
+                                  rtr_gather_out* d_out, int64_t n, int blocking);
+int rtr_capture_set_lookup_one(const rtr_capture_set* set, const rtr_cube_level* levels, int32_t n_levels,
+                               const rtr_gather_out* records, const rtr_capture_query* query, rtr_gather_out* out);
+int rtr_shade_ibl_set(rtr_context* ctx, const rtr_shade_env* env, const rtr_capture_set* set, const rtr_shade_query* queries,
+                      rtr_gather_out* out, int64_t n);
+int rtr_shade_ibl_set_device(rtr_context* ctx, const rtr_shade_env* env, const rtr_capture_set* set,
+                             const rtr_shade_query* d_queries, rtr_gather_out* d_out, int64_t n, int blocking);
+int rtr_shade_ibl_set_one(const rtr_shade_env* env, const rtr_capture_set* set, const rtr_shade_query* query, rtr_gather_out* out);
+int rtr_preview_set(rtr_context* ctx, const rtr_preview_params* params, const rtr_shade_env* env, const rtr_capture_set* set,
+                    double* h_linear, int64_t row_stride, int32_t* h_lit);
+int rtr_preview_set_device(rtr_context* ctx, const rtr_preview_params* params, const rtr_shade_env* env,
+                           const rtr_capture_set* set, double* d_linear, int64_t row_stride, int32_t* d_lit, int blocking);
+
 /* Host-only: the checks rtr_upload_scene() runs before touching the GPU.  Returns RTR_OK,
  * RTR_ERR_INVALID or RTR_ERR_UNSUPPORTED; `msg` (may be NULL) receives the reason. */
 int rtr_validate_scene(const rtr_scene_desc* scene, rtr_scene_info* info, char* msg, size_t msg_cap);

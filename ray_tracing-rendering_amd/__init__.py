@@ -27,10 +27,11 @@ def __getattr__(name):
                 "probe_rays", "sh_basis", "sh_irradiance", "probe_grid", "capture_defaults", "capture_ray", "capture_rays",
                 "cube_lookup_host", "latlong_direction", "cube_to_latlong", "write_rgbe", "cube_filter_defaults",
                 "cube_filter_host", "cube_chain_plan", "cube_chain_lookup_host", "cube_queries", "brdf_table_host",
-                "brdf_fetch_one", "shade_env", "shade_queries", "shade_ibl_one"):
+                "brdf_fetch_one", "shade_env", "shade_queries", "shade_ibl_one", "capture_set", "capture_queries",
+                "capture_set_lookup_host", "shade_ibl_set_one"):
         from . import native
         return getattr(native, name)
-    if name in ("Renderer", "RenderBuffer", "ProbeGrid", "Cubemap", "CubeChain", "BrdfTable", "IblEnvironment", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):
+    if name in ("Renderer", "RenderBuffer", "ProbeGrid", "Cubemap", "CubeChain", "CaptureSet", "BrdfTable", "IblEnvironment", "render_sharded", "tiles_of_rank", "gather_tiles", "pack_tiles", "unpack_tiles"):
         from . import renderer
         return getattr(renderer, name)
     raise AttributeError(name)

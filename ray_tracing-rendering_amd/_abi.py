@@ -222,6 +222,26 @@ BRDF_MAX = 256
 SHADE_DIFFUSE, SHADE_SPECULAR = 1, 2
 
 
+class CaptureVolumeC(C.Structure):
+    """rtr_capture_volume (include/rtr_hip.h): where a capture of a set was taken, the box its reflections are projected
+    onto, the box of points it serves and the width of the band over which its weight rises"""
+    _fields_ = [("centre", C.c_double * 3), ("proxy_lo", C.c_double * 3), ("proxy_hi", C.c_double * 3),
+                ("reach_lo", C.c_double * 3), ("reach_hi", C.c_double * 3), ("fade", C.c_double)]
+
+
+class CaptureSetC(C.Structure):
+    """rtr_capture_set (include/rtr_hip.h): 1 .. 16 volumes and the capture read where none reaches (-1: none)"""
+    _fields_ = [("n_captures", C.c_int32), ("fallback", C.c_int32), ("volumes", C.c_void_p)]
+
+
+CAPTURE_VOLUME_SIZE, CAPTURE_SET_SIZE, CAPTURE_SET_MAX = 128, 16, 16
+assert C.sizeof(CaptureVolumeC) == CAPTURE_VOLUME_SIZE and C.sizeof(CaptureSetC) == CAPTURE_SET_SIZE
+CAPTURE_VOLUME_DTYPE = np.dtype([("centre", "<f8", (3,)), ("proxy_lo", "<f8", (3,)), ("proxy_hi", "<f8", (3,)),
+                                 ("reach_lo", "<f8", (3,)), ("reach_hi", "<f8", (3,)), ("fade", "<f8")])  # rtr_capture_volume
+CAPTURE_QUERY_DTYPE = np.dtype([("p", "<f8", (3,)), ("d", "<f8", (3,)), ("alpha", "<f8"), ("pad", "<f8")])  # rtr_capture_query
+assert CAPTURE_VOLUME_DTYPE.itemsize == 128 and CAPTURE_QUERY_DTYPE.itemsize == 64
+
+
 class PreviewParamsC(C.Structure):
     """rtr_preview_params (include/rtr_hip.h): a frame shaded from a bake, rtr_preview / rtr_preview_samples"""
     _fields_ = [("image_width", C.c_int32), ("image_height", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),

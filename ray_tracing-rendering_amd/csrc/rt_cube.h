@@ -1,5 +1,6 @@
 /*
- * rt_cube.h -- the kernels of the filtered cube maps (include/rtr_hip.h: rtr_cube_filter*, rtr_cube_chain_lookup*),
+ * rt_cube.h -- the kernels of the filtered cube maps (include/rtr_hip.h: rtr_cube_filter*, rtr_cube_chain_lookup*,
+ * rtr_capture_set_lookup*),
  * instantiated and launched by rtr_cube.hip.  Their arithmetic is rt_render.h's, shared with the host forms.
  */
 #pragma once
@@ -96,5 +97,16 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_cube_chain_lookup(const ChainK C,
                                                                   rtr_gather_out* __restrict__ out, long long n) {
     const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
     if (k >= n) return;
-    out[k] = cube_chain_lookup_one(C.lv, C.n, texels, queries[k]);
+    out[k] = cube_chain_lookup_one(C.lv, C.n, texels, queries[k], 1, 0);
+}
+
+/* rtr_capture_set_lookup: one lane per query (capture_set_lookup_one of rt_render.h): a loop over the captures with one chain
+ * lookup in it; `texels` holds the set level-major */
+__global__ void __launch_bounds__(RTR_BLOCK) k_capture_set_lookup(const SetK S, const ChainK C, const rtr_gather_out* __restrict__ texels,
+                                                                   const rtr_capture_query* __restrict__ queries,
+                                                                   rtr_gather_out* __restrict__ out, long long n) {
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const rtr_capture_query q = queries[k];
+    out[k] = capture_set_lookup_one(S, C.lv, C.n, texels, q.p, q.d, q.alpha);
 }

@@ -129,8 +129,10 @@ RT_HD bool shade_query_bad(const rtr_shade_query& q, double& nlen, double& vlen)
     return !(ok && nlen > 0.0 && nlen < __builtin_huge_val() && vlen > 0.0 && vlen < __builtin_huge_val());
 }
 /* rtr_shade_ibl of one query that is not BAD.  The phases follow each other: the diffuse record is down to three doubles
- * and a count before the chain is read */
-RT_HD rtr_gather_out shade_ibl_one(const ShadeK& K, const rtr_shade_query& q, double nlen, double vlen) {
+ * and a count before the chain is read.  SET: rtr_shade_ibl_set -- K.texels holds the capture set *S level-major, K.chain the
+ * plan of one capture, and the specular record is the set lookup of (q.p, R, alpha); every other line is shared */
+template <bool SET = false>
+RT_HD rtr_gather_out shade_ibl_one(const ShadeK& K, const rtr_shade_query& q, double nlen, double vlen, const SetK* S = nullptr) {
     rtr_gather_out o;
     o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
     const double rn = 1 / nlen, rv = 1 / vlen;
@@ -154,7 +156,11 @@ RT_HD rtr_gather_out shade_ibl_one(const ShadeK& K, const rtr_shade_query& q, do
         rtr_cube_query cq;
         for (int a = 0; a < 3; ++a) cq.d[a] = (2.0 * mu) * N[a] - Vd[a];
         cq.alpha = rough * rough;
-        const rtr_gather_out rec = cube_chain_lookup_one(K.chain.lv, K.chain.n, K.texels, cq);
+        rtr_gather_out rec;
+        if constexpr (SET)
+            rec = capture_set_lookup_one(*S, K.chain.lv, K.chain.n, K.texels, q.p, cq.d, cq.alpha);
+        else
+            rec = cube_chain_lookup_one(K.chain.lv, K.chain.n, K.texels, cq, 1, 0);
         if (!rec.valid) return o;
         X[0] = rec.v[0], X[1] = rec.v[1], X[2] = rec.v[2], count += rec.count;
     }
@@ -195,18 +201,35 @@ inline const char* env_why(const rtr_shade_env* e) {
     return nullptr;
 }
 
-/* bytes of the arrays of a valid environment: of a part that is not selected 0 */
+/* the set forms (rtr_shade_ibl_set, rtr_preview_set): the environment's rules, and the set's when SPECULAR reads it */
+inline const char* env_set_why(const rtr_shade_env* e, const rtr_capture_set* set) {
+    if (const char* why = env_why(e)) return why;
+    return e->parts & RTR_SHADE_SPECULAR ? capture_set_why(set) : nullptr;
+}
+/* the captures whose chains e->chain holds: the set's when SPECULAR reads it */
+inline long long env_cubes(const rtr_shade_env* e, const rtr_capture_set* set) {
+    return e->parts & RTR_SHADE_SPECULAR ? set->n_captures : 1;
+}
+/* the kernel's argument of the set of a valid pair: empty, and not read, without SPECULAR */
+inline SetK env_set_k(const rtr_shade_env* e, const rtr_capture_set* set) {
+    SetK none{};
+    none.fallback = -1;
+    return e->parts & RTR_SHADE_SPECULAR ? set_k(set) : none;
+}
+
+/* bytes of the arrays of a valid environment: of a part that is not selected 0.  `cubes`: e->chain holds that many chains
+ * of e->n_records records each (a capture set) */
 struct EnvBytes {
     size_t probes, depth, chain, table;
     size_t total() const { return probes + depth + chain + table; }
 };
-inline EnvBytes env_bytes(const rtr_shade_env* e) {
+inline EnvBytes env_bytes(const rtr_shade_env* e, long long cubes = 1) {
     EnvBytes b{0, 0, 0, (size_t)e->n_mu * e->n_rough * sizeof(rtr_brdf_entry)};
     if (e->parts & RTR_SHADE_DIFFUSE) {
         b.probes = (size_t)grid_probes(e->grid) * sizeof(rtr_probe_sh);
         if (e->visible) b.depth = (size_t)grid_probes(e->grid) * e->visible->map_size * e->visible->map_size * sizeof(rtr_probe_depth_texel);
     }
-    if (e->parts & RTR_SHADE_SPECULAR) b.chain = (size_t)e->n_records * sizeof(rtr_gather_out);
+    if (e->parts & RTR_SHADE_SPECULAR) b.chain = (size_t)cubes * (size_t)e->n_records * sizeof(rtr_gather_out);
     return b;
 }
 /* the kernel's argument of a valid environment whose arrays are at these addresses */

@@ -1,5 +1,6 @@
 /*
- * rt_ibl_kernels.h -- the two kernels of image-based shading (rt_ibl.h has their arithmetic), instantiated and launched by
+ * rt_ibl_kernels.h -- the kernels of image-based shading (rt_ibl.h has their arithmetic), the set form of the shader among
+ * them, instantiated and launched by
  * rtr_ibl.hip alone: a unit that only composes shade_ibl_one (rtr_preview.hip) includes rt_ibl.h without them.
  */
 #pragma once
@@ -61,5 +62,18 @@ __global__ void __launch_bounds__(RTR_BLOCK) k_shade_ibl(const ShadeK K, const r
     rtr_gather_out o;
     o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
     if (!shade_query_bad(q, nlen, vlen)) o = shade_ibl_one(K, q, nlen, vlen);
+    out[k] = o;
+}
+
+/* rtr_shade_ibl_set: the same lane per query; the specular record comes from the capture set S (capture_set_lookup_one) */
+__global__ void __launch_bounds__(RTR_BLOCK) k_shade_ibl_set(const ShadeK K, const SetK S, const rtr_shade_query* __restrict__ queries,
+                                                              rtr_gather_out* __restrict__ out, long long n) {
+    const long long k = (long long)blockIdx.x * RTR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const rtr_shade_query q = queries[k];
+    double nlen, vlen;
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    if (!shade_query_bad(q, nlen, vlen)) o = shade_ibl_one<true>(K, q, nlen, vlen, &S);
     out[k] = o;
 }

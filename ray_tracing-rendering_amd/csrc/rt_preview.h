@@ -104,8 +104,9 @@ RT_DEV rtr_preview_sample preview_sample(const DScene& sc, const PreviewK& P, in
 #ifndef RTR_PREVIEW_WAVES
 #define RTR_PREVIEW_WAVES 2
 #endif
-template <int TRAV, bool SAMPLES>
-__global__ void __launch_bounds__(RTR_BLOCK) __attribute__((amdgpu_waves_per_eu(RTR_PREVIEW_WAVES))) k_preview(const DScene sc, const PreviewK P, const ShadeK E) {
+/* the lane's pixel, the body of every kernel below.  SET: the shader reads the capture set *S (rtr_preview_set) */
+template <int TRAV, bool SAMPLES, bool SET>
+RT_DEV void preview_pixel(const DScene& sc, const PreviewK& P, const ShadeK& E, const SetK* S) {
     extern __shared__ int lds_stack[];
     const Stack st{lds_stack + threadIdx.x};
     const int i = P.x0 + (int)blockIdx.x * 16 + (int)(threadIdx.x & 15);
@@ -128,7 +129,7 @@ __global__ void __launch_bounds__(RTR_BLOCK) __attribute__((amdgpu_waves_per_eu(
         }
         double nlen, vlen;
         if (shade_query_bad(r.q, nlen, vlen)) continue;
-        const rtr_gather_out o = shade_ibl_one(E, r.q, nlen, vlen);
+        const rtr_gather_out o = shade_ibl_one<SET>(E, r.q, nlen, vlen, S);
         if (!o.valid) continue;
         for (int c = 0; c < 3; ++c) acc[c] = acc[c] + o.v[c];
         ++lit;
@@ -137,4 +138,13 @@ __global__ void __launch_bounds__(RTR_BLOCK) __attribute__((amdgpu_waves_per_eu(
     const double scale = 1.0 / kk;
     for (int c = 0; c < 3; ++c) P.linear[pixel * 3 + c] = scale * acc[c];
     if (P.lit) P.lit[pixel] = lit;
+}
+template <int TRAV, bool SAMPLES>
+__global__ void __launch_bounds__(RTR_BLOCK) __attribute__((amdgpu_waves_per_eu(RTR_PREVIEW_WAVES))) k_preview(const DScene sc, const PreviewK P, const ShadeK E) {
+    preview_pixel<TRAV, SAMPLES, false>(sc, P, E, nullptr);
+}
+/* rtr_preview_set: the frame form with the capture set as a fourth argument */
+template <int TRAV>
+__global__ void __launch_bounds__(RTR_BLOCK) __attribute__((amdgpu_waves_per_eu(RTR_PREVIEW_WAVES))) k_preview_set(const DScene sc, const PreviewK P, const ShadeK E, const SetK S) {
+    preview_pixel<TRAV, false, true>(sc, P, E, &S);
 }

@@ -744,9 +744,14 @@ struct ChainK {
     rtr_cube_level lv[RTR_CHAIN_MAX_LEVELS];
     int n;
 };
-/* rtr_cube_chain_lookup of one query over the records of a valid chain */
+/* where level `l` of cube `cube` starts in an array that holds `cubes` chains level-major (a capture set; include/rtr_hip.h:
+ * CAPTURE SETS): a single chain is (1, 0), the level's own offset */
+RT_HD long long cube_level_base(const rtr_cube_level& l, long long cubes, long long cube) {
+    return l.offset * cubes + cube * (6ll * l.face_size * l.face_size);
+}
+/* rtr_cube_chain_lookup of one query over the records of a valid chain: chain `cube` of `cubes` */
 RT_HD rtr_gather_out cube_chain_lookup_one(const rtr_cube_level* lv, int n, const rtr_gather_out* __restrict__ texels,
-                                           const rtr_cube_query& q) {
+                                           const rtr_cube_query& q, long long cubes, long long cube) {
     rtr_gather_out o;
     o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
     const double x = q.d[0], y = q.d[1], z = q.d[2];
@@ -761,12 +766,120 @@ RT_HD rtr_gather_out cube_chain_lookup_one(const rtr_cube_level* lv, int n, cons
         if (lv[k].alpha <= a) i = k;
     if (n >= 2 && i > n - 2) i = n - 2;
     const double t = n >= 2 ? (a - lv[i].alpha) / (lv[i + 1].alpha - lv[i].alpha) : 0.0;
-    const rtr_gather_out x0 = cube_seam_lookup(lv[i].face_size, texels + lv[i].offset, x, y, z);
+    const rtr_gather_out x0 = cube_seam_lookup(lv[i].face_size, texels + cube_level_base(lv[i], cubes, cube), x, y, z);
     if (t == 0) return x0;
-    const rtr_gather_out x1 = cube_seam_lookup(lv[i + 1].face_size, texels + lv[i + 1].offset, x, y, z);
+    const rtr_gather_out x1 = cube_seam_lookup(lv[i + 1].face_size, texels + cube_level_base(lv[i + 1], cubes, cube), x, y, z);
     if (!x0.valid || !x1.valid) return o;
     for (int ch = 0; ch < 3; ++ch) o.v[ch] = (1.0 - t) * x0.v[ch] + t * x1.v[ch];
     o.count = x0.count + x1.count, o.valid = 1;
+    return o;
+}
+
+/* ---- capture sets (include/rtr_hip.h: rtr_capture_set*) ----
+ * The arithmetic of that contract, written once for host (the _one forms, the entries' checks) and device
+ * (k_capture_set_lookup of rt_cube.h, the set forms of the shader and of the preview). */
+#define RTR_CAPTURE_SET_MAX 16
+/* a valid set as a kernel argument, next to ChainK / ShadeK: 2056 bytes.  The loop below indexes it with a counter that is
+ * the same in every lane, so a volume comes in through scalar loads */
+struct SetK {
+    int n, fallback;
+    rtr_capture_volume vol[RTR_CAPTURE_SET_MAX];
+};
+/* why the set is none, or nullptr */
+inline const char* capture_set_why(const rtr_capture_set* s) {
+    if (!s) return "null capture set";
+    if (s->n_captures < 1 || s->n_captures > RTR_CAPTURE_SET_MAX) return "n_captures outside 1 .. 16";
+    if (s->fallback < -1 || s->fallback >= s->n_captures) return "fallback outside -1 .. n_captures - 1";
+    if (!s->volumes) return "null volumes";
+    for (int k = 0; k < s->n_captures; ++k) {
+        const rtr_capture_volume& v = s->volumes[k];
+        bool finite = __builtin_isfinite(v.fade);
+        for (int a = 0; a < 3; ++a)
+            finite = finite && __builtin_isfinite(v.centre[a]) && __builtin_isfinite(v.proxy_lo[a]) && __builtin_isfinite(v.proxy_hi[a]) &&
+                     __builtin_isfinite(v.reach_lo[a]) && __builtin_isfinite(v.reach_hi[a]);
+        if (!finite) return "a volume has a non-finite number";
+        for (int a = 0; a < 3; ++a) {
+            if (!(v.proxy_lo[a] < v.centre[a] && v.centre[a] < v.proxy_hi[a])) return "a centre is not strictly inside its proxy box";
+            if (!(v.proxy_lo[a] <= v.reach_lo[a] && v.reach_lo[a] <= v.reach_hi[a] && v.reach_hi[a] <= v.proxy_hi[a]))
+                return "a reach box is empty or leaves its proxy box";
+        }
+        if (!(v.fade >= 0.0) || __builtin_signbit(v.fade)) return "fade outside [+0, inf)";
+    }
+    return nullptr;
+}
+inline SetK set_k(const rtr_capture_set* s) {
+    SetK S{};
+    S.n = s->n_captures, S.fallback = s->fallback;
+    for (int k = 0; k < s->n_captures; ++k) S.vol[k] = s->volumes[k];
+    return S;
+}
+/* BAD: one of the seven numbers is not finite, or the length of d is not in (0, inf) */
+RT_HD bool capture_query_bad(const double* p, const double* d, double alpha) {
+    bool ok = __builtin_isfinite(alpha);
+    for (int a = 0; a < 3; ++a) ok = ok && __builtin_isfinite(p[a]) && __builtin_isfinite(d[a]);
+    const double len = __builtin_sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    return !(ok && len > 0.0 && len < __builtin_huge_val());
+}
+/* SET LOOKUP of (p, d, alpha) over the level-major records of a valid set and the chain plan of one capture.  One loop with
+ * one chain lookup in it: round S.n is the fallback's, taken when no capture reached p, so the lookup's text and registers
+ * exist once.  A capture that does not reach p costs its six subtractions; a lane no capture reaches and without a fallback
+ * reads no record */
+RT_HD rtr_gather_out capture_set_lookup_one(const SetK& S, const rtr_cube_level* lv, int n, const rtr_gather_out* __restrict__ texels,
+                                            const double* p, const double* d, double alpha) {
+    rtr_gather_out o;
+    o.v[0] = o.v[1] = o.v[2] = 0.0, o.count = 0, o.valid = 0;
+    if (capture_query_bad(p, d, alpha)) return o;
+    double acc[3] = {0.0, 0.0, 0.0}, wsum = 0.0;
+    int count = 0, used = 0;
+#pragma unroll 1
+    for (int k = 0; k <= S.n; ++k) {
+        rtr_cube_query cq;
+        cq.alpha = alpha;
+        double w = 1.0;
+        int cube = k;
+        if (k < S.n) {
+            const rtr_capture_volume& V = S.vol[k];
+            double m = p[0] - V.reach_lo[0];
+            for (int a = 0; a < 3; ++a) {
+                if (a > 0) {
+                    const double lo = p[a] - V.reach_lo[a];
+                    m = lo < m ? lo : m;
+                }
+                const double hi = V.reach_hi[a] - p[a];
+                m = hi < m ? hi : m;
+            }
+            if (m < 0) continue;
+            if (V.fade != 0) {
+                const double r = m / V.fade;
+                w = 1.0 < r ? 1.0 : r;
+            }
+            if (!(w > 0)) continue;
+            double t = __builtin_huge_val();
+            for (int a = 0; a < 3; ++a) {
+                if (d[a] > 0) {
+                    const double ta = (V.proxy_hi[a] - p[a]) / d[a];
+                    t = ta < t ? ta : t;
+                } else if (d[a] < 0) {
+                    const double ta = (V.proxy_lo[a] - p[a]) / d[a];
+                    t = ta < t ? ta : t;
+                }
+            }
+            for (int a = 0; a < 3; ++a) cq.d[a] = (p[a] + t * d[a]) - V.centre[a];
+        } else {
+            if (used > 0 || S.fallback < 0) break;
+            for (int a = 0; a < 3; ++a) cq.d[a] = d[a];
+            cube = S.fallback;
+        }
+        const rtr_gather_out X = cube_chain_lookup_one(lv, n, texels, cq, S.n, cube);
+        if (k == S.n) return X;
+        if (!X.valid) return o;
+        for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + w * X.v[ch];
+        wsum = wsum + w, count += X.count, ++used;
+    }
+    if (used == 0) return o;
+    const double r = 1.0 / wsum;
+    o.v[0] = r * acc[0], o.v[1] = r * acc[1], o.v[2] = r * acc[2];
+    o.count = count, o.valid = 1;
     return o;
 }
 

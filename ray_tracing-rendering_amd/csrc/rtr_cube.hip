@@ -2,7 +2,8 @@
  * rtr_cube.hip -- filtered cube maps (include/rtr_hip.h: rtr_cube_filter*, rtr_cube_chain_*): the parameter and chain checks,
  * the split of a filter call into launches of bounded work, the two kernels of rt_cube.h and their launches, the entries,
  * and the host-only pieces that need no context (rtr_cube_filter_defaults, rtr_cube_filter_one, rtr_cube_chain_plan,
- * rtr_cube_chain_lookup_one).  The entries' common checks, the staging of the host entries, the body of the device
+ * rtr_cube_chain_lookup_one), and the lookup of a capture set (rtr_capture_set_lookup*: the set's rules and arithmetic are
+ * rt_render.h's, the kernel rt_cube.h's).  The entries' common checks, the staging of the host entries, the body of the device
  * entries, the chunked launcher of the chain lookup and the cap hook are rt_batch.h's, shared with the other batch units.
  */
 #include "rt_batch.h"
@@ -84,9 +85,67 @@ int chain_launch(rtr_context* c, const rtr_cube_level* lv, int n_levels, const r
                           [&](long long k0, long long m) { return std::make_tuple(C, d_texels, d_q + k0, d_out + k0, m); });
 }
 
+/* what both set lookups check before any device work: context, set, the chain of one capture, n / NULL; no scene is needed */
+int set_check(rtr_context* c, const rtr_capture_set* set, const rtr_cube_level* lv, int32_t n_levels, const void* texels,
+              int64_t n_records, const void* q, const void* out, int64_t n) {
+    if (!c) return RTR_ERR_INVALID;
+    if (const char* why = capture_set_why(set)) return fail(c, RTR_ERR_INVALID, std::string("rtr_capture_set_lookup: ") + why);
+    if (n_records < 0) return fail(c, RTR_ERR_INVALID, "rtr_capture_set_lookup: negative n_records");
+    if (const char* why = cube_chain_why(lv, n_levels, n_records))
+        return fail(c, RTR_ERR_INVALID, std::string("rtr_capture_set_lookup: ") + why);
+    return batch_check(c, "rtr_capture_set_lookup", n, texels && q && out);
+}
+int set_launch(rtr_context* c, const rtr_capture_set* set, const rtr_cube_level* lv, int n_levels, const rtr_gather_out* d_texels,
+               const rtr_capture_query* d_q, rtr_gather_out* d_out, int64_t n) {
+    ChainK C{};
+    for (int i = 0; i < n_levels; ++i) C.lv[i] = lv[i];
+    C.n = n_levels;
+    const SetK S = set_k(set);
+    return launch_records(c, "rtr_capture_set_lookup", k_capture_set_lookup, 0, n, 0,
+                          [&](long long k0, long long m) { return std::make_tuple(S, C, d_texels, d_q + k0, d_out + k0, m); });
+}
+
 } // namespace
 
 extern "C" {
+
+int rtr_capture_set_lookup_one(const rtr_capture_set* set, const rtr_cube_level* lv, int32_t n_levels, const rtr_gather_out* texels,
+                               const rtr_capture_query* q, rtr_gather_out* out) {
+    if (capture_set_why(set) || cube_chain_why(lv, n_levels, -1) || !texels || !q || !out) return RTR_ERR_INVALID;
+    *out = capture_set_lookup_one(set_k(set), lv, n_levels, texels, q->p, q->d, q->alpha);
+    return RTR_OK;
+}
+
+int rtr_capture_set_lookup(rtr_context* c, const rtr_capture_set* set, const rtr_cube_level* lv, int32_t n_levels,
+                           const rtr_gather_out* texels, int64_t n_records, const rtr_capture_query* q, rtr_gather_out* out, int64_t n) {
+    if (int rc = set_check(c, set, lv, n_levels, texels, n_records, q, out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    /* the records of all captures stay at the head of the staging buffer for all slices: the first one brings them.
+     * RTR_SET_SLICE, a test hook, lowers the slice */
+    const size_t set_bytes = (size_t)set->n_captures * (size_t)n_records * sizeof(rtr_gather_out);
+    const StagedIO io{set_bytes, sizeof(rtr_capture_query), q, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
+    return staged_slices(c, n, env_cap("RTR_SET_SLICE", kCubeSlice), io, [&](const Slice& s) {
+        if (s.k0 == 0) HIPCHK(c, hipMemcpyAsync(s.head, texels, set_bytes, hipMemcpyHostToDevice, c->stream));
+        return set_launch(c, set, lv, n_levels, static_cast<const rtr_gather_out*>(s.head), static_cast<const rtr_capture_query*>(s.in),
+                          static_cast<rtr_gather_out*>(s.out[0]), s.m);
+    });
+}
+
+int rtr_capture_set_lookup_device(rtr_context* c, const rtr_capture_set* set, const rtr_cube_level* lv, int32_t n_levels,
+                                  const rtr_gather_out* d_texels, int64_t n_records, const rtr_capture_query* d_q,
+                                  rtr_gather_out* d_out, int64_t n, int blocking) {
+    if (int rc = set_check(c, set, lv, n_levels, d_texels, n_records, d_q, d_out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    const uintptr_t u0 = (uintptr_t)d_out;
+    const size_t un = (size_t)n * sizeof(rtr_gather_out);
+    const size_t set_bytes = (size_t)set->n_captures * (size_t)n_records * sizeof(rtr_gather_out);
+    const auto meets = [&](uintptr_t b0, size_t bn) { return u0 < b0 + bn && b0 < u0 + un; };
+    if (meets((uintptr_t)d_texels, set_bytes) || meets((uintptr_t)d_q, (size_t)n * sizeof(rtr_capture_query)))
+        return fail(c, RTR_ERR_INVALID, "rtr_capture_set_lookup_device: out overlaps an input");
+    return device_entry(c, "rtr_capture_set_lookup_device", (uintptr_t)d_texels | (uintptr_t)d_q | u0, blocking,
+                        [&] { return set_launch(c, set, lv, n_levels, d_texels, d_q, d_out, n); });
+}
+
 
 void rtr_cube_filter_defaults(rtr_cube_filter_params* p) {
     if (!p) return;
@@ -167,7 +226,7 @@ int rtr_cube_chain_plan(int32_t S, int32_t n_levels, rtr_cube_level* levels, int
 int rtr_cube_chain_lookup_one(const rtr_cube_level* lv, int32_t n_levels, const rtr_gather_out* texels, const rtr_cube_query* q,
                               rtr_gather_out* out) {
     if (cube_chain_why(lv, n_levels, -1) || !texels || !q || !out) return RTR_ERR_INVALID;
-    *out = cube_chain_lookup_one(lv, n_levels, texels, *q);
+    *out = cube_chain_lookup_one(lv, n_levels, texels, *q, 1, 0);
     return RTR_OK;
 }
 

@@ -1,7 +1,8 @@
 /*
  * rtr_ibl.hip -- image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*): the parameter and environment checks,
  * the split of a table call into launches of bounded work, the two kernels of rt_ibl_kernels.h and their launches, the entries, and
- * the host-only pieces that need no context (rtr_brdf_entry_one, rtr_brdf_fetch_one, rtr_shade_ibl_one).  The entries'
+ * the host-only pieces that need no context (rtr_brdf_entry_one, rtr_brdf_fetch_one, rtr_shade_ibl_one), and the set forms
+ * of the shader (rtr_shade_ibl_set*: the same entries with a capture set behind the environment).  The entries'
  * common checks, the staging of the host entries, the body of the device entries, the chunked launcher of the shader and
  * the cap hook are rt_batch.h's, shared with the other batch units; the staging of an environment is rt_ibl.h's.
  */
@@ -58,9 +59,66 @@ int shade_launch(rtr_context* c, const ShadeK& K, const rtr_shade_query* d_q, rt
                           [&](long long k0, long long m) { return std::make_tuple(K, d_q + k0, d_out + k0, m); });
 }
 
+/* the set forms: the same checks with the set's rules behind the environment's; without SPECULAR the set is not looked at */
+int shade_set_check(rtr_context* c, const rtr_shade_env* env, const rtr_capture_set* set, const void* q, const void* out, int64_t n) {
+    if (!c) return RTR_ERR_INVALID;
+    if (const char* why = env_set_why(env, set)) return fail(c, RTR_ERR_INVALID, std::string("rtr_shade_ibl_set: ") + why);
+    return batch_check(c, "rtr_shade_ibl_set", n, q && out);
+}
+int shade_set_launch(rtr_context* c, const ShadeK& K, const SetK& S, const rtr_shade_query* d_q, rtr_gather_out* d_out, int64_t n) {
+    return launch_records(c, "rtr_shade_ibl_set", k_shade_ibl_set, 0, n, 0,
+                          [&](long long k0, long long m) { return std::make_tuple(K, S, d_q + k0, d_out + k0, m); });
+}
+
 } // namespace
 
 extern "C" {
+
+int rtr_shade_ibl_set_one(const rtr_shade_env* env, const rtr_capture_set* set, const rtr_shade_query* q, rtr_gather_out* out) {
+    double nlen, vlen;
+    if (env_set_why(env, set) || !q || !out || shade_query_bad(*q, nlen, vlen)) return RTR_ERR_INVALID;
+    const SetK S = env_set_k(env, set);
+    *out = shade_ibl_one<true>(shade_k(env, env->probes, env->depth, env->chain, env->table), *q, nlen, vlen, &S);
+    return RTR_OK;
+}
+
+int rtr_shade_ibl_set(rtr_context* c, const rtr_shade_env* env, const rtr_capture_set* set, const rtr_shade_query* q,
+                      rtr_gather_out* out, int64_t n) {
+    if (int rc = shade_set_check(c, env, set, q, out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    if (int rc = records_check(c, "rtr_shade_ibl_set", "query", "a non-finite field, or a normal or view vector whose length is not in (0, inf)",
+                               n, [&](int64_t k) {
+                                   double nlen, vlen;
+                                   return shade_query_bad(q[k], nlen, vlen);
+                               }))
+        return rc;
+    /* as rtr_shade_ibl: the arrays at the head of the staging buffer, the set's chains among them; the set itself travels as
+     * a kernel argument.  RTR_SET_SLICE, a test hook, lowers the slice */
+    const EnvBytes b = env_bytes(env, env_cubes(env, set));
+    const SetK S = env_set_k(env, set);
+    const StagedIO io{b.total(), sizeof(rtr_shade_query), q, {sizeof(rtr_gather_out), 0}, {out, nullptr}};
+    return staged_slices(c, n, env_cap("RTR_SET_SLICE", kShadeSlice), io, [&](const Slice& s) {
+        ShadeK K;
+        HIPCHK(c, env_stage(env, b, static_cast<char*>(s.head), s.k0 == 0, c->stream, K));
+        return shade_set_launch(c, K, S, static_cast<const rtr_shade_query*>(s.in), static_cast<rtr_gather_out*>(s.out[0]), s.m);
+    });
+}
+
+int rtr_shade_ibl_set_device(rtr_context* c, const rtr_shade_env* env, const rtr_capture_set* set, const rtr_shade_query* d_q,
+                             rtr_gather_out* d_out, int64_t n, int blocking) {
+    if (int rc = shade_set_check(c, env, set, d_q, d_out, n)) return rc;
+    if (n == 0) return RTR_OK;
+    const EnvBytes b = env_bytes(env, env_cubes(env, set));
+    const uintptr_t u0 = (uintptr_t)d_out;
+    const size_t un = (size_t)n * sizeof(rtr_gather_out);
+    uintptr_t bits = u0 | (uintptr_t)d_q;
+    if (spans_overlap(u0, un, (uintptr_t)d_q, (size_t)n * sizeof(rtr_shade_query)) || env_overlaps(env, b, u0, un, bits))
+        return fail(c, RTR_ERR_INVALID, "rtr_shade_ibl_set_device: out overlaps an input");
+    const SetK S = env_set_k(env, set);
+    return device_entry(c, "rtr_shade_ibl_set_device", bits, blocking, [&] {
+        return shade_set_launch(c, shade_k(env, env->probes, env->depth, env->chain, env->table), S, d_q, d_out, n);
+    });
+}
 
 int rtr_brdf_entry_one(const rtr_brdf_params* bp, int32_t r, int32_t c, rtr_brdf_entry* out) {
     if (brdf_params_why(bp) || !out || r < 0 || r >= bp->n_rough || c < 0 || c >= bp->n_mu) return RTR_ERR_INVALID;

@@ -57,6 +57,14 @@
  *                                   --probe-depth-out and --brdf-out are not needed), the frame is shaded from them and stored
  *                                   to --out like a render.  A missing part is an error.  Not with --pick, --ao, --adaptive,
  *                                   --turntable
+ *           [--capture-set FILE [--capture-fallback K]]   with --preview, in the place of --capture x,y,z: a capture set
+ *                                   (include/rtr_hip.h: CAPTURE SETS).  FILE is text, one volume per line: sixteen numbers in
+ *                                   struct order (centre, proxy_lo, proxy_hi, reach_lo, reach_hi: three each; fade), separated
+ *                                   by blanks or commas; `#` starts a comment; 1..16 volumes.  Renderer::capture_set bakes one
+ *                                   capture per volume with --face, --capture-spp and --capture-levels, and the frame's
+ *                                   reflections are box-projected and blended (rtr_preview_set).  K (default -1: none) is the
+ *                                   capture read where no volume reaches.  A malformed file or a set that breaks a rule is
+ *                                   refused before anything touches the device
  *           [--tonemap clamp|reinhard|aces] [--auto-exposure] [--exposure X] [--key X] [--white X] [--srgb]
  *                                   any of these: the file holds the bytes of the display transform (include/rtr_hip.h:
  *                                   rtr_display_host through Renderer::display; with --turntable rtr_display_device on
@@ -81,6 +89,8 @@ static const int hipSuccess = 0, hipMemcpyDeviceToHost = 2;
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <fstream>
+#include <sstream>
 
 /* --turntable: the device form of the frame loop of INTEGRATION.md section 4 on the C ABI itself: per frame everything is
  * queued, then one wait and one copy of the bytes.  `dp`: the display transform takes the place of the reference's store.
@@ -216,6 +226,9 @@ int main(int argc, char** argv) {
     bool capture = false, capture_face_set = false, capture_spp_set = false, latlong_set = false;
     std::string capture_out;
     int preview = 0; /* --preview K */
+    std::vector<rtr_capture_volume> set_volumes; /* --capture-set FILE */
+    bool capture_set = false, capture_fallback_set = false;
+    int capture_fallback = -1;
     std::vector<int> devices{0}, passes;
     unsigned seed = 1;
     std::string out;
@@ -359,6 +372,54 @@ int main(int argc, char** argv) {
             }
             preview = (int)v;
         }
+        else if (!std::strcmp(argv[k], "--capture-set") && k + 1 < argc) {
+            std::ifstream f(argv[++k]);
+            if (!f) {
+                std::cerr << "--capture-set: cannot read " << argv[k] << "\n";
+                return 2;
+            }
+            std::string line;
+            for (int no = 1; std::getline(f, line); ++no) {
+                line = line.substr(0, line.find('#'));
+                for (char& ch : line)
+                    if (ch == ',') ch = ' ';
+                std::istringstream in(line);
+                double v[17];
+                int got = 0;
+                std::string word;
+                bool ok = true;
+                while (in >> word) {
+                    char* end = nullptr;
+                    const double x = std::strtod(word.c_str(), &end);
+                    if (end == word.c_str() || *end != '\0' || got == 17) ok = false;
+                    else v[got++] = x;
+                    if (!ok) break;
+                }
+                if (ok && got == 0) continue; /* blank or comment */
+                if (!ok || got != 16) {
+                    std::cerr << "--capture-set: " << argv[k] << " line " << no << ": sixteen numbers expected (centre, proxy_lo, "
+                              << "proxy_hi, reach_lo, reach_hi, fade)\n";
+                    return 2;
+                }
+                rtr_capture_volume vol;
+                std::memcpy(&vol, v, sizeof vol);
+                set_volumes.push_back(vol);
+            }
+            if (set_volumes.empty() || set_volumes.size() > 16) {
+                std::cerr << "--capture-set: " << argv[k] << " holds " << set_volumes.size() << " volumes, 1..16 expected\n";
+                return 2;
+            }
+            capture_set = true;
+        }
+        else if (!std::strcmp(argv[k], "--capture-fallback") && k + 1 < argc) {
+            char* end = nullptr;
+            const long v = std::strtol(argv[++k], &end, 10);
+            if (end == argv[k] || *end != '\0' || v < -1 || v > 15) {
+                std::cerr << "--capture-fallback: an integer in -1..15, not " << argv[k] << "\n";
+                return 2;
+            }
+            capture_fallback = (int)v, capture_fallback_set = true;
+        }
         else if (!std::strcmp(argv[k], "--capture-levels") && k + 1 < argc) {
             char* end = nullptr;
             const long v = std::strtol(argv[++k], &end, 10);
@@ -482,7 +543,8 @@ int main(int argc, char** argv) {
     }
     if (preview) { /* the three parts of the bake go together here, and nothing of them is written */
         const char* missing = !probes ? "--probes NX,NY,NZ --probe-box x0,y0,z0,x1,y1,z1 (the probe grid)"
-                              : !capture || capture_levels < 1 ? "--capture x,y,z --capture-levels L (the cube chain)"
+                              : !(capture || capture_set) || capture_levels < 1
+                                  ? "--capture x,y,z (or --capture-set FILE) --capture-levels L (the cube chain)"
                               : !brdf ? "--brdf-table NMU,NROUGH (the table)" : nullptr;
         if (missing) {
             std::cerr << "--preview needs " << missing << "\n";
@@ -511,7 +573,28 @@ int main(int argc, char** argv) {
                 std::cerr << "--probe-box: the upper corner must lie above the lower one on every axis with more than one probe\n";
                 return 2;
             }
-    if ((capture_face_set || capture_spp_set || !capture_out.empty() || latlong_set || capture_levels) && !capture) {
+    if (capture_fallback_set && !capture_set) {
+        std::cerr << "--capture-fallback goes with --capture-set\n";
+        return 2;
+    }
+    if (capture_set) {
+        if (!preview || capture || !capture_out.empty() || latlong_set) {
+            std::cerr << "--capture-set goes with --preview and takes the place of --capture; --capture-out and --latlong do not apply\n";
+            return 2;
+        }
+        /* the rules of a set (include/rtr_hip.h), asked of the library's host-only lookup over a chain of one texel per face */
+        const rtr_capture_set set{(int32_t)set_volumes.size(), capture_fallback, set_volumes.data()};
+        const rtr_cube_level one{1, 0, 0, 0.0};
+        const std::vector<rtr_gather_out> texels(6 * set_volumes.size());
+        const rtr_capture_query q{{0, 0, 0}, {0, 0, 1}, 0.0, 0.0};
+        rtr_gather_out o;
+        if (rtr_capture_set_lookup_one(&set, &one, 1, texels.data(), &q, &o) != RTR_OK) {
+            std::cerr << "--capture-set: not a capture set: every number finite, proxy_lo < centre < proxy_hi, proxy_lo <= reach_lo <= "
+                      << "reach_hi <= proxy_hi, fade >= 0, --capture-fallback below the number of volumes\n";
+            return 2;
+        }
+    }
+    if ((capture_face_set || capture_spp_set || !capture_out.empty() || latlong_set || capture_levels) && !capture && !capture_set) {
         std::cerr << "--face, --capture-spp, --capture-out, --latlong and --capture-levels go with --capture\n";
         return 2;
     }
@@ -700,21 +783,31 @@ int main(int argc, char** argv) {
             if (maps.size() != points.size() * (size_t)probe_depth * probe_depth) return failed("probe depth");
             vp.map_size = probe_depth, vp.normal_bias = 0.25 * std::min(sp[0], std::min(sp[1], sp[2]));
         }
-        const std::vector<rtr_gather_out> cube =
-            renderer.capture_cube({point3(capture_at[0], capture_at[1], capture_at[2])}, capture_face, capture_spp, seed);
-        if (cube.empty()) return failed("capture");
         std::vector<rtr_cube_level> plan;
-        const std::vector<rtr_gather_out> chain = renderer.prefilter_cube(cube, capture_face, capture_levels, plan);
-        if (chain.empty()) return failed("prefilter");
+        std::vector<rtr_gather_out> chain;
+        if (capture_set) {
+            chain = renderer.capture_set(set_volumes, capture_face, capture_spp, capture_levels, plan, seed);
+            if (chain.empty()) return failed("capture set");
+        } else {
+            const std::vector<rtr_gather_out> cube =
+                renderer.capture_cube({point3(capture_at[0], capture_at[1], capture_at[2])}, capture_face, capture_spp, seed);
+            if (cube.empty()) return failed("capture");
+            chain = renderer.prefilter_cube(cube, capture_face, capture_levels, plan);
+            if (chain.empty()) return failed("prefilter");
+        }
         const std::vector<rtr_brdf_entry> table = renderer.brdf_table(brdf_dims[0], brdf_dims[1], brdf_nodes);
         if (table.size() != (size_t)brdf_dims[0] * brdf_dims[1]) return failed("brdf table");
         rtr_shade_env env{};
         env.parts = RTR_SHADE_DIFFUSE | RTR_SHADE_SPECULAR;
         env.grid = &grid, env.probes = sh.data();
         if (probe_depth_set) env.depth = maps.data(), env.visible = &vp;
-        env.levels = plan.data(), env.n_levels = (int32_t)plan.size(), env.chain = chain.data(), env.n_records = (int64_t)chain.size();
+        env.levels = plan.data(), env.n_levels = (int32_t)plan.size(), env.chain = chain.data();
+        env.n_records = (int64_t)(chain.size() / (capture_set ? set_volumes.size() : 1)); /* of one capture */
         env.table = table.data(), env.n_mu = brdf_dims[0], env.n_rough = brdf_dims[1];
-        if (renderer.render_preview(env, buffer, preview) != RTR_OK) return failed("preview");
+        const rtr_capture_set set{(int32_t)set_volumes.size(), capture_fallback, set_volumes.data()};
+        if ((capture_set ? renderer.render_preview(env, set, buffer, preview) : renderer.render_preview(env, buffer, preview)) != RTR_OK)
+            return failed("preview");
+        if (capture_set) std::cout << "capture set: " << set_volumes.size() << " volumes, fallback " << capture_fallback << "\n";
         std::cout << "preview: " << W << " x " << H << " pixels x " << preview * preview << " rays, " << points.size() << " probes, "
                   << capture_levels << " cube levels of face " << capture_face << ", table " << brdf_dims[1] << " x " << brdf_dims[0] << "\n";
         std::vector<unsigned char> shown;

@@ -668,6 +668,73 @@ class Renderer {
         return m_status;
     }
 
+    /* Capture sets (include/rtr_hip.h: CAPTURE SETS), on the first context and the scene uploaded there.  capture_set: one
+     * capture per volume from its centre and the GGX-filtered levels of all of them, level-major as the set entries read
+     * them: one rtr_capture_cube call and one rtr_cube_filter call per further level, each written where it belongs;
+     * `plan` receives the levels of ONE capture.  The overloads of shade_points and render_preview read such an array
+     * through env.chain (env.levels / n_levels / n_records describe one capture) with the specular record from `set`.  An
+     * empty vector / the status and last_status() / last_error() on failure. */
+    std::vector<rtr_gather_out> capture_set(const std::vector<rtr_capture_volume>& volumes, int face_size, int samples, int levels,
+                                            std::vector<rtr_cube_level>& plan, unsigned seed = 0, double cos_cut = 0.0) {
+        m_status = RTR_OK;
+        std::vector<point3> centres;
+        for (const rtr_capture_volume& v : volumes) centres.emplace_back(v.centre[0], v.centre[1], v.centre[2]);
+        int64_t n_records = 0;
+        plan.assign(levels > 0 ? (size_t)levels : 0, rtr_cube_level{});
+        std::vector<rtr_gather_out> out;
+        if (volumes.empty() || volumes.size() > 16) {
+            m_error = "1 .. 16 volumes expected", m_status = RTR_ERR_INVALID;
+            return out;
+        }
+        if ((m_status = rtr_cube_chain_plan(face_size, levels, plan.data(), &n_records))) {
+            m_error = "face_size outside 1 .. 4096 or levels outside 1 .. 13";
+            return out;
+        }
+        const std::vector<rtr_gather_out> level0 = capture_cube(centres, face_size, samples, seed);
+        if (level0.empty()) return out;
+        const size_t C = volumes.size();
+        out.resize(C * (size_t)n_records);
+        std::copy(level0.begin(), level0.end(), out.begin());
+        for (int i = 1; i < levels && m_status == RTR_OK; ++i) {
+            rtr_cube_filter_params fp;
+            rtr_cube_filter_defaults(&fp);
+            fp.face_in = face_size, fp.face_out = plan[i].face_size, fp.alpha = plan[i].alpha, fp.cos_cut = cos_cut;
+            if ((m_status = rtr_cube_filter(m_ctx[0], &fp, level0.data(), out.data() + (size_t)plan[i].offset * C, (int64_t)C)))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+    std::vector<rtr_gather_out> shade_points(const rtr_shade_env& env, const rtr_capture_set& set, const std::vector<rtr_shade_query>& queries) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) m_error = m_create_error, m_status = m_create_status;
+        else if (m_ctx.empty()) m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        std::vector<rtr_gather_out> out;
+        if (m_status == RTR_OK) {
+            out.resize(queries.size());
+            if ((m_status = rtr_shade_ibl_set(m_ctx[0], &env, &set, queries.data(), out.data(), (int64_t)queries.size())))
+                m_error = rtr_last_error(m_ctx[0]);
+        }
+        if (m_status != RTR_OK) out.clear();
+        return out;
+    }
+    int render_preview(const rtr_shade_env& env, const rtr_capture_set& set, RenderBuffer& target, int grid = 1) {
+        m_status = RTR_OK;
+        if (m_create_status != RTR_OK) return m_error = m_create_error, m_status = m_create_status;
+        if (m_ctx.empty()) return m_error = rtr_last_error(nullptr), m_status = RTR_ERR_DEVICE;
+        rtr_preview_params pp;
+        rtr_preview_defaults(&pp);
+        pp.image_width = target.width(), pp.image_height = target.height();
+        pp.x1 = target.width(), pp.y1 = target.height();
+        pp.grid = grid;
+        std::vector<double> lin((size_t)target.width() * target.height() * 3);
+        if ((m_status = rtr_preview_set(m_ctx[0], &pp, &env, &set, lin.data(), target.width(), nullptr)))
+            m_error = rtr_last_error(m_ctx[0]);
+        else
+            target.store_linear_rows(lin.data(), 0, target.height(), target.width());
+        return m_status;
+    }
+
     /* The display transform (include/rtr_hip.h: rtr_display_host) of the buffer's linear image on the first context:
      * width * height * 3 bytes, the top row first, for save_to_png / save_to_ppm.  Needs no scene.  Metering is global,
      * so with several contexts it runs once, on the gathered image.  Returns the status (last_status() / last_error()). */

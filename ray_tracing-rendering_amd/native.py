@@ -43,7 +43,8 @@ EXPORTS = ("rtr_abi_version", "rtr_device_count", "rtr_create", "rtr_destroy", "
            "rtr_probe_lookup_visible_device", "rtr_probe_lookup_visible_one", "rtr_brdf_table", "rtr_brdf_table_device",
            "rtr_brdf_entry_one", "rtr_brdf_fetch_one", "rtr_shade_ibl", "rtr_shade_ibl_device", "rtr_shade_ibl_one",
            "rtr_preview_defaults", "rtr_preview_ray", "rtr_preview_samples", "rtr_preview_samples_device", "rtr_preview",
-           "rtr_preview_device")
+           "rtr_preview_device", "rtr_capture_set_lookup", "rtr_capture_set_lookup_device", "rtr_capture_set_lookup_one",
+           "rtr_shade_ibl_set", "rtr_shade_ibl_set_device", "rtr_shade_ibl_set_one", "rtr_preview_set", "rtr_preview_set_device")
 # ... and include/rtr_hip_test.h (librtr_hip_test.so: device unit kernels of the parity tests, not part of the product)
 TEST_EXPORTS = ("rtr_test_hits", "rtr_test_materials", "rtr_test_lights", "rtr_test_li", "rtr_test_reference_order",
                 "rtr_test_stream8", "rtr_test_sincos_exhaustive", "rtr_test_shared_division", "rtr_test_issue_rates", "rtr_test_last_kernel",
@@ -268,6 +269,14 @@ def lib():
     L.rtr_preview_samples_device.argtypes = [vp, P(A.PreviewParamsC), vp, C.c_int]
     L.rtr_preview.argtypes = [vp, P(A.PreviewParamsC), P(A.ShadeEnvC), vp, C.c_int64, vp]
     L.rtr_preview_device.argtypes = [vp, P(A.PreviewParamsC), P(A.ShadeEnvC), vp, C.c_int64, vp, C.c_int]
+    L.rtr_capture_set_lookup.argtypes = [vp, P(A.CaptureSetC), vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64]
+    L.rtr_capture_set_lookup_device.argtypes = [vp, P(A.CaptureSetC), vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, C.c_int]
+    L.rtr_capture_set_lookup_one.argtypes = [P(A.CaptureSetC), vp, C.c_int32, vp, vp, vp]
+    L.rtr_shade_ibl_set.argtypes = [vp, P(A.ShadeEnvC), P(A.CaptureSetC), vp, vp, C.c_int64]
+    L.rtr_shade_ibl_set_device.argtypes = [vp, P(A.ShadeEnvC), P(A.CaptureSetC), vp, vp, C.c_int64, C.c_int]
+    L.rtr_shade_ibl_set_one.argtypes = [P(A.ShadeEnvC), P(A.CaptureSetC), vp, vp]
+    L.rtr_preview_set.argtypes = [vp, P(A.PreviewParamsC), P(A.ShadeEnvC), P(A.CaptureSetC), vp, C.c_int64, vp]
+    L.rtr_preview_set_device.argtypes = [vp, P(A.PreviewParamsC), P(A.ShadeEnvC), P(A.CaptureSetC), vp, C.c_int64, vp, C.c_int]
     if L.rtr_abi_version() != A.RTR_ABI_VERSION:
         raise RtrError(A.RTR_ERR_INVALID, "librtr_hip.so ABI version mismatch")
     _LIB = L
@@ -983,6 +992,62 @@ def shade_ibl_one(env, queries):
     return out
 
 
+def capture_set(volumes, fallback=-1):
+    """An rtr_capture_set from ``CAPTURE_VOLUME_DTYPE`` records (or rows of sixteen numbers in struct order: centre,
+    proxy_lo, proxy_hi, reach_lo, reach_hi, fade) and the capture read where none reaches (-1: none).  The struct keeps its
+    volumes alive; ``.records`` is that array.  The rules are the library's: a bad set fails the call that takes it."""
+    v = np.asarray(volumes)
+    if v.dtype != A.CAPTURE_VOLUME_DTYPE:
+        v = np.ascontiguousarray(np.asarray(volumes, dtype=np.float64).reshape(-1, 16)).view(A.CAPTURE_VOLUME_DTYPE)
+    v = np.ascontiguousarray(v).reshape(-1).copy()
+    s = A.CaptureSetC()
+    s.n_captures, s.fallback, s.volumes = len(v), int(fallback), v.ctypes.data
+    s.records = v
+    return s
+
+
+def capture_queries(points, directions, alpha):
+    """A ``CAPTURE_QUERY_DTYPE`` array from (n, 3) points and directions and alphas (a number or [n])"""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    q = np.zeros(len(p), dtype=A.CAPTURE_QUERY_DTYPE)
+    q["p"], q["d"], q["alpha"] = p, directions, alpha
+    return q
+
+
+def capture_set_lookup_host(cset, levels, records, queries, n_levels=None):
+    """rtr_capture_set_lookup_one for every query (``CAPTURE_QUERY_DTYPE``; host only, no context) over the level-major
+    records of ``cset`` (``capture_set``); ``levels`` is the plan of one capture.  A ``GATHER_OUT_DTYPE`` array."""
+    lv = cube_levels(levels)
+    n_levels = len(levels) if n_levels is None else int(n_levels)
+    t = np.ascontiguousarray(records, dtype=A.GATHER_OUT_DTYPE).reshape(-1)
+    q = np.ascontiguousarray(queries, dtype=A.CAPTURE_QUERY_DTYPE).reshape(-1)
+    out = np.zeros(len(q), dtype=A.GATHER_OUT_DTYPE)
+    L = lib()
+    for k in range(len(q)):
+        rc = L.rtr_capture_set_lookup_one(C.byref(cset), C.byref(lv), n_levels, t.ctypes.data, q.ctypes.data + 64 * k,
+                                          out.ctypes.data + 32 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_capture_set_lookup_one: bad set or chain")
+    return out
+
+
+def shade_ibl_set_one(env, cset, queries):
+    """rtr_shade_ibl_set_one for every query: ``shade_ibl_one`` with the specular record from the capture set ``cset``
+    (``env.chain`` holds the set level-major; ``cset`` may be None without SPECULAR)."""
+    q = np.ascontiguousarray(queries, dtype=A.SHADE_QUERY_DTYPE).reshape(-1)
+    out = np.zeros(len(q), dtype=A.GATHER_OUT_DTYPE)
+    L = lib()
+    for k in range(len(q)):
+        rc = L.rtr_shade_ibl_set_one(C.byref(env), _set_ref(cset), q.ctypes.data + 112 * k, out.ctypes.data + 32 * k)
+        if rc != 0:
+            raise RtrError(rc, "rtr_shade_ibl_set_one: bad environment or set, or bad query at index %d" % k)
+    return out
+
+
+def _set_ref(cset):
+    return None if cset is None else C.byref(cset)
+
+
 def preview_params(width, height, grid=1, region=None, t_min=None, reference_order=False):
     """An rtr_preview_params from rtr_preview_defaults: a ``width`` x ``height`` image, ``grid`` x ``grid`` rays per
     pixel, ``region`` (x0, y0, x1, y1) or the whole image"""
@@ -1475,6 +1540,29 @@ class Context:
                                                        C.c_void_p(texels_ptr), int(n_records),
                                                        *_into_tail(queries_ptr, out_ptr, n, blocking)))
 
+    # capture sets (include/rtr_hip.h: rtr_capture_set*)
+    def capture_set_lookup(self, cset, levels, records, queries, out=None, n_levels=None):
+        """rtr_capture_set_lookup: the box-projected, blended lookup of ``queries`` (``CAPTURE_QUERY_DTYPE``) in the set
+        ``cset`` (``native.capture_set``) over its level-major ``records``; ``levels`` is the plan of one capture.  Returns a
+        ``GATHER_OUT_DTYPE`` array.  Blocking; needs no scene."""
+        lv = cube_levels(levels)
+        t = np.ascontiguousarray(records, dtype=A.GATHER_OUT_DTYPE).reshape(-1)
+        q = np.ascontiguousarray(queries, dtype=A.CAPTURE_QUERY_DTYPE).reshape(-1)
+        out = _records_out(out, len(q), A.GATHER_OUT_DTYPE)
+        c = max(int(cset.n_captures), 1)
+        self._chk(self._L.rtr_capture_set_lookup(self._h, C.byref(cset), C.byref(lv), len(levels) if n_levels is None else int(n_levels),
+                                                 t.ctypes.data, len(t) // c, q.ctypes.data, out.ctypes.data, len(q)))
+        return out
+
+    def capture_set_lookup_into(self, cset, levels, records_ptr, n_records, queries_ptr, out_ptr, n, blocking=False, n_levels=None):
+        """rtr_capture_set_lookup_device: the same over device pointers (``cset`` and ``levels`` stay on the host;
+        ``n_records`` is one capture's count), on the context stream behind what is queued there."""
+        lv = cube_levels(levels)
+        self._chk(self._L.rtr_capture_set_lookup_device(self._h, C.byref(cset), C.byref(lv),
+                                                        len(levels) if n_levels is None else int(n_levels),
+                                                        C.c_void_p(records_ptr), int(n_records),
+                                                        *_into_tail(queries_ptr, out_ptr, n, blocking)))
+
     # image-based shading (include/rtr_hip.h: rtr_brdf_*, rtr_shade_ibl*)
     def brdf_table(self, n_mu, n_rough, nodes=128, params=None, out=None):
         """rtr_brdf_table: the environment BRDF table, ``BRDF_ENTRY_DTYPE`` [n_rough, n_mu].  Blocking; needs no scene."""
@@ -1490,27 +1578,43 @@ class Context:
         bp = params if params is not None else brdf_params(n_mu, n_rough, nodes)
         self._chk(self._L.rtr_brdf_table_device(self._h, C.byref(bp), C.c_void_p(out_ptr), 1 if blocking else 0))
 
-    def shade_ibl(self, env, queries, out=None):
+    def shade_ibl(self, env, queries, out=None, captures=None):
         """rtr_shade_ibl: the radiance of the ``SHADE_QUERY_DTYPE`` queries under ``env`` (``native.shade_env`` of host
-        arrays), a ``GATHER_OUT_DTYPE`` array.  Blocking; needs no scene; raises RtrError naming the first bad query."""
+        arrays), a ``GATHER_OUT_DTYPE`` array.  Blocking; needs no scene; raises RtrError naming the first bad query.
+        ``captures`` (``native.capture_set``): rtr_shade_ibl_set -- ``env.chain`` holds that set level-major."""
         q = np.ascontiguousarray(queries, dtype=A.SHADE_QUERY_DTYPE).reshape(-1)
         out = _records_out(out, len(q), A.GATHER_OUT_DTYPE)
-        self._chk(self._L.rtr_shade_ibl(self._h, C.byref(env), q.ctypes.data, out.ctypes.data, len(q)))
+        if captures is None:
+            self._chk(self._L.rtr_shade_ibl(self._h, C.byref(env), q.ctypes.data, out.ctypes.data, len(q)))
+        else:
+            self._chk(self._L.rtr_shade_ibl_set(self._h, C.byref(env), C.byref(captures), q.ctypes.data, out.ctypes.data, len(q)))
         return out
 
-    def shade_ibl_into(self, env, queries_ptr, out_ptr, n, blocking=False):
+    def shade_ibl_into(self, env, queries_ptr, out_ptr, n, blocking=False, captures=None):
         """rtr_shade_ibl_device: the same over device pointers (``env``: ``native.shade_env`` of device pointers; the
-        struct, its grid, visible params and levels stay on the host), on the context stream behind what is queued there."""
-        self._chk(self._L.rtr_shade_ibl_device(self._h, C.byref(env), *_into_tail(queries_ptr, out_ptr, n, blocking)))
+        struct, its grid, visible params and levels stay on the host), on the context stream behind what is queued there.
+        ``captures``: rtr_shade_ibl_set_device."""
+        if captures is None:
+            self._chk(self._L.rtr_shade_ibl_device(self._h, C.byref(env), *_into_tail(queries_ptr, out_ptr, n, blocking)))
+        else:
+            self._chk(self._L.rtr_shade_ibl_set_device(self._h, C.byref(env), C.byref(captures),
+                                                       *_into_tail(queries_ptr, out_ptr, n, blocking)))
 
     # baked previews (include/rtr_hip.h: rtr_preview_*)
-    def preview(self, params, env, out=None, return_lit=False):
+    def preview(self, params, env, out=None, return_lit=False, captures=None):
         """rtr_preview: the frame of ``params``' region shaded under ``env`` (``native.shade_env`` of host arrays) from the
         context's current camera: linear (h, w, 3) float64, row 0 the lowest row, or with ``return_lit`` the pair
-        (linear, lit (h, w) int32).  Blocking.  ``out`` may be a view with strided rows: only region pixels are written."""
+        (linear, lit (h, w) int32).  Blocking.  ``out`` may be a view with strided rows: only region pixels are written.
+        ``captures`` (``native.capture_set``): rtr_preview_set -- ``env.chain`` holds that set level-major."""
         h, w = params.y1 - params.y0, params.x1 - params.x0
+
+        def run(linear, stride, lit):
+            if captures is None:
+                return self._L.rtr_preview(self._h, C.byref(params), C.byref(env), linear, stride, lit)
+            return self._L.rtr_preview_set(self._h, C.byref(params), C.byref(env), C.byref(captures), linear, stride, lit)
+
         if h <= 0 or w <= 0:  # an empty region: the library's error
-            self._chk(self._L.rtr_preview(self._h, C.byref(params), C.byref(env), np.zeros(3).ctypes.data, 1, None))
+            self._chk(run(np.zeros(3).ctypes.data, 1, None))
         if out is None:
             out = np.zeros((h, w, 3), dtype=np.float64)
         if (out.dtype != np.float64 or out.shape != (h, w, 3) or out.strides[2] != 8 or out.strides[1] != 24 or
@@ -1518,16 +1622,18 @@ class Context:
             raise ValueError("out must be a float64 array of shape (%d, %d, 3) whose rows are whole pixels apart" % (h, w))
         stride = out.strides[0] // 24 if h > 1 else w
         lit = np.zeros((max(h, 0), stride), dtype=np.int32) if return_lit else None
-        self._chk(self._L.rtr_preview(self._h, C.byref(params), C.byref(env), out.ctypes.data, stride,
-                                      lit.ctypes.data if return_lit else None))
+        self._chk(run(out.ctypes.data, stride, lit.ctypes.data if return_lit else None))
         return (out, lit[:, :w]) if return_lit else out
 
-    def preview_into(self, params, env, linear_ptr, row_stride, lit_ptr=None, blocking=False):
+    def preview_into(self, params, env, linear_ptr, row_stride, lit_ptr=None, blocking=False, captures=None):
         """rtr_preview_device: the same into device pointers (``env``: ``native.shade_env`` of device pointers), rows
         ``row_stride`` pixels apart, on the context stream behind what is queued there -- the bakes included; the layout
-        ``display_into`` reads."""
-        self._chk(self._L.rtr_preview_device(self._h, C.byref(params), C.byref(env), C.c_void_p(linear_ptr), int(row_stride),
-                                             C.c_void_p(lit_ptr or None), 1 if blocking else 0))
+        ``display_into`` reads.  ``captures``: rtr_preview_set_device."""
+        tail = (C.c_void_p(linear_ptr), int(row_stride), C.c_void_p(lit_ptr or None), 1 if blocking else 0)
+        if captures is None:
+            self._chk(self._L.rtr_preview_device(self._h, C.byref(params), C.byref(env), *tail))
+        else:
+            self._chk(self._L.rtr_preview_set_device(self._h, C.byref(params), C.byref(env), C.byref(captures), *tail))
 
     def preview_samples(self, params, out=None):
         """rtr_preview_samples: the G-buffer of a preview, ``PREVIEW_SAMPLE_DTYPE`` [h, w, grid^2].  Blocking."""

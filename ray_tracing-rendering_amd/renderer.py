@@ -330,6 +330,15 @@ class Renderer:
                                              samples=samples, seed=self.seed if seed is None else seed, jitter=jitter, time=time)
         return Cubemap(rec[0])
 
+    def capture_environments(self, scene, volumes, face_size=32, samples=16, levels=5, fallback=-1, seed=None, jitter=1):
+        """A ``CaptureSet`` of ``scene``: one capture per volume (``CAPTURE_VOLUME_DTYPE`` records) from its centre under this
+        renderer's integrator and depth, filtered into ``levels`` levels, baked in place on the device
+        (include/rtr_hip.h: CAPTURE SETS)."""
+        self._scene_on_device(scene, own_camera=False)
+        p = A.make_params(2, 2, 1, integrator=self._integrator, seed=self.seed, max_depth=self._max_depth)
+        return CaptureSet.bake(self._ctx, p, volumes, face_size=face_size, samples=samples, levels=levels, fallback=fallback,
+                               seed=self.seed if seed is None else seed, jitter=jitter)
+
     def render_preview(self, scene, env, target_buffer, grid=1, display=None):
         """The baked preview of ``scene`` under ``env`` (an ``IblEnvironment``) into ``target_buffer``
         (include/rtr_hip.h: rtr_preview): ``grid`` x ``grid`` pixel-centred rays per pixel, each hit shaded from the
@@ -370,7 +379,7 @@ class Renderer:
         d_lin = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         d_rgb = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(d_lin.device)  # the library works on a stream of its own
-        self._ctx.preview_into(p, d_env, d_lin.data_ptr(), w)
+        self._ctx.preview_into(p, d_env, d_lin.data_ptr(), w, captures=env.captures)
         self._ctx.display_into(d_lin.data_ptr(), w, w, h, d_rgb.data_ptr(), display)
         self._ctx.synchronize()
         target_buffer.store_linear(d_lin.cpu().numpy())
@@ -591,6 +600,80 @@ class CubeChain:
         return paths
 
 
+class CaptureSet:
+    """Several captures of one scene with the boxes they serve (include/rtr_hip.h: rtr_capture_set*): ``volumes``,
+    ``CAPTURE_VOLUME_DTYPE`` records, ``fallback`` (the capture read where none reaches, or -1), ``levels``, the plan of ONE
+    capture, and ``records``, the ``GATHER_OUT_DTYPE`` records of all captures level-major.  A lookup projects the
+    direction onto the proxy box of every capture that reaches the point and blends what they hold."""
+
+    def __init__(self, volumes, levels, records, fallback=-1):
+        from . import native
+        self._set = native.capture_set(volumes, fallback)
+        self.volumes, self.fallback = self._set.records, int(fallback)
+        self.levels = levels
+        self.records = np.ascontiguousarray(records, dtype=A.GATHER_OUT_DTYPE).reshape(-1)
+        if len(self.records) % len(self.volumes):
+            raise ValueError("records must hold the same number of records for every capture")
+
+    def __len__(self):
+        return len(self.volumes)
+
+    @property
+    def n_records(self):
+        """records of one capture"""
+        return len(self.records) // len(self.volumes)
+
+    def set(self):
+        """The rtr_capture_set over the host volumes"""
+        return self._set
+
+    @classmethod
+    def bake(cls, ctx, render_params, volumes, face_size=32, samples=16, levels=5, fallback=-1, seed=0, jitter=1, cos_cut=0.0):
+        """One rtr_capture_cube_device call over the volumes' centres and one rtr_cube_filter_device call per further
+        level, straight into the level-major array on the device and with no host wait between them; the records come
+        back once at the end.  ``ctx`` holds the scene; ``render_params`` an rtr_render_params (integrator, depth)."""
+        import torch
+        from . import native
+        vols = native.capture_set(volumes, fallback).records
+        C_ = len(vols)
+        plan, n_records = native.cube_chain_plan(face_size, levels)
+        dev = "cuda:%d" % ctx.device
+        d_centres = torch.from_numpy(native.probe_points(vols["centre"]).view(np.uint8).reshape(-1).copy()).to(dev)
+        d_set = torch.zeros(C_ * n_records * 32, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(d_set.device)  # the library works on a stream of its own
+        base = d_set.data_ptr()
+        ctx.capture_cube_into(render_params, d_centres.data_ptr(), base, C_, face_size=face_size, samples=samples, seed=seed,
+                              jitter=jitter)
+        for lv in list(plan)[1:]:
+            ctx.cube_filter_into(base, base + C_ * lv.offset * 32, C_, face_in=face_size, face_out=lv.face_size, alpha=lv.alpha,
+                                 cos_cut=cos_cut)
+        ctx.synchronize()
+        return cls(vols, plan, d_set.cpu().numpy().view(A.GATHER_OUT_DTYPE), fallback)
+
+    def chain(self, k):
+        """Capture ``k`` as a ``CubeChain``"""
+        C_ = len(self.volumes)
+        parts = []
+        for lv in self.levels:
+            F = 6 * lv.face_size * lv.face_size
+            parts.append(self.records[lv.offset * C_ + k * F:lv.offset * C_ + (k + 1) * F])
+        return CubeChain(self.levels, np.concatenate(parts))
+
+    def lookup_records(self, points, directions, roughness, ctx=None):
+        """The ``GATHER_OUT_DTYPE`` records of rtr_capture_set_lookup at the points [n, 3] along the directions [n, 3] at
+        ``roughness`` (a number or [n]; alpha = roughness squared); ``ctx``: a context to run it on the device."""
+        from . import native
+        r = np.asarray(roughness, dtype=np.float64)
+        q = native.capture_queries(points, directions, r * r)
+        if ctx is not None:
+            return ctx.capture_set_lookup(self._set, self.levels, self.records, q)
+        return native.capture_set_lookup_host(self._set, self.levels, self.records, q)
+
+    def lookup(self, points, directions, roughness, ctx=None):
+        """[n, 3] radiance of ``lookup_records``; zero where the lookup is invalid."""
+        return self.lookup_records(points, directions, roughness, ctx)["v"]
+
+
 class BrdfTable:
     """The environment BRDF table of the split-sum approximation (include/rtr_hip.h: rtr_brdf_table): ``entries``,
     ``BRDF_ENTRY_DTYPE`` [n_rough, n_mu]; int f_spec cos dw ~ F0 * a + b at (mu, roughness)."""
@@ -615,13 +698,19 @@ class BrdfTable:
 
 class IblEnvironment:
     """What rtr_shade_ibl shades under: a ``ProbeGrid`` (diffuse; its distance maps select the visible lookup), a
-    ``CubeChain`` (specular) and a ``BrdfTable``.  ``grid`` or ``chain`` may be None: that part is left out."""
+    ``CubeChain`` or a ``CaptureSet`` (specular; a set runs the rtr_*_set entries) and a ``BrdfTable``.  ``grid`` or
+    ``chain`` may be None: that part is left out."""
 
     def __init__(self, grid, chain, table, normal_bias=None):
         if grid is None and chain is None:
             raise ValueError("an environment needs a grid, a chain or both")
         self.grid, self.chain, self.table = grid, chain, table
         self.normal_bias = normal_bias
+
+    @property
+    def captures(self):
+        """The rtr_capture_set of a ``CaptureSet`` environment, or None"""
+        return self.chain.set() if isinstance(self.chain, CaptureSet) else None
 
     def env(self):
         """The rtr_shade_env over the host arrays"""
@@ -634,6 +723,8 @@ class IblEnvironment:
                 kw.update(depth=self.grid.depth, visible=native.probe_visible_params(self.grid.depth.shape[-1], bias))
         if self.chain is not None:
             kw.update(levels=self.chain.levels, chain=self.chain.records)
+            if isinstance(self.chain, CaptureSet):
+                kw.update(n_records=self.chain.n_records)
         return native.shade_env(self.table.entries, **kw)
 
     def shade_records(self, points, normals, views, base, roughness, metallic, ctx=None):
@@ -642,7 +733,11 @@ class IblEnvironment:
         from . import native
         q = native.shade_queries(points, normals, views, base, roughness, metallic)
         ctx = ctx if ctx is not None else (self.grid._ctx if self.grid is not None else None)
-        return ctx.shade_ibl(self.env(), q) if ctx is not None else native.shade_ibl_one(self.env(), q)
+        if ctx is not None:
+            return ctx.shade_ibl(self.env(), q, captures=self.captures)
+        if self.captures is not None:
+            return native.shade_ibl_set_one(self.env(), self.captures, q)
+        return native.shade_ibl_one(self.env(), q)
 
     def shade(self, points, normals, views, base, roughness, metallic, ctx=None):
         """[n, 3] radiance towards the viewers: points, normals and view vectors [n, 3], base colour [n, 3] or one colour,
@@ -653,7 +748,7 @@ class IblEnvironment:
         """rtr_preview: the frame of the scene ``ctx`` holds, seen from its current camera and shaded under this
         environment; ``params`` from ``native.preview_params``.  Linear (h, w, 3), row 0 the lowest row; with
         ``return_lit`` also the (h, w) count of samples per pixel that found something to add."""
-        return ctx.preview(params, self.env(), return_lit=return_lit)
+        return ctx.preview(params, self.env(), return_lit=return_lit, captures=self.captures)
 
 
 def _visible_of(env):
